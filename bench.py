@@ -2,7 +2,7 @@
 """Headline benchmark: frames/s of the AprilTag hot path at 1280x720, 20 tags/frame
 (BASELINE.json configs[1]: detection + batched PnP on one MI355X), frames resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W [--batch B]
+    python bench.py --gpus N --steps K --warmup W [--batch B] [--dump-outputs DIR]
 
 A step = one batch of B synthetic BGR frames through asl_detect_batch_device (threshold -> components ->
 clusters -> quads -> decode -> PnP -> de-duplication, results copied back).  With --gpus N > 1 the script starts N
@@ -211,6 +211,36 @@ def cpu_baseline(frames, K, budget_s=12.0, gpu=None):
                              "pose_rmse_translation_mm": float(np.sqrt(np.mean(np.square(dtr))) * MM_PER_UNIT) if dtr else None,
                              "pose_rmse_rotation_mrad": float(np.sqrt(np.mean(np.square(drot))) * 1e3) if drot else None}
     return out
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6 - 4096  # --dump-outputs: at most 64 MB in all, .npy headers included
+
+
+def dump_outputs(path, dets, poses, npf, cam_poses=None, seed=20250620):
+    """What the last timed step returned to its caller, as DIR/<name>.npy (float64; `det_margin` stays float32):
+    per detection id, hamming, margin, frame, center, corners and its PnP pose (rvec, tvec, T, ok), detections per frame,
+    and with the exchange on the camera poses of the graph update (world, frames, 4, 4).  `frames` lists the frame
+    indices written: all of them when the output fits in 64 MB, else a seeded sample of whole frames (ascending)."""
+    npf = np.asarray(npf, dtype=np.int64)
+    B = len(npf)
+    start = np.concatenate(([0], np.cumsum(npf)[:-1]))
+    per_det = 8 * 36 + 4  # the float64 fields below plus the float32 margin
+    per_frame = 8 * 2 + npf * per_det + (0 if cam_poses is None else 8 * 16 * cam_poses.shape[0])
+    if per_frame.sum() <= DUMP_BUDGET_BYTES:
+        keep = np.arange(B)
+    else:
+        order = np.random.default_rng(seed).permutation(B)
+        keep = np.sort(order[:int(np.searchsorted(np.cumsum(per_frame[order]), DUMP_BUDGET_BYTES, side="right"))])
+    rows = np.concatenate([np.arange(start[f], start[f] + npf[f]) for f in keep]) if len(keep) else np.zeros(0, np.int64)
+    d, p = dets[rows], poses[rows]
+    out = {"frames": keep, "npf": npf[keep], "det_id": d["id"], "det_hamming": d["hamming"], "det_margin": d["margin"],
+           "det_frame": d["frame"], "det_center": d["center"], "det_corners": d["corners"], "pose_rvec": p["rvec"],
+           "pose_tvec": p["tvec"], "pose_T": p["T"], "pose_ok": p["ok"]}
+    if cam_poses is not None:
+        out["camera_pose"] = cam_poses[:, keep]
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64))
 
 
 def spawn_ranks(n, argv, timeout_s=1500.0):
@@ -430,7 +460,10 @@ def main():
     ap.add_argument("--gn-every", type=int, default=-1, help="pose-graph LM on a window every this many steps of the exchange (0 = never, -1 = the workload's default)")
     ap.add_argument("--gn-frames", type=int, default=8, help="frames per stream in the LM window")
     ap.add_argument("--exchange", action="store_true", help="N = 1: run the exchange + graph update + LM of the multi-GPU step anyway (the collective degenerates to a copy)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned (rank 0) to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     global W, H, NTAGS
     wl = WORKLOADS[args.workload]
     W, H, NTAGS = wl["w"], wl["h"], wl["tags"]
@@ -586,6 +619,7 @@ def main():
             return x["h_last"].numpy().view(np.uint32).copy(), x["h_picks"].numpy().reshape(-1).view(adist.OBS_DTYPE).copy()
         poses, nseq = adist.apply_block(slam, block, res, picks=picks, tail=None if tail_frames is None else tail_frames[:, -1],
                                         picker=picker if res is not None else None)
+        state["camera_poses"] = poses
         t2 = time.perf_counter()
         serial["gather"].append(t1 - t0); serial["graph"].append(t2 - t1); serial["seq_frames"] += nseq
         state["blocks"] = state.get("blocks", 0) + 1
@@ -611,7 +645,7 @@ def main():
             update_graph(k)
         for kk, v in detectors[k].stage_times().items():
             kernel_ms.setdefault(kk, []).append(v)
-        return dets, npf
+        return dets, poses, npf
 
     def step():
         """Submit one batch of B frames; collect the oldest batch once P are in flight."""
@@ -651,7 +685,7 @@ def main():
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
-    drain()
+    last_step = drain()  # views of the last step's results, valid until that detector's next submit
     torch.cuda.synchronize(dev)
     if use_pg:
         dist.barrier()
@@ -660,6 +694,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if args.rehearse else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last_step, cam_poses=state.get("camera_poses") if xchg else None)
 
     # one extra synchronous batch (nothing else on the GPU) for un-overlapped kernel durations
     detectors[0].submit_device(d_frames.data_ptr(), B, 3, W, H, stream=streams[0].cuda_stream, K=K, dist=zeros4, tag_size=TAG_INNER)
