@@ -23,6 +23,15 @@ class AslPose(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class AslMapTag(C.Structure):
+    _fields_ = [("T", C.c_double * 12), ("valid", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AslCamPose(C.Structure):
+    _fields_ = [("T", C.c_double * 16), ("rms_px", C.c_double), ("rms_seed_px", C.c_double), ("n_tags", C.c_int32),
+                ("n_rejected", C.c_int32), ("status", C.c_int32), ("seed_slot", C.c_int32)]
+
+
 class AslDebugQuad(C.Structure):
     _fields_ = [("p", (C.c_double * 2) * 4), ("cluster", C.c_uint64), ("frame", C.c_int32), ("reversed_border", C.c_int32)]
 
@@ -34,14 +43,20 @@ assert OBS_DTYPE.itemsize == 136
 DET_DTYPE = np.dtype([("id", "<i4"), ("hamming", "<i4"), ("margin", "<f4"), ("frame", "<i4"),
                       ("center", "<f8", (2,)), ("corners", "<f8", (4, 2))])
 POSE_DTYPE = np.dtype([("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)), ("T", "<f8", (4, 4)), ("ok", "<i4"), ("reserved", "<i4")])
+MAP_TAG_DTYPE = np.dtype([("T", "<f8", (12,)), ("valid", "<i4"), ("reserved", "<i4")])  # asl_map_tag
+CAM_POSE_DTYPE = np.dtype([("T", "<f8", (4, 4)), ("rms_px", "<f8"), ("rms_seed_px", "<f8"), ("n_tags", "<i4"), ("n_rejected", "<i4"),
+                           ("status", "<i4"), ("seed_slot", "<i4")])  # asl_cam_pose
 QUAD_DTYPE = np.dtype([("p", "<f8", (4, 2)), ("cluster", "<u8"), ("frame", "<i4"), ("reversed_border", "<i4")])
 assert DET_DTYPE.itemsize == C.sizeof(AslDetection)
 assert POSE_DTYPE.itemsize == C.sizeof(AslPose)
 assert QUAD_DTYPE.itemsize == C.sizeof(AslDebugQuad)
+assert MAP_TAG_DTYPE.itemsize == C.sizeof(AslMapTag) == 104
+assert CAM_POSE_DTYPE.itemsize == C.sizeof(AslCamPose) == 160
 
 EXPORTS = [
     "asl_detector_create", "asl_detector_destroy", "asl_detector_set_id_limit", "asl_detector_set_pnp_both_minima", "asl_last_error", "asl_version", "asl_detect_gray_u8",
     "asl_detect_bgr_u8", "asl_detect_batch_u8", "asl_detect_batch_pose_u8", "asl_detect_batch_device", "asl_submit_batch_device", "asl_collect_batch", "asl_collect_batch_view", "asl_solve_pnp_batch", "asl_gn_solve", "asl_pack_observations_device", "asl_graph_frames_device", "asl_graph_picks_device", "asl_render_frames_device",
+    "asl_localize_frames_device", "asl_localize_batch",
     "asl_debug_fetch", "asl_stage_times", "asl_set_profiling", "asl_debug_phase_cycles",
 ]
 
@@ -89,6 +104,8 @@ def load():
     L.asl_pack_observations_device.argtypes = [vp, vp, i32, vp]
     L.asl_graph_frames_device.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp]
     L.asl_graph_picks_device.argtypes = [vp, vp, i32, i32, i32, vp, C.c_uint32, C.c_uint32, vp, i32, vp, vp]
+    L.asl_localize_frames_device.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, C.c_double, vp, vp]
+    L.asl_localize_batch.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, C.c_double, vp]
     L.asl_debug_fetch.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.asl_stage_times.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32, C.POINTER(i32)]
     L.asl_set_profiling.argtypes = [vp, i32]
@@ -271,6 +288,44 @@ class Detector:
         check(self._L.asl_graph_picks_device(self._h, C.c_void_p(int(obs_ptr)), int(world), int(n_frames), int(max_tags), C.c_void_p(int(status_ptr)),
                                              int(order_lo), int(order_hi), C.c_void_p(int(last_ptr)), int(n_ids), C.c_void_p(int(picks_ptr)),
                                              C.c_void_p(int(stream))))
+
+    @staticmethod
+    def _camera_args(K, dist):
+        dp = C.POINTER(C.c_double)
+        Kc = np.ascontiguousarray(K, dtype=np.float64)
+        if Kc.shape != (3, 3):
+            raise ValueError("K must be 3x3")
+        dc = np.ascontiguousarray(np.zeros(0) if dist is None else dist, dtype=np.float64).ravel()
+        if len(dc) not in (0, 4, 5):
+            raise ValueError("dist must have 0, 4 or 5 coefficients")
+        return (Kc, dc), Kc.ctypes.data_as(dp), (dc.ctypes.data_as(dp) if len(dc) else None), len(dc)
+
+    def localize(self, obs, tag_map, K, dist, tag_size, max_tag_rms_px=0.0):
+        """asl_localize_batch: host records obs (n_frames, max_tags) OBS_DTYPE (e.g. dist.pack_observations) against
+        tag_map (n_ids,) MAP_TAG_DTYPE (or a localize.TagMap) -> (n_frames,) CAM_POSE_DTYPE, world<-camera per frame."""
+        if hasattr(tag_map, "as_records"):
+            tag_map = tag_map.as_records()
+        o = np.ascontiguousarray(obs, dtype=OBS_DTYPE)
+        if o.ndim == 1:
+            o = o[None]
+        if o.ndim != 2:
+            raise ValueError("obs must be (n_frames, max_tags) asl_obs records")
+        m = np.ascontiguousarray(tag_map, dtype=MAP_TAG_DTYPE).ravel()
+        keep, Kp, dpp, nd = self._camera_args(K, dist)
+        out = np.zeros(o.shape[0], dtype=CAM_POSE_DTYPE)
+        check(self._L.asl_localize_batch(self._h, o.ctypes.data if o.size else None, o.shape[0], o.shape[1],
+                                         m.ctypes.data if m.size else None, len(m), Kp, dpp, nd, float(tag_size),
+                                         float(max_tag_rms_px), out.ctypes.data if out.size else None))
+        return out
+
+    def localize_device(self, obs_ptr, n_frames, max_tags, map_ptr, n_ids, out_ptr, K, dist, tag_size, max_tag_rms_px=0.0,
+                        stream=0):
+        """asl_localize_frames_device: obs_ptr (n_frames x max_tags asl_obs, e.g. from pack_observations_device), map_ptr
+        (n_ids asl_map_tag) and out_ptr (n_frames asl_cam_pose) are device addresses; enqueued on `stream`, no wait."""
+        keep, Kp, dpp, nd = self._camera_args(K, dist)
+        check(self._L.asl_localize_frames_device(self._h, C.c_void_p(int(obs_ptr)), int(n_frames), int(max_tags), C.c_void_p(int(map_ptr)),
+                                                 int(n_ids), Kp, dpp, nd, float(tag_size), float(max_tag_rms_px),
+                                                 C.c_void_p(int(out_ptr)), C.c_void_p(int(stream))))
 
     def collect_view(self):
         """Wait for the submitted batch; (dets, poses or None, n_per_frame) as numpy VIEWS of the detector's page-locked result

@@ -27,6 +27,7 @@
 #include "k_graph.inc"
 #include "k_render.inc"
 #include "k_gn.inc"
+#include "k_localize.inc"
 
 static thread_local std::string g_err;
 
@@ -113,6 +114,7 @@ struct asl_detector {
     DevBuf<double> pnp_out;
     DevBuf<uint8_t> pnp_ok;
     GnWorkspace gn;
+    DevBuf<uint8_t> loc_obs, loc_map, loc_out;  // asl_localize_batch: the host records' device copies (grow on demand)
     hipStream_t copy_stream = nullptr, host_stream = nullptr;  // host frames: transfers and the chunks' kernels (detect_host_frames)
     std::vector<hipEvent_t> copy_done;
     hipStream_t aux_stream = nullptr;  // highest priority, for the small latency-bound jobs next to a running batch (pose-graph LM)
@@ -265,6 +267,7 @@ extern "C" void asl_detector_destroy(asl_detector *d)
     d->slot_cluster.release(); d->clusters.release(); d->quads.release(); d->scratch.release(); d->side_mom.release(); d->quadH.release(); d->wtab.release(); d->dets.release();
     d->counters.release(); d->pnp_corners.release(); d->pnp_out.release(); d->pnp_ok.release();
     d->gn.release();
+    d->loc_obs.release(); d->loc_map.release(); d->loc_out.release();
     if (d->aux_stream) (void)hipStreamDestroy(d->aux_stream);
     if (d->copy_stream) (void)hipStreamDestroy(d->copy_stream);
     if (d->host_stream) (void)hipStreamDestroy(d->host_stream);
@@ -963,6 +966,64 @@ extern "C" int asl_solve_pnp_batch(asl_detector *d, const float *corners, const 
     HIPCHK(hipMemcpy(tvec, dt, sizeof(double) * 3 * (size_t)N, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(T, dT, sizeof(double) * 16 * (size_t)N, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(ok, d->pnp_ok.p, (size_t)N, hipMemcpyDeviceToHost));
+    return ASL_OK;
+}
+
+static int check_localize_args(const void *obs, int n_frames, int max_tags, const void *map, int n_ids, const double *K, const double *dist,
+                               int n_dist, double tag_size, double max_tag_rms_px, const void *out)
+{
+    if (!obs || !map || !K || !out) return fail(ASL_EINVAL, "NULL argument");
+    if (n_frames < 0) return fail(ASL_EINVAL, "n_frames < 0");
+    if (max_tags < 1 || max_tags > 256) return fail(ASL_EINVAL, "max_tags must be in [1, 256] (got %d)", max_tags);
+    if (n_ids < 1) return fail(ASL_EINVAL, "n_ids must be >= 1 (got %d)", n_ids);
+    if (n_dist != 0 && n_dist != 4 && n_dist != 5) return fail(ASL_EINVAL, "n_dist must be 0, 4 or 5");
+    if (n_dist && !dist) return fail(ASL_EINVAL, "dist is NULL with n_dist = %d", n_dist);
+    if (!(tag_size > 0) || !std::isfinite(tag_size)) return fail(ASL_EINVAL, "tag_size must be positive (got %g)", tag_size);
+    if (!(max_tag_rms_px >= 0) || !std::isfinite(max_tag_rms_px)) return fail(ASL_EINVAL, "max_tag_rms_px must be >= 0 (got %g)", max_tag_rms_px);
+    return ASL_OK;
+}
+
+static void launch_localize(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids, const double *K,
+                            const double *dist, int n_dist, double tag_size, double max_tag_rms_px, void *d_out, hipStream_t st)
+{
+    CamDev cam = make_cam(d, K, dist, n_dist, tag_size);
+    hipLaunchKernelGGL(k_localize, dim3((unsigned int)n_frames), dim3(ASL_WAVE), loc_lds_bytes(max_tags), st, (const ObsRec *)d_obs, max_tags,
+                       (const MapTagRec *)d_map, n_ids, cam, max_tag_rms_px, (CamPoseRec *)d_out);
+}
+
+extern "C" int asl_localize_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                          const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
+                                          void *d_out, void *stream)
+{
+    static_assert(sizeof(MapTagRec) == sizeof(asl_map_tag) && sizeof(asl_map_tag) == 104, "asl_map_tag layout");
+    static_assert(sizeof(CamPoseRec) == sizeof(asl_cam_pose) && sizeof(asl_cam_pose) == 160, "asl_cam_pose layout");
+    if (!d) return fail(ASL_EINVAL, "NULL detector");
+    int rc = check_localize_args(d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, d_out);
+    if (rc) return rc;
+    if (n_frames == 0) return ASL_OK;
+    HIPCHK(hipSetDevice(d->device));
+    launch_localize(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, d_out, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return ASL_OK;
+}
+
+extern "C" int asl_localize_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                  const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px, asl_cam_pose *out)
+{
+    if (!d) return fail(ASL_EINVAL, "NULL detector");
+    int rc = check_localize_args(obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, out);
+    if (rc) return rc;
+    if (n_frames == 0) return ASL_OK;
+    HIPCHK(hipSetDevice(d->device));
+    const size_t obs_bytes = sizeof(asl_obs) * (size_t)n_frames * (size_t)max_tags, map_bytes = sizeof(asl_map_tag) * (size_t)n_ids,
+                 out_bytes = sizeof(asl_cam_pose) * (size_t)n_frames;
+    if (d->loc_obs.ensure(obs_bytes) || d->loc_map.ensure(map_bytes) || d->loc_out.ensure(out_bytes))
+        return fail(ASL_ENOMEM, "localisation workspace allocation failed");
+    HIPCHK(hipMemcpy(d->loc_obs.p, obs, obs_bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d->loc_map.p, map, map_bytes, hipMemcpyHostToDevice));
+    launch_localize(d, d->loc_obs.p, n_frames, max_tags, d->loc_map.p, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, d->loc_out.p, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, d->loc_out.p, out_bytes, hipMemcpyDeviceToHost));
     return ASL_OK;
 }
 

@@ -1,0 +1,335 @@
+// Multi-tag camera localisation against a known tag map (asl_localize_frames_device / asl_localize_batch).
+// One wavefront per frame, float64 throughout.  The frame's max_tags slots x 4 corners are spread over the 64 lanes
+// (corner c = 4 * slot + q on lane c % 64); every pass over the corners ends in a butterfly sum over the wave
+// (lane_xor<1..32>: DPP and v_permlane*_swap, no LDS), after which every lane holds the same bits -- a + b is
+// commutative, and the order of the additions is fixed -- so the small serial parts (candidate choice, 6x6 Cholesky,
+// the step) run redundantly in all lanes on identical inputs, without a broadcast, and a frame's result does not depend
+// on the run.
+//   gather  taking-part slots (flags & 1, mapped id) -> world corners (LDS, double) and image corners (LDS, float32 as packed)
+//   seed    <= 8 seeding slots (flags & 2) of largest corner area; each slot's PnP pose and its mirrored planar minimum,
+//           composed with the map, scored over ALL taking-part corners: reseed_poses' camera half with the tags held fixed
+//   refine  Levenberg-Marquardt on camera<-world, T <- [Rod(w) | v] T, 10 trial steps at most
+//   gate    optional: while the slot of largest own 4-corner RMS exceeds max_tag_rms_px it is dropped and the solve runs
+//           again (one slot at a time, at most 8)
+// tests/localize_ref.py is the NumPy statement of the same computation.  Latency-bound scalar float64 like k_pnp.inc:
+// the time goes into the dependent chains of the passes and reductions, not into bytes (136 B per slot in, 160 B per frame out).
+
+struct MapTagRec {  // == asl_map_tag, 104 bytes
+    double T[12];   // rows 0..2 of world<-tag
+    int32_t valid, reserved;
+};
+
+struct CamPoseRec {  // == asl_cam_pose, 160 bytes
+    double T[16];
+    double rms_px, rms_seed_px;
+    int32_t n_tags, n_rejected, status, seed_slot;
+};
+
+#define LOC_MAX_SEEDS 8
+#define LOC_LM_ITERS 10
+#define LOC_MIRRORED 256
+#define LOC_MAX_GATE_DROPS 8
+#define LOC_Z_MIN 1e-9
+#define LOC_BEHIND_COST 1e12
+
+__device__ __forceinline__ double wave_sum_f64(double v)
+{
+    v += __builtin_bit_cast(double, lane_xor<1>(__builtin_bit_cast(unsigned long long, v)));
+    v += __builtin_bit_cast(double, lane_xor<2>(__builtin_bit_cast(unsigned long long, v)));
+    v += __builtin_bit_cast(double, lane_xor<4>(__builtin_bit_cast(unsigned long long, v)));
+    v += __builtin_bit_cast(double, lane_xor<8>(__builtin_bit_cast(unsigned long long, v)));
+    v += __builtin_bit_cast(double, lane_xor<16>(__builtin_bit_cast(unsigned long long, v)));
+    v += __builtin_bit_cast(double, lane_xor<32>(__builtin_bit_cast(unsigned long long, v)));
+    return v;
+}
+
+__device__ __forceinline__ int wave_sum_i32(int v)
+{
+    v += (int)lane_xor32<1>((unsigned int)v);
+    v += (int)lane_xor32<2>((unsigned int)v);
+    v += (int)lane_xor32<4>((unsigned int)v);
+    v += (int)lane_xor32<8>((unsigned int)v);
+    v += (int)lane_xor32<16>((unsigned int)v);
+    v += (int)lane_xor32<32>((unsigned int)v);
+    return v;
+}
+
+// (area, slot) with the larger area, the lower slot on a tie: the same pair in every lane afterwards
+template <int J>
+__device__ __forceinline__ void argmax_step(double &a, int &s)
+{
+    const double pa = __builtin_bit_cast(double, lane_xor<J>(__builtin_bit_cast(unsigned long long, a)));
+    const int ps = (int)lane_xor32<J>((unsigned int)s);
+    if (pa > a || (pa == a && ps < s)) { a = pa; s = ps; }
+}
+
+// Squared pixel error of one corner at camera point P = R X + t; with NE its rows of the Jacobian
+// d uv / d delta = J_proj [-[P]x | I] are added to acc: JtJ (packed lower triangle, 21) and Jt r (6).
+// (A template rather than a null pointer: a pointer chosen at run time keeps the arrays out of registers.)
+template <bool NE>
+__device__ __forceinline__ double loc_corner(const CamDev &c, const double *R, const double *t, const double *X, double iu, double iv,
+                                             double *acc)
+{
+    double P[3], uv[2], Jp[6];
+#pragma unroll
+    for (int r = 0; r < 3; r++) P[r] = R[3 * r] * X[0] + R[3 * r + 1] * X[1] + R[3 * r + 2] * X[2] + t[r];
+    if (!(P[2] > LOC_Z_MIN)) return LOC_BEHIND_COST;
+    project_dev(c, P, uv, NE ? Jp : nullptr);
+    const double r0 = uv[0] - iu, r1 = uv[1] - iv;
+    if constexpr (NE) {
+        const double nPx[9] = {0, P[2], -P[1], -P[2], 0, P[0], P[1], -P[0], 0};  // -[P]x
+        double J0[6], J1[6];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            J0[k] = Jp[0] * nPx[k] + Jp[1] * nPx[3 + k] + Jp[2] * nPx[6 + k];
+            J0[3 + k] = Jp[k];
+            J1[k] = Jp[3] * nPx[k] + Jp[4] * nPx[3 + k] + Jp[5] * nPx[6 + k];
+            J1[3 + k] = Jp[3 + k];
+        }
+#pragma unroll
+        for (int a = 0; a < 6; a++) {
+            acc[21 + a] += J0[a] * r0 + J1[a] * r1;
+#pragma unroll
+            for (int b = 0; b <= a; b++) acc[TRI(a, b)] += J0[a] * J0[b] + J1[a] * J1[b];
+        }
+    }
+    return r0 * r0 + r1 * r1;
+}
+
+// Total cost over the frame's active corners (state == 1), identical in every lane; with NE also the normal equations in ne.
+template <bool NE>
+__device__ __forceinline__ double loc_pass(const CamDev &c, const double *R, const double *t, const double *s_X, const float *s_uv, const int *s_state,
+                           int n4, int lane, double *ne)
+{
+    double cost = 0, acc[27];
+#pragma unroll
+    for (int i = 0; i < 27; i++) acc[i] = 0;
+    for (int k = lane; k < n4; k += ASL_WAVE) {
+        if (s_state[k >> 2] != 1) continue;
+        cost += loc_corner<NE>(c, R, t, s_X + 3 * k, (double)s_uv[2 * k], (double)s_uv[2 * k + 1], acc);
+    }
+    if constexpr (NE) {
+#pragma unroll
+        for (int i = 0; i < 27; i++) ne[i] = wave_sum_f64(acc[i]);
+    }
+    return wave_sum_f64(cost);
+}
+
+// The fixed schedule (tests/localize_ref.py: lm): (R, t) camera<-world refined in place; returns the final cost.
+__device__ __forceinline__ double loc_lm(const CamDev &c, double *R, double *t, const double *s_X, const float *s_uv, const int *s_state, int n4, int lane)
+{
+    double ne[27];
+    double cost = loc_pass<true>(c, R, t, s_X, s_uv, s_state, n4, lane, ne);
+    double lambda = 1e-3;
+    for (int it = 0; it < LOC_LM_ITERS; it++) {
+        double A[21], d[6];
+#pragma unroll
+        for (int i = 0; i < 21; i++) A[i] = ne[i];
+#pragma unroll
+        for (int a = 0; a < 6; a++) { A[TRI(a, a)] += lambda * ne[TRI(a, a)]; d[a] = -ne[21 + a]; }
+        if (!chol6_solve_tri_dev(A, d)) { lambda *= 10; continue; }
+        double dR[9], Rn[9], tn[3];
+        rodrigues_dev(d, dR);
+        mat3_mul_dev(dR, R, Rn);
+#pragma unroll
+        for (int r = 0; r < 3; r++) tn[r] = dR[3 * r] * t[0] + dR[3 * r + 1] * t[1] + dR[3 * r + 2] * t[2] + d[3 + r];
+        const double cn = loc_pass<false>(c, Rn, tn, s_X, s_uv, s_state, n4, lane, nullptr);
+        if (cn < cost) {
+            const bool stop = cost - cn < 1e-12 * cost;
+#pragma unroll
+            for (int i = 0; i < 9; i++) R[i] = Rn[i];
+            t[0] = tn[0]; t[1] = tn[1]; t[2] = tn[2];
+            cost = cn;
+            lambda *= 0.1;
+            if (stop) break;
+            cost = loc_pass<true>(c, R, t, s_X, s_uv, s_state, n4, lane, ne);
+        } else
+            lambda *= 10;
+    }
+    return cost;
+}
+
+// camera<-world of slot s's PnP pose (or its mirrored planar minimum, map_init.mirrored_pose) and map tag M: T_obs inv(M)
+__device__ __forceinline__ void loc_candidate(const double *To, const double *M, bool mirror, double *R, double *t)
+{
+    double Ro[9], to[3] = {To[3], To[7], To[11]};
+#pragma unroll
+    for (int r = 0; r < 3; r++) { Ro[3 * r] = To[4 * r]; Ro[3 * r + 1] = To[4 * r + 1]; Ro[3 * r + 2] = To[4 * r + 2]; }
+    if (mirror) {  // R' = (2 s s^T - I) R diag(-1, -1, 1), s = t / |t|
+        const double n = sqrt(to[0] * to[0] + to[1] * to[1] + to[2] * to[2]);
+        const double s[3] = {to[0] / n, to[1] / n, to[2] / n};
+        double Rs[9], Rm[9];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) Rs[3 * i + j] = 2.0 * s[i] * s[j] - (i == j ? 1.0 : 0.0);
+        mat3_mul_dev(Rs, Ro, Rm);
+#pragma unroll
+        for (int r = 0; r < 3; r++) { Ro[3 * r] = -Rm[3 * r]; Ro[3 * r + 1] = -Rm[3 * r + 1]; Ro[3 * r + 2] = Rm[3 * r + 2]; }
+    }
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) R[3 * i + j] = Ro[3 * i] * M[4 * j] + Ro[3 * i + 1] * M[4 * j + 1] + Ro[3 * i + 2] * M[4 * j + 2];  // Ro Rm^T
+#pragma unroll
+    for (int i = 0; i < 3; i++) t[i] = to[i] - (R[3 * i] * M[3] + R[3 * i + 1] * M[7] + R[3 * i + 2] * M[11]);
+}
+
+// LDS of one frame (dynamic): world corners double[3 * n4], image corners float[2 * n4], slot area double[max_tags],
+// slot state int[max_tags] (0 out, 1 taking part, 2 dropped by the gate)
+__host__ __device__ constexpr size_t loc_lds_bytes(int max_tags)
+{
+    return (size_t)max_tags * (4 * 3 * sizeof(double) + 4 * 2 * sizeof(float) + sizeof(double) + sizeof(int));
+}
+
+// status 1 (no taking-part slot) / 2 (no candidate): identity pose, nothing used
+__device__ __forceinline__ void loc_write_none(CamPoseRec *o, int status)
+{
+#pragma unroll
+    for (int i = 0; i < 16; i++) o->T[i] = (i % 5 == 0) ? 1.0 : 0.0;
+    o->rms_px = 0; o->rms_seed_px = 0; o->n_tags = 0; o->n_rejected = 0; o->status = status; o->seed_slot = -1;
+}
+
+__global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs, int max_tags, const MapTagRec *__restrict__ map, int n_ids,
+                                                 CamDev cam, double gate, CamPoseRec *__restrict__ out)
+{
+    extern __shared__ double s_dyn[];
+    const int n4 = 4 * max_tags, lane = threadIdx.x;
+    double *s_X = s_dyn;
+    double *s_area = s_X + 3 * n4;
+    float *s_uv = (float *)(s_area + max_tags);
+    int *s_state = (int *)(s_uv + 2 * n4);
+    const ObsRec *fo = obs + (size_t)blockIdx.x * max_tags;
+    CamPoseRec *o = out + blockIdx.x;
+
+    // 1: gather
+    int npart = 0, nseed = 0;
+    for (int s = lane; s < max_tags; s += ASL_WAVE) {
+        const int id = fo[s].id, fl = fo[s].flags;
+        const bool part = (fl & 1) && id >= 0 && id < n_ids && map[id].valid;
+        s_state[s] = part ? 1 : 0;
+        s_area[s] = -1.0;
+        if (!part) continue;
+        npart++;
+        const double *M = map[id].T;
+        float cf[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) cf[k] = fo[s].corners[k];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const double ox = (q == 1 || q == 2) ? cam.half : -cam.half, oy = (q >= 2) ? cam.half : -cam.half;
+#pragma unroll
+            for (int r = 0; r < 3; r++) s_X[3 * (4 * s + q) + r] = M[4 * r] * ox + M[4 * r + 1] * oy + M[4 * r + 3];
+            s_uv[2 * (4 * s + q)] = cf[2 * q];
+            s_uv[2 * (4 * s + q) + 1] = cf[2 * q + 1];
+        }
+        if (fl & 2) {
+            nseed++;
+            const double x0 = cf[0], y0 = cf[1], x1 = cf[2], y1 = cf[3], x2 = cf[4], y2 = cf[5], x3 = cf[6], y3 = cf[7];
+            const double a = (x0 * y1 - x1 * y0) + (x1 * y2 - x2 * y1) + (x2 * y3 - x3 * y2) + (x3 * y0 - x0 * y3);
+            s_area[s] = 0.5 * fabs(a);
+        }
+    }
+    __syncthreads();
+    npart = wave_sum_i32(npart);
+    nseed = wave_sum_i32(nseed);
+    if (npart == 0 || nseed == 0) {
+        if (lane == 0) loc_write_none(o, npart == 0 ? 1 : 2);
+        return;
+    }
+
+    // 2: the seeding slots of largest area (ties: lower slot), then every candidate in slot order, plain before mirrored
+    int sel[LOC_MAX_SEEDS];
+    int nsel = 0;
+#pragma unroll
+    for (int r = 0; r < LOC_MAX_SEEDS; r++) {
+        double ba = -1.0;
+        int bs = 0x7fffffff;
+        for (int s = lane; s < max_tags; s += ASL_WAVE)
+            if (s_area[s] > ba) { ba = s_area[s]; bs = s; }  // a lane's slots ascend: a tie keeps the lower one
+        argmax_step<1>(ba, bs); argmax_step<2>(ba, bs); argmax_step<4>(ba, bs);
+        argmax_step<8>(ba, bs); argmax_step<16>(ba, bs); argmax_step<32>(ba, bs);
+        sel[r] = ba >= 0 ? bs : 0x7fffffff;
+        if (ba >= 0) nsel++;
+        __syncthreads();
+        if (lane == 0 && ba >= 0) s_area[bs] = -1.0;
+        __syncthreads();
+    }
+    double R[9], t[3], best = INFINITY;
+    int code = -1, prev = -1;
+    for (int j = 0; j < nsel; j++) {
+        int s = 0x7fffffff;
+#pragma unroll
+        for (int r = 0; r < LOC_MAX_SEEDS; r++)
+            if (sel[r] > prev && sel[r] < s) s = sel[r];
+        prev = s;
+        double To[12], M[12];
+        const double *Mp = map[fo[s].id].T;
+#pragma unroll
+        for (int k = 0; k < 12; k++) { To[k] = fo[s].T[k]; M[k] = Mp[k]; }
+        for (int m = 0; m < 2; m++) {
+            double Rc[9], tc[3];
+            loc_candidate(To, M, m == 1, Rc, tc);
+            const double cc = loc_pass<false>(cam, Rc, tc, s_X, s_uv, s_state, n4, lane, nullptr);
+            if (cc < best) {
+                best = cc;
+                code = s + LOC_MIRRORED * m;
+#pragma unroll
+                for (int i = 0; i < 9; i++) R[i] = Rc[i];
+                t[0] = tc[0]; t[1] = tc[1]; t[2] = tc[2];
+            }
+        }
+    }
+    if (code < 0) {  // every candidate scored NaN
+        if (lane == 0) loc_write_none(o, 2);
+        return;
+    }
+
+    // 3: refine
+    double cost = loc_lm(cam, R, t, s_X, s_uv, s_state, n4, lane);
+
+    // 4: the gate, one slot at a time: the worst slot over the gate goes, and the solve runs again from the current pose
+    int nused = npart, nrej = 0;
+    if (gate > 0) {
+        for (int round = 0; round < LOC_MAX_GATE_DROPS && nused > 1; round++) {
+            double wr = -1.0;
+            int ws = 0x7fffffff;
+            for (int s = lane; s < max_tags; s += ASL_WAVE) {
+                if (s_state[s] != 1) continue;
+                double e[4];
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const int k = 4 * s + q;
+                    e[q] = loc_corner<false>(cam, R, t, s_X + 3 * k, (double)s_uv[2 * k], (double)s_uv[2 * k + 1], nullptr);
+                }
+                const double rms = sqrt(((e[0] + e[1]) + (e[2] + e[3])) / 4);
+                if (rms > wr) { wr = rms; ws = s; }
+            }
+            argmax_step<1>(wr, ws); argmax_step<2>(wr, ws); argmax_step<4>(wr, ws);
+            argmax_step<8>(wr, ws); argmax_step<16>(wr, ws); argmax_step<32>(wr, ws);
+            if (!(wr > gate)) break;
+            __syncthreads();
+            if (lane == 0) s_state[ws] = 2;
+            __syncthreads();
+            nrej++;
+            nused--;
+            cost = loc_lm(cam, R, t, s_X, s_uv, s_state, n4, lane);
+        }
+    }
+
+    // 5: world<-camera = inv(camera<-world)
+    if (lane == 0) {
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            o->T[4 * r] = R[r]; o->T[4 * r + 1] = R[3 + r]; o->T[4 * r + 2] = R[6 + r];
+            o->T[4 * r + 3] = -(R[r] * t[0] + R[3 + r] * t[1] + R[6 + r] * t[2]);
+        }
+        o->T[12] = 0; o->T[13] = 0; o->T[14] = 0; o->T[15] = 1;
+        o->rms_px = sqrt(cost / (4.0 * nused));
+        o->rms_seed_px = sqrt(best / (4.0 * npart));
+        o->n_tags = nused;
+        o->n_rejected = nrej;
+        o->status = 0;
+        o->seed_slot = code;
+    }
+}

@@ -1,0 +1,75 @@
+"""Camera localisation against a known map of tag poses (asl_localize_batch / asl_localize_frames_device).
+
+A frame that sees n mapped tags gives 8n pixel residuals for the 6 unknowns of its camera pose; the joint solve
+(k_localize.inc: best single-view seed -> Levenberg-Marquardt over every tag's corners) is far better conditioned than
+any one tag's planar PnP.  The map may come from SLAM.optimize() (SLAM.tag_map()), from a survey or from a synthetic
+scene (TagMap.from_scene).
+
+    TagMap          ids -> world<-tag 4x4, as the asl_map_tag records the library reads (indexed by id)
+    CAM_POSE_DTYPE  one asl_cam_pose per frame: world<-camera T, rms_px, rms_seed_px, n_tags, n_rejected, status, seed_slot
+"""
+import numpy as np
+
+from ._lib import CAM_POSE_DTYPE, MAP_TAG_DTYPE
+
+STATUS_OK, STATUS_NO_MAPPED_TAG, STATUS_NO_PNP = 0, 1, 2
+
+__all__ = ["TagMap", "CAM_POSE_DTYPE", "MAP_TAG_DTYPE", "STATUS_OK", "STATUS_NO_MAPPED_TAG", "STATUS_NO_PNP"]
+
+
+class TagMap:
+    """World<-tag poses by tag id.  The tag frame is the one the per-tag PnP reports (camera<-tag): corners at (+-h, +-h, 0)
+    in the order lb, rb, rt, lt."""
+
+    def __init__(self, poses=None):
+        self.poses = {}
+        for tag_id, T in (poses or {}).items():
+            self[tag_id] = T
+
+    def __setitem__(self, tag_id, T):
+        tag_id = int(tag_id)
+        if tag_id < 0:
+            raise ValueError("tag ids are non-negative")
+        T = np.array(T, dtype=np.float64)
+        if T.shape == (3, 4):
+            T = np.vstack([T, [0.0, 0.0, 0.0, 1.0]])
+        if T.shape != (4, 4) or not np.all(np.isfinite(T)):
+            raise ValueError("a map pose is a finite 4x4 (or 3x4) world<-tag transform")
+        self.poses[tag_id] = T
+
+    def __getitem__(self, tag_id):
+        return self.poses[int(tag_id)]
+
+    def __contains__(self, tag_id):
+        return int(tag_id) in self.poses
+
+    def __len__(self):
+        return len(self.poses)
+
+    def ids(self):
+        return sorted(self.poses)
+
+    @property
+    def n_ids(self):
+        """length of the id-indexed record array: max id + 1"""
+        return max(self.poses) + 1 if self.poses else 0
+
+    @classmethod
+    def from_dict(cls, poses):
+        """{id: world<-tag 4x4 (or 3x4)}"""
+        return cls(poses)
+
+    @classmethod
+    def from_scene(cls, tags):
+        """tags of synth.random_scene / default_scene ({"id", "position", "rotation"}): the scene's world frame with
+        synth.tag_model_matrix as the tag frame -- the frame in which synth's ground truth camera<-tag poses are given."""
+        from .synth import tag_model_matrix
+        return cls({int(t["id"]): tag_model_matrix(t["position"], t["rotation"]) for t in tags})
+
+    def as_records(self):
+        """(n_ids,) MAP_TAG_DTYPE, indexed by id; ids without a pose have valid = 0"""
+        rec = np.zeros(max(self.n_ids, 1), dtype=MAP_TAG_DTYPE)
+        for tag_id, T in self.poses.items():
+            rec["T"][tag_id] = T[:3].ravel()
+            rec["valid"][tag_id] = 1
+        return rec

@@ -235,6 +235,17 @@ class SLAM:
                               "tags_flipped": [int(tag_ids[j]) for j in flipped], "camera_poses": cam1}
         return self.last_optimize
 
+    # -- localisation against the current map (not in the reference) -------------------------------------------------
+    def tag_map(self):
+        """The graph's nodes as a localize.TagMap: world<-tag = project_se3(node.world), the convention optimize_window uses."""
+        from .localize import TagMap
+        return TagMap({tag_id: project_se3(node.world) for tag_id, node in self.graph.get_nodes().items()})
+
+    def localize(self, detections, max_tag_rms_px=0.0):
+        """Camera pose of one frame from all its mapped tags at once (TagDetector.localize against tag_map()).  Leaves
+        estimated_pose, the graph and the window alone; my_pose() stays the reference's estimator."""
+        return self.detector.localize(detections, self.tag_map(), max_tag_rms_px=max_tag_rms_px)
+
     def average_distance_to_nodes(self):
         """Mean distance camera <-> tag over ALL nodes of the graph (0 for an empty graph), slam.py:65-80."""
         nodes = self.graph.get_nodes()

@@ -123,6 +123,48 @@ class TagDetector:
         rvec, tvec, T, ok = self.detector._det.solve_pnp(c, self.camera_matrix, self._dist(), self.tag_size)
         return ok, rvec, tvec, T
 
+    # -- camera pose from every visible tag against a known map (asl_localize_batch) ---------------------------------
+    def localize(self, detections, tag_map, max_tag_rms_px=0.0):
+        """One frame's detection dicts (as detect() returns them) -> the camera pose from all mapped tags at once:
+        {"ok", "T" world<-camera 4x4, "rms_px", "n_tags", "n_rejected", "status"}.  The poses detect() solved in its own
+        submission are reused; detections without one get their PnP first (one launch).  max_tag_rms_px > 0 drops tags
+        whose own corner RMS exceeds it (moved or mis-identified tags) and solves again."""
+        dets = list(detections)
+        if len(dets) > 256:
+            raise ValueError("at most 256 detections per frame")
+        obs = np.zeros((1, max(1, len(dets))), dtype=_lib.OBS_DTYPE)
+        obs["id"] = -1
+        Ts = [None] * len(dets)
+        oks = [False] * len(dets)
+        missing = []
+        for k, d in enumerate(dets):
+            cached = d.get('_pose') if isinstance(d, dict) else None
+            if cached is not None and cached[1] == self._pose_key() and np.array_equal(cached[0], d['lb-rb-rt-lt']):
+                oks[k], Ts[k] = cached[2], self.transformation(cached[3], cached[4])
+            else:
+                missing.append(k)
+        if missing:
+            ok, _, _, T = self.get_poses([dets[k] for k in missing])
+            for j, k in enumerate(missing):
+                oks[k], Ts[k] = bool(ok[j]), T[j]
+        for k, d in enumerate(dets):
+            obs["id"][0, k] = int(d['id'])
+            obs["flags"][0, k] = 1 | (2 if oks[k] else 0)
+            obs["corners"][0, k] = np.asarray(d['lb-rb-rt-lt'], dtype=np.float32).reshape(8)
+            obs["T"][0, k] = np.asarray(Ts[k], dtype=np.float64).reshape(16)[:12]
+        r = self.detector._det.localize(obs, tag_map, self.camera_matrix, self._dist(), self.tag_size, max_tag_rms_px)[0]
+        return {"ok": int(r["status"]) == 0, "T": np.array(r["T"]), "rms_px": float(r["rms_px"]), "n_tags": int(r["n_tags"]),
+                "n_rejected": int(r["n_rejected"]), "status": int(r["status"])}
+
+    def localize_batch(self, dets, poses, n_per_frame, tag_map, max_tag_rms_px=0.0, max_tags=None):
+        """The structured arrays detect_host / collect return (detections in (frame, id) order, their poses, the count per
+        frame) -> one CAM_POSE_DTYPE record per frame.  max_tags: slots per frame (default: the most detections of a frame)."""
+        from .dist import pack_observations
+        npf = np.asarray(n_per_frame, dtype=np.int64)
+        mt = int(max_tags) if max_tags is not None else max(1, int(npf.max()) if len(npf) else 1)
+        obs = pack_observations(dets, poses, npf, mt)
+        return self.detector._det.localize(obs, tag_map, self.camera_matrix, self._dist(), self.tag_size, max_tag_rms_px)
+
     def detect_batch_device(self, data_ptr, n_frames, channels, width, height, with_pose=True, stream=0, **kw):
         """Frames resident in HBM -> (dets, poses, n_per_frame) structured arrays (see _lib)."""
         K = self.camera_matrix if with_pose else None

@@ -184,6 +184,39 @@ int asl_graph_frames_device(asl_detector *det, const void *d_obs, int world, int
 int asl_graph_picks_device(asl_detector *det, const void *d_obs, int world, int n_frames, int max_tags, const uint8_t *d_status,
                            unsigned int order_lo, unsigned int order_hi, uint32_t *d_last, int n_ids, void *d_picks, void *stream);
 
+/* ---- after the detector: the camera pose of every frame from all its tags against a known map of tag poses (a "tag bundle").
+   The map may come from the pose-graph back-end, from a survey or from a synthetic scene. */
+typedef struct {
+    double T[12];    /* world<-tag, rows 0..2 of the 4x4 (the tag frame of asl_pose: corners (+-h, +-h, 0), lb rb rt lt) */
+    int32_t valid;   /* 0: no pose for this id */
+    int32_t reserved;
+} asl_map_tag;       /* indexed by tag id; 104 bytes */
+
+typedef struct {
+    double T[16];        /* world<-camera, row-major (the convention of asl_gn_solve's cam_T) */
+    double rms_px;       /* final reprojection RMS (pixels per corner) over the slots used */
+    double rms_seed_px;  /* the same of the winning candidate before refinement, over every slot that took part */
+    int32_t n_tags;      /* slots used in the final solve */
+    int32_t n_rejected;  /* slots dropped by the gate */
+    int32_t status;      /* 0 ok, 1 no mapped tag in view, 2 no slot with a successful PnP */
+    int32_t seed_slot;   /* slot of the winning candidate; +256 if it was the mirrored one; -1 if none */
+} asl_cam_pose;          /* 160 bytes */
+
+/* One camera pose per frame of d_obs (n_frames x max_tags records as asl_pack_observations_device writes them), device
+   pointers, asynchronous on `stream`.  A slot takes part if flags & 1 and its id has a valid map entry (id < n_ids); its
+   4 corners are residuals against the map tag's corners.  The seed is the best, over all taking-part corners, of the
+   poses that the PnP of the <= 8 largest slots with flags & 2 imply through the map, each also in its mirrored planar
+   minimum; Levenberg-Marquardt on the 6 pose parameters refines it (K 9 doubles row-major, dist n_dist = 0, 4 or 5
+   coefficients, as asl_solve_pnp_batch).  max_tag_rms_px > 0 is an outlier gate: while the slot of largest own corner RMS
+   exceeds it, that slot is dropped and the solve runs again (one slot at a time, at most 8, never the last); 0 turns it off.  max_tags in [1, 256]; deterministic: the same input gives the same bytes. */
+int asl_localize_frames_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                               const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
+                               void *d_out, void *stream);
+/* The same computation on host records, synchronous (the detector keeps the device copies and grows them on demand). */
+int asl_localize_batch(asl_detector *det, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                       const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
+                       asl_cam_pose *out);
+
 /* ---- before the detector: the image-formation step on the device (reference src/simulation/renderer.py:197-274:
    purple clear colour, one GL_LINEAR-textured quad per tag, BGR read-back).  One plane per visible tag and frame, in
    painter's order (far to near); a plane with tex < 0 ends a frame's list. */

@@ -1,0 +1,297 @@
+"""NumPy statement of the multi-tag camera localisation (asl_localize_frames_device / asl_localize_batch,
+aprilslam_amd/csrc/k_localize.inc): the same gather, candidate order, tie-break, Levenberg-Marquardt schedule and outlier
+gate, frame by frame on the host.  Test infrastructure, as oracle/gn_oracle.py is for the pose-graph LM.
+
+Per frame (one row of n_frames x max_tags asl_obs records) against a map of world<-tag poses indexed by id:
+
+  gather   a slot takes part if flags & 1, 0 <= id < n_ids and map[id].valid; its 4 corners are 4 residual pairs
+           against the map tag's corners (object corners +-h, h = float32(tag_size / 2), lb rb rt lt).  A slot seeds
+           candidates only if its PnP succeeded (flags & 2).
+  seed     the <= 8 seeding slots of largest corner area (ties: lower slot), in slot order, each with its PnP pose and
+           that pose's mirrored planar minimum: camera<-world = T_obs inv(map[id]).  Every candidate is scored by its
+           total squared pixel error over ALL taking-part corners; the strictly lowest wins, so ties go to the lower
+           slot and to the plain pose before the mirrored one.  seed_slot = slot (+256 if mirrored).
+  refine   LM on camera<-world, left update T <- [Rod(w) | v] T, delta = (w, v), analytic Jacobian
+           dp_c/d delta = [-[p_c]x | I] through the camera model of k_pnp.inc (pinhole + 0 / 4 / 5 cv2 coefficients):
+           at most 10 trial steps; (H + lambda diag(H)) delta = -g with lambda0 = 1e-3, x10 after a rejected step (or a
+           failed Cholesky), x0.1 after an accepted one; an accepted step whose cost decrease is below 1e-12 of the
+           cost before it ends the solve.  A corner at z <= 1e-9 costs 1e12 and adds nothing to H and g.
+  gate     max_tag_rms_px > 0: after the solve, the slot with the largest own 4-corner RMS
+           (sqrt(((e0 + e1) + (e2 + e3)) / 4), e = squared pixel distance of a corner; ties: lower slot) is dropped if
+           that RMS exceeds the gate, and the solve runs again from the current pose; repeated while the worst slot of
+           the new solve exceeds the gate, at most 8 times, and never down to no slot.  One slot at a time: a moved tag
+           drags the first solve, and with it the residuals of its neighbours, over the gate as well.
+  output   T = world<-camera 4x4; rms_px = sqrt(cost / (4 n_tags)) of the final solve; rms_seed_px the same of the
+           winning candidate over all taking-part slots; status 1 (no taking-part slot) / 2 (no seeding slot) leave T the
+           identity, the counts 0 and seed_slot -1.
+"""
+import numpy as np
+
+from aprilslam_amd.localize import CAM_POSE_DTYPE
+
+MAX_SEED_SLOTS = 8
+LM_ITERS = 10
+LAMBDA0 = 1e-3
+REL_STOP = 1e-12
+Z_MIN = 1e-9
+BEHIND_COST = 1e12
+MIRRORED = 256
+MAX_GATE_DROPS = 8
+
+
+def half_size(tag_size):
+    return float(np.float32(tag_size / 2))
+
+
+def object_corners(tag_size):
+    h = half_size(tag_size)
+    return np.array([[-h, -h], [h, -h], [h, h], [-h, h]], dtype=np.float64)
+
+
+def camera(K, dist):
+    K = np.asarray(K, dtype=np.float64)
+    d = (list(np.asarray(dist if dist is not None else [], dtype=np.float64).ravel()) + [0.0] * 5)[:5]
+    return (K[0, 0], K[1, 1], K[0, 2], K[1, 2]) + tuple(d)
+
+
+def project(cam, P, jac=False):
+    """pixel coordinates (n, 2) of camera-frame points P (n, 3), and d uv / d P (n, 2, 3): the formulas of project_dev"""
+    fx, fy, cx, cy, k1, k2, p1, p2, k3 = cam
+    iz = 1 / P[:, 2]
+    x, y = P[:, 0] * iz, P[:, 1] * iz
+    r2 = x * x + y * y
+    cd = 1 + ((k3 * r2 + k2) * r2 + k1) * r2
+    dcd = k1 + r2 * (2 * k2 + 3 * k3 * r2)
+    xd = x * cd + 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
+    yd = y * cd + p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+    uv = np.stack([fx * xd + cx, fy * yd + cy], axis=1)
+    if not jac:
+        return uv
+    dxd_dx = cd + x * dcd * 2 * x + 2 * p1 * y + p2 * (2 * x + 4 * x)
+    dxd_dy = x * dcd * 2 * y + 2 * p1 * x + p2 * 2 * y
+    dyd_dx = y * dcd * 2 * x + p1 * 2 * x + 2 * p2 * y
+    dyd_dy = cd + y * dcd * 2 * y + p1 * (2 * y + 4 * y) + 2 * p2 * x
+    z0 = np.zeros_like(iz)
+    dx_dP = np.stack([iz, z0, -x * iz], axis=1)
+    dy_dP = np.stack([z0, iz, -y * iz], axis=1)
+    J = np.empty((len(P), 2, 3))
+    J[:, 0] = fx * (dxd_dx[:, None] * dx_dP + dxd_dy[:, None] * dy_dP)
+    J[:, 1] = fy * (dyd_dx[:, None] * dx_dP + dyd_dy[:, None] * dy_dP)
+    return uv, J
+
+
+def rodrigues(r):
+    """rodrigues_dev"""
+    theta = np.sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2])
+    if theta < 2.220446049250313e-16:
+        return np.eye(3)
+    c, s = np.cos(theta), np.sin(theta)
+    c1, it = 1 - c, 1 / theta
+    x, y, z = r[0] * it, r[1] * it, r[2] * it
+    return np.array([[c + c1 * x * x, c1 * x * y - s * z, c1 * x * z + s * y],
+                     [c1 * x * y + s * z, c + c1 * y * y, c1 * y * z - s * x],
+                     [c1 * x * z - s * y, c1 * y * z + s * x, c + c1 * z * z]])
+
+
+def mirrored(R, t):
+    """map_init.mirrored_pose of camera<-tag (R, t)"""
+    s = t / np.sqrt(t @ t)
+    Rs = 2.0 * np.outer(s, s) - np.eye(3)
+    return Rs @ R @ np.diag([-1.0, -1.0, 1.0]), t.copy()
+
+
+def corner_area(c8):
+    """shoelace area of the float32 corners, in the kernel's operation order"""
+    x = [float(c8[0]), float(c8[2]), float(c8[4]), float(c8[6])]
+    y = [float(c8[1]), float(c8[3]), float(c8[5]), float(c8[7])]
+    a = (x[0] * y[1] - x[1] * y[0]) + (x[1] * y[2] - x[2] * y[1]) + (x[2] * y[3] - x[3] * y[2]) + (x[3] * y[0] - x[0] * y[3])
+    return 0.5 * abs(a)
+
+
+def corner_costs(cam, R, t, Xw, uv):
+    P = Xw @ R.T + t
+    ok = P[:, 2] > Z_MIN
+    e = np.full(len(P), BEHIND_COST)
+    if ok.any():
+        r = project(cam, P[ok]) - uv[ok]
+        e[ok] = r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1]
+    return e
+
+
+def linearise(cam, R, t, Xw, uv):
+    P = Xw @ R.T + t
+    ok = P[:, 2] > Z_MIN
+    cost = BEHIND_COST * float((~ok).sum())
+    H, g = np.zeros((6, 6)), np.zeros(6)
+    if ok.any():
+        p = P[ok]
+        q, Jp = project(cam, p, jac=True)
+        r = q - uv[ok]
+        cost += float((r * r).sum())
+        neg_px = np.zeros((len(p), 3, 3))           # -[p]x
+        neg_px[:, 0, 1], neg_px[:, 0, 2] = p[:, 2], -p[:, 1]
+        neg_px[:, 1, 0], neg_px[:, 1, 2] = -p[:, 2], p[:, 0]
+        neg_px[:, 2, 0], neg_px[:, 2, 1] = p[:, 1], -p[:, 0]
+        J = np.concatenate([Jp @ neg_px, Jp], axis=2).reshape(-1, 6)
+        H = J.T @ J
+        g = J.T @ r.reshape(-1)
+    return cost, H, g
+
+
+def chol6_solve(A, b):
+    """chol6_solve_tri_dev on the lower triangle; None if A is not positive definite"""
+    L = np.zeros((6, 6))
+    inv = np.zeros(6)
+    for i in range(6):
+        for j in range(i + 1):
+            s = A[i, j]
+            for k in range(j):
+                s -= L[i, k] * L[j, k]
+            if i == j:
+                if not s > 0:
+                    return None
+                L[i, i] = np.sqrt(s)
+                inv[i] = 1 / L[i, i]
+            else:
+                L[i, j] = s * inv[j]
+    x = np.array(b, dtype=np.float64)
+    for i in range(6):
+        s = x[i]
+        for k in range(i):
+            s -= L[i, k] * x[k]
+        x[i] = s * inv[i]
+    for i in range(5, -1, -1):
+        s = x[i]
+        for k in range(i + 1, 6):
+            s -= L[k, i] * x[k]
+        x[i] = s * inv[i]
+    return x
+
+
+def lm(cam, R, t, Xw, uv):
+    """the fixed schedule of the module docstring; returns (R, t, cost)"""
+    cost, H, g = linearise(cam, R, t, Xw, uv)
+    lam = LAMBDA0
+    for _ in range(LM_ITERS):
+        A = H.copy()
+        A[np.diag_indices(6)] += lam * np.diag(H)
+        d = chol6_solve(A, -g)
+        if d is None:
+            lam *= 10
+            continue
+        dR = rodrigues(d[:3])
+        Rn, tn = dR @ R, dR @ t + d[3:]
+        cn = float(corner_costs(cam, Rn, tn, Xw, uv).sum())
+        if cn < cost:
+            stop = cost - cn < REL_STOP * cost
+            R, t, cost = Rn, tn, cn
+            lam *= 0.1
+            if stop:
+                break
+            cost, H, g = linearise(cam, R, t, Xw, uv)
+        else:
+            lam *= 10
+    return R, t, cost
+
+
+def _world_corners(M12, obj):
+    M = np.asarray(M12, dtype=np.float64).reshape(3, 4)
+    return np.stack([M[:, 0] * ox + M[:, 1] * oy + M[:, 3] for ox, oy in obj])
+
+
+def seed_candidates(rows, tag_map, cam, seeds, Xw, uv):
+    """[(R, t, seed code, score)] in candidate order: the <= 8 seeding slots of largest area in slot order, plain then mirrored"""
+    area = {s: corner_area(rows["corners"][s]) for s in seeds}
+    chosen = sorted(sorted(seeds, key=lambda s: (-area[s], s))[:MAX_SEED_SLOTS])
+    out = []
+    for s in chosen:
+        To = rows["T"][s].reshape(3, 4)
+        M = tag_map["T"][rows["id"][s]].reshape(3, 4)
+        for m in (0, 1):
+            Ro, to = To[:, :3], To[:, 3]
+            if m:
+                Ro, to = mirrored(Ro, to)
+            Rc = Ro @ M[:, :3].T                    # camera<-world = T_obs inv(map)
+            tc = to - Rc @ M[:, 3]
+            out.append((Rc, tc, s + MIRRORED * m, float(corner_costs(cam, Rc, tc, Xw, uv).sum())))
+    return out
+
+
+def candidate_scores(rows, tag_map, K, dist, tag_size):
+    """{seed code: score} of one frame's candidates (for comparing a choice between candidates that tie to rounding)"""
+    cam = camera(K, dist)
+    n_ids = len(tag_map)
+    obj = object_corners(tag_size)
+    part = [s for s, o in enumerate(rows) if (o["flags"] & 1) and 0 <= o["id"] < n_ids and tag_map["valid"][o["id"]]]
+    seeds = [s for s in part if rows["flags"][s] & 2]
+    if not seeds:
+        return {}
+    Xw = np.concatenate([_world_corners(tag_map["T"][rows["id"][s]], obj) for s in part])
+    uv = np.concatenate([rows["corners"][s].astype(np.float64).reshape(4, 2) for s in part])
+    return {code: c for _, _, code, c in seed_candidates(rows, tag_map, cam, seeds, Xw, uv)}
+
+
+def localize_frame(rows, tag_map, cam, tag_size, gate):
+    """one frame's max_tags asl_obs records -> one CAM_POSE_DTYPE record"""
+    out = np.zeros((), dtype=CAM_POSE_DTYPE)
+    out["T"] = np.eye(4)
+    out["seed_slot"] = -1
+    n_ids = len(tag_map)
+    obj = object_corners(tag_size)
+    part = [s for s, o in enumerate(rows) if (o["flags"] & 1) and 0 <= o["id"] < n_ids and tag_map["valid"][o["id"]]]
+    if not part:
+        out["status"] = 1
+        return out
+    seeds = [s for s in part if rows["flags"][s] & 2]
+    if not seeds:
+        out["status"] = 2
+        return out
+    Xw = np.concatenate([_world_corners(tag_map["T"][rows["id"][s]], obj) for s in part])
+    uv = np.concatenate([rows["corners"][s].astype(np.float64).reshape(4, 2) for s in part])
+
+    cands = seed_candidates(rows, tag_map, cam, seeds, Xw, uv)
+    best, best_cost = None, np.inf
+    for Rc, tc, code, c in cands:
+        if c < best_cost:
+            best, best_cost = (Rc, tc, code), c
+    if best is None:
+        out["status"] = 2
+        return out
+    R, t, code = best
+    n_part = len(part)
+    R, t, cost = lm(cam, R, t, Xw, uv)
+    n_used, n_rej = n_part, 0
+    if gate > 0:
+        active = np.ones(n_part, dtype=bool)
+        while n_rej < MAX_GATE_DROPS and n_used > 1:
+            e = corner_costs(cam, R, t, Xw, uv).reshape(-1, 4)
+            rms = np.where(active, np.sqrt(((e[:, 0] + e[:, 1]) + (e[:, 2] + e[:, 3])) / 4), -1.0)
+            worst = int(np.argmax(rms))                 # the first of equal maxima: the lower slot
+            if not rms[worst] > gate:
+                break
+            active[worst] = False
+            n_rej += 1
+            n_used -= 1
+            keep = np.repeat(active, 4)
+            R, t, cost = lm(cam, R, t, Xw[keep], uv[keep])
+    T = np.eye(4)
+    T[:3, :3] = R.T
+    T[:3, 3] = -(R.T @ t)
+    out["T"] = T
+    out["rms_px"] = np.sqrt(cost / (4 * n_used))
+    out["rms_seed_px"] = np.sqrt(best_cost / (4 * n_part))
+    out["n_tags"] = n_used
+    out["n_rejected"] = n_rej
+    out["status"] = 0
+    out["seed_slot"] = code
+    return out
+
+
+def localize(obs, tag_map, K, dist, tag_size, max_tag_rms_px=0.0):
+    """obs (n_frames, max_tags) asl_obs records, tag_map (n_ids,) asl_map_tag records -> (n_frames,) CAM_POSE_DTYPE"""
+    obs = np.asarray(obs)
+    if obs.ndim == 1:
+        obs = obs[None]
+    cam = camera(K, dist)
+    return np.array([localize_frame(obs[f], tag_map, cam, tag_size, float(max_tag_rms_px)) for f in range(len(obs))],
+                    dtype=CAM_POSE_DTYPE)
