@@ -32,6 +32,12 @@ class AslCamPose(C.Structure):
                 ("n_rejected", C.c_int32), ("status", C.c_int32), ("seed_slot", C.c_int32)]
 
 
+class AslCalibResult(C.Structure):
+    _fields_ = [("K", C.c_double * 9), ("dist", C.c_double * 5), ("std", C.c_double * 9), ("rms_px", C.c_double),
+                ("rms_init_px", C.c_double), ("n_frames_used", C.c_int32), ("n_corners", C.c_int32), ("iterations", C.c_int32),
+                ("status", C.c_int32)]
+
+
 class AslDebugQuad(C.Structure):
     _fields_ = [("p", (C.c_double * 2) * 4), ("cluster", C.c_uint64), ("frame", C.c_int32), ("reversed_border", C.c_int32)]
 
@@ -46,17 +52,21 @@ POSE_DTYPE = np.dtype([("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)), ("T", "<f8"
 MAP_TAG_DTYPE = np.dtype([("T", "<f8", (12,)), ("valid", "<i4"), ("reserved", "<i4")])  # asl_map_tag
 CAM_POSE_DTYPE = np.dtype([("T", "<f8", (4, 4)), ("rms_px", "<f8"), ("rms_seed_px", "<f8"), ("n_tags", "<i4"), ("n_rejected", "<i4"),
                            ("status", "<i4"), ("seed_slot", "<i4")])  # asl_cam_pose
+CALIB_RESULT_DTYPE = np.dtype([("K", "<f8", (3, 3)), ("dist", "<f8", (5,)), ("std", "<f8", (9,)), ("rms_px", "<f8"),
+                               ("rms_init_px", "<f8"), ("n_frames_used", "<i4"), ("n_corners", "<i4"), ("iterations", "<i4"),
+                               ("status", "<i4")])  # asl_calib_result
 QUAD_DTYPE = np.dtype([("p", "<f8", (4, 2)), ("cluster", "<u8"), ("frame", "<i4"), ("reversed_border", "<i4")])
 assert DET_DTYPE.itemsize == C.sizeof(AslDetection)
 assert POSE_DTYPE.itemsize == C.sizeof(AslPose)
 assert QUAD_DTYPE.itemsize == C.sizeof(AslDebugQuad)
 assert MAP_TAG_DTYPE.itemsize == C.sizeof(AslMapTag) == 104
 assert CAM_POSE_DTYPE.itemsize == C.sizeof(AslCamPose) == 160
+assert CALIB_RESULT_DTYPE.itemsize == C.sizeof(AslCalibResult) == 216
 
 EXPORTS = [
     "asl_detector_create", "asl_detector_destroy", "asl_detector_set_id_limit", "asl_detector_set_pnp_both_minima", "asl_last_error", "asl_version", "asl_detect_gray_u8",
     "asl_detect_bgr_u8", "asl_detect_batch_u8", "asl_detect_batch_pose_u8", "asl_detect_batch_device", "asl_submit_batch_device", "asl_collect_batch", "asl_collect_batch_view", "asl_solve_pnp_batch", "asl_gn_solve", "asl_pack_observations_device", "asl_graph_frames_device", "asl_graph_picks_device", "asl_render_frames_device",
-    "asl_localize_frames_device", "asl_localize_batch",
+    "asl_localize_frames_device", "asl_localize_batch", "asl_calibrate_frames_device", "asl_calibrate_batch",
     "asl_debug_fetch", "asl_stage_times", "asl_set_profiling", "asl_debug_phase_cycles",
 ]
 
@@ -106,6 +116,8 @@ def load():
     L.asl_graph_picks_device.argtypes = [vp, vp, i32, i32, i32, vp, C.c_uint32, C.c_uint32, vp, i32, vp, vp]
     L.asl_localize_frames_device.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, C.c_double, vp, vp]
     L.asl_localize_batch.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, C.c_double, vp]
+    L.asl_calibrate_frames_device.argtypes = [vp, vp, i32, i32, vp, i32, C.c_double, i32, i32, dp, i32, i32, i32, vp, vp, vp]
+    L.asl_calibrate_batch.argtypes = [vp, vp, i32, i32, vp, i32, C.c_double, i32, i32, dp, i32, i32, i32, vp, vp]
     L.asl_debug_fetch.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.asl_stage_times.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32, C.POINTER(i32)]
     L.asl_set_profiling.argtypes = [vp, i32]
@@ -326,6 +338,48 @@ class Detector:
         check(self._L.asl_localize_frames_device(self._h, C.c_void_p(int(obs_ptr)), int(n_frames), int(max_tags), C.c_void_p(int(map_ptr)),
                                                  int(n_ids), Kp, dpp, nd, float(tag_size), float(max_tag_rms_px),
                                                  C.c_void_p(int(out_ptr)), C.c_void_p(int(stream))))
+
+    @staticmethod
+    def _calib_args(K_init, n_dist):
+        if int(n_dist) not in (0, 4, 5):
+            raise ValueError("n_dist must be 0, 4 or 5")
+        if K_init is None:
+            return None, None
+        Kc = np.ascontiguousarray(K_init, dtype=np.float64)
+        if Kc.shape != (3, 3):
+            raise ValueError("K_init must be 3x3")
+        return Kc, Kc.ctypes.data_as(C.POINTER(C.c_double))
+
+    def calibrate(self, obs, tag_map, tag_size, width, height, K_init=None, n_dist=5, flags=0, max_iters=30):
+        """asl_calibrate_batch: host records obs (n_frames, max_tags) OBS_DTYPE of a target whose tag poses tag_map
+        ((n_ids,) MAP_TAG_DTYPE or a localize.TagMap) gives -> (CALIB_RESULT_DTYPE record, (n_frames,) CAM_POSE_DTYPE)."""
+        if hasattr(tag_map, "as_records"):
+            tag_map = tag_map.as_records()
+        o = np.ascontiguousarray(obs, dtype=OBS_DTYPE)
+        if o.ndim == 1:
+            o = o[None]
+        if o.ndim != 2:
+            raise ValueError("obs must be (n_frames, max_tags) asl_obs records")
+        m = np.ascontiguousarray(tag_map, dtype=MAP_TAG_DTYPE).ravel()
+        keep, Kp = self._calib_args(K_init, n_dist)
+        res = np.zeros((), dtype=CALIB_RESULT_DTYPE)
+        poses = np.zeros(o.shape[0], dtype=CAM_POSE_DTYPE)
+        check(self._L.asl_calibrate_batch(self._h, o.ctypes.data if o.size else None, o.shape[0], o.shape[1],
+                                          m.ctypes.data if m.size else None, len(m), float(tag_size), int(width), int(height), Kp,
+                                          int(n_dist), int(flags), int(max_iters), res.ctypes.data,
+                                          poses.ctypes.data if poses.size else None))
+        return res, poses
+
+    def calibrate_device(self, obs_ptr, n_frames, max_tags, map_ptr, n_ids, tag_size, width, height, result_ptr, poses_ptr,
+                         K_init=None, n_dist=5, flags=0, max_iters=30, stream=0):
+        """asl_calibrate_frames_device: obs_ptr (n_frames x max_tags asl_obs), map_ptr (n_ids asl_map_tag), result_ptr (one
+        asl_calib_result) and poses_ptr (n_frames asl_cam_pose) are device addresses; the whole solve is enqueued on
+        `stream`, no wait."""
+        keep, Kp = self._calib_args(K_init, n_dist)
+        check(self._L.asl_calibrate_frames_device(self._h, C.c_void_p(int(obs_ptr)), int(n_frames), int(max_tags), C.c_void_p(int(map_ptr)),
+                                                  int(n_ids), float(tag_size), int(width), int(height), Kp, int(n_dist), int(flags),
+                                                  int(max_iters), C.c_void_p(int(result_ptr)), C.c_void_p(int(poses_ptr)),
+                                                  C.c_void_p(int(stream))))
 
     def collect_view(self):
         """Wait for the submitted batch; (dets, poses or None, n_per_frame) as numpy VIEWS of the detector's page-locked result

@@ -28,6 +28,7 @@
 #include "k_render.inc"
 #include "k_gn.inc"
 #include "k_localize.inc"
+#include "k_calib.inc"
 
 static thread_local std::string g_err;
 
@@ -115,6 +116,7 @@ struct asl_detector {
     DevBuf<uint8_t> pnp_ok;
     GnWorkspace gn;
     DevBuf<uint8_t> loc_obs, loc_map, loc_out;  // asl_localize_batch: the host records' device copies (grow on demand)
+    DevBuf<uint8_t> cal_ws, cal_out;  // calibration: per-frame workspace and state (k_calib.inc); asl_calibrate_batch's results
     hipStream_t copy_stream = nullptr, host_stream = nullptr;  // host frames: transfers and the chunks' kernels (detect_host_frames)
     std::vector<hipEvent_t> copy_done;
     hipStream_t aux_stream = nullptr;  // highest priority, for the small latency-bound jobs next to a running batch (pose-graph LM)
@@ -268,6 +270,7 @@ extern "C" void asl_detector_destroy(asl_detector *d)
     d->counters.release(); d->pnp_corners.release(); d->pnp_out.release(); d->pnp_ok.release();
     d->gn.release();
     d->loc_obs.release(); d->loc_map.release(); d->loc_out.release();
+    d->cal_ws.release(); d->cal_out.release();
     if (d->aux_stream) (void)hipStreamDestroy(d->aux_stream);
     if (d->copy_stream) (void)hipStreamDestroy(d->copy_stream);
     if (d->host_stream) (void)hipStreamDestroy(d->host_stream);
@@ -1024,6 +1027,114 @@ extern "C" int asl_localize_batch(asl_detector *d, const asl_obs *obs, int n_fra
     launch_localize(d, d->loc_obs.p, n_frames, max_tags, d->loc_map.p, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, d->loc_out.p, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(out, d->loc_out.p, out_bytes, hipMemcpyDeviceToHost));
+    return ASL_OK;
+}
+
+static int check_calib_args(const void *obs, int n_frames, int max_tags, const void *map, int n_ids, double tag_size, int width, int height,
+                            const double *K_init, int n_dist, int flags, int max_iters, const void *result, const void *poses)
+{
+    if (!obs || !map || !result || !poses) return fail(ASL_EINVAL, "NULL argument");
+    if (n_frames < 1) return fail(ASL_EINVAL, "n_frames must be >= 1 (got %d)", n_frames);
+    if (max_tags < 1 || max_tags > 256) return fail(ASL_EINVAL, "max_tags must be in [1, 256] (got %d)", max_tags);
+    if (n_ids < 1) return fail(ASL_EINVAL, "n_ids must be >= 1 (got %d)", n_ids);
+    if (n_dist != 0 && n_dist != 4 && n_dist != 5) return fail(ASL_EINVAL, "n_dist must be 0, 4 or 5");
+    if (!(tag_size > 0) || !std::isfinite(tag_size)) return fail(ASL_EINVAL, "tag_size must be positive (got %g)", tag_size);
+    if (width < 1 || height < 1) return fail(ASL_EINVAL, "width and height must be positive (got %d x %d)", width, height);
+    if (max_iters < 1) return fail(ASL_EINVAL, "max_iters must be >= 1 (got %d)", max_iters);
+    if (flags & ~(ASL_CALIB_FIX_PRINCIPAL_POINT | ASL_CALIB_FIX_ASPECT_RATIO | ASL_CALIB_ZERO_TANGENT_DIST))
+        return fail(ASL_EINVAL, "unknown calibration flags 0x%x", flags);
+    if (K_init && !(K_init[0] > 0 && K_init[4] > 0 && std::isfinite(K_init[0]) && std::isfinite(K_init[4]) && std::isfinite(K_init[2]) &&
+                    std::isfinite(K_init[5])))
+        return fail(ASL_EINVAL, "K_init must have finite, positive focal lengths");
+    return ASL_OK;
+}
+
+// the calibration workspace: state, frame lists and per-frame buffers, each 256-byte aligned, in d->cal_ws
+static int launch_calibrate(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids, double tag_size,
+                            int width, int height, const double *K_init, int n_dist, int flags, int max_iters, void *d_result, void *d_poses,
+                            hipStream_t st)
+{
+    static_assert(sizeof(CalibResultRec) == sizeof(asl_calib_result) && sizeof(asl_calib_result) == 216, "asl_calib_result layout");
+    const size_t nf = (size_t)n_frames;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_st = take(sizeof(CalibState)), o_list = take(sizeof(int) * nf), o_fr = take(sizeof(int) * CAL_FR * nf),
+                 o_zh = take(sizeof(double) * CAL_ZH * nf), o_seed = take(sizeof(double) * nf), o_pose = take(sizeof(double) * 2 * 12 * nf),
+                 o_H = take(sizeof(double) * 2 * CAL_HS * nf), o_SB = take(sizeof(double) * CAL_SB * nf), o_bk = take(sizeof(double) * CAL_BK * nf);
+    if (d->cal_ws.ensure(off)) return fail(ASL_ENOMEM, "calibration workspace allocation failed");
+    uint8_t *w = d->cal_ws.p;
+    CalibArgs a{};
+    a.obs = (const ObsRec *)d_obs; a.map = (const MapTagRec *)d_map;
+    a.st = (CalibState *)(w + o_st); a.list = (int *)(w + o_list); a.fr = (int *)(w + o_fr);
+    a.zh = (double *)(w + o_zh); a.seedc = (double *)(w + o_seed); a.pose = (double *)(w + o_pose); a.H = (double *)(w + o_H);
+    a.SB = (double *)(w + o_SB); a.back = (double *)(w + o_bk);
+    a.res = (CalibResultRec *)d_result; a.out = (CamPoseRec *)d_poses;
+    a.half = (double)(float)(tag_size / 2);  // object corners are float32, as in the PnP
+    a.width = width; a.height = height;
+    a.has_init = K_init != nullptr;
+    if (K_init) { a.Kinit[0] = K_init[0]; a.Kinit[1] = K_init[4]; a.Kinit[2] = K_init[2]; a.Kinit[3] = K_init[5]; }
+    a.n_frames = n_frames; a.max_tags = max_tags; a.n_ids = n_ids; a.n_dist = n_dist; a.flags = flags; a.max_iters = max_iters;
+    int np = 0;  // the free entries of (fx, fy, cx, cy, k1, k2, p1, p2, k3)
+    if (!(flags & ASL_CALIB_FIX_ASPECT_RATIO)) a.sel[np++] = 0;
+    a.sel[np++] = 1;
+    if (!(flags & ASL_CALIB_FIX_PRINCIPAL_POINT)) { a.sel[np++] = 2; a.sel[np++] = 3; }
+    if (n_dist >= 4) {
+        a.sel[np++] = 4; a.sel[np++] = 5;
+        if (!(flags & ASL_CALIB_ZERO_TANGENT_DIST)) { a.sel[np++] = 6; a.sel[np++] = 7; }
+    }
+    if (n_dist == 5) a.sel[np++] = 8;
+    a.np = np;
+    const dim3 frames((unsigned int)n_frames), wave(ASL_WAVE), wg(CAL_WG);
+    const size_t lds = loc_lds_bytes(max_tags);
+    auto seed = n_dist == 5 ? k_calib_seed<5> : n_dist == 4 ? k_calib_seed<4> : k_calib_seed<0>;
+    auto step = n_dist == 5 ? k_calib_step<5> : n_dist == 4 ? k_calib_step<4> : k_calib_step<0>;
+    hipLaunchKernelGGL(k_calib_init, frames, wave, 0, st, a);
+    hipLaunchKernelGGL(k_calib_k0, dim3(1), wg, 0, st, a);
+    hipLaunchKernelGGL(seed, frames, wave, lds, st, a);
+    hipLaunchKernelGGL(k_calib_start, dim3(1), wg, 0, st, a);
+    for (int it = 0; it < max_iters; it++) {
+        hipLaunchKernelGGL(k_calib_schur, frames, wave, 0, st, a, 0);
+        hipLaunchKernelGGL(k_calib_solve, dim3(1), wg, 0, st, a);
+        hipLaunchKernelGGL(step, frames, wave, lds, st, a);
+        hipLaunchKernelGGL(k_calib_decide, dim3(1), wg, 0, st, a);
+    }
+    hipLaunchKernelGGL(k_calib_schur, frames, wave, 0, st, a, 1);
+    hipLaunchKernelGGL(k_calib_finish, dim3(1), wg, 0, st, a);
+    HIPCHK(hipGetLastError());
+    return ASL_OK;
+}
+
+extern "C" int asl_calibrate_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                           double tag_size, int width, int height, const double *K_init, int n_dist, int flags, int max_iters,
+                                           void *d_result, void *d_poses, void *stream)
+{
+    if (!d) return fail(ASL_EINVAL, "NULL detector");
+    int rc = check_calib_args(d_obs, n_frames, max_tags, d_map, n_ids, tag_size, width, height, K_init, n_dist, flags, max_iters, d_result, d_poses);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(d->device));
+    return launch_calibrate(d, d_obs, n_frames, max_tags, d_map, n_ids, tag_size, width, height, K_init, n_dist, flags, max_iters, d_result,
+                            d_poses, (hipStream_t)stream);
+}
+
+extern "C" int asl_calibrate_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                   double tag_size, int width, int height, const double *K_init, int n_dist, int flags, int max_iters,
+                                   asl_calib_result *result, asl_cam_pose *poses)
+{
+    if (!d) return fail(ASL_EINVAL, "NULL detector");
+    int rc = check_calib_args(obs, n_frames, max_tags, map, n_ids, tag_size, width, height, K_init, n_dist, flags, max_iters, result, poses);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(d->device));
+    const size_t obs_bytes = sizeof(asl_obs) * (size_t)n_frames * (size_t)max_tags, map_bytes = sizeof(asl_map_tag) * (size_t)n_ids,
+                 res_bytes = 256, out_bytes = sizeof(asl_cam_pose) * (size_t)n_frames;
+    if (d->loc_obs.ensure(obs_bytes) || d->loc_map.ensure(map_bytes) || d->cal_out.ensure(res_bytes + out_bytes))
+        return fail(ASL_ENOMEM, "calibration workspace allocation failed");
+    HIPCHK(hipMemcpy(d->loc_obs.p, obs, obs_bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d->loc_map.p, map, map_bytes, hipMemcpyHostToDevice));
+    rc = launch_calibrate(d, d->loc_obs.p, n_frames, max_tags, d->loc_map.p, n_ids, tag_size, width, height, K_init, n_dist, flags, max_iters,
+                          d->cal_out.p, d->cal_out.p + res_bytes, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(result, d->cal_out.p, sizeof(asl_calib_result), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(poses, d->cal_out.p + res_bytes, out_bytes, hipMemcpyDeviceToHost));
     return ASL_OK;
 }
 

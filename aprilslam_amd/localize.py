@@ -66,6 +66,24 @@ class TagMap:
         from .synth import tag_model_matrix
         return cls({int(t["id"]): tag_model_matrix(t["position"], t["rotation"]) for t in tags})
 
+    @classmethod
+    def grid(cls, rows, cols, tag_size, spacing, first_id=0):
+        """A planar board of rows x cols tags in the board's z = 0 plane, tag axes along the board's: the tag of row r and
+        column c has id first_id + r * cols + c and its centre at (c * spacing, r * spacing, 0).  spacing is the distance
+        between neighbouring tag centres; tag_size (the side the PnP uses) must fit into it."""
+        rows, cols, first_id = int(rows), int(cols), int(first_id)
+        if rows < 1 or cols < 1 or first_id < 0:
+            raise ValueError("a grid has rows, cols >= 1 and first_id >= 0")
+        if not (tag_size > 0 and spacing >= tag_size):
+            raise ValueError("tag_size must be positive and spacing >= tag_size")
+        poses = {}
+        for r in range(rows):
+            for c in range(cols):
+                T = np.eye(4)
+                T[0, 3], T[1, 3] = c * float(spacing), r * float(spacing)
+                poses[first_id + r * cols + c] = T
+        return cls(poses)
+
     def as_records(self):
         """(n_ids,) MAP_TAG_DTYPE, indexed by id; ids without a pose have valid = 0"""
         rec = np.zeros(max(self.n_ids, 1), dtype=MAP_TAG_DTYPE)

@@ -165,6 +165,26 @@ class TagDetector:
         obs = pack_observations(dets, poses, npf, mt)
         return self.detector._det.localize(obs, tag_map, self.camera_matrix, self._dist(), self.tag_size, max_tag_rms_px)
 
+    # -- camera calibration from frames of a known target (asl_calibrate_batch) ------------------------------------------
+    def calibrate(self, frames, tag_map, n_dist=5, K_init=None, flags=0, max_iters=30):
+        """Host frames ((n, H, W, 3) BGR or (n, H, W) gray uint8, or a list of them) that see the target tag_map (a
+        localize.TagMap, e.g. TagMap.grid) -> calibrate.CalibrationResult: K, dist (n_dist coefficients), std, per-frame
+        poses.  Detect, pack (asl_obs records) and calibrate; this detector's own camera model is not used.  Pass the
+        result's camera_params to a TagDetector afterwards."""
+        from .calibrate import CalibrationResult
+        from .dist import pack_observations
+        a = np.ascontiguousarray(np.stack(frames) if isinstance(frames, (list, tuple)) else frames)
+        if a.ndim not in (3, 4) or a.dtype != np.uint8:
+            raise ValueError("frames must be (n, H, W[, 3]) uint8")
+        height, width = a.shape[1], a.shape[2]
+        dets, npf = self.detector._det.detect_host(a, channels=1 if a.ndim == 3 else None)
+        npf = np.asarray(npf, dtype=np.int64)
+        mt = max(1, min(256, int(npf.max()) if len(npf) else 1))
+        obs = pack_observations(dets, np.zeros(len(dets), dtype=_lib.POSE_DTYPE), npf, mt)  # the calibration reads no PnP pose
+        res, cam = self.detector._det.calibrate(obs, tag_map, self.tag_size, width, height, K_init=K_init, n_dist=n_dist, flags=flags,
+                                                max_iters=max_iters)
+        return CalibrationResult(res, cam, n_dist)
+
     def detect_batch_device(self, data_ptr, n_frames, channels, width, height, with_pose=True, stream=0, **kw):
         """Frames resident in HBM -> (dets, poses, n_per_frame) structured arrays (see _lib)."""
         K = self.camera_matrix if with_pose else None

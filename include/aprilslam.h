@@ -217,6 +217,41 @@ int asl_localize_batch(asl_detector *det, const asl_obs *obs, int n_frames, int 
                        const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
                        asl_cam_pose *out);
 
+/* ---- camera calibration from tag observations: intrinsics and lens distortion of the camera model above (fx fy cx cy,
+   k1 k2 p1 p2 [k3]) from frames that see a rigid target of known tag poses (a planar board or any surveyed arrangement). */
+#define ASL_CALIB_FIX_PRINCIPAL_POINT 1  /* cx, cy stay at K_init's (or the image centre) */
+#define ASL_CALIB_FIX_ASPECT_RATIO    2  /* fx = r fy, r = fx / fy of K_init (1 without) */
+#define ASL_CALIB_ZERO_TANGENT_DIST   4  /* p1 = p2 = 0 */
+typedef struct {
+    double K[9];          /* row-major */
+    double dist[5];       /* k1 k2 p1 p2 k3; unused = 0 */
+    double std[9];        /* fx fy cx cy k1 k2 p1 p2 k3; fixed / unused = 0 */
+    double rms_px;        /* final, per corner, over the frames used */
+    double rms_init_px;   /* after the seed, with K0 and no distortion */
+    int32_t n_frames_used, n_corners, iterations;
+    int32_t status;       /* 0 ok, 1 too few frames/corners, 2 no closed-form focal length, 3 solve failed (non-finite) */
+} asl_calib_result;       /* 216 bytes */
+
+/* Calibrate from d_obs (n_frames x max_tags records as asl_pack_observations_device writes them; only flags & 1, id and
+   corners are read -- the PnP pose in the record was computed with some other K) against d_map (n_ids asl_map_tag).
+   A frame takes part with >= 2 mapped slots.  Without K_init the principal point starts at (width / 2, height / 2) and
+   the focal lengths come in closed form from every tag's homography (Zhang's constraints, least squares); each frame is
+   seeded with that K0 and no distortion (planar pose of its <= 8 largest tags and their mirrored minima, scored over all
+   its corners, then pose-only LM), then Levenberg-Marquardt refines the n_dist = 0, 4 or 5 coefficients, the free
+   intrinsics and every frame's pose together, each frame eliminating its pose block (Schur complement).  std is
+   sqrt(sigma^2 diag(S^-1)) at the solution.  d_result: one asl_calib_result; d_poses: n_frames asl_cam_pose, world<-camera,
+   rms_px final, rms_seed_px after the seed, n_tags, status 0 used, 1 fewer than 2 mapped slots, 3 dropped (every seed
+   candidate had a corner behind the camera), 4 taking part in a calibration that failed.  The whole solve (max_iters >= 1
+   trials) is enqueued on `stream` without a wait; max_tags in [1, 256]; deterministic: the same input gives the same
+   bytes.  tests/calib_ref.py states the algorithm. */
+int asl_calibrate_frames_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                double tag_size, int width, int height, const double *K_init /* 9 or NULL */, int n_dist,
+                                int flags, int max_iters, void *d_result, void *d_poses, void *stream);
+/* The same computation on host records, synchronous (the detector keeps the device copies and grows them on demand). */
+int asl_calibrate_batch(asl_detector *det, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                        double tag_size, int width, int height, const double *K_init, int n_dist, int flags, int max_iters,
+                        asl_calib_result *result, asl_cam_pose *poses);
+
 /* ---- before the detector: the image-formation step on the device (reference src/simulation/renderer.py:197-274:
    purple clear colour, one GL_LINEAR-textured quad per tag, BGR read-back).  One plane per visible tag and frame, in
    painter's order (far to near); a plane with tex < 0 ends a frame's list. */
