@@ -38,6 +38,12 @@ class AslCalibResult(C.Structure):
                 ("status", C.c_int32)]
 
 
+class AslMapResult(C.Structure):
+    _fields_ = [("cost_seed", C.c_double), ("cost", C.c_double), ("rms_px", C.c_double), ("rms_seed_px", C.c_double),
+                ("n_frames_used", C.c_int32), ("n_tags", C.c_int32), ("n_obs", C.c_int32), ("n_obs_dropped", C.c_int32),
+                ("iterations", C.c_int32), ("world_id", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 class AslDebugQuad(C.Structure):
     _fields_ = [("p", (C.c_double * 2) * 4), ("cluster", C.c_uint64), ("frame", C.c_int32), ("reversed_border", C.c_int32)]
 
@@ -55,6 +61,9 @@ CAM_POSE_DTYPE = np.dtype([("T", "<f8", (4, 4)), ("rms_px", "<f8"), ("rms_seed_p
 CALIB_RESULT_DTYPE = np.dtype([("K", "<f8", (3, 3)), ("dist", "<f8", (5,)), ("std", "<f8", (9,)), ("rms_px", "<f8"),
                                ("rms_init_px", "<f8"), ("n_frames_used", "<i4"), ("n_corners", "<i4"), ("iterations", "<i4"),
                                ("status", "<i4")])  # asl_calib_result
+MAP_RESULT_DTYPE = np.dtype([("cost_seed", "<f8"), ("cost", "<f8"), ("rms_px", "<f8"), ("rms_seed_px", "<f8"),
+                             ("n_frames_used", "<i4"), ("n_tags", "<i4"), ("n_obs", "<i4"), ("n_obs_dropped", "<i4"),
+                             ("iterations", "<i4"), ("world_id", "<i4"), ("status", "<i4"), ("reserved", "<i4")])  # asl_map_result
 QUAD_DTYPE = np.dtype([("p", "<f8", (4, 2)), ("cluster", "<u8"), ("frame", "<i4"), ("reversed_border", "<i4")])
 assert DET_DTYPE.itemsize == C.sizeof(AslDetection)
 assert POSE_DTYPE.itemsize == C.sizeof(AslPose)
@@ -62,11 +71,13 @@ assert QUAD_DTYPE.itemsize == C.sizeof(AslDebugQuad)
 assert MAP_TAG_DTYPE.itemsize == C.sizeof(AslMapTag) == 104
 assert CAM_POSE_DTYPE.itemsize == C.sizeof(AslCamPose) == 160
 assert CALIB_RESULT_DTYPE.itemsize == C.sizeof(AslCalibResult) == 216
+assert MAP_RESULT_DTYPE.itemsize == C.sizeof(AslMapResult) == 64
 
 EXPORTS = [
     "asl_detector_create", "asl_detector_destroy", "asl_detector_set_id_limit", "asl_detector_set_pnp_both_minima", "asl_last_error", "asl_version", "asl_detect_gray_u8",
     "asl_detect_bgr_u8", "asl_detect_batch_u8", "asl_detect_batch_pose_u8", "asl_detect_batch_device", "asl_submit_batch_device", "asl_collect_batch", "asl_collect_batch_view", "asl_solve_pnp_batch", "asl_gn_solve", "asl_pack_observations_device", "asl_graph_frames_device", "asl_graph_picks_device", "asl_render_frames_device",
     "asl_localize_frames_device", "asl_localize_batch", "asl_calibrate_frames_device", "asl_calibrate_batch",
+    "asl_map_frames_device", "asl_map_batch",
     "asl_debug_fetch", "asl_stage_times", "asl_set_profiling", "asl_debug_phase_cycles",
 ]
 
@@ -118,6 +129,8 @@ def load():
     L.asl_localize_batch.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, C.c_double, vp]
     L.asl_calibrate_frames_device.argtypes = [vp, vp, i32, i32, vp, i32, C.c_double, i32, i32, dp, i32, i32, i32, vp, vp, vp]
     L.asl_calibrate_batch.argtypes = [vp, vp, i32, i32, vp, i32, C.c_double, i32, i32, dp, i32, i32, i32, vp, vp]
+    L.asl_map_frames_device.argtypes = [vp, vp, i32, i32, i32, dp, dp, i32, C.c_double, i32, i32, vp, vp, vp, vp, vp]
+    L.asl_map_batch.argtypes = [vp, vp, i32, i32, i32, dp, dp, i32, C.c_double, i32, i32, vp, vp, vp, vp]
     L.asl_debug_fetch.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.asl_stage_times.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32, C.POINTER(i32)]
     L.asl_set_profiling.argtypes = [vp, i32]
@@ -380,6 +393,35 @@ class Detector:
                                                   int(n_ids), float(tag_size), int(width), int(height), Kp, int(n_dist), int(flags),
                                                   int(max_iters), C.c_void_p(int(result_ptr)), C.c_void_p(int(poses_ptr)),
                                                   C.c_void_p(int(stream))))
+
+    def build_map(self, obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_std=True):
+        """asl_map_batch: host records obs (n_frames, max_tags) OBS_DTYPE that see an unknown set of tags -> (MAP_RESULT_DTYPE
+        record, (n_ids,) MAP_TAG_DTYPE world<-tag map, (n_ids, 6) tag std or None, (n_frames,) CAM_POSE_DTYPE world<-camera)."""
+        o = np.ascontiguousarray(obs, dtype=OBS_DTYPE)
+        if o.ndim == 1:
+            o = o[None]
+        if o.ndim != 2:
+            raise ValueError("obs must be (n_frames, max_tags) asl_obs records")
+        keep, Kp, dpp, nd = self._camera_args(K, dist)
+        res = np.zeros((), dtype=MAP_RESULT_DTYPE)
+        tmap = np.zeros(max(int(n_ids), 1), dtype=MAP_TAG_DTYPE)
+        std = np.zeros((max(int(n_ids), 1), 6), dtype=np.float64) if with_std else None
+        poses = np.zeros(o.shape[0], dtype=CAM_POSE_DTYPE)
+        check(self._L.asl_map_batch(self._h, o.ctypes.data if o.size else None, o.shape[0], o.shape[1], int(n_ids), Kp, dpp, nd,
+                                    float(tag_size), int(world_id), int(max_iters), tmap.ctypes.data,
+                                    std.ctypes.data if with_std else None, poses.ctypes.data if poses.size else None, res.ctypes.data))
+        return res, tmap, std, poses
+
+    def build_map_device(self, obs_ptr, n_frames, max_tags, n_ids, K, dist, tag_size, map_ptr, std_ptr, poses_ptr, result_ptr,
+                         world_id=-1, max_iters=30, stream=0):
+        """asl_map_frames_device: obs_ptr (n_frames x max_tags asl_obs, e.g. from pack_observations_device), map_ptr (n_ids
+        asl_map_tag, out), std_ptr (n_ids x 6 doubles or 0), poses_ptr (n_frames asl_cam_pose) and result_ptr (one
+        asl_map_result) are device addresses; enqueued on `stream` after one wait for the problem size."""
+        keep, Kp, dpp, nd = self._camera_args(K, dist)
+        check(self._L.asl_map_frames_device(self._h, C.c_void_p(int(obs_ptr)), int(n_frames), int(max_tags), int(n_ids), Kp, dpp, nd,
+                                            float(tag_size), int(world_id), int(max_iters), C.c_void_p(int(map_ptr)),
+                                            C.c_void_p(int(std_ptr)) if std_ptr else None, C.c_void_p(int(poses_ptr)),
+                                            C.c_void_p(int(result_ptr)), C.c_void_p(int(stream))))
 
     def collect_view(self):
         """Wait for the submitted batch; (dets, poses or None, n_per_frame) as numpy VIEWS of the detector's page-locked result

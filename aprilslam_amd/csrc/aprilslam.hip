@@ -29,6 +29,7 @@
 #include "k_gn.inc"
 #include "k_localize.inc"
 #include "k_calib.inc"
+#include "k_map.inc"
 
 static thread_local std::string g_err;
 
@@ -117,6 +118,7 @@ struct asl_detector {
     GnWorkspace gn;
     DevBuf<uint8_t> loc_obs, loc_map, loc_out;  // asl_localize_batch: the host records' device copies (grow on demand)
     DevBuf<uint8_t> cal_ws, cal_out;  // calibration: per-frame workspace and state (k_calib.inc); asl_calibrate_batch's results
+    DevBuf<uint8_t> map_ws, map_lm, map_out;  // map reconstruction (k_map.inc): sized by the input / by the problem; asl_map_batch's results
     hipStream_t copy_stream = nullptr, host_stream = nullptr;  // host frames: transfers and the chunks' kernels (detect_host_frames)
     std::vector<hipEvent_t> copy_done;
     hipStream_t aux_stream = nullptr;  // highest priority, for the small latency-bound jobs next to a running batch (pose-graph LM)
@@ -271,6 +273,7 @@ extern "C" void asl_detector_destroy(asl_detector *d)
     d->gn.release();
     d->loc_obs.release(); d->loc_map.release(); d->loc_out.release();
     d->cal_ws.release(); d->cal_out.release();
+    d->map_ws.release(); d->map_lm.release(); d->map_out.release();
     if (d->aux_stream) (void)hipStreamDestroy(d->aux_stream);
     if (d->copy_stream) (void)hipStreamDestroy(d->copy_stream);
     if (d->host_stream) (void)hipStreamDestroy(d->host_stream);
@@ -1328,6 +1331,200 @@ extern "C" int asl_debug_phase_cycles(asl_detector *d, unsigned long long *out64
         std::fill(all.begin(), all.end(), 0ull);
         HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_phase_cycles), all.data(), sizeof(unsigned long long) * all.size()));
     }
+    return ASL_OK;
+}
+
+static int check_map_args(const void *obs, int n_frames, int max_tags, int n_ids, const double *K, const double *dist, int n_dist,
+                          double tag_size, int world_id, int max_iters, const void *map, const void *poses, const void *result)
+{
+    if (!obs || !K || !map || !poses || !result) return fail(ASL_EINVAL, "NULL argument");
+    if (n_frames < 1) return fail(ASL_EINVAL, "n_frames must be >= 1 (got %d)", n_frames);
+    if (max_tags < 1 || max_tags > 256) return fail(ASL_EINVAL, "max_tags must be in [1, 256] (got %d)", max_tags);
+    if (n_ids < 1) return fail(ASL_EINVAL, "n_ids must be >= 1 (got %d)", n_ids);
+    if (n_dist != 0 && n_dist != 4 && n_dist != 5) return fail(ASL_EINVAL, "n_dist must be 0, 4 or 5");
+    if (n_dist && !dist) return fail(ASL_EINVAL, "dist is NULL with n_dist = %d", n_dist);
+    if (!(tag_size > 0) || !std::isfinite(tag_size)) return fail(ASL_EINVAL, "tag_size must be positive (got %g)", tag_size);
+    if (world_id < -1 || world_id >= n_ids) return fail(ASL_EINVAL, "world_id must be -1 or in [0, n_ids) (got %d)", world_id);
+    if (max_iters < 1 || max_iters > MAP_MAX_ITERS) return fail(ASL_EINVAL, "max_iters must be in [1, %d] (got %d)", MAP_MAX_ITERS, max_iters);
+    return ASL_OK;
+}
+
+static int launch_map(asl_detector *d, const void *d_obs, int n_frames, int max_tags, int n_ids, const double *K, const double *dist, int n_dist,
+                      double tag_size, int world_id, int max_iters, void *d_map, void *d_std, void *d_poses, void *d_result, hipStream_t st)
+{
+    static_assert(sizeof(MapResultRec) == sizeof(asl_map_result) && sizeof(asl_map_result) == 64, "asl_map_result layout");
+    const size_t nf = (size_t)n_frames, ni = (size_t)n_ids, nsl = nf * (size_t)max_tags;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_head = take(sizeof(MapHead)), o_id = take(4 * 4 * (ni + 1)), o_fr = take(4 * 3 * (nf + 1)), o_cam = take(4 * 4 * (nf + 1)),
+                 o_tag = take(4 * (ni + 1)), o_slot = take(4 * nsl), o_obs = take(4 * 4 * nsl), o_csr = take(4 * (2 * nsl + nf + ni + 2)),
+                 o_W = take(8 * 12 * nf), o_G = take(8 * 12 * ni);
+    if (d->map_ws.ensure(off)) return fail(ASL_ENOMEM, "map workspace allocation failed");
+    uint8_t *w = d->map_ws.p;
+    MapArgs a{};
+    a.obs = (const ObsRec *)d_obs; a.n_frames = n_frames; a.max_tags = max_tags; a.n_ids = n_ids; a.world_req = world_id;
+    a.head = (MapHead *)(w + o_head);
+    int *ip = (int *)(w + o_id);
+    a.seen = ip; a.id_tag = ip + (ni + 1); a.tag_id = ip + 2 * (ni + 1); a.tmp = ip + 3 * (ni + 1);
+    ip = (int *)(w + o_fr);
+    a.fr_npart = ip; a.fr_cam = ip + (nf + 1); a.fr_obs0 = ip + 2 * (nf + 1);
+    ip = (int *)(w + o_cam);
+    a.cam_frame = ip; a.cam_ptr0 = ip + (nf + 1); a.cam_state = ip + 2 * (nf + 1); a.cam_seed = ip + 3 * (nf + 1);
+    a.tag_state = (int *)(w + o_tag);
+    a.slot_obs = (int *)(w + o_slot);
+    ip = (int *)(w + o_obs);
+    a.obs_slot = ip; a.obs_cam = ip + nsl; a.obs_tag = ip + 2 * nsl; a.obs_act = ip + 3 * nsl;
+    ip = (int *)(w + o_csr);
+    a.cam_obs = ip; a.tag_obs = ip + nsl; a.cam_ptr = ip + 2 * nsl; a.tag_ptr = ip + 2 * nsl + nf + 1;
+    a.W = (double *)(w + o_W); a.G = (double *)(w + o_G);
+    const CamDev cam = make_cam(d, K, dist, n_dist, tag_size);
+
+    hipLaunchKernelGGL(k_map_gather, dim3(1), dim3(MAP_WG), 0, st, a);
+    MapHead h;
+    HIPCHK(hipMemcpyAsync(&h, a.head, sizeof h, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));  // the one wait before the end: the reduced system is sized by the tags seen
+    const int NC = h.n_cams, NT = h.n_tags, NM = h.n_obs, WT = h.world_tag;
+    auto finish_nothing = [&]() {
+        hipLaunchKernelGGL(k_map_finish, dim3(1), dim3(MAP_WG), 0, st, a, NC, NT, NM, WT, 1, (const double *)nullptr, (const double *)nullptr,
+                           (const double *)nullptr, (const double *)nullptr, (const int *)nullptr, (MapTagRec *)d_map, (double *)d_std, (CamPoseRec *)d_poses,
+                           (MapResultRec *)d_result);
+        HIPCHK(hipGetLastError());
+        return ASL_OK;
+    };
+    if (NT > MAP_MAX_TAGS) return fail(ASL_EINVAL, "the frames see %d tags; the map's dense reduced system takes at most %d", NT, MAP_MAX_TAGS);
+    if (WT < 0) {
+        int rc = finish_nothing();
+        if (rc) return rc;
+        if (world_id >= 0) return fail(ASL_EINVAL, "world tag %d is not seen by any frame with 2 or more taking-part slots", world_id);
+        return ASL_OK;
+    }
+
+    // the problem-sized part: (camera, tag) table, LM buffers (k_gn.inc's layout)
+    const int n = 6 * NT;
+    const size_t nc = (size_t)NC, nt = (size_t)NT, nm = (size_t)NM;
+    off = 0;
+    const size_t p_of = take(4 * nc * nt), p_flag = take(8), p_lm = take(8 * 2 * MAP_LM__N), p_Wn = take(8 * 12 * nc), p_Gn = take(8 * 12 * nt),
+                 p_D = take(8 * GN_DSTRIDE * nm), p_Dn = take(8 * GN_DSTRIDE * nm), p_co = take(8 * nm), p_so = take(8 * nm),
+                 p_Hi = take(8 * 36 * nc), p_gc = take(8 * 6 * nc), p_T = take(8 * 36 * nm), p_S = take(8 * (size_t)(n + 1) * n), p_rhs = take(8 * n),
+                 p_Li = take(8 * (size_t)((n + GN_NB - 1) / GN_NB) * GN_NB * GN_NB), p_var = take(8 * n),
+                 p_lcp = take(4 * (nc + 1)), p_ltp = take(4 * (nt + 1));
+    if (d->map_lm.ensure(off)) return fail(ASL_ENOMEM, "map workspace allocation failed");
+    uint8_t *v = d->map_lm.p;
+    a.obs_of = (int *)(v + p_of);
+    int *flag = (int *)(v + p_flag);
+    double *lm = (double *)(v + p_lm), *lm0 = lm + MAP_LM__N;
+    double *Wc = a.W, *Gc = a.G, *Wt = (double *)(v + p_Wn), *Gt = (double *)(v + p_Gn), *Dc = (double *)(v + p_D), *Dt = (double *)(v + p_Dn);
+    double *cost_obs = (double *)(v + p_co), *seed_obs = (double *)(v + p_so), *Hinv = (double *)(v + p_Hi), *gc = (double *)(v + p_gc);
+    double *Tfj = (double *)(v + p_T), *S = (double *)(v + p_S), *rhs = (double *)(v + p_rhs), *Linv = (double *)(v + p_Li), *var = (double *)(v + p_var);
+    int *lcp = (int *)(v + p_lcp), *ltp = (int *)(v + p_ltp);  // the LM's copies of the list offsets (k_map_park)
+    const dim3 wg(MAP_WG);
+
+    range_push("map: seed");
+    HIPCHK(hipMemsetAsync(a.obs_of, 0xff, 4 * nc * nt, st));
+    hipLaunchKernelGGL(k_map_table, dim3((NM + 255) / 256), dim3(256), 0, st, a, NM, NT);
+    hipLaunchKernelGGL(k_map_csr, dim3(1), wg, 0, st, a, NC, NT);
+    hipLaunchKernelGGL(k_map_chain, dim3(1), wg, 0, st, a, NC, NT, NM, WT);
+    hipLaunchKernelGGL(k_map_csr, dim3(1), wg, 0, st, a, NC, NT);
+    for (int sw = 0; sw < 2; sw++) {
+        hipLaunchKernelGGL(k_map_sweep_cam, dim3(NC), dim3(ASL_WAVE), loc_lds_bytes(max_tags), st, a, cam);
+        hipLaunchKernelGGL(k_map_sweep_tag, dim3(NT), dim3(ASL_WAVE), 0, st, a, cam);
+    }
+    hipLaunchKernelGGL(k_map_gauge, dim3(1), wg, 0, st, a, NC, NT, WT);
+    hipLaunchKernelGGL(k_map_flip, dim3(NT), dim3(ASL_WAVE), 0, st, a, cam, WT);
+    hipLaunchKernelGGL(k_map_behind, dim3((NC + 63) / 64), dim3(64), 0, st, a, NC, cam.half);
+    hipLaunchKernelGGL(k_map_csr, dim3(1), wg, 0, st, a, NC, NT);
+    hipLaunchKernelGGL(k_map_lm_init, dim3(1), dim3(1), 0, st, (const MapHead *)a.head, lm, lm0);
+    HIPCHK(hipMemsetAsync(flag, 0, 8, st));
+    range_pop();
+
+    range_push("map: LM");
+    const unsigned int lin_blocks = (unsigned int)((NM + 3) / 4);
+    hipLaunchKernelGGL(k_map_linearize, dim3(lin_blocks), dim3(256), 0, st, a, Wc, Gc, NM, cam, Dc, cost_obs, lm, 1);
+    hipLaunchKernelGGL(k_gn_cost, dim3(1), dim3(256), 0, st, cost_obs, NM, lm + GN_LM_COST);
+    HIPCHK(hipMemcpyAsync(lm + GN_LM_COST0, lm + GN_LM_COST, 8, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(seed_obs, cost_obs, 8 * nm, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(lcp, a.cam_ptr, 4 * (nc + 1), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(ltp, a.tag_ptr, 4 * (nt + 1), hipMemcpyDeviceToDevice, st));
+    // reduced system, factorisation, solve (k_gn.inc, unchanged); lmp: the lambda the damping reads
+    auto factor = [&](const double *lmp, int *fl, const int *cptr, const int *tptr) {
+        hipLaunchKernelGGL(k_gn_reduce_cam, dim3(NC), dim3(64), 0, st, Dc, cptr, a.cam_obs, NC, lmp, Hinv, gc, Tfj);
+        hipLaunchKernelGGL(k_gn_schur, dim3(NT, NT), dim3(64), 0, st, Dc, Tfj, Hinv, gc, tptr, a.tag_obs, a.obs_cam, a.obs_of, NC, NT, WT, lmp,
+                           S, rhs);
+        HIPCHK(hipMemcpyAsync(S + (size_t)n * n, rhs, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+        for (int k0 = 0; k0 < n; k0 += GN_NB) {
+            const int nb = std::min(GN_NB, n - k0), rem = n + 1 - k0 - nb;
+            hipLaunchKernelGGL(k_gn_chol_diag, dim3(1), dim3(64), 0, st, S, n, k0, nb, fl, Linv);
+            hipLaunchKernelGGL(k_gn_chol_panel, dim3((rem + 15) / 16), dim3(256), 0, st, S, n, n + 1, k0, nb);
+            if (rem > 1) {
+                const unsigned int tiles = (unsigned int)((rem + GN_NB - 1) / GN_NB);
+                hipLaunchKernelGGL(k_gn_chol_update, dim3(tiles, tiles), dim3(256), 0, st, S, n, n + 1, k0, nb);
+            }
+        }
+        return ASL_OK;
+    };
+    const size_t nw = 12 * nc, ng = 12 * nt, nd = (size_t)GN_DSTRIDE * nm;
+    for (int it = 0; it < max_iters; it++) {
+        int rc = factor(lm, flag, lcp, ltp);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_gn_trisolve, dim3(1), dim3(GN_TRI_THREADS), (size_t)n * sizeof(double), st, S, Linv, rhs, n);
+        hipLaunchKernelGGL(k_gn_update, dim3((NC + NT + 63) / 64), dim3(64), 0, st, Dc, Hinv, gc, lcp, a.cam_obs, a.obs_tag, rhs, NC, NT,
+                           Wc, Gc, Wt, Gt);
+        hipLaunchKernelGGL(k_map_linearize, dim3(lin_blocks), dim3(256), 0, st, a, Wt, Gt, NM, cam, Dt, cost_obs, lm, 0);
+        hipLaunchKernelGGL(k_gn_cost, dim3(1), dim3(256), 0, st, cost_obs, NM, lm + GN_LM_TRIAL);
+        hipLaunchKernelGGL(k_map_decide, dim3(1), dim3(1), 0, st, lm, flag);
+        hipLaunchKernelGGL(k_gn_commit, dim3((unsigned int)std::min<size_t>((nw + ng + nd + 255) / 256, 1024)), dim3(256), 0, st, lm, Wt, Gt, Dt,
+                           Wc, Gc, Dc, nw, ng, nd);
+        hipLaunchKernelGGL(k_map_park, dim3((NC + NT + 2 + 255) / 256), dim3(256), 0, st, lm, lcp, NC, ltp, NT);
+    }
+    // the final state's per-observation costs (and its blocks again, for the std)
+    hipLaunchKernelGGL(k_map_linearize, dim3(lin_blocks), dim3(256), 0, st, a, Wc, Gc, NM, cam, Dc, cost_obs, lm, 1);
+    range_pop();
+    if (d_std) {
+        int rc = factor(lm0, flag + 1, a.cam_ptr, a.tag_ptr);  // undamped
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_map_std, dim3(n), dim3(256), (size_t)n * sizeof(double), st, S, Linv, n, var);
+    }
+    hipLaunchKernelGGL(k_map_finish, dim3(1), wg, 0, st, a, NC, NT, NM, WT, 0, lm, cost_obs, seed_obs, d_std ? var : nullptr, flag + 1,
+                       (MapTagRec *)d_map,
+                       (double *)d_std, (CamPoseRec *)d_poses, (MapResultRec *)d_result);
+    HIPCHK(hipGetLastError());
+    return ASL_OK;
+}
+
+extern "C" int asl_map_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, int n_ids, const double *K, const double *dist,
+                                     int n_dist, double tag_size, int world_id, int max_iters, void *d_map, void *d_tag_std, void *d_poses,
+                                     void *d_result, void *stream)
+{
+    if (!d) return fail(ASL_EINVAL, "NULL detector");
+    int rc = check_map_args(d_obs, n_frames, max_tags, n_ids, K, dist, n_dist, tag_size, world_id, max_iters, d_map, d_poses, d_result);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(d->device));
+    return launch_map(d, d_obs, n_frames, max_tags, n_ids, K, dist, n_dist, tag_size, world_id, max_iters, d_map, d_tag_std, d_poses, d_result,
+                      (hipStream_t)stream);
+}
+
+extern "C" int asl_map_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, int n_ids, const double *K, const double *dist,
+                             int n_dist, double tag_size, int world_id, int max_iters, asl_map_tag *map, double *tag_std, asl_cam_pose *poses,
+                             asl_map_result *result)
+{
+    if (!d) return fail(ASL_EINVAL, "NULL detector");
+    int rc = check_map_args(obs, n_frames, max_tags, n_ids, K, dist, n_dist, tag_size, world_id, max_iters, map, poses, result);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(d->device));
+    const size_t obs_bytes = sizeof(asl_obs) * (size_t)n_frames * (size_t)max_tags, res_bytes = 256,
+                 map_bytes = ((sizeof(asl_map_tag) * (size_t)n_ids + 255) & ~(size_t)255), std_bytes = ((48 * (size_t)n_ids + 255) & ~(size_t)255),
+                 out_bytes = sizeof(asl_cam_pose) * (size_t)n_frames;
+    if (d->loc_obs.ensure(obs_bytes) || d->map_out.ensure(res_bytes + map_bytes + std_bytes + out_bytes))
+        return fail(ASL_ENOMEM, "map workspace allocation failed");
+    uint8_t *o = d->map_out.p;
+    HIPCHK(hipMemcpy(d->loc_obs.p, obs, obs_bytes, hipMemcpyHostToDevice));
+    rc = launch_map(d, d->loc_obs.p, n_frames, max_tags, n_ids, K, dist, n_dist, tag_size, world_id, max_iters, o + res_bytes,
+                    tag_std ? o + res_bytes + map_bytes : nullptr, o + res_bytes + map_bytes + std_bytes, o, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(result, o, sizeof(asl_map_result), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(map, o + res_bytes, sizeof(asl_map_tag) * (size_t)n_ids, hipMemcpyDeviceToHost));
+    if (tag_std) HIPCHK(hipMemcpy(tag_std, o + res_bytes + map_bytes, 48 * (size_t)n_ids, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(poses, o + res_bytes + map_bytes + std_bytes, out_bytes, hipMemcpyDeviceToHost));
     return ASL_OK;
 }
 

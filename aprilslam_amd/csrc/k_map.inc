@@ -1,0 +1,837 @@
+// Tag-map reconstruction from a batch of frames (asl_map_frames_device / asl_map_batch): world<-tag poses of every tag
+// the frames see, each frame's camera pose and a per-tag std, from the asl_obs block alone.  float64 throughout;
+// tests/map_ref.py is the NumPy statement of the same computation.
+//   k_map_gather    one workgroup: taking-part slots, used frames (>= 2 slots) -> cameras, ids seen -> tags (ascending),
+//                   observations in (frame, slot) order, the world tag; the host reads the sizes (its one wait)
+//   k_map_table     the (camera, tag) -> observation table k_gn_schur reads
+//   k_map_csr       one workgroup: the per-camera and per-tag lists of the active observations (in observation order,
+//                   tag lists in camera order), inactive entries of the table cleared; run after each stage that drops
+//   k_map_chain     one workgroup: breadth-first rounds from the world tag (cameras, then tags, each half reading the state
+//                   the previous one left) -- map_init.chain_initial_map without its dependence on frame order
+//   k_map_sweep_cam per camera (one wavefront): reseed_poses' camera half -- k_localize.inc's gather, candidates
+//                   (loc_candidate) and scoring (loc_pass) against the current map, the current pose as candidate 0
+//   k_map_sweep_tag per tag (one wavefront): the dual, the cameras held; candidate poses inv(W) T_obs and its mirror
+//   k_map_gauge     one workgroup: the world tag back at the identity
+//   k_map_flip      per tag: the pose and its mirror (built in the view of largest area) each polished by pose-only LM
+//   k_map_behind    per camera: observations with a corner at z <= 1e-6 leave; a camera left with < 2 is dropped
+//   then k_gn.inc's Levenberg-Marquardt step, unchanged (k_gn_reduce_cam, k_gn_schur, the blocked Cholesky,
+//   k_gn_trisolve, k_gn_update, k_gn_cost, k_gn_commit) around k_map_linearize (the lens-aware counterpart of
+//   k_gn_linearize: same 12 x 13 block per observation, same MFMA contraction) and k_map_decide (the accept / stop rule); after the stop k_map_park empties the
+//                   LM's copy of the list offsets, so that the remaining trials reduce and factor an identity system;
+//   k_map_std       per tag parameter: diag of S^-1 = |L^-1 e_i|^2 by blocked forward substitution with the factor
+//   k_map_finish    one workgroup: the records.
+// No atomics: every sum has a fixed order (wave butterflies, per-thread loops in list order, k_gn_cost's fixed tree), so the
+// same input gives the same bytes; frames without taking-part slots change no list, no index and no sum.
+
+struct MapResultRec {  // == asl_map_result, 64 bytes
+    double cost_seed, cost, rms_px, rms_seed_px;
+    int32_t n_frames_used, n_tags, n_obs, n_obs_dropped, iterations, world_id, status, reserved;
+};
+
+struct MapHead {  // the sizes the host reads once
+    int n_cams, n_tags, n_obs, world_tag, world_id, n_act, pad0, pad1;
+};
+
+#define MAP_WG 1024
+#define MAP_MAX_CAND 8
+#define MAP_BEHIND_MARGIN 1e-6
+#define MAP_MAX_TAGS 1000
+#define MAP_MAX_ITERS 1000  // every trial is enqueued up front (the host does not wait for the stop)
+// LM state beyond k_gn.inc's GN_LM__N entries (the k_gn kernels read only those)
+enum { MAP_LM_STOP = GN_LM__N, MAP_LM_ITERS, MAP_LM_STATUS, MAP_LM__N = 16 };
+
+struct MapArgs {
+    const ObsRec *obs;
+    int n_frames, max_tags, n_ids, world_req;
+    MapHead *head;
+    int *seen, *id_tag, *tag_id, *tmp;                      // per id (n_ids + 1)
+    int *fr_npart, *fr_cam, *fr_obs0;                       // per frame (+1)
+    int *cam_frame, *cam_ptr0, *cam_state, *cam_seed;       // per camera (<= n_frames, +1)
+    int *tag_state;                                         // per tag (<= n_ids)
+    int *slot_obs;                                          // per slot
+    int *obs_slot, *obs_cam, *obs_tag, *obs_act;            // per observation (<= n_frames * max_tags)
+    int *cam_ptr, *cam_obs, *tag_ptr, *tag_obs, *obs_of;    // active lists, (camera, tag) table
+    double *W, *G;                                          // camera<-world, world<-tag: R row-major (9), t (3)
+};
+
+// ---- small helpers on 12-double poses
+__device__ __forceinline__ void pk_mul(const double *A, const double *B, double *C)
+{
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) C[3 * r + c] = A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c] + A[3 * r + 2] * B[6 + c];
+        C[9 + r] = A[3 * r] * B[9] + A[3 * r + 1] * B[10] + A[3 * r + 2] * B[11] + A[9 + r];
+    }
+}
+
+__device__ __forceinline__ void pk_inv(const double *A, double *B)
+{
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) B[3 * r + c] = A[3 * c + r];
+#pragma unroll
+    for (int r = 0; r < 3; r++) B[9 + r] = -(B[3 * r] * A[9] + B[3 * r + 1] * A[10] + B[3 * r + 2] * A[11]);
+}
+
+__device__ __forceinline__ void pk_eye(double *A)
+{
+#pragma unroll
+    for (int i = 0; i < 12; i++) A[i] = (i == 0 || i == 4 || i == 8) ? 1.0 : 0.0;
+}
+
+// 12-double pose -> rows 0..2 of a 4x4 (asl_obs.T, asl_map_tag.T)
+__device__ __forceinline__ void pk_to34(const double *A, double *T)
+{
+#pragma unroll
+    for (int r = 0; r < 3; r++) { T[4 * r] = A[3 * r]; T[4 * r + 1] = A[3 * r + 1]; T[4 * r + 2] = A[3 * r + 2]; T[4 * r + 3] = A[9 + r]; }
+}
+
+// camera<-tag of a slot's PnP pose, or its mirrored planar minimum (loc_candidate against the identity)
+__device__ __forceinline__ void map_obs_pose(const ObsRec &o, bool mirror, double *A)
+{
+    double To[12], I34[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, R[9], t[3];
+#pragma unroll
+    for (int k = 0; k < 12; k++) To[k] = o.T[k];
+    loc_candidate(To, I34, mirror, R, t);
+#pragma unroll
+    for (int k = 0; k < 9; k++) A[k] = R[k];
+    A[9] = t[0]; A[10] = t[1]; A[11] = t[2];
+}
+
+__device__ __forceinline__ double map_area(const ObsRec &o)
+{
+    const double x0 = o.corners[0], y0 = o.corners[1], x1 = o.corners[2], y1 = o.corners[3];
+    const double x2 = o.corners[4], y2 = o.corners[5], x3 = o.corners[6], y3 = o.corners[7];
+    const double a = (x0 * y1 - x1 * y0) + (x1 * y2 - x2 * y1) + (x2 * y3 - x3 * y2) + (x3 * y0 - x0 * y3);
+    return 0.5 * fabs(a);
+}
+
+// exclusive prefix sum of cnt(i), i < n, by the MAP_WG threads (contiguous chunks, then the chunks in order) into out[0..n]
+// (if out); returns the total in every thread
+template <class Cnt>
+__device__ __forceinline__ int map_scan(int n, Cnt cnt, int *s_part, int *out)
+{
+    const int tid = threadIdx.x, per = (n + MAP_WG - 1) / MAP_WG;
+    const int i0 = min(n, tid * per), i1 = min(n, i0 + per);
+    int c = 0;
+    for (int i = i0; i < i1; i++) c += cnt(i);
+    s_part[tid] = c;
+    __syncthreads();
+    if (tid == 0) {
+        int run = 0;
+        for (int i = 0; i < MAP_WG; i++) { const int v = s_part[i]; s_part[i] = run; run += v; }
+        s_part[MAP_WG] = run;
+    }
+    __syncthreads();
+    if (out) {
+        int o = s_part[tid];
+        for (int i = i0; i < i1; i++) { out[i] = o; o += cnt(i); }
+        if (tid == 0) out[n] = s_part[MAP_WG];
+    }
+    const int total = s_part[MAP_WG];
+    __syncthreads();
+    return total;
+}
+
+// ---- gather: one workgroup
+__global__ void __launch_bounds__(MAP_WG) k_map_gather(MapArgs a)
+{
+    __shared__ int s_part[MAP_WG + 1];
+    const int tid = threadIdx.x, S = a.max_tags;
+    for (int i = tid; i < a.n_ids; i += MAP_WG) a.seen[i] = 0;
+    for (int f = tid; f < a.n_frames; f += MAP_WG) {
+        const ObsRec *fo = a.obs + (size_t)f * S;
+        int np = 0;
+        for (int s = 0; s < S; s++) {
+            const int id = fo[s].id;
+            bool p = (fo[s].flags & 1) && id >= 0 && id < a.n_ids;
+            for (int s2 = 0; p && s2 < s; s2++)  // a repeated id takes part once, in its first slot
+                if ((fo[s2].flags & 1) && fo[s2].id == id) p = false;
+            a.slot_obs[(size_t)f * S + s] = p ? 1 : -1;
+            np += p;
+        }
+        a.fr_npart[f] = np;
+    }
+    __syncthreads();
+    for (int f = tid; f < a.n_frames; f += MAP_WG) {
+        if (a.fr_npart[f] < 2) continue;
+        for (int s = 0; s < S; s++)
+            if (a.slot_obs[(size_t)f * S + s] == 1) a.seen[a.obs[(size_t)f * S + s].id] = 1;  // every writer stores the same 1
+    }
+    __syncthreads();
+    const int n_cams = map_scan(a.n_frames, [&](int f) { return a.fr_npart[f] >= 2 ? 1 : 0; }, s_part, a.fr_cam);
+    const int n_obs = map_scan(a.n_frames, [&](int f) { return a.fr_npart[f] >= 2 ? a.fr_npart[f] : 0; }, s_part, a.fr_obs0);
+    const int n_tags = map_scan(a.n_ids, [&](int i) { return a.seen[i]; }, s_part, a.id_tag);
+    for (int f = tid; f < a.n_frames; f += MAP_WG) {
+        const bool used = a.fr_npart[f] >= 2;
+        const int c = a.fr_cam[f];
+        int m = a.fr_obs0[f];
+        if (used) { a.cam_frame[c] = f; a.cam_ptr0[c] = m; }
+        for (int s = 0; s < S; s++) {
+            const size_t k = (size_t)f * S + s;
+            if (used && a.slot_obs[k] == 1) {
+                a.obs_slot[m] = (int)k; a.obs_cam[m] = c; a.obs_tag[m] = a.id_tag[a.obs[k].id]; a.obs_act[m] = 1;
+                a.slot_obs[k] = m++;
+            } else
+                a.slot_obs[k] = -1;
+        }
+    }
+    for (int i = tid; i < a.n_ids; i += MAP_WG)
+        if (a.seen[i]) a.tag_id[a.id_tag[i]] = i;
+    __syncthreads();
+    if (tid == 0) {
+        a.cam_ptr0[n_cams] = n_obs;
+        int wt = -1, wid = a.world_req;
+        if (a.world_req < 0) { if (n_tags > 0) { wt = 0; wid = a.tag_id[0]; } }
+        else if (a.world_req < a.n_ids && a.seen[a.world_req]) wt = a.id_tag[a.world_req];
+        MapHead h = {n_cams, n_tags, n_obs, wt, wid, 0, 0, 0};
+        *a.head = h;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_map_table(MapArgs a, int n_obs, int n_tags)
+{
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    if (m < n_obs) a.obs_of[(size_t)a.obs_cam[m] * n_tags + a.obs_tag[m]] = m;
+}
+
+// ---- active lists: one workgroup
+__global__ void __launch_bounds__(MAP_WG) k_map_csr(MapArgs a, int n_cams, int n_tags)
+{
+    __shared__ int s_part[MAP_WG + 1];
+    const int tid = threadIdx.x;
+    auto cam_cnt = [&](int c) {
+        int k = 0;
+        for (int m = a.cam_ptr0[c]; m < a.cam_ptr0[c + 1]; m++) k += a.obs_act[m];
+        return k;
+    };
+    const int n_act = map_scan(n_cams, cam_cnt, s_part, a.cam_ptr);
+    for (int c = tid; c < n_cams; c += MAP_WG) {
+        int o = a.cam_ptr[c];
+        for (int m = a.cam_ptr0[c]; m < a.cam_ptr0[c + 1]; m++)
+            if (a.obs_act[m]) a.cam_obs[o++] = m;
+    }
+    for (int j = tid; j < n_tags; j += MAP_WG) {
+        int k = 0;
+        for (int c = 0; c < n_cams; c++) {
+            int *e = a.obs_of + (size_t)c * n_tags + j;
+            const int m = *e;
+            if (m < 0) continue;
+            if (a.obs_act[m]) k++;
+            else *e = -1;
+        }
+        a.tmp[j] = k;
+    }
+    __syncthreads();
+    map_scan(n_tags, [&](int j) { return a.tmp[j]; }, s_part, a.tag_ptr);
+    for (int j = tid; j < n_tags; j += MAP_WG) {
+        int o = a.tag_ptr[j];
+        for (int c = 0; c < n_cams; c++) {
+            const int m = a.obs_of[(size_t)c * n_tags + j];
+            if (m >= 0) a.tag_obs[o++] = m;
+        }
+    }
+    if (tid == 0) a.head->n_act = n_act;
+}
+
+// ---- breadth-first initial map: one workgroup
+__global__ void __launch_bounds__(MAP_WG) k_map_chain(MapArgs a, int n_cams, int n_tags, int n_obs, int wt)
+{
+    __shared__ int s_changed;
+    const int tid = threadIdx.x, S = a.max_tags;
+    for (int c = tid; c < n_cams; c += MAP_WG) { a.cam_state[c] = 0; a.cam_seed[c] = -1; pk_eye(a.W + 12 * (size_t)c); }
+    for (int j = tid; j < n_tags; j += MAP_WG) { a.tag_state[j] = j == wt; pk_eye(a.G + 12 * (size_t)j); }
+    __syncthreads();
+    for (;;) {
+        if (tid == 0) s_changed = 0;
+        __syncthreads();
+        for (int c = tid; c < n_cams; c += MAP_WG) {
+            if (a.cam_state[c]) continue;
+            double ba = -1.0;
+            int bm = -1, bt = 0x7fffffff;
+            for (int m = a.cam_ptr0[c]; m < a.cam_ptr0[c + 1]; m++) {
+                const ObsRec &o = a.obs[a.obs_slot[m]];
+                const int j = a.obs_tag[m];
+                if (!(o.flags & 2) || !a.tag_state[j]) continue;
+                const double ar = map_area(o);
+                if (ar > ba || (ar == ba && j < bt)) { ba = ar; bm = m; bt = j; }
+            }
+            if (bm < 0) continue;
+            double To[12], Gi[12];
+            map_obs_pose(a.obs[a.obs_slot[bm]], false, To);
+            pk_inv(a.G + 12 * (size_t)bt, Gi);
+            pk_mul(To, Gi, a.W + 12 * (size_t)c);
+            a.cam_state[c] = 1;
+            a.cam_seed[c] = a.obs_slot[bm] % S;
+            s_changed = 1;
+        }
+        __syncthreads();
+        for (int j = tid; j < n_tags; j += MAP_WG) {
+            if (a.tag_state[j]) continue;
+            double ba = -1.0;
+            int bm = -1;
+            for (int o = a.tag_ptr[j]; o < a.tag_ptr[j + 1]; o++) {  // camera order: a tie keeps the lower camera
+                const int m = a.tag_obs[o];
+                const ObsRec &r = a.obs[a.obs_slot[m]];
+                if (!(r.flags & 2) || !a.cam_state[a.obs_cam[m]]) continue;
+                const double ar = map_area(r);
+                if (ar > ba) { ba = ar; bm = m; }
+            }
+            if (bm < 0) continue;
+            double To[12], Wi[12];
+            map_obs_pose(a.obs[a.obs_slot[bm]], false, To);
+            pk_inv(a.W + 12 * (size_t)a.obs_cam[bm], Wi);
+            pk_mul(Wi, To, a.G + 12 * (size_t)j);
+            a.tag_state[j] = 1;
+            s_changed = 1;
+        }
+        __syncthreads();
+        const int ch = s_changed;
+        __syncthreads();
+        if (!ch) break;
+    }
+    for (int m = tid; m < n_obs; m += MAP_WG) a.obs_act[m] = a.cam_state[a.obs_cam[m]] == 1 && a.tag_state[a.obs_tag[m]] == 1;
+}
+
+// ---- reseed, camera half: one wavefront per camera, k_localize.inc's layout and functions
+__global__ void __launch_bounds__(64) k_map_sweep_cam(MapArgs a, CamDev cam)
+{
+    extern __shared__ double s_dyn[];
+    const int c = blockIdx.x, lane = threadIdx.x, S = a.max_tags, n4 = 4 * S;
+    if (a.cam_state[c] != 1) return;
+    double *s_X = s_dyn;
+    double *s_area = s_X + 3 * n4;
+    float *s_uv = (float *)(s_area + S);
+    int *s_state = (int *)(s_uv + 2 * n4);
+    const int f = a.cam_frame[c];
+    const ObsRec *fo = a.obs + (size_t)f * S;
+    int npart = 0;
+    for (int s = lane; s < S; s += ASL_WAVE) {
+        const int m = a.slot_obs[(size_t)f * S + s];
+        const bool part = m >= 0 && a.obs_act[m];
+        s_state[s] = part ? 1 : 0;
+        s_area[s] = -1.0;
+        if (!part) continue;
+        npart++;
+        const double *Gj = a.G + 12 * (size_t)a.obs_tag[m];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const double ox = (q == 1 || q == 2) ? cam.half : -cam.half, oy = (q >= 2) ? cam.half : -cam.half;
+#pragma unroll
+            for (int r = 0; r < 3; r++) s_X[3 * (4 * s + q) + r] = Gj[3 * r] * ox + Gj[3 * r + 1] * oy + Gj[9 + r];
+            s_uv[2 * (4 * s + q)] = fo[s].corners[2 * q];
+            s_uv[2 * (4 * s + q) + 1] = fo[s].corners[2 * q + 1];
+        }
+        if (fo[s].flags & 2) s_area[s] = map_area(fo[s]);
+    }
+    __syncthreads();
+    npart = wave_sum_i32(npart);
+    if (npart == 0) return;
+    double R[9], t[3];
+    const double *Wc = a.W + 12 * (size_t)c;
+#pragma unroll
+    for (int i = 0; i < 9; i++) R[i] = Wc[i];
+    t[0] = Wc[9]; t[1] = Wc[10]; t[2] = Wc[11];
+    double best = loc_pass<false>(cam, R, t, s_X, s_uv, s_state, n4, lane, nullptr);
+    int sel[MAP_MAX_CAND];
+    int nsel = 0;
+#pragma unroll
+    for (int r = 0; r < MAP_MAX_CAND; r++) {
+        double ba = -1.0;
+        int bs = 0x7fffffff;
+        for (int s = lane; s < S; s += ASL_WAVE)
+            if (s_area[s] > ba) { ba = s_area[s]; bs = s; }
+        argmax_step<1>(ba, bs); argmax_step<2>(ba, bs); argmax_step<4>(ba, bs);
+        argmax_step<8>(ba, bs); argmax_step<16>(ba, bs); argmax_step<32>(ba, bs);
+        sel[r] = ba >= 0 ? bs : 0x7fffffff;
+        if (ba >= 0) nsel++;
+        __syncthreads();
+        if (lane == 0 && ba >= 0) s_area[bs] = -1.0;
+        __syncthreads();
+    }
+    int prev = -1;
+    for (int k = 0; k < nsel; k++) {
+        int s = 0x7fffffff;
+#pragma unroll
+        for (int r = 0; r < MAP_MAX_CAND; r++)
+            if (sel[r] > prev && sel[r] < s) s = sel[r];
+        prev = s;
+        double To[12], M[12];
+        pk_to34(a.G + 12 * (size_t)a.obs_tag[a.slot_obs[(size_t)f * S + s]], M);
+#pragma unroll
+        for (int i = 0; i < 12; i++) To[i] = fo[s].T[i];
+        for (int mi = 0; mi < 2; mi++) {
+            double Rc[9], tc[3];
+            loc_candidate(To, M, mi == 1, Rc, tc);
+            const double cc = loc_pass<false>(cam, Rc, tc, s_X, s_uv, s_state, n4, lane, nullptr);
+            if (cc < best) {
+                best = cc;
+#pragma unroll
+                for (int i = 0; i < 9; i++) R[i] = Rc[i];
+                t[0] = tc[0]; t[1] = tc[1]; t[2] = tc[2];
+            }
+        }
+    }
+    if (lane == 0) {
+        double *Wo = a.W + 12 * (size_t)c;
+#pragma unroll
+        for (int i = 0; i < 9; i++) Wo[i] = R[i];
+        Wo[9] = t[0]; Wo[10] = t[1]; Wo[11] = t[2];
+    }
+}
+
+// Total corner cost of world<-tag (R, t) over the tag's observations b..e of the active list, the cameras held; with NE
+// also the normal equations of the left update of the tag (packed lower triangle 21, then J^T r 6), identical in every lane.
+template <bool NE>
+__device__ __forceinline__ double map_tag_pass(const MapArgs &a, const CamDev &c, const double *R, const double *t, int b, int e, int lane,
+                                               double *ne)
+{
+    double cost = 0, acc[27];
+#pragma unroll
+    for (int i = 0; i < 27; i++) acc[i] = 0;
+    for (int k = lane; k < 4 * (e - b); k += ASL_WAVE) {
+        const int m = a.tag_obs[b + (k >> 2)], q = k & 3;
+        const double *Wc = a.W + 12 * (size_t)a.obs_cam[m];
+        const ObsRec &o = a.obs[a.obs_slot[m]];
+        const double ox = (q == 1 || q == 2) ? c.half : -c.half, oy = (q >= 2) ? c.half : -c.half;
+        double X[3], P[3], uv[2], Jp[6];
+#pragma unroll
+        for (int r = 0; r < 3; r++) X[r] = R[3 * r] * ox + R[3 * r + 1] * oy + t[r];
+#pragma unroll
+        for (int r = 0; r < 3; r++) P[r] = Wc[3 * r] * X[0] + Wc[3 * r + 1] * X[1] + Wc[3 * r + 2] * X[2] + Wc[9 + r];
+        if (!(P[2] > LOC_Z_MIN)) { cost += LOC_BEHIND_COST; continue; }
+        project_dev(c, P, uv, NE ? Jp : nullptr);
+        const double r0 = uv[0] - (double)o.corners[2 * q], r1 = uv[1] - (double)o.corners[2 * q + 1];
+        if constexpr (NE) {
+            double a0[3], a1[3], J0[6], J1[6];  // a = jp R_W: d uv / d X_world
+#pragma unroll
+            for (int k2 = 0; k2 < 3; k2++) {
+                a0[k2] = Jp[0] * Wc[k2] + Jp[1] * Wc[3 + k2] + Jp[2] * Wc[6 + k2];
+                a1[k2] = Jp[3] * Wc[k2] + Jp[4] * Wc[3 + k2] + Jp[5] * Wc[6 + k2];
+            }
+            J0[0] = X[1] * a0[2] - X[2] * a0[1]; J0[1] = X[2] * a0[0] - X[0] * a0[2]; J0[2] = X[0] * a0[1] - X[1] * a0[0];
+            J1[0] = X[1] * a1[2] - X[2] * a1[1]; J1[1] = X[2] * a1[0] - X[0] * a1[2]; J1[2] = X[0] * a1[1] - X[1] * a1[0];
+#pragma unroll
+            for (int k2 = 0; k2 < 3; k2++) { J0[3 + k2] = a0[k2]; J1[3 + k2] = a1[k2]; }
+#pragma unroll
+            for (int p = 0; p < 6; p++) {
+                acc[21 + p] += J0[p] * r0 + J1[p] * r1;
+#pragma unroll
+                for (int q2 = 0; q2 <= p; q2++) acc[TRI(p, q2)] += J0[p] * J0[q2] + J1[p] * J1[q2];
+            }
+        }
+        cost += r0 * r0 + r1 * r1;
+    }
+    if constexpr (NE) {
+#pragma unroll
+        for (int i = 0; i < 27; i++) ne[i] = wave_sum_f64(acc[i]);
+    }
+    return wave_sum_f64(cost);
+}
+
+// loc_lm's schedule on a tag's world<-tag (R, t), the cameras held: R <- Rod(w) R, t <- Rod(w) t + v
+__device__ __forceinline__ double map_tag_lm(const MapArgs &a, const CamDev &c, double *R, double *t, int b, int e, int lane)
+{
+    double ne[27];
+    double cost = map_tag_pass<true>(a, c, R, t, b, e, lane, ne);
+    double lambda = 1e-3;
+    for (int it = 0; it < LOC_LM_ITERS; it++) {
+        double A[21], d[6];
+#pragma unroll
+        for (int i = 0; i < 21; i++) A[i] = ne[i];
+#pragma unroll
+        for (int p = 0; p < 6; p++) { A[TRI(p, p)] += lambda * ne[TRI(p, p)]; d[p] = -ne[21 + p]; }
+        if (!chol6_solve_tri_dev(A, d)) { lambda *= 10; continue; }
+        double dR[9], Rn[9], tn[3];
+        rodrigues_dev(d, dR);
+        mat3_mul_dev(dR, R, Rn);
+#pragma unroll
+        for (int r = 0; r < 3; r++) tn[r] = dR[3 * r] * t[0] + dR[3 * r + 1] * t[1] + dR[3 * r + 2] * t[2] + d[3 + r];
+        const double cn = map_tag_pass<false>(a, c, Rn, tn, b, e, lane, nullptr);
+        if (cn < cost) {
+            const bool stop = cost - cn < 1e-12 * cost;
+#pragma unroll
+            for (int i = 0; i < 9; i++) R[i] = Rn[i];
+            t[0] = tn[0]; t[1] = tn[1]; t[2] = tn[2];
+            cost = cn;
+            lambda *= 0.1;
+            if (stop) break;
+            cost = map_tag_pass<true>(a, c, R, t, b, e, lane, ne);
+        } else
+            lambda *= 10;
+    }
+    return cost;
+}
+
+// ---- reseed, tag half: one wavefront per tag, the cameras held
+__global__ void __launch_bounds__(64) k_map_sweep_tag(MapArgs a, CamDev cam)
+{
+    const int j = blockIdx.x, lane = threadIdx.x;
+    if (a.tag_state[j] != 1) return;
+    const int b = a.tag_ptr[j], e = a.tag_ptr[j + 1], n = e - b;
+    if (n == 0) return;
+    double R[9], t[3];
+    const double *Gj = a.G + 12 * (size_t)j;
+#pragma unroll
+    for (int i = 0; i < 9; i++) R[i] = Gj[i];
+    t[0] = Gj[9]; t[1] = Gj[10]; t[2] = Gj[11];
+    double best = map_tag_pass<false>(a, cam, R, t, b, e, lane, nullptr);
+    // the <= 8 seeding observations of largest area (ties: lower list position = lower camera), picked in that order
+    int sel[MAP_MAX_CAND];
+    int nsel = 0;
+    double pa = INFINITY;
+    int pp = -1;
+#pragma unroll
+    for (int r = 0; r < MAP_MAX_CAND; r++) {
+        double ba = -1.0;
+        int bs = 0x7fffffff;
+        for (int o = lane; o < n; o += ASL_WAVE) {
+            const ObsRec &rec = a.obs[a.obs_slot[a.tag_obs[b + o]]];
+            if (!(rec.flags & 2)) continue;
+            const double ar = map_area(rec);
+            if (!(ar < pa || (ar == pa && o > pp))) continue;  // taken already
+            if (ar > ba) { ba = ar; bs = o; }
+        }
+        argmax_step<1>(ba, bs); argmax_step<2>(ba, bs); argmax_step<4>(ba, bs);
+        argmax_step<8>(ba, bs); argmax_step<16>(ba, bs); argmax_step<32>(ba, bs);
+        sel[r] = ba >= 0 ? bs : 0x7fffffff;
+        if (ba >= 0) { nsel++; pa = ba; pp = bs; }
+    }
+    int prev = -1;
+    for (int k = 0; k < nsel; k++) {
+        int o = 0x7fffffff;
+#pragma unroll
+        for (int r = 0; r < MAP_MAX_CAND; r++)
+            if (sel[r] > prev && sel[r] < o) o = sel[r];
+        prev = o;
+        const int m = a.tag_obs[b + o];
+        double Wi[12];
+        pk_inv(a.W + 12 * (size_t)a.obs_cam[m], Wi);
+        for (int mi = 0; mi < 2; mi++) {
+            double To[12], Gc[12];
+            map_obs_pose(a.obs[a.obs_slot[m]], mi == 1, To);
+            pk_mul(Wi, To, Gc);
+            const double cc = map_tag_pass<false>(a, cam, Gc, Gc + 9, b, e, lane, nullptr);
+            if (cc < best) {
+                best = cc;
+#pragma unroll
+                for (int i = 0; i < 9; i++) R[i] = Gc[i];
+                t[0] = Gc[9]; t[1] = Gc[10]; t[2] = Gc[11];
+            }
+        }
+    }
+    if (lane == 0) {
+        double *Go = a.G + 12 * (size_t)j;
+#pragma unroll
+        for (int i = 0; i < 9; i++) Go[i] = R[i];
+        Go[9] = t[0]; Go[10] = t[1]; Go[11] = t[2];
+    }
+}
+
+// ---- the gauge: world tag at the identity (one workgroup)
+__global__ void __launch_bounds__(MAP_WG) k_map_gauge(MapArgs a, int n_cams, int n_tags, int wt)
+{
+    __shared__ double sG[12], sGi[12];
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        for (int i = 0; i < 12; i++) sG[i] = a.G[12 * (size_t)wt + i];
+        pk_inv(sG, sGi);
+    }
+    __syncthreads();
+    for (int c = tid; c < n_cams; c += MAP_WG) {
+        double Wc[12];
+        for (int i = 0; i < 12; i++) Wc[i] = a.W[12 * (size_t)c + i];
+        pk_mul(Wc, sG, a.W + 12 * (size_t)c);
+    }
+    for (int j = tid; j < n_tags; j += MAP_WG) {
+        if (j == wt) { pk_eye(a.G + 12 * (size_t)j); continue; }
+        double Gj[12];
+        for (int i = 0; i < 12; i++) Gj[i] = a.G[12 * (size_t)j + i];
+        pk_mul(sGi, Gj, a.G + 12 * (size_t)j);
+    }
+}
+
+// ---- flip test: one wavefront per tag
+__global__ void __launch_bounds__(64) k_map_flip(MapArgs a, CamDev cam, int wt)
+{
+    const int j = blockIdx.x, lane = threadIdx.x;
+    if (j == wt || a.tag_state[j] != 1) return;
+    const int b = a.tag_ptr[j], e = a.tag_ptr[j + 1], n = e - b;
+    if (n == 0) return;
+    double G0[12], R0[9], t0[3], R1[9], t1[3];
+    for (int i = 0; i < 12; i++) G0[i] = a.G[12 * (size_t)j + i];
+    // the view where the tag is largest (ties: lower camera)
+    double ba = -1.0;
+    int bo = 0x7fffffff;
+    for (int o = lane; o < n; o += ASL_WAVE) {
+        const double ar = map_area(a.obs[a.obs_slot[a.tag_obs[b + o]]]);
+        if (ar > ba) { ba = ar; bo = o; }
+    }
+    argmax_step<1>(ba, bo); argmax_step<2>(ba, bo); argmax_step<4>(ba, bo);
+    argmax_step<8>(ba, bo); argmax_step<16>(ba, bo); argmax_step<32>(ba, bo);
+    const double *Wb = a.W + 12 * (size_t)a.obs_cam[a.tag_obs[b + bo]];
+    double CT[12], CT34[12], I34[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, Mr[12], Wi[12], Gm[12];
+    pk_mul(Wb, G0, CT);
+    pk_to34(CT, CT34);
+    loc_candidate(CT34, I34, true, Mr, Mr + 9);
+    pk_inv(Wb, Wi);
+    pk_mul(Wi, Mr, Gm);
+    for (int i = 0; i < 9; i++) { R0[i] = G0[i]; R1[i] = Gm[i]; }
+    for (int i = 0; i < 3; i++) { t0[i] = G0[9 + i]; t1[i] = Gm[9 + i]; }
+    const double c0 = map_tag_lm(a, cam, R0, t0, b, e, lane);
+    const double c1 = map_tag_lm(a, cam, R1, t1, b, e, lane);
+    if (lane == 0) {
+        const bool flip = c1 < c0;
+        double *Go = a.G + 12 * (size_t)j;
+        for (int i = 0; i < 9; i++) Go[i] = flip ? R1[i] : R0[i];
+        for (int i = 0; i < 3; i++) Go[9 + i] = flip ? t1[i] : t0[i];
+    }
+}
+
+// ---- behind the camera: one thread per camera
+__global__ void __launch_bounds__(64) k_map_behind(MapArgs a, int n_cams, double half)
+{
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= n_cams || a.cam_state[c] != 1) return;
+    const double *Wc = a.W + 12 * (size_t)c;
+    int k = 0;
+    for (int m = a.cam_ptr0[c]; m < a.cam_ptr0[c + 1]; m++) {
+        if (!a.obs_act[m]) continue;
+        const double *Gj = a.G + 12 * (size_t)a.obs_tag[m];
+        bool ok = true;
+        for (int q = 0; q < 4; q++) {
+            const double ox = (q == 1 || q == 2) ? half : -half, oy = (q >= 2) ? half : -half;
+            double X[3];
+            for (int r = 0; r < 3; r++) X[r] = Gj[3 * r] * ox + Gj[3 * r + 1] * oy + Gj[9 + r];
+            const double z = Wc[6] * X[0] + Wc[7] * X[1] + Wc[8] * X[2] + Wc[11];
+            ok = ok && z > MAP_BEHIND_MARGIN;
+        }
+        a.obs_act[m] = ok;
+        k += ok;
+    }
+    if (k < 2) {
+        a.cam_state[c] = 3;
+        for (int m = a.cam_ptr0[c]; m < a.cam_ptr0[c + 1]; m++) a.obs_act[m] = 0;
+    }
+}
+
+__global__ void k_map_lm_init(const MapHead *head, double *lm, double *lm0)
+{
+    for (int i = 0; i < MAP_LM__N; i++) { lm[i] = 0; lm0[i] = 0; }
+    lm[GN_LM_LAMBDA] = 1e-3;
+    if (head->n_act == 0) { lm[MAP_LM_STOP] = 1; lm[MAP_LM_STATUS] = 1; }
+}
+
+// k_gn_linearize with the k_pnp.inc camera model: one wavefront per observation, the same 12 x 13 block [J^T J | J^T r] per
+// observation (GN_DSTRIDE) from two v_mfma_f64_16x16x4_f64; a corner at z <= 1e-9 costs 1e12 and adds no row.  Inactive
+// observations cost 0 and leave their block alone (no list refers to it).  Nothing happens after the stop unless forced.
+__global__ void __launch_bounds__(256) k_map_linearize(MapArgs a, const double *__restrict__ W, const double *__restrict__ G, int n_obs, CamDev cam,
+                                                       double *__restrict__ D, double *__restrict__ cost_obs, const double *__restrict__ lm, int force)
+{
+    const int lane = threadIdx.x & 63;
+    const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= n_obs || (!force && lm[MAP_LM_STOP] != 0.0)) return;
+    if (!a.obs_act[m]) {
+        if (lane == 0) cost_obs[m] = 0.0;
+        return;
+    }
+    const double *Wf = W + 12 * (size_t)a.obs_cam[m], *Gj = G + 12 * (size_t)a.obs_tag[m];
+    const ObsRec &o = a.obs[a.obs_slot[m]];
+    const int n = lane & 15, kk = lane >> 4;
+    gn_v4d acc = {0, 0, 0, 0};
+    double rsq = 0;
+#pragma unroll
+    for (int step = 0; step < 2; step++) {
+        const int k = kk + 4 * step;
+        const int corner = k >> 1, comp = k & 1;
+        const double ox = (corner == 1 || corner == 2) ? cam.half : -cam.half, oy = (corner >= 2) ? cam.half : -cam.half;
+        double q[3], p[3], uv[2], Jp[6];
+#pragma unroll
+        for (int r = 0; r < 3; r++) q[r] = Gj[3 * r] * ox + Gj[3 * r + 1] * oy + Gj[9 + r];
+#pragma unroll
+        for (int r = 0; r < 3; r++) p[r] = Wf[3 * r] * q[0] + Wf[3 * r + 1] * q[1] + Wf[3 * r + 2] * q[2] + Wf[9 + r];
+        double res = 0, jp[3] = {0, 0, 0}, add = 0;
+        if (p[2] > LOC_Z_MIN) {
+            project_dev(cam, p, uv, Jp);
+            res = uv[comp] - (double)o.corners[k];
+#pragma unroll
+            for (int r = 0; r < 3; r++) jp[r] = Jp[3 * comp + r];
+            add = res * res;
+        } else if (comp == 0)
+            add = LOC_BEHIND_COST;
+        double Jrow[12];
+        Jrow[0] = p[1] * jp[2] - p[2] * jp[1];
+        Jrow[1] = p[2] * jp[0] - p[0] * jp[2];
+        Jrow[2] = p[0] * jp[1] - p[1] * jp[0];
+        Jrow[3] = jp[0]; Jrow[4] = jp[1]; Jrow[5] = jp[2];
+        double av[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) av[c] = Wf[c] * jp[0] + Wf[3 + c] * jp[1] + Wf[6 + c] * jp[2];
+        Jrow[6] = q[1] * av[2] - q[2] * av[1];
+        Jrow[7] = q[2] * av[0] - q[0] * av[2];
+        Jrow[8] = q[0] * av[1] - q[1] * av[0];
+        Jrow[9] = av[0]; Jrow[10] = av[1]; Jrow[11] = av[2];
+        double sel = 0;
+#pragma unroll
+        for (int c = 0; c < 12; c++) sel = (n == c) ? Jrow[c] : sel;
+        const double A = n < 12 ? sel : 0.0;
+        const double B = n < 12 ? sel : (n == 12 ? res : 0.0);
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A, B, acc, 0, 0, 0);
+        if (n == 0) rsq += add;
+    }
+    double *Dm = D + (size_t)m * GN_DSTRIDE;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int row = kk + 4 * i;
+        if (row < 12 && n < 13) Dm[row * 13 + n] = acc[i];
+    }
+    double c = rsq;
+    c += __shfl_xor(c, 16);
+    c += __shfl_xor(c, 32);
+    if (lane == 0) cost_obs[m] = c;
+}
+
+// accept / reject the trial, count it, stop on a small accepted decrease or a failed factorisation
+__global__ void k_map_decide(double *lm, int *fail)
+{
+    if (lm[MAP_LM_STOP] != 0.0) { lm[GN_LM_FLAG] = 0.0; return; }
+    lm[MAP_LM_ITERS] += 1.0;
+    if (*fail) { lm[GN_LM_FLAG] = 0.0; lm[MAP_LM_STOP] = 1.0; lm[MAP_LM_STATUS] = 2.0; return; }
+    if (lm[GN_LM_TRIAL] < lm[GN_LM_COST]) {
+        const bool stop = lm[GN_LM_COST] - lm[GN_LM_TRIAL] < 1e-12 * lm[GN_LM_COST];
+        lm[GN_LM_COST] = lm[GN_LM_TRIAL];
+        lm[GN_LM_LAMBDA] = fmax(lm[GN_LM_LAMBDA] * 0.1, 1e-12);
+        lm[GN_LM_ACCEPTED] += 1.0;
+        lm[GN_LM_FLAG] = 1.0;
+        if (stop) lm[MAP_LM_STOP] = 1.0;
+    } else {
+        lm[GN_LM_LAMBDA] *= 10.0;
+        lm[GN_LM_FLAG] = 0.0;
+    }
+}
+
+// after the stop: the list offsets the LM's k_gn kernels read (a copy) become empty, so that every later trial reduces,
+// factors and solves an identity system instead of the real one (its result is discarded anyway)
+__global__ void __launch_bounds__(256) k_map_park(const double *__restrict__ lm, int *__restrict__ cam_ptr, int n_cams, int *__restrict__ tag_ptr,
+                                                  int n_tags)
+{
+    if (lm[MAP_LM_STOP] == 0.0) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i <= n_cams) cam_ptr[i] = 0;
+    else if (i <= n_cams + 1 + n_tags) tag_ptr[i - n_cams - 1] = 0;
+}
+
+// diag(S^-1)_i = |L^-1 e_i|^2: one workgroup per tag parameter i, y in LDS (n doubles), forward substitution by blocks of
+// GN_NB with the diagonal-block inverses k_gn_chol_diag left in Linv; only the blocks from i's on are touched
+__global__ void __launch_bounds__(256) k_map_std(const double *__restrict__ S, const double *__restrict__ Linv, int n, double *__restrict__ var)
+{
+    extern __shared__ double y[];
+    __shared__ double yb[GN_NB], red[256];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    for (int r = tid; r < n; r += 256) y[r] = r == i ? 1.0 : 0.0;
+    __syncthreads();
+    const int nblk = (n + GN_NB - 1) / GN_NB;
+    for (int bi = i / GN_NB; bi < nblk; bi++) {
+        const int k0 = bi * GN_NB, nb = min(GN_NB, n - k0);
+        const double *Lb = Linv + (size_t)bi * GN_NB * GN_NB;
+        if (tid < nb) {
+            double s = 0;
+            for (int c = 0; c < nb; c++) s += Lb[tid * GN_NB + c] * y[k0 + c];
+            yb[tid] = s;
+        }
+        __syncthreads();
+        if (tid < nb) y[k0 + tid] = yb[tid];
+        for (int r = k0 + nb + tid; r < n; r += 256) {
+            double s = 0;
+            for (int c = 0; c < nb; c++) s += S[(size_t)r * n + k0 + c] * yb[c];
+            y[r] -= s;
+        }
+        __syncthreads();
+    }
+    double s = 0;
+    for (int r = tid; r < n; r += 256) s += y[r] * y[r];
+    red[tid] = s;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (tid < st) red[tid] += red[tid + st];
+        __syncthreads();
+    }
+    if (tid == 0) var[i] = red[0];
+}
+
+// ---- the records: one workgroup.  nothing: no world tag (sizes only, no stage after the gather ran)
+__global__ void __launch_bounds__(MAP_WG) k_map_finish(MapArgs a, int n_cams, int n_tags, int n_obs, int wt, int nothing, const double *lm,
+                                                       const double *cost_obs, const double *seed_obs, const double *var, const int *var_fail,
+                                                       MapTagRec *map,
+                                                       double *tag_std, CamPoseRec *poses, MapResultRec *res)
+{
+    __shared__ int s_part[MAP_WG + 1];
+    const int tid = threadIdx.x;
+    const int n_act = nothing ? 0 : map_scan(n_obs, [&](int m) { return a.obs_act[m]; }, s_part, nullptr);
+    const int n_used = nothing ? 0 : map_scan(n_cams, [&](int c) { return a.cam_state[c] == 1 ? 1 : 0; }, s_part, nullptr);
+    auto mapped = [&](int j) { return j == wt || a.tag_ptr[j + 1] > a.tag_ptr[j]; };
+    const int n_mapped = nothing ? 0 : map_scan(n_tags, [&](int j) { return (a.tag_state[j] == 1 && mapped(j)) ? 1 : 0; }, s_part, nullptr);
+    int status = nothing ? 1 : (int)lm[MAP_LM_STATUS];
+    const double cost = nothing ? 0.0 : lm[GN_LM_COST], cost0 = nothing ? 0.0 : lm[GN_LM_COST0];
+    if (status == 0 && !isfinite(cost)) status = 3;
+    const int dof = 8 * n_act - 6 * n_used - 6 * (n_mapped - 1);
+    const double s2 = dof > 0 ? cost / dof : 0.0;
+    const bool std_ok = var && !(var_fail && *var_fail);  // an undamped system that is not positive definite gives no std
+    for (int f = tid; f < a.n_frames; f += MAP_WG) {
+        CamPoseRec *o = poses + f;
+        const int np = a.fr_npart[f];
+        int st = 1, na = 0, seed = -1;
+        double T[12], rms = 0, rms0 = 0;
+        pk_eye(T);
+        if (np >= 2) {
+            const int c = a.fr_cam[f];
+            st = nothing ? 5 : (a.cam_state[c] == 1 ? (status == 0 ? 0 : 4) : a.cam_state[c] == 3 ? 3 : 5);
+            seed = nothing ? -1 : a.cam_seed[c];
+            if (st == 0 || st == 4) {
+                double e = 0, e0 = 0;
+                for (int m = a.cam_ptr0[c]; m < a.cam_ptr0[c + 1]; m++)
+                    if (a.obs_act[m]) { na++; e += cost_obs[m]; e0 += seed_obs[m]; }
+                pk_inv(a.W + 12 * (size_t)c, T);
+                if (na) { rms = sqrt(e / (4.0 * na)); rms0 = sqrt(e0 / (4.0 * na)); }
+            }
+        }
+        for (int r = 0; r < 3; r++) {
+            o->T[4 * r] = T[3 * r]; o->T[4 * r + 1] = T[3 * r + 1]; o->T[4 * r + 2] = T[3 * r + 2]; o->T[4 * r + 3] = T[9 + r];
+        }
+        o->T[12] = 0; o->T[13] = 0; o->T[14] = 0; o->T[15] = 1;
+        o->rms_px = rms; o->rms_seed_px = rms0;
+        o->n_tags = na;
+        o->n_rejected = np >= 2 ? np - na : 0;
+        o->status = st;
+        o->seed_slot = seed;
+    }
+    for (int i = tid; i < a.n_ids; i += MAP_WG) {
+        const int j = (!nothing && a.seen[i]) ? a.id_tag[i] : -1;
+        const bool ok = j >= 0 && status == 0 && a.tag_state[j] == 1 && mapped(j);
+        MapTagRec *r = map + i;
+        double T[12];
+        if (ok) pk_to34(a.G + 12 * (size_t)j, T);
+        for (int k = 0; k < 12; k++) r->T[k] = ok ? T[k] : 0.0;
+        r->valid = ok ? 1 : 0;
+        r->reserved = 0;
+        if (tag_std)
+            for (int k = 0; k < 6; k++) tag_std[6 * (size_t)i + k] = (ok && j != wt && std_ok) ? sqrt(s2 * var[6 * j + k]) : 0.0;
+    }
+    if (tid == 0) {
+        MapResultRec r;
+        r.cost_seed = cost0; r.cost = cost;
+        r.rms_px = n_act ? sqrt(cost / (4.0 * n_act)) : 0.0;
+        r.rms_seed_px = n_act ? sqrt(cost0 / (4.0 * n_act)) : 0.0;
+        r.n_frames_used = status == 0 ? n_used : 0;
+        r.n_tags = status == 0 ? n_mapped : 0;
+        r.n_obs = n_act;
+        r.n_obs_dropped = n_obs - n_act;
+        r.iterations = nothing ? 0 : (int)lm[MAP_LM_ITERS];
+        r.world_id = a.head->world_id;
+        r.status = status;
+        r.reserved = 0;
+        *res = r;
+    }
+}

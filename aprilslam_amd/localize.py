@@ -84,6 +84,27 @@ class TagMap:
                 poses[first_id + r * cols + c] = T
         return cls(poses)
 
+    def save(self, path):
+        """Write the map to an .npz file: ids (n,) and T (n, 4, 4) world<-tag, in ascending id order."""
+        ids = self.ids()
+        T = np.array([self.poses[i] for i in ids], dtype=np.float64).reshape(-1, 4, 4)
+        np.savez(path, ids=np.array(ids, dtype=np.int64), T=T)
+
+    @classmethod
+    def load(cls, path):
+        """The map TagMap.save wrote."""
+        with np.load(path) as z:
+            ids, T = z["ids"], z["T"]
+            if ids.ndim != 1 or T.shape != (len(ids), 4, 4):
+                raise ValueError("%s is not a saved TagMap (ids (n,), T (n, 4, 4))" % path)
+            return cls({int(i): T[k] for k, i in enumerate(ids)})
+
+    @classmethod
+    def from_records(cls, rec):
+        """The valid entries of an (n_ids,) MAP_TAG_DTYPE block (e.g. asl_map_frames_device's output)."""
+        rec = np.asarray(rec, dtype=MAP_TAG_DTYPE).ravel()
+        return cls({int(i): rec["T"][i].reshape(3, 4) for i in np.flatnonzero(rec["valid"])})
+
     def as_records(self):
         """(n_ids,) MAP_TAG_DTYPE, indexed by id; ids without a pose have valid = 0"""
         rec = np.zeros(max(self.n_ids, 1), dtype=MAP_TAG_DTYPE)

@@ -1,0 +1,70 @@
+"""Tag-map reconstruction from a batch of frames (asl_map_batch / asl_map_frames_device).
+
+Frames that see an unknown set of tags give the tags' world<-tag poses (the world tag at the identity), every frame's
+camera pose and a per-tag standard deviation; the map is the asl_map_tag block localisation reads (localize.TagMap).
+
+    MapResult           the records of one solve, with .tag_map, .tag_std, .camera_poses, .frame_status
+    MAP_RESULT_DTYPE    asl_map_result
+"""
+import numpy as np
+
+from ._lib import MAP_RESULT_DTYPE
+from .localize import TagMap
+
+STATUS_OK, STATUS_NOTHING, STATUS_NOT_PD, STATUS_NON_FINITE = 0, 1, 2, 3
+FRAME_USED, FRAME_FEW_SLOTS, FRAME_DROPPED, FRAME_SOLVE_FAILED, FRAME_NOT_CONNECTED = 0, 1, 3, 4, 5
+
+__all__ = ["MapResult", "MAP_RESULT_DTYPE", "STATUS_OK", "STATUS_NOTHING", "STATUS_NOT_PD", "STATUS_NON_FINITE",
+           "FRAME_USED", "FRAME_FEW_SLOTS", "FRAME_DROPPED", "FRAME_SOLVE_FAILED", "FRAME_NOT_CONNECTED"]
+
+
+class MapResult:
+    """One map solve: result (MAP_RESULT_DTYPE record), map (n_ids,) MAP_TAG_DTYPE, std (n_ids, 6) or None, poses
+    (n_frames,) CAM_POSE_DTYPE."""
+
+    def __init__(self, result, map_records, tag_std, poses):
+        self.result = np.asarray(result, dtype=MAP_RESULT_DTYPE).reshape(())
+        self.records = map_records
+        self.std = tag_std
+        self.poses = poses
+
+    @property
+    def status(self):
+        return int(self.result["status"])
+
+    @property
+    def ok(self):
+        return self.status == STATUS_OK
+
+    @property
+    def world_id(self):
+        return int(self.result["world_id"])
+
+    @property
+    def rms_px(self):
+        return float(self.result["rms_px"])
+
+    @property
+    def tag_map(self):
+        """TagMap of the mapped tags (world<-tag, the world tag at the identity)"""
+        return TagMap.from_records(self.records)
+
+    @property
+    def tag_std(self):
+        """{id: (6,) std of (omega, v) of a left update in the world frame}; zeros for the world tag"""
+        if self.std is None:
+            return {}
+        return {int(i): np.array(self.std[i]) for i in np.flatnonzero(self.records["valid"])}
+
+    @property
+    def camera_poses(self):
+        """(n_frames, 4, 4) world<-camera; the identity where frame_status is not 0 or 4"""
+        return np.array(self.poses["T"])
+
+    @property
+    def frame_status(self):
+        return np.array(self.poses["status"])
+
+    def __repr__(self):
+        return "MapResult(status=%d, world_id=%d, tags=%d, frames=%d, rms_px=%.4g)" % (
+            self.status, self.world_id, int(self.result["n_tags"]), int(self.result["n_frames_used"]), self.rms_px)

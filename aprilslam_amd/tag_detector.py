@@ -185,6 +185,30 @@ class TagDetector:
                                                 max_iters=max_iters)
         return CalibrationResult(res, cam, n_dist)
 
+    def build_map(self, frames, world_id=None, max_iters=30, with_std=True):
+        """Host frames ((n, H, W, 3) BGR or (n, H, W) gray uint8, or a list of them) that see an unknown set of tags ->
+        mapping.MapResult: the tags' world<-tag poses (tag_map, world tag world_id, default the lowest id seen), every
+        frame's camera pose and a per-tag std.  Detect with this detector's camera model and tag size, pack (asl_obs
+        records) and map (asl_map_batch)."""
+        from .dist import pack_observations
+        from .mapping import MapResult
+        if self.camera_matrix is None:
+            raise ValueError("build_map needs the detector's camera parameters")
+        a = np.ascontiguousarray(np.stack(frames) if isinstance(frames, (list, tuple)) else frames)
+        if a.ndim not in (3, 4) or a.dtype != np.uint8:
+            raise ValueError("frames must be (n, H, W[, 3]) uint8")
+        dist = self._dist()
+        dets, poses, npf = self.detector._det.detect_host(a, channels=1 if a.ndim == 3 else None, K=self.camera_matrix, dist=dist,
+                                                          tag_size=self.tag_size)
+        npf = np.asarray(npf, dtype=np.int64)
+        mt = max(1, min(256, int(npf.max()) if len(npf) else 1))
+        obs = pack_observations(dets, poses, npf, mt)
+        n_ids = int(max(1, obs["id"].max() + 1 if obs.size else 1))
+        res, tmap, std, cams = self.detector._det.build_map(obs, n_ids, self.camera_matrix, dist, self.tag_size,
+                                                             world_id=-1 if world_id is None else int(world_id), max_iters=max_iters,
+                                                             with_std=with_std)
+        return MapResult(res, tmap, std, cams)
+
     def detect_batch_device(self, data_ptr, n_frames, channels, width, height, with_pose=True, stream=0, **kw):
         """Frames resident in HBM -> (dets, poses, n_per_frame) structured arrays (see _lib)."""
         K = self.camera_matrix if with_pose else None

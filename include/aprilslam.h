@@ -252,6 +252,50 @@ int asl_calibrate_batch(asl_detector *det, const asl_obs *obs, int n_frames, int
                         double tag_size, int width, int height, const double *K_init, int n_dist, int flags, int max_iters,
                         asl_calib_result *result, asl_cam_pose *poses);
 
+/* ---- tag-map reconstruction: the world<-tag pose of every tag a batch of frames sees, every frame's camera pose and a
+   per-tag std, from the asl_obs block alone (no map given).  The output is the asl_map_tag block
+   asl_localize_frames_device reads. */
+typedef struct {
+    double cost_seed, cost;        /* sum of squared pixel residuals after the seed / at the end */
+    double rms_px, rms_seed_px;    /* per corner, over the observations in the solve */
+    int32_t n_frames_used, n_tags, n_obs, n_obs_dropped;  /* n_tags counts the world tag; n_obs_dropped: taking-part slots
+                                                             of frames with >= 2 of them that are not in the solve */
+    int32_t iterations;            /* LM trials run */
+    int32_t world_id;
+    int32_t status;                /* 0 ok, 1 nothing to solve (no world tag in a used frame, or no observation left),
+                                      2 reduced system not positive definite, 3 non-finite */
+    int32_t reserved;
+} asl_map_result;                  /* 64 bytes */
+
+/* Map from d_obs (n_frames x max_tags records as asl_pack_observations_device writes them), device pointers.  A slot takes
+   part if flags & 1 and 0 <= id < n_ids (a repeated id only in its first slot); a frame is used with >= 2 such slots.  The
+   tags are the ids seen in used frames; world_id (-1: the lowest of them) is the identity of the map.  Seed: breadth-first
+   rounds from the world tag through the largest flags & 2 observation (ties: lower tag id / lower frame), two reseed sweeps
+   (cameras, then tags: the current pose, or the pose the PnP of one of the <= 8 largest flags & 2 observations implies, or
+   its mirrored planar minimum, whichever has the least total reprojection error), the world tag back at the identity, a
+   flip test per tag (its pose against its mirror, each polished by pose-only LM).  An observation with a corner at
+   z <= 1e-6 in its camera then leaves; a frame with fewer than 2 left is dropped.  Joint Levenberg-Marquardt over 6
+   parameters per frame and per tag but the world tag, the camera model of asl_solve_pnp_batch (K, n_dist = 0, 4 or 5
+   coefficients, corners (+-h, +-h, 0), h = float32(tag_size / 2)), at most max_iters trials (in [1, 1000]; all of them are
+   enqueued, and after the stop each remaining one still factors an identity system of the reduced size), stopping on an
+   accepted trial of relative decrease below 1e-12.  d_map: n_ids asl_map_tag, world<-tag, valid for the mapped tags; d_tag_std (NULL:
+   skipped): n_ids x 6 doubles, sqrt(sigma^2 diag) of the tag's block of the inverse undamped normal matrix, (omega, v) of a
+   left update in the world frame, sigma^2 = cost / (8 n_obs - 6 frames - 6 (tags - 1)), 0 for the world tag and unmapped
+   ids, and 0 for every tag if the undamped reduced system at the solution is not positive definite; d_poses: n_frames asl_cam_pose, world<-camera, rms_px final and rms_seed_px after the seed over the frame's
+   observations in the solve, n_tags those, n_rejected the rest of its taking-part slots, seed_slot the slot that placed the
+   frame, status 0 used, 1 fewer than 2 taking-part slots, 3 dropped (fewer than 2 observations in front of the camera),
+   4 in a solve that failed, 5 not connected to the world tag; d_result: one asl_map_result.  The host waits once, for the
+   problem size (cameras, tags, observations), then enqueues the rest on `stream` and returns.  More than 1000 tags, or a
+   world_id >= 0 that no used frame sees, is an error.  max_tags in [1, 256]; deterministic: the same input gives the same
+   bytes.  tests/map_ref.py states the algorithm. */
+int asl_map_frames_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, int n_ids, const double *K,
+                          const double *dist, int n_dist, double tag_size, int world_id, int max_iters, void *d_map,
+                          void *d_tag_std, void *d_poses, void *d_result, void *stream);
+/* The same computation on host records, synchronous (the detector keeps the device copies and grows them on demand). */
+int asl_map_batch(asl_detector *det, const asl_obs *obs, int n_frames, int max_tags, int n_ids, const double *K,
+                  const double *dist, int n_dist, double tag_size, int world_id, int max_iters, asl_map_tag *map,
+                  double *tag_std, asl_cam_pose *poses, asl_map_result *result);
+
 /* ---- before the detector: the image-formation step on the device (reference src/simulation/renderer.py:197-274:
    purple clear colour, one GL_LINEAR-textured quad per tag, BGR read-back).  One plane per visible tag and frame, in
    painter's order (far to near); a plane with tex < 0 ends a frame's list. */

@@ -1,0 +1,398 @@
+"""NumPy statement of the tag-map reconstruction (asl_map_frames_device / asl_map_batch, aprilslam_amd/csrc/k_map.inc):
+the same gather, breadth-first initial map, reseed sweeps, flip test, behind-camera test and joint Levenberg-Marquardt,
+on the host.  Test infrastructure, as tests/localize_ref.py is for the localisation.
+
+  gather   a slot takes part if flags & 1, 0 <= id < n_ids and no earlier slot of the frame took part with the same id;
+           a frame is used with >= 2 taking-part slots (else status 1).  Cameras are the used frames in frame order,
+           tags the ids seen in used frames in ascending order, observations the taking-part slots of used frames in
+           (frame, slot) order.  world_id -1 picks the lowest id seen.
+  chain    the world tag sits at the identity; rounds of two halves until nothing changes.  (a) every unplaced camera
+           that sees a placed tag through a slot with flags & 2 takes camera<-world = T_obs inv(G) from the one of
+           largest corner area (ties: lower tag); (b) every unplaced tag seen through a flags & 2 slot of a placed camera
+           takes G = inv(W) T_obs from the camera where its area is largest (ties: lower camera).  Each half reads the
+           state the previous half left.  Cameras / tags never reached get status 5 / valid 0, their observations drop.
+  sweeps   twice: all cameras, then all tags (localize_ref's candidate and scoring rules): candidates are the current
+           pose, then, for the <= 8 seeding observations of largest area (ties: lower slot / lower camera) in their own
+           order, the pose the PnP pose implies and the one its mirrored planar minimum implies; the strictly lowest
+           total corner cost over every active observation wins.  Then the gauge: the world tag back at the identity.
+  flip     every other tag with an observation: its pose and its mirror (the mirrored planar minimum of the tag in the
+           view where it is largest, ties: lower camera) are each polished by pose-only LM (localize_ref.lm's schedule,
+           the cameras held, left update of world<-tag); the mirror replaces the pose only at a strictly lower cost.
+  behind   an observation with a corner at z <= 1e-6 in its camera leaves the solve; a camera left with fewer than
+           2 observations is dropped (status 3) with all of them; a tag left with none is not mapped.
+  LM       unknowns 6 per camera (camera<-world) and 6 per mapped tag but the world tag (world<-tag), left updates
+           R <- exp(w) R, t <- exp(w) t + v; residuals the k_pnp.inc camera model at the corners (+-h, +-h, 0); a corner
+           at z <= 1e-9 costs 1e12 and adds no row.  (H + lambda diag(max(H_ii, 1e-12))) d = -g, lambda0 = 1e-3,
+           x0.1 (floor 1e-12) after an accepted trial, x10 after a rejected one; max_iters trials at most, an accepted
+           trial of relative decrease below 1e-12 stops; a system that is not positive definite stops with status 2.
+  std      sigma^2 = cost / (8 n_obs - 6 frames - 6 (tags - 1)), std = sqrt(sigma^2 diag(H^-1)) of each tag's block of
+           the undamped normal matrix at the solution (w then v, world frame).
+"""
+import os
+import sys
+
+import numpy as np
+
+import localize_ref as LR
+from aprilslam_amd._lib import CAM_POSE_DTYPE, MAP_RESULT_DTYPE, MAP_TAG_DTYPE
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
+import gn_oracle  # noqa: E402
+
+MAX_CAND = 8
+SWEEPS = 2
+BEHIND_MARGIN = 1e-6
+MAX_MAP_TAGS = 1000
+
+
+def inv(T):
+    out = np.eye(4)
+    out[:3, :3] = T[:3, :3].T
+    out[:3, 3] = -T[:3, :3].T @ T[:3, 3]
+    return out
+
+
+def rec4(T12):
+    T = np.eye(4)
+    T[:3] = np.asarray(T12, dtype=np.float64).reshape(3, 4)
+    return T
+
+
+def mirror4(T):
+    R, t = LR.mirrored(T[:3, :3], T[:3, 3])
+    out = np.eye(4)
+    out[:3, :3], out[:3, 3] = R, t
+    return out
+
+
+def obj3(h):
+    return np.array([[-h, -h, 0.0], [h, -h, 0.0], [h, h, 0.0], [-h, h, 0.0]])
+
+
+def obs_cost(cam, Wc, Gj, uv, h):
+    """total corner cost of one observation (4 corners, localize_ref's rules)"""
+    Xw = obj3(h) @ Gj[:3, :3].T + Gj[:3, 3]
+    return float(LR.corner_costs(cam, Wc[:3, :3], Wc[:3, 3], Xw, uv).sum())
+
+
+def top_k(areas, k=MAX_CAND):
+    """positions of the k largest areas (ties: lower position), in ascending position order"""
+    order = sorted(range(len(areas)), key=lambda i: (-areas[i], i))
+    return sorted(order[:k])
+
+
+def tag_lm(cam, G, Ws, uvs, h):
+    """pose-only LM of one world<-tag G with the cameras Ws (camera<-world) held; localize_ref.lm's schedule"""
+    X = obj3(h)
+
+    def lin_wrap(G, want):
+        Xw = X @ G[:3, :3].T + G[:3, 3]
+        if not want:
+            return sum(float(LR.corner_costs(cam, Wc[:3, :3], Wc[:3, 3], Xw, uv).sum()) for Wc, uv in zip(Ws, uvs)), None, None
+        cost, H, g = 0.0, np.zeros((6, 6)), np.zeros(6)
+        for Wc, uv in zip(Ws, uvs):
+            P = Xw @ Wc[:3, :3].T + Wc[:3, 3]
+            for q in range(4):
+                if not P[q, 2] > LR.Z_MIN:
+                    cost += LR.BEHIND_COST
+                    continue
+                pr, Jp = LR.project(cam, P[q:q + 1], jac=True)
+                r = pr[0] - uv[q]
+                cost += float(r @ r)
+                a = Jp[0] @ Wc[:3, :3]                      # (2, 3): d uv / d Xw
+                J = np.concatenate([np.cross(Xw[q], a), a], axis=1)
+                H += J.T @ J
+                g += J.T @ r
+        return cost, H, g
+
+    cost, H, g = lin_wrap(G, True)
+    lam = LR.LAMBDA0
+    for _ in range(LR.LM_ITERS):
+        A = H.copy()
+        A[np.diag_indices(6)] += lam * np.diag(H)
+        d = LR.chol6_solve(A, -g)
+        if d is None:
+            lam *= 10
+            continue
+        dR = LR.rodrigues(d[:3])
+        Gn = np.eye(4)
+        Gn[:3, :3] = dR @ G[:3, :3]
+        Gn[:3, 3] = dR @ G[:3, 3] + d[3:]
+        cn, _, _ = lin_wrap(Gn, False)
+        if cn < cost:
+            stop = cost - cn < LR.REL_STOP * cost
+            G, cost = Gn, cn
+            lam *= 0.1
+            if stop:
+                break
+            cost, H, g = lin_wrap(G, True)
+        else:
+            lam *= 10
+    return G, cost
+
+
+def _project_many(cam, P):
+    """(n, 2) pixels and (n, 2, 3) Jacobians; rows with z <= Z_MIN come back as zeros"""
+    ok = P[:, 2] > LR.Z_MIN
+    uv, J = np.zeros((len(P), 2)), np.zeros((len(P), 2, 3))
+    if ok.any():
+        uv[ok], J[ok] = LR.project(cam, P[ok], jac=True)
+    return uv, J, ok
+
+
+def joint_linearise(cam, W, G, oc, ot, uv, h, cam_col, tag_col, n_par):
+    """cost, H, g of the joint problem: cam_col[c] / tag_col[j] = first column or -1 (held)"""
+    X = obj3(h)
+    M = len(oc)
+    q = np.einsum('mij,kj->mki', G[ot][:, :3, :3], X) + G[ot][:, None, :3, 3]               # (M, 4, 3) world
+    P = np.einsum('mij,mkj->mki', W[oc][:, :3, :3], q) + W[oc][:, None, :3, 3]               # (M, 4, 3) camera
+    pr, Jp, ok = _project_many(cam, P.reshape(-1, 3))
+    r = (pr - uv.reshape(-1, 2)) * ok[:, None]
+    cost = float((r * r).sum()) + LR.BEHIND_COST * float((~ok).sum())
+    Jp = Jp * ok[:, None, None]
+    Pf, qf = P.reshape(-1, 3), q.reshape(-1, 3)
+    Jc = np.concatenate([np.cross(Pf[:, None, :], Jp), Jp], axis=2)                           # [P x jp | jp]
+    a = np.einsum('nri,nij->nrj', Jp, np.repeat(W[oc][:, :3, :3], 4, axis=0))
+    Jt = np.concatenate([np.cross(qf[:, None, :], a), a], axis=2)
+    J = np.zeros((8 * M, n_par))
+    rows = np.arange(8 * M).reshape(-1, 2)
+    cc, tc = np.repeat(cam_col[oc], 4), np.repeat(tag_col[ot], 4)
+    for n in range(4 * M):
+        if cc[n] >= 0:
+            J[rows[n], cc[n]:cc[n] + 6] = Jc[n]
+        if tc[n] >= 0:
+            J[rows[n], tc[n]:tc[n] + 6] = Jt[n]
+    return cost, J.T @ J, J.T @ r.ravel()
+
+
+def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_std=True, trace=None):
+    """(result MAP_RESULT_DTYPE record, map (n_ids,) MAP_TAG_DTYPE, tag_std (n_ids, 6), poses (n_frames,) CAM_POSE_DTYPE);
+    trace (a dict, optional) receives the ids the flip test turned over ("flipped")"""
+    obs = np.asarray(obs)
+    F, S = obs.shape
+    cam = LR.camera(K, dist)
+    h = LR.half_size(tag_size)
+    res = np.zeros((), dtype=MAP_RESULT_DTYPE)
+    out_map = np.zeros(n_ids, dtype=MAP_TAG_DTYPE)
+    tag_std = np.zeros((n_ids, 6))
+    poses = np.zeros(F, dtype=CAM_POSE_DTYPE)
+    poses["T"] = np.eye(4)
+    poses["seed_slot"] = -1
+    poses["status"] = 1
+
+    # gather
+    part = np.zeros((F, S), dtype=bool)
+    for f in range(F):
+        seen = set()
+        for s in range(S):
+            i, fl = int(obs["id"][f, s]), int(obs["flags"][f, s])
+            if (fl & 1) and 0 <= i < n_ids and i not in seen:
+                part[f, s] = True
+                seen.add(i)
+    npart = part.sum(axis=1)
+    frames = [f for f in range(F) if npart[f] >= 2]
+    ids = sorted({int(obs["id"][f, s]) for f in frames for s in range(S) if part[f, s]})
+    tag_of = {i: j for j, i in enumerate(ids)}
+    ob = [(c, tag_of[int(obs["id"][f, s])], f, s) for c, f in enumerate(frames) for s in range(S) if part[f, s]]
+    oc = np.array([o[0] for o in ob], dtype=np.int64)
+    ot = np.array([o[1] for o in ob], dtype=np.int64)
+    ofr = np.array([o[2] for o in ob], dtype=np.int64)
+    osl = np.array([o[3] for o in ob], dtype=np.int64)
+    M, NC, NT = len(ob), len(frames), len(ids)
+    if world_id < 0:
+        world_id = ids[0] if ids else -1
+    res["world_id"] = world_id
+    res["n_obs_dropped"] = M
+    if world_id not in tag_of:
+        res["status"] = 1
+        for f in frames:
+            poses["status"][f] = 5
+            poses["n_rejected"][f] = npart[f]
+        return res, out_map, tag_std, poses
+    if NT > MAX_MAP_TAGS:
+        raise ValueError("more than %d tags" % MAX_MAP_TAGS)
+    wt = tag_of[world_id]
+    uv = np.stack([obs["corners"][f, s].astype(np.float64).reshape(4, 2) for f, s in zip(ofr, osl)]) if M else np.zeros((0, 4, 2))
+    To = [rec4(obs["T"][f, s]) for f, s in zip(ofr, osl)]
+    seedable = np.array([bool(obs["flags"][f, s] & 2) for f, s in zip(ofr, osl)], dtype=bool)
+    area = np.array([LR.corner_area(obs["corners"][f, s]) for f, s in zip(ofr, osl)])
+    by_cam = [np.flatnonzero(oc == c) for c in range(NC)]
+    by_tag = [np.flatnonzero(ot == j) for j in range(NT)]
+
+    # chain
+    W = np.tile(np.eye(4), (NC, 1, 1))
+    G = np.tile(np.eye(4), (NT, 1, 1))
+    cplaced = np.zeros(NC, dtype=bool)
+    tplaced = np.zeros(NT, dtype=bool)
+    tplaced[wt] = True
+    seed_slot = np.full(NC, -1)
+    changed = True
+    while changed:
+        changed = False
+        for c in range(NC):
+            if cplaced[c]:
+                continue
+            cand = [m for m in by_cam[c] if seedable[m] and tplaced[ot[m]]]
+            if cand:
+                m = min(cand, key=lambda m: (-area[m], ot[m]))
+                W[c] = To[m] @ inv(G[ot[m]])
+                cplaced[c] = True
+                seed_slot[c] = osl[m]
+                changed = True
+        for j in range(NT):
+            if tplaced[j]:
+                continue
+            cand = [m for m in by_tag[j] if seedable[m] and cplaced[oc[m]]]
+            if cand:
+                m = min(cand, key=lambda m: (-area[m], oc[m]))
+                G[j] = inv(W[oc[m]]) @ To[m]
+                tplaced[j] = True
+                changed = True
+    act = cplaced[oc] & tplaced[ot] if M else np.zeros(0, dtype=bool)
+
+    # sweeps
+    for _ in range(SWEEPS):
+        Wn = W.copy()
+        for c in range(NC):
+            ms = [m for m in by_cam[c] if act[m]]
+            if not cplaced[c] or not ms:
+                continue
+            cands = [W[c]]
+            sm = [m for m in ms if seedable[m]]
+            for k in top_k([area[m] for m in sm]):
+                m = sm[k]
+                cands += [To[m] @ inv(G[ot[m]]), mirror4(To[m]) @ inv(G[ot[m]])]
+            costs = [sum(obs_cost(cam, Tc, G[ot[m]], uv[m], h) for m in ms) for Tc in cands]
+            Wn[c] = cands[int(np.argmin(costs))]
+        W = Wn
+        Gn = G.copy()
+        for j in range(NT):
+            ms = [m for m in by_tag[j] if act[m]]
+            if not tplaced[j] or not ms:
+                continue
+            cands = [G[j]]
+            sm = [m for m in ms if seedable[m]]
+            for k in top_k([area[m] for m in sm]):
+                m = sm[k]
+                Wi = inv(W[oc[m]])
+                cands += [Wi @ To[m], Wi @ mirror4(To[m])]
+            costs = [sum(obs_cost(cam, W[oc[m]], Tg, uv[m], h) for m in ms) for Tg in cands]
+            Gn[j] = cands[int(np.argmin(costs))]
+        G = Gn
+    Gw = G[wt].copy()
+    Mi = inv(Gw)
+    W = W @ Gw[None]
+    G = Mi[None] @ G
+    G[wt] = np.eye(4)
+
+    # flip test
+    for j in range(NT):
+        ms = [m for m in by_tag[j] if act[m]]
+        if j == wt or not ms:
+            continue
+        Ws, uvs = [W[oc[m]] for m in ms], [uv[m] for m in ms]
+        T0, c0 = tag_lm(cam, G[j], Ws, uvs, h)
+        big = min(range(len(ms)), key=lambda k: (-area[ms[k]], k))
+        Wb = Ws[big]
+        T1, c1 = tag_lm(cam, inv(Wb) @ mirror4(Wb @ G[j]), Ws, uvs, h)
+        G[j] = T1 if c1 < c0 else T0
+        if trace is not None and c1 < c0:
+            trace.setdefault("flipped", []).append(ids[j])
+
+    # behind the camera, dropped frames, mapped tags
+    X = obj3(h)
+    for m in range(M):
+        if act[m]:
+            Pm = (X @ G[ot[m]][:3, :3].T + G[ot[m]][:3, 3]) @ W[oc[m]][:3, :3].T + W[oc[m]][:3, 3]
+            act[m] = bool((Pm[:, 2] > BEHIND_MARGIN).all())
+    cstat = np.where(cplaced, 0, 5)
+    for c in range(NC):
+        if cplaced[c] and act[by_cam[c]].sum() < 2:
+            cstat[c] = 3
+            act[by_cam[c]] = False
+    mapped = np.array([j == wt or act[by_tag[j]].any() for j in range(NT)], dtype=bool)
+    n_obs = int(act.sum())
+
+    status = 0
+    cost0 = cost = 0.0
+    it = 0
+    cams_used = [c for c in range(NC) if cstat[c] == 0]
+    free_tags = [j for j in range(NT) if mapped[j] and j != wt]
+    if n_obs == 0:
+        status = 1
+    else:
+        cam_col = np.full(NC, -1)
+        tag_col = np.full(NT, -1)
+        for k, c in enumerate(cams_used):
+            cam_col[c] = 6 * k
+        for k, j in enumerate(free_tags):
+            tag_col[j] = 6 * (len(cams_used) + k)
+        npar = 6 * (len(cams_used) + len(free_tags))
+        a = np.flatnonzero(act)
+        seed_obs = np.array([obs_cost(cam, W[oc[m]], G[ot[m]], uv[m], h) for m in range(M)])
+        cost, H, g = joint_linearise(cam, W, G, oc[a], ot[a], uv[a], h, cam_col, tag_col, npar)
+        cost0 = cost
+        lam = 1e-3
+        while it < max_iters:
+            it += 1
+            A = H.copy()
+            A[np.diag_indices(npar)] += lam * np.maximum(np.diag(H), 1e-12)
+            try:
+                L = np.linalg.cholesky(A)
+            except np.linalg.LinAlgError:
+                status = 2
+                break
+            d = np.linalg.solve(L.T, np.linalg.solve(L, -g))
+            Wn, Gn = W.copy(), G.copy()
+            for c in cams_used:
+                Wn[c] = gn_oracle.apply_update(W[c], d[cam_col[c]:cam_col[c] + 6])
+            for j in free_tags:
+                Gn[j] = gn_oracle.apply_update(G[j], d[tag_col[j]:tag_col[j] + 6])
+            cn, Hn, gn = joint_linearise(cam, Wn, Gn, oc[a], ot[a], uv[a], h, cam_col, tag_col, npar)
+            if cn < cost:
+                stop = cost - cn < 1e-12 * cost
+                W, G, cost, H, g = Wn, Gn, cn, Hn, gn
+                lam = max(lam * 0.1, 1e-12)
+                if stop:
+                    break
+            else:
+                lam *= 10
+        if status == 0 and not np.isfinite(cost):
+            status = 3
+        if status == 0 and with_std:
+            dof = 8 * n_obs - 6 * len(cams_used) - 6 * len(free_tags)
+            s2 = cost / dof if dof > 0 else 0.0
+            Hi = np.linalg.inv(H)
+            for j in free_tags:
+                tag_std[ids[j]] = np.sqrt(s2 * np.diag(Hi)[tag_col[j]:tag_col[j] + 6])
+        fin = np.array([obs_cost(cam, W[oc[m]], G[ot[m]], uv[m], h) for m in range(M)])
+
+    # records
+    for c, f in enumerate(frames):
+        na = int(act[by_cam[c]].sum())
+        st = int(cstat[c])
+        if st == 0 and status != 0:
+            st = 4
+        poses["status"][f] = st
+        poses["seed_slot"][f] = seed_slot[c]
+        poses["n_tags"][f] = na if st in (0, 4) else 0
+        poses["n_rejected"][f] = npart[f] - (na if st in (0, 4) else 0)
+        if st in (0, 4):
+            poses["T"][f] = inv(W[c])
+            if na and n_obs:
+                poses["rms_px"][f] = np.sqrt(sum(fin[m] for m in by_cam[c] if act[m]) / (4.0 * na))
+                poses["rms_seed_px"][f] = np.sqrt(sum(seed_obs[m] for m in by_cam[c] if act[m]) / (4.0 * na))
+    for j in range(NT):
+        if mapped[j] and status == 0:
+            out_map["T"][ids[j]] = G[j][:3].ravel()
+            out_map["valid"][ids[j]] = 1
+    res["cost_seed"], res["cost"] = cost0, cost
+    if n_obs:
+        res["rms_px"], res["rms_seed_px"] = np.sqrt(cost / (4.0 * n_obs)), np.sqrt(cost0 / (4.0 * n_obs))
+    res["n_frames_used"] = len(cams_used) if status == 0 else 0
+    res["n_tags"] = int(mapped.sum()) if status == 0 else 0
+    res["n_obs"] = n_obs
+    res["n_obs_dropped"] = M - n_obs
+    res["iterations"] = it
+    res["status"] = status
+    return res, out_map, tag_std, poses

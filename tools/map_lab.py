@@ -1,0 +1,137 @@
+"""Times asl_map_frames_device (HIP events, median after warm-up) on the bench scene (1024 frames x 20 tags, 720p) and on a
+200-tag scene, the host path it replaces (map_init.chain_initial_map + reseed_poses on the host, asl_gn_solve) on the same
+observations, and the map and camera errors against the truth in the world-tag gauge.
+
+    python tools/map_lab.py [--frames 1024] [--reps 10] [--out results.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import localize_cases as LC  # noqa: E402
+import map_cases as MC  # noqa: E402
+import map_ref as MR  # noqa: E402
+from aprilslam_amd import _lib, map_init, synth  # noqa: E402
+
+
+def scene_block(n_frames, ntags, noise, rng):
+    K = synth.camera_matrix(LC.W, LC.H, 45.0)
+    tags = LC.bench_scene(ntags=ntags)
+    cams = LC.trajectory(n_frames)
+    mt = min(256, ntags)
+    obs = np.stack([LC.exact_frame(tags, p, r, K, max_tags=mt) for p, r in cams])
+    obs["corners"] += np.where(obs["id"][..., None] >= 0, rng.normal(0, noise, obs["corners"].shape), 0).astype(np.float32)
+    return K, tags, cams, obs
+
+
+def time_device(det, obs, n_ids, K, reps):
+    import torch
+    dev = torch.device("cuda:0")
+    n, mt = obs.shape
+    d_obs = torch.from_numpy(np.ascontiguousarray(obs).view(np.uint8).reshape(n, -1)).to(dev)
+    d_map = torch.empty((n_ids, _lib.MAP_TAG_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    d_std = torch.empty((n_ids, 6), dtype=torch.float64, device=dev)
+    d_poses = torch.empty((n, _lib.CAM_POSE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    d_res = torch.empty((64,), dtype=torch.uint8, device=dev)
+    s = torch.cuda.Stream(dev)
+    ms = []
+    for r in range(reps + 2):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(s)
+        det.build_map_device(d_obs.data_ptr(), n, mt, n_ids, K, None, LC.TAG_INNER, d_map.data_ptr(), d_std.data_ptr(), d_poses.data_ptr(),
+                             d_res.data_ptr(), stream=s.cuda_stream)
+        b.record(s)
+        s.synchronize()
+        if r >= 2:
+            ms.append(a.elapsed_time(b))
+    res = d_res.cpu().numpy().view(_lib.MAP_RESULT_DTYPE).reshape(())
+    tmap = d_map.cpu().numpy().view(_lib.MAP_TAG_DTYPE).reshape(n_ids)
+    poses = d_poses.cpu().numpy().view(_lib.CAM_POSE_DTYPE).reshape(n)
+    return float(np.median(ms)), res, tmap, poses
+
+
+def time_host(det, obs, K, iters):
+    t0 = time.perf_counter()
+    frames = [[(int(o["id"]), MR.rec4(o["T"]), o["corners"].astype(np.float64).reshape(4, 2)) for o in fr if o["flags"] & 1 and o["id"] >= 0]
+              for fr in obs]
+    world, tags, cams = map_init.chain_initial_map(frames)
+    ids = sorted(tags)
+    cam_idx = [f for f in range(len(frames)) if cams[f] is not None]
+    oc, ot, oT, oC = [], [], [], []
+    for k, f in enumerate(cam_idx):
+        for i, T, c in frames[f]:
+            oc.append(k); ot.append(ids.index(i)); oT.append(T); oC.append(c)
+    cam_T, tag_T = map_init.reseed_poses(np.array([cams[f] for f in cam_idx]), np.array([tags[i] for i in ids]), oc, ot, oT, oC, K,
+                                         LC.TAG_INNER, ids.index(world), sweeps=2, max_cand=8)
+    t1 = time.perf_counter()
+    cam_T, tag_T, stats = det.gn_solve(cam_T, tag_T, np.array(oc, np.int32), np.array(ot, np.int32), np.array(oC), K, LC.TAG_INNER,
+                                       fixed_tag=ids.index(world), iters=iters)
+    t2 = time.perf_counter()
+    return 1e3 * (t1 - t0), 1e3 * (t2 - t1), world, ids, cam_idx, cam_T, tag_T, stats
+
+
+def rigid_align(A, B):
+    """rotation + translation taking points A (n, 3) onto B, least squares"""
+    ca, cb = A.mean(0), B.mean(0)
+    U, _, Vt = np.linalg.svd((A - ca).T @ (B - cb))
+    D = np.diag([1, 1, np.sign(np.linalg.det(Vt.T @ U.T))])
+    R = Vt.T @ D @ U.T
+    return lambda X: (X - ca) @ R.T + cb
+
+
+def errors(tmap, poses, tags, cams, world):
+    gt_t, gt_c = MC.truth(tags, cams, world)
+    ids = [int(i) for i in np.flatnonzero(tmap["valid"])]
+    P = np.array([MR.rec4(tmap["T"][i])[:3, 3] for i in ids])
+    Q = np.array([gt_t[i][:3, 3] for i in ids])
+    al = rigid_align(P, Q)
+    used = np.flatnonzero(poses["status"] == 0)
+    C = np.array([poses["T"][f][:3, 3] for f in used])
+    Cq = np.array([gt_c[f][:3, 3] for f in used])
+    return dict(tag_max=float(np.abs(P - Q).max()), tag_max_aligned=float(np.abs(al(P) - Q).max()),
+                cam_max=float(np.abs(C - Cq).max()), cam_max_aligned=float(np.abs(al(C) - Cq).max()))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=1024)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    det = _lib.Detector("tagStandard41h12", id_limit=0)
+    rng = np.random.default_rng(7)
+    out = {}
+    for name, ntags, nf in (("bench_20", 20, a.frames), ("scene_200", 200, min(a.frames, 256))):
+        K, tags, cams, obs = scene_block(nf, ntags, 0.3, rng)
+        n_ids = 1 + max(t["id"] for t in tags)
+        ms, res, tmap, poses = time_device(det, obs, n_ids, K, a.reps)
+        hs, hg, world, ids, cam_idx, cam_T, tag_T, stats = time_host(det, obs, K, a.iters)
+        hmap = np.zeros(n_ids, dtype=_lib.MAP_TAG_DTYPE)
+        for j, i in enumerate(ids):
+            hmap["T"][i], hmap["valid"][i] = tag_T[j][:3].ravel(), 1
+        hp = np.zeros(nf, dtype=_lib.CAM_POSE_DTYPE)
+        hp["status"] = 1
+        for k, f in enumerate(cam_idx):
+            hp["T"][f], hp["status"][f] = cam_T[k], 0
+        r = dict(frames=nf, tags=int(res["n_tags"]), obs=int(res["n_obs"]), status=int(res["status"]), iterations=int(res["iterations"]),
+                 rms_px=float(res["rms_px"]), device_ms=ms, host_seed_ms=hs, host_gn_ms=hg, host_cost=float(stats[1]), device_cost=float(res["cost"]),
+                 device_err=errors(tmap, poses, tags, cams, int(res["world_id"])), host_err=errors(hmap, hp, tags, cams, world))
+        out[name] = r
+        print(name, json.dumps(r), flush=True)
+    det.close()
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
