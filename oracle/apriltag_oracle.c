@@ -274,7 +274,7 @@ static void fit_line(const lfp_t *lfps, int sz, int i0, int i1, double *lineparm
 static const float LPF[7] = {0.011108996538242306f, 0.1353352832366127f, 0.6065306597126334f, 1.0f,
                              0.6065306597126334f, 0.1353352832366127f, 0.011108996538242306f};
 
-static int quad_segment_maxima(const lfp_t *lfps, int sz, int indices[4])
+static int quad_segment_maxima(const lfp_t *lfps, int sz, int indices[4], aso_maxima_stat *st)
 {
     int ksz = sz / 12 < 20 ? sz / 12 : 20;
     if (ksz < 2) return 0;
@@ -296,6 +296,7 @@ static int quad_segment_maxima(const lfp_t *lfps, int sz, int indices[4])
             nmaxima++;
         }
     free(errs); free(sm);
+    if (st) st->nmaxima = nmaxima;
     int ok = 0;
     if (nmaxima < 4) goto done;
     if (nmaxima > MAX_NMAXIMA) {
@@ -308,6 +309,7 @@ static int quad_segment_maxima(const lfp_t *lfps, int sz, int indices[4])
             double t = cp[i]; cp[i] = cp[best]; cp[best] = t;
         }
         double thresh = cp[MAX_NMAXIMA];
+        if (st) st->tie = cp[MAX_NMAXIMA - 1] == thresh;
         free(cp);
         int out = 0;
         for (int in = 0; in < nmaxima; in++) {
@@ -316,6 +318,7 @@ static int quad_segment_maxima(const lfp_t *lfps, int sz, int indices[4])
         }
         nmaxima = out;
     }
+    if (st) st->nkept = nmaxima;
     {
         int best_indices[4] = {0, 0, 0, 0};
         double best_error = HUGE_VALF;
@@ -362,7 +365,7 @@ static double sq(double x) { return x * x; }
 
 /* one cluster -> quad (corners in decimated-image pixel coordinates) */
 static int fit_quad(const uint8_t *im, int w, int h, const aso_point *pts, int sz, int tag_width,
-                    int normal_border, int reversed_border, aso_quad *quad)
+                    int normal_border, int reversed_border, aso_quad *quad, aso_maxima_stat *st)
 {
     if (sz < 24) return 0;
     int xmax = pts[0].x, xmin = pts[0].x, ymax = pts[0].y, ymin = pts[0].y;
@@ -398,6 +401,7 @@ static int fit_quad(const uint8_t *im, int w, int h, const aso_point *pts, int s
         /* sp[i-1] is still the previous INPUT element here: writes only reach indices < i-1 or i itself */
         sz = outpos;
     }
+    if (st) st->unique = sz;
     if (sz < 24) { free(sp); return 0; }
 
     lfp_t *lfps = calloc((size_t)sz, sizeof(lfp_t));
@@ -419,7 +423,7 @@ static int fit_quad(const uint8_t *im, int w, int h, const aso_point *pts, int s
 
     int res = 0, indices[4];
     double lines[4][4];
-    if (!quad_segment_maxima(lfps, sz, indices)) goto finish;
+    if (!quad_segment_maxima(lfps, sz, indices, st)) goto finish;
     for (int i = 0; i < 4; i++) {
         /* The points next to a corner are the least reliable ones of a side (a missing corner pixel or
            unequal gradient weights on the two sides move the error maximum by a point or two), so a sixth
@@ -494,7 +498,7 @@ int aso_fit_quads(const uint8_t *dec, int w, int h, const aso_point *pts, long n
         if (sz >= 24 && sz <= 3L * (2 * w + 2 * h) && nq < cap) {
             aso_quad q;
             memset(&q, 0, sizeof q);
-            if (fit_quad(dec, w, h, pts + i, (int)sz, min_tag_width, normal_border, reversed_border, &q)) {
+            if (fit_quad(dec, w, h, pts + i, (int)sz, min_tag_width, normal_border, reversed_border, &q, NULL)) {
                 q.cluster = pts[i].cluster;
                 out[nq++] = q;
             }
@@ -502,6 +506,35 @@ int aso_fit_quads(const uint8_t *dec, int w, int h, const aso_point *pts, long n
         i = j;
     }
     return nq;
+}
+
+long aso_quad_maxima(const uint8_t *dec, int w, int h, const aso_point *pts, long npts,
+                     const aso_family *fam, int decimate, aso_maxima_stat *out, long cap)
+{
+    int min_tag_width = fam->width_at_border / decimate;
+    if (min_tag_width < 3) min_tag_width = 3;
+    int normal_border = !fam->reversed_border, reversed_border = fam->reversed_border;
+    long n = 0, i = 0;
+    while (i < npts) {
+        long j = i;
+        while (j < npts && pts[j].cluster == pts[i].cluster) j++;
+        long sz = j - i;
+        if (n < cap) {
+            aso_maxima_stat *st = &out[n];
+            memset(st, 0, sizeof *st);
+            st->cluster = pts[i].cluster;
+            st->count = (int32_t)sz;
+            st->unique = st->nmaxima = st->nkept = -1;
+            if (sz >= 24 && sz <= 3L * (2 * w + 2 * h)) {
+                aso_quad q;
+                memset(&q, 0, sizeof q);
+                st->fitted = fit_quad(dec, w, h, pts + i, (int)sz, min_tag_width, normal_border, reversed_border, &q, st);
+            }
+        }
+        n++;
+        i = j;
+    }
+    return n;
 }
 
 /* ------------------------------------------------------- S6 edge refinement */

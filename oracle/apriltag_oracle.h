@@ -84,6 +84,21 @@ long aso_gradient_clusters(const uint8_t *th, int w, int h, const uint32_t *labe
 /* S5: fit quads to all clusters of the decimated image; corners in decimated pixel coords */
 int aso_fit_quads(const uint8_t *dec, int w, int h, const aso_point *pts, long npts,
                   const aso_family *fam, int decimate, aso_quad *out, int cap);
+/* Diagnostic of the S5 fit, one record per cluster (test infrastructure): the raw point count the size filter sees; -1
+   for each stage the cluster did not reach.  tie: more than 10 maxima and the 10th and 11th largest errors are equal,
+   so the cap keeps fewer than 10. */
+typedef struct {
+    uint64_t cluster;
+    int32_t count;    /* raw boundary points */
+    int32_t unique;   /* after dropping duplicates (-1: outside [24, 3(2w + 2h)] or rejected by box / polarity) */
+    int32_t nmaxima;  /* local maxima of the smoothed line-fit error, before the cap */
+    int32_t nkept;    /* maxima the corner search sees */
+    int32_t tie;
+    int32_t fitted;   /* a quad came out */
+} aso_maxima_stat;
+/* returns the number of clusters (records beyond cap are counted, not written) */
+long aso_quad_maxima(const uint8_t *dec, int w, int h, const aso_point *pts, long npts,
+                     const aso_family *fam, int decimate, aso_maxima_stat *out, long cap);
 /* S6: refine quad edges on the full-resolution gray image (in place) */
 void aso_refine_edges(const uint8_t *gray, int w, int h, int stride, int decimate, aso_quad *q);
 /* S7: homography + decode one quad; returns 1 and fills det on success */

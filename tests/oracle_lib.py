@@ -32,6 +32,8 @@ class AsoQuad(C.Structure):
     _fields_ = [("p", (C.c_double * 2) * 4), ("reversed_border", C.c_int), ("cluster", C.c_uint64)]
 
 
+MAXIMA_DTYPE = np.dtype([("cluster", "<u8"), ("count", "<i4"), ("unique", "<i4"), ("nmaxima", "<i4"), ("nkept", "<i4"),
+                         ("tie", "<i4"), ("fitted", "<i4")])
 POINT_DTYPE = np.dtype([("cluster", "<u8"), ("x", "<u2"), ("y", "<u2"), ("gx", "<i2"), ("gy", "<i2")])
 assert POINT_DTYPE.itemsize == C.sizeof(AsoPoint)
 
@@ -50,6 +52,7 @@ def lib():
         L.aso_detect_bgr.restype = C.c_int
         L.aso_fit_quads.restype = C.c_int
         L.aso_decode_quad.restype = C.c_int
+        L.aso_quad_maxima.restype = C.c_long
         _lib = L
     return _lib
 
@@ -125,6 +128,20 @@ def fit_quads(dec, pts, fam, decimate_f, cap=4096):
                             C.byref(F.c), decimate_f, out, cap)
     return [dict(p=np.array([[q.p[i][0], q.p[i][1]] for i in range(4)]), reversed_border=q.reversed_border,
                  cluster=q.cluster) for q in out[:n]]
+
+
+def quad_maxima(dec, pts, fam, decimate_f):
+    """Per cluster of `pts` (sorted by cluster, as gradient_clusters returns them): MAXIMA_DTYPE records of how far the
+    quad fit got -- raw and de-duplicated point counts, local maxima before and after the 10-maxima cap, a tie at the cap."""
+    h, w = dec.shape
+    F = Family(fam)
+    pts = np.ascontiguousarray(pts)
+    cap = max(1, len(np.unique(pts["cluster"])))
+    out = np.zeros(cap, dtype=MAXIMA_DTYPE)
+    n = lib().aso_quad_maxima(_u8(np.ascontiguousarray(dec)), w, h, pts.ctypes.data_as(C.c_void_p), C.c_long(len(pts)),
+                              C.byref(F.c), decimate_f, out.ctypes.data_as(C.c_void_p), C.c_long(cap))
+    assert n <= cap
+    return out[:n]
 
 
 def _dets(arr, n):
