@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "asl_common.h"
@@ -975,16 +976,44 @@ extern "C" int asl_solve_pnp_batch(asl_detector *d, const float *corners, const 
     return ASL_OK;
 }
 
+#include "gn_host.inc"
+
+// ---- the device solvers on asl_obs blocks: localisation (k_localize.inc), calibration (k_calib.inc), mapping (k_map.inc)
+
+// The checks they share on the obs block (max_tags slots per frame, ids below n_ids), the lens model and the tag size;
+// no_dist: the caller takes coefficients and dist is NULL
+static int check_obs_args(int max_tags, int n_ids, int n_dist, bool no_dist, double tag_size)
+{
+    if (max_tags < 1 || max_tags > 256) return fail(ASL_EINVAL, "max_tags must be in [1, 256] (got %d)", max_tags);
+    if (n_ids < 1) return fail(ASL_EINVAL, "n_ids must be >= 1 (got %d)", n_ids);
+    if (n_dist != 0 && n_dist != 4 && n_dist != 5) return fail(ASL_EINVAL, "n_dist must be 0, 4 or 5");
+    if (n_dist && no_dist) return fail(ASL_EINVAL, "dist is NULL with n_dist = %d", n_dist);
+    if (!(tag_size > 0) || !std::isfinite(tag_size)) return fail(ASL_EINVAL, "tag_size must be positive (got %g)", tag_size);
+    return ASL_OK;
+}
+
+// The *_batch entry points: the host obs block (and the map, if given) into the detector's device copies
+static int upload_obs(asl_detector *d, const char *what, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids)
+{
+    const size_t obs_bytes = sizeof(asl_obs) * (size_t)n_frames * (size_t)max_tags, map_bytes = sizeof(asl_map_tag) * (size_t)n_ids;
+    if (d->loc_obs.ensure(obs_bytes) || (map && d->loc_map.ensure(map_bytes))) return fail(ASL_ENOMEM, "%s workspace allocation failed", what);
+    HIPCHK(hipMemcpy(d->loc_obs.p, obs, obs_bytes, hipMemcpyHostToDevice));
+    if (map) HIPCHK(hipMemcpy(d->loc_map.p, map, map_bytes, hipMemcpyHostToDevice));
+    return ASL_OK;
+}
+
+// A workspace carved into consecutive pieces, each 256-byte aligned: take(bytes) returns a piece's offset, off the size so far
+struct WsCarve {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
+};
+
 static int check_localize_args(const void *obs, int n_frames, int max_tags, const void *map, int n_ids, const double *K, const double *dist,
                                int n_dist, double tag_size, double max_tag_rms_px, const void *out)
 {
     if (!obs || !map || !K || !out) return fail(ASL_EINVAL, "NULL argument");
     if (n_frames < 0) return fail(ASL_EINVAL, "n_frames < 0");
-    if (max_tags < 1 || max_tags > 256) return fail(ASL_EINVAL, "max_tags must be in [1, 256] (got %d)", max_tags);
-    if (n_ids < 1) return fail(ASL_EINVAL, "n_ids must be >= 1 (got %d)", n_ids);
-    if (n_dist != 0 && n_dist != 4 && n_dist != 5) return fail(ASL_EINVAL, "n_dist must be 0, 4 or 5");
-    if (n_dist && !dist) return fail(ASL_EINVAL, "dist is NULL with n_dist = %d", n_dist);
-    if (!(tag_size > 0) || !std::isfinite(tag_size)) return fail(ASL_EINVAL, "tag_size must be positive (got %g)", tag_size);
+    if (int rc = check_obs_args(max_tags, n_ids, n_dist, !dist, tag_size)) return rc;
     if (!(max_tag_rms_px >= 0) || !std::isfinite(max_tag_rms_px)) return fail(ASL_EINVAL, "max_tag_rms_px must be >= 0 (got %g)", max_tag_rms_px);
     return ASL_OK;
 }
@@ -1021,12 +1050,9 @@ extern "C" int asl_localize_batch(asl_detector *d, const asl_obs *obs, int n_fra
     if (rc) return rc;
     if (n_frames == 0) return ASL_OK;
     HIPCHK(hipSetDevice(d->device));
-    const size_t obs_bytes = sizeof(asl_obs) * (size_t)n_frames * (size_t)max_tags, map_bytes = sizeof(asl_map_tag) * (size_t)n_ids,
-                 out_bytes = sizeof(asl_cam_pose) * (size_t)n_frames;
-    if (d->loc_obs.ensure(obs_bytes) || d->loc_map.ensure(map_bytes) || d->loc_out.ensure(out_bytes))
-        return fail(ASL_ENOMEM, "localisation workspace allocation failed");
-    HIPCHK(hipMemcpy(d->loc_obs.p, obs, obs_bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d->loc_map.p, map, map_bytes, hipMemcpyHostToDevice));
+    const size_t out_bytes = sizeof(asl_cam_pose) * (size_t)n_frames;
+    if (d->loc_out.ensure(out_bytes)) return fail(ASL_ENOMEM, "localisation workspace allocation failed");
+    if ((rc = upload_obs(d, "localisation", obs, n_frames, max_tags, map, n_ids))) return rc;
     launch_localize(d, d->loc_obs.p, n_frames, max_tags, d->loc_map.p, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, d->loc_out.p, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(out, d->loc_out.p, out_bytes, hipMemcpyDeviceToHost));
@@ -1038,10 +1064,7 @@ static int check_calib_args(const void *obs, int n_frames, int max_tags, const v
 {
     if (!obs || !map || !result || !poses) return fail(ASL_EINVAL, "NULL argument");
     if (n_frames < 1) return fail(ASL_EINVAL, "n_frames must be >= 1 (got %d)", n_frames);
-    if (max_tags < 1 || max_tags > 256) return fail(ASL_EINVAL, "max_tags must be in [1, 256] (got %d)", max_tags);
-    if (n_ids < 1) return fail(ASL_EINVAL, "n_ids must be >= 1 (got %d)", n_ids);
-    if (n_dist != 0 && n_dist != 4 && n_dist != 5) return fail(ASL_EINVAL, "n_dist must be 0, 4 or 5");
-    if (!(tag_size > 0) || !std::isfinite(tag_size)) return fail(ASL_EINVAL, "tag_size must be positive (got %g)", tag_size);
+    if (int rc = check_obs_args(max_tags, n_ids, n_dist, false, tag_size)) return rc;
     if (width < 1 || height < 1) return fail(ASL_EINVAL, "width and height must be positive (got %d x %d)", width, height);
     if (max_iters < 1) return fail(ASL_EINVAL, "max_iters must be >= 1 (got %d)", max_iters);
     if (flags & ~(ASL_CALIB_FIX_PRINCIPAL_POINT | ASL_CALIB_FIX_ASPECT_RATIO | ASL_CALIB_ZERO_TANGENT_DIST))
@@ -1059,12 +1082,12 @@ static int launch_calibrate(asl_detector *d, const void *d_obs, int n_frames, in
 {
     static_assert(sizeof(CalibResultRec) == sizeof(asl_calib_result) && sizeof(asl_calib_result) == 216, "asl_calib_result layout");
     const size_t nf = (size_t)n_frames;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_st = take(sizeof(CalibState)), o_list = take(sizeof(int) * nf), o_fr = take(sizeof(int) * CAL_FR * nf),
-                 o_zh = take(sizeof(double) * CAL_ZH * nf), o_seed = take(sizeof(double) * nf), o_pose = take(sizeof(double) * 2 * 12 * nf),
-                 o_H = take(sizeof(double) * 2 * CAL_HS * nf), o_SB = take(sizeof(double) * CAL_SB * nf), o_bk = take(sizeof(double) * CAL_BK * nf);
-    if (d->cal_ws.ensure(off)) return fail(ASL_ENOMEM, "calibration workspace allocation failed");
+    WsCarve c;
+    const size_t o_st = c.take(sizeof(CalibState)), o_list = c.take(sizeof(int) * nf), o_fr = c.take(sizeof(int) * CAL_FR * nf),
+                 o_zh = c.take(sizeof(double) * CAL_ZH * nf), o_seed = c.take(sizeof(double) * nf),
+                 o_pose = c.take(sizeof(double) * 2 * 12 * nf), o_H = c.take(sizeof(double) * 2 * CAL_HS * nf),
+                 o_SB = c.take(sizeof(double) * CAL_SB * nf), o_bk = c.take(sizeof(double) * CAL_BK * nf);
+    if (d->cal_ws.ensure(c.off)) return fail(ASL_ENOMEM, "calibration workspace allocation failed");
     uint8_t *w = d->cal_ws.p;
     CalibArgs a{};
     a.obs = (const ObsRec *)d_obs; a.map = (const MapTagRec *)d_map;
@@ -1127,12 +1150,9 @@ extern "C" int asl_calibrate_batch(asl_detector *d, const asl_obs *obs, int n_fr
     int rc = check_calib_args(obs, n_frames, max_tags, map, n_ids, tag_size, width, height, K_init, n_dist, flags, max_iters, result, poses);
     if (rc) return rc;
     HIPCHK(hipSetDevice(d->device));
-    const size_t obs_bytes = sizeof(asl_obs) * (size_t)n_frames * (size_t)max_tags, map_bytes = sizeof(asl_map_tag) * (size_t)n_ids,
-                 res_bytes = 256, out_bytes = sizeof(asl_cam_pose) * (size_t)n_frames;
-    if (d->loc_obs.ensure(obs_bytes) || d->loc_map.ensure(map_bytes) || d->cal_out.ensure(res_bytes + out_bytes))
-        return fail(ASL_ENOMEM, "calibration workspace allocation failed");
-    HIPCHK(hipMemcpy(d->loc_obs.p, obs, obs_bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d->loc_map.p, map, map_bytes, hipMemcpyHostToDevice));
+    const size_t res_bytes = 256, out_bytes = sizeof(asl_cam_pose) * (size_t)n_frames;
+    if (d->cal_out.ensure(res_bytes + out_bytes)) return fail(ASL_ENOMEM, "calibration workspace allocation failed");
+    if ((rc = upload_obs(d, "calibration", obs, n_frames, max_tags, map, n_ids))) return rc;
     rc = launch_calibrate(d, d->loc_obs.p, n_frames, max_tags, d->loc_map.p, n_ids, tag_size, width, height, K_init, n_dist, flags, max_iters,
                           d->cal_out.p, d->cal_out.p + res_bytes, nullptr);
     if (rc) return rc;
@@ -1339,11 +1359,7 @@ static int check_map_args(const void *obs, int n_frames, int max_tags, int n_ids
 {
     if (!obs || !K || !map || !poses || !result) return fail(ASL_EINVAL, "NULL argument");
     if (n_frames < 1) return fail(ASL_EINVAL, "n_frames must be >= 1 (got %d)", n_frames);
-    if (max_tags < 1 || max_tags > 256) return fail(ASL_EINVAL, "max_tags must be in [1, 256] (got %d)", max_tags);
-    if (n_ids < 1) return fail(ASL_EINVAL, "n_ids must be >= 1 (got %d)", n_ids);
-    if (n_dist != 0 && n_dist != 4 && n_dist != 5) return fail(ASL_EINVAL, "n_dist must be 0, 4 or 5");
-    if (n_dist && !dist) return fail(ASL_EINVAL, "dist is NULL with n_dist = %d", n_dist);
-    if (!(tag_size > 0) || !std::isfinite(tag_size)) return fail(ASL_EINVAL, "tag_size must be positive (got %g)", tag_size);
+    if (int rc = check_obs_args(max_tags, n_ids, n_dist, !dist, tag_size)) return rc;
     if (world_id < -1 || world_id >= n_ids) return fail(ASL_EINVAL, "world_id must be -1 or in [0, n_ids) (got %d)", world_id);
     if (max_iters < 1 || max_iters > MAP_MAX_ITERS) return fail(ASL_EINVAL, "max_iters must be in [1, %d] (got %d)", MAP_MAX_ITERS, max_iters);
     return ASL_OK;
@@ -1354,12 +1370,11 @@ static int launch_map(asl_detector *d, const void *d_obs, int n_frames, int max_
 {
     static_assert(sizeof(MapResultRec) == sizeof(asl_map_result) && sizeof(asl_map_result) == 64, "asl_map_result layout");
     const size_t nf = (size_t)n_frames, ni = (size_t)n_ids, nsl = nf * (size_t)max_tags;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_head = take(sizeof(MapHead)), o_id = take(4 * 4 * (ni + 1)), o_fr = take(4 * 3 * (nf + 1)), o_cam = take(4 * 4 * (nf + 1)),
-                 o_tag = take(4 * (ni + 1)), o_slot = take(4 * nsl), o_obs = take(4 * 4 * nsl), o_csr = take(4 * (2 * nsl + nf + ni + 2)),
-                 o_W = take(8 * 12 * nf), o_G = take(8 * 12 * ni);
-    if (d->map_ws.ensure(off)) return fail(ASL_ENOMEM, "map workspace allocation failed");
+    WsCarve c;
+    const size_t o_head = c.take(sizeof(MapHead)), o_id = c.take(4 * 4 * (ni + 1)), o_fr = c.take(4 * 3 * (nf + 1)),
+                 o_cam = c.take(4 * 4 * (nf + 1)), o_tag = c.take(4 * (ni + 1)), o_slot = c.take(4 * nsl), o_obs = c.take(4 * 4 * nsl),
+                 o_csr = c.take(4 * (2 * nsl + nf + ni + 2)), o_W = c.take(8 * 12 * nf), o_G = c.take(8 * 12 * ni);
+    if (d->map_ws.ensure(c.off)) return fail(ASL_ENOMEM, "map workspace allocation failed");
     uint8_t *w = d->map_ws.p;
     MapArgs a{};
     a.obs = (const ObsRec *)d_obs; a.n_frames = n_frames; a.max_tags = max_tags; a.n_ids = n_ids; a.world_req = world_id;
@@ -1402,13 +1417,13 @@ static int launch_map(asl_detector *d, const void *d_obs, int n_frames, int max_
     // the problem-sized part: (camera, tag) table, LM buffers (k_gn.inc's layout)
     const int n = 6 * NT;
     const size_t nc = (size_t)NC, nt = (size_t)NT, nm = (size_t)NM;
-    off = 0;
-    const size_t p_of = take(4 * nc * nt), p_flag = take(8), p_lm = take(8 * 2 * MAP_LM__N), p_Wn = take(8 * 12 * nc), p_Gn = take(8 * 12 * nt),
-                 p_D = take(8 * GN_DSTRIDE * nm), p_Dn = take(8 * GN_DSTRIDE * nm), p_co = take(8 * nm), p_so = take(8 * nm),
-                 p_Hi = take(8 * 36 * nc), p_gc = take(8 * 6 * nc), p_T = take(8 * 36 * nm), p_S = take(8 * (size_t)(n + 1) * n), p_rhs = take(8 * n),
-                 p_Li = take(8 * (size_t)((n + GN_NB - 1) / GN_NB) * GN_NB * GN_NB), p_var = take(8 * n),
-                 p_lcp = take(4 * (nc + 1)), p_ltp = take(4 * (nt + 1));
-    if (d->map_lm.ensure(off)) return fail(ASL_ENOMEM, "map workspace allocation failed");
+    WsCarve p;
+    const size_t p_of = p.take(4 * nc * nt), p_flag = p.take(8), p_lm = p.take(8 * 2 * MAP_LM__N), p_Wn = p.take(8 * 12 * nc),
+                 p_Gn = p.take(8 * 12 * nt), p_D = p.take(8 * GN_DSTRIDE * nm), p_Dn = p.take(8 * GN_DSTRIDE * nm), p_co = p.take(8 * nm),
+                 p_so = p.take(8 * nm), p_Hi = p.take(8 * 36 * nc), p_gc = p.take(8 * 6 * nc), p_T = p.take(8 * 36 * nm),
+                 p_S = p.take(8 * (size_t)(n + 1) * n), p_rhs = p.take(8 * n), p_Li = p.take(8 * (size_t)((n + GN_NB - 1) / GN_NB) * GN_NB * GN_NB),
+                 p_var = p.take(8 * n), p_lcp = p.take(4 * (nc + 1)), p_ltp = p.take(4 * (nt + 1));
+    if (d->map_lm.ensure(p.off)) return fail(ASL_ENOMEM, "map workspace allocation failed");
     uint8_t *v = d->map_lm.p;
     a.obs_of = (int *)(v + p_of);
     int *flag = (int *)(v + p_flag);
@@ -1445,30 +1460,12 @@ static int launch_map(asl_detector *d, const void *d_obs, int n_frames, int max_
     HIPCHK(hipMemcpyAsync(seed_obs, cost_obs, 8 * nm, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(lcp, a.cam_ptr, 4 * (nc + 1), hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(ltp, a.tag_ptr, 4 * (nt + 1), hipMemcpyDeviceToDevice, st));
-    // reduced system, factorisation, solve (k_gn.inc, unchanged); lmp: the lambda the damping reads
-    auto factor = [&](const double *lmp, int *fl, const int *cptr, const int *tptr) {
-        hipLaunchKernelGGL(k_gn_reduce_cam, dim3(NC), dim3(64), 0, st, Dc, cptr, a.cam_obs, NC, lmp, Hinv, gc, Tfj);
-        hipLaunchKernelGGL(k_gn_schur, dim3(NT, NT), dim3(64), 0, st, Dc, Tfj, Hinv, gc, tptr, a.tag_obs, a.obs_cam, a.obs_of, NC, NT, WT, lmp,
-                           S, rhs);
-        HIPCHK(hipMemcpyAsync(S + (size_t)n * n, rhs, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
-        for (int k0 = 0; k0 < n; k0 += GN_NB) {
-            const int nb = std::min(GN_NB, n - k0), rem = n + 1 - k0 - nb;
-            hipLaunchKernelGGL(k_gn_chol_diag, dim3(1), dim3(64), 0, st, S, n, k0, nb, fl, Linv);
-            hipLaunchKernelGGL(k_gn_chol_panel, dim3((rem + 15) / 16), dim3(256), 0, st, S, n, n + 1, k0, nb);
-            if (rem > 1) {
-                const unsigned int tiles = (unsigned int)((rem + GN_NB - 1) / GN_NB);
-                hipLaunchKernelGGL(k_gn_chol_update, dim3(tiles, tiles), dim3(256), 0, st, S, n, n + 1, k0, nb);
-            }
-        }
-        return ASL_OK;
-    };
+    // reduced system, factorisation, step (gn_host.inc) over the LM's copies of the list offsets
+    const GnSystem sys = {Dc, lcp, a.cam_obs, ltp, a.tag_obs, a.obs_cam, a.obs_tag, a.obs_of, NC, NT, WT, Hinv, gc, Tfj, S, rhs, Linv};
     const size_t nw = 12 * nc, ng = 12 * nt, nd = (size_t)GN_DSTRIDE * nm;
     for (int it = 0; it < max_iters; it++) {
-        int rc = factor(lm, flag, lcp, ltp);
+        int rc = gn_factor_step(sys, lm, flag, st, Wc, Gc, Wt, Gt);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_gn_trisolve, dim3(1), dim3(GN_TRI_THREADS), (size_t)n * sizeof(double), st, S, Linv, rhs, n);
-        hipLaunchKernelGGL(k_gn_update, dim3((NC + NT + 63) / 64), dim3(64), 0, st, Dc, Hinv, gc, lcp, a.cam_obs, a.obs_tag, rhs, NC, NT,
-                           Wc, Gc, Wt, Gt);
         hipLaunchKernelGGL(k_map_linearize, dim3(lin_blocks), dim3(256), 0, st, a, Wt, Gt, NM, cam, Dt, cost_obs, lm, 0);
         hipLaunchKernelGGL(k_gn_cost, dim3(1), dim3(256), 0, st, cost_obs, NM, lm + GN_LM_TRIAL);
         hipLaunchKernelGGL(k_map_decide, dim3(1), dim3(1), 0, st, lm, flag);
@@ -1480,7 +1477,10 @@ static int launch_map(asl_detector *d, const void *d_obs, int n_frames, int max_
     hipLaunchKernelGGL(k_map_linearize, dim3(lin_blocks), dim3(256), 0, st, a, Wc, Gc, NM, cam, Dc, cost_obs, lm, 1);
     range_pop();
     if (d_std) {
-        int rc = factor(lm0, flag + 1, a.cam_ptr, a.tag_ptr);  // undamped
+        GnSystem full = sys;  // undamped, over every active observation
+        full.cam_ptr = a.cam_ptr;
+        full.tag_ptr = a.tag_ptr;
+        int rc = gn_factor_step(full, lm0, flag + 1, st);
         if (rc) return rc;
         hipLaunchKernelGGL(k_map_std, dim3(n), dim3(256), (size_t)n * sizeof(double), st, S, Linv, n, var);
     }
@@ -1511,13 +1511,11 @@ extern "C" int asl_map_batch(asl_detector *d, const asl_obs *obs, int n_frames, 
     int rc = check_map_args(obs, n_frames, max_tags, n_ids, K, dist, n_dist, tag_size, world_id, max_iters, map, poses, result);
     if (rc) return rc;
     HIPCHK(hipSetDevice(d->device));
-    const size_t obs_bytes = sizeof(asl_obs) * (size_t)n_frames * (size_t)max_tags, res_bytes = 256,
-                 map_bytes = ((sizeof(asl_map_tag) * (size_t)n_ids + 255) & ~(size_t)255), std_bytes = ((48 * (size_t)n_ids + 255) & ~(size_t)255),
-                 out_bytes = sizeof(asl_cam_pose) * (size_t)n_frames;
-    if (d->loc_obs.ensure(obs_bytes) || d->map_out.ensure(res_bytes + map_bytes + std_bytes + out_bytes))
-        return fail(ASL_ENOMEM, "map workspace allocation failed");
+    const size_t res_bytes = 256, map_bytes = ((sizeof(asl_map_tag) * (size_t)n_ids + 255) & ~(size_t)255),
+                 std_bytes = ((48 * (size_t)n_ids + 255) & ~(size_t)255), out_bytes = sizeof(asl_cam_pose) * (size_t)n_frames;
+    if (d->map_out.ensure(res_bytes + map_bytes + std_bytes + out_bytes)) return fail(ASL_ENOMEM, "map workspace allocation failed");
+    if ((rc = upload_obs(d, "map", obs, n_frames, max_tags, nullptr, n_ids))) return rc;
     uint8_t *o = d->map_out.p;
-    HIPCHK(hipMemcpy(d->loc_obs.p, obs, obs_bytes, hipMemcpyHostToDevice));
     rc = launch_map(d, d->loc_obs.p, n_frames, max_tags, n_ids, K, dist, n_dist, tag_size, world_id, max_iters, o + res_bytes,
                     tag_std ? o + res_bytes + map_bytes : nullptr, o + res_bytes + map_bytes + std_bytes, o, nullptr);
     if (rc) return rc;
@@ -1528,4 +1526,3 @@ extern "C" int asl_map_batch(asl_detector *d, const asl_obs *obs, int n_frames, 
     return ASL_OK;
 }
 
-#include "gn_host.inc"

@@ -1,4 +1,40 @@
-// Host loop of the pose-graph Levenberg-Marquardt back-end (kernels: k_gn.inc).
+// Host loop of the pose-graph Levenberg-Marquardt back-end (kernels: k_gn.inc), and the reduced-system sequence the map
+// solver (k_map.inc) shares with it.
+
+// One problem's reduced system on the device: observation blocks D, the active lists and (camera, tag) table, scratch
+struct GnSystem {
+    const double *D;
+    const int *cam_ptr, *cam_obs, *tag_ptr, *tag_obs, *obs_cam, *obs_tag, *obs_of;
+    int n_cams, n_tags, fixed_tag;
+    double *Hinv, *gc, *Tfj, *S, *rhs, *Linv;
+};
+
+// Enqueued on st: the cameras eliminated and the Schur complement over the tags (damping: lm[GN_LM_LAMBDA]), its blocked
+// Cholesky with the right-hand side carried as row n (fail set if it is not positive definite); with Wn, also the step:
+// the triangular solves and the trial poses (Wn, Gn) from (W, G)
+static int gn_factor_step(const GnSystem &g, const double *lm, int *fail_flag, hipStream_t st, const double *W = nullptr,
+                          const double *G = nullptr, double *Wn = nullptr, double *Gn = nullptr)
+{
+    const int n = 6 * g.n_tags;
+    hipLaunchKernelGGL(k_gn_reduce_cam, dim3(g.n_cams), dim3(64), 0, st, g.D, g.cam_ptr, g.cam_obs, g.n_cams, lm, g.Hinv, g.gc, g.Tfj);
+    hipLaunchKernelGGL(k_gn_schur, dim3(g.n_tags, g.n_tags), dim3(64), 0, st, g.D, g.Tfj, g.Hinv, g.gc, g.tag_ptr, g.tag_obs, g.obs_cam,
+                       g.obs_of, g.n_cams, g.n_tags, g.fixed_tag, lm, g.S, g.rhs);
+    HIPCHK(hipMemcpyAsync(g.S + (size_t)n * n, g.rhs, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+    for (int k0 = 0; k0 < n; k0 += GN_NB) {
+        const int nb = std::min(GN_NB, n - k0), rem = n + 1 - k0 - nb;  // rows below the block, including row n
+        hipLaunchKernelGGL(k_gn_chol_diag, dim3(1), dim3(64), 0, st, g.S, n, k0, nb, fail_flag, g.Linv);
+        hipLaunchKernelGGL(k_gn_chol_panel, dim3((rem + 15) / 16), dim3(256), 0, st, g.S, n, n + 1, k0, nb);
+        if (rem > 1) {
+            const unsigned int tiles = (unsigned int)((rem + GN_NB - 1) / GN_NB);
+            hipLaunchKernelGGL(k_gn_chol_update, dim3(tiles, tiles), dim3(256), 0, st, g.S, n, n + 1, k0, nb);
+        }
+    }
+    if (!Wn) return ASL_OK;
+    hipLaunchKernelGGL(k_gn_trisolve, dim3(1), dim3(GN_TRI_THREADS), (size_t)n * sizeof(double), st, g.S, g.Linv, g.rhs, n);
+    hipLaunchKernelGGL(k_gn_update, dim3((g.n_cams + g.n_tags + 63) / 64), dim3(64), 0, st, g.D, g.Hinv, g.gc, g.cam_ptr, g.cam_obs,
+                       g.obs_tag, g.rhs, g.n_cams, g.n_tags, W, G, Wn, Gn);
+    return ASL_OK;
+}
 
 static void gn_rigid_inverse(const double *T, double *W12)
 {
@@ -99,24 +135,11 @@ extern "C" int asl_gn_solve(asl_detector *d, int n_cams, int n_tags, int n_obs, 
     linearize(Wc, Gc, Dc, GN_LM_COST);
     HIPCHK(hipMemcpyAsync(w.cost.p + GN_LM_COST0, w.cost.p + GN_LM_COST, 8, hipMemcpyDeviceToDevice, st));
     const size_t nw = (size_t)12 * n_cams, ng = (size_t)12 * n_tags, nd = (size_t)GN_DSTRIDE * n_obs;
+    const GnSystem sys = {Dc, w.cam_ptr.p, w.cam_obs.p, w.tag_ptr.p, w.tag_obs.p, w.obs_cam.p, w.obs_tag.p, w.obs_of.p, n_cams, n_tags,
+                          fixed_tag, w.Hinv.p, w.gc.p, w.Tfj.p, w.S.p, w.rhs.p, w.Linv.p};
     for (int it = 0; it < iters; it++) {
-        hipLaunchKernelGGL(k_gn_reduce_cam, dim3(n_cams), dim3(64), 0, st, Dc, w.cam_ptr.p, w.cam_obs.p, n_cams, w.cost.p, w.Hinv.p,
-                           w.gc.p, w.Tfj.p);
-        hipLaunchKernelGGL(k_gn_schur, dim3(n_tags, n_tags), dim3(64), 0, st, Dc, w.Tfj.p, w.Hinv.p, w.gc.p, w.tag_ptr.p, w.tag_obs.p,
-                           w.obs_cam.p, w.obs_of.p, n_cams, n_tags, fixed_tag, w.cost.p, w.S.p, w.rhs.p);
-        HIPCHK(hipMemcpyAsync(w.S.p + (size_t)n * n, w.rhs.p, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
-        for (int k0 = 0; k0 < n; k0 += GN_NB) {
-            const int nb = std::min(GN_NB, n - k0), rem = n + 1 - k0 - nb;  // rows below the block, including row n
-            hipLaunchKernelGGL(k_gn_chol_diag, dim3(1), dim3(64), 0, st, w.S.p, n, k0, nb, w.flag.p, w.Linv.p);
-            hipLaunchKernelGGL(k_gn_chol_panel, dim3((rem + 15) / 16), dim3(256), 0, st, w.S.p, n, n + 1, k0, nb);
-            if (rem > 1) {
-                const unsigned int tiles = (unsigned int)((rem + GN_NB - 1) / GN_NB);
-                hipLaunchKernelGGL(k_gn_chol_update, dim3(tiles, tiles), dim3(256), 0, st, w.S.p, n, n + 1, k0, nb);
-            }
-        }
-        hipLaunchKernelGGL(k_gn_trisolve, dim3(1), dim3(GN_TRI_THREADS), (size_t)n * sizeof(double), st, w.S.p, w.Linv.p, w.rhs.p, n);
-        hipLaunchKernelGGL(k_gn_update, dim3((n_cams + n_tags + 63) / 64), dim3(64), 0, st, Dc, w.Hinv.p, w.gc.p, w.cam_ptr.p, w.cam_obs.p,
-                           w.obs_tag.p, w.rhs.p, n_cams, n_tags, Wc, Gc, Wt, Gt);
+        int rc = gn_factor_step(sys, w.cost.p, w.flag.p, st, Wc, Gc, Wt, Gt);
+        if (rc) return rc;
         linearize(Wt, Gt, Dt, GN_LM_TRIAL);
         hipLaunchKernelGGL(k_gn_decide, dim3(1), dim3(1), 0, st, w.cost.p);
         hipLaunchKernelGGL(k_gn_commit, dim3((unsigned int)std::min<size_t>((nw + ng + nd + 255) / 256, 1024)), dim3(256), 0, st, w.cost.p, Wt, Gt, Dt, Wc, Gc, Dc,

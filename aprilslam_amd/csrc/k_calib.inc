@@ -5,7 +5,7 @@
 //                   (Zhang's two constraints per tag from its square -> quad homography, divided by |h1| |h2|)
 //   k_calib_k0      one workgroup: the list of taking-part frames (>= 2 mapped slots), K0 (closed form or K_init)
 //   k_calib_seed    per frame: planar pose of the <= 8 largest tags under K0 and its mirrored minimum, composed with the map
-//                   and scored over all corners, pose-only LM (k_localize.inc: loc_candidate, loc_pass, loc_lm); then the
+//                   and scored over all corners, pose-only LM (k_localize.inc: loc_candidate, loc_pass, pose_lm); then the
 //                   frame's normal equations at (K0, no distortion, that pose)
 //   k_calib_start   one workgroup: the list of used frames, the cost, lambda0
 //   then max_iters times (joint Levenberg-Marquardt, the arrow-shaped normal equations reduced by the Schur complement):
@@ -60,37 +60,11 @@ struct CalibArgs {
 
 __device__ __forceinline__ int cal_nt(int n_dist) { return 11 + n_dist; }  // 6 pose + 4 + n_dist theta + residual
 
-// Gather of one frame into LDS (k_localize's layout): world corners, image corners, state 1 for a taking-part slot and
-// its corner area; returns the number of taking-part slots (identical in every lane)
-__device__ __forceinline__ int cal_gather(const CalibArgs &a, int f, int lane, double *s_X, float *s_uv, double *s_area, int *s_state)
+// Gather of one frame into LDS (k_localize.inc: loc_gather), every taking-part slot seeding; returns the number of
+// taking-part slots (identical in every lane)
+__device__ __forceinline__ int cal_gather(const CalibArgs &a, int f, int lane, const LocLds &L)
 {
-    const ObsRec *fo = a.obs + (size_t)f * a.max_tags;
-    int npart = 0;
-    for (int s = lane; s < a.max_tags; s += ASL_WAVE) {
-        const int id = fo[s].id, fl = fo[s].flags;
-        const bool part = (fl & 1) && id >= 0 && id < a.n_ids && a.map[id].valid;
-        s_state[s] = part ? 1 : 0;
-        s_area[s] = -1.0;
-        if (!part) continue;
-        npart++;
-        const double *M = a.map[id].T;
-        float cf[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) cf[k] = fo[s].corners[k];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const double ox = (q == 1 || q == 2) ? a.half : -a.half, oy = (q >= 2) ? a.half : -a.half;
-#pragma unroll
-            for (int r = 0; r < 3; r++) s_X[3 * (4 * s + q) + r] = M[4 * r] * ox + M[4 * r + 1] * oy + M[4 * r + 3];
-            s_uv[2 * (4 * s + q)] = cf[2 * q];
-            s_uv[2 * (4 * s + q) + 1] = cf[2 * q + 1];
-        }
-        const double x0 = cf[0], y0 = cf[1], x1 = cf[2], y1 = cf[3], x2 = cf[4], y2 = cf[5], x3 = cf[6], y3 = cf[7];
-        const double ar = (x0 * y1 - x1 * y0) + (x1 * y2 - x2 * y1) + (x2 * y3 - x3 * y2) + (x3 * y0 - x0 * y3);
-        s_area[s] = 0.5 * fabs(ar);
-    }
-    __syncthreads();
-    return wave_sum_i32(npart);
+    return loc_gather(a.obs + (size_t)f * a.max_tags, a.max_tags, a.map, a.n_ids, a.half, [](int) { return true; }, L, lane);
 }
 
 // Homography (row-major 3x3) of the square (+-1, +-1), lb rb rt lt, onto the corners in x' = (u - cx) / s: the closed-form
@@ -190,17 +164,17 @@ __device__ __forceinline__ bool cal_rows(const CamDev &c, bool fix_aspect, doubl
 // Entries [LO, HI) of the frame's packed augmented normal equations, summed over its corners and written to Hf.  The
 // triangle is built in chunks so that the accumulators stay in registers (the corner's rows are recomputed per chunk).
 template <int NT, int LO, int HI>
-__device__ __forceinline__ void cal_chunk(const CamDev &c, bool fa, double ratio, const double *R, const double *t, const double *s_X,
-                                          const float *s_uv, const int *s_state, int n4, int lane, double *Hf)
+__device__ __forceinline__ void cal_chunk(const CamDev &c, bool fa, double ratio, const double *R, const double *t, const LocLds &L, int n4,
+                                          int lane, double *Hf)
 {
     constexpr int NTRI = NT * (NT + 1) / 2;
     double acc[HI - LO], behind = 0;
 #pragma unroll
     for (int i = 0; i < HI - LO; i++) acc[i] = 0;
     for (int k = lane; k < n4; k += ASL_WAVE) {
-        if (s_state[k >> 2] != 1) continue;
+        if (L.state[k >> 2] != 1) continue;
         double J0[NT], J1[NT];
-        if (!cal_rows<NT>(c, fa, ratio, R, t, s_X + 3 * k, (double)s_uv[2 * k], (double)s_uv[2 * k + 1], J0, J1)) {
+        if (!cal_rows<NT>(c, fa, ratio, R, t, L.X + 3 * k, (double)L.uv[2 * k], (double)L.uv[2 * k + 1], J0, J1)) {
             behind += LOC_BEHIND_COST;
             continue;
         }
@@ -221,14 +195,14 @@ __device__ __forceinline__ void cal_chunk(const CamDev &c, bool fa, double ratio
 }
 
 template <int NT>
-__device__ __forceinline__ void cal_linearise(const CamDev &c, bool fa, double ratio, const double *R, const double *t, const double *s_X,
-                                              const float *s_uv, const int *s_state, int n4, int lane, double *Hf)
+__device__ __forceinline__ void cal_linearise(const CamDev &c, bool fa, double ratio, const double *R, const double *t, const LocLds &L, int n4,
+                                              int lane, double *Hf)
 {
     constexpr int NTRI = NT * (NT + 1) / 2, C = (NTRI + 3) / 4;
-    cal_chunk<NT, 0, C>(c, fa, ratio, R, t, s_X, s_uv, s_state, n4, lane, Hf);
-    cal_chunk<NT, C, 2 * C>(c, fa, ratio, R, t, s_X, s_uv, s_state, n4, lane, Hf);
-    cal_chunk<NT, 2 * C, 3 * C>(c, fa, ratio, R, t, s_X, s_uv, s_state, n4, lane, Hf);
-    cal_chunk<NT, 3 * C, NTRI>(c, fa, ratio, R, t, s_X, s_uv, s_state, n4, lane, Hf);
+    cal_chunk<NT, 0, C>(c, fa, ratio, R, t, L, n4, lane, Hf);
+    cal_chunk<NT, C, 2 * C>(c, fa, ratio, R, t, L, n4, lane, Hf);
+    cal_chunk<NT, 2 * C, 3 * C>(c, fa, ratio, R, t, L, n4, lane, Hf);
+    cal_chunk<NT, 3 * C, NTRI>(c, fa, ratio, R, t, L, n4, lane, Hf);
 }
 
 // Sum over the list of frames of rows[f * stride + e] for e < ne (<= 64), by a CAL_WG workgroup: CAL_CHUNKS contiguous chunks
@@ -402,70 +376,38 @@ __global__ void __launch_bounds__(64) k_calib_seed(CalibArgs a)
     extern __shared__ double s_dyn[];
     const int f = blockIdx.x, lane = threadIdx.x, n4 = 4 * a.max_tags;
     if (a.st->status != 0 || a.fr[CAL_FR * f] != 0) return;
-    double *s_X = s_dyn;
-    double *s_area = s_X + 3 * n4;
-    float *s_uv = (float *)(s_area + a.max_tags);
-    int *s_state = (int *)(s_uv + 2 * n4);
-    cal_gather(a, f, lane, s_X, s_uv, s_area, s_state);
+    const LocLds L = loc_lds(s_dyn, a.max_tags);
+    cal_gather(a, f, lane, L);
     const ObsRec *fo = a.obs + (size_t)f * a.max_tags;
     double th[9];
 #pragma unroll
     for (int i = 0; i < 9; i++) th[i] = a.st->theta[0][i];
     const CamDev cam0 = cal_cam(th, 0, a.half);
     const double s = 0.5 * (a.width + a.height);
+    auto pass = [&](const double *R, const double *t, auto ne_tag, double *ne) {
+        return loc_pass<decltype(ne_tag)::value>(cam0, R, t, L, n4, lane, ne);
+    };
 
     // the <= 8 taking-part slots of largest area (ties: lower slot), then every candidate in slot order, plain before mirrored
     int sel[LOC_MAX_SEEDS];
-    int nsel = 0;
-#pragma unroll
-    for (int r = 0; r < LOC_MAX_SEEDS; r++) {
-        double ba = -1.0;
-        int bs = 0x7fffffff;
-        for (int k = lane; k < a.max_tags; k += ASL_WAVE)
-            if (s_area[k] > ba) { ba = s_area[k]; bs = k; }
-        argmax_step<1>(ba, bs); argmax_step<2>(ba, bs); argmax_step<4>(ba, bs);
-        argmax_step<8>(ba, bs); argmax_step<16>(ba, bs); argmax_step<32>(ba, bs);
-        sel[r] = ba >= 0 ? bs : 0x7fffffff;
-        if (ba >= 0) nsel++;
-        __syncthreads();
-        if (lane == 0 && ba >= 0) s_area[bs] = -1.0;
-        __syncthreads();
-    }
-    double R[9], t[3], best = INFINITY;
-    int code = -1, prev = -1;
-    for (int j = 0; j < nsel; j++) {
-        int k = 0x7fffffff;
-#pragma unroll
-        for (int r = 0; r < LOC_MAX_SEEDS; r++)
-            if (sel[r] > prev && sel[r] < k) k = sel[r];
-        prev = k;
-        float cf[8];
-#pragma unroll
-        for (int q = 0; q < 8; q++) cf[q] = fo[k].corners[q];
+    const int nsel = loc_top_k(a.max_tags, lane, [&](int k) { return L.area[k]; }, sel);
+    auto make = [&](int k) {
         double H[9], To[12], M[12];
-        cal_square_h(cf, th[2], th[3], s, H);
+        cal_square_h(fo[k].corners, th[2], th[3], s, H);
         cal_planar_pose(H, th[0], th[1], s, a.half, To);
         const double *Mp = a.map[fo[k].id].T;
 #pragma unroll
         for (int i = 0; i < 12; i++) M[i] = Mp[i];
-        for (int m = 0; m < 2; m++) {
-            double Rc[9], tc[3];
-            loc_candidate(To, M, m == 1, Rc, tc);
-            const double cc = loc_pass<false>(cam0, Rc, tc, s_X, s_uv, s_state, n4, lane, nullptr);
-            if (cc < best) {
-                best = cc;
-                code = k + LOC_MIRRORED * m;
-#pragma unroll
-                for (int i = 0; i < 9; i++) R[i] = Rc[i];
-                t[0] = tc[0]; t[1] = tc[1]; t[2] = tc[2];
-            }
-        }
-    }
+        return [=](bool mirror, double *C) { loc_candidate(To, M, mirror, C, C + 9); };
+    };
+    double Pb[12], best = INFINITY;
+    const int code = loc_best_candidate(sel, nsel, make, [&](const double *C) { return pass(C, C + 9, std::false_type{}, nullptr); }, best, Pb);
     if (!(best < LOC_BEHIND_COST)) {
         if (lane == 0) a.fr[CAL_FR * f] = 3;
         return;
     }
-    const double cost = loc_lm(cam0, R, t, s_X, s_uv, s_state, n4, lane);
+    double *R = Pb, *t = Pb + 9;
+    const double cost = pose_lm(pass, R, t);
     double *P = a.pose + (size_t)12 * f;  // buffer 0: cur = 0 at the start
     if (lane == 0) {
 #pragma unroll
@@ -474,7 +416,7 @@ __global__ void __launch_bounds__(64) k_calib_seed(CalibArgs a)
         a.seedc[f] = cost;
         a.fr[CAL_FR * f + 2] = code;
     }
-    cal_linearise<NT>(cam0, (a.flags & CAL_FIX_ASPECT) != 0, a.st->ratio, R, t, s_X, s_uv, s_state, n4, lane, a.H + (size_t)CAL_HS * f);
+    cal_linearise<NT>(cam0, (a.flags & CAL_FIX_ASPECT) != 0, a.st->ratio, R, t, L, n4, lane, a.H + (size_t)CAL_HS * f);
 }
 
 // ---- one workgroup: used frames, initial cost, lambda0
@@ -621,14 +563,10 @@ __global__ void __launch_bounds__(64) k_calib_step(CalibArgs a)
         for (int i = 0; i < 9; i++) Pn[i] = R[i];
         Pn[9] = t[0]; Pn[10] = t[1]; Pn[11] = t[2];
     }
-    double *s_X = s_dyn;
-    double *s_area = s_X + 3 * n4;
-    float *s_uv = (float *)(s_area + a.max_tags);
-    int *s_state = (int *)(s_uv + 2 * n4);
-    cal_gather(a, f, lane, s_X, s_uv, s_area, s_state);
+    const LocLds L = loc_lds(s_dyn, a.max_tags);
+    cal_gather(a, f, lane, L);
     const CamDev c = cal_cam(st->theta[1 - cur], ND, a.half);
-    cal_linearise<NT>(c, (a.flags & CAL_FIX_ASPECT) != 0, st->ratio, R, t, s_X, s_uv, s_state, n4, lane,
-                      a.H + ((size_t)(1 - cur) * a.n_frames + f) * CAL_HS);
+    cal_linearise<NT>(c, (a.flags & CAL_FIX_ASPECT) != 0, st->ratio, R, t, L, n4, lane, a.H + ((size_t)(1 - cur) * a.n_frames + f) * CAL_HS);
 }
 
 // ---- one workgroup: accept or reject the trial

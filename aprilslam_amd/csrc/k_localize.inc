@@ -96,17 +96,143 @@ __device__ __forceinline__ double loc_corner(const CamDev &c, const double *R, c
     return r0 * r0 + r1 * r1;
 }
 
+// LDS of one frame (dynamic): world corners double[3 * n4], slot area double[max_tags], image corners float[2 * n4],
+// slot state int[max_tags] (0 out, 1 taking part, 2 dropped by the gate)
+struct LocLds {
+    double *X, *area;
+    float *uv;
+    int *state;
+};
+
+__host__ __device__ constexpr size_t loc_lds_bytes(int max_tags)
+{
+    return (size_t)max_tags * (4 * 3 * sizeof(double) + 4 * 2 * sizeof(float) + sizeof(double) + sizeof(int));
+}
+
+__device__ __forceinline__ LocLds loc_lds(double *s_dyn, int max_tags)
+{
+    LocLds L;
+    L.X = s_dyn;
+    L.area = L.X + 12 * max_tags;
+    L.uv = (float *)(L.area + max_tags);
+    L.state = (int *)(L.uv + 8 * max_tags);
+    return L;
+}
+
+// Shoelace area of a slot's 8 float corners, in this order of operations (tests/localize_ref.py: corner_area)
+__device__ __forceinline__ double loc_area(const float *cf)
+{
+    const double x0 = cf[0], y0 = cf[1], x1 = cf[2], y1 = cf[3], x2 = cf[4], y2 = cf[5], x3 = cf[6], y3 = cf[7];
+    const double a = (x0 * y1 - x1 * y0) + (x1 * y2 - x2 * y1) + (x2 * y3 - x3 * y2) + (x3 * y0 - x0 * y3);
+    return 0.5 * fabs(a);
+}
+
+// Slot s into L: its 4 world corners (object corners +-half, lb rb rt lt, through the 3x4 world<-tag M) and 4 image corners
+__device__ __forceinline__ void loc_gather_slot(const LocLds &L, int s, const double *M, double half, const float *cf)
+{
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const double ox = (q == 1 || q == 2) ? half : -half, oy = (q >= 2) ? half : -half;
+#pragma unroll
+        for (int r = 0; r < 3; r++) L.X[3 * (4 * s + q) + r] = M[4 * r] * ox + M[4 * r + 1] * oy + M[4 * r + 3];
+        L.uv[2 * (4 * s + q)] = cf[2 * q];
+        L.uv[2 * (4 * s + q) + 1] = cf[2 * q + 1];
+    }
+}
+
+// Gather of one frame's max_tags slots against the map: state 1 for a taking-part slot (flags & 1, mapped id), its area
+// if seeds(flags), else -1.  Returns the number of taking-part slots and, with nseed, sets the number of seeding ones,
+// both identical in every lane.
+template <class Seeds>
+__device__ __forceinline__ int loc_gather(const ObsRec *fo, int max_tags, const MapTagRec *map, int n_ids, double half, Seeds seeds,
+                                          const LocLds &L, int lane, int *nseed = nullptr)
+{
+    int npart = 0, ns = 0;
+    for (int s = lane; s < max_tags; s += ASL_WAVE) {
+        const int id = fo[s].id, fl = fo[s].flags;
+        const bool part = (fl & 1) && id >= 0 && id < n_ids && map[id].valid;
+        L.state[s] = part ? 1 : 0;
+        L.area[s] = -1.0;
+        if (!part) continue;
+        npart++;
+        float cf[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) cf[k] = fo[s].corners[k];
+        loc_gather_slot(L, s, map[id].T, half, cf);
+        if (seeds(fl)) {
+            ns++;
+            L.area[s] = loc_area(cf);
+        }
+    }
+    __syncthreads();
+    if (nseed) *nseed = wave_sum_i32(ns);
+    return wave_sum_i32(npart);
+}
+
+// The first K indices of [0, n) in the order (area descending, index ascending), counting only areas >= 0 (a negative or
+// NaN area never takes part), identical in every lane: sel[0..nsel) in that order, 0x7fffffff after; returns nsel.  Each
+// round takes the largest of what the earlier rounds left, so nothing is written and no barrier is needed.
+template <int K, class Area>
+__device__ __forceinline__ int loc_top_k(int n, int lane, Area area, int (&sel)[K])
+{
+    int nsel = 0, pp = -1;
+    double pa = INFINITY;
+#pragma unroll
+    for (int r = 0; r < K; r++) {
+        double ba = -1.0;
+        int bs = 0x7fffffff;
+        for (int i = lane; i < n; i += ASL_WAVE) {  // a lane's indices ascend: a tie keeps the lower one
+            const double ar = area(i);
+            if (ar > ba && (ar < pa || (ar == pa && i > pp))) { ba = ar; bs = i; }  // the second test: not taken already
+        }
+        argmax_step<1>(ba, bs); argmax_step<2>(ba, bs); argmax_step<4>(ba, bs);
+        argmax_step<8>(ba, bs); argmax_step<16>(ba, bs); argmax_step<32>(ba, bs);
+        sel[r] = ba >= 0 ? bs : 0x7fffffff;
+        if (ba >= 0) { nsel++; pa = ba; pp = bs; }
+    }
+    return nsel;
+}
+
+// Every candidate of the chosen indices, in ascending index order, plain before mirrored: make(i) does index i's own work
+// once and returns a callable cand(mirrored, P) that writes the candidate pose P (R row-major 9, t 3); score(P) is its
+// cost.  A cost strictly below best replaces best and Pb; returns the code of the last replacement (index, + LOC_MIRRORED
+// if mirrored), -1 if none.  k_localize has this loop written out (see there).
+template <int K, class Make, class Score>
+__device__ __forceinline__ int loc_best_candidate(const int (&sel)[K], int nsel, Make make, Score score, double &best, double *Pb)
+{
+    int code = -1, prev = -1;
+    for (int j = 0; j < nsel; j++) {
+        int i = 0x7fffffff;
+#pragma unroll
+        for (int r = 0; r < K; r++)
+            if (sel[r] > prev && sel[r] < i) i = sel[r];
+        prev = i;
+        const auto cand = make(i);
+        for (int m = 0; m < 2; m++) {
+            double P[12];
+            cand(m == 1, P);
+            const double c = score(P);
+            if (c < best) {
+                best = c;
+                code = i + LOC_MIRRORED * m;
+#pragma unroll
+                for (int k = 0; k < 12; k++) Pb[k] = P[k];
+            }
+        }
+    }
+    return code;
+}
+
 // Total cost over the frame's active corners (state == 1), identical in every lane; with NE also the normal equations in ne.
 template <bool NE>
-__device__ __forceinline__ double loc_pass(const CamDev &c, const double *R, const double *t, const double *s_X, const float *s_uv, const int *s_state,
-                           int n4, int lane, double *ne)
+__device__ __forceinline__ double loc_pass(const CamDev &c, const double *R, const double *t, const LocLds &L, int n4, int lane, double *ne)
 {
     double cost = 0, acc[27];
 #pragma unroll
     for (int i = 0; i < 27; i++) acc[i] = 0;
     for (int k = lane; k < n4; k += ASL_WAVE) {
-        if (s_state[k >> 2] != 1) continue;
-        cost += loc_corner<NE>(c, R, t, s_X + 3 * k, (double)s_uv[2 * k], (double)s_uv[2 * k + 1], acc);
+        if (L.state[k >> 2] != 1) continue;
+        cost += loc_corner<NE>(c, R, t, L.X + 3 * k, (double)L.uv[2 * k], (double)L.uv[2 * k + 1], acc);
     }
     if constexpr (NE) {
 #pragma unroll
@@ -115,11 +241,14 @@ __device__ __forceinline__ double loc_pass(const CamDev &c, const double *R, con
     return wave_sum_f64(cost);
 }
 
-// The fixed schedule (tests/localize_ref.py: lm): (R, t) camera<-world refined in place; returns the final cost.
-__device__ __forceinline__ double loc_lm(const CamDev &c, double *R, double *t, const double *s_X, const float *s_uv, const int *s_state, int n4, int lane)
+// The fixed schedule (tests/localize_ref.py: lm) on a pose (R, t), refined in place by the left update R <- Rod(w) R,
+// t <- Rod(w) t + v; returns the final cost.  pass(R, t, std::true_type{} / std::false_type{}, ne) returns the cost at
+// (R, t), with true_type also the normal equations (packed lower triangle 21, then J^T r 6) in ne.
+template <class Pass>
+__device__ __forceinline__ double pose_lm(Pass pass, double *R, double *t)
 {
     double ne[27];
-    double cost = loc_pass<true>(c, R, t, s_X, s_uv, s_state, n4, lane, ne);
+    double cost = pass(R, t, std::true_type{}, ne);
     double lambda = 1e-3;
     for (int it = 0; it < LOC_LM_ITERS; it++) {
         double A[21], d[6];
@@ -133,7 +262,7 @@ __device__ __forceinline__ double loc_lm(const CamDev &c, double *R, double *t, 
         mat3_mul_dev(dR, R, Rn);
 #pragma unroll
         for (int r = 0; r < 3; r++) tn[r] = dR[3 * r] * t[0] + dR[3 * r + 1] * t[1] + dR[3 * r + 2] * t[2] + d[3 + r];
-        const double cn = loc_pass<false>(c, Rn, tn, s_X, s_uv, s_state, n4, lane, nullptr);
+        const double cn = pass(Rn, tn, std::false_type{}, nullptr);
         if (cn < cost) {
             const bool stop = cost - cn < 1e-12 * cost;
 #pragma unroll
@@ -142,7 +271,7 @@ __device__ __forceinline__ double loc_lm(const CamDev &c, double *R, double *t, 
             cost = cn;
             lambda *= 0.1;
             if (stop) break;
-            cost = loc_pass<true>(c, R, t, s_X, s_uv, s_state, n4, lane, ne);
+            cost = pass(R, t, std::true_type{}, ne);
         } else
             lambda *= 10;
     }
@@ -175,13 +304,6 @@ __device__ __forceinline__ void loc_candidate(const double *To, const double *M,
     for (int i = 0; i < 3; i++) t[i] = to[i] - (R[3 * i] * M[3] + R[3 * i + 1] * M[7] + R[3 * i + 2] * M[11]);
 }
 
-// LDS of one frame (dynamic): world corners double[3 * n4], image corners float[2 * n4], slot area double[max_tags],
-// slot state int[max_tags] (0 out, 1 taking part, 2 dropped by the gate)
-__host__ __device__ constexpr size_t loc_lds_bytes(int max_tags)
-{
-    return (size_t)max_tags * (4 * 3 * sizeof(double) + 4 * 2 * sizeof(float) + sizeof(double) + sizeof(int));
-}
-
 // status 1 (no taking-part slot) / 2 (no candidate): identity pose, nothing used
 __device__ __forceinline__ void loc_write_none(CamPoseRec *o, int status)
 {
@@ -195,44 +317,16 @@ __global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs,
 {
     extern __shared__ double s_dyn[];
     const int n4 = 4 * max_tags, lane = threadIdx.x;
-    double *s_X = s_dyn;
-    double *s_area = s_X + 3 * n4;
-    float *s_uv = (float *)(s_area + max_tags);
-    int *s_state = (int *)(s_uv + 2 * n4);
+    const LocLds L = loc_lds(s_dyn, max_tags);
     const ObsRec *fo = obs + (size_t)blockIdx.x * max_tags;
     CamPoseRec *o = out + blockIdx.x;
+    auto pass = [&](const double *R, const double *t, auto ne_tag, double *ne) {
+        return loc_pass<decltype(ne_tag)::value>(cam, R, t, L, n4, lane, ne);
+    };
 
     // 1: gather
-    int npart = 0, nseed = 0;
-    for (int s = lane; s < max_tags; s += ASL_WAVE) {
-        const int id = fo[s].id, fl = fo[s].flags;
-        const bool part = (fl & 1) && id >= 0 && id < n_ids && map[id].valid;
-        s_state[s] = part ? 1 : 0;
-        s_area[s] = -1.0;
-        if (!part) continue;
-        npart++;
-        const double *M = map[id].T;
-        float cf[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) cf[k] = fo[s].corners[k];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const double ox = (q == 1 || q == 2) ? cam.half : -cam.half, oy = (q >= 2) ? cam.half : -cam.half;
-#pragma unroll
-            for (int r = 0; r < 3; r++) s_X[3 * (4 * s + q) + r] = M[4 * r] * ox + M[4 * r + 1] * oy + M[4 * r + 3];
-            s_uv[2 * (4 * s + q)] = cf[2 * q];
-            s_uv[2 * (4 * s + q) + 1] = cf[2 * q + 1];
-        }
-        if (fl & 2) {
-            nseed++;
-            const double x0 = cf[0], y0 = cf[1], x1 = cf[2], y1 = cf[3], x2 = cf[4], y2 = cf[5], x3 = cf[6], y3 = cf[7];
-            const double a = (x0 * y1 - x1 * y0) + (x1 * y2 - x2 * y1) + (x2 * y3 - x3 * y2) + (x3 * y0 - x0 * y3);
-            s_area[s] = 0.5 * fabs(a);
-        }
-    }
-    __syncthreads();
-    npart = wave_sum_i32(npart);
-    nseed = wave_sum_i32(nseed);
+    int nseed;
+    const int npart = loc_gather(fo, max_tags, map, n_ids, cam.half, [](int fl) { return (fl & 2) != 0; }, L, lane, &nseed);
     if (npart == 0 || nseed == 0) {
         if (lane == 0) loc_write_none(o, npart == 0 ? 1 : 2);
         return;
@@ -240,21 +334,10 @@ __global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs,
 
     // 2: the seeding slots of largest area (ties: lower slot), then every candidate in slot order, plain before mirrored
     int sel[LOC_MAX_SEEDS];
-    int nsel = 0;
-#pragma unroll
-    for (int r = 0; r < LOC_MAX_SEEDS; r++) {
-        double ba = -1.0;
-        int bs = 0x7fffffff;
-        for (int s = lane; s < max_tags; s += ASL_WAVE)
-            if (s_area[s] > ba) { ba = s_area[s]; bs = s; }  // a lane's slots ascend: a tie keeps the lower one
-        argmax_step<1>(ba, bs); argmax_step<2>(ba, bs); argmax_step<4>(ba, bs);
-        argmax_step<8>(ba, bs); argmax_step<16>(ba, bs); argmax_step<32>(ba, bs);
-        sel[r] = ba >= 0 ? bs : 0x7fffffff;
-        if (ba >= 0) nsel++;
-        __syncthreads();
-        if (lane == 0 && ba >= 0) s_area[bs] = -1.0;
-        __syncthreads();
-    }
+    const int nsel = loc_top_k(max_tags, lane, [&](int s) { return L.area[s]; }, sel);
+    // loc_best_candidate's loop, written out: through the helper this kernel measured 5 % slower (tools/localize_lab.py,
+    // interleaved runs; about 2 % when the winner is rebuilt instead of copied), with the same instructions but for the
+    // copy of the best pose and the layout.  A change to the candidate rule goes into both.
     double R[9], t[3], best = INFINITY;
     int code = -1, prev = -1;
     for (int j = 0; j < nsel; j++) {
@@ -270,7 +353,7 @@ __global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs,
         for (int m = 0; m < 2; m++) {
             double Rc[9], tc[3];
             loc_candidate(To, M, m == 1, Rc, tc);
-            const double cc = loc_pass<false>(cam, Rc, tc, s_X, s_uv, s_state, n4, lane, nullptr);
+            const double cc = pass(Rc, tc, std::false_type{}, nullptr);
             if (cc < best) {
                 best = cc;
                 code = s + LOC_MIRRORED * m;
@@ -286,7 +369,7 @@ __global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs,
     }
 
     // 3: refine
-    double cost = loc_lm(cam, R, t, s_X, s_uv, s_state, n4, lane);
+    double cost = pose_lm(pass, R, t);
 
     // 4: the gate, one slot at a time: the worst slot over the gate goes, and the solve runs again from the current pose
     int nused = npart, nrej = 0;
@@ -295,12 +378,12 @@ __global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs,
             double wr = -1.0;
             int ws = 0x7fffffff;
             for (int s = lane; s < max_tags; s += ASL_WAVE) {
-                if (s_state[s] != 1) continue;
+                if (L.state[s] != 1) continue;
                 double e[4];
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     const int k = 4 * s + q;
-                    e[q] = loc_corner<false>(cam, R, t, s_X + 3 * k, (double)s_uv[2 * k], (double)s_uv[2 * k + 1], nullptr);
+                    e[q] = loc_corner<false>(cam, R, t, L.X + 3 * k, (double)L.uv[2 * k], (double)L.uv[2 * k + 1], nullptr);
                 }
                 const double rms = sqrt(((e[0] + e[1]) + (e[2] + e[3])) / 4);
                 if (rms > wr) { wr = rms; ws = s; }
@@ -309,11 +392,11 @@ __global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs,
             argmax_step<8>(wr, ws); argmax_step<16>(wr, ws); argmax_step<32>(wr, ws);
             if (!(wr > gate)) break;
             __syncthreads();
-            if (lane == 0) s_state[ws] = 2;
+            if (lane == 0) L.state[ws] = 2;
             __syncthreads();
             nrej++;
             nused--;
-            cost = loc_lm(cam, R, t, s_X, s_uv, s_state, n4, lane);
+            cost = pose_lm(pass, R, t);
         }
     }
 

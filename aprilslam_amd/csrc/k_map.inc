@@ -8,11 +8,12 @@
 //                   tag lists in camera order), inactive entries of the table cleared; run after each stage that drops
 //   k_map_chain     one workgroup: breadth-first rounds from the world tag (cameras, then tags, each half reading the state
 //                   the previous one left) -- map_init.chain_initial_map without its dependence on frame order
-//   k_map_sweep_cam per camera (one wavefront): reseed_poses' camera half -- k_localize.inc's gather, candidates
-//                   (loc_candidate) and scoring (loc_pass) against the current map, the current pose as candidate 0
+//   k_map_sweep_cam per camera (one wavefront): reseed_poses' camera half -- k_localize.inc's slot gather, top-8 choice,
+//                   candidates (loc_candidate) and scoring (loc_pass) against the current map, the current pose as candidate 0
 //   k_map_sweep_tag per tag (one wavefront): the dual, the cameras held; candidate poses inv(W) T_obs and its mirror
 //   k_map_gauge     one workgroup: the world tag back at the identity
 //   k_map_flip      per tag: the pose and its mirror (built in the view of largest area) each polished by pose-only LM
+//                   (k_localize.inc: pose_lm)
 //   k_map_behind    per camera: observations with a corner at z <= 1e-6 leave; a camera left with < 2 is dropped
 //   then k_gn.inc's Levenberg-Marquardt step, unchanged (k_gn_reduce_cam, k_gn_schur, the blocked Cholesky,
 //   k_gn_trisolve, k_gn_update, k_gn_cost, k_gn_commit) around k_map_linearize (the lens-aware counterpart of
@@ -98,14 +99,6 @@ __device__ __forceinline__ void map_obs_pose(const ObsRec &o, bool mirror, doubl
 #pragma unroll
     for (int k = 0; k < 9; k++) A[k] = R[k];
     A[9] = t[0]; A[10] = t[1]; A[11] = t[2];
-}
-
-__device__ __forceinline__ double map_area(const ObsRec &o)
-{
-    const double x0 = o.corners[0], y0 = o.corners[1], x1 = o.corners[2], y1 = o.corners[3];
-    const double x2 = o.corners[4], y2 = o.corners[5], x3 = o.corners[6], y3 = o.corners[7];
-    const double a = (x0 * y1 - x1 * y0) + (x1 * y2 - x2 * y1) + (x2 * y3 - x3 * y2) + (x3 * y0 - x0 * y3);
-    return 0.5 * fabs(a);
 }
 
 // exclusive prefix sum of cnt(i), i < n, by the MAP_WG threads (contiguous chunks, then the chunks in order) into out[0..n]
@@ -255,7 +248,7 @@ __global__ void __launch_bounds__(MAP_WG) k_map_chain(MapArgs a, int n_cams, int
                 const ObsRec &o = a.obs[a.obs_slot[m]];
                 const int j = a.obs_tag[m];
                 if (!(o.flags & 2) || !a.tag_state[j]) continue;
-                const double ar = map_area(o);
+                const double ar = loc_area(o.corners);
                 if (ar > ba || (ar == ba && j < bt)) { ba = ar; bm = m; bt = j; }
             }
             if (bm < 0) continue;
@@ -276,7 +269,7 @@ __global__ void __launch_bounds__(MAP_WG) k_map_chain(MapArgs a, int n_cams, int
                 const int m = a.tag_obs[o];
                 const ObsRec &r = a.obs[a.obs_slot[m]];
                 if (!(r.flags & 2) || !a.cam_state[a.obs_cam[m]]) continue;
-                const double ar = map_area(r);
+                const double ar = loc_area(r.corners);
                 if (ar > ba) { ba = ar; bm = m; }
             }
             if (bm < 0) continue;
@@ -301,84 +294,45 @@ __global__ void __launch_bounds__(64) k_map_sweep_cam(MapArgs a, CamDev cam)
     extern __shared__ double s_dyn[];
     const int c = blockIdx.x, lane = threadIdx.x, S = a.max_tags, n4 = 4 * S;
     if (a.cam_state[c] != 1) return;
-    double *s_X = s_dyn;
-    double *s_area = s_X + 3 * n4;
-    float *s_uv = (float *)(s_area + S);
-    int *s_state = (int *)(s_uv + 2 * n4);
+    const LocLds L = loc_lds(s_dyn, S);
     const int f = a.cam_frame[c];
     const ObsRec *fo = a.obs + (size_t)f * S;
     int npart = 0;
     for (int s = lane; s < S; s += ASL_WAVE) {
         const int m = a.slot_obs[(size_t)f * S + s];
         const bool part = m >= 0 && a.obs_act[m];
-        s_state[s] = part ? 1 : 0;
-        s_area[s] = -1.0;
+        L.state[s] = part ? 1 : 0;
+        L.area[s] = -1.0;
         if (!part) continue;
         npart++;
-        const double *Gj = a.G + 12 * (size_t)a.obs_tag[m];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const double ox = (q == 1 || q == 2) ? cam.half : -cam.half, oy = (q >= 2) ? cam.half : -cam.half;
-#pragma unroll
-            for (int r = 0; r < 3; r++) s_X[3 * (4 * s + q) + r] = Gj[3 * r] * ox + Gj[3 * r + 1] * oy + Gj[9 + r];
-            s_uv[2 * (4 * s + q)] = fo[s].corners[2 * q];
-            s_uv[2 * (4 * s + q) + 1] = fo[s].corners[2 * q + 1];
-        }
-        if (fo[s].flags & 2) s_area[s] = map_area(fo[s]);
+        double M[12];
+        pk_to34(a.G + 12 * (size_t)a.obs_tag[m], M);
+        loc_gather_slot(L, s, M, cam.half, fo[s].corners);
+        if (fo[s].flags & 2) L.area[s] = loc_area(fo[s].corners);
     }
     __syncthreads();
     npart = wave_sum_i32(npart);
     if (npart == 0) return;
-    double R[9], t[3];
+    auto score = [&](const double *P) { return loc_pass<false>(cam, P, P + 9, L, n4, lane, nullptr); };
+    double P[12];
     const double *Wc = a.W + 12 * (size_t)c;
 #pragma unroll
-    for (int i = 0; i < 9; i++) R[i] = Wc[i];
-    t[0] = Wc[9]; t[1] = Wc[10]; t[2] = Wc[11];
-    double best = loc_pass<false>(cam, R, t, s_X, s_uv, s_state, n4, lane, nullptr);
+    for (int i = 0; i < 12; i++) P[i] = Wc[i];
+    double best = score(P);  // the current pose is candidate 0
     int sel[MAP_MAX_CAND];
-    int nsel = 0;
-#pragma unroll
-    for (int r = 0; r < MAP_MAX_CAND; r++) {
-        double ba = -1.0;
-        int bs = 0x7fffffff;
-        for (int s = lane; s < S; s += ASL_WAVE)
-            if (s_area[s] > ba) { ba = s_area[s]; bs = s; }
-        argmax_step<1>(ba, bs); argmax_step<2>(ba, bs); argmax_step<4>(ba, bs);
-        argmax_step<8>(ba, bs); argmax_step<16>(ba, bs); argmax_step<32>(ba, bs);
-        sel[r] = ba >= 0 ? bs : 0x7fffffff;
-        if (ba >= 0) nsel++;
-        __syncthreads();
-        if (lane == 0 && ba >= 0) s_area[bs] = -1.0;
-        __syncthreads();
-    }
-    int prev = -1;
-    for (int k = 0; k < nsel; k++) {
-        int s = 0x7fffffff;
-#pragma unroll
-        for (int r = 0; r < MAP_MAX_CAND; r++)
-            if (sel[r] > prev && sel[r] < s) s = sel[r];
-        prev = s;
+    const int nsel = loc_top_k(S, lane, [&](int s) { return L.area[s]; }, sel);
+    auto make = [&](int s) {
         double To[12], M[12];
         pk_to34(a.G + 12 * (size_t)a.obs_tag[a.slot_obs[(size_t)f * S + s]], M);
 #pragma unroll
         for (int i = 0; i < 12; i++) To[i] = fo[s].T[i];
-        for (int mi = 0; mi < 2; mi++) {
-            double Rc[9], tc[3];
-            loc_candidate(To, M, mi == 1, Rc, tc);
-            const double cc = loc_pass<false>(cam, Rc, tc, s_X, s_uv, s_state, n4, lane, nullptr);
-            if (cc < best) {
-                best = cc;
-#pragma unroll
-                for (int i = 0; i < 9; i++) R[i] = Rc[i];
-                t[0] = tc[0]; t[1] = tc[1]; t[2] = tc[2];
-            }
-        }
-    }
+        return [=](bool mirror, double *C) { loc_candidate(To, M, mirror, C, C + 9); };
+    };
+    loc_best_candidate(sel, nsel, make, score, best, P);
     if (lane == 0) {
         double *Wo = a.W + 12 * (size_t)c;
 #pragma unroll
-        for (int i = 0; i < 9; i++) Wo[i] = R[i];
-        Wo[9] = t[0]; Wo[10] = t[1]; Wo[11] = t[2];
+        for (int i = 0; i < 12; i++) Wo[i] = P[i];
     }
 }
 
@@ -431,40 +385,6 @@ __device__ __forceinline__ double map_tag_pass(const MapArgs &a, const CamDev &c
     return wave_sum_f64(cost);
 }
 
-// loc_lm's schedule on a tag's world<-tag (R, t), the cameras held: R <- Rod(w) R, t <- Rod(w) t + v
-__device__ __forceinline__ double map_tag_lm(const MapArgs &a, const CamDev &c, double *R, double *t, int b, int e, int lane)
-{
-    double ne[27];
-    double cost = map_tag_pass<true>(a, c, R, t, b, e, lane, ne);
-    double lambda = 1e-3;
-    for (int it = 0; it < LOC_LM_ITERS; it++) {
-        double A[21], d[6];
-#pragma unroll
-        for (int i = 0; i < 21; i++) A[i] = ne[i];
-#pragma unroll
-        for (int p = 0; p < 6; p++) { A[TRI(p, p)] += lambda * ne[TRI(p, p)]; d[p] = -ne[21 + p]; }
-        if (!chol6_solve_tri_dev(A, d)) { lambda *= 10; continue; }
-        double dR[9], Rn[9], tn[3];
-        rodrigues_dev(d, dR);
-        mat3_mul_dev(dR, R, Rn);
-#pragma unroll
-        for (int r = 0; r < 3; r++) tn[r] = dR[3 * r] * t[0] + dR[3 * r + 1] * t[1] + dR[3 * r + 2] * t[2] + d[3 + r];
-        const double cn = map_tag_pass<false>(a, c, Rn, tn, b, e, lane, nullptr);
-        if (cn < cost) {
-            const bool stop = cost - cn < 1e-12 * cost;
-#pragma unroll
-            for (int i = 0; i < 9; i++) R[i] = Rn[i];
-            t[0] = tn[0]; t[1] = tn[1]; t[2] = tn[2];
-            cost = cn;
-            lambda *= 0.1;
-            if (stop) break;
-            cost = map_tag_pass<true>(a, c, R, t, b, e, lane, ne);
-        } else
-            lambda *= 10;
-    }
-    return cost;
-}
-
 // ---- reseed, tag half: one wavefront per tag, the cameras held
 __global__ void __launch_bounds__(64) k_map_sweep_tag(MapArgs a, CamDev cam)
 {
@@ -472,61 +392,34 @@ __global__ void __launch_bounds__(64) k_map_sweep_tag(MapArgs a, CamDev cam)
     if (a.tag_state[j] != 1) return;
     const int b = a.tag_ptr[j], e = a.tag_ptr[j + 1], n = e - b;
     if (n == 0) return;
-    double R[9], t[3];
+    auto score = [&](const double *P) { return map_tag_pass<false>(a, cam, P, P + 9, b, e, lane, nullptr); };
+    double P[12];
     const double *Gj = a.G + 12 * (size_t)j;
 #pragma unroll
-    for (int i = 0; i < 9; i++) R[i] = Gj[i];
-    t[0] = Gj[9]; t[1] = Gj[10]; t[2] = Gj[11];
-    double best = map_tag_pass<false>(a, cam, R, t, b, e, lane, nullptr);
-    // the <= 8 seeding observations of largest area (ties: lower list position = lower camera), picked in that order
+    for (int i = 0; i < 12; i++) P[i] = Gj[i];
+    double best = score(P);  // the current pose is candidate 0
+    // the <= 8 seeding observations of largest area (ties: lower list position = lower camera)
     int sel[MAP_MAX_CAND];
-    int nsel = 0;
-    double pa = INFINITY;
-    int pp = -1;
-#pragma unroll
-    for (int r = 0; r < MAP_MAX_CAND; r++) {
-        double ba = -1.0;
-        int bs = 0x7fffffff;
-        for (int o = lane; o < n; o += ASL_WAVE) {
-            const ObsRec &rec = a.obs[a.obs_slot[a.tag_obs[b + o]]];
-            if (!(rec.flags & 2)) continue;
-            const double ar = map_area(rec);
-            if (!(ar < pa || (ar == pa && o > pp))) continue;  // taken already
-            if (ar > ba) { ba = ar; bs = o; }
-        }
-        argmax_step<1>(ba, bs); argmax_step<2>(ba, bs); argmax_step<4>(ba, bs);
-        argmax_step<8>(ba, bs); argmax_step<16>(ba, bs); argmax_step<32>(ba, bs);
-        sel[r] = ba >= 0 ? bs : 0x7fffffff;
-        if (ba >= 0) { nsel++; pa = ba; pp = bs; }
-    }
-    int prev = -1;
-    for (int k = 0; k < nsel; k++) {
-        int o = 0x7fffffff;
-#pragma unroll
-        for (int r = 0; r < MAP_MAX_CAND; r++)
-            if (sel[r] > prev && sel[r] < o) o = sel[r];
-        prev = o;
+    const int nsel = loc_top_k(n, lane, [&](int o) {
+        const ObsRec &rec = a.obs[a.obs_slot[a.tag_obs[b + o]]];
+        return (rec.flags & 2) ? loc_area(rec.corners) : -1.0;
+    }, sel);
+    auto make = [&](int o) {
         const int m = a.tag_obs[b + o];
         double Wi[12];
         pk_inv(a.W + 12 * (size_t)a.obs_cam[m], Wi);
-        for (int mi = 0; mi < 2; mi++) {
-            double To[12], Gc[12];
-            map_obs_pose(a.obs[a.obs_slot[m]], mi == 1, To);
-            pk_mul(Wi, To, Gc);
-            const double cc = map_tag_pass<false>(a, cam, Gc, Gc + 9, b, e, lane, nullptr);
-            if (cc < best) {
-                best = cc;
-#pragma unroll
-                for (int i = 0; i < 9; i++) R[i] = Gc[i];
-                t[0] = Gc[9]; t[1] = Gc[10]; t[2] = Gc[11];
-            }
-        }
-    }
+        const ObsRec *rec = a.obs + a.obs_slot[m];
+        return [=](bool mirror, double *C) {
+            double To[12];
+            map_obs_pose(*rec, mirror, To);
+            pk_mul(Wi, To, C);
+        };
+    };
+    loc_best_candidate(sel, nsel, make, score, best, P);
     if (lane == 0) {
         double *Go = a.G + 12 * (size_t)j;
 #pragma unroll
-        for (int i = 0; i < 9; i++) Go[i] = R[i];
-        Go[9] = t[0]; Go[10] = t[1]; Go[11] = t[2];
+        for (int i = 0; i < 12; i++) Go[i] = P[i];
     }
 }
 
@@ -566,7 +459,7 @@ __global__ void __launch_bounds__(64) k_map_flip(MapArgs a, CamDev cam, int wt)
     double ba = -1.0;
     int bo = 0x7fffffff;
     for (int o = lane; o < n; o += ASL_WAVE) {
-        const double ar = map_area(a.obs[a.obs_slot[a.tag_obs[b + o]]]);
+        const double ar = loc_area(a.obs[a.obs_slot[a.tag_obs[b + o]]].corners);
         if (ar > ba) { ba = ar; bo = o; }
     }
     argmax_step<1>(ba, bo); argmax_step<2>(ba, bo); argmax_step<4>(ba, bo);
@@ -580,8 +473,11 @@ __global__ void __launch_bounds__(64) k_map_flip(MapArgs a, CamDev cam, int wt)
     pk_mul(Wi, Mr, Gm);
     for (int i = 0; i < 9; i++) { R0[i] = G0[i]; R1[i] = Gm[i]; }
     for (int i = 0; i < 3; i++) { t0[i] = G0[9 + i]; t1[i] = Gm[9 + i]; }
-    const double c0 = map_tag_lm(a, cam, R0, t0, b, e, lane);
-    const double c1 = map_tag_lm(a, cam, R1, t1, b, e, lane);
+    auto pass = [&](const double *R, const double *t, auto ne_tag, double *ne) {
+        return map_tag_pass<decltype(ne_tag)::value>(a, cam, R, t, b, e, lane, ne);
+    };
+    const double c0 = pose_lm(pass, R0, t0);
+    const double c1 = pose_lm(pass, R1, t1);
     if (lane == 0) {
         const bool flip = c1 < c0;
         double *Go = a.G + 12 * (size_t)j;

@@ -143,10 +143,8 @@ def seed_frame(rows, part, Xw, uv, tag_map, theta0, width, height, tag_size):
     fx, fy, cx, cy = theta0[:4]
     cam0 = (fx, fy, cx, cy, 0.0, 0.0, 0.0, 0.0, 0.0)
     s, half = 0.5 * (width + height), LR.half_size(tag_size)
-    area = {k: LR.corner_area(rows["corners"][k]) for k in part}
-    chosen = sorted(sorted(part, key=lambda k: (-area[k], k))[:LR.MAX_SEED_SLOTS])
     best, best_cost = None, np.inf
-    for k in chosen:
+    for k in [part[i] for i in LR.top_k([LR.corner_area(rows["corners"][k]) for k in part])]:
         Ro, to = planar_pose(square_homography(rows["corners"][k], cx, cy, s), fx, fy, s, half)
         M = tag_map["T"][rows["id"][k]].reshape(3, 4)
         for m in (0, 1):
@@ -158,7 +156,7 @@ def seed_frame(rows, part, Xw, uv, tag_map, theta0, width, height, tag_size):
                 best, best_cost = (Rc, tc, k + LR.MIRRORED * m), c
     if best is None or not best_cost < LR.BEHIND_COST:
         return None
-    R, t, cost = LR.lm(cam0, best[0], best[1], Xw, uv)
+    R, t, cost = LR.lm(LR.corner_lin(cam0, Xw, uv), best[0], best[1])
     return R, t, cost, best[2]
 
 

@@ -168,9 +168,19 @@ def chol6_solve(A, b):
     return x
 
 
-def lm(cam, R, t, Xw, uv):
-    """the fixed schedule of the module docstring; returns (R, t, cost)"""
-    cost, H, g = linearise(cam, R, t, Xw, uv)
+def corner_lin(cam, Xw, uv):
+    """lm's lin over a frame's corners: (cost, H, g) of linearise, or (cost, None, None) for the trial cost alone"""
+    def lin(R, t, want):
+        if want:
+            return linearise(cam, R, t, Xw, uv)
+        return float(corner_costs(cam, R, t, Xw, uv).sum()), None, None
+    return lin
+
+
+def lm(lin, R, t):
+    """the fixed schedule of the module docstring on (R, t), the left update R <- Rod(w) R, t <- Rod(w) t + v;
+    lin(R, t, want) -> (cost, H, g), H and g only if want; returns (R, t, cost)"""
+    cost, H, g = lin(R, t, True)
     lam = LAMBDA0
     for _ in range(LM_ITERS):
         A = H.copy()
@@ -181,17 +191,23 @@ def lm(cam, R, t, Xw, uv):
             continue
         dR = rodrigues(d[:3])
         Rn, tn = dR @ R, dR @ t + d[3:]
-        cn = float(corner_costs(cam, Rn, tn, Xw, uv).sum())
+        cn = lin(Rn, tn, False)[0]
         if cn < cost:
             stop = cost - cn < REL_STOP * cost
             R, t, cost = Rn, tn, cn
             lam *= 0.1
             if stop:
                 break
-            cost, H, g = linearise(cam, R, t, Xw, uv)
+            cost, H, g = lin(R, t, True)
         else:
             lam *= 10
     return R, t, cost
+
+
+def top_k(areas, k=MAX_SEED_SLOTS):
+    """positions of the k largest areas (ties: lower position), in ascending position order"""
+    order = sorted(range(len(areas)), key=lambda i: (-areas[i], i))
+    return sorted(order[:k])
 
 
 def _world_corners(M12, obj):
@@ -201,10 +217,8 @@ def _world_corners(M12, obj):
 
 def seed_candidates(rows, tag_map, cam, seeds, Xw, uv):
     """[(R, t, seed code, score)] in candidate order: the <= 8 seeding slots of largest area in slot order, plain then mirrored"""
-    area = {s: corner_area(rows["corners"][s]) for s in seeds}
-    chosen = sorted(sorted(seeds, key=lambda s: (-area[s], s))[:MAX_SEED_SLOTS])
     out = []
-    for s in chosen:
+    for s in [seeds[k] for k in top_k([corner_area(rows["corners"][s]) for s in seeds])]:
         To = rows["T"][s].reshape(3, 4)
         M = tag_map["T"][rows["id"][s]].reshape(3, 4)
         for m in (0, 1):
@@ -259,7 +273,7 @@ def localize_frame(rows, tag_map, cam, tag_size, gate):
         return out
     R, t, code = best
     n_part = len(part)
-    R, t, cost = lm(cam, R, t, Xw, uv)
+    R, t, cost = lm(corner_lin(cam, Xw, uv), R, t)
     n_used, n_rej = n_part, 0
     if gate > 0:
         active = np.ones(n_part, dtype=bool)
@@ -273,7 +287,7 @@ def localize_frame(rows, tag_map, cam, tag_size, gate):
             n_rej += 1
             n_used -= 1
             keep = np.repeat(active, 4)
-            R, t, cost = lm(cam, R, t, Xw[keep], uv[keep])
+            R, t, cost = lm(corner_lin(cam, Xw[keep], uv[keep]), R, t)
     T = np.eye(4)
     T[:3, :3] = R.T
     T[:3, 3] = -(R.T @ t)

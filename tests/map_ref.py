@@ -75,18 +75,12 @@ def obs_cost(cam, Wc, Gj, uv, h):
     return float(LR.corner_costs(cam, Wc[:3, :3], Wc[:3, 3], Xw, uv).sum())
 
 
-def top_k(areas, k=MAX_CAND):
-    """positions of the k largest areas (ties: lower position), in ascending position order"""
-    order = sorted(range(len(areas)), key=lambda i: (-areas[i], i))
-    return sorted(order[:k])
-
-
 def tag_lm(cam, G, Ws, uvs, h):
     """pose-only LM of one world<-tag G with the cameras Ws (camera<-world) held; localize_ref.lm's schedule"""
     X = obj3(h)
 
-    def lin_wrap(G, want):
-        Xw = X @ G[:3, :3].T + G[:3, 3]
+    def lin(R, t, want):
+        Xw = X @ R.T + t
         if not want:
             return sum(float(LR.corner_costs(cam, Wc[:3, :3], Wc[:3, 3], Xw, uv).sum()) for Wc, uv in zip(Ws, uvs)), None, None
         cost, H, g = 0.0, np.zeros((6, 6)), np.zeros(6)
@@ -105,30 +99,10 @@ def tag_lm(cam, G, Ws, uvs, h):
                 g += J.T @ r
         return cost, H, g
 
-    cost, H, g = lin_wrap(G, True)
-    lam = LR.LAMBDA0
-    for _ in range(LR.LM_ITERS):
-        A = H.copy()
-        A[np.diag_indices(6)] += lam * np.diag(H)
-        d = LR.chol6_solve(A, -g)
-        if d is None:
-            lam *= 10
-            continue
-        dR = LR.rodrigues(d[:3])
-        Gn = np.eye(4)
-        Gn[:3, :3] = dR @ G[:3, :3]
-        Gn[:3, 3] = dR @ G[:3, 3] + d[3:]
-        cn, _, _ = lin_wrap(Gn, False)
-        if cn < cost:
-            stop = cost - cn < LR.REL_STOP * cost
-            G, cost = Gn, cn
-            lam *= 0.1
-            if stop:
-                break
-            cost, H, g = lin_wrap(G, True)
-        else:
-            lam *= 10
-    return G, cost
+    R, t, cost = LR.lm(lin, G[:3, :3], G[:3, 3])
+    out = G.copy()
+    out[:3, :3], out[:3, 3] = R, t
+    return out, cost
 
 
 def _project_many(cam, P):
@@ -259,7 +233,7 @@ def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_st
                 continue
             cands = [W[c]]
             sm = [m for m in ms if seedable[m]]
-            for k in top_k([area[m] for m in sm]):
+            for k in LR.top_k([area[m] for m in sm], MAX_CAND):
                 m = sm[k]
                 cands += [To[m] @ inv(G[ot[m]]), mirror4(To[m]) @ inv(G[ot[m]])]
             costs = [sum(obs_cost(cam, Tc, G[ot[m]], uv[m], h) for m in ms) for Tc in cands]
@@ -272,7 +246,7 @@ def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_st
                 continue
             cands = [G[j]]
             sm = [m for m in ms if seedable[m]]
-            for k in top_k([area[m] for m in sm]):
+            for k in LR.top_k([area[m] for m in sm], MAX_CAND):
                 m = sm[k]
                 Wi = inv(W[oc[m]])
                 cands += [Wi @ To[m], Wi @ mirror4(To[m])]

@@ -38,7 +38,7 @@ def test_exact_corners_recover_the_pose(scene):
         Xw, uv = np.concatenate(Xw), np.concatenate(uv)
         Tcw = np.linalg.inv(truth)
         start = LR.rodrigues(np.array([0.01, -0.02, 0.015])) @ Tcw[:3, :3], Tcw[:3, 3] + np.array([0.3, -0.2, 0.5])
-        R, t, cost = LR.lm(cam, start[0], start[1], Xw, uv)
+        R, t, cost = LR.lm(LR.corner_lin(cam, Xw, uv), start[0], start[1])
         est = np.eye(4)
         est[:3, :3], est[:3, 3] = R.T, -(R.T @ t)
         assert LC.rel_err(est, truth) <= 1e-9, LC.rel_err(est, truth)
