@@ -245,8 +245,10 @@ def candidate_scores(rows, tag_map, K, dist, tag_size):
     return {code: c for _, _, code, c in seed_candidates(rows, tag_map, cam, seeds, Xw, uv)}
 
 
-def localize_frame(rows, tag_map, cam, tag_size, gate):
-    """one frame's max_tags asl_obs records -> one CAM_POSE_DTYPE record"""
+def localize_frame(rows, tag_map, cam, tag_size, gate, trace=None):
+    """one frame's max_tags asl_obs records -> one CAM_POSE_DTYPE record; trace (a dict, optional) receives the chosen
+    seeding slots (top_k, in slot order: "top_k"), the slots the gate dropped in order ("dropped") and each gate round's own
+    RMS per taking-part slot ("gate_rms")"""
     out = np.zeros((), dtype=CAM_POSE_DTYPE)
     out["T"] = np.eye(4)
     out["seed_slot"] = -1
@@ -263,6 +265,10 @@ def localize_frame(rows, tag_map, cam, tag_size, gate):
     Xw = np.concatenate([_world_corners(tag_map["T"][rows["id"][s]], obj) for s in part])
     uv = np.concatenate([rows["corners"][s].astype(np.float64).reshape(4, 2) for s in part])
 
+    if trace is not None:
+        areas = [corner_area(rows["corners"][s]) for s in seeds]
+        trace["top_k"] = [seeds[k] for k in top_k(areas)]
+        trace["dropped"], trace["gate_rms"] = [], []
     cands = seed_candidates(rows, tag_map, cam, seeds, Xw, uv)
     best, best_cost = None, np.inf
     for Rc, tc, code, c in cands:
@@ -281,9 +287,13 @@ def localize_frame(rows, tag_map, cam, tag_size, gate):
             e = corner_costs(cam, R, t, Xw, uv).reshape(-1, 4)
             rms = np.where(active, np.sqrt(((e[:, 0] + e[:, 1]) + (e[:, 2] + e[:, 3])) / 4), -1.0)
             worst = int(np.argmax(rms))                 # the first of equal maxima: the lower slot
+            if trace is not None:
+                trace["gate_rms"].append(rms)
             if not rms[worst] > gate:
                 break
             active[worst] = False
+            if trace is not None:
+                trace["dropped"].append(part[worst])
             n_rej += 1
             n_used -= 1
             keep = np.repeat(active, 4)
@@ -301,11 +311,17 @@ def localize_frame(rows, tag_map, cam, tag_size, gate):
     return out
 
 
-def localize(obs, tag_map, K, dist, tag_size, max_tag_rms_px=0.0):
-    """obs (n_frames, max_tags) asl_obs records, tag_map (n_ids,) asl_map_tag records -> (n_frames,) CAM_POSE_DTYPE"""
+def localize(obs, tag_map, K, dist, tag_size, max_tag_rms_px=0.0, traces=None):
+    """obs (n_frames, max_tags) asl_obs records, tag_map (n_ids,) asl_map_tag records -> (n_frames,) CAM_POSE_DTYPE;
+    traces (a list, optional) receives localize_frame's trace of every frame"""
     obs = np.asarray(obs)
     if obs.ndim == 1:
         obs = obs[None]
     cam = camera(K, dist)
-    return np.array([localize_frame(obs[f], tag_map, cam, tag_size, float(max_tag_rms_px)) for f in range(len(obs))],
-                    dtype=CAM_POSE_DTYPE)
+    out = []
+    for f in range(len(obs)):
+        tr = {} if traces is not None else None
+        out.append(localize_frame(obs[f], tag_map, cam, tag_size, float(max_tag_rms_px), tr))
+        if traces is not None:
+            traces.append(tr)
+    return np.array(out, dtype=CAM_POSE_DTYPE)

@@ -32,6 +32,7 @@ import os
 import sys
 
 import numpy as np
+from scipy.linalg import solve_triangular
 
 import localize_ref as LR
 from aprilslam_amd._lib import CAM_POSE_DTYPE, MAP_RESULT_DTYPE, MAP_TAG_DTYPE
@@ -69,34 +70,50 @@ def obj3(h):
     return np.array([[-h, -h, 0.0], [h, -h, 0.0], [h, h, 0.0], [-h, h, 0.0]])
 
 
-def obs_cost(cam, Wc, Gj, uv, h):
-    """total corner cost of one observation (4 corners, localize_ref's rules)"""
-    Xw = obj3(h) @ Gj[:3, :3].T + Gj[:3, 3]
-    return float(LR.corner_costs(cam, Wc[:3, :3], Wc[:3, 3], Xw, uv).sum())
+def corner_costs_many(cam, Wc, Xw, uv):
+    """localize_ref.corner_costs of n observations at once: Wc (n, 4, 4) camera<-world, Xw (n, 4, 3) world corners,
+    uv (n, 4, 2) -> (n, 4) squared pixel errors (1e12 for a corner at z <= 1e-9)"""
+    P = np.einsum('nij,nkj->nki', Wc[:, :3, :3], Xw) + Wc[:, None, :3, 3]
+    Pf = P.reshape(-1, 3)
+    ok = Pf[:, 2] > LR.Z_MIN
+    e = np.full(len(Pf), LR.BEHIND_COST)
+    if ok.any():
+        r = LR.project(cam, Pf[ok]) - uv.reshape(-1, 2)[ok]
+        e[ok] = r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1]
+    return e.reshape(len(Wc), 4)
+
+
+def obs_costs(cam, W, G, uv, h):
+    """obs_cost of n observations at once: W (n, 4, 4) camera<-world, G (n, 4, 4) world<-tag, uv (n, 4, 2) -> (n,)"""
+    Xw = np.einsum('nij,kj->nki', G[:, :3, :3], obj3(h)) + G[:, None, :3, 3]
+    return corner_costs_many(cam, W, Xw, uv).sum(axis=1)
 
 
 def tag_lm(cam, G, Ws, uvs, h):
     """pose-only LM of one world<-tag G with the cameras Ws (camera<-world) held; localize_ref.lm's schedule"""
     X = obj3(h)
 
+    Wa = np.stack(Ws)
+    uva = np.stack(uvs)
+    n = len(Wa)
+
     def lin(R, t, want):
         Xw = X @ R.T + t
         if not want:
-            return sum(float(LR.corner_costs(cam, Wc[:3, :3], Wc[:3, 3], Xw, uv).sum()) for Wc, uv in zip(Ws, uvs)), None, None
-        cost, H, g = 0.0, np.zeros((6, 6)), np.zeros(6)
-        for Wc, uv in zip(Ws, uvs):
-            P = Xw @ Wc[:3, :3].T + Wc[:3, 3]
-            for q in range(4):
-                if not P[q, 2] > LR.Z_MIN:
-                    cost += LR.BEHIND_COST
-                    continue
-                pr, Jp = LR.project(cam, P[q:q + 1], jac=True)
-                r = pr[0] - uv[q]
-                cost += float(r @ r)
-                a = Jp[0] @ Wc[:3, :3]                      # (2, 3): d uv / d Xw
-                J = np.concatenate([np.cross(Xw[q], a), a], axis=1)
-                H += J.T @ J
-                g += J.T @ r
+            return float(corner_costs_many(cam, Wa, np.broadcast_to(Xw, (n, 4, 3)), uva).sum()), None, None
+        P = (np.einsum('nij,kj->nki', Wa[:, :3, :3], Xw) + Wa[:, None, :3, 3]).reshape(-1, 3)
+        ok = P[:, 2] > LR.Z_MIN
+        cost = LR.BEHIND_COST * float((~ok).sum())
+        H, g = np.zeros((6, 6)), np.zeros(6)
+        if ok.any():
+            pr, Jp = LR.project(cam, P[ok], jac=True)
+            r = pr - uva.reshape(-1, 2)[ok]
+            cost += float((r * r).sum())
+            a = np.einsum('nri,nij->nrj', Jp, np.repeat(Wa[:, :3, :3], 4, axis=0)[ok])    # (k, 2, 3): d uv / d Xw
+            Xq = np.tile(Xw, (n, 1))[ok]
+            J = np.concatenate([np.cross(Xq[:, None, :], a), a], axis=2).reshape(-1, 6)
+            H = J.T @ J
+            g = J.T @ r.reshape(-1)
         return cost, H, g
 
     R, t, cost = LR.lm(lin, G[:3, :3], G[:3, 3])
@@ -128,15 +145,27 @@ def joint_linearise(cam, W, G, oc, ot, uv, h, cam_col, tag_col, n_par):
     Jc = np.concatenate([np.cross(Pf[:, None, :], Jp), Jp], axis=2)                           # [P x jp | jp]
     a = np.einsum('nri,nij->nrj', Jp, np.repeat(W[oc][:, :3, :3], 4, axis=0))
     Jt = np.concatenate([np.cross(qf[:, None, :], a), a], axis=2)
-    J = np.zeros((8 * M, n_par))
-    rows = np.arange(8 * M).reshape(-1, 2)
-    cc, tc = np.repeat(cam_col[oc], 4), np.repeat(tag_col[ot], 4)
-    for n in range(4 * M):
-        if cc[n] >= 0:
-            J[rows[n], cc[n]:cc[n] + 6] = Jc[n]
-        if tc[n] >= 0:
-            J[rows[n], tc[n]:tc[n] + 6] = Jt[n]
-    return cost, J.T @ J, J.T @ r.ravel()
+    # J^T J and J^T r block by block: per observation its 8 rows' camera / tag products, added into their columns
+    Jc, Jt, r8 = Jc.reshape(M, 8, 6), Jt.reshape(M, 8, 6), r.reshape(M, 8)
+    ccol, tcol = cam_col[oc], tag_col[ot]
+    H, g = np.zeros((n_par, n_par)), np.zeros(n_par)
+    i6 = np.arange(6)
+
+    def add(rc, cc, blk, sel):
+        if sel.any():
+            np.add.at(H, (rc[sel][:, None, None] + i6[None, :, None], cc[sel][:, None, None] + i6[None, None, :]), blk[sel])
+
+    cm, tm = ccol >= 0, tcol >= 0
+    add(ccol, ccol, np.einsum('mri,mrj->mij', Jc, Jc), cm)
+    add(tcol, tcol, np.einsum('mri,mrj->mij', Jt, Jt), tm)
+    ct = np.einsum('mri,mrj->mij', Jc, Jt)
+    add(ccol, tcol, ct, cm & tm)
+    add(tcol, ccol, ct.transpose(0, 2, 1), cm & tm)
+    if cm.any():
+        np.add.at(g, ccol[cm][:, None] + i6, np.einsum('mri,mr->mi', Jc, r8)[cm])
+    if tm.any():
+        np.add.at(g, tcol[tm][:, None] + i6, np.einsum('mri,mr->mi', Jt, r8)[tm])
+    return cost, H, g
 
 
 def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_std=True, trace=None):
@@ -236,7 +265,8 @@ def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_st
             for k in LR.top_k([area[m] for m in sm], MAX_CAND):
                 m = sm[k]
                 cands += [To[m] @ inv(G[ot[m]]), mirror4(To[m]) @ inv(G[ot[m]])]
-            costs = [sum(obs_cost(cam, Tc, G[ot[m]], uv[m], h) for m in ms) for Tc in cands]
+            Gm, uvm = G[ot[ms]], uv[ms]
+            costs = [float(obs_costs(cam, np.broadcast_to(Tc, (len(ms), 4, 4)), Gm, uvm, h).sum()) for Tc in cands]
             Wn[c] = cands[int(np.argmin(costs))]
         W = Wn
         Gn = G.copy()
@@ -250,7 +280,8 @@ def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_st
                 m = sm[k]
                 Wi = inv(W[oc[m]])
                 cands += [Wi @ To[m], Wi @ mirror4(To[m])]
-            costs = [sum(obs_cost(cam, W[oc[m]], Tg, uv[m], h) for m in ms) for Tg in cands]
+            Wm, uvm = W[oc[ms]], uv[ms]
+            costs = [float(obs_costs(cam, Wm, np.broadcast_to(Tg, (len(ms), 4, 4)), uvm, h).sum()) for Tg in cands]
             Gn[j] = cands[int(np.argmin(costs))]
         G = Gn
     Gw = G[wt].copy()
@@ -303,7 +334,7 @@ def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_st
             tag_col[j] = 6 * (len(cams_used) + k)
         npar = 6 * (len(cams_used) + len(free_tags))
         a = np.flatnonzero(act)
-        seed_obs = np.array([obs_cost(cam, W[oc[m]], G[ot[m]], uv[m], h) for m in range(M)])
+        seed_obs = obs_costs(cam, W[oc], G[ot], uv, h)
         cost, H, g = joint_linearise(cam, W, G, oc[a], ot[a], uv[a], h, cam_col, tag_col, npar)
         cost0 = cost
         lam = 1e-3
@@ -316,7 +347,7 @@ def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_st
             except np.linalg.LinAlgError:
                 status = 2
                 break
-            d = np.linalg.solve(L.T, np.linalg.solve(L, -g))
+            d = solve_triangular(L, solve_triangular(L, -g, lower=True), lower=True, trans='T')
             Wn, Gn = W.copy(), G.copy()
             for c in cams_used:
                 Wn[c] = gn_oracle.apply_update(W[c], d[cam_col[c]:cam_col[c] + 6])
@@ -336,10 +367,11 @@ def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_st
         if status == 0 and with_std:
             dof = 8 * n_obs - 6 * len(cams_used) - 6 * len(free_tags)
             s2 = cost / dof if dof > 0 else 0.0
-            Hi = np.linalg.inv(H)
+            Li = solve_triangular(np.linalg.cholesky(H), np.eye(npar), lower=True)    # diag(H^-1)_i = |L^-1 e_i|^2
+            Hid = (Li * Li).sum(axis=0)
             for j in free_tags:
-                tag_std[ids[j]] = np.sqrt(s2 * np.diag(Hi)[tag_col[j]:tag_col[j] + 6])
-        fin = np.array([obs_cost(cam, W[oc[m]], G[ot[m]], uv[m], h) for m in range(M)])
+                tag_std[ids[j]] = np.sqrt(s2 * Hid[tag_col[j]:tag_col[j] + 6])
+        fin = obs_costs(cam, W[oc], G[ot], uv, h)
 
     # records
     for c, f in enumerate(frames):
