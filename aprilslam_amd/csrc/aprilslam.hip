@@ -116,7 +116,7 @@ struct asl_detector {
     DevBuf<float> pnp_corners;
     DevBuf<double> pnp_out;
     DevBuf<uint8_t> pnp_ok;
-    GnWorkspace gn;
+    DevBuf<uint8_t> gn_ws;  // asl_gn_solve: its inputs and the LM's buffers (gn_host.inc)
     DevBuf<uint8_t> loc_obs, loc_map, loc_out;  // asl_localize_batch: the host records' device copies (grow on demand)
     DevBuf<uint8_t> cal_ws, cal_out;  // calibration: per-frame workspace and state (k_calib.inc); asl_calibrate_batch's results
     DevBuf<uint8_t> map_ws, map_lm, map_out;  // map reconstruction (k_map.inc): sized by the input / by the problem; asl_map_batch's results
@@ -271,7 +271,7 @@ extern "C" void asl_detector_destroy(asl_detector *d)
     d->parent.release(); d->sizes.release(); d->hkeys.release(); d->points.release(); d->hcounts.release(); d->class_lists.release(); d->stage_pos.release(); d->frame_cursor.release(); d->stage_rec.release();
     d->slot_cluster.release(); d->clusters.release(); d->quads.release(); d->scratch.release(); d->side_mom.release(); d->quadH.release(); d->wtab.release(); d->dets.release();
     d->counters.release(); d->pnp_corners.release(); d->pnp_out.release(); d->pnp_ok.release();
-    d->gn.release();
+    d->gn_ws.release();
     d->loc_obs.release(); d->loc_map.release(); d->loc_out.release();
     d->cal_ws.release(); d->cal_out.release();
     d->map_ws.release(); d->map_lm.release(); d->map_out.release();
@@ -1002,12 +1002,6 @@ static int upload_obs(asl_detector *d, const char *what, const asl_obs *obs, int
     return ASL_OK;
 }
 
-// A workspace carved into consecutive pieces, each 256-byte aligned: take(bytes) returns a piece's offset, off the size so far
-struct WsCarve {
-    size_t off = 0;
-    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
-};
-
 static int check_localize_args(const void *obs, int n_frames, int max_tags, const void *map, int n_ids, const double *K, const double *dist,
                                int n_dist, double tag_size, double max_tag_rms_px, const void *out)
 {
@@ -1414,24 +1408,23 @@ static int launch_map(asl_detector *d, const void *d_obs, int n_frames, int max_
         return ASL_OK;
     }
 
-    // the problem-sized part: (camera, tag) table, LM buffers (k_gn.inc's layout)
+    // the problem-sized part: the LM's buffers (gn_lm_carve), the seed costs, the std; the reduced system reads the LM's
+    // copies of the list offsets (k_map_park empties them after the stop)
     const int n = 6 * NT;
     const size_t nc = (size_t)NC, nt = (size_t)NT, nm = (size_t)NM;
-    WsCarve p;
-    const size_t p_of = p.take(4 * nc * nt), p_flag = p.take(8), p_lm = p.take(8 * 2 * MAP_LM__N), p_Wn = p.take(8 * 12 * nc),
-                 p_Gn = p.take(8 * 12 * nt), p_D = p.take(8 * GN_DSTRIDE * nm), p_Dn = p.take(8 * GN_DSTRIDE * nm), p_co = p.take(8 * nm),
-                 p_so = p.take(8 * nm), p_Hi = p.take(8 * 36 * nc), p_gc = p.take(8 * 6 * nc), p_T = p.take(8 * 36 * nm),
-                 p_S = p.take(8 * (size_t)(n + 1) * n), p_rhs = p.take(8 * n), p_Li = p.take(8 * (size_t)((n + GN_NB - 1) / GN_NB) * GN_NB * GN_NB),
-                 p_var = p.take(8 * n), p_lcp = p.take(4 * (nc + 1)), p_ltp = p.take(4 * (nt + 1));
-    if (d->map_lm.ensure(p.off)) return fail(ASL_ENOMEM, "map workspace allocation failed");
-    uint8_t *v = d->map_lm.p;
-    a.obs_of = (int *)(v + p_of);
-    int *flag = (int *)(v + p_flag);
-    double *lm = (double *)(v + p_lm), *lm0 = lm + MAP_LM__N;
-    double *Wc = a.W, *Gc = a.G, *Wt = (double *)(v + p_Wn), *Gt = (double *)(v + p_Gn), *Dc = (double *)(v + p_D), *Dt = (double *)(v + p_Dn);
-    double *cost_obs = (double *)(v + p_co), *seed_obs = (double *)(v + p_so), *Hinv = (double *)(v + p_Hi), *gc = (double *)(v + p_gc);
-    double *Tfj = (double *)(v + p_T), *S = (double *)(v + p_S), *rhs = (double *)(v + p_rhs), *Linv = (double *)(v + p_Li), *var = (double *)(v + p_var);
-    int *lcp = (int *)(v + p_lcp), *ltp = (int *)(v + p_ltp);  // the LM's copies of the list offsets (k_map_park)
+    GnSystem sys = {nullptr, nullptr, a.cam_obs, nullptr, a.tag_obs, a.obs_cam, a.obs_tag, nullptr, NC, NT, WT};
+    GnLmBufs b;
+    double *seed_obs, *var;
+    auto carve = [&](uint8_t *base) {
+        WsCarve c{(uintptr_t)base};
+        b = gn_lm_carve(c, sys, NM, 2 * MAP_LM__N);
+        seed_obs = c.take<double>(nm); var = c.take<double>(n); sys.cam_ptr = c.take<int>(nc + 1); sys.tag_ptr = c.take<int>(nt + 1);
+        return c.off;
+    };
+    if (d->map_lm.ensure(carve(nullptr))) return fail(ASL_ENOMEM, "map workspace allocation failed");
+    carve(d->map_lm.p);
+    a.obs_of = sys.obs_of;
+    double *lm = b.lm, *lm0 = lm + MAP_LM__N;
     const dim3 wg(MAP_WG);
 
     range_push("map: seed");
@@ -1449,44 +1442,34 @@ static int launch_map(asl_detector *d, const void *d_obs, int n_frames, int max_
     hipLaunchKernelGGL(k_map_behind, dim3((NC + 63) / 64), dim3(64), 0, st, a, NC, cam.half);
     hipLaunchKernelGGL(k_map_csr, dim3(1), wg, 0, st, a, NC, NT);
     hipLaunchKernelGGL(k_map_lm_init, dim3(1), dim3(1), 0, st, (const MapHead *)a.head, lm, lm0);
-    HIPCHK(hipMemsetAsync(flag, 0, 8, st));
+    HIPCHK(hipMemsetAsync(b.flag, 0, 8, st));
     range_pop();
 
     range_push("map: LM");
-    const unsigned int lin_blocks = (unsigned int)((NM + 3) / 4);
-    hipLaunchKernelGGL(k_map_linearize, dim3(lin_blocks), dim3(256), 0, st, a, Wc, Gc, NM, cam, Dc, cost_obs, lm, 1);
-    hipLaunchKernelGGL(k_gn_cost, dim3(1), dim3(256), 0, st, cost_obs, NM, lm + GN_LM_COST);
-    HIPCHK(hipMemcpyAsync(lm + GN_LM_COST0, lm + GN_LM_COST, 8, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(seed_obs, cost_obs, 8 * nm, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(lcp, a.cam_ptr, 4 * (nc + 1), hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(ltp, a.tag_ptr, 4 * (nt + 1), hipMemcpyDeviceToDevice, st));
-    // reduced system, factorisation, step (gn_host.inc) over the LM's copies of the list offsets
-    const GnSystem sys = {Dc, lcp, a.cam_obs, ltp, a.tag_obs, a.obs_cam, a.obs_tag, a.obs_of, NC, NT, WT, Hinv, gc, Tfj, S, rhs, Linv};
-    const size_t nw = 12 * nc, ng = 12 * nt, nd = (size_t)GN_DSTRIDE * nm;
-    for (int it = 0; it < max_iters; it++) {
-        int rc = gn_factor_step(sys, lm, flag, st, Wc, Gc, Wt, Gt);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_map_linearize, dim3(lin_blocks), dim3(256), 0, st, a, Wt, Gt, NM, cam, Dt, cost_obs, lm, 0);
-        hipLaunchKernelGGL(k_gn_cost, dim3(1), dim3(256), 0, st, cost_obs, NM, lm + GN_LM_TRIAL);
-        hipLaunchKernelGGL(k_map_decide, dim3(1), dim3(1), 0, st, lm, flag);
-        hipLaunchKernelGGL(k_gn_commit, dim3((unsigned int)std::min<size_t>((nw + ng + nd + 255) / 256, 1024)), dim3(256), 0, st, lm, Wt, Gt, Dt,
-                           Wc, Gc, Dc, nw, ng, nd);
-        hipLaunchKernelGGL(k_map_park, dim3((NC + NT + 2 + 255) / 256), dim3(256), 0, st, lm, lcp, NC, ltp, NT);
-    }
+    auto lin = [&](const double *W, const double *G, double *D, int force) {
+        hipLaunchKernelGGL(k_map_linearize, dim3((NM + 3) / 4), dim3(256), 0, st, a, W, G, NM, cam, D, b.cost_obs, lm, force);
+    };
+    auto decide = [&]() { hipLaunchKernelGGL(k_map_decide, dim3(1), dim3(1), 0, st, lm, b.flag); };
+    auto park = [&]() {
+        hipLaunchKernelGGL(k_map_park, dim3((NC + NT + 2 + 255) / 256), dim3(256), 0, st, lm, sys.cam_ptr, NC, sys.tag_ptr, NT);
+    };
+    HIPCHK(hipMemcpyAsync(sys.cam_ptr, a.cam_ptr, 4 * (nc + 1), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(sys.tag_ptr, a.tag_ptr, 4 * (nt + 1), hipMemcpyDeviceToDevice, st));
+    int rc = gn_lm_run(sys, b, a.W, a.G, NM, max_iters, seed_obs, lin, decide, park, st);
+    if (rc) return rc;
     // the final state's per-observation costs (and its blocks again, for the std)
-    hipLaunchKernelGGL(k_map_linearize, dim3(lin_blocks), dim3(256), 0, st, a, Wc, Gc, NM, cam, Dc, cost_obs, lm, 1);
+    lin(a.W, a.G, sys.D, 1);
     range_pop();
     if (d_std) {
         GnSystem full = sys;  // undamped, over every active observation
         full.cam_ptr = a.cam_ptr;
         full.tag_ptr = a.tag_ptr;
-        int rc = gn_factor_step(full, lm0, flag + 1, st);
+        rc = gn_factor_step(full, lm0, b.flag + 1, st);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_map_std, dim3(n), dim3(256), (size_t)n * sizeof(double), st, S, Linv, n, var);
+        hipLaunchKernelGGL(k_map_std, dim3(n), dim3(256), (size_t)n * sizeof(double), st, sys.S, sys.Linv, n, var);
     }
-    hipLaunchKernelGGL(k_map_finish, dim3(1), wg, 0, st, a, NC, NT, NM, WT, 0, lm, cost_obs, seed_obs, d_std ? var : nullptr, flag + 1,
-                       (MapTagRec *)d_map,
-                       (double *)d_std, (CamPoseRec *)d_poses, (MapResultRec *)d_result);
+    hipLaunchKernelGGL(k_map_finish, dim3(1), wg, 0, st, a, NC, NT, NM, WT, 0, lm, b.cost_obs, seed_obs, d_std ? var : nullptr, b.flag + 1,
+                       (MapTagRec *)d_map, (double *)d_std, (CamPoseRec *)d_poses, (MapResultRec *)d_result);
     HIPCHK(hipGetLastError());
     return ASL_OK;
 }

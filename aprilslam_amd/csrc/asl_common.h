@@ -37,6 +37,16 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
 };
 
+// A workspace carved into consecutive pieces, each 256-byte aligned: take(bytes) returns a piece's offset, off the size so
+// far; take<T>(n) a piece of n T's at base + offset (a carve with base 0 sizes the workspace, then one at its address)
+struct WsCarve {
+    uintptr_t base = 0;
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
+    template <typename T>
+    T *take(size_t n) { return (T *)(base + take(sizeof(T) * n)); }
+};
+
 // Geometry of one batch, passed by value to every kernel.
 struct Geom {
     int w, h;          // full-resolution frame

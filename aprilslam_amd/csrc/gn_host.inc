@@ -1,10 +1,10 @@
-// Host loop of the pose-graph Levenberg-Marquardt back-end (kernels: k_gn.inc), and the reduced-system sequence the map
-// solver (k_map.inc) shares with it.
+// Host side of the pose-graph Levenberg-Marquardt back-end (kernels: k_gn.inc): the LM's buffers, the reduced-system
+// sequence and the trial loop that asl_gn_solve and the map solver (k_map.inc, launch_map) share, and asl_gn_solve itself.
 
 // One problem's reduced system on the device: observation blocks D, the active lists and (camera, tag) table, scratch
 struct GnSystem {
-    const double *D;
-    const int *cam_ptr, *cam_obs, *tag_ptr, *tag_obs, *obs_cam, *obs_tag, *obs_of;
+    double *D;
+    int *cam_ptr, *cam_obs, *tag_ptr, *tag_obs, *obs_cam, *obs_tag, *obs_of;
     int n_cams, n_tags, fixed_tag;
     double *Hinv, *gc, *Tfj, *S, *rhs, *Linv;
 };
@@ -33,6 +33,53 @@ static int gn_factor_step(const GnSystem &g, const double *lm, int *fail_flag, h
     hipLaunchKernelGGL(k_gn_trisolve, dim3(1), dim3(GN_TRI_THREADS), (size_t)n * sizeof(double), st, g.S, g.Linv, g.rhs, n);
     hipLaunchKernelGGL(k_gn_update, dim3((g.n_cams + g.n_tags + 63) / 64), dim3(64), 0, st, g.D, g.Hinv, g.gc, g.cam_ptr, g.cam_obs,
                        g.obs_tag, g.rhs, g.n_cams, g.n_tags, W, G, Wn, Gn);
+    return ASL_OK;
+}
+
+// The LM's buffers beside the reduced system: two failure flags (the LM's factorisation, and one for the caller), the LM
+// state (n_lm doubles), trial poses and blocks, per-observation costs.  gn_lm_carve carves them and the reduced system's
+// problem-sized ones (blocks D, (camera, tag) table, scratch) for sys.n_cams cameras and sys.n_tags tags.
+struct GnLmBufs {
+    int *flag;
+    double *lm, *Wn, *Gn, *Dn, *cost_obs;
+};
+
+static GnLmBufs gn_lm_carve(WsCarve &c, GnSystem &sys, int n_obs, int n_lm)
+{
+    const size_t nc = (size_t)sys.n_cams, nt = (size_t)sys.n_tags, nm = (size_t)n_obs, n = 6 * nt;
+    GnLmBufs b;
+    sys.obs_of = c.take<int>(nc * nt); b.flag = c.take<int>(2); b.lm = c.take<double>((size_t)n_lm);
+    b.Wn = c.take<double>(12 * nc); b.Gn = c.take<double>(12 * nt);
+    sys.D = c.take<double>(GN_DSTRIDE * nm); b.Dn = c.take<double>(GN_DSTRIDE * nm); b.cost_obs = c.take<double>(nm);
+    sys.Hinv = c.take<double>(36 * nc); sys.gc = c.take<double>(6 * nc); sys.Tfj = c.take<double>(36 * nm);
+    sys.S = c.take<double>((n + 1) * n);  // row n carries the right-hand side through the factorisation
+    sys.rhs = c.take<double>(n); sys.Linv = c.take<double>((n + GN_NB - 1) / GN_NB * GN_NB * GN_NB);
+    return b;
+}
+
+// The LM, all enqueued on st: the current state (W, G, sys.D) linearised and costed (lm[GN_LM_COST], and COST0; its
+// per-observation costs also to seed_obs, if given), then iters trials: the damped step into (b.Wn, b.Gn), linearised into
+// b.Dn, costed (lm[GN_LM_TRIAL]), decided and committed.  lin(W, G, D, force) enqueues a linearisation into D and
+// b.cost_obs, decide() the accept rule, tail() whatever follows a trial.
+template <class Lin, class Decide, class Tail>
+static int gn_lm_run(const GnSystem &sys, const GnLmBufs &b, double *W, double *G, int n_obs, int iters, double *seed_obs, Lin lin,
+                     Decide decide, Tail tail, hipStream_t st)
+{
+    lin(W, G, sys.D, 1);
+    hipLaunchKernelGGL(k_gn_cost, dim3(1), dim3(256), 0, st, b.cost_obs, n_obs, b.lm + GN_LM_COST);
+    HIPCHK(hipMemcpyAsync(b.lm + GN_LM_COST0, b.lm + GN_LM_COST, 8, hipMemcpyDeviceToDevice, st));
+    if (seed_obs) HIPCHK(hipMemcpyAsync(seed_obs, b.cost_obs, 8 * (size_t)n_obs, hipMemcpyDeviceToDevice, st));
+    const size_t nw = (size_t)12 * sys.n_cams, ng = (size_t)12 * sys.n_tags, nd = (size_t)GN_DSTRIDE * n_obs;
+    const unsigned int commit_blocks = (unsigned int)std::min<size_t>((nw + ng + nd + 255) / 256, 1024);
+    for (int it = 0; it < iters; it++) {
+        int rc = gn_factor_step(sys, b.lm, b.flag, st, W, G, b.Wn, b.Gn);
+        if (rc) return rc;
+        lin(b.Wn, b.Gn, b.Dn, 0);
+        hipLaunchKernelGGL(k_gn_cost, dim3(1), dim3(256), 0, st, b.cost_obs, n_obs, b.lm + GN_LM_TRIAL);
+        decide();
+        hipLaunchKernelGGL(k_gn_commit, dim3(commit_blocks), dim3(256), 0, st, b.lm, b.Wn, b.Gn, b.Dn, W, G, sys.D, nw, ng, nd);
+        tail();
+    }
     return ASL_OK;
 }
 
@@ -70,8 +117,6 @@ extern "C" int asl_gn_solve(asl_detector *d, int n_cams, int n_tags, int n_obs, 
     if (fixed_tag < 0 || fixed_tag >= n_tags) return fail(ASL_EINVAL, "fixed_tag out of range");
     if ((long long)n_tags * 6 > 6000) return fail(ASL_EINVAL, "more than 1000 tags: the dense reduced system is not meant for that");
     HIPCHK(hipSetDevice(d->device));
-    GnWorkspace &w = d->gn;
-    const int n = 6 * n_tags;
 
     // CSR lists by camera and by tag (observation order kept), and the (camera, tag) -> observation table
     std::vector<int> cam_ptr(n_cams + 1, 0), tag_ptr(n_tags + 1, 0), cam_obs(n_obs), tag_obs(n_obs), obs_of((size_t)n_cams * n_tags, -1);
@@ -92,14 +137,21 @@ extern "C" int asl_gn_solve(asl_detector *d, int n_cams, int n_tags, int n_obs, 
     for (int f = 0; f < n_cams; f++) gn_rigid_inverse(cam_T + 16 * (size_t)f, &W[12 * (size_t)f]);
     for (int j = 0; j < n_tags; j++) gn_pack(tag_T + 16 * (size_t)j, &G[12 * (size_t)j]);
 
-    int bad = 0;
-    bad |= w.W.ensure(W.size()); bad |= w.Wn.ensure(W.size()); bad |= w.G.ensure(G.size()); bad |= w.Gn.ensure(G.size());
-    bad |= w.corners.ensure((size_t)8 * n_obs); bad |= w.D.ensure((size_t)GN_DSTRIDE * n_obs); bad |= w.Dn.ensure((size_t)GN_DSTRIDE * n_obs);
-    bad |= w.cost_obs.ensure(n_obs); bad |= w.Hinv.ensure((size_t)36 * n_cams); bad |= w.gc.ensure((size_t)6 * n_cams);
-    bad |= w.Tfj.ensure((size_t)36 * n_obs); bad |= w.S.ensure((size_t)(n + 1) * n) /* row n carries the right-hand side through the factorisation */; bad |= w.rhs.ensure(n); bad |= w.cost.ensure(GN_LM__N); bad |= w.Linv.ensure((size_t)((n + GN_NB - 1) / GN_NB) * GN_NB * GN_NB);
-    bad |= w.obs_cam.ensure(n_obs); bad |= w.obs_tag.ensure(n_obs); bad |= w.cam_ptr.ensure(n_cams + 1); bad |= w.cam_obs.ensure(n_obs);
-    bad |= w.tag_ptr.ensure(n_tags + 1); bad |= w.tag_obs.ensure(n_obs); bad |= w.obs_of.ensure(obs_of.size()); bad |= w.flag.ensure(1);
-    if (bad) return fail(ASL_ENOMEM, "Gauss-Newton workspace allocation failed");
+    // one workspace: the inputs (poses, corners, observation lists and their CSR) and the LM's buffers
+    GnSystem sys{};
+    sys.n_cams = n_cams; sys.n_tags = n_tags; sys.fixed_tag = fixed_tag;
+    double *Wc, *Gc, *corners;
+    GnLmBufs b;
+    auto carve = [&](uint8_t *base) {
+        WsCarve c{(uintptr_t)base};
+        Wc = c.take<double>(W.size()); Gc = c.take<double>(G.size()); corners = c.take<double>((size_t)8 * n_obs);
+        sys.obs_cam = c.take<int>(n_obs); sys.obs_tag = c.take<int>(n_obs); sys.cam_ptr = c.take<int>(cam_ptr.size());
+        sys.cam_obs = c.take<int>(n_obs); sys.tag_ptr = c.take<int>(tag_ptr.size()); sys.tag_obs = c.take<int>(n_obs);
+        b = gn_lm_carve(c, sys, n_obs, GN_LM__N);
+        return c.off;
+    };
+    if (d->gn_ws.ensure(carve(nullptr))) return fail(ASL_ENOMEM, "Gauss-Newton workspace allocation failed");
+    carve(d->gn_ws.p);
     // a stream of its own, at the highest priority: the solve is a chain of small launches and read-backs, and behind a
     // detector batch on a shared queue every one of them would wait for the whole batch
     if (!d->aux_stream) {
@@ -108,48 +160,35 @@ extern "C" int asl_gn_solve(asl_detector *d, int n_cams, int n_tags, int n_obs, 
         HIPCHK(hipStreamCreateWithPriority(&d->aux_stream, hipStreamNonBlocking, hi));
     }
     hipStream_t st = d->aux_stream;
-    HIPCHK(hipMemcpyAsync(w.W.p, W.data(), W.size() * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(w.G.p, G.data(), G.size() * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(w.corners.p, obs_corners, (size_t)8 * n_obs * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(w.obs_cam.p, obs_cam, (size_t)n_obs * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(w.obs_tag.p, obs_tag, (size_t)n_obs * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(w.cam_ptr.p, cam_ptr.data(), cam_ptr.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(w.cam_obs.p, cam_obs.data(), cam_obs.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(w.tag_ptr.p, tag_ptr.data(), tag_ptr.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(w.tag_obs.p, tag_obs.data(), tag_obs.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(w.obs_of.p, obs_of.data(), obs_of.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(w.flag.p, 0, 4, st));
+    HIPCHK(hipMemcpyAsync(Wc, W.data(), W.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(Gc, G.data(), G.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(corners, obs_corners, (size_t)8 * n_obs * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sys.obs_cam, obs_cam, (size_t)n_obs * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sys.obs_tag, obs_tag, (size_t)n_obs * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sys.cam_ptr, cam_ptr.data(), cam_ptr.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sys.cam_obs, cam_obs.data(), cam_obs.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sys.tag_ptr, tag_ptr.data(), tag_ptr.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sys.tag_obs, tag_obs.data(), tag_obs.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sys.obs_of, obs_of.data(), obs_of.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(b.flag, 0, 4, st));
 
-    GnCam cam = {K[0], K[4], K[2], K[5], (double)(float)(tag_size / 2)};
-    auto linearize = [&](double *Wp, double *Gp, double *Dp, int slot) {
-        hipLaunchKernelGGL(k_gn_linearize, dim3((n_obs + 3) / 4), dim3(256), 0, st, Wp, Gp, w.obs_cam.p, w.obs_tag.p, w.corners.p, n_obs, cam, Dp,
-                           w.cost_obs.p);
-        hipLaunchKernelGGL(k_gn_cost, dim3(1), dim3(256), 0, st, w.cost_obs.p, n_obs, w.cost.p + slot);
+    const CamDev cam = make_cam(d, K, nullptr, 0, tag_size);
+    auto lin = [&](const double *Wp, const double *Gp, double *Dp, int) {
+        hipLaunchKernelGGL(k_gn_linearize, dim3((n_obs + 3) / 4), dim3(256), 0, st, Wp, Gp, sys.obs_cam, sys.obs_tag, corners, n_obs, cam, Dp, b.cost_obs);
     };
-    // The whole solve is enqueued at once: cost, lambda and the accept / reject decision live in device memory (w.cost),
-    // an accepted trial is copied over the current state, and the host waits exactly once, at the end.
-    double *Wc = w.W.p, *Gc = w.G.p, *Wt = w.Wn.p, *Gt = w.Gn.p, *Dc = w.D.p, *Dt = w.Dn.p;
+    auto decide = [&]() { hipLaunchKernelGGL(k_gn_decide, dim3(1), dim3(1), 0, st, b.lm); };
+    // The whole solve is enqueued at once: cost, lambda and the accept / reject decision live in device memory (b.lm), an
+    // accepted trial is copied over the current state, and the host waits exactly once, at the end.
     range_push("G pose-graph LM");
     double lm_init[GN_LM__N] = {0, 0, 1e-3, 0, 0, 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(w.cost.p, lm_init, sizeof lm_init, hipMemcpyHostToDevice, st));
-    linearize(Wc, Gc, Dc, GN_LM_COST);
-    HIPCHK(hipMemcpyAsync(w.cost.p + GN_LM_COST0, w.cost.p + GN_LM_COST, 8, hipMemcpyDeviceToDevice, st));
-    const size_t nw = (size_t)12 * n_cams, ng = (size_t)12 * n_tags, nd = (size_t)GN_DSTRIDE * n_obs;
-    const GnSystem sys = {Dc, w.cam_ptr.p, w.cam_obs.p, w.tag_ptr.p, w.tag_obs.p, w.obs_cam.p, w.obs_tag.p, w.obs_of.p, n_cams, n_tags,
-                          fixed_tag, w.Hinv.p, w.gc.p, w.Tfj.p, w.S.p, w.rhs.p, w.Linv.p};
-    for (int it = 0; it < iters; it++) {
-        int rc = gn_factor_step(sys, w.cost.p, w.flag.p, st, Wc, Gc, Wt, Gt);
-        if (rc) return rc;
-        linearize(Wt, Gt, Dt, GN_LM_TRIAL);
-        hipLaunchKernelGGL(k_gn_decide, dim3(1), dim3(1), 0, st, w.cost.p);
-        hipLaunchKernelGGL(k_gn_commit, dim3((unsigned int)std::min<size_t>((nw + ng + nd + 255) / 256, 1024)), dim3(256), 0, st, w.cost.p, Wt, Gt, Dt, Wc, Gc, Dc,
-                           nw, ng, nd);
-    }
+    HIPCHK(hipMemcpyAsync(b.lm, lm_init, sizeof lm_init, hipMemcpyHostToDevice, st));
+    int rc = gn_lm_run(sys, b, Wc, Gc, n_obs, iters, nullptr, lin, decide, [] {}, st);
+    if (rc) return rc;
     double lm[GN_LM__N];
-    HIPCHK(hipMemcpyAsync(lm, w.cost.p, sizeof lm, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(lm, b.lm, sizeof lm, hipMemcpyDeviceToHost, st));
     HIPCHK(hipGetLastError());
     int flag = 0;
-    HIPCHK(hipMemcpyAsync(&flag, w.flag.p, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&flag, b.flag, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(W.data(), Wc, W.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(G.data(), Gc, G.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));

@@ -1,33 +1,27 @@
 // Pose-graph Levenberg-Marquardt back-end (row G of SURVEY.md section 8a) -- NOT in the reference
 // (slam_graph.py:72-76 is a stub); build-defined; the tests hold a NumPy restatement of the same step.
 //
-// Unknowns: camera poses W_f (camera<-world) and tag poses G_j (world<-tag), 12 doubles each
-// (R row-major, t).  Observation m = (camera f, tag j, 4 pixel corners); residual = pinhole
-// projection of W_f G_j X_k minus the corner, 8 per observation.  Left-multiplicative updates
+// Unknowns: camera poses W_f (camera<-world) and tag poses G_j (world<-tag), 12 doubles each (R row-major, t).
+// Observation m = (camera f, tag j, 4 pixel corners); residual = projection of W_f G_j X_k minus the corner, 8 per
+// observation (asl_gn_solve: pinhole; the map solver, k_map.inc: the k_pnp.inc lens model).  Left-multiplicative updates
 // (omega, v): R <- exp(omega) R, t <- exp(omega) t + v.
 //
-// One LM step on the device:
-//   k_gn_linearize  one wavefront per observation.  The 8 x 12 Jacobian [J_cam | J_tag] and the
-//                   residual are built in registers, and the 12 x 12 normal block J^T J together with
-//                   J^T r (as a 13th column) comes out of TWO v_mfma_f64_16x16x4_f64 issues (K = 8 =
-//                   2 x 4): A[i][k] = J[k][i], B[k][j] = [J | r][k][j].  This is the only MFMA use on
-//                   the whole path -- the contraction is 8-deep and 12 wide, so the matrix pipe is used,
-//                   not filled.
-//   k_gn_reduce     per-camera / per-tag sums of the observation blocks in observation order
-//                   (deterministic, no float atomics), LM damping, 6x6 camera inverses
-//   k_gn_schur      reduced tag system S = H_ll - sum_f W_fj^T H_cc^-1 W_fj', rhs likewise
-//   k_gn_chol_*     blocked dense Cholesky of S (diagonal block, panel, trailing update per block column)
-//   k_gn_trisolve   the two triangular solves
-//   k_gn_backsub    camera steps, trial poses
-// The host loop (gn_host.inc) accepts a step when the cost decreases (lambda *= 0.1) else lambda *= 10.
-
+// One LM step on the device (gn_host.inc enqueues the whole loop, gn_lm_run, for both solvers):
+//   gn_obs_block     one wavefront per observation (in k_gn_linearize / k_map_linearize, with their camera model): the
+//                    8 x 12 Jacobian [J_cam | J_tag] and the residual in registers, the 12 x 12 normal block J^T J with
+//                    J^T r as a 13th column from TWO v_mfma_f64_16x16x4_f64 issues (K = 8 = 2 x 4: used, not filled)
+//   k_gn_reduce_cam  per-camera sums of the observation blocks in observation order (deterministic, no float
+//                    atomics), LM damping, 6x6 camera inverses
+//   k_gn_schur       reduced tag system S = H_ll - sum_f W_fj^T H_cc^-1 W_fj', rhs likewise
+//   k_gn_chol_*      blocked dense Cholesky of S (diagonal block, panel, MFMA trailing update per block column); the rhs
+//                    rides along as row n, so the forward substitution comes out of it
+//   k_gn_trisolve    the back substitution;  k_gn_update  camera steps, trial poses
+//   k_gn_cost, k_gn_decide (gn_accept: cost down, lambda *= 0.1; else lambda *= 10), k_gn_commit (an accepted trial)
 typedef double gn_v4d __attribute__((ext_vector_type(4)));
 
 #define GN_DSTRIDE 156  /* 12 x 13 doubles per observation */
 // LM state in device memory, so that a whole solve is enqueued without a host round trip per iteration
 enum { GN_LM_COST = 0, GN_LM_TRIAL, GN_LM_LAMBDA, GN_LM_ACCEPTED, GN_LM_FLAG, GN_LM_COST0, GN_LM__N = 8 };
-
-struct GnCam { double fx, fy, cx, cy, half; };
 
 __device__ __forceinline__ void gn_exp_rot(const double *w, double *R)
 {
@@ -40,36 +34,28 @@ __device__ __forceinline__ void gn_exp_rot(const double *w, double *R)
     R[6] = -s * y + c1 * x * z;         R[7] = s * x + c1 * y * z;        R[8] = 1 + c1 * (-(x * x + y * y));
 }
 
-// one wavefront per observation; blockDim = 256 (4 observations per workgroup)
-__global__ void __launch_bounds__(256) k_gn_linearize(const double *__restrict__ W, const double *__restrict__ G, const int *__restrict__ obs_cam,
-                                                      const int *__restrict__ obs_tag, const double *__restrict__ obs_corners, int n_obs,
-                                                      GnCam cam, double *__restrict__ D, double *__restrict__ cost_obs)
+// One observation's 12 x 13 block [J^T J | J^T r] at Dm, by one wavefront, for the poses Wf (camera<-world) and Gj
+// (world<-tag); returns the observation's cost in lane 0.  Residual rows k = kk, kk + 4 (corner k >> 1, component k & 1)
+// are the K slices of the two MFMA issues: A[i][k] = J[k][i], B[k][j] = [J | r][k][j].  row(k, p, jp, add), the camera
+// model at the camera-frame corner p, returns residual k and writes d u / d p (row k & 1) to jp, the row's cost to add.
+template <class Row>
+__device__ __forceinline__ double gn_obs_block(const double *Wf, const double *Gj, double half, int lane, Row row, double *Dm)
 {
-    const int lane = threadIdx.x & 63;
-    const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (m >= n_obs) return;
-    const double *Wf = W + 12 * (size_t)obs_cam[m], *Gj = G + 12 * (size_t)obs_tag[m];
     const int n = lane & 15, kk = lane >> 4;
     gn_v4d acc = {0, 0, 0, 0};
     double rsq = 0;
 #pragma unroll
     for (int step = 0; step < 2; step++) {
-        const int k = kk + 4 * step;        // residual row: corner k>>1, component k&1
-        const int corner = k >> 1, comp = k & 1;
-        const double ox = (corner == 1 || corner == 2) ? cam.half : -cam.half, oy = (corner >= 2) ? cam.half : -cam.half;
+        const int k = kk + 4 * step;
+        const int corner = k >> 1;
+        const double ox = (corner == 1 || corner == 2) ? half : -half, oy = (corner >= 2) ? half : -half;
         double q[3], p[3];
 #pragma unroll
         for (int r = 0; r < 3; r++) q[r] = Gj[3 * r] * ox + Gj[3 * r + 1] * oy + Gj[9 + r];
 #pragma unroll
         for (int r = 0; r < 3; r++) p[r] = Wf[3 * r] * q[0] + Wf[3 * r + 1] * q[1] + Wf[3 * r + 2] * q[2] + Wf[9 + r];
-        double iz = 1.0 / p[2];
-        double u = comp == 0 ? cam.fx * p[0] * iz + cam.cx : cam.fy * p[1] * iz + cam.cy;
-        double res = u - obs_corners[8 * (size_t)m + k];
-        // d u / d p (row `comp` of the 2x3 projection Jacobian)
-        double jp[3];
-        jp[0] = comp == 0 ? cam.fx * iz : 0.0;
-        jp[1] = comp == 0 ? 0.0 : cam.fy * iz;
-        jp[2] = comp == 0 ? -cam.fx * p[0] * iz * iz : -cam.fy * p[1] * iz * iz;
+        double jp[3], add;
+        const double res = row(k, p, jp, add);
         // camera block: dp/d(omega,v) = [-[p]x | I]  ->  jp * that
         double Jrow[12];
         Jrow[0] = p[1] * jp[2] - p[2] * jp[1];   // jp (-[p]x) = (p x jp)^T
@@ -90,19 +76,42 @@ __global__ void __launch_bounds__(256) k_gn_linearize(const double *__restrict__
         double av = n < 12 ? sel : 0.0;
         double bv = n < 12 ? sel : (n == 12 ? res : 0.0);
         acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-        if (n == 0) rsq += res * res;  // one lane per residual row
+        if (n == 0) rsq += add;  // one lane per residual row
     }
-    // D[row][col]: lane holds rows (lane>>4) + 4i, column lane&15
-    double *Dm = D + (size_t)m * GN_DSTRIDE;
+    // Dm[row][col]: lane holds rows (lane>>4) + 4i, column lane&15
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-        int row = kk + 4 * i;
-        if (row < 12 && n < 13) Dm[row * 13 + n] = acc[i];
+        int r = kk + 4 * i;
+        if (r < 12 && n < 13) Dm[r * 13 + n] = acc[i];
     }
     // cost of this observation: lanes 0,16,32,48 hold two rows each
     double c = rsq;
     c += __shfl_xor(c, 16);
     c += __shfl_xor(c, 32);
+    return c;
+}
+
+// one wavefront per observation (gn_obs_block, pinhole camera); blockDim = 256 (4 observations per workgroup)
+__global__ void __launch_bounds__(256) k_gn_linearize(const double *__restrict__ W, const double *__restrict__ G, const int *__restrict__ obs_cam,
+                                                      const int *__restrict__ obs_tag, const double *__restrict__ obs_corners, int n_obs,
+                                                      CamDev cam, double *__restrict__ D, double *__restrict__ cost_obs)
+{
+    const int lane = threadIdx.x & 63;
+    const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= n_obs) return;
+    const double *corners = obs_corners + 8 * (size_t)m;
+    auto row = [=](int k, const double *p, double *jp, double &add) {
+        const int comp = k & 1;
+        double iz = 1.0 / p[2];
+        double u = comp == 0 ? cam.fx * p[0] * iz + cam.cx : cam.fy * p[1] * iz + cam.cy;
+        double res = u - corners[k];
+        jp[0] = comp == 0 ? cam.fx * iz : 0.0;
+        jp[1] = comp == 0 ? 0.0 : cam.fy * iz;
+        jp[2] = comp == 0 ? -cam.fx * p[0] * iz * iz : -cam.fy * p[1] * iz * iz;
+        add = res * res;
+        return res;
+    };
+    const double c = gn_obs_block(W + 12 * (size_t)obs_cam[m], G + 12 * (size_t)obs_tag[m], cam.half, lane, row, D + (size_t)m * GN_DSTRIDE);
     if (lane == 0) cost_obs[m] = c;
 }
 
@@ -121,19 +130,22 @@ __global__ void __launch_bounds__(256) k_gn_cost(const double *__restrict__ cost
     if (threadIdx.x == 0) *out = s[0];
 }
 
-// accept the trial step if the cost went down (lambda /= 10), otherwise keep the current poses (lambda *= 10)
-__global__ void k_gn_decide(double *lm)
+// the accept rule: a trial that lowers the cost is taken (lambda /= 10, counted), otherwise the current poses stay
+// (lambda *= 10); FLAG and the return value say which
+__device__ __forceinline__ bool gn_accept(double *lm)
 {
-    if (lm[GN_LM_TRIAL] < lm[GN_LM_COST]) {
+    const bool take = lm[GN_LM_TRIAL] < lm[GN_LM_COST];
+    if (take) {
         lm[GN_LM_COST] = lm[GN_LM_TRIAL];
         lm[GN_LM_LAMBDA] = fmax(lm[GN_LM_LAMBDA] * 0.1, 1e-12);
         lm[GN_LM_ACCEPTED] += 1.0;
-        lm[GN_LM_FLAG] = 1.0;
-    } else {
+    } else
         lm[GN_LM_LAMBDA] *= 10.0;
-        lm[GN_LM_FLAG] = 0.0;
-    }
+    lm[GN_LM_FLAG] = take ? 1.0 : 0.0;
+    return take;
 }
+
+__global__ void k_gn_decide(double *lm) { gn_accept(lm); }
 
 // an accepted trial becomes the current state: poses and the linearisation that was computed for them
 __global__ void __launch_bounds__(256) k_gn_commit(const double *__restrict__ lm, const double *__restrict__ Wt, const double *__restrict__ Gt,
@@ -538,15 +550,3 @@ __global__ void __launch_bounds__(64) k_gn_update(const double *__restrict__ D, 
         dst[9 + r] = R[3 * r] * src[9] + R[3 * r + 1] * src[10] + R[3 * r + 2] * src[11] + d[3 + r];
     }
 }
-
-struct GnWorkspace {
-    DevBuf<double> W, G, Wn, Gn, corners, D, Dn, cost_obs, Hinv, gc, Tfj, S, rhs, cost, Linv;
-    DevBuf<int> obs_cam, obs_tag, cam_ptr, cam_obs, tag_ptr, tag_obs, obs_of, flag;
-    void release()
-    {
-        W.release(); G.release(); Wn.release(); Gn.release(); corners.release(); D.release(); Dn.release(); cost_obs.release();
-        Hinv.release(); gc.release(); Tfj.release(); S.release(); rhs.release(); cost.release(); Linv.release();
-        obs_cam.release(); obs_tag.release(); cam_ptr.release(); cam_obs.release(); tag_ptr.release(); tag_obs.release();
-        obs_of.release(); flag.release();
-    }
-};

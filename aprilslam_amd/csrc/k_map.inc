@@ -15,10 +15,10 @@
 //   k_map_flip      per tag: the pose and its mirror (built in the view of largest area) each polished by pose-only LM
 //                   (k_localize.inc: pose_lm)
 //   k_map_behind    per camera: observations with a corner at z <= 1e-6 leave; a camera left with < 2 is dropped
-//   then k_gn.inc's Levenberg-Marquardt step, unchanged (k_gn_reduce_cam, k_gn_schur, the blocked Cholesky,
-//   k_gn_trisolve, k_gn_update, k_gn_cost, k_gn_commit) around k_map_linearize (the lens-aware counterpart of
-//   k_gn_linearize: same 12 x 13 block per observation, same MFMA contraction) and k_map_decide (the accept / stop rule); after the stop k_map_park empties the
-//                   LM's copy of the list offsets, so that the remaining trials reduce and factor an identity system;
+//   then gn_host.inc's LM loop (gn_lm_run: k_gn.inc's reduced system, Cholesky, step, cost and commit) with
+//   k_map_linearize (k_gn.inc's gn_obs_block with the lens model), k_map_decide (gn_accept, and the stop rule) and, after
+//   each trial, k_map_park: after the stop it empties the LM's copy of the list offsets, so that the remaining trials
+//   reduce and factor an identity system;
 //   k_map_std       per tag parameter: diag of S^-1 = |L^-1 e_i|^2 by blocked forward substitution with the factor
 //   k_map_finish    one workgroup: the records.
 // No atomics: every sum has a fixed order (wave butterflies, per-thread loops in list order, k_gn_cost's fixed tree), so the
@@ -520,9 +520,9 @@ __global__ void k_map_lm_init(const MapHead *head, double *lm, double *lm0)
     if (head->n_act == 0) { lm[MAP_LM_STOP] = 1; lm[MAP_LM_STATUS] = 1; }
 }
 
-// k_gn_linearize with the k_pnp.inc camera model: one wavefront per observation, the same 12 x 13 block [J^T J | J^T r] per
-// observation (GN_DSTRIDE) from two v_mfma_f64_16x16x4_f64; a corner at z <= 1e-9 costs 1e12 and adds no row.  Inactive
-// observations cost 0 and leave their block alone (no list refers to it).  Nothing happens after the stop unless forced.
+// k_gn_linearize with the k_pnp.inc camera model: one wavefront per observation, gn_obs_block with project_dev; a corner at
+// z <= 1e-9 costs 1e12 and adds no row.  Inactive observations cost 0 and leave their block alone (no list refers to it).
+// Nothing happens after the stop unless forced.
 __global__ void __launch_bounds__(256) k_map_linearize(MapArgs a, const double *__restrict__ W, const double *__restrict__ G, int n_obs, CamDev cam,
                                                        double *__restrict__ D, double *__restrict__ cost_obs, const double *__restrict__ lm, int force)
 {
@@ -533,23 +533,13 @@ __global__ void __launch_bounds__(256) k_map_linearize(MapArgs a, const double *
         if (lane == 0) cost_obs[m] = 0.0;
         return;
     }
-    const double *Wf = W + 12 * (size_t)a.obs_cam[m], *Gj = G + 12 * (size_t)a.obs_tag[m];
     const ObsRec &o = a.obs[a.obs_slot[m]];
-    const int n = lane & 15, kk = lane >> 4;
-    gn_v4d acc = {0, 0, 0, 0};
-    double rsq = 0;
-#pragma unroll
-    for (int step = 0; step < 2; step++) {
-        const int k = kk + 4 * step;
-        const int corner = k >> 1, comp = k & 1;
-        const double ox = (corner == 1 || corner == 2) ? cam.half : -cam.half, oy = (corner >= 2) ? cam.half : -cam.half;
-        double q[3], p[3], uv[2], Jp[6];
-#pragma unroll
-        for (int r = 0; r < 3; r++) q[r] = Gj[3 * r] * ox + Gj[3 * r + 1] * oy + Gj[9 + r];
-#pragma unroll
-        for (int r = 0; r < 3; r++) p[r] = Wf[3 * r] * q[0] + Wf[3 * r + 1] * q[1] + Wf[3 * r + 2] * q[2] + Wf[9 + r];
-        double res = 0, jp[3] = {0, 0, 0}, add = 0;
+    auto row = [&](int k, const double *p, double *jp, double &add) {
+        const int comp = k & 1;
+        double res = 0;
+        jp[0] = 0; jp[1] = 0; jp[2] = 0; add = 0;
         if (p[2] > LOC_Z_MIN) {
+            double uv[2], Jp[6];
             project_dev(cam, p, uv, Jp);
             res = uv[comp] - (double)o.corners[k];
 #pragma unroll
@@ -557,35 +547,9 @@ __global__ void __launch_bounds__(256) k_map_linearize(MapArgs a, const double *
             add = res * res;
         } else if (comp == 0)
             add = LOC_BEHIND_COST;
-        double Jrow[12];
-        Jrow[0] = p[1] * jp[2] - p[2] * jp[1];
-        Jrow[1] = p[2] * jp[0] - p[0] * jp[2];
-        Jrow[2] = p[0] * jp[1] - p[1] * jp[0];
-        Jrow[3] = jp[0]; Jrow[4] = jp[1]; Jrow[5] = jp[2];
-        double av[3];
-#pragma unroll
-        for (int c = 0; c < 3; c++) av[c] = Wf[c] * jp[0] + Wf[3 + c] * jp[1] + Wf[6 + c] * jp[2];
-        Jrow[6] = q[1] * av[2] - q[2] * av[1];
-        Jrow[7] = q[2] * av[0] - q[0] * av[2];
-        Jrow[8] = q[0] * av[1] - q[1] * av[0];
-        Jrow[9] = av[0]; Jrow[10] = av[1]; Jrow[11] = av[2];
-        double sel = 0;
-#pragma unroll
-        for (int c = 0; c < 12; c++) sel = (n == c) ? Jrow[c] : sel;
-        const double A = n < 12 ? sel : 0.0;
-        const double B = n < 12 ? sel : (n == 12 ? res : 0.0);
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A, B, acc, 0, 0, 0);
-        if (n == 0) rsq += add;
-    }
-    double *Dm = D + (size_t)m * GN_DSTRIDE;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const int row = kk + 4 * i;
-        if (row < 12 && n < 13) Dm[row * 13 + n] = acc[i];
-    }
-    double c = rsq;
-    c += __shfl_xor(c, 16);
-    c += __shfl_xor(c, 32);
+        return res;
+    };
+    const double c = gn_obs_block(W + 12 * (size_t)a.obs_cam[m], G + 12 * (size_t)a.obs_tag[m], cam.half, lane, row, D + (size_t)m * GN_DSTRIDE);
     if (lane == 0) cost_obs[m] = c;
 }
 
@@ -595,17 +559,8 @@ __global__ void k_map_decide(double *lm, int *fail)
     if (lm[MAP_LM_STOP] != 0.0) { lm[GN_LM_FLAG] = 0.0; return; }
     lm[MAP_LM_ITERS] += 1.0;
     if (*fail) { lm[GN_LM_FLAG] = 0.0; lm[MAP_LM_STOP] = 1.0; lm[MAP_LM_STATUS] = 2.0; return; }
-    if (lm[GN_LM_TRIAL] < lm[GN_LM_COST]) {
-        const bool stop = lm[GN_LM_COST] - lm[GN_LM_TRIAL] < 1e-12 * lm[GN_LM_COST];
-        lm[GN_LM_COST] = lm[GN_LM_TRIAL];
-        lm[GN_LM_LAMBDA] = fmax(lm[GN_LM_LAMBDA] * 0.1, 1e-12);
-        lm[GN_LM_ACCEPTED] += 1.0;
-        lm[GN_LM_FLAG] = 1.0;
-        if (stop) lm[MAP_LM_STOP] = 1.0;
-    } else {
-        lm[GN_LM_LAMBDA] *= 10.0;
-        lm[GN_LM_FLAG] = 0.0;
-    }
+    const double cost = lm[GN_LM_COST];
+    if (gn_accept(lm) && cost - lm[GN_LM_COST] < 1e-12 * cost) lm[MAP_LM_STOP] = 1.0;
 }
 
 // after the stop: the list offsets the LM's k_gn kernels read (a copy) become empty, so that every later trial reduces,
