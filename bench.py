@@ -2,7 +2,7 @@
 """Headline benchmark: frames/s of the AprilTag hot path at 1280x720, 20 tags/frame
 (BASELINE.json configs[1]: detection + batched PnP on one MI355X), frames resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W [--batch B] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--batch B] [--dump-outputs DIR] [--full]
 
 A step = one batch of B synthetic BGR frames through asl_detect_batch_device (threshold -> components ->
 clusters -> quads -> decode -> PnP -> de-duplication, results copied back).  With --gpus N > 1 the script starts N
@@ -11,6 +11,11 @@ scaling), and inside the timed region the ranks all-gather their observation rec
 all_gather_into_tensor), apply the gathered block to the tag graph (k_graph_frames + the last-sighting update) and
 every --gn-every steps run the pose-graph LM on a window -- the serial term the scaling curve pays for.
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the field definitions).
+
+A plain run does what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line (with the
+per-kernel times and the multi-GPU figures gathered inside the timed steps).  --full adds every leg that takes a run of
+its own: the isolated batch and the roofline / stage figures built on it, pose RMSE against ground truth, the
+both-minima, H2D-inclusive, render-inclusive and decimate-1 legs, the multi-GPU projection and the CPU baselines.
 """
 import argparse
 import json
@@ -444,6 +449,79 @@ def project_serial_term(det, d_frames, K, dev, max_tags, world=8, reps=5):
             "note": "PROJECTED on one GPU: this rank's block replicated %d x on the device, graph kernel + read-back + host apply of a %d-GPU step; the all-gather itself is not included" % (world, world)}
 
 
+def roofline_legs(det0, avg, isolated, B, workload):
+    """--full: the roofline of the threshold + segmentation stage, its isolated figure and one HBM roofline per kernel with a
+    byte model, from the per-kernel times of the timed steps (`avg`) and of the isolated batch that det0 ran last."""
+    kernels_only = {k: v for k, v in avg.items() if k.startswith("k_")}
+    # the slowest kernel of the step that has an HBM byte model (the per-cluster / per-quad kernels have none)
+    if workload != "configs1":
+        # the per-run / per-point terms of the byte models: measured points of this scene, runs in the bench scene's proportion
+        pts_frame = float(det0.debug_counters()[4]) / B
+        _ab = algorithmic_bytes
+        algorithmic_bytes_wl = lambda k_, w_, h_, c_, f_: _ab(k_, w_, h_, c_, f_, runs=int(0.39 * pts_frame), points=int(pts_frame))  # noqa: E731
+    else:
+        algorithmic_bytes_wl = algorithmic_bytes
+    modelled = {k: v for k, v in kernels_only.items() if algorithmic_bytes_wl(k, W, H, 3, 2) is not None}
+    dom = max(modelled or kernels_only, key=(modelled or kernels_only).get)
+    ab = algorithmic_bytes_wl(dom, W, H, 3, 2)
+    roof = None
+    if ab is not None:
+        achieved = ab * B / (avg[dom] * 1e-3) / 1e9
+        roof = {"kernel": dom, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": None, "avg_launch_ms": avg[dom],
+                "avg_launch_ms_isolated": isolated.get(dom), "algorithmic_bytes_per_frame": ab}
+    else:
+        # per-cluster / per-quad kernels: latency- and occupancy-bound work on L2-resident slabs; their
+        # compulsory HBM bytes are the boundary-point keys (8 B read) plus the moment slab (64 B written)
+        pts = 8.0 * int(det0.debug_counters()[4]) / B
+        achieved = (pts * 9) * B / (avg[dom] * 1e-3) / 1e9
+        roof = {"kernel": dom, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": None, "avg_launch_ms": avg[dom],
+                "avg_launch_ms_isolated": isolated.get(dom), "algorithmic_bytes_per_frame": pts * 9}
+    # HBM traffic: not measurable live; taken from the committed rocprofv3 --pmc pass of the same build
+    tr = None
+    try:
+        import glob
+        tr = json.load(open(sorted(glob.glob(os.path.join(ROOT, "profiles", "r0*_traffic.json")))[-1]))  # the latest round's counter passes
+        if tr.get("batch_frames") != B:
+            tr = None
+    except Exception:
+        tr = None
+    if tr and dom in tr["bytes_per_launch"]:
+        roof["traffic"] = tr["bytes_per_launch"][dom]
+        roof["traffic_source"] = tr["source"]
+    line_rooflines = []
+    for kname, ms_ in sorted(kernels_only.items(), key=lambda kv: -kv[1]):
+        ab_ = algorithmic_bytes_wl(kname, W, H, 3, 2)
+        if ab_ is not None:
+            gbs = ab_ * B / (ms_ * 1e-3) / 1e9
+            line_rooflines.append({"kernel": kname, "avg_launch_ms": ms_, "avg_launch_ms_isolated": isolated.get(kname),
+                                   "algorithmic_bytes_per_frame": ab_, "achieved_GBs": gbs, "frac": gbs / HBM_PEAK_GBS})
+    seg_names = ("k_hash_clear", "k_decimate_minmax", "k_tile_cut", "k_seg_tile", "k_seg_border", "k_seg_roots", "k_seg_points", "k_cluster_filter",
+                 "k_point_place")
+    seg = sum(isolated.get(k, 0.0) for k in seg_names)
+    seg_bytes = stage_algorithmic_read_bytes(W, H, 3, 2)
+    seg_gbs = seg_bytes * B / (seg * 1e-3) / 1e9 if seg > 0 else 0.0
+    # The headline roofline is the stage SURVEY 8(d) defines the algorithmic bytes for: threshold + segmentation is a
+    # chain of launches (K1-K9), each of them processes the same B frames, so "the kernel" is the chain and its launch
+    # duration the sum of its members' HIP-event durations inside the timed region (where the two pipeline parts share
+    # the GPU, so each member runs longer than alone; the isolated sum is given beside it).  The slowest single kernel
+    # with a byte model of its own is kept as `dominant_kernel`.
+    seg_live = sum(avg.get(k, 0.0) for k in seg_names)
+    live_gbs = seg_bytes * B / (seg_live * 1e-3) / 1e9 if seg_live > 0 else 0.0
+    stage_roof = {"kernel": "threshold + segmentation stage (k_hash_clear, k_decimate_minmax, k_tile_cut, k_seg_tile, k_seg_border, "
+                            "k_seg_roots, k_seg_points, k_cluster_filter, k_point_place)",
+                  "bound": "hbm", "achieved": live_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": live_gbs / HBM_PEAK_GBS,
+                  "traffic": (sum(tr["bytes_per_launch"].get(k, 0.0) for k in seg_names) if tr else None),
+                  "traffic_source": tr["source"] if tr else None,
+                  "avg_launch_ms": seg_live, "avg_launch_ms_isolated": seg, "achieved_isolated": seg_gbs, "frac_isolated": seg_gbs / HBM_PEAK_GBS,
+                  "algorithmic_bytes_per_frame": seg_bytes, "units_per_launch": B,
+                  "members_ms": {k: avg.get(k, 0.0) for k in seg_names}, "dominant_kernel": roof}
+    stage = {"ms_per_batch_isolated": seg, "algorithmic_read_bytes_per_frame": seg_bytes, "achieved_GBs": seg_gbs,
+             "frac_of_hbm_peak": seg_gbs / HBM_PEAK_GBS}
+    return stage_roof, stage, line_rooflines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -453,8 +531,9 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="frames per step per GPU (0 = the workload's default)")
     ap.add_argument("--distinct", type=int, default=0, help="distinct rendered frames (tiled to --batch); 0 = every frame of the batch is distinct")
     ap.add_argument("--pipeline", type=int, default=3, help="detector workspaces/streams per GPU; the batch is split among them so one part's host post-processing and latency-bound tail kernels overlap the other part's bulk kernels")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--timed-only", action="store_true", help="only the warm-up, the timed steps and the one isolated batch: no h2d / render / both-minima / projection / CPU legs (for rocprofv3 passes: every detector launch then has the full batch size)")
+    ap.add_argument("--full", action="store_true", help="also run every leg beyond the headline (see the module docstring); a plain run only sets up, warms up, times the steps, dumps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
+    ap.add_argument("--timed-only", action="store_true", help="with --full: only the warm-up, the timed steps and the one isolated batch: no h2d / render / both-minima / projection / CPU legs (for rocprofv3 passes: every detector launch then has the full batch size)")
     ap.add_argument("--rehearse", action="store_true", help="multi-rank rehearsal on a one-GPU box: gloo backend, every rank on cuda:0")
     ap.add_argument("--max-tags", type=int, default=0, help="tag slots per frame in the exchanged observation records (0 = tags per frame + 4)")
     ap.add_argument("--gn-every", type=int, default=-1, help="pose-graph LM on a window every this many steps of the exchange (0 = never, -1 = the workload's default)")
@@ -517,8 +596,8 @@ def main():
         d_distinct, distinct_gt, rerender = render_stream_device(render_det, ndist, dev, phase=np.pi * rank / max(world, 1) / max(ndist, 1))
     render_det.close()
     d_frames = d_distinct if ndist == B else d_distinct.repeat((B + ndist - 1) // ndist, 1, 1, 1)[:B].contiguous()
-    NCHK = min(32, ndist)  # frames checked against ground truth / handed to the CPU baseline
-    distinct = d_distinct[:NCHK].cpu().numpy()
+    NCHK = min(32, ndist)  # frames checked against ground truth / handed to the CPU baseline (--full)
+    distinct = d_distinct[:NCHK].cpu().numpy() if args.full else None
     # P detector workspaces used round-robin: batch i is submitted before batch i-1 is collected, so the host
     # post-processing (dedup/sort/copy-out) and the latency-bound tail kernels of one batch overlap the bulk
     # kernels of the next.  P = 1 is the plain synchronous call.
@@ -697,79 +776,15 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, *last_step, cam_poses=state.get("camera_poses") if xchg else None)
 
-    # one extra synchronous batch (nothing else on the GPU) for un-overlapped kernel durations
-    detectors[0].submit_device(d_frames.data_ptr(), B, 3, W, H, stream=streams[0].cuda_stream, K=K, dist=zeros4, tag_size=TAG_INNER)
-    last = detectors[0].collect(max_per_frame=MAXDET)
-    last = (last[0].copy(), last[1].copy(), last[2].copy())
-    isolated = detectors[0].stage_times()
+    if args.full:
+        # one extra synchronous batch (nothing else on the GPU) for un-overlapped kernel durations
+        detectors[0].submit_device(d_frames.data_ptr(), B, 3, W, H, stream=streams[0].cuda_stream, K=K, dist=zeros4, tag_size=TAG_INNER)
+        last = detectors[0].collect(max_per_frame=MAXDET)
+        last = (last[0].copy(), last[1].copy(), last[2].copy())
+        isolated = detectors[0].stage_times()
 
     if rank == 0:
         avg = {k: float(np.mean(v)) for k, v in kernel_ms.items()}
-        kernels_only = {k: v for k, v in avg.items() if k.startswith("k_")}
-        # the slowest kernel of the step that has an HBM byte model (the per-cluster / per-quad kernels have none)
-        if args.workload != "configs1":
-            # the per-run / per-point terms of the byte models: measured points of this scene, runs in the bench scene's proportion
-            pts_frame = float(detectors[0].debug_counters()[4]) / B
-            _ab = algorithmic_bytes
-            algorithmic_bytes_wl = lambda k_, w_, h_, c_, f_: _ab(k_, w_, h_, c_, f_, runs=int(0.39 * pts_frame), points=int(pts_frame))  # noqa: E731
-        else:
-            algorithmic_bytes_wl = algorithmic_bytes
-        modelled = {k: v for k, v in kernels_only.items() if algorithmic_bytes_wl(k, W, H, 3, 2) is not None}
-        dom = max(modelled or kernels_only, key=(modelled or kernels_only).get)
-        ab = algorithmic_bytes_wl(dom, W, H, 3, 2)
-        roof = None
-        if ab is not None:
-            achieved = ab * B / (avg[dom] * 1e-3) / 1e9
-            roof = {"kernel": dom, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": achieved / HBM_PEAK_GBS, "traffic": None, "avg_launch_ms": avg[dom],
-                    "avg_launch_ms_isolated": isolated.get(dom), "algorithmic_bytes_per_frame": ab}
-        else:
-            # per-cluster / per-quad kernels: latency- and occupancy-bound work on L2-resident slabs; their
-            # compulsory HBM bytes are the boundary-point keys (8 B read) plus the moment slab (64 B written)
-            pts = 8.0 * int(detectors[0].debug_counters()[4]) / B
-            achieved = (pts * 9) * B / (avg[dom] * 1e-3) / 1e9
-            roof = {"kernel": dom, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": achieved / HBM_PEAK_GBS, "traffic": None, "avg_launch_ms": avg[dom],
-                    "avg_launch_ms_isolated": isolated.get(dom), "algorithmic_bytes_per_frame": pts * 9}
-        # HBM traffic: not measurable live; taken from the committed rocprofv3 --pmc pass of the same build
-        tr = None
-        try:
-            import glob
-            tr = json.load(open(sorted(glob.glob(os.path.join(ROOT, "profiles", "r0*_traffic.json")))[-1]))  # the latest round's counter passes
-            if tr.get("batch_frames") != B:
-                tr = None
-        except Exception:
-            tr = None
-        if tr and dom in tr["bytes_per_launch"]:
-            roof["traffic"] = tr["bytes_per_launch"][dom]
-            roof["traffic_source"] = tr["source"]
-        line_rooflines = []
-        for kname, ms_ in sorted(kernels_only.items(), key=lambda kv: -kv[1]):
-            ab_ = algorithmic_bytes_wl(kname, W, H, 3, 2)
-            if ab_ is not None:
-                gbs = ab_ * B / (ms_ * 1e-3) / 1e9
-                line_rooflines.append({"kernel": kname, "avg_launch_ms": ms_, "avg_launch_ms_isolated": isolated.get(kname),
-                                       "algorithmic_bytes_per_frame": ab_, "achieved_GBs": gbs, "frac": gbs / HBM_PEAK_GBS})
-        seg_names = ("k_hash_clear", "k_decimate_minmax", "k_tile_cut", "k_seg_tile", "k_seg_border", "k_seg_roots", "k_seg_points", "k_cluster_filter",
-                     "k_point_place")
-        seg = sum(isolated.get(k, 0.0) for k in seg_names)
-        seg_bytes = stage_algorithmic_read_bytes(W, H, 3, 2)
-        seg_gbs = seg_bytes * B / (seg * 1e-3) / 1e9 if seg > 0 else 0.0
-        # The headline roofline is the stage SURVEY 8(d) defines the algorithmic bytes for: threshold + segmentation is a
-        # chain of launches (K1-K9), each of them processes the same B frames, so "the kernel" is the chain and its launch
-        # duration the sum of its members' HIP-event durations inside the timed region (where the two pipeline parts share
-        # the GPU, so each member runs longer than alone; the isolated sum is given beside it).  The slowest single kernel
-        # with a byte model of its own is kept as `dominant_kernel`.
-        seg_live = sum(avg.get(k, 0.0) for k in seg_names)
-        live_gbs = seg_bytes * B / (seg_live * 1e-3) / 1e9 if seg_live > 0 else 0.0
-        stage_roof = {"kernel": "threshold + segmentation stage (k_hash_clear, k_decimate_minmax, k_tile_cut, k_seg_tile, k_seg_border, "
-                                "k_seg_roots, k_seg_points, k_cluster_filter, k_point_place)",
-                      "bound": "hbm", "achieved": live_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": live_gbs / HBM_PEAK_GBS,
-                      "traffic": (sum(tr["bytes_per_launch"].get(k, 0.0) for k in seg_names) if tr else None),
-                      "traffic_source": tr["source"] if tr else None,
-                      "avg_launch_ms": seg_live, "avg_launch_ms_isolated": seg, "achieved_isolated": seg_gbs, "frac_isolated": seg_gbs / HBM_PEAK_GBS,
-                      "algorithmic_bytes_per_frame": seg_bytes, "units_per_launch": B,
-                      "members_ms": {k: avg.get(k, 0.0) for k in seg_names}, "dominant_kernel": roof}
         line = {
             "metric": "frames/sec at %dx%d, %d tags/frame (detection + batched PnP%s)" % (W, H, NTAGS, ", graph update + pose-graph LM" if xchg else ""),
             "value": world * B * args.steps / elapsed, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
@@ -787,16 +802,15 @@ def main():
                 "frames_through_sequential_update": serial["seq_frames"], "lm_runs": serial["gn_runs"],
                 "lm_last": {k_: v_ for k_, v_ in (state.get("gn_last") or {}).items() if k_ != "camera_poses"} or None,
                 "graph_nodes": len(slam.graph.get_nodes()), "world_tag": slam.coordinate_id},
-            "roofline": stage_roof,
-            "stage_threshold_segmentation": {"ms_per_batch_isolated": seg, "algorithmic_read_bytes_per_frame": seg_bytes,
-                                             "achieved_GBs": seg_gbs, "frac_of_hbm_peak": seg_gbs / HBM_PEAK_GBS},
-            "kernel_rooflines_hbm": line_rooflines,
             "kernel_ms_per_batch": avg,
-            "kernel_ms_per_batch_isolated": isolated,
         }
         nchk = NCHK
-        line["pose_rmse"] = pose_rmse_vs_ground_truth(last[0], last[1], last[2], distinct_gt[:nchk])
-        if world == 1 and not args.timed_only:
+        if args.full:
+            stage_roof, stage_seg, line_rooflines = roofline_legs(detectors[0], avg, isolated, B, args.workload)
+            line.update({"roofline": stage_roof, "stage_threshold_segmentation": stage_seg, "kernel_rooflines_hbm": line_rooflines,
+                         "kernel_ms_per_batch_isolated": isolated})
+            line["pose_rmse"] = pose_rmse_vs_ground_truth(last[0], last[1], last[2], distinct_gt[:nchk])
+        if args.full and world == 1 and not args.timed_only:
             # the same frames with the better of the two planar poses per tag (not what the reference computes: reported apart)
             detectors[0].set_pnp_both_minima(True)
             detectors[0].submit_device(d_frames.data_ptr(), B, 3, W, H, stream=streams[0].cuda_stream, K=K, dist=zeros4, tag_size=TAG_INNER)
@@ -823,7 +837,7 @@ def main():
                 tr = time.perf_counter() - tr0
                 line["render_included"] = {"value": B * nrs / tr, "unit": "frames/s", "steps": nrs, "ms_per_step": 1e3 * tr / nrs,
                                            "note": "asl_render_frames_device (k_render) of the step's 1024 frames + the same batch, one workspace, synchronous; not the headline value"}
-        if not args.no_cpu_baseline and not args.timed_only and world == 1:  # reported at N = 1 only
+        if args.full and not args.no_cpu_baseline and not args.timed_only and world == 1:  # reported at N = 1 only
             line["cpu_baseline"] = cpu_baseline(distinct[:nchk], K, gpu=last)
             line["cpu_baseline_all_cores"] = cpu_baseline_all_cores(distinct[:nchk], K)
         print(json.dumps(line))

@@ -3,8 +3,8 @@
 committed summaries under profiles/.
 
 Inputs:
-  gpurun_out/<tag>_bench_final.log        python bench.py                               (last line = the JSON)
-  gpurun_out/<tag>_f_kernel_stats.csv     rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline
+  <tag>_bench_final.log                   python bench.py --full                        (last line = the JSON)
+  <tag>_f_kernel_stats.csv                rocprofv3 --kernel-trace --stats -- python3 bench.py --full --timed-only
   gpurun_out/pmc_<tag>_{fetch,write,sq1,sq2}.csv   tools/pmc_summary.py over rocprofv3 --pmc passes of
                                           python3 bench.py --steps 2 --warmup 1 --pipeline 1 --no-cpu-baseline
   gpurun_out/<tag>_config3.json, _config5.json, _gn_kernel_stats.csv, _pmc_gn.csv   tools/run_config3.py (plain, traced, counted)

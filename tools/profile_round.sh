@@ -10,11 +10,11 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 cd $R
 if [[ $part == *a* ]]; then
-python bench.py > $O/${tag}_bench_final.log 2> $O/${tag}_bench_final.err
+python bench.py --full > $O/${tag}_bench_final.log 2> $O/${tag}_bench_final.err
 echo "bench done: $(tail -c 300 $O/${tag}_bench_final.log | head -c 120)"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_f
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_f -- python3 $R/bench.py --timed-only > $O/${tag}_prof_f.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_f -- python3 $R/bench.py --full --timed-only > $O/${tag}_prof_f.log 2>&1
 cp $(ls /tmp/prof_f/*/*kernel_stats.csv | head -1) $O/${tag}_f_kernel_stats.csv
 echo "kernel trace done"
 bash $R/tools/pmc_run.sh $tag
@@ -33,12 +33,12 @@ python3 $R/tools/pmc_summary.py /tmp/pmc_gn $O/${tag}_pmc_gn.csv
 echo "gn done"
 # the multi-GPU step: the exchange at N = 1 (RCCL, the collective degenerates to a copy) and a 2-rank gloo rehearsal on this one GPU
 cd $R
-python bench.py --exchange --timed-only > $O/${tag}_exchange_n1.json 2> /dev/null
-python bench.py --gpus 2 --rehearse --steps 8 --warmup 3 --gn-every 4 --no-cpu-baseline > $O/${tag}_rehearse_gpus2.json 2> /dev/null
+python bench.py --full --exchange --timed-only > $O/${tag}_exchange_n1.json 2> /dev/null
+python bench.py --full --gpus 2 --rehearse --steps 8 --warmup 3 --gn-every 4 --no-cpu-baseline > $O/${tag}_rehearse_gpus2.json 2> /dev/null
 # the other BASELINE.json configs through the same harness (graph update and pose-graph LM inside the timed region)
-python bench.py --workload configs2 --timed-only > $O/${tag}_bench_configs2.json 2> /dev/null
-python bench.py --workload configs4 --timed-only > $O/${tag}_bench_configs4_n1.json 2> /dev/null
-python bench.py --workload configs4 --gpus 2 --rehearse --steps 6 --warmup 2 --batch 64 --no-cpu-baseline > $O/${tag}_bench_configs4_rehearse_gpus2.json 2> /dev/null
+python bench.py --full --workload configs2 --timed-only > $O/${tag}_bench_configs2.json 2> /dev/null
+python bench.py --full --workload configs4 --timed-only > $O/${tag}_bench_configs4_n1.json 2> /dev/null
+python bench.py --full --workload configs4 --gpus 2 --rehearse --steps 6 --warmup 2 --batch 64 --no-cpu-baseline > $O/${tag}_bench_configs4_rehearse_gpus2.json 2> /dev/null
 echo "multi-gpu legs done"
 # ROCTX ranges of the stage groups (host-side enqueue spans) next to the kernel trace, one short run
 cd /tmp
