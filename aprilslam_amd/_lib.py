@@ -13,41 +13,6 @@ class AslError(RuntimeError):
     pass
 
 
-class AslDetection(C.Structure):
-    _fields_ = [("id", C.c_int32), ("hamming", C.c_int32), ("margin", C.c_float), ("frame", C.c_int32),
-                ("center", C.c_double * 2), ("corners", (C.c_double * 2) * 4)]
-
-
-class AslPose(C.Structure):
-    _fields_ = [("rvec", C.c_double * 3), ("tvec", C.c_double * 3), ("T", C.c_double * 16), ("ok", C.c_int32),
-                ("reserved", C.c_int32)]
-
-
-class AslMapTag(C.Structure):
-    _fields_ = [("T", C.c_double * 12), ("valid", C.c_int32), ("reserved", C.c_int32)]
-
-
-class AslCamPose(C.Structure):
-    _fields_ = [("T", C.c_double * 16), ("rms_px", C.c_double), ("rms_seed_px", C.c_double), ("n_tags", C.c_int32),
-                ("n_rejected", C.c_int32), ("status", C.c_int32), ("seed_slot", C.c_int32)]
-
-
-class AslCalibResult(C.Structure):
-    _fields_ = [("K", C.c_double * 9), ("dist", C.c_double * 5), ("std", C.c_double * 9), ("rms_px", C.c_double),
-                ("rms_init_px", C.c_double), ("n_frames_used", C.c_int32), ("n_corners", C.c_int32), ("iterations", C.c_int32),
-                ("status", C.c_int32)]
-
-
-class AslMapResult(C.Structure):
-    _fields_ = [("cost_seed", C.c_double), ("cost", C.c_double), ("rms_px", C.c_double), ("rms_seed_px", C.c_double),
-                ("n_frames_used", C.c_int32), ("n_tags", C.c_int32), ("n_obs", C.c_int32), ("n_obs_dropped", C.c_int32),
-                ("iterations", C.c_int32), ("world_id", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
-
-
-class AslDebugQuad(C.Structure):
-    _fields_ = [("p", (C.c_double * 2) * 4), ("cluster", C.c_uint64), ("frame", C.c_int32), ("reversed_border", C.c_int32)]
-
-
 PLANE_DTYPE = np.dtype([("Hi", "<f8", (9,)), ("bbox", "<i4", (4,)), ("tex", "<i4"), ("pad", "<i4")])  # asl_render_plane
 assert PLANE_DTYPE.itemsize == 96
 OBS_DTYPE = np.dtype([("id", "<i4"), ("flags", "<i4"), ("corners", "<f4", (8,)), ("T", "<f8", (12,))])  # asl_obs
@@ -64,14 +29,12 @@ CALIB_RESULT_DTYPE = np.dtype([("K", "<f8", (3, 3)), ("dist", "<f8", (5,)), ("st
 MAP_RESULT_DTYPE = np.dtype([("cost_seed", "<f8"), ("cost", "<f8"), ("rms_px", "<f8"), ("rms_seed_px", "<f8"),
                              ("n_frames_used", "<i4"), ("n_tags", "<i4"), ("n_obs", "<i4"), ("n_obs_dropped", "<i4"),
                              ("iterations", "<i4"), ("world_id", "<i4"), ("status", "<i4"), ("reserved", "<i4")])  # asl_map_result
-QUAD_DTYPE = np.dtype([("p", "<f8", (4, 2)), ("cluster", "<u8"), ("frame", "<i4"), ("reversed_border", "<i4")])
-assert DET_DTYPE.itemsize == C.sizeof(AslDetection)
-assert POSE_DTYPE.itemsize == C.sizeof(AslPose)
-assert QUAD_DTYPE.itemsize == C.sizeof(AslDebugQuad)
-assert MAP_TAG_DTYPE.itemsize == C.sizeof(AslMapTag) == 104
-assert CAM_POSE_DTYPE.itemsize == C.sizeof(AslCamPose) == 160
-assert CALIB_RESULT_DTYPE.itemsize == C.sizeof(AslCalibResult) == 216
-assert MAP_RESULT_DTYPE.itemsize == C.sizeof(AslMapResult) == 64
+QUAD_DTYPE = np.dtype([("p", "<f8", (4, 2)), ("cluster", "<u8"), ("frame", "<i4"), ("reversed_border", "<i4")])  # asl_debug_quad
+assert DET_DTYPE.itemsize == 96 and POSE_DTYPE.itemsize == 184 and QUAD_DTYPE.itemsize == 80  # asl_detection, asl_pose, asl_debug_quad
+assert MAP_TAG_DTYPE.itemsize == 104
+assert CAM_POSE_DTYPE.itemsize == 160
+assert CALIB_RESULT_DTYPE.itemsize == 216
+assert MAP_RESULT_DTYPE.itemsize == 64
 
 EXPORTS = [
     "asl_detector_create", "asl_detector_destroy", "asl_detector_set_id_limit", "asl_detector_set_pnp_both_minima", "asl_last_error", "asl_version", "asl_detect_gray_u8",
@@ -144,6 +107,48 @@ def check(rc):
         raise AslError("libaprilslam error %d: %s" % (rc, load().asl_last_error().decode("utf-8", "replace")))
 
 
+_DP = C.POINTER(C.c_double)
+
+
+def _ptr(addr):
+    """a device address"""
+    return C.c_void_p(int(addr))
+
+
+def _opt_ptr(addr):
+    """a device address, or NULL for 0 / None"""
+    return C.c_void_p(int(addr)) if addr else None
+
+
+def _camera(K, dist, square=False):
+    """K and dist as the C ABI takes them: (arrays to keep alive, K pointer, dist pointer or None, n_dist).  dist: None or
+    0, 4 or 5 coefficients; square: K must be 3x3."""
+    Kc = np.ascontiguousarray(K, dtype=np.float64)
+    if square and Kc.shape != (3, 3):
+        raise ValueError("K must be 3x3")
+    dc = np.ascontiguousarray(np.zeros(0) if dist is None else dist, dtype=np.float64).ravel()
+    if len(dc) not in (0, 4, 5):
+        raise ValueError("dist must have 0, 4 or 5 coefficients")
+    return (Kc, dc), Kc.ctypes.data_as(_DP), (dc.ctypes.data_as(_DP) if len(dc) else None), len(dc)
+
+
+def _obs_records(obs):
+    """host asl_obs records as one contiguous (n_frames, max_tags) block; one frame's row may be 1-D"""
+    o = np.ascontiguousarray(obs, dtype=OBS_DTYPE)
+    if o.ndim == 1:
+        o = o[None]
+    if o.ndim != 2:
+        raise ValueError("obs must be (n_frames, max_tags) asl_obs records")
+    return o
+
+
+def _map_records(tag_map):
+    """(n_ids,) MAP_TAG_DTYPE records of a record array or a localize.TagMap"""
+    if hasattr(tag_map, "as_records"):
+        tag_map = tag_map.as_records()
+    return np.ascontiguousarray(tag_map, dtype=MAP_TAG_DTYPE).ravel()
+
+
 class Detector:
     """Owns one asl_detector (one GPU workspace).  Not re-entrant."""
 
@@ -153,6 +158,7 @@ class Detector:
         L = load()
         self._L = L
         self._h = C.c_void_p()
+        self._outbuf = self._posebuf = None  # detection / pose results kept across calls (_result_buffers)
         check(L.asl_detector_create(family.encode(), int(threads), int(maxhamming), float(decimate), float(blur),
                                     1 if refine_edges else 0, int(device), C.byref(self._h)))
         self.device = int(device)
@@ -199,14 +205,9 @@ class Detector:
         npf = (C.c_int * B)()
         n = C.c_int()
         if K is not None:
-            dp = C.POINTER(C.c_double)
-            Kc = np.ascontiguousarray(K, dtype=np.float64)
-            dc = np.ascontiguousarray(np.zeros(0) if dist is None else dist, dtype=np.float64).ravel()
-            if len(dc) not in (0, 4, 5):
-                raise ValueError("dist must have 0, 4 or 5 coefficients")
+            keep, Kp, dpp, nd = _camera(K, dist)
             poses = np.empty(cap, dtype=POSE_DTYPE)
-            check(self._L.asl_detect_batch_pose_u8(self._h, ptrs, B, ch, W, H, stride, Kc.ctypes.data_as(dp),
-                                                   dc.ctypes.data_as(dp) if len(dc) else None, len(dc), float(tag_size),
+            check(self._L.asl_detect_batch_pose_u8(self._h, ptrs, B, ch, W, H, stride, Kp, dpp, nd, float(tag_size),
                                                    out.ctypes.data, poses.ctypes.data, cap, npf, C.byref(n)))
             if n.value > cap:
                 return self.detect_host(images, (n.value + B - 1) // B + 1, channels, K, dist, tag_size)
@@ -223,37 +224,16 @@ class Detector:
         frame_pitch = frame_pitch or stride * height
         cap = n_frames * max_per_frame
         want_poses = (K is not None) if want_poses is None else want_poses
-        # result buffers are kept and reused (fresh multi-MB arrays cost ~1 ms of page faults per call);
-        # the returned arrays are views into them, valid until the next call on this detector
-        if reuse_buffers and getattr(self, "_outbuf", None) is not None and len(self._outbuf) >= cap:
-            out = self._outbuf
+        if reuse_buffers:  # the returned arrays are views into the kept buffers, valid until the next call on this detector
+            out, poses = self._result_buffers(cap, want_poses)
         else:
-            out = np.empty(cap, dtype=DET_DTYPE)
-            self._outbuf = out if reuse_buffers else None
-        if not want_poses:
-            poses = np.empty(0, dtype=POSE_DTYPE)
-        elif reuse_buffers and getattr(self, "_posebuf", None) is not None and len(self._posebuf) >= cap:
-            poses = self._posebuf
-        else:
-            poses = np.empty(cap, dtype=POSE_DTYPE)
-            self._posebuf = poses if reuse_buffers else None
+            out, poses = np.empty(cap, dtype=DET_DTYPE), (np.empty(cap, dtype=POSE_DTYPE) if want_poses else None)
         npf = (C.c_int * n_frames)()
         n = C.c_int()
-        dp = C.POINTER(C.c_double)
-        if K is not None:
-            Kc = np.ascontiguousarray(K, dtype=np.float64)
-            dc = np.ascontiguousarray(np.zeros(0) if dist is None else dist, dtype=np.float64).ravel()
-            nd = len(dc)
-            if nd not in (0, 4, 5):
-                raise ValueError("dist must have 0, 4 or 5 coefficients")
-            Kp = Kc.ctypes.data_as(dp)
-            dpp = dc.ctypes.data_as(dp) if nd else None
-        else:
-            Kp, dpp, nd = None, None, 0
-        check(self._L.asl_detect_batch_device(self._h, C.c_void_p(int(data_ptr)), n_frames, channels, width, height, stride,
-                                              frame_pitch, C.c_void_p(int(stream)), Kp, dpp, nd, float(tag_size),
-                                              out.ctypes.data, poses.ctypes.data if want_poses else None, cap, npf,
-                                              C.byref(n)))
+        keep, Kp, dpp, nd = _camera(K, dist) if K is not None else (None, None, None, 0)
+        check(self._L.asl_detect_batch_device(self._h, _ptr(data_ptr), n_frames, channels, width, height, stride, frame_pitch,
+                                              _ptr(stream), Kp, dpp, nd, float(tag_size), out.ctypes.data,
+                                              poses.ctypes.data if want_poses else None, cap, npf, C.byref(n)))
         if n.value > cap:
             return self.detect_device(data_ptr, n_frames, channels, width, height, stride, frame_pitch, stream, K, dist,
                                       tag_size, max_per_frame=(n.value + n_frames - 1) // n_frames + 1, want_poses=want_poses,
@@ -265,17 +245,9 @@ class Detector:
         """Enqueue a batch resident in HBM and return immediately (asl_submit_batch_device); pair with collect()."""
         stride = stride or width * channels
         frame_pitch = frame_pitch or stride * height
-        dp = C.POINTER(C.c_double)
-        if K is not None:
-            Kc = np.ascontiguousarray(K, dtype=np.float64)
-            dc = np.ascontiguousarray(np.zeros(0) if dist is None else dist, dtype=np.float64).ravel()
-            if len(dc) not in (0, 4, 5):
-                raise ValueError("dist must have 0, 4 or 5 coefficients")
-            Kp, dpp, nd = Kc.ctypes.data_as(dp), (dc.ctypes.data_as(dp) if len(dc) else None), len(dc)
-        else:
-            Kp, dpp, nd = None, None, 0
-        check(self._L.asl_submit_batch_device(self._h, C.c_void_p(int(data_ptr)), n_frames, channels, width, height, stride,
-                                              frame_pitch, C.c_void_p(int(stream)), Kp, dpp, nd, float(tag_size)))
+        keep, Kp, dpp, nd = _camera(K, dist) if K is not None else (None, None, None, 0)
+        check(self._L.asl_submit_batch_device(self._h, _ptr(data_ptr), n_frames, channels, width, height, stride, frame_pitch,
+                                              _ptr(stream), Kp, dpp, nd, float(tag_size)))
         self._inflight = (n_frames, K is not None)
 
     def render_frames_device(self, frames_ptr, n_frames, width, height, planes_ptr, max_planes, textures_ptr, tw, th, half, K=None, dist=None,
@@ -284,59 +256,39 @@ class Detector:
         addresses; K / dist are host arrays, only for a camera with lens distortion)."""
         stride = stride or 3 * width
         frame_pitch = frame_pitch or stride * height
-        dp = C.POINTER(C.c_double)
         Kp = dpp = None
         nd = 0
         if dist is not None:
             Kc = np.ascontiguousarray(K, dtype=np.float64)
             dc = np.ascontiguousarray(dist, dtype=np.float64).ravel()
-            Kp, dpp, nd = Kc.ctypes.data_as(dp), dc.ctypes.data_as(dp), len(dc)
-        check(self._L.asl_render_frames_device(self._h, C.c_void_p(int(frames_ptr)), int(n_frames), int(width), int(height), int(stride),
-                                               int(frame_pitch), C.c_void_p(int(planes_ptr)), int(max_planes), C.c_void_p(int(textures_ptr)),
-                                               int(tw), int(th), float(half), Kp, dpp, nd, C.c_void_p(int(stream))))
+            Kp, dpp, nd = Kc.ctypes.data_as(_DP), dc.ctypes.data_as(_DP), len(dc)
+        check(self._L.asl_render_frames_device(self._h, _ptr(frames_ptr), int(n_frames), int(width), int(height), int(stride),
+                                               int(frame_pitch), _ptr(planes_ptr), int(max_planes), _ptr(textures_ptr),
+                                               int(tw), int(th), float(half), Kp, dpp, nd, _ptr(stream)))
 
     def pack_observations_device(self, out_ptr, max_tags, stream=0):
         """asl_pack_observations_device: the submitted batch's results as n_frames x max_tags asl_obs records at the
         device address `out_ptr`, enqueued on `stream` (use the stream the batch was submitted on)."""
-        check(self._L.asl_pack_observations_device(self._h, C.c_void_p(int(out_ptr)), int(max_tags), C.c_void_p(int(stream))))
+        check(self._L.asl_pack_observations_device(self._h, _ptr(out_ptr), int(max_tags), _ptr(stream)))
 
     def graph_frames_device(self, obs_ptr, world, n_frames, max_tags, coordinate_id, pose_ptr, status_ptr, last_ptr, n_ids, picks_ptr=0,
                             stream=0):
         """asl_graph_frames_device (all pointers are device addresses; picks_ptr = 0 skips the picks)."""
-        check(self._L.asl_graph_frames_device(self._h, C.c_void_p(int(obs_ptr)), int(world), int(n_frames), int(max_tags),
-                                              int(coordinate_id), C.c_void_p(int(pose_ptr)), C.c_void_p(int(status_ptr)),
-                                              C.c_void_p(int(last_ptr)), int(n_ids), C.c_void_p(int(picks_ptr)) if picks_ptr else None,
-                                              C.c_void_p(int(stream))))
+        check(self._L.asl_graph_frames_device(self._h, _ptr(obs_ptr), int(world), int(n_frames), int(max_tags), int(coordinate_id),
+                                              _ptr(pose_ptr), _ptr(status_ptr), _ptr(last_ptr), int(n_ids), _opt_ptr(picks_ptr),
+                                              _ptr(stream)))
 
     def graph_picks_device(self, obs_ptr, world, n_frames, max_tags, status_ptr, order_lo, order_hi, last_ptr, n_ids, picks_ptr, stream=0):
         """asl_graph_picks_device: last sightings + picks of the status-0 frames at positions [order_lo, order_hi)."""
-        check(self._L.asl_graph_picks_device(self._h, C.c_void_p(int(obs_ptr)), int(world), int(n_frames), int(max_tags), C.c_void_p(int(status_ptr)),
-                                             int(order_lo), int(order_hi), C.c_void_p(int(last_ptr)), int(n_ids), C.c_void_p(int(picks_ptr)),
-                                             C.c_void_p(int(stream))))
-
-    @staticmethod
-    def _camera_args(K, dist):
-        dp = C.POINTER(C.c_double)
-        Kc = np.ascontiguousarray(K, dtype=np.float64)
-        if Kc.shape != (3, 3):
-            raise ValueError("K must be 3x3")
-        dc = np.ascontiguousarray(np.zeros(0) if dist is None else dist, dtype=np.float64).ravel()
-        if len(dc) not in (0, 4, 5):
-            raise ValueError("dist must have 0, 4 or 5 coefficients")
-        return (Kc, dc), Kc.ctypes.data_as(dp), (dc.ctypes.data_as(dp) if len(dc) else None), len(dc)
+        check(self._L.asl_graph_picks_device(self._h, _ptr(obs_ptr), int(world), int(n_frames), int(max_tags), _ptr(status_ptr),
+                                             int(order_lo), int(order_hi), _ptr(last_ptr), int(n_ids), _ptr(picks_ptr), _ptr(stream)))
 
     def localize(self, obs, tag_map, K, dist, tag_size, max_tag_rms_px=0.0):
         """asl_localize_batch: host records obs (n_frames, max_tags) OBS_DTYPE (e.g. dist.pack_observations) against
         tag_map (n_ids,) MAP_TAG_DTYPE (or a localize.TagMap) -> (n_frames,) CAM_POSE_DTYPE, world<-camera per frame."""
-        if hasattr(tag_map, "as_records"):
-            tag_map = tag_map.as_records()
-        o = np.ascontiguousarray(obs, dtype=OBS_DTYPE)
-        if o.ndim == 1:
-            o = o[None]
-        if o.ndim != 2:
-            raise ValueError("obs must be (n_frames, max_tags) asl_obs records")
-        m = np.ascontiguousarray(tag_map, dtype=MAP_TAG_DTYPE).ravel()
-        keep, Kp, dpp, nd = self._camera_args(K, dist)
+        o = _obs_records(obs)
+        m = _map_records(tag_map)
+        keep, Kp, dpp, nd = _camera(K, dist, square=True)
         out = np.zeros(o.shape[0], dtype=CAM_POSE_DTYPE)
         check(self._L.asl_localize_batch(self._h, o.ctypes.data if o.size else None, o.shape[0], o.shape[1],
                                          m.ctypes.data if m.size else None, len(m), Kp, dpp, nd, float(tag_size),
@@ -347,10 +299,9 @@ class Detector:
                         stream=0):
         """asl_localize_frames_device: obs_ptr (n_frames x max_tags asl_obs, e.g. from pack_observations_device), map_ptr
         (n_ids asl_map_tag) and out_ptr (n_frames asl_cam_pose) are device addresses; enqueued on `stream`, no wait."""
-        keep, Kp, dpp, nd = self._camera_args(K, dist)
-        check(self._L.asl_localize_frames_device(self._h, C.c_void_p(int(obs_ptr)), int(n_frames), int(max_tags), C.c_void_p(int(map_ptr)),
-                                                 int(n_ids), Kp, dpp, nd, float(tag_size), float(max_tag_rms_px),
-                                                 C.c_void_p(int(out_ptr)), C.c_void_p(int(stream))))
+        keep, Kp, dpp, nd = _camera(K, dist, square=True)
+        check(self._L.asl_localize_frames_device(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids), Kp, dpp,
+                                                 nd, float(tag_size), float(max_tag_rms_px), _ptr(out_ptr), _ptr(stream)))
 
     @staticmethod
     def _calib_args(K_init, n_dist):
@@ -361,19 +312,13 @@ class Detector:
         Kc = np.ascontiguousarray(K_init, dtype=np.float64)
         if Kc.shape != (3, 3):
             raise ValueError("K_init must be 3x3")
-        return Kc, Kc.ctypes.data_as(C.POINTER(C.c_double))
+        return Kc, Kc.ctypes.data_as(_DP)
 
     def calibrate(self, obs, tag_map, tag_size, width, height, K_init=None, n_dist=5, flags=0, max_iters=30):
         """asl_calibrate_batch: host records obs (n_frames, max_tags) OBS_DTYPE of a target whose tag poses tag_map
         ((n_ids,) MAP_TAG_DTYPE or a localize.TagMap) gives -> (CALIB_RESULT_DTYPE record, (n_frames,) CAM_POSE_DTYPE)."""
-        if hasattr(tag_map, "as_records"):
-            tag_map = tag_map.as_records()
-        o = np.ascontiguousarray(obs, dtype=OBS_DTYPE)
-        if o.ndim == 1:
-            o = o[None]
-        if o.ndim != 2:
-            raise ValueError("obs must be (n_frames, max_tags) asl_obs records")
-        m = np.ascontiguousarray(tag_map, dtype=MAP_TAG_DTYPE).ravel()
+        o = _obs_records(obs)
+        m = _map_records(tag_map)
         keep, Kp = self._calib_args(K_init, n_dist)
         res = np.zeros((), dtype=CALIB_RESULT_DTYPE)
         poses = np.zeros(o.shape[0], dtype=CAM_POSE_DTYPE)
@@ -389,20 +334,15 @@ class Detector:
         asl_calib_result) and poses_ptr (n_frames asl_cam_pose) are device addresses; the whole solve is enqueued on
         `stream`, no wait."""
         keep, Kp = self._calib_args(K_init, n_dist)
-        check(self._L.asl_calibrate_frames_device(self._h, C.c_void_p(int(obs_ptr)), int(n_frames), int(max_tags), C.c_void_p(int(map_ptr)),
-                                                  int(n_ids), float(tag_size), int(width), int(height), Kp, int(n_dist), int(flags),
-                                                  int(max_iters), C.c_void_p(int(result_ptr)), C.c_void_p(int(poses_ptr)),
-                                                  C.c_void_p(int(stream))))
+        check(self._L.asl_calibrate_frames_device(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids),
+                                                  float(tag_size), int(width), int(height), Kp, int(n_dist), int(flags), int(max_iters),
+                                                  _ptr(result_ptr), _ptr(poses_ptr), _ptr(stream)))
 
     def build_map(self, obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_std=True):
         """asl_map_batch: host records obs (n_frames, max_tags) OBS_DTYPE that see an unknown set of tags -> (MAP_RESULT_DTYPE
         record, (n_ids,) MAP_TAG_DTYPE world<-tag map, (n_ids, 6) tag std or None, (n_frames,) CAM_POSE_DTYPE world<-camera)."""
-        o = np.ascontiguousarray(obs, dtype=OBS_DTYPE)
-        if o.ndim == 1:
-            o = o[None]
-        if o.ndim != 2:
-            raise ValueError("obs must be (n_frames, max_tags) asl_obs records")
-        keep, Kp, dpp, nd = self._camera_args(K, dist)
+        o = _obs_records(obs)
+        keep, Kp, dpp, nd = _camera(K, dist, square=True)
         res = np.zeros((), dtype=MAP_RESULT_DTYPE)
         tmap = np.zeros(max(int(n_ids), 1), dtype=MAP_TAG_DTYPE)
         std = np.zeros((max(int(n_ids), 1), 6), dtype=np.float64) if with_std else None
@@ -417,11 +357,10 @@ class Detector:
         """asl_map_frames_device: obs_ptr (n_frames x max_tags asl_obs, e.g. from pack_observations_device), map_ptr (n_ids
         asl_map_tag, out), std_ptr (n_ids x 6 doubles or 0), poses_ptr (n_frames asl_cam_pose) and result_ptr (one
         asl_map_result) are device addresses; enqueued on `stream` after one wait for the problem size."""
-        keep, Kp, dpp, nd = self._camera_args(K, dist)
-        check(self._L.asl_map_frames_device(self._h, C.c_void_p(int(obs_ptr)), int(n_frames), int(max_tags), int(n_ids), Kp, dpp, nd,
-                                            float(tag_size), int(world_id), int(max_iters), C.c_void_p(int(map_ptr)),
-                                            C.c_void_p(int(std_ptr)) if std_ptr else None, C.c_void_p(int(poses_ptr)),
-                                            C.c_void_p(int(result_ptr)), C.c_void_p(int(stream))))
+        keep, Kp, dpp, nd = _camera(K, dist, square=True)
+        check(self._L.asl_map_frames_device(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), int(n_ids), Kp, dpp, nd, float(tag_size),
+                                            int(world_id), int(max_iters), _ptr(map_ptr), _opt_ptr(std_ptr), _ptr(poses_ptr),
+                                            _ptr(result_ptr), _ptr(stream)))
 
     def collect_view(self):
         """Wait for the submitted batch; (dets, poses or None, n_per_frame) as numpy VIEWS of the detector's page-locked result
@@ -445,30 +384,30 @@ class Detector:
         buffers owned by the detector, valid until its next collect()."""
         n_frames, want_poses = self._inflight
         cap = n_frames * max_per_frame
-        if getattr(self, "_outbuf", None) is None or len(self._outbuf) < cap:
-            self._outbuf = np.empty(cap, dtype=DET_DTYPE)
-        if want_poses and (getattr(self, "_posebuf", None) is None or len(self._posebuf) < cap):
-            self._posebuf = np.empty(cap, dtype=POSE_DTYPE)
+        out, poses = self._result_buffers(cap, want_poses)
         npf = (C.c_int * n_frames)()
         n = C.c_int()
-        check(self._L.asl_collect_batch(self._h, self._outbuf.ctypes.data, self._posebuf.ctypes.data if want_poses else None,
-                                        cap, npf, C.byref(n)))
+        check(self._L.asl_collect_batch(self._h, out.ctypes.data, poses.ctypes.data if want_poses else None, cap, npf, C.byref(n)))
         if n.value > cap:
             raise AslError("more than %d detections per frame on average; raise max_per_frame" % max_per_frame)
-        return self._outbuf[:n.value], (self._posebuf[:n.value] if want_poses else None), np.frombuffer(npf, dtype=np.int32)
+        return out[:n.value], (poses[:n.value] if want_poses else None), np.frombuffer(npf, dtype=np.int32)
+
+    def _result_buffers(self, cap, want_poses):
+        """The detection and pose buffers kept across calls, grown to cap records (fresh multi-MB arrays cost ~1 ms of page
+        faults per call); the pose buffer is None without poses."""
+        if self._outbuf is None or len(self._outbuf) < cap:
+            self._outbuf = np.empty(cap, dtype=DET_DTYPE)
+        if want_poses and (self._posebuf is None or len(self._posebuf) < cap):
+            self._posebuf = np.empty(cap, dtype=POSE_DTYPE)
+        return self._outbuf, (self._posebuf if want_poses else None)
 
     def solve_pnp(self, corners, K, dist, tag_size):
         c = np.ascontiguousarray(np.asarray(corners, dtype=np.float32).reshape(-1, 4, 2))
         N = c.shape[0]
-        Kc = np.ascontiguousarray(K, dtype=np.float64)
-        dc = np.ascontiguousarray(np.zeros(0) if dist is None else dist, dtype=np.float64).ravel()
-        if len(dc) not in (0, 4, 5):
-            raise ValueError("dist must have 0, 4 or 5 coefficients")
+        keep, Kp, dpp, nd = _camera(K, dist)
         rvec = np.zeros((N, 3)); tvec = np.zeros((N, 3)); T = np.zeros((N, 4, 4)); ok = np.zeros(N, np.uint8)
-        dp = C.POINTER(C.c_double)
-        check(self._L.asl_solve_pnp_batch(self._h, c.ctypes.data_as(C.POINTER(C.c_float)), Kc.ctypes.data_as(dp),
-                                          dc.ctypes.data_as(dp) if len(dc) else None, len(dc), float(tag_size),
-                                          rvec.ctypes.data_as(dp), tvec.ctypes.data_as(dp), T.ctypes.data_as(dp),
+        check(self._L.asl_solve_pnp_batch(self._h, c.ctypes.data_as(C.POINTER(C.c_float)), Kp, dpp, nd, float(tag_size),
+                                          rvec.ctypes.data_as(_DP), tvec.ctypes.data_as(_DP), T.ctypes.data_as(_DP),
                                           ok.ctypes.data_as(C.POINTER(C.c_uint8)), N))
         return rvec, tvec, T, ok.astype(bool)
 

@@ -9,6 +9,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -83,7 +84,7 @@ struct asl_detector {
     int refine = 1;
     int pnp_both_minima = 0;
     FamilyDev fam;
-    unsigned long long *d_codes = nullptr;
+    DevBuf<unsigned long long> codes;        // the family's code book (FamilyDev::codes)
     DevBuf<unsigned short> idx_start;        // code-book index of the family (FamilyDev), rebuilt when the id limit changes
     DevBuf<unsigned long long> idx_entries;
 
@@ -117,9 +118,10 @@ struct asl_detector {
     DevBuf<double> pnp_out;
     DevBuf<uint8_t> pnp_ok;
     DevBuf<uint8_t> gn_ws;  // asl_gn_solve: its inputs and the LM's buffers (gn_host.inc)
-    DevBuf<uint8_t> loc_obs, loc_map, loc_out;  // asl_localize_batch: the host records' device copies (grow on demand)
-    DevBuf<uint8_t> cal_ws, cal_out;  // calibration: per-frame workspace and state (k_calib.inc); asl_calibrate_batch's results
-    DevBuf<uint8_t> map_ws, map_lm, map_out;  // map reconstruction (k_map.inc): sized by the input / by the problem; asl_map_batch's results
+    DevBuf<uint8_t> loc_obs, loc_map;  // the *_batch solver entries: the host records' device copies (grow on demand)
+    DevBuf<uint8_t> solve_out;         // the *_batch solver entries: their results, until copied back
+    DevBuf<uint8_t> cal_ws;  // calibration: per-frame workspace and state (k_calib.inc)
+    DevBuf<uint8_t> map_ws, map_lm;  // map reconstruction (k_map.inc): sized by the input / by the problem
     hipStream_t copy_stream = nullptr, host_stream = nullptr;  // host frames: transfers and the chunks' kernels (detect_host_frames)
     std::vector<hipEvent_t> copy_done;
     hipStream_t aux_stream = nullptr;  // highest priority, for the small latency-bound jobs next to a running batch (pose-graph LM)
@@ -137,12 +139,10 @@ struct asl_detector {
     CamDev p_cam{};
     size_t prefetched = 0, nd_guess = 0;
     std::chrono::steady_clock::time_point t_submit, t_enqueued;
-    long long *pinned_counters = nullptr;  // D2H target that does not force a blocking staging copy
-    DetOut *host_det = nullptr;    // pinned staging of the results
-    PoseOut *host_pose = nullptr;
-    size_t host_cap = 0;
-    unsigned int *host_nkeep = nullptr;  // pinned, per frame
-    size_t host_nkeep_cap = 0;
+    PinnedBuf<long long> pinned_counters;  // D2H target that does not force a blocking staging copy
+    PinnedBuf<DetOut> host_det;    // pinned staging of the results, grown together with host_pose
+    PinnedBuf<PoseOut> host_pose;
+    PinnedBuf<unsigned int> host_nkeep;  // per frame
 
     // profiling
     int profiling = 0;
@@ -152,6 +152,16 @@ struct asl_detector {
     float stage_ms[MAX_STAGES] = {0};
     int nstages = 0;
     float host_ms[4] = {0, 0, 0, 0};  // enqueue, wait, copy, post-process of the last batch
+
+    size_t host_cap() const { return std::min(host_det.n, host_pose.n); }  // results the pinned staging holds
+    ~asl_detector()  // the buffers free themselves
+    {
+        for (hipStream_t s : {aux_stream, copy_stream, host_stream})
+            if (s) (void)hipStreamDestroy(s);
+        for (hipEvent_t e : copy_done) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
 };
 
 static const char *kVersion = "aprilslam 0.1 gfx950 (HIP, tagStandard41h12)";
@@ -211,7 +221,7 @@ extern "C" int asl_detector_create(const char *family, int nthreads, int maxhamm
     if (e != hipSuccess || ndev <= 0) return fail(ASL_EDEVICE, "no HIP device available (%s)", hipGetErrorString(e));
     if (device < 0 || device >= ndev) return fail(ASL_EINVAL, "device %d out of range (have %d)", device, ndev);
     HIPCHK(hipSetDevice(device));
-    asl_detector *d = new asl_detector();
+    std::unique_ptr<asl_detector> d(new asl_detector());  // freed with everything it holds on every failure below
     d->device = device;
     d->maxhamming = maxhamming;
     d->decimate = (int)decimate;
@@ -223,37 +233,17 @@ extern "C" int asl_detector_create(const char *family, int nthreads, int maxhamm
     d->fam.reversed_border = 1;
     d->fam.ncodes = kTag41h12PinnedIds;  // ids the reference's own tag images pin; asl_detector_set_id_limit opens the rest
     for (int i = 0; i < kTag41h12NBits; i++) { d->fam.bit_x[i] = kTag41h12BitX[i]; d->fam.bit_y[i] = kTag41h12BitY[i]; }
-    if (hipMalloc((void **)&d->d_codes, sizeof(unsigned long long) * kTag41h12NCodes) != hipSuccess) {
-        delete d;
-        return fail(ASL_ENOMEM, "hipMalloc(code book) failed");
-    }
-    if (hipMemcpy(d->d_codes, kTag41h12Codes, sizeof(unsigned long long) * kTag41h12NCodes, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(d->d_codes);
-        delete d;
+    if (d->codes.ensure(kTag41h12NCodes)) return fail(ASL_ENOMEM, "hipMalloc(code book) failed");
+    if (hipMemcpy(d->codes.p, kTag41h12Codes, sizeof(unsigned long long) * kTag41h12NCodes, hipMemcpyHostToDevice) != hipSuccess)
         return fail(ASL_EDEVICE, "hipMemcpy(code book) failed");
-    }
-    d->fam.codes = d->d_codes;
-    if (build_code_index(d)) {
-        d->idx_start.release(); d->idx_entries.release();
-        (void)hipFree(d->d_codes);
-        delete d;
-        return fail(ASL_ENOMEM, "code-book index allocation failed");
-    }
-    if (d->wtab.ensure(WEIGHT_TABLE_N)) {
-        (void)hipFree(d->d_codes);
-        delete d;
-        return fail(ASL_ENOMEM, "hipMalloc(weight table) failed");
-    }
+    d->fam.codes = d->codes.p;
+    if (build_code_index(d.get())) return fail(ASL_ENOMEM, "code-book index allocation failed");
+    if (d->wtab.ensure(WEIGHT_TABLE_N)) return fail(ASL_ENOMEM, "hipMalloc(weight table) failed");
     hipLaunchKernelGGL(k_weight_table, dim3((WEIGHT_TABLE_N + 255) / 256), dim3(256), 0, 0, d->wtab.p);
-    if (hipDeviceSynchronize() != hipSuccess) {
-        d->wtab.release();
-        (void)hipFree(d->d_codes);
-        delete d;
-        return fail(ASL_EDEVICE, "weight table kernel failed");
-    }
+    if (hipDeviceSynchronize() != hipSuccess) return fail(ASL_EDEVICE, "weight table kernel failed");
     // class-3 quad fit uses 64 KB of dynamic LDS on top of a few hundred static bytes
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fit_quads<256, true, CLASS3_CAP / 256>), hipFuncAttributeMaxDynamicSharedMemorySize, QUAD_LDS_BYTES(CLASS3_CAP));
-    *out = d;
+    *out = d.release();
     return ASL_OK;
 }
 
@@ -262,28 +252,6 @@ extern "C" void asl_detector_destroy(asl_detector *d)
     if (!d) return;
     (void)hipSetDevice(d->device);
     if (d->pending) (void)hipStreamSynchronize(d->p_stream);  // a batch still in flight reads and writes the workspace
-    d->rootmask.release(); d->quad_list.release(); d->dense_tiles.release(); d->dense_seg.release(); d->seg_edges.release(); d->wmask.release(); d->bmask.release();
-    d->dbg_thresh.release(); d->dbg_labels.release();
-    d->frame_ndets.release(); d->frame_idx.release(); d->frame_nkeep.release(); d->frame_off.release(); d->out_det.release(); d->out_pose.release();
-    if (d->host_pose) (void)hipHostFree(d->host_pose);
-    if (d->host_nkeep) (void)hipHostFree(d->host_nkeep);
-    d->in.release(); d->dgray.release(); d->tmin.release(); d->tmax.release(); d->tcut.release();
-    d->parent.release(); d->sizes.release(); d->hkeys.release(); d->points.release(); d->hcounts.release(); d->class_lists.release(); d->stage_pos.release(); d->frame_cursor.release(); d->stage_rec.release();
-    d->slot_cluster.release(); d->clusters.release(); d->quads.release(); d->scratch.release(); d->side_mom.release(); d->quadH.release(); d->wtab.release(); d->dets.release();
-    d->counters.release(); d->pnp_corners.release(); d->pnp_out.release(); d->pnp_ok.release();
-    d->gn_ws.release();
-    d->loc_obs.release(); d->loc_map.release(); d->loc_out.release();
-    d->cal_ws.release(); d->cal_out.release();
-    d->map_ws.release(); d->map_lm.release(); d->map_out.release();
-    if (d->aux_stream) (void)hipStreamDestroy(d->aux_stream);
-    if (d->copy_stream) (void)hipStreamDestroy(d->copy_stream);
-    if (d->host_stream) (void)hipStreamDestroy(d->host_stream);
-    for (hipEvent_t e : d->copy_done) (void)hipEventDestroy(e);
-    if (d->d_codes) (void)hipFree(d->d_codes);
-    d->idx_start.release(); d->idx_entries.release();
-    if (d->host_det) (void)hipHostFree(d->host_det);
-    if (d->pinned_counters) (void)hipHostFree(d->pinned_counters);
-    for (int i = 0; i <= MAX_STAGES; i++) if (d->ev[i]) (void)hipEventDestroy(d->ev[i]);
     delete d;
 }
 
@@ -422,46 +390,39 @@ static int ensure_workspace(asl_detector *d, const Geom &g)
         }                                                                  \
     } while (0)
 
+// tag width in decimated pixels, at least 3 (the quad fit and its finish)
+static int tag_width(const asl_detector *d, const Geom &g) { return std::max(3, d->fam.width_at_border / g.f); }
+
 // Quad fit of one size class (k_quad.inc): grid-stride kernels over the class's device-side cluster list -- many more
 // workgroups than fit on the chip, so the heavy-tailed per-cluster costs balance out (workgroups without work leave at once).
-static void launch_fit_class(asl_detector *d, const Geom &g, int cls, unsigned int B, hipStream_t st)
+// CAP: the class's largest cluster, all in LDS; 0 for the global-slab class.
+template <int BLOCK, int CAP>
+static void launch_fit(asl_detector *d, const Geom &g, int cls, unsigned int grid, hipStream_t st)
 {
     const int want_rev = d->fam.reversed_border ? 1 : 0, want_norm = d->fam.reversed_border ? 0 : 1;
-    int tag_width = d->fam.width_at_border / g.f;
-    if (tag_width < 3) tag_width = 3;
+    hipLaunchKernelGGL((k_fit_quads<BLOCK, (CAP > 0), CAP / BLOCK>), dim3(grid), dim3(BLOCK), CAP > 0 ? QUAD_LDS_BYTES(CAP) : 0, st, d->clusters.p,
+                       d->class_lists.p + (size_t)cls * d->max_clusters, d->counters.p, cls, d->max_clusters, CAP, d->points.p, d->dgray.p, g,
+                       tag_width(d, g), want_rev, want_norm, d->scratch.p, d->quads.p, d->wtab.p, d->side_mom.p);
+}
+
+static void launch_fit_class(asl_detector *d, const Geom &g, int cls, unsigned int B, hipStream_t st)
+{
     const unsigned int qgrid = std::min<unsigned int>(d->max_clusters, std::max<unsigned int>(16384u, 32u * B));
     const unsigned int q2grid = std::min<unsigned int>(d->max_clusters, 2048u);
-    const unsigned int *list = d->class_lists.p + (size_t)cls * d->max_clusters;
     switch (cls) {
-    case 0:
-        hipLaunchKernelGGL((k_fit_quads<64, true, CLASS0_CAP / 64>), dim3(qgrid), dim3(64), QUAD_LDS_BYTES(CLASS0_CAP), st, d->clusters.p, list, d->counters.p, 0,
-                           d->max_clusters, CLASS0_CAP, d->points.p, d->dgray.p, g, tag_width, want_rev, want_norm, d->scratch.p, d->quads.p, d->wtab.p, d->side_mom.p);
-        break;
-    case 1:  // two wavefronts per cluster: the 16 KB slab limits a CU to 7 workgroups, so wider workgroups keep more waves in flight
-        hipLaunchKernelGGL((k_fit_quads<128, true, CLASS1_CAP / 128>), dim3(qgrid), dim3(128), QUAD_LDS_BYTES(CLASS1_CAP), st, d->clusters.p, list, d->counters.p, 1,
-                           d->max_clusters, CLASS1_CAP, d->points.p, d->dgray.p, g, tag_width, want_rev, want_norm, d->scratch.p, d->quads.p, d->wtab.p, d->side_mom.p);
-        break;
-    case 2:
-        hipLaunchKernelGGL((k_fit_quads<256, true, CLASS2_CAP / 256>), dim3(q2grid), dim3(256), QUAD_LDS_BYTES(CLASS2_CAP), st, d->clusters.p, list, d->counters.p, 2,
-                           d->max_clusters, CLASS2_CAP, d->points.p, d->dgray.p, g, tag_width, want_rev, want_norm, d->scratch.p, d->quads.p, d->wtab.p, d->side_mom.p);
-        break;
-    case 3:
-        hipLaunchKernelGGL((k_fit_quads<256, true, CLASS3_CAP / 256>), dim3(q2grid), dim3(256), QUAD_LDS_BYTES(CLASS3_CAP), st, d->clusters.p, list, d->counters.p, 3,
-                           d->max_clusters, CLASS3_CAP, d->points.p, d->dgray.p, g, tag_width, want_rev, want_norm, d->scratch.p, d->quads.p, d->wtab.p, d->side_mom.p);
-        break;
-    default:
-        hipLaunchKernelGGL((k_fit_quads<256, false, 0>), dim3(q2grid), dim3(256), 0, st, d->clusters.p, list, d->counters.p, 4, d->max_clusters, 0, d->points.p,
-                           d->dgray.p, g, tag_width, want_rev, want_norm, d->scratch.p, d->quads.p, d->wtab.p, d->side_mom.p);
-        break;
+    case 0: return launch_fit<64, CLASS0_CAP>(d, g, 0, qgrid, st);
+    // two wavefronts per cluster: the 16 KB slab limits a CU to 7 workgroups, so wider workgroups keep more waves in flight
+    case 1: return launch_fit<128, CLASS1_CAP>(d, g, 1, qgrid, st);
+    case 2: return launch_fit<256, CLASS2_CAP>(d, g, 2, q2grid, st);
+    case 3: return launch_fit<256, CLASS3_CAP>(d, g, 3, q2grid, st);
+    default: return launch_fit<256, 0>(d, g, 4, q2grid, st);
     }
 }
 
 static void launch_quad_finish(asl_detector *d, const Geom &g, hipStream_t st)
 {
-    int tag_width = d->fam.width_at_border / g.f;
-    if (tag_width < 3) tag_width = 3;
     hipLaunchKernelGGL(k_quad_finish, dim3(std::min<unsigned int>((d->max_clusters + 63) / 64, 4096u)), dim3(256), 0, st, d->quads.p, d->side_mom.p, d->counters.p,
-                       d->max_clusters, tag_width);
+                       d->max_clusters, tag_width(d, g));
 }
 
 // enqueue the whole detector for frames resident at d_frames; no host sync
@@ -598,22 +559,16 @@ static CamDev make_cam(const asl_detector *d, const double *K, const double *dis
 using clk = std::chrono::steady_clock;
 static float msf(clk::time_point a, clk::time_point b) { return std::chrono::duration<float, std::milli>(b - a).count(); }
 
+// pinned staging of the results: the per-frame counts at the batch's frame count, detections and poses (together) at
+// twice what is asked for, 4096 or more
 static int ensure_host_out(asl_detector *d, size_t want, size_t nframes)
 {
-    if (nframes > d->host_nkeep_cap) {
-        if (d->host_nkeep) (void)hipHostFree(d->host_nkeep);
-        d->host_nkeep = nullptr; d->host_nkeep_cap = 0;
-        HIPCHK(hipHostMalloc((void **)&d->host_nkeep, nframes * sizeof(unsigned int), hipHostMallocDefault));
-        d->host_nkeep_cap = nframes;
-    }
-    if (want <= d->host_cap) return ASL_OK;
-    if (d->host_det) (void)hipHostFree(d->host_det);
-    if (d->host_pose) (void)hipHostFree(d->host_pose);
-    d->host_det = nullptr; d->host_pose = nullptr; d->host_cap = 0;
+    HIPCHK(d->host_nkeep.ensure(nframes, hipHostMallocDefault));
+    if (want <= d->host_cap()) return ASL_OK;
+    d->host_det.release(); d->host_pose.release();
     want = std::max<size_t>(want * 2, 4096);
-    HIPCHK(hipHostMalloc((void **)&d->host_det, want * sizeof(DetOut), hipHostMallocNonCoherent));  // coarse-grained: CPU-cached
-    HIPCHK(hipHostMalloc((void **)&d->host_pose, want * sizeof(PoseOut), hipHostMallocNonCoherent));
-    d->host_cap = want;
+    HIPCHK(d->host_det.ensure(want, hipHostMallocNonCoherent));  // coarse-grained: CPU-cached
+    HIPCHK(d->host_pose.ensure(want, hipHostMallocNonCoherent));
     return ASL_OK;
 }
 
@@ -627,16 +582,16 @@ static int submit_batch(asl_detector *d, const uint8_t *d_frames, const Geom &g,
     d->t_submit = clk::now();
     rc = enqueue_detect(d, d_frames, g, st, cam);
     if (rc) return rc;
-    if (!d->pinned_counters) HIPCHK(hipHostMalloc((void **)&d->pinned_counters, sizeof(long long) * CNT__N, hipHostMallocDefault));
-    HIPCHK(hipMemcpyAsync(d->pinned_counters, d->counters.p, sizeof(long long) * CNT__N, hipMemcpyDeviceToHost, st));
+    HIPCHK(d->pinned_counters.ensure(CNT__N, hipHostMallocDefault));
+    HIPCHK(hipMemcpyAsync(d->pinned_counters.p, d->counters.p, sizeof(long long) * CNT__N, hipMemcpyDeviceToHost, st));
     d->prefetched = 0;
     rc = ensure_host_out(d, std::min<size_t>(d->nd_guess, d->max_dets), (size_t)g.nframes);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(d->host_nkeep, d->frame_nkeep.p, sizeof(unsigned int) * (size_t)g.nframes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(d->host_nkeep.p, d->frame_nkeep.p, sizeof(unsigned int) * (size_t)g.nframes, hipMemcpyDeviceToHost, st));
     if (d->nd_guess > 0) {  // as many results as the previous batch produced: the usual case needs no second copy
         size_t guess = std::min<size_t>(d->nd_guess, d->max_dets);
-        HIPCHK(hipMemcpyAsync(d->host_det, d->out_det.p, guess * sizeof(DetOut), hipMemcpyDeviceToHost, st));
-        if (cam) HIPCHK(hipMemcpyAsync(d->host_pose, d->out_pose.p, guess * sizeof(PoseOut), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(d->host_det.p, d->out_det.p, guess * sizeof(DetOut), hipMemcpyDeviceToHost, st));
+        if (cam) HIPCHK(hipMemcpyAsync(d->host_pose.p, d->out_pose.p, guess * sizeof(PoseOut), hipMemcpyDeviceToHost, st));
         d->prefetched = guess;
     }
     d->pending = true;
@@ -662,7 +617,7 @@ static int collect_batch(asl_detector *d, asl_detection *out, asl_pose *poses, i
         }
         HIPCHK(hipStreamSynchronize(st));
         t2 = clk::now();
-        memcpy(d->last_counters, d->pinned_counters, sizeof(long long) * CNT__N);
+        memcpy(d->last_counters, d->pinned_counters.p, sizeof(long long) * CNT__N);
         d->last = g;
         long long *c = d->last_counters;
         if (c[CNT_UF_GUARD]) {
@@ -695,11 +650,11 @@ static int collect_batch(asl_detector *d, asl_detection *out, asl_pose *poses, i
     if (nd > d->max_dets) nd = d->max_dets;
     if (nd > d->prefetched) {
         size_t have = d->prefetched;
-        if (nd > d->host_cap) have = 0;  // the staging buffers are about to be replaced
+        if (nd > d->host_cap()) have = 0;  // the staging buffers are about to be replaced
         int rc = ensure_host_out(d, nd, (size_t)g.nframes);
         if (rc) return rc;
-        HIPCHK(hipMemcpy(d->host_det + have, d->out_det.p + have, (nd - have) * sizeof(DetOut), hipMemcpyDeviceToHost));
-        if (cam) HIPCHK(hipMemcpy(d->host_pose + have, d->out_pose.p + have, (nd - have) * sizeof(PoseOut), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(d->host_det.p + have, d->out_det.p + have, (nd - have) * sizeof(DetOut), hipMemcpyDeviceToHost));
+        if (cam) HIPCHK(hipMemcpy(d->host_pose.p + have, d->out_pose.p + have, (nd - have) * sizeof(PoseOut), hipMemcpyDeviceToHost));
     }
     d->nd_guess = nd + nd / 4 + 256;
     clk::time_point t3 = clk::now();
@@ -707,11 +662,18 @@ static int collect_batch(asl_detector *d, asl_detection *out, asl_pose *poses, i
     static_assert(sizeof(DetOut) == sizeof(asl_detection) && sizeof(PoseOut) == sizeof(asl_pose), "device results are copied verbatim");
     int total = (int)nd;
     int nw = std::min(total, max_out);
-    if (out && nw > 0) memcpy(out, d->host_det, (size_t)nw * sizeof(asl_detection));
-    if (poses && cam && nw > 0) memcpy(poses, d->host_pose, (size_t)nw * sizeof(asl_pose));
-    if (n_per_frame) for (int f = 0; f < g.nframes; f++) n_per_frame[f] = (int)d->host_nkeep[f];
+    if (out && nw > 0) memcpy(out, d->host_det.p, (size_t)nw * sizeof(asl_detection));
+    if (poses && cam && nw > 0) memcpy(poses, d->host_pose.p, (size_t)nw * sizeof(asl_pose));
+    if (n_per_frame) for (int f = 0; f < g.nframes; f++) n_per_frame[f] = (int)d->host_nkeep.p[f];
     if (n_out) *n_out = total;
     d->host_ms[0] = msf(t0, t1); d->host_ms[1] = msf(t1, t2); d->host_ms[2] = msf(t2, t3); d->host_ms[3] = msf(t3, clk::now());
+    return ASL_OK;
+}
+
+// the lens models the PnP and the solvers take: none, (k1, k2, p1, p2) or (k1, k2, p1, p2, k3)
+static int check_n_dist(int n_dist)
+{
+    if (n_dist != 0 && n_dist != 4 && n_dist != 5) return fail(ASL_EINVAL, "n_dist must be 0, 4 or 5");
     return ASL_OK;
 }
 
@@ -719,7 +681,7 @@ static int check_device_args(asl_detector *d, const void *d_frames, int n_frames
                              int n_dist, Geom *g)
 {
     if (!d || !d_frames) return fail(ASL_EINVAL, "NULL detector or frames");
-    if (n_dist != 0 && n_dist != 4 && n_dist != 5) return fail(ASL_EINVAL, "n_dist must be 0, 4 or 5");
+    if (int rc = check_n_dist(n_dist)) return rc;
     HIPCHK(hipSetDevice(d->device));
     int rc = make_geom(d, n_frames, channels, w, h, stride, frame_pitch, g);
     if (rc) return rc;
@@ -753,9 +715,9 @@ extern "C" int asl_collect_batch_view(asl_detector *d, const asl_detection **out
     const bool with_poses = d->p_has_cam;
     int rc = collect_batch(d, nullptr, nullptr, 0, nullptr, n_out);  // waits, checks, fills the detector's page-locked result buffers
     if (rc) return rc;
-    *out = reinterpret_cast<const asl_detection *>(d->host_det);
-    if (poses) *poses = with_poses ? reinterpret_cast<const asl_pose *>(d->host_pose) : nullptr;
-    *n_per_frame = d->host_nkeep;
+    *out = reinterpret_cast<const asl_detection *>(d->host_det.p);
+    if (poses) *poses = with_poses ? reinterpret_cast<const asl_pose *>(d->host_pose.p) : nullptr;
+    *n_per_frame = d->host_nkeep.p;
     return ASL_OK;
 }
 
@@ -860,7 +822,7 @@ extern "C" int asl_detect_batch_pose_u8(asl_detector *d, const uint8_t *const *f
 {
     if (!d || !frames || !K || !poses) return fail(ASL_EINVAL, "NULL detector, frames, K or poses");
     if (max_out < 0 || (max_out > 0 && !out)) return fail(ASL_EINVAL, "out is NULL");
-    if (n_dist != 0 && n_dist != 4 && n_dist != 5) return fail(ASL_EINVAL, "n_dist must be 0, 4 or 5");
+    if (int rc = check_n_dist(n_dist)) return rc;
     if (n_dist && !dist) return fail(ASL_EINVAL, "dist is NULL but n_dist = %d", n_dist);
     HIPCHK(hipSetDevice(d->device));
     CamDev cam = make_cam(d, K, dist, n_dist, tag_size);
@@ -959,7 +921,7 @@ extern "C" int asl_solve_pnp_batch(asl_detector *d, const float *corners, const 
 {
     if (!d || !corners || !K || !rvec || !tvec || !T || !ok) return fail(ASL_EINVAL, "NULL argument");
     if (N < 0) return fail(ASL_EINVAL, "N < 0");
-    if (n_dist != 0 && n_dist != 4 && n_dist != 5) return fail(ASL_EINVAL, "n_dist must be 0, 4 or 5");
+    if (int rc = check_n_dist(n_dist)) return rc;
     if (N == 0) return ASL_OK;
     HIPCHK(hipSetDevice(d->device));
     if (d->pnp_corners.ensure((size_t)N * 8) || d->pnp_out.ensure((size_t)N * 22) || d->pnp_ok.ensure((size_t)N))
@@ -986,7 +948,7 @@ static int check_obs_args(int max_tags, int n_ids, int n_dist, bool no_dist, dou
 {
     if (max_tags < 1 || max_tags > 256) return fail(ASL_EINVAL, "max_tags must be in [1, 256] (got %d)", max_tags);
     if (n_ids < 1) return fail(ASL_EINVAL, "n_ids must be >= 1 (got %d)", n_ids);
-    if (n_dist != 0 && n_dist != 4 && n_dist != 5) return fail(ASL_EINVAL, "n_dist must be 0, 4 or 5");
+    if (int rc = check_n_dist(n_dist)) return rc;
     if (n_dist && no_dist) return fail(ASL_EINVAL, "dist is NULL with n_dist = %d", n_dist);
     if (!(tag_size > 0) || !std::isfinite(tag_size)) return fail(ASL_EINVAL, "tag_size must be positive (got %g)", tag_size);
     return ASL_OK;
@@ -1045,11 +1007,11 @@ extern "C" int asl_localize_batch(asl_detector *d, const asl_obs *obs, int n_fra
     if (n_frames == 0) return ASL_OK;
     HIPCHK(hipSetDevice(d->device));
     const size_t out_bytes = sizeof(asl_cam_pose) * (size_t)n_frames;
-    if (d->loc_out.ensure(out_bytes)) return fail(ASL_ENOMEM, "localisation workspace allocation failed");
+    if (d->solve_out.ensure(out_bytes)) return fail(ASL_ENOMEM, "localisation workspace allocation failed");
     if ((rc = upload_obs(d, "localisation", obs, n_frames, max_tags, map, n_ids))) return rc;
-    launch_localize(d, d->loc_obs.p, n_frames, max_tags, d->loc_map.p, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, d->loc_out.p, nullptr);
+    launch_localize(d, d->loc_obs.p, n_frames, max_tags, d->loc_map.p, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, d->solve_out.p, nullptr);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(out, d->loc_out.p, out_bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, d->solve_out.p, out_bytes, hipMemcpyDeviceToHost));
     return ASL_OK;
 }
 
@@ -1069,25 +1031,21 @@ static int check_calib_args(const void *obs, int n_frames, int max_tags, const v
     return ASL_OK;
 }
 
-// the calibration workspace: state, frame lists and per-frame buffers, each 256-byte aligned, in d->cal_ws
+// the calibration workspace: state, frame lists and per-frame buffers, carved from d->cal_ws
 static int launch_calibrate(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids, double tag_size,
                             int width, int height, const double *K_init, int n_dist, int flags, int max_iters, void *d_result, void *d_poses,
                             hipStream_t st)
 {
     static_assert(sizeof(CalibResultRec) == sizeof(asl_calib_result) && sizeof(asl_calib_result) == 216, "asl_calib_result layout");
     const size_t nf = (size_t)n_frames;
-    WsCarve c;
-    const size_t o_st = c.take(sizeof(CalibState)), o_list = c.take(sizeof(int) * nf), o_fr = c.take(sizeof(int) * CAL_FR * nf),
-                 o_zh = c.take(sizeof(double) * CAL_ZH * nf), o_seed = c.take(sizeof(double) * nf),
-                 o_pose = c.take(sizeof(double) * 2 * 12 * nf), o_H = c.take(sizeof(double) * 2 * CAL_HS * nf),
-                 o_SB = c.take(sizeof(double) * CAL_SB * nf), o_bk = c.take(sizeof(double) * CAL_BK * nf);
-    if (d->cal_ws.ensure(c.off)) return fail(ASL_ENOMEM, "calibration workspace allocation failed");
-    uint8_t *w = d->cal_ws.p;
     CalibArgs a{};
+    if (carve_ws(d->cal_ws, [&](WsCarve &c) {
+            a.st = c.take<CalibState>(1); a.list = c.take<int>(nf); a.fr = c.take<int>(CAL_FR * nf);
+            a.zh = c.take<double>(CAL_ZH * nf); a.seedc = c.take<double>(nf); a.pose = c.take<double>(2 * 12 * nf);
+            a.H = c.take<double>(2 * CAL_HS * nf); a.SB = c.take<double>(CAL_SB * nf); a.back = c.take<double>(CAL_BK * nf);
+        }))
+        return fail(ASL_ENOMEM, "calibration workspace allocation failed");
     a.obs = (const ObsRec *)d_obs; a.map = (const MapTagRec *)d_map;
-    a.st = (CalibState *)(w + o_st); a.list = (int *)(w + o_list); a.fr = (int *)(w + o_fr);
-    a.zh = (double *)(w + o_zh); a.seedc = (double *)(w + o_seed); a.pose = (double *)(w + o_pose); a.H = (double *)(w + o_H);
-    a.SB = (double *)(w + o_SB); a.back = (double *)(w + o_bk);
     a.res = (CalibResultRec *)d_result; a.out = (CamPoseRec *)d_poses;
     a.half = (double)(float)(tag_size / 2);  // object corners are float32, as in the PnP
     a.width = width; a.height = height;
@@ -1144,14 +1102,16 @@ extern "C" int asl_calibrate_batch(asl_detector *d, const asl_obs *obs, int n_fr
     int rc = check_calib_args(obs, n_frames, max_tags, map, n_ids, tag_size, width, height, K_init, n_dist, flags, max_iters, result, poses);
     if (rc) return rc;
     HIPCHK(hipSetDevice(d->device));
-    const size_t res_bytes = 256, out_bytes = sizeof(asl_cam_pose) * (size_t)n_frames;
-    if (d->cal_out.ensure(res_bytes + out_bytes)) return fail(ASL_ENOMEM, "calibration workspace allocation failed");
+    asl_calib_result *d_result;
+    asl_cam_pose *d_poses;
+    if (carve_ws(d->solve_out, [&](WsCarve &c) { d_result = c.take<asl_calib_result>(1); d_poses = c.take<asl_cam_pose>(n_frames); }))
+        return fail(ASL_ENOMEM, "calibration workspace allocation failed");
     if ((rc = upload_obs(d, "calibration", obs, n_frames, max_tags, map, n_ids))) return rc;
     rc = launch_calibrate(d, d->loc_obs.p, n_frames, max_tags, d->loc_map.p, n_ids, tag_size, width, height, K_init, n_dist, flags, max_iters,
-                          d->cal_out.p, d->cal_out.p + res_bytes, nullptr);
+                          d_result, d_poses, nullptr);
     if (rc) return rc;
-    HIPCHK(hipMemcpy(result, d->cal_out.p, sizeof(asl_calib_result), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(poses, d->cal_out.p + res_bytes, out_bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(result, d_result, sizeof(asl_calib_result), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(poses, d_poses, sizeof(asl_cam_pose) * (size_t)n_frames, hipMemcpyDeviceToHost));
     return ASL_OK;
 }
 
@@ -1177,6 +1137,17 @@ __global__ void __launch_bounds__(256) k_div_check(unsigned long long seed, int 
     if (nbad) atomicAdd(bad, nbad);
 }
 
+// asl_debug_fetch items 1 and 3: the last batch's threshold image as bytes, into d->dbg_thresh (the pipeline keeps it as
+// two bit masks per 64 pixels)
+static int expand_thresh(asl_detector *d, const Geom &g, size_t total)
+{
+    if (d->dbg_thresh.ensure(total)) return fail(ASL_ENOMEM, "debug buffer allocation failed");
+    hipLaunchKernelGGL(k_seg_debug_thresh, dim3((g.sw + 63) / 64, (g.sh + 3) / 4, (unsigned int)g.nframes), dim3(64, 4), 0, nullptr,
+                       d->wmask.p, d->bmask.p, g, seg_nwx(g), d->dbg_thresh.p);
+    HIPCHK(hipGetLastError());
+    return ASL_OK;
+}
+
 extern "C" int asl_debug_fetch(asl_detector *d, int what, void *dst, size_t bytes, size_t *n_items)
 {
     if (!d || !dst || !n_items) return fail(ASL_EINVAL, "NULL argument");
@@ -1191,12 +1162,9 @@ extern "C" int asl_debug_fetch(asl_detector *d, int what, void *dst, size_t byte
         *n_items = total;
         return ASL_OK;
     }
-    case 1: {  // the pipeline keeps the threshold image as two bit masks per 64 pixels: expand it for the caller
+    case 1: {
         if (bytes < total) return fail(ASL_EINVAL, "dst too small: need %zu bytes", total);
-        if (d->dbg_thresh.ensure(total)) return fail(ASL_ENOMEM, "debug buffer allocation failed");
-        hipLaunchKernelGGL(k_seg_debug_thresh, dim3((g.sw + 63) / 64, (g.sh + 3) / 4, (unsigned int)g.nframes), dim3(64, 4), 0, nullptr,
-                           d->wmask.p, d->bmask.p, g, seg_nwx(g), d->dbg_thresh.p);
-        HIPCHK(hipGetLastError());
+        if (int rc = expand_thresh(d, g, total)) return rc;
         HIPCHK(hipMemcpy(dst, d->dbg_thresh.p, total, hipMemcpyDeviceToHost));
         *n_items = total;
         return ASL_OK;
@@ -1213,10 +1181,7 @@ extern "C" int asl_debug_fetch(asl_detector *d, int what, void *dst, size_t byte
     }
     case 3: {  // sizes are kept at the global roots; "no contrast" pixels are singletons whose size is implied
         if (bytes < total * 4) return fail(ASL_EINVAL, "dst too small: need %zu bytes", total * 4);
-        if (d->dbg_thresh.ensure(total)) return fail(ASL_ENOMEM, "debug buffer allocation failed");
-        hipLaunchKernelGGL(k_seg_debug_thresh, dim3((g.sw + 63) / 64, (g.sh + 3) / 4, (unsigned int)g.nframes), dim3(64, 4), 0, nullptr,
-                           d->wmask.p, d->bmask.p, g, seg_nwx(g), d->dbg_thresh.p);
-        HIPCHK(hipGetLastError());
+        if (int rc = expand_thresh(d, g, total)) return rc;
         std::vector<uint8_t> th(total);
         HIPCHK(hipMemcpy(th.data(), d->dbg_thresh.p, total, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(dst, d->sizes.p, total * 4, hipMemcpyDeviceToHost));
@@ -1364,28 +1329,20 @@ static int launch_map(asl_detector *d, const void *d_obs, int n_frames, int max_
 {
     static_assert(sizeof(MapResultRec) == sizeof(asl_map_result) && sizeof(asl_map_result) == 64, "asl_map_result layout");
     const size_t nf = (size_t)n_frames, ni = (size_t)n_ids, nsl = nf * (size_t)max_tags;
-    WsCarve c;
-    const size_t o_head = c.take(sizeof(MapHead)), o_id = c.take(4 * 4 * (ni + 1)), o_fr = c.take(4 * 3 * (nf + 1)),
-                 o_cam = c.take(4 * 4 * (nf + 1)), o_tag = c.take(4 * (ni + 1)), o_slot = c.take(4 * nsl), o_obs = c.take(4 * 4 * nsl),
-                 o_csr = c.take(4 * (2 * nsl + nf + ni + 2)), o_W = c.take(8 * 12 * nf), o_G = c.take(8 * 12 * ni);
-    if (d->map_ws.ensure(c.off)) return fail(ASL_ENOMEM, "map workspace allocation failed");
-    uint8_t *w = d->map_ws.p;
     MapArgs a{};
+    int *per_id, *per_frame, *per_cam, *per_obs, *csr;  // the grouped int arrays, one piece per group
+    if (carve_ws(d->map_ws, [&](WsCarve &c) {
+            a.head = c.take<MapHead>(1); per_id = c.take<int>(4 * (ni + 1)); per_frame = c.take<int>(3 * (nf + 1));
+            per_cam = c.take<int>(4 * (nf + 1)); a.tag_state = c.take<int>(ni + 1); a.slot_obs = c.take<int>(nsl); per_obs = c.take<int>(4 * nsl);
+            csr = c.take<int>(2 * nsl + nf + ni + 2); a.W = c.take<double>(12 * nf); a.G = c.take<double>(12 * ni);
+        }))
+        return fail(ASL_ENOMEM, "map workspace allocation failed");
     a.obs = (const ObsRec *)d_obs; a.n_frames = n_frames; a.max_tags = max_tags; a.n_ids = n_ids; a.world_req = world_id;
-    a.head = (MapHead *)(w + o_head);
-    int *ip = (int *)(w + o_id);
-    a.seen = ip; a.id_tag = ip + (ni + 1); a.tag_id = ip + 2 * (ni + 1); a.tmp = ip + 3 * (ni + 1);
-    ip = (int *)(w + o_fr);
-    a.fr_npart = ip; a.fr_cam = ip + (nf + 1); a.fr_obs0 = ip + 2 * (nf + 1);
-    ip = (int *)(w + o_cam);
-    a.cam_frame = ip; a.cam_ptr0 = ip + (nf + 1); a.cam_state = ip + 2 * (nf + 1); a.cam_seed = ip + 3 * (nf + 1);
-    a.tag_state = (int *)(w + o_tag);
-    a.slot_obs = (int *)(w + o_slot);
-    ip = (int *)(w + o_obs);
-    a.obs_slot = ip; a.obs_cam = ip + nsl; a.obs_tag = ip + 2 * nsl; a.obs_act = ip + 3 * nsl;
-    ip = (int *)(w + o_csr);
-    a.cam_obs = ip; a.tag_obs = ip + nsl; a.cam_ptr = ip + 2 * nsl; a.tag_ptr = ip + 2 * nsl + nf + 1;
-    a.W = (double *)(w + o_W); a.G = (double *)(w + o_G);
+    a.seen = per_id; a.id_tag = per_id + (ni + 1); a.tag_id = per_id + 2 * (ni + 1); a.tmp = per_id + 3 * (ni + 1);
+    a.fr_npart = per_frame; a.fr_cam = per_frame + (nf + 1); a.fr_obs0 = per_frame + 2 * (nf + 1);
+    a.cam_frame = per_cam; a.cam_ptr0 = per_cam + (nf + 1); a.cam_state = per_cam + 2 * (nf + 1); a.cam_seed = per_cam + 3 * (nf + 1);
+    a.obs_slot = per_obs; a.obs_cam = per_obs + nsl; a.obs_tag = per_obs + 2 * nsl; a.obs_act = per_obs + 3 * nsl;
+    a.cam_obs = csr; a.tag_obs = csr + nsl; a.cam_ptr = csr + 2 * nsl; a.tag_ptr = csr + 2 * nsl + nf + 1;
     const CamDev cam = make_cam(d, K, dist, n_dist, tag_size);
 
     hipLaunchKernelGGL(k_map_gather, dim3(1), dim3(MAP_WG), 0, st, a);
@@ -1415,14 +1372,11 @@ static int launch_map(asl_detector *d, const void *d_obs, int n_frames, int max_
     GnSystem sys = {nullptr, nullptr, a.cam_obs, nullptr, a.tag_obs, a.obs_cam, a.obs_tag, nullptr, NC, NT, WT};
     GnLmBufs b;
     double *seed_obs, *var;
-    auto carve = [&](uint8_t *base) {
-        WsCarve c{(uintptr_t)base};
-        b = gn_lm_carve(c, sys, NM, 2 * MAP_LM__N);
-        seed_obs = c.take<double>(nm); var = c.take<double>(n); sys.cam_ptr = c.take<int>(nc + 1); sys.tag_ptr = c.take<int>(nt + 1);
-        return c.off;
-    };
-    if (d->map_lm.ensure(carve(nullptr))) return fail(ASL_ENOMEM, "map workspace allocation failed");
-    carve(d->map_lm.p);
+    if (carve_ws(d->map_lm, [&](WsCarve &c) {
+            b = gn_lm_carve(c, sys, NM, 2 * MAP_LM__N);
+            seed_obs = c.take<double>(nm); var = c.take<double>(n); sys.cam_ptr = c.take<int>(nc + 1); sys.tag_ptr = c.take<int>(nt + 1);
+        }))
+        return fail(ASL_ENOMEM, "map workspace allocation failed");
     a.obs_of = sys.obs_of;
     double *lm = b.lm, *lm0 = lm + MAP_LM__N;
     const dim3 wg(MAP_WG);
@@ -1494,18 +1448,23 @@ extern "C" int asl_map_batch(asl_detector *d, const asl_obs *obs, int n_frames, 
     int rc = check_map_args(obs, n_frames, max_tags, n_ids, K, dist, n_dist, tag_size, world_id, max_iters, map, poses, result);
     if (rc) return rc;
     HIPCHK(hipSetDevice(d->device));
-    const size_t res_bytes = 256, map_bytes = ((sizeof(asl_map_tag) * (size_t)n_ids + 255) & ~(size_t)255),
-                 std_bytes = ((48 * (size_t)n_ids + 255) & ~(size_t)255), out_bytes = sizeof(asl_cam_pose) * (size_t)n_frames;
-    if (d->map_out.ensure(res_bytes + map_bytes + std_bytes + out_bytes)) return fail(ASL_ENOMEM, "map workspace allocation failed");
+    asl_map_result *d_result;
+    asl_map_tag *d_map;
+    double *d_std;
+    asl_cam_pose *d_poses;
+    if (carve_ws(d->solve_out, [&](WsCarve &c) {
+            d_result = c.take<asl_map_result>(1); d_map = c.take<asl_map_tag>(n_ids); d_std = c.take<double>(6 * (size_t)n_ids);
+            d_poses = c.take<asl_cam_pose>(n_frames);
+        }))
+        return fail(ASL_ENOMEM, "map workspace allocation failed");
     if ((rc = upload_obs(d, "map", obs, n_frames, max_tags, nullptr, n_ids))) return rc;
-    uint8_t *o = d->map_out.p;
-    rc = launch_map(d, d->loc_obs.p, n_frames, max_tags, n_ids, K, dist, n_dist, tag_size, world_id, max_iters, o + res_bytes,
-                    tag_std ? o + res_bytes + map_bytes : nullptr, o + res_bytes + map_bytes + std_bytes, o, nullptr);
+    rc = launch_map(d, d->loc_obs.p, n_frames, max_tags, n_ids, K, dist, n_dist, tag_size, world_id, max_iters, d_map, tag_std ? d_std : nullptr,
+                    d_poses, d_result, nullptr);
     if (rc) return rc;
-    HIPCHK(hipMemcpy(result, o, sizeof(asl_map_result), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(map, o + res_bytes, sizeof(asl_map_tag) * (size_t)n_ids, hipMemcpyDeviceToHost));
-    if (tag_std) HIPCHK(hipMemcpy(tag_std, o + res_bytes + map_bytes, 48 * (size_t)n_ids, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(poses, o + res_bytes + map_bytes + std_bytes, out_bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(result, d_result, sizeof(asl_map_result), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(map, d_map, sizeof(asl_map_tag) * (size_t)n_ids, hipMemcpyDeviceToHost));
+    if (tag_std) HIPCHK(hipMemcpy(tag_std, d_std, sizeof(double) * 6 * (size_t)n_ids, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(poses, d_poses, sizeof(asl_cam_pose) * (size_t)n_frames, hipMemcpyDeviceToHost));
     return ASL_OK;
 }
 

@@ -20,15 +20,19 @@
 #define CLASS2_CAP 512
 #define CLASS3_CAP 1024
 
-// growable device buffer
+// growable device buffer, freed with its owner
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
     int ensure(size_t want)
     {
         if (want <= n) return 0;
-        if (p) { (void)hipFree(p); p = nullptr; n = 0; }
+        release();
         hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
         if (e != hipSuccess) { p = nullptr; return -1; }
         n = want;
@@ -37,8 +41,29 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
 };
 
+// growable page-locked host buffer (hipHostMalloc flags chosen per buffer), freed with its owner
+template <typename T>
+struct PinnedBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { release(); }
+    hipError_t ensure(size_t want, unsigned int flags)
+    {
+        if (want <= n) return hipSuccess;
+        release();
+        hipError_t e = hipHostMalloc((void **)&p, want * sizeof(T), flags);
+        if (e != hipSuccess) { p = nullptr; return e; }
+        n = want;
+        return hipSuccess;
+    }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; n = 0; }
+};
+
 // A workspace carved into consecutive pieces, each 256-byte aligned: take(bytes) returns a piece's offset, off the size so
-// far; take<T>(n) a piece of n T's at base + offset (a carve with base 0 sizes the workspace, then one at its address)
+// far; take<T>(n) a piece of n T's at base + offset
 struct WsCarve {
     uintptr_t base = 0;
     size_t off = 0;
@@ -46,6 +71,19 @@ struct WsCarve {
     template <typename T>
     T *take(size_t n) { return (T *)(base + take(sizeof(T) * n)); }
 };
+
+// carve(c) takes every piece of a workspace from c: once from base 0 to size it, then, buf grown to fit, at buf's address.
+// Nonzero if buf cannot grow.
+template <class Carve>
+static int carve_ws(DevBuf<uint8_t> &buf, Carve carve)
+{
+    WsCarve c;
+    carve(c);
+    if (buf.ensure(c.off)) return -1;
+    c = WsCarve{(uintptr_t)buf.p};
+    carve(c);
+    return 0;
+}
 
 // Geometry of one batch, passed by value to every kernel.
 struct Geom {

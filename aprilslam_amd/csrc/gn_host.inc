@@ -142,16 +142,13 @@ extern "C" int asl_gn_solve(asl_detector *d, int n_cams, int n_tags, int n_obs, 
     sys.n_cams = n_cams; sys.n_tags = n_tags; sys.fixed_tag = fixed_tag;
     double *Wc, *Gc, *corners;
     GnLmBufs b;
-    auto carve = [&](uint8_t *base) {
-        WsCarve c{(uintptr_t)base};
-        Wc = c.take<double>(W.size()); Gc = c.take<double>(G.size()); corners = c.take<double>((size_t)8 * n_obs);
-        sys.obs_cam = c.take<int>(n_obs); sys.obs_tag = c.take<int>(n_obs); sys.cam_ptr = c.take<int>(cam_ptr.size());
-        sys.cam_obs = c.take<int>(n_obs); sys.tag_ptr = c.take<int>(tag_ptr.size()); sys.tag_obs = c.take<int>(n_obs);
-        b = gn_lm_carve(c, sys, n_obs, GN_LM__N);
-        return c.off;
-    };
-    if (d->gn_ws.ensure(carve(nullptr))) return fail(ASL_ENOMEM, "Gauss-Newton workspace allocation failed");
-    carve(d->gn_ws.p);
+    if (carve_ws(d->gn_ws, [&](WsCarve &c) {
+            Wc = c.take<double>(W.size()); Gc = c.take<double>(G.size()); corners = c.take<double>((size_t)8 * n_obs);
+            sys.obs_cam = c.take<int>(n_obs); sys.obs_tag = c.take<int>(n_obs); sys.cam_ptr = c.take<int>(cam_ptr.size());
+            sys.cam_obs = c.take<int>(n_obs); sys.tag_ptr = c.take<int>(tag_ptr.size()); sys.tag_obs = c.take<int>(n_obs);
+            b = gn_lm_carve(c, sys, n_obs, GN_LM__N);
+        }))
+        return fail(ASL_ENOMEM, "Gauss-Newton workspace allocation failed");
     // a stream of its own, at the highest priority: the solve is a chain of small launches and read-backs, and behind a
     // detector batch on a shared queue every one of them would wait for the whole batch
     if (!d->aux_stream) {

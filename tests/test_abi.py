@@ -3,6 +3,7 @@ product path fails loudly instead of falling back to anything."""
 import os
 import re
 
+import numpy as np
 import pytest
 
 from aprilslam_amd import _lib
@@ -26,11 +27,16 @@ def test_header_functions_are_exported():
     assert b"gfx950" in L.asl_version()
 
 
-def test_struct_layouts_match_header():
-    import ctypes as C
-    assert C.sizeof(_lib.AslDetection) == 4 + 4 + 4 + 4 + 16 + 64
-    assert C.sizeof(_lib.AslPose) == 24 + 24 + 128 + 8
-    assert _lib.DET_DTYPE.itemsize == C.sizeof(_lib.AslDetection)
+def test_record_dtypes_have_the_header_layout():
+    """The ABI's records as numpy dtypes: the header's sizes, and every field where a C compiler puts it (the same fields
+    laid out with C alignment land at the same offsets)."""
+    assert _lib.DET_DTYPE.itemsize == 4 + 4 + 4 + 4 + 16 + 64
+    assert _lib.POSE_DTYPE.itemsize == 24 + 24 + 128 + 8
+    for name in ("DET_DTYPE", "POSE_DTYPE", "QUAD_DTYPE", "OBS_DTYPE", "PLANE_DTYPE", "MAP_TAG_DTYPE", "CAM_POSE_DTYPE",
+                 "CALIB_RESULT_DTYPE", "MAP_RESULT_DTYPE"):
+        dt = getattr(_lib, name)
+        c = np.dtype(dt.descr, align=True)
+        assert c.itemsize == dt.itemsize and [c.fields[f][1] for f in c.names] == [dt.fields[f][1] for f in dt.names], name
 
 
 def test_no_cpu_fallback_without_gpu():

@@ -1,7 +1,6 @@
 """Camera calibration from tag observations: the NumPy statement (tests/calib_ref.py) on exact projections, with noise, on
 degenerate input and on the distorted webcam through the CPU oracle detector; the calibration file and the board.  No GPU
 needed."""
-import ctypes as C
 import os
 import re
 
@@ -203,8 +202,8 @@ def test_grid_board_equals_the_synth_scene():
             TagMap.grid(**{**dict(rows=2, cols=2, tag_size=1.0, spacing=2.0), **bad})
 
 
-def test_abi_record_matches_the_header():
-    assert C.sizeof(_lib.AslCalibResult) == 216 and CALIB_RESULT_DTYPE.itemsize == 216
+def test_calib_result_dtype_matches_the_header():
+    assert CALIB_RESULT_DTYPE.itemsize == 216
     src = open(os.path.join(ROOT, "include", "aprilslam.h")).read()
     assert re.search(r"\} asl_calib_result;\s*/\* 216 bytes", src)
     for name in ("asl_calibrate_frames_device", "asl_calibrate_batch"):

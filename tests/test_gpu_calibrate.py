@@ -158,10 +158,9 @@ def test_tag_detector_calibrate_and_camera_params():
     assert r["ok"] and LC.rot_err(r["T"], LC.world_from_camera(*cams[0])) <= 3e-3
 
 
-def test_errors_and_layout(gpu_detector):
-    import ctypes as C
+def test_errors_and_record_size(gpu_detector):
     import torch
-    assert C.sizeof(_lib.AslCalibResult) == CALIB_RESULT_DTYPE.itemsize == 216
+    assert CALIB_RESULT_DTYPE.itemsize == 216
     dev = torch.device("cuda:0")
     obs, rec, _ = CC.scene_case(n=4)
     d_obs = torch.from_numpy(obs.view(np.uint8).copy()).to(dev)

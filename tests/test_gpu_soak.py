@@ -306,3 +306,48 @@ def test_a_batch_gives_the_same_bytes_every_time():
                 assert cur == first, "repetition %d differs from the first" % it
     finally:
         det.close()
+
+
+def test_detectors_created_and_closed_again_and_again():
+    """20 lives of a detector in one process: created; a device batch with PnP; a host batch of two chunks of 64 frames (the
+    copy stream, the chunks' stream and their events); the pose-graph LM, localisation, calibration and map on small cases;
+    profiling on and one more batch; closed.  Every round gives the bytes of the first: a detector frees what it holds
+    exactly once, whatever it created on the way."""
+    import torch
+
+    import calib_cases as CC
+    import localize_cases as LC
+    import map_cases as MC
+    from aprilslam_amd.localize import TagMap
+    from gn_problem import make_problem
+
+    w, h = 320, 240
+    distinct = np.stack([_scene(w, h, 2 + s % 4, 7000 + s, noise=0.0) for s in range(8)])
+    host_frames = np.ascontiguousarray(distinct[np.arange(128) % len(distinct)])
+    d_frames = torch.from_numpy(distinct).to("cuda:0")
+    K, Kb = synth.camera_matrix(w, h), MC.K_bench()
+    obs, tags, _ = MC.exact_block(4, dist=MC.DIST5, K=Kb)
+    rec = TagMap.from_scene(tags).as_records()
+    cal_obs, cal_rec, _ = CC.scene_case(n=8)
+    pr = make_problem(P=8, L=4, seed=1)
+    first = None
+    for r in range(20):
+        det = _lib.Detector("tagStandard41h12", id_limit=0)
+        try:
+            out = list(det.detect_device(d_frames.data_ptr(), len(distinct), 3, w, h, K=K, dist=np.zeros(4), tag_size=10.0))
+            out += det.detect_host(host_frames, K=K, dist=np.zeros(4), tag_size=10.0)
+            out += det.gn_solve(pr["cam0"], pr["tag0"], pr["obs_cam"], pr["obs_tag"], pr["obs_corners"], pr["K"], 10.0, iters=8)
+            out.append(det.localize(obs, rec, Kb, MC.DIST5, LC.TAG_INNER))
+            out += det.calibrate(cal_obs, cal_rec, LC.TAG_INNER, CC.W, CC.H, n_dist=5, max_iters=10)
+            out += det.build_map(obs, MC.N_IDS, Kb, MC.DIST5, LC.TAG_INNER)
+            det.set_profiling(True)
+            out += det.detect_device(d_frames.data_ptr(), len(distinct), 3, w, h, K=K, dist=np.zeros(4), tag_size=10.0)
+            assert "k_decode" in det.stage_times()
+        finally:
+            det.close()
+        cur = [np.ascontiguousarray(x).tobytes() for x in out]
+        if first is None:
+            first = cur
+            assert len(out[0]) >= len(distinct) and len(out[3]) == len(host_frames) // len(distinct) * len(out[0])
+        else:
+            assert cur == first, "round %d differs from the first" % r
