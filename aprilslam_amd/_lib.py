@@ -41,7 +41,7 @@ EXPORTS = [
     "asl_detect_bgr_u8", "asl_detect_batch_u8", "asl_detect_batch_pose_u8", "asl_detect_batch_device", "asl_submit_batch_device", "asl_collect_batch", "asl_collect_batch_view", "asl_solve_pnp_batch", "asl_gn_solve", "asl_pack_observations_device", "asl_graph_frames_device", "asl_graph_picks_device", "asl_render_frames_device",
     "asl_localize_frames_device", "asl_localize_batch", "asl_calibrate_frames_device", "asl_calibrate_batch",
     "asl_map_frames_device", "asl_map_batch",
-    "asl_debug_fetch", "asl_stage_times", "asl_set_profiling", "asl_debug_phase_cycles",
+    "asl_debug_fetch", "asl_debug_refit", "asl_debug_division_check", "asl_stage_times", "asl_set_profiling", "asl_debug_phase_cycles",
 ]
 
 _lib = None
@@ -95,9 +95,11 @@ def load():
     L.asl_map_frames_device.argtypes = [vp, vp, i32, i32, i32, dp, dp, i32, C.c_double, i32, i32, vp, vp, vp, vp, vp]
     L.asl_map_batch.argtypes = [vp, vp, i32, i32, i32, dp, dp, i32, C.c_double, i32, i32, vp, vp, vp, vp]
     L.asl_debug_fetch.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.asl_debug_refit.argtypes = [vp, i32, vp, C.c_size_t]
+    L.asl_debug_division_check.argtypes = [vp, i32, vp, C.c_size_t]
     L.asl_stage_times.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32, C.POINTER(i32)]
     L.asl_set_profiling.argtypes = [vp, i32]
-    L.asl_debug_phase_cycles.argtypes = [vp, C.POINTER(C.c_uint64), i32]
+    L.asl_debug_phase_cycles.argtypes = [vp, C.POINTER(C.c_uint64), C.c_size_t, i32]
     _lib = L
     return L
 
@@ -461,20 +463,18 @@ class Detector:
     def debug_refit(self, reps):
         """Re-run the quad fit of the last batch `reps` times; int64[7]: reps, quads differing from the first run, by size class."""
         buf = np.zeros(7, dtype=np.int64)
-        n = C.c_size_t()
-        check(self._L.asl_debug_fetch(self._h, 7, buf.ctypes.data, int(reps), C.byref(n)))
+        check(self._L.asl_debug_refit(self._h, int(reps), buf.ctypes.data, len(buf)))
         return buf
 
     def debug_division_check(self, exponent_limit=100):
         """(pairs, mismatches) of div_by(a, recip_of(d)) against a / d on the device, exponents within +-exponent_limit."""
         buf = np.zeros(2, dtype=np.int64)
-        n = C.c_size_t()
-        check(self._L.asl_debug_fetch(self._h, 8, buf.ctypes.data, int(exponent_limit), C.byref(n)))
+        check(self._L.asl_debug_division_check(self._h, int(exponent_limit), buf.ctypes.data, len(buf)))
         return int(buf[0]), int(buf[1])
 
     def phase_cycles(self, reset=True):
         buf = (C.c_uint64 * 64)()
-        check(self._L.asl_debug_phase_cycles(self._h, buf, 1 if reset else 0))
+        check(self._L.asl_debug_phase_cycles(self._h, buf, len(buf), 1 if reset else 0))
         return np.array(list(buf), dtype=np.uint64)
 
     def set_profiling(self, on=True):

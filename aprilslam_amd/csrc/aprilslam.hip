@@ -1115,204 +1115,6 @@ extern "C" int asl_calibrate_batch(asl_detector *d, const asl_obs *obs, int n_fr
     return ASL_OK;
 }
 
-// asl_debug_fetch item 8: div_by(a, recip_of(d)) (asl_common.h) against a / d, as compiled into this library: log-uniform
-// magnitudes with exponents within +-lim, both signs, a = 0 now and then
-__global__ void __launch_bounds__(256) k_div_check(unsigned long long seed, int per_thread, int lim, unsigned long long *bad)
-{
-    unsigned long long s = seed + 0x9E3779B97F4A7C15ull * (blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x + 1);
-    auto rng = [&]() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return s; };
-    for (int i = 0; i < 8; i++) rng();
-    unsigned long long nbad = 0;
-    for (int i = 0; i < per_thread; i++) {
-        const unsigned long long u = rng(), v = rng(), w = rng();
-        const int ea = (int)(u % (unsigned)(2 * lim + 1)) - lim, ed = (int)((u >> 20) % (unsigned)(2 * lim + 1)) - lim;
-        double a = ldexp(1.0 + (double)(v & 0xFFFFFFFFFFFFFull) * 0x1p-52, ea);
-        double dd = ldexp(1.0 + (double)(w & 0xFFFFFFFFFFFFFull) * 0x1p-52, ed);
-        if (u & (1ull << 60)) a = -a;
-        if (u & (1ull << 61)) dd = -dd;
-        if ((u >> 40) % 257 == 0) a = 0.0;
-        const double want = a / dd, got = div_by(a, recip_of(dd));
-        if (__double_as_longlong(want) != __double_as_longlong(got)) nbad++;
-    }
-    if (nbad) atomicAdd(bad, nbad);
-}
-
-// asl_debug_fetch items 1 and 3: the last batch's threshold image as bytes, into d->dbg_thresh (the pipeline keeps it as
-// two bit masks per 64 pixels)
-static int expand_thresh(asl_detector *d, const Geom &g, size_t total)
-{
-    if (d->dbg_thresh.ensure(total)) return fail(ASL_ENOMEM, "debug buffer allocation failed");
-    hipLaunchKernelGGL(k_seg_debug_thresh, dim3((g.sw + 63) / 64, (g.sh + 3) / 4, (unsigned int)g.nframes), dim3(64, 4), 0, nullptr,
-                       d->wmask.p, d->bmask.p, g, seg_nwx(g), d->dbg_thresh.p);
-    HIPCHK(hipGetLastError());
-    return ASL_OK;
-}
-
-extern "C" int asl_debug_fetch(asl_detector *d, int what, void *dst, size_t bytes, size_t *n_items)
-{
-    if (!d || !dst || !n_items) return fail(ASL_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(d->device));
-    const Geom &g = d->last;
-    size_t total = (size_t)g.nframes * g.npix;
-    if (what >= 0 && what <= 3 && total == 0) return fail(ASL_EINVAL, "no batch has run yet");
-    switch (what) {
-    case 0: {
-        if (bytes < total) return fail(ASL_EINVAL, "dst too small: need %zu bytes", total);
-        HIPCHK(hipMemcpy(dst, d->dgray.p, total, hipMemcpyDeviceToHost));
-        *n_items = total;
-        return ASL_OK;
-    }
-    case 1: {
-        if (bytes < total) return fail(ASL_EINVAL, "dst too small: need %zu bytes", total);
-        if (int rc = expand_thresh(d, g, total)) return rc;
-        HIPCHK(hipMemcpy(dst, d->dbg_thresh.p, total, hipMemcpyDeviceToHost));
-        *n_items = total;
-        return ASL_OK;
-    }
-    case 2: {  // labels live at run starts (run start -> tile-local root -> global root): resolve them per pixel for the caller
-        if (bytes < total * 4) return fail(ASL_EINVAL, "dst too small: need %zu bytes", total * 4);
-        if (d->dbg_labels.ensure(total)) return fail(ASL_ENOMEM, "debug buffer allocation failed");
-        hipLaunchKernelGGL(k_seg_debug_labels, dim3((g.sw + 63) / 64, (g.sh + 3) / 4, (unsigned int)g.nframes), dim3(64, 4), 0, nullptr,
-                           d->wmask.p, d->bmask.p, g, seg_nwx(g), d->parent.p, d->dbg_labels.p);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpy(dst, d->dbg_labels.p, total * 4, hipMemcpyDeviceToHost));
-        *n_items = total;
-        return ASL_OK;
-    }
-    case 3: {  // sizes are kept at the global roots; "no contrast" pixels are singletons whose size is implied
-        if (bytes < total * 4) return fail(ASL_EINVAL, "dst too small: need %zu bytes", total * 4);
-        if (int rc = expand_thresh(d, g, total)) return rc;
-        std::vector<uint8_t> th(total);
-        HIPCHK(hipMemcpy(th.data(), d->dbg_thresh.p, total, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(dst, d->sizes.p, total * 4, hipMemcpyDeviceToHost));
-        unsigned int *o = (unsigned int *)dst;
-        for (size_t i = 0; i < total; i++)
-            if (th[i] == 127) o[i] = 1u;
-        *n_items = total;
-        return ASL_OK;
-    }
-    case 4: {
-        size_t ncl = (size_t)std::min<long long>(d->last_counters[CNT_NCLUSTERS], (long long)d->max_clusters);
-        std::vector<QuadRec> q(ncl);
-        if (ncl) HIPCHK(hipMemcpy(q.data(), d->quads.p, ncl * sizeof(QuadRec), hipMemcpyDeviceToHost));
-        std::sort(q.begin(), q.end(), [](const QuadRec &a, const QuadRec &b) { return a.key < b.key; });
-        asl_debug_quad *o = (asl_debug_quad *)dst;
-        size_t cap = bytes / sizeof(asl_debug_quad), k = 0;
-        for (size_t i = 0; i < ncl; i++) {
-            if (!q[i].valid) continue;
-            if (k >= cap) return fail(ASL_EINVAL, "dst too small for the quads");
-            for (int a = 0; a < 4; a++) { o[k].p[a][0] = q[i].p[a][0]; o[k].p[a][1] = q[i].p[a][1]; }
-            unsigned long long key = q[i].key;
-            o[k].frame = (int)(key >> 48);
-            o[k].cluster = (((key >> 24) & 0xFFFFFFull) << 32) + (key & 0xFFFFFFull);
-            o[k].reversed_border = q[i].reversed_border;
-            k++;
-        }
-        *n_items = k;
-        return ASL_OK;
-    }
-    case 5: {
-        if (bytes < sizeof(long long) * 18) return fail(ASL_EINVAL, "dst too small");
-        long long *o = (long long *)dst;
-        o[0] = g.nframes; o[1] = g.sw; o[2] = g.sh;
-        o[3] = d->last_counters[CNT_NCLUSTERS]; o[4] = d->last_counters[CNT_NPOINTS]; o[5] = d->last_counters[CNT_NQUADS];
-        o[6] = d->last_counters[CNT_NDETS]; o[7] = d->nslots; o[8] = d->max_clusters; o[9] = d->max_points; o[10] = d->max_dets;
-        o[11] = d->last_counters[CNT_OVERFLOW_HASH]; o[12] = d->last_counters[CNT_OVERFLOW_CLUSTERS];
-        o[13] = d->last_counters[CNT_OVERFLOW_POINTS]; o[14] = d->last_counters[CNT_OVERFLOW_DETS]; o[15] = d->last_counters[CNT_CLASS0];
-        o[16] = d->last_counters[CNT_DENSE_TILES]; o[17] = d->last_counters[CNT_DENSE_SEG];  // tiles that took the dense launches
-        *n_items = 18;
-        return ASL_OK;
-    }
-    case 6: {  // clusters as the quad fit receives them: (key, count, hash of the sorted point records), ordered by key
-        size_t ncl = (size_t)std::min<long long>(d->last_counters[CNT_NCLUSTERS], (long long)d->max_clusters);
-        size_t npts = (size_t)std::min<long long>(d->last_counters[CNT_NPOINTS], (long long)d->max_points);
-        if (bytes < ncl * 24) return fail(ASL_EINVAL, "dst too small: need %zu bytes", ncl * 24);
-        std::vector<ClusterRec> cl(ncl);
-        std::vector<unsigned long long> pts(npts);
-        if (ncl) HIPCHK(hipMemcpy(cl.data(), d->clusters.p, ncl * sizeof(ClusterRec), hipMemcpyDeviceToHost));
-        if (npts) HIPCHK(hipMemcpy(pts.data(), d->points.p, npts * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        std::sort(cl.begin(), cl.end(), [](const ClusterRec &a, const ClusterRec &b) { return a.key < b.key; });
-        unsigned long long *o = (unsigned long long *)dst;
-        for (size_t i = 0; i < ncl; i++) {
-            unsigned long long h = 0xcbf29ce484222325ull;
-            if ((size_t)cl[i].offset + cl[i].count <= npts) {
-                std::sort(pts.begin() + cl[i].offset, pts.begin() + cl[i].offset + cl[i].count);
-                for (unsigned int k = 0; k < cl[i].count; k++) { h ^= pts[(size_t)cl[i].offset + k]; h *= 0x100000001b3ull; }
-            }
-            o[3 * i] = cl[i].key; o[3 * i + 1] = cl[i].count; o[3 * i + 2] = h;
-        }
-        *n_items = ncl;
-        return ASL_OK;
-    }
-    case 7: {  // run the quad fit of the last batch again, `bytes` times, on the buffers it left behind: dst (int64[2 + NCLASSES])
-        // receives the repetitions, the quads that came out differently from the first repetition, and those by size class.
-        // The fit is a pure function of the clusters, so any difference is a race.
-        if (d->pending) return fail(ASL_EINVAL, "a batch is in flight on this detector");
-        size_t ncl = (size_t)std::min<long long>(d->last_counters[CNT_NCLUSTERS], (long long)d->max_clusters);
-        if (!ncl) return fail(ASL_EINVAL, "no clusters in the last batch");
-        const size_t reps = bytes;
-        std::vector<QuadRec> ref(ncl), cur(ncl);
-        std::vector<ClusterRec> cl(ncl);
-        HIPCHK(hipMemcpy(cl.data(), d->clusters.p, ncl * sizeof(ClusterRec), hipMemcpyDeviceToHost));
-        long long *o = (long long *)dst;
-        for (int k = 0; k < 2 + NCLASSES; k++) o[k] = 0;
-        for (size_t r = 0; r < reps; r++) {
-            // the all-LDS classes only: the global-slab class (more than 1024 points) sorts and de-duplicates inside its
-            // clusters' point records, so a second run of it would not see the first one's input
-            for (int cls = 0; cls < NCLASSES - 1; cls++) launch_fit_class(d, g, cls, (unsigned int)g.nframes, nullptr);
-            launch_quad_finish(d, g, nullptr);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpy((r ? cur : ref).data(), d->quads.p, ncl * sizeof(QuadRec), hipMemcpyDeviceToHost));
-            if (!r) continue;
-            for (size_t i = 0; i < ncl; i++) {
-                const bool same = cur[i].valid == ref[i].valid && (!ref[i].valid || memcmp(cur[i].p, ref[i].p, sizeof ref[i].p) == 0);
-                if (same) continue;
-                const unsigned int cnt = cl[i].count;
-                if (cnt > CLASS3_CAP) continue;  // not re-run (above)
-                o[1]++;
-                o[2 + (cnt <= CLASS0_CAP ? 0 : (cnt <= CLASS1_CAP ? 1 : (cnt <= CLASS2_CAP ? 2 : (cnt <= CLASS3_CAP ? 3 : 4))))]++;
-            }
-        }
-        o[0] = (long long)reps;
-        *n_items = 2 + NCLASSES;
-        return ASL_OK;
-    }
-    case 8: {  // the shared-reciprocal division of the line fits against the compiler's division: dst int64[2] = pairs, mismatches
-        unsigned long long *d_bad = nullptr, h_bad = 0;
-        const int lim = bytes > 0 && bytes <= 900 ? (int)bytes : 100, blocks = 2048, per = 1024;
-        HIPCHK(hipMalloc((void **)&d_bad, sizeof h_bad));
-        HIPCHK(hipMemset(d_bad, 0, sizeof h_bad));
-        hipLaunchKernelGGL(k_div_check, dim3(blocks), dim3(256), 0, nullptr, 20260301ull, per, lim, d_bad);
-        hipError_t e8 = hipMemcpy(&h_bad, d_bad, sizeof h_bad, hipMemcpyDeviceToHost);
-        (void)hipFree(d_bad);
-        if (e8 != hipSuccess) return fail(ASL_EDEVICE, "division check failed: %s", hipGetErrorString(e8));
-        ((long long *)dst)[0] = (long long)blocks * 256 * per;
-        ((long long *)dst)[1] = (long long)h_bad;
-        *n_items = 2;
-        return ASL_OK;
-    }
-    default:
-        return fail(ASL_EINVAL, "unknown debug item %d", what);
-    }
-}
-
-extern "C" int asl_debug_phase_cycles(asl_detector *d, unsigned long long *out64, int reset)
-{
-    if (!d || !out64) return fail(ASL_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(d->device));
-    std::vector<unsigned long long> all((size_t)64 * PHASE_SPREAD);
-    HIPCHK(hipMemcpyFromSymbol(all.data(), HIP_SYMBOL(g_phase_cycles), sizeof(unsigned long long) * all.size()));
-    for (int i = 0; i < 64; i++) {
-        out64[i] = 0;
-        for (int k = 0; k < PHASE_SPREAD; k++) out64[i] += all[(size_t)i * PHASE_SPREAD + k];
-    }
-    if (reset) {
-        std::fill(all.begin(), all.end(), 0ull);
-        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_phase_cycles), all.data(), sizeof(unsigned long long) * all.size()));
-    }
-    return ASL_OK;
-}
-
 static int check_map_args(const void *obs, int n_frames, int max_tags, int n_ids, const double *K, const double *dist, int n_dist,
                           double tag_size, int world_id, int max_iters, const void *map, const void *poses, const void *result)
 {
@@ -1468,3 +1270,4 @@ extern "C" int asl_map_batch(asl_detector *d, const asl_obs *obs, int n_frames, 
     return ASL_OK;
 }
 
+#include "debug_host.inc"

@@ -1,0 +1,212 @@
+// Host side of the diagnostics (device side: k_seg_debug_* in k_seg.inc, k_div_check below): asl_debug_fetch, the quad-fit
+// refit, the division check and the phase counters; each checks the room it may write into before it writes anything.
+
+// asl_debug_division_check: div_by(a, recip_of(d)) (asl_common.h) against a / d, as compiled into this library: log-uniform
+// magnitudes with exponents within +-lim, both signs, a = 0 now and then
+__global__ void __launch_bounds__(256) k_div_check(unsigned long long seed, int per_thread, int lim, unsigned long long *bad)
+{
+    unsigned long long s = seed + 0x9E3779B97F4A7C15ull * (blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x + 1);
+    auto rng = [&]() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return s; };
+    for (int i = 0; i < 8; i++) rng();
+    unsigned long long nbad = 0;
+    for (int i = 0; i < per_thread; i++) {
+        const unsigned long long u = rng(), v = rng(), w = rng();
+        const int ea = (int)(u % (unsigned)(2 * lim + 1)) - lim, ed = (int)((u >> 20) % (unsigned)(2 * lim + 1)) - lim;
+        double a = ldexp(1.0 + (double)(v & 0xFFFFFFFFFFFFFull) * 0x1p-52, ea);
+        double dd = ldexp(1.0 + (double)(w & 0xFFFFFFFFFFFFFull) * 0x1p-52, ed);
+        if (u & (1ull << 60)) a = -a;
+        if (u & (1ull << 61)) dd = -dd;
+        if ((u >> 40) % 257 == 0) a = 0.0;
+        const double want = a / dd, got = div_by(a, recip_of(dd));
+        if (__double_as_longlong(want) != __double_as_longlong(got)) nbad++;
+    }
+    if (nbad) atomicAdd(bad, nbad);
+}
+
+// asl_debug_fetch items 1 and 3: the last batch's threshold image as bytes, into d->dbg_thresh (the pipeline keeps it as
+// two bit masks per 64 pixels)
+static int expand_thresh(asl_detector *d, const Geom &g, size_t total)
+{
+    if (d->dbg_thresh.ensure(total)) return fail(ASL_ENOMEM, "debug buffer allocation failed");
+    hipLaunchKernelGGL(k_seg_debug_thresh, dim3((g.sw + 63) / 64, (g.sh + 3) / 4, (unsigned int)g.nframes), dim3(64, 4), 0, nullptr,
+                       d->wmask.p, d->bmask.p, g, seg_nwx(g), d->dbg_thresh.p);
+    HIPCHK(hipGetLastError());
+    return ASL_OK;
+}
+
+extern "C" int asl_debug_fetch(asl_detector *d, int what, void *dst, size_t bytes, size_t *n_items)
+{
+    if (!d || !dst || !n_items) return fail(ASL_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(d->device));
+    const Geom &g = d->last;
+    size_t total = (size_t)g.nframes * g.npix;
+    if (what >= 0 && what <= 3 && total == 0) return fail(ASL_EINVAL, "no batch has run yet");
+    switch (what) {
+    case 0: {
+        if (bytes < total) return fail(ASL_EINVAL, "dst too small: need %zu bytes", total);
+        HIPCHK(hipMemcpy(dst, d->dgray.p, total, hipMemcpyDeviceToHost));
+        *n_items = total;
+        return ASL_OK;
+    }
+    case 1: {
+        if (bytes < total) return fail(ASL_EINVAL, "dst too small: need %zu bytes", total);
+        if (int rc = expand_thresh(d, g, total)) return rc;
+        HIPCHK(hipMemcpy(dst, d->dbg_thresh.p, total, hipMemcpyDeviceToHost));
+        *n_items = total;
+        return ASL_OK;
+    }
+    case 2: {  // labels live at run starts (run start -> tile-local root -> global root): resolve them per pixel for the caller
+        if (bytes < total * 4) return fail(ASL_EINVAL, "dst too small: need %zu bytes", total * 4);
+        if (d->dbg_labels.ensure(total)) return fail(ASL_ENOMEM, "debug buffer allocation failed");
+        hipLaunchKernelGGL(k_seg_debug_labels, dim3((g.sw + 63) / 64, (g.sh + 3) / 4, (unsigned int)g.nframes), dim3(64, 4), 0, nullptr,
+                           d->wmask.p, d->bmask.p, g, seg_nwx(g), d->parent.p, d->dbg_labels.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy(dst, d->dbg_labels.p, total * 4, hipMemcpyDeviceToHost));
+        *n_items = total;
+        return ASL_OK;
+    }
+    case 3: {  // sizes are kept at the global roots; "no contrast" pixels are singletons whose size is implied
+        if (bytes < total * 4) return fail(ASL_EINVAL, "dst too small: need %zu bytes", total * 4);
+        if (int rc = expand_thresh(d, g, total)) return rc;
+        std::vector<uint8_t> th(total);
+        HIPCHK(hipMemcpy(th.data(), d->dbg_thresh.p, total, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(dst, d->sizes.p, total * 4, hipMemcpyDeviceToHost));
+        unsigned int *o = (unsigned int *)dst;
+        for (size_t i = 0; i < total; i++)
+            if (th[i] == 127) o[i] = 1u;
+        *n_items = total;
+        return ASL_OK;
+    }
+    case 4: {  // the count is known once the records are on the host: checked there, before dst is written
+        size_t ncl = (size_t)std::min<long long>(d->last_counters[CNT_NCLUSTERS], (long long)d->max_clusters);
+        std::vector<QuadRec> q(ncl);
+        if (ncl) HIPCHK(hipMemcpy(q.data(), d->quads.p, ncl * sizeof(QuadRec), hipMemcpyDeviceToHost));
+        const size_t nvalid = (size_t)std::count_if(q.begin(), q.end(), [](const QuadRec &r) { return r.valid != 0; });
+        if (bytes < nvalid * sizeof(asl_debug_quad))
+            return fail(ASL_EINVAL, "dst too small: need %zu bytes for %zu quads", nvalid * sizeof(asl_debug_quad), nvalid);
+        std::sort(q.begin(), q.end(), [](const QuadRec &a, const QuadRec &b) { return a.key < b.key; });
+        asl_debug_quad *o = (asl_debug_quad *)dst;
+        size_t k = 0;
+        for (size_t i = 0; i < ncl; i++) {
+            if (!q[i].valid) continue;
+            for (int a = 0; a < 4; a++) { o[k].p[a][0] = q[i].p[a][0]; o[k].p[a][1] = q[i].p[a][1]; }
+            unsigned long long key = q[i].key;
+            o[k].frame = (int)(key >> 48);
+            o[k].cluster = (((key >> 24) & 0xFFFFFFull) << 32) + (key & 0xFFFFFFull);
+            o[k].reversed_border = q[i].reversed_border;
+            k++;
+        }
+        *n_items = k;
+        return ASL_OK;
+    }
+    case 5: {
+        if (bytes < sizeof(long long) * 18) return fail(ASL_EINVAL, "dst too small: need %zu bytes", sizeof(long long) * 18);
+        long long *o = (long long *)dst;
+        o[0] = g.nframes; o[1] = g.sw; o[2] = g.sh;
+        o[3] = d->last_counters[CNT_NCLUSTERS]; o[4] = d->last_counters[CNT_NPOINTS]; o[5] = d->last_counters[CNT_NQUADS];
+        o[6] = d->last_counters[CNT_NDETS]; o[7] = d->nslots; o[8] = d->max_clusters; o[9] = d->max_points; o[10] = d->max_dets;
+        o[11] = d->last_counters[CNT_OVERFLOW_HASH]; o[12] = d->last_counters[CNT_OVERFLOW_CLUSTERS];
+        o[13] = d->last_counters[CNT_OVERFLOW_POINTS]; o[14] = d->last_counters[CNT_OVERFLOW_DETS]; o[15] = d->last_counters[CNT_CLASS0];
+        o[16] = d->last_counters[CNT_DENSE_TILES]; o[17] = d->last_counters[CNT_DENSE_SEG];  // tiles that took the dense launches
+        *n_items = 18;
+        return ASL_OK;
+    }
+    case 6: {  // clusters as the quad fit receives them: (key, count, hash of the sorted point records), ordered by key
+        size_t ncl = (size_t)std::min<long long>(d->last_counters[CNT_NCLUSTERS], (long long)d->max_clusters);
+        size_t npts = (size_t)std::min<long long>(d->last_counters[CNT_NPOINTS], (long long)d->max_points);
+        if (bytes < ncl * 24) return fail(ASL_EINVAL, "dst too small: need %zu bytes", ncl * 24);
+        std::vector<ClusterRec> cl(ncl);
+        std::vector<unsigned long long> pts(npts);
+        if (ncl) HIPCHK(hipMemcpy(cl.data(), d->clusters.p, ncl * sizeof(ClusterRec), hipMemcpyDeviceToHost));
+        if (npts) HIPCHK(hipMemcpy(pts.data(), d->points.p, npts * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        std::sort(cl.begin(), cl.end(), [](const ClusterRec &a, const ClusterRec &b) { return a.key < b.key; });
+        unsigned long long *o = (unsigned long long *)dst;
+        for (size_t i = 0; i < ncl; i++) {
+            unsigned long long h = 0xcbf29ce484222325ull;
+            if ((size_t)cl[i].offset + cl[i].count <= npts) {
+                std::sort(pts.begin() + cl[i].offset, pts.begin() + cl[i].offset + cl[i].count);
+                for (unsigned int k = 0; k < cl[i].count; k++) { h ^= pts[(size_t)cl[i].offset + k]; h *= 0x100000001b3ull; }
+            }
+            o[3 * i] = cl[i].key; o[3 * i + 1] = cl[i].count; o[3 * i + 2] = h;
+        }
+        *n_items = ncl;
+        return ASL_OK;
+    }
+    default:
+        return fail(ASL_EINVAL, "unknown debug item %d", what);
+    }
+}
+
+// Run the quad fit of the last batch again, reps times, on the buffers it left behind; the fit is a pure function of the
+// clusters, so any quad that comes out differently from the first repetition is a race.
+extern "C" int asl_debug_refit(asl_detector *d, int reps, int64_t *out, size_t n_out)
+{
+    if (!d || !out) return fail(ASL_EINVAL, "NULL argument");
+    if (reps < 1) return fail(ASL_EINVAL, "reps must be >= 1 (got %d)", reps);
+    if (n_out < 2 + NCLASSES) return fail(ASL_EINVAL, "out too small: need %d values (got %zu)", 2 + NCLASSES, n_out);
+    if (d->pending) return fail(ASL_EINVAL, "a batch is in flight on this detector");
+    size_t ncl = (size_t)std::min<long long>(d->last_counters[CNT_NCLUSTERS], (long long)d->max_clusters);
+    if (!ncl) return fail(ASL_EINVAL, "no clusters in the last batch");
+    HIPCHK(hipSetDevice(d->device));
+    const Geom &g = d->last;
+    std::vector<QuadRec> ref(ncl), cur(ncl);
+    std::vector<ClusterRec> cl(ncl);
+    HIPCHK(hipMemcpy(cl.data(), d->clusters.p, ncl * sizeof(ClusterRec), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 2 + NCLASSES; k++) out[k] = 0;
+    for (int r = 0; r < reps; r++) {
+        // the all-LDS classes only: the global-slab class (more than 1024 points) sorts and de-duplicates inside its
+        // clusters' point records, so a second run of it would not see the first one's input
+        for (int cls = 0; cls < NCLASSES - 1; cls++) launch_fit_class(d, g, cls, (unsigned int)g.nframes, nullptr);
+        launch_quad_finish(d, g, nullptr);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy((r ? cur : ref).data(), d->quads.p, ncl * sizeof(QuadRec), hipMemcpyDeviceToHost));
+        if (!r) continue;
+        for (size_t i = 0; i < ncl; i++) {
+            const bool same = cur[i].valid == ref[i].valid && (!ref[i].valid || memcmp(cur[i].p, ref[i].p, sizeof ref[i].p) == 0);
+            if (same) continue;
+            const unsigned int cnt = cl[i].count;
+            if (cnt > CLASS3_CAP) continue;  // not re-run (above)
+            out[1]++;
+            out[2 + (cnt <= CLASS0_CAP ? 0 : (cnt <= CLASS1_CAP ? 1 : (cnt <= CLASS2_CAP ? 2 : (cnt <= CLASS3_CAP ? 3 : 4))))]++;
+        }
+    }
+    out[0] = reps;
+    return ASL_OK;
+}
+
+extern "C" int asl_debug_division_check(asl_detector *d, int exponent_limit, int64_t *out, size_t n_out)
+{
+    if (!d || !out) return fail(ASL_EINVAL, "NULL argument");
+    if (exponent_limit < 1 || exponent_limit > 900) return fail(ASL_EINVAL, "exponent_limit must be in [1, 900] (got %d)", exponent_limit);
+    if (n_out < 2) return fail(ASL_EINVAL, "out too small: need 2 values (got %zu)", n_out);
+    HIPCHK(hipSetDevice(d->device));
+    const int blocks = 2048, per = 1024;
+    DevBuf<unsigned long long> d_bad;  // freed on every path
+    if (d_bad.ensure(1)) return fail(ASL_ENOMEM, "debug buffer allocation failed");
+    HIPCHK(hipMemset(d_bad.p, 0, sizeof(unsigned long long)));
+    hipLaunchKernelGGL(k_div_check, dim3(blocks), dim3(256), 0, nullptr, 20260301ull, per, exponent_limit, d_bad.p);
+    HIPCHK(hipGetLastError());
+    unsigned long long h_bad = 0;
+    HIPCHK(hipMemcpy(&h_bad, d_bad.p, sizeof h_bad, hipMemcpyDeviceToHost));
+    out[0] = (int64_t)blocks * 256 * per;
+    out[1] = (int64_t)h_bad;
+    return ASL_OK;
+}
+
+extern "C" int asl_debug_phase_cycles(asl_detector *d, unsigned long long *out, size_t n_out, int reset)
+{
+    if (!d || !out) return fail(ASL_EINVAL, "NULL argument");
+    if (n_out < 64) return fail(ASL_EINVAL, "out too small: need 64 values (got %zu)", n_out);
+    HIPCHK(hipSetDevice(d->device));
+    std::vector<unsigned long long> all((size_t)64 * PHASE_SPREAD);
+    HIPCHK(hipMemcpyFromSymbol(all.data(), HIP_SYMBOL(g_phase_cycles), sizeof(unsigned long long) * all.size()));
+    for (int i = 0; i < 64; i++) {
+        out[i] = 0;
+        for (int k = 0; k < PHASE_SPREAD; k++) out[i] += all[(size_t)i * PHASE_SPREAD + k];
+    }
+    if (reset) {
+        std::fill(all.begin(), all.end(), 0ull);
+        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_phase_cycles), all.data(), sizeof(unsigned long long) * all.size()));
+    }
+    return ASL_OK;
+}

@@ -317,18 +317,19 @@ int asl_render_frames_device(asl_detector *det, void *d_frames, int n_frames, in
                              const void *d_planes, int max_planes, const void *d_textures, int tw, int th, double half,
                              const double *K, const double *dist, int n_dist, void *stream);
 
-/* Introspection for the parity tests: copy an intermediate buffer of the LAST batch to host.
+/* ---- introspection and diagnostics.  asl_debug_fetch, asl_stage_times and the counters (item 5) describe the LAST batch
+   the detector ran.  asl_detect_batch_u8 and asl_detect_batch_pose_u8 run a call of 128 frames or more as consecutive
+   batches of 64 frames, so after such a call that is the call's last chunk (frames 128..149 of a 150-frame call), not the
+   whole call.  asl_debug_fetch, asl_debug_refit, asl_debug_division_check and asl_debug_phase_cycles are told the room
+   they may write into and return ASL_EINVAL, writing nothing, when it is too small; asl_stage_times fills at most max_n. */
+
+/* Copy an intermediate buffer of the last batch to host, for the parity tests.
    what: 0 = decimated gray (u8, B*sh*sw)     1 = threshold image (u8, B*sh*sw)
          2 = component labels (u32, B*sh*sw)  3 = component sizes by label (u32, B*sh*sw)
          4 = candidate quads (asl_debug_quad, count via *n_items)
          5 = stage counters (int64[18]: frames, sw, sh, clusters, points, quads, detections, ..., tiles of the two dense launches)
-         7 = diagnostic: re-run the quad fit of the last batch `bytes` times on the device buffers it left behind; dst receives
-             int64[7]: repetitions, quads that differ from the first repetition, and those by size class (any is a race); clusters of
-             more than 1024 points are left out: their fit sorts in place, a second run would not see the same input
-         8 = diagnostic: the shared-reciprocal division of the line fits (asl_common.h) against the compiler's on 2^29 random
-             operand pairs with exponents within +-`bytes` (default 100); dst receives int64[2]: pairs, mismatches
          6 = clusters handed to the quad fit (uint64[3] each: key, points, hash of the sorted point records), ordered by key
-   bytes = capacity of dst; *n_items = number of elements written. */
+   bytes = capacity of dst in bytes; *n_items = number of elements written. */
 typedef struct {
     double p[4][2]; /* decimated-image pixel coordinates, before the full-resolution rescale */
     uint64_t cluster;
@@ -337,15 +338,24 @@ typedef struct {
 } asl_debug_quad;
 int asl_debug_fetch(asl_detector *det, int what, void *dst, size_t bytes, size_t *n_items);
 
+/* Diagnostic: re-run the quad fit of the last batch reps (>= 1) times on the device buffers it left behind.  It overwrites
+   the last batch's quad records.  Clusters of more than 1024 points are not re-run: their fit sorts in place, so a second
+   run would not see the same input.  out (n_out >= 7) = {repetitions, quads that differ from the first repetition, those
+   by size class 0-4}; any difference is a race.  Fails if a batch is pending or the last batch had no clusters. */
+int asl_debug_refit(asl_detector *det, int reps, int64_t *out, size_t n_out);
+/* Diagnostic: the shared-reciprocal division of the line fits (asl_common.h) against the compiler's on 2^29 random operand
+   pairs with exponents within +-exponent_limit (in [1, 900]).  out (n_out >= 2) = {pairs, mismatches}. */
+int asl_debug_division_check(asl_detector *det, int exponent_limit, int64_t *out, size_t n_out);
+
 /* Time of each stage of the last batch in milliseconds (HIP events on the detector's stream):
    names[i] / ms[i], i < *n. */
 int asl_stage_times(asl_detector *det, const char **names, float *ms, int max_n, int *n);
 /* Enable/disable per-stage event timing (adds a few events per batch; off by default). */
 int asl_set_profiling(asl_detector *det, int enabled);
 
-/* Diagnostic builds only (-DASL_PHASE_TIMING): summed shader-clock cycles per kernel phase
-   (64 counters); all zeros in the shipped library. */
-int asl_debug_phase_cycles(asl_detector *det, unsigned long long *out64, int reset);
+/* Diagnostic builds only (-DASL_PHASE_TIMING): summed shader-clock cycles per kernel phase into out (n_out >= 64
+   counters); all zeros in the shipped library.  reset != 0 zeroes the counters afterwards. */
+int asl_debug_phase_cycles(asl_detector *det, unsigned long long *out, size_t n_out, int reset);
 
 #ifdef __cplusplus
 }

@@ -245,7 +245,7 @@ def test_host_batch_in_chunks_equals_the_device_batch(family):
 
 def test_quad_fit_gives_the_same_quads_every_time():
     """The quad fit is a pure function of the clusters: run again and again on the buffers one batch left behind
-    (asl_debug_fetch item 7) it must return the same quads.  Round 3 found a flag shared by three checks in k_fit_quads
+    (asl_debug_refit) it must return the same quads.  Round 3 found a flag shared by three checks in k_fit_quads
     that let the two wavefronts of a workgroup fall one barrier apart: one quad lost in ~170 batches of 1024 frames,
     invisible to every comparison against the oracle (tools/race_hunt.py is the long form of this test)."""
     import torch
@@ -276,6 +276,55 @@ def test_shared_reciprocal_division_is_the_ieee_quotient():
         for lim in (100, 400):
             pairs, bad = det.debug_division_check(lim)
             assert pairs == 2048 * 256 * 1024 and bad == 0, (lim, pairs, bad)
+    finally:
+        det.close()
+
+
+def test_diagnostics_check_their_room_before_any_work():
+    """The diagnostic entry points called through ctypes as the binding calls them, after one small batch (so the refit
+    has clusters): too little room or an argument out of range is ASL_EINVAL with the need in the message, and the
+    sentinel-filled output stays untouched; exactly enough room is enough; asl_debug_fetch no longer knows items 7 and 8."""
+    import ctypes as C
+
+    import torch
+
+    import bench
+    det = _lib.Detector("tagStandard41h12", decimate=2.0, id_limit=0)
+    try:
+        dev = torch.device("cuda", 0)
+        B = 16
+        d_frames, _, _ = bench.render_stream_device(det, B, dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        K = synth.camera_matrix(bench.W, bench.H)
+        det.submit_device(d_frames.data_ptr(), B, 3, bench.W, bench.H, stream=st, K=K, dist=np.zeros(4), tag_size=bench.TAG_INNER)
+        dets, _, _ = det.collect(max_per_frame=bench.MAXDET)
+        assert len(dets) == 20 * B and det.debug_counters()[3] > 0
+        L, h = det._L, det._h
+        out = np.full(8, -7, dtype=np.int64)
+
+        def refused(rc, need, buf=out, sentinel=-7):
+            assert rc == -1, rc  # ASL_EINVAL
+            msg = L.asl_last_error().decode()
+            assert need in msg, msg
+            assert (buf == sentinel).all(), buf
+
+        refused(L.asl_debug_refit(h, 1, out.ctypes.data, 6), "need 7 values")
+        refused(L.asl_debug_refit(h, 0, out.ctypes.data, 7), "reps must be >= 1")
+        refused(L.asl_debug_division_check(h, 0, out.ctypes.data, 2), "must be in [1, 900]")
+        refused(L.asl_debug_division_check(h, 901, out.ctypes.data, 2), "must be in [1, 900]")
+        refused(L.asl_debug_division_check(h, 100, out.ctypes.data, 1), "need 2 values")
+        n = C.c_size_t(0)
+        for what in (7, 8):
+            refused(L.asl_debug_fetch(h, what, out.ctypes.data, out.nbytes, C.byref(n)), "unknown debug item %d" % what)
+        one_quad = np.full(_lib.QUAD_DTYPE.itemsize, 0xA5, dtype=np.uint8)
+        refused(L.asl_debug_fetch(h, 4, one_quad.ctypes.data, one_quad.nbytes, C.byref(n)), "need", buf=one_quad, sentinel=0xA5)
+        cyc = np.full(64, 7, dtype=np.uint64)
+        cyc_p = cyc.ctypes.data_as(C.POINTER(C.c_uint64))
+        refused(L.asl_debug_phase_cycles(h, cyc_p, 63, 0), "need 64 values", buf=cyc, sentinel=7)
+
+        assert L.asl_debug_refit(h, 2, out.ctypes.data, 7) == 0
+        assert out[:7].tolist() == [2, 0, 0, 0, 0, 0, 0] and out[7] == -7
+        assert L.asl_debug_phase_cycles(h, cyc_p, 64, 0) == 0
     finally:
         det.close()
 

@@ -23,7 +23,7 @@ def main():
     ap.add_argument("--reps", type=int, default=40)
     ap.add_argument("--clutter", type=int, default=0, help="instead of the bench scene: a batch of this many cluttered 720p frames (tools/fuzz_clutter.py: noise, stripes, "
                     "checkerboards over tag scenes -- the dense launches, the large size classes, buffers that grow)")
-    ap.add_argument("--refit", type=int, default=0, help="after one batch, re-run only the quad fit this many times (asl_debug_fetch item 7)")
+    ap.add_argument("--refit", type=int, default=0, help="after one batch, re-run only the quad fit this many times (asl_debug_refit)")
     ap.add_argument("--quads", action="store_true", help="compare the quads of every repetition; on a difference also the clusters")
     ap.add_argument("--deep", action="store_true", help="also compare labels, sizes, clusters (sorted points) and quads of every repetition")
     args = ap.parse_args()
