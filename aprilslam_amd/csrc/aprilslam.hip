@@ -16,12 +16,12 @@
 
 #include "asl_common.h"
 #include "tag_standard41h12.inc"
+#include "k_wave.inc"
 
 #include "k_threshold.inc"
 #include "k_cc.inc"
 #include "k_cluster.inc"
 #include "k_seg.inc"
-#include "k_xchg.inc"
 #include "k_quad.inc"
 #include "k_decode.inc"
 #include "k_pnp.inc"

@@ -17,7 +17,7 @@
 //   and once more k_calib_schur undamped, k_calib_finish (std from the reduced system's inverse, the records).
 // lambda, the accepted state (cur: which of the two pose / normal-equation / theta buffers is current) and the stop flag
 // live in device memory, so the whole solve is one submission; after the stop every kernel returns at once.  Sums over
-// corners are butterfly sums over the wave (wave_sum_f64), sums over frames run over the list of used frames in
+// corners are butterfly sums over the wave (butterfly_sum, k_wave.inc), sums over frames run over the list of used frames in
 // contiguous chunks of a fixed count, then over the chunks in order: no atomics, the same bytes on every run, and frames
 // that do not take part change nothing.  Latency-bound like k_localize.inc: ~4 dependent launches per iteration.
 
@@ -188,8 +188,8 @@ __device__ __forceinline__ void cal_chunk(const CamDev &c, bool fa, double ratio
     }
 #pragma unroll
     for (int i = 0; i < HI - LO; i++) {
-        double v = wave_sum_f64(acc[i]);
-        if (LO + i == NTRI - 1) v += wave_sum_f64(behind);  // the cost entry
+        double v = butterfly_sum<64>(acc[i]);
+        if (LO + i == NTRI - 1) v += butterfly_sum<64>(behind);  // the cost entry
         if (lane == ((LO + i) & (ASL_WAVE - 1))) Hf[LO + i] = v;
     }
 }
@@ -315,10 +315,10 @@ __global__ void __launch_bounds__(64) k_calib_init(CalibArgs a)
             acc[5] += e * e; acc[6] += e * r[2]; acc[7] += 1.0;
         }
     }
-    npart = wave_sum_i32(npart);
+    npart = butterfly_sum<64>(npart);
 #pragma unroll
     for (int i = 0; i < CAL_ZH; i++) {
-        const double v = wave_sum_f64(acc[i]);
+        const double v = butterfly_sum<64>(acc[i]);
         if (lane == i) a.zh[(size_t)CAL_ZH * f + i] = v;
     }
     if (lane == 0) {

@@ -38,25 +38,17 @@ __device__ __forceinline__ void half_angle_normal_dev(double a, double b, double
 // The pivot row and the solved unknowns travel through ds_bpermute (source lane from a ballot); maxima and ties through
 // DPP (xor 1, xor 2, half-row mirror).  corners_H: 10 doubles per cluster -- in: the four refined corners and 0.5 in
 // slot 9 (k_refine); out: H[0..8] and 1.0 (or 0.0 for a singular system).
-template <int CTRL>
-__device__ __forceinline__ double grp8_dpp(double v)
-{
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-    const unsigned int lo = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)(unsigned int)u, CTRL, 0xf, 0xf, false);
-    const unsigned int hi = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)(unsigned int)(u >> 32), CTRL, 0xf, 0xf, false);
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
 __device__ __forceinline__ double grp8_max(double v)  // maximum over the 8 lanes of a group, in all of them
 {
-    v = fmax(v, grp8_dpp<0xB1>(v));   // quad_perm [1,0,3,2]
-    v = fmax(v, grp8_dpp<0x4E>(v));   // quad_perm [2,3,0,1]
-    return fmax(v, grp8_dpp<0x141>(v));  // row_half_mirror: lane i <-> 7 - i, the other quad of the group
+    v = fmax(v, dpp_mov<QUAD_XOR1>(0.0, v));
+    v = fmax(v, dpp_mov<QUAD_XOR2>(0.0, v));
+    return fmax(v, dpp_mov<0x141>(0.0, v));  // row_half_mirror: lane i <-> 7 - i, the other quad of the group
 }
 __device__ __forceinline__ int grp8_min(int v)
 {
-    v = min(v, __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false));
-    v = min(v, __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false));
-    return min(v, __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false));
+    v = min(v, dpp_mov<QUAD_XOR1>(0, v));
+    v = min(v, dpp_mov<QUAD_XOR2>(0, v));
+    return min(v, dpp_mov<0x141>(0, v));
 }
 // value of the group's lane for which `mine` holds (exactly one per group), in all 8 lanes
 __device__ __forceinline__ int grp8_owner(bool mine, int lane)
@@ -92,7 +84,7 @@ __global__ void __launch_bounds__(256) k_homography(double *__restrict__ corners
             double nx, ny;
             half_angle_normal_dev(Cyy - Cxx, -2 * Cxy, &nx, &ny);
             // lines e (own) and e + 1 (next lane of the quad) -> corner e + 1
-            const double n0 = quad_dpp<QUAD_ROT1>(Ex), n1 = quad_dpp<QUAD_ROT1>(Ey), n2 = quad_dpp<QUAD_ROT1>(nx), n3 = quad_dpp<QUAD_ROT1>(ny);
+            const double n0 = dpp_mov<QUAD_ROT1>(0.0, Ex), n1 = dpp_mov<QUAD_ROT1>(0.0, Ey), n2 = dpp_mov<QUAD_ROT1>(0.0, nx), n3 = dpp_mov<QUAD_ROT1>(0.0, ny);
             const double A00 = ny, A01 = -n3;
             const double A10 = -nx, A11 = n2;
             const double B0 = -Ex + n0;
@@ -103,8 +95,8 @@ __global__ void __launch_bounds__(256) k_homography(double *__restrict__ corners
             const double L0 = W00 * B0 + W01 * B1;
             const double cx = Ex + L0 * A00, cy = Ey + L0 * A10;
             // corner e comes from the lane of edge e - 1
-            const double fx = quad_dpp<QUAD_ROT3>(cx), fy = quad_dpp<QUAD_ROT3>(cy);
-            const bool fm = __builtin_amdgcn_update_dpp(0, moved ? 1 : 0, QUAD_ROT3, 0xf, 0xf, false) != 0;
+            const double fx = dpp_mov<QUAD_ROT3>(0.0, cx), fy = dpp_mov<QUAD_ROT3>(0.0, cy);
+            const bool fm = dpp_mov<QUAD_ROT3>(0, moved ? 1 : 0) != 0;
             if (state == 0.25 && fm) { Pex = fx; Pey = fy; }
         }
         // row r: corner i = r / 2; even rows the x equation, odd rows the y equation
@@ -638,7 +630,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) k_
                     if (dd <= (unsigned int)maxhamming && packed < best) best = packed;
                 }
             }
-            best = wave_reduce(best, 0xFFFFFFFFu, [](unsigned int a, unsigned int b2) { return a < b2 ? a : b2; });
+            best = wave_scan<true>(best, 0xFFFFFFFFu, [](unsigned int a, unsigned int b2) { return a < b2 ? a : b2; });
             if (best != 0xFFFFFFFFu) { id = (int)(best & 0xFFFFu); hamming = (int)((best >> 16) & 0xFFu); rotation = (int)(best >> 24); }
         } else {
             // no index (a family wider than 48 bits): every rotation against the whole book

@@ -1,10 +1,8 @@
 // Multi-tag camera localisation against a known tag map (asl_localize_frames_device / asl_localize_batch).
 // One wavefront per frame, float64 throughout.  The frame's max_tags slots x 4 corners are spread over the 64 lanes
 // (corner c = 4 * slot + q on lane c % 64); every pass over the corners ends in a butterfly sum over the wave
-// (lane_xor<1..32>: DPP and v_permlane*_swap, no LDS), after which every lane holds the same bits -- a + b is
-// commutative, and the order of the additions is fixed -- so the small serial parts (candidate choice, 6x6 Cholesky,
-// the step) run redundantly in all lanes on identical inputs, without a broadcast, and a frame's result does not depend
-// on the run.
+// (butterfly_sum, k_wave.inc: every lane then holds the same bits), so the small serial parts (candidate choice, 6x6
+// Cholesky, the step) run redundantly in all lanes on identical inputs, without a broadcast.
 //   gather  taking-part slots (flags & 1, mapped id) -> world corners (LDS, double) and image corners (LDS, float32 as packed)
 //   seed    <= 8 seeding slots (flags & 2) of largest corner area; each slot's PnP pose and its mirrored planar minimum,
 //           composed with the map, scored over ALL taking-part corners: reseed_poses' camera half with the tags held fixed
@@ -31,28 +29,6 @@ struct CamPoseRec {  // == asl_cam_pose, 160 bytes
 #define LOC_MAX_GATE_DROPS 8
 #define LOC_Z_MIN 1e-9
 #define LOC_BEHIND_COST 1e12
-
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-    v += __builtin_bit_cast(double, lane_xor<1>(__builtin_bit_cast(unsigned long long, v)));
-    v += __builtin_bit_cast(double, lane_xor<2>(__builtin_bit_cast(unsigned long long, v)));
-    v += __builtin_bit_cast(double, lane_xor<4>(__builtin_bit_cast(unsigned long long, v)));
-    v += __builtin_bit_cast(double, lane_xor<8>(__builtin_bit_cast(unsigned long long, v)));
-    v += __builtin_bit_cast(double, lane_xor<16>(__builtin_bit_cast(unsigned long long, v)));
-    v += __builtin_bit_cast(double, lane_xor<32>(__builtin_bit_cast(unsigned long long, v)));
-    return v;
-}
-
-__device__ __forceinline__ int wave_sum_i32(int v)
-{
-    v += (int)lane_xor32<1>((unsigned int)v);
-    v += (int)lane_xor32<2>((unsigned int)v);
-    v += (int)lane_xor32<4>((unsigned int)v);
-    v += (int)lane_xor32<8>((unsigned int)v);
-    v += (int)lane_xor32<16>((unsigned int)v);
-    v += (int)lane_xor32<32>((unsigned int)v);
-    return v;
-}
 
 // (area, slot) with the larger area, the lower slot on a tie: the same pair in every lane afterwards
 template <int J>
@@ -165,8 +141,8 @@ __device__ __forceinline__ int loc_gather(const ObsRec *fo, int max_tags, const 
         }
     }
     __syncthreads();
-    if (nseed) *nseed = wave_sum_i32(ns);
-    return wave_sum_i32(npart);
+    if (nseed) *nseed = butterfly_sum<64>(ns);
+    return butterfly_sum<64>(npart);
 }
 
 // The first K indices of [0, n) in the order (area descending, index ascending), counting only areas >= 0 (a negative or
@@ -236,9 +212,9 @@ __device__ __forceinline__ double loc_pass(const CamDev &c, const double *R, con
     }
     if constexpr (NE) {
 #pragma unroll
-        for (int i = 0; i < 27; i++) ne[i] = wave_sum_f64(acc[i]);
+        for (int i = 0; i < 27; i++) ne[i] = butterfly_sum<64>(acc[i]);
     }
-    return wave_sum_f64(cost);
+    return butterfly_sum<64>(cost);
 }
 
 // The fixed schedule (tests/localize_ref.py: lm) on a pose (R, t), refined in place by the left update R <- Rod(w) R,

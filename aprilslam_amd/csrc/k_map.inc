@@ -311,7 +311,7 @@ __global__ void __launch_bounds__(64) k_map_sweep_cam(MapArgs a, CamDev cam)
         if (fo[s].flags & 2) L.area[s] = loc_area(fo[s].corners);
     }
     __syncthreads();
-    npart = wave_sum_i32(npart);
+    npart = butterfly_sum<64>(npart);
     if (npart == 0) return;
     auto score = [&](const double *P) { return loc_pass<false>(cam, P, P + 9, L, n4, lane, nullptr); };
     double P[12];
@@ -380,9 +380,9 @@ __device__ __forceinline__ double map_tag_pass(const MapArgs &a, const CamDev &c
     }
     if constexpr (NE) {
 #pragma unroll
-        for (int i = 0; i < 27; i++) ne[i] = wave_sum_f64(acc[i]);
+        for (int i = 0; i < 27; i++) ne[i] = butterfly_sum<64>(acc[i]);
     }
-    return wave_sum_f64(cost);
+    return butterfly_sum<64>(cost);
 }
 
 // ---- reseed, tag half: one wavefront per tag, the cameras held

@@ -147,28 +147,12 @@ __device__ __forceinline__ void project_dev(const CamDev &c, const double P[3], 
 
 // ---- One tag is solved by a QUAD of lanes, lane q of the quad = corner q.  Everything per corner (undistortion,
 // projection, its two rows of the Jacobian and their contribution to the normal equations) is done by the corner's lane;
-// the four contributions are added with two DPP exchanges inside the quad (every lane ends up with the sum, bit for bit the
-// same in all four: a + b is commutative), and the small serial parts (6x6 Cholesky, Rodrigues, the 3x3 Jacobi sweep) are
-// computed redundantly by the four lanes on identical inputs -- their control flow is identical too.  Against one thread
-// per tag this halves the serial chain of a Levenberg-Marquardt trial, fills every lane of a wave with 16 tags instead of
-// 64 (a wave runs as long as its slowest tag: the trip count has a heavy tail), and the normal equations keep only their
-// lower triangle: the kernel fits 128 registers without scratch (one thread per tag: 256 + 56 and 304 bytes of scratch).
-__device__ __forceinline__ double quad_sum(double v)
-{
-    v += __builtin_bit_cast(double, lane_xor<1>(__builtin_bit_cast(unsigned long long, v)));
-    v += __builtin_bit_cast(double, lane_xor<2>(__builtin_bit_cast(unsigned long long, v)));
-    return v;
-}
-
-template <int K>
-__device__ __forceinline__ double quad_bcast(double v)  // value of lane K of the quad
-{
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-    constexpr int ctrl = K * 0x55;  // quad_perm [K,K,K,K]
-    const unsigned int lo = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)(unsigned int)u, ctrl, 0xf, 0xf, false);
-    const unsigned int hi = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)(unsigned int)(u >> 32), ctrl, 0xf, 0xf, false);
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
+// the four contributions are added by butterfly_sum<4> (k_wave.inc: the same bits in all four lanes), and the small serial
+// parts (6x6 Cholesky, Rodrigues, the 3x3 Jacobi sweep) are computed redundantly by the four lanes on identical inputs --
+// their control flow is identical too.  Against one thread per tag this halves the serial chain of a Levenberg-Marquardt
+// trial, fills every lane of a wave with 16 tags instead of 64 (a wave runs as long as its slowest tag: the trip count has
+// a heavy tail), and the normal equations keep only their lower triangle: the kernel fits 128 registers without scratch
+// (one thread per tag: 256 + 56 and 304 bytes of scratch).
 
 // index of (a, b), a >= b, in the packed lower triangle
 #define TRI(a, b) ((a) * ((a) + 1) / 2 + (b))
@@ -236,7 +220,7 @@ __device__ __forceinline__ double pnp_accumulate_quad(const CamDev &c, const dou
     }
     project_dev(c, P, uv, ne ? Jp : nullptr);
     const double r0 = uv[0] - iu, r1 = uv[1] - iv;
-    const double cost = quad_sum(r0 * r0 + r1 * r1);
+    const double cost = butterfly_sum<4>(r0 * r0 + r1 * r1);
     if (ne) {
         // P(dw) = exp([dw]x) R X + t  ->  dP/dw = -[RX]x ,  dP/dt = I
         const double dPdw[9] = {0, RX[2], -RX[1], -RX[2], 0, RX[0], RX[1], -RX[0], 0};
@@ -250,11 +234,11 @@ __device__ __forceinline__ double pnp_accumulate_quad(const CamDev &c, const dou
         }
 #pragma unroll
         for (int a = 0; a < 6; a++) {
-            const double ga = quad_sum(J0[a] * r0 + J1[a] * r1);
+            const double ga = butterfly_sum<4>(J0[a] * r0 + J1[a] * r1);
             ne[(21 + a) * PNP_TAGS_PER_WAVE] = ga;  // all four lanes: the same value to the same address (no branch, the sum's register is free at once)
 #pragma unroll
             for (int b = 0; b <= a; b++) {
-                const double hab = quad_sum(J0[a] * J0[b] + J1[a] * J1[b]);
+                const double hab = butterfly_sum<4>(J0[a] * J0[b] + J1[a] * J1[b]);
                 ne[TRI(a, b) * PNP_TAGS_PER_WAVE] = hab;
             }
         }

@@ -192,45 +192,10 @@ __device__ __forceinline__ int block_compact(int n, int *s_wave, int *s_base, Pr
     return *s_base;
 }
 
-// One step of a wavefront reduction on the DPP path (no LDS round trip as with ds_bpermute): lanes whose source lies
-// outside the row, or whose row is masked, receive `ident`.
-template <int CTRL, int ROWMASK, typename T>
-__device__ __forceinline__ T dpp_step(T ident, T v)
-{
-    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "32- or 64-bit values");
-    if constexpr (sizeof(T) == 4) {
-        return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, ident), __builtin_bit_cast(int, v), CTRL, ROWMASK, 0xf, false));
-    } else {
-        const unsigned long long iu = __builtin_bit_cast(unsigned long long, ident), vu = __builtin_bit_cast(unsigned long long, v);
-        const unsigned int lo = (unsigned int)__builtin_amdgcn_update_dpp((int)(unsigned int)iu, (int)(unsigned int)vu, CTRL, ROWMASK, 0xf, false);
-        const unsigned int hi = (unsigned int)__builtin_amdgcn_update_dpp((int)(unsigned int)(iu >> 32), (int)(unsigned int)(vu >> 32), CTRL, ROWMASK, 0xf, false);
-        return __builtin_bit_cast(T, ((unsigned long long)hi << 32) | lo);
-    }
-}
-
-// all 64 lanes of the wavefront must be active; the result is wave-uniform
-template <typename T, typename Op>
-__device__ __forceinline__ T wave_reduce(T v, T ident, Op op)
-{
-    v = op(v, dpp_step<0x111, 0xf>(ident, v));  // row_shr:1
-    v = op(v, dpp_step<0x112, 0xf>(ident, v));  // row_shr:2
-    v = op(v, dpp_step<0x114, 0xf>(ident, v));  // row_shr:4
-    v = op(v, dpp_step<0x118, 0xf>(ident, v));  // row_shr:8   -> lane 15 of every row holds the row's result
-    v = op(v, dpp_step<0x142, 0xa>(ident, v));  // row_bcast:15 into rows 1 and 3
-    v = op(v, dpp_step<0x143, 0xc>(ident, v));  // row_bcast:31 into rows 2 and 3 -> lane 63 holds the result
-    if constexpr (sizeof(T) == 4) {
-        return __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-    } else {
-        const unsigned long long vu = __builtin_bit_cast(unsigned long long, v);
-        const unsigned int lo = (unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)vu, 63), hi = (unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)(vu >> 32), 63);
-        return __builtin_bit_cast(T, ((unsigned long long)hi << 32) | lo);
-    }
-}
-
 template <int NT, typename T, typename Op>
 __device__ __forceinline__ T block_reduce(T v, T ident, T *s_tmp, Op op)
 {
-    v = wave_reduce(v, ident, op);
+    v = wave_scan<true>(v, ident, op);
     if (NT == 64) return v;
     int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     __syncthreads();
@@ -250,7 +215,7 @@ __device__ __forceinline__ unsigned int float_sortable(float f)
 }
 
 // ---- bitonic network over PPT keys per thread, element i = e * NT + tid, with every stride a compile-time constant:
-//   stride < 64          partner in the same wavefront: lane_xor<J> (DPP / v_permlane swaps, k_xchg.inc), no LDS round trip
+//   stride < 64          partner in the same wavefront: lane_xor<J> (DPP / v_permlane swaps, k_wave.inc), no LDS round trip
 //   64 <= stride < NT    partner in another wavefront: one pass through LDS (2 of the 36 stages for 256 keys)
 //   stride >= NT         partner is another register of the same thread
 // A network is a chain of ~30 dependent exchanges: with ds_bpermute each of them waits for the LDS crossbar.
@@ -698,18 +663,6 @@ __global__ void __launch_bounds__(NT) k_fit_quads(const ClusterRec *__restrict__
 // and (2,3,0) by lane 1, added in that order; the angle at corner l+1); neighbours' values come through DPP quad
 // permutations.  A cluster that fails a check is computed to the end like the others (no lane leaves; infinities and NaNs of
 // a degenerate cluster stay in its four lanes) and is marked invalid.
-template <int CTRL>
-__device__ __forceinline__ double quad_dpp(double v)
-{
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-    const unsigned int lo = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)(unsigned int)u, CTRL, 0xf, 0xf, false);
-    const unsigned int hi = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)(unsigned int)(u >> 32), CTRL, 0xf, 0xf, false);
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-#define QUAD_ROT1 0x39 /* quad_perm [1,2,3,0]: value of lane l + 1 */
-#define QUAD_ROT2 0x4E /* quad_perm [2,3,0,1]: value of lane l + 2 */
-#define QUAD_ROT3 0x93 /* quad_perm [3,0,1,2]: value of lane l + 3 */
-
 __global__ void __launch_bounds__(256) k_quad_finish(QuadRec *__restrict__ quads, const double *__restrict__ side_mom, const long long *__restrict__ counters,
                                                      unsigned int max_clusters, int tag_width)
 {
@@ -729,7 +682,7 @@ __global__ void __launch_bounds__(256) k_quad_finish(QuadRec *__restrict__ quads
         fit_line_moments_dev(M, 0, line, nullptr, &mse);
         bool fail = mse > MAX_LINE_FIT_MSE;
         // corner l: sides l and l + 1
-        const double n0 = quad_dpp<QUAD_ROT1>(line[0]), n1 = quad_dpp<QUAD_ROT1>(line[1]), n2 = quad_dpp<QUAD_ROT1>(line[2]), n3 = quad_dpp<QUAD_ROT1>(line[3]);
+        const double n0 = dpp_mov<QUAD_ROT1>(0.0, line[0]), n1 = dpp_mov<QUAD_ROT1>(0.0, line[1]), n2 = dpp_mov<QUAD_ROT1>(0.0, line[2]), n3 = dpp_mov<QUAD_ROT1>(0.0, line[3]);
         const double A00 = line[3], A01 = -n3;
         const double A10 = -line[2], A11 = n2;
         const double B0 = -line[0] + n0;
@@ -743,8 +696,8 @@ __global__ void __launch_bounds__(256) k_quad_finish(QuadRec *__restrict__ quads
             Px = line[0] + L0v * A00;
             Py = line[1] + L0v * A10;
         }
-        const double P1x = quad_dpp<QUAD_ROT1>(Px), P1y = quad_dpp<QUAD_ROT1>(Py), P2x = quad_dpp<QUAD_ROT2>(Px), P2y = quad_dpp<QUAD_ROT2>(Py);
-        const double P3x = quad_dpp<QUAD_ROT3>(Px), P3y = quad_dpp<QUAD_ROT3>(Py);
+        const double P1x = dpp_mov<QUAD_ROT1>(0.0, Px), P1y = dpp_mov<QUAD_ROT1>(0.0, Py), P2x = dpp_mov<QUAD_ROT2>(0.0, Px), P2y = dpp_mov<QUAD_ROT2>(0.0, Py);
+        const double P3x = dpp_mov<QUAD_ROT3>(0.0, Px), P3y = dpp_mov<QUAD_ROT3>(0.0, Py);
         // triangles (0,1,2) in lane 0 and (2,3,0) in lane 1: the vertices are this lane's corners l, l+1, l+2 resp. l+1, l+2, l+3
         const bool t0 = l == 0;
         const double ax = t0 ? Px : P1x, ay = t0 ? Py : P1y, bx = t0 ? P1x : P2x, by = t0 ? P1y : P2y, cx = t0 ? P2x : P3x, cy = t0 ? P2y : P3y;
@@ -758,8 +711,8 @@ __global__ void __launch_bounds__(256) k_quad_finish(QuadRec *__restrict__ quads
         if ((cos_dtheta > COS_CRITICAL_RAD || cos_dtheta < -COS_CRITICAL_RAD) || dx1 * dy2 < dy1 * dx2) fail = true;
         const bool any_fail = ((__ballot(fail) >> (lane & ~3)) & 0xFull) != 0;
         double area = 0;
-        area += tri;                          // lane 0: s_tri[0]
-        area += quad_dpp<QUAD_ROT1>(tri);     // lane 0: + s_tri[1]
+        area += tri;                           // lane 0: s_tri[0]
+        area += dpp_mov<QUAD_ROT1>(0.0, tri);  // lane 0: + s_tri[1]
         if (pending) {
             quads[ci].p[l][0] = Px; quads[ci].p[l][1] = Py;
             if (l == 0) quads[ci].valid = (!any_fail && !(area < 0.95 * tag_width * tag_width)) ? 1 : 0;

@@ -189,20 +189,6 @@ __global__ void __launch_bounds__(256) k_tile_cut(const uint8_t *__restrict__ tm
 #endif
 #define SEG_CAP 512  /* runs (and links) of a tile the common launch labels; a tile with more goes on the dense list (k_seg_tile_dense) */
 
-// inclusive prefix sum over the 64 lanes on the DPP path (no LDS round trip as with ds_bpermute); all lanes must be active
-__device__ __forceinline__ unsigned int seg_wave_scan(unsigned int v)
-{
-#define SEG_DPP_ADD(CTRL, ROWMASK) v += (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWMASK, 0xf, false)
-    SEG_DPP_ADD(0x111, 0xf);  // row_shr:1
-    SEG_DPP_ADD(0x112, 0xf);  // row_shr:2
-    SEG_DPP_ADD(0x114, 0xf);  // row_shr:4
-    SEG_DPP_ADD(0x118, 0xf);  // row_shr:8   -> prefix sums inside every row of 16 lanes
-    SEG_DPP_ADD(0x142, 0xa);  // row_bcast:15 into rows 1 and 3
-    SEG_DPP_ADD(0x143, 0xc);  // row_bcast:31 into rows 2 and 3
-#undef SEG_DPP_ADD
-    return v;
-}
-
 // bits 0 .. x of a word
 __device__ __forceinline__ unsigned long long seg_upto(int x) { return ~0ull >> (63 - x); }
 
@@ -257,10 +243,7 @@ __device__ __forceinline__ unsigned long long seg_threshold_tile(const uint8_t *
         cbits &= left >= 16 ? 0xFFFFu : (left <= 0 ? 0u : (1u << left) - 1u);
         wbits &= cbits;
         const unsigned int pk = wbits | ((cbits & ~wbits) << 16);  // white | black << 16
-        const unsigned int q0 = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)pk, 0x00, 0xf, 0xf, false);  // quad_perm [0,0,0,0]
-        const unsigned int q1 = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)pk, 0x55, 0xf, 0xf, false);
-        const unsigned int q2 = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)pk, 0xAA, 0xf, 0xf, false);
-        const unsigned int q3 = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)pk, 0xFF, 0xf, 0xf, false);
+        const unsigned int q0 = quad_bcast<0>(pk), q1 = quad_bcast<1>(pk), q2 = quad_bcast<2>(pk), q3 = quad_bcast<3>(pk);
         const bool blk = (seg & 1) != 0;  // lane 4r' keeps the white mask of its row, lane 4r' + 1 the black one
         xlo[hf] = blk ? ((q0 >> 16) | (q1 & 0xFFFF0000u)) : ((q0 & 0xFFFFu) | (q1 << 16));
         xhi[hf] = blk ? ((q2 >> 16) | (q3 & 0xFFFF0000u)) : ((q2 & 0xFFFFu) | (q3 << 16));
@@ -334,8 +317,9 @@ __global__ void __launch_bounds__(64 * SEG_TILE_WAVES) k_seg_tile(const uint8_t 
     link[1] = isw ? (M & J & (Mp << 1) & ~Mp) : 0ull;               // up-left, only where "up" does not already connect
     link[2] = isw ? (M & J & (Mp >> 1) & ~(Mp & (J >> 1))) : 0ull;  // up-right, unless up connects and x+1 joins x above
     const unsigned int nlinks_lane = (unsigned int)(__popcll(link[0]) + __popcll(link[1]) + __popcll(link[2])), nruns_lane = (unsigned int)__popcll(S);
-    const unsigned int incl = seg_wave_scan(nlinks_lane | (nruns_lane << 16));  // at most 64 x 96 links and 64 x 32 runs: both fit 16 bits
-    const unsigned int tot = (unsigned int)__builtin_amdgcn_readlane((int)incl, 63);
+    // inclusive prefix sums; at most 64 x 96 links and 64 x 32 runs: both fit 16 bits
+    const unsigned int incl = wave_scan<false>(nlinks_lane | (nruns_lane << 16), 0u, [](unsigned int a, unsigned int b) { return a + b; });
+    const unsigned int tot = readlane(incl, 63);
     const int nlinks = (int)(tot & 0xFFFFu), nruns = (int)(tot >> 16);
     PHASE_COUNT(12, nlinks); PHASE_COUNT(13, nruns); PHASE_COUNT(14, 1);
     if (nlinks > SEG_CAP || nruns > SEG_CAP) {

@@ -2,7 +2,7 @@
 // v_permlane16_swap, v_permlane32_swap) against __shfl_xor, on the device.  hipcc --offload-arch=gfx950 tools/xchg_test.hip -o build/xchg_test
 #include <hip/hip_runtime.h>
 #include <cstdio>
-#include "../aprilslam_amd/csrc/k_xchg.inc"
+#include "../aprilslam_amd/csrc/k_wave.inc"
 
 __global__ void k(unsigned long long *out, const unsigned long long *in)
 {
