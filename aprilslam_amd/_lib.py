@@ -29,17 +29,20 @@ CALIB_RESULT_DTYPE = np.dtype([("K", "<f8", (3, 3)), ("dist", "<f8", (5,)), ("st
 MAP_RESULT_DTYPE = np.dtype([("cost_seed", "<f8"), ("cost", "<f8"), ("rms_px", "<f8"), ("rms_seed_px", "<f8"),
                              ("n_frames_used", "<i4"), ("n_tags", "<i4"), ("n_obs", "<i4"), ("n_obs_dropped", "<i4"),
                              ("iterations", "<i4"), ("world_id", "<i4"), ("status", "<i4"), ("reserved", "<i4")])  # asl_map_result
+POSE_COV_DTYPE = np.dtype([("cov", "<f8", (6, 6)), ("sigma_px", "<f8"), ("dof", "<i4"), ("status", "<i4")])  # asl_pose_cov
 QUAD_DTYPE = np.dtype([("p", "<f8", (4, 2)), ("cluster", "<u8"), ("frame", "<i4"), ("reversed_border", "<i4")])  # asl_debug_quad
 assert DET_DTYPE.itemsize == 96 and POSE_DTYPE.itemsize == 184 and QUAD_DTYPE.itemsize == 80  # asl_detection, asl_pose, asl_debug_quad
 assert MAP_TAG_DTYPE.itemsize == 104
 assert CAM_POSE_DTYPE.itemsize == 160
 assert CALIB_RESULT_DTYPE.itemsize == 216
 assert MAP_RESULT_DTYPE.itemsize == 64
+assert POSE_COV_DTYPE.itemsize == 304
 
 EXPORTS = [
     "asl_detector_create", "asl_detector_destroy", "asl_detector_set_id_limit", "asl_detector_set_pnp_both_minima", "asl_last_error", "asl_version", "asl_detect_gray_u8",
     "asl_detect_bgr_u8", "asl_detect_batch_u8", "asl_detect_batch_pose_u8", "asl_detect_batch_device", "asl_submit_batch_device", "asl_collect_batch", "asl_collect_batch_view", "asl_solve_pnp_batch", "asl_gn_solve", "asl_pack_observations_device", "asl_graph_frames_device", "asl_graph_picks_device", "asl_render_frames_device",
-    "asl_localize_frames_device", "asl_localize_batch", "asl_calibrate_frames_device", "asl_calibrate_batch",
+    "asl_localize_frames_device", "asl_localize_batch", "asl_localize_cov_frames_device", "asl_localize_cov_batch",
+    "asl_pose_cov_device", "asl_solve_pnp_cov_batch", "asl_calibrate_frames_device", "asl_calibrate_batch",
     "asl_map_frames_device", "asl_map_batch",
     "asl_debug_fetch", "asl_debug_refit", "asl_debug_division_check", "asl_stage_times", "asl_set_profiling", "asl_debug_phase_cycles",
 ]
@@ -90,6 +93,10 @@ def load():
     L.asl_graph_picks_device.argtypes = [vp, vp, i32, i32, i32, vp, C.c_uint32, C.c_uint32, vp, i32, vp, vp]
     L.asl_localize_frames_device.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, C.c_double, vp, vp]
     L.asl_localize_batch.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, C.c_double, vp]
+    L.asl_localize_cov_frames_device.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp]
+    L.asl_localize_cov_batch.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, C.c_double, C.c_double, vp, vp]
+    L.asl_pose_cov_device.argtypes = [vp, vp, i32, dp, dp, i32, C.c_double, C.c_double, vp, vp]
+    L.asl_solve_pnp_cov_batch.argtypes = [vp, C.POINTER(C.c_float), dp, dp, dp, i32, C.c_double, C.c_double, vp, i32]
     L.asl_calibrate_frames_device.argtypes = [vp, vp, i32, i32, vp, i32, C.c_double, i32, i32, dp, i32, i32, i32, vp, vp, vp]
     L.asl_calibrate_batch.argtypes = [vp, vp, i32, i32, vp, i32, C.c_double, i32, i32, dp, i32, i32, i32, vp, vp]
     L.asl_map_frames_device.argtypes = [vp, vp, i32, i32, i32, dp, dp, i32, C.c_double, i32, i32, vp, vp, vp, vp, vp]
@@ -285,25 +292,55 @@ class Detector:
         check(self._L.asl_graph_picks_device(self._h, _ptr(obs_ptr), int(world), int(n_frames), int(max_tags), _ptr(status_ptr),
                                              int(order_lo), int(order_hi), _ptr(last_ptr), int(n_ids), _ptr(picks_ptr), _ptr(stream)))
 
-    def localize(self, obs, tag_map, K, dist, tag_size, max_tag_rms_px=0.0):
+    def localize(self, obs, tag_map, K, dist, tag_size, max_tag_rms_px=0.0, sigma_px=None):
         """asl_localize_batch: host records obs (n_frames, max_tags) OBS_DTYPE (e.g. dist.pack_observations) against
-        tag_map (n_ids,) MAP_TAG_DTYPE (or a localize.TagMap) -> (n_frames,) CAM_POSE_DTYPE, world<-camera per frame."""
+        tag_map (n_ids,) MAP_TAG_DTYPE (or a localize.TagMap) -> (n_frames,) CAM_POSE_DTYPE, world<-camera per frame.
+        sigma_px not None: asl_localize_cov_batch -> (poses, (n_frames,) POSE_COV_DTYPE), the covariance scaled by that
+        corner sigma, or by the solve's own estimate for 0."""
         o = _obs_records(obs)
         m = _map_records(tag_map)
         keep, Kp, dpp, nd = _camera(K, dist, square=True)
         out = np.zeros(o.shape[0], dtype=CAM_POSE_DTYPE)
-        check(self._L.asl_localize_batch(self._h, o.ctypes.data if o.size else None, o.shape[0], o.shape[1],
-                                         m.ctypes.data if m.size else None, len(m), Kp, dpp, nd, float(tag_size),
-                                         float(max_tag_rms_px), out.ctypes.data if out.size else None))
-        return out
+        args = (self._h, o.ctypes.data if o.size else None, o.shape[0], o.shape[1], m.ctypes.data if m.size else None, len(m), Kp, dpp, nd,
+                float(tag_size), float(max_tag_rms_px))
+        if sigma_px is None:
+            check(self._L.asl_localize_batch(*args, out.ctypes.data if out.size else None))
+            return out
+        cov = np.zeros(o.shape[0], dtype=POSE_COV_DTYPE)
+        check(self._L.asl_localize_cov_batch(*args, float(sigma_px), out.ctypes.data if out.size else None, cov.ctypes.data if cov.size else None))
+        return out, cov
 
     def localize_device(self, obs_ptr, n_frames, max_tags, map_ptr, n_ids, out_ptr, K, dist, tag_size, max_tag_rms_px=0.0,
-                        stream=0):
+                        stream=0, cov_ptr=None, sigma_px=0.0):
         """asl_localize_frames_device: obs_ptr (n_frames x max_tags asl_obs, e.g. from pack_observations_device), map_ptr
-        (n_ids asl_map_tag) and out_ptr (n_frames asl_cam_pose) are device addresses; enqueued on `stream`, no wait."""
+        (n_ids asl_map_tag) and out_ptr (n_frames asl_cam_pose) are device addresses; enqueued on `stream`, no wait.
+        cov_ptr not None (n_frames asl_pose_cov): asl_localize_cov_frames_device with sigma_px."""
         keep, Kp, dpp, nd = _camera(K, dist, square=True)
-        check(self._L.asl_localize_frames_device(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids), Kp, dpp,
-                                                 nd, float(tag_size), float(max_tag_rms_px), _ptr(out_ptr), _ptr(stream)))
+        args = (self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids), Kp, dpp, nd, float(tag_size), float(max_tag_rms_px))
+        if cov_ptr is None:
+            check(self._L.asl_localize_frames_device(*args, _ptr(out_ptr), _ptr(stream)))
+        else:
+            check(self._L.asl_localize_cov_frames_device(*args, float(sigma_px), _ptr(out_ptr), _ptr(cov_ptr), _ptr(stream)))
+
+    def pose_cov(self, corners, T, K, dist, tag_size, sigma_px=0.0):
+        """asl_solve_pnp_cov_batch: the covariance of the camera<-tag poses T (N, 4, 4) that solve_pnp returned for corners
+        (N, 4, 2) -> (N,) POSE_COV_DTYPE; a T with non-finite entries (a failed PnP) gets status 1."""
+        c = np.ascontiguousarray(np.asarray(corners, dtype=np.float32).reshape(-1, 4, 2))
+        Tc = np.ascontiguousarray(np.asarray(T, dtype=np.float64).reshape(-1, 16))
+        if len(Tc) != len(c):
+            raise ValueError("one 4x4 pose per 4 corners")
+        keep, Kp, dpp, nd = _camera(K, dist)
+        cov = np.zeros(len(c), dtype=POSE_COV_DTYPE)
+        check(self._L.asl_solve_pnp_cov_batch(self._h, c.ctypes.data_as(C.POINTER(C.c_float)), Tc.ctypes.data_as(_DP), Kp, dpp, nd, float(tag_size),
+                                              float(sigma_px), cov.ctypes.data if cov.size else None, len(c)))
+        return cov
+
+    def pose_cov_device(self, obs_ptr, n_records, cov_ptr, K, dist, tag_size, sigma_px=0.0, stream=0):
+        """asl_pose_cov_device: obs_ptr (n_records asl_obs, e.g. a pack_observations_device block) and cov_ptr (n_records
+        asl_pose_cov) are device addresses; enqueued on `stream`, no wait."""
+        keep, Kp, dpp, nd = _camera(K, dist)
+        check(self._L.asl_pose_cov_device(self._h, _ptr(obs_ptr), int(n_records), Kp, dpp, nd, float(tag_size), float(sigma_px), _ptr(cov_ptr),
+                                          _ptr(stream)))
 
     @staticmethod
     def _calib_args(K_init, n_dist):

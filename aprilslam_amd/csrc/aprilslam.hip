@@ -30,6 +30,7 @@
 #include "k_render.inc"
 #include "k_gn.inc"
 #include "k_localize.inc"
+#include "k_posecov.inc"
 #include "k_calib.inc"
 #include "k_map.inc"
 
@@ -974,44 +975,153 @@ static int check_localize_args(const void *obs, int n_frames, int max_tags, cons
     return ASL_OK;
 }
 
+// d_cov NULL: the plain kernel, what asl_localize_frames_device / asl_localize_batch launch
 static void launch_localize(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids, const double *K,
-                            const double *dist, int n_dist, double tag_size, double max_tag_rms_px, void *d_out, hipStream_t st)
+                            const double *dist, int n_dist, double tag_size, double max_tag_rms_px, void *d_out, void *d_cov, double sigma_px,
+                            hipStream_t st)
 {
     CamDev cam = make_cam(d, K, dist, n_dist, tag_size);
-    hipLaunchKernelGGL(k_localize, dim3((unsigned int)n_frames), dim3(ASL_WAVE), loc_lds_bytes(max_tags), st, (const ObsRec *)d_obs, max_tags,
-                       (const MapTagRec *)d_map, n_ids, cam, max_tag_rms_px, (CamPoseRec *)d_out);
+    if (d_cov)
+        hipLaunchKernelGGL(k_localize<true>, dim3((unsigned int)n_frames), dim3(ASL_WAVE), loc_lds_bytes(max_tags), st, (const ObsRec *)d_obs, max_tags,
+                           (const MapTagRec *)d_map, n_ids, cam, max_tag_rms_px, (CamPoseRec *)d_out, (PoseCovRec *)d_cov, sigma_px);
+    else
+        hipLaunchKernelGGL(k_localize<false>, dim3((unsigned int)n_frames), dim3(ASL_WAVE), loc_lds_bytes(max_tags), st, (const ObsRec *)d_obs, max_tags,
+                           (const MapTagRec *)d_map, n_ids, cam, max_tag_rms_px, (CamPoseRec *)d_out, (PoseCovRec *)nullptr, 0.0);
+}
+
+static int check_sigma_px(double sigma_px)
+{
+    if (!(sigma_px >= 0) || !std::isfinite(sigma_px)) return fail(ASL_EINVAL, "sigma_px must be >= 0 and finite (got %g)", sigma_px);
+    return ASL_OK;
+}
+
+// the two device forms: d_cov NULL without the covariance
+static int localize_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids, const double *K,
+                                  const double *dist, int n_dist, double tag_size, double max_tag_rms_px, double sigma_px, void *d_out,
+                                  void *d_cov, void *stream)
+{
+    static_assert(sizeof(MapTagRec) == sizeof(asl_map_tag) && sizeof(asl_map_tag) == 104, "asl_map_tag layout");
+    static_assert(sizeof(CamPoseRec) == sizeof(asl_cam_pose) && sizeof(asl_cam_pose) == 160, "asl_cam_pose layout");
+    static_assert(sizeof(PoseCovRec) == sizeof(asl_pose_cov) && sizeof(asl_pose_cov) == 304, "asl_pose_cov layout");
+    if (!d) return fail(ASL_EINVAL, "NULL detector");
+    int rc = check_localize_args(d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, d_out);
+    if (rc) return rc;
+    if ((rc = check_sigma_px(sigma_px))) return rc;
+    if (n_frames == 0) return ASL_OK;
+    HIPCHK(hipSetDevice(d->device));
+    launch_localize(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, d_out, d_cov, sigma_px, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return ASL_OK;
 }
 
 extern "C" int asl_localize_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
                                           const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
                                           void *d_out, void *stream)
 {
-    static_assert(sizeof(MapTagRec) == sizeof(asl_map_tag) && sizeof(asl_map_tag) == 104, "asl_map_tag layout");
-    static_assert(sizeof(CamPoseRec) == sizeof(asl_cam_pose) && sizeof(asl_cam_pose) == 160, "asl_cam_pose layout");
+    return localize_frames_device(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, 0.0, d_out, nullptr, stream);
+}
+
+extern "C" int asl_localize_cov_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                              const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
+                                              double sigma_px, void *d_out, void *d_cov, void *stream)
+{
+    if (!d_cov) return fail(ASL_EINVAL, "NULL argument");
+    return localize_frames_device(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, sigma_px, d_out, d_cov, stream);
+}
+
+// the two host forms: cov NULL without the covariance
+static int localize_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids, const double *K,
+                          const double *dist, int n_dist, double tag_size, double max_tag_rms_px, double sigma_px, asl_cam_pose *out,
+                          asl_pose_cov *cov)
+{
     if (!d) return fail(ASL_EINVAL, "NULL detector");
-    int rc = check_localize_args(d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, d_out);
+    int rc = check_localize_args(obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, out);
     if (rc) return rc;
+    if ((rc = check_sigma_px(sigma_px))) return rc;
     if (n_frames == 0) return ASL_OK;
     HIPCHK(hipSetDevice(d->device));
-    launch_localize(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, d_out, (hipStream_t)stream);
+    asl_cam_pose *d_out = nullptr;
+    asl_pose_cov *d_cov = nullptr;
+    if (carve_ws(d->solve_out, [&](WsCarve &c) { d_out = c.take<asl_cam_pose>(n_frames); d_cov = c.take<asl_pose_cov>(cov ? n_frames : 0); }))
+        return fail(ASL_ENOMEM, "localisation workspace allocation failed");
+    if ((rc = upload_obs(d, "localisation", obs, n_frames, max_tags, map, n_ids))) return rc;
+    launch_localize(d, d->loc_obs.p, n_frames, max_tags, d->loc_map.p, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, d_out, cov ? d_cov : nullptr,
+                    sigma_px, nullptr);
     HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, d_out, sizeof(asl_cam_pose) * (size_t)n_frames, hipMemcpyDeviceToHost));
+    if (cov) HIPCHK(hipMemcpy(cov, d_cov, sizeof(asl_pose_cov) * (size_t)n_frames, hipMemcpyDeviceToHost));
     return ASL_OK;
 }
 
 extern "C" int asl_localize_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
                                   const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px, asl_cam_pose *out)
 {
+    return localize_batch(d, obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, 0.0, out, nullptr);
+}
+
+extern "C" int asl_localize_cov_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                      const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px, double sigma_px,
+                                      asl_cam_pose *out, asl_pose_cov *cov)
+{
+    if (!cov) return fail(ASL_EINVAL, "NULL argument");
+    return localize_batch(d, obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, sigma_px, out, cov);
+}
+
+// ---- per-tag pose covariance (k_posecov.inc)
+
+static int check_pose_cov_args(const void *in, int n, const double *K, const double *dist, int n_dist, double tag_size, double sigma_px, const void *cov)
+{
+    if (!in || !K || !cov) return fail(ASL_EINVAL, "NULL argument");
+    if (n < 0) return fail(ASL_EINVAL, "record count < 0");
+    if (int rc = check_n_dist(n_dist)) return rc;
+    if (n_dist && !dist) return fail(ASL_EINVAL, "dist is NULL with n_dist = %d", n_dist);
+    if (!(tag_size > 0) || !std::isfinite(tag_size)) return fail(ASL_EINVAL, "tag_size must be positive (got %g)", tag_size);
+    return check_sigma_px(sigma_px);
+}
+
+static void launch_pose_cov(asl_detector *d, const void *d_obs, int n, const double *K, const double *dist, int n_dist, double tag_size,
+                            double sigma_px, void *d_cov, hipStream_t st)
+{
+    CamDev cam = make_cam(d, K, dist, n_dist, tag_size);
+    hipLaunchKernelGGL(k_pnp_cov, dim3((unsigned int)((n + PNP_TAGS_PER_WAVE - 1) / PNP_TAGS_PER_WAVE)), dim3(ASL_WAVE), 0, st, (const ObsRec *)d_obs, n, cam,
+                       sigma_px, (PoseCovRec *)d_cov);
+}
+
+extern "C" int asl_pose_cov_device(asl_detector *d, const void *d_obs, int n_records, const double *K, const double *dist, int n_dist,
+                                   double tag_size, double sigma_px, void *d_cov, void *stream)
+{
     if (!d) return fail(ASL_EINVAL, "NULL detector");
-    int rc = check_localize_args(obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, out);
-    if (rc) return rc;
-    if (n_frames == 0) return ASL_OK;
+    if (int rc = check_pose_cov_args(d_obs, n_records, K, dist, n_dist, tag_size, sigma_px, d_cov)) return rc;
+    if (n_records == 0) return ASL_OK;
     HIPCHK(hipSetDevice(d->device));
-    const size_t out_bytes = sizeof(asl_cam_pose) * (size_t)n_frames;
-    if (d->solve_out.ensure(out_bytes)) return fail(ASL_ENOMEM, "localisation workspace allocation failed");
-    if ((rc = upload_obs(d, "localisation", obs, n_frames, max_tags, map, n_ids))) return rc;
-    launch_localize(d, d->loc_obs.p, n_frames, max_tags, d->loc_map.p, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, d->solve_out.p, nullptr);
+    launch_pose_cov(d, d_obs, n_records, K, dist, n_dist, tag_size, sigma_px, d_cov, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(out, d->solve_out.p, out_bytes, hipMemcpyDeviceToHost));
+    return ASL_OK;
+}
+
+extern "C" int asl_solve_pnp_cov_batch(asl_detector *d, const float *corners, const double *T, const double *K, const double *dist, int n_dist,
+                                       double tag_size, double sigma_px, asl_pose_cov *cov, int N)
+{
+    if (!d) return fail(ASL_EINVAL, "NULL detector");
+    if (!T) return fail(ASL_EINVAL, "NULL argument");
+    if (int rc = check_pose_cov_args(corners, N, K, dist, n_dist, tag_size, sigma_px, cov)) return rc;
+    if (N == 0) return ASL_OK;
+    HIPCHK(hipSetDevice(d->device));
+    std::vector<asl_obs> rec((size_t)N);
+    for (int i = 0; i < N; i++) {  // a pose with a non-finite entry (a failed PnP) is no pose: status 1
+        bool finite = true;
+        for (int k = 0; k < 12; k++) finite = finite && std::isfinite(T[16 * (size_t)i + k]);
+        rec[i].id = 0;
+        rec[i].flags = finite ? 3 : 1;
+        memcpy(rec[i].corners, corners + 8 * (size_t)i, sizeof rec[i].corners);
+        memcpy(rec[i].T, T + 16 * (size_t)i, sizeof rec[i].T);
+    }
+    const size_t cov_bytes = sizeof(asl_pose_cov) * (size_t)N;
+    if (d->solve_out.ensure(cov_bytes)) return fail(ASL_ENOMEM, "pose covariance workspace allocation failed");
+    if (int rc = upload_obs(d, "pose covariance", rec.data(), 1, N, nullptr, 0)) return rc;
+    launch_pose_cov(d, d->loc_obs.p, N, K, dist, n_dist, tag_size, sigma_px, d->solve_out.p, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(cov, d->solve_out.p, cov_bytes, hipMemcpyDeviceToHost));
     return ASL_OK;
 }
 

@@ -9,6 +9,8 @@
 //   refine  Levenberg-Marquardt on camera<-world, T <- [Rod(w) | v] T, 10 trial steps at most
 //   gate    optional: while the slot of largest own 4-corner RMS exceeds max_tag_rms_px it is dropped and the solve runs
 //           again (one slot at a time, at most 8)
+//   cov     k_localize<true> only (asl_localize_cov_*): one more linearisation at the pose written, then lane c solves column c
+//           of sigma^2 (J^T J)^-1 in the output convention (pose_cov_column_dev, k_pnp.inc; tests/pose_cov_ref.py)
 // tests/localize_ref.py is the NumPy statement of the same computation.  Latency-bound scalar float64 like k_pnp.inc:
 // the time goes into the dependent chains of the passes and reductions, not into bytes (136 B per slot in, 160 B per frame out).
 
@@ -288,8 +290,20 @@ __device__ __forceinline__ void loc_write_none(CamPoseRec *o, int status)
     o->rms_px = 0; o->rms_seed_px = 0; o->n_tags = 0; o->n_rejected = 0; o->status = status; o->seed_slot = -1;
 }
 
+// status 1 of a frame's covariance (the frame has no pose): zeros, the sigma as given, by the lanes that store a solved one
+__device__ __forceinline__ void loc_cov_write_none(PoseCovRec *oc, double sigma_px, int lane)
+{
+    if (lane < 36) oc->cov[lane] = 0.0;
+    if (lane == 36) oc->sigma_px = sigma_px;
+    if (lane == 37) { oc->dof = 0; oc->status = 1; }
+}
+
+// COV: also the first-order covariance of the pose written (asl_pose_cov, world<-camera) into cov[frame], scaled by
+// sigma_px or, for 0, by the solve's own cost / dof.  The plain instantiation never touches cov and sigma_px.
+template <bool COV>
 __global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs, int max_tags, const MapTagRec *__restrict__ map, int n_ids,
-                                                 CamDev cam, double gate, CamPoseRec *__restrict__ out)
+                                                 CamDev cam, double gate, CamPoseRec *__restrict__ out, PoseCovRec *__restrict__ cov,
+                                                 double sigma_px)
 {
     extern __shared__ double s_dyn[];
     const int n4 = 4 * max_tags, lane = threadIdx.x;
@@ -305,6 +319,7 @@ __global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs,
     const int npart = loc_gather(fo, max_tags, map, n_ids, cam.half, [](int fl) { return (fl & 2) != 0; }, L, lane, &nseed);
     if (npart == 0 || nseed == 0) {
         if (lane == 0) loc_write_none(o, npart == 0 ? 1 : 2);
+        if constexpr (COV) loc_cov_write_none(cov + blockIdx.x, sigma_px, lane);
         return;
     }
 
@@ -341,6 +356,7 @@ __global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs,
     }
     if (code < 0) {  // every candidate scored NaN
         if (lane == 0) loc_write_none(o, 2);
+        if constexpr (COV) loc_cov_write_none(cov + blockIdx.x, sigma_px, lane);
         return;
     }
 
@@ -390,5 +406,20 @@ __global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs,
         o->n_rejected = nrej;
         o->status = 0;
         o->seed_slot = code;
+    }
+
+    // 6: the covariance at the pose just written: one more linearisation over the corners still in LDS, then lane c
+    // solves column c (every lane holds the same J^T J after the butterfly sums; lanes past 5 repeat column 5 and store nothing)
+    if constexpr (COV) {
+        PoseCovRec *oc = cov + blockIdx.x;
+        double ne[27], col[6], sig;
+        const double c1 = loc_pass<true>(cam, R, t, L, n4, lane, ne);
+        const int dof = 8 * nused - 6;
+        const double s2 = pose_cov_sigma2(sigma_px, c1, dof, &sig);
+        const int c = lane < 6 ? lane : 5;
+        const bool pd = pose_cov_column_dev<true>(ne, R, t, c, col) && isfinite(s2);
+        if (lane < 6) pose_cov_store_column(oc, c, col, s2, pd);
+        if (lane == 36) oc->sigma_px = sig;
+        if (lane == 37) { oc->dof = dof; oc->status = pd ? 0 : 2; }
     }
 }

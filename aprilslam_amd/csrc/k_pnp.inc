@@ -195,6 +195,87 @@ __device__ __forceinline__ bool chol6_solve_tri_dev(double *A, double *b)
     return true;
 }
 
+// ---- first-order pose covariance (asl_pose_cov), shared by k_localize<true> (k_localize.inc) and k_pnp_cov (k_posecov.inc)
+
+struct PoseCovRec {  // == asl_pose_cov, 304 bytes
+    double cov[36];
+    double sigma_px;
+    int32_t dof, status;
+};
+
+// A pivot of the undamped Cholesky below this fraction of its diagonal entry means the normal matrix has no positive
+// definite meaning left in float64 (Jacobi-scaled condition number past ~1e13): status 2 (tests/pose_cov_ref.py: PIVOT_TOL)
+#define POSE_COV_PIVOT_TOL 1e-13
+
+// Column c (0..5) of (J^T J)^-1 in the output convention of asl_pose_cov.  H: the packed lower triangle of J^T J in the
+// solvers' own coordinates (w, v) of the left update R <- Rod(w) R, t <- Rod(w) t + v on camera<-X = (R, t).  The
+// output error (r, d) = A (w, v) to first order, so column c of A H^-1 A^T is A x with H x = A^T e_c: one Cholesky
+// (the same in every lane that holds the same H) and one pair of triangular solves per column, and no lane ever holds
+// the whole inverse.
+//   WFC (world<-camera = inverse of (R, t)):  A = diag(-R^T, -R^T)
+//   else (camera<-tag = (R, t) itself):       A = [I 0; -[t]x I]
+// false: H is not positive definite (col is not written).
+template <bool WFC>
+__device__ __forceinline__ bool pose_cov_column_dev(const double *H, const double *R, const double *t, int c, double *col)
+{
+    // c picks by a one-hot product, not by an index or a chain of selects: either makes the compiler keep R in scratch
+    const int k = c < 3 ? c : c - 3;
+    const double e0 = k == 0 ? 1.0 : 0.0, e1 = k == 1 ? 1.0 : 0.0, e2 = k == 2 ? 1.0 : 0.0, lo = c < 3 ? 1.0 : 0.0, hi = 1.0 - lo;
+    double A[21], x[6];
+#pragma unroll
+    for (int i = 0; i < 21; i++) A[i] = H[i];
+    if constexpr (WFC) {  // A^T e_c: column k of -R in the block of c
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            const double m = -(R[3 * i] * e0 + R[3 * i + 1] * e1 + R[3 * i + 2] * e2);
+            x[i] = lo * m;
+            x[3 + i] = hi * m;
+        }
+    } else {  // A^T = [I [t]x; 0 I]: e_k, or column k of [t]x over e_k
+        x[0] = lo * e0 + hi * (t[1] * e2 - t[2] * e1);
+        x[1] = lo * e1 + hi * (t[2] * e0 - t[0] * e2);
+        x[2] = lo * e2 + hi * (t[0] * e1 - t[1] * e0);
+        x[3] = hi * e0; x[4] = hi * e1; x[5] = hi * e2;
+    }
+    if (!chol6_solve_tri_dev(A, x)) return false;
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+        if (!(A[TRI(i, i)] * A[TRI(i, i)] > POSE_COV_PIVOT_TOL * H[TRI(i, i)])) return false;
+    if constexpr (WFC) {
+#pragma unroll
+        for (int b = 0; b < 2; b++)
+#pragma unroll
+            for (int i = 0; i < 3; i++) col[3 * b + i] = -(R[i] * x[3 * b] + R[3 + i] * x[3 * b + 1] + R[6 + i] * x[3 * b + 2]);
+    } else {
+        col[0] = x[0]; col[1] = x[1]; col[2] = x[2];
+        col[3] = x[3] - (t[1] * x[2] - t[2] * x[1]);
+        col[4] = x[4] - (t[2] * x[0] - t[0] * x[2]);
+        col[5] = x[5] - (t[0] * x[1] - t[1] * x[0]);
+    }
+    return true;
+}
+
+// sigma^2 and the record's sigma_px / dof: the given sigma, or cost / dof of the solve for sigma_px == 0
+__device__ __forceinline__ double pose_cov_sigma2(double sigma_px, double cost, int dof, double *sigma_out)
+{
+    const double s2 = sigma_px > 0 ? sigma_px * sigma_px : cost / (double)dof;
+    *sigma_out = sigma_px > 0 ? sigma_px : sqrt(s2);
+    return s2;
+}
+
+// Column c of the scaled covariance into the record, by the lane that solved it: its entries on and below the diagonal
+// go to both triangles, so the stored matrix is symmetric to the bit.  ok false: zeros.
+__device__ __forceinline__ void pose_cov_store_column(PoseCovRec *o, int c, const double *col, double s2, bool ok)
+{
+#pragma unroll
+    for (int r = 0; r < 6; r++) {
+        if (r < c) continue;
+        const double v = ok ? s2 * col[r] : 0.0;
+        o->cov[6 * r + c] = v;
+        o->cov[6 * c + r] = v;
+    }
+}
+
 #define PNP_TAGS_PER_WAVE 16
 #define PNP_NE 27  /* the normal equations of a tag: 21 entries of JtJ (packed lower triangle) + 6 of Jt r */
 

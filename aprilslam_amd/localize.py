@@ -7,14 +7,26 @@ scene (TagMap.from_scene).
 
     TagMap          ids -> world<-tag 4x4, as the asl_map_tag records the library reads (indexed by id)
     CAM_POSE_DTYPE  one asl_cam_pose per frame: world<-camera T, rms_px, rms_seed_px, n_tags, n_rejected, status, seed_slot
+    POSE_COV_DTYPE  one asl_pose_cov per pose: cov 6x6 (rx ry rz | px py pz), sigma_px, dof, status; pose_std reads it
 """
 import numpy as np
 
-from ._lib import CAM_POSE_DTYPE, MAP_TAG_DTYPE
+from ._lib import CAM_POSE_DTYPE, MAP_TAG_DTYPE, POSE_COV_DTYPE
 
 STATUS_OK, STATUS_NO_MAPPED_TAG, STATUS_NO_PNP = 0, 1, 2
 
-__all__ = ["TagMap", "CAM_POSE_DTYPE", "MAP_TAG_DTYPE", "STATUS_OK", "STATUS_NO_MAPPED_TAG", "STATUS_NO_PNP"]
+COV_OK, COV_NO_POSE, COV_NOT_POSITIVE_DEFINITE = 0, 1, 2
+
+__all__ = ["TagMap", "CAM_POSE_DTYPE", "MAP_TAG_DTYPE", "POSE_COV_DTYPE", "STATUS_OK", "STATUS_NO_MAPPED_TAG", "STATUS_NO_PNP",
+           "COV_OK", "COV_NO_POSE", "COV_NOT_POSITIVE_DEFINITE", "pose_std"]
+
+
+def pose_std(cov):
+    """(rotation std in rad (3), translation std (3)) of a 6x6 pose covariance in the order (rx ry rz | px py pz), or of a
+    stack of them (..., 6, 6): the roots of the diagonal.  Rotation about the axes of the pose's target frame, translation
+    of its translation column (include/aprilslam.h: asl_pose_cov)."""
+    d = np.sqrt(np.diagonal(np.asarray(cov, dtype=np.float64), axis1=-2, axis2=-1))
+    return d[..., :3], d[..., 3:]
 
 
 class TagMap:

@@ -241,10 +241,11 @@ class SLAM:
         from .localize import TagMap
         return TagMap({tag_id: project_se3(node.world) for tag_id, node in self.graph.get_nodes().items()})
 
-    def localize(self, detections, max_tag_rms_px=0.0):
+    def localize(self, detections, max_tag_rms_px=0.0, with_cov=False, sigma_px=0.0):
         """Camera pose of one frame from all its mapped tags at once (TagDetector.localize against tag_map()).  Leaves
-        estimated_pose, the graph and the window alone; my_pose() stays the reference's estimator."""
-        return self.detector.localize(detections, self.tag_map(), max_tag_rms_px=max_tag_rms_px)
+        estimated_pose, the graph and the window alone; my_pose() stays the reference's estimator.  with_cov / sigma_px:
+        the pose's covariance as TagDetector.localize reports it (the graph's tags taken as exact)."""
+        return self.detector.localize(detections, self.tag_map(), max_tag_rms_px=max_tag_rms_px, with_cov=with_cov, sigma_px=sigma_px)
 
     def average_distance_to_nodes(self):
         """Mean distance camera <-> tag over ALL nodes of the graph (0 for an empty graph), slam.py:65-80."""

@@ -123,12 +123,26 @@ class TagDetector:
         rvec, tvec, T, ok = self.detector._det.solve_pnp(c, self.camera_matrix, self._dist(), self.tag_size)
         return ok, rvec, tvec, T
 
+    def get_poses_cov(self, detections, sigma_px=0.0):
+        """get_poses with each pose's covariance (asl_solve_pnp_cov_batch): (ok[N], rvec[N,3], tvec[N,3], T[N,4,4],
+        cov[N] POSE_COV_DTYPE), camera<-tag, (rx ry rz | tvec); sigma_px = 0 estimates the corner sigma from the tag's own
+        8 residuals (2 degrees of freedom: a given sigma_px is the better choice).  A pose that is not ok has status 1."""
+        ok, rvec, tvec, T = self.get_poses(detections)
+        if not len(ok):
+            return ok, rvec, tvec, T, np.zeros(0, dtype=_lib.POSE_COV_DTYPE)
+        c = np.stack([np.asarray(d['lb-rb-rt-lt'], dtype=np.float32) for d in detections])
+        Tc = np.where(np.asarray(ok, dtype=bool)[:, None, None], T, np.nan)
+        cov = self.detector._det.pose_cov(c, Tc, self.camera_matrix, self._dist(), self.tag_size, sigma_px)
+        return ok, rvec, tvec, T, cov
+
     # -- camera pose from every visible tag against a known map (asl_localize_batch) ---------------------------------
-    def localize(self, detections, tag_map, max_tag_rms_px=0.0):
+    def localize(self, detections, tag_map, max_tag_rms_px=0.0, with_cov=False, sigma_px=0.0):
         """One frame's detection dicts (as detect() returns them) -> the camera pose from all mapped tags at once:
         {"ok", "T" world<-camera 4x4, "rms_px", "n_tags", "n_rejected", "status"}.  The poses detect() solved in its own
         submission are reused; detections without one get their PnP first (one launch).  max_tag_rms_px > 0 drops tags
-        whose own corner RMS exceeds it (moved or mis-identified tags) and solves again."""
+        whose own corner RMS exceeds it (moved or mis-identified tags) and solves again.  with_cov adds "cov" (6x6,
+        rotation about the world axes | camera position, zeros unless "cov_status" is 0) and "sigma_px", the corner sigma
+        that scaled it: the given one, or for 0 the solve's own estimate (localize.pose_std reads the std off it)."""
         dets = list(detections)
         if len(dets) > 256:
             raise ValueError("at most 256 detections per frame")
@@ -152,18 +166,26 @@ class TagDetector:
             obs["flags"][0, k] = 1 | (2 if oks[k] else 0)
             obs["corners"][0, k] = np.asarray(d['lb-rb-rt-lt'], dtype=np.float32).reshape(8)
             obs["T"][0, k] = np.asarray(Ts[k], dtype=np.float64).reshape(16)[:12]
-        r = self.detector._det.localize(obs, tag_map, self.camera_matrix, self._dist(), self.tag_size, max_tag_rms_px)[0]
-        return {"ok": int(r["status"]) == 0, "T": np.array(r["T"]), "rms_px": float(r["rms_px"]), "n_tags": int(r["n_tags"]),
-                "n_rejected": int(r["n_rejected"]), "status": int(r["status"])}
+        res = self.detector._det.localize(obs, tag_map, self.camera_matrix, self._dist(), self.tag_size, max_tag_rms_px,
+                                          sigma_px=float(sigma_px) if with_cov else None)
+        r = (res[0] if with_cov else res)[0]
+        out = {"ok": int(r["status"]) == 0, "T": np.array(r["T"]), "rms_px": float(r["rms_px"]), "n_tags": int(r["n_tags"]),
+               "n_rejected": int(r["n_rejected"]), "status": int(r["status"])}
+        if with_cov:
+            c = res[1][0]
+            out.update(cov=np.array(c["cov"]), sigma_px=float(c["sigma_px"]), cov_status=int(c["status"]))
+        return out
 
-    def localize_batch(self, dets, poses, n_per_frame, tag_map, max_tag_rms_px=0.0, max_tags=None):
+    def localize_batch(self, dets, poses, n_per_frame, tag_map, max_tag_rms_px=0.0, max_tags=None, with_cov=False, sigma_px=0.0):
         """The structured arrays detect_host / collect return (detections in (frame, id) order, their poses, the count per
-        frame) -> one CAM_POSE_DTYPE record per frame.  max_tags: slots per frame (default: the most detections of a frame)."""
+        frame) -> one CAM_POSE_DTYPE record per frame.  max_tags: slots per frame (default: the most detections of a frame).
+        with_cov: (poses, one POSE_COV_DTYPE record per frame) instead."""
         from .dist import pack_observations
         npf = np.asarray(n_per_frame, dtype=np.int64)
         mt = int(max_tags) if max_tags is not None else max(1, int(npf.max()) if len(npf) else 1)
         obs = pack_observations(dets, poses, npf, mt)
-        return self.detector._det.localize(obs, tag_map, self.camera_matrix, self._dist(), self.tag_size, max_tag_rms_px)
+        return self.detector._det.localize(obs, tag_map, self.camera_matrix, self._dist(), self.tag_size, max_tag_rms_px,
+                                           sigma_px=float(sigma_px) if with_cov else None)
 
     # -- camera calibration from frames of a known target (asl_calibrate_batch) ------------------------------------------
     def calibrate(self, frames, tag_map, n_dist=5, K_init=None, flags=0, max_iters=30):

@@ -217,6 +217,51 @@ int asl_localize_batch(asl_detector *det, const asl_obs *obs, int n_frames, int 
                        const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
                        asl_cam_pose *out);
 
+/* ---- how good a pose is: its first-order (Gauss-Newton) covariance C = sigma^2 (J^T J)^-1 at the solution the solver
+   returned, J the Jacobian of the pixel residuals that solver minimised.
+   Convention: for a pose T = [R | p] the error is (r, d) with R_true = Rod(r) R and p_true = p + d.  So the lower 3x3
+   block is the covariance of the translation column itself (the camera position in world axes for world<-camera, tvec
+   for camera<-tag) and the upper block that of the rotation error about the axes of the pose's target frame (world /
+   camera).  This is not the (omega, v) of a left update T_true = [Rod(omega) | v] T that d_tag_std reports: there
+   p_true = Rod(omega) p + v, so the v of a pose far from the origin carries the lever arm omega x p.  To first order
+   r = omega, d = v - [p]x omega, i.e. (r, d) = A (omega, v) with A = [I 0; -[p]x I] and C_(r,d) = A C_(omega,v) A^T.
+   (The solvers update camera<-X by (w, v) on the left; camera<-tag is that pose itself, A as above with p = tvec;
+   world<-camera is its inverse, r = -R_cx^T w, d = -R_cx^T v.)  tests/pose_cov_ref.py states the computation.
+   sigma_px > 0: the corner noise (pixels, per coordinate) the caller assumes.  sigma_px == 0: estimated from the solve,
+   sigma^2 = cost / dof with dof = 8 n_tags - 6.  For one tag that is 2 degrees of freedom: the estimate is then itself
+   uncertain by a factor of about two either way, and a given sigma_px is the better choice.  A covariance is as good as
+   the model: independent Gaussian corner noise, a linearisation that holds over the error, and (localisation) a map taken
+   as exact -- the uncertainty of the map tags is not propagated. */
+typedef struct {
+    double cov[36];     /* row-major 6x6, symmetric to the bit, order (rx ry rz | px py pz) */
+    double sigma_px;    /* the pixel sigma that scaled it (given, or estimated) */
+    int32_t dof;        /* residuals - 6 of the solve it belongs to (0 with status 1) */
+    int32_t status;     /* 0 ok; 1 the pose has none (its own status != 0 / PnP not ok); 2 J^T J not positive definite */
+} asl_pose_cov;         /* 304 bytes; status != 0: cov all zero */
+
+/* asl_localize_frames_device with the covariance of every frame's world<-camera pose: d_out receives exactly what
+   asl_localize_frames_device writes, byte for byte; d_cov one asl_pose_cov per frame, over the slots in the final solve
+   (after the gate), computed in the same kernel from the corners still on chip.  sigma_px < 0 or non-finite is
+   ASL_EINVAL.  Deterministic: the same input gives the same bytes. */
+int asl_localize_cov_frames_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                   const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
+                                   double sigma_px, void *d_out, void *d_cov, void *stream);
+/* The same computation on host records, synchronous. */
+int asl_localize_cov_batch(asl_detector *det, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                           const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
+                           double sigma_px, asl_cam_pose *out, asl_pose_cov *cov);
+
+/* One asl_pose_cov per asl_obs record (n_records of them, as asl_pack_observations_device writes them; device pointers,
+   asynchronous on `stream`): the covariance of the camera<-tag pose in the record from its 4 corners (8 residuals, dof 2),
+   re-linearised at that pose with the camera model of asl_solve_pnp_batch.  Records without flags & 2 get status 1.
+   The fused detect + PnP has no covariance output: the device path is submit -> pack -> this call. */
+int asl_pose_cov_device(asl_detector *det, const void *d_obs, int n_records, const double *K, const double *dist, int n_dist,
+                        double tag_size, double sigma_px, void *d_cov, void *stream);
+/* The same on what asl_solve_pnp_batch took and returned (host pointers, synchronous): corners N x 4 x 2 float32,
+   T N x 16.  A T with a non-finite entry in its first three rows (a failed PnP) gets status 1. */
+int asl_solve_pnp_cov_batch(asl_detector *det, const float *corners, const double *T, const double *K, const double *dist,
+                            int n_dist, double tag_size, double sigma_px, asl_pose_cov *cov, int N);
+
 /* ---- camera calibration from tag observations: intrinsics and lens distortion of the camera model above (fx fy cx cy,
    k1 k2 p1 p2 [k3]) from frames that see a rigid target of known tag poses (a planar board or any surveyed arrangement). */
 #define ASL_CALIB_FIX_PRINCIPAL_POINT 1  /* cx, cy stay at K_init's (or the image centre) */

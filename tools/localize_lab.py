@@ -6,7 +6,12 @@ Prints one JSON line: the isolated kernel time per 1024 frames (HIP events aroun
 --reps after warm-up) and the camera pose error against the renderer's ground truth, single-view (each tag's PnP
 composed with the true map) and joint.
 
-    python tools/localize_lab.py [--frames 1024] [--reps 30] [--max-tags 32] [--gate 0]
+--cov adds the covariance leg: asl_localize_cov_frames_device timed against the plain call, the two launches alternating
+inside every repetition; asl_pose_cov_device over the same records (the per-tag covariance of every slot); and the squared
+Mahalanobis distance of the joint pose's error against the ground truth under the reported covariance (6 on average for
+Gaussian corner noise of the estimated sigma; detected corners are not that, so it is a finding, not a check).
+
+    python tools/localize_lab.py [--frames 1024] [--reps 30] [--max-tags 32] [--gate 0] [--cov]
 """
 import argparse
 import json
@@ -31,13 +36,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--max-tags", type=int, default=32)
     ap.add_argument("--gate", type=float, default=0.0)
+    ap.add_argument("--cov", action="store_true", help="also time the calls with covariance, interleaved with the plain one")
     a = ap.parse_args()
 
     import torch
 
     import bench
     from aprilslam_amd import _lib, synth
-    from aprilslam_amd.localize import CAM_POSE_DTYPE, TagMap
+    from aprilslam_amd.localize import CAM_POSE_DTYPE, POSE_COV_DTYPE, TagMap
 
     dev = torch.device("cuda:0")
     W, H, n, mt = bench.W, bench.H, a.frames, a.max_tags
@@ -55,21 +61,38 @@ def main():
     det.pack_observations_device(d_obs.data_ptr(), mt, stream=stream.cuda_stream)
     det.collect()
 
+    d_cov = torch.empty((n, POSE_COV_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    d_tag_cov = torch.empty((n * mt, POSE_COV_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+
     def launch():
         det.localize_device(d_obs.data_ptr(), n, mt, d_map.data_ptr(), len(rec), d_out.data_ptr(), K, None, bench.TAG_INNER,
                             max_tag_rms_px=a.gate, stream=stream.cuda_stream)
 
+    def launch_cov():
+        det.localize_device(d_obs.data_ptr(), n, mt, d_map.data_ptr(), len(rec), d_out.data_ptr(), K, None, bench.TAG_INNER,
+                            max_tag_rms_px=a.gate, stream=stream.cuda_stream, cov_ptr=d_cov.data_ptr(), sigma_px=0.0)
+
+    def launch_tag_cov():
+        det.pose_cov_device(d_obs.data_ptr(), n * mt, d_tag_cov.data_ptr(), K, None, bench.TAG_INNER, 0.0, stream=stream.cuda_stream)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    legs = [launch] + ([launch_cov, launch_tag_cov] if a.cov else [])
     with torch.cuda.stream(stream):
         for _ in range(a.warmup):
-            launch()
-        ms = []
+            for fn in legs:
+                fn()
+        times = [[] for _ in legs]
         for _ in range(a.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            launch()
-            e1.record(stream)
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
+            for k, fn in enumerate(legs):    # alternating: every repetition runs each leg once, back to back
+                times[k].append(timed(fn))
+        ms = times[0]
     stream.synchronize()
     out = d_out.cpu().numpy().view(CAM_POSE_DTYPE).reshape(n)
     obs = d_obs.cpu().numpy().view(_lib.OBS_DTYPE).reshape(n, mt)
@@ -99,6 +122,32 @@ def main():
         "single_view": {"rotation_mrad": rms(sr) * 1e3, "translation_mm": rms(st) * bench.MM_PER_UNIT, "poses": len(sr)},
         "note": "camera world<-camera vs the renderer's ground truth; single view = each tag's PnP composed with the true map",
     }
+    if a.cov:
+        cov = d_cov.cpu().numpy().view(POSE_COV_DTYPE).reshape(n)
+        tag_cov = d_tag_cov.cpu().numpy().view(POSE_COV_DTYPE).reshape(n, mt)
+        m2 = []
+        for f in np.flatnonzero((out["status"] == 0) & (cov["status"] == 0)):
+            Q = truths[f][:3, :3] @ out["T"][f][:3, :3].T       # Rod(r) = R_true R^T, d = p_true - p
+            w = np.array([Q[2, 1] - Q[1, 2], Q[0, 2] - Q[2, 0], Q[1, 0] - Q[0, 1]]) / 2
+            s = np.sqrt(w @ w)
+            r = w * (np.arctan2(s, (np.trace(Q) - 1) / 2) / s) if s > 1e-12 else w
+            e = np.concatenate([r, truths[f][:3, 3] - out["T"][f][:3, 3]])
+            m2.append(float(e @ np.linalg.solve(cov["cov"][f], e)))
+        std = np.sqrt(np.diagonal(cov["cov"][cov["status"] == 0], axis1=1, axis2=2))
+        tstd = np.sqrt(np.diagonal(tag_cov["cov"][tag_cov["status"] == 0], axis1=1, axis2=2))
+        line["cov"] = {
+            "kernel_ms_median": float(np.median(times[1])), "kernel_ms_min": float(np.min(times[1])),
+            "plain_ms_median_interleaved": float(np.median(times[0])),
+            "pose_cov_records": n * mt, "pose_cov_records_posed": int((tag_cov["status"] == 0).sum()),
+            "pose_cov_ms_median": float(np.median(times[2])), "pose_cov_ms_min": float(np.min(times[2])),
+            "frames_with_cov": int((cov["status"] == 0).sum()), "sigma_px_median": float(np.median(cov["sigma_px"][cov["status"] == 0])),
+            "mahalanobis2_mean": float(np.mean(m2)), "mahalanobis2_median": float(np.median(m2)),
+            "joint_std": {"rotation_mrad_median": float(np.median(std[:, :3])) * 1e3,
+                          "translation_mm_median": float(np.median(std[:, 3:])) * bench.MM_PER_UNIT},
+            "single_tag_std": {"rotation_mrad_median": float(np.median(tstd[:, :3])) * 1e3,
+                               "translation_mm_median": float(np.median(tstd[:, 3:])) * bench.MM_PER_UNIT},
+            "note": "sigma estimated per solve (sigma_px = 0); chi-square(6) has mean 6, median 5.35",
+        }
     print(json.dumps(line))
     det.close()
 
