@@ -1,0 +1,1 @@
+from .rig import Rig, RigCamera  # noqa: F401

@@ -37,12 +37,15 @@ assert CAM_POSE_DTYPE.itemsize == 160
 assert CALIB_RESULT_DTYPE.itemsize == 216
 assert MAP_RESULT_DTYPE.itemsize == 64
 assert POSE_COV_DTYPE.itemsize == 304
+RIG_CAMERA_DTYPE = np.dtype([("K", "<f8", (3, 3)), ("dist", "<f8", (5,)), ("E", "<f8", (3, 4)), ("n_dist", "<i4"), ("reserved", "<i4")])  # asl_rig_camera
+assert RIG_CAMERA_DTYPE.itemsize == 216
 
 EXPORTS = [
     "asl_detector_create", "asl_detector_destroy", "asl_detector_set_id_limit", "asl_detector_set_pnp_both_minima", "asl_last_error", "asl_version", "asl_detect_gray_u8",
     "asl_detect_bgr_u8", "asl_detect_batch_u8", "asl_detect_batch_pose_u8", "asl_detect_batch_device", "asl_submit_batch_device", "asl_collect_batch", "asl_collect_batch_view", "asl_solve_pnp_batch", "asl_gn_solve", "asl_pack_observations_device", "asl_graph_frames_device", "asl_graph_picks_device", "asl_render_frames_device",
     "asl_localize_frames_device", "asl_localize_batch", "asl_localize_cov_frames_device", "asl_localize_cov_batch",
     "asl_pose_cov_device", "asl_solve_pnp_cov_batch", "asl_calibrate_frames_device", "asl_calibrate_batch",
+    "asl_localize_rig_frames_device", "asl_localize_rig_cov_frames_device", "asl_localize_rig_batch", "asl_localize_rig_cov_batch",
     "asl_map_frames_device", "asl_map_batch",
     "asl_debug_fetch", "asl_debug_refit", "asl_debug_division_check", "asl_stage_times", "asl_set_profiling", "asl_debug_phase_cycles",
 ]
@@ -96,6 +99,10 @@ def load():
     L.asl_localize_cov_frames_device.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp]
     L.asl_localize_cov_batch.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, C.c_double, C.c_double, vp, vp]
     L.asl_pose_cov_device.argtypes = [vp, vp, i32, dp, dp, i32, C.c_double, C.c_double, vp, vp]
+    L.asl_localize_rig_frames_device.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, C.c_double, C.c_double, vp, vp]
+    L.asl_localize_rig_cov_frames_device.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, C.c_double, C.c_double, C.c_double, vp, vp, vp]
+    L.asl_localize_rig_batch.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, C.c_double, C.c_double, vp]
+    L.asl_localize_rig_cov_batch.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, C.c_double, C.c_double, C.c_double, vp, vp]
     L.asl_solve_pnp_cov_batch.argtypes = [vp, C.POINTER(C.c_float), dp, dp, dp, i32, C.c_double, C.c_double, vp, i32]
     L.asl_calibrate_frames_device.argtypes = [vp, vp, i32, i32, vp, i32, C.c_double, i32, i32, dp, i32, i32, i32, vp, vp, vp]
     L.asl_calibrate_batch.argtypes = [vp, vp, i32, i32, vp, i32, C.c_double, i32, i32, dp, i32, i32, i32, vp, vp]
@@ -156,6 +163,13 @@ def _map_records(tag_map):
     if hasattr(tag_map, "as_records"):
         tag_map = tag_map.as_records()
     return np.ascontiguousarray(tag_map, dtype=MAP_TAG_DTYPE).ravel()
+
+
+def _rig_records(rig):
+    """(n_cams,) RIG_CAMERA_DTYPE records of a record array or a rig.Rig"""
+    if hasattr(rig, "as_records"):
+        rig = rig.as_records()
+    return np.ascontiguousarray(rig, dtype=RIG_CAMERA_DTYPE).ravel()
 
 
 class Detector:
@@ -321,6 +335,39 @@ class Detector:
             check(self._L.asl_localize_frames_device(*args, _ptr(out_ptr), _ptr(stream)))
         else:
             check(self._L.asl_localize_cov_frames_device(*args, float(sigma_px), _ptr(out_ptr), _ptr(cov_ptr), _ptr(stream)))
+
+    def localize_rig(self, obs, tag_map, rig, tag_size, max_tag_rms_px=0.0, sigma_px=None):
+        """asl_localize_rig_batch: host records obs (n_cams, n_frames, max_tags) OBS_DTYPE, camera-major, against tag_map and
+        the camera table rig ((n_cams,) RIG_CAMERA_DTYPE, or a rig.Rig) -> (n_frames,) CAM_POSE_DTYPE, world<-rig per frame.
+        sigma_px not None: asl_localize_rig_cov_batch -> (poses, (n_frames,) POSE_COV_DTYPE), as localize."""
+        o = np.ascontiguousarray(obs, dtype=OBS_DTYPE)
+        if o.ndim != 3:
+            raise ValueError("obs must be (n_cams, n_frames, max_tags) asl_obs records")
+        m = _map_records(tag_map)
+        r = _rig_records(rig)
+        if len(r) != o.shape[0]:
+            raise ValueError("the rig has %d cameras, obs has %d" % (len(r), o.shape[0]))
+        out = np.zeros(o.shape[1], dtype=CAM_POSE_DTYPE)
+        args = (self._h, o.ctypes.data if o.size else None, o.shape[0], o.shape[1], o.shape[2], m.ctypes.data if m.size else None, len(m),
+                r.ctypes.data if r.size else None, float(tag_size), float(max_tag_rms_px))
+        if sigma_px is None:
+            check(self._L.asl_localize_rig_batch(*args, out.ctypes.data if out.size else None))
+            return out
+        cov = np.zeros(o.shape[1], dtype=POSE_COV_DTYPE)
+        check(self._L.asl_localize_rig_cov_batch(*args, float(sigma_px), out.ctypes.data if out.size else None, cov.ctypes.data if cov.size else None))
+        return out, cov
+
+    def localize_rig_device(self, obs_ptr, n_cams, n_frames, max_tags, map_ptr, n_ids, rig_ptr, out_ptr, tag_size, max_tag_rms_px=0.0,
+                            stream=0, cov_ptr=None, sigma_px=0.0):
+        """asl_localize_rig_frames_device: obs_ptr (n_cams x n_frames x max_tags asl_obs, camera-major), map_ptr (n_ids
+        asl_map_tag), rig_ptr (n_cams asl_rig_camera, complete when the call is made) and out_ptr (n_frames asl_cam_pose) are
+        device addresses; enqueued on `stream`.  cov_ptr not None (n_frames asl_pose_cov): asl_localize_rig_cov_frames_device."""
+        args = (self._h, _ptr(obs_ptr), int(n_cams), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids), _ptr(rig_ptr), float(tag_size),
+                float(max_tag_rms_px))
+        if cov_ptr is None:
+            check(self._L.asl_localize_rig_frames_device(*args, _ptr(out_ptr), _ptr(stream)))
+        else:
+            check(self._L.asl_localize_rig_cov_frames_device(*args, float(sigma_px), _ptr(out_ptr), _ptr(cov_ptr), _ptr(stream)))
 
     def pose_cov(self, corners, T, K, dist, tag_size, sigma_px=0.0):
         """asl_solve_pnp_cov_batch: the covariance of the camera<-tag poses T (N, 4, 4) that solve_pnp returned for corners

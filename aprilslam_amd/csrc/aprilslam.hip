@@ -31,6 +31,7 @@
 #include "k_gn.inc"
 #include "k_localize.inc"
 #include "k_posecov.inc"
+#include "k_rig.inc"
 #include "k_calib.inc"
 #include "k_map.inc"
 
@@ -121,6 +122,7 @@ struct asl_detector {
     DevBuf<uint8_t> gn_ws;  // asl_gn_solve: its inputs and the LM's buffers (gn_host.inc)
     DevBuf<uint8_t> loc_obs, loc_map;  // the *_batch solver entries: the host records' device copies (grow on demand)
     DevBuf<uint8_t> solve_out;         // the *_batch solver entries: their results, until copied back
+    DevBuf<uint8_t> rig_cams;          // asl_localize_rig_batch: the device copy of the camera table
     DevBuf<uint8_t> cal_ws;  // calibration: per-frame workspace and state (k_calib.inc)
     DevBuf<uint8_t> map_ws, map_lm;  // map reconstruction (k_map.inc): sized by the input / by the problem
     hipStream_t copy_stream = nullptr, host_stream = nullptr;  // host frames: transfers and the chunks' kernels (detect_host_frames)
@@ -1065,6 +1067,132 @@ extern "C" int asl_localize_cov_batch(asl_detector *d, const asl_obs *obs, int n
 {
     if (!cov) return fail(ASL_EINVAL, "NULL argument");
     return localize_batch(d, obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, sigma_px, out, cov);
+}
+
+// ---- rig localisation (k_rig.inc)
+
+// one camera table, wherever it came from: the model and the mounting of every camera
+static int check_rig_table(const asl_rig_camera *rig, int n_cams)
+{
+    for (int c = 0; c < n_cams; c++) {
+        const asl_rig_camera &r = rig[c];
+        if (check_n_dist(r.n_dist)) return fail(ASL_EINVAL, "camera %d: n_dist must be 0, 4 or 5 (got %d)", c, r.n_dist);
+        for (int k = 0; k < 9; k++)
+            if (!std::isfinite(r.K[k])) return fail(ASL_EINVAL, "camera %d: K is not finite", c);
+        for (int k = 0; k < r.n_dist; k++)
+            if (!std::isfinite(r.dist[k])) return fail(ASL_EINVAL, "camera %d: dist is not finite", c);
+        for (int k = 0; k < 12; k++)
+            if (!std::isfinite(r.E[k])) return fail(ASL_EINVAL, "camera %d: E is not finite", c);
+        const double *E = r.E;
+        double dev = 0;
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++)
+                dev = std::max(dev, std::fabs(E[4 * i] * E[4 * j] + E[4 * i + 1] * E[4 * j + 1] + E[4 * i + 2] * E[4 * j + 2] - (i == j ? 1.0 : 0.0)));
+        const double det = E[0] * (E[5] * E[10] - E[6] * E[9]) - E[1] * (E[4] * E[10] - E[6] * E[8]) + E[2] * (E[4] * E[9] - E[5] * E[8]);
+        if (!(dev <= 1e-6) || !(det > 0))
+            return fail(ASL_EINVAL, "camera %d: the rotation part of E is not a rotation (|R R^T - I| = %g, det %g)", c, dev, det);
+    }
+    return ASL_OK;
+}
+
+static int check_rig_args(const void *obs, int n_cams, int n_frames, int max_tags, const void *map, int n_ids, const void *rig, double tag_size,
+                          double max_tag_rms_px, double sigma_px, const void *out)
+{
+    if (!obs || !map || !rig || !out) return fail(ASL_EINVAL, "NULL argument");
+    if (n_frames < 0) return fail(ASL_EINVAL, "n_frames < 0");
+    if (n_cams < 1 || n_cams > RIG_MAX_CAMS) return fail(ASL_EINVAL, "n_cams must be in [1, %d] (got %d)", RIG_MAX_CAMS, n_cams);
+    if (int rc = check_obs_args(max_tags, n_ids, 0, false, tag_size)) return rc;
+    if (n_cams * max_tags > RIG_MAX_SLOTS) return fail(ASL_EINVAL, "n_cams * max_tags must be <= %d (got %d x %d)", RIG_MAX_SLOTS, n_cams, max_tags);
+    if (!(max_tag_rms_px >= 0) || !std::isfinite(max_tag_rms_px)) return fail(ASL_EINVAL, "max_tag_rms_px must be >= 0 (got %g)", max_tag_rms_px);
+    return check_sigma_px(sigma_px);
+}
+
+// d_cov NULL: the plain kernel
+static void launch_localize_rig(const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map, int n_ids, const void *d_rig,
+                                double tag_size, double max_tag_rms_px, void *d_out, void *d_cov, double sigma_px, hipStream_t st)
+{
+    const double half = (double)(float)(tag_size / 2);  // make_cam's
+    if (d_cov)
+        hipLaunchKernelGGL(k_localize_rig<true>, dim3((unsigned int)n_frames), dim3(ASL_WAVE), rig_lds_bytes(n_cams, max_tags), st, (const ObsRec *)d_obs,
+                           n_cams, max_tags, (const MapTagRec *)d_map, n_ids, (const RigCamRec *)d_rig, half, max_tag_rms_px, (CamPoseRec *)d_out,
+                           (PoseCovRec *)d_cov, sigma_px);
+    else
+        hipLaunchKernelGGL(k_localize_rig<false>, dim3((unsigned int)n_frames), dim3(ASL_WAVE), rig_lds_bytes(n_cams, max_tags), st, (const ObsRec *)d_obs,
+                           n_cams, max_tags, (const MapTagRec *)d_map, n_ids, (const RigCamRec *)d_rig, half, max_tag_rms_px, (CamPoseRec *)d_out,
+                           (PoseCovRec *)nullptr, 0.0);
+}
+
+// the two device forms: d_cov NULL without the covariance.  The table (at most 16 x 216 bytes) is read back and checked
+// before the launch: it must be complete when the call is made.
+static int localize_rig_frames_device(asl_detector *d, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                      const void *d_rig, double tag_size, double max_tag_rms_px, double sigma_px, void *d_out, void *d_cov,
+                                      void *stream)
+{
+    static_assert(sizeof(RigCamRec) == sizeof(asl_rig_camera) && sizeof(asl_rig_camera) == 216, "asl_rig_camera layout");
+    if (!d) return fail(ASL_EINVAL, "NULL detector");
+    if (int rc = check_rig_args(d_obs, n_cams, n_frames, max_tags, d_map, n_ids, d_rig, tag_size, max_tag_rms_px, sigma_px, d_out)) return rc;
+    HIPCHK(hipSetDevice(d->device));
+    asl_rig_camera tab[RIG_MAX_CAMS];
+    HIPCHK(hipMemcpy(tab, d_rig, sizeof(asl_rig_camera) * (size_t)n_cams, hipMemcpyDeviceToHost));
+    if (int rc = check_rig_table(tab, n_cams)) return rc;
+    if (n_frames == 0) return ASL_OK;
+    launch_localize_rig(d_obs, n_cams, n_frames, max_tags, d_map, n_ids, d_rig, tag_size, max_tag_rms_px, d_out, d_cov, sigma_px, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return ASL_OK;
+}
+
+extern "C" int asl_localize_rig_frames_device(asl_detector *d, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map,
+                                              int n_ids, const void *d_rig, double tag_size, double max_tag_rms_px, void *d_out, void *stream)
+{
+    return localize_rig_frames_device(d, d_obs, n_cams, n_frames, max_tags, d_map, n_ids, d_rig, tag_size, max_tag_rms_px, 0.0, d_out, nullptr, stream);
+}
+
+extern "C" int asl_localize_rig_cov_frames_device(asl_detector *d, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map,
+                                                  int n_ids, const void *d_rig, double tag_size, double max_tag_rms_px, double sigma_px,
+                                                  void *d_out, void *d_cov, void *stream)
+{
+    if (!d_cov) return fail(ASL_EINVAL, "NULL argument");
+    return localize_rig_frames_device(d, d_obs, n_cams, n_frames, max_tags, d_map, n_ids, d_rig, tag_size, max_tag_rms_px, sigma_px, d_out, d_cov, stream);
+}
+
+// the two host forms: cov NULL without the covariance
+static int localize_rig_batch(asl_detector *d, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                              const asl_rig_camera *rig, double tag_size, double max_tag_rms_px, double sigma_px, asl_cam_pose *out,
+                              asl_pose_cov *cov)
+{
+    if (!d) return fail(ASL_EINVAL, "NULL detector");
+    int rc = check_rig_args(obs, n_cams, n_frames, max_tags, map, n_ids, rig, tag_size, max_tag_rms_px, sigma_px, out);
+    if (rc) return rc;
+    if ((rc = check_rig_table(rig, n_cams))) return rc;
+    if (n_frames == 0) return ASL_OK;
+    HIPCHK(hipSetDevice(d->device));
+    asl_cam_pose *d_out = nullptr;
+    asl_pose_cov *d_cov = nullptr;
+    if (carve_ws(d->solve_out, [&](WsCarve &c) { d_out = c.take<asl_cam_pose>(n_frames); d_cov = c.take<asl_pose_cov>(cov ? n_frames : 0); }) ||
+        d->rig_cams.ensure(sizeof(asl_rig_camera) * (size_t)n_cams))
+        return fail(ASL_ENOMEM, "rig localisation workspace allocation failed");
+    if ((rc = upload_obs(d, "rig localisation", obs, n_cams * n_frames, max_tags, map, n_ids))) return rc;
+    HIPCHK(hipMemcpy(d->rig_cams.p, rig, sizeof(asl_rig_camera) * (size_t)n_cams, hipMemcpyHostToDevice));
+    launch_localize_rig(d->loc_obs.p, n_cams, n_frames, max_tags, d->loc_map.p, n_ids, d->rig_cams.p, tag_size, max_tag_rms_px, d_out,
+                        cov ? d_cov : nullptr, sigma_px, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, d_out, sizeof(asl_cam_pose) * (size_t)n_frames, hipMemcpyDeviceToHost));
+    if (cov) HIPCHK(hipMemcpy(cov, d_cov, sizeof(asl_pose_cov) * (size_t)n_frames, hipMemcpyDeviceToHost));
+    return ASL_OK;
+}
+
+extern "C" int asl_localize_rig_batch(asl_detector *d, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                      const asl_rig_camera *rig, double tag_size, double max_tag_rms_px, asl_cam_pose *out)
+{
+    return localize_rig_batch(d, obs, n_cams, n_frames, max_tags, map, n_ids, rig, tag_size, max_tag_rms_px, 0.0, out, nullptr);
+}
+
+extern "C" int asl_localize_rig_cov_batch(asl_detector *d, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_map_tag *map,
+                                          int n_ids, const asl_rig_camera *rig, double tag_size, double max_tag_rms_px, double sigma_px,
+                                          asl_cam_pose *out, asl_pose_cov *cov)
+{
+    if (!cov) return fail(ASL_EINVAL, "NULL argument");
+    return localize_rig_batch(d, obs, n_cams, n_frames, max_tags, map, n_ids, rig, tag_size, max_tag_rms_px, sigma_px, out, cov);
 }
 
 // ---- per-tag pose covariance (k_posecov.inc)

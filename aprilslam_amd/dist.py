@@ -146,6 +146,34 @@ class ObsBlock:
         return self._host
 
 
+def localize_rig_block(det, obs, tag_map, rig, tag_size, max_tag_rms_px=0.0, with_cov=False, sigma_px=0.0):
+    """The gathered block read as one rig: stream (rank) c is camera c of `rig` (a rig.Rig or RIG_CAMERA_DTYPE records)
+    and frame f one instant for all of them.  The block is camera-major as all_gather_observations returns it, so it goes to
+    asl_localize_rig_frames_device where it lies (a device ObsBlock: on the current torch stream, one read-back of the
+    results) or to asl_localize_rig_batch (a host block).  Returns (n_frames,) CAM_POSE_DTYPE world<-rig, with_cov also
+    (n_frames,) POSE_COV_DTYPE.  Nothing of the graph update (apply_block) is touched."""
+    blk = obs if isinstance(obs, ObsBlock) else ObsBlock(obs)
+    world, n_frames, max_tags = blk.shape
+    if blk.on_host:
+        return det.localize_rig(blk.data, tag_map, rig, tag_size, max_tag_rms_px, float(sigma_px) if with_cov else None)
+    import torch
+    dev = blk.data.device
+    m, r = _lib._map_records(tag_map), _lib._rig_records(rig)
+    if len(r) != world:
+        raise ValueError("the rig has %d cameras, the block %d streams" % (len(r), world))
+    d_map = torch.from_numpy(m.view(np.uint8).reshape(-1)).to(dev)
+    d_rig = torch.from_numpy(r.view(np.uint8).reshape(-1)).to(dev)
+    d_out = torch.empty(n_frames * _lib.CAM_POSE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    d_cov = torch.empty(n_frames * _lib.POSE_COV_DTYPE.itemsize, dtype=torch.uint8, device=dev) if with_cov else None
+    det.localize_rig_device(blk.data.data_ptr(), world, n_frames, max_tags, d_map.data_ptr(), len(m), d_rig.data_ptr(), d_out.data_ptr(),
+                            tag_size, max_tag_rms_px, stream=torch.cuda.current_stream(dev).cuda_stream,
+                            cov_ptr=d_cov.data_ptr() if with_cov else None, sigma_px=sigma_px)
+    poses = d_out.cpu().numpy().view(_lib.CAM_POSE_DTYPE).reshape(n_frames)
+    if not with_cov:
+        return poses
+    return poses, d_cov.cpu().numpy().view(_lib.POSE_COV_DTYPE).reshape(n_frames)
+
+
 def _full(T12):
     T = np.zeros(T12.shape[:-1] + (4, 4))
     T[..., :3, :] = T12.reshape(T12.shape[:-1] + (3, 4))

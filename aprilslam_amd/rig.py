@@ -1,0 +1,126 @@
+"""Several cameras on one rigid body localised together against a tag map (asl_localize_rig_batch /
+asl_localize_rig_frames_device, k_rig.inc).
+
+One pose world<-rig per frame from every camera's corners in one solve: cameras that each see one or two small tags
+(each alone badly conditioned in tilt, or without any tag for a few frames) constrain one another through the known
+mounting.  A frame index is one instant for all cameras.
+
+    RigCamera       one camera: K, dist (0, 4 or 5 coefficients), T_cam_rig = camera<-rig 4x4 (the mounting)
+    Rig             the cameras in block order; as_records() -> RIG_CAMERA_DTYPE (asl_rig_camera), save / load,
+                    localize(), from_camera_poses()
+"""
+import numpy as np
+
+from ._lib import CAM_POSE_DTYPE, OBS_DTYPE, RIG_CAMERA_DTYPE
+
+MAX_CAMERAS = 16
+MAX_SLOTS = 256          # n_cams * max_tags
+ORTHONORMAL_TOL = 1e-6
+
+__all__ = ["Rig", "RigCamera", "RIG_CAMERA_DTYPE", "MAX_CAMERAS", "MAX_SLOTS"]
+
+
+def _transform(T, what):
+    T = np.array(T, dtype=np.float64)
+    if T.shape == (3, 4):
+        T = np.vstack([T, [0.0, 0.0, 0.0, 1.0]])
+    if T.shape != (4, 4) or not np.all(np.isfinite(T)):
+        raise ValueError("%s is a finite 4x4 (or 3x4) transform" % what)
+    R = T[:3, :3]
+    if np.abs(R @ R.T - np.eye(3)).max() > ORTHONORMAL_TOL or not np.linalg.det(R) > 0:
+        raise ValueError("the rotation part of %s is not a rotation" % what)
+    T[3] = [0.0, 0.0, 0.0, 1.0]
+    return T
+
+
+class RigCamera:
+    """One camera of a rig: its pinhole + lens model and its mounting T_cam_rig = camera<-rig."""
+
+    def __init__(self, K, dist=None, T_cam_rig=None):
+        self.K = np.array(K, dtype=np.float64)
+        if self.K.shape != (3, 3) or not np.all(np.isfinite(self.K)):
+            raise ValueError("K must be a finite 3x3 matrix")
+        self.dist = np.array([] if dist is None else dist, dtype=np.float64).ravel()
+        if len(self.dist) not in (0, 4, 5) or not np.all(np.isfinite(self.dist)):
+            raise ValueError("dist must have 0, 4 or 5 finite coefficients")
+        self.T_cam_rig = _transform(np.eye(4) if T_cam_rig is None else T_cam_rig, "T_cam_rig")
+
+
+class Rig:
+    """The cameras of a rig, in the order of the observation block's leading axis."""
+
+    def __init__(self, cameras):
+        self.cameras = list(cameras)
+        if not 1 <= len(self.cameras) <= MAX_CAMERAS or not all(isinstance(c, RigCamera) for c in self.cameras):
+            raise ValueError("a rig has 1 to %d RigCamera" % MAX_CAMERAS)
+
+    def __len__(self):
+        return len(self.cameras)
+
+    def as_records(self):
+        """(n_cams,) RIG_CAMERA_DTYPE: the table the library reads"""
+        rec = np.zeros(len(self.cameras), dtype=RIG_CAMERA_DTYPE)
+        for k, c in enumerate(self.cameras):
+            rec["K"][k] = c.K
+            rec["dist"][k][:len(c.dist)] = c.dist
+            rec["E"][k] = c.T_cam_rig[:3]
+            rec["n_dist"][k] = len(c.dist)
+        return rec
+
+    @classmethod
+    def from_records(cls, rec):
+        rec = np.asarray(rec, dtype=RIG_CAMERA_DTYPE).ravel()
+        return cls([RigCamera(r["K"], r["dist"][:r["n_dist"]], r["E"]) for r in rec])
+
+    def save(self, path):
+        """Write the rig to an .npz file: K (n, 3, 3), dist (n, 5), n_dist (n,), T_cam_rig (n, 4, 4)."""
+        rec = self.as_records()
+        np.savez(path, K=rec["K"], dist=rec["dist"], n_dist=rec["n_dist"].astype(np.int64),
+                 T_cam_rig=np.array([c.T_cam_rig for c in self.cameras], dtype=np.float64))
+
+    @classmethod
+    def load(cls, path):
+        """The rig Rig.save wrote."""
+        with np.load(path) as z:
+            K, dist, nd, T = z["K"], z["dist"], z["n_dist"], z["T_cam_rig"]
+            n = len(nd)
+            if nd.ndim != 1 or K.shape != (n, 3, 3) or dist.shape != (n, 5) or T.shape != (n, 4, 4):
+                raise ValueError("%s is not a saved Rig (K (n, 3, 3), dist (n, 5), n_dist (n,), T_cam_rig (n, 4, 4))" % path)
+            return cls([RigCamera(K[k], dist[k][:int(nd[k])], T[k]) for k in range(n)])
+
+    def localize(self, det, obs, tag_map, tag_size, max_tag_rms_px=0.0, with_cov=False, sigma_px=0.0):
+        """obs (n_cams, n_frames, max_tags) OBS_DTYPE, camera-major, against tag_map (a localize.TagMap or MAP_TAG_DTYPE
+        records) on det (a _lib.Detector) -> (n_frames,) CAM_POSE_DTYPE with T = world<-rig; with_cov: (poses, (n_frames,)
+        POSE_COV_DTYPE), scaled by sigma_px or, for 0, by the solve's own estimate."""
+        o = np.asarray(obs)
+        if o.dtype != OBS_DTYPE or o.ndim != 3 or o.shape[0] != len(self.cameras):
+            raise ValueError("obs must be (%d, n_frames, max_tags) asl_obs records" % len(self.cameras))
+        if o.shape[0] * o.shape[2] > MAX_SLOTS:
+            raise ValueError("n_cams * max_tags must be <= %d" % MAX_SLOTS)
+        return det.localize_rig(o, tag_map, self.as_records(), tag_size, max_tag_rms_px, float(sigma_px) if with_cov else None)
+
+    @classmethod
+    def from_camera_poses(cls, cams, poses_by_cam):
+        """The mounting from per-camera localisations of the same frames.  cams: (K, dist) per camera; poses_by_cam:
+        per camera an (n_frames,) CAM_POSE_DTYPE array (Detector.localize on that camera's stream).  The rig frame is
+        camera 0.  For every frame where camera 0 and camera c both have status 0, E_c(f) = inv(T_wc_c(f)) T_wc_0(f); E_c is
+        the rotation nearest to the mean of the R (SVD, det +1) and the mean translation.  The mountings are not refined
+        jointly with anything: this is the average of what the single-camera solves imply."""
+        poses = [np.asarray(p, dtype=CAM_POSE_DTYPE).ravel() for p in poses_by_cam]
+        if len(cams) != len(poses) or not poses or any(len(p) != len(poses[0]) for p in poses):
+            raise ValueError("one (K, dist) and one pose array of the same frames per camera")
+        out = []
+        for c, ((K, dist), p) in enumerate(zip(cams, poses)):
+            if c == 0:
+                out.append(RigCamera(K, dist, np.eye(4)))
+                continue
+            both = np.flatnonzero((poses[0]["status"] == 0) & (p["status"] == 0))
+            if len(both) == 0:
+                raise ValueError("camera %d shares no localised frame with camera 0" % c)
+            E = np.array([np.linalg.inv(p["T"][f]) @ poses[0]["T"][f] for f in both])
+            U, _, Vt = np.linalg.svd(E[:, :3, :3].mean(axis=0))
+            R = U @ np.diag([1.0, 1.0, np.linalg.det(U @ Vt)]) @ Vt
+            T = np.eye(4)
+            T[:3, :3], T[:3, 3] = R, E[:, :3, 3].mean(axis=0)
+            out.append(RigCamera(K, dist, T))
+        return cls(out)

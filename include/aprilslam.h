@@ -251,6 +251,47 @@ int asl_localize_cov_batch(asl_detector *det, const asl_obs *obs, int n_frames, 
                            const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
                            double sigma_px, asl_cam_pose *out, asl_pose_cov *cov);
 
+/* ---- several cameras on one rigid body (a "rig") localised together: one pose rig<-world per frame, every camera's
+   corners in one solve.  Camera c has its own model (K, dist: as asl_solve_pnp_batch) and a fixed mounting
+   E = camera_c<-rig; a world corner X seen by camera c contributes project_c(E_c (rig<-world) X) - pixel.  The rig frame
+   is whatever frame the mountings are given in (Rig.from_camera_poses: camera 0). */
+typedef struct {
+    double K[9];      /* row-major */
+    double dist[5];   /* k1 k2 p1 p2 k3; unused = 0 (entries past n_dist are not read) */
+    double E[12];     /* camera<-rig, rows 0..2 of the 4x4 */
+    int32_t n_dist;   /* 0, 4 or 5 */
+    int32_t reserved;
+} asl_rig_camera;     /* 216 bytes */
+
+/* asl_localize_frames_device for a rig.  d_obs: n_cams x n_frames x max_tags records, camera-major (what
+   all_gather_into_tensor makes of the ranks' packed blocks, or asl_pack_observations_device called once per camera at
+   d_obs + c * n_frames * max_tags records); frame f of every camera is one instant.  The frame's records are its global
+   slots g = c * max_tags + s, and gather, seed, refinement and gate are those of asl_localize_frames_device over global
+   slots: the seeds are the <= 8 global slots with flags & 2 of largest corner area -- in pixels squared as they are, so
+   cameras of different focal length are not put on one scale -- and a seed of camera c implies the rig pose
+   inv(E_c) T_obs inv(map[id]), scored over the taking-part corners of all cameras.  tag_size is one value for the rig.
+   d_out: one asl_cam_pose per frame with T = world<-rig; n_tags / n_rejected count global slots, status 1: no mapped tag
+   in any camera, 2: no slot with a successful PnP, seed_slot the global slot of the winner (+256 if mirrored).  A rig of
+   one camera with E = identity is asl_localize_frames_device.
+   d_rig: n_cams asl_rig_camera in device memory; it is read back and checked before the launch (the one synchronous
+   step), so it must be complete when the call is made.  n_cams in [1, 16], max_tags in [1, 256],
+   n_cams * max_tags <= 256; a camera with n_dist not 0 / 4 / 5, a non-finite K or E or an E whose rotation part is not
+   orthonormal to 1e-6 is ASL_EINVAL.  Deterministic: the same input gives the same bytes. */
+int asl_localize_rig_frames_device(asl_detector *det, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map,
+                                   int n_ids, const void *d_rig, double tag_size, double max_tag_rms_px, void *d_out, void *stream);
+/* With the covariance of every frame's world<-rig pose (asl_pose_cov, dof = 8 n_tags - 6), as
+   asl_localize_cov_frames_device: d_out byte for byte what the plain call writes.  The mountings and the map are taken as
+   exact: their uncertainty is not propagated. */
+int asl_localize_rig_cov_frames_device(asl_detector *det, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map,
+                                       int n_ids, const void *d_rig, double tag_size, double max_tag_rms_px, double sigma_px,
+                                       void *d_out, void *d_cov, void *stream);
+/* The same computations on host records, synchronous (the detector keeps the device copies and grows them on demand). */
+int asl_localize_rig_batch(asl_detector *det, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_map_tag *map,
+                           int n_ids, const asl_rig_camera *rig, double tag_size, double max_tag_rms_px, asl_cam_pose *out);
+int asl_localize_rig_cov_batch(asl_detector *det, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_map_tag *map,
+                               int n_ids, const asl_rig_camera *rig, double tag_size, double max_tag_rms_px, double sigma_px,
+                               asl_cam_pose *out, asl_pose_cov *cov);
+
 /* One asl_pose_cov per asl_obs record (n_records of them, as asl_pack_observations_device writes them; device pointers,
    asynchronous on `stream`): the covariance of the camera<-tag pose in the record from its 4 corners (8 residuals, dof 2),
    re-linearised at that pose with the camera model of asl_solve_pnp_batch.  Records without flags & 2 get status 1.

@@ -1,0 +1,344 @@
+"""Rig localisation on the device (asl_localize_rig_frames_device / asl_localize_rig_batch and their covariance forms,
+k_rig.inc) against the NumPy statement (tests/rig_ref.py), against the single-camera kernel it reduces to, and end to end
+on rendered frames against the renderer's ground truth.
+
+Bars: pose, rms_px, rms_seed_px 1e-9 relative on the cases of rig_cases (that of test_gpu_localize's
+test_kernel_matches_the_statement_on_the_cpu_cases); covariance per element 600 eps kappa (test_gpu_pose_cov).  A frame
+where a trial is accepted on one side and rejected on the other at rounding level may be held to 1e-7 if it is named in
+LOOSE_FRAMES; at most 3 % of the compared frames may be."""
+import numpy as np
+import pytest
+
+import localize_cases as LC
+import pose_cov_ref as PC
+import rig_cases as RC
+import rig_ref as RR
+from aprilslam_amd import _lib, synth
+from aprilslam_amd.localize import CAM_POSE_DTYPE, TagMap
+from aprilslam_amd.rig import Rig, RigCamera
+
+pytestmark = pytest.mark.gpu
+
+K = synth.camera_matrix(LC.W, LC.H, 45.0)
+EPS = np.finfo(np.float64).eps
+SIGMA = 0.5
+LOOSE_FRAMES = set()           # (case name, frame) held to 1e-7 instead of 1e-9: none
+LOOSE_SINGLE = set()           # the same for the one-camera comparison on localize_cases.cpu_cases: none
+
+
+def dev_bytes(a, dev):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
+
+
+def rel(a, b):
+    return abs(a - b) / max(1.0, abs(b))
+
+
+def test_loose_frames_are_few():
+    total = sum(c["obs"].shape[1] for c in RC.cases())
+    assert len(LOOSE_FRAMES) <= 0.03 * total
+    assert len(LOOSE_SINGLE) <= 0.03 * sum(c[1].shape[0] for c in LC.cpu_cases(K))
+
+
+@pytest.mark.parametrize("name", RC.NAMES)
+def test_kernel_matches_the_statement(gpu_detector, name):
+    c = RC.case(name)
+    obs, rec, rig, ts, gate = c["obs"], c["rec"], c["rig"], c["tag_size"], c["gate"]
+    plain = rig.localize(gpu_detector, obs, rec, ts, gate)
+    out, cov = rig.localize(gpu_detector, obs, rec, ts, gate, with_cov=True, sigma_px=SIGMA)
+    assert out.tobytes() == plain.tobytes()
+    traces = []
+    want = RR.localize(obs, rec, rig, ts, gate, traces=traces)
+    table = RR.rig_table(rig)
+    for f, (g, w, cv) in enumerate(zip(out, want, cov)):
+        tol = 1e-7 if (name, f) in LOOSE_FRAMES else 1e-9
+        print(name, f, "pose %.2e rms %.2e seed rms %.2e" % (LC.rel_err(g["T"], w["T"]), rel(g["rms_px"], w["rms_px"]),
+                                                             rel(g["rms_seed_px"], w["rms_seed_px"])))
+        for field in ("status", "n_tags", "n_rejected", "seed_slot"):
+            assert g[field] == w[field], (f, field, g[field], w[field])
+        assert LC.rel_err(g["T"], w["T"]) <= tol, (f, LC.rel_err(g["T"], w["T"]))
+        assert rel(g["rms_px"], w["rms_px"]) <= tol and rel(g["rms_seed_px"], w["rms_seed_px"]) <= tol, f
+        assert g["status"] == 0
+        # the covariance: the statement at the device's own pose on the statement's active set
+        Xw, uv, ci = RR.frame_points(obs[:, f], rec, ts, traces[f]["active"])
+        R = g["T"][:3, :3].T
+        t = -(R @ g["T"][:3, 3])
+        ref, sig, dof, status = RR.pose_cov(table, R, t, Xw, uv, ci, SIGMA)
+        assert status == 0 and cv["status"] == 0 and cv["dof"] == dof == 8 * g["n_tags"] - 6 and cv["sigma_px"] == SIGMA, f
+        kappa = PC.scaled_condition(RR.linearise(table, R, t, Xw, uv, ci)[1])
+        bar = 600 * EPS * kappa
+        assert bar <= 1e-6, (f, kappa)
+        s = np.sqrt(np.diag(ref))
+        err = np.abs(cv["cov"] - ref) / np.outer(s, s)
+        assert err.max() <= bar, (f, err.max(), bar)
+        assert np.array_equal(cv["cov"], cv["cov"].T), f
+
+
+def test_statuses_and_estimated_sigma(gpu_detector):
+    """frames without a mapped tag / without a seed, and sigma_px = 0 on noisy corners against the statement"""
+    c = RC.case("side_by_side")
+    rng = np.random.default_rng(12)
+    obs = c["obs"].copy()
+    obs["corners"] = (obs["corners"].astype(np.float64) + rng.normal(scale=0.2, size=obs["corners"].shape)).astype(np.float32)
+    obs["flags"][:, 0] = 0
+    obs["flags"][:, 1] &= 1
+    out, cov = c["rig"].localize(gpu_detector, obs, c["rec"], c["tag_size"], with_cov=True, sigma_px=0.0)
+    want, wcov = RR.localize(obs, c["rec"], c["rig"], c["tag_size"], sigma_px=0.0)
+    assert list(out["status"]) == list(want["status"]) == [1, 2, 0, 0, 0, 0]
+    for f in (0, 1):
+        assert out[f].tobytes() == want[f].tobytes()
+        assert cov["status"][f] == 1 and cov["dof"][f] == 0 and cov["sigma_px"][f] == 0.0 and not cov["cov"][f].any()
+    for f in range(2, 6):
+        assert out["seed_slot"][f] == want["seed_slot"][f] and LC.rel_err(out["T"][f], want["T"][f]) <= 1e-9
+        assert cov["status"][f] == 0 and abs(cov["sigma_px"][f] - wcov["sigma_px"][f]) <= 1e-6 * wcov["sigma_px"][f]
+        assert 0.1 < cov["sigma_px"][f] < 0.3
+
+
+@pytest.mark.parametrize("case", [c[0] for c in LC.cpu_cases(K)])
+def test_one_camera_at_the_identity_is_the_single_camera_kernel(gpu_detector, case):
+    name, obs, rec, dist, gate = [c for c in LC.cpu_cases(K) if c[0] == case][0]
+    want, wcov = gpu_detector.localize(obs, rec, K, dist, LC.TAG_INNER, max_tag_rms_px=gate, sigma_px=SIGMA)
+    rig = Rig([RigCamera(K, dist, np.eye(4))])
+    got, gcov = rig.localize(gpu_detector, obs[None], rec, LC.TAG_INNER, gate, with_cov=True, sigma_px=SIGMA)
+    print(case, "pose bytes identical:", got.tobytes() == want.tobytes(), "covariance bytes identical:", gcov.tobytes() == wcov.tobytes())
+    for f, (g, w, gc, wc) in enumerate(zip(got, want, gcov, wcov)):
+        tol = 1e-7 if (case, f) in LOOSE_SINGLE else 1e-12
+        for field in ("status", "n_tags", "n_rejected", "seed_slot"):
+            assert g[field] == w[field], (f, field)
+        assert LC.rel_err(g["T"], w["T"]) <= tol, (f, LC.rel_err(g["T"], w["T"]))
+        assert gc["status"] == wc["status"] and gc["dof"] == wc["dof"] and gc["sigma_px"] == wc["sigma_px"], f
+        if wc["status"] == 0:
+            s = np.sqrt(np.diag(wc["cov"]))
+            assert (np.abs(gc["cov"] - wc["cov"]) / np.outer(s, s)).max() <= tol, f
+        else:
+            assert not gc["cov"].any()
+
+
+def test_repeated_calls_give_identical_bytes(gpu_detector):
+    """the device-pointer forms on the 256-slot case, plain and with covariance; d_out the bytes of the host form"""
+    import torch
+    dev = torch.device("cuda:0")
+    c = RC.case("slots_256")
+    obs, rec, rig = c["obs"], c["rec"], c["rig"].as_records()
+    n_cams, n, mt = obs.shape
+    host, hcov = gpu_detector.localize_rig(obs, rec, rig, c["tag_size"], 1.0, sigma_px=SIGMA)
+    d_obs, d_map, d_rig = dev_bytes(obs, dev), dev_bytes(rec, dev), dev_bytes(rig, dev)
+    st = torch.cuda.current_stream().cuda_stream
+    for _ in range(10):
+        d_out = torch.full((n * CAM_POSE_DTYPE.itemsize,), 0xAB, dtype=torch.uint8, device=dev)
+        d_cov = torch.full((n * _lib.POSE_COV_DTYPE.itemsize,), 0xAB, dtype=torch.uint8, device=dev)
+        gpu_detector.localize_rig_device(d_obs.data_ptr(), n_cams, n, mt, d_map.data_ptr(), len(rec), d_rig.data_ptr(), d_out.data_ptr(),
+                                         c["tag_size"], 1.0, stream=st)
+        torch.cuda.synchronize()
+        assert d_out.cpu().numpy().tobytes() == host.tobytes()
+        d_out.fill_(0xAB)
+        gpu_detector.localize_rig_device(d_obs.data_ptr(), n_cams, n, mt, d_map.data_ptr(), len(rec), d_rig.data_ptr(), d_out.data_ptr(),
+                                         c["tag_size"], 1.0, stream=st, cov_ptr=d_cov.data_ptr(), sigma_px=SIGMA)
+        torch.cuda.synchronize()
+        assert d_out.cpu().numpy().tobytes() == host.tobytes() and d_cov.cpu().numpy().tobytes() == hcov.tobytes()
+
+
+# ---- end to end on the device
+
+E2E_FRAMES, E2E_MAX_TAGS = 128, 32
+
+
+@pytest.fixture(scope="module")
+def rig_block():
+    """Two cameras on one rig (camera 0 = the rig frame, camera 1 6 units to its right, turned 8 degrees out and 1 down)
+    moved along the bench trajectory through the bench scene: each stream rendered on the device, detected, and packed
+    into its half of one block; then the rig solve and each camera's own localisation on that block, one read-back"""
+    import torch
+
+    import bench
+    dev = torch.device("cuda:0")
+    n, mt = E2E_FRAMES, E2E_MAX_TAGS
+    tags = LC.bench_scene()
+    rec = TagMap.from_scene(tags).as_records()
+    E1 = RC.mounting(8.0, (6.0, 0.5, 0.0), 1.0)
+    rig = Rig([RigCamera(K, None, np.eye(4)), RigCamera(K, None, E1)])
+    cams0 = bench.camera_trajectory(n)
+    truth = [LC.world_from_camera(p, r) for p, r in cams0]
+    cams = [cams0, [RC.synth_camera(T @ np.linalg.inv(E1)) for T in truth]]
+    tex = synth.gray_textures([int(t["id"]) for t in tags])
+    d_tex = torch.from_numpy(tex).to(dev)
+    stream = torch.cuda.Stream(dev)
+    st = stream.cuda_stream
+    d_obs = torch.empty((2, n, mt, _lib.OBS_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    d_map, d_rig = dev_bytes(rec, dev), dev_bytes(rig.as_records(), dev)
+    d_out = torch.empty((3, n, CAM_POSE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    dets, keep = [], []
+    for c in range(2):
+        det = _lib.Detector("tagStandard41h12", id_limit=0)
+        planes, _ = synth.render_planes(LC.W, LC.H, tags, LC.TAG_OUTER, cams[c])
+        d_planes = torch.from_numpy(planes.view(np.uint8).reshape(planes.shape + (-1,))).to(dev)
+        frames = torch.empty((n, LC.H, LC.W, 3), dtype=torch.uint8, device=dev)
+        keep += [d_planes, frames]
+        det.render_frames_device(frames.data_ptr(), n, LC.W, LC.H, d_planes.data_ptr(), planes.shape[1], d_tex.data_ptr(), tex.shape[2],
+                                 tex.shape[1], 0.5 * LC.TAG_OUTER, stream=st)
+        det.submit_device(frames.data_ptr(), n, 3, LC.W, LC.H, stream=st, K=K, dist=np.zeros(4), tag_size=LC.TAG_INNER)
+        det.pack_observations_device(d_obs[c].data_ptr(), mt, stream=st)
+        dets.append(det)
+    det = dets[0]
+    det.localize_rig_device(d_obs.data_ptr(), 2, n, mt, d_map.data_ptr(), len(rec), d_rig.data_ptr(), d_out[0].data_ptr(), LC.TAG_INNER, stream=st)
+    for c in range(2):
+        det.localize_device(d_obs[c].data_ptr(), n, mt, d_map.data_ptr(), len(rec), d_out[1 + c].data_ptr(), K, None, LC.TAG_INNER, stream=st)
+    stream.synchronize()
+    out = d_out.cpu().numpy().view(CAM_POSE_DTYPE).reshape(3, n)
+    obs = d_obs.cpu().numpy().view(_lib.OBS_DTYPE).reshape(2, n, mt)
+    for d in dets:
+        d.collect()
+    yield det, obs, rec, rig, out, truth
+    for d in dets:
+        d.close()
+
+
+def pose_rms(Ts, truth):
+    rot = np.array([LC.rot_err(T, t) for T, t in zip(Ts, truth)])
+    tr = np.array([np.linalg.norm(T[:3, 3] - t[:3, 3]) for T, t in zip(Ts, truth)]) * LC.MM_PER_UNIT
+    return float(np.sqrt(np.mean(rot ** 2)) * 1e3), float(np.sqrt(np.mean(tr ** 2)))
+
+
+def test_device_block_matches_the_statement(rig_block):
+    """the bar of test_gpu_localize.test_device_frames_match_the_statement: 1e-7 on detector corners, counts identical,
+    the same seed or one of equal score"""
+    _, obs, rec, rig, out, _ = rig_block
+    want = RR.localize(obs, rec, rig, LC.TAG_INNER)
+    worst = 0.0
+    for f, (g, w) in enumerate(zip(out[0], want)):
+        assert g["status"] == w["status"] and g["n_tags"] == w["n_tags"] and g["n_rejected"] == w["n_rejected"], f
+        worst = max(worst, LC.rel_err(g["T"], w["T"]))
+        assert LC.rel_err(g["T"], w["T"]) <= 1e-7, (f, LC.rel_err(g["T"], w["T"]))
+        assert rel(g["rms_px"], w["rms_px"]) <= 1e-6 and rel(g["rms_seed_px"], w["rms_seed_px"]) <= 1e-6, f
+        if g["seed_slot"] != w["seed_slot"]:
+            sc = RR.candidate_scores(obs[:, f], rec, rig, LC.TAG_INNER)
+            assert g["seed_slot"] in sc and abs(sc[g["seed_slot"]] - sc[w["seed_slot"]]) <= 1e-9 * max(1.0, sc[w["seed_slot"]]), f
+    print("rig kernel against the statement on %d rendered frames: worst pose difference %.2e" % (len(want), worst))
+    assert (out[0]["status"] == 0).all() and (out[0]["n_tags"] >= 20).all()
+
+
+def test_device_block_against_ground_truth(rig_block):
+    """the rig pose is no worse than the worse of its two cameras localised alone on the same block (RMS over the frames,
+    rotation and translation); all three figures are printed"""
+    _, obs, rec, rig, out, truth = rig_block
+    assert (out["status"] == 0).all()
+    r = pose_rms(out[0]["T"], truth)
+    single = [pose_rms([T @ rc.T_cam_rig for T in out[1 + c]["T"]], truth) for c, rc in enumerate(rig.cameras)]
+    print("world<-rig against the renderer: rig %.4f mrad %.4f mm; camera 0 alone %.4f mrad %.4f mm; camera 1 alone %.4f mrad %.4f mm"
+          % (r + single[0] + single[1]))
+    assert r[0] <= max(single[0][0], single[1][0]) and r[1] <= max(single[0][1], single[1][1])
+
+
+def test_mounting_from_the_single_camera_poses(rig_block):
+    """Rig.from_camera_poses on the two streams' own localisations.  Every per-frame mounting is off by the two cameras'
+    pose errors of that frame; their mean is no further off than their RMS, so solving with it must move the rig poses
+    by less than the worse camera's own pose error."""
+    det, obs, rec, rig, out, truth = rig_block
+    est = Rig.from_camera_poses([(K, None), (K, None)], [out[1], out[2]])
+    moved = est.localize(det, obs, rec, LC.TAG_INNER)
+    change = pose_rms(moved["T"], out[0]["T"])
+    single = [pose_rms([T @ rc.T_cam_rig for T in out[1 + c]["T"]], truth) for c, rc in enumerate(rig.cameras)]
+    dE = est.cameras[1].T_cam_rig @ np.linalg.inv(rig.cameras[1].T_cam_rig)
+    print("estimated mounting off by %.4f mrad %.4f mm; rig poses change by %.4f mrad %.4f mm; single-camera error %.4f mrad %.4f mm / %.4f mrad %.4f mm"
+          % ((LC.rot_err(dE, np.eye(4)) * 1e3, np.linalg.norm(dE[:3, 3]) * LC.MM_PER_UNIT) + change + single[0] + single[1]))
+    assert change[0] < max(single[0][0], single[1][0]) and change[1] < max(single[0][1], single[1][1])
+
+
+# ---- the ABI
+
+def test_errors_are_loud_and_write_nothing(gpu_detector):
+    import torch
+    dev = torch.device("cuda:0")
+    L = _lib.load()
+    c = RC.case("side_by_side")
+    obs, rec, rig = np.ascontiguousarray(c["obs"]), c["rec"], c["rig"].as_records()
+    n_cams, n, mt = obs.shape
+    d_obs, d_map = dev_bytes(obs, dev), dev_bytes(rec, dev)
+
+    def bad_table(field, value, cam=1):
+        r = rig.copy()
+        r[field][cam] = value
+        return r
+
+    skew = rig["E"][1].copy()
+    skew[0, 0] += 1e-4
+    tables = [bad_table("n_dist", 3), bad_table("n_dist", -1, 0), bad_table("K", np.full((3, 3), np.nan)), bad_table("E", np.full((3, 4), np.inf)),
+              bad_table("E", skew), bad_table("E", np.c_[np.diag([1.0, 1.0, -1.0]), np.zeros(3)])]
+    ok = dict(obs=d_obs.data_ptr(), n_cams=n_cams, n_frames=n, max_tags=mt, map=d_map.data_ptr(), n_ids=len(rec), rig=None, tag_size=c["tag_size"],
+              gate=0.0, sigma=0.5)
+    host_ok = dict(ok, obs=obs.ctypes.data, map=rec.ctypes.data)
+    bad = [dict(obs=None), dict(map=None), dict(rig=None), dict(n_cams=0), dict(n_cams=17), dict(max_tags=0), dict(max_tags=257),
+           dict(n_cams=8, max_tags=33), dict(n_ids=0), dict(n_frames=-1), dict(tag_size=0.0), dict(tag_size=float("nan")), dict(gate=-1.0),
+           dict(gate=float("inf")), dict(sigma=-1.0), dict(sigma=float("nan"))]
+    keep = []
+
+    def call(a, device, with_cov, out_ptr, cov_ptr):
+        if a["rig"] is not None and not isinstance(a["rig"], int):
+            tab = np.ascontiguousarray(a["rig"])
+            if device:
+                t = dev_bytes(tab, dev)
+                keep.append(t)
+                rp = t.data_ptr()
+            else:
+                keep.append(tab)
+                rp = tab.ctypes.data
+        else:
+            rp = a["rig"]
+        head = (gpu_detector._h, a["obs"], a["n_cams"], a["n_frames"], a["max_tags"], a["map"], a["n_ids"], rp, a["tag_size"], a["gate"])
+        if device:
+            if with_cov:
+                return L.asl_localize_rig_cov_frames_device(*head, a["sigma"], out_ptr, cov_ptr, None)
+            return L.asl_localize_rig_frames_device(*head, out_ptr, None)
+        if with_cov:
+            return L.asl_localize_rig_cov_batch(*head, a["sigma"], out_ptr, cov_ptr)
+        return L.asl_localize_rig_batch(*head, out_ptr)
+
+    for device in (True, False):
+        base = ok if device else host_ok
+        for with_cov in (False, True):
+            if device:
+                out = torch.full((n * CAM_POSE_DTYPE.itemsize,), 0x55, dtype=torch.uint8, device=dev)
+                cov = torch.full((n * _lib.POSE_COV_DTYPE.itemsize,), 0x55, dtype=torch.uint8, device=dev)
+                op, cp = out.data_ptr(), cov.data_ptr()
+            else:
+                out = np.full(n * CAM_POSE_DTYPE.itemsize, 0x55, dtype=np.uint8)
+                cov = np.full(n * _lib.POSE_COV_DTYPE.itemsize, 0x55, dtype=np.uint8)
+                op, cp = out.ctypes.data, cov.ctypes.data
+            variants = [dict(base, **{"rig": rig, **b}) for b in bad if with_cov or "sigma" not in b] + [dict(base, rig=t) for t in tables]
+            for a in variants:
+                assert call(a, device, with_cov, op, cp) == -1, (device, with_cov, a)
+                assert len(L.asl_last_error()) > 0
+            assert call(dict(base, rig=rig), device, with_cov, None, cp) == -1           # no room for the poses
+            if with_cov:
+                assert call(dict(base, rig=rig), device, with_cov, op, None) == -1       # ... for the covariance
+            if device:
+                torch.cuda.synchronize()
+                assert bool((out == 0x55).all()) and bool((cov == 0x55).all())
+            else:
+                assert (out == 0x55).all() and (cov == 0x55).all()
+    assert L.asl_localize_rig_batch(None, obs.ctypes.data, n_cams, n, mt, rec.ctypes.data, len(rec), rig.ctypes.data, c["tag_size"], 0.0, None) == -1
+    # the Python surface raises, with the library's message
+    with pytest.raises(_lib.AslError, match="n_cams"):
+        gpu_detector.localize_rig(np.zeros((17, 1, 1), dtype=_lib.OBS_DTYPE), rec, np.zeros(17, dtype=_lib.RIG_CAMERA_DTYPE), 1.0)
+    with pytest.raises(_lib.AslError, match="rotation"):
+        gpu_detector.localize_rig(obs, rec, tables[4], c["tag_size"])
+    with pytest.raises(ValueError):
+        gpu_detector.localize_rig(obs, rec, rig[:1], c["tag_size"])
+    with pytest.raises(ValueError):
+        c["rig"].localize(gpu_detector, obs[:1], rec, c["tag_size"])
+
+
+def test_gathered_block_feeds_the_rig_solve(gpu_detector):
+    """dist.localize_rig_block on a gathered device block (world = cameras): the bytes of the host form"""
+    import torch
+
+    from aprilslam_amd import dist as D
+    dev = torch.device("cuda:0")
+    c = RC.case("side_by_side")
+    obs = np.ascontiguousarray(c["obs"])
+    want = gpu_detector.localize_rig(obs, c["rec"], c["rig"], c["tag_size"])
+    blk = D.ObsBlock(dev_bytes(obs, dev).view(obs.shape + (_lib.OBS_DTYPE.itemsize,)))
+    got = D.localize_rig_block(gpu_detector, blk, c["rec"], c["rig"], c["tag_size"])
+    assert got.tobytes() == want.tobytes()
+    assert D.localize_rig_block(gpu_detector, D.ObsBlock(obs), c["rec"], c["rig"], c["tag_size"]).tobytes() == want.tobytes()
