@@ -64,7 +64,8 @@ __device__ __forceinline__ int cal_nt(int n_dist) { return 11 + n_dist; }  // 6 
 // taking-part slots (identical in every lane)
 __device__ __forceinline__ int cal_gather(const CalibArgs &a, int f, int lane, const LocLds &L)
 {
-    return loc_gather(a.obs + (size_t)f * a.max_tags, a.max_tags, a.map, a.n_ids, a.half, [](int) { return true; }, L, lane);
+    const ObsRec *fo = a.obs + (size_t)f * a.max_tags;
+    return loc_gather([=](int s) { return fo + s; }, a.max_tags, a.map, a.n_ids, a.half, [](int) { return true; }, L, lane);
 }
 
 // Homography (row-major 3x3) of the square (+-1, +-1), lb rb rt lt, onto the corners in x' = (u - cx) / s: the closed-form

@@ -13,6 +13,10 @@
 //           of sigma^2 (J^T J)^-1 in the output convention (pose_cov_column_dev, k_pnp.inc; tests/pose_cov_ref.py)
 // tests/localize_ref.py is the NumPy statement of the same computation.  Latency-bound scalar float64 like k_pnp.inc:
 // the time goes into the dependent chains of the passes and reductions, not into bytes (136 B per slot in, 160 B per frame out).
+// These steps are written once, in loc_solve_frame<COV, Model>, over the slots of a model: where slot g's record lives,
+// how one of its corners is projected, and how its camera<-world candidate becomes the pose solved for.  LocOneCam (here)
+// is one camera's max_tags slots and makes k_localize; LocRig (k_rig.inc) is the n_cams * max_tags global slots of a rig
+// and makes k_localize_rig.  Each kernel is its set-up, a model and one call.
 
 struct MapTagRec {  // == asl_map_tag, 104 bytes
     double T[12];   // rows 0..2 of world<-tag
@@ -74,6 +78,23 @@ __device__ __forceinline__ double loc_corner(const CamDev &c, const double *R, c
     return r0 * r0 + r1 * r1;
 }
 
+// The slot model of one camera: slot s is record fo[s], every corner goes through cam, and the pose solved for is the
+// camera's, so a slot's camera<-world candidate is written straight to where the caller wants it (no copy).
+struct LocOneCam {
+    const CamDev &cam;
+    const ObsRec *fo;  // the frame's max_tags records
+    int max_tags;
+    __device__ __forceinline__ int nslots() const { return max_tags; }
+    __device__ __forceinline__ const ObsRec *rec(int s) const { return fo + s; }
+    template <bool NE>
+    __device__ __forceinline__ double corner(int, const double *R, const double *t, const double *X, double iu, double iv, double *acc) const
+    {
+        return loc_corner<NE>(cam, R, t, X, iu, iv, acc);
+    }
+    // the solved pose (R, t) that slot s's PnP pose To and map tag M propose (loc_candidate)
+    __device__ __forceinline__ void candidate(int, const double *To, const double *M, bool mirror, double *R, double *t) const;
+};
+
 // LDS of one frame (dynamic): world corners double[3 * n4], slot area double[max_tags], image corners float[2 * n4],
 // slot state int[max_tags] (0 out, 1 taking part, 2 dropped by the gate)
 struct LocLds {
@@ -118,16 +139,17 @@ __device__ __forceinline__ void loc_gather_slot(const LocLds &L, int s, const do
     }
 }
 
-// Gather of one frame's max_tags slots against the map: state 1 for a taking-part slot (flags & 1, mapped id), its area
-// if seeds(flags), else -1.  Returns the number of taking-part slots and, with nseed, sets the number of seeding ones,
-// both identical in every lane.
-template <class Seeds>
-__device__ __forceinline__ int loc_gather(const ObsRec *fo, int max_tags, const MapTagRec *map, int n_ids, double half, Seeds seeds,
-                                          const LocLds &L, int lane, int *nseed = nullptr)
+// Gather of one frame's n slots against the map, slot s being the record rec(s): state 1 for a taking-part slot
+// (flags & 1, mapped id), its area if seeds(flags), else -1.  Returns the number of taking-part slots and, with nseed,
+// sets the number of seeding ones, both identical in every lane.
+template <class Rec, class Seeds>
+__device__ __forceinline__ int loc_gather(Rec rec, int n, const MapTagRec *map, int n_ids, double half, Seeds seeds, const LocLds &L, int lane,
+                                          int *nseed = nullptr)
 {
     int npart = 0, ns = 0;
-    for (int s = lane; s < max_tags; s += ASL_WAVE) {
-        const int id = fo[s].id, fl = fo[s].flags;
+    for (int s = lane; s < n; s += ASL_WAVE) {
+        const ObsRec *r = rec(s);
+        const int id = r->id, fl = r->flags;
         const bool part = (fl & 1) && id >= 0 && id < n_ids && map[id].valid;
         L.state[s] = part ? 1 : 0;
         L.area[s] = -1.0;
@@ -135,7 +157,7 @@ __device__ __forceinline__ int loc_gather(const ObsRec *fo, int max_tags, const 
         npart++;
         float cf[8];
 #pragma unroll
-        for (int k = 0; k < 8; k++) cf[k] = fo[s].corners[k];
+        for (int k = 0; k < 8; k++) cf[k] = r->corners[k];
         loc_gather_slot(L, s, map[id].T, half, cf);
         if (seeds(fl)) {
             ns++;
@@ -174,7 +196,8 @@ __device__ __forceinline__ int loc_top_k(int n, int lane, Area area, int (&sel)[
 // Every candidate of the chosen indices, in ascending index order, plain before mirrored: make(i) does index i's own work
 // once and returns a callable cand(mirrored, P) that writes the candidate pose P (R row-major 9, t 3); score(P) is its
 // cost.  A cost strictly below best replaces best and Pb; returns the code of the last replacement (index, + LOC_MIRRORED
-// if mirrored), -1 if none.  k_localize has this loop written out (see there).
+// if mirrored), -1 if none.  For k_calib and k_map.  loc_solve_frame has the same loop written out, once for k_localize and
+// k_localize_rig: through this helper k_localize measured 5 % slower (see there), and the two here are not that hot.
 template <int K, class Make, class Score>
 __device__ __forceinline__ int loc_best_candidate(const int (&sel)[K], int nsel, Make make, Score score, double &best, double *Pb)
 {
@@ -201,22 +224,31 @@ __device__ __forceinline__ int loc_best_candidate(const int (&sel)[K], int nsel,
     return code;
 }
 
-// Total cost over the frame's active corners (state == 1), identical in every lane; with NE also the normal equations in ne.
-template <bool NE>
-__device__ __forceinline__ double loc_pass(const CamDev &c, const double *R, const double *t, const LocLds &L, int n4, int lane, double *ne)
+// Total cost over the active corners (state == 1) of the model's slots, identical in every lane; with NE also the normal
+// equations in ne.
+template <bool NE, class Model>
+__device__ __forceinline__ double loc_pass(const Model &m, const double *R, const double *t, const LocLds &L, int lane, double *ne)
 {
+    const int n4 = 4 * m.nslots();
     double cost = 0, acc[27];
 #pragma unroll
     for (int i = 0; i < 27; i++) acc[i] = 0;
     for (int k = lane; k < n4; k += ASL_WAVE) {
         if (L.state[k >> 2] != 1) continue;
-        cost += loc_corner<NE>(c, R, t, L.X + 3 * k, (double)L.uv[2 * k], (double)L.uv[2 * k + 1], acc);
+        cost += m.template corner<NE>(k >> 2, R, t, L.X + 3 * k, (double)L.uv[2 * k], (double)L.uv[2 * k + 1], acc);
     }
     if constexpr (NE) {
 #pragma unroll
         for (int i = 0; i < 27; i++) ne[i] = butterfly_sum<64>(acc[i]);
     }
     return butterfly_sum<64>(cost);
+}
+
+// The one-camera spelling, for k_calib and k_map: the n4 / 4 slots of camera c (no records: a pass reads LDS only)
+template <bool NE>
+__device__ __forceinline__ double loc_pass(const CamDev &c, const double *R, const double *t, const LocLds &L, int n4, int lane, double *ne)
+{
+    return loc_pass<NE>(LocOneCam{c, nullptr, n4 >> 2}, R, t, L, lane, ne);
 }
 
 // The fixed schedule (tests/localize_ref.py: lm) on a pose (R, t), refined in place by the left update R <- Rod(w) R,
@@ -282,6 +314,11 @@ __device__ __forceinline__ void loc_candidate(const double *To, const double *M,
     for (int i = 0; i < 3; i++) t[i] = to[i] - (R[3 * i] * M[3] + R[3 * i + 1] * M[7] + R[3 * i + 2] * M[11]);
 }
 
+__device__ __forceinline__ void LocOneCam::candidate(int, const double *To, const double *M, bool mirror, double *R, double *t) const
+{
+    loc_candidate(To, M, mirror, R, t);
+}
+
 // status 1 (no taking-part slot) / 2 (no candidate): identity pose, nothing used
 __device__ __forceinline__ void loc_write_none(CamPoseRec *o, int status)
 {
@@ -298,37 +335,34 @@ __device__ __forceinline__ void loc_cov_write_none(PoseCovRec *oc, double sigma_
     if (lane == 37) { oc->dof = 0; oc->status = 1; }
 }
 
-// COV: also the first-order covariance of the pose written (asl_pose_cov, world<-camera) into cov[frame], scaled by
-// sigma_px or, for 0, by the solve's own cost / dof.  The plain instantiation never touches cov and sigma_px.
-template <bool COV>
-__global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs, int max_tags, const MapTagRec *__restrict__ map, int n_ids,
-                                                 CamDev cam, double gate, CamPoseRec *__restrict__ out, PoseCovRec *__restrict__ cov,
-                                                 double sigma_px)
+// One frame's solve over the slots of model m, steps 1 to 6 of the header, by one wavefront: the pose solved for (the
+// camera's, or the rig's) goes to o as world<-body.  COV: also the first-order covariance of the pose written (asl_pose_cov)
+// into oc, scaled by sigma_px or, for 0, by the solve's own cost / dof.  The plain instantiation never touches oc and sigma_px.
+template <bool COV, class Model>
+__device__ __forceinline__ void loc_solve_frame(const Model &m, const LocLds &L, const MapTagRec *__restrict__ map, int n_ids, double half,
+                                                double gate, CamPoseRec *o, PoseCovRec *oc, double sigma_px, int lane)
 {
-    extern __shared__ double s_dyn[];
-    const int n4 = 4 * max_tags, lane = threadIdx.x;
-    const LocLds L = loc_lds(s_dyn, max_tags);
-    const ObsRec *fo = obs + (size_t)blockIdx.x * max_tags;
-    CamPoseRec *o = out + blockIdx.x;
+    const int n = m.nslots();
     auto pass = [&](const double *R, const double *t, auto ne_tag, double *ne) {
-        return loc_pass<decltype(ne_tag)::value>(cam, R, t, L, n4, lane, ne);
+        return loc_pass<decltype(ne_tag)::value>(m, R, t, L, lane, ne);
     };
 
-    // 1: gather
+    // 1: gather (its barrier also publishes what the caller put into LDS before: the rig's camera table)
     int nseed;
-    const int npart = loc_gather(fo, max_tags, map, n_ids, cam.half, [](int fl) { return (fl & 2) != 0; }, L, lane, &nseed);
+    const int npart = loc_gather([&](int s) { return m.rec(s); }, n, map, n_ids, half, [](int fl) { return (fl & 2) != 0; }, L, lane, &nseed);
     if (npart == 0 || nseed == 0) {
         if (lane == 0) loc_write_none(o, npart == 0 ? 1 : 2);
-        if constexpr (COV) loc_cov_write_none(cov + blockIdx.x, sigma_px, lane);
+        if constexpr (COV) loc_cov_write_none(oc, sigma_px, lane);
         return;
     }
 
     // 2: the seeding slots of largest area (ties: lower slot), then every candidate in slot order, plain before mirrored
     int sel[LOC_MAX_SEEDS];
-    const int nsel = loc_top_k(max_tags, lane, [&](int s) { return L.area[s]; }, sel);
-    // loc_best_candidate's loop, written out: through the helper this kernel measured 5 % slower (tools/localize_lab.py,
+    const int nsel = loc_top_k(n, lane, [&](int s) { return L.area[s]; }, sel);
+    // loc_best_candidate's loop, written out: through the helper k_localize measured 5 % slower (tools/localize_lab.py,
     // interleaved runs; about 2 % when the winner is rebuilt instead of copied), with the same instructions but for the
-    // copy of the best pose and the layout.  A change to the candidate rule goes into both.
+    // copy of the best pose and the layout.  This is the one written-out copy, for both kernels; a change to the candidate
+    // rule goes here and into loc_best_candidate.
     double R[9], t[3], best = INFINITY;
     int code = -1, prev = -1;
     for (int j = 0; j < nsel; j++) {
@@ -337,17 +371,18 @@ __global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs,
         for (int r = 0; r < LOC_MAX_SEEDS; r++)
             if (sel[r] > prev && sel[r] < s) s = sel[r];
         prev = s;
+        const ObsRec *fo = m.rec(s);
         double To[12], M[12];
-        const double *Mp = map[fo[s].id].T;
+        const double *Mp = map[fo->id].T;
 #pragma unroll
-        for (int k = 0; k < 12; k++) { To[k] = fo[s].T[k]; M[k] = Mp[k]; }
-        for (int m = 0; m < 2; m++) {
+        for (int k = 0; k < 12; k++) { To[k] = fo->T[k]; M[k] = Mp[k]; }
+        for (int mi = 0; mi < 2; mi++) {
             double Rc[9], tc[3];
-            loc_candidate(To, M, m == 1, Rc, tc);
+            m.candidate(s, To, M, mi == 1, Rc, tc);
             const double cc = pass(Rc, tc, std::false_type{}, nullptr);
             if (cc < best) {
                 best = cc;
-                code = s + LOC_MIRRORED * m;
+                code = s + LOC_MIRRORED * mi;
 #pragma unroll
                 for (int i = 0; i < 9; i++) R[i] = Rc[i];
                 t[0] = tc[0]; t[1] = tc[1]; t[2] = tc[2];
@@ -356,7 +391,7 @@ __global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs,
     }
     if (code < 0) {  // every candidate scored NaN
         if (lane == 0) loc_write_none(o, 2);
-        if constexpr (COV) loc_cov_write_none(cov + blockIdx.x, sigma_px, lane);
+        if constexpr (COV) loc_cov_write_none(oc, sigma_px, lane);
         return;
     }
 
@@ -369,13 +404,13 @@ __global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs,
         for (int round = 0; round < LOC_MAX_GATE_DROPS && nused > 1; round++) {
             double wr = -1.0;
             int ws = 0x7fffffff;
-            for (int s = lane; s < max_tags; s += ASL_WAVE) {
+            for (int s = lane; s < n; s += ASL_WAVE) {
                 if (L.state[s] != 1) continue;
                 double e[4];
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     const int k = 4 * s + q;
-                    e[q] = loc_corner<false>(cam, R, t, L.X + 3 * k, (double)L.uv[2 * k], (double)L.uv[2 * k + 1], nullptr);
+                    e[q] = m.template corner<false>(s, R, t, L.X + 3 * k, (double)L.uv[2 * k], (double)L.uv[2 * k + 1], nullptr);
                 }
                 const double rms = sqrt(((e[0] + e[1]) + (e[2] + e[3])) / 4);
                 if (rms > wr) { wr = rms; ws = s; }
@@ -392,7 +427,7 @@ __global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs,
         }
     }
 
-    // 5: world<-camera = inv(camera<-world)
+    // 5: world<-body = inv(body<-world)
     if (lane == 0) {
 #pragma unroll
         for (int r = 0; r < 3; r++) {
@@ -411,9 +446,8 @@ __global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs,
     // 6: the covariance at the pose just written: one more linearisation over the corners still in LDS, then lane c
     // solves column c (every lane holds the same J^T J after the butterfly sums; lanes past 5 repeat column 5 and store nothing)
     if constexpr (COV) {
-        PoseCovRec *oc = cov + blockIdx.x;
         double ne[27], col[6], sig;
-        const double c1 = loc_pass<true>(cam, R, t, L, n4, lane, ne);
+        const double c1 = loc_pass<true>(m, R, t, L, lane, ne);
         const int dof = 8 * nused - 6;
         const double s2 = pose_cov_sigma2(sigma_px, c1, dof, &sig);
         const int c = lane < 6 ? lane : 5;
@@ -422,4 +456,16 @@ __global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs,
         if (lane == 36) oc->sigma_px = sig;
         if (lane == 37) { oc->dof = dof; oc->status = pd ? 0 : 2; }
     }
+}
+
+// One wavefront per frame; COV: also cov[frame] (world<-camera), which the plain instantiation never touches
+template <bool COV>
+__global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs, int max_tags, const MapTagRec *__restrict__ map, int n_ids,
+                                                 CamDev cam, double gate, CamPoseRec *__restrict__ out, PoseCovRec *__restrict__ cov,
+                                                 double sigma_px)
+{
+    extern __shared__ double s_dyn[];
+    const LocOneCam m{cam, obs + (size_t)blockIdx.x * max_tags, max_tags};
+    loc_solve_frame<COV>(m, loc_lds(s_dyn, max_tags), map, n_ids, cam.half, gate, out + blockIdx.x, COV ? cov + blockIdx.x : nullptr, sigma_px,
+                         (int)threadIdx.x);
 }
