@@ -967,109 +967,11 @@ static int upload_obs(asl_detector *d, const char *what, const asl_obs *obs, int
     return ASL_OK;
 }
 
-static int check_localize_args(const void *obs, int n_frames, int max_tags, const void *map, int n_ids, const double *K, const double *dist,
-                               int n_dist, double tag_size, double max_tag_rms_px, const void *out)
-{
-    if (!obs || !map || !K || !out) return fail(ASL_EINVAL, "NULL argument");
-    if (n_frames < 0) return fail(ASL_EINVAL, "n_frames < 0");
-    if (int rc = check_obs_args(max_tags, n_ids, n_dist, !dist, tag_size)) return rc;
-    if (!(max_tag_rms_px >= 0) || !std::isfinite(max_tag_rms_px)) return fail(ASL_EINVAL, "max_tag_rms_px must be >= 0 (got %g)", max_tag_rms_px);
-    return ASL_OK;
-}
-
-// d_cov NULL: the plain kernel, what asl_localize_frames_device / asl_localize_batch launch
-static void launch_localize(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids, const double *K,
-                            const double *dist, int n_dist, double tag_size, double max_tag_rms_px, void *d_out, void *d_cov, double sigma_px,
-                            hipStream_t st)
-{
-    CamDev cam = make_cam(d, K, dist, n_dist, tag_size);
-    if (d_cov)
-        hipLaunchKernelGGL(k_localize<true>, dim3((unsigned int)n_frames), dim3(ASL_WAVE), loc_lds_bytes(max_tags), st, (const ObsRec *)d_obs, max_tags,
-                           (const MapTagRec *)d_map, n_ids, cam, max_tag_rms_px, (CamPoseRec *)d_out, (PoseCovRec *)d_cov, sigma_px);
-    else
-        hipLaunchKernelGGL(k_localize<false>, dim3((unsigned int)n_frames), dim3(ASL_WAVE), loc_lds_bytes(max_tags), st, (const ObsRec *)d_obs, max_tags,
-                           (const MapTagRec *)d_map, n_ids, cam, max_tag_rms_px, (CamPoseRec *)d_out, (PoseCovRec *)nullptr, 0.0);
-}
-
 static int check_sigma_px(double sigma_px)
 {
     if (!(sigma_px >= 0) || !std::isfinite(sigma_px)) return fail(ASL_EINVAL, "sigma_px must be >= 0 and finite (got %g)", sigma_px);
     return ASL_OK;
 }
-
-// the two device forms: d_cov NULL without the covariance
-static int localize_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids, const double *K,
-                                  const double *dist, int n_dist, double tag_size, double max_tag_rms_px, double sigma_px, void *d_out,
-                                  void *d_cov, void *stream)
-{
-    static_assert(sizeof(MapTagRec) == sizeof(asl_map_tag) && sizeof(asl_map_tag) == 104, "asl_map_tag layout");
-    static_assert(sizeof(CamPoseRec) == sizeof(asl_cam_pose) && sizeof(asl_cam_pose) == 160, "asl_cam_pose layout");
-    static_assert(sizeof(PoseCovRec) == sizeof(asl_pose_cov) && sizeof(asl_pose_cov) == 304, "asl_pose_cov layout");
-    if (!d) return fail(ASL_EINVAL, "NULL detector");
-    int rc = check_localize_args(d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, d_out);
-    if (rc) return rc;
-    if ((rc = check_sigma_px(sigma_px))) return rc;
-    if (n_frames == 0) return ASL_OK;
-    HIPCHK(hipSetDevice(d->device));
-    launch_localize(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, d_out, d_cov, sigma_px, (hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return ASL_OK;
-}
-
-extern "C" int asl_localize_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
-                                          const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
-                                          void *d_out, void *stream)
-{
-    return localize_frames_device(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, 0.0, d_out, nullptr, stream);
-}
-
-extern "C" int asl_localize_cov_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
-                                              const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
-                                              double sigma_px, void *d_out, void *d_cov, void *stream)
-{
-    if (!d_cov) return fail(ASL_EINVAL, "NULL argument");
-    return localize_frames_device(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, sigma_px, d_out, d_cov, stream);
-}
-
-// the two host forms: cov NULL without the covariance
-static int localize_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids, const double *K,
-                          const double *dist, int n_dist, double tag_size, double max_tag_rms_px, double sigma_px, asl_cam_pose *out,
-                          asl_pose_cov *cov)
-{
-    if (!d) return fail(ASL_EINVAL, "NULL detector");
-    int rc = check_localize_args(obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, out);
-    if (rc) return rc;
-    if ((rc = check_sigma_px(sigma_px))) return rc;
-    if (n_frames == 0) return ASL_OK;
-    HIPCHK(hipSetDevice(d->device));
-    asl_cam_pose *d_out = nullptr;
-    asl_pose_cov *d_cov = nullptr;
-    if (carve_ws(d->solve_out, [&](WsCarve &c) { d_out = c.take<asl_cam_pose>(n_frames); d_cov = c.take<asl_pose_cov>(cov ? n_frames : 0); }))
-        return fail(ASL_ENOMEM, "localisation workspace allocation failed");
-    if ((rc = upload_obs(d, "localisation", obs, n_frames, max_tags, map, n_ids))) return rc;
-    launch_localize(d, d->loc_obs.p, n_frames, max_tags, d->loc_map.p, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, d_out, cov ? d_cov : nullptr,
-                    sigma_px, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(out, d_out, sizeof(asl_cam_pose) * (size_t)n_frames, hipMemcpyDeviceToHost));
-    if (cov) HIPCHK(hipMemcpy(cov, d_cov, sizeof(asl_pose_cov) * (size_t)n_frames, hipMemcpyDeviceToHost));
-    return ASL_OK;
-}
-
-extern "C" int asl_localize_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
-                                  const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px, asl_cam_pose *out)
-{
-    return localize_batch(d, obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, 0.0, out, nullptr);
-}
-
-extern "C" int asl_localize_cov_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
-                                      const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px, double sigma_px,
-                                      asl_cam_pose *out, asl_pose_cov *cov)
-{
-    if (!cov) return fail(ASL_EINVAL, "NULL argument");
-    return localize_batch(d, obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, max_tag_rms_px, sigma_px, out, cov);
-}
-
-// ---- rig localisation (k_rig.inc)
 
 // one camera table, wherever it came from: the model and the mounting of every camera
 static int check_rig_table(const asl_rig_camera *rig, int n_cams)
@@ -1095,104 +997,168 @@ static int check_rig_table(const asl_rig_camera *rig, int n_cams)
     return ASL_OK;
 }
 
-static int check_rig_args(const void *obs, int n_cams, int n_frames, int max_tags, const void *map, int n_ids, const void *rig, double tag_size,
-                          double max_tag_rms_px, double sigma_px, const void *out)
-{
-    if (!obs || !map || !rig || !out) return fail(ASL_EINVAL, "NULL argument");
-    if (n_frames < 0) return fail(ASL_EINVAL, "n_frames < 0");
-    if (n_cams < 1 || n_cams > RIG_MAX_CAMS) return fail(ASL_EINVAL, "n_cams must be in [1, %d] (got %d)", RIG_MAX_CAMS, n_cams);
-    if (int rc = check_obs_args(max_tags, n_ids, 0, false, tag_size)) return rc;
-    if (n_cams * max_tags > RIG_MAX_SLOTS) return fail(ASL_EINVAL, "n_cams * max_tags must be <= %d (got %d x %d)", RIG_MAX_SLOTS, n_cams, max_tags);
-    if (!(max_tag_rms_px >= 0) || !std::isfinite(max_tag_rms_px)) return fail(ASL_EINVAL, "max_tag_rms_px must be >= 0 (got %g)", max_tag_rms_px);
-    return check_sigma_px(sigma_px);
-}
+// One localisation call (k_localize.inc, k_rig.inc), whichever of the eight entry points made it, in their argument order.  The single-camera forms
+// leave n_cams 0 and rig NULL and give K / dist / n_dist; the rig forms give n_cams and the table and leave those NULL.
+// The plain forms leave sigma_px 0 and cov NULL.  obs, map, rig, out and cov are all host or all device pointers.
+struct LocCall {
+    const void *obs; int n_cams, n_frames, max_tags;
+    const void *map; int n_ids;
+    const double *K, *dist; int n_dist;
+    const void *rig;
+    double tag_size, gate, sigma_px;
+    void *out, *cov;
+    bool with_cov;      // a covariance form: cov must be there
+};
 
-// d_cov NULL: the plain kernel
-static void launch_localize_rig(const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map, int n_ids, const void *d_rig,
-                                double tag_size, double max_tag_rms_px, void *d_out, void *d_cov, double sigma_px, hipStream_t st)
-{
-    const double half = (double)(float)(tag_size / 2);  // make_cam's
-    if (d_cov)
-        hipLaunchKernelGGL(k_localize_rig<true>, dim3((unsigned int)n_frames), dim3(ASL_WAVE), rig_lds_bytes(n_cams, max_tags), st, (const ObsRec *)d_obs,
-                           n_cams, max_tags, (const MapTagRec *)d_map, n_ids, (const RigCamRec *)d_rig, half, max_tag_rms_px, (CamPoseRec *)d_out,
-                           (PoseCovRec *)d_cov, sigma_px);
-    else
-        hipLaunchKernelGGL(k_localize_rig<false>, dim3((unsigned int)n_frames), dim3(ASL_WAVE), rig_lds_bytes(n_cams, max_tags), st, (const ObsRec *)d_obs,
-                           n_cams, max_tags, (const MapTagRec *)d_map, n_ids, (const RigCamRec *)d_rig, half, max_tag_rms_px, (CamPoseRec *)d_out,
-                           (PoseCovRec *)nullptr, 0.0);
-}
+static bool is_rig(const LocCall &c) { return c.n_cams || c.rig; }
 
-// the two device forms: d_cov NULL without the covariance.  The table (at most 16 x 216 bytes) is read back and checked
-// before the launch: it must be complete when the call is made.
-static int localize_rig_frames_device(asl_detector *d, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map, int n_ids,
-                                      const void *d_rig, double tag_size, double max_tag_rms_px, double sigma_px, void *d_out, void *d_cov,
-                                      void *stream)
+// Every refusal, before anything is written or enqueued.  A rig's table is checked last: where it is, or (device: the
+// pointers are the device's) in a copy read back, at most 16 x 216 bytes; it must be complete when the call is made.
+static int check_localize_call(const asl_detector *d, const LocCall &c, bool device)
 {
+    static_assert(sizeof(MapTagRec) == sizeof(asl_map_tag) && sizeof(asl_map_tag) == 104, "asl_map_tag layout");
+    static_assert(sizeof(CamPoseRec) == sizeof(asl_cam_pose) && sizeof(asl_cam_pose) == 160, "asl_cam_pose layout");
+    static_assert(sizeof(PoseCovRec) == sizeof(asl_pose_cov) && sizeof(asl_pose_cov) == 304, "asl_pose_cov layout");
     static_assert(sizeof(RigCamRec) == sizeof(asl_rig_camera) && sizeof(asl_rig_camera) == 216, "asl_rig_camera layout");
+    const bool rig = is_rig(c);
+    if (c.with_cov && !c.cov) return fail(ASL_EINVAL, "NULL argument");
     if (!d) return fail(ASL_EINVAL, "NULL detector");
-    if (int rc = check_rig_args(d_obs, n_cams, n_frames, max_tags, d_map, n_ids, d_rig, tag_size, max_tag_rms_px, sigma_px, d_out)) return rc;
-    HIPCHK(hipSetDevice(d->device));
+    if (!c.obs || !c.map || !(rig ? c.rig : (const void *)c.K) || !c.out) return fail(ASL_EINVAL, "NULL argument");
+    if (c.n_frames < 0) return fail(ASL_EINVAL, "n_frames < 0");
+    if (rig && (c.n_cams < 1 || c.n_cams > RIG_MAX_CAMS)) return fail(ASL_EINVAL, "n_cams must be in [1, %d] (got %d)", RIG_MAX_CAMS, c.n_cams);
+    if (int rc = check_obs_args(c.max_tags, c.n_ids, c.n_dist, !c.dist, c.tag_size)) return rc;
+    if (rig && c.n_cams * c.max_tags > RIG_MAX_SLOTS)
+        return fail(ASL_EINVAL, "n_cams * max_tags must be <= %d (got %d x %d)", RIG_MAX_SLOTS, c.n_cams, c.max_tags);
+    if (!(c.gate >= 0) || !std::isfinite(c.gate)) return fail(ASL_EINVAL, "max_tag_rms_px must be >= 0 (got %g)", c.gate);
+    if (int rc = check_sigma_px(c.sigma_px)) return rc;
+    if (!rig) return ASL_OK;
     asl_rig_camera tab[RIG_MAX_CAMS];
-    HIPCHK(hipMemcpy(tab, d_rig, sizeof(asl_rig_camera) * (size_t)n_cams, hipMemcpyDeviceToHost));
-    if (int rc = check_rig_table(tab, n_cams)) return rc;
-    if (n_frames == 0) return ASL_OK;
-    launch_localize_rig(d_obs, n_cams, n_frames, max_tags, d_map, n_ids, d_rig, tag_size, max_tag_rms_px, d_out, d_cov, sigma_px, (hipStream_t)stream);
+    if (device) {
+        HIPCHK(hipSetDevice(d->device));
+        HIPCHK(hipMemcpy(tab, c.rig, sizeof(asl_rig_camera) * (size_t)c.n_cams, hipMemcpyDeviceToHost));
+    }
+    return check_rig_table(device ? tab : (const asl_rig_camera *)c.rig, c.n_cams);
+}
+
+// c's pointers are the device's; cov NULL: the plain kernel
+static void launch_localize(const asl_detector *d, const LocCall &c, hipStream_t st)
+{
+    static const double no_K[9] = {};
+    const bool rig = is_rig(c);
+    const CamDev cam = make_cam(d, rig ? no_K : c.K, c.dist, c.n_dist, c.tag_size);   // a rig: for its half alone
+    const dim3 grid((unsigned int)c.n_frames), block(ASL_WAVE);
+    const ObsRec *obs = (const ObsRec *)c.obs;
+    const MapTagRec *map = (const MapTagRec *)c.map;
+    const RigCamRec *tab = (const RigCamRec *)c.rig;
+    CamPoseRec *out = (CamPoseRec *)c.out;
+    PoseCovRec *cov = (PoseCovRec *)c.cov;
+    const size_t lds = rig ? rig_lds_bytes(c.n_cams, c.max_tags) : loc_lds_bytes(c.max_tags);
+    if (!rig && cov)
+        hipLaunchKernelGGL(k_localize<true>, grid, block, lds, st, obs, c.max_tags, map, c.n_ids, cam, c.gate, out, cov, c.sigma_px);
+    else if (!rig)
+        hipLaunchKernelGGL(k_localize<false>, grid, block, lds, st, obs, c.max_tags, map, c.n_ids, cam, c.gate, out, cov, c.sigma_px);
+    else if (cov)
+        hipLaunchKernelGGL(k_localize_rig<true>, grid, block, lds, st, obs, c.n_cams, c.max_tags, map, c.n_ids, tab, cam.half, c.gate, out, cov, c.sigma_px);
+    else
+        hipLaunchKernelGGL(k_localize_rig<false>, grid, block, lds, st, obs, c.n_cams, c.max_tags, map, c.n_ids, tab, cam.half, c.gate, out, cov, c.sigma_px);
+}
+
+// the four device forms
+static int localize_frames_device(asl_detector *d, const LocCall &c, void *stream)
+{
+    if (int rc = check_localize_call(d, c, true)) return rc;
+    if (c.n_frames == 0) return ASL_OK;
+    HIPCHK(hipSetDevice(d->device));
+    launch_localize(d, c, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return ASL_OK;
+}
+
+// the four host forms: the block, the map and the table into the detector's device copies, the records back from solve_out
+static int localize_batch(asl_detector *d, const LocCall &c)
+{
+    if (int rc = check_localize_call(d, c, false)) return rc;
+    if (c.n_frames == 0) return ASL_OK;
+    HIPCHK(hipSetDevice(d->device));
+    const bool rig = is_rig(c);
+    const size_t n = (size_t)c.n_frames, rig_bytes = sizeof(asl_rig_camera) * (size_t)c.n_cams;
+    asl_cam_pose *d_out = nullptr;
+    asl_pose_cov *d_cov = nullptr;
+    if (carve_ws(d->solve_out, [&](WsCarve &w) { d_out = w.take<asl_cam_pose>(n); d_cov = w.take<asl_pose_cov>(c.cov ? n : 0); }) ||
+        (rig && d->rig_cams.ensure(rig_bytes)))
+        return fail(ASL_ENOMEM, "%slocalisation workspace allocation failed", rig ? "rig " : "");
+    if (int rc = upload_obs(d, rig ? "rig localisation" : "localisation", (const asl_obs *)c.obs, (rig ? c.n_cams : 1) * c.n_frames, c.max_tags,
+                            (const asl_map_tag *)c.map, c.n_ids))
+        return rc;
+    if (rig) HIPCHK(hipMemcpy(d->rig_cams.p, c.rig, rig_bytes, hipMemcpyHostToDevice));
+    LocCall dc = c;
+    dc.obs = d->loc_obs.p; dc.map = d->loc_map.p; dc.rig = rig ? d->rig_cams.p : nullptr; dc.out = d_out; dc.cov = c.cov ? d_cov : nullptr;
+    launch_localize(d, dc, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(c.out, d_out, sizeof(asl_cam_pose) * n, hipMemcpyDeviceToHost));
+    if (c.cov) HIPCHK(hipMemcpy(c.cov, d_cov, sizeof(asl_pose_cov) * n, hipMemcpyDeviceToHost));
+    return ASL_OK;
+}
+
+extern "C" int asl_localize_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                          const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
+                                          void *d_out, void *stream)
+{
+    return localize_frames_device(d, {d_obs, 0, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, nullptr,
+                                      tag_size, max_tag_rms_px, 0.0, d_out, nullptr, false}, stream);
+}
+
+extern "C" int asl_localize_cov_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                              const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
+                                              double sigma_px, void *d_out, void *d_cov, void *stream)
+{
+    return localize_frames_device(d, {d_obs, 0, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, nullptr,
+                                      tag_size, max_tag_rms_px, sigma_px, d_out, d_cov, true}, stream);
+}
+
+extern "C" int asl_localize_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                  const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px, asl_cam_pose *out)
+{
+    return localize_batch(d, {obs, 0, n_frames, max_tags, map, n_ids, K, dist, n_dist, nullptr,
+                              tag_size, max_tag_rms_px, 0.0, out, nullptr, false});
+}
+
+extern "C" int asl_localize_cov_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                      const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px, double sigma_px,
+                                      asl_cam_pose *out, asl_pose_cov *cov)
+{
+    return localize_batch(d, {obs, 0, n_frames, max_tags, map, n_ids, K, dist, n_dist, nullptr,
+                              tag_size, max_tag_rms_px, sigma_px, out, cov, true});
 }
 
 extern "C" int asl_localize_rig_frames_device(asl_detector *d, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map,
                                               int n_ids, const void *d_rig, double tag_size, double max_tag_rms_px, void *d_out, void *stream)
 {
-    return localize_rig_frames_device(d, d_obs, n_cams, n_frames, max_tags, d_map, n_ids, d_rig, tag_size, max_tag_rms_px, 0.0, d_out, nullptr, stream);
+    return localize_frames_device(d, {d_obs, n_cams, n_frames, max_tags, d_map, n_ids, nullptr, nullptr, 0, d_rig,
+                                      tag_size, max_tag_rms_px, 0.0, d_out, nullptr, false}, stream);
 }
 
 extern "C" int asl_localize_rig_cov_frames_device(asl_detector *d, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map,
                                                   int n_ids, const void *d_rig, double tag_size, double max_tag_rms_px, double sigma_px,
                                                   void *d_out, void *d_cov, void *stream)
 {
-    if (!d_cov) return fail(ASL_EINVAL, "NULL argument");
-    return localize_rig_frames_device(d, d_obs, n_cams, n_frames, max_tags, d_map, n_ids, d_rig, tag_size, max_tag_rms_px, sigma_px, d_out, d_cov, stream);
-}
-
-// the two host forms: cov NULL without the covariance
-static int localize_rig_batch(asl_detector *d, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
-                              const asl_rig_camera *rig, double tag_size, double max_tag_rms_px, double sigma_px, asl_cam_pose *out,
-                              asl_pose_cov *cov)
-{
-    if (!d) return fail(ASL_EINVAL, "NULL detector");
-    int rc = check_rig_args(obs, n_cams, n_frames, max_tags, map, n_ids, rig, tag_size, max_tag_rms_px, sigma_px, out);
-    if (rc) return rc;
-    if ((rc = check_rig_table(rig, n_cams))) return rc;
-    if (n_frames == 0) return ASL_OK;
-    HIPCHK(hipSetDevice(d->device));
-    asl_cam_pose *d_out = nullptr;
-    asl_pose_cov *d_cov = nullptr;
-    if (carve_ws(d->solve_out, [&](WsCarve &c) { d_out = c.take<asl_cam_pose>(n_frames); d_cov = c.take<asl_pose_cov>(cov ? n_frames : 0); }) ||
-        d->rig_cams.ensure(sizeof(asl_rig_camera) * (size_t)n_cams))
-        return fail(ASL_ENOMEM, "rig localisation workspace allocation failed");
-    if ((rc = upload_obs(d, "rig localisation", obs, n_cams * n_frames, max_tags, map, n_ids))) return rc;
-    HIPCHK(hipMemcpy(d->rig_cams.p, rig, sizeof(asl_rig_camera) * (size_t)n_cams, hipMemcpyHostToDevice));
-    launch_localize_rig(d->loc_obs.p, n_cams, n_frames, max_tags, d->loc_map.p, n_ids, d->rig_cams.p, tag_size, max_tag_rms_px, d_out,
-                        cov ? d_cov : nullptr, sigma_px, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(out, d_out, sizeof(asl_cam_pose) * (size_t)n_frames, hipMemcpyDeviceToHost));
-    if (cov) HIPCHK(hipMemcpy(cov, d_cov, sizeof(asl_pose_cov) * (size_t)n_frames, hipMemcpyDeviceToHost));
-    return ASL_OK;
+    return localize_frames_device(d, {d_obs, n_cams, n_frames, max_tags, d_map, n_ids, nullptr, nullptr, 0, d_rig,
+                                      tag_size, max_tag_rms_px, sigma_px, d_out, d_cov, true}, stream);
 }
 
 extern "C" int asl_localize_rig_batch(asl_detector *d, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
                                       const asl_rig_camera *rig, double tag_size, double max_tag_rms_px, asl_cam_pose *out)
 {
-    return localize_rig_batch(d, obs, n_cams, n_frames, max_tags, map, n_ids, rig, tag_size, max_tag_rms_px, 0.0, out, nullptr);
+    return localize_batch(d, {obs, n_cams, n_frames, max_tags, map, n_ids, nullptr, nullptr, 0, rig,
+                              tag_size, max_tag_rms_px, 0.0, out, nullptr, false});
 }
 
 extern "C" int asl_localize_rig_cov_batch(asl_detector *d, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_map_tag *map,
                                           int n_ids, const asl_rig_camera *rig, double tag_size, double max_tag_rms_px, double sigma_px,
                                           asl_cam_pose *out, asl_pose_cov *cov)
 {
-    if (!cov) return fail(ASL_EINVAL, "NULL argument");
-    return localize_rig_batch(d, obs, n_cams, n_frames, max_tags, map, n_ids, rig, tag_size, max_tag_rms_px, sigma_px, out, cov);
+    return localize_batch(d, {obs, n_cams, n_frames, max_tags, map, n_ids, nullptr, nullptr, 0, rig,
+                              tag_size, max_tag_rms_px, sigma_px, out, cov, true});
 }
 
 // ---- per-tag pose covariance (k_posecov.inc)

@@ -1,17 +1,31 @@
-"""NumPy statement of the multi-tag camera localisation (asl_localize_frames_device / asl_localize_batch,
-aprilslam_amd/csrc/k_localize.inc): the same gather, candidate order, tie-break, Levenberg-Marquardt schedule and outlier
-gate, frame by frame on the host.  Test infrastructure, as oracle/gn_oracle.py is for the pose-graph LM.
+"""NumPy statement of the localisation against a tag map, for one camera (asl_localize_frames_device / asl_localize_batch)
+and for a rig (asl_localize_rig_frames_device / asl_localize_rig_batch; the rig model is in rig_ref.py), with their
+covariance forms: the same gather, candidate order, tie-break, Levenberg-Marquardt schedule and outlier gate as
+loc_solve_frame<COV, Model> of aprilslam_amd/csrc/k_localize.inc (LocRig: k_rig.inc), frame by frame on the host.  Test infrastructure, as
+oracle/gn_oracle.py is for the pose-graph LM.
 
-Per frame (one row of n_frames x max_tags asl_obs records) against a map of world<-tag poses indexed by id:
+Layout: the camera model and the pose primitives (camera .. lm), the slot model of one camera (OneCamera), and the one
+frame solve over a slot model (gather .. localize_frames) with the covariance step (frame_cov, through
+pose_cov_ref.cov_from_normal; pose_cov_ref imports nothing from here).  A slot model says three things, as LocOneCam and
+LocRig do on the device:
+
+  slot_camera(slot, max_tags)       the camera a flat slot belongs to
+  costs / linearise(R, t, Xw, uv, ci)   squared pixel error per corner / (cost, H, g) at the pose solved for (ci: camera per corner)
+  pose(Rk, tk, camera)              the pose solved for, of a slot's candidate camera<-world = (Rk, tk)
+
+OneCamera costs every corner through its one camera and hands the candidate through: the pose solved for is camera<-world.
+
+Per frame (n_cams x max_tags asl_obs records, n_cams = 1 for one camera; flat slot g = camera * max_tags + slot) against a map
+of world<-tag poses indexed by id:
 
   gather   a slot takes part if flags & 1, 0 <= id < n_ids and map[id].valid; its 4 corners are 4 residual pairs
            against the map tag's corners (object corners +-h, h = float32(tag_size / 2), lb rb rt lt).  A slot seeds
            candidates only if its PnP succeeded (flags & 2).
   seed     the <= 8 seeding slots of largest corner area (ties: lower slot), in slot order, each with its PnP pose and
-           that pose's mirrored planar minimum: camera<-world = T_obs inv(map[id]).  Every candidate is scored by its
-           total squared pixel error over ALL taking-part corners; the strictly lowest wins, so ties go to the lower
-           slot and to the plain pose before the mirrored one.  seed_slot = slot (+256 if mirrored).
-  refine   LM on camera<-world, left update T <- [Rod(w) | v] T, delta = (w, v), analytic Jacobian
+           that pose's mirrored planar minimum: camera<-world = T_obs inv(map[id]), through the model's pose().  Every
+           candidate is scored by its total squared pixel error over ALL taking-part corners; the strictly lowest wins, so
+           ties go to the lower slot and to the plain pose before the mirrored one.  seed_slot = slot (+256 if mirrored).
+  refine   LM on the pose solved for, left update T <- [Rod(w) | v] T, delta = (w, v), analytic Jacobian
            dp_c/d delta = [-[p_c]x | I] through the camera model of k_pnp.inc (pinhole + 0 / 4 / 5 cv2 coefficients):
            at most 10 trial steps; (H + lambda diag(H)) delta = -g with lambda0 = 1e-3, x10 after a rejected step (or a
            failed Cholesky), x0.1 after an accepted one; an accepted step whose cost decrease is below 1e-12 of the
@@ -21,13 +35,16 @@ Per frame (one row of n_frames x max_tags asl_obs records) against a map of worl
            that RMS exceeds the gate, and the solve runs again from the current pose; repeated while the worst slot of
            the new solve exceeds the gate, at most 8 times, and never down to no slot.  One slot at a time: a moved tag
            drags the first solve, and with it the residuals of its neighbours, over the gate as well.
-  output   T = world<-camera 4x4; rms_px = sqrt(cost / (4 n_tags)) of the final solve; rms_seed_px the same of the
-           winning candidate over all taking-part slots; status 1 (no taking-part slot) / 2 (no seeding slot) leave T the
-           identity, the counts 0 and seed_slot -1.
+  output   T = world<-camera (world<-rig) 4x4; rms_px = sqrt(cost / (4 n_tags)) of the final solve; rms_seed_px the same
+           of the winning candidate over all taking-part slots; status 1 (no taking-part slot) / 2 (no seeding slot) leave
+           T the identity, the counts 0 and seed_slot -1.
+  cov      pose_cov_ref.cov_from_normal of the model's normal matrix at the final pose over the slots still active,
+           world<-camera convention, dof = 8 n_used - 6; status 1 without a pose.
 """
 import numpy as np
 
-from aprilslam_amd.localize import CAM_POSE_DTYPE
+import pose_cov_ref as PC
+from aprilslam_amd.localize import CAM_POSE_DTYPE, POSE_COV_DTYPE
 
 MAX_SEED_SLOTS = 8
 LM_ITERS = 10
@@ -108,6 +125,15 @@ def corner_area(c8):
     return 0.5 * abs(a)
 
 
+def neg_skew(p):
+    """-[p]x of every point of p (n, 3): d (Rod(w) p) / d w at w = 0"""
+    S = np.zeros((len(p), 3, 3))
+    S[:, 0, 1], S[:, 0, 2] = p[:, 2], -p[:, 1]
+    S[:, 1, 0], S[:, 1, 2] = -p[:, 2], p[:, 0]
+    S[:, 2, 0], S[:, 2, 1] = p[:, 1], -p[:, 0]
+    return S
+
+
 def corner_costs(cam, R, t, Xw, uv):
     P = Xw @ R.T + t
     ok = P[:, 2] > Z_MIN
@@ -128,11 +154,7 @@ def linearise(cam, R, t, Xw, uv):
         q, Jp = project(cam, p, jac=True)
         r = q - uv[ok]
         cost += float((r * r).sum())
-        neg_px = np.zeros((len(p), 3, 3))           # -[p]x
-        neg_px[:, 0, 1], neg_px[:, 0, 2] = p[:, 2], -p[:, 1]
-        neg_px[:, 1, 0], neg_px[:, 1, 2] = -p[:, 2], p[:, 0]
-        neg_px[:, 2, 0], neg_px[:, 2, 1] = p[:, 1], -p[:, 0]
-        J = np.concatenate([Jp @ neg_px, Jp], axis=2).reshape(-1, 6)
+        J = np.concatenate([Jp @ neg_skew(p), Jp], axis=2).reshape(-1, 6)
         H = J.T @ J
         g = J.T @ r.reshape(-1)
     return cost, H, g
@@ -168,13 +190,37 @@ def chol6_solve(A, b):
     return x
 
 
-def corner_lin(cam, Xw, uv):
-    """lm's lin over a frame's corners: (cost, H, g) of linearise, or (cost, None, None) for the trial cost alone"""
+class OneCamera:
+    """the slot model of one camera (LocOneCam): every slot is its own, and a candidate is handed through"""
+
+    def __init__(self, cam):
+        self.cam = cam
+
+    def slot_camera(self, slot, max_tags):
+        return 0
+
+    def costs(self, R, t, Xw, uv, ci):
+        return corner_costs(self.cam, R, t, Xw, uv)
+
+    def linearise(self, R, t, Xw, uv, ci):
+        return linearise(self.cam, R, t, Xw, uv)
+
+    def pose(self, Rk, tk, camera):
+        return Rk, tk
+
+
+def model_lin(model, Xw, uv, ci):
+    """lm's lin over a frame's corners: (cost, H, g) of the model's linearise, or (cost, None, None) for the trial cost alone"""
     def lin(R, t, want):
         if want:
-            return linearise(cam, R, t, Xw, uv)
-        return float(corner_costs(cam, R, t, Xw, uv).sum()), None, None
+            return model.linearise(R, t, Xw, uv, ci)
+        return float(model.costs(R, t, Xw, uv, ci).sum()), None, None
     return lin
+
+
+def corner_lin(cam, Xw, uv):
+    """model_lin of one camera"""
+    return model_lin(OneCamera(cam), Xw, uv, None)
 
 
 def lm(lin, R, t):
@@ -215,89 +261,101 @@ def _world_corners(M12, obj):
     return np.stack([M[:, 0] * ox + M[:, 1] * oy + M[:, 3] for ox, oy in obj])
 
 
-def seed_candidates(rows, tag_map, cam, seeds, Xw, uv):
-    """[(R, t, seed code, score)] in candidate order: the <= 8 seeding slots of largest area in slot order, plain then mirrored"""
+def tag_points(corners8, tag_size):
+    """a tag's own corners (4, 3) in its frame and its image corners (4, 2)"""
+    return np.c_[object_corners(tag_size), np.zeros(4)], np.asarray(corners8, dtype=np.float64).reshape(4, 2)
+
+
+def gather(rows, tag_map):
+    """one frame's records -> (the records over flat slots, the taking-part slots, the seeding ones)"""
+    flat = rows.reshape(-1)
+    n_ids = len(tag_map)
+    part = [s for s, o in enumerate(flat) if (o["flags"] & 1) and 0 <= o["id"] < n_ids and tag_map["valid"][o["id"]]]
+    seeds = [s for s in part if flat["flags"][s] & 2]
+    return flat, part, seeds
+
+
+def frame_points(model, rows, tag_map, tag_size, slots):
+    """world corners (4n, 3), image corners (4n, 2) and camera per corner (4n,) of the given flat slots of one frame"""
+    flat = rows.reshape(-1)
+    obj = object_corners(tag_size)
+    Xw = np.concatenate([_world_corners(tag_map["T"][flat["id"][s]], obj) for s in slots])
+    uv = np.concatenate([flat["corners"][s].astype(np.float64).reshape(4, 2) for s in slots])
+    ci = np.repeat(np.array([model.slot_camera(s, rows.shape[-1]) for s in slots], dtype=np.int64), 4)
+    return Xw, uv, ci
+
+
+def seed_candidates(model, rows, tag_map, seeds, Xw, uv, ci):
+    """(the <= 8 seeding slots of largest area in slot order, [(R, t, seed code, score)] in candidate order: those slots,
+    plain then mirrored)"""
+    flat = rows.reshape(-1)
+    chosen = [seeds[k] for k in top_k([corner_area(flat["corners"][s]) for s in seeds])]
     out = []
-    for s in [seeds[k] for k in top_k([corner_area(rows["corners"][s]) for s in seeds])]:
-        To = rows["T"][s].reshape(3, 4)
-        M = tag_map["T"][rows["id"][s]].reshape(3, 4)
+    for s in chosen:
+        To = flat["T"][s].reshape(3, 4)
+        M = tag_map["T"][flat["id"][s]].reshape(3, 4)
         for m in (0, 1):
             Ro, to = To[:, :3], To[:, 3]
             if m:
                 Ro, to = mirrored(Ro, to)
-            Rc = Ro @ M[:, :3].T                    # camera<-world = T_obs inv(map)
-            tc = to - Rc @ M[:, 3]
-            out.append((Rc, tc, s + MIRRORED * m, float(corner_costs(cam, Rc, tc, Xw, uv).sum())))
-    return out
+            Rk = Ro @ M[:, :3].T                    # camera<-world = T_obs inv(map)
+            tk = to - Rk @ M[:, 3]
+            Rc, tc = model.pose(Rk, tk, model.slot_camera(s, rows.shape[-1]))
+            out.append((Rc, tc, s + MIRRORED * m, float(model.costs(Rc, tc, Xw, uv, ci).sum())))
+    return chosen, out
 
 
-def candidate_scores(rows, tag_map, K, dist, tag_size):
+def candidate_scores(model, rows, tag_map, tag_size):
     """{seed code: score} of one frame's candidates (for comparing a choice between candidates that tie to rounding)"""
-    cam = camera(K, dist)
-    n_ids = len(tag_map)
-    obj = object_corners(tag_size)
-    part = [s for s, o in enumerate(rows) if (o["flags"] & 1) and 0 <= o["id"] < n_ids and tag_map["valid"][o["id"]]]
-    seeds = [s for s in part if rows["flags"][s] & 2]
+    _, part, seeds = gather(rows, tag_map)
     if not seeds:
         return {}
-    Xw = np.concatenate([_world_corners(tag_map["T"][rows["id"][s]], obj) for s in part])
-    uv = np.concatenate([rows["corners"][s].astype(np.float64).reshape(4, 2) for s in part])
-    return {code: c for _, _, code, c in seed_candidates(rows, tag_map, cam, seeds, Xw, uv)}
+    Xw, uv, ci = frame_points(model, rows, tag_map, tag_size, part)
+    return {code: c for _, _, code, c in seed_candidates(model, rows, tag_map, seeds, Xw, uv, ci)[1]}
 
 
-def localize_frame(rows, tag_map, cam, tag_size, gate, trace=None):
-    """one frame's max_tags asl_obs records -> one CAM_POSE_DTYPE record; trace (a dict, optional) receives the chosen
-    seeding slots (top_k, in slot order: "top_k"), the slots the gate dropped in order ("dropped") and each gate round's own
-    RMS per taking-part slot ("gate_rms")"""
+def solve_frame(model, rows, tag_map, tag_size, gate):
+    """one frame's asl_obs records, (max_tags,) or (n_cams, max_tags) -> (CAM_POSE_DTYPE record, the pose solved for (R, t)
+    or None without one, the flat slots in the final solve, trace); trace: the chosen seeding slots in slot order
+    ("top_k"), the slots the gate dropped in order ("dropped"), each gate round's own RMS per taking-part slot
+    ("gate_rms") and the slots in the final solve ("active")"""
     out = np.zeros((), dtype=CAM_POSE_DTYPE)
     out["T"] = np.eye(4)
     out["seed_slot"] = -1
-    n_ids = len(tag_map)
-    obj = object_corners(tag_size)
-    part = [s for s, o in enumerate(rows) if (o["flags"] & 1) and 0 <= o["id"] < n_ids and tag_map["valid"][o["id"]]]
-    if not part:
-        out["status"] = 1
-        return out
-    seeds = [s for s in part if rows["flags"][s] & 2]
-    if not seeds:
-        out["status"] = 2
-        return out
-    Xw = np.concatenate([_world_corners(tag_map["T"][rows["id"][s]], obj) for s in part])
-    uv = np.concatenate([rows["corners"][s].astype(np.float64).reshape(4, 2) for s in part])
-
-    if trace is not None:
-        areas = [corner_area(rows["corners"][s]) for s in seeds]
-        trace["top_k"] = [seeds[k] for k in top_k(areas)]
-        trace["dropped"], trace["gate_rms"] = [], []
-    cands = seed_candidates(rows, tag_map, cam, seeds, Xw, uv)
+    trace = {"top_k": [], "dropped": [], "gate_rms": [], "active": []}
+    _, part, seeds = gather(rows, tag_map)
+    if not part or not seeds:
+        out["status"] = 1 if not part else 2
+        return out, None, [], trace
+    Xw, uv, ci = frame_points(model, rows, tag_map, tag_size, part)
+    trace["top_k"], cands = seed_candidates(model, rows, tag_map, seeds, Xw, uv, ci)
     best, best_cost = None, np.inf
     for Rc, tc, code, c in cands:
         if c < best_cost:
             best, best_cost = (Rc, tc, code), c
     if best is None:
         out["status"] = 2
-        return out
+        return out, None, [], trace
     R, t, code = best
     n_part = len(part)
-    R, t, cost = lm(corner_lin(cam, Xw, uv), R, t)
+    R, t, cost = lm(model_lin(model, Xw, uv, ci), R, t)
     n_used, n_rej = n_part, 0
+    active = np.ones(n_part, dtype=bool)
     if gate > 0:
-        active = np.ones(n_part, dtype=bool)
         while n_rej < MAX_GATE_DROPS and n_used > 1:
-            e = corner_costs(cam, R, t, Xw, uv).reshape(-1, 4)
+            e = model.costs(R, t, Xw, uv, ci).reshape(-1, 4)
             rms = np.where(active, np.sqrt(((e[:, 0] + e[:, 1]) + (e[:, 2] + e[:, 3])) / 4), -1.0)
             worst = int(np.argmax(rms))                 # the first of equal maxima: the lower slot
-            if trace is not None:
-                trace["gate_rms"].append(rms)
+            trace["gate_rms"].append(rms)
             if not rms[worst] > gate:
                 break
             active[worst] = False
-            if trace is not None:
-                trace["dropped"].append(part[worst])
+            trace["dropped"].append(part[worst])
             n_rej += 1
             n_used -= 1
             keep = np.repeat(active, 4)
-            R, t, cost = lm(corner_lin(cam, Xw[keep], uv[keep]), R, t)
+            R, t, cost = lm(model_lin(model, Xw[keep], uv[keep], ci[keep]), R, t)
+    trace["active"] = [s for s, a in zip(part, active) if a]
     T = np.eye(4)
     T[:3, :3] = R.T
     T[:3, 3] = -(R.T @ t)
@@ -308,20 +366,48 @@ def localize_frame(rows, tag_map, cam, tag_size, gate, trace=None):
     out["n_rejected"] = n_rej
     out["status"] = 0
     out["seed_slot"] = code
-    return out
+    return out, (R, t), trace["active"], trace
 
 
-def localize(obs, tag_map, K, dist, tag_size, max_tag_rms_px=0.0, traces=None):
-    """obs (n_frames, max_tags) asl_obs records, tag_map (n_ids,) asl_map_tag records -> (n_frames,) CAM_POSE_DTYPE;
-    traces (a list, optional) receives localize_frame's trace of every frame"""
+def pose_cov(model, R, t, Xw, uv, ci, sigma_px, world_from_camera=True):
+    """Covariance of the pose (R, t) (reported for its inverse if world_from_camera) that minimises the model's pixel
+    residuals of the points Xw (n, 3) seen at uv (n, 2) by the cameras ci (n,):
+    (cov 6x6 in the order rx ry rz px py pz, sigma_px used, dof, status)"""
+    cost, H, _ = model.linearise(R, t, Xw, uv, ci)
+    return PC.cov_from_normal(H, cost, len(Xw), R, t, float(sigma_px), world_from_camera)
+
+
+def frame_cov(model, rows, tag_map, tag_size, Rt, active, sigma_px):
+    """the POSE_COV_DTYPE record of solve_frame's pose Rt over its active slots; status 1 without a pose"""
+    cov = np.zeros((), dtype=POSE_COV_DTYPE)
+    cov["sigma_px"], cov["status"] = sigma_px, PC.STATUS_NO_POSE
+    if Rt is not None:
+        Xw, uv, ci = frame_points(model, rows, tag_map, tag_size, active)
+        cov["cov"], cov["sigma_px"], cov["dof"], cov["status"] = pose_cov(model, Rt[0], Rt[1], Xw, uv, ci, sigma_px)
+    return cov
+
+
+def localize_frames(model, frames, tag_map, tag_size, gate, sigma_px=None, traces=None):
+    """solve_frame of every frame -> (n_frames,) CAM_POSE_DTYPE; with sigma_px not None also (n_frames,) POSE_COV_DTYPE;
+    traces (a list, optional) receives every frame's trace"""
+    poses, covs = [], []
+    for rows in frames:
+        out, Rt, active, trace = solve_frame(model, rows, tag_map, tag_size, float(gate))
+        poses.append(out)
+        if sigma_px is not None:
+            covs.append(frame_cov(model, rows, tag_map, tag_size, Rt, active, sigma_px))
+        if traces is not None:
+            traces.append(trace)
+    poses = np.array(poses, dtype=CAM_POSE_DTYPE)
+    if sigma_px is None:
+        return poses
+    return poses, np.array(covs, dtype=POSE_COV_DTYPE)
+
+
+def localize(obs, tag_map, K, dist, tag_size, max_tag_rms_px=0.0, sigma_px=None, traces=None):
+    """obs (n_frames, max_tags) asl_obs records, tag_map (n_ids,) asl_map_tag records -> localize_frames of one camera,
+    world<-camera"""
     obs = np.asarray(obs)
     if obs.ndim == 1:
         obs = obs[None]
-    cam = camera(K, dist)
-    out = []
-    for f in range(len(obs)):
-        tr = {} if traces is not None else None
-        out.append(localize_frame(obs[f], tag_map, cam, tag_size, float(max_tag_rms_px), tr))
-        if traces is not None:
-            traces.append(tr)
-    return np.array(out, dtype=CAM_POSE_DTYPE)
+    return localize_frames(OneCamera(camera(K, dist)), obs, tag_map, tag_size, max_tag_rms_px, sigma_px, traces)

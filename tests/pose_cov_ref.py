@@ -1,6 +1,7 @@
 """NumPy statement of the first-order pose covariance (asl_pose_cov: asl_localize_cov_frames_device /
 asl_localize_cov_batch in k_localize.inc, asl_pose_cov_device / asl_solve_pnp_cov_batch in k_posecov.inc).  It is the
-definition the kernels are compared with.  Test infrastructure, as localize_ref.py is for the solver itself.
+definition the kernels are compared with.  Test infrastructure, as localize_ref.py is for the solver itself, which
+imports this module: localize_ref.pose_cov applies cov_from_normal to a slot model's normal matrix.
 
 The solvers refine camera<-X = (R, t) by the left update R <- Rod(w) R, t <- Rod(w) t + v and minimise the squared pixel
 residuals of the corners; localize_ref.linearise gives their cost, H = J^T J and g in those coordinates (w, v).  At the
@@ -20,8 +21,6 @@ PIVOT_TOL times its diagonal entry.  In Jacobi-scaled terms that pivot is 1 / (s
 threshold only refuses matrices whose condition number has passed ~1e13, where float64 has no digit of the inverse left.
 """
 import numpy as np
-
-import localize_ref as LR
 
 PIVOT_TOL = 1e-13
 STATUS_OK, STATUS_NO_POSE, STATUS_NOT_PD = 0, 1, 2
@@ -81,14 +80,6 @@ def cov_from_normal(H, cost, n_corners, R, t, sigma_px, world_from_camera):
     return s2 * (A @ np.linalg.inv(H) @ A.T), sig, dof, STATUS_OK
 
 
-def pose_cov(cam, R, t, Xw, uv, sigma_px, world_from_camera):
-    """Covariance of the pose camera<-X = (R, t) (reported for its inverse if world_from_camera) that minimises the pixel
-    residuals of the points Xw (n, 3) seen at uv (n, 2) through cam (localize_ref.camera):
-    (cov 6x6 in the order rx ry rz px py pz, sigma_px used, dof, status)"""
-    cost, H, _ = LR.linearise(cam, R, t, Xw, uv)
-    return cov_from_normal(H, cost, len(Xw), R, t, float(sigma_px), world_from_camera)
-
-
 def no_pose(sigma_px):
     """status 1: the pose has no covariance"""
     return np.zeros((6, 6)), float(sigma_px), 0, STATUS_NO_POSE
@@ -102,16 +93,3 @@ def pose_error(R_est, p_est, R_true, p_true):
     ang = np.arctan2(s, (np.trace(Q) - 1) / 2)
     r = w * (ang / s) if s > 1e-12 else w
     return np.concatenate([r, p_true - p_est])
-
-
-def frame_points(rows, tag_map, tag_size, active_slots):
-    """world corners (4n, 3) and image corners (4n, 2) of the given slots of one frame's asl_obs records"""
-    obj = LR.object_corners(tag_size)
-    Xw = np.concatenate([LR._world_corners(tag_map["T"][rows["id"][s]], obj) for s in active_slots])
-    uv = np.concatenate([rows["corners"][s].astype(np.float64).reshape(4, 2) for s in active_slots])
-    return Xw, uv
-
-
-def tag_points(corners8, tag_size):
-    """a tag's own corners (4, 3) in its frame and its image corners (4, 2)"""
-    return np.c_[LR.object_corners(tag_size), np.zeros(4)], np.asarray(corners8, dtype=np.float64).reshape(4, 2)

@@ -23,7 +23,7 @@ def assert_same(got, want, obs, rec, Kc=K, dist=None, tol=1e-9):
         assert abs(g["rms_px"] - w["rms_px"]) <= 1e-6 * max(1.0, w["rms_px"])
         assert abs(g["rms_seed_px"] - w["rms_seed_px"]) <= 1e-6 * max(1.0, w["rms_seed_px"])
         if g["seed_slot"] != w["seed_slot"]:
-            sc = LR.candidate_scores(obs[f], rec, Kc, dist, LC.TAG_INNER)
+            sc = LR.candidate_scores(LR.OneCamera(LR.camera(Kc, dist)), obs[f], rec, LC.TAG_INNER)
             assert g["seed_slot"] in sc and abs(sc[g["seed_slot"]] - sc[w["seed_slot"]]) <= 1e-9 * max(1.0, sc[w["seed_slot"]]), (f, g["seed_slot"], w["seed_slot"])
 
 

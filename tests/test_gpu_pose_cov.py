@@ -1,9 +1,6 @@
 """Pose covariance on the device (asl_localize_cov_frames_device / asl_localize_cov_batch in k_localize.inc,
-asl_pose_cov_device / asl_solve_pnp_cov_batch in k_posecov.inc) against the NumPy statement tests/pose_cov_ref.py.
-
-Bound on the covariance, per element: |C_gpu - C_ref|_ij <= 600 eps kappa sqrt(C_ii C_jj), kappa the 2-norm condition
-number of the Jacobi-scaled reference normal matrix (a backward-stable Cholesky inverse errs by a small multiple of
-n eps kappa; 600 = 100 n).  Every compared pose must have 600 eps kappa <= 1e-6, which the test asserts as well."""
+asl_pose_cov_device / asl_solve_pnp_cov_batch in k_posecov.inc) against the NumPy statement (localize_ref.pose_cov over
+tests/pose_cov_ref.py), to the covariance bar of solver_checks.assert_cov_close."""
 import ctypes as C
 
 import numpy as np
@@ -11,15 +8,14 @@ import pytest
 
 import localize_cases as LC
 import localize_ref as LR
-import pose_cov_ref as PC
 import solver_edge_cases as SE
 from aprilslam_amd import _lib, synth
 from aprilslam_amd.localize import CAM_POSE_DTYPE, TagMap, pose_std
+from solver_checks import assert_cov_close
 
 pytestmark = pytest.mark.gpu
 
 K = synth.camera_matrix(LC.W, LC.H, 45.0)
-EPS = np.finfo(np.float64).eps
 DIST5 = np.array([-0.12, 0.05, 0.001, -0.0015, 0.01])
 SIGMA = 0.5            # the given sigma of the comparisons
 NOISE = 0.2            # corner noise (px) of the copies the estimated sigma is compared on
@@ -46,36 +42,24 @@ def noisy(obs, seed):
     return out
 
 
-def assert_cov_close(got, ref, H, what):
-    kappa = PC.scaled_condition(H)
-    tol = 600 * EPS * kappa
-    assert tol <= 1e-6, (what, kappa)
-    s = np.sqrt(np.diag(ref))
-    err = np.abs(got - ref) / np.outer(s, s)
-    assert err.max() <= tol, (what, err.max(), tol)
-    assert np.array_equal(got, got.T), what
-
-
 def check_localize_cov(obs, rec, dist, gate, sigma_px, out, cov, compare_cov):
     """device records against the statement evaluated at the device's own pose on the statement's active set"""
     traces = []
     want = LR.localize(obs, rec, K, dist, LC.TAG_INNER, gate, traces=traces)
-    cam = LR.camera(K, dist)
+    one = LR.OneCamera(LR.camera(K, dist))
     for f, (g, w, c) in enumerate(zip(out, want, cov)):
         assert g["status"] == w["status"] and g["n_rejected"] == w["n_rejected"] and g["n_tags"] == w["n_tags"], f
         if g["status"] != 0:
             assert c["status"] == 1 and c["dof"] == 0 and c["sigma_px"] == sigma_px and not c["cov"].any(), f
             continue
-        part = [s for s, o in enumerate(obs[f]) if (o["flags"] & 1) and 0 <= o["id"] < len(rec) and rec["valid"][o["id"]]]
-        active = [s for s in part if s not in traces[f]["dropped"]]
-        Xw, uv = PC.frame_points(obs[f], rec, LC.TAG_INNER, active)
+        Xw, uv, ci = LR.frame_points(one, obs[f], rec, LC.TAG_INNER, traces[f]["active"])
         R = g["T"][:3, :3].T
         t = -(R @ g["T"][:3, 3])
-        ref, sig, dof, status = PC.pose_cov(cam, R, t, Xw, uv, sigma_px, True)
+        ref, sig, dof, status = LR.pose_cov(one, R, t, Xw, uv, ci, sigma_px)
         assert status == 0 and c["status"] == 0 and c["dof"] == dof == 8 * g["n_tags"] - 6, f
         assert abs(c["sigma_px"] - sig) <= 1e-6 * sig, (f, c["sigma_px"], sig)
         if compare_cov:
-            assert_cov_close(c["cov"], ref, LR.linearise(cam, R, t, Xw, uv)[1], f)
+            assert_cov_close(c["cov"], ref, one.linearise(R, t, Xw, uv, ci)[1], f)
 
 
 @pytest.mark.parametrize("case", LOC_NAMES)
@@ -146,9 +130,9 @@ def check_pnp_cov(corners, T, posed, dist, sigma_px, cov, compare_cov):
         if not posed[i]:
             assert c["status"] == 1 and c["dof"] == 0 and c["sigma_px"] == sigma_px and not c["cov"].any(), i
             continue
-        Xw, uv = PC.tag_points(corners[i].reshape(8), LC.TAG_INNER)
+        Xw, uv = LR.tag_points(corners[i].reshape(8), LC.TAG_INNER)
         R, t = T[i][:3, :3], T[i][:3, 3]
-        ref, sig, dof, status = PC.pose_cov(cam, R, t, Xw, uv, sigma_px, False)
+        ref, sig, dof, status = LR.pose_cov(LR.OneCamera(cam), R, t, Xw, uv, None, sigma_px, False)
         assert status == 0 and c["status"] == 0 and c["dof"] == dof == 2, i
         assert abs(c["sigma_px"] - sig) <= 1e-6 * sig, (i, c["sigma_px"], sig)
         if compare_cov:

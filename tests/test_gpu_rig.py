@@ -3,36 +3,27 @@ k_rig.inc) against the NumPy statement (tests/rig_ref.py), against the single-ca
 on rendered frames against the renderer's ground truth.
 
 Bars: pose, rms_px, rms_seed_px 1e-9 relative on the cases of rig_cases (that of test_gpu_localize's
-test_kernel_matches_the_statement_on_the_cpu_cases); covariance per element 600 eps kappa (test_gpu_pose_cov).  A frame
-where a trial is accepted on one side and rejected on the other at rounding level may be held to 1e-7 if it is named in
-LOOSE_FRAMES; at most 3 % of the compared frames may be."""
+test_kernel_matches_the_statement_on_the_cpu_cases); covariance per element 600 eps kappa
+(solver_checks.assert_cov_close).  A frame where a trial is accepted on one side and rejected on the other at rounding
+level may be held to 1e-7 if it is named in LOOSE_FRAMES; at most 3 % of the compared frames may be."""
 import numpy as np
 import pytest
 
 import localize_cases as LC
-import pose_cov_ref as PC
+import localize_ref as LR
 import rig_cases as RC
 import rig_ref as RR
 from aprilslam_amd import _lib, synth
 from aprilslam_amd.localize import CAM_POSE_DTYPE, TagMap
 from aprilslam_amd.rig import Rig, RigCamera
+from solver_checks import assert_cov_close, dev_bytes, rel
 
 pytestmark = pytest.mark.gpu
 
 K = synth.camera_matrix(LC.W, LC.H, 45.0)
-EPS = np.finfo(np.float64).eps
 SIGMA = 0.5
 LOOSE_FRAMES = set()           # (case name, frame) held to 1e-7 instead of 1e-9: none
 LOOSE_SINGLE = set()           # the same for the one-camera comparison on localize_cases.cpu_cases: none
-
-
-def dev_bytes(a, dev):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
-
-
-def rel(a, b):
-    return abs(a - b) / max(1.0, abs(b))
 
 
 def test_loose_frames_are_few():
@@ -50,7 +41,7 @@ def test_kernel_matches_the_statement(gpu_detector, name):
     assert out.tobytes() == plain.tobytes()
     traces = []
     want = RR.localize(obs, rec, rig, ts, gate, traces=traces)
-    table = RR.rig_table(rig)
+    model = RR.RigModel(rig)
     for f, (g, w, cv) in enumerate(zip(out, want, cov)):
         tol = 1e-7 if (name, f) in LOOSE_FRAMES else 1e-9
         print(name, f, "pose %.2e rms %.2e seed rms %.2e" % (LC.rel_err(g["T"], w["T"]), rel(g["rms_px"], w["rms_px"]),
@@ -61,18 +52,12 @@ def test_kernel_matches_the_statement(gpu_detector, name):
         assert rel(g["rms_px"], w["rms_px"]) <= tol and rel(g["rms_seed_px"], w["rms_seed_px"]) <= tol, f
         assert g["status"] == 0
         # the covariance: the statement at the device's own pose on the statement's active set
-        Xw, uv, ci = RR.frame_points(obs[:, f], rec, ts, traces[f]["active"])
+        Xw, uv, ci = LR.frame_points(model, obs[:, f], rec, ts, traces[f]["active"])
         R = g["T"][:3, :3].T
         t = -(R @ g["T"][:3, 3])
-        ref, sig, dof, status = RR.pose_cov(table, R, t, Xw, uv, ci, SIGMA)
+        ref, sig, dof, status = LR.pose_cov(model, R, t, Xw, uv, ci, SIGMA)
         assert status == 0 and cv["status"] == 0 and cv["dof"] == dof == 8 * g["n_tags"] - 6 and cv["sigma_px"] == SIGMA, f
-        kappa = PC.scaled_condition(RR.linearise(table, R, t, Xw, uv, ci)[1])
-        bar = 600 * EPS * kappa
-        assert bar <= 1e-6, (f, kappa)
-        s = np.sqrt(np.diag(ref))
-        err = np.abs(cv["cov"] - ref) / np.outer(s, s)
-        assert err.max() <= bar, (f, err.max(), bar)
-        assert np.array_equal(cv["cov"], cv["cov"].T), f
+        assert_cov_close(cv["cov"], ref, model.linearise(R, t, Xw, uv, ci)[1], f)
 
 
 def test_statuses_and_estimated_sigma(gpu_detector):
@@ -212,7 +197,7 @@ def test_device_block_matches_the_statement(rig_block):
         assert LC.rel_err(g["T"], w["T"]) <= 1e-7, (f, LC.rel_err(g["T"], w["T"]))
         assert rel(g["rms_px"], w["rms_px"]) <= 1e-6 and rel(g["rms_seed_px"], w["rms_seed_px"]) <= 1e-6, f
         if g["seed_slot"] != w["seed_slot"]:
-            sc = RR.candidate_scores(obs[:, f], rec, rig, LC.TAG_INNER)
+            sc = LR.candidate_scores(RR.RigModel(rig), obs[:, f], rec, LC.TAG_INNER)
             assert g["seed_slot"] in sc and abs(sc[g["seed_slot"]] - sc[w["seed_slot"]]) <= 1e-9 * max(1.0, sc[w["seed_slot"]]), f
     print("rig kernel against the statement on %d rendered frames: worst pose difference %.2e" % (len(want), worst))
     assert (out[0]["status"] == 0).all() and (out[0]["n_tags"] >= 20).all()

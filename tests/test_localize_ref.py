@@ -48,6 +48,23 @@ def test_exact_corners_recover_the_pose(scene):
         assert 0 <= out["seed_slot"] < len(obs)
 
 
+def test_statuses_without_tags_or_seeds(scene):
+    """the single-camera twin of test_rig_ref's: three exact frames, the covariance statuses through sigma_px"""
+    tags, tm = scene
+    obs = np.stack([LC.exact_frame(tags, pos, rot, K) for pos, rot in LC.trajectory(16)[:3]])
+    obs["flags"][0] = 0               # frame 0: no slot taking part -> status 1
+    obs["flags"][1] &= 1              # frame 1: nothing with a PnP -> status 2
+    traces = []
+    out, cov = LR.localize(obs, tm.as_records(), K, None, LC.TAG_INNER, 0.0, sigma_px=0.5, traces=traces)
+    assert list(out["status"]) == [1, 2, 0] and list(cov["status"]) == [1, 1, 0]
+    for f in (0, 1):
+        assert np.array_equal(out["T"][f], np.eye(4)) and out["n_tags"][f] == 0 and out["seed_slot"][f] == -1
+        assert cov["dof"][f] == 0 and cov["sigma_px"][f] == 0.5 and not cov["cov"][f].any()
+        assert traces[f] == {"top_k": [], "dropped": [], "gate_rms": [], "active": []}
+    assert cov["dof"][2] == 8 * out["n_tags"][2] - 6 and cov["sigma_px"][2] == 0.5 and len(traces[2]["active"]) == out["n_tags"][2]
+    assert out.tobytes() == LR.localize(obs, tm.as_records(), K, None, LC.TAG_INNER, 0.0).tobytes()
+
+
 @pytest.fixture(scope="module")
 def oracle_frames(scene):
     """the first 8 of 16 bench trajectory poses, rendered on the host, through the CPU oracle detector + PnP"""

@@ -1,6 +1,6 @@
-"""The NumPy statement of the pose covariance (tests/pose_cov_ref.py) against what it claims: the convention map against
-finite differences of the pose composition itself, and the covariance against the scatter of solved poses around the
-truth under corner noise of a known sigma."""
+"""The NumPy statement of the pose covariance (tests/pose_cov_ref.py, through localize_ref.pose_cov) against what it
+claims: the convention map against finite differences of the pose composition itself, and the covariance against the
+scatter of solved poses around the truth under corner noise of a known sigma."""
 import numpy as np
 
 import localize_cases as LC
@@ -11,6 +11,7 @@ from aprilslam_amd.localize import TagMap
 
 K = synth.camera_matrix(LC.W, LC.H, 45.0)
 CAM = LR.camera(K, None)
+ONE = LR.OneCamera(CAM)
 N_TRIALS = 500
 BOUND = 5 * np.sqrt(12.0 / N_TRIALS)    # chi-square(6): variance 12; five standard errors of the mean of N_TRIALS
 
@@ -23,7 +24,7 @@ def multi_tag_scene():
     obs = LC.exact_frame(tags, pos, rot, K)
     slots = [s for s in range(len(obs)) if obs["id"][s] >= 0]
     assert len(slots) >= 6
-    Xw, _ = PC.frame_points(obs, rec, LC.TAG_INNER, slots)
+    Xw, _, _ = LR.frame_points(ONE, obs, rec, LC.TAG_INNER, slots)
     Tcw = np.linalg.inv(LC.world_from_camera(pos, rot))
     R, t = Tcw[:3, :3], Tcw[:3, 3]
     return R, t, Xw, LR.project(CAM, Xw @ R.T + t)
@@ -71,7 +72,7 @@ def mahalanobis_trials(scene, sigma, wfc, seed, sigma_arg):
     for _ in range(N_TRIALS):
         uv = uv0 + rng.normal(scale=sigma, size=uv0.shape)
         R, t, _ = LR.lm(LR.corner_lin(CAM, Xw, uv), R0.copy(), t0.copy())
-        C, s, dof, status = PC.pose_cov(CAM, R, t, Xw, uv, sigma_arg, wfc)
+        C, s, dof, status = LR.pose_cov(ONE, R, t, Xw, uv, None, sigma_arg, wfc)
         assert status == 0 and dof == 2 * len(Xw) - 6
         Re, pe = PC.output_pose(R, t, wfc)
         e = PC.pose_error(Re, pe, Rt, pt)
@@ -113,9 +114,9 @@ def test_status_1_and_2_give_zeros():
     Xw = np.tile(np.array([[1.0, 2.0, 0.0]]), (8, 1))
     uv = LR.project(CAM, Xw @ R.T + t) + 0.1
     for wfc in (True, False):
-        C, s, dof, status = PC.pose_cov(CAM, R, t, Xw, uv, 0.5, wfc)
+        C, s, dof, status = LR.pose_cov(ONE, R, t, Xw, uv, None, 0.5, wfc)
         assert status == 2 and dof == 10 and not C.any()
     R, t, Xw, uv = multi_tag_scene()
-    C, s, dof, status = PC.pose_cov(CAM, R, t, Xw, uv, 0.5, True)
+    C, s, dof, status = LR.pose_cov(ONE, R, t, Xw, uv, None, 0.5, True)
     assert status == 0 and (np.diag(C) > 0).all()
     assert np.abs(C - C.T).max() <= 1e-12 * np.abs(C).max()
