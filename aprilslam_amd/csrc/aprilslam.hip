@@ -245,7 +245,7 @@ extern "C" int asl_detector_create(const char *family, int nthreads, int maxhamm
     hipLaunchKernelGGL(k_weight_table, dim3((WEIGHT_TABLE_N + 255) / 256), dim3(256), 0, 0, d->wtab.p);
     if (hipDeviceSynchronize() != hipSuccess) return fail(ASL_EDEVICE, "weight table kernel failed");
     // class-3 quad fit uses 64 KB of dynamic LDS on top of a few hundred static bytes
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fit_quads<256, true, CLASS3_CAP / 256>), hipFuncAttributeMaxDynamicSharedMemorySize, QUAD_LDS_BYTES(CLASS3_CAP));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fit_quads<256, CLASS3_CAP / 256>), hipFuncAttributeMaxDynamicSharedMemorySize, QUAD_LDS_BYTES(CLASS3_CAP));
     *out = d.release();
     return ASL_OK;
 }
@@ -403,7 +403,7 @@ template <int BLOCK, int CAP>
 static void launch_fit(asl_detector *d, const Geom &g, int cls, unsigned int grid, hipStream_t st)
 {
     const int want_rev = d->fam.reversed_border ? 1 : 0, want_norm = d->fam.reversed_border ? 0 : 1;
-    hipLaunchKernelGGL((k_fit_quads<BLOCK, (CAP > 0), CAP / BLOCK>), dim3(grid), dim3(BLOCK), CAP > 0 ? QUAD_LDS_BYTES(CAP) : 0, st, d->clusters.p,
+    hipLaunchKernelGGL((k_fit_quads<BLOCK, CAP / BLOCK>), dim3(grid), dim3(BLOCK), CAP > 0 ? QUAD_LDS_BYTES(CAP) : 0, st, d->clusters.p,
                        d->class_lists.p + (size_t)cls * d->max_clusters, d->counters.p, cls, d->max_clusters, CAP, d->points.p, d->dgray.p, g,
                        tag_width(d, g), want_rev, want_norm, d->scratch.p, d->quads.p, d->wtab.p, d->side_mom.p);
 }
