@@ -41,7 +41,7 @@ RIG_CAMERA_DTYPE = np.dtype([("K", "<f8", (3, 3)), ("dist", "<f8", (5,)), ("E", 
 assert RIG_CAMERA_DTYPE.itemsize == 216
 
 EXPORTS = [
-    "asl_detector_create", "asl_detector_destroy", "asl_detector_set_id_limit", "asl_detector_set_pnp_both_minima", "asl_last_error", "asl_version", "asl_detect_gray_u8",
+    "asl_detector_create", "asl_detector_destroy", "asl_detector_set_id_limit", "asl_detector_set_pnp_both_minima", "asl_detector_set_quad_sigma", "asl_blur_taps", "asl_last_error", "asl_version", "asl_detect_gray_u8",
     "asl_detect_bgr_u8", "asl_detect_batch_u8", "asl_detect_batch_pose_u8", "asl_detect_batch_device", "asl_submit_batch_device", "asl_collect_batch", "asl_collect_batch_view", "asl_solve_pnp_batch", "asl_gn_solve", "asl_pack_observations_device", "asl_graph_frames_device", "asl_graph_picks_device", "asl_render_frames_device",
     "asl_localize_frames_device", "asl_localize_batch", "asl_localize_cov_frames_device", "asl_localize_cov_batch",
     "asl_pose_cov_device", "asl_solve_pnp_cov_batch", "asl_calibrate_frames_device", "asl_calibrate_batch",
@@ -77,6 +77,8 @@ def load():
     L.asl_detector_destroy.restype = None
     L.asl_detector_set_id_limit.argtypes = [vp, i32]
     L.asl_detector_set_pnp_both_minima.argtypes = [vp, i32]
+    L.asl_detector_set_quad_sigma.argtypes = [vp, C.c_float]
+    L.asl_blur_taps.argtypes = [C.c_float, u8p, i32, C.POINTER(i32)]
     L.asl_detect_gray_u8.argtypes = [vp, vp, i32, i32, i32, vp, i32, C.POINTER(i32)]
     L.asl_detect_bgr_u8.argtypes = [vp, vp, i32, i32, i32, vp, i32, C.POINTER(i32)]
     L.asl_detect_batch_u8.argtypes = [vp, C.POINTER(vp), i32, i32, i32, i32, i32, vp, i32, C.POINTER(i32), C.POINTER(i32)]
@@ -124,6 +126,14 @@ def check(rc):
 
 
 _DP = C.POINTER(C.c_double)
+
+
+def blur_taps(quad_sigma):
+    """asl_blur_taps: the uint8 taps k_quad_blur uses for this quad_sigma (empty: off).  A host function: no GPU needed."""
+    taps = np.zeros(15, dtype=np.uint8)
+    ksz = C.c_int()
+    check(load().asl_blur_taps(float(quad_sigma), taps.ctypes.data_as(C.POINTER(C.c_uint8)), len(taps), C.byref(ksz)))
+    return taps[:ksz.value].copy()
 
 
 def _ptr(addr):
@@ -191,6 +201,11 @@ class Detector:
     def set_pnp_both_minima(self, enabled):
         """asl_detector_set_pnp_both_minima: off = the reference's (cv2's) single minimum, on = the better of the two planar poses"""
         check(self._L.asl_detector_set_pnp_both_minima(self._h, 1 if enabled else 0))
+
+    def set_quad_sigma(self, quad_sigma):
+        """asl_detector_set_quad_sigma: Gaussian blur (> 0) or sharpening (< 0) of the decimated image from the next batch on;
+        0 = off.  |quad_sigma| < 4."""
+        check(self._L.asl_detector_set_quad_sigma(self._h, float(quad_sigma)))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -524,7 +539,7 @@ class Detector:
     def debug_image(self, what):
         c = self.debug_counters()
         B, sw, sh = int(c[0]), int(c[1]), int(c[2])
-        dt = np.uint8 if what in (0, 1) else np.uint32
+        dt = np.uint8 if what in (0, 1, 9) else np.uint32
         buf = np.zeros((B, sh, sw), dtype=dt)
         n = C.c_size_t()
         check(self._L.asl_debug_fetch(self._h, what, buf.ctypes.data, buf.nbytes, C.byref(n)))

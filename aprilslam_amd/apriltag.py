@@ -21,7 +21,10 @@ class apriltag(object):
             raise TypeError("family must be a string")
         try:
             # id_limit=None: only the ids the reference pins (0..4) are decoded; 0 opens the build-defined rest
-            self._det = _lib.Detector(family, threads, maxhamming, decimate, blur, refine_edges, device, id_limit)
+            # blur (upstream's quad_sigma) goes in through the setter: asl_detector_create itself takes 0 only
+            self._det = _lib.Detector(family, threads, maxhamming, decimate, 0.0, refine_edges, device, id_limit)
+            if blur != 0:
+                self._det.set_quad_sigma(blur)
         except _lib.AslError as e:
             # upstream raises RuntimeError for an unrecognised family / bad options
             raise RuntimeError(str(e))

@@ -19,6 +19,7 @@
 #include "k_wave.inc"
 
 #include "k_threshold.inc"
+#include "k_blur.inc"
 #include "k_cc.inc"
 #include "k_cluster.inc"
 #include "k_seg.inc"
@@ -85,6 +86,7 @@ struct asl_detector {
     int decimate = 2;
     int refine = 1;
     int pnp_both_minima = 0;
+    BlurTaps blur{};  // asl_detector_set_quad_sigma; r = 0: off
     FamilyDev fam;
     DevBuf<unsigned long long> codes;        // the family's code book (FamilyDev::codes)
     DevBuf<unsigned short> idx_start;        // code-book index of the family (FamilyDev), rebuilt when the id limit changes
@@ -98,6 +100,8 @@ struct asl_detector {
 
     // workspace
     DevBuf<uint8_t> in, dgray, tmin, tmax, tcut;
+    DevBuf<uint8_t> bgray;               // k_quad_blur's output; allocated by the first batch that runs with quad_sigma set
+    const uint8_t *qgray = nullptr;      // the image the last enqueued batch thresholds and fits on: dgray, or bgray under quad_sigma
     DevBuf<uint8_t> dbg_thresh;         // asl_debug_fetch only: the threshold image as bytes
     DevBuf<unsigned int> dbg_labels;    // asl_debug_fetch only: per-pixel labels
     DevBuf<unsigned int> parent, sizes;
@@ -217,7 +221,7 @@ extern "C" int asl_detector_create(const char *family, int nthreads, int maxhamm
         return fail(ASL_EINVAL, "unknown tag family '%s' (supported: tagStandard41h12)", family ? family : "(null)");
     if (!(decimate >= 1.0f) || decimate != std::floor(decimate) || decimate > 8.0f)
         return fail(ASL_EINVAL, "decimate must be an integer value in [1, 8] (got %g)", (double)decimate);
-    if (blur != 0.0f) return fail(ASL_EINVAL, "blur (quad_sigma) != 0 is not supported (the reference never sets it)");
+    if (blur != 0.0f) return fail(ASL_EINVAL, "blur must be 0 here: set quad_sigma with asl_detector_set_quad_sigma");
     if (maxhamming < 0 || maxhamming > 3) return fail(ASL_EINVAL, "maxhamming must be in [0, 3]");
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
@@ -266,6 +270,55 @@ extern "C" int asl_detector_set_id_limit(asl_detector *d, int n_ids)
     d->fam.ncodes = n_ids <= 0 ? kTag41h12NCodes : n_ids;
     HIPCHK(hipSetDevice(d->device));
     if (build_code_index(d)) return fail(ASL_ENOMEM, "code-book index allocation failed");
+    return ASL_OK;
+}
+
+// The taps of tests/blur_ref.py: ksz = int(4 * |sigma|) in float32, made odd; floor(255 * normalised Gaussian) in double.
+// Returns ksz (0: off), or -1 for a sigma the detector does not take.
+static int blur_kernel(float quad_sigma, uint8_t taps[2 * BLUR_HALO + 1])
+{
+    if (!std::isfinite(quad_sigma) || !(std::fabs(quad_sigma) < 4.0f)) return -1;
+    const float sigma = std::fabs(quad_sigma);
+    int ksz = (int)(4.0f * sigma);
+    if ((ksz & 1) == 0) ksz++;
+    if (ksz <= 1) return 0;
+    double dk[2 * BLUR_HALO + 1], sum = 0.0;
+    for (int i = 0; i < ksz; i++) {
+        const double x = (double)(i - ksz / 2) / (double)sigma;
+        dk[i] = std::exp(-0.5 * (x * x));
+        sum += dk[i];
+    }
+    for (int i = 0; i < ksz; i++) taps[i] = (uint8_t)std::floor(dk[i] / sum * 255.0);
+    return ksz;
+}
+
+extern "C" int asl_blur_taps(float quad_sigma, uint8_t *taps, int max_taps, int *ksz)
+{
+    if (!ksz) return fail(ASL_EINVAL, "ksz is NULL");
+    uint8_t k[2 * BLUR_HALO + 1];
+    const int n = blur_kernel(quad_sigma, k);
+    if (n < 0) return fail(ASL_EINVAL, "quad_sigma must be finite and |quad_sigma| < 4 (got %g)", (double)quad_sigma);
+    if (n > 0 && (!taps || max_taps < n)) return fail(ASL_EINVAL, "taps too small: need %d (got %d)", n, taps ? max_taps : 0);
+    for (int i = 0; i < n; i++) taps[i] = k[i];
+    *ksz = n;
+    return ASL_OK;
+}
+
+extern "C" int asl_detector_set_quad_sigma(asl_detector *d, float quad_sigma)
+{
+    if (!d) return fail(ASL_EINVAL, "detector is NULL");
+    uint8_t k[2 * BLUR_HALO + 1];
+    const int n = blur_kernel(quad_sigma, k);
+    if (n < 0) return fail(ASL_EINVAL, "quad_sigma must be finite and |quad_sigma| < 4 (got %g)", (double)quad_sigma);
+    if (d->pending) return fail(ASL_EINVAL, "a batch is in flight on this detector");
+    BlurTaps b{};
+    b.r = n / 2;  // 0: off
+    b.sharpen = quad_sigma < 0.0f ? 1 : 0;
+    for (int i = 0; i < n; i++) {  // centred in 15 bytes (k_blur.inc)
+        const int u = BLUR_HALO - b.r + i;
+        b.k[u >> 2] |= (unsigned int)k[i] << (8 * (u & 3));
+    }
+    d->blur = b;
     return ASL_OK;
 }
 
@@ -345,7 +398,9 @@ static int ensure_workspace(asl_detector *d, const Geom &g)
     d->max_points = (unsigned int)std::min<unsigned long long>(mp, 0xFFFFFFF0ull);
     d->max_dets = (unsigned int)std::min<unsigned long long>((unsigned long long)B * d->dets_per_frame, 0x7FFFFFFFull);
     int bad = 0;
+    d->qgray = nullptr;  // set by the enqueue; the buffers below may move
     bad |= d->dgray.ensure(total);
+    if (d->blur.r) bad |= d->bgray.ensure(total);
     bad |= d->tmin.ensure(B * (size_t)std::max(1, g.tw * g.th) + 8);  // + 8: k_tile_cut's last 8-byte load
     bad |= d->tmax.ensure(B * (size_t)std::max(1, g.tw * g.th) + 8);
     bad |= d->tcut.ensure(B * (size_t)std::max(1, g.tw * g.th));
@@ -404,7 +459,7 @@ static void launch_fit(asl_detector *d, const Geom &g, int cls, unsigned int gri
 {
     const int want_rev = d->fam.reversed_border ? 1 : 0, want_norm = d->fam.reversed_border ? 0 : 1;
     hipLaunchKernelGGL((k_fit_quads<BLOCK, CAP / BLOCK>), dim3(grid), dim3(BLOCK), CAP > 0 ? QUAD_LDS_BYTES(CAP) : 0, st, d->clusters.p,
-                       d->class_lists.p + (size_t)cls * d->max_clusters, d->counters.p, cls, d->max_clusters, CAP, d->points.p, d->dgray.p, g,
+                       d->class_lists.p + (size_t)cls * d->max_clusters, d->counters.p, cls, d->max_clusters, CAP, d->points.p, d->qgray, g,
                        tag_width(d, g), want_rev, want_norm, d->scratch.p, d->quads.p, d->wtab.p, d->side_mom.p);
 }
 
@@ -453,6 +508,14 @@ static int enqueue_detect(asl_detector *d, const uint8_t *d_frames, const Geom &
     } else
         hipLaunchKernelGGL((g.channels == 1 ? k_decimate_minmax<1> : k_decimate_minmax<3>), dim3((g.sw + 63) / 64, (thx + 3) / 4, B), blk, 0, st, d_frames, g, d->dgray.p, d->tmin.p, d->tmax.p);
 
+    d->qgray = d->dgray.p;
+    if (d->blur.r) {  // quad_sigma: the tile cut, the threshold and the quad fit read the blurred image from here on
+        STAGE("k_quad_blur");
+        hipLaunchKernelGGL(k_quad_blur, dim3((g.sw + BLUR_TW - 1) / BLUR_TW, (g.sh + BLUR_TH - 1) / BLUR_TH, B), dim3(256), 0, st, d->dgray.p, g, d->blur,
+                           d->bgray.p, d->tmin.p, d->tmax.p);
+        d->qgray = d->bgray.p;
+    }
+
     const int nwx = seg_nwx(g), pty = seg_point_tiles_y(g);
     const size_t nwords = (size_t)B * g.sh * nwx;
     STAGE("k_tile_cut");
@@ -461,7 +524,7 @@ static int enqueue_detect(asl_detector *d, const uint8_t *d_frames, const Geom &
     STAGE("k_seg_tile");
     {
         const int ntiles = nwx * ((g.sh + SEG_TH - 1) / SEG_TH);
-        hipLaunchKernelGGL(k_seg_tile, dim3((ntiles + SEG_TILE_WAVES - 1) / SEG_TILE_WAVES, 1, B), dim3(64 * SEG_TILE_WAVES), 0, st, d->dgray.p, d->tcut.p, g, nwx, ntiles,
+        hipLaunchKernelGGL(k_seg_tile, dim3((ntiles + SEG_TILE_WAVES - 1) / SEG_TILE_WAVES, 1, B), dim3(64 * SEG_TILE_WAVES), 0, st, d->qgray, d->tcut.p, g, nwx, ntiles,
                            d->wmask.p, d->bmask.p, d->parent.p, d->sizes.p, d->rootmask.p, d->seg_edges.p, d->dense_seg.p, d->counters.p);
         // tiles with more runs or links than the common launch's tables hold (none in ordinary frames: the launch finds an empty list)
         hipLaunchKernelGGL(k_seg_tile_dense, dim3(1024), dim3(64), 0, st, g, nwx, ntiles, d->wmask.p, d->bmask.p, d->parent.p, d->sizes.p,

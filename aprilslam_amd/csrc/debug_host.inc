@@ -40,11 +40,12 @@ extern "C" int asl_debug_fetch(asl_detector *d, int what, void *dst, size_t byte
     HIPCHK(hipSetDevice(d->device));
     const Geom &g = d->last;
     size_t total = (size_t)g.nframes * g.npix;
-    if (what >= 0 && what <= 3 && total == 0) return fail(ASL_EINVAL, "no batch has run yet");
+    if (((what >= 0 && what <= 3) || what == 9) && total == 0) return fail(ASL_EINVAL, "no batch has run yet");
     switch (what) {
-    case 0: {
+    case 0:    // the image the threshold read: k_quad_blur's under quad_sigma
+    case 9: {  // the decimation's own output (7 and 8 are retired numbers and stay unknown)
         if (bytes < total) return fail(ASL_EINVAL, "dst too small: need %zu bytes", total);
-        HIPCHK(hipMemcpy(dst, d->dgray.p, total, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(dst, what == 0 ? d->qgray : d->dgray.p, total, hipMemcpyDeviceToHost));
         *n_items = total;
         return ASL_OK;
     }

@@ -28,8 +28,9 @@ def rodrigues(rvec):
 class TagDetector:
     """Handles AprilTag detection and pose estimation (GPU-backed)."""
 
-    def __init__(self, camera_params, tag_type="tagStandard41h12", tag_size=0.06, device=0, id_limit=None):
-        self.detector = apriltag(tag_type, device=device, id_limit=id_limit)
+    def __init__(self, camera_params, tag_type="tagStandard41h12", tag_size=0.06, device=0, id_limit=None, quad_sigma=0.0):
+        """quad_sigma: the detector's blur (> 0) or sharpening (< 0) of the decimated image; the reference leaves it 0."""
+        self.detector = apriltag(tag_type, blur=quad_sigma, device=device, id_limit=id_limit)
         self.tag_size = tag_size
         self.camera_matrix = camera_params['camera_matrix']
         self.dist_coeffs = camera_params['dist_coeffs']

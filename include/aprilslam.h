@@ -63,7 +63,8 @@ typedef struct {
 
 /* Replaces `apriltag(family, threads=1, maxhamming=1, decimate=2.0, blur=0.0, refine_edges=True)`
    (reference tag_detector.py:18 passes the family only; the wrapper's defaults apply).
-   decimate must be an integer value >= 1; blur must be 0 (the reference never sets either).
+   decimate must be an integer value >= 1 (the reference never sets it).  blur must be 0 here: upstream's blur
+   (quad_sigma) is set on the created detector with asl_detector_set_quad_sigma.
    device = HIP device ordinal. */
 int asl_detector_create(const char *family, int nthreads, int maxhamming, float decimate, float blur,
                         int refine_edges, int device, asl_detector **out);
@@ -79,6 +80,17 @@ int asl_detector_set_id_limit(asl_detector *det, int n_ids);
    enabled = 1 refines the mirrored pose as well and keeps the one with the lower reprojection error (IPPE's
    two-solution test): better orientation for small, near-frontal tags, but no longer what the reference computes. */
 int asl_detector_set_pnp_both_minima(asl_detector *det, int enabled);
+/* Upstream's quad_sigma (the `blur` keyword of its Python wrapper): > 0 blurs the decimated image with a Gaussian of that
+   sigma before the threshold, < 0 sharpens it (2 * image - blurred, clipped); 0 = off, the default.  The threshold,
+   the segmentation and the quad fit then read the filtered image; edge refinement and decoding keep sampling the
+   original frame, as upstream.  The kernel has ksz = int(4 * |quad_sigma|) taps, made odd; a sigma whose ksz is 1 is
+   accepted and is off.  ASL_EINVAL for a non-finite value, for |quad_sigma| >= 4 (ksz <= 15) and while a batch is pending
+   (between submit and collect).  Takes effect from the next batch, on every detect entry point. */
+int asl_detector_set_quad_sigma(asl_detector *det, float quad_sigma);
+/* The taps asl_detector_set_quad_sigma(quad_sigma) filters with: uint8 = floor(255 * normalised Gaussian), *ksz of them
+   (0 = off) into taps[max_taps].  A pure host function: no GPU, no detector.  ASL_EINVAL, nothing written, for a
+   quad_sigma the setter refuses or max_taps < *ksz. */
+int asl_blur_taps(float quad_sigma, uint8_t *taps, int max_taps, int *ksz);
 const char *asl_last_error(void);
 /* "aprilslam <version> gfx950 ..." */
 const char *asl_version(void);
@@ -410,11 +422,14 @@ int asl_render_frames_device(asl_detector *det, void *d_frames, int n_frames, in
    they may write into and return ASL_EINVAL, writing nothing, when it is too small; asl_stage_times fills at most max_n. */
 
 /* Copy an intermediate buffer of the last batch to host, for the parity tests.
-   what: 0 = decimated gray (u8, B*sh*sw)     1 = threshold image (u8, B*sh*sw)
+   what: 0 = decimated gray as the threshold read it: blurred / sharpened under quad_sigma (u8, B*sh*sw)
+         1 = threshold image (u8, B*sh*sw)
          2 = component labels (u32, B*sh*sw)  3 = component sizes by label (u32, B*sh*sw)
          4 = candidate quads (asl_debug_quad, count via *n_items)
          5 = stage counters (int64[18]: frames, sw, sh, clusters, points, quads, detections, ..., tiles of the two dense launches)
          6 = clusters handed to the quad fit (uint64[3] each: key, points, hash of the sorted point records), ordered by key
+         9 = decimated gray before quad_sigma's filter (u8, B*sh*sw); the same as 0 while quad_sigma is off
+         (7 and 8 named diagnostics that are gone; the numbers are not reused and stay ASL_EINVAL)
    bytes = capacity of dst in bytes; *n_items = number of elements written. */
 typedef struct {
     double p[4][2]; /* decimated-image pixel coordinates, before the full-resolution rescale */

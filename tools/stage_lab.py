@@ -2,7 +2,7 @@
 """Diagnostic: isolated per-kernel times of one detector batch on the bench scene, median over several
 synchronous batches, plus a checksum of the results (so that two builds can be compared for identical output).
 
-    ASL_LIB=build/libaprilslam_x.so python tools/stage_lab.py [--batch 1024] [--reps 9] [--decimate 2] [--tag NAME]
+    ASL_LIB=build/libaprilslam_x.so python tools/stage_lab.py [--batch 1024] [--reps 9] [--decimate 2] [--quad-sigma S] [--tag NAME]
 
 Prints one JSON line.  Nothing else runs on the GPU meanwhile, so the figures are the `*_isolated` ones of bench.py."""
 import argparse
@@ -19,7 +19,7 @@ import torch  # noqa: E402
 import bench  # noqa: E402
 from aprilslam_amd import _lib, synth  # noqa: E402
 
-SEG = ("k_hash_clear", "k_decimate_minmax", "k_tile_cut", "k_seg_tile", "k_seg_border", "k_seg_roots", "k_seg_points", "k_cluster_filter",
+SEG = ("k_hash_clear", "k_decimate_minmax", "k_quad_blur", "k_tile_cut", "k_seg_tile", "k_seg_border", "k_seg_roots", "k_seg_points", "k_cluster_filter",
        "k_point_place")
 
 
@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--decimate", type=int, default=2)
     ap.add_argument("--tag", default=os.path.basename(os.environ.get("ASL_LIB", "libaprilslam.so")))
+    ap.add_argument("--quad-sigma", type=float, default=0.0, help="blur (> 0) or sharpen (< 0) the decimated image: adds k_quad_blur")
     ap.add_argument("--blank", action="store_true", help="uniform frames: the floor of every kernel (no contrast anywhere)")
     ap.add_argument("--phases", action="store_true", help="print the phase-cycle shares (needs a -DASL_PHASE_TIMING build)")
     args = ap.parse_args()
@@ -38,6 +39,7 @@ def main():
     d_frames, gts, _ = bench.render_stream_device(det, B, dev)
     if args.blank:
         d_frames.fill_(128)
+    det.set_quad_sigma(args.quad_sigma)
     det.set_profiling(True)
     K = synth.camera_matrix(bench.W, bench.H)
     st = torch.cuda.current_stream(dev).cuda_stream
@@ -65,7 +67,7 @@ def main():
     kern = {k: v for k, v in med.items() if k.startswith("k_")}
     seg = sum(med.get(k, 0.0) for k in SEG)
     seg_bytes = bench.stage_algorithmic_read_bytes(bench.W, bench.H, 3, args.decimate)
-    out = {"tag": args.tag, "batch": B, "decimate": args.decimate, "n_dets": int(len(dets)), "digest_dets": digest[0], "digest_poses": digest[1],
+    out = {"tag": args.tag, "batch": B, "decimate": args.decimate, "quad_sigma": args.quad_sigma, "n_dets": int(len(dets)), "digest_dets": digest[0], "digest_poses": digest[1],
            "stage_ms": round(seg, 4), "stage_frac": round(seg_bytes * B / (seg * 1e-3) / 1e9 / bench.HBM_PEAK_GBS, 4),
            "all_kernels_ms": round(sum(kern.values()), 4),
            "median_ms": {k: round(v, 4) for k, v in med.items()}, "min_ms": {k: round(v, 4) for k, v in mn.items()},
