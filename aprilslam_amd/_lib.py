@@ -43,6 +43,7 @@ assert RIG_CAMERA_DTYPE.itemsize == 216
 EXPORTS = [
     "asl_detector_create", "asl_detector_destroy", "asl_detector_set_id_limit", "asl_detector_set_pnp_both_minima", "asl_detector_set_quad_sigma", "asl_blur_taps", "asl_last_error", "asl_version", "asl_detect_gray_u8",
     "asl_detect_bgr_u8", "asl_detect_batch_u8", "asl_detect_batch_pose_u8", "asl_detect_batch_device", "asl_submit_batch_device", "asl_collect_batch", "asl_collect_batch_view", "asl_solve_pnp_batch", "asl_gn_solve", "asl_pack_observations_device", "asl_graph_frames_device", "asl_graph_picks_device", "asl_render_frames_device",
+    "asl_rectify_frames_device", "asl_rectify_u8",
     "asl_localize_frames_device", "asl_localize_batch", "asl_localize_cov_frames_device", "asl_localize_cov_batch",
     "asl_pose_cov_device", "asl_solve_pnp_cov_batch", "asl_calibrate_frames_device", "asl_calibrate_batch",
     "asl_localize_rig_frames_device", "asl_localize_rig_cov_frames_device", "asl_localize_rig_batch", "asl_localize_rig_cov_batch",
@@ -93,6 +94,8 @@ def load():
     L.asl_gn_solve.argtypes = [vp, i32, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, dp, C.c_double, i32,
                                dp, dp, i32, dp]
     L.asl_render_frames_device.argtypes = [vp, vp, i32, i32, i32, i32, C.c_size_t, vp, i32, vp, i32, i32, C.c_double, dp, dp, i32, vp]
+    L.asl_rectify_frames_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.c_size_t, vp, i32, i32, i32, C.c_size_t, dp, dp, i32, dp, i32, vp]
+    L.asl_rectify_u8.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, dp, dp, i32, dp, i32]
     L.asl_pack_observations_device.argtypes = [vp, vp, i32, vp]
     L.asl_graph_frames_device.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp]
     L.asl_graph_picks_device.argtypes = [vp, vp, i32, i32, i32, vp, C.c_uint32, C.c_uint32, vp, i32, vp, vp]
@@ -303,6 +306,42 @@ class Detector:
         check(self._L.asl_render_frames_device(self._h, _ptr(frames_ptr), int(n_frames), int(width), int(height), int(stride),
                                                int(frame_pitch), _ptr(planes_ptr), int(max_planes), _ptr(textures_ptr),
                                                int(tw), int(th), float(half), Kp, dpp, nd, _ptr(stream)))
+
+    def rectify_frames_device(self, src_ptr, n_frames, channels, width, height, dst_ptr, K, dist, K_new=None, width_out=None,
+                              height_out=None, fill=0, stride=None, frame_pitch=None, stride_out=None, frame_pitch_out=None, stream=0):
+        """asl_rectify_frames_device: n_frames gray / BGR frames of the camera (K, dist) at the device address src_ptr -> the
+        gray frames of the pinhole K_new (default K) at dst_ptr, width_out x height_out (default: the source's size);
+        enqueued on `stream`, no wait.  K, dist and K_new are host arrays."""
+        width_out, height_out = int(width_out or width), int(height_out or height)
+        stride = stride or width * channels
+        frame_pitch = frame_pitch or stride * height
+        stride_out = stride_out or width_out
+        frame_pitch_out = frame_pitch_out or stride_out * height_out
+        keep, Kp, dpp, nd = _camera(K, dist, square=True)
+        Kn = None if K_new is None else np.ascontiguousarray(K_new, dtype=np.float64)
+        if Kn is not None and Kn.shape != (3, 3):
+            raise ValueError("K_new must be 3x3")
+        check(self._L.asl_rectify_frames_device(self._h, _ptr(src_ptr), int(n_frames), int(channels), int(width), int(height), int(stride),
+                                                int(frame_pitch), _ptr(dst_ptr), width_out, height_out, int(stride_out), int(frame_pitch_out),
+                                                Kp, dpp, nd, None if Kn is None else Kn.ctypes.data_as(_DP), int(fill), _ptr(stream)))
+
+    def rectify(self, image, K, dist, K_new=None, size=None, fill=0):
+        """asl_rectify_u8: one host image, (H, W) gray or (H, W, 3) BGR uint8, of the camera (K, dist) -> the (h_out, w_out)
+        gray image of the pinhole K_new (default K); size = (w_out, h_out), default the source's."""
+        a = np.ascontiguousarray(image)
+        if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3):
+            raise ValueError("expected an (H, W) or (H, W, 3) uint8 image")
+        h, w = a.shape[:2]
+        ch = 1 if a.ndim == 2 else 3
+        w_out, h_out = (w, h) if size is None else (int(size[0]), int(size[1]))
+        keep, Kp, dpp, nd = _camera(K, dist, square=True)
+        Kn = None if K_new is None else np.ascontiguousarray(K_new, dtype=np.float64)
+        if Kn is not None and Kn.shape != (3, 3):
+            raise ValueError("K_new must be 3x3")
+        out = np.empty((max(h_out, 0), max(w_out, 0)), dtype=np.uint8)
+        check(self._L.asl_rectify_u8(self._h, a.ctypes.data, ch, w, h, w * ch, out.ctypes.data, w_out, h_out, w_out, Kp, dpp, nd,
+                                     None if Kn is None else Kn.ctypes.data_as(_DP), int(fill)))
+        return out
 
     def pack_observations_device(self, out_ptr, max_tags, stream=0):
         """asl_pack_observations_device: the submitted batch's results as n_frames x max_tags asl_obs records at the

@@ -29,6 +29,7 @@
 #include "k_dedup.inc"
 #include "k_graph.inc"
 #include "k_render.inc"
+#include "k_rectify.inc"
 #include "k_gn.inc"
 #include "k_localize.inc"
 #include "k_posecov.inc"
@@ -127,6 +128,7 @@ struct asl_detector {
     DevBuf<uint8_t> loc_obs, loc_map;  // the *_batch solver entries: the host records' device copies (grow on demand)
     DevBuf<uint8_t> solve_out;         // the *_batch solver entries: their results, until copied back
     DevBuf<uint8_t> rig_cams;          // asl_localize_rig_batch: the device copy of the camera table
+    DevBuf<uint8_t> rect_src, rect_dst;  // asl_rectify_u8: the host image's device copy and the result (no batch reads them)
     DevBuf<uint8_t> cal_ws;  // calibration: per-frame workspace and state (k_calib.inc)
     DevBuf<uint8_t> map_ws, map_lm;  // map reconstruction (k_map.inc): sized by the input / by the problem
     hipStream_t copy_stream = nullptr, host_stream = nullptr;  // host frames: transfers and the chunks' kernels (detect_host_frames)
@@ -929,6 +931,98 @@ extern "C" int asl_render_frames_device(asl_detector *d, void *d_frames, int n_f
     hipLaunchKernelGGL(k_render, dim3((w + RENDER_TW - 1) / RENDER_TW, (h + 4 * RENDER_TH - 1) / (4 * RENDER_TH), (unsigned int)n_frames), dim3(64, 4), 0, (hipStream_t)stream, (uint8_t *)d_frames, w, h,
                        stride, frame_pitch, (const RenderPlane *)d_planes, max_planes, (const uint8_t *)d_textures, tw, th, half, cam);
     HIPCHK(hipGetLastError());
+    return ASL_OK;
+}
+
+// ---- lens rectification ahead of the detector (k_rectify.inc).  The detector supplies the device and, for the host form,
+// the staging buffers; no batch state is read or written, so both calls are legal while a batch is pending.
+struct RectifyCall {
+    const void *src; int n_frames, channels, w, h, stride; size_t frame_pitch;
+    void *dst; int w_out, h_out, stride_out; size_t frame_pitch_out;
+    const double *K, *dist; int n_dist; const double *K_new; int fill;
+};
+#define RECTIFY_MAX_DIM 16384  // the detector's own limit (make_geom); keeps every row offset and the launch grid in range
+
+// every argument check of the two entry points: nothing is written before it passes.  `device`: the frame pitches count.
+static int check_rectify_call(const asl_detector *d, const RectifyCall &c, bool device, RectifyCam *cam)
+{
+    if (!d || !c.src || !c.dst || !c.K) return fail(ASL_EINVAL, "NULL detector, source, destination or K");
+    if (c.channels != 1 && c.channels != 3) return fail(ASL_EINVAL, "channels must be 1 (gray) or 3 (BGR), got %d", c.channels);
+    if (c.n_frames <= 0 || c.w <= 0 || c.h <= 0 || c.w_out <= 0 || c.h_out <= 0)
+        return fail(ASL_EINVAL, "sizes must be positive (n_frames %d, source %dx%d, output %dx%d)", c.n_frames, c.w, c.h, c.w_out, c.h_out);
+    if (c.w > RECTIFY_MAX_DIM || c.h > RECTIFY_MAX_DIM || c.w_out > RECTIFY_MAX_DIM || c.h_out > RECTIFY_MAX_DIM)
+        return fail(ASL_EINVAL, "unsupported image size (source %dx%d, output %dx%d; at most %d each way)", c.w, c.h, c.w_out, c.h_out, RECTIFY_MAX_DIM);
+    if (c.stride < c.w * c.channels) return fail(ASL_EINVAL, "stride %d smaller than a source row (%d bytes)", c.stride, c.w * c.channels);
+    if (c.stride_out < c.w_out) return fail(ASL_EINVAL, "stride_out %d smaller than an output row (%d bytes)", c.stride_out, c.w_out);
+    if (device && c.frame_pitch < (size_t)c.stride * (size_t)c.h) return fail(ASL_EINVAL, "frame_pitch smaller than one source frame");
+    if (device && c.frame_pitch_out < (size_t)c.stride_out * (size_t)c.h_out) return fail(ASL_EINVAL, "frame_pitch_out smaller than one output frame");
+    if (int rc = check_n_dist(c.n_dist)) return rc;
+    if (c.n_dist && !c.dist) return fail(ASL_EINVAL, "dist is NULL with n_dist = %d", c.n_dist);
+    if (c.fill < 0 || c.fill > 255) return fail(ASL_EINVAL, "fill must be in [0, 255] (got %d)", c.fill);
+    const double *Kn = c.K_new ? c.K_new : c.K;
+    for (int k = 0; k < 9; k++)
+        if (!std::isfinite(c.K[k]) || !std::isfinite(Kn[k])) return fail(ASL_EINVAL, "K / K_new is not finite");
+    for (int k = 0; k < c.n_dist; k++)
+        if (!std::isfinite(c.dist[k])) return fail(ASL_EINVAL, "dist is not finite");
+    if (!(c.K[0] > 0) || !(c.K[4] > 0) || !(Kn[0] > 0) || !(Kn[4] > 0)) return fail(ASL_EINVAL, "K and K_new must have positive focal lengths");
+    // the bytes the kernel may read / write: whole strides but for the last row of the last frame
+    const size_t src_bytes = (size_t)(c.n_frames - 1) * c.frame_pitch + (size_t)(c.h - 1) * (size_t)c.stride + (size_t)c.w * (size_t)c.channels;
+    const size_t dst_bytes = (size_t)(c.n_frames - 1) * c.frame_pitch_out + (size_t)(c.h_out - 1) * (size_t)c.stride_out + (size_t)c.w_out;
+    const uintptr_t s0 = (uintptr_t)c.src, d0 = (uintptr_t)c.dst;
+    if (s0 < d0 + dst_bytes && d0 < s0 + src_bytes) return fail(ASL_EINVAL, "source and destination overlap");
+    memset(cam, 0, sizeof *cam);
+    cam->fx = c.K[0]; cam->fy = c.K[4]; cam->cx = c.K[2]; cam->cy = c.K[5];
+    if (c.n_dist) { cam->k1 = c.dist[0]; cam->k2 = c.dist[1]; cam->p1 = c.dist[2]; cam->p2 = c.dist[3]; cam->k3 = c.n_dist >= 5 ? c.dist[4] : 0.0; }
+    cam->nfx = Kn[0]; cam->nfy = Kn[4]; cam->ncx = Kn[2]; cam->ncy = Kn[5];
+    cam->fill = c.fill;
+    return ASL_OK;
+}
+
+// frames along blockIdx.z, as many to a launch as the grid takes
+static int launch_rectify(const RectifyCall &c, const RectifyCam &cam, hipStream_t st)
+{
+    const dim3 tiles((c.w_out + RECTIFY_TW - 1) / RECTIFY_TW, (c.h_out + 4 * RECTIFY_TH - 1) / (4 * RECTIFY_TH));
+    const unsigned long long per_frame = 256ull * tiles.x * tiles.y;
+    const int step = (int)std::max<unsigned long long>(1ull, std::min<unsigned long long>(65535ull, (1ull << 31) / per_frame));
+    for (int f0 = 0; f0 < c.n_frames; f0 += step) {
+        const dim3 grid(tiles.x, tiles.y, (unsigned int)std::min(step, c.n_frames - f0));
+        const uint8_t *s = (const uint8_t *)c.src + (size_t)f0 * c.frame_pitch;
+        uint8_t *o = (uint8_t *)c.dst + (size_t)f0 * c.frame_pitch_out;
+        if (c.channels == 1)
+            hipLaunchKernelGGL(k_rectify<1>, grid, dim3(64, 4), 0, st, s, c.w, c.h, c.stride, c.frame_pitch, o, c.w_out, c.h_out, c.stride_out, c.frame_pitch_out, cam);
+        else
+            hipLaunchKernelGGL(k_rectify<3>, grid, dim3(64, 4), 0, st, s, c.w, c.h, c.stride, c.frame_pitch, o, c.w_out, c.h_out, c.stride_out, c.frame_pitch_out, cam);
+        HIPCHK(hipGetLastError());
+    }
+    return ASL_OK;
+}
+
+extern "C" int asl_rectify_frames_device(asl_detector *d, const void *d_src, int n_frames, int channels, int w, int h, int stride, size_t frame_pitch,
+                                         void *d_dst, int w_out, int h_out, int stride_out, size_t frame_pitch_out, const double *K,
+                                         const double *dist, int n_dist, const double *K_new, int fill, void *stream)
+{
+    const RectifyCall c{d_src, n_frames, channels, w, h, stride, frame_pitch, d_dst, w_out, h_out, stride_out, frame_pitch_out, K, dist, n_dist, K_new, fill};
+    RectifyCam cam;
+    if (int rc = check_rectify_call(d, c, true, &cam)) return rc;
+    HIPCHK(hipSetDevice(d->device));
+    return launch_rectify(c, cam, (hipStream_t)stream);
+}
+
+extern "C" int asl_rectify_u8(asl_detector *d, const uint8_t *src, int channels, int w, int h, int stride, uint8_t *dst, int w_out, int h_out,
+                              int stride_out, const double *K, const double *dist, int n_dist, const double *K_new, int fill)
+{
+    RectifyCall c{src, 1, channels, w, h, stride, 0, dst, w_out, h_out, stride_out, 0, K, dist, n_dist, K_new, fill};
+    RectifyCam cam;
+    if (int rc = check_rectify_call(d, c, false, &cam)) return rc;
+    HIPCHK(hipSetDevice(d->device));
+    const size_t row = (size_t)w * (size_t)channels;
+    if (d->rect_src.ensure(row * (size_t)h) || d->rect_dst.ensure((size_t)w_out * (size_t)h_out)) return fail(ASL_ENOMEM, "rectification staging allocation failed");
+    // rows packed on the device; the padding of the caller's rows is neither read nor written
+    HIPCHK(hipMemcpy2D(d->rect_src.p, row, src, (size_t)stride, row, (size_t)h, hipMemcpyHostToDevice));
+    c.src = d->rect_src.p; c.stride = (int)row; c.frame_pitch = row * (size_t)h;
+    c.dst = d->rect_dst.p; c.stride_out = w_out; c.frame_pitch_out = (size_t)w_out * (size_t)h_out;
+    if (int rc = launch_rectify(c, cam, nullptr)) return rc;
+    HIPCHK(hipMemcpy2D(dst, (size_t)stride_out, d->rect_dst.p, (size_t)w_out, (size_t)w_out, (size_t)h_out, hipMemcpyDeviceToHost));
     return ASL_OK;
 }
 

@@ -28,25 +28,41 @@ def rodrigues(rvec):
 class TagDetector:
     """Handles AprilTag detection and pose estimation (GPU-backed)."""
 
-    def __init__(self, camera_params, tag_type="tagStandard41h12", tag_size=0.06, device=0, id_limit=None, quad_sigma=0.0):
-        """quad_sigma: the detector's blur (> 0) or sharpening (< 0) of the decimated image; the reference leaves it 0."""
+    def __init__(self, camera_params, tag_type="tagStandard41h12", tag_size=0.06, device=0, id_limit=None, quad_sigma=0.0,
+                 rectify=False, rectified_K=None):
+        """quad_sigma: the detector's blur (> 0) or sharpening (< 0) of the decimated image; the reference leaves it 0.
+        rectify: take every frame through the lens rectification first (asl_rectify_u8 / asl_rectify_frames_device with
+        camera_params as the source camera), into a buffer this detector owns, and detect on the gray result -- for a lens
+        strong enough to bend a tag's edges.  DETECTIONS ARE THEN IN RECTIFIED PIXELS (rectify.distort_points takes them back
+        into the frame the camera delivered), and every pose call uses the pinhole rectified_K (default: the camera matrix)
+        with no distortion.  False, the default, is the path without the keyword."""
         self.detector = apriltag(tag_type, blur=quad_sigma, device=device, id_limit=id_limit)
         self.tag_size = tag_size
         self.camera_matrix = camera_params['camera_matrix']
         self.dist_coeffs = camera_params['dist_coeffs']
+        self.rectify = bool(rectify)
+        self.rectified_K = None
+        if self.rectify:
+            self.rectified_K = np.array(self.camera_matrix if rectified_K is None else rectified_K, dtype=np.float64).reshape(3, 3)
+        elif rectified_K is not None:
+            raise ValueError("rectified_K needs rectify=True")
+        self._device = int(device)
+        self._rect_buf = None  # detect_batch_device: the rectified frames on the device, grown on demand
 
     # -- reference call surface ------------------------------------------------------
     def detect(self, image):
         """BGR (H,W,3) uint8 image -> list of detection dicts sorted by id (tag_detector.py:23-28)."""
         a = np.asarray(image)
         if a.ndim == 2:
-            return sorted(self.detector.detect(a), key=lambda d: d['id'])
+            return sorted(self.detector.detect(self._rectified_host(a) if self.rectify else a), key=lambda d: d['id'])
         if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8:
             raise ValueError("expected an (H, W, 3) uint8 BGR image")
+        if self.rectify:
+            a = self._rectified_host(a)  # (H, W) gray, in rectified pixels
         # the poses are solved in the same device submission (asl_detect_batch_pose_u8) and ride along under a
         # private key, so that get_pose() of these detections needs no second trip to the GPU; the arithmetic is
         # the one get_pose() does on its own (float32-rounded corners -> asl_solve_pnp_batch), bit for bit
-        dets, poses, _ = self.detector._det.detect_host(np.ascontiguousarray(a), K=self.camera_matrix, dist=self._dist(),
+        dets, poses, _ = self.detector._det.detect_host(np.ascontiguousarray(a), K=self._K(), dist=self._dist(),
                                                         tag_size=self.tag_size)
         out = [{"hamming": int(d["hamming"]), "margin": float(d["margin"]), "id": int(d["id"]),
                 "center": np.array(d["center"]), "lb-rb-rt-lt": np.array(d["corners"]),
@@ -61,7 +77,7 @@ class TagDetector:
             rv, tv = cached[3].reshape(3, 1).copy(), cached[4].reshape(3, 1).copy()
             return cached[2], rv, tv, self.transformation(rv, tv)
         corners = np.array(detection['lb-rb-rt-lt'], dtype=np.float32)
-        rvec, tvec, _, ok = self.detector._det.solve_pnp(corners[None], self.camera_matrix, self._dist(), self.tag_size)
+        rvec, tvec, _, ok = self.detector._det.solve_pnp(corners[None], self._K(), self._dist(), self.tag_size)
         rv, tv = rvec[0].reshape(3, 1), tvec[0].reshape(3, 1)
         return bool(ok[0]), rv, tv, self.transformation(rv, tv)
 
@@ -108,20 +124,33 @@ class TagDetector:
     # -- batched forms ------------------------------------------------------------------
     def _pose_key(self):
         """what a cached pose depends on besides the corners: tag size and intrinsics, by value"""
-        return (float(self.tag_size), np.asarray(self.camera_matrix, dtype=np.float64).tobytes(), self._dist().tobytes())
+        return (float(self.tag_size), np.asarray(self._K(), dtype=np.float64).tobytes(), self._dist().tobytes())
 
-    def _dist(self):
+    def _lens(self):
+        """the camera's own lens coefficients"""
         d = np.asarray(self.dist_coeffs, dtype=np.float64).ravel()
         if len(d) not in (0, 4, 5):
             raise ValueError("dist_coeffs must hold 0, 4 or 5 values")
         return d
+
+    def _K(self):
+        """the camera matrix of the pixels the detections are in"""
+        return self.rectified_K if self.rectify else self.camera_matrix
+
+    def _dist(self):
+        """the lens of the pixels the detections are in: none once the frames are rectified"""
+        return np.zeros(0) if self.rectify else self._lens()
+
+    def _rectified_host(self, image):
+        """one host image, gray or BGR -> its rectified gray image (asl_rectify_u8)"""
+        return self.detector._det.rectify(image, self.camera_matrix, self._lens(), K_new=self.rectified_K)
 
     def get_poses(self, detections):
         """PnP for many detections in one launch: returns (ok[N], rvec[N,3], tvec[N,3], T[N,4,4])."""
         if not detections:
             return np.zeros(0, bool), np.zeros((0, 3)), np.zeros((0, 3)), np.zeros((0, 4, 4))
         c = np.stack([np.asarray(d['lb-rb-rt-lt'], dtype=np.float32) for d in detections])
-        rvec, tvec, T, ok = self.detector._det.solve_pnp(c, self.camera_matrix, self._dist(), self.tag_size)
+        rvec, tvec, T, ok = self.detector._det.solve_pnp(c, self._K(), self._dist(), self.tag_size)
         return ok, rvec, tvec, T
 
     def get_poses_cov(self, detections, sigma_px=0.0):
@@ -133,7 +162,7 @@ class TagDetector:
             return ok, rvec, tvec, T, np.zeros(0, dtype=_lib.POSE_COV_DTYPE)
         c = np.stack([np.asarray(d['lb-rb-rt-lt'], dtype=np.float32) for d in detections])
         Tc = np.where(np.asarray(ok, dtype=bool)[:, None, None], T, np.nan)
-        cov = self.detector._det.pose_cov(c, Tc, self.camera_matrix, self._dist(), self.tag_size, sigma_px)
+        cov = self.detector._det.pose_cov(c, Tc, self._K(), self._dist(), self.tag_size, sigma_px)
         return ok, rvec, tvec, T, cov
 
     # -- camera pose from every visible tag against a known map (asl_localize_batch) ---------------------------------
@@ -167,7 +196,7 @@ class TagDetector:
             obs["flags"][0, k] = 1 | (2 if oks[k] else 0)
             obs["corners"][0, k] = np.asarray(d['lb-rb-rt-lt'], dtype=np.float32).reshape(8)
             obs["T"][0, k] = np.asarray(Ts[k], dtype=np.float64).reshape(16)[:12]
-        res = self.detector._det.localize(obs, tag_map, self.camera_matrix, self._dist(), self.tag_size, max_tag_rms_px,
+        res = self.detector._det.localize(obs, tag_map, self._K(), self._dist(), self.tag_size, max_tag_rms_px,
                                           sigma_px=float(sigma_px) if with_cov else None)
         r = (res[0] if with_cov else res)[0]
         out = {"ok": int(r["status"]) == 0, "T": np.array(r["T"]), "rms_px": float(r["rms_px"]), "n_tags": int(r["n_tags"]),
@@ -185,7 +214,7 @@ class TagDetector:
         npf = np.asarray(n_per_frame, dtype=np.int64)
         mt = int(max_tags) if max_tags is not None else max(1, int(npf.max()) if len(npf) else 1)
         obs = pack_observations(dets, poses, npf, mt)
-        return self.detector._det.localize(obs, tag_map, self.camera_matrix, self._dist(), self.tag_size, max_tag_rms_px,
+        return self.detector._det.localize(obs, tag_map, self._K(), self._dist(), self.tag_size, max_tag_rms_px,
                                            sigma_px=float(sigma_px) if with_cov else None)
 
     # -- camera calibration from frames of a known target (asl_calibrate_batch) ------------------------------------------
@@ -196,6 +225,8 @@ class TagDetector:
         result's camera_params to a TagDetector afterwards."""
         from .calibrate import CalibrationResult
         from .dist import pack_observations
+        if self.rectify:
+            raise ValueError("calibrate needs the raw corners: use a TagDetector with rectify=False")
         a = np.ascontiguousarray(np.stack(frames) if isinstance(frames, (list, tuple)) else frames)
         if a.ndim not in (3, 4) or a.dtype != np.uint8:
             raise ValueError("frames must be (n, H, W[, 3]) uint8")
@@ -220,20 +251,32 @@ class TagDetector:
         a = np.ascontiguousarray(np.stack(frames) if isinstance(frames, (list, tuple)) else frames)
         if a.ndim not in (3, 4) or a.dtype != np.uint8:
             raise ValueError("frames must be (n, H, W[, 3]) uint8")
+        if self.rectify:
+            a = np.stack([self._rectified_host(f) for f in a])
         dist = self._dist()
-        dets, poses, npf = self.detector._det.detect_host(a, channels=1 if a.ndim == 3 else None, K=self.camera_matrix, dist=dist,
+        dets, poses, npf = self.detector._det.detect_host(a, channels=1 if a.ndim == 3 else None, K=self._K(), dist=dist,
                                                           tag_size=self.tag_size)
         npf = np.asarray(npf, dtype=np.int64)
         mt = max(1, min(256, int(npf.max()) if len(npf) else 1))
         obs = pack_observations(dets, poses, npf, mt)
         n_ids = int(max(1, obs["id"].max() + 1 if obs.size else 1))
-        res, tmap, std, cams = self.detector._det.build_map(obs, n_ids, self.camera_matrix, dist, self.tag_size,
+        res, tmap, std, cams = self.detector._det.build_map(obs, n_ids, self._K(), dist, self.tag_size,
                                                              world_id=-1 if world_id is None else int(world_id), max_iters=max_iters,
                                                              with_std=with_std)
         return MapResult(res, tmap, std, cams)
 
     def detect_batch_device(self, data_ptr, n_frames, channels, width, height, with_pose=True, stream=0, **kw):
-        """Frames resident in HBM -> (dets, poses, n_per_frame) structured arrays (see _lib)."""
-        K = self.camera_matrix if with_pose else None
+        """Frames resident in HBM -> (dets, poses, n_per_frame) structured arrays (see _lib).  With rectify the frames are
+        rectified on `stream` first, device to device, and the detections are in rectified pixels."""
+        if self.rectify:
+            import torch
+            need = int(n_frames) * int(width) * int(height)
+            if self._rect_buf is None or self._rect_buf.numel() < need:
+                self._rect_buf = torch.empty(need, dtype=torch.uint8, device="cuda:%d" % self._device)
+            self.detector._det.rectify_frames_device(data_ptr, n_frames, channels, width, height, self._rect_buf.data_ptr(),
+                                                     self.camera_matrix, self._lens(), K_new=self.rectified_K,
+                                                     stride=kw.pop("stride", None), frame_pitch=kw.pop("frame_pitch", None), stream=stream)
+            data_ptr, channels = self._rect_buf.data_ptr(), 1
+        K = self._K() if with_pose else None
         return self.detector._det.detect_device(data_ptr, n_frames, channels, width, height, stream=stream, K=K,
                                                 dist=self._dist(), tag_size=self.tag_size, **kw)

@@ -62,11 +62,12 @@ def process_detections(detector, detections, frame=None, out=print):
     return frame, records
 
 
-def run(frames, camera_params, tag_type="tagStandard41h12", tag_size=0.06, out=print, detector=None, **detector_kw):
+def run(frames, camera_params, tag_type="tagStandard41h12", tag_size=0.06, out=print, detector=None, rectify=False, **detector_kw):
     """The detection loop of the reference's main() (video_detection.py:209-296) over an iterable of BGR frames.
-    Returns (per-frame record lists, frames per second over the run)."""
+    Returns (per-frame record lists, frames per second over the run).  rectify: TagDetector's keyword -- rectify every frame
+    with the calibration first; corners are then in rectified pixels."""
     if detector is None:
-        detector = TagDetector(camera_params=camera_params, tag_type=tag_type, tag_size=tag_size, **detector_kw)
+        detector = TagDetector(camera_params=camera_params, tag_type=tag_type, tag_size=tag_size, rectify=rectify, **detector_kw)
     per_frame = []
     t0 = time.perf_counter()
     for frame in frames:

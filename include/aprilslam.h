@@ -415,6 +415,33 @@ int asl_render_frames_device(asl_detector *det, void *d_frames, int n_frames, in
                              const void *d_planes, int max_planes, const void *d_textures, int tw, int th, double half,
                              const double *K, const double *dist, int n_dist, void *stream);
 
+/* Lens rectification, the step between calibration and detection (what cv2.undistort / remap do for upstream's users):
+   n_frames gray or BGR frames of a camera with a lens (K 9 doubles row-major, dist n_dist = 0, 4 or 5 coefficients
+   k1 k2 p1 p2 [k3], as asl_solve_pnp_batch; host pointers) in, the GRAY frames of w_out x h_out pixels an ideal pinhole
+   K_new (9 doubles, NULL = K) would have delivered out; device pointers, frame i at d_src + i*frame_pitch and
+   d_dst + i*frame_pitch_out, asynchronous on `stream`.  Output pixel (x, y): xn = (x + 0.5 - cx') / fx',
+   yn = (y + 0.5 - cy') / fy' under K_new; the forward Brown-Conrady model, closed form (r2 = xn^2 + yn^2,
+   rad = 1 + ((k3 r2 + k2) r2 + k1) r2, xd = xn rad + 2 p1 xn yn + p2 (r2 + 2 xn^2), yd = yn rad + p1 (r2 + 2 yn^2) + 2 p2 xn yn);
+   u = fx xd + cx, v = fy yd + cy under K.  A sample outside the source (not 0 <= u < w and 0 <= v < h) gives `fill`;
+   otherwise the source is sampled bilinearly at (u, v), texel centres at +0.5, the four taps clamped to the edge, a BGR
+   tap first turned into gray with the detector's formula ((3735 B + 19235 G + 9798 R + 16384) >> 15), and the result is
+   floor(o + 0.5).  All in float64: the frames are byte-identical to tests/rectify_ref.py, and n_dist = 0 with
+   K_new = NULL at the source's size is the detector's gray conversion, exactly.  Detections on the result are in
+   rectified pixels: their camera is K_new with no distortion.  The detector supplies the device only; no batch state is
+   touched, so the call is legal between submit and collect.
+   ASL_EINVAL, nothing written: channels not 1 or 3; a size that is not positive (or above 16384); a stride or pitch
+   smaller than a row or frame; n_dist not 0, 4 or 5, or n_dist > 0 with dist NULL; a non-finite entry of K, K_new or
+   dist; fx or fy <= 0 in either matrix; fill outside 0..255; source and destination ranges that overlap. */
+int asl_rectify_frames_device(asl_detector *det, const void *d_src, int n_frames, int channels, int w, int h,
+                              int stride, size_t frame_pitch, void *d_dst, int w_out, int h_out, int stride_out,
+                              size_t frame_pitch_out, const double *K, const double *dist, int n_dist,
+                              const double *K_new /* 9, or NULL = K */, int fill, void *stream);
+/* The same for one host image, synchronous: the cv2.undistort of one frame (the detector keeps the device copies and
+   grows them on demand).  Only the w_out bytes of each of the h_out destination rows are written. */
+int asl_rectify_u8(asl_detector *det, const uint8_t *src, int channels, int w, int h, int stride,
+                   uint8_t *dst, int w_out, int h_out, int stride_out, const double *K, const double *dist,
+                   int n_dist, const double *K_new, int fill);
+
 /* ---- introspection and diagnostics.  asl_debug_fetch, asl_stage_times and the counters (item 5) describe the LAST batch
    the detector ran.  asl_detect_batch_u8 and asl_detect_batch_pose_u8 run a call of 128 frames or more as consecutive
    batches of 64 frames, so after such a call that is the call's last chunk (frames 128..149 of a 150-frame call), not the
