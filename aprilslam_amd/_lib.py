@@ -29,6 +29,9 @@ CALIB_RESULT_DTYPE = np.dtype([("K", "<f8", (3, 3)), ("dist", "<f8", (5,)), ("st
 MAP_RESULT_DTYPE = np.dtype([("cost_seed", "<f8"), ("cost", "<f8"), ("rms_px", "<f8"), ("rms_seed_px", "<f8"),
                              ("n_frames_used", "<i4"), ("n_tags", "<i4"), ("n_obs", "<i4"), ("n_obs_dropped", "<i4"),
                              ("iterations", "<i4"), ("world_id", "<i4"), ("status", "<i4"), ("reserved", "<i4")])  # asl_map_result
+SMOOTH_RESULT_DTYPE = np.dtype([("cost_seed", "<f8"), ("cost", "<f8"), ("rms_px", "<f8"), ("rms_seed_px", "<f8"),
+                                ("n_frames_data", "<i4"), ("n_filled", "<i4"), ("n_flipped", "<i4"), ("iterations", "<i4"),
+                                ("status", "<i4"), ("reserved", "<i4", (3,))])  # asl_smooth_result
 POSE_COV_DTYPE = np.dtype([("cov", "<f8", (6, 6)), ("sigma_px", "<f8"), ("dof", "<i4"), ("status", "<i4")])  # asl_pose_cov
 QUAD_DTYPE = np.dtype([("p", "<f8", (4, 2)), ("cluster", "<u8"), ("frame", "<i4"), ("reversed_border", "<i4")])  # asl_debug_quad
 assert DET_DTYPE.itemsize == 96 and POSE_DTYPE.itemsize == 184 and QUAD_DTYPE.itemsize == 80  # asl_detection, asl_pose, asl_debug_quad
@@ -36,6 +39,7 @@ assert MAP_TAG_DTYPE.itemsize == 104
 assert CAM_POSE_DTYPE.itemsize == 160
 assert CALIB_RESULT_DTYPE.itemsize == 216
 assert MAP_RESULT_DTYPE.itemsize == 64
+assert SMOOTH_RESULT_DTYPE.itemsize == 64
 assert POSE_COV_DTYPE.itemsize == 304
 RIG_CAMERA_DTYPE = np.dtype([("K", "<f8", (3, 3)), ("dist", "<f8", (5,)), ("E", "<f8", (3, 4)), ("n_dist", "<i4"), ("reserved", "<i4")])  # asl_rig_camera
 assert RIG_CAMERA_DTYPE.itemsize == 216
@@ -47,7 +51,7 @@ EXPORTS = [
     "asl_localize_frames_device", "asl_localize_batch", "asl_localize_cov_frames_device", "asl_localize_cov_batch",
     "asl_pose_cov_device", "asl_solve_pnp_cov_batch", "asl_calibrate_frames_device", "asl_calibrate_batch",
     "asl_localize_rig_frames_device", "asl_localize_rig_cov_frames_device", "asl_localize_rig_batch", "asl_localize_rig_cov_batch",
-    "asl_map_frames_device", "asl_map_batch",
+    "asl_map_frames_device", "asl_map_batch", "asl_smooth_frames_device", "asl_smooth_batch",
     "asl_debug_fetch", "asl_debug_refit", "asl_debug_division_check", "asl_stage_times", "asl_set_profiling", "asl_debug_phase_cycles",
 ]
 
@@ -113,6 +117,9 @@ def load():
     L.asl_calibrate_batch.argtypes = [vp, vp, i32, i32, vp, i32, C.c_double, i32, i32, dp, i32, i32, i32, vp, vp]
     L.asl_map_frames_device.argtypes = [vp, vp, i32, i32, i32, dp, dp, i32, C.c_double, i32, i32, vp, vp, vp, vp, vp]
     L.asl_map_batch.argtypes = [vp, vp, i32, i32, i32, dp, dp, i32, C.c_double, i32, i32, vp, vp, vp, vp]
+    L.asl_smooth_frames_device.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, vp, C.c_double, C.c_double, C.c_double, i32,
+                                           vp, vp, vp]
+    L.asl_smooth_batch.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, vp, C.c_double, C.c_double, C.c_double, i32, vp, vp]
     L.asl_debug_fetch.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.asl_debug_refit.argtypes = [vp, i32, vp, C.c_size_t]
     L.asl_debug_division_check.argtypes = [vp, i32, vp, C.c_size_t]
@@ -501,6 +508,36 @@ class Detector:
         check(self._L.asl_map_frames_device(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), int(n_ids), Kp, dpp, nd, float(tag_size),
                                             int(world_id), int(max_iters), _ptr(map_ptr), _opt_ptr(std_ptr), _ptr(poses_ptr),
                                             _ptr(result_ptr), _ptr(stream)))
+
+    def smooth(self, obs, tag_map, K, dist, tag_size, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, seed=None):
+        """asl_smooth_batch: host records obs (n_frames, max_tags) OBS_DTYPE of one camera's consecutive frames against tag_map
+        -> ((n_frames,) CAM_POSE_DTYPE, world<-camera for EVERY frame, SMOOTH_RESULT_DTYPE record): the reprojection error of
+        all frames (corner sigma sigma_px) plus a random-walk motion prior between consecutive frames (sigma_rot rad,
+        sigma_trans scene units per frame step).  seed: (n_frames,) CAM_POSE_DTYPE as localize() returns them for the same
+        obs; None: that localisation runs first."""
+        o = _obs_records(obs)
+        m = _map_records(tag_map)
+        keep, Kp, dpp, nd = _camera(K, dist, square=True)
+        sd = None if seed is None else np.ascontiguousarray(seed, dtype=CAM_POSE_DTYPE).ravel()
+        if sd is not None and len(sd) != o.shape[0]:
+            raise ValueError("seed must hold one pose per frame")
+        out = np.zeros(o.shape[0], dtype=CAM_POSE_DTYPE)
+        res = np.zeros((), dtype=SMOOTH_RESULT_DTYPE)
+        check(self._L.asl_smooth_batch(self._h, o.ctypes.data if o.size else None, o.shape[0], o.shape[1], m.ctypes.data if m.size else None,
+                                       len(m), Kp, dpp, nd, float(tag_size), None if sd is None else sd.ctypes.data, float(sigma_px),
+                                       float(sigma_rot), float(sigma_trans), int(max_iters), out.ctypes.data if out.size else None,
+                                       res.ctypes.data))
+        return out, res
+
+    def smooth_device(self, obs_ptr, n_frames, max_tags, map_ptr, n_ids, seed_ptr, out_ptr, result_ptr, K, dist, tag_size, sigma_px=1.0,
+                      sigma_rot=0.05, sigma_trans=0.5, max_iters=20, stream=0):
+        """asl_smooth_frames_device: obs_ptr (n_frames x max_tags asl_obs), map_ptr (n_ids asl_map_tag), seed_ptr (n_frames
+        asl_cam_pose, as localize_device wrote them), out_ptr (n_frames asl_cam_pose) and result_ptr (one asl_smooth_result)
+        are device addresses; enqueued on `stream`, no wait."""
+        keep, Kp, dpp, nd = _camera(K, dist, square=True)
+        check(self._L.asl_smooth_frames_device(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids), Kp, dpp, nd,
+                                               float(tag_size), _ptr(seed_ptr), float(sigma_px), float(sigma_rot), float(sigma_trans),
+                                               int(max_iters), _ptr(out_ptr), _ptr(result_ptr), _ptr(stream)))
 
     def collect_view(self):
         """Wait for the submitted batch; (dets, poses or None, n_per_frame) as numpy VIEWS of the detector's page-locked result

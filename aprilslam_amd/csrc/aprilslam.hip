@@ -36,6 +36,7 @@
 #include "k_rig.inc"
 #include "k_calib.inc"
 #include "k_map.inc"
+#include "k_smooth.inc"
 
 static thread_local std::string g_err;
 
@@ -131,6 +132,7 @@ struct asl_detector {
     DevBuf<uint8_t> rect_src, rect_dst;  // asl_rectify_u8: the host image's device copy and the result (no batch reads them)
     DevBuf<uint8_t> cal_ws;  // calibration: per-frame workspace and state (k_calib.inc)
     DevBuf<uint8_t> map_ws, map_lm;  // map reconstruction (k_map.inc): sized by the input / by the problem
+    DevBuf<uint8_t> smooth_ws;  // sequence localisation (k_smooth.inc): the chain's and the LM's buffers, sized by n_frames
     hipStream_t copy_stream = nullptr, host_stream = nullptr;  // host frames: transfers and the chunks' kernels (detect_host_frames)
     std::vector<hipEvent_t> copy_done;
     hipStream_t aux_stream = nullptr;  // highest priority, for the small latency-bound jobs next to a running batch (pose-graph LM)
@@ -1628,6 +1630,117 @@ extern "C" int asl_map_batch(asl_detector *d, const asl_obs *obs, int n_frames, 
     HIPCHK(hipMemcpy(map, d_map, sizeof(asl_map_tag) * (size_t)n_ids, hipMemcpyDeviceToHost));
     if (tag_std) HIPCHK(hipMemcpy(tag_std, d_std, sizeof(double) * 6 * (size_t)n_ids, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(poses, d_poses, sizeof(asl_cam_pose) * (size_t)n_frames, hipMemcpyDeviceToHost));
+    return ASL_OK;
+}
+
+// ---- sequence localisation with a motion prior (k_smooth.inc)
+
+// Every refusal of the two entry points, before anything is written or enqueued
+static int check_smooth_args(const asl_detector *d, const void *obs, int n_frames, int max_tags, const void *map, int n_ids, const double *K,
+                             const double *dist, int n_dist, double tag_size, double sigma_px, double sigma_rot, double sigma_trans,
+                             int max_iters, const void *out, const void *result)
+{
+    if (!d) return fail(ASL_EINVAL, "NULL detector");
+    if (!obs || !map || !K || !out || !result) return fail(ASL_EINVAL, "NULL argument");
+    if (n_frames < 1 || n_frames > 65535) return fail(ASL_EINVAL, "n_frames must be in [1, 65535] (got %d)", n_frames);
+    if (int rc = check_obs_args(max_tags, n_ids, n_dist, !dist, tag_size)) return rc;
+    for (int k = 0; k < 9; k++)
+        if (!std::isfinite(K[k])) return fail(ASL_EINVAL, "K is not finite");
+    const double sig[3] = {sigma_px, sigma_rot, sigma_trans};
+    for (double s : sig)
+        if (!(s > 0) || !std::isfinite(s)) return fail(ASL_EINVAL, "sigma_px, sigma_rot and sigma_trans must be positive and finite (got %g)", s);
+    if (max_iters < 1 || max_iters > 100) return fail(ASL_EINVAL, "max_iters must be in [1, 100] (got %d)", max_iters);
+    return ASL_OK;
+}
+
+// All device pointers; everything is enqueued on st, nothing waits
+static int launch_smooth(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids, const double *K,
+                         const double *dist, int n_dist, double tag_size, const void *d_seed, double sigma_px, double sigma_rot,
+                         double sigma_trans, int max_iters, void *d_out, void *d_result, hipStream_t st)
+{
+    static_assert(sizeof(SmoothResultRec) == sizeof(asl_smooth_result) && sizeof(asl_smooth_result) == 64, "asl_smooth_result layout");
+    const size_t n = (size_t)n_frames;
+    SmoothBufs b{};
+    b.n = n_frames;
+    if (carve_ws(d->smooth_ws, [&](WsCarve &c) {
+            b.cand = c.take<double>(24 * n); b.dcost = c.take<double>(2 * n); b.tcost = c.take<double>(4 * n);
+            b.posed = c.take<int>(n); b.ntags = c.take<int>(n); b.src = c.take<int>(n); b.back = c.take<int>(n); b.choice = c.take<int>(n);
+            b.code = c.take<int>(n); b.head = c.take<int>(SMH__N); b.lm = c.take<double>(SM__N); b.cseed = c.take<double>(n);
+            b.delta = c.take<double>(6 * n); b.fac = c.take<double>(SM_FAC * n);
+            b.set[0] = c.take<double>(SM_SET * n); b.set[1] = c.take<double>(SM_SET * n);
+        }))
+        return fail(ASL_ENOMEM, "sequence localisation workspace allocation failed");
+    const CamDev cam = make_cam(d, K, dist, n_dist, tag_size);
+    const ObsRec *obs = (const ObsRec *)d_obs;
+    const MapTagRec *map = (const MapTagRec *)d_map;
+    const CamPoseRec *seed = (const CamPoseRec *)d_seed;
+    const double w = 1.0 / (sigma_px * sigma_px), isr = 1.0 / sigma_rot, ist = 1.0 / sigma_trans;
+    const size_t lds = loc_lds_bytes(max_tags);
+    const dim3 frames((unsigned int)n_frames), wave(ASL_WAVE), one(1), wg(SM_WG), per_thread((unsigned int)((n + SM_WG - 1) / SM_WG));
+
+    const dim3 commit_blocks((unsigned int)std::min<size_t>((SM_SET * n + SM_WG - 1) / SM_WG, 1024));
+
+    range_push("smooth: seed chain");
+    hipLaunchKernelGGL(k_smooth_cand, frames, wave, lds, st, obs, max_tags, map, n_ids, cam, seed, w, b);
+    hipLaunchKernelGGL(k_smooth_scan, one, wave, 0, st, b);
+    hipLaunchKernelGGL(k_smooth_trans, dim3((unsigned int)((n + ASL_WAVE - 1) / ASL_WAVE)), wave, 0, st, b, isr, ist);
+    hipLaunchKernelGGL(k_smooth_dp, one, wave, 0, st, b);
+    hipLaunchKernelGGL(k_smooth_fill, per_thread, wg, 0, st, b, seed);
+    hipLaunchKernelGGL(k_smooth_lin, frames, wave, lds, st, obs, max_tags, map, n_ids, cam, b, 0, isr, ist);
+    hipLaunchKernelGGL(k_smooth_init, one, wg, 0, st, b, w);
+    range_pop();
+    range_push("smooth: LM");
+    for (int it = 0; it < max_iters; it++) {
+        hipLaunchKernelGGL(k_smooth_solve, one, wave, 0, st, b, w);
+        hipLaunchKernelGGL(k_smooth_lin, frames, wave, lds, st, obs, max_tags, map, n_ids, cam, b, 1, isr, ist);
+        hipLaunchKernelGGL(k_smooth_decide, one, wg, 0, st, b, w);
+        hipLaunchKernelGGL(k_smooth_commit, commit_blocks, wg, 0, st, b);
+    }
+    hipLaunchKernelGGL(k_smooth_finish, per_thread, wg, 0, st, b, (CamPoseRec *)d_out, (SmoothResultRec *)d_result);
+    range_pop();
+    HIPCHK(hipGetLastError());
+    return ASL_OK;
+}
+
+extern "C" int asl_smooth_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                        const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed, double sigma_px,
+                                        double sigma_rot, double sigma_trans, int max_iters, void *d_out, void *d_result, void *stream)
+{
+    if (int rc = check_smooth_args(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, sigma_px, sigma_rot, sigma_trans,
+                                   max_iters, d_out, d_result))
+        return rc;
+    if (!d_seed) return fail(ASL_EINVAL, "NULL argument");
+    const uintptr_t s0 = (uintptr_t)d_seed, o0 = (uintptr_t)d_out, bytes = sizeof(asl_cam_pose) * (uintptr_t)n_frames;
+    if (s0 < o0 + bytes && o0 < s0 + bytes) return fail(ASL_EINVAL, "d_out overlaps d_seed");
+    HIPCHK(hipSetDevice(d->device));
+    return launch_smooth(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, d_seed, sigma_px, sigma_rot, sigma_trans,
+                         max_iters, d_out, d_result, (hipStream_t)stream);
+}
+
+extern "C" int asl_smooth_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed, double sigma_px,
+                                double sigma_rot, double sigma_trans, int max_iters, asl_cam_pose *out, asl_smooth_result *result)
+{
+    if (int rc = check_smooth_args(d, obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, sigma_px, sigma_rot, sigma_trans,
+                                   max_iters, out, result))
+        return rc;
+    HIPCHK(hipSetDevice(d->device));
+    const size_t n = (size_t)n_frames;
+    asl_cam_pose *d_out = nullptr, *d_seed = nullptr;
+    asl_smooth_result *d_result = nullptr;
+    if (carve_ws(d->solve_out, [&](WsCarve &c) { d_result = c.take<asl_smooth_result>(1); d_out = c.take<asl_cam_pose>(n); d_seed = c.take<asl_cam_pose>(n); }))
+        return fail(ASL_ENOMEM, "sequence localisation workspace allocation failed");
+    if (int rc = upload_obs(d, "sequence localisation", obs, n_frames, max_tags, map, n_ids)) return rc;
+    if (seed)
+        HIPCHK(hipMemcpy(d_seed, seed, sizeof(asl_cam_pose) * n, hipMemcpyHostToDevice));
+    else  // the per-frame localisation of the same block, gate 0
+        launch_localize(d, {d->loc_obs.p, 0, n_frames, max_tags, d->loc_map.p, n_ids, K, dist, n_dist, nullptr, tag_size, 0.0, 0.0, d_seed, nullptr, false},
+                        nullptr);
+    if (int rc = launch_smooth(d, d->loc_obs.p, n_frames, max_tags, d->loc_map.p, n_ids, K, dist, n_dist, tag_size, d_seed, sigma_px, sigma_rot,
+                               sigma_trans, max_iters, d_out, d_result, nullptr))
+        return rc;
+    HIPCHK(hipMemcpy(out, d_out, sizeof(asl_cam_pose) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(result, d_result, sizeof(asl_smooth_result), hipMemcpyDeviceToHost));
     return ASL_OK;
 }
 

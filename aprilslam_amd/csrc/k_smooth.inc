@@ -1,0 +1,615 @@
+// Sequence localisation against a fixed tag map with a random-walk motion prior (asl_smooth_frames_device /
+// asl_smooth_batch): one camera<-world pose per frame of one camera's consecutive frames, minimising the reprojection
+// error of all mapped corners (/ sigma_px^2) plus |(Log(R_D) / sigma_rot, t_D / sigma_trans)|^2 between consecutive
+// frames, R_D = R_{f+1} R_f^T, t_D = t_{f+1} - R_D t_f.  tests/smooth_ref.py is the NumPy statement of the same
+// computation, operation order of the linear solve included.  float64, contraction off, no scratch.
+//   seed chain   k_smooth_cand   one wavefront per frame: the seed's pose A and, for a frame of exactly one taking-part slot,
+//                                its mirrored planar minimum B (loc_candidate), both costed over the frame's corners
+//                k_smooth_scan   one wavefront: the nearest posed frame at or before every frame (wave_scan of a maximum)
+//                k_smooth_trans  one thread per posed frame: the four motion costs from its predecessor's candidates
+//                k_smooth_dp     one wavefront: the two-state dynamic programme, forward and back, 64 frames' costs a load
+//                k_smooth_fill   one thread per frame: the chosen pose, or the nearest earlier posed frame's
+//                k_smooth_lin    (below) once at the chain's poses, then k_smooth_init: one workgroup, the cost after the
+//                                chain, the LM state (lambda0, status 1 / 3), the per-frame seed costs
+//   per trial    k_smooth_lin    one wavefront per frame: the pose (stepped by delta), the frame's cost, H and g from its
+//                                corners (loc_gather, loc_pass), and the motion blocks of the pair (f, f + 1), a lane an entry
+//                k_smooth_solve  one wavefront: the block-tridiagonal Cholesky forward and back over the frames, the 6x6
+//                                block spread over 36 lanes with its operands in LDS
+//                k_smooth_decide one workgroup: the trial's cost in a fixed order, the accept rule, lambda, the stop
+//                k_smooth_commit an accepted trial copied over the current state, spread over the device
+//   end          k_smooth_finish one thread per frame: the records
+// Serial by nature are the scan, the dynamic programme and the factor-and-solve: each is a chain over the frames, so each
+// is one wavefront that carries a small state (a maximum, two costs, a 6x6 coupling block) from frame to frame.  All trials are enqueued at once;
+// lm[SM_STOP] makes the ones after the stop return at once (k_map.inc works the same way).
+
+struct SmoothResultRec {  // == asl_smooth_result, 64 bytes
+    double cost_seed, cost, rms_px, rms_seed_px;
+    int32_t n_frames_data, n_filled, n_flipped, iterations, status, reserved[3];
+};
+
+enum { SM_COST = 0, SM_LAMBDA, SM_STOP, SM_ITERS, SM_STATUS, SM_COST0, SM_SOLVED, SM_PIX, SM_PIX0, SM_CORNERS, SM_NDATA, SM_TAKE, SM__N = 16 };
+enum { SMH_NPOSED = 0, SMH_FIRST, SMH_FAIL, SMH_NFLIP, SMH__N = 4 };
+#define SM_MOT 121                // per pair: QN 36, QP 36, C 36, gN 6, gP 6, |m|^2
+#define SM_SET (12 + 27 + 1 + SM_MOT)  // doubles per frame of one state: pose, normal equations, pixel cost, motion blocks
+#define SM_FAC 84                 // per frame of the factorisation: L 36, M 36, 1 / diag 6, y 6
+#define SM_WG 256
+
+// One state of the solve over n frames, one allocation: poses (R 9, t 3), packed normal equations (21 + 6), pixel costs,
+// motion blocks of the pairs (f, f + 1)
+struct SmoothSet {
+    double *P, *ne, *c, *mot;
+};
+
+__host__ __device__ inline SmoothSet smooth_set(double *base, size_t n)
+{
+    return {base, base + 12 * n, base + 39 * n, base + 40 * n};
+}
+
+struct SmoothBufs {
+    double *cand, *dcost, *tcost;   // per frame: A and B (2 x 12), their weighted data costs (2), transitions (4: from * 2 + to)
+    int *posed, *ntags, *src, *back, *choice, *code, *head;
+    double *lm, *cseed, *delta, *fac;
+    double *set[2];                 // the current state and the trial
+    int n;
+};
+
+__device__ __forceinline__ void smooth_relative(const double *Ra, const double *ta, const double *Rb, const double *tb, double *RD, double *tD)
+{
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) RD[3 * i + j] = Rb[3 * i] * Ra[3 * j] + Rb[3 * i + 1] * Ra[3 * j + 1] + Rb[3 * i + 2] * Ra[3 * j + 2];
+#pragma unroll
+    for (int i = 0; i < 3; i++) tD[i] = tb[i] - (RD[3 * i] * ta[0] + RD[3 * i + 1] * ta[1] + RD[3 * i + 2] * ta[2]);
+}
+
+// m = (Log(R_D) isr, t_D ist) of the poses a = (R_f, t_f) and b = (R_{f+1}, t_{f+1}); returns |m|^2
+__device__ __forceinline__ double smooth_residual(const double *Pa, const double *Pb, double isr, double ist, double *RD, double *tD, double *m)
+{
+    smooth_relative(Pa, Pa + 9, Pb, Pb + 9, RD, tD);
+    const double a[3] = {0.5 * (RD[7] - RD[5]), 0.5 * (RD[2] - RD[6]), 0.5 * (RD[3] - RD[1])};
+    const double s = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+    const double c = 0.5 * ((RD[0] + RD[4] + RD[8]) - 1.0);
+    const double k = s > 1e-12 ? atan2(s, c) / s : 1.0;
+    double mm = 0;
+#pragma unroll
+    for (int i = 0; i < 3; i++) m[i] = (s > 1e-12 ? a[i] * k : a[i]) * isr;
+#pragma unroll
+    for (int i = 0; i < 3; i++) m[3 + i] = tD[i] * ist;
+#pragma unroll
+    for (int i = 0; i < 6; i++) mm += m[i] * m[i];
+    return mm;
+}
+
+// P <- [Rod(w) | v] P, d = (w, v): the localisation's left update
+__device__ __forceinline__ void smooth_update(double *P, const double *d)
+{
+    double dR[9], Rn[9], tn[3];
+    rodrigues_dev(d, dR);
+    mat3_mul_dev(dR, P, Rn);
+#pragma unroll
+    for (int r = 0; r < 3; r++) tn[r] = dR[3 * r] * P[9] + dR[3 * r + 1] * P[10] + dR[3 * r + 2] * P[11] + d[3 + r];
+#pragma unroll
+    for (int i = 0; i < 9; i++) P[i] = Rn[i];
+    P[9] = tn[0]; P[10] = tn[1]; P[11] = tn[2];
+}
+
+// [t]x (a, b), t in LDS (indexed at run time: not a register array)
+__device__ __forceinline__ double smooth_skew(const double *t, int a, int b)
+{
+    if (a == b) return 0.0;
+    const double v = t[3 - a - b];
+    return (b - a + 3) % 3 == 1 ? -v : v;
+}
+
+// sum over the workgroup (SM_WG threads) in a fixed order, in every thread; sh: SM_WG doubles
+__device__ __forceinline__ double smooth_block_sum(double v, double *sh)
+{
+    __syncthreads();
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = SM_WG / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+// Candidates of one frame and their data costs
+__global__ void __launch_bounds__(64) k_smooth_cand(const ObsRec *__restrict__ obs, int max_tags, const MapTagRec *__restrict__ map, int n_ids,
+                                                    CamDev cam, const CamPoseRec *__restrict__ seed, double w, SmoothBufs b)
+{
+    extern __shared__ double s_dyn[];
+    const int lane = (int)threadIdx.x, f = (int)blockIdx.x;
+    const LocLds L = loc_lds(s_dyn, max_tags);
+    const ObsRec *fo = obs + (size_t)f * max_tags;
+    const LocOneCam m{cam, fo, max_tags};
+    const int npart = loc_gather([&](int s) { return fo + s; }, max_tags, map, n_ids, cam.half, [](int) { return false; }, L, lane);
+    const bool posed = seed[f].status == 0;
+    if (lane == 0) { b.ntags[f] = npart; b.posed[f] = posed ? 1 : 0; }
+    if (!posed) return;
+    double RA[9], tA[3], RB[9], tB[3];
+    const double *T = seed[f].T;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) RA[3 * i + j] = T[4 * j + i];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; i++) tA[i] = -(RA[3 * i] * T[3] + RA[3 * i + 1] * T[7] + RA[3 * i + 2] * T[11]);
+    const double dA = loc_pass<false>(m, RA, tA, L, lane, nullptr) * w;
+    double dB = dA;
+    const bool has_b = npart == 1;
+    if (has_b) {  // the one taking-part slot: the only term of the sum
+        int ls = 0;
+        for (int s = lane; s < max_tags; s += ASL_WAVE)
+            if (L.state[s] == 1) ls += s;
+        const int s1 = butterfly_sum<64>(ls);
+        const double *Mp = map[fo[s1].id].T;
+        double M[12], To[12];
+#pragma unroll
+        for (int k = 0; k < 12; k++) M[k] = Mp[k];
+#pragma unroll
+        for (int i = 0; i < 3; i++) {  // camera<-tag = A map[id]
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                To[4 * i + j] = RA[3 * i] * M[j] + RA[3 * i + 1] * M[4 + j] + RA[3 * i + 2] * M[8 + j] + (j == 3 ? tA[i] : 0.0);
+        }
+        loc_candidate(To, M, true, RB, tB);
+        dB = loc_pass<false>(m, RB, tB, L, lane, nullptr) * w;
+    }
+    if (lane == 0) {
+        double *c = b.cand + 24 * (size_t)f;
+#pragma unroll
+        for (int i = 0; i < 9; i++) { c[i] = RA[i]; c[12 + i] = has_b ? RB[i] : RA[i]; }
+#pragma unroll
+        for (int i = 0; i < 3; i++) { c[9 + i] = tA[i]; c[21 + i] = has_b ? tB[i] : tA[i]; }
+        b.dcost[2 * f] = dA;
+        b.dcost[2 * f + 1] = dB;
+    }
+}
+
+// src[f]: the nearest posed frame at or before f (-1: none); head: the number of posed frames and the first one
+__global__ void __launch_bounds__(64) k_smooth_scan(SmoothBufs b)
+{
+    const int lane = (int)threadIdx.x;
+    int carry = -1, np = 0, first = -1;
+    for (int base = 0; base < b.n; base += ASL_WAVE) {
+        const int f = base + lane;
+        const int v = (f < b.n && b.posed[f]) ? f : -1;
+        int s = wave_scan<false>(v, -1, [](int x, int y) { return x > y ? x : y; });
+        s = s > carry ? s : carry;
+        if (f < b.n) b.src[f] = s;
+        carry = readlane(s, 63);
+        np += butterfly_sum<64>(v >= 0 ? 1 : 0);
+        const int mn = wave_scan<true>(v >= 0 ? v : 0x7fffffff, 0x7fffffff, [](int x, int y) { return x < y ? x : y; });
+        if (first < 0 && mn != 0x7fffffff) first = mn;
+    }
+    if (lane == 0) { b.head[SMH_NPOSED] = np; b.head[SMH_FIRST] = first; b.head[SMH_FAIL] = 0; b.head[SMH_NFLIP] = 0; }
+}
+
+// The four transition costs of a posed frame from its predecessor, over a gap of g frame steps divided by g
+__global__ void __launch_bounds__(64) k_smooth_trans(SmoothBufs b, double isr, double ist)
+{
+    const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (f >= b.n || !b.posed[f]) return;
+    const int p = f > 0 ? b.src[f - 1] : -1;
+    double *tc = b.tcost + 4 * (size_t)f;
+    if (p < 0) { tc[0] = 0; tc[1] = 0; tc[2] = 0; tc[3] = 0; return; }
+    const double gap = (double)(f - p);
+    double Pa[12], Pb[12], RD[9], tD[3], m[6];
+    for (int a = 0; a < 2; a++)
+        for (int c = 0; c < 2; c++) {
+#pragma unroll
+            for (int k = 0; k < 12; k++) { Pa[k] = b.cand[24 * (size_t)p + 12 * a + k]; Pb[k] = b.cand[24 * (size_t)f + 12 * c + k]; }
+            tc[2 * a + c] = smooth_residual(Pa, Pb, isr, ist, RD, tD, m) / gap;
+        }
+}
+
+// The dynamic programme over the posed frames: forward (ties to A), then back from the lower-cost state (tie: A).  A lane
+// loads one frame of each chunk of 64; the chain reads them lane by lane (readlane) and leaves lane l's result with lane l.
+__global__ void __launch_bounds__(64) k_smooth_dp(SmoothBufs b)
+{
+    if (b.head[SMH_NPOSED] == 0) return;
+    const int lane = (int)threadIdx.x, n = b.n;
+    double cA = 0, cB = 0;
+    bool started = false;
+    for (int base = 0; base < n; base += ASL_WAVE) {
+        const int f = base + lane;
+        const int my = (f < n && b.posed[f]) ? 1 : 0;
+        double dA = 0, dB = 0, t00 = 0, t01 = 0, t10 = 0, t11 = 0;
+        if (my) {
+            dA = b.dcost[2 * f]; dB = b.dcost[2 * f + 1];
+            t00 = b.tcost[4 * (size_t)f]; t01 = b.tcost[4 * (size_t)f + 1]; t10 = b.tcost[4 * (size_t)f + 2]; t11 = b.tcost[4 * (size_t)f + 3];
+        }
+        int my_back = 0;
+        for (int l = 0; l < ASL_WAVE; l++) {
+            if (!readlane(my, l)) continue;
+            const double a = readlane(dA, l), bb = readlane(dB, l);
+            int bk = 0;
+            if (!started) {
+                cA = a; cB = bb; started = true;
+            } else {
+                double best = cA + readlane(t00, l), alt = cB + readlane(t10, l);
+                if (alt < best) { best = alt; bk |= 1; }
+                const double nA = best + a;
+                best = cA + readlane(t01, l); alt = cB + readlane(t11, l);
+                if (alt < best) { best = alt; bk |= 2; }
+                cB = best + bb;
+                cA = nA;
+            }
+            if (lane == l) my_back = bk;
+        }
+        if (f < n) b.back[f] = my_back;   // read back below by the lane that wrote it
+    }
+    int cur = cB < cA ? 1 : 0, nflip = 0;
+    for (int base = (n - 1) / ASL_WAVE * ASL_WAVE; base >= 0; base -= ASL_WAVE) {
+        const int f = base + lane;
+        const int my = (f < n && b.posed[f]) ? 1 : 0;
+        const int my_back = f < n ? b.back[f] : 0;
+        int my_choice = 0;
+        for (int l = ASL_WAVE - 1; l >= 0; l--) {
+            if (!readlane(my, l)) continue;
+            if (lane == l) my_choice = cur;
+            nflip += cur;
+            cur = (readlane(my_back, l) >> cur) & 1;
+        }
+        if (f < n) b.choice[f] = my_choice;
+    }
+    if (lane == 0) b.head[SMH_NFLIP] = nflip;
+}
+
+// Every frame's start pose and seed code
+__global__ void __launch_bounds__(SM_WG) k_smooth_fill(SmoothBufs b, const CamPoseRec *__restrict__ seed)
+{
+    const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (f >= b.n || b.head[SMH_NPOSED] == 0) return;
+    int s = b.src[f];
+    if (s < 0) s = b.head[SMH_FIRST];
+    const int ch = b.choice[s];
+    const double *c = b.cand + 24 * (size_t)s + 12 * ch;
+    double *P = b.set[0] + 12 * (size_t)f;
+    for (int k = 0; k < 12; k++) P[k] = c[k];
+    b.code[f] = b.posed[f] ? seed[f].seed_slot + LOC_MIRRORED * ch : -1;
+}
+
+// Frame f of a state: its pose (trial: the current one stepped by delta), pixel cost, H and g, and the motion blocks of
+// the pair (f, f + 1) at the same state
+__global__ void __launch_bounds__(64) k_smooth_lin(const ObsRec *__restrict__ obs, int max_tags, const MapTagRec *__restrict__ map, int n_ids,
+                                                   CamDev cam, SmoothBufs b, int trial, double isr, double ist)
+{
+    extern __shared__ double s_dyn[];
+    __shared__ double s_RD[9], s_tD[3], s_m[6], s_B[36], s_Ad[36], s_Jn[36], s_Jp[36];
+    if (b.head[SMH_NPOSED] == 0) return;
+    if (trial && (b.lm[SM_STOP] != 0.0 || b.head[SMH_FAIL])) return;
+    const int lane = (int)threadIdx.x, f = (int)blockIdx.x, n = b.n;
+    const SmoothSet in = smooth_set(b.set[0], (size_t)n), out = smooth_set(b.set[trial], (size_t)n);
+    double P[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) P[k] = in.P[12 * (size_t)f + k];
+    if (trial) {
+        double d[6];
+#pragma unroll
+        for (int k = 0; k < 6; k++) d[k] = b.delta[6 * (size_t)f + k];
+        smooth_update(P, d);
+    }
+    const LocLds L = loc_lds(s_dyn, max_tags);
+    const ObsRec *fo = obs + (size_t)f * max_tags;
+    const LocOneCam m{cam, fo, max_tags};
+    loc_gather([&](int s) { return fo + s; }, max_tags, map, n_ids, cam.half, [](int) { return false; }, L, lane);
+    double ne[27];
+    const double c = loc_pass<true>(m, P, P + 9, L, lane, ne);
+    if (lane == 0) {
+        if (trial) {  // trial 0 linearises the current state in place: its poses stay as they are (block f - 1 reads them)
+#pragma unroll
+            for (int k = 0; k < 12; k++) out.P[12 * (size_t)f + k] = P[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 27; k++) out.ne[27 * (size_t)f + k] = ne[k];
+        out.c[f] = c;
+    }
+    if (f + 1 >= n) return;
+
+    double Q[12], RD[9], tD[3], mv[6];
+#pragma unroll
+    for (int k = 0; k < 12; k++) Q[k] = in.P[12 * (size_t)(f + 1) + k];
+    if (trial) {
+        double d[6];
+#pragma unroll
+        for (int k = 0; k < 6; k++) d[k] = b.delta[6 * (size_t)(f + 1) + k];
+        smooth_update(Q, d);
+    }
+    const double mm = smooth_residual(P, Q, isr, ist, RD, tD, mv);
+    double *mot = out.mot + SM_MOT * (size_t)f;
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; k++) s_RD[k] = RD[k];
+#pragma unroll
+        for (int k = 0; k < 3; k++) s_tD[k] = tD[k];
+#pragma unroll
+        for (int k = 0; k < 6; k++) s_m[k] = mv[k];
+        mot[120] = mm;
+    }
+    __syncthreads();
+    const int i = lane / 6, j = lane % 6;   // lanes 0..35: entry (i, j) of a 6x6 block
+    if (lane < 36) {  // B = [[I, 0], [-[t_D]x, I]], Ad = [[R_D, 0], [[t_D]x R_D, R_D]]
+        double bv = i == j ? 1.0 : 0.0, av = 0.0;
+        if (i >= 3 && j < 3) {
+            bv = -smooth_skew(s_tD, i - 3, j);
+            av = smooth_skew(s_tD, i - 3, 0) * s_RD[j] + smooth_skew(s_tD, i - 3, 1) * s_RD[3 + j] + smooth_skew(s_tD, i - 3, 2) * s_RD[6 + j];
+        } else if (i < 3 && j < 3)
+            av = s_RD[3 * i + j];
+        else if (i >= 3 && j >= 3)
+            av = s_RD[3 * (i - 3) + j - 3];
+        s_B[lane] = bv;
+        s_Ad[lane] = av;
+    }
+    __syncthreads();
+    if (lane < 36) {  // Jn = W B, Jp = -W B Ad
+        const double wi = i < 3 ? isr : ist;
+        double s = 0;
+        for (int k = 0; k < 6; k++) s += s_B[6 * i + k] * s_Ad[6 * k + j];
+        s_Jn[lane] = wi * s_B[lane];
+        s_Jp[lane] = -(wi * s);
+    }
+    __syncthreads();
+    if (lane < 36) {
+        double qn = 0, qp = 0, cc = 0;
+        for (int k = 0; k < 6; k++) {
+            qn += s_Jp[6 * k + i] * s_Jp[6 * k + j];
+            qp += s_Jn[6 * k + i] * s_Jn[6 * k + j];
+            cc += s_Jn[6 * k + i] * s_Jp[6 * k + j];
+        }
+        mot[lane] = qn;
+        mot[36 + lane] = qp;
+        mot[72 + lane] = cc;
+    }
+    if (lane < 6) {
+        double gn = 0, gp = 0;
+        for (int k = 0; k < 6; k++) { gn += s_Jp[6 * k + lane] * s_m[k]; gp += s_Jn[6 * k + lane] * s_m[k]; }
+        mot[108 + lane] = gn;
+        mot[114 + lane] = gp;
+    }
+}
+
+// After the chain's linearisation: the LM state, the seed costs
+__global__ void __launch_bounds__(SM_WG) k_smooth_init(SmoothBufs b, double w)
+{
+    __shared__ double sh[SM_WG];
+    const int n = b.n, tid = (int)threadIdx.x;
+    double *lm = b.lm;
+    if (b.head[SMH_NPOSED] == 0) {
+        if (tid < SM__N) lm[tid] = 0.0;
+        __syncthreads();
+        if (tid == 0) { lm[SM_STOP] = 1.0; lm[SM_STATUS] = 1.0; }
+        return;
+    }
+    const SmoothSet s = smooth_set(b.set[0], (size_t)n);
+    double cost = 0, pix = 0, corners = 0, ndata = 0;
+    for (int f = tid; f < n; f += SM_WG) {
+        const double c = s.c[f];
+        b.cseed[f] = c;
+        cost += c * w + (f + 1 < n ? s.mot[SM_MOT * (size_t)f + 120] : 0.0);
+        pix += c;
+        corners += 4.0 * b.ntags[f];
+        ndata += b.ntags[f] > 0 ? 1.0 : 0.0;
+    }
+    cost = smooth_block_sum(cost, sh);
+    pix = smooth_block_sum(pix, sh);
+    corners = smooth_block_sum(corners, sh);
+    ndata = smooth_block_sum(ndata, sh);
+    if (tid == 0) {
+        const bool bad = !isfinite(cost);
+        lm[SM_COST] = cost; lm[SM_COST0] = cost; lm[SM_PIX] = pix; lm[SM_PIX0] = pix; lm[SM_CORNERS] = corners; lm[SM_NDATA] = ndata;
+        lm[SM_LAMBDA] = 1e-3; lm[SM_ITERS] = 0.0; lm[SM_SOLVED] = 0.0;
+        lm[SM_STOP] = bad ? 1.0 : 0.0;
+        lm[SM_STATUS] = bad ? 3.0 : 0.0;
+    }
+}
+
+// (A + lambda diag(A)) delta = -g, A block tridiagonal: forward S_f = A_ff (damped) - M_{f-1} M_{f-1}^T = L_f L_f^T,
+// L_f y_f = -g_f - M_{f-1} y_{f-1}, M_f = C_f L_f^-T; back L_f^T x_f = y_f - M_f^T x_{f+1}.  Lane 6 i + j holds entry (i, j)
+// of the block on its way through the right-looking Cholesky (every entry loses its products in the order k = 0, 1, ...,
+// as chol6_solve_tri_dev's do); the triangular solves of six numbers run in every lane on the same LDS operands.  A pivot
+// that is not positive sets head[SMH_FAIL] and ends the kernel.
+__global__ void __launch_bounds__(64) k_smooth_solve(SmoothBufs b, double w)
+{
+    __shared__ double S[36], Mp[36], yv[6], rr[6], iv[6];
+    if (b.lm[SM_STOP] != 0.0) return;
+    const int lane = (int)threadIdx.x, n = b.n, i = lane / 6, j = lane % 6;
+    const double lambda = b.lm[SM_LAMBDA];
+    const SmoothSet s = smooth_set(b.set[0], (size_t)n);
+    for (int f = 0; f < n; f++) {
+        const double *ne = s.ne + 27 * (size_t)f, *mot = s.mot + SM_MOT * (size_t)f, *motp = mot - SM_MOT;
+        double v = 0;
+        if (lane < 36) {
+            v = ne[i >= j ? TRI(i, j) : TRI(j, i)] * w;
+            if (f > 0) v = v + motp[36 + lane];
+            if (f + 1 < n) v = v + mot[lane];
+            if (i == j) v = v + lambda * v;
+            if (f > 0)
+                for (int k = 0; k < 6; k++) v = v - Mp[6 * i + k] * Mp[6 * j + k];
+        } else if (lane < 42) {
+            const int r = lane - 36;
+            double g = ne[21 + r] * w;
+            if (f > 0) g = g + motp[114 + r];
+            if (f + 1 < n) g = g + mot[108 + r];
+            v = -g;
+            if (f > 0)
+                for (int k = 0; k < 6; k++) v = v - Mp[6 * r + k] * yv[k];
+        }
+        __syncthreads();
+        if (lane < 36) S[lane] = v;
+        else if (lane < 42) rr[lane - 36] = v;
+        __syncthreads();
+        double inv[6];
+#pragma unroll
+        for (int c = 0; c < 6; c++) {
+            const double p = S[7 * c];
+            if (!(p > 0)) {  // the same LDS word in every lane: the whole wavefront leaves
+                if (lane == 0) b.head[SMH_FAIL] = 1;
+                return;
+            }
+            const double dc = sqrt(p);
+            inv[c] = 1.0 / dc;
+            __syncthreads();
+            if (lane < 36 && j == c) {
+                if (i == c) S[lane] = dc;
+                else if (i > c) S[lane] = S[lane] * inv[c];
+            }
+            __syncthreads();
+            if (lane < 36 && j > c && i >= j) S[lane] = S[lane] - S[6 * i + c] * S[6 * j + c];
+            __syncthreads();
+        }
+        double y[6];
+#pragma unroll
+        for (int a = 0; a < 6; a++) {
+            double t = rr[a];
+#pragma unroll
+            for (int k = 0; k < a; k++) t -= S[6 * a + k] * y[k];
+            y[a] = t * inv[a];
+        }
+        double Mr[6] = {0, 0, 0, 0, 0, 0};
+        if (f + 1 < n && lane < 6) {  // row `lane` of M_f = C_f L_f^-T
+#pragma unroll
+            for (int c = 0; c < 6; c++) {
+                double t = mot[72 + 6 * lane + c];
+#pragma unroll
+                for (int k = 0; k < c; k++) t -= Mr[k] * S[6 * c + k];
+                Mr[c] = t * inv[c];
+            }
+        }
+        __syncthreads();
+        double *fac = b.fac + SM_FAC * (size_t)f;
+        if (lane == 0) {
+#pragma unroll
+            for (int a = 0; a < 6; a++) { yv[a] = y[a]; fac[72 + a] = inv[a]; fac[78 + a] = y[a]; }
+        }
+        if (lane < 36) fac[lane] = i >= j ? S[lane] : 0.0;
+        if (f + 1 < n && lane < 6) {
+#pragma unroll
+            for (int c = 0; c < 6; c++) { Mp[6 * lane + c] = Mr[c]; fac[36 + 6 * lane + c] = Mr[c]; }
+        }
+        __syncthreads();
+    }
+    __threadfence();  // fac: written by some lanes, read by others below
+    double x[6] = {0, 0, 0, 0, 0, 0};
+    for (int f = n - 1; f >= 0; f--) {
+        const double *fac = b.fac + SM_FAC * (size_t)f;   // written above by this wavefront
+        __syncthreads();
+        if (lane < 36) { S[lane] = fac[lane]; Mp[lane] = f + 1 < n ? fac[36 + lane] : 0.0; }
+        if (lane < 6) { iv[lane] = fac[72 + lane]; yv[lane] = fac[78 + lane]; }
+        __syncthreads();
+        double r[6], xn[6];
+#pragma unroll
+        for (int a = 0; a < 6; a++) {
+            double t = yv[a];
+            if (f + 1 < n) {
+#pragma unroll
+                for (int k = 0; k < 6; k++) t -= Mp[6 * k + a] * x[k];
+            }
+            r[a] = t;
+        }
+#pragma unroll
+        for (int a = 5; a >= 0; a--) {
+            double t = r[a];
+#pragma unroll
+            for (int k = a + 1; k < 6; k++) t -= S[6 * k + a] * xn[k];
+            xn[a] = t * iv[a];
+        }
+#pragma unroll
+        for (int a = 0; a < 6; a++) x[a] = xn[a];
+        if (lane == 0) {
+#pragma unroll
+            for (int a = 0; a < 6; a++) b.delta[6 * (size_t)f + a] = x[a];
+        }
+    }
+}
+
+// The trial's cost and the localisation's accept rule on it; lm[SM_TAKE]: k_smooth_commit has a trial to copy
+__global__ void __launch_bounds__(SM_WG) k_smooth_decide(SmoothBufs b, double w)
+{
+    __shared__ double sh[SM_WG];
+    double *lm = b.lm;
+    const int n = b.n, tid = (int)threadIdx.x;
+    if (lm[SM_STOP] != 0.0) {
+        if (tid == 0) lm[SM_TAKE] = 0.0;
+        return;
+    }
+    const bool failed = b.head[SMH_FAIL] != 0;
+    const double cost = lm[SM_COST];
+    __syncthreads();
+    if (failed) {
+        if (tid == 0) { lm[SM_ITERS] += 1.0; lm[SM_LAMBDA] *= 10.0; lm[SM_TAKE] = 0.0; b.head[SMH_FAIL] = 0; }
+        return;
+    }
+    const SmoothSet t = smooth_set(b.set[1], (size_t)n);
+    double cn = 0, pix = 0;
+    for (int f = tid; f < n; f += SM_WG) {
+        const double c = t.c[f];
+        cn += c * w + (f + 1 < n ? t.mot[SM_MOT * (size_t)f + 120] : 0.0);
+        pix += c;
+    }
+    cn = smooth_block_sum(cn, sh);
+    pix = smooth_block_sum(pix, sh);
+    const bool take = cn < cost;
+    if (tid == 0) {
+        lm[SM_ITERS] += 1.0;
+        lm[SM_SOLVED] = 1.0;
+        lm[SM_TAKE] = take ? 1.0 : 0.0;
+        if (take) {
+            if (cost - cn < 1e-12 * cost) lm[SM_STOP] = 1.0;
+            lm[SM_COST] = cn;
+            lm[SM_PIX] = pix;
+            lm[SM_LAMBDA] *= 0.1;
+        } else
+            lm[SM_LAMBDA] *= 10.0;
+    }
+}
+
+__global__ void __launch_bounds__(SM_WG) k_smooth_commit(SmoothBufs b)
+{
+    if (b.lm[SM_TAKE] == 0.0) return;
+    const size_t total = (size_t)SM_SET * b.n, stride = (size_t)gridDim.x * SM_WG;
+    for (size_t k = (size_t)blockIdx.x * SM_WG + threadIdx.x; k < total; k += stride) b.set[0][k] = b.set[1][k];
+}
+
+__global__ void __launch_bounds__(SM_WG) k_smooth_finish(SmoothBufs b, CamPoseRec *__restrict__ out, SmoothResultRec *__restrict__ res)
+{
+    const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x), n = b.n;
+    if (f >= n) return;
+    const double *lm = b.lm;
+    const bool nothing = b.head[SMH_NPOSED] == 0;
+    int status = (int)lm[SM_STATUS];
+    if (!nothing && status == 0 && lm[SM_SOLVED] == 0.0) status = 2;
+    if (f == 0) {
+        const double k = nothing ? 0.0 : lm[SM_CORNERS];
+        res->cost_seed = nothing ? 0.0 : lm[SM_COST0];
+        res->cost = nothing ? 0.0 : lm[SM_COST];
+        res->rms_px = k > 0 ? sqrt(lm[SM_PIX] / k) : 0.0;
+        res->rms_seed_px = k > 0 ? sqrt(lm[SM_PIX0] / k) : 0.0;
+        res->n_frames_data = nothing ? 0 : (int)lm[SM_NDATA];
+        res->n_filled = nothing ? 0 : n - b.head[SMH_NPOSED];
+        res->n_flipped = nothing ? 0 : b.head[SMH_NFLIP];
+        res->iterations = (int)lm[SM_ITERS];
+        res->status = status;
+        res->reserved[0] = 0; res->reserved[1] = 0; res->reserved[2] = 0;
+    }
+    CamPoseRec *o = out + f;
+    if (nothing) { loc_write_none(o, 1); return; }
+    const SmoothSet s = smooth_set(b.set[0], (size_t)n);
+    const double *R = s.P + 12 * (size_t)f, *t = R + 9;
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        o->T[4 * r] = R[r]; o->T[4 * r + 1] = R[3 + r]; o->T[4 * r + 2] = R[6 + r];
+        o->T[4 * r + 3] = -(R[r] * t[0] + R[3 + r] * t[1] + R[6 + r] * t[2]);
+    }
+    o->T[12] = 0; o->T[13] = 0; o->T[14] = 0; o->T[15] = 1;
+    const int nt = b.ntags[f];
+    o->rms_px = nt > 0 ? sqrt(s.c[f] / (4.0 * nt)) : 0.0;
+    o->rms_seed_px = nt > 0 ? sqrt(b.cseed[f] / (4.0 * nt)) : 0.0;
+    o->n_tags = nt;
+    o->n_rejected = 0;
+    o->status = status != 0 ? 4 : nt > 0 ? 0 : 6;
+    o->seed_slot = b.code[f];
+}

@@ -247,6 +247,11 @@ class SLAM:
         the pose's covariance as TagDetector.localize reports it (the graph's tags taken as exact)."""
         return self.detector.localize(detections, self.tag_map(), max_tag_rms_px=max_tag_rms_px, with_cov=with_cov, sigma_px=sigma_px)
 
+    def localize_sequence(self, dets, poses, n_per_frame, **kw):
+        """Camera poses of consecutive frames against tag_map(), solved together with a motion prior
+        (TagDetector.localize_sequence); like localize it leaves the graph, the window and my_pose() alone."""
+        return self.detector.localize_sequence(dets, poses, n_per_frame, self.tag_map(), **kw)
+
     def average_distance_to_nodes(self):
         """Mean distance camera <-> tag over ALL nodes of the graph (0 for an empty graph), slam.py:65-80."""
         nodes = self.graph.get_nodes()

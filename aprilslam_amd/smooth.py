@@ -1,0 +1,52 @@
+"""Sequence localisation: the camera poses of one camera's consecutive frames against a known tag map, solved together
+under a random-walk motion prior (asl_smooth_batch / asl_smooth_frames_device, k_smooth.inc).  Every frame gets a pose: one
+without a mapped tag is carried by its neighbours, a single-tag frame is kept out of its mirrored planar minimum by them,
+and corner noise is averaged over the sequence.
+
+    SmoothResult         the poses (CAM_POSE_DTYPE per frame), the SMOOTH_RESULT_DTYPE record, the filled / flipped masks
+    SMOOTH_RESULT_DTYPE  cost_seed, cost, rms_px, rms_seed_px, n_frames_data, n_filled, n_flipped, iterations, status
+"""
+import numpy as np
+
+from ._lib import CAM_POSE_DTYPE, SMOOTH_RESULT_DTYPE
+
+FRAME_DATA, FRAME_NOTHING, FRAME_FAILED, FRAME_PRIOR = 0, 1, 4, 6
+STATUS_OK, STATUS_NO_POSED_FRAME, STATUS_NOT_POSITIVE_DEFINITE, STATUS_NON_FINITE = 0, 1, 2, 3
+FLIPPED = 256   # added to seed_slot where the seed chain chose the mirrored candidate
+
+__all__ = ["SmoothResult", "SMOOTH_RESULT_DTYPE", "CAM_POSE_DTYPE", "FRAME_DATA", "FRAME_NOTHING", "FRAME_FAILED", "FRAME_PRIOR",
+           "STATUS_OK", "STATUS_NO_POSED_FRAME", "STATUS_NOT_POSITIVE_DEFINITE", "STATUS_NON_FINITE", "FLIPPED"]
+
+
+class SmoothResult:
+    """What Detector.smooth returns, named."""
+
+    def __init__(self, poses, result, seed=None):
+        self.poses = np.asarray(poses, dtype=CAM_POSE_DTYPE)
+        self.result = np.asarray(result, dtype=SMOOTH_RESULT_DTYPE).reshape(())
+        self.seed = seed    # the per-frame localisation that seeded the solve (None: not kept)
+
+    @property
+    def ok(self):
+        return int(self.result["status"]) == STATUS_OK
+
+    @property
+    def filled(self):
+        """frames that had no pose of their own (no seed): started from a neighbour's"""
+        return (self.poses["seed_slot"] < 0) & (self.poses["status"] != FRAME_NOTHING)
+
+    @property
+    def flipped(self):
+        """frames where the seed chain took the mirrored planar minimum instead of the seed"""
+        if self.seed is None:
+            raise ValueError("the flipped mask needs the seed poses the solve started from")
+        return (self.poses["seed_slot"] >= 0) & (self.poses["seed_slot"] == np.asarray(self.seed)["seed_slot"] + FLIPPED)
+
+    @property
+    def prior_only(self):
+        """frames without a mapped tag: their pose comes from the motion prior alone"""
+        return self.poses["status"] == FRAME_PRIOR
+
+    def trajectory(self):
+        """(n_frames, 4, 4) world<-camera"""
+        return np.array(self.poses["T"], dtype=np.float64).reshape(-1, 4, 4)

@@ -394,6 +394,53 @@ int asl_map_batch(asl_detector *det, const asl_obs *obs, int n_frames, int max_t
                   const double *dist, int n_dist, double tag_size, int world_id, int max_iters, asl_map_tag *map,
                   double *tag_std, asl_cam_pose *poses, asl_map_result *result);
 
+/* ---- sequence localisation: the camera poses of one camera's consecutive frames against a fixed map, solved together
+   under a random-walk motion prior, so that EVERY frame gets a pose: frames without a mapped tag are carried by their
+   neighbours, a single-tag frame cannot end in its mirrored planar minimum alone, and corner noise is averaged. */
+typedef struct {
+    double cost_seed, cost;        /* the objective below after the seed chain / at the end */
+    double rms_px, rms_seed_px;    /* pixel residuals alone, per corner, over all frames: at the end / after the chain */
+    int32_t n_frames_data;         /* frames with a taking-part slot */
+    int32_t n_filled;              /* frames without a seed pose, started from a neighbour's */
+    int32_t n_flipped;             /* frames where the chain chose the mirrored candidate */
+    int32_t iterations;            /* LM trials run */
+    int32_t status;                /* 0 ok, 1 no frame with a seed pose (nothing solved), 2 never positive definite,
+                                      3 non-finite cost after the chain */
+    int32_t reserved[3];
+} asl_smooth_result;               /* 64 bytes */
+
+/* Smooth d_obs (n_frames x max_tags records of consecutive frames, as asl_pack_observations_device writes them) against
+   d_map (n_ids asl_map_tag) from d_seed (n_frames asl_cam_pose, what asl_localize_frames_device wrote for the same obs, map
+   and camera; status 0: the frame has a pose); device pointers, everything enqueued on `stream`, no host wait (the detector
+   owns the work buffers: the first call at a larger n_frames allocates, which synchronises the device).  Unknowns:
+   camera<-world (R_f, t_f) of every frame, left update as the localisation.  Minimised:
+   sum_f |r_f|^2 / sigma_px^2 + sum_f |(Log(R_D) / sigma_rot, t_D / sigma_trans)|^2, r_f the localisation's residuals of
+   frame f (slots with flags & 1 and a mapped id, the camera model of asl_solve_pnp_batch, a corner at z <= 1e-9 costs 1e12,
+   no gate), R_D = R_{f+1} R_f^T, t_D = t_{f+1} - R_D t_f; sigma_rot in radians, sigma_trans in scene units, per frame step.
+   Seed chain: each posed frame has its seed pose A and, with exactly one taking-part slot, the mirrored planar minimum B
+   through that slot's map tag; a two-state dynamic programme over the posed frames picks one per frame (data cost plus
+   motion cost, divided by the gap in frames; ties to A); a frame without a seed pose starts from the nearest earlier posed
+   frame's (the leading ones from the first).  Then Levenberg-Marquardt on all frames: block-tridiagonal normal matrix,
+   motion Jacobians to first order in the relative rotation, block Cholesky forward and back over the frames, lambda0 1e-3,
+   x10 rejected or not positive definite / x0.1 accepted, at most max_iters trials (in [1, 100]; all enqueued, the ones after
+   the stop return at once), stop on an accepted trial of relative decrease below 1e-12.
+   d_out: n_frames asl_cam_pose, T world<-camera, rms_px / rms_seed_px the frame's own corner RMS at the end / after the
+   chain, n_tags its taking-part slots, n_rejected 0, seed_slot the seed's (+256 if the chain chose B, -1 for a frame without
+   a seed pose), status 0 solved with data, 6 solved and carried by the motion prior alone, 4 in a solve that failed (result
+   status 2 or 3; T is the chain's), 1 nothing to solve (T the identity).  d_result: one asl_smooth_result.
+   ASL_EINVAL, nothing written: a NULL pointer; n_frames outside [1, 65535]; max_tags outside [1, 256]; n_dist not 0, 4 or 5,
+   or n_dist > 0 with dist NULL; a non-finite K, tag_size or sigma; a sigma <= 0; max_iters outside [1, 100]; d_out
+   overlapping d_seed.  One sequence per call, even frame spacing.  Deterministic: the same input gives the same bytes.
+   tests/smooth_ref.py states the algorithm. */
+int asl_smooth_frames_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                             const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed, double sigma_px,
+                             double sigma_rot, double sigma_trans, int max_iters, void *d_out, void *d_result, void *stream);
+/* The same computation on host records, synchronous (the detector keeps the device copies and grows them on demand).
+   seed == NULL: the per-frame localisation (asl_localize_frames_device, max_tag_rms_px 0) runs first and seeds it. */
+int asl_smooth_batch(asl_detector *det, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                     const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed, double sigma_px,
+                     double sigma_rot, double sigma_trans, int max_iters, asl_cam_pose *out, asl_smooth_result *result);
+
 /* ---- before the detector: the image-formation step on the device (reference src/simulation/renderer.py:197-274:
    purple clear colour, one GL_LINEAR-textured quad per tag, BGR read-back).  One plane per visible tag and frame, in
    painter's order (far to near); a plane with tex < 0 ends a frame's list. */

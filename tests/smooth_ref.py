@@ -1,0 +1,357 @@
+"""NumPy statement of the sequence localisation (asl_smooth_frames_device / asl_smooth_batch, aprilslam_amd/csrc/k_smooth.inc):
+one camera<-world pose (R_f, t_f) for EVERY frame of one camera's consecutive frames against a fixed tag map, minimising
+
+    sum_f  |r_f|^2 / sigma_px^2   +   sum_f  |m_f|^2
+
+r_f: the localisation's own pixel residuals of frame f (localize_ref: every taking-part slot, flags & 1, 0 <= id < n_ids,
+     map[id].valid, corners +-h through the camera model; a corner at z <= 1e-9 costs 1e12 and adds nothing to H and g; no gate)
+m_f: the random-walk motion residual between frames f and f + 1: R_D = R_{f+1} R_f^T, t_D = t_{f+1} - R_D t_f,
+     m_f = (Log(R_D) / sigma_rot, t_D / sigma_trans).  Log through atan2(|a|, c), a = vee(R_D - R_D^T) / 2, c = (tr R_D - 1) / 2:
+     exact to rounding at small angles, meant for relative rotations well below pi.
+
+Left update of the localisation, R <- Rod(w) R, t <- Rod(w) t + v, delta = (w, v).  To first order in the relative rotation
+(J_l^-1 ~ I), with B = [[I, 0], [-[t_D]x, I]], Ad = [[R_D, 0], [[t_D]x R_D, R_D]], W = diag(1/sigma_rot x3, 1/sigma_trans x3):
+d m_f / d delta_{f+1} = W B = Jn and d m_f / d delta_f = -W B Ad = Jp.
+
+Normal matrix, block tridiagonal in 6x6 blocks, assembled in this order (w = 1 / sigma_px^2):
+    A[f][f] = (H_f w + Jn_{f-1}^T Jn_{f-1}) + Jp_f^T Jp_f      g_f = (g_f w + Jn_{f-1}^T m_{f-1}) + Jp_f^T m_f
+    A[f+1][f] = C_f = Jn_f^T Jp_f
+(A + lambda diag(A)) delta = -g by the block Cholesky of tridiag_solve, forward and back over the frames; a diagonal block
+that is not positive definite fails the trial.  LM schedule of the localisation: lambda0 = 1e-3, x10 after a rejected or
+failed trial, x0.1 after an accepted one, at most max_iters trials, an accepted trial whose decrease is below 1e-12 of the
+cost before it ends the solve.
+
+Seed chain, before the LM: seed[f] is the frame's asl_cam_pose of the per-frame localisation (status 0: posed).  Candidate A
+is the seed's camera<-world; B, only for a frame with exactly one taking-part slot, the mirrored planar minimum through that
+slot's map tag (localize_ref.mirrored of camera<-tag = A map[id], taken back through inv(map[id])), else B = A.  A two-state
+dynamic programme over the posed frames in frame order minimises the candidates' data costs (/ sigma_px^2) plus |m|^2 between
+consecutive posed frames, divided by the gap in frame steps; ties go to A, the backtracking starts from the lower-cost state
+(tie: A).  A frame without a seed pose takes the chosen pose of the nearest earlier posed frame, the leading ones the first
+posed frame's.  Without any posed frame nothing is solved.
+
+Output per frame (asl_cam_pose): T world<-camera, rms_px / rms_seed_px the frame's own corner RMS at the end / after the
+chain, n_tags its taking-part slots, n_rejected 0, seed_slot the seed's (+256 if the chain chose B; -1 for a filled frame),
+status 0 solved with data, 6 solved and carried by the motion prior alone, 4 in a solve that failed, 1 nothing to solve
+(T the identity).  One asl_smooth_result: total cost after the chain and at the end, the corner RMS of both over all
+frames, frames with data, frames filled, frames where B was chosen, trials run, status 0 ok / 1 no posed frame / 2 never
+positive definite / 3 non-finite (the cost after the chain).  Test infrastructure, as localize_ref.py is.
+"""
+import numpy as np
+
+import localize_ref as LR
+from aprilslam_amd._lib import CAM_POSE_DTYPE, SMOOTH_RESULT_DTYPE
+
+LAMBDA0 = 1e-3
+REL_STOP = 1e-12
+FLIPPED = 256
+FRAME_DATA, FRAME_NOTHING, FRAME_FAILED, FRAME_PRIOR = 0, 1, 4, 6
+OK, NO_POSED_FRAME, NOT_POSITIVE_DEFINITE, NON_FINITE = 0, 1, 2, 3
+
+
+def skew(t):
+    return np.array([[0.0, -t[2], t[1]], [t[2], 0.0, -t[0]], [-t[1], t[0], 0.0]])
+
+
+def log_so3(R):
+    a = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s = np.sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2])
+    c = 0.5 * ((R[0, 0] + R[1, 1] + R[2, 2]) - 1.0)
+    if s > 1e-12:
+        return a * (np.arctan2(s, c) / s)
+    return a
+
+
+def relative(Pa, Pb):
+    """(R_D, t_D) of the poses Pa = (R_f, t_f) and Pb = (R_{f+1}, t_{f+1})"""
+    RD = Pb[0] @ Pa[0].T
+    return RD, Pb[1] - RD @ Pa[1]
+
+
+def motion_residual(Pa, Pb, sigma_rot, sigma_trans):
+    RD, tD = relative(Pa, Pb)
+    return np.concatenate([log_so3(RD) * (1.0 / sigma_rot), tD * (1.0 / sigma_trans)])
+
+
+def motion_jacobians(RD, tD, sigma_rot, sigma_trans):
+    """(Jn = d m / d delta_{f+1}, Jp = d m / d delta_f)"""
+    B, Ad = np.eye(6), np.zeros((6, 6))
+    B[3:, :3] = -skew(tD)
+    Ad[:3, :3] = RD
+    Ad[3:, :3] = skew(tD) @ RD
+    Ad[3:, 3:] = RD
+    w = np.array([1.0 / sigma_rot] * 3 + [1.0 / sigma_trans] * 3)
+    return w[:, None] * B, -(w[:, None] * (B @ Ad))
+
+
+def update(P, d):
+    dR = LR.rodrigues(d[:3])
+    return dR @ P[0], dR @ P[1] + d[3:]
+
+
+def chol6(S):
+    """right-looking Cholesky of the lower triangle of S in place -> 1 / diagonal, or None: the products leave every entry
+    in the order k = 0, 1, ... (chol6_solve_tri_dev's), one lane per entry on the device"""
+    inv = np.zeros(6)
+    for j in range(6):
+        p = S[j, j]
+        if not p > 0:
+            return None
+        S[j, j] = np.sqrt(p)
+        inv[j] = 1.0 / S[j, j]
+        S[j + 1:, j] = S[j + 1:, j] * inv[j]
+        for c in range(j + 1, 6):
+            S[c:, c] = S[c:, c] - S[c:, j] * S[c, j]
+    return inv
+
+
+def tridiag_solve(D, C, b, lam):
+    """x of (A + lam diag(A)) x = b, A block tridiagonal: D (n, 6, 6) its diagonal blocks, C (n - 1, 6, 6) = A[f+1][f];
+    None if a diagonal block is not positive definite.  Forward: S_f = D_f (damped) - M_{f-1} M_{f-1}^T = L_f L_f^T,
+    L_f y_f = b_f - M_{f-1} y_{f-1}, M_f = C_f L_f^-T; back: L_f^T x_f = y_f - M_f^T x_{f+1}."""
+    n = len(D)
+    L, inv, M, y, x = np.zeros((n, 6, 6)), np.zeros((n, 6)), np.zeros((n, 6, 6)), np.zeros((n, 6)), np.zeros((n, 6))
+    for f in range(n):
+        S = np.array(D[f], dtype=np.float64)
+        S[np.diag_indices(6)] += lam * np.diag(D[f])
+        r = np.array(b[f], dtype=np.float64)
+        if f:
+            for k in range(6):
+                S = S - np.outer(M[f - 1][:, k], M[f - 1][:, k])
+                r = r - M[f - 1][:, k] * y[f - 1, k]
+        iv = chol6(S)
+        if iv is None:
+            return None
+        L[f], inv[f] = np.tril(S), iv
+        for i in range(6):
+            s = r[i]
+            for k in range(i):
+                s -= L[f, i, k] * y[f, k]
+            y[f, i] = s * iv[i]
+        if f + 1 < n:
+            for c in range(6):
+                s = C[f][:, c].copy()
+                for k in range(c):
+                    s = s - M[f][:, k] * L[f, c, k]
+                M[f][:, c] = s * iv[c]
+    for f in range(n - 1, -1, -1):
+        r = y[f].copy()
+        if f + 1 < n:
+            for k in range(6):
+                r = r - M[f][k, :] * x[f + 1, k]
+        for i in range(5, -1, -1):
+            s = r[i]
+            for k in range(i + 1, 6):
+                s -= L[f, k, i] * x[f, k]
+            x[f, i] = s * inv[f, i]
+    return x
+
+
+def dense(D, C):
+    """the assembled matrix of tridiag_solve's blocks (for the tests)"""
+    n = len(D)
+    A = np.zeros((6 * n, 6 * n))
+    for f in range(n):
+        A[6 * f:6 * f + 6, 6 * f:6 * f + 6] = D[f]
+        if f + 1 < n:
+            A[6 * f + 6:6 * f + 12, 6 * f:6 * f + 6] = C[f]
+            A[6 * f:6 * f + 6, 6 * f + 6:6 * f + 12] = C[f].T
+    return A
+
+
+class Problem:
+    """the frames' corners (taking-part slots; reverse: accumulated in reversed slot order, a rounding perturbation) and the weights"""
+
+    def __init__(self, obs, tag_map, K, dist, tag_size, sigma_px, sigma_rot, sigma_trans, reverse=False):
+        self.cam = LR.camera(K, dist)
+        self.model = LR.OneCamera(self.cam)
+        self.obs, self.tag_map, self.tag_size = obs, tag_map, tag_size
+        self.w = 1.0 / (sigma_px * sigma_px)
+        self.sr, self.st = float(sigma_rot), float(sigma_trans)
+        self.n = len(obs)
+        self.part, self.pts = [], []
+        for rows in obs:
+            part = LR.gather(rows, tag_map)[1]
+            self.part.append(part)
+            order = part[::-1] if reverse else part
+            self.pts.append(LR.frame_points(self.model, rows, tag_map, tag_size, order)[:2] if part else None)
+        self.n_tags = np.array([len(p) for p in self.part], dtype=np.int64)
+
+    def data_cost(self, f, P):
+        """the frame's squared pixel error at P (not yet weighted)"""
+        if self.pts[f] is None:
+            return 0.0
+        return float(LR.corner_costs(self.cam, P[0], P[1], *self.pts[f]).sum())
+
+    def motion_cost(self, Pa, Pb):
+        m = motion_residual(Pa, Pb, self.sr, self.st)
+        return float(m @ m)
+
+    def linearise(self, P):
+        """everything a trial needs at the poses P: per frame the pixel cost c, H, g; per pair the motion blocks"""
+        n = self.n
+        lin = {"c": np.zeros(n), "H": np.zeros((n, 6, 6)), "g": np.zeros((n, 6)), "mc": np.zeros(n), "QN": np.zeros((n, 6, 6)),
+               "QP": np.zeros((n, 6, 6)), "C": np.zeros((n, 6, 6)), "gN": np.zeros((n, 6)), "gP": np.zeros((n, 6))}
+        for f in range(n):
+            if self.pts[f] is not None:
+                lin["c"][f], lin["H"][f], lin["g"][f] = LR.linearise(self.cam, P[f][0], P[f][1], *self.pts[f])
+            if f + 1 < n:
+                RD, tD = relative(P[f], P[f + 1])
+                m = np.concatenate([log_so3(RD) * (1.0 / self.sr), tD * (1.0 / self.st)])
+                Jn, Jp = motion_jacobians(RD, tD, self.sr, self.st)
+                lin["mc"][f] = m @ m
+                lin["QN"][f], lin["QP"][f], lin["C"][f] = Jp.T @ Jp, Jn.T @ Jn, Jn.T @ Jp
+                lin["gN"][f], lin["gP"][f] = Jp.T @ m, Jn.T @ m
+        lin["cost"] = float(np.sum(lin["c"] * self.w + lin["mc"]))
+        return lin
+
+    def blocks(self, lin):
+        """(D, C, b) of tridiag_solve, in the assembly order of the module docstring"""
+        n = self.n
+        D, g = lin["H"] * self.w, lin["g"] * self.w
+        D[1:] = D[1:] + lin["QP"][:n - 1]
+        g[1:] = g[1:] + lin["gP"][:n - 1]
+        D[:n - 1] = D[:n - 1] + lin["QN"][:n - 1]
+        g[:n - 1] = g[:n - 1] + lin["gN"][:n - 1]
+        return D, lin["C"][:n - 1], -g
+
+
+def pose_of_seed(rec):
+    """camera<-world of an asl_cam_pose's world<-camera T"""
+    T = np.asarray(rec["T"], dtype=np.float64)
+    R = T[:3, :3].T
+    return R, -(R @ T[:3, 3])
+
+
+def candidates(pb, seed):
+    """per frame None (no seed pose) or (A, B, has_b)"""
+    out = []
+    for f in range(pb.n):
+        if seed["status"][f] != 0:
+            out.append(None)
+            continue
+        A = pose_of_seed(seed[f])
+        if len(pb.part[f]) != 1:
+            out.append((A, A, False))
+            continue
+        M = pb.tag_map["T"][pb.obs[f]["id"][pb.part[f][0]]].reshape(3, 4)
+        Rm, tm = LR.mirrored(A[0] @ M[:, :3], A[0] @ M[:, 3] + A[1])     # camera<-tag = A map[id], mirrored
+        RB = Rm @ M[:, :3].T
+        out.append((A, (RB, tm - RB @ M[:, 3]), True))
+    return out
+
+
+def chain_costs(pb, cand):
+    """(posed frames, data costs (n_posed, 2) weighted, transition costs (n_posed, 2, 2) [from, to] of each posed frame from its
+    predecessor, divided by the gap; the first one's are 0)"""
+    posed = [f for f in range(pb.n) if cand[f] is not None]
+    d = np.zeros((len(posed), 2))
+    tr = np.zeros((len(posed), 2, 2))
+    for k, f in enumerate(posed):
+        for b in (0, 1):
+            d[k, b] = pb.data_cost(f, cand[f][b]) * pb.w
+            for a in (0, 1):
+                if k:
+                    p = posed[k - 1]
+                    tr[k, a, b] = pb.motion_cost(cand[p][a], cand[f][b]) / float(f - p)
+    return posed, d, tr
+
+
+def chain_choose(d, tr):
+    """the two-state dynamic programme -> choice per posed frame (0 A, 1 B)"""
+    n = len(d)
+    c = [d[0, 0], d[0, 1]]
+    back = np.zeros((n, 2), dtype=np.int64)
+    for k in range(1, n):
+        nc = [0.0, 0.0]
+        for b in (0, 1):
+            best, alt = c[0] + tr[k, 0, b], c[1] + tr[k, 1, b]
+            if alt < best:
+                best, back[k, b] = alt, 1
+            nc[b] = best + d[k, b]
+        c = nc
+    choice = np.zeros(n, dtype=np.int64)
+    cur = 1 if c[1] < c[0] else 0
+    for k in range(n - 1, -1, -1):
+        choice[k] = cur
+        cur = back[k, cur]
+    return choice
+
+
+def chain_total(d, tr, choice):
+    """the chain cost of a choice (for comparing choices that tie to rounding)"""
+    return float(sum(d[k, choice[k]] + (tr[k, choice[k - 1], choice[k]] if k else 0.0) for k in range(len(d))))
+
+
+def smooth(obs, tag_map, K, dist, tag_size, seed, sigma_px, sigma_rot, sigma_trans, max_iters, reverse=False):
+    """obs (n_frames, max_tags) asl_obs records, tag_map (n_ids,) asl_map_tag records, seed (n_frames,) asl_cam_pose ->
+    ((n_frames,) CAM_POSE_DTYPE, SMOOTH_RESULT_DTYPE record, trace); trace: "posed", "d", "tr", "choice" of the chain"""
+    obs = np.asarray(obs)
+    pb = Problem(obs, tag_map, K, dist, tag_size, sigma_px, sigma_rot, sigma_trans, reverse)
+    n = pb.n
+    out = np.zeros(n, dtype=CAM_POSE_DTYPE)
+    out["T"] = np.eye(4)
+    out["seed_slot"] = -1
+    out["status"] = FRAME_NOTHING
+    res = np.zeros((), dtype=SMOOTH_RESULT_DTYPE)
+    cand = candidates(pb, seed)
+    posed, d, tr = chain_costs(pb, cand)
+    trace = {"posed": posed, "d": d, "tr": tr, "choice": np.zeros(0, dtype=np.int64)}
+    if not posed:
+        res["status"] = NO_POSED_FRAME
+        return out, res, trace
+    choice = chain_choose(d, tr)
+    trace["choice"] = choice
+    P, src = [], -1
+    for f in range(n):
+        if cand[f] is not None:
+            src += 1
+        k = max(src, 0)
+        P.append(cand[posed[k]][choice[k]])
+        if cand[f] is not None:
+            out["seed_slot"][f] = seed["seed_slot"][f] + FLIPPED * choice[k]
+    out["n_tags"] = pb.n_tags
+    res["n_frames_data"] = int((pb.n_tags > 0).sum())
+    res["n_filled"] = n - len(posed)
+    res["n_flipped"] = int(choice.sum())
+
+    lin = pb.linearise(P)
+    corners = 4.0 * float(pb.n_tags.sum())
+
+    def rms(c, k):
+        return np.sqrt(c / k) if k > 0 else 0.0
+
+    res["cost_seed"], res["rms_seed_px"] = lin["cost"], rms(float(lin["c"].sum()), corners)
+    out["rms_seed_px"] = [rms(c, 4.0 * k) for c, k in zip(lin["c"], pb.n_tags)]
+    status, iters = OK, 0
+    if not np.isfinite(lin["cost"]):
+        status = NON_FINITE
+    else:
+        lam, solved = LAMBDA0, False
+        for _ in range(int(max_iters)):
+            iters += 1
+            delta = tridiag_solve(*pb.blocks(lin), lam)
+            if delta is None:
+                lam *= 10
+                continue
+            solved = True
+            Pn = [update(P[f], delta[f]) for f in range(n)]
+            ln = pb.linearise(Pn)
+            if ln["cost"] < lin["cost"]:
+                stop = lin["cost"] - ln["cost"] < REL_STOP * lin["cost"]
+                P, lin = Pn, ln
+                lam *= 0.1
+                if stop:
+                    break
+            else:
+                lam *= 10
+        if not solved:
+            status = NOT_POSITIVE_DEFINITE
+    for f in range(n):
+        T = np.eye(4)
+        T[:3, :3] = P[f][0].T
+        T[:3, 3] = -(P[f][0].T @ P[f][1])
+        out["T"][f] = T
+    out["rms_px"] = [rms(c, 4.0 * k) for c, k in zip(lin["c"], pb.n_tags)]
+    out["status"] = FRAME_FAILED if status != OK else np.where(pb.n_tags > 0, FRAME_DATA, FRAME_PRIOR)
+    res["cost"], res["rms_px"], res["iterations"], res["status"] = lin["cost"], rms(float(lin["c"].sum()), corners), iters, status
+    return out, res, trace

@@ -1,0 +1,126 @@
+#!/usr/bin/env python3
+"""Sequence localisation (asl_smooth_frames_device) on the bench workload: 1024 device-rendered 1280x720 frames of the
+seeded 20-tag scene along the bench trajectory -> detect + PnP -> asl_obs records on the device -> the per-frame
+localisation (the seed) -> one smoothed pose per frame.
+
+Prints one JSON line: the time of the smoothing and of the per-frame localisation of the same block (HIP events around each
+call alone, the two alternating inside every repetition, median of --reps after warm-up) and the position and rotation
+error against the renderer's ground truth before (the per-frame poses) and after.  --drop-every N empties every Nth frame
+first, so that the smoothing has holes to fill.
+
+    python tools/smooth_lab.py [--frames 1024] [--reps 20] [--max-tags 32] [--sigma-px 0.3] [--sigma-rot 0.01]
+                               [--sigma-trans 0.05] [--max-iters 20] [--drop-every 0]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def rot_err(Ta, Tb):
+    R = Ta[:3, :3] @ Tb[:3, :3].T
+    return float(np.arccos(np.clip((np.trace(R) - 1) / 2, -1, 1)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=1024)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--max-tags", type=int, default=32)
+    ap.add_argument("--sigma-px", type=float, default=0.3)
+    ap.add_argument("--sigma-rot", type=float, default=0.01)
+    ap.add_argument("--sigma-trans", type=float, default=0.05)
+    ap.add_argument("--max-iters", type=int, default=20)
+    ap.add_argument("--drop-every", type=int, default=0)
+    a = ap.parse_args()
+
+    import torch
+
+    import bench
+    from aprilslam_amd import _lib, synth
+    from aprilslam_amd.localize import CAM_POSE_DTYPE, TagMap
+
+    dev = torch.device("cuda:0")
+    W, H, n, mt = bench.W, bench.H, a.frames, a.max_tags
+    K = synth.camera_matrix(W, H, 45.0)
+    det = _lib.Detector("tagStandard41h12", id_limit=0)
+    frames, _, _ = bench.render_stream_device(det, n, dev)
+    tags = synth.random_scene(W, H, bench.NTAGS, np.random.default_rng(20250620 + 1), tag_size_outer=bench.TAG_OUTER)
+    rec = TagMap.from_scene(tags).as_records()
+    stream = torch.cuda.Stream(dev)
+    d_obs = torch.empty((n, mt, _lib.OBS_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    d_map = torch.from_numpy(rec.view(np.uint8)).to(dev)
+    d_seed = torch.empty((n, CAM_POSE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    d_out = torch.empty((n, CAM_POSE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    d_res = torch.empty(_lib.SMOOTH_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    det.submit_device(frames.data_ptr(), n, 3, W, H, stream=stream.cuda_stream, K=K, dist=np.zeros(4), tag_size=bench.TAG_INNER)
+    det.pack_observations_device(d_obs.data_ptr(), mt, stream=stream.cuda_stream)
+    det.collect()
+    if a.drop_every > 0:
+        obs = d_obs.cpu().numpy().view(_lib.OBS_DTYPE).reshape(n, mt).copy()
+        obs["flags"][a.drop_every - 1::a.drop_every] = 0
+        d_obs.copy_(torch.from_numpy(obs.view(np.uint8).reshape(n, mt, -1)))
+
+    def localize():
+        det.localize_device(d_obs.data_ptr(), n, mt, d_map.data_ptr(), len(rec), d_seed.data_ptr(), K, None, bench.TAG_INNER,
+                            stream=stream.cuda_stream)
+
+    def smooth():
+        det.smooth_device(d_obs.data_ptr(), n, mt, d_map.data_ptr(), len(rec), d_seed.data_ptr(), d_out.data_ptr(), d_res.data_ptr(), K, None,
+                          bench.TAG_INNER, sigma_px=a.sigma_px, sigma_rot=a.sigma_rot, sigma_trans=a.sigma_trans, max_iters=a.max_iters,
+                          stream=stream.cuda_stream)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    legs = [localize, smooth]
+    with torch.cuda.stream(stream):
+        for _ in range(a.warmup):
+            for fn in legs:
+                fn()
+        times = [[] for _ in legs]
+        for _ in range(a.reps):
+            for k, fn in enumerate(legs):    # alternating: every repetition runs each leg once, back to back
+                times[k].append(timed(fn))
+    stream.synchronize()
+    seed = d_seed.cpu().numpy().view(CAM_POSE_DTYPE).reshape(n)
+    out = d_out.cpu().numpy().view(CAM_POSE_DTYPE).reshape(n)
+    res = d_res.cpu().numpy().view(_lib.SMOOTH_RESULT_DTYPE)[0]
+
+    flip = np.diag([1.0, -1.0, -1.0, 1.0])
+    truths = [np.linalg.inv(flip @ synth.view_matrix(p, r)) for p, r in bench.camera_trajectory(n)]
+    rms = lambda v: float(np.sqrt(np.mean(np.square(v)))) if len(v) else None  # noqa: E731
+
+    def errors(poses, keep):
+        fr = np.flatnonzero(keep)
+        return {"frames": int(len(fr)), "rotation_mrad": rms([rot_err(poses["T"][f], truths[f]) for f in fr]) * 1e3 if len(fr) else None,
+                "translation_mm": rms([np.linalg.norm(poses["T"][f][:3, 3] - truths[f][:3, 3]) for f in fr]) * bench.MM_PER_UNIT if len(fr) else None}
+
+    posed = seed["status"] == 0
+    line = {
+        "metric": "asl_smooth_frames_device", "frames": n, "max_tags": mt, "tags_per_frame": bench.NTAGS,
+        "sigma_px": a.sigma_px, "sigma_rot": a.sigma_rot, "sigma_trans": a.sigma_trans, "max_iters": a.max_iters, "drop_every": a.drop_every,
+        "smooth_ms_median": float(np.median(times[1])), "smooth_ms_min": float(np.min(times[1])),
+        "localize_ms_median": float(np.median(times[0])), "localize_ms_min": float(np.min(times[0])), "reps": a.reps,
+        "result": {k: (float(res[k]) if res[k].dtype.kind == "f" else int(res[k])) for k in res.dtype.names if k != "reserved"},
+        "before": errors(seed, posed), "after_same_frames": errors(out, posed & np.isin(out["status"], (0, 6))),
+        "after_filled_frames": errors(out, ~posed & np.isin(out["status"], (0, 6))),
+        "note": "world<-camera vs the renderer's ground truth; before = the per-frame localisation (the seed)",
+    }
+    print(json.dumps(line))
+    det.close()
+
+
+if __name__ == "__main__":
+    main()
