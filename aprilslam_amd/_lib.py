@@ -51,7 +51,7 @@ EXPORTS = [
     "asl_localize_frames_device", "asl_localize_batch", "asl_localize_cov_frames_device", "asl_localize_cov_batch",
     "asl_pose_cov_device", "asl_solve_pnp_cov_batch", "asl_calibrate_frames_device", "asl_calibrate_batch",
     "asl_localize_rig_frames_device", "asl_localize_rig_cov_frames_device", "asl_localize_rig_batch", "asl_localize_rig_cov_batch",
-    "asl_map_frames_device", "asl_map_batch", "asl_smooth_frames_device", "asl_smooth_batch",
+    "asl_map_frames_device", "asl_map_batch", "asl_smooth_frames_device", "asl_smooth_batch", "asl_smooth_cov_frames_device", "asl_smooth_cov_batch",
     "asl_debug_fetch", "asl_debug_refit", "asl_debug_division_check", "asl_stage_times", "asl_set_profiling", "asl_debug_phase_cycles",
 ]
 
@@ -120,6 +120,8 @@ def load():
     L.asl_smooth_frames_device.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, vp, C.c_double, C.c_double, C.c_double, i32,
                                            vp, vp, vp]
     L.asl_smooth_batch.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, vp, C.c_double, C.c_double, C.c_double, i32, vp, vp]
+    L.asl_smooth_cov_frames_device.argtypes = L.asl_smooth_frames_device.argtypes[:-1] + [vp, vp]
+    L.asl_smooth_cov_batch.argtypes = L.asl_smooth_batch.argtypes + [vp]
     L.asl_debug_fetch.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.asl_debug_refit.argtypes = [vp, i32, vp, C.c_size_t]
     L.asl_debug_division_check.argtypes = [vp, i32, vp, C.c_size_t]
@@ -509,12 +511,15 @@ class Detector:
                                             int(world_id), int(max_iters), _ptr(map_ptr), _opt_ptr(std_ptr), _ptr(poses_ptr),
                                             _ptr(result_ptr), _ptr(stream)))
 
-    def smooth(self, obs, tag_map, K, dist, tag_size, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, seed=None):
+    def smooth(self, obs, tag_map, K, dist, tag_size, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, seed=None,
+               with_cov=False):
         """asl_smooth_batch: host records obs (n_frames, max_tags) OBS_DTYPE of one camera's consecutive frames against tag_map
         -> ((n_frames,) CAM_POSE_DTYPE, world<-camera for EVERY frame, SMOOTH_RESULT_DTYPE record): the reprojection error of
         all frames (corner sigma sigma_px) plus a random-walk motion prior between consecutive frames (sigma_rot rad,
         sigma_trans scene units per frame step).  seed: (n_frames,) CAM_POSE_DTYPE as localize() returns them for the same
-        obs; None: that localisation runs first."""
+        obs; None: that localisation runs first.
+        with_cov: asl_smooth_cov_batch -> (poses, result, (n_frames,) POSE_COV_DTYPE), every pose's marginal covariance under
+        the three sigmas (the same poses and result, byte for byte)."""
         o = _obs_records(obs)
         m = _map_records(tag_map)
         keep, Kp, dpp, nd = _camera(K, dist, square=True)
@@ -523,21 +528,30 @@ class Detector:
             raise ValueError("seed must hold one pose per frame")
         out = np.zeros(o.shape[0], dtype=CAM_POSE_DTYPE)
         res = np.zeros((), dtype=SMOOTH_RESULT_DTYPE)
-        check(self._L.asl_smooth_batch(self._h, o.ctypes.data if o.size else None, o.shape[0], o.shape[1], m.ctypes.data if m.size else None,
-                                       len(m), Kp, dpp, nd, float(tag_size), None if sd is None else sd.ctypes.data, float(sigma_px),
-                                       float(sigma_rot), float(sigma_trans), int(max_iters), out.ctypes.data if out.size else None,
-                                       res.ctypes.data))
-        return out, res
+        args = (self._h, o.ctypes.data if o.size else None, o.shape[0], o.shape[1], m.ctypes.data if m.size else None,
+                len(m), Kp, dpp, nd, float(tag_size), None if sd is None else sd.ctypes.data, float(sigma_px),
+                float(sigma_rot), float(sigma_trans), int(max_iters), out.ctypes.data if out.size else None, res.ctypes.data)
+        if not with_cov:
+            check(self._L.asl_smooth_batch(*args))
+            return out, res
+        cov = np.zeros(o.shape[0], dtype=POSE_COV_DTYPE)
+        check(self._L.asl_smooth_cov_batch(*args, cov.ctypes.data if cov.size else None))
+        return out, res, cov
 
     def smooth_device(self, obs_ptr, n_frames, max_tags, map_ptr, n_ids, seed_ptr, out_ptr, result_ptr, K, dist, tag_size, sigma_px=1.0,
-                      sigma_rot=0.05, sigma_trans=0.5, max_iters=20, stream=0):
+                      sigma_rot=0.05, sigma_trans=0.5, max_iters=20, stream=0, cov_ptr=None):
         """asl_smooth_frames_device: obs_ptr (n_frames x max_tags asl_obs), map_ptr (n_ids asl_map_tag), seed_ptr (n_frames
         asl_cam_pose, as localize_device wrote them), out_ptr (n_frames asl_cam_pose) and result_ptr (one asl_smooth_result)
-        are device addresses; enqueued on `stream`, no wait."""
+        are device addresses; enqueued on `stream`, no wait.  cov_ptr not None (n_frames asl_pose_cov):
+        asl_smooth_cov_frames_device."""
         keep, Kp, dpp, nd = _camera(K, dist, square=True)
-        check(self._L.asl_smooth_frames_device(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids), Kp, dpp, nd,
-                                               float(tag_size), _ptr(seed_ptr), float(sigma_px), float(sigma_rot), float(sigma_trans),
-                                               int(max_iters), _ptr(out_ptr), _ptr(result_ptr), _ptr(stream)))
+        args = (self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids), Kp, dpp, nd,
+                float(tag_size), _ptr(seed_ptr), float(sigma_px), float(sigma_rot), float(sigma_trans),
+                int(max_iters), _ptr(out_ptr), _ptr(result_ptr))
+        if cov_ptr is None:
+            check(self._L.asl_smooth_frames_device(*args, _ptr(stream)))
+        else:
+            check(self._L.asl_smooth_cov_frames_device(*args, _ptr(cov_ptr), _ptr(stream)))
 
     def collect_view(self):
         """Wait for the submitted batch; (dets, poses or None, n_per_frame) as numpy VIEWS of the detector's page-locked result

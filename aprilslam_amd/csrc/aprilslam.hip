@@ -1653,12 +1653,13 @@ static int check_smooth_args(const asl_detector *d, const void *obs, int n_frame
     return ASL_OK;
 }
 
-// All device pointers; everything is enqueued on st, nothing waits
+// All device pointers; everything is enqueued on st, nothing waits.  d_cov: NULL, or the frames' asl_pose_cov (two more launches)
 static int launch_smooth(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids, const double *K,
                          const double *dist, int n_dist, double tag_size, const void *d_seed, double sigma_px, double sigma_rot,
-                         double sigma_trans, int max_iters, void *d_out, void *d_result, hipStream_t st)
+                         double sigma_trans, int max_iters, void *d_out, void *d_result, void *d_cov, hipStream_t st)
 {
     static_assert(sizeof(SmoothResultRec) == sizeof(asl_smooth_result) && sizeof(asl_smooth_result) == 64, "asl_smooth_result layout");
+    static_assert(sizeof(PoseCovRec) == sizeof(asl_pose_cov) && sizeof(asl_pose_cov) == 304, "asl_pose_cov layout");
     const size_t n = (size_t)n_frames;
     SmoothBufs b{};
     b.n = n_frames;
@@ -1698,37 +1699,74 @@ static int launch_smooth(asl_detector *d, const void *d_obs, int n_frames, int m
     }
     hipLaunchKernelGGL(k_smooth_finish, per_thread, wg, 0, st, b, (CamPoseRec *)d_out, (SmoothResultRec *)d_result);
     range_pop();
+    if (d_cov) {
+        range_push("smooth: covariance");
+        hipLaunchKernelGGL(k_smooth_cov, one, wave, 0, st, b, w, (PoseCovRec *)d_cov);
+        hipLaunchKernelGGL(k_smooth_cov_finish, per_thread, wg, 0, st, b, sigma_px, (PoseCovRec *)d_cov);
+        range_pop();
+    }
     HIPCHK(hipGetLastError());
     return ASL_OK;
+}
+
+static bool smooth_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// d_cov NULL: the plain call
+static int smooth_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids, const double *K,
+                                const double *dist, int n_dist, double tag_size, const void *d_seed, double sigma_px, double sigma_rot,
+                                double sigma_trans, int max_iters, void *d_out, void *d_result, void *d_cov, bool with_cov, void *stream)
+{
+    if (int rc = check_smooth_args(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, sigma_px, sigma_rot, sigma_trans,
+                                   max_iters, d_out, d_result))
+        return rc;
+    if (!d_seed || (with_cov && !d_cov)) return fail(ASL_EINVAL, "NULL argument");
+    const size_t poses = sizeof(asl_cam_pose) * (size_t)n_frames, covs = sizeof(asl_pose_cov) * (size_t)n_frames;
+    if (smooth_overlap(d_seed, poses, d_out, poses)) return fail(ASL_EINVAL, "d_out overlaps d_seed");
+    if (with_cov && (smooth_overlap(d_cov, covs, d_out, poses) || smooth_overlap(d_cov, covs, d_seed, poses)))
+        return fail(ASL_EINVAL, "d_cov overlaps d_out or d_seed");
+    HIPCHK(hipSetDevice(d->device));
+    return launch_smooth(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, d_seed, sigma_px, sigma_rot, sigma_trans,
+                         max_iters, d_out, d_result, with_cov ? d_cov : nullptr, (hipStream_t)stream);
 }
 
 extern "C" int asl_smooth_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
                                         const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed, double sigma_px,
                                         double sigma_rot, double sigma_trans, int max_iters, void *d_out, void *d_result, void *stream)
 {
-    if (int rc = check_smooth_args(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, sigma_px, sigma_rot, sigma_trans,
-                                   max_iters, d_out, d_result))
-        return rc;
-    if (!d_seed) return fail(ASL_EINVAL, "NULL argument");
-    const uintptr_t s0 = (uintptr_t)d_seed, o0 = (uintptr_t)d_out, bytes = sizeof(asl_cam_pose) * (uintptr_t)n_frames;
-    if (s0 < o0 + bytes && o0 < s0 + bytes) return fail(ASL_EINVAL, "d_out overlaps d_seed");
-    HIPCHK(hipSetDevice(d->device));
-    return launch_smooth(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, d_seed, sigma_px, sigma_rot, sigma_trans,
-                         max_iters, d_out, d_result, (hipStream_t)stream);
+    return smooth_frames_device(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, d_seed, sigma_px, sigma_rot, sigma_trans,
+                                max_iters, d_out, d_result, nullptr, false, stream);
 }
 
-extern "C" int asl_smooth_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
-                                const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed, double sigma_px,
-                                double sigma_rot, double sigma_trans, int max_iters, asl_cam_pose *out, asl_smooth_result *result)
+extern "C" int asl_smooth_cov_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                            const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed,
+                                            double sigma_px, double sigma_rot, double sigma_trans, int max_iters, void *d_out, void *d_result,
+                                            void *d_cov, void *stream)
+{
+    return smooth_frames_device(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, d_seed, sigma_px, sigma_rot, sigma_trans,
+                                max_iters, d_out, d_result, d_cov, true, stream);
+}
+
+static int smooth_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids, const double *K,
+                        const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed, double sigma_px, double sigma_rot,
+                        double sigma_trans, int max_iters, asl_cam_pose *out, asl_smooth_result *result, asl_pose_cov *cov, bool with_cov)
 {
     if (int rc = check_smooth_args(d, obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, sigma_px, sigma_rot, sigma_trans,
                                    max_iters, out, result))
         return rc;
+    if (with_cov && !cov) return fail(ASL_EINVAL, "NULL argument");
     HIPCHK(hipSetDevice(d->device));
     const size_t n = (size_t)n_frames;
     asl_cam_pose *d_out = nullptr, *d_seed = nullptr;
     asl_smooth_result *d_result = nullptr;
-    if (carve_ws(d->solve_out, [&](WsCarve &c) { d_result = c.take<asl_smooth_result>(1); d_out = c.take<asl_cam_pose>(n); d_seed = c.take<asl_cam_pose>(n); }))
+    asl_pose_cov *d_cov = nullptr;
+    if (carve_ws(d->solve_out, [&](WsCarve &c) {
+            d_result = c.take<asl_smooth_result>(1); d_out = c.take<asl_cam_pose>(n); d_seed = c.take<asl_cam_pose>(n);
+            if (with_cov) d_cov = c.take<asl_pose_cov>(n);
+        }))
         return fail(ASL_ENOMEM, "sequence localisation workspace allocation failed");
     if (int rc = upload_obs(d, "sequence localisation", obs, n_frames, max_tags, map, n_ids)) return rc;
     if (seed)
@@ -1737,11 +1775,29 @@ extern "C" int asl_smooth_batch(asl_detector *d, const asl_obs *obs, int n_frame
         launch_localize(d, {d->loc_obs.p, 0, n_frames, max_tags, d->loc_map.p, n_ids, K, dist, n_dist, nullptr, tag_size, 0.0, 0.0, d_seed, nullptr, false},
                         nullptr);
     if (int rc = launch_smooth(d, d->loc_obs.p, n_frames, max_tags, d->loc_map.p, n_ids, K, dist, n_dist, tag_size, d_seed, sigma_px, sigma_rot,
-                               sigma_trans, max_iters, d_out, d_result, nullptr))
+                               sigma_trans, max_iters, d_out, d_result, d_cov, nullptr))
         return rc;
     HIPCHK(hipMemcpy(out, d_out, sizeof(asl_cam_pose) * n, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(result, d_result, sizeof(asl_smooth_result), hipMemcpyDeviceToHost));
+    if (with_cov) HIPCHK(hipMemcpy(cov, d_cov, sizeof(asl_pose_cov) * n, hipMemcpyDeviceToHost));
     return ASL_OK;
+}
+
+extern "C" int asl_smooth_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed, double sigma_px,
+                                double sigma_rot, double sigma_trans, int max_iters, asl_cam_pose *out, asl_smooth_result *result)
+{
+    return smooth_batch(d, obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, seed, sigma_px, sigma_rot, sigma_trans, max_iters,
+                        out, result, nullptr, false);
+}
+
+extern "C" int asl_smooth_cov_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                    const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed, double sigma_px,
+                                    double sigma_rot, double sigma_trans, int max_iters, asl_cam_pose *out, asl_smooth_result *result,
+                                    asl_pose_cov *cov)
+{
+    return smooth_batch(d, obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, seed, sigma_px, sigma_rot, sigma_trans, max_iters,
+                        out, result, cov, true);
 }
 
 #include "debug_host.inc"

@@ -18,6 +18,9 @@
 //                k_smooth_decide one workgroup: the trial's cost in a fixed order, the accept rule, lambda, the stop
 //                k_smooth_commit an accepted trial copied over the current state, spread over the device
 //   end          k_smooth_finish one thread per frame: the records
+//   covariance   k_smooth_cov    (asl_smooth_cov_*, only when asked for) one wavefront: the undamped block Cholesky of the
+//                                returned state forward, the diagonal blocks of the inverse back, a 6x6 block from frame to frame
+//                k_smooth_cov_finish  one thread per frame: sigma_px, dof, status, and the zeros of a status 1 / 2
 // Serial by nature are the scan, the dynamic programme and the factor-and-solve: each is a chain over the frames, so each
 // is one wavefront that carries a small state (a maximum, two costs, a 6x6 coupling block) from frame to frame.  All trials are enqueued at once;
 // lm[SM_STOP] makes the ones after the stop return at once (k_map.inc works the same way).
@@ -27,11 +30,11 @@ struct SmoothResultRec {  // == asl_smooth_result, 64 bytes
     int32_t n_frames_data, n_filled, n_flipped, iterations, status, reserved[3];
 };
 
-enum { SM_COST = 0, SM_LAMBDA, SM_STOP, SM_ITERS, SM_STATUS, SM_COST0, SM_SOLVED, SM_PIX, SM_PIX0, SM_CORNERS, SM_NDATA, SM_TAKE, SM__N = 16 };
+enum { SM_COST = 0, SM_LAMBDA, SM_STOP, SM_ITERS, SM_STATUS, SM_COST0, SM_SOLVED, SM_PIX, SM_PIX0, SM_CORNERS, SM_NDATA, SM_TAKE, SM_COV, SM__N = 16 };
 enum { SMH_NPOSED = 0, SMH_FIRST, SMH_FAIL, SMH_NFLIP, SMH__N = 4 };
 #define SM_MOT 121                // per pair: QN 36, QP 36, C 36, gN 6, gP 6, |m|^2
 #define SM_SET (12 + 27 + 1 + SM_MOT)  // doubles per frame of one state: pose, normal equations, pixel cost, motion blocks
-#define SM_FAC 84                 // per frame of the factorisation: L 36, M 36, 1 / diag 6, y 6
+#define SM_FAC 84                 // per frame of the factorisation: L 36, M 36, 1 / diag 6, y 6 (k_smooth_cov: the undamped one, no y)
 #define SM_WG 256
 
 // One state of the solve over n frames, one allocation: poses (R 9, t 3), packed normal equations (21 + 6), pixel costs,
@@ -612,4 +615,192 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_finish(SmoothBufs b, CamPoseRe
     o->n_rejected = 0;
     o->status = status != 0 ? 4 : nt > 0 ? 0 : 6;
     o->seed_slot = b.code[f];
+}
+
+// The covariance of the returned poses (asl_smooth_cov_*): the diagonal blocks of A^-1, A the undamped matrix of
+// k_smooth_solve at set[0] (the state k_smooth_finish writes out; its blocks are the ones linearised there).  Forward as the
+// solve's, lambda = 0: S_f = D_f - M_{f-1} M_{f-1}^T = L_f L_f^T, M_f = C_f L_f^-T, kept in b.fac (free once the trials are
+// over; the LM's own last factor is damped and may be a rejected trial's).  Back, Sigma_{f+1} carried in LDS:
+//   Sigma_f = L_f^-T (I + M_f^T Sigma_{f+1} M_f) L_f^-1
+// T = Sigma_{f+1} M_f and X = I + M_f^T T an entry a lane (lane 6 i + j: entry (i, j)), then L^T Z = X a column a lane and
+// L^T Y^T = Z^T a row a lane.  Y's lower triangle, mirrored, is Sigma_f: the carry and, as R^T . R on each 3x3 block
+// (world<-camera: A = diag(-R^T, -R^T), the sign drops out), lower triangle mirrored again, the record's cov.
+// lm[SM_COV] is the status of every record: 1 without a solve, 2 if a pivot p of column c of S_f is not above
+// max(0, POSE_COV_PIVOT_TOL D_f[c][c]) (the inverse is global: no frame has a covariance then), else 0.  A lane loads the
+// next frame's operands before it works on the current one: the chain waits for arithmetic, not for memory.
+__global__ void __launch_bounds__(64) k_smooth_cov(SmoothBufs b, double w, PoseCovRec *__restrict__ cov)
+{
+    __shared__ double S[36], Mp[36], Cs[36], Sg[36], T[36], X[36], Rm[9], iv[6], dg[6];
+    const int lane = (int)threadIdx.x, n = b.n, i = lane / 6, j = lane % 6;
+    double *lm = b.lm;
+    if (b.head[SMH_NPOSED] == 0 || lm[SM_STATUS] != 0.0 || lm[SM_SOLVED] == 0.0) {
+        if (lane == 0) lm[SM_COV] = 1.0;
+        return;
+    }
+    const SmoothSet s = smooth_set(b.set[0], (size_t)n);
+    const int tri = i >= j ? TRI(i, j) : TRI(j, i);
+    double h = 0, qn = 0, cc = 0, qp = 0;   // frame f's H, QN_f, C_f and QP_{f-1} entry of this lane
+    if (lane < 36) {
+        h = s.ne[tri];
+        if (n > 1) { qn = s.mot[lane]; cc = s.mot[72 + lane]; }
+    }
+    for (int f = 0; f < n; f++) {
+        double v = 0;
+        if (lane < 36) {
+            v = h * w;
+            if (f > 0) v = v + qp;
+            if (f + 1 < n) v = v + qn;
+        }
+        const double d = v, c0 = cc;
+        qp = 0;
+        if (lane < 36 && f + 1 < n) {  // the next frame's
+            const double *mot = s.mot + SM_MOT * (size_t)f;
+            qp = mot[36 + lane];
+            h = s.ne[27 * (size_t)(f + 1) + tri];
+            if (f + 2 < n) { qn = mot[SM_MOT + lane]; cc = mot[SM_MOT + 72 + lane]; }
+        }
+        if (lane < 36 && f > 0)
+            for (int k = 0; k < 6; k++) v = v - Mp[6 * i + k] * Mp[6 * j + k];
+        __syncthreads();
+        if (lane < 36) {
+            S[lane] = v;
+            Cs[lane] = c0;
+            if (i == j) dg[i] = d;
+        }
+        __syncthreads();
+        double inv[6];
+#pragma unroll
+        for (int c = 0; c < 6; c++) {
+            const double p = S[7 * c];
+            if (!(p > 0 && p > POSE_COV_PIVOT_TOL * dg[c])) {  // the same LDS words in every lane: the whole wavefront leaves
+                if (lane == 0) lm[SM_COV] = 2.0;
+                return;
+            }
+            const double dc = sqrt(p);
+            inv[c] = 1.0 / dc;
+            __syncthreads();
+            if (lane < 36 && j == c) {
+                if (i == c) S[lane] = dc;
+                else if (i > c) S[lane] = S[lane] * inv[c];
+            }
+            __syncthreads();
+            if (lane < 36 && j > c && i >= j) S[lane] = S[lane] - S[6 * i + c] * S[6 * j + c];
+            __syncthreads();
+        }
+        double Mr[6] = {0, 0, 0, 0, 0, 0};
+        if (f + 1 < n && lane < 6) {  // row `lane` of M_f = C_f L_f^-T
+#pragma unroll
+            for (int c = 0; c < 6; c++) {
+                double t = Cs[6 * lane + c];
+#pragma unroll
+                for (int k = 0; k < c; k++) t -= Mr[k] * S[6 * c + k];
+                Mr[c] = t * inv[c];
+            }
+        }
+        __syncthreads();
+        double *fac = b.fac + SM_FAC * (size_t)f;
+        if (lane < 36) fac[lane] = i >= j ? S[lane] : 0.0;
+        if (lane == 0) {
+#pragma unroll
+            for (int a = 0; a < 6; a++) fac[72 + a] = inv[a];
+        }
+        if (f + 1 < n && lane < 6) {
+#pragma unroll
+            for (int c = 0; c < 6; c++) { Mp[6 * lane + c] = Mr[c]; fac[36 + 6 * lane + c] = Mr[c]; }
+        }
+        __syncthreads();
+    }
+    __threadfence();  // fac: written by some lanes, read by others below
+    if (lane == 0) lm[SM_COV] = 0.0;
+    double l = 0, m = 0, iq = 0, r = 0;   // frame f's L, M, 1 / diag and R entry of this lane
+    {
+        const double *fac = b.fac + SM_FAC * (size_t)(n - 1);
+        if (lane < 36) l = fac[lane];
+        if (lane < 6) iq = fac[72 + lane];
+        if (lane < 9) r = s.P[12 * (size_t)(n - 1) + lane];
+    }
+    for (int f = n - 1; f >= 0; f--) {
+        __syncthreads();
+        if (lane < 36) { S[lane] = l; Mp[lane] = m; }
+        if (lane < 6) iv[lane] = iq;
+        if (lane < 9) Rm[lane] = r;
+        if (f > 0) {  // the next frame's
+            const double *fac = b.fac - SM_FAC + SM_FAC * (size_t)f;
+            if (lane < 36) { l = fac[lane]; m = fac[36 + lane]; }
+            if (lane < 6) iq = fac[72 + lane];
+            if (lane < 9) r = s.P[12 * (size_t)(f - 1) + lane];
+        }
+        __syncthreads();
+        double x = i == j ? 1.0 : 0.0;
+        if (f + 1 < n) {
+            if (lane < 36) {
+                double t = 0;
+                for (int k = 0; k < 6; k++) t += Sg[6 * i + k] * Mp[6 * k + j];
+                T[lane] = t;
+            }
+            __syncthreads();
+            if (lane < 36) {
+                double a = 0;
+                for (int k = 0; k < 6; k++) a += Mp[6 * k + i] * T[6 * k + j];
+                x = x + a;
+            }
+        }
+        if (lane < 36) X[lane] = x;
+        __syncthreads();
+        if (lane < 6) {  // column `lane` of Z = L^-T X
+            double z[6];
+#pragma unroll
+            for (int a = 5; a >= 0; a--) {
+                double t = X[6 * a + lane];
+#pragma unroll
+                for (int k = a + 1; k < 6; k++) t -= S[6 * k + a] * z[k];
+                z[a] = t * iv[a];
+            }
+#pragma unroll
+            for (int a = 0; a < 6; a++) T[6 * a + lane] = z[a];
+        }
+        __syncthreads();
+        if (lane < 6) {  // row `lane` of Y = Z L^-1
+            double y[6];
+#pragma unroll
+            for (int a = 5; a >= 0; a--) {
+                double t = T[6 * lane + a];
+#pragma unroll
+                for (int k = a + 1; k < 6; k++) t -= S[6 * k + a] * y[k];
+                y[a] = t * iv[a];
+            }
+#pragma unroll
+            for (int a = 0; a < 6; a++) X[6 * lane + a] = y[a];
+        }
+        __syncthreads();
+        if (lane < 36) Sg[lane] = X[i >= j ? lane : 6 * j + i];
+        __syncthreads();
+        if (lane < 36) {  // U = Sigma diag(R, R)
+            const int c0 = 6 * i + 3 * (j / 3), jj = j % 3;
+            T[lane] = Sg[c0] * Rm[jj] + Sg[c0 + 1] * Rm[3 + jj] + Sg[c0 + 2] * Rm[6 + jj];
+        }
+        __syncthreads();
+        if (lane < 36) {  // diag(R, R)^T U
+            const int r0 = 18 * (i / 3) + j, ii = i % 3;
+            X[lane] = Rm[ii] * T[r0] + Rm[3 + ii] * T[r0 + 6] + Rm[6 + ii] * T[r0 + 12];
+        }
+        __syncthreads();
+        if (lane < 36) cov[f].cov[lane] = X[i >= j ? lane : 6 * j + i];
+    }
+}
+
+// What every record of the sequence shares, and the zeros of a sequence without a covariance
+__global__ void __launch_bounds__(SM_WG) k_smooth_cov_finish(SmoothBufs b, double sigma_px, PoseCovRec *__restrict__ cov)
+{
+    const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (f >= b.n) return;
+    const int status = (int)b.lm[SM_COV];
+    PoseCovRec *o = cov + f;
+    if (status != 0) {
+#pragma unroll
+        for (int k = 0; k < 36; k++) o->cov[k] = 0.0;
+    }
+    o->sigma_px = sigma_px;
+    o->dof = status == 1 ? 0 : 2 * (int)b.lm[SM_CORNERS] - 6;   // 8 a taking-part slot, less the 6 of one free pose
+    o->status = status;
 }

@@ -3,12 +3,14 @@ under a random-walk motion prior (asl_smooth_batch / asl_smooth_frames_device, k
 without a mapped tag is carried by its neighbours, a single-tag frame is kept out of its mirrored planar minimum by them,
 and corner noise is averaged over the sequence.
 
-    SmoothResult         the poses (CAM_POSE_DTYPE per frame), the SMOOTH_RESULT_DTYPE record, the filled / flipped masks
+    SmoothResult         the poses (CAM_POSE_DTYPE per frame), the SMOOTH_RESULT_DTYPE record, the filled / flipped masks and,
+                         from a solve with with_cov (asl_smooth_cov_batch), every pose's covariance (POSE_COV_DTYPE per frame)
     SMOOTH_RESULT_DTYPE  cost_seed, cost, rms_px, rms_seed_px, n_frames_data, n_filled, n_flipped, iterations, status
 """
 import numpy as np
 
-from ._lib import CAM_POSE_DTYPE, SMOOTH_RESULT_DTYPE
+from ._lib import CAM_POSE_DTYPE, POSE_COV_DTYPE, SMOOTH_RESULT_DTYPE
+from .localize import pose_std
 
 FRAME_DATA, FRAME_NOTHING, FRAME_FAILED, FRAME_PRIOR = 0, 1, 4, 6
 STATUS_OK, STATUS_NO_POSED_FRAME, STATUS_NOT_POSITIVE_DEFINITE, STATUS_NON_FINITE = 0, 1, 2, 3
@@ -21,10 +23,11 @@ __all__ = ["SmoothResult", "SMOOTH_RESULT_DTYPE", "CAM_POSE_DTYPE", "FRAME_DATA"
 class SmoothResult:
     """What Detector.smooth returns, named."""
 
-    def __init__(self, poses, result, seed=None):
+    def __init__(self, poses, result, seed=None, cov=None):
         self.poses = np.asarray(poses, dtype=CAM_POSE_DTYPE)
         self.result = np.asarray(result, dtype=SMOOTH_RESULT_DTYPE).reshape(())
         self.seed = seed    # the per-frame localisation that seeded the solve (None: not kept)
+        self.cov_records = None if cov is None else np.asarray(cov, dtype=POSE_COV_DTYPE)   # None: solved without with_cov
 
     @property
     def ok(self):
@@ -50,3 +53,25 @@ class SmoothResult:
     def trajectory(self):
         """(n_frames, 4, 4) world<-camera"""
         return np.array(self.poses["T"], dtype=np.float64).reshape(-1, 4, 4)
+
+    def _cov_records(self):
+        if self.cov_records is None:
+            raise ValueError("the solve ran without the covariance: pass with_cov=True")
+        return self.cov_records
+
+    @property
+    def cov(self):
+        """(n_frames, 6, 6) covariance of every frame's world<-camera pose, order (rx ry rz | px py pz) (include/aprilslam.h:
+        asl_pose_cov): the frame's marginal under the corner noise and the motion prior of the solve.  Zeros where
+        cov_status is not 0."""
+        return np.array(self._cov_records()["cov"], dtype=np.float64).reshape(-1, 6, 6)
+
+    @property
+    def cov_status(self):
+        """per frame, the same in all: 0 ok, 1 the solve has no covariance (it failed or had nothing to solve), 2 the
+        information matrix is not positive definite (e.g. no frame of the sequence has a mapped tag)"""
+        return np.array(self._cov_records()["status"])
+
+    def pose_std(self):
+        """(rotation std in rad (n_frames, 3), position std (n_frames, 3)): localize.pose_std of cov"""
+        return pose_std(self.cov)

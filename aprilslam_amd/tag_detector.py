@@ -218,11 +218,13 @@ class TagDetector:
                                            sigma_px=float(sigma_px) if with_cov else None)
 
     def localize_sequence(self, dets, poses, n_per_frame, tag_map, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20,
-                          max_tags=None):
+                          max_tags=None, with_cov=False):
         """The structured arrays detect_host / collect return for one camera's CONSECUTIVE frames -> smooth.SmoothResult: a
         world<-camera pose for every frame, the frames solved together with a random-walk motion prior (sigma_rot rad and
         sigma_trans scene units per frame step) next to the corners (sigma_px).  Packs, localises every frame on its own
-        (the seed, kept in the result) and smooths (asl_smooth_batch)."""
+        (the seed, kept in the result) and smooths (asl_smooth_batch).  with_cov: asl_smooth_cov_batch, and the result
+        carries every pose's covariance under the three sigmas (.cov, .cov_status, .pose_std()), the frames carried by the
+        prior alone included."""
         from .dist import pack_observations
         from .smooth import SmoothResult
         npf = np.asarray(n_per_frame, dtype=np.int64)
@@ -230,9 +232,9 @@ class TagDetector:
         obs = pack_observations(dets, poses, npf, mt)
         det = self.detector._det
         seed = det.localize(obs, tag_map, self._K(), self._dist(), self.tag_size)
-        out, res = det.smooth(obs, tag_map, self._K(), self._dist(), self.tag_size, sigma_px=sigma_px, sigma_rot=sigma_rot,
-                              sigma_trans=sigma_trans, max_iters=max_iters, seed=seed)
-        return SmoothResult(out, res, seed)
+        got = det.smooth(obs, tag_map, self._K(), self._dist(), self.tag_size, sigma_px=sigma_px, sigma_rot=sigma_rot,
+                         sigma_trans=sigma_trans, max_iters=max_iters, seed=seed, with_cov=with_cov)
+        return SmoothResult(got[0], got[1], seed, got[2] if with_cov else None)
 
     # -- camera calibration from frames of a known target (asl_calibrate_batch) ------------------------------------------
     def calibrate(self, frames, tag_map, n_dist=5, K_init=None, flags=0, max_iters=30):

@@ -441,6 +441,30 @@ int asl_smooth_batch(asl_detector *det, const asl_obs *obs, int n_frames, int ma
                      const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed, double sigma_px,
                      double sigma_rot, double sigma_trans, int max_iters, asl_cam_pose *out, asl_smooth_result *result);
 
+/* asl_smooth_frames_device with the covariance of every frame's world<-camera pose: d_out and d_result receive exactly what
+   the plain call writes, byte for byte; d_cov one asl_pose_cov per frame, in the convention above.  The objective is already
+   whitened by sigma_px, sigma_rot and sigma_trans, so the covariance of the stacked left updates (w, v) of all frames is
+   A^-1, A the undamped block-tridiagonal normal matrix at the returned poses, with no sigma^2 factor and no estimate from
+   the residuals; a frame's record is its own diagonal block Sigma_ff of A^-1 (the marginal: the other frames are not held
+   fixed), mapped as C_f = diag(-R_f^T, -R_f^T) Sigma_ff diag(-R_f^T, -R_f^T)^T.  Block Cholesky forward over the frames,
+   then back: Sigma_{n-1} = L^-T L^-1, Sigma_f = L_f^-T (I + M_f^T Sigma_{f+1} M_f) L_f^-1.  A frame carried by the prior
+   alone (status 6) has the covariance the prior leaves it: it grows with the distance to the nearest frames with data.
+   sigma_px: the given one.  dof: 8 (taking-part slots of all frames) - 6, the same in every record (0 with status 1).
+   status: 0 ok; 1 the solve has none (result status != 0: frame status 1 or 4); 2 A is not positive definite (a pivot not
+   above 1e-13 of its diagonal entry: e.g. posed frames without any taking-part slot, where the prior alone leaves six
+   directions free) -- in every record, because the inverse is global.  cov is all zero with status != 0.
+   ASL_EINVAL, nothing written: whatever the plain call refuses; a NULL d_cov; d_cov overlapping d_out or d_seed.
+   Deterministic: the same input gives the same bytes.  tests/smooth_cov_ref.py states the computation. */
+int asl_smooth_cov_frames_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                 const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed, double sigma_px,
+                                 double sigma_rot, double sigma_trans, int max_iters, void *d_out, void *d_result, void *d_cov,
+                                 void *stream);
+/* The same computation on host records, synchronous; seed as asl_smooth_batch. */
+int asl_smooth_cov_batch(asl_detector *det, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                         const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed, double sigma_px,
+                         double sigma_rot, double sigma_trans, int max_iters, asl_cam_pose *out, asl_smooth_result *result,
+                         asl_pose_cov *cov);
+
 /* ---- before the detector: the image-formation step on the device (reference src/simulation/renderer.py:197-274:
    purple clear colour, one GL_LINEAR-textured quad per tag, BGR read-back).  One plane per visible tag and frame, in
    painter's order (far to near); a plane with tex < 0 ends a frame's list. */

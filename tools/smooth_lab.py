@@ -6,10 +6,12 @@ localisation (the seed) -> one smoothed pose per frame.
 Prints one JSON line: the time of the smoothing and of the per-frame localisation of the same block (HIP events around each
 call alone, the two alternating inside every repetition, median of --reps after warm-up) and the position and rotation
 error against the renderer's ground truth before (the per-frame poses) and after.  --drop-every N empties every Nth frame
-first, so that the smoothing has holes to fill.
+first, so that the smoothing has holes to fill.  --cov adds the covariance leg: asl_smooth_cov_frames_device timed next
+to the plain call, the two alternating inside every repetition (smooth_cov_ms_median / _min), and under "cov" the median
+reported std of the frames with data and of the filled ones next to the errors above.
 
     python tools/smooth_lab.py [--frames 1024] [--reps 20] [--max-tags 32] [--sigma-px 0.3] [--sigma-rot 0.01]
-                               [--sigma-trans 0.05] [--max-iters 20] [--drop-every 0]
+                               [--sigma-trans 0.05] [--max-iters 20] [--drop-every 0] [--cov]
 """
 import argparse
 import json
@@ -38,13 +40,14 @@ def main():
     ap.add_argument("--sigma-trans", type=float, default=0.05)
     ap.add_argument("--max-iters", type=int, default=20)
     ap.add_argument("--drop-every", type=int, default=0)
+    ap.add_argument("--cov", action="store_true", help="also time the call with the covariance, alternating with the plain one")
     a = ap.parse_args()
 
     import torch
 
     import bench
     from aprilslam_amd import _lib, synth
-    from aprilslam_amd.localize import CAM_POSE_DTYPE, TagMap
+    from aprilslam_amd.localize import CAM_POSE_DTYPE, POSE_COV_DTYPE, TagMap
 
     dev = torch.device("cuda:0")
     W, H, n, mt = bench.W, bench.H, a.frames, a.max_tags
@@ -59,6 +62,7 @@ def main():
     d_seed = torch.empty((n, CAM_POSE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
     d_out = torch.empty((n, CAM_POSE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
     d_res = torch.empty(_lib.SMOOTH_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    d_cov = torch.empty((n, POSE_COV_DTYPE.itemsize), dtype=torch.uint8, device=dev)
     det.submit_device(frames.data_ptr(), n, 3, W, H, stream=stream.cuda_stream, K=K, dist=np.zeros(4), tag_size=bench.TAG_INNER)
     det.pack_observations_device(d_obs.data_ptr(), mt, stream=stream.cuda_stream)
     det.collect()
@@ -71,10 +75,13 @@ def main():
         det.localize_device(d_obs.data_ptr(), n, mt, d_map.data_ptr(), len(rec), d_seed.data_ptr(), K, None, bench.TAG_INNER,
                             stream=stream.cuda_stream)
 
-    def smooth():
+    def smooth(cov_ptr=None):
         det.smooth_device(d_obs.data_ptr(), n, mt, d_map.data_ptr(), len(rec), d_seed.data_ptr(), d_out.data_ptr(), d_res.data_ptr(), K, None,
                           bench.TAG_INNER, sigma_px=a.sigma_px, sigma_rot=a.sigma_rot, sigma_trans=a.sigma_trans, max_iters=a.max_iters,
-                          stream=stream.cuda_stream)
+                          stream=stream.cuda_stream, cov_ptr=cov_ptr)
+
+    def smooth_cov():
+        smooth(d_cov.data_ptr())
 
     def timed(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -84,7 +91,7 @@ def main():
         e1.synchronize()
         return e0.elapsed_time(e1)
 
-    legs = [localize, smooth]
+    legs = [localize, smooth] + ([smooth_cov] if a.cov else [])
     with torch.cuda.stream(stream):
         for _ in range(a.warmup):
             for fn in legs:
@@ -118,6 +125,18 @@ def main():
         "after_filled_frames": errors(out, ~posed & np.isin(out["status"], (0, 6))),
         "note": "world<-camera vs the renderer's ground truth; before = the per-frame localisation (the seed)",
     }
+    if a.cov:
+        cov = d_cov.cpu().numpy().view(POSE_COV_DTYPE).reshape(n)
+        std = np.sqrt(np.diagonal(cov["cov"], axis1=1, axis2=2))
+
+        def stds(keep):
+            fr = keep & (cov["status"] == 0)
+            return {"frames": int(fr.sum()), "rotation_mrad_median": float(np.median(np.linalg.norm(std[fr, :3], axis=1))) * 1e3 if fr.any() else None,
+                    "translation_mm_median": float(np.median(np.linalg.norm(std[fr, 3:], axis=1))) * bench.MM_PER_UNIT if fr.any() else None}
+        line["smooth_cov_ms_median"], line["smooth_cov_ms_min"] = float(np.median(times[2])), float(np.min(times[2]))
+        line["cov"] = {"status": sorted(set(cov["status"].tolist())), "dof": int(cov["dof"][0]),
+                       "std_same_frames": stds(posed & np.isin(out["status"], (0, 6))), "std_filled_frames": stds(~posed & np.isin(out["status"], (0, 6))),
+                       "note": "median over the frames of |std of the three rotation / translation components|: compare with the RMS errors above"}
     print(json.dumps(line))
     det.close()
 
