@@ -52,6 +52,7 @@ EXPORTS = [
     "asl_pose_cov_device", "asl_solve_pnp_cov_batch", "asl_calibrate_frames_device", "asl_calibrate_batch",
     "asl_localize_rig_frames_device", "asl_localize_rig_cov_frames_device", "asl_localize_rig_batch", "asl_localize_rig_cov_batch",
     "asl_map_frames_device", "asl_map_batch", "asl_smooth_frames_device", "asl_smooth_batch", "asl_smooth_cov_frames_device", "asl_smooth_cov_batch",
+    "asl_smooth_sequences_device", "asl_smooth_sequences_batch",
     "asl_debug_fetch", "asl_debug_refit", "asl_debug_division_check", "asl_stage_times", "asl_set_profiling", "asl_debug_phase_cycles",
 ]
 
@@ -122,6 +123,10 @@ def load():
     L.asl_smooth_batch.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, vp, C.c_double, C.c_double, C.c_double, i32, vp, vp]
     L.asl_smooth_cov_frames_device.argtypes = L.asl_smooth_frames_device.argtypes[:-1] + [vp, vp]
     L.asl_smooth_cov_batch.argtypes = L.asl_smooth_batch.argtypes + [vp]
+    i32p = C.POINTER(C.c_int32)
+    L.asl_smooth_sequences_device.argtypes = (L.asl_smooth_cov_frames_device.argtypes[:11] + [i32p, i32]
+                                              + L.asl_smooth_cov_frames_device.argtypes[11:])
+    L.asl_smooth_sequences_batch.argtypes = L.asl_smooth_cov_batch.argtypes[:11] + [i32p, i32] + L.asl_smooth_cov_batch.argtypes[11:]
     L.asl_debug_fetch.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.asl_debug_refit.argtypes = [vp, i32, vp, C.c_size_t]
     L.asl_debug_division_check.argtypes = [vp, i32, vp, C.c_size_t]
@@ -552,6 +557,51 @@ class Detector:
             check(self._L.asl_smooth_frames_device(*args, _ptr(stream)))
         else:
             check(self._L.asl_smooth_cov_frames_device(*args, _ptr(cov_ptr), _ptr(stream)))
+
+    @staticmethod
+    def _seq_start(seq_start, n_frames):
+        """the offsets as the C ABI takes them: (array to keep alive, pointer, n_seq).  Every refusal is the library's
+        (ASL_EINVAL -> AslError); an offset that does not fit an int32 becomes -1 here, which the library refuses, so that the
+        cast cannot wrap into a valid one"""
+        ss = np.atleast_1d(np.asarray(seq_start, dtype=np.int64)).ravel()
+        ss = np.where((ss < 0) | (ss > 0x7fffffff), -1, ss).astype(np.int32)
+        if len(ss) == 0:
+            ss = np.full(1, -1, dtype=np.int32)
+        return ss, ss.ctypes.data_as(C.POINTER(C.c_int32)), len(ss) - 1
+
+    def smooth_sequences(self, obs, seq_start, tag_map, K, dist, tag_size, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20,
+                         seed=None, with_cov=False):
+        """asl_smooth_sequences_batch: smooth() for several sequences in one call, solved side by side.  obs (n_frames, max_tags)
+        OBS_DTYPE holds the sequences end to end, sequence k the frames seq_start[k]:seq_start[k + 1] (n_seq + 1 offsets, from
+        0 to n_frames) -> ((n_frames,) CAM_POSE_DTYPE, (n_seq,) SMOOTH_RESULT_DTYPE[, (n_frames,) POSE_COV_DTYPE]): for every
+        sequence the bytes smooth() returns for its frames alone.  The map, the camera, the sigmas and max_iters are shared."""
+        o = _obs_records(obs)
+        m = _map_records(tag_map)
+        keep, Kp, dpp, nd = _camera(K, dist, square=True)
+        ss, ssp, n_seq = self._seq_start(seq_start, o.shape[0])
+        sd = None if seed is None else np.ascontiguousarray(seed, dtype=CAM_POSE_DTYPE).ravel()
+        if sd is not None and len(sd) != o.shape[0]:
+            raise ValueError("seed must hold one pose per frame")
+        out = np.zeros(o.shape[0], dtype=CAM_POSE_DTYPE)
+        res = np.zeros(n_seq, dtype=SMOOTH_RESULT_DTYPE)
+        cov = np.zeros(o.shape[0], dtype=POSE_COV_DTYPE) if with_cov else None
+        check(self._L.asl_smooth_sequences_batch(
+            self._h, o.ctypes.data if o.size else None, o.shape[0], o.shape[1], m.ctypes.data if m.size else None, len(m), Kp, dpp, nd,
+            float(tag_size), None if sd is None else sd.ctypes.data, ssp, n_seq, float(sigma_px), float(sigma_rot), float(sigma_trans),
+            int(max_iters), out.ctypes.data if out.size else None, res.ctypes.data, cov.ctypes.data if with_cov and cov.size else None))
+        return (out, res, cov) if with_cov else (out, res)
+
+    def smooth_sequences_device(self, obs_ptr, n_frames, max_tags, map_ptr, n_ids, seed_ptr, seq_start, out_ptr, results_ptr, K, dist,
+                                tag_size, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, stream=0, cov_ptr=None):
+        """asl_smooth_sequences_device: smooth_device for several sequences; seq_start is a HOST array of n_seq + 1 offsets,
+        results_ptr n_seq asl_smooth_result on the device, cov_ptr None or n_frames asl_pose_cov.  Enqueued on `stream`, no
+        wait; seq_start is read before this returns."""
+        keep, Kp, dpp, nd = _camera(K, dist, square=True)
+        ss, ssp, n_seq = self._seq_start(seq_start, n_frames)
+        check(self._L.asl_smooth_sequences_device(
+            self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids), Kp, dpp, nd, float(tag_size), _ptr(seed_ptr),
+            ssp, n_seq, float(sigma_px), float(sigma_rot), float(sigma_trans), int(max_iters), _ptr(out_ptr), _ptr(results_ptr),
+            _opt_ptr(cov_ptr), _ptr(stream)))
 
     def collect_view(self):
         """Wait for the submitted batch; (dets, poses or None, n_per_frame) as numpy VIEWS of the detector's page-locked result

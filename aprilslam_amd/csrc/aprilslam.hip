@@ -132,7 +132,7 @@ struct asl_detector {
     DevBuf<uint8_t> rect_src, rect_dst;  // asl_rectify_u8: the host image's device copy and the result (no batch reads them)
     DevBuf<uint8_t> cal_ws;  // calibration: per-frame workspace and state (k_calib.inc)
     DevBuf<uint8_t> map_ws, map_lm;  // map reconstruction (k_map.inc): sized by the input / by the problem
-    DevBuf<uint8_t> smooth_ws;  // sequence localisation (k_smooth.inc): the chain's and the LM's buffers, sized by n_frames
+    DevBuf<uint8_t> smooth_ws;  // sequence localisation (k_smooth.inc): the chain's and the LM's buffers, sized by n_frames and n_seq
     hipStream_t copy_stream = nullptr, host_stream = nullptr;  // host frames: transfers and the chunks' kernels (detect_host_frames)
     std::vector<hipEvent_t> copy_done;
     hipStream_t aux_stream = nullptr;  // highest priority, for the small latency-bound jobs next to a running batch (pose-graph LM)
@@ -1635,14 +1635,30 @@ extern "C" int asl_map_batch(asl_detector *d, const asl_obs *obs, int n_frames, 
 
 // ---- sequence localisation with a motion prior (k_smooth.inc)
 
-// Every refusal of the two entry points, before anything is written or enqueued
+#define SMOOTH_SEQ_FRAMES 65535   // frames of one sequence
+#define SMOOTH_SEQS 65535         // sequences of one call
+#define SMOOTH_FRAMES 1048576     // frames of one call: the work buffers, about 3.6 KB a frame, stay under 4 GB
+
+// Every refusal of the entry points, before anything is written or enqueued.  seq_start (host, n_seq + 1 offsets): the
+// sequences of an asl_smooth_sequences_* call; NULL with n_seq 1: the one sequence {0, n_frames} of the other calls
 static int check_smooth_args(const asl_detector *d, const void *obs, int n_frames, int max_tags, const void *map, int n_ids, const double *K,
                              const double *dist, int n_dist, double tag_size, double sigma_px, double sigma_rot, double sigma_trans,
-                             int max_iters, const void *out, const void *result)
+                             int max_iters, const void *out, const void *result, const int32_t *seq_start, int n_seq, bool sequences)
 {
     if (!d) return fail(ASL_EINVAL, "NULL detector");
-    if (!obs || !map || !K || !out || !result) return fail(ASL_EINVAL, "NULL argument");
-    if (n_frames < 1 || n_frames > 65535) return fail(ASL_EINVAL, "n_frames must be in [1, 65535] (got %d)", n_frames);
+    if (!obs || !map || !K || !out || !result || (sequences && !seq_start)) return fail(ASL_EINVAL, "NULL argument");
+    if (!sequences) {
+        if (n_frames < 1 || n_frames > SMOOTH_SEQ_FRAMES) return fail(ASL_EINVAL, "n_frames must be in [1, %d] (got %d)", SMOOTH_SEQ_FRAMES, n_frames);
+    } else {
+        if (n_frames < 1 || n_frames > SMOOTH_FRAMES) return fail(ASL_EINVAL, "n_frames must be in [1, %d] (got %d)", SMOOTH_FRAMES, n_frames);
+        if (n_seq < 1 || n_seq > SMOOTH_SEQS) return fail(ASL_EINVAL, "n_seq must be in [1, %d] (got %d)", SMOOTH_SEQS, n_seq);
+        if (seq_start[0] != 0 || seq_start[n_seq] != n_frames)
+            return fail(ASL_EINVAL, "seq_start must run from 0 to n_frames (got %d to %d, n_frames %d)", seq_start[0], seq_start[n_seq], n_frames);
+        for (int k = 0; k < n_seq; k++) {
+            const int64_t len = (int64_t)seq_start[k + 1] - seq_start[k];
+            if (len < 1 || len > SMOOTH_SEQ_FRAMES) return fail(ASL_EINVAL, "sequence %d must have 1 to %d frames (got %lld)", k, SMOOTH_SEQ_FRAMES, (long long)len);
+        }
+    }
     if (int rc = check_obs_args(max_tags, n_ids, n_dist, !dist, tag_size)) return rc;
     for (int k = 0; k < 9; k++)
         if (!std::isfinite(K[k])) return fail(ASL_EINVAL, "K is not finite");
@@ -1653,22 +1669,28 @@ static int check_smooth_args(const asl_detector *d, const void *obs, int n_frame
     return ASL_OK;
 }
 
-// All device pointers; everything is enqueued on st, nothing waits.  d_cov: NULL, or the frames' asl_pose_cov (two more launches)
+// All device pointers but seq_start (host, n_seq + 1; not read for n_seq 1: the one sequence {0, n_frames}); everything is
+// enqueued on st, nothing waits.  d_cov: NULL, or the frames' asl_pose_cov (two more launches).  n_seq > 1: k_smooth_seqs
+// first, a launch per SM_SEQ_CHUNK sequences, which carries the offsets to the device in its arguments.
 static int launch_smooth(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids, const double *K,
-                         const double *dist, int n_dist, double tag_size, const void *d_seed, double sigma_px, double sigma_rot,
-                         double sigma_trans, int max_iters, void *d_out, void *d_result, void *d_cov, hipStream_t st)
+                         const double *dist, int n_dist, double tag_size, const void *d_seed, const int32_t *seq_start, int n_seq,
+                         double sigma_px, double sigma_rot, double sigma_trans, int max_iters, void *d_out, void *d_result, void *d_cov,
+                         hipStream_t st)
 {
     static_assert(sizeof(SmoothResultRec) == sizeof(asl_smooth_result) && sizeof(asl_smooth_result) == 64, "asl_smooth_result layout");
     static_assert(sizeof(PoseCovRec) == sizeof(asl_pose_cov) && sizeof(asl_pose_cov) == 304, "asl_pose_cov layout");
     const size_t n = (size_t)n_frames;
     SmoothBufs b{};
     b.n = n_frames;
+    b.n_seq = n_seq;
+    const size_t ns = (size_t)n_seq;
     if (carve_ws(d->smooth_ws, [&](WsCarve &c) {
             b.cand = c.take<double>(24 * n); b.dcost = c.take<double>(2 * n); b.tcost = c.take<double>(4 * n);
             b.posed = c.take<int>(n); b.ntags = c.take<int>(n); b.src = c.take<int>(n); b.back = c.take<int>(n); b.choice = c.take<int>(n);
-            b.code = c.take<int>(n); b.head = c.take<int>(SMH__N); b.lm = c.take<double>(SM__N); b.cseed = c.take<double>(n);
+            b.code = c.take<int>(n); b.head = c.take<int>(SMH__N * ns); b.lm = c.take<double>(SM__N * ns); b.cseed = c.take<double>(n);
             b.delta = c.take<double>(6 * n); b.fac = c.take<double>(SM_FAC * n);
             b.set[0] = c.take<double>(SM_SET * n); b.set[1] = c.take<double>(SM_SET * n);
+            if (n_seq > 1) { b.seq = c.take<int>(ns + 1); b.fseq = c.take<int>(n); }
         }))
         return fail(ASL_ENOMEM, "sequence localisation workspace allocation failed");
     const CamDev cam = make_cam(d, K, dist, n_dist, tag_size);
@@ -1677,31 +1699,39 @@ static int launch_smooth(asl_detector *d, const void *d_obs, int n_frames, int m
     const CamPoseRec *seed = (const CamPoseRec *)d_seed;
     const double w = 1.0 / (sigma_px * sigma_px), isr = 1.0 / sigma_rot, ist = 1.0 / sigma_trans;
     const size_t lds = loc_lds_bytes(max_tags);
-    const dim3 frames((unsigned int)n_frames), wave(ASL_WAVE), one(1), wg(SM_WG), per_thread((unsigned int)((n + SM_WG - 1) / SM_WG));
+    const dim3 frames((unsigned int)n_frames), wave(ASL_WAVE), seqs((unsigned int)n_seq), wg(SM_WG), per_thread((unsigned int)((n + SM_WG - 1) / SM_WG));
 
-    const dim3 commit_blocks((unsigned int)std::min<size_t>((SM_SET * n + SM_WG - 1) / SM_WG, 1024));
+    static_assert(SM_SET <= SM_WG, "k_smooth_commit: a thread an entry of a frame");
+    const dim3 commit_blocks((unsigned int)std::min<size_t>(n, 1024));
 
     range_push("smooth: seed chain");
+    for (int k0 = 0; n_seq > 1 && k0 < n_seq; k0 += SM_SEQ_CHUNK) {
+        SmoothSeqChunk c;
+        c.k0 = k0;
+        c.count = std::min(n_seq - k0, SM_SEQ_CHUNK);
+        memcpy(c.start, seq_start + k0, sizeof(int32_t) * ((size_t)c.count + 1));
+        hipLaunchKernelGGL(k_smooth_seqs, dim3((unsigned int)c.count), wg, 0, st, b, c);
+    }
     hipLaunchKernelGGL(k_smooth_cand, frames, wave, lds, st, obs, max_tags, map, n_ids, cam, seed, w, b);
-    hipLaunchKernelGGL(k_smooth_scan, one, wave, 0, st, b);
+    hipLaunchKernelGGL(k_smooth_scan, seqs, wave, 0, st, b);
     hipLaunchKernelGGL(k_smooth_trans, dim3((unsigned int)((n + ASL_WAVE - 1) / ASL_WAVE)), wave, 0, st, b, isr, ist);
-    hipLaunchKernelGGL(k_smooth_dp, one, wave, 0, st, b);
+    hipLaunchKernelGGL(k_smooth_dp, seqs, wave, 0, st, b);
     hipLaunchKernelGGL(k_smooth_fill, per_thread, wg, 0, st, b, seed);
     hipLaunchKernelGGL(k_smooth_lin, frames, wave, lds, st, obs, max_tags, map, n_ids, cam, b, 0, isr, ist);
-    hipLaunchKernelGGL(k_smooth_init, one, wg, 0, st, b, w);
+    hipLaunchKernelGGL(k_smooth_init, seqs, wg, 0, st, b, w);
     range_pop();
     range_push("smooth: LM");
     for (int it = 0; it < max_iters; it++) {
-        hipLaunchKernelGGL(k_smooth_solve, one, wave, 0, st, b, w);
+        hipLaunchKernelGGL(k_smooth_solve, seqs, wave, 0, st, b, w);
         hipLaunchKernelGGL(k_smooth_lin, frames, wave, lds, st, obs, max_tags, map, n_ids, cam, b, 1, isr, ist);
-        hipLaunchKernelGGL(k_smooth_decide, one, wg, 0, st, b, w);
+        hipLaunchKernelGGL(k_smooth_decide, seqs, wg, 0, st, b, w);
         hipLaunchKernelGGL(k_smooth_commit, commit_blocks, wg, 0, st, b);
     }
     hipLaunchKernelGGL(k_smooth_finish, per_thread, wg, 0, st, b, (CamPoseRec *)d_out, (SmoothResultRec *)d_result);
     range_pop();
     if (d_cov) {
         range_push("smooth: covariance");
-        hipLaunchKernelGGL(k_smooth_cov, one, wave, 0, st, b, w, (PoseCovRec *)d_cov);
+        hipLaunchKernelGGL(k_smooth_cov, seqs, wave, 0, st, b, w, (PoseCovRec *)d_cov);
         hipLaunchKernelGGL(k_smooth_cov_finish, per_thread, wg, 0, st, b, sigma_px, (PoseCovRec *)d_cov);
         range_pop();
     }
@@ -1715,13 +1745,15 @@ static bool smooth_overlap(const void *a, size_t a_bytes, const void *b, size_t 
     return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
-// d_cov NULL: the plain call
+// The device forms.  with_cov false: the plain call, d_cov not looked at.  sequences: asl_smooth_sequences_device (else
+// seq_start NULL, n_seq 1)
 static int smooth_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids, const double *K,
-                                const double *dist, int n_dist, double tag_size, const void *d_seed, double sigma_px, double sigma_rot,
-                                double sigma_trans, int max_iters, void *d_out, void *d_result, void *d_cov, bool with_cov, void *stream)
+                                const double *dist, int n_dist, double tag_size, const void *d_seed, const int32_t *seq_start, int n_seq,
+                                bool sequences, double sigma_px, double sigma_rot, double sigma_trans, int max_iters, void *d_out,
+                                void *d_result, void *d_cov, bool with_cov, void *stream)
 {
     if (int rc = check_smooth_args(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, sigma_px, sigma_rot, sigma_trans,
-                                   max_iters, d_out, d_result))
+                                   max_iters, d_out, d_result, seq_start, n_seq, sequences))
         return rc;
     if (!d_seed || (with_cov && !d_cov)) return fail(ASL_EINVAL, "NULL argument");
     const size_t poses = sizeof(asl_cam_pose) * (size_t)n_frames, covs = sizeof(asl_pose_cov) * (size_t)n_frames;
@@ -1729,16 +1761,16 @@ static int smooth_frames_device(asl_detector *d, const void *d_obs, int n_frames
     if (with_cov && (smooth_overlap(d_cov, covs, d_out, poses) || smooth_overlap(d_cov, covs, d_seed, poses)))
         return fail(ASL_EINVAL, "d_cov overlaps d_out or d_seed");
     HIPCHK(hipSetDevice(d->device));
-    return launch_smooth(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, d_seed, sigma_px, sigma_rot, sigma_trans,
-                         max_iters, d_out, d_result, with_cov ? d_cov : nullptr, (hipStream_t)stream);
+    return launch_smooth(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, d_seed, seq_start, n_seq, sigma_px, sigma_rot,
+                         sigma_trans, max_iters, d_out, d_result, with_cov ? d_cov : nullptr, (hipStream_t)stream);
 }
 
 extern "C" int asl_smooth_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
                                         const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed, double sigma_px,
                                         double sigma_rot, double sigma_trans, int max_iters, void *d_out, void *d_result, void *stream)
 {
-    return smooth_frames_device(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, d_seed, sigma_px, sigma_rot, sigma_trans,
-                                max_iters, d_out, d_result, nullptr, false, stream);
+    return smooth_frames_device(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, d_seed, nullptr, 1, false, sigma_px,
+                                sigma_rot, sigma_trans, max_iters, d_out, d_result, nullptr, false, stream);
 }
 
 extern "C" int asl_smooth_cov_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
@@ -1746,16 +1778,26 @@ extern "C" int asl_smooth_cov_frames_device(asl_detector *d, const void *d_obs, 
                                             double sigma_px, double sigma_rot, double sigma_trans, int max_iters, void *d_out, void *d_result,
                                             void *d_cov, void *stream)
 {
-    return smooth_frames_device(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, d_seed, sigma_px, sigma_rot, sigma_trans,
-                                max_iters, d_out, d_result, d_cov, true, stream);
+    return smooth_frames_device(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, d_seed, nullptr, 1, false, sigma_px,
+                                sigma_rot, sigma_trans, max_iters, d_out, d_result, d_cov, true, stream);
+}
+
+extern "C" int asl_smooth_sequences_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                           const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed,
+                                           const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
+                                           int max_iters, void *d_out, void *d_results, void *d_cov, void *stream)
+{
+    return smooth_frames_device(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, d_seed, seq_start, n_seq, true, sigma_px,
+                                sigma_rot, sigma_trans, max_iters, d_out, d_results, d_cov, d_cov != nullptr, stream);
 }
 
 static int smooth_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids, const double *K,
-                        const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed, double sigma_px, double sigma_rot,
-                        double sigma_trans, int max_iters, asl_cam_pose *out, asl_smooth_result *result, asl_pose_cov *cov, bool with_cov)
+                        const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed, const int32_t *seq_start, int n_seq,
+                        bool sequences, double sigma_px, double sigma_rot, double sigma_trans, int max_iters, asl_cam_pose *out,
+                        asl_smooth_result *result, asl_pose_cov *cov, bool with_cov)
 {
     if (int rc = check_smooth_args(d, obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, sigma_px, sigma_rot, sigma_trans,
-                                   max_iters, out, result))
+                                   max_iters, out, result, seq_start, n_seq, sequences))
         return rc;
     if (with_cov && !cov) return fail(ASL_EINVAL, "NULL argument");
     HIPCHK(hipSetDevice(d->device));
@@ -1764,7 +1806,7 @@ static int smooth_batch(asl_detector *d, const asl_obs *obs, int n_frames, int m
     asl_smooth_result *d_result = nullptr;
     asl_pose_cov *d_cov = nullptr;
     if (carve_ws(d->solve_out, [&](WsCarve &c) {
-            d_result = c.take<asl_smooth_result>(1); d_out = c.take<asl_cam_pose>(n); d_seed = c.take<asl_cam_pose>(n);
+            d_result = c.take<asl_smooth_result>((size_t)n_seq); d_out = c.take<asl_cam_pose>(n); d_seed = c.take<asl_cam_pose>(n);
             if (with_cov) d_cov = c.take<asl_pose_cov>(n);
         }))
         return fail(ASL_ENOMEM, "sequence localisation workspace allocation failed");
@@ -1774,11 +1816,11 @@ static int smooth_batch(asl_detector *d, const asl_obs *obs, int n_frames, int m
     else  // the per-frame localisation of the same block, gate 0
         launch_localize(d, {d->loc_obs.p, 0, n_frames, max_tags, d->loc_map.p, n_ids, K, dist, n_dist, nullptr, tag_size, 0.0, 0.0, d_seed, nullptr, false},
                         nullptr);
-    if (int rc = launch_smooth(d, d->loc_obs.p, n_frames, max_tags, d->loc_map.p, n_ids, K, dist, n_dist, tag_size, d_seed, sigma_px, sigma_rot,
-                               sigma_trans, max_iters, d_out, d_result, d_cov, nullptr))
+    if (int rc = launch_smooth(d, d->loc_obs.p, n_frames, max_tags, d->loc_map.p, n_ids, K, dist, n_dist, tag_size, d_seed, seq_start, n_seq, sigma_px,
+                               sigma_rot, sigma_trans, max_iters, d_out, d_result, d_cov, nullptr))
         return rc;
     HIPCHK(hipMemcpy(out, d_out, sizeof(asl_cam_pose) * n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(result, d_result, sizeof(asl_smooth_result), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(result, d_result, sizeof(asl_smooth_result) * (size_t)n_seq, hipMemcpyDeviceToHost));
     if (with_cov) HIPCHK(hipMemcpy(cov, d_cov, sizeof(asl_pose_cov) * n, hipMemcpyDeviceToHost));
     return ASL_OK;
 }
@@ -1787,8 +1829,8 @@ extern "C" int asl_smooth_batch(asl_detector *d, const asl_obs *obs, int n_frame
                                 const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed, double sigma_px,
                                 double sigma_rot, double sigma_trans, int max_iters, asl_cam_pose *out, asl_smooth_result *result)
 {
-    return smooth_batch(d, obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, seed, sigma_px, sigma_rot, sigma_trans, max_iters,
-                        out, result, nullptr, false);
+    return smooth_batch(d, obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, seed, nullptr, 1, false, sigma_px, sigma_rot,
+                        sigma_trans, max_iters, out, result, nullptr, false);
 }
 
 extern "C" int asl_smooth_cov_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
@@ -1796,8 +1838,17 @@ extern "C" int asl_smooth_cov_batch(asl_detector *d, const asl_obs *obs, int n_f
                                     double sigma_rot, double sigma_trans, int max_iters, asl_cam_pose *out, asl_smooth_result *result,
                                     asl_pose_cov *cov)
 {
-    return smooth_batch(d, obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, seed, sigma_px, sigma_rot, sigma_trans, max_iters,
-                        out, result, cov, true);
+    return smooth_batch(d, obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, seed, nullptr, 1, false, sigma_px, sigma_rot,
+                        sigma_trans, max_iters, out, result, cov, true);
+}
+
+extern "C" int asl_smooth_sequences_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                          const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed,
+                                          const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
+                                          int max_iters, asl_cam_pose *out, asl_smooth_result *results, asl_pose_cov *cov)
+{
+    return smooth_batch(d, obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, seed, seq_start, n_seq, true, sigma_px, sigma_rot,
+                        sigma_trans, max_iters, out, results, cov, cov != nullptr);
 }
 
 #include "debug_host.inc"

@@ -5,22 +5,27 @@
 // computation, operation order of the linear solve included.  float64, contraction off, no scratch.
 //   seed chain   k_smooth_cand   one wavefront per frame: the seed's pose A and, for a frame of exactly one taking-part slot,
 //                                its mirrored planar minimum B (loc_candidate), both costed over the frame's corners
-//                k_smooth_scan   one wavefront: the nearest posed frame at or before every frame (wave_scan of a maximum)
+//                k_smooth_scan   one wavefront a sequence: the nearest posed frame at or before every frame (wave_scan of a maximum)
 //                k_smooth_trans  one thread per posed frame: the four motion costs from its predecessor's candidates
-//                k_smooth_dp     one wavefront: the two-state dynamic programme, forward and back, 64 frames' costs a load
+//                k_smooth_dp     one wavefront a sequence: the two-state dynamic programme, forward and back, 64 frames' costs a load
 //                k_smooth_fill   one thread per frame: the chosen pose, or the nearest earlier posed frame's
-//                k_smooth_lin    (below) once at the chain's poses, then k_smooth_init: one workgroup, the cost after the
+//                k_smooth_lin    (below) once at the chain's poses, then k_smooth_init: one workgroup a sequence, the cost after the
 //                                chain, the LM state (lambda0, status 1 / 3), the per-frame seed costs
 //   per trial    k_smooth_lin    one wavefront per frame: the pose (stepped by delta), the frame's cost, H and g from its
 //                                corners (loc_gather, loc_pass), and the motion blocks of the pair (f, f + 1), a lane an entry
-//                k_smooth_solve  one wavefront: the block-tridiagonal Cholesky forward and back over the frames, the 6x6
+//                k_smooth_solve  one wavefront a sequence: the block-tridiagonal Cholesky forward and back over the frames, the 6x6
 //                                block spread over 36 lanes with its operands in LDS
-//                k_smooth_decide one workgroup: the trial's cost in a fixed order, the accept rule, lambda, the stop
-//                k_smooth_commit an accepted trial copied over the current state, spread over the device
+//                k_smooth_decide one workgroup a sequence: the trial's cost in a fixed order, the accept rule, lambda, the stop
+//                k_smooth_commit the accepted trials copied over the current state, spread over the device
 //   end          k_smooth_finish one thread per frame: the records
-//   covariance   k_smooth_cov    (asl_smooth_cov_*, only when asked for) one wavefront: the undamped block Cholesky of the
+//   covariance   k_smooth_cov    (asl_smooth_cov_*, only when asked for) one wavefront a sequence: the undamped block Cholesky of the
 //                                returned state forward, the diagonal blocks of the inverse back, a 6x6 block from frame to frame
 //                k_smooth_cov_finish  one thread per frame: sigma_px, dof, status, and the zeros of a status 1 / 2
+// Several sequences per call (asl_smooth_sequences_*): sequence k is the frames [seq[k], seq[k + 1]) of the call's, with its own
+// lm[SM__N] and head[SMH__N]; no term links two sequences.  The chain kernels and the per-sequence sums run one workgroup per
+// sequence, each over its own frames with the arithmetic of the single-sequence call, indexed from the sequence's first
+// frame; a per-frame kernel reads the state of its frame's sequence (smooth_seq_of).  The single-sequence calls are n_seq = 1:
+// the same launches, the one range {0, n} taken from the arguments (smooth_seq), no table.
 // Serial by nature are the scan, the dynamic programme and the factor-and-solve: each is a chain over the frames, so each
 // is one wavefront that carries a small state (a maximum, two costs, a 6x6 coupling block) from frame to frame.  All trials are enqueued at once;
 // lm[SM_STOP] makes the ones after the stop return at once (k_map.inc works the same way).
@@ -53,8 +58,60 @@ struct SmoothBufs {
     int *posed, *ntags, *src, *back, *choice, *code, *head;
     double *lm, *cseed, *delta, *fac;
     double *set[2];                 // the current state and the trial
-    int n;
+    int *seq, *fseq;                // n_seq > 1: the sequences' first frames (n_seq + 1) and every frame's sequence (k_smooth_seqs)
+    int n, n_seq;                   // lm and head: n_seq of each
 };
+
+// Sequence k of a call: frames [f0, f0 + n)
+struct SmoothSeq {
+    int k, f0, n;
+};
+
+__device__ __forceinline__ SmoothSeq smooth_seq(const SmoothBufs &b, int k)
+{
+    if (b.n_seq == 1) return {0, 0, b.n};
+    const int f0 = b.seq[k];
+    return {k, f0, b.seq[k + 1] - f0};
+}
+
+// The same for a k that is one value in the whole wavefront (a workgroup a sequence): the range in scalar registers, so
+// that the loops over the frames and their addresses stay scalar, as they are with the one range of the arguments
+__device__ __forceinline__ SmoothSeq smooth_seq_uniform(const SmoothBufs &b, int k)
+{
+    const SmoothSeq q = smooth_seq(b, k);
+    return {__builtin_amdgcn_readfirstlane(q.k), __builtin_amdgcn_readfirstlane(q.f0), __builtin_amdgcn_readfirstlane(q.n)};
+}
+
+// The sequence of frame f
+__device__ __forceinline__ SmoothSeq smooth_seq_of(const SmoothBufs &b, int f)
+{
+    return smooth_seq(b, b.n_seq == 1 ? 0 : b.fseq[f]);
+}
+
+// The same for an f that is one value in the whole wavefront (a wavefront or a workgroup a frame)
+__device__ __forceinline__ SmoothSeq smooth_seq_of_uniform(const SmoothBufs &b, int f)
+{
+    return smooth_seq_uniform(b, b.n_seq == 1 ? 0 : b.fseq[f]);
+}
+
+// The offsets of up to SM_SEQ_CHUNK sequences, carried in the launch's own arguments: they reach the device in stream order
+// without a staging buffer that a later call could overwrite, and the host array is free when the launch returns.
+#define SM_SEQ_CHUNK 896
+struct SmoothSeqChunk {
+    int k0, count;                  // sequences [k0, k0 + count)
+    int32_t start[SM_SEQ_CHUNK + 1];
+};
+
+// One workgroup per sequence of the chunk: its entry of seq (the last one also the end) and its frames' entries of fseq
+__global__ void __launch_bounds__(SM_WG) k_smooth_seqs(SmoothBufs b, SmoothSeqChunk c)
+{
+    const int j = (int)blockIdx.x, k = c.k0 + j, f0 = c.start[j], f1 = c.start[j + 1];
+    if (threadIdx.x == 0) {
+        b.seq[k] = f0;
+        if (j + 1 == c.count) b.seq[k + 1] = f1;
+    }
+    for (int f = f0 + (int)threadIdx.x; f < f1; f += SM_WG) b.fseq[f] = k;
+}
 
 __device__ __forceinline__ void smooth_relative(const double *Ra, const double *ta, const double *Rb, const double *tb, double *RD, double *tD)
 {
@@ -172,23 +229,27 @@ __global__ void __launch_bounds__(64) k_smooth_cand(const ObsRec *__restrict__ o
     }
 }
 
-// src[f]: the nearest posed frame at or before f (-1: none); head: the number of posed frames and the first one
+// A sequence's src[f]: the nearest posed frame of the sequence at or before f (-1: none), as a frame of the call; its head:
+// the number of posed frames and the first one
 __global__ void __launch_bounds__(64) k_smooth_scan(SmoothBufs b)
 {
     const int lane = (int)threadIdx.x;
+    const SmoothSeq q = smooth_seq_uniform(b, (int)blockIdx.x);
+    int *head = b.head + SMH__N * q.k;
     int carry = -1, np = 0, first = -1;
-    for (int base = 0; base < b.n; base += ASL_WAVE) {
-        const int f = base + lane;
-        const int v = (f < b.n && b.posed[f]) ? f : -1;
+    for (int base = 0; base < q.n; base += ASL_WAVE) {
+        const int f = q.f0 + base + lane;
+        const bool in = base + lane < q.n;
+        const int v = (in && b.posed[f]) ? f : -1;
         int s = wave_scan<false>(v, -1, [](int x, int y) { return x > y ? x : y; });
         s = s > carry ? s : carry;
-        if (f < b.n) b.src[f] = s;
+        if (in) b.src[f] = s;
         carry = readlane(s, 63);
         np += butterfly_sum<64>(v >= 0 ? 1 : 0);
         const int mn = wave_scan<true>(v >= 0 ? v : 0x7fffffff, 0x7fffffff, [](int x, int y) { return x < y ? x : y; });
         if (first < 0 && mn != 0x7fffffff) first = mn;
     }
-    if (lane == 0) { b.head[SMH_NPOSED] = np; b.head[SMH_FIRST] = first; b.head[SMH_FAIL] = 0; b.head[SMH_NFLIP] = 0; }
+    if (lane == 0) { head[SMH_NPOSED] = np; head[SMH_FIRST] = first; head[SMH_FAIL] = 0; head[SMH_NFLIP] = 0; }
 }
 
 // The four transition costs of a posed frame from its predecessor, over a gap of g frame steps divided by g
@@ -196,7 +257,7 @@ __global__ void __launch_bounds__(64) k_smooth_trans(SmoothBufs b, double isr, d
 {
     const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (f >= b.n || !b.posed[f]) return;
-    const int p = f > 0 ? b.src[f - 1] : -1;
+    const int p = f > smooth_seq_of(b, f).f0 ? b.src[f - 1] : -1;
     double *tc = b.tcost + 4 * (size_t)f;
     if (p < 0) { tc[0] = 0; tc[1] = 0; tc[2] = 0; tc[3] = 0; return; }
     const double gap = (double)(f - p);
@@ -213,13 +274,16 @@ __global__ void __launch_bounds__(64) k_smooth_trans(SmoothBufs b, double isr, d
 // loads one frame of each chunk of 64; the chain reads them lane by lane (readlane) and leaves lane l's result with lane l.
 __global__ void __launch_bounds__(64) k_smooth_dp(SmoothBufs b)
 {
-    if (b.head[SMH_NPOSED] == 0) return;
-    const int lane = (int)threadIdx.x, n = b.n;
+    const SmoothSeq q = smooth_seq_uniform(b, (int)blockIdx.x);
+    int *head = b.head + SMH__N * q.k;
+    if (head[SMH_NPOSED] == 0) return;
+    const int lane = (int)threadIdx.x, n = q.n;
     double cA = 0, cB = 0;
     bool started = false;
     for (int base = 0; base < n; base += ASL_WAVE) {
-        const int f = base + lane;
-        const int my = (f < n && b.posed[f]) ? 1 : 0;
+        const int f = q.f0 + base + lane;
+        const bool in = base + lane < n;
+        const int my = (in && b.posed[f]) ? 1 : 0;
         double dA = 0, dB = 0, t00 = 0, t01 = 0, t10 = 0, t11 = 0;
         if (my) {
             dA = b.dcost[2 * f]; dB = b.dcost[2 * f + 1];
@@ -243,13 +307,14 @@ __global__ void __launch_bounds__(64) k_smooth_dp(SmoothBufs b)
             }
             if (lane == l) my_back = bk;
         }
-        if (f < n) b.back[f] = my_back;   // read back below by the lane that wrote it
+        if (in) b.back[f] = my_back;   // read back below by the lane that wrote it
     }
     int cur = cB < cA ? 1 : 0, nflip = 0;
     for (int base = (n - 1) / ASL_WAVE * ASL_WAVE; base >= 0; base -= ASL_WAVE) {
-        const int f = base + lane;
-        const int my = (f < n && b.posed[f]) ? 1 : 0;
-        const int my_back = f < n ? b.back[f] : 0;
+        const int f = q.f0 + base + lane;
+        const bool in = base + lane < n;
+        const int my = (in && b.posed[f]) ? 1 : 0;
+        const int my_back = in ? b.back[f] : 0;
         int my_choice = 0;
         for (int l = ASL_WAVE - 1; l >= 0; l--) {
             if (!readlane(my, l)) continue;
@@ -257,18 +322,20 @@ __global__ void __launch_bounds__(64) k_smooth_dp(SmoothBufs b)
             nflip += cur;
             cur = (readlane(my_back, l) >> cur) & 1;
         }
-        if (f < n) b.choice[f] = my_choice;
+        if (in) b.choice[f] = my_choice;
     }
-    if (lane == 0) b.head[SMH_NFLIP] = nflip;
+    if (lane == 0) head[SMH_NFLIP] = nflip;
 }
 
 // Every frame's start pose and seed code
 __global__ void __launch_bounds__(SM_WG) k_smooth_fill(SmoothBufs b, const CamPoseRec *__restrict__ seed)
 {
     const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (f >= b.n || b.head[SMH_NPOSED] == 0) return;
+    if (f >= b.n) return;
+    const int *head = b.head + SMH__N * smooth_seq_of(b, f).k;
+    if (head[SMH_NPOSED] == 0) return;
     int s = b.src[f];
-    if (s < 0) s = b.head[SMH_FIRST];
+    if (s < 0) s = head[SMH_FIRST];
     const int ch = b.choice[s];
     const double *c = b.cand + 24 * (size_t)s + 12 * ch;
     double *P = b.set[0] + 12 * (size_t)f;
@@ -283,9 +350,11 @@ __global__ void __launch_bounds__(64) k_smooth_lin(const ObsRec *__restrict__ ob
 {
     extern __shared__ double s_dyn[];
     __shared__ double s_RD[9], s_tD[3], s_m[6], s_B[36], s_Ad[36], s_Jn[36], s_Jp[36];
-    if (b.head[SMH_NPOSED] == 0) return;
-    if (trial && (b.lm[SM_STOP] != 0.0 || b.head[SMH_FAIL])) return;
     const int lane = (int)threadIdx.x, f = (int)blockIdx.x, n = b.n;
+    const SmoothSeq q = smooth_seq_of_uniform(b, f);
+    const int *head = b.head + SMH__N * q.k;
+    if (head[SMH_NPOSED] == 0) return;
+    if (trial && (b.lm[SM__N * q.k + SM_STOP] != 0.0 || head[SMH_FAIL])) return;
     const SmoothSet in = smooth_set(b.set[0], (size_t)n), out = smooth_set(b.set[trial], (size_t)n);
     double P[12];
 #pragma unroll
@@ -311,7 +380,7 @@ __global__ void __launch_bounds__(64) k_smooth_lin(const ObsRec *__restrict__ ob
         for (int k = 0; k < 27; k++) out.ne[27 * (size_t)f + k] = ne[k];
         out.c[f] = c;
     }
-    if (f + 1 >= n) return;
+    if (f + 1 >= q.f0 + q.n) return;   // the last frame of its sequence: no pair
 
     double Q[12], RD[9], tD[3], mv[6];
 #pragma unroll
@@ -379,20 +448,22 @@ __global__ void __launch_bounds__(64) k_smooth_lin(const ObsRec *__restrict__ ob
 __global__ void __launch_bounds__(SM_WG) k_smooth_init(SmoothBufs b, double w)
 {
     __shared__ double sh[SM_WG];
-    const int n = b.n, tid = (int)threadIdx.x;
-    double *lm = b.lm;
-    if (b.head[SMH_NPOSED] == 0) {
+    const int tid = (int)threadIdx.x;
+    const SmoothSeq q = smooth_seq_uniform(b, (int)blockIdx.x);
+    double *lm = b.lm + SM__N * q.k;
+    if (b.head[SMH__N * q.k + SMH_NPOSED] == 0) {
         if (tid < SM__N) lm[tid] = 0.0;
         __syncthreads();
         if (tid == 0) { lm[SM_STOP] = 1.0; lm[SM_STATUS] = 1.0; }
         return;
     }
-    const SmoothSet s = smooth_set(b.set[0], (size_t)n);
+    const SmoothSet s = smooth_set(b.set[0], (size_t)b.n);
     double cost = 0, pix = 0, corners = 0, ndata = 0;
-    for (int f = tid; f < n; f += SM_WG) {
+    for (int lf = tid; lf < q.n; lf += SM_WG) {
+        const int f = q.f0 + lf;
         const double c = s.c[f];
         b.cseed[f] = c;
-        cost += c * w + (f + 1 < n ? s.mot[SM_MOT * (size_t)f + 120] : 0.0);
+        cost += c * w + (lf + 1 < q.n ? s.mot[SM_MOT * (size_t)f + 120] : 0.0);
         pix += c;
         corners += 4.0 * b.ntags[f];
         ndata += b.ntags[f] > 0 ? 1.0 : 0.0;
@@ -418,12 +489,15 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_init(SmoothBufs b, double w)
 __global__ void __launch_bounds__(64) k_smooth_solve(SmoothBufs b, double w)
 {
     __shared__ double S[36], Mp[36], yv[6], rr[6], iv[6];
-    if (b.lm[SM_STOP] != 0.0) return;
-    const int lane = (int)threadIdx.x, n = b.n, i = lane / 6, j = lane % 6;
-    const double lambda = b.lm[SM_LAMBDA];
-    const SmoothSet s = smooth_set(b.set[0], (size_t)n);
+    const SmoothSeq q = smooth_seq_uniform(b, (int)blockIdx.x);
+    const double *lm = b.lm + SM__N * q.k;
+    if (lm[SM_STOP] != 0.0) return;
+    const int lane = (int)threadIdx.x, n = q.n, i = lane / 6, j = lane % 6;
+    const double lambda = lm[SM_LAMBDA];
+    const SmoothSet s = smooth_set(b.set[0], (size_t)b.n);
+    // f: the frame counted from the sequence's first; the buffers are indexed by the call's frame q.f0 + f
     for (int f = 0; f < n; f++) {
-        const double *ne = s.ne + 27 * (size_t)f, *mot = s.mot + SM_MOT * (size_t)f, *motp = mot - SM_MOT;
+        const double *ne = s.ne + 27 * (size_t)(q.f0 + f), *mot = s.mot + SM_MOT * (size_t)(q.f0 + f), *motp = mot - SM_MOT;
         double v = 0;
         if (lane < 36) {
             v = ne[i >= j ? TRI(i, j) : TRI(j, i)] * w;
@@ -450,7 +524,7 @@ __global__ void __launch_bounds__(64) k_smooth_solve(SmoothBufs b, double w)
         for (int c = 0; c < 6; c++) {
             const double p = S[7 * c];
             if (!(p > 0)) {  // the same LDS word in every lane: the whole wavefront leaves
-                if (lane == 0) b.head[SMH_FAIL] = 1;
+                if (lane == 0) b.head[SMH__N * q.k + SMH_FAIL] = 1;
                 return;
             }
             const double dc = sqrt(p);
@@ -483,7 +557,7 @@ __global__ void __launch_bounds__(64) k_smooth_solve(SmoothBufs b, double w)
             }
         }
         __syncthreads();
-        double *fac = b.fac + SM_FAC * (size_t)f;
+        double *fac = b.fac + SM_FAC * (size_t)(q.f0 + f);
         if (lane == 0) {
 #pragma unroll
             for (int a = 0; a < 6; a++) { yv[a] = y[a]; fac[72 + a] = inv[a]; fac[78 + a] = y[a]; }
@@ -498,7 +572,7 @@ __global__ void __launch_bounds__(64) k_smooth_solve(SmoothBufs b, double w)
     __threadfence();  // fac: written by some lanes, read by others below
     double x[6] = {0, 0, 0, 0, 0, 0};
     for (int f = n - 1; f >= 0; f--) {
-        const double *fac = b.fac + SM_FAC * (size_t)f;   // written above by this wavefront
+        const double *fac = b.fac + SM_FAC * (size_t)(q.f0 + f);   // written above by this wavefront
         __syncthreads();
         if (lane < 36) { S[lane] = fac[lane]; Mp[lane] = f + 1 < n ? fac[36 + lane] : 0.0; }
         if (lane < 6) { iv[lane] = fac[72 + lane]; yv[lane] = fac[78 + lane]; }
@@ -524,7 +598,7 @@ __global__ void __launch_bounds__(64) k_smooth_solve(SmoothBufs b, double w)
         for (int a = 0; a < 6; a++) x[a] = xn[a];
         if (lane == 0) {
 #pragma unroll
-            for (int a = 0; a < 6; a++) b.delta[6 * (size_t)f + a] = x[a];
+            for (int a = 0; a < 6; a++) b.delta[6 * (size_t)(q.f0 + f) + a] = x[a];
         }
     }
 }
@@ -533,24 +607,27 @@ __global__ void __launch_bounds__(64) k_smooth_solve(SmoothBufs b, double w)
 __global__ void __launch_bounds__(SM_WG) k_smooth_decide(SmoothBufs b, double w)
 {
     __shared__ double sh[SM_WG];
-    double *lm = b.lm;
-    const int n = b.n, tid = (int)threadIdx.x;
+    const SmoothSeq q = smooth_seq_uniform(b, (int)blockIdx.x);
+    double *lm = b.lm + SM__N * q.k;
+    int *head = b.head + SMH__N * q.k;
+    const int tid = (int)threadIdx.x;
     if (lm[SM_STOP] != 0.0) {
         if (tid == 0) lm[SM_TAKE] = 0.0;
         return;
     }
-    const bool failed = b.head[SMH_FAIL] != 0;
+    const bool failed = head[SMH_FAIL] != 0;
     const double cost = lm[SM_COST];
     __syncthreads();
     if (failed) {
-        if (tid == 0) { lm[SM_ITERS] += 1.0; lm[SM_LAMBDA] *= 10.0; lm[SM_TAKE] = 0.0; b.head[SMH_FAIL] = 0; }
+        if (tid == 0) { lm[SM_ITERS] += 1.0; lm[SM_LAMBDA] *= 10.0; lm[SM_TAKE] = 0.0; head[SMH_FAIL] = 0; }
         return;
     }
-    const SmoothSet t = smooth_set(b.set[1], (size_t)n);
+    const SmoothSet t = smooth_set(b.set[1], (size_t)b.n);
     double cn = 0, pix = 0;
-    for (int f = tid; f < n; f += SM_WG) {
+    for (int lf = tid; lf < q.n; lf += SM_WG) {
+        const int f = q.f0 + lf;
         const double c = t.c[f];
-        cn += c * w + (f + 1 < n ? t.mot[SM_MOT * (size_t)f + 120] : 0.0);
+        cn += c * w + (lf + 1 < q.n ? t.mot[SM_MOT * (size_t)f + 120] : 0.0);
         pix += c;
     }
     cn = smooth_block_sum(cn, sh);
@@ -570,30 +647,40 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_decide(SmoothBufs b, double w)
     }
 }
 
+// A workgroup a frame at a time, where the frame's sequence took its trial: a thread an entry of the frame's SM_SET (pose,
+// normal equations, pixel cost, the pair's motion blocks)
 __global__ void __launch_bounds__(SM_WG) k_smooth_commit(SmoothBufs b)
 {
-    if (b.lm[SM_TAKE] == 0.0) return;
-    const size_t total = (size_t)SM_SET * b.n, stride = (size_t)gridDim.x * SM_WG;
-    for (size_t k = (size_t)blockIdx.x * SM_WG + threadIdx.x; k < total; k += stride) b.set[0][k] = b.set[1][k];
+    if (b.n_seq == 1 && b.lm[SM_TAKE] == 0.0) return;
+    const size_t n = (size_t)b.n;
+    const int e = (int)threadIdx.x;
+    for (size_t f = blockIdx.x; f < n; f += gridDim.x) {
+        if (e >= SM_SET || b.lm[SM__N * smooth_seq_of_uniform(b, (int)f).k + SM_TAKE] == 0.0) continue;
+        const size_t at = e < 12 ? 12 * f + e : e < 39 ? 12 * n + 27 * f + (e - 12) : e == 39 ? 39 * n + f : 40 * n + SM_MOT * f + (e - 40);
+        b.set[0][at] = b.set[1][at];
+    }
 }
 
 __global__ void __launch_bounds__(SM_WG) k_smooth_finish(SmoothBufs b, CamPoseRec *__restrict__ out, SmoothResultRec *__restrict__ res)
 {
     const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x), n = b.n;
     if (f >= n) return;
-    const double *lm = b.lm;
-    const bool nothing = b.head[SMH_NPOSED] == 0;
+    const SmoothSeq q = smooth_seq_of(b, f);
+    const double *lm = b.lm + SM__N * q.k;
+    const int *head = b.head + SMH__N * q.k;
+    const bool nothing = head[SMH_NPOSED] == 0;
     int status = (int)lm[SM_STATUS];
     if (!nothing && status == 0 && lm[SM_SOLVED] == 0.0) status = 2;
-    if (f == 0) {
+    if (f == q.f0) {
+        res += q.k;
         const double k = nothing ? 0.0 : lm[SM_CORNERS];
         res->cost_seed = nothing ? 0.0 : lm[SM_COST0];
         res->cost = nothing ? 0.0 : lm[SM_COST];
         res->rms_px = k > 0 ? sqrt(lm[SM_PIX] / k) : 0.0;
         res->rms_seed_px = k > 0 ? sqrt(lm[SM_PIX0] / k) : 0.0;
         res->n_frames_data = nothing ? 0 : (int)lm[SM_NDATA];
-        res->n_filled = nothing ? 0 : n - b.head[SMH_NPOSED];
-        res->n_flipped = nothing ? 0 : b.head[SMH_NFLIP];
+        res->n_filled = nothing ? 0 : q.n - head[SMH_NPOSED];
+        res->n_flipped = nothing ? 0 : head[SMH_NFLIP];
         res->iterations = (int)lm[SM_ITERS];
         res->status = status;
         res->reserved[0] = 0; res->reserved[1] = 0; res->reserved[2] = 0;
@@ -631,13 +718,17 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_finish(SmoothBufs b, CamPoseRe
 __global__ void __launch_bounds__(64) k_smooth_cov(SmoothBufs b, double w, PoseCovRec *__restrict__ cov)
 {
     __shared__ double S[36], Mp[36], Cs[36], Sg[36], T[36], X[36], Rm[9], iv[6], dg[6];
-    const int lane = (int)threadIdx.x, n = b.n, i = lane / 6, j = lane % 6;
-    double *lm = b.lm;
-    if (b.head[SMH_NPOSED] == 0 || lm[SM_STATUS] != 0.0 || lm[SM_SOLVED] == 0.0) {
+    const SmoothSeq q = smooth_seq_uniform(b, (int)blockIdx.x);
+    const int lane = (int)threadIdx.x, n = q.n, i = lane / 6, j = lane % 6;
+    double *lm = b.lm + SM__N * q.k;
+    if (b.head[SMH__N * q.k + SMH_NPOSED] == 0 || lm[SM_STATUS] != 0.0 || lm[SM_SOLVED] == 0.0) {
         if (lane == 0) lm[SM_COV] = 1.0;
         return;
     }
-    const SmoothSet s = smooth_set(b.set[0], (size_t)n);
+    SmoothSet s = smooth_set(b.set[0], (size_t)b.n);   // from here on at the sequence's first frame: f counts from it
+    s.P += 12 * (size_t)q.f0; s.ne += 27 * (size_t)q.f0; s.mot += SM_MOT * (size_t)q.f0;
+    double *facs = b.fac + SM_FAC * (size_t)q.f0;
+    cov += q.f0;
     const int tri = i >= j ? TRI(i, j) : TRI(j, i);
     double h = 0, qn = 0, cc = 0, qp = 0;   // frame f's H, QN_f, C_f and QP_{f-1} entry of this lane
     if (lane < 36) {
@@ -698,7 +789,7 @@ __global__ void __launch_bounds__(64) k_smooth_cov(SmoothBufs b, double w, PoseC
             }
         }
         __syncthreads();
-        double *fac = b.fac + SM_FAC * (size_t)f;
+        double *fac = facs + SM_FAC * (size_t)f;
         if (lane < 36) fac[lane] = i >= j ? S[lane] : 0.0;
         if (lane == 0) {
 #pragma unroll
@@ -714,7 +805,7 @@ __global__ void __launch_bounds__(64) k_smooth_cov(SmoothBufs b, double w, PoseC
     if (lane == 0) lm[SM_COV] = 0.0;
     double l = 0, m = 0, iq = 0, r = 0;   // frame f's L, M, 1 / diag and R entry of this lane
     {
-        const double *fac = b.fac + SM_FAC * (size_t)(n - 1);
+        const double *fac = facs + SM_FAC * (size_t)(n - 1);
         if (lane < 36) l = fac[lane];
         if (lane < 6) iq = fac[72 + lane];
         if (lane < 9) r = s.P[12 * (size_t)(n - 1) + lane];
@@ -725,7 +816,7 @@ __global__ void __launch_bounds__(64) k_smooth_cov(SmoothBufs b, double w, PoseC
         if (lane < 6) iv[lane] = iq;
         if (lane < 9) Rm[lane] = r;
         if (f > 0) {  // the next frame's
-            const double *fac = b.fac - SM_FAC + SM_FAC * (size_t)f;
+            const double *fac = facs - SM_FAC + SM_FAC * (size_t)f;
             if (lane < 36) { l = fac[lane]; m = fac[36 + lane]; }
             if (lane < 6) iq = fac[72 + lane];
             if (lane < 9) r = s.P[12 * (size_t)(f - 1) + lane];
@@ -794,13 +885,14 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_cov_finish(SmoothBufs b, doubl
 {
     const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (f >= b.n) return;
-    const int status = (int)b.lm[SM_COV];
+    const double *lm = b.lm + SM__N * smooth_seq_of(b, f).k;
+    const int status = (int)lm[SM_COV];
     PoseCovRec *o = cov + f;
     if (status != 0) {
 #pragma unroll
         for (int k = 0; k < 36; k++) o->cov[k] = 0.0;
     }
     o->sigma_px = sigma_px;
-    o->dof = status == 1 ? 0 : 2 * (int)b.lm[SM_CORNERS] - 6;   // 8 a taking-part slot, less the 6 of one free pose
+    o->dof = status == 1 ? 0 : 2 * (int)lm[SM_CORNERS] - 6;   // 8 a taking-part slot, less the 6 of one free pose
     o->status = status;
 }

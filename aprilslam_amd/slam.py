@@ -252,6 +252,12 @@ class SLAM:
         (TagDetector.localize_sequence); like localize it leaves the graph, the window and my_pose() alone."""
         return self.detector.localize_sequence(dets, poses, n_per_frame, self.tag_map(), **kw)
 
+    def localize_sequences(self, sequences, **kw):
+        """Several sequences of consecutive frames ((dets, poses, n_per_frame) triples) against tag_map(), solved side by side in
+        one call (TagDetector.localize_sequences) -> a list of smooth.SmoothResult; the graph, the window and my_pose() stay
+        as they are."""
+        return self.detector.localize_sequences(sequences, self.tag_map(), **kw)
+
     def average_distance_to_nodes(self):
         """Mean distance camera <-> tag over ALL nodes of the graph (0 for an empty graph), slam.py:65-80."""
         nodes = self.graph.get_nodes()

@@ -2,6 +2,8 @@
 under a random-walk motion prior (asl_smooth_batch / asl_smooth_frames_device, k_smooth.inc).  Every frame gets a pose: one
 without a mapped tag is carried by its neighbours, a single-tag frame is kept out of its mirrored planar minimum by them,
 and corner noise is averaged over the sequence.
+Several sequences in one call, solved side by side: Detector.smooth_sequences / TagDetector.localize_sequences
+(asl_smooth_sequences_batch), one SmoothResult per sequence.
 
     SmoothResult         the poses (CAM_POSE_DTYPE per frame), the SMOOTH_RESULT_DTYPE record, the filled / flipped masks and,
                          from a solve with with_cov (asl_smooth_cov_batch), every pose's covariance (POSE_COV_DTYPE per frame)

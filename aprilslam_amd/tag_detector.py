@@ -236,6 +236,31 @@ class TagDetector:
                          sigma_trans=sigma_trans, max_iters=max_iters, seed=seed, with_cov=with_cov)
         return SmoothResult(got[0], got[1], seed, got[2] if with_cov else None)
 
+    def localize_sequences(self, sequences, tag_map, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, max_tags=None,
+                           with_cov=False):
+        """localize_sequence for several sequences in one call: `sequences` is a list of (dets, poses, n_per_frame) triples as
+        detect_host / collect return them, each one camera's consecutive frames (different cameras, recordings, or the pieces
+        of a recording cut where the camera was off) -> a list of smooth.SmoothResult, one per sequence, each what
+        localize_sequence returns for it alone at the same max_tags.  Packs them end to end with one common max_tags,
+        localises every frame once (the seeds, kept in the results) and smooths all sequences side by side
+        (asl_smooth_sequences_batch): no term links two sequences."""
+        from .dist import pack_observations
+        from .smooth import SmoothResult
+        if not len(sequences):
+            return []
+        npfs = [np.asarray(s[2], dtype=np.int64) for s in sequences]
+        if any(len(n) == 0 for n in npfs):
+            raise ValueError("every sequence needs at least one frame")
+        mt = int(max_tags) if max_tags is not None else max(1, min(256, max(int(n.max()) for n in npfs)))
+        obs = np.concatenate([pack_observations(s[0], s[1], n, mt) for s, n in zip(sequences, npfs)])
+        start = np.concatenate([[0], np.cumsum([len(n) for n in npfs])])
+        det = self.detector._det
+        seed = det.localize(obs, tag_map, self._K(), self._dist(), self.tag_size)
+        got = det.smooth_sequences(obs, start, tag_map, self._K(), self._dist(), self.tag_size, sigma_px=sigma_px, sigma_rot=sigma_rot,
+                                   sigma_trans=sigma_trans, max_iters=max_iters, seed=seed, with_cov=with_cov)
+        return [SmoothResult(got[0][a:b], got[1][k], seed[a:b], got[2][a:b] if with_cov else None)
+                for k, (a, b) in enumerate(zip(start[:-1], start[1:]))]
+
     # -- camera calibration from frames of a known target (asl_calibrate_batch) ------------------------------------------
     def calibrate(self, frames, tag_map, n_dist=5, K_init=None, flags=0, max_iters=30):
         """Host frames ((n, H, W, 3) BGR or (n, H, W) gray uint8, or a list of them) that see the target tag_map (a

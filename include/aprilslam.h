@@ -430,8 +430,8 @@ typedef struct {
    status 2 or 3; T is the chain's), 1 nothing to solve (T the identity).  d_result: one asl_smooth_result.
    ASL_EINVAL, nothing written: a NULL pointer; n_frames outside [1, 65535]; max_tags outside [1, 256]; n_dist not 0, 4 or 5,
    or n_dist > 0 with dist NULL; a non-finite K, tag_size or sigma; a sigma <= 0; max_iters outside [1, 100]; d_out
-   overlapping d_seed.  One sequence per call, even frame spacing.  Deterministic: the same input gives the same bytes.
-   tests/smooth_ref.py states the algorithm. */
+   overlapping d_seed.  One sequence per call (several: asl_smooth_sequences_device), even frame spacing.  Deterministic:
+   the same input gives the same bytes.  tests/smooth_ref.py states the algorithm. */
 int asl_smooth_frames_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
                              const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed, double sigma_px,
                              double sigma_rot, double sigma_trans, int max_iters, void *d_out, void *d_result, void *stream);
@@ -464,6 +464,32 @@ int asl_smooth_cov_batch(asl_detector *det, const asl_obs *obs, int n_frames, in
                          const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed, double sigma_px,
                          double sigma_rot, double sigma_trans, int max_iters, asl_cam_pose *out, asl_smooth_result *result,
                          asl_pose_cov *cov);
+
+/* Several sequences in one call, solved side by side: sequence k is the frames [seq_start[k], seq_start[k + 1]) of d_obs,
+   d_seed, d_out and d_cov (different cameras, recordings, or the pieces of a recording cut where the camera was off).
+   Sequence k's d_out records, its d_cov records and d_results[k] are, byte for byte, what asl_smooth_cov_frames_device
+   (d_cov NULL: asl_smooth_frames_device) writes for those frames alone with the same arguments; d_out and d_results do not
+   depend on whether d_cov is given.  No term links two sequences: no motion block across a boundary, no seed carried over,
+   and each has its own lambda, stop, failed trials, result status, covariance status and dof -- one that stops early, fails
+   (status 1, 2, 3) or has no covariance changes nothing in another.  The map, the camera, the sigmas, max_iters and max_tags
+   are the call's.  The serial chains over the frames run one wavefront per sequence, side by side, so the chains' share of
+   the time is that of the slowest sequence (frames x trials), not the sum (DESIGN.md 7g has the measurements).  d_results: n_seq asl_smooth_result.  d_cov: NULL, or n_frames asl_pose_cov.
+   seq_start: a HOST array of n_seq + 1 offsets, as K and dist are host arrays; it is read before the call returns (the
+   caller may overwrite it then) and reaches the device in stream order, so calls enqueued back to back each see their own.
+   Nothing waits; the first call at a larger n_frames or n_seq grows the work buffers, which synchronises.
+   ASL_EINVAL, nothing written: whatever the single-sequence calls refuse, except that n_frames may be in [1, 1048576];
+   seq_start NULL; n_seq outside [1, 65535]; seq_start[0] != 0; seq_start[n_seq] != n_frames; a sequence of fewer than 1 or
+   more than 65535 frames (offsets that do not strictly increase).  Deterministic: the same input gives the same bytes. */
+int asl_smooth_sequences_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed,
+                                const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
+                                int max_iters, void *d_out, void *d_results, void *d_cov, void *stream);
+/* The same computation on host records, synchronous; seed == NULL: the per-frame localisation of all frames runs first, as
+   in asl_smooth_batch.  results: n_seq records.  cov: NULL, or n_frames records. */
+int asl_smooth_sequences_batch(asl_detector *det, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                               const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed,
+                               const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
+                               int max_iters, asl_cam_pose *out, asl_smooth_result *results, asl_pose_cov *cov);
 
 /* ---- before the detector: the image-formation step on the device (reference src/simulation/renderer.py:197-274:
    purple clear colour, one GL_LINEAR-textured quad per tag, BGR read-back).  One plane per visible tag and frame, in

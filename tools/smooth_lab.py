@@ -8,10 +8,14 @@ call alone, the two alternating inside every repetition, median of --reps after 
 error against the renderer's ground truth before (the per-frame poses) and after.  --drop-every N empties every Nth frame
 first, so that the smoothing has holes to fill.  --cov adds the covariance leg: asl_smooth_cov_frames_device timed next
 to the plain call, the two alternating inside every repetition (smooth_cov_ms_median / _min), and under "cov" the median
-reported std of the frames with data and of the filled ones next to the errors above.
+reported std of the frames with data and of the filled ones next to the errors above.  --sequences S adds the block cut into
+S equal sequences, solved in one batched call (asl_smooth_sequences_device) and in a loop of S single-sequence device calls,
+the legs again alternating inside every repetition ("sequences": batched_ms_median / _min, loop_ms_median / _min, with --cov
+both with the covariance; same_bytes: the two wrote the same poses, results and covariances).  --loop-only leaves the batched
+call out (a build that does not have it).
 
     python tools/smooth_lab.py [--frames 1024] [--reps 20] [--max-tags 32] [--sigma-px 0.3] [--sigma-rot 0.01]
-                               [--sigma-trans 0.05] [--max-iters 20] [--drop-every 0] [--cov]
+                               [--sigma-trans 0.05] [--max-iters 20] [--drop-every 0] [--cov] [--sequences S [--loop-only]]
 """
 import argparse
 import json
@@ -41,7 +45,11 @@ def main():
     ap.add_argument("--max-iters", type=int, default=20)
     ap.add_argument("--drop-every", type=int, default=0)
     ap.add_argument("--cov", action="store_true", help="also time the call with the covariance, alternating with the plain one")
+    ap.add_argument("--sequences", type=int, default=0, help="also cut the block into S equal sequences: one batched call against a loop of S calls")
+    ap.add_argument("--loop-only", action="store_true", help="with --sequences: time the loop of single calls alone")
     a = ap.parse_args()
+    if a.sequences and (a.sequences < 1 or a.frames % a.sequences):
+        ap.error("--sequences must divide --frames")
 
     import torch
 
@@ -91,7 +99,30 @@ def main():
         e1.synchronize()
         return e0.elapsed_time(e1)
 
+    S = a.sequences
+    m = n // S if S else 0
+    seq_start = np.arange(S + 1, dtype=np.int32) * m
+    if S:   # outputs of their own, so that the two can be compared
+        d_outs = [torch.zeros_like(d_out) for _ in range(2)]
+        d_ress = [torch.zeros(S * _lib.SMOOTH_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev) for _ in range(2)]
+        d_covs = [torch.zeros_like(d_cov) for _ in range(2)]
+        torch.cuda.synchronize()
+    kw = dict(sigma_px=a.sigma_px, sigma_rot=a.sigma_rot, sigma_trans=a.sigma_trans, max_iters=a.max_iters, stream=stream.cuda_stream)
+
+    def batched():
+        det.smooth_sequences_device(d_obs.data_ptr(), n, mt, d_map.data_ptr(), len(rec), d_seed.data_ptr(), seq_start, d_outs[0].data_ptr(),
+                                    d_ress[0].data_ptr(), K, None, bench.TAG_INNER, cov_ptr=d_covs[0].data_ptr() if a.cov else None, **kw)
+
+    def loop():
+        for k in range(S):
+            det.smooth_device(d_obs[k * m:].data_ptr(), m, mt, d_map.data_ptr(), len(rec), d_seed[k * m:].data_ptr(),
+                              d_outs[1][k * m:].data_ptr(), d_ress[1][64 * k:].data_ptr(), K, None, bench.TAG_INNER,
+                              cov_ptr=d_covs[1][k * m:].data_ptr() if a.cov else None, **kw)
+
     legs = [localize, smooth] + ([smooth_cov] if a.cov else [])
+    seq_legs = ([] if a.loop_only else [batched]) + [loop] if S else []
+    first_seq_leg = len(legs)
+    legs += seq_legs
     with torch.cuda.stream(stream):
         for _ in range(a.warmup):
             for fn in legs:
@@ -137,6 +168,17 @@ def main():
         line["cov"] = {"status": sorted(set(cov["status"].tolist())), "dof": int(cov["dof"][0]),
                        "std_same_frames": stds(posed & np.isin(out["status"], (0, 6))), "std_filled_frames": stds(~posed & np.isin(out["status"], (0, 6))),
                        "note": "median over the frames of |std of the three rotation / translation components|: compare with the RMS errors above"}
+    if S:
+        t = dict(zip([fn.__name__ for fn in seq_legs], times[first_seq_leg:]))
+        line["sequences"] = {"n_seq": S, "frames_each": m, "with_cov": bool(a.cov),
+                             "loop_ms_median": float(np.median(t["loop"])), "loop_ms_min": float(np.min(t["loop"]))}
+        if not a.loop_only:
+            line["sequences"].update({"batched_ms_median": float(np.median(t["batched"])), "batched_ms_min": float(np.min(t["batched"])),
+                                      "loop_over_batched": float(np.median(t["loop"]) / np.median(t["batched"])),
+                                      "same_bytes": all(torch.equal(x[0], x[1]) for x in (d_outs, d_ress) + ((d_covs,) if a.cov else ()))})
+        r = d_ress[1].cpu().numpy().view(_lib.SMOOTH_RESULT_DTYPE)
+        line["sequences"]["iterations"] = [int(r["iterations"].min()), int(r["iterations"].max())]
+        line["sequences"]["status"] = sorted(set(r["status"].tolist()))
     print(json.dumps(line))
     det.close()
 
