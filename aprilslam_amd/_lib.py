@@ -104,29 +104,35 @@ def load():
     L.asl_pack_observations_device.argtypes = [vp, vp, i32, vp]
     L.asl_graph_frames_device.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp]
     L.asl_graph_picks_device.argtypes = [vp, vp, i32, i32, i32, vp, C.c_uint32, C.c_uint32, vp, i32, vp, vp]
-    L.asl_localize_frames_device.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, C.c_double, vp, vp]
-    L.asl_localize_batch.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, C.c_double, vp]
-    L.asl_localize_cov_frames_device.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp]
-    L.asl_localize_cov_batch.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, C.c_double, C.c_double, vp, vp]
-    L.asl_pose_cov_device.argtypes = [vp, vp, i32, dp, dp, i32, C.c_double, C.c_double, vp, vp]
-    L.asl_localize_rig_frames_device.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, C.c_double, C.c_double, vp, vp]
-    L.asl_localize_rig_cov_frames_device.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, C.c_double, C.c_double, C.c_double, vp, vp, vp]
-    L.asl_localize_rig_batch.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, C.c_double, C.c_double, vp]
-    L.asl_localize_rig_cov_batch.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, C.c_double, C.c_double, C.c_double, vp, vp]
-    L.asl_solve_pnp_cov_batch.argtypes = [vp, C.POINTER(C.c_float), dp, dp, dp, i32, C.c_double, C.c_double, vp, i32]
-    L.asl_calibrate_frames_device.argtypes = [vp, vp, i32, i32, vp, i32, C.c_double, i32, i32, dp, i32, i32, i32, vp, vp, vp]
-    L.asl_calibrate_batch.argtypes = [vp, vp, i32, i32, vp, i32, C.c_double, i32, i32, dp, i32, i32, i32, vp, vp]
-    L.asl_map_frames_device.argtypes = [vp, vp, i32, i32, i32, dp, dp, i32, C.c_double, i32, i32, vp, vp, vp, vp, vp]
-    L.asl_map_batch.argtypes = [vp, vp, i32, i32, i32, dp, dp, i32, C.c_double, i32, i32, vp, vp, vp, vp]
-    L.asl_smooth_frames_device.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, vp, C.c_double, C.c_double, C.c_double, i32,
-                                           vp, vp, vp]
-    L.asl_smooth_batch.argtypes = [vp, vp, i32, i32, vp, i32, dp, dp, i32, C.c_double, vp, C.c_double, C.c_double, C.c_double, i32, vp, vp]
-    L.asl_smooth_cov_frames_device.argtypes = L.asl_smooth_frames_device.argtypes[:-1] + [vp, vp]
-    L.asl_smooth_cov_batch.argtypes = L.asl_smooth_batch.argtypes + [vp]
-    i32p = C.POINTER(C.c_int32)
-    L.asl_smooth_sequences_device.argtypes = (L.asl_smooth_cov_frames_device.argtypes[:11] + [i32p, i32]
-                                              + L.asl_smooth_cov_frames_device.argtypes[11:])
-    L.asl_smooth_sequences_batch.argtypes = L.asl_smooth_cov_batch.argtypes[:11] + [i32p, i32] + L.asl_smooth_cov_batch.argtypes[11:]
+    # the solver entries (csrc/solve_host.inc), from the pieces their argument lists share
+    dbl, obs_block, tag_map = C.c_double, [vp, i32, i32], [vp, i32]    # obs, n_frames, max_tags; map, n_ids
+    camera, sigmas = [dp, dp, i32, dbl], [dbl, dbl, dbl]          # K, dist, n_dist, tag_size; sigma_px, sigma_rot, sigma_trans
+    loc = [vp] + obs_block + tag_map + camera + [dbl]             # detector, ..., max_tag_rms_px
+    L.asl_localize_frames_device.argtypes = loc + [vp, vp]
+    L.asl_localize_batch.argtypes = loc + [vp]
+    L.asl_localize_cov_frames_device.argtypes = loc + [dbl, vp, vp, vp]
+    L.asl_localize_cov_batch.argtypes = loc + [dbl, vp, vp]
+    rig = [vp, vp, i32, i32, i32] + tag_map + [vp, dbl, dbl]      # detector, obs, n_cams, n_frames, max_tags, ..., rig, tag_size, max_tag_rms_px
+    L.asl_localize_rig_frames_device.argtypes = rig + [vp, vp]
+    L.asl_localize_rig_batch.argtypes = rig + [vp]
+    L.asl_localize_rig_cov_frames_device.argtypes = rig + [dbl, vp, vp, vp]
+    L.asl_localize_rig_cov_batch.argtypes = rig + [dbl, vp, vp]
+    L.asl_pose_cov_device.argtypes = [vp, vp, i32] + camera + [dbl, vp, vp]
+    L.asl_solve_pnp_cov_batch.argtypes = [vp, C.POINTER(C.c_float), dp] + camera + [dbl, vp, i32]
+    calib = [vp] + obs_block + tag_map + [dbl, i32, i32, dp, i32, i32, i32, vp, vp]    # ..., tag_size, width, height, K_init, n_dist, flags, max_iters, the two results
+    L.asl_calibrate_frames_device.argtypes = calib + [vp]
+    L.asl_calibrate_batch.argtypes = calib
+    mapping = [vp] + obs_block + [i32] + camera + [i32, i32, vp, vp, vp, vp]    # ..., n_ids, camera, world_id, max_iters, the four results
+    L.asl_map_frames_device.argtypes = mapping + [vp]
+    L.asl_map_batch.argtypes = mapping
+    smooth, seqs = [vp] + obs_block + tag_map + camera + [vp], [C.POINTER(C.c_int32), i32]    # ..., seed; seq_start, n_seq
+    solve = sigmas + [i32, vp, vp]                                # ..., max_iters, out, result
+    L.asl_smooth_frames_device.argtypes = smooth + solve + [vp]
+    L.asl_smooth_batch.argtypes = smooth + solve
+    L.asl_smooth_cov_frames_device.argtypes = smooth + solve + [vp, vp]
+    L.asl_smooth_cov_batch.argtypes = smooth + solve + [vp]
+    L.asl_smooth_sequences_device.argtypes = smooth + seqs + solve + [vp, vp]
+    L.asl_smooth_sequences_batch.argtypes = smooth + seqs + solve + [vp]
     L.asl_debug_fetch.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.asl_debug_refit.argtypes = [vp, i32, vp, C.c_size_t]
     L.asl_debug_division_check.argtypes = [vp, i32, vp, C.c_size_t]
@@ -156,6 +162,11 @@ def blur_taps(quad_sigma):
 def _ptr(addr):
     """a device address"""
     return C.c_void_p(int(addr))
+
+
+def _data(a):
+    """the address of a host array's data, or NULL for an empty one"""
+    return a.ctypes.data if a.size else None
 
 
 def _opt_ptr(addr):
@@ -379,17 +390,15 @@ class Detector:
         tag_map (n_ids,) MAP_TAG_DTYPE (or a localize.TagMap) -> (n_frames,) CAM_POSE_DTYPE, world<-camera per frame.
         sigma_px not None: asl_localize_cov_batch -> (poses, (n_frames,) POSE_COV_DTYPE), the covariance scaled by that
         corner sigma, or by the solve's own estimate for 0."""
-        o = _obs_records(obs)
-        m = _map_records(tag_map)
+        o, m = _obs_records(obs), _map_records(tag_map)
         keep, Kp, dpp, nd = _camera(K, dist, square=True)
         out = np.zeros(o.shape[0], dtype=CAM_POSE_DTYPE)
-        args = (self._h, o.ctypes.data if o.size else None, o.shape[0], o.shape[1], m.ctypes.data if m.size else None, len(m), Kp, dpp, nd,
-                float(tag_size), float(max_tag_rms_px))
+        args = (self._h, _data(o), o.shape[0], o.shape[1], _data(m), len(m), Kp, dpp, nd, float(tag_size), float(max_tag_rms_px))
         if sigma_px is None:
-            check(self._L.asl_localize_batch(*args, out.ctypes.data if out.size else None))
+            check(self._L.asl_localize_batch(*args, _data(out)))
             return out
         cov = np.zeros(o.shape[0], dtype=POSE_COV_DTYPE)
-        check(self._L.asl_localize_cov_batch(*args, float(sigma_px), out.ctypes.data if out.size else None, cov.ctypes.data if cov.size else None))
+        check(self._L.asl_localize_cov_batch(*args, float(sigma_px), _data(out), _data(cov)))
         return out, cov
 
     def localize_device(self, obs_ptr, n_frames, max_tags, map_ptr, n_ids, out_ptr, K, dist, tag_size, max_tag_rms_px=0.0,
@@ -416,13 +425,12 @@ class Detector:
         if len(r) != o.shape[0]:
             raise ValueError("the rig has %d cameras, obs has %d" % (len(r), o.shape[0]))
         out = np.zeros(o.shape[1], dtype=CAM_POSE_DTYPE)
-        args = (self._h, o.ctypes.data if o.size else None, o.shape[0], o.shape[1], o.shape[2], m.ctypes.data if m.size else None, len(m),
-                r.ctypes.data if r.size else None, float(tag_size), float(max_tag_rms_px))
+        args = (self._h, _data(o), o.shape[0], o.shape[1], o.shape[2], _data(m), len(m), _data(r), float(tag_size), float(max_tag_rms_px))
         if sigma_px is None:
-            check(self._L.asl_localize_rig_batch(*args, out.ctypes.data if out.size else None))
+            check(self._L.asl_localize_rig_batch(*args, _data(out)))
             return out
         cov = np.zeros(o.shape[1], dtype=POSE_COV_DTYPE)
-        check(self._L.asl_localize_rig_cov_batch(*args, float(sigma_px), out.ctypes.data if out.size else None, cov.ctypes.data if cov.size else None))
+        check(self._L.asl_localize_rig_cov_batch(*args, float(sigma_px), _data(out), _data(cov)))
         return out, cov
 
     def localize_rig_device(self, obs_ptr, n_cams, n_frames, max_tags, map_ptr, n_ids, rig_ptr, out_ptr, tag_size, max_tag_rms_px=0.0,
@@ -447,7 +455,7 @@ class Detector:
         keep, Kp, dpp, nd = _camera(K, dist)
         cov = np.zeros(len(c), dtype=POSE_COV_DTYPE)
         check(self._L.asl_solve_pnp_cov_batch(self._h, c.ctypes.data_as(C.POINTER(C.c_float)), Tc.ctypes.data_as(_DP), Kp, dpp, nd, float(tag_size),
-                                              float(sigma_px), cov.ctypes.data if cov.size else None, len(c)))
+                                              float(sigma_px), _data(cov), len(c)))
         return cov
 
     def pose_cov_device(self, obs_ptr, n_records, cov_ptr, K, dist, tag_size, sigma_px=0.0, stream=0):
@@ -471,15 +479,12 @@ class Detector:
     def calibrate(self, obs, tag_map, tag_size, width, height, K_init=None, n_dist=5, flags=0, max_iters=30):
         """asl_calibrate_batch: host records obs (n_frames, max_tags) OBS_DTYPE of a target whose tag poses tag_map
         ((n_ids,) MAP_TAG_DTYPE or a localize.TagMap) gives -> (CALIB_RESULT_DTYPE record, (n_frames,) CAM_POSE_DTYPE)."""
-        o = _obs_records(obs)
-        m = _map_records(tag_map)
+        o, m = _obs_records(obs), _map_records(tag_map)
         keep, Kp = self._calib_args(K_init, n_dist)
         res = np.zeros((), dtype=CALIB_RESULT_DTYPE)
         poses = np.zeros(o.shape[0], dtype=CAM_POSE_DTYPE)
-        check(self._L.asl_calibrate_batch(self._h, o.ctypes.data if o.size else None, o.shape[0], o.shape[1],
-                                          m.ctypes.data if m.size else None, len(m), float(tag_size), int(width), int(height), Kp,
-                                          int(n_dist), int(flags), int(max_iters), res.ctypes.data,
-                                          poses.ctypes.data if poses.size else None))
+        check(self._L.asl_calibrate_batch(self._h, _data(o), o.shape[0], o.shape[1], _data(m), len(m), float(tag_size), int(width), int(height), Kp,
+                                          int(n_dist), int(flags), int(max_iters), res.ctypes.data, _data(poses)))
         return res, poses
 
     def calibrate_device(self, obs_ptr, n_frames, max_tags, map_ptr, n_ids, tag_size, width, height, result_ptr, poses_ptr,
@@ -501,9 +506,8 @@ class Detector:
         tmap = np.zeros(max(int(n_ids), 1), dtype=MAP_TAG_DTYPE)
         std = np.zeros((max(int(n_ids), 1), 6), dtype=np.float64) if with_std else None
         poses = np.zeros(o.shape[0], dtype=CAM_POSE_DTYPE)
-        check(self._L.asl_map_batch(self._h, o.ctypes.data if o.size else None, o.shape[0], o.shape[1], int(n_ids), Kp, dpp, nd,
-                                    float(tag_size), int(world_id), int(max_iters), tmap.ctypes.data,
-                                    std.ctypes.data if with_std else None, poses.ctypes.data if poses.size else None, res.ctypes.data))
+        check(self._L.asl_map_batch(self._h, _data(o), o.shape[0], o.shape[1], int(n_ids), Kp, dpp, nd, float(tag_size), int(world_id), int(max_iters),
+                                    tmap.ctypes.data, std.ctypes.data if with_std else None, _data(poses), res.ctypes.data))
         return res, tmap, std, poses
 
     def build_map_device(self, obs_ptr, n_frames, max_tags, n_ids, K, dist, tag_size, map_ptr, std_ptr, poses_ptr, result_ptr,
@@ -525,23 +529,7 @@ class Detector:
         obs; None: that localisation runs first.
         with_cov: asl_smooth_cov_batch -> (poses, result, (n_frames,) POSE_COV_DTYPE), every pose's marginal covariance under
         the three sigmas (the same poses and result, byte for byte)."""
-        o = _obs_records(obs)
-        m = _map_records(tag_map)
-        keep, Kp, dpp, nd = _camera(K, dist, square=True)
-        sd = None if seed is None else np.ascontiguousarray(seed, dtype=CAM_POSE_DTYPE).ravel()
-        if sd is not None and len(sd) != o.shape[0]:
-            raise ValueError("seed must hold one pose per frame")
-        out = np.zeros(o.shape[0], dtype=CAM_POSE_DTYPE)
-        res = np.zeros((), dtype=SMOOTH_RESULT_DTYPE)
-        args = (self._h, o.ctypes.data if o.size else None, o.shape[0], o.shape[1], m.ctypes.data if m.size else None,
-                len(m), Kp, dpp, nd, float(tag_size), None if sd is None else sd.ctypes.data, float(sigma_px),
-                float(sigma_rot), float(sigma_trans), int(max_iters), out.ctypes.data if out.size else None, res.ctypes.data)
-        if not with_cov:
-            check(self._L.asl_smooth_batch(*args))
-            return out, res
-        cov = np.zeros(o.shape[0], dtype=POSE_COV_DTYPE)
-        check(self._L.asl_smooth_cov_batch(*args, cov.ctypes.data if cov.size else None))
-        return out, res, cov
+        return self._smooth_host(obs, None, tag_map, K, dist, tag_size, (sigma_px, sigma_rot, sigma_trans), max_iters, seed, with_cov)
 
     def smooth_device(self, obs_ptr, n_frames, max_tags, map_ptr, n_ids, seed_ptr, out_ptr, result_ptr, K, dist, tag_size, sigma_px=1.0,
                       sigma_rot=0.05, sigma_trans=0.5, max_iters=20, stream=0, cov_ptr=None):
@@ -549,14 +537,8 @@ class Detector:
         asl_cam_pose, as localize_device wrote them), out_ptr (n_frames asl_cam_pose) and result_ptr (one asl_smooth_result)
         are device addresses; enqueued on `stream`, no wait.  cov_ptr not None (n_frames asl_pose_cov):
         asl_smooth_cov_frames_device."""
-        keep, Kp, dpp, nd = _camera(K, dist, square=True)
-        args = (self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids), Kp, dpp, nd,
-                float(tag_size), _ptr(seed_ptr), float(sigma_px), float(sigma_rot), float(sigma_trans),
-                int(max_iters), _ptr(out_ptr), _ptr(result_ptr))
-        if cov_ptr is None:
-            check(self._L.asl_smooth_frames_device(*args, _ptr(stream)))
-        else:
-            check(self._L.asl_smooth_cov_frames_device(*args, _ptr(cov_ptr), _ptr(stream)))
+        self._smooth_device((obs_ptr, map_ptr, seed_ptr, out_ptr, result_ptr), n_frames, max_tags, n_ids, None, K, dist, tag_size,
+                            (sigma_px, sigma_rot, sigma_trans), max_iters, stream, cov_ptr)
 
     @staticmethod
     def _seq_start(seq_start, n_frames):
@@ -575,33 +557,49 @@ class Detector:
         OBS_DTYPE holds the sequences end to end, sequence k the frames seq_start[k]:seq_start[k + 1] (n_seq + 1 offsets, from
         0 to n_frames) -> ((n_frames,) CAM_POSE_DTYPE, (n_seq,) SMOOTH_RESULT_DTYPE[, (n_frames,) POSE_COV_DTYPE]): for every
         sequence the bytes smooth() returns for its frames alone.  The map, the camera, the sigmas and max_iters are shared."""
-        o = _obs_records(obs)
-        m = _map_records(tag_map)
-        keep, Kp, dpp, nd = _camera(K, dist, square=True)
-        ss, ssp, n_seq = self._seq_start(seq_start, o.shape[0])
-        sd = None if seed is None else np.ascontiguousarray(seed, dtype=CAM_POSE_DTYPE).ravel()
-        if sd is not None and len(sd) != o.shape[0]:
-            raise ValueError("seed must hold one pose per frame")
-        out = np.zeros(o.shape[0], dtype=CAM_POSE_DTYPE)
-        res = np.zeros(n_seq, dtype=SMOOTH_RESULT_DTYPE)
-        cov = np.zeros(o.shape[0], dtype=POSE_COV_DTYPE) if with_cov else None
-        check(self._L.asl_smooth_sequences_batch(
-            self._h, o.ctypes.data if o.size else None, o.shape[0], o.shape[1], m.ctypes.data if m.size else None, len(m), Kp, dpp, nd,
-            float(tag_size), None if sd is None else sd.ctypes.data, ssp, n_seq, float(sigma_px), float(sigma_rot), float(sigma_trans),
-            int(max_iters), out.ctypes.data if out.size else None, res.ctypes.data, cov.ctypes.data if with_cov and cov.size else None))
-        return (out, res, cov) if with_cov else (out, res)
+        return self._smooth_host(obs, seq_start, tag_map, K, dist, tag_size, (sigma_px, sigma_rot, sigma_trans), max_iters, seed, with_cov)
 
     def smooth_sequences_device(self, obs_ptr, n_frames, max_tags, map_ptr, n_ids, seed_ptr, seq_start, out_ptr, results_ptr, K, dist,
                                 tag_size, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, stream=0, cov_ptr=None):
         """asl_smooth_sequences_device: smooth_device for several sequences; seq_start is a HOST array of n_seq + 1 offsets,
         results_ptr n_seq asl_smooth_result on the device, cov_ptr None or n_frames asl_pose_cov.  Enqueued on `stream`, no
         wait; seq_start is read before this returns."""
+        self._smooth_device((obs_ptr, map_ptr, seed_ptr, out_ptr, results_ptr), n_frames, max_tags, n_ids, seq_start, K, dist, tag_size,
+                            (sigma_px, sigma_rot, sigma_trans), max_iters, stream, cov_ptr)
+
+    def _smooth_host(self, obs, seq_start, tag_map, K, dist, tag_size, sigmas, max_iters, seed, with_cov):
+        """smooth (seq_start None: asl_smooth_batch / asl_smooth_cov_batch, whose n_frames bound is a sequence's) and
+        smooth_sequences (asl_smooth_sequences_batch)"""
+        o, m = _obs_records(obs), _map_records(tag_map)
         keep, Kp, dpp, nd = _camera(K, dist, square=True)
-        ss, ssp, n_seq = self._seq_start(seq_start, n_frames)
-        check(self._L.asl_smooth_sequences_device(
-            self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids), Kp, dpp, nd, float(tag_size), _ptr(seed_ptr),
-            ssp, n_seq, float(sigma_px), float(sigma_rot), float(sigma_trans), int(max_iters), _ptr(out_ptr), _ptr(results_ptr),
-            _opt_ptr(cov_ptr), _ptr(stream)))
+        n = o.shape[0]
+        sd = None if seed is None else np.ascontiguousarray(seed, dtype=CAM_POSE_DTYPE).ravel()
+        if sd is not None and len(sd) != n:
+            raise ValueError("seed must hold one pose per frame")
+        out = np.zeros(n, dtype=CAM_POSE_DTYPE)
+        cov = np.zeros(n, dtype=POSE_COV_DTYPE) if with_cov else None
+        if seq_start is None:
+            fn, seqs, last = (self._L.asl_smooth_cov_batch, (), (_data(cov),)) if with_cov else (self._L.asl_smooth_batch, (), ())
+        else:
+            ss, ssp, n_seq = self._seq_start(seq_start, n)
+            fn, seqs, last = self._L.asl_smooth_sequences_batch, (ssp, n_seq), (_data(cov) if with_cov else None,)
+        res = np.zeros(seqs[1] if seqs else (), dtype=SMOOTH_RESULT_DTYPE)
+        check(fn(self._h, _data(o), n, o.shape[1], _data(m), len(m), Kp, dpp, nd, float(tag_size), None if sd is None else sd.ctypes.data, *seqs,
+                 *map(float, sigmas), int(max_iters), _data(out), res.ctypes.data, *last))
+        return (out, res, cov) if with_cov else (out, res)
+
+    def _smooth_device(self, ptrs, n_frames, max_tags, n_ids, seq_start, K, dist, tag_size, sigmas, max_iters, stream, cov_ptr):
+        """smooth_device (seq_start None: asl_smooth_frames_device / asl_smooth_cov_frames_device) and smooth_sequences_device
+        (asl_smooth_sequences_device); ptrs: the addresses of obs, map, seed, out and result(s)"""
+        obs_ptr, map_ptr, seed_ptr, out_ptr, result_ptr = ptrs
+        keep, Kp, dpp, nd = _camera(K, dist, square=True)
+        if seq_start is None:
+            fn, seqs, last = (self._L.asl_smooth_frames_device, (), ()) if cov_ptr is None else (self._L.asl_smooth_cov_frames_device, (), (_ptr(cov_ptr),))
+        else:
+            ss, ssp, n_seq = self._seq_start(seq_start, n_frames)
+            fn, seqs, last = self._L.asl_smooth_sequences_device, (ssp, n_seq), (_opt_ptr(cov_ptr),)
+        check(fn(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids), Kp, dpp, nd, float(tag_size), _ptr(seed_ptr), *seqs,
+                 *map(float, sigmas), int(max_iters), _ptr(out_ptr), _ptr(result_ptr), *last, _ptr(stream)))
 
     def collect_view(self):
         """Wait for the submitted batch; (dets, poses or None, n_per_frame) as numpy VIEWS of the detector's page-locked result

@@ -128,7 +128,6 @@ struct asl_detector {
     DevBuf<uint8_t> gn_ws;  // asl_gn_solve: its inputs and the LM's buffers (gn_host.inc)
     DevBuf<uint8_t> loc_obs, loc_map;  // the *_batch solver entries: the host records' device copies (grow on demand)
     DevBuf<uint8_t> solve_out;         // the *_batch solver entries: their results, until copied back
-    DevBuf<uint8_t> rig_cams;          // asl_localize_rig_batch: the device copy of the camera table
     DevBuf<uint8_t> rect_src, rect_dst;  // asl_rectify_u8: the host image's device copy and the result (no batch reads them)
     DevBuf<uint8_t> cal_ws;  // calibration: per-frame workspace and state (k_calib.inc)
     DevBuf<uint8_t> map_ws, map_lm;  // map reconstruction (k_map.inc): sized by the input / by the problem
@@ -1101,754 +1100,5 @@ extern "C" int asl_solve_pnp_batch(asl_detector *d, const float *corners, const 
 }
 
 #include "gn_host.inc"
-
-// ---- the device solvers on asl_obs blocks: localisation (k_localize.inc), calibration (k_calib.inc), mapping (k_map.inc)
-
-// The checks they share on the obs block (max_tags slots per frame, ids below n_ids), the lens model and the tag size;
-// no_dist: the caller takes coefficients and dist is NULL
-static int check_obs_args(int max_tags, int n_ids, int n_dist, bool no_dist, double tag_size)
-{
-    if (max_tags < 1 || max_tags > 256) return fail(ASL_EINVAL, "max_tags must be in [1, 256] (got %d)", max_tags);
-    if (n_ids < 1) return fail(ASL_EINVAL, "n_ids must be >= 1 (got %d)", n_ids);
-    if (int rc = check_n_dist(n_dist)) return rc;
-    if (n_dist && no_dist) return fail(ASL_EINVAL, "dist is NULL with n_dist = %d", n_dist);
-    if (!(tag_size > 0) || !std::isfinite(tag_size)) return fail(ASL_EINVAL, "tag_size must be positive (got %g)", tag_size);
-    return ASL_OK;
-}
-
-// The *_batch entry points: the host obs block (and the map, if given) into the detector's device copies
-static int upload_obs(asl_detector *d, const char *what, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids)
-{
-    const size_t obs_bytes = sizeof(asl_obs) * (size_t)n_frames * (size_t)max_tags, map_bytes = sizeof(asl_map_tag) * (size_t)n_ids;
-    if (d->loc_obs.ensure(obs_bytes) || (map && d->loc_map.ensure(map_bytes))) return fail(ASL_ENOMEM, "%s workspace allocation failed", what);
-    HIPCHK(hipMemcpy(d->loc_obs.p, obs, obs_bytes, hipMemcpyHostToDevice));
-    if (map) HIPCHK(hipMemcpy(d->loc_map.p, map, map_bytes, hipMemcpyHostToDevice));
-    return ASL_OK;
-}
-
-static int check_sigma_px(double sigma_px)
-{
-    if (!(sigma_px >= 0) || !std::isfinite(sigma_px)) return fail(ASL_EINVAL, "sigma_px must be >= 0 and finite (got %g)", sigma_px);
-    return ASL_OK;
-}
-
-// one camera table, wherever it came from: the model and the mounting of every camera
-static int check_rig_table(const asl_rig_camera *rig, int n_cams)
-{
-    for (int c = 0; c < n_cams; c++) {
-        const asl_rig_camera &r = rig[c];
-        if (check_n_dist(r.n_dist)) return fail(ASL_EINVAL, "camera %d: n_dist must be 0, 4 or 5 (got %d)", c, r.n_dist);
-        for (int k = 0; k < 9; k++)
-            if (!std::isfinite(r.K[k])) return fail(ASL_EINVAL, "camera %d: K is not finite", c);
-        for (int k = 0; k < r.n_dist; k++)
-            if (!std::isfinite(r.dist[k])) return fail(ASL_EINVAL, "camera %d: dist is not finite", c);
-        for (int k = 0; k < 12; k++)
-            if (!std::isfinite(r.E[k])) return fail(ASL_EINVAL, "camera %d: E is not finite", c);
-        const double *E = r.E;
-        double dev = 0;
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++)
-                dev = std::max(dev, std::fabs(E[4 * i] * E[4 * j] + E[4 * i + 1] * E[4 * j + 1] + E[4 * i + 2] * E[4 * j + 2] - (i == j ? 1.0 : 0.0)));
-        const double det = E[0] * (E[5] * E[10] - E[6] * E[9]) - E[1] * (E[4] * E[10] - E[6] * E[8]) + E[2] * (E[4] * E[9] - E[5] * E[8]);
-        if (!(dev <= 1e-6) || !(det > 0))
-            return fail(ASL_EINVAL, "camera %d: the rotation part of E is not a rotation (|R R^T - I| = %g, det %g)", c, dev, det);
-    }
-    return ASL_OK;
-}
-
-// One localisation call (k_localize.inc, k_rig.inc), whichever of the eight entry points made it, in their argument order.  The single-camera forms
-// leave n_cams 0 and rig NULL and give K / dist / n_dist; the rig forms give n_cams and the table and leave those NULL.
-// The plain forms leave sigma_px 0 and cov NULL.  obs, map, rig, out and cov are all host or all device pointers.
-struct LocCall {
-    const void *obs; int n_cams, n_frames, max_tags;
-    const void *map; int n_ids;
-    const double *K, *dist; int n_dist;
-    const void *rig;
-    double tag_size, gate, sigma_px;
-    void *out, *cov;
-    bool with_cov;      // a covariance form: cov must be there
-};
-
-static bool is_rig(const LocCall &c) { return c.n_cams || c.rig; }
-
-// Every refusal, before anything is written or enqueued.  A rig's table is checked last: where it is, or (device: the
-// pointers are the device's) in a copy read back, at most 16 x 216 bytes; it must be complete when the call is made.
-static int check_localize_call(const asl_detector *d, const LocCall &c, bool device)
-{
-    static_assert(sizeof(MapTagRec) == sizeof(asl_map_tag) && sizeof(asl_map_tag) == 104, "asl_map_tag layout");
-    static_assert(sizeof(CamPoseRec) == sizeof(asl_cam_pose) && sizeof(asl_cam_pose) == 160, "asl_cam_pose layout");
-    static_assert(sizeof(PoseCovRec) == sizeof(asl_pose_cov) && sizeof(asl_pose_cov) == 304, "asl_pose_cov layout");
-    static_assert(sizeof(RigCamRec) == sizeof(asl_rig_camera) && sizeof(asl_rig_camera) == 216, "asl_rig_camera layout");
-    const bool rig = is_rig(c);
-    if (c.with_cov && !c.cov) return fail(ASL_EINVAL, "NULL argument");
-    if (!d) return fail(ASL_EINVAL, "NULL detector");
-    if (!c.obs || !c.map || !(rig ? c.rig : (const void *)c.K) || !c.out) return fail(ASL_EINVAL, "NULL argument");
-    if (c.n_frames < 0) return fail(ASL_EINVAL, "n_frames < 0");
-    if (rig && (c.n_cams < 1 || c.n_cams > RIG_MAX_CAMS)) return fail(ASL_EINVAL, "n_cams must be in [1, %d] (got %d)", RIG_MAX_CAMS, c.n_cams);
-    if (int rc = check_obs_args(c.max_tags, c.n_ids, c.n_dist, !c.dist, c.tag_size)) return rc;
-    if (rig && c.n_cams * c.max_tags > RIG_MAX_SLOTS)
-        return fail(ASL_EINVAL, "n_cams * max_tags must be <= %d (got %d x %d)", RIG_MAX_SLOTS, c.n_cams, c.max_tags);
-    if (!(c.gate >= 0) || !std::isfinite(c.gate)) return fail(ASL_EINVAL, "max_tag_rms_px must be >= 0 (got %g)", c.gate);
-    if (int rc = check_sigma_px(c.sigma_px)) return rc;
-    if (!rig) return ASL_OK;
-    asl_rig_camera tab[RIG_MAX_CAMS];
-    if (device) {
-        HIPCHK(hipSetDevice(d->device));
-        HIPCHK(hipMemcpy(tab, c.rig, sizeof(asl_rig_camera) * (size_t)c.n_cams, hipMemcpyDeviceToHost));
-    }
-    return check_rig_table(device ? tab : (const asl_rig_camera *)c.rig, c.n_cams);
-}
-
-// c's pointers are the device's; cov NULL: the plain kernel
-static void launch_localize(const asl_detector *d, const LocCall &c, hipStream_t st)
-{
-    static const double no_K[9] = {};
-    const bool rig = is_rig(c);
-    const CamDev cam = make_cam(d, rig ? no_K : c.K, c.dist, c.n_dist, c.tag_size);   // a rig: for its half alone
-    const dim3 grid((unsigned int)c.n_frames), block(ASL_WAVE);
-    const ObsRec *obs = (const ObsRec *)c.obs;
-    const MapTagRec *map = (const MapTagRec *)c.map;
-    const RigCamRec *tab = (const RigCamRec *)c.rig;
-    CamPoseRec *out = (CamPoseRec *)c.out;
-    PoseCovRec *cov = (PoseCovRec *)c.cov;
-    const size_t lds = rig ? rig_lds_bytes(c.n_cams, c.max_tags) : loc_lds_bytes(c.max_tags);
-    if (!rig && cov)
-        hipLaunchKernelGGL(k_localize<true>, grid, block, lds, st, obs, c.max_tags, map, c.n_ids, cam, c.gate, out, cov, c.sigma_px);
-    else if (!rig)
-        hipLaunchKernelGGL(k_localize<false>, grid, block, lds, st, obs, c.max_tags, map, c.n_ids, cam, c.gate, out, cov, c.sigma_px);
-    else if (cov)
-        hipLaunchKernelGGL(k_localize_rig<true>, grid, block, lds, st, obs, c.n_cams, c.max_tags, map, c.n_ids, tab, cam.half, c.gate, out, cov, c.sigma_px);
-    else
-        hipLaunchKernelGGL(k_localize_rig<false>, grid, block, lds, st, obs, c.n_cams, c.max_tags, map, c.n_ids, tab, cam.half, c.gate, out, cov, c.sigma_px);
-}
-
-// the four device forms
-static int localize_frames_device(asl_detector *d, const LocCall &c, void *stream)
-{
-    if (int rc = check_localize_call(d, c, true)) return rc;
-    if (c.n_frames == 0) return ASL_OK;
-    HIPCHK(hipSetDevice(d->device));
-    launch_localize(d, c, (hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return ASL_OK;
-}
-
-// the four host forms: the block, the map and the table into the detector's device copies, the records back from solve_out
-static int localize_batch(asl_detector *d, const LocCall &c)
-{
-    if (int rc = check_localize_call(d, c, false)) return rc;
-    if (c.n_frames == 0) return ASL_OK;
-    HIPCHK(hipSetDevice(d->device));
-    const bool rig = is_rig(c);
-    const size_t n = (size_t)c.n_frames, rig_bytes = sizeof(asl_rig_camera) * (size_t)c.n_cams;
-    asl_cam_pose *d_out = nullptr;
-    asl_pose_cov *d_cov = nullptr;
-    if (carve_ws(d->solve_out, [&](WsCarve &w) { d_out = w.take<asl_cam_pose>(n); d_cov = w.take<asl_pose_cov>(c.cov ? n : 0); }) ||
-        (rig && d->rig_cams.ensure(rig_bytes)))
-        return fail(ASL_ENOMEM, "%slocalisation workspace allocation failed", rig ? "rig " : "");
-    if (int rc = upload_obs(d, rig ? "rig localisation" : "localisation", (const asl_obs *)c.obs, (rig ? c.n_cams : 1) * c.n_frames, c.max_tags,
-                            (const asl_map_tag *)c.map, c.n_ids))
-        return rc;
-    if (rig) HIPCHK(hipMemcpy(d->rig_cams.p, c.rig, rig_bytes, hipMemcpyHostToDevice));
-    LocCall dc = c;
-    dc.obs = d->loc_obs.p; dc.map = d->loc_map.p; dc.rig = rig ? d->rig_cams.p : nullptr; dc.out = d_out; dc.cov = c.cov ? d_cov : nullptr;
-    launch_localize(d, dc, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(c.out, d_out, sizeof(asl_cam_pose) * n, hipMemcpyDeviceToHost));
-    if (c.cov) HIPCHK(hipMemcpy(c.cov, d_cov, sizeof(asl_pose_cov) * n, hipMemcpyDeviceToHost));
-    return ASL_OK;
-}
-
-extern "C" int asl_localize_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
-                                          const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
-                                          void *d_out, void *stream)
-{
-    return localize_frames_device(d, {d_obs, 0, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, nullptr,
-                                      tag_size, max_tag_rms_px, 0.0, d_out, nullptr, false}, stream);
-}
-
-extern "C" int asl_localize_cov_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
-                                              const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
-                                              double sigma_px, void *d_out, void *d_cov, void *stream)
-{
-    return localize_frames_device(d, {d_obs, 0, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, nullptr,
-                                      tag_size, max_tag_rms_px, sigma_px, d_out, d_cov, true}, stream);
-}
-
-extern "C" int asl_localize_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
-                                  const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px, asl_cam_pose *out)
-{
-    return localize_batch(d, {obs, 0, n_frames, max_tags, map, n_ids, K, dist, n_dist, nullptr,
-                              tag_size, max_tag_rms_px, 0.0, out, nullptr, false});
-}
-
-extern "C" int asl_localize_cov_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
-                                      const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px, double sigma_px,
-                                      asl_cam_pose *out, asl_pose_cov *cov)
-{
-    return localize_batch(d, {obs, 0, n_frames, max_tags, map, n_ids, K, dist, n_dist, nullptr,
-                              tag_size, max_tag_rms_px, sigma_px, out, cov, true});
-}
-
-extern "C" int asl_localize_rig_frames_device(asl_detector *d, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map,
-                                              int n_ids, const void *d_rig, double tag_size, double max_tag_rms_px, void *d_out, void *stream)
-{
-    return localize_frames_device(d, {d_obs, n_cams, n_frames, max_tags, d_map, n_ids, nullptr, nullptr, 0, d_rig,
-                                      tag_size, max_tag_rms_px, 0.0, d_out, nullptr, false}, stream);
-}
-
-extern "C" int asl_localize_rig_cov_frames_device(asl_detector *d, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map,
-                                                  int n_ids, const void *d_rig, double tag_size, double max_tag_rms_px, double sigma_px,
-                                                  void *d_out, void *d_cov, void *stream)
-{
-    return localize_frames_device(d, {d_obs, n_cams, n_frames, max_tags, d_map, n_ids, nullptr, nullptr, 0, d_rig,
-                                      tag_size, max_tag_rms_px, sigma_px, d_out, d_cov, true}, stream);
-}
-
-extern "C" int asl_localize_rig_batch(asl_detector *d, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
-                                      const asl_rig_camera *rig, double tag_size, double max_tag_rms_px, asl_cam_pose *out)
-{
-    return localize_batch(d, {obs, n_cams, n_frames, max_tags, map, n_ids, nullptr, nullptr, 0, rig,
-                              tag_size, max_tag_rms_px, 0.0, out, nullptr, false});
-}
-
-extern "C" int asl_localize_rig_cov_batch(asl_detector *d, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_map_tag *map,
-                                          int n_ids, const asl_rig_camera *rig, double tag_size, double max_tag_rms_px, double sigma_px,
-                                          asl_cam_pose *out, asl_pose_cov *cov)
-{
-    return localize_batch(d, {obs, n_cams, n_frames, max_tags, map, n_ids, nullptr, nullptr, 0, rig,
-                              tag_size, max_tag_rms_px, sigma_px, out, cov, true});
-}
-
-// ---- per-tag pose covariance (k_posecov.inc)
-
-static int check_pose_cov_args(const void *in, int n, const double *K, const double *dist, int n_dist, double tag_size, double sigma_px, const void *cov)
-{
-    if (!in || !K || !cov) return fail(ASL_EINVAL, "NULL argument");
-    if (n < 0) return fail(ASL_EINVAL, "record count < 0");
-    if (int rc = check_n_dist(n_dist)) return rc;
-    if (n_dist && !dist) return fail(ASL_EINVAL, "dist is NULL with n_dist = %d", n_dist);
-    if (!(tag_size > 0) || !std::isfinite(tag_size)) return fail(ASL_EINVAL, "tag_size must be positive (got %g)", tag_size);
-    return check_sigma_px(sigma_px);
-}
-
-static void launch_pose_cov(asl_detector *d, const void *d_obs, int n, const double *K, const double *dist, int n_dist, double tag_size,
-                            double sigma_px, void *d_cov, hipStream_t st)
-{
-    CamDev cam = make_cam(d, K, dist, n_dist, tag_size);
-    hipLaunchKernelGGL(k_pnp_cov, dim3((unsigned int)((n + PNP_TAGS_PER_WAVE - 1) / PNP_TAGS_PER_WAVE)), dim3(ASL_WAVE), 0, st, (const ObsRec *)d_obs, n, cam,
-                       sigma_px, (PoseCovRec *)d_cov);
-}
-
-extern "C" int asl_pose_cov_device(asl_detector *d, const void *d_obs, int n_records, const double *K, const double *dist, int n_dist,
-                                   double tag_size, double sigma_px, void *d_cov, void *stream)
-{
-    if (!d) return fail(ASL_EINVAL, "NULL detector");
-    if (int rc = check_pose_cov_args(d_obs, n_records, K, dist, n_dist, tag_size, sigma_px, d_cov)) return rc;
-    if (n_records == 0) return ASL_OK;
-    HIPCHK(hipSetDevice(d->device));
-    launch_pose_cov(d, d_obs, n_records, K, dist, n_dist, tag_size, sigma_px, d_cov, (hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return ASL_OK;
-}
-
-extern "C" int asl_solve_pnp_cov_batch(asl_detector *d, const float *corners, const double *T, const double *K, const double *dist, int n_dist,
-                                       double tag_size, double sigma_px, asl_pose_cov *cov, int N)
-{
-    if (!d) return fail(ASL_EINVAL, "NULL detector");
-    if (!T) return fail(ASL_EINVAL, "NULL argument");
-    if (int rc = check_pose_cov_args(corners, N, K, dist, n_dist, tag_size, sigma_px, cov)) return rc;
-    if (N == 0) return ASL_OK;
-    HIPCHK(hipSetDevice(d->device));
-    std::vector<asl_obs> rec((size_t)N);
-    for (int i = 0; i < N; i++) {  // a pose with a non-finite entry (a failed PnP) is no pose: status 1
-        bool finite = true;
-        for (int k = 0; k < 12; k++) finite = finite && std::isfinite(T[16 * (size_t)i + k]);
-        rec[i].id = 0;
-        rec[i].flags = finite ? 3 : 1;
-        memcpy(rec[i].corners, corners + 8 * (size_t)i, sizeof rec[i].corners);
-        memcpy(rec[i].T, T + 16 * (size_t)i, sizeof rec[i].T);
-    }
-    const size_t cov_bytes = sizeof(asl_pose_cov) * (size_t)N;
-    if (d->solve_out.ensure(cov_bytes)) return fail(ASL_ENOMEM, "pose covariance workspace allocation failed");
-    if (int rc = upload_obs(d, "pose covariance", rec.data(), 1, N, nullptr, 0)) return rc;
-    launch_pose_cov(d, d->loc_obs.p, N, K, dist, n_dist, tag_size, sigma_px, d->solve_out.p, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(cov, d->solve_out.p, cov_bytes, hipMemcpyDeviceToHost));
-    return ASL_OK;
-}
-
-static int check_calib_args(const void *obs, int n_frames, int max_tags, const void *map, int n_ids, double tag_size, int width, int height,
-                            const double *K_init, int n_dist, int flags, int max_iters, const void *result, const void *poses)
-{
-    if (!obs || !map || !result || !poses) return fail(ASL_EINVAL, "NULL argument");
-    if (n_frames < 1) return fail(ASL_EINVAL, "n_frames must be >= 1 (got %d)", n_frames);
-    if (int rc = check_obs_args(max_tags, n_ids, n_dist, false, tag_size)) return rc;
-    if (width < 1 || height < 1) return fail(ASL_EINVAL, "width and height must be positive (got %d x %d)", width, height);
-    if (max_iters < 1) return fail(ASL_EINVAL, "max_iters must be >= 1 (got %d)", max_iters);
-    if (flags & ~(ASL_CALIB_FIX_PRINCIPAL_POINT | ASL_CALIB_FIX_ASPECT_RATIO | ASL_CALIB_ZERO_TANGENT_DIST))
-        return fail(ASL_EINVAL, "unknown calibration flags 0x%x", flags);
-    if (K_init && !(K_init[0] > 0 && K_init[4] > 0 && std::isfinite(K_init[0]) && std::isfinite(K_init[4]) && std::isfinite(K_init[2]) &&
-                    std::isfinite(K_init[5])))
-        return fail(ASL_EINVAL, "K_init must have finite, positive focal lengths");
-    return ASL_OK;
-}
-
-// the calibration workspace: state, frame lists and per-frame buffers, carved from d->cal_ws
-static int launch_calibrate(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids, double tag_size,
-                            int width, int height, const double *K_init, int n_dist, int flags, int max_iters, void *d_result, void *d_poses,
-                            hipStream_t st)
-{
-    static_assert(sizeof(CalibResultRec) == sizeof(asl_calib_result) && sizeof(asl_calib_result) == 216, "asl_calib_result layout");
-    const size_t nf = (size_t)n_frames;
-    CalibArgs a{};
-    if (carve_ws(d->cal_ws, [&](WsCarve &c) {
-            a.st = c.take<CalibState>(1); a.list = c.take<int>(nf); a.fr = c.take<int>(CAL_FR * nf);
-            a.zh = c.take<double>(CAL_ZH * nf); a.seedc = c.take<double>(nf); a.pose = c.take<double>(2 * 12 * nf);
-            a.H = c.take<double>(2 * CAL_HS * nf); a.SB = c.take<double>(CAL_SB * nf); a.back = c.take<double>(CAL_BK * nf);
-        }))
-        return fail(ASL_ENOMEM, "calibration workspace allocation failed");
-    a.obs = (const ObsRec *)d_obs; a.map = (const MapTagRec *)d_map;
-    a.res = (CalibResultRec *)d_result; a.out = (CamPoseRec *)d_poses;
-    a.half = (double)(float)(tag_size / 2);  // object corners are float32, as in the PnP
-    a.width = width; a.height = height;
-    a.has_init = K_init != nullptr;
-    if (K_init) { a.Kinit[0] = K_init[0]; a.Kinit[1] = K_init[4]; a.Kinit[2] = K_init[2]; a.Kinit[3] = K_init[5]; }
-    a.n_frames = n_frames; a.max_tags = max_tags; a.n_ids = n_ids; a.n_dist = n_dist; a.flags = flags; a.max_iters = max_iters;
-    int np = 0;  // the free entries of (fx, fy, cx, cy, k1, k2, p1, p2, k3)
-    if (!(flags & ASL_CALIB_FIX_ASPECT_RATIO)) a.sel[np++] = 0;
-    a.sel[np++] = 1;
-    if (!(flags & ASL_CALIB_FIX_PRINCIPAL_POINT)) { a.sel[np++] = 2; a.sel[np++] = 3; }
-    if (n_dist >= 4) {
-        a.sel[np++] = 4; a.sel[np++] = 5;
-        if (!(flags & ASL_CALIB_ZERO_TANGENT_DIST)) { a.sel[np++] = 6; a.sel[np++] = 7; }
-    }
-    if (n_dist == 5) a.sel[np++] = 8;
-    a.np = np;
-    const dim3 frames((unsigned int)n_frames), wave(ASL_WAVE), wg(CAL_WG);
-    const size_t lds = loc_lds_bytes(max_tags);
-    auto seed = n_dist == 5 ? k_calib_seed<5> : n_dist == 4 ? k_calib_seed<4> : k_calib_seed<0>;
-    auto step = n_dist == 5 ? k_calib_step<5> : n_dist == 4 ? k_calib_step<4> : k_calib_step<0>;
-    hipLaunchKernelGGL(k_calib_init, frames, wave, 0, st, a);
-    hipLaunchKernelGGL(k_calib_k0, dim3(1), wg, 0, st, a);
-    hipLaunchKernelGGL(seed, frames, wave, lds, st, a);
-    hipLaunchKernelGGL(k_calib_start, dim3(1), wg, 0, st, a);
-    for (int it = 0; it < max_iters; it++) {
-        hipLaunchKernelGGL(k_calib_schur, frames, wave, 0, st, a, 0);
-        hipLaunchKernelGGL(k_calib_solve, dim3(1), wg, 0, st, a);
-        hipLaunchKernelGGL(step, frames, wave, lds, st, a);
-        hipLaunchKernelGGL(k_calib_decide, dim3(1), wg, 0, st, a);
-    }
-    hipLaunchKernelGGL(k_calib_schur, frames, wave, 0, st, a, 1);
-    hipLaunchKernelGGL(k_calib_finish, dim3(1), wg, 0, st, a);
-    HIPCHK(hipGetLastError());
-    return ASL_OK;
-}
-
-extern "C" int asl_calibrate_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
-                                           double tag_size, int width, int height, const double *K_init, int n_dist, int flags, int max_iters,
-                                           void *d_result, void *d_poses, void *stream)
-{
-    if (!d) return fail(ASL_EINVAL, "NULL detector");
-    int rc = check_calib_args(d_obs, n_frames, max_tags, d_map, n_ids, tag_size, width, height, K_init, n_dist, flags, max_iters, d_result, d_poses);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(d->device));
-    return launch_calibrate(d, d_obs, n_frames, max_tags, d_map, n_ids, tag_size, width, height, K_init, n_dist, flags, max_iters, d_result,
-                            d_poses, (hipStream_t)stream);
-}
-
-extern "C" int asl_calibrate_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
-                                   double tag_size, int width, int height, const double *K_init, int n_dist, int flags, int max_iters,
-                                   asl_calib_result *result, asl_cam_pose *poses)
-{
-    if (!d) return fail(ASL_EINVAL, "NULL detector");
-    int rc = check_calib_args(obs, n_frames, max_tags, map, n_ids, tag_size, width, height, K_init, n_dist, flags, max_iters, result, poses);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(d->device));
-    asl_calib_result *d_result;
-    asl_cam_pose *d_poses;
-    if (carve_ws(d->solve_out, [&](WsCarve &c) { d_result = c.take<asl_calib_result>(1); d_poses = c.take<asl_cam_pose>(n_frames); }))
-        return fail(ASL_ENOMEM, "calibration workspace allocation failed");
-    if ((rc = upload_obs(d, "calibration", obs, n_frames, max_tags, map, n_ids))) return rc;
-    rc = launch_calibrate(d, d->loc_obs.p, n_frames, max_tags, d->loc_map.p, n_ids, tag_size, width, height, K_init, n_dist, flags, max_iters,
-                          d_result, d_poses, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(result, d_result, sizeof(asl_calib_result), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(poses, d_poses, sizeof(asl_cam_pose) * (size_t)n_frames, hipMemcpyDeviceToHost));
-    return ASL_OK;
-}
-
-static int check_map_args(const void *obs, int n_frames, int max_tags, int n_ids, const double *K, const double *dist, int n_dist,
-                          double tag_size, int world_id, int max_iters, const void *map, const void *poses, const void *result)
-{
-    if (!obs || !K || !map || !poses || !result) return fail(ASL_EINVAL, "NULL argument");
-    if (n_frames < 1) return fail(ASL_EINVAL, "n_frames must be >= 1 (got %d)", n_frames);
-    if (int rc = check_obs_args(max_tags, n_ids, n_dist, !dist, tag_size)) return rc;
-    if (world_id < -1 || world_id >= n_ids) return fail(ASL_EINVAL, "world_id must be -1 or in [0, n_ids) (got %d)", world_id);
-    if (max_iters < 1 || max_iters > MAP_MAX_ITERS) return fail(ASL_EINVAL, "max_iters must be in [1, %d] (got %d)", MAP_MAX_ITERS, max_iters);
-    return ASL_OK;
-}
-
-static int launch_map(asl_detector *d, const void *d_obs, int n_frames, int max_tags, int n_ids, const double *K, const double *dist, int n_dist,
-                      double tag_size, int world_id, int max_iters, void *d_map, void *d_std, void *d_poses, void *d_result, hipStream_t st)
-{
-    static_assert(sizeof(MapResultRec) == sizeof(asl_map_result) && sizeof(asl_map_result) == 64, "asl_map_result layout");
-    const size_t nf = (size_t)n_frames, ni = (size_t)n_ids, nsl = nf * (size_t)max_tags;
-    MapArgs a{};
-    int *per_id, *per_frame, *per_cam, *per_obs, *csr;  // the grouped int arrays, one piece per group
-    if (carve_ws(d->map_ws, [&](WsCarve &c) {
-            a.head = c.take<MapHead>(1); per_id = c.take<int>(4 * (ni + 1)); per_frame = c.take<int>(3 * (nf + 1));
-            per_cam = c.take<int>(4 * (nf + 1)); a.tag_state = c.take<int>(ni + 1); a.slot_obs = c.take<int>(nsl); per_obs = c.take<int>(4 * nsl);
-            csr = c.take<int>(2 * nsl + nf + ni + 2); a.W = c.take<double>(12 * nf); a.G = c.take<double>(12 * ni);
-        }))
-        return fail(ASL_ENOMEM, "map workspace allocation failed");
-    a.obs = (const ObsRec *)d_obs; a.n_frames = n_frames; a.max_tags = max_tags; a.n_ids = n_ids; a.world_req = world_id;
-    a.seen = per_id; a.id_tag = per_id + (ni + 1); a.tag_id = per_id + 2 * (ni + 1); a.tmp = per_id + 3 * (ni + 1);
-    a.fr_npart = per_frame; a.fr_cam = per_frame + (nf + 1); a.fr_obs0 = per_frame + 2 * (nf + 1);
-    a.cam_frame = per_cam; a.cam_ptr0 = per_cam + (nf + 1); a.cam_state = per_cam + 2 * (nf + 1); a.cam_seed = per_cam + 3 * (nf + 1);
-    a.obs_slot = per_obs; a.obs_cam = per_obs + nsl; a.obs_tag = per_obs + 2 * nsl; a.obs_act = per_obs + 3 * nsl;
-    a.cam_obs = csr; a.tag_obs = csr + nsl; a.cam_ptr = csr + 2 * nsl; a.tag_ptr = csr + 2 * nsl + nf + 1;
-    const CamDev cam = make_cam(d, K, dist, n_dist, tag_size);
-
-    hipLaunchKernelGGL(k_map_gather, dim3(1), dim3(MAP_WG), 0, st, a);
-    MapHead h;
-    HIPCHK(hipMemcpyAsync(&h, a.head, sizeof h, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));  // the one wait before the end: the reduced system is sized by the tags seen
-    const int NC = h.n_cams, NT = h.n_tags, NM = h.n_obs, WT = h.world_tag;
-    auto finish_nothing = [&]() {
-        hipLaunchKernelGGL(k_map_finish, dim3(1), dim3(MAP_WG), 0, st, a, NC, NT, NM, WT, 1, (const double *)nullptr, (const double *)nullptr,
-                           (const double *)nullptr, (const double *)nullptr, (const int *)nullptr, (MapTagRec *)d_map, (double *)d_std, (CamPoseRec *)d_poses,
-                           (MapResultRec *)d_result);
-        HIPCHK(hipGetLastError());
-        return ASL_OK;
-    };
-    if (NT > MAP_MAX_TAGS) return fail(ASL_EINVAL, "the frames see %d tags; the map's dense reduced system takes at most %d", NT, MAP_MAX_TAGS);
-    if (WT < 0) {
-        int rc = finish_nothing();
-        if (rc) return rc;
-        if (world_id >= 0) return fail(ASL_EINVAL, "world tag %d is not seen by any frame with 2 or more taking-part slots", world_id);
-        return ASL_OK;
-    }
-
-    // the problem-sized part: the LM's buffers (gn_lm_carve), the seed costs, the std; the reduced system reads the LM's
-    // copies of the list offsets (k_map_park empties them after the stop)
-    const int n = 6 * NT;
-    const size_t nc = (size_t)NC, nt = (size_t)NT, nm = (size_t)NM;
-    GnSystem sys = {nullptr, nullptr, a.cam_obs, nullptr, a.tag_obs, a.obs_cam, a.obs_tag, nullptr, NC, NT, WT};
-    GnLmBufs b;
-    double *seed_obs, *var;
-    if (carve_ws(d->map_lm, [&](WsCarve &c) {
-            b = gn_lm_carve(c, sys, NM, 2 * MAP_LM__N);
-            seed_obs = c.take<double>(nm); var = c.take<double>(n); sys.cam_ptr = c.take<int>(nc + 1); sys.tag_ptr = c.take<int>(nt + 1);
-        }))
-        return fail(ASL_ENOMEM, "map workspace allocation failed");
-    a.obs_of = sys.obs_of;
-    double *lm = b.lm, *lm0 = lm + MAP_LM__N;
-    const dim3 wg(MAP_WG);
-
-    range_push("map: seed");
-    HIPCHK(hipMemsetAsync(a.obs_of, 0xff, 4 * nc * nt, st));
-    hipLaunchKernelGGL(k_map_table, dim3((NM + 255) / 256), dim3(256), 0, st, a, NM, NT);
-    hipLaunchKernelGGL(k_map_csr, dim3(1), wg, 0, st, a, NC, NT);
-    hipLaunchKernelGGL(k_map_chain, dim3(1), wg, 0, st, a, NC, NT, NM, WT);
-    hipLaunchKernelGGL(k_map_csr, dim3(1), wg, 0, st, a, NC, NT);
-    for (int sw = 0; sw < 2; sw++) {
-        hipLaunchKernelGGL(k_map_sweep_cam, dim3(NC), dim3(ASL_WAVE), loc_lds_bytes(max_tags), st, a, cam);
-        hipLaunchKernelGGL(k_map_sweep_tag, dim3(NT), dim3(ASL_WAVE), 0, st, a, cam);
-    }
-    hipLaunchKernelGGL(k_map_gauge, dim3(1), wg, 0, st, a, NC, NT, WT);
-    hipLaunchKernelGGL(k_map_flip, dim3(NT), dim3(ASL_WAVE), 0, st, a, cam, WT);
-    hipLaunchKernelGGL(k_map_behind, dim3((NC + 63) / 64), dim3(64), 0, st, a, NC, cam.half);
-    hipLaunchKernelGGL(k_map_csr, dim3(1), wg, 0, st, a, NC, NT);
-    hipLaunchKernelGGL(k_map_lm_init, dim3(1), dim3(1), 0, st, (const MapHead *)a.head, lm, lm0);
-    HIPCHK(hipMemsetAsync(b.flag, 0, 8, st));
-    range_pop();
-
-    range_push("map: LM");
-    auto lin = [&](const double *W, const double *G, double *D, int force) {
-        hipLaunchKernelGGL(k_map_linearize, dim3((NM + 3) / 4), dim3(256), 0, st, a, W, G, NM, cam, D, b.cost_obs, lm, force);
-    };
-    auto decide = [&]() { hipLaunchKernelGGL(k_map_decide, dim3(1), dim3(1), 0, st, lm, b.flag); };
-    auto park = [&]() {
-        hipLaunchKernelGGL(k_map_park, dim3((NC + NT + 2 + 255) / 256), dim3(256), 0, st, lm, sys.cam_ptr, NC, sys.tag_ptr, NT);
-    };
-    HIPCHK(hipMemcpyAsync(sys.cam_ptr, a.cam_ptr, 4 * (nc + 1), hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(sys.tag_ptr, a.tag_ptr, 4 * (nt + 1), hipMemcpyDeviceToDevice, st));
-    int rc = gn_lm_run(sys, b, a.W, a.G, NM, max_iters, seed_obs, lin, decide, park, st);
-    if (rc) return rc;
-    // the final state's per-observation costs (and its blocks again, for the std)
-    lin(a.W, a.G, sys.D, 1);
-    range_pop();
-    if (d_std) {
-        GnSystem full = sys;  // undamped, over every active observation
-        full.cam_ptr = a.cam_ptr;
-        full.tag_ptr = a.tag_ptr;
-        rc = gn_factor_step(full, lm0, b.flag + 1, st);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_map_std, dim3(n), dim3(256), (size_t)n * sizeof(double), st, sys.S, sys.Linv, n, var);
-    }
-    hipLaunchKernelGGL(k_map_finish, dim3(1), wg, 0, st, a, NC, NT, NM, WT, 0, lm, b.cost_obs, seed_obs, d_std ? var : nullptr, b.flag + 1,
-                       (MapTagRec *)d_map, (double *)d_std, (CamPoseRec *)d_poses, (MapResultRec *)d_result);
-    HIPCHK(hipGetLastError());
-    return ASL_OK;
-}
-
-extern "C" int asl_map_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, int n_ids, const double *K, const double *dist,
-                                     int n_dist, double tag_size, int world_id, int max_iters, void *d_map, void *d_tag_std, void *d_poses,
-                                     void *d_result, void *stream)
-{
-    if (!d) return fail(ASL_EINVAL, "NULL detector");
-    int rc = check_map_args(d_obs, n_frames, max_tags, n_ids, K, dist, n_dist, tag_size, world_id, max_iters, d_map, d_poses, d_result);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(d->device));
-    return launch_map(d, d_obs, n_frames, max_tags, n_ids, K, dist, n_dist, tag_size, world_id, max_iters, d_map, d_tag_std, d_poses, d_result,
-                      (hipStream_t)stream);
-}
-
-extern "C" int asl_map_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, int n_ids, const double *K, const double *dist,
-                             int n_dist, double tag_size, int world_id, int max_iters, asl_map_tag *map, double *tag_std, asl_cam_pose *poses,
-                             asl_map_result *result)
-{
-    if (!d) return fail(ASL_EINVAL, "NULL detector");
-    int rc = check_map_args(obs, n_frames, max_tags, n_ids, K, dist, n_dist, tag_size, world_id, max_iters, map, poses, result);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(d->device));
-    asl_map_result *d_result;
-    asl_map_tag *d_map;
-    double *d_std;
-    asl_cam_pose *d_poses;
-    if (carve_ws(d->solve_out, [&](WsCarve &c) {
-            d_result = c.take<asl_map_result>(1); d_map = c.take<asl_map_tag>(n_ids); d_std = c.take<double>(6 * (size_t)n_ids);
-            d_poses = c.take<asl_cam_pose>(n_frames);
-        }))
-        return fail(ASL_ENOMEM, "map workspace allocation failed");
-    if ((rc = upload_obs(d, "map", obs, n_frames, max_tags, nullptr, n_ids))) return rc;
-    rc = launch_map(d, d->loc_obs.p, n_frames, max_tags, n_ids, K, dist, n_dist, tag_size, world_id, max_iters, d_map, tag_std ? d_std : nullptr,
-                    d_poses, d_result, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(result, d_result, sizeof(asl_map_result), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(map, d_map, sizeof(asl_map_tag) * (size_t)n_ids, hipMemcpyDeviceToHost));
-    if (tag_std) HIPCHK(hipMemcpy(tag_std, d_std, sizeof(double) * 6 * (size_t)n_ids, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(poses, d_poses, sizeof(asl_cam_pose) * (size_t)n_frames, hipMemcpyDeviceToHost));
-    return ASL_OK;
-}
-
-// ---- sequence localisation with a motion prior (k_smooth.inc)
-
-#define SMOOTH_SEQ_FRAMES 65535   // frames of one sequence
-#define SMOOTH_SEQS 65535         // sequences of one call
-#define SMOOTH_FRAMES 1048576     // frames of one call: the work buffers, about 3.6 KB a frame, stay under 4 GB
-
-// Every refusal of the entry points, before anything is written or enqueued.  seq_start (host, n_seq + 1 offsets): the
-// sequences of an asl_smooth_sequences_* call; NULL with n_seq 1: the one sequence {0, n_frames} of the other calls
-static int check_smooth_args(const asl_detector *d, const void *obs, int n_frames, int max_tags, const void *map, int n_ids, const double *K,
-                             const double *dist, int n_dist, double tag_size, double sigma_px, double sigma_rot, double sigma_trans,
-                             int max_iters, const void *out, const void *result, const int32_t *seq_start, int n_seq, bool sequences)
-{
-    if (!d) return fail(ASL_EINVAL, "NULL detector");
-    if (!obs || !map || !K || !out || !result || (sequences && !seq_start)) return fail(ASL_EINVAL, "NULL argument");
-    if (!sequences) {
-        if (n_frames < 1 || n_frames > SMOOTH_SEQ_FRAMES) return fail(ASL_EINVAL, "n_frames must be in [1, %d] (got %d)", SMOOTH_SEQ_FRAMES, n_frames);
-    } else {
-        if (n_frames < 1 || n_frames > SMOOTH_FRAMES) return fail(ASL_EINVAL, "n_frames must be in [1, %d] (got %d)", SMOOTH_FRAMES, n_frames);
-        if (n_seq < 1 || n_seq > SMOOTH_SEQS) return fail(ASL_EINVAL, "n_seq must be in [1, %d] (got %d)", SMOOTH_SEQS, n_seq);
-        if (seq_start[0] != 0 || seq_start[n_seq] != n_frames)
-            return fail(ASL_EINVAL, "seq_start must run from 0 to n_frames (got %d to %d, n_frames %d)", seq_start[0], seq_start[n_seq], n_frames);
-        for (int k = 0; k < n_seq; k++) {
-            const int64_t len = (int64_t)seq_start[k + 1] - seq_start[k];
-            if (len < 1 || len > SMOOTH_SEQ_FRAMES) return fail(ASL_EINVAL, "sequence %d must have 1 to %d frames (got %lld)", k, SMOOTH_SEQ_FRAMES, (long long)len);
-        }
-    }
-    if (int rc = check_obs_args(max_tags, n_ids, n_dist, !dist, tag_size)) return rc;
-    for (int k = 0; k < 9; k++)
-        if (!std::isfinite(K[k])) return fail(ASL_EINVAL, "K is not finite");
-    const double sig[3] = {sigma_px, sigma_rot, sigma_trans};
-    for (double s : sig)
-        if (!(s > 0) || !std::isfinite(s)) return fail(ASL_EINVAL, "sigma_px, sigma_rot and sigma_trans must be positive and finite (got %g)", s);
-    if (max_iters < 1 || max_iters > 100) return fail(ASL_EINVAL, "max_iters must be in [1, 100] (got %d)", max_iters);
-    return ASL_OK;
-}
-
-// All device pointers but seq_start (host, n_seq + 1; not read for n_seq 1: the one sequence {0, n_frames}); everything is
-// enqueued on st, nothing waits.  d_cov: NULL, or the frames' asl_pose_cov (two more launches).  n_seq > 1: k_smooth_seqs
-// first, a launch per SM_SEQ_CHUNK sequences, which carries the offsets to the device in its arguments.
-static int launch_smooth(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids, const double *K,
-                         const double *dist, int n_dist, double tag_size, const void *d_seed, const int32_t *seq_start, int n_seq,
-                         double sigma_px, double sigma_rot, double sigma_trans, int max_iters, void *d_out, void *d_result, void *d_cov,
-                         hipStream_t st)
-{
-    static_assert(sizeof(SmoothResultRec) == sizeof(asl_smooth_result) && sizeof(asl_smooth_result) == 64, "asl_smooth_result layout");
-    static_assert(sizeof(PoseCovRec) == sizeof(asl_pose_cov) && sizeof(asl_pose_cov) == 304, "asl_pose_cov layout");
-    const size_t n = (size_t)n_frames;
-    SmoothBufs b{};
-    b.n = n_frames;
-    b.n_seq = n_seq;
-    const size_t ns = (size_t)n_seq;
-    if (carve_ws(d->smooth_ws, [&](WsCarve &c) {
-            b.cand = c.take<double>(24 * n); b.dcost = c.take<double>(2 * n); b.tcost = c.take<double>(4 * n);
-            b.posed = c.take<int>(n); b.ntags = c.take<int>(n); b.src = c.take<int>(n); b.back = c.take<int>(n); b.choice = c.take<int>(n);
-            b.code = c.take<int>(n); b.head = c.take<int>(SMH__N * ns); b.lm = c.take<double>(SM__N * ns); b.cseed = c.take<double>(n);
-            b.delta = c.take<double>(6 * n); b.fac = c.take<double>(SM_FAC * n);
-            b.set[0] = c.take<double>(SM_SET * n); b.set[1] = c.take<double>(SM_SET * n);
-            if (n_seq > 1) { b.seq = c.take<int>(ns + 1); b.fseq = c.take<int>(n); }
-        }))
-        return fail(ASL_ENOMEM, "sequence localisation workspace allocation failed");
-    const CamDev cam = make_cam(d, K, dist, n_dist, tag_size);
-    const ObsRec *obs = (const ObsRec *)d_obs;
-    const MapTagRec *map = (const MapTagRec *)d_map;
-    const CamPoseRec *seed = (const CamPoseRec *)d_seed;
-    const double w = 1.0 / (sigma_px * sigma_px), isr = 1.0 / sigma_rot, ist = 1.0 / sigma_trans;
-    const size_t lds = loc_lds_bytes(max_tags);
-    const dim3 frames((unsigned int)n_frames), wave(ASL_WAVE), seqs((unsigned int)n_seq), wg(SM_WG), per_thread((unsigned int)((n + SM_WG - 1) / SM_WG));
-
-    static_assert(SM_SET <= SM_WG, "k_smooth_commit: a thread an entry of a frame");
-    const dim3 commit_blocks((unsigned int)std::min<size_t>(n, 1024));
-
-    range_push("smooth: seed chain");
-    for (int k0 = 0; n_seq > 1 && k0 < n_seq; k0 += SM_SEQ_CHUNK) {
-        SmoothSeqChunk c;
-        c.k0 = k0;
-        c.count = std::min(n_seq - k0, SM_SEQ_CHUNK);
-        memcpy(c.start, seq_start + k0, sizeof(int32_t) * ((size_t)c.count + 1));
-        hipLaunchKernelGGL(k_smooth_seqs, dim3((unsigned int)c.count), wg, 0, st, b, c);
-    }
-    hipLaunchKernelGGL(k_smooth_cand, frames, wave, lds, st, obs, max_tags, map, n_ids, cam, seed, w, b);
-    hipLaunchKernelGGL(k_smooth_scan, seqs, wave, 0, st, b);
-    hipLaunchKernelGGL(k_smooth_trans, dim3((unsigned int)((n + ASL_WAVE - 1) / ASL_WAVE)), wave, 0, st, b, isr, ist);
-    hipLaunchKernelGGL(k_smooth_dp, seqs, wave, 0, st, b);
-    hipLaunchKernelGGL(k_smooth_fill, per_thread, wg, 0, st, b, seed);
-    hipLaunchKernelGGL(k_smooth_lin, frames, wave, lds, st, obs, max_tags, map, n_ids, cam, b, 0, isr, ist);
-    hipLaunchKernelGGL(k_smooth_init, seqs, wg, 0, st, b, w);
-    range_pop();
-    range_push("smooth: LM");
-    for (int it = 0; it < max_iters; it++) {
-        hipLaunchKernelGGL(k_smooth_solve, seqs, wave, 0, st, b, w);
-        hipLaunchKernelGGL(k_smooth_lin, frames, wave, lds, st, obs, max_tags, map, n_ids, cam, b, 1, isr, ist);
-        hipLaunchKernelGGL(k_smooth_decide, seqs, wg, 0, st, b, w);
-        hipLaunchKernelGGL(k_smooth_commit, commit_blocks, wg, 0, st, b);
-    }
-    hipLaunchKernelGGL(k_smooth_finish, per_thread, wg, 0, st, b, (CamPoseRec *)d_out, (SmoothResultRec *)d_result);
-    range_pop();
-    if (d_cov) {
-        range_push("smooth: covariance");
-        hipLaunchKernelGGL(k_smooth_cov, seqs, wave, 0, st, b, w, (PoseCovRec *)d_cov);
-        hipLaunchKernelGGL(k_smooth_cov_finish, per_thread, wg, 0, st, b, sigma_px, (PoseCovRec *)d_cov);
-        range_pop();
-    }
-    HIPCHK(hipGetLastError());
-    return ASL_OK;
-}
-
-static bool smooth_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
-// The device forms.  with_cov false: the plain call, d_cov not looked at.  sequences: asl_smooth_sequences_device (else
-// seq_start NULL, n_seq 1)
-static int smooth_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids, const double *K,
-                                const double *dist, int n_dist, double tag_size, const void *d_seed, const int32_t *seq_start, int n_seq,
-                                bool sequences, double sigma_px, double sigma_rot, double sigma_trans, int max_iters, void *d_out,
-                                void *d_result, void *d_cov, bool with_cov, void *stream)
-{
-    if (int rc = check_smooth_args(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, sigma_px, sigma_rot, sigma_trans,
-                                   max_iters, d_out, d_result, seq_start, n_seq, sequences))
-        return rc;
-    if (!d_seed || (with_cov && !d_cov)) return fail(ASL_EINVAL, "NULL argument");
-    const size_t poses = sizeof(asl_cam_pose) * (size_t)n_frames, covs = sizeof(asl_pose_cov) * (size_t)n_frames;
-    if (smooth_overlap(d_seed, poses, d_out, poses)) return fail(ASL_EINVAL, "d_out overlaps d_seed");
-    if (with_cov && (smooth_overlap(d_cov, covs, d_out, poses) || smooth_overlap(d_cov, covs, d_seed, poses)))
-        return fail(ASL_EINVAL, "d_cov overlaps d_out or d_seed");
-    HIPCHK(hipSetDevice(d->device));
-    return launch_smooth(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, d_seed, seq_start, n_seq, sigma_px, sigma_rot,
-                         sigma_trans, max_iters, d_out, d_result, with_cov ? d_cov : nullptr, (hipStream_t)stream);
-}
-
-extern "C" int asl_smooth_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
-                                        const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed, double sigma_px,
-                                        double sigma_rot, double sigma_trans, int max_iters, void *d_out, void *d_result, void *stream)
-{
-    return smooth_frames_device(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, d_seed, nullptr, 1, false, sigma_px,
-                                sigma_rot, sigma_trans, max_iters, d_out, d_result, nullptr, false, stream);
-}
-
-extern "C" int asl_smooth_cov_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
-                                            const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed,
-                                            double sigma_px, double sigma_rot, double sigma_trans, int max_iters, void *d_out, void *d_result,
-                                            void *d_cov, void *stream)
-{
-    return smooth_frames_device(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, d_seed, nullptr, 1, false, sigma_px,
-                                sigma_rot, sigma_trans, max_iters, d_out, d_result, d_cov, true, stream);
-}
-
-extern "C" int asl_smooth_sequences_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
-                                           const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed,
-                                           const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
-                                           int max_iters, void *d_out, void *d_results, void *d_cov, void *stream)
-{
-    return smooth_frames_device(d, d_obs, n_frames, max_tags, d_map, n_ids, K, dist, n_dist, tag_size, d_seed, seq_start, n_seq, true, sigma_px,
-                                sigma_rot, sigma_trans, max_iters, d_out, d_results, d_cov, d_cov != nullptr, stream);
-}
-
-static int smooth_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids, const double *K,
-                        const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed, const int32_t *seq_start, int n_seq,
-                        bool sequences, double sigma_px, double sigma_rot, double sigma_trans, int max_iters, asl_cam_pose *out,
-                        asl_smooth_result *result, asl_pose_cov *cov, bool with_cov)
-{
-    if (int rc = check_smooth_args(d, obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, sigma_px, sigma_rot, sigma_trans,
-                                   max_iters, out, result, seq_start, n_seq, sequences))
-        return rc;
-    if (with_cov && !cov) return fail(ASL_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(d->device));
-    const size_t n = (size_t)n_frames;
-    asl_cam_pose *d_out = nullptr, *d_seed = nullptr;
-    asl_smooth_result *d_result = nullptr;
-    asl_pose_cov *d_cov = nullptr;
-    if (carve_ws(d->solve_out, [&](WsCarve &c) {
-            d_result = c.take<asl_smooth_result>((size_t)n_seq); d_out = c.take<asl_cam_pose>(n); d_seed = c.take<asl_cam_pose>(n);
-            if (with_cov) d_cov = c.take<asl_pose_cov>(n);
-        }))
-        return fail(ASL_ENOMEM, "sequence localisation workspace allocation failed");
-    if (int rc = upload_obs(d, "sequence localisation", obs, n_frames, max_tags, map, n_ids)) return rc;
-    if (seed)
-        HIPCHK(hipMemcpy(d_seed, seed, sizeof(asl_cam_pose) * n, hipMemcpyHostToDevice));
-    else  // the per-frame localisation of the same block, gate 0
-        launch_localize(d, {d->loc_obs.p, 0, n_frames, max_tags, d->loc_map.p, n_ids, K, dist, n_dist, nullptr, tag_size, 0.0, 0.0, d_seed, nullptr, false},
-                        nullptr);
-    if (int rc = launch_smooth(d, d->loc_obs.p, n_frames, max_tags, d->loc_map.p, n_ids, K, dist, n_dist, tag_size, d_seed, seq_start, n_seq, sigma_px,
-                               sigma_rot, sigma_trans, max_iters, d_out, d_result, d_cov, nullptr))
-        return rc;
-    HIPCHK(hipMemcpy(out, d_out, sizeof(asl_cam_pose) * n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(result, d_result, sizeof(asl_smooth_result) * (size_t)n_seq, hipMemcpyDeviceToHost));
-    if (with_cov) HIPCHK(hipMemcpy(cov, d_cov, sizeof(asl_pose_cov) * n, hipMemcpyDeviceToHost));
-    return ASL_OK;
-}
-
-extern "C" int asl_smooth_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
-                                const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed, double sigma_px,
-                                double sigma_rot, double sigma_trans, int max_iters, asl_cam_pose *out, asl_smooth_result *result)
-{
-    return smooth_batch(d, obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, seed, nullptr, 1, false, sigma_px, sigma_rot,
-                        sigma_trans, max_iters, out, result, nullptr, false);
-}
-
-extern "C" int asl_smooth_cov_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
-                                    const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed, double sigma_px,
-                                    double sigma_rot, double sigma_trans, int max_iters, asl_cam_pose *out, asl_smooth_result *result,
-                                    asl_pose_cov *cov)
-{
-    return smooth_batch(d, obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, seed, nullptr, 1, false, sigma_px, sigma_rot,
-                        sigma_trans, max_iters, out, result, cov, true);
-}
-
-extern "C" int asl_smooth_sequences_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
-                                          const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed,
-                                          const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
-                                          int max_iters, asl_cam_pose *out, asl_smooth_result *results, asl_pose_cov *cov)
-{
-    return smooth_batch(d, obs, n_frames, max_tags, map, n_ids, K, dist, n_dist, tag_size, seed, seq_start, n_seq, true, sigma_px, sigma_rot,
-                        sigma_trans, max_iters, out, results, cov, cov != nullptr);
-}
-
+#include "solve_host.inc"
 #include "debug_host.inc"

@@ -1,0 +1,749 @@
+// Host side of the device solvers on asl_obs blocks: localisation and rig localisation (kernels: k_localize.inc, k_rig.inc),
+// per-tag pose covariance (k_posecov.inc), calibration (k_calib.inc), mapping (k_map.inc) and sequence smoothing
+// (k_smooth.inc).  Every solver has one call record, filled by its extern "C" entry points in their argument order, one
+// check_*_call with every refusal, one launch_* on device pointers, one device form and one host form.  The host forms
+// share stage_host_call (the block and the map in, the results carved from d->solve_out) and fetch_out (the results back).
+
+static_assert(sizeof(MapTagRec) == sizeof(asl_map_tag) && sizeof(asl_map_tag) == 104, "asl_map_tag layout");
+static_assert(sizeof(CamPoseRec) == sizeof(asl_cam_pose) && sizeof(asl_cam_pose) == 160, "asl_cam_pose layout");
+static_assert(sizeof(PoseCovRec) == sizeof(asl_pose_cov) && sizeof(asl_pose_cov) == 304, "asl_pose_cov layout");
+static_assert(sizeof(RigCamRec) == sizeof(asl_rig_camera) && sizeof(asl_rig_camera) == 216, "asl_rig_camera layout");
+static_assert(sizeof(CalibResultRec) == sizeof(asl_calib_result) && sizeof(asl_calib_result) == 216, "asl_calib_result layout");
+static_assert(sizeof(MapResultRec) == sizeof(asl_map_result) && sizeof(asl_map_result) == 64, "asl_map_result layout");
+static_assert(sizeof(SmoothResultRec) == sizeof(asl_smooth_result) && sizeof(asl_smooth_result) == 64, "asl_smooth_result layout");
+
+// The camera model as the entry points take it (K and dist are host arrays).  K NULL is each solver's "NULL argument".
+struct Camera {
+    const double *K, *dist; int n_dist; double tag_size;
+};
+
+// solved: calibration, which takes the number of coefficients to solve for and no dist
+static int check_camera(const Camera &c, bool solved = false)
+{
+    if (int rc = check_n_dist(c.n_dist)) return rc;
+    if (c.n_dist && !c.dist && !solved) return fail(ASL_EINVAL, "dist is NULL with n_dist = %d", c.n_dist);
+    if (!(c.tag_size > 0) || !std::isfinite(c.tag_size)) return fail(ASL_EINVAL, "tag_size must be positive (got %g)", c.tag_size);
+    return ASL_OK;
+}
+
+static CamDev make_cam(const asl_detector *d, const Camera &c) { return make_cam(d, c.K, c.dist, c.n_dist, c.tag_size); }
+
+// The checks the solvers share on the obs block (max_tags slots per frame, ids below n_ids) and the camera
+static int check_obs_args(int max_tags, int n_ids, const Camera &cam, bool solved = false)
+{
+    if (max_tags < 1 || max_tags > 256) return fail(ASL_EINVAL, "max_tags must be in [1, 256] (got %d)", max_tags);
+    if (n_ids < 1) return fail(ASL_EINVAL, "n_ids must be >= 1 (got %d)", n_ids);
+    return check_camera(cam, solved);
+}
+
+static int check_sigma_px(double sigma_px)
+{
+    if (!(sigma_px >= 0) || !std::isfinite(sigma_px)) return fail(ASL_EINVAL, "sigma_px must be >= 0 and finite (got %g)", sigma_px);
+    return ASL_OK;
+}
+
+// The device forms: every refusal, then the launch on the caller's stream
+template <class Call, int (*check)(const asl_detector *, const Call &, bool), int (*launch)(asl_detector *, const Call &, hipStream_t)>
+static int frames_device(asl_detector *d, const Call &c, void *stream)
+{
+    if (int rc = check(d, c, true)) return rc;
+    HIPCHK(hipSetDevice(d->device));
+    return launch(d, c, (hipStream_t)stream);
+}
+
+// One piece of d->solve_out in a host (*_batch) form: a result the kernels write at dev and fetch_out copies to host.  No
+// bytes: an output the caller did not ask for, dev stays NULL.  host NULL: staged on the device only (smoothing's seed).
+struct OutPiece {
+    void *host; size_t bytes; void *dev;
+};
+
+// The host forms begin here: the pieces carved from solve_out, the host obs block (rows x max_tags) and the map, if given,
+// into the detector's device copies
+template <size_t N>
+static int stage_host_call(asl_detector *d, const char *what, OutPiece (&pieces)[N], const void *obs, int rows, int max_tags, const void *map, int n_ids)
+{
+    HIPCHK(hipSetDevice(d->device));
+    const size_t obs_bytes = sizeof(asl_obs) * (size_t)rows * (size_t)max_tags, map_bytes = sizeof(asl_map_tag) * (size_t)n_ids;
+    if (carve_ws(d->solve_out, [&](WsCarve &w) { for (OutPiece &p : pieces) p.dev = p.bytes ? w.take<uint8_t>(p.bytes) : nullptr; }) ||
+        d->loc_obs.ensure(obs_bytes) || (map && d->loc_map.ensure(map_bytes)))
+        return fail(ASL_ENOMEM, "%s workspace allocation failed", what);
+    HIPCHK(hipMemcpy(d->loc_obs.p, obs, obs_bytes, hipMemcpyHostToDevice));
+    if (map) HIPCHK(hipMemcpy(d->loc_map.p, map, map_bytes, hipMemcpyHostToDevice));
+    return ASL_OK;
+}
+
+// and end here: the results back
+template <size_t N>
+static int fetch_out(const OutPiece (&pieces)[N])
+{
+    for (const OutPiece &p : pieces)
+        if (p.host && p.bytes) HIPCHK(hipMemcpy(p.host, p.dev, p.bytes, hipMemcpyDeviceToHost));
+    return ASL_OK;
+}
+
+// ---- localisation of single frames, one camera or a rig (k_localize.inc, k_rig.inc)
+
+// one camera table, wherever it came from: the model and the mounting of every camera
+static int check_rig_table(const asl_rig_camera *rig, int n_cams)
+{
+    for (int c = 0; c < n_cams; c++) {
+        const asl_rig_camera &r = rig[c];
+        if (check_n_dist(r.n_dist)) return fail(ASL_EINVAL, "camera %d: n_dist must be 0, 4 or 5 (got %d)", c, r.n_dist);
+        for (int k = 0; k < 9; k++)
+            if (!std::isfinite(r.K[k])) return fail(ASL_EINVAL, "camera %d: K is not finite", c);
+        for (int k = 0; k < r.n_dist; k++)
+            if (!std::isfinite(r.dist[k])) return fail(ASL_EINVAL, "camera %d: dist is not finite", c);
+        for (int k = 0; k < 12; k++)
+            if (!std::isfinite(r.E[k])) return fail(ASL_EINVAL, "camera %d: E is not finite", c);
+        const double *E = r.E;
+        double dev = 0;
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++)
+                dev = std::max(dev, std::fabs(E[4 * i] * E[4 * j] + E[4 * i + 1] * E[4 * j + 1] + E[4 * i + 2] * E[4 * j + 2] - (i == j ? 1.0 : 0.0)));
+        const double det = E[0] * (E[5] * E[10] - E[6] * E[9]) - E[1] * (E[4] * E[10] - E[6] * E[8]) + E[2] * (E[4] * E[9] - E[5] * E[8]);
+        if (!(dev <= 1e-6) || !(det > 0))
+            return fail(ASL_EINVAL, "camera %d: the rotation part of E is not a rotation (|R R^T - I| = %g, det %g)", c, dev, det);
+    }
+    return ASL_OK;
+}
+
+// One localisation call, whichever of the eight entry points made it, in their argument order.  The single-camera forms
+// leave n_cams 0 and rig NULL; the rig forms give n_cams and the table and leave cam's K and dist NULL, n_dist 0.
+// The plain forms leave sigma_px 0 and cov NULL.  obs, map, rig, out and cov are all host or all device pointers.
+struct LocCall {
+    const void *obs; int n_cams, n_frames, max_tags;
+    const void *map; int n_ids;
+    const void *rig; Camera cam;
+    double gate, sigma_px;
+    void *out, *cov;
+    bool with_cov;      // a covariance form: cov must be there
+};
+
+static bool is_rig(const LocCall &c) { return c.n_cams || c.rig; }
+
+// Every refusal, before anything is written or enqueued.  A rig's table is checked last: where it is, or (device: the
+// pointers are the device's) in a copy read back, at most 16 x 216 bytes; it must be complete when the call is made.
+static int check_localize_call(const asl_detector *d, const LocCall &c, bool device)
+{
+    const bool rig = is_rig(c);
+    if (c.with_cov && !c.cov) return fail(ASL_EINVAL, "NULL argument");
+    if (!d) return fail(ASL_EINVAL, "NULL detector");
+    if (!c.obs || !c.map || !(rig ? c.rig : (const void *)c.cam.K) || !c.out) return fail(ASL_EINVAL, "NULL argument");
+    if (c.n_frames < 0) return fail(ASL_EINVAL, "n_frames < 0");
+    if (rig && (c.n_cams < 1 || c.n_cams > RIG_MAX_CAMS)) return fail(ASL_EINVAL, "n_cams must be in [1, %d] (got %d)", RIG_MAX_CAMS, c.n_cams);
+    if (int rc = check_obs_args(c.max_tags, c.n_ids, c.cam)) return rc;
+    if (rig && c.n_cams * c.max_tags > RIG_MAX_SLOTS)
+        return fail(ASL_EINVAL, "n_cams * max_tags must be <= %d (got %d x %d)", RIG_MAX_SLOTS, c.n_cams, c.max_tags);
+    if (!(c.gate >= 0) || !std::isfinite(c.gate)) return fail(ASL_EINVAL, "max_tag_rms_px must be >= 0 (got %g)", c.gate);
+    if (int rc = check_sigma_px(c.sigma_px)) return rc;
+    if (!rig) return ASL_OK;
+    asl_rig_camera tab[RIG_MAX_CAMS];
+    if (device) {
+        HIPCHK(hipSetDevice(d->device));
+        HIPCHK(hipMemcpy(tab, c.rig, sizeof(asl_rig_camera) * (size_t)c.n_cams, hipMemcpyDeviceToHost));
+    }
+    return check_rig_table(device ? tab : (const asl_rig_camera *)c.rig, c.n_cams);
+}
+
+// c's pointers are the device's; cov NULL: the plain kernel
+static int launch_localize(asl_detector *d, const LocCall &c, hipStream_t st)
+{
+    if (c.n_frames == 0) return ASL_OK;
+    static const double no_K[9] = {};
+    const bool rig = is_rig(c);
+    const CamDev cam = make_cam(d, rig ? no_K : c.cam.K, c.cam.dist, c.cam.n_dist, c.cam.tag_size);   // a rig: for its half alone
+    const dim3 grid((unsigned int)c.n_frames), block(ASL_WAVE);
+    const ObsRec *obs = (const ObsRec *)c.obs;
+    const MapTagRec *map = (const MapTagRec *)c.map;
+    const RigCamRec *tab = (const RigCamRec *)c.rig;
+    CamPoseRec *out = (CamPoseRec *)c.out;
+    PoseCovRec *cov = (PoseCovRec *)c.cov;
+    const size_t lds = rig ? rig_lds_bytes(c.n_cams, c.max_tags) : loc_lds_bytes(c.max_tags);
+    if (!rig && cov)
+        hipLaunchKernelGGL(k_localize<true>, grid, block, lds, st, obs, c.max_tags, map, c.n_ids, cam, c.gate, out, cov, c.sigma_px);
+    else if (!rig)
+        hipLaunchKernelGGL(k_localize<false>, grid, block, lds, st, obs, c.max_tags, map, c.n_ids, cam, c.gate, out, cov, c.sigma_px);
+    else if (cov)
+        hipLaunchKernelGGL(k_localize_rig<true>, grid, block, lds, st, obs, c.n_cams, c.max_tags, map, c.n_ids, tab, cam.half, c.gate, out, cov, c.sigma_px);
+    else
+        hipLaunchKernelGGL(k_localize_rig<false>, grid, block, lds, st, obs, c.n_cams, c.max_tags, map, c.n_ids, tab, cam.half, c.gate, out, cov, c.sigma_px);
+    HIPCHK(hipGetLastError());
+    return ASL_OK;
+}
+
+static constexpr auto localize_frames_device = frames_device<LocCall, check_localize_call, launch_localize>;   // the four device forms
+
+// the four host forms; a rig's table is staged in solve_out too
+static int localize_batch(asl_detector *d, const LocCall &c)
+{
+    if (int rc = check_localize_call(d, c, false)) return rc;
+    if (c.n_frames == 0) return ASL_OK;
+    const bool rig = is_rig(c);
+    const size_t n = (size_t)c.n_frames, rig_bytes = sizeof(asl_rig_camera) * (size_t)c.n_cams;
+    OutPiece o[] = {{c.out, sizeof(asl_cam_pose) * n}, {c.cov, c.cov ? sizeof(asl_pose_cov) * n : 0}, {nullptr, rig_bytes}};
+    if (int rc = stage_host_call(d, rig ? "rig localisation" : "localisation", o, c.obs, (rig ? c.n_cams : 1) * c.n_frames, c.max_tags, c.map, c.n_ids))
+        return rc;
+    if (rig) HIPCHK(hipMemcpy(o[2].dev, c.rig, rig_bytes, hipMemcpyHostToDevice));
+    LocCall dc = c;
+    dc.obs = d->loc_obs.p; dc.map = d->loc_map.p; dc.out = o[0].dev; dc.cov = o[1].dev; dc.rig = o[2].dev;
+    if (int rc = launch_localize(d, dc, nullptr)) return rc;
+    return fetch_out(o);
+}
+
+extern "C" int asl_localize_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                          const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
+                                          void *d_out, void *stream)
+{
+    return localize_frames_device(d, {d_obs, 0, n_frames, max_tags, d_map, n_ids, nullptr, {K, dist, n_dist, tag_size}, max_tag_rms_px, 0.0, d_out, nullptr, false}, stream);
+}
+
+extern "C" int asl_localize_cov_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                              const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
+                                              double sigma_px, void *d_out, void *d_cov, void *stream)
+{
+    return localize_frames_device(d, {d_obs, 0, n_frames, max_tags, d_map, n_ids, nullptr, {K, dist, n_dist, tag_size}, max_tag_rms_px, sigma_px, d_out, d_cov, true}, stream);
+}
+
+extern "C" int asl_localize_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                  const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px, asl_cam_pose *out)
+{
+    return localize_batch(d, {obs, 0, n_frames, max_tags, map, n_ids, nullptr, {K, dist, n_dist, tag_size}, max_tag_rms_px, 0.0, out, nullptr, false});
+}
+
+extern "C" int asl_localize_cov_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                      const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px, double sigma_px,
+                                      asl_cam_pose *out, asl_pose_cov *cov)
+{
+    return localize_batch(d, {obs, 0, n_frames, max_tags, map, n_ids, nullptr, {K, dist, n_dist, tag_size}, max_tag_rms_px, sigma_px, out, cov, true});
+}
+
+extern "C" int asl_localize_rig_frames_device(asl_detector *d, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map,
+                                              int n_ids, const void *d_rig, double tag_size, double max_tag_rms_px, void *d_out, void *stream)
+{
+    return localize_frames_device(d, {d_obs, n_cams, n_frames, max_tags, d_map, n_ids, d_rig, {nullptr, nullptr, 0, tag_size}, max_tag_rms_px, 0.0, d_out, nullptr, false}, stream);
+}
+
+extern "C" int asl_localize_rig_cov_frames_device(asl_detector *d, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map,
+                                                  int n_ids, const void *d_rig, double tag_size, double max_tag_rms_px, double sigma_px,
+                                                  void *d_out, void *d_cov, void *stream)
+{
+    return localize_frames_device(d, {d_obs, n_cams, n_frames, max_tags, d_map, n_ids, d_rig, {nullptr, nullptr, 0, tag_size}, max_tag_rms_px, sigma_px, d_out, d_cov, true}, stream);
+}
+
+extern "C" int asl_localize_rig_batch(asl_detector *d, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                      const asl_rig_camera *rig, double tag_size, double max_tag_rms_px, asl_cam_pose *out)
+{
+    return localize_batch(d, {obs, n_cams, n_frames, max_tags, map, n_ids, rig, {nullptr, nullptr, 0, tag_size}, max_tag_rms_px, 0.0, out, nullptr, false});
+}
+
+extern "C" int asl_localize_rig_cov_batch(asl_detector *d, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_map_tag *map,
+                                          int n_ids, const asl_rig_camera *rig, double tag_size, double max_tag_rms_px, double sigma_px,
+                                          asl_cam_pose *out, asl_pose_cov *cov)
+{
+    return localize_batch(d, {obs, n_cams, n_frames, max_tags, map, n_ids, rig, {nullptr, nullptr, 0, tag_size}, max_tag_rms_px, sigma_px, out, cov, true});
+}
+
+// ---- per-tag pose covariance (k_posecov.inc)
+
+// n asl_obs records with their poses -> n asl_pose_cov; obs and cov are both host or both device pointers
+struct PoseCovCall {
+    const void *obs; int n;
+    Camera cam; double sigma_px;
+    void *cov;
+};
+
+static int check_pose_cov_call(const asl_detector *d, const PoseCovCall &c, bool)
+{
+    if (!d) return fail(ASL_EINVAL, "NULL detector");
+    if (!c.obs || !c.cam.K || !c.cov) return fail(ASL_EINVAL, "NULL argument");
+    if (c.n < 0) return fail(ASL_EINVAL, "record count < 0");
+    if (int rc = check_camera(c.cam)) return rc;
+    return check_sigma_px(c.sigma_px);
+}
+
+static int launch_pose_cov(asl_detector *d, const PoseCovCall &c, hipStream_t st)
+{
+    if (c.n == 0) return ASL_OK;
+    hipLaunchKernelGGL(k_pnp_cov, dim3((unsigned int)((c.n + PNP_TAGS_PER_WAVE - 1) / PNP_TAGS_PER_WAVE)), dim3(ASL_WAVE), 0, st, (const ObsRec *)c.obs, c.n,
+                       make_cam(d, c.cam), c.sigma_px, (PoseCovRec *)c.cov);
+    HIPCHK(hipGetLastError());
+    return ASL_OK;
+}
+
+extern "C" int asl_pose_cov_device(asl_detector *d, const void *d_obs, int n_records, const double *K, const double *dist, int n_dist,
+                                   double tag_size, double sigma_px, void *d_cov, void *stream)
+{
+    return frames_device<PoseCovCall, check_pose_cov_call, launch_pose_cov>(d, {d_obs, n_records, {K, dist, n_dist, tag_size}, sigma_px, d_cov}, stream);
+}
+
+extern "C" int asl_solve_pnp_cov_batch(asl_detector *d, const float *corners, const double *T, const double *K, const double *dist, int n_dist,
+                                       double tag_size, double sigma_px, asl_pose_cov *cov, int N)
+{
+    // the records are made of corners and T: either missing is the missing obs
+    if (int rc = check_pose_cov_call(d, {T ? corners : nullptr, N, {K, dist, n_dist, tag_size}, sigma_px, cov}, false)) return rc;
+    if (N == 0) return ASL_OK;
+    std::vector<asl_obs> rec((size_t)N);
+    for (int i = 0; i < N; i++) {  // a pose with a non-finite entry (a failed PnP) is no pose: status 1
+        bool finite = true;
+        for (int k = 0; k < 12; k++) finite = finite && std::isfinite(T[16 * (size_t)i + k]);
+        rec[i].id = 0; rec[i].flags = finite ? 3 : 1;
+        memcpy(rec[i].corners, corners + 8 * (size_t)i, sizeof rec[i].corners);
+        memcpy(rec[i].T, T + 16 * (size_t)i, sizeof rec[i].T);
+    }
+    OutPiece o[] = {{cov, sizeof(asl_pose_cov) * (size_t)N}};
+    if (int rc = stage_host_call(d, "pose covariance", o, rec.data(), 1, N, nullptr, 0)) return rc;
+    if (int rc = launch_pose_cov(d, {d->loc_obs.p, N, {K, dist, n_dist, tag_size}, sigma_px, o[0].dev}, nullptr)) return rc;
+    return fetch_out(o);
+}
+
+// ---- calibration (k_calib.inc)
+
+// One calibration call, in the entry points' argument order; K_init may be NULL.  obs, map, result and poses are all host
+// (asl_calibrate_batch) or all device pointers (asl_calibrate_frames_device); no field is left empty by either.
+struct CalibCall {
+    const void *obs; int n_frames, max_tags;
+    const void *map; int n_ids;
+    double tag_size; int width, height;
+    const double *K_init; int n_dist, flags, max_iters;
+    void *result, *poses;
+};
+
+// every refusal, before anything is written or enqueued; the same for both forms
+static int check_calibrate_call(const asl_detector *d, const CalibCall &c, bool)
+{
+    if (!d) return fail(ASL_EINVAL, "NULL detector");
+    if (!c.obs || !c.map || !c.result || !c.poses) return fail(ASL_EINVAL, "NULL argument");
+    if (c.n_frames < 1) return fail(ASL_EINVAL, "n_frames must be >= 1 (got %d)", c.n_frames);
+    if (int rc = check_obs_args(c.max_tags, c.n_ids, {nullptr, nullptr, c.n_dist, c.tag_size}, true)) return rc;
+    if (c.width < 1 || c.height < 1) return fail(ASL_EINVAL, "width and height must be positive (got %d x %d)", c.width, c.height);
+    if (c.max_iters < 1) return fail(ASL_EINVAL, "max_iters must be >= 1 (got %d)", c.max_iters);
+    if (c.flags & ~(ASL_CALIB_FIX_PRINCIPAL_POINT | ASL_CALIB_FIX_ASPECT_RATIO | ASL_CALIB_ZERO_TANGENT_DIST))
+        return fail(ASL_EINVAL, "unknown calibration flags 0x%x", c.flags);
+    if (const double *K = c.K_init; K && !(K[0] > 0 && K[4] > 0 && std::isfinite(K[0]) && std::isfinite(K[4]) && std::isfinite(K[2]) && std::isfinite(K[5])))
+        return fail(ASL_EINVAL, "K_init must have finite, positive focal lengths");
+    return ASL_OK;
+}
+
+// c's pointers are the device's.  The calibration workspace: state, frame lists and per-frame buffers, carved from d->cal_ws
+static int launch_calibrate(asl_detector *d, const CalibCall &c, hipStream_t st)
+{
+    const size_t nf = (size_t)c.n_frames;
+    CalibArgs a{};
+    if (carve_ws(d->cal_ws, [&](WsCarve &w) {
+            a.st = w.take<CalibState>(1); a.list = w.take<int>(nf); a.fr = w.take<int>(CAL_FR * nf);
+            a.zh = w.take<double>(CAL_ZH * nf); a.seedc = w.take<double>(nf); a.pose = w.take<double>(2 * 12 * nf);
+            a.H = w.take<double>(2 * CAL_HS * nf); a.SB = w.take<double>(CAL_SB * nf); a.back = w.take<double>(CAL_BK * nf);
+        }))
+        return fail(ASL_ENOMEM, "calibration workspace allocation failed");
+    a.obs = (const ObsRec *)c.obs; a.map = (const MapTagRec *)c.map;
+    a.res = (CalibResultRec *)c.result; a.out = (CamPoseRec *)c.poses;
+    a.half = (double)(float)(c.tag_size / 2);  // object corners are float32, as in the PnP
+    a.width = c.width; a.height = c.height;
+    a.has_init = c.K_init != nullptr;
+    if (c.K_init) { a.Kinit[0] = c.K_init[0]; a.Kinit[1] = c.K_init[4]; a.Kinit[2] = c.K_init[2]; a.Kinit[3] = c.K_init[5]; }
+    a.n_frames = c.n_frames; a.max_tags = c.max_tags; a.n_ids = c.n_ids; a.n_dist = c.n_dist; a.flags = c.flags; a.max_iters = c.max_iters;
+    int np = 0;  // the free entries of (fx, fy, cx, cy, k1, k2, p1, p2, k3)
+    if (!(c.flags & ASL_CALIB_FIX_ASPECT_RATIO)) a.sel[np++] = 0;
+    a.sel[np++] = 1;
+    if (!(c.flags & ASL_CALIB_FIX_PRINCIPAL_POINT)) { a.sel[np++] = 2; a.sel[np++] = 3; }
+    if (c.n_dist >= 4) {
+        a.sel[np++] = 4; a.sel[np++] = 5;
+        if (!(c.flags & ASL_CALIB_ZERO_TANGENT_DIST)) { a.sel[np++] = 6; a.sel[np++] = 7; }
+    }
+    if (c.n_dist == 5) a.sel[np++] = 8;
+    a.np = np;
+    const dim3 frames((unsigned int)c.n_frames), wave(ASL_WAVE), wg(CAL_WG);
+    const size_t lds = loc_lds_bytes(c.max_tags);
+    auto seed = c.n_dist == 5 ? k_calib_seed<5> : c.n_dist == 4 ? k_calib_seed<4> : k_calib_seed<0>;
+    auto step = c.n_dist == 5 ? k_calib_step<5> : c.n_dist == 4 ? k_calib_step<4> : k_calib_step<0>;
+    hipLaunchKernelGGL(k_calib_init, frames, wave, 0, st, a);
+    hipLaunchKernelGGL(k_calib_k0, dim3(1), wg, 0, st, a);
+    hipLaunchKernelGGL(seed, frames, wave, lds, st, a);
+    hipLaunchKernelGGL(k_calib_start, dim3(1), wg, 0, st, a);
+    for (int it = 0; it < c.max_iters; it++) {
+        hipLaunchKernelGGL(k_calib_schur, frames, wave, 0, st, a, 0);
+        hipLaunchKernelGGL(k_calib_solve, dim3(1), wg, 0, st, a);
+        hipLaunchKernelGGL(step, frames, wave, lds, st, a);
+        hipLaunchKernelGGL(k_calib_decide, dim3(1), wg, 0, st, a);
+    }
+    hipLaunchKernelGGL(k_calib_schur, frames, wave, 0, st, a, 1);
+    hipLaunchKernelGGL(k_calib_finish, dim3(1), wg, 0, st, a);
+    HIPCHK(hipGetLastError());
+    return ASL_OK;
+}
+
+static constexpr auto calibrate_frames_device = frames_device<CalibCall, check_calibrate_call, launch_calibrate>;
+
+static int calibrate_batch(asl_detector *d, const CalibCall &c)
+{
+    if (int rc = check_calibrate_call(d, c, false)) return rc;
+    OutPiece o[] = {{c.result, sizeof(asl_calib_result)}, {c.poses, sizeof(asl_cam_pose) * (size_t)c.n_frames}};
+    if (int rc = stage_host_call(d, "calibration", o, c.obs, c.n_frames, c.max_tags, c.map, c.n_ids)) return rc;
+    CalibCall dc = c;
+    dc.obs = d->loc_obs.p; dc.map = d->loc_map.p; dc.result = o[0].dev; dc.poses = o[1].dev;
+    if (int rc = launch_calibrate(d, dc, nullptr)) return rc;
+    return fetch_out(o);
+}
+
+extern "C" int asl_calibrate_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                           double tag_size, int width, int height, const double *K_init, int n_dist, int flags, int max_iters,
+                                           void *d_result, void *d_poses, void *stream)
+{
+    return calibrate_frames_device(d, {d_obs, n_frames, max_tags, d_map, n_ids, tag_size, width, height, K_init, n_dist, flags, max_iters, d_result, d_poses}, stream);
+}
+
+extern "C" int asl_calibrate_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                   double tag_size, int width, int height, const double *K_init, int n_dist, int flags, int max_iters,
+                                   asl_calib_result *result, asl_cam_pose *poses)
+{
+    return calibrate_batch(d, {obs, n_frames, max_tags, map, n_ids, tag_size, width, height, K_init, n_dist, flags, max_iters, result, poses});
+}
+
+// ---- mapping (k_map.inc)
+
+// One map call, in the entry points' argument order.  tag_std may be NULL: no std asked for.  obs, map, tag_std, poses and
+// result are all host (asl_map_batch) or all device pointers (asl_map_frames_device); no field is left empty by either.
+struct MapCall {
+    const void *obs; int n_frames, max_tags, n_ids;
+    Camera cam;
+    int world_id, max_iters;
+    void *map, *tag_std, *poses, *result;
+};
+
+// every refusal that needs no look at the block, before anything is written or enqueued; the same for both forms
+static int check_map_call(const asl_detector *d, const MapCall &c, bool)
+{
+    if (!d) return fail(ASL_EINVAL, "NULL detector");
+    if (!c.obs || !c.cam.K || !c.map || !c.poses || !c.result) return fail(ASL_EINVAL, "NULL argument");
+    if (c.n_frames < 1) return fail(ASL_EINVAL, "n_frames must be >= 1 (got %d)", c.n_frames);
+    if (int rc = check_obs_args(c.max_tags, c.n_ids, c.cam)) return rc;
+    if (c.world_id < -1 || c.world_id >= c.n_ids) return fail(ASL_EINVAL, "world_id must be -1 or in [0, n_ids) (got %d)", c.world_id);
+    if (c.max_iters < 1 || c.max_iters > MAP_MAX_ITERS) return fail(ASL_EINVAL, "max_iters must be in [1, %d] (got %d)", MAP_MAX_ITERS, c.max_iters);
+    return ASL_OK;
+}
+
+// c's pointers are the device's
+static int launch_map(asl_detector *d, const MapCall &c, hipStream_t st)
+{
+    const size_t nf = (size_t)c.n_frames, ni = (size_t)c.n_ids, nsl = nf * (size_t)c.max_tags;
+    MapArgs a{};
+    int *per_id, *per_frame, *per_cam, *per_obs, *csr;  // the grouped int arrays, one piece per group
+    if (carve_ws(d->map_ws, [&](WsCarve &w) {
+            a.head = w.take<MapHead>(1); per_id = w.take<int>(4 * (ni + 1)); per_frame = w.take<int>(3 * (nf + 1));
+            per_cam = w.take<int>(4 * (nf + 1)); a.tag_state = w.take<int>(ni + 1); a.slot_obs = w.take<int>(nsl); per_obs = w.take<int>(4 * nsl);
+            csr = w.take<int>(2 * nsl + nf + ni + 2); a.W = w.take<double>(12 * nf); a.G = w.take<double>(12 * ni);
+        }))
+        return fail(ASL_ENOMEM, "map workspace allocation failed");
+    a.obs = (const ObsRec *)c.obs; a.n_frames = c.n_frames; a.max_tags = c.max_tags; a.n_ids = c.n_ids; a.world_req = c.world_id;
+    a.seen = per_id; a.id_tag = per_id + (ni + 1); a.tag_id = per_id + 2 * (ni + 1); a.tmp = per_id + 3 * (ni + 1);
+    a.fr_npart = per_frame; a.fr_cam = per_frame + (nf + 1); a.fr_obs0 = per_frame + 2 * (nf + 1);
+    a.cam_frame = per_cam; a.cam_ptr0 = per_cam + (nf + 1); a.cam_state = per_cam + 2 * (nf + 1); a.cam_seed = per_cam + 3 * (nf + 1);
+    a.obs_slot = per_obs; a.obs_cam = per_obs + nsl; a.obs_tag = per_obs + 2 * nsl; a.obs_act = per_obs + 3 * nsl;
+    a.cam_obs = csr; a.tag_obs = csr + nsl; a.cam_ptr = csr + 2 * nsl; a.tag_ptr = csr + 2 * nsl + nf + 1;
+    const CamDev cam = make_cam(d, c.cam);
+
+    hipLaunchKernelGGL(k_map_gather, dim3(1), dim3(MAP_WG), 0, st, a);
+    MapHead h;
+    HIPCHK(hipMemcpyAsync(&h, a.head, sizeof h, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));  // the one wait before the end: the reduced system is sized by the tags seen
+    const int NC = h.n_cams, NT = h.n_tags, NM = h.n_obs, WT = h.world_tag;
+    auto finish_nothing = [&]() {
+        hipLaunchKernelGGL(k_map_finish, dim3(1), dim3(MAP_WG), 0, st, a, NC, NT, NM, WT, 1, (const double *)nullptr, (const double *)nullptr,
+                           (const double *)nullptr, (const double *)nullptr, (const int *)nullptr, (MapTagRec *)c.map, (double *)c.tag_std, (CamPoseRec *)c.poses,
+                           (MapResultRec *)c.result);
+        HIPCHK(hipGetLastError());
+        return ASL_OK;
+    };
+    if (NT > MAP_MAX_TAGS) return fail(ASL_EINVAL, "the frames see %d tags; the map's dense reduced system takes at most %d", NT, MAP_MAX_TAGS);
+    if (WT < 0) {
+        int rc = finish_nothing();
+        if (rc) return rc;
+        if (c.world_id >= 0) return fail(ASL_EINVAL, "world tag %d is not seen by any frame with 2 or more taking-part slots", c.world_id);
+        return ASL_OK;
+    }
+
+    // the problem-sized part: the LM's buffers (gn_lm_carve), the seed costs, the std; the reduced system reads the LM's
+    // copies of the list offsets (k_map_park empties them after the stop)
+    const int n = 6 * NT;
+    const size_t nc = (size_t)NC, nt = (size_t)NT, nm = (size_t)NM;
+    GnSystem sys = {nullptr, nullptr, a.cam_obs, nullptr, a.tag_obs, a.obs_cam, a.obs_tag, nullptr, NC, NT, WT};
+    GnLmBufs b;
+    double *seed_obs, *var;
+    if (carve_ws(d->map_lm, [&](WsCarve &w) {
+            b = gn_lm_carve(w, sys, NM, 2 * MAP_LM__N);
+            seed_obs = w.take<double>(nm); var = w.take<double>(n); sys.cam_ptr = w.take<int>(nc + 1); sys.tag_ptr = w.take<int>(nt + 1);
+        }))
+        return fail(ASL_ENOMEM, "map workspace allocation failed");
+    a.obs_of = sys.obs_of;
+    double *lm = b.lm, *lm0 = lm + MAP_LM__N;
+    const dim3 wg(MAP_WG);
+
+    range_push("map: seed");
+    HIPCHK(hipMemsetAsync(a.obs_of, 0xff, 4 * nc * nt, st));
+    hipLaunchKernelGGL(k_map_table, dim3((NM + 255) / 256), dim3(256), 0, st, a, NM, NT);
+    hipLaunchKernelGGL(k_map_csr, dim3(1), wg, 0, st, a, NC, NT);
+    hipLaunchKernelGGL(k_map_chain, dim3(1), wg, 0, st, a, NC, NT, NM, WT);
+    hipLaunchKernelGGL(k_map_csr, dim3(1), wg, 0, st, a, NC, NT);
+    for (int sw = 0; sw < 2; sw++) {
+        hipLaunchKernelGGL(k_map_sweep_cam, dim3(NC), dim3(ASL_WAVE), loc_lds_bytes(c.max_tags), st, a, cam);
+        hipLaunchKernelGGL(k_map_sweep_tag, dim3(NT), dim3(ASL_WAVE), 0, st, a, cam);
+    }
+    hipLaunchKernelGGL(k_map_gauge, dim3(1), wg, 0, st, a, NC, NT, WT);
+    hipLaunchKernelGGL(k_map_flip, dim3(NT), dim3(ASL_WAVE), 0, st, a, cam, WT);
+    hipLaunchKernelGGL(k_map_behind, dim3((NC + 63) / 64), dim3(64), 0, st, a, NC, cam.half);
+    hipLaunchKernelGGL(k_map_csr, dim3(1), wg, 0, st, a, NC, NT);
+    hipLaunchKernelGGL(k_map_lm_init, dim3(1), dim3(1), 0, st, (const MapHead *)a.head, lm, lm0);
+    HIPCHK(hipMemsetAsync(b.flag, 0, 8, st));
+    range_pop();
+
+    range_push("map: LM");
+    auto lin = [&](const double *W, const double *G, double *D, int force) {
+        hipLaunchKernelGGL(k_map_linearize, dim3((NM + 3) / 4), dim3(256), 0, st, a, W, G, NM, cam, D, b.cost_obs, lm, force);
+    };
+    auto decide = [&]() { hipLaunchKernelGGL(k_map_decide, dim3(1), dim3(1), 0, st, lm, b.flag); };
+    auto park = [&]() {
+        hipLaunchKernelGGL(k_map_park, dim3((NC + NT + 2 + 255) / 256), dim3(256), 0, st, lm, sys.cam_ptr, NC, sys.tag_ptr, NT);
+    };
+    HIPCHK(hipMemcpyAsync(sys.cam_ptr, a.cam_ptr, 4 * (nc + 1), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(sys.tag_ptr, a.tag_ptr, 4 * (nt + 1), hipMemcpyDeviceToDevice, st));
+    int rc = gn_lm_run(sys, b, a.W, a.G, NM, c.max_iters, seed_obs, lin, decide, park, st);
+    if (rc) return rc;
+    // the final state's per-observation costs (and its blocks again, for the std)
+    lin(a.W, a.G, sys.D, 1);
+    range_pop();
+    if (c.tag_std) {
+        GnSystem full = sys;  // undamped, over every active observation
+        full.cam_ptr = a.cam_ptr;
+        full.tag_ptr = a.tag_ptr;
+        rc = gn_factor_step(full, lm0, b.flag + 1, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_map_std, dim3(n), dim3(256), (size_t)n * sizeof(double), st, sys.S, sys.Linv, n, var);
+    }
+    hipLaunchKernelGGL(k_map_finish, dim3(1), wg, 0, st, a, NC, NT, NM, WT, 0, lm, b.cost_obs, seed_obs, c.tag_std ? var : nullptr, b.flag + 1,
+                       (MapTagRec *)c.map, (double *)c.tag_std, (CamPoseRec *)c.poses, (MapResultRec *)c.result);
+    HIPCHK(hipGetLastError());
+    return ASL_OK;
+}
+
+static constexpr auto map_frames_device = frames_device<MapCall, check_map_call, launch_map>;
+
+static int map_batch(asl_detector *d, const MapCall &c)
+{
+    if (int rc = check_map_call(d, c, false)) return rc;
+    const size_t ni = (size_t)c.n_ids;
+    OutPiece o[] = {{c.result, sizeof(asl_map_result)}, {c.map, sizeof(asl_map_tag) * ni}, {c.tag_std, c.tag_std ? sizeof(double) * 6 * ni : 0},
+                    {c.poses, sizeof(asl_cam_pose) * (size_t)c.n_frames}};
+    if (int rc = stage_host_call(d, "map", o, c.obs, c.n_frames, c.max_tags, nullptr, c.n_ids)) return rc;
+    MapCall dc = c;
+    dc.obs = d->loc_obs.p; dc.result = o[0].dev; dc.map = o[1].dev; dc.tag_std = o[2].dev; dc.poses = o[3].dev;
+    if (int rc = launch_map(d, dc, nullptr)) return rc;
+    return fetch_out(o);
+}
+
+extern "C" int asl_map_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, int n_ids, const double *K, const double *dist,
+                                     int n_dist, double tag_size, int world_id, int max_iters, void *d_map, void *d_tag_std, void *d_poses,
+                                     void *d_result, void *stream)
+{
+    return map_frames_device(d, {d_obs, n_frames, max_tags, n_ids, {K, dist, n_dist, tag_size}, world_id, max_iters, d_map, d_tag_std, d_poses, d_result}, stream);
+}
+
+extern "C" int asl_map_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, int n_ids, const double *K, const double *dist,
+                             int n_dist, double tag_size, int world_id, int max_iters, asl_map_tag *map, double *tag_std, asl_cam_pose *poses,
+                             asl_map_result *result)
+{
+    return map_batch(d, {obs, n_frames, max_tags, n_ids, {K, dist, n_dist, tag_size}, world_id, max_iters, map, tag_std, poses, result});
+}
+
+// ---- sequence localisation with a motion prior (k_smooth.inc)
+
+#define SMOOTH_SEQ_FRAMES 65535   // frames of one sequence
+#define SMOOTH_SEQS 65535         // sequences of one call
+#define SMOOTH_FRAMES 1048576     // frames of one call: the work buffers, about 3.6 KB a frame, stay under 4 GB
+
+// One smoothing call, whichever of the six entry points made it, in their argument order.  The single-sequence forms leave
+// seq_start NULL, n_seq 1 and sequences false: the one sequence {0, n_frames}; seq_start is a host array of n_seq + 1
+// offsets in every form.  The plain forms leave cov NULL and with_cov false; the sequences forms set with_cov where cov is
+// given.  The host forms may leave seed NULL: the per-frame localisation of the same block.  obs, map, seed, out, result
+// and cov are all host or all device pointers.
+struct SmoothCall {
+    const void *obs; int n_frames, max_tags;
+    const void *map; int n_ids;
+    Camera cam;
+    const void *seed; const int32_t *seq_start; int n_seq;
+    double sigma_px, sigma_rot, sigma_trans; int max_iters;
+    void *out, *result, *cov;
+    bool with_cov, sequences;
+};
+
+static bool smooth_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// Every refusal, before anything is written or enqueued.  device: the seed must be there, and the outputs apart from it
+// and from each other (host arrays are apart by contract).
+static int check_smooth_call(const asl_detector *d, const SmoothCall &c, bool device)
+{
+    if (!d) return fail(ASL_EINVAL, "NULL detector");
+    if (!c.obs || !c.map || !c.cam.K || !c.out || !c.result || (c.sequences && !c.seq_start)) return fail(ASL_EINVAL, "NULL argument");
+    const int most = c.sequences ? SMOOTH_FRAMES : SMOOTH_SEQ_FRAMES;
+    if (c.n_frames < 1 || c.n_frames > most) return fail(ASL_EINVAL, "n_frames must be in [1, %d] (got %d)", most, c.n_frames);
+    if (c.sequences) {
+        if (c.n_seq < 1 || c.n_seq > SMOOTH_SEQS) return fail(ASL_EINVAL, "n_seq must be in [1, %d] (got %d)", SMOOTH_SEQS, c.n_seq);
+        if (c.seq_start[0] != 0 || c.seq_start[c.n_seq] != c.n_frames)
+            return fail(ASL_EINVAL, "seq_start must run from 0 to n_frames (got %d to %d, n_frames %d)", c.seq_start[0], c.seq_start[c.n_seq], c.n_frames);
+        for (int k = 0; k < c.n_seq; k++) {
+            const int64_t len = (int64_t)c.seq_start[k + 1] - c.seq_start[k];
+            if (len < 1 || len > SMOOTH_SEQ_FRAMES) return fail(ASL_EINVAL, "sequence %d must have 1 to %d frames (got %lld)", k, SMOOTH_SEQ_FRAMES, (long long)len);
+        }
+    }
+    if (int rc = check_obs_args(c.max_tags, c.n_ids, c.cam)) return rc;
+    for (int k = 0; k < 9; k++)
+        if (!std::isfinite(c.cam.K[k])) return fail(ASL_EINVAL, "K is not finite");
+    for (double s : {c.sigma_px, c.sigma_rot, c.sigma_trans})
+        if (!(s > 0) || !std::isfinite(s)) return fail(ASL_EINVAL, "sigma_px, sigma_rot and sigma_trans must be positive and finite (got %g)", s);
+    if (c.max_iters < 1 || c.max_iters > 100) return fail(ASL_EINVAL, "max_iters must be in [1, 100] (got %d)", c.max_iters);
+    if ((device && !c.seed) || (c.with_cov && !c.cov)) return fail(ASL_EINVAL, "NULL argument");
+    if (!device) return ASL_OK;
+    const size_t poses = sizeof(asl_cam_pose) * (size_t)c.n_frames, covs = sizeof(asl_pose_cov) * (size_t)c.n_frames;
+    if (smooth_overlap(c.seed, poses, c.out, poses)) return fail(ASL_EINVAL, "d_out overlaps d_seed");
+    if (c.with_cov && (smooth_overlap(c.cov, covs, c.out, poses) || smooth_overlap(c.cov, covs, c.seed, poses)))
+        return fail(ASL_EINVAL, "d_cov overlaps d_out or d_seed");
+    return ASL_OK;
+}
+
+// c's pointers are the device's but seq_start (host, not read for n_seq 1); everything is enqueued on st, nothing waits.
+// cov: NULL, or the frames' asl_pose_cov (two more launches).  n_seq > 1: k_smooth_seqs first, a launch per SM_SEQ_CHUNK
+// sequences, which carries the offsets to the device in its arguments.
+static int launch_smooth(asl_detector *d, const SmoothCall &c, hipStream_t st)
+{
+    const size_t n = (size_t)c.n_frames, ns = (size_t)c.n_seq;
+    SmoothBufs b{};
+    b.n = c.n_frames; b.n_seq = c.n_seq;
+    if (carve_ws(d->smooth_ws, [&](WsCarve &ws) {
+            b.cand = ws.take<double>(24 * n); b.dcost = ws.take<double>(2 * n); b.tcost = ws.take<double>(4 * n);
+            b.posed = ws.take<int>(n); b.ntags = ws.take<int>(n); b.src = ws.take<int>(n); b.back = ws.take<int>(n); b.choice = ws.take<int>(n);
+            b.code = ws.take<int>(n); b.head = ws.take<int>(SMH__N * ns); b.lm = ws.take<double>(SM__N * ns); b.cseed = ws.take<double>(n);
+            b.delta = ws.take<double>(6 * n); b.fac = ws.take<double>(SM_FAC * n);
+            b.set[0] = ws.take<double>(SM_SET * n); b.set[1] = ws.take<double>(SM_SET * n);
+            if (c.n_seq > 1) { b.seq = ws.take<int>(ns + 1); b.fseq = ws.take<int>(n); }
+        }))
+        return fail(ASL_ENOMEM, "sequence localisation workspace allocation failed");
+    const CamDev cam = make_cam(d, c.cam);
+    const ObsRec *obs = (const ObsRec *)c.obs;
+    const MapTagRec *map = (const MapTagRec *)c.map;
+    const CamPoseRec *seed = (const CamPoseRec *)c.seed;
+    const double w = 1.0 / (c.sigma_px * c.sigma_px), isr = 1.0 / c.sigma_rot, ist = 1.0 / c.sigma_trans;
+    const size_t lds = loc_lds_bytes(c.max_tags);
+    const dim3 frames((unsigned int)c.n_frames), wave(ASL_WAVE), seqs((unsigned int)c.n_seq), wg(SM_WG), per_thread((unsigned int)((n + SM_WG - 1) / SM_WG));
+
+    static_assert(SM_SET <= SM_WG, "k_smooth_commit: a thread an entry of a frame");
+    const dim3 commit_blocks((unsigned int)std::min<size_t>(n, 1024));
+
+    range_push("smooth: seed chain");
+    for (int k0 = 0; c.n_seq > 1 && k0 < c.n_seq; k0 += SM_SEQ_CHUNK) {
+        SmoothSeqChunk ch;
+        ch.k0 = k0;
+        ch.count = std::min(c.n_seq - k0, SM_SEQ_CHUNK);
+        memcpy(ch.start, c.seq_start + k0, sizeof(int32_t) * ((size_t)ch.count + 1));
+        hipLaunchKernelGGL(k_smooth_seqs, dim3((unsigned int)ch.count), wg, 0, st, b, ch);
+    }
+    hipLaunchKernelGGL(k_smooth_cand, frames, wave, lds, st, obs, c.max_tags, map, c.n_ids, cam, seed, w, b);
+    hipLaunchKernelGGL(k_smooth_scan, seqs, wave, 0, st, b);
+    hipLaunchKernelGGL(k_smooth_trans, dim3((unsigned int)((n + ASL_WAVE - 1) / ASL_WAVE)), wave, 0, st, b, isr, ist);
+    hipLaunchKernelGGL(k_smooth_dp, seqs, wave, 0, st, b);
+    hipLaunchKernelGGL(k_smooth_fill, per_thread, wg, 0, st, b, seed);
+    hipLaunchKernelGGL(k_smooth_lin, frames, wave, lds, st, obs, c.max_tags, map, c.n_ids, cam, b, 0, isr, ist);
+    hipLaunchKernelGGL(k_smooth_init, seqs, wg, 0, st, b, w);
+    range_pop();
+    range_push("smooth: LM");
+    for (int it = 0; it < c.max_iters; it++) {
+        hipLaunchKernelGGL(k_smooth_solve, seqs, wave, 0, st, b, w);
+        hipLaunchKernelGGL(k_smooth_lin, frames, wave, lds, st, obs, c.max_tags, map, c.n_ids, cam, b, 1, isr, ist);
+        hipLaunchKernelGGL(k_smooth_decide, seqs, wg, 0, st, b, w);
+        hipLaunchKernelGGL(k_smooth_commit, commit_blocks, wg, 0, st, b);
+    }
+    hipLaunchKernelGGL(k_smooth_finish, per_thread, wg, 0, st, b, (CamPoseRec *)c.out, (SmoothResultRec *)c.result);
+    range_pop();
+    if (c.cov) {
+        range_push("smooth: covariance");
+        hipLaunchKernelGGL(k_smooth_cov, seqs, wave, 0, st, b, w, (PoseCovRec *)c.cov);
+        hipLaunchKernelGGL(k_smooth_cov_finish, per_thread, wg, 0, st, b, c.sigma_px, (PoseCovRec *)c.cov);
+        range_pop();
+    }
+    HIPCHK(hipGetLastError());
+    return ASL_OK;
+}
+
+static constexpr auto smooth_frames_device = frames_device<SmoothCall, check_smooth_call, launch_smooth>;   // the three device forms
+
+// the three host forms; a seed not given is the per-frame localisation of the same block, gate 0
+static int smooth_batch(asl_detector *d, const SmoothCall &c)
+{
+    if (int rc = check_smooth_call(d, c, false)) return rc;
+    const size_t poses = sizeof(asl_cam_pose) * (size_t)c.n_frames;
+    OutPiece o[] = {{c.result, sizeof(asl_smooth_result) * (size_t)c.n_seq}, {c.out, poses}, {nullptr, poses},
+                    {c.cov, c.cov ? sizeof(asl_pose_cov) * (size_t)c.n_frames : 0}};
+    if (int rc = stage_host_call(d, "sequence localisation", o, c.obs, c.n_frames, c.max_tags, c.map, c.n_ids)) return rc;
+    SmoothCall dc = c;
+    dc.obs = d->loc_obs.p; dc.map = d->loc_map.p; dc.result = o[0].dev; dc.out = o[1].dev; dc.seed = o[2].dev; dc.cov = o[3].dev;
+    if (c.seed)
+        HIPCHK(hipMemcpy(o[2].dev, c.seed, poses, hipMemcpyHostToDevice));
+    else if (int rc = launch_localize(d, {dc.obs, 0, c.n_frames, c.max_tags, dc.map, c.n_ids, nullptr, c.cam, 0.0, 0.0, o[2].dev, nullptr, false}, nullptr))
+        return rc;
+    if (int rc = launch_smooth(d, dc, nullptr)) return rc;
+    return fetch_out(o);
+}
+
+extern "C" int asl_smooth_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                        const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed, double sigma_px,
+                                        double sigma_rot, double sigma_trans, int max_iters, void *d_out, void *d_result, void *stream)
+{
+    return smooth_frames_device(d, {d_obs, n_frames, max_tags, d_map, n_ids, {K, dist, n_dist, tag_size}, d_seed, nullptr, 1,
+                                    sigma_px, sigma_rot, sigma_trans, max_iters, d_out, d_result, nullptr, false, false}, stream);
+}
+
+extern "C" int asl_smooth_cov_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                            const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed,
+                                            double sigma_px, double sigma_rot, double sigma_trans, int max_iters, void *d_out, void *d_result,
+                                            void *d_cov, void *stream)
+{
+    return smooth_frames_device(d, {d_obs, n_frames, max_tags, d_map, n_ids, {K, dist, n_dist, tag_size}, d_seed, nullptr, 1,
+                                    sigma_px, sigma_rot, sigma_trans, max_iters, d_out, d_result, d_cov, true, false}, stream);
+}
+
+extern "C" int asl_smooth_sequences_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                           const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed,
+                                           const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
+                                           int max_iters, void *d_out, void *d_results, void *d_cov, void *stream)
+{
+    return smooth_frames_device(d, {d_obs, n_frames, max_tags, d_map, n_ids, {K, dist, n_dist, tag_size}, d_seed, seq_start, n_seq,
+                                    sigma_px, sigma_rot, sigma_trans, max_iters, d_out, d_results, d_cov, d_cov != nullptr, true}, stream);
+}
+
+extern "C" int asl_smooth_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed, double sigma_px,
+                                double sigma_rot, double sigma_trans, int max_iters, asl_cam_pose *out, asl_smooth_result *result)
+{
+    return smooth_batch(d, {obs, n_frames, max_tags, map, n_ids, {K, dist, n_dist, tag_size}, seed, nullptr, 1,
+                            sigma_px, sigma_rot, sigma_trans, max_iters, out, result, nullptr, false, false});
+}
+
+extern "C" int asl_smooth_cov_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                    const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed, double sigma_px,
+                                    double sigma_rot, double sigma_trans, int max_iters, asl_cam_pose *out, asl_smooth_result *result,
+                                    asl_pose_cov *cov)
+{
+    return smooth_batch(d, {obs, n_frames, max_tags, map, n_ids, {K, dist, n_dist, tag_size}, seed, nullptr, 1,
+                            sigma_px, sigma_rot, sigma_trans, max_iters, out, result, cov, true, false});
+}
+
+extern "C" int asl_smooth_sequences_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                          const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed,
+                                          const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
+                                          int max_iters, asl_cam_pose *out, asl_smooth_result *results, asl_pose_cov *cov)
+{
+    return smooth_batch(d, {obs, n_frames, max_tags, map, n_ids, {K, dist, n_dist, tag_size}, seed, seq_start, n_seq,
+                            sigma_px, sigma_rot, sigma_trans, max_iters, out, results, cov, cov != nullptr, true});
+}
