@@ -48,9 +48,12 @@ __device__ __forceinline__ void argmax_step(double &a, int &s)
 // Squared pixel error of one corner at camera point P = R X + t; with NE its rows of the Jacobian
 // d uv / d delta = J_proj [-[P]x | I] are added to acc: JtJ (packed lower triangle, 21) and Jt r (6).
 // (A template rather than a null pointer: a pointer chosen at run time keeps the arrays out of registers.)
-template <bool NE>
+// ROBUST (the sequence solve's Huber loss, k_smooth.inc; every other caller leaves it false and gets the code above alone):
+// with s = |r| > hk the corner costs 2 hk s - hk^2 instead of s^2, its rows enter acc times wgt = hk / s, and *over is set;
+// else wgt = 1 and the sums are the plain ones to the bit.  Lane-local: one sqrt, one division, 27 products.
+template <bool NE, bool ROBUST = false>
 __device__ __forceinline__ double loc_corner(const CamDev &c, const double *R, const double *t, const double *X, double iu, double iv,
-                                             double *acc)
+                                             double *acc, double hk = 0.0, bool *over = nullptr)
 {
     double P[3], uv[2], Jp[6];
 #pragma unroll
@@ -58,6 +61,14 @@ __device__ __forceinline__ double loc_corner(const CamDev &c, const double *R, c
     if (!(P[2] > LOC_Z_MIN)) return LOC_BEHIND_COST;
     project_dev(c, P, uv, NE ? Jp : nullptr);
     const double r0 = uv[0] - iu, r1 = uv[1] - iv;
+    [[maybe_unused]] double wgt = 1.0, rho = 0.0;
+    if constexpr (ROBUST) {
+        const double e = r0 * r0 + r1 * r1, s = sqrt(e);
+        const bool o = s > hk;
+        wgt = o ? hk / s : 1.0;
+        rho = o ? 2.0 * hk * s - hk * hk : e;
+        *over = o;
+    }
     if constexpr (NE) {
         const double nPx[9] = {0, P[2], -P[1], -P[2], 0, P[0], P[1], -P[0], 0};  // -[P]x
         double J0[6], J1[6];
@@ -70,12 +81,17 @@ __device__ __forceinline__ double loc_corner(const CamDev &c, const double *R, c
         }
 #pragma unroll
         for (int a = 0; a < 6; a++) {
-            acc[21 + a] += J0[a] * r0 + J1[a] * r1;
+            if constexpr (ROBUST) acc[21 + a] += wgt * (J0[a] * r0 + J1[a] * r1);
+            else acc[21 + a] += J0[a] * r0 + J1[a] * r1;
 #pragma unroll
-            for (int b = 0; b <= a; b++) acc[TRI(a, b)] += J0[a] * J0[b] + J1[a] * J1[b];
+            for (int b = 0; b <= a; b++) {
+                if constexpr (ROBUST) acc[TRI(a, b)] += wgt * (J0[a] * J0[b] + J1[a] * J1[b]);
+                else acc[TRI(a, b)] += J0[a] * J0[b] + J1[a] * J1[b];
+            }
         }
     }
-    return r0 * r0 + r1 * r1;
+    if constexpr (ROBUST) return rho;
+    else return r0 * r0 + r1 * r1;
 }
 
 // The slot model of one camera: slot s is record fo[s], every corner goes through cam, and the pose solved for is the
@@ -86,10 +102,11 @@ struct LocOneCam {
     int max_tags;
     __device__ __forceinline__ int nslots() const { return max_tags; }
     __device__ __forceinline__ const ObsRec *rec(int s) const { return fo + s; }
-    template <bool NE>
-    __device__ __forceinline__ double corner(int, const double *R, const double *t, const double *X, double iu, double iv, double *acc) const
+    template <bool NE, bool ROBUST = false>
+    __device__ __forceinline__ double corner(int, const double *R, const double *t, const double *X, double iu, double iv, double *acc,
+                                             double hk = 0.0, bool *over = nullptr) const
     {
-        return loc_corner<NE>(cam, R, t, X, iu, iv, acc);
+        return loc_corner<NE, ROBUST>(cam, R, t, X, iu, iv, acc, hk, over);
     }
     // the solved pose (R, t) that slot s's PnP pose To and map tag M propose (loc_candidate)
     __device__ __forceinline__ void candidate(int, const double *To, const double *M, bool mirror, double *R, double *t) const;
@@ -226,16 +243,35 @@ __device__ __forceinline__ int loc_best_candidate(const int (&sel)[K], int nsel,
 
 // Total cost over the active corners (state == 1) of the model's slots, identical in every lane; with NE also the normal
 // equations in ne.
-template <bool NE, class Model>
-__device__ __forceinline__ double loc_pass(const Model &m, const double *R, const double *t, const LocLds &L, int lane, double *ne)
+// ROBUST (LocOneCam only): every corner through the Huber loss of threshold hk (loc_corner), and *soft the number of active
+// slots with a corner over it.  A slot's corners are four neighbouring lanes of one round of the loop (64 is a multiple of 4),
+// so the slot's OR is two quad exchanges; every lane takes every round, for the exchanges to read live lanes.
+template <bool NE, bool ROBUST = false, class Model>
+__device__ __forceinline__ double loc_pass(const Model &m, const double *R, const double *t, const LocLds &L, int lane, double *ne,
+                                           [[maybe_unused]] double hk = 0.0, [[maybe_unused]] int *soft = nullptr)
 {
     const int n4 = 4 * m.nslots();
     double cost = 0, acc[27];
 #pragma unroll
     for (int i = 0; i < 27; i++) acc[i] = 0;
-    for (int k = lane; k < n4; k += ASL_WAVE) {
-        if (L.state[k >> 2] != 1) continue;
-        cost += m.template corner<NE>(k >> 2, R, t, L.X + 3 * k, (double)L.uv[2 * k], (double)L.uv[2 * k + 1], acc);
+    if constexpr (ROBUST) {
+        int ns = 0;
+        for (int base = 0; base < n4; base += ASL_WAVE) {
+            const int k = base + lane;
+            const bool act = k < n4 && L.state[k >> 2] == 1;
+            bool over = false;
+            if (act) cost += m.template corner<NE, true>(k >> 2, R, t, L.X + 3 * k, (double)L.uv[2 * k], (double)L.uv[2 * k + 1], acc, hk, &over);
+            unsigned int o = over ? 1u : 0u;
+            o |= lane_xor32<1>(o);
+            o |= lane_xor32<2>(o);
+            ns += (o && (k & 3) == 0) ? 1 : 0;
+        }
+        *soft = butterfly_sum<64>(ns);
+    } else {
+        for (int k = lane; k < n4; k += ASL_WAVE) {
+            if (L.state[k >> 2] != 1) continue;
+            cost += m.template corner<NE>(k >> 2, R, t, L.X + 3 * k, (double)L.uv[2 * k], (double)L.uv[2 * k + 1], acc);
+        }
     }
     if constexpr (NE) {
 #pragma unroll

@@ -3,6 +3,11 @@
 // error of all mapped corners (/ sigma_px^2) plus |(Log(R_D) / sigma_rot, t_D / sigma_trans)|^2 between consecutive
 // frames, R_D = R_{f+1} R_f^T, t_D = t_{f+1} - R_D t_f.  tests/smooth_ref.py is the NumPy statement of the same
 // computation, operation order of the linear solve included.  float64, contraction off, no scratch.
+// asl_smooth_robust_sequences_* (huber_px > 0): the same launches with k_smooth_cand<true> and k_smooth_lin<true>, which put every
+// corner's pixel residual through a Huber loss (loc_corner<NE, true>, k_localize.inc): its cost in every place the squared
+// one stands, its weight on J^T J and J^T r, and per frame the number of slots with a corner over the threshold, carried
+// with the state (SmoothSet.soft) as the pixel cost is.  tests/smooth_robust_ref.py states it.  The plain calls run the
+// <false> instantiations: the code they ran before, the counts 0.
 //   seed chain   k_smooth_cand   one wavefront per frame: the seed's pose A and, for a frame of exactly one taking-part slot,
 //                                its mirrored planar minimum B (loc_candidate), both costed over the frame's corners
 //                k_smooth_scan   one wavefront a sequence: the nearest posed frame at or before every frame (wave_scan of a maximum)
@@ -17,7 +22,8 @@
 //                                block spread over 36 lanes with its operands in LDS
 //                k_smooth_decide one workgroup a sequence: the trial's cost in a fixed order, the accept rule, lambda, the stop
 //                k_smooth_commit the accepted trials copied over the current state, spread over the device
-//   end          k_smooth_finish one thread per frame: the records
+//   end          k_smooth_finish one thread per frame: the records (n_rejected: the frame's soft slots; n_soft: lm[SM_SOFT], their
+//                                sum over the sequence by k_smooth_init / k_smooth_decide's fixed-order sums)
 //   covariance   k_smooth_cov    (asl_smooth_cov_*, only when asked for) one wavefront a sequence: the undamped block Cholesky of the
 //                                returned state forward, the diagonal blocks of the inverse back, a 6x6 block from frame to frame
 //                k_smooth_cov_finish  one thread per frame: sigma_px, dof, status, and the zeros of a status 1 / 2
@@ -32,25 +38,25 @@
 
 struct SmoothResultRec {  // == asl_smooth_result, 64 bytes
     double cost_seed, cost, rms_px, rms_seed_px;
-    int32_t n_frames_data, n_filled, n_flipped, iterations, status, reserved[3];
+    int32_t n_frames_data, n_filled, n_flipped, iterations, status, n_soft, reserved[2];
 };
 
-enum { SM_COST = 0, SM_LAMBDA, SM_STOP, SM_ITERS, SM_STATUS, SM_COST0, SM_SOLVED, SM_PIX, SM_PIX0, SM_CORNERS, SM_NDATA, SM_TAKE, SM_COV, SM__N = 16 };
+enum { SM_COST = 0, SM_LAMBDA, SM_STOP, SM_ITERS, SM_STATUS, SM_COST0, SM_SOLVED, SM_PIX, SM_PIX0, SM_CORNERS, SM_NDATA, SM_TAKE, SM_COV, SM_SOFT, SM__N = 16 };
 enum { SMH_NPOSED = 0, SMH_FIRST, SMH_FAIL, SMH_NFLIP, SMH__N = 4 };
 #define SM_MOT 121                // per pair: QN 36, QP 36, C 36, gN 6, gP 6, |m|^2
-#define SM_SET (12 + 27 + 1 + SM_MOT)  // doubles per frame of one state: pose, normal equations, pixel cost, motion blocks
+#define SM_SET (12 + 27 + 2 + SM_MOT)  // doubles per frame of one state: pose, normal equations, pixel cost, soft slots, motion blocks
 #define SM_FAC 84                 // per frame of the factorisation: L 36, M 36, 1 / diag 6, y 6 (k_smooth_cov: the undamped one, no y)
 #define SM_WG 256
 
 // One state of the solve over n frames, one allocation: poses (R 9, t 3), packed normal equations (21 + 6), pixel costs,
-// motion blocks of the pairs (f, f + 1)
+// soft-slot counts (the robust call's; 0 from the plain ones), motion blocks of the pairs (f, f + 1)
 struct SmoothSet {
-    double *P, *ne, *c, *mot;
+    double *P, *ne, *c, *soft, *mot;
 };
 
 __host__ __device__ inline SmoothSet smooth_set(double *base, size_t n)
 {
-    return {base, base + 12 * n, base + 39 * n, base + 40 * n};
+    return {base, base + 12 * n, base + 39 * n, base + 40 * n, base + 41 * n};
 }
 
 struct SmoothBufs {
@@ -175,9 +181,11 @@ __device__ __forceinline__ double smooth_block_sum(double v, double *sh)
     return sh[0];
 }
 
-// Candidates of one frame and their data costs
+// Candidates of one frame and their data costs; ROBUST: under the Huber loss of threshold hk pixels (loc_corner), as every
+// later cost of the call is
+template <bool ROBUST>
 __global__ void __launch_bounds__(64) k_smooth_cand(const ObsRec *__restrict__ obs, int max_tags, const MapTagRec *__restrict__ map, int n_ids,
-                                                    CamDev cam, const CamPoseRec *__restrict__ seed, double w, SmoothBufs b)
+                                                    CamDev cam, const CamPoseRec *__restrict__ seed, double w, SmoothBufs b, double hk)
 {
     extern __shared__ double s_dyn[];
     const int lane = (int)threadIdx.x, f = (int)blockIdx.x;
@@ -197,7 +205,12 @@ __global__ void __launch_bounds__(64) k_smooth_cand(const ObsRec *__restrict__ o
     }
 #pragma unroll
     for (int i = 0; i < 3; i++) tA[i] = -(RA[3 * i] * T[3] + RA[3 * i + 1] * T[7] + RA[3 * i + 2] * T[11]);
-    const double dA = loc_pass<false>(m, RA, tA, L, lane, nullptr) * w;
+    [[maybe_unused]] int soft;
+    const auto data_cost = [&](const double *R, const double *t) {
+        if constexpr (ROBUST) return loc_pass<false, true>(m, R, t, L, lane, nullptr, hk, &soft);
+        else return loc_pass<false>(m, R, t, L, lane, nullptr);
+    };
+    const double dA = data_cost(RA, tA) * w;
     double dB = dA;
     const bool has_b = npart == 1;
     if (has_b) {  // the one taking-part slot: the only term of the sum
@@ -216,7 +229,7 @@ __global__ void __launch_bounds__(64) k_smooth_cand(const ObsRec *__restrict__ o
                 To[4 * i + j] = RA[3 * i] * M[j] + RA[3 * i + 1] * M[4 + j] + RA[3 * i + 2] * M[8 + j] + (j == 3 ? tA[i] : 0.0);
         }
         loc_candidate(To, M, true, RB, tB);
-        dB = loc_pass<false>(m, RB, tB, L, lane, nullptr) * w;
+        dB = data_cost(RB, tB) * w;
     }
     if (lane == 0) {
         double *c = b.cand + 24 * (size_t)f;
@@ -327,11 +340,14 @@ __global__ void __launch_bounds__(64) k_smooth_dp(SmoothBufs b)
     if (lane == 0) head[SMH_NFLIP] = nflip;
 }
 
-// Every frame's start pose and seed code
+// Every frame's start pose and seed code; the soft-slot counts of both states start at 0 (the robust k_smooth_lin alone
+// writes them again)
 __global__ void __launch_bounds__(SM_WG) k_smooth_fill(SmoothBufs b, const CamPoseRec *__restrict__ seed)
 {
     const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (f >= b.n) return;
+    smooth_set(b.set[0], (size_t)b.n).soft[f] = 0.0;
+    smooth_set(b.set[1], (size_t)b.n).soft[f] = 0.0;
     const int *head = b.head + SMH__N * smooth_seq_of(b, f).k;
     if (head[SMH_NPOSED] == 0) return;
     int s = b.src[f];
@@ -344,9 +360,11 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_fill(SmoothBufs b, const CamPo
 }
 
 // Frame f of a state: its pose (trial: the current one stepped by delta), pixel cost, H and g, and the motion blocks of
-// the pair (f, f + 1) at the same state
+// the pair (f, f + 1) at the same state.  ROBUST: the cost is the Huber loss of threshold hk pixels, H and g are the sums
+// weighted by it (iteratively reweighted Gauss-Newton, no second-order term), and the state carries the frame's soft slots
+template <bool ROBUST>
 __global__ void __launch_bounds__(64) k_smooth_lin(const ObsRec *__restrict__ obs, int max_tags, const MapTagRec *__restrict__ map, int n_ids,
-                                                   CamDev cam, SmoothBufs b, int trial, double isr, double ist)
+                                                   CamDev cam, SmoothBufs b, int trial, double isr, double ist, double hk)
 {
     extern __shared__ double s_dyn[];
     __shared__ double s_RD[9], s_tD[3], s_m[6], s_B[36], s_Ad[36], s_Jn[36], s_Jp[36];
@@ -369,8 +387,10 @@ __global__ void __launch_bounds__(64) k_smooth_lin(const ObsRec *__restrict__ ob
     const ObsRec *fo = obs + (size_t)f * max_tags;
     const LocOneCam m{cam, fo, max_tags};
     loc_gather([&](int s) { return fo + s; }, max_tags, map, n_ids, cam.half, [](int) { return false; }, L, lane);
-    double ne[27];
-    const double c = loc_pass<true>(m, P, P + 9, L, lane, ne);
+    double ne[27], c;
+    [[maybe_unused]] int soft;
+    if constexpr (ROBUST) c = loc_pass<true, true>(m, P, P + 9, L, lane, ne, hk, &soft);
+    else c = loc_pass<true>(m, P, P + 9, L, lane, ne);
     if (lane == 0) {
         if (trial) {  // trial 0 linearises the current state in place: its poses stay as they are (block f - 1 reads them)
 #pragma unroll
@@ -379,6 +399,7 @@ __global__ void __launch_bounds__(64) k_smooth_lin(const ObsRec *__restrict__ ob
 #pragma unroll
         for (int k = 0; k < 27; k++) out.ne[27 * (size_t)f + k] = ne[k];
         out.c[f] = c;
+        if constexpr (ROBUST) out.soft[f] = (double)soft;   // the plain kernel leaves k_smooth_fill's 0
     }
     if (f + 1 >= q.f0 + q.n) return;   // the last frame of its sequence: no pair
 
@@ -458,11 +479,12 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_init(SmoothBufs b, double w)
         return;
     }
     const SmoothSet s = smooth_set(b.set[0], (size_t)b.n);
-    double cost = 0, pix = 0, corners = 0, ndata = 0;
+    double cost = 0, pix = 0, corners = 0, ndata = 0, soft = 0;
     for (int lf = tid; lf < q.n; lf += SM_WG) {
         const int f = q.f0 + lf;
         const double c = s.c[f];
         b.cseed[f] = c;
+        soft += s.soft[f];
         cost += c * w + (lf + 1 < q.n ? s.mot[SM_MOT * (size_t)f + 120] : 0.0);
         pix += c;
         corners += 4.0 * b.ntags[f];
@@ -472,9 +494,11 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_init(SmoothBufs b, double w)
     pix = smooth_block_sum(pix, sh);
     corners = smooth_block_sum(corners, sh);
     ndata = smooth_block_sum(ndata, sh);
+    soft = smooth_block_sum(soft, sh);
     if (tid == 0) {
         const bool bad = !isfinite(cost);
         lm[SM_COST] = cost; lm[SM_COST0] = cost; lm[SM_PIX] = pix; lm[SM_PIX0] = pix; lm[SM_CORNERS] = corners; lm[SM_NDATA] = ndata;
+        lm[SM_SOFT] = soft;
         lm[SM_LAMBDA] = 1e-3; lm[SM_ITERS] = 0.0; lm[SM_SOLVED] = 0.0;
         lm[SM_STOP] = bad ? 1.0 : 0.0;
         lm[SM_STATUS] = bad ? 3.0 : 0.0;
@@ -623,15 +647,17 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_decide(SmoothBufs b, double w)
         return;
     }
     const SmoothSet t = smooth_set(b.set[1], (size_t)b.n);
-    double cn = 0, pix = 0;
+    double cn = 0, pix = 0, soft = 0;
     for (int lf = tid; lf < q.n; lf += SM_WG) {
         const int f = q.f0 + lf;
         const double c = t.c[f];
+        soft += t.soft[f];
         cn += c * w + (lf + 1 < q.n ? t.mot[SM_MOT * (size_t)f + 120] : 0.0);
         pix += c;
     }
     cn = smooth_block_sum(cn, sh);
     pix = smooth_block_sum(pix, sh);
+    soft = smooth_block_sum(soft, sh);
     const bool take = cn < cost;
     if (tid == 0) {
         lm[SM_ITERS] += 1.0;
@@ -641,6 +667,7 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_decide(SmoothBufs b, double w)
             if (cost - cn < 1e-12 * cost) lm[SM_STOP] = 1.0;
             lm[SM_COST] = cn;
             lm[SM_PIX] = pix;
+            lm[SM_SOFT] = soft;
             lm[SM_LAMBDA] *= 0.1;
         } else
             lm[SM_LAMBDA] *= 10.0;
@@ -648,7 +675,7 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_decide(SmoothBufs b, double w)
 }
 
 // A workgroup a frame at a time, where the frame's sequence took its trial: a thread an entry of the frame's SM_SET (pose,
-// normal equations, pixel cost, the pair's motion blocks)
+// normal equations, pixel cost, soft slots, the pair's motion blocks)
 __global__ void __launch_bounds__(SM_WG) k_smooth_commit(SmoothBufs b)
 {
     if (b.n_seq == 1 && b.lm[SM_TAKE] == 0.0) return;
@@ -656,7 +683,7 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_commit(SmoothBufs b)
     const int e = (int)threadIdx.x;
     for (size_t f = blockIdx.x; f < n; f += gridDim.x) {
         if (e >= SM_SET || b.lm[SM__N * smooth_seq_of_uniform(b, (int)f).k + SM_TAKE] == 0.0) continue;
-        const size_t at = e < 12 ? 12 * f + e : e < 39 ? 12 * n + 27 * f + (e - 12) : e == 39 ? 39 * n + f : 40 * n + SM_MOT * f + (e - 40);
+        const size_t at = e < 12 ? 12 * f + e : e < 39 ? 12 * n + 27 * f + (e - 12) : e < 41 ? (size_t)e * n + f : 41 * n + SM_MOT * f + (e - 41);
         b.set[0][at] = b.set[1][at];
     }
 }
@@ -683,7 +710,8 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_finish(SmoothBufs b, CamPoseRe
         res->n_flipped = nothing ? 0 : head[SMH_NFLIP];
         res->iterations = (int)lm[SM_ITERS];
         res->status = status;
-        res->reserved[0] = 0; res->reserved[1] = 0; res->reserved[2] = 0;
+        res->n_soft = nothing ? 0 : (int)lm[SM_SOFT];
+        res->reserved[0] = 0; res->reserved[1] = 0;
     }
     CamPoseRec *o = out + f;
     if (nothing) { loc_write_none(o, 1); return; }
@@ -699,7 +727,7 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_finish(SmoothBufs b, CamPoseRe
     o->rms_px = nt > 0 ? sqrt(s.c[f] / (4.0 * nt)) : 0.0;
     o->rms_seed_px = nt > 0 ? sqrt(b.cseed[f] / (4.0 * nt)) : 0.0;
     o->n_tags = nt;
-    o->n_rejected = 0;
+    o->n_rejected = (int)s.soft[f];
     o->status = status != 0 ? 4 : nt > 0 ? 0 : 6;
     o->seed_slot = b.code[f];
 }

@@ -560,17 +560,18 @@ extern "C" int asl_map_batch(asl_detector *d, const asl_obs *obs, int n_frames, 
 #define SMOOTH_SEQS 65535         // sequences of one call
 #define SMOOTH_FRAMES 1048576     // frames of one call: the work buffers, about 3.6 KB a frame, stay under 4 GB
 
-// One smoothing call, whichever of the six entry points made it, in their argument order.  The single-sequence forms leave
+// One smoothing call, whichever of the eight entry points made it, in their argument order.  The single-sequence forms leave
 // seq_start NULL, n_seq 1 and sequences false: the one sequence {0, n_frames}; seq_start is a host array of n_seq + 1
 // offsets in every form.  The plain forms leave cov NULL and with_cov false; the sequences forms set with_cov where cov is
 // given.  The host forms may leave seed NULL: the per-frame localisation of the same block.  obs, map, seed, out, result
-// and cov are all host or all device pointers.
+// and cov are all host or all device pointers.  huber_px: 0 from the six plain entry points (the squared corner loss and
+// its kernels), the robust pair's threshold in pixels otherwise.
 struct SmoothCall {
     const void *obs; int n_frames, max_tags;
     const void *map; int n_ids;
     Camera cam;
     const void *seed; const int32_t *seq_start; int n_seq;
-    double sigma_px, sigma_rot, sigma_trans; int max_iters;
+    double sigma_px, sigma_rot, sigma_trans, huber_px; int max_iters;
     void *out, *result, *cov;
     bool with_cov, sequences;
 };
@@ -603,6 +604,7 @@ static int check_smooth_call(const asl_detector *d, const SmoothCall &c, bool de
         if (!std::isfinite(c.cam.K[k])) return fail(ASL_EINVAL, "K is not finite");
     for (double s : {c.sigma_px, c.sigma_rot, c.sigma_trans})
         if (!(s > 0) || !std::isfinite(s)) return fail(ASL_EINVAL, "sigma_px, sigma_rot and sigma_trans must be positive and finite (got %g)", s);
+    if (!(c.huber_px >= 0) || !std::isfinite(c.huber_px)) return fail(ASL_EINVAL, "huber_px must be finite and not negative (got %g)", c.huber_px);
     if (c.max_iters < 1 || c.max_iters > 100) return fail(ASL_EINVAL, "max_iters must be in [1, 100] (got %d)", c.max_iters);
     if ((device && !c.seed) || (c.with_cov && !c.cov)) return fail(ASL_EINVAL, "NULL argument");
     if (!device) return ASL_OK;
@@ -615,7 +617,8 @@ static int check_smooth_call(const asl_detector *d, const SmoothCall &c, bool de
 
 // c's pointers are the device's but seq_start (host, not read for n_seq 1); everything is enqueued on st, nothing waits.
 // cov: NULL, or the frames' asl_pose_cov (two more launches).  n_seq > 1: k_smooth_seqs first, a launch per SM_SEQ_CHUNK
-// sequences, which carries the offsets to the device in its arguments.
+// sequences, which carries the offsets to the device in its arguments.  huber_px > 0: the robust instantiations of the two
+// kernels that cost corners, the same launches otherwise.
 static int launch_smooth(asl_detector *d, const SmoothCall &c, hipStream_t st)
 {
     const size_t n = (size_t)c.n_frames, ns = (size_t)c.n_seq;
@@ -649,18 +652,21 @@ static int launch_smooth(asl_detector *d, const SmoothCall &c, hipStream_t st)
         memcpy(ch.start, c.seq_start + k0, sizeof(int32_t) * ((size_t)ch.count + 1));
         hipLaunchKernelGGL(k_smooth_seqs, dim3((unsigned int)ch.count), wg, 0, st, b, ch);
     }
-    hipLaunchKernelGGL(k_smooth_cand, frames, wave, lds, st, obs, c.max_tags, map, c.n_ids, cam, seed, w, b);
+    const bool robust = c.huber_px > 0;
+    const auto cand = robust ? k_smooth_cand<true> : k_smooth_cand<false>;
+    const auto lin = robust ? k_smooth_lin<true> : k_smooth_lin<false>;
+    hipLaunchKernelGGL(cand, frames, wave, lds, st, obs, c.max_tags, map, c.n_ids, cam, seed, w, b, c.huber_px);
     hipLaunchKernelGGL(k_smooth_scan, seqs, wave, 0, st, b);
     hipLaunchKernelGGL(k_smooth_trans, dim3((unsigned int)((n + ASL_WAVE - 1) / ASL_WAVE)), wave, 0, st, b, isr, ist);
     hipLaunchKernelGGL(k_smooth_dp, seqs, wave, 0, st, b);
     hipLaunchKernelGGL(k_smooth_fill, per_thread, wg, 0, st, b, seed);
-    hipLaunchKernelGGL(k_smooth_lin, frames, wave, lds, st, obs, c.max_tags, map, c.n_ids, cam, b, 0, isr, ist);
+    hipLaunchKernelGGL(lin, frames, wave, lds, st, obs, c.max_tags, map, c.n_ids, cam, b, 0, isr, ist, c.huber_px);
     hipLaunchKernelGGL(k_smooth_init, seqs, wg, 0, st, b, w);
     range_pop();
     range_push("smooth: LM");
     for (int it = 0; it < c.max_iters; it++) {
         hipLaunchKernelGGL(k_smooth_solve, seqs, wave, 0, st, b, w);
-        hipLaunchKernelGGL(k_smooth_lin, frames, wave, lds, st, obs, c.max_tags, map, c.n_ids, cam, b, 1, isr, ist);
+        hipLaunchKernelGGL(lin, frames, wave, lds, st, obs, c.max_tags, map, c.n_ids, cam, b, 1, isr, ist, c.huber_px);
         hipLaunchKernelGGL(k_smooth_decide, seqs, wg, 0, st, b, w);
         hipLaunchKernelGGL(k_smooth_commit, commit_blocks, wg, 0, st, b);
     }
@@ -676,9 +682,9 @@ static int launch_smooth(asl_detector *d, const SmoothCall &c, hipStream_t st)
     return ASL_OK;
 }
 
-static constexpr auto smooth_frames_device = frames_device<SmoothCall, check_smooth_call, launch_smooth>;   // the three device forms
+static constexpr auto smooth_frames_device = frames_device<SmoothCall, check_smooth_call, launch_smooth>;   // the four device forms
 
-// the three host forms; a seed not given is the per-frame localisation of the same block, gate 0
+// the four host forms; a seed not given is the per-frame localisation of the same block, gate 0
 static int smooth_batch(asl_detector *d, const SmoothCall &c)
 {
     if (int rc = check_smooth_call(d, c, false)) return rc;
@@ -701,7 +707,7 @@ extern "C" int asl_smooth_frames_device(asl_detector *d, const void *d_obs, int 
                                         double sigma_rot, double sigma_trans, int max_iters, void *d_out, void *d_result, void *stream)
 {
     return smooth_frames_device(d, {d_obs, n_frames, max_tags, d_map, n_ids, {K, dist, n_dist, tag_size}, d_seed, nullptr, 1,
-                                    sigma_px, sigma_rot, sigma_trans, max_iters, d_out, d_result, nullptr, false, false}, stream);
+                                    sigma_px, sigma_rot, sigma_trans, 0.0, max_iters, d_out, d_result, nullptr, false, false}, stream);
 }
 
 extern "C" int asl_smooth_cov_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
@@ -710,7 +716,7 @@ extern "C" int asl_smooth_cov_frames_device(asl_detector *d, const void *d_obs, 
                                             void *d_cov, void *stream)
 {
     return smooth_frames_device(d, {d_obs, n_frames, max_tags, d_map, n_ids, {K, dist, n_dist, tag_size}, d_seed, nullptr, 1,
-                                    sigma_px, sigma_rot, sigma_trans, max_iters, d_out, d_result, d_cov, true, false}, stream);
+                                    sigma_px, sigma_rot, sigma_trans, 0.0, max_iters, d_out, d_result, d_cov, true, false}, stream);
 }
 
 extern "C" int asl_smooth_sequences_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
@@ -719,7 +725,7 @@ extern "C" int asl_smooth_sequences_device(asl_detector *d, const void *d_obs, i
                                            int max_iters, void *d_out, void *d_results, void *d_cov, void *stream)
 {
     return smooth_frames_device(d, {d_obs, n_frames, max_tags, d_map, n_ids, {K, dist, n_dist, tag_size}, d_seed, seq_start, n_seq,
-                                    sigma_px, sigma_rot, sigma_trans, max_iters, d_out, d_results, d_cov, d_cov != nullptr, true}, stream);
+                                    sigma_px, sigma_rot, sigma_trans, 0.0, max_iters, d_out, d_results, d_cov, d_cov != nullptr, true}, stream);
 }
 
 extern "C" int asl_smooth_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
@@ -727,7 +733,7 @@ extern "C" int asl_smooth_batch(asl_detector *d, const asl_obs *obs, int n_frame
                                 double sigma_rot, double sigma_trans, int max_iters, asl_cam_pose *out, asl_smooth_result *result)
 {
     return smooth_batch(d, {obs, n_frames, max_tags, map, n_ids, {K, dist, n_dist, tag_size}, seed, nullptr, 1,
-                            sigma_px, sigma_rot, sigma_trans, max_iters, out, result, nullptr, false, false});
+                            sigma_px, sigma_rot, sigma_trans, 0.0, max_iters, out, result, nullptr, false, false});
 }
 
 extern "C" int asl_smooth_cov_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
@@ -736,7 +742,7 @@ extern "C" int asl_smooth_cov_batch(asl_detector *d, const asl_obs *obs, int n_f
                                     asl_pose_cov *cov)
 {
     return smooth_batch(d, {obs, n_frames, max_tags, map, n_ids, {K, dist, n_dist, tag_size}, seed, nullptr, 1,
-                            sigma_px, sigma_rot, sigma_trans, max_iters, out, result, cov, true, false});
+                            sigma_px, sigma_rot, sigma_trans, 0.0, max_iters, out, result, cov, true, false});
 }
 
 extern "C" int asl_smooth_sequences_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
@@ -745,5 +751,23 @@ extern "C" int asl_smooth_sequences_batch(asl_detector *d, const asl_obs *obs, i
                                           int max_iters, asl_cam_pose *out, asl_smooth_result *results, asl_pose_cov *cov)
 {
     return smooth_batch(d, {obs, n_frames, max_tags, map, n_ids, {K, dist, n_dist, tag_size}, seed, seq_start, n_seq,
-                            sigma_px, sigma_rot, sigma_trans, max_iters, out, results, cov, cov != nullptr, true});
+                            sigma_px, sigma_rot, sigma_trans, 0.0, max_iters, out, results, cov, cov != nullptr, true});
+}
+
+extern "C" int asl_smooth_robust_sequences_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                                  const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed,
+                                                  const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
+                                                  double huber_px, int max_iters, void *d_out, void *d_results, void *d_cov, void *stream)
+{
+    return smooth_frames_device(d, {d_obs, n_frames, max_tags, d_map, n_ids, {K, dist, n_dist, tag_size}, d_seed, seq_start, n_seq,
+                                    sigma_px, sigma_rot, sigma_trans, huber_px, max_iters, d_out, d_results, d_cov, d_cov != nullptr, true}, stream);
+}
+
+extern "C" int asl_smooth_robust_sequences_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                                 const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed,
+                                                 const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
+                                                 double huber_px, int max_iters, asl_cam_pose *out, asl_smooth_result *results, asl_pose_cov *cov)
+{
+    return smooth_batch(d, {obs, n_frames, max_tags, map, n_ids, {K, dist, n_dist, tag_size}, seed, seq_start, n_seq,
+                            sigma_px, sigma_rot, sigma_trans, huber_px, max_iters, out, results, cov, cov != nullptr, true});
 }

@@ -4,10 +4,13 @@ without a mapped tag is carried by its neighbours, a single-tag frame is kept ou
 and corner noise is averaged over the sequence.
 Several sequences in one call, solved side by side: Detector.smooth_sequences / TagDetector.localize_sequences
 (asl_smooth_sequences_batch), one SmoothResult per sequence.
+With huber_px > 0 (asl_smooth_robust_sequences_batch) every corner's pixel residual goes through a Huber loss of that
+threshold: a slipped corner or a slot with another tag's corners is down-weighted instead of bending its frame and its
+neighbours.  SmoothResult.n_soft counts the slots it down-weighted, .soft marks their frames.
 
-    SmoothResult         the poses (CAM_POSE_DTYPE per frame), the SMOOTH_RESULT_DTYPE record, the filled / flipped masks and,
+    SmoothResult         the poses (CAM_POSE_DTYPE per frame), the SMOOTH_RESULT_DTYPE record, the filled / flipped / soft masks and,
                          from a solve with with_cov (asl_smooth_cov_batch), every pose's covariance (POSE_COV_DTYPE per frame)
-    SMOOTH_RESULT_DTYPE  cost_seed, cost, rms_px, rms_seed_px, n_frames_data, n_filled, n_flipped, iterations, status
+    SMOOTH_RESULT_DTYPE  cost_seed, cost, rms_px, rms_seed_px, n_frames_data, n_filled, n_flipped, iterations, status, n_soft
 """
 import numpy as np
 
@@ -51,6 +54,17 @@ class SmoothResult:
     def prior_only(self):
         """frames without a mapped tag: their pose comes from the motion prior alone"""
         return self.poses["status"] == FRAME_PRIOR
+
+    @property
+    def n_soft(self):
+        """taking-part slots, over all frames, with a corner over the Huber threshold at the returned poses (0 from a solve
+        without huber_px)"""
+        return int(self.result["n_soft"])
+
+    @property
+    def soft(self):
+        """frames with such a slot (their n_rejected counts them): down-weighted, not removed"""
+        return self.poses["n_rejected"] > 0
 
     def trajectory(self):
         """(n_frames, 4, 4) world<-camera"""

@@ -218,13 +218,15 @@ class TagDetector:
                                            sigma_px=float(sigma_px) if with_cov else None)
 
     def localize_sequence(self, dets, poses, n_per_frame, tag_map, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20,
-                          max_tags=None, with_cov=False):
+                          max_tags=None, with_cov=False, huber_px=0.0):
         """The structured arrays detect_host / collect return for one camera's CONSECUTIVE frames -> smooth.SmoothResult: a
         world<-camera pose for every frame, the frames solved together with a random-walk motion prior (sigma_rot rad and
         sigma_trans scene units per frame step) next to the corners (sigma_px).  Packs, localises every frame on its own
         (the seed, kept in the result) and smooths (asl_smooth_batch).  with_cov: asl_smooth_cov_batch, and the result
         carries every pose's covariance under the three sigmas (.cov, .cov_status, .pose_std()), the frames carried by the
-        prior alone included."""
+        prior alone included.  huber_px > 0: a Huber loss of that many pixels on every corner's residual
+        (asl_smooth_robust_sequences_batch), for a slipped corner or a slot with another tag's corners; the result's .n_soft
+        and .soft say which slots and frames it down-weighted.  Its linear tail needs more trials: raise max_iters."""
         from .dist import pack_observations
         from .smooth import SmoothResult
         npf = np.asarray(n_per_frame, dtype=np.int64)
@@ -233,17 +235,17 @@ class TagDetector:
         det = self.detector._det
         seed = det.localize(obs, tag_map, self._K(), self._dist(), self.tag_size)
         got = det.smooth(obs, tag_map, self._K(), self._dist(), self.tag_size, sigma_px=sigma_px, sigma_rot=sigma_rot,
-                         sigma_trans=sigma_trans, max_iters=max_iters, seed=seed, with_cov=with_cov)
+                         sigma_trans=sigma_trans, max_iters=max_iters, seed=seed, with_cov=with_cov, huber_px=huber_px)
         return SmoothResult(got[0], got[1], seed, got[2] if with_cov else None)
 
     def localize_sequences(self, sequences, tag_map, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, max_tags=None,
-                           with_cov=False):
+                           with_cov=False, huber_px=0.0):
         """localize_sequence for several sequences in one call: `sequences` is a list of (dets, poses, n_per_frame) triples as
         detect_host / collect return them, each one camera's consecutive frames (different cameras, recordings, or the pieces
         of a recording cut where the camera was off) -> a list of smooth.SmoothResult, one per sequence, each what
         localize_sequence returns for it alone at the same max_tags.  Packs them end to end with one common max_tags,
         localises every frame once (the seeds, kept in the results) and smooths all sequences side by side
-        (asl_smooth_sequences_batch): no term links two sequences."""
+        (asl_smooth_sequences_batch): no term links two sequences.  huber_px as in localize_sequence, the same for all."""
         from .dist import pack_observations
         from .smooth import SmoothResult
         if not len(sequences):
@@ -257,7 +259,7 @@ class TagDetector:
         det = self.detector._det
         seed = det.localize(obs, tag_map, self._K(), self._dist(), self.tag_size)
         got = det.smooth_sequences(obs, start, tag_map, self._K(), self._dist(), self.tag_size, sigma_px=sigma_px, sigma_rot=sigma_rot,
-                                   sigma_trans=sigma_trans, max_iters=max_iters, seed=seed, with_cov=with_cov)
+                                   sigma_trans=sigma_trans, max_iters=max_iters, seed=seed, with_cov=with_cov, huber_px=huber_px)
         return [SmoothResult(got[0][a:b], got[1][k], seed[a:b], got[2][a:b] if with_cov else None)
                 for k, (a, b) in enumerate(zip(start[:-1], start[1:]))]
 

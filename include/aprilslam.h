@@ -406,7 +406,9 @@ typedef struct {
     int32_t iterations;            /* LM trials run */
     int32_t status;                /* 0 ok, 1 no frame with a seed pose (nothing solved), 2 never positive definite,
                                       3 non-finite cost after the chain */
-    int32_t reserved[3];
+    int32_t n_soft;                /* asl_smooth_robust_sequences_*: taking-part slots, over all frames, with a corner over the
+                                      threshold at the returned poses (the frames' n_rejected summed); 0 from the plain calls */
+    int32_t reserved[2];
 } asl_smooth_result;               /* 64 bytes */
 
 /* Smooth d_obs (n_frames x max_tags records of consecutive frames, as asl_pack_observations_device writes them) against
@@ -490,6 +492,38 @@ int asl_smooth_sequences_batch(asl_detector *det, const asl_obs *obs, int n_fram
                                const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed,
                                const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
                                int max_iters, asl_cam_pose *out, asl_smooth_result *results, asl_pose_cov *cov);
+
+/* asl_smooth_sequences_device with a robust (Huber) loss on every corner's pixel residual, for footage where a corner slips
+   or a slot carries another tag's corners: the squared loss lets one such slot bend its frame and, through the prior, its
+   neighbours.  huber_px = k > 0, in pixels, on the raw residual r = (r0, r1) of a corner (before sigma_px), s = |r|:
+   s <= k costs s^2 with weight 1 (the plain term); s > k costs 2 k s - k^2 with weight k / s; a corner at z <= 1e-9 costs 1e12
+   and adds nothing, as before.  The frame's data cost is the sum of these, divided by sigma_px^2 where |r_f|^2 is in the plain
+   objective; the corner adds weight J^T J and weight J^T r to the normal equations (iteratively reweighted Gauss-Newton, no
+   second-order term of the loss).  The robust cost stands wherever the squared one does: the candidates of the seed chain,
+   the cost after the chain, every trial and the accept rule, cost_seed and cost.  rms_px and rms_seed_px, per frame and in
+   the result, are sqrt(sum of the corner costs / corners): the plain RMS whenever no corner is over the threshold.
+   A frame's n_rejected is the number of its taking-part slots with at least one corner of weight < 1 at the returned poses
+   ("soft" slots: down-weighted, not removed); the result's n_soft is their sum over the sequence's frames.  The motion
+   prior, the linear solve, the LM schedule, the stop rule and the fill of unposed frames are those of the plain call, and
+   n_seq = 1 is the single sequence.
+   d_cov (NULL: none): as asl_smooth_cov_frames_device, A built from the weighted normal equations at the returned poses, so
+   a down-weighted corner contributes k / s of its information; d_out and d_results do not depend on whether it is given.
+   A frame whose only tag carries the outlier has nothing to be corrected by except its neighbours through the prior.  The
+   linear tail of the loss needs more trials than the quadratic one (a corrupted 40-frame scene used all 30 it was given
+   where the clean one stopped after 5): raise max_iters.  huber_px == 0 is the plain computation: d_out, d_results and d_cov are byte for byte what
+   asl_smooth_sequences_device writes, n_soft 0.
+   ASL_EINVAL, nothing written: whatever asl_smooth_sequences_device refuses; huber_px < 0 or not finite.  Nothing waits;
+   deterministic: the same input gives the same bytes.  tests/smooth_robust_ref.py states the computation. */
+int asl_smooth_robust_sequences_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                       const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed,
+                                       const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
+                                       double huber_px, int max_iters, void *d_out, void *d_results, void *d_cov, void *stream);
+/* The same computation on host records, synchronous; seed == NULL: the per-frame localisation of all frames runs first, as
+   in asl_smooth_sequences_batch. */
+int asl_smooth_robust_sequences_batch(asl_detector *det, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                      const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed,
+                                      const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
+                                      double huber_px, int max_iters, asl_cam_pose *out, asl_smooth_result *results, asl_pose_cov *cov);
 
 /* ---- before the detector: the image-formation step on the device (reference src/simulation/renderer.py:197-274:
    purple clear colour, one GL_LINEAR-textured quad per tag, BGR read-back).  One plane per visible tag and frame, in

@@ -12,10 +12,15 @@ reported std of the frames with data and of the filled ones next to the errors a
 S equal sequences, solved in one batched call (asl_smooth_sequences_device) and in a loop of S single-sequence device calls,
 the legs again alternating inside every repetition ("sequences": batched_ms_median / _min, loop_ms_median / _min, with --cov
 both with the covariance; same_bytes: the two wrote the same poses, results and covariances).  --loop-only leaves the batched
-call out (a build that does not have it).
+call out (a build that does not have it).  --huber K adds the robust call (asl_smooth_robust_sequences_device, Huber threshold
+K pixels) on the same input, alternating with the plain one: under "robust" its time, trials, ms per trial next to the plain
+call's, n_soft and the position RMSE against the truth next to the plain call's; with --sequences also the batched robust
+call.  --outliers N corrupts N taking-part slots first (--outlier-seed): half get one corner moved by 8 px, half the corners
+of another slot of their frame.
 
     python tools/smooth_lab.py [--frames 1024] [--reps 20] [--max-tags 32] [--sigma-px 0.3] [--sigma-rot 0.01]
                                [--sigma-trans 0.05] [--max-iters 20] [--drop-every 0] [--cov] [--sequences S [--loop-only]]
+                               [--huber K] [--outliers N [--outlier-seed 1]]
 """
 import argparse
 import json
@@ -47,6 +52,9 @@ def main():
     ap.add_argument("--cov", action="store_true", help="also time the call with the covariance, alternating with the plain one")
     ap.add_argument("--sequences", type=int, default=0, help="also cut the block into S equal sequences: one batched call against a loop of S calls")
     ap.add_argument("--loop-only", action="store_true", help="with --sequences: time the loop of single calls alone")
+    ap.add_argument("--huber", type=float, default=0.0, help="also run the robust call with this Huber threshold in pixels")
+    ap.add_argument("--outliers", type=int, default=0, help="corrupt N taking-part slots: half one corner moved by 8 px, half another slot's corners")
+    ap.add_argument("--outlier-seed", type=int, default=1)
     a = ap.parse_args()
     if a.sequences and (a.sequences < 1 or a.frames % a.sequences):
         ap.error("--sequences must divide --frames")
@@ -79,6 +87,26 @@ def main():
         obs["flags"][a.drop_every - 1::a.drop_every] = 0
         d_obs.copy_(torch.from_numpy(obs.view(np.uint8).reshape(n, mt, -1)))
 
+    corrupted = np.zeros(n, dtype=bool)
+    if a.outliers > 0:
+        obs = d_obs.cpu().numpy().view(_lib.OBS_DTYPE).reshape(n, mt).copy()
+        part = (obs["flags"] & 1).astype(bool) & (obs["id"] >= 0) & (obs["id"] < len(rec))
+        part[part] = rec["valid"][obs["id"][part]] != 0
+        rng = np.random.default_rng(a.outlier_seed)
+        slots = np.argwhere(part)
+        pick = slots[rng.choice(len(slots), size=min(a.outliers, len(slots)), replace=False)]
+        src = obs["corners"].copy()
+        for k, (f, sl) in enumerate(pick):
+            others = [o for o in np.flatnonzero(part[f]) if o != sl]
+            if k % 2 == 0 or not others:   # one corner moved by 8 px, in a direction of the seed's choosing
+                ang = rng.uniform(0.0, 2 * np.pi)
+                c = obs["corners"][f, sl].reshape(4, 2)
+                c[rng.integers(4)] += np.array([8.0 * np.cos(ang), 8.0 * np.sin(ang)], dtype=np.float32)
+            else:                          # the corners of another slot of the frame
+                obs["corners"][f, sl] = src[f, others[rng.integers(len(others))]]
+            corrupted[f] = True
+        d_obs.copy_(torch.from_numpy(obs.view(np.uint8).reshape(n, mt, -1)))
+
     def localize():
         det.localize_device(d_obs.data_ptr(), n, mt, d_map.data_ptr(), len(rec), d_seed.data_ptr(), K, None, bench.TAG_INNER,
                             stream=stream.cuda_stream)
@@ -91,6 +119,13 @@ def main():
     def smooth_cov():
         smooth(d_cov.data_ptr())
 
+    d_out_r, d_res_r = torch.zeros_like(d_out), torch.zeros_like(d_res)
+
+    def smooth_robust():
+        det.smooth_device(d_obs.data_ptr(), n, mt, d_map.data_ptr(), len(rec), d_seed.data_ptr(), d_out_r.data_ptr(), d_res_r.data_ptr(), K, None,
+                          bench.TAG_INNER, sigma_px=a.sigma_px, sigma_rot=a.sigma_rot, sigma_trans=a.sigma_trans, max_iters=a.max_iters,
+                          stream=stream.cuda_stream, huber_px=a.huber)
+
     def timed(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(stream)
@@ -102,10 +137,10 @@ def main():
     S = a.sequences
     m = n // S if S else 0
     seq_start = np.arange(S + 1, dtype=np.int32) * m
-    if S:   # outputs of their own, so that the two can be compared
-        d_outs = [torch.zeros_like(d_out) for _ in range(2)]
-        d_ress = [torch.zeros(S * _lib.SMOOTH_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev) for _ in range(2)]
-        d_covs = [torch.zeros_like(d_cov) for _ in range(2)]
+    if S:   # outputs of their own, so that the two can be compared (the third: the batched robust call's)
+        d_outs = [torch.zeros_like(d_out) for _ in range(3)]
+        d_ress = [torch.zeros(S * _lib.SMOOTH_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev) for _ in range(3)]
+        d_covs = [torch.zeros_like(d_cov) for _ in range(3)]
         torch.cuda.synchronize()
     kw = dict(sigma_px=a.sigma_px, sigma_rot=a.sigma_rot, sigma_trans=a.sigma_trans, max_iters=a.max_iters, stream=stream.cuda_stream)
 
@@ -113,14 +148,19 @@ def main():
         det.smooth_sequences_device(d_obs.data_ptr(), n, mt, d_map.data_ptr(), len(rec), d_seed.data_ptr(), seq_start, d_outs[0].data_ptr(),
                                     d_ress[0].data_ptr(), K, None, bench.TAG_INNER, cov_ptr=d_covs[0].data_ptr() if a.cov else None, **kw)
 
+    def batched_robust():
+        det.smooth_sequences_device(d_obs.data_ptr(), n, mt, d_map.data_ptr(), len(rec), d_seed.data_ptr(), seq_start, d_outs[2].data_ptr(),
+                                    d_ress[2].data_ptr(), K, None, bench.TAG_INNER, cov_ptr=d_covs[2].data_ptr() if a.cov else None,
+                                    huber_px=a.huber, **kw)
+
     def loop():
         for k in range(S):
             det.smooth_device(d_obs[k * m:].data_ptr(), m, mt, d_map.data_ptr(), len(rec), d_seed[k * m:].data_ptr(),
                               d_outs[1][k * m:].data_ptr(), d_ress[1][64 * k:].data_ptr(), K, None, bench.TAG_INNER,
                               cov_ptr=d_covs[1][k * m:].data_ptr() if a.cov else None, **kw)
 
-    legs = [localize, smooth] + ([smooth_cov] if a.cov else [])
-    seq_legs = ([] if a.loop_only else [batched]) + [loop] if S else []
+    legs = [localize, smooth] + ([smooth_cov] if a.cov else []) + ([smooth_robust] if a.huber > 0 else [])
+    seq_legs = ([] if a.loop_only else [batched]) + [loop] + ([batched_robust] if a.huber > 0 else []) if S else []
     first_seq_leg = len(legs)
     legs += seq_legs
     with torch.cuda.stream(stream):
@@ -168,6 +208,28 @@ def main():
         line["cov"] = {"status": sorted(set(cov["status"].tolist())), "dof": int(cov["dof"][0]),
                        "std_same_frames": stds(posed & np.isin(out["status"], (0, 6))), "std_filled_frames": stds(~posed & np.isin(out["status"], (0, 6))),
                        "note": "median over the frames of |std of the three rotation / translation components|: compare with the RMS errors above"}
+    def result(r):
+        return {k: (float(r[k]) if r[k].dtype.kind == "f" else int(r[k])) for k in r.dtype.names if k != "reserved"}
+
+    def rmse_units(poses, keep):
+        fr = np.flatnonzero(keep)
+        return rms([np.linalg.norm(poses["T"][f][:3, 3] - truths[f][:3, 3]) for f in fr])
+
+    if a.outliers > 0:
+        line["outliers"] = {"slots": int(len(pick)), "frames": int(corrupted.sum()), "seed": a.outlier_seed}
+    if a.huber > 0:
+        tr = times[[fn.__name__ for fn in legs].index("smooth_robust")]
+        out_r = d_out_r.cpu().numpy().view(CAM_POSE_DTYPE).reshape(n)
+        res_r = d_res_r.cpu().numpy().view(_lib.SMOOTH_RESULT_DTYPE)[0]
+        solved = np.isin(out["status"], (0, 6)) & np.isin(out_r["status"], (0, 6))
+        line["robust"] = {"huber_px": a.huber, "smooth_robust_ms_median": float(np.median(tr)), "smooth_robust_ms_min": float(np.min(tr)),
+                          "result": result(res_r), "soft_frames": int((out_r["n_rejected"] > 0).sum()),
+                          "corrupted_frames_soft": int((out_r["n_rejected"][corrupted] > 0).sum()),
+                          "ms_per_trial": float(np.median(tr)) / max(1, int(res_r["iterations"])),
+                          "plain_ms_per_trial": float(np.median(times[1])) / max(1, int(res["iterations"])),
+                          "position_rmse_units": rmse_units(out_r, solved), "plain_position_rmse_units": rmse_units(out, solved),
+                          "seed_position_rmse_units": rmse_units(seed, posed),
+                          "after_same_frames": errors(out_r, posed & np.isin(out_r["status"], (0, 6)))}
     if S:
         t = dict(zip([fn.__name__ for fn in seq_legs], times[first_seq_leg:]))
         line["sequences"] = {"n_seq": S, "frames_each": m, "with_cov": bool(a.cov),
@@ -179,6 +241,15 @@ def main():
         r = d_ress[1].cpu().numpy().view(_lib.SMOOTH_RESULT_DTYPE)
         line["sequences"]["iterations"] = [int(r["iterations"].min()), int(r["iterations"].max())]
         line["sequences"]["status"] = sorted(set(r["status"].tolist()))
+        if a.huber > 0:
+            rr = d_ress[2].cpu().numpy().view(_lib.SMOOTH_RESULT_DTYPE)
+            pr = d_outs[2].cpu().numpy().view(CAM_POSE_DTYPE).reshape(n)
+            pl = d_outs[1].cpu().numpy().view(CAM_POSE_DTYPE).reshape(n)
+            solved = np.isin(pr["status"], (0, 6)) & np.isin(pl["status"], (0, 6))
+            line["sequences"]["robust"] = {"batched_ms_median": float(np.median(t["batched_robust"])), "batched_ms_min": float(np.min(t["batched_robust"])),
+                                           "iterations": [int(rr["iterations"].min()), int(rr["iterations"].max())],
+                                           "status": sorted(set(rr["status"].tolist())), "n_soft": int(rr["n_soft"].sum()),
+                                           "position_rmse_units": rmse_units(pr, solved), "plain_position_rmse_units": rmse_units(pl, solved)}
     print(json.dumps(line))
     det.close()
 
