@@ -53,7 +53,7 @@ EXPORTS = [
     "asl_localize_rig_frames_device", "asl_localize_rig_cov_frames_device", "asl_localize_rig_batch", "asl_localize_rig_cov_batch",
     "asl_map_frames_device", "asl_map_batch", "asl_smooth_frames_device", "asl_smooth_batch", "asl_smooth_cov_frames_device", "asl_smooth_cov_batch",
     "asl_smooth_sequences_device", "asl_smooth_sequences_batch", "asl_smooth_robust_sequences_device", "asl_smooth_robust_sequences_batch",
-    "asl_debug_fetch", "asl_debug_refit", "asl_debug_division_check", "asl_stage_times", "asl_set_profiling", "asl_debug_phase_cycles",
+    "asl_debug_fetch", "asl_debug_refit", "asl_debug_dedup", "asl_debug_division_check", "asl_stage_times", "asl_set_profiling", "asl_debug_phase_cycles",
 ]
 
 _lib = None
@@ -138,6 +138,7 @@ def load():
     L.asl_smooth_robust_sequences_batch.argtypes = smooth + seqs + robust + [vp]
     L.asl_debug_fetch.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.asl_debug_refit.argtypes = [vp, i32, vp, C.c_size_t]
+    L.asl_debug_dedup.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, C.c_size_t]
     L.asl_debug_division_check.argtypes = [vp, i32, vp, C.c_size_t]
     L.asl_stage_times.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32, C.POINTER(i32)]
     L.asl_set_profiling.argtypes = [vp, i32]
@@ -716,6 +717,20 @@ class Detector:
         buf = np.zeros(7, dtype=np.int64)
         check(self._L.asl_debug_refit(self._h, int(reps), buf.ctypes.data, len(buf)))
         return buf
+
+    def debug_dedup(self, dets, keys, n_frames, cap_per_frame=1024):
+        """asl_debug_dedup: the de-duplication stage alone on DET_DTYPE records and their uint64 cluster keys (low 48 bits) ->
+        (survivors in device order, (n_frames,) int32 counts, int64[3]: survivors, records past a full list, frames above 1024)."""
+        d = np.ascontiguousarray(dets, dtype=DET_DTYPE).ravel()
+        k = np.ascontiguousarray(keys, dtype=np.uint64).ravel()
+        if len(k) != len(d):
+            raise ValueError("one key per record")
+        out = np.zeros(max(len(d), 1), dtype=DET_DTYPE)
+        npf = np.zeros(max(int(n_frames), 1), dtype=np.int32)
+        cnt = np.zeros(3, dtype=np.int64)
+        check(self._L.asl_debug_dedup(self._h, d.ctypes.data, k.ctypes.data, len(d), int(n_frames), int(cap_per_frame), out.ctypes.data,
+                                      len(out), npf.ctypes.data, cnt.ctypes.data, len(cnt)))
+        return out[:int(cnt[0])], npf, cnt
 
     def debug_division_check(self, exponent_limit=100):
         """(pairs, mismatches) of div_by(a, recip_of(d)) against a / d on the device, exponents within +-exponent_limit."""

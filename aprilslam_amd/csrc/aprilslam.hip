@@ -451,6 +451,29 @@ static int ensure_workspace(asl_detector *d, const Geom &g)
         }                                                                  \
     } while (0)
 
+// S8 (k_dedup.inc): the four launches of the de-duplication over B frames.  enqueue_detect and asl_debug_dedup both come
+// through here, so the diagnostic runs the product's launch shapes.  frame_ndets must be zero and counters[CNT_NDETS]
+// hold the number of records when the first kernel starts.
+struct S8Buffers {
+    const DetRec *dets;
+    long long *counters;
+    unsigned int max_dets;   // records dets holds; out_det / out_pose hold as many
+    unsigned int *frame_ndets, *frame_idx;
+    unsigned int cap_f;      // entries of frame_idx per frame
+    unsigned int *frame_nkeep, *frame_off;
+    DetOut *out_det;
+    PoseOut *out_pose;       // not written without poses
+};
+static void launch_dedup(const S8Buffers &b, unsigned int B, int with_pose, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_det_bucket, dim3((b.max_dets + 255) / 256), dim3(256), 0, st, b.dets, b.counters, b.max_dets, b.frame_ndets, b.frame_idx, b.cap_f,
+                       b.counters);
+    hipLaunchKernelGGL(k_det_dedup, dim3(B), dim3(256), 0, st, b.dets, b.counters, b.frame_ndets, b.frame_idx, b.cap_f, b.frame_nkeep, b.counters);
+    hipLaunchKernelGGL(k_det_offsets, dim3(1), dim3(1024), 0, st, b.frame_nkeep, B, b.frame_off, b.counters);
+    hipLaunchKernelGGL(k_det_gather, dim3((b.cap_f + 255) / 256, B), dim3(256), 0, st, b.dets, b.frame_idx, b.cap_f, b.frame_nkeep, b.frame_off, b.out_det,
+                       b.out_pose, b.max_dets, with_pose);
+}
+
 // tag width in decimated pixels, at least 3 (the quad fit and its finish)
 static int tag_width(const asl_detector *d, const Geom &g) { return std::max(3, d->fam.width_at_border / g.f); }
 
@@ -597,16 +620,9 @@ static int enqueue_detect(asl_detector *d, const uint8_t *d_frames, const Geom &
     }
     // ---- S8: de-duplicate, order by id, lay out the results
     STAGE("k_det_dedup");
-    {
-        const unsigned int cap_f = d->dets_per_frame;
-        hipLaunchKernelGGL(k_det_bucket, dim3((d->max_dets + 255) / 256), dim3(256), 0, st, d->dets.p, d->counters.p, d->max_dets, d->frame_ndets.p,
-                           d->frame_idx.p, cap_f, d->counters.p);
-        hipLaunchKernelGGL(k_det_dedup, dim3(B), dim3(256), 0, st, d->dets.p, d->counters.p, d->frame_ndets.p, d->frame_idx.p, cap_f,
-                           d->frame_nkeep.p, d->counters.p);
-        hipLaunchKernelGGL(k_det_offsets, dim3(1), dim3(1024), 0, st, d->frame_nkeep.p, B, d->frame_off.p, d->counters.p);
-        hipLaunchKernelGGL(k_det_gather, dim3((cap_f + 255) / 256, B), dim3(256), 0, st, d->dets.p, d->frame_idx.p, cap_f, d->frame_nkeep.p,
-                           d->frame_off.p, d->out_det.p, d->out_pose.p, d->max_dets, cam ? 1 : 0);
-    }
+    launch_dedup(S8Buffers{d->dets.p, d->counters.p, d->max_dets, d->frame_ndets.p, d->frame_idx.p, d->dets_per_frame, d->frame_nkeep.p, d->frame_off.p,
+                           d->out_det.p, d->out_pose.p},
+                 B, cam ? 1 : 0, st);
     range_pop();
     if (d->profiling && d->nev <= MAX_STAGES) HIPCHK(hipEventRecord(d->ev[d->nev], st));
     HIPCHK(hipGetLastError());

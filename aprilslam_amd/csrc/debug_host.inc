@@ -1,5 +1,6 @@
 // Host side of the diagnostics (device side: k_seg_debug_* in k_seg.inc, k_div_check below): asl_debug_fetch, the quad-fit
-// refit, the division check and the phase counters; each checks the room it may write into before it writes anything.
+// refit, the de-duplication of given records, the division check and the phase counters; each checks the room it may write
+// into before it writes anything.
 
 // asl_debug_division_check: div_by(a, recip_of(d)) (asl_common.h) against a / d, as compiled into this library: log-uniform
 // magnitudes with exponents within +-lim, both signs, a = 0 now and then
@@ -172,6 +173,60 @@ extern "C" int asl_debug_refit(asl_detector *d, int reps, int64_t *out, size_t n
         }
     }
     out[0] = reps;
+    return ASL_OK;
+}
+
+// S8 (k_dedup.inc) on the caller's records, through launch_dedup as a batch runs it, in device buffers of this call's own
+// (freed on every path: DevBuf); the detector gives the device only.  One run, no growth: the counters say what a batch's
+// host loop would have acted on.
+extern "C" int asl_debug_dedup(asl_detector *d, const asl_detection *dets, const uint64_t *keys, int n, int n_frames, int cap_per_frame,
+                               asl_detection *out, int max_out, int *n_per_frame, int64_t *counters, size_t n_counters)
+{
+    if (!d || !dets || !keys || !out || !n_per_frame || !counters) return fail(ASL_EINVAL, "NULL argument");
+    if (n < 0) return fail(ASL_EINVAL, "n must be >= 0 (got %d)", n);
+    if (n_frames < 1 || n_frames > 65535) return fail(ASL_EINVAL, "n_frames must be in [1, 65535] (got %d)", n_frames);
+    if (cap_per_frame < 1) return fail(ASL_EINVAL, "cap_per_frame must be >= 1 (got %d)", cap_per_frame);
+    if (max_out < n) return fail(ASL_EINVAL, "out too small: need %d records (got %d)", n, max_out);
+    if (n_counters < 3) return fail(ASL_EINVAL, "counters too small: need 3 values (got %zu)", n_counters);
+    if (d->pending) return fail(ASL_EINVAL, "a batch is in flight on this detector");
+    for (int i = 0; i < n; i++)
+        if (dets[i].frame < 0 || dets[i].frame >= n_frames)
+            return fail(ASL_EINVAL, "record %d: frame %d is outside [0, %d)", i, dets[i].frame, n_frames);
+    HIPCHK(hipSetDevice(d->device));
+    const size_t B = (size_t)n_frames, nrec = (size_t)std::max(n, 1);
+    std::vector<DetRec> h_recs(nrec);
+    memset(h_recs.data(), 0, nrec * sizeof(DetRec));
+    for (int i = 0; i < n; i++) {
+        DetRec &r = h_recs[i];
+        r.id = dets[i].id; r.hamming = dets[i].hamming; r.margin = dets[i].margin; r.frame = dets[i].frame;
+        memcpy(r.center, dets[i].center, sizeof r.center);
+        memcpy(r.corners, dets[i].corners, sizeof r.corners);
+        r.key = ((uint64_t)dets[i].frame << 48) | (keys[i] & 0xFFFFFFFFFFFFull);  // a cluster key: the frame above 48 bits
+    }
+    DevBuf<DetRec> d_recs;
+    DevBuf<long long> d_cnt;
+    DevBuf<unsigned int> d_ndets, d_idx, d_nkeep, d_off;
+    DevBuf<DetOut> d_out;
+    if (d_recs.ensure(nrec) || d_cnt.ensure(CNT__N) || d_ndets.ensure(B) || d_idx.ensure(B * (size_t)cap_per_frame) || d_nkeep.ensure(B) ||
+        d_off.ensure(B) || d_out.ensure(nrec))
+        return fail(ASL_ENOMEM, "debug buffer allocation failed (%d records, %d frames of %d)", n, n_frames, cap_per_frame);
+    std::vector<long long> h_cnt(CNT__N, 0);
+    h_cnt[CNT_NDETS] = n;
+    HIPCHK(hipMemcpy(d_recs.p, h_recs.data(), nrec * sizeof(DetRec), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_cnt.p, h_cnt.data(), sizeof(long long) * CNT__N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_ndets.p, 0, B * sizeof(unsigned int)));
+    launch_dedup(S8Buffers{d_recs.p, d_cnt.p, (unsigned int)nrec, d_ndets.p, d_idx.p, (unsigned int)cap_per_frame, d_nkeep.p, d_off.p, d_out.p, nullptr},
+                 (unsigned int)B, 0, nullptr);
+    HIPCHK(hipGetLastError());
+    std::vector<unsigned int> h_nkeep(B);
+    HIPCHK(hipMemcpy(h_cnt.data(), d_cnt.p, sizeof(long long) * CNT__N, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h_nkeep.data(), d_nkeep.p, B * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    const long long nkeep = h_cnt[CNT_NKEEP];
+    if (nkeep < 0 || nkeep > (long long)n) return fail(ASL_EDEVICE, "the de-duplication kept %lld of %d records", nkeep, n);
+    static_assert(sizeof(DetOut) == sizeof(asl_detection), "device results are copied verbatim");
+    if (nkeep) HIPCHK(hipMemcpy(out, d_out.p, (size_t)nkeep * sizeof(DetOut), hipMemcpyDeviceToHost));
+    for (size_t f = 0; f < B; f++) n_per_frame[f] = (int)h_nkeep[f];
+    counters[0] = nkeep; counters[1] = h_cnt[CNT_OVERFLOW_DETS]; counters[2] = h_cnt[CNT_DEDUP_LIMIT];
     return ASL_OK;
 }
 

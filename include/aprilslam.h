@@ -576,7 +576,7 @@ int asl_rectify_u8(asl_detector *det, const uint8_t *src, int channels, int w, i
 /* ---- introspection and diagnostics.  asl_debug_fetch, asl_stage_times and the counters (item 5) describe the LAST batch
    the detector ran.  asl_detect_batch_u8 and asl_detect_batch_pose_u8 run a call of 128 frames or more as consecutive
    batches of 64 frames, so after such a call that is the call's last chunk (frames 128..149 of a 150-frame call), not the
-   whole call.  asl_debug_fetch, asl_debug_refit, asl_debug_division_check and asl_debug_phase_cycles are told the room
+   whole call.  asl_debug_fetch, asl_debug_refit, asl_debug_dedup, asl_debug_division_check and asl_debug_phase_cycles are told the room
    they may write into and return ASL_EINVAL, writing nothing, when it is too small; asl_stage_times fills at most max_n. */
 
 /* Copy an intermediate buffer of the last batch to host, for the parity tests.
@@ -602,6 +602,19 @@ int asl_debug_fetch(asl_detector *det, int what, void *dst, size_t bytes, size_t
    run would not see the same input.  out (n_out >= 7) = {repetitions, quads that differ from the first repetition, those
    by size class 0-4}; any difference is a race.  Fails if a batch is pending or the last batch had no clusters. */
 int asl_debug_refit(asl_detector *det, int reps, int64_t *out, size_t n_out);
+/* Diagnostic: the de-duplication stage (S8) alone on n records of the caller's, through the launches a batch uses.  dets[i]
+   is one decoded tag of frame dets[i].frame in [0, n_frames) and keys[i] its cluster key, of which the low 48 bits count:
+   within a frame the stage walks the records in ascending key order, whatever their order in memory (keys of one frame
+   should differ).  cap_per_frame is the room of a frame's list, the capacity a batch grows on overflow; nothing grows
+   here.  out (max_out >= n records) receives the survivors frame by frame, inside a frame by (id, hamming, corners), as a
+   detect call returns them; n_per_frame (n_frames values) their counts; counters (n_counters >= 3) = {survivors, records
+   that found their frame's list full, frames with more than 1024 records}.  A full list empties every frame and a frame
+   above 1024 records is empty itself, as in a batch, which then grows and runs again or fails.  Synchronous; works in
+   device buffers of its own, so the detector's workspace and the last batch's results and counters stay as they were.
+   ASL_EINVAL, nothing written: a NULL pointer, n < 0, n_frames outside [1, 65535], cap_per_frame < 1, a frame index out
+   of range, max_out < n, n_counters < 3, a batch pending. */
+int asl_debug_dedup(asl_detector *det, const asl_detection *dets, const uint64_t *keys, int n, int n_frames, int cap_per_frame,
+                    asl_detection *out, int max_out, int *n_per_frame, int64_t *counters, size_t n_counters);
 /* Diagnostic: the shared-reciprocal division of the line fits (asl_common.h) against the compiler's on 2^29 random operand
    pairs with exponents within +-exponent_limit (in [1, 900]).  out (n_out >= 2) = {pairs, mismatches}. */
 int asl_debug_division_check(asl_detector *det, int exponent_limit, int64_t *out, size_t n_out);

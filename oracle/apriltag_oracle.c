@@ -893,6 +893,8 @@ static int dedup_and_sort(aso_detection *d, int n)
     return n;
 }
 
+int aso_dedup_and_sort(aso_detection *d, int n) { return dedup_and_sort(d, n); }
+
 /* ---------------------------------------------------------- full detector */
 int aso_detect_gray(const uint8_t *gray, int w, int h, int stride, const aso_family *fam,
                     const aso_params *prm, aso_detection *out, int cap)

@@ -104,6 +104,9 @@ void aso_refine_edges(const uint8_t *gray, int w, int h, int stride, int decimat
 /* S7: homography + decode one quad; returns 1 and fills det on success */
 int aso_decode_quad(const uint8_t *gray, int w, int h, int stride, const aso_family *fam, int maxhamming,
                     const aso_quad *q, aso_detection *det);
+/* S8 alone: upstream's elimination loop over d[0..n) in the order given (the order of decoding), then the sort by
+   (id, hamming, corners), in place; returns the number kept */
+int aso_dedup_and_sort(aso_detection *d, int n);
 /* full detector (S1..S8) on a gray image; detections sorted by id */
 int aso_detect_gray(const uint8_t *gray, int w, int h, int stride, const aso_family *fam,
                     const aso_params *prm, aso_detection *out, int cap);

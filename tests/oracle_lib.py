@@ -53,6 +53,7 @@ def lib():
         L.aso_fit_quads.restype = C.c_int
         L.aso_decode_quad.restype = C.c_int
         L.aso_quad_maxima.restype = C.c_long
+        L.aso_dedup_and_sort.restype = C.c_int
         _lib = L
     return _lib
 
@@ -167,6 +168,16 @@ def detect_bgr(bgr, fam, decimate_f=2, maxhamming=1, refine_edges=1, cap=1024):
     out = (AsoDetection * cap)()
     n = lib().aso_detect_bgr(_u8(bgr), w, h, w * 3, C.byref(F.c), C.byref(prm), out, cap)
     return _dets(out, n)
+
+
+def dedup_and_sort(recs):
+    """S8 alone (aso_dedup_and_sort) on 96-byte detection records (aso_detection's layout, e.g. _lib.DET_DTYPE) in the
+    order of decoding; returns the records kept, sorted by (id, hamming, corners), as a new array of the same dtype."""
+    a = np.array(recs, copy=True, order="C").ravel()
+    assert a.dtype.itemsize == C.sizeof(AsoDetection)
+    n = lib().aso_dedup_and_sort(a.ctypes.data_as(C.POINTER(AsoDetection)), len(a))
+    assert 0 <= n <= len(a)
+    return a[:n].copy()
 
 
 def solve_pnp(corners, K, dist, tag_size):
