@@ -6,8 +6,8 @@
 // asl_smooth_robust_sequences_* (huber_px > 0): the same launches with k_smooth_cand<true> and k_smooth_lin<true>, which put every
 // corner's pixel residual through a Huber loss (loc_corner<NE, true>, k_localize.inc): its cost in every place the squared
 // one stands, its weight on J^T J and J^T r, and per frame the number of slots with a corner over the threshold, carried
-// with the state (SmoothSet.soft) as the pixel cost is.  tests/smooth_robust_ref.py states it.  The plain calls run the
-// <false> instantiations: the code they ran before, the counts 0.
+// with the state (SmoothSet.soft) as the pixel cost is.  tests/smooth_ref.py states it at huber_px > 0.  The plain calls run
+// the <false> instantiations: the code they ran before, the counts 0.
 //   seed chain   k_smooth_cand   one wavefront per frame: the seed's pose A and, for a frame of exactly one taking-part slot,
 //                                its mirrored planar minimum B (loc_candidate), both costed over the frame's corners
 //                k_smooth_scan   one wavefront a sequence: the nearest posed frame at or before every frame (wave_scan of a maximum)
@@ -19,13 +19,14 @@
 //   per trial    k_smooth_lin    one wavefront per frame: the pose (stepped by delta), the frame's cost, H and g from its
 //                                corners (loc_gather, loc_pass), and the motion blocks of the pair (f, f + 1), a lane an entry
 //                k_smooth_solve  one wavefront a sequence: the block-tridiagonal Cholesky forward and back over the frames, the 6x6
-//                                block spread over 36 lanes with its operands in LDS
-//                k_smooth_decide one workgroup a sequence: the trial's cost in a fixed order, the accept rule, lambda, the stop
-//                k_smooth_commit the accepted trials copied over the current state, spread over the device
+//                                block spread over 36 lanes with its operands in LDS (forward step: smooth_chol6, smooth_couple)
+//                k_smooth_decide one workgroup a sequence: the trial's cost in a fixed order (smooth_sums), the accept rule, lambda, the stop
+//                k_smooth_commit the accepted trials copied over the current state (smooth_set_at), spread over the device
 //   end          k_smooth_finish one thread per frame: the records (n_rejected: the frame's soft slots; n_soft: lm[SM_SOFT], their
 //                                sum over the sequence by k_smooth_init / k_smooth_decide's fixed-order sums)
 //   covariance   k_smooth_cov    (asl_smooth_cov_*, only when asked for) one wavefront a sequence: the undamped block Cholesky of the
-//                                returned state forward, the diagonal blocks of the inverse back, a 6x6 block from frame to frame
+//                                returned state forward (the solve's forward step under its own pivot rule), the diagonal blocks of
+//                                the inverse back, a 6x6 block from frame to frame
 //                k_smooth_cov_finish  one thread per frame: sigma_px, dof, status, and the zeros of a status 1 / 2
 // Several sequences per call (asl_smooth_sequences_*): sequence k is the frames [seq[k], seq[k + 1]) of the call's, with its own
 // lm[SM__N] and head[SMH__N]; no term links two sequences.  The chain kernels and the per-sequence sums run one workgroup per
@@ -44,19 +45,31 @@ struct SmoothResultRec {  // == asl_smooth_result, 64 bytes
 enum { SM_COST = 0, SM_LAMBDA, SM_STOP, SM_ITERS, SM_STATUS, SM_COST0, SM_SOLVED, SM_PIX, SM_PIX0, SM_CORNERS, SM_NDATA, SM_TAKE, SM_COV, SM_SOFT, SM__N = 16 };
 enum { SMH_NPOSED = 0, SMH_FIRST, SMH_FAIL, SMH_NFLIP, SMH__N = 4 };
 #define SM_MOT 121                // per pair: QN 36, QP 36, C 36, gN 6, gP 6, |m|^2
-#define SM_SET (12 + 27 + 2 + SM_MOT)  // doubles per frame of one state: pose, normal equations, pixel cost, soft slots, motion blocks
+// One state's arrays, in doubles per frame from the start of the allocation: pose (R 9, t 3), packed normal equations
+// (21 + 6), pixel cost, soft slots, motion blocks.  smooth_set() and smooth_set_at() are the two readings of this layout.
+enum { SMS_POSE = 0, SMS_NE = 12, SMS_PIX = 39, SMS_SOFT = 40, SMS_MOT = 41 };
+#define SM_SET (SMS_MOT + SM_MOT)  // doubles per frame of one state
 #define SM_FAC 84                 // per frame of the factorisation: L 36, M 36, 1 / diag 6, y 6 (k_smooth_cov: the undamped one, no y)
 #define SM_WG 256
 
-// One state of the solve over n frames, one allocation: poses (R 9, t 3), packed normal equations (21 + 6), pixel costs,
-// soft-slot counts (the robust call's; 0 from the plain ones), motion blocks of the pairs (f, f + 1)
+// One state of the solve over n frames, one allocation (soft slots: the robust call's, 0 from the plain ones; motion blocks:
+// of the pairs (f, f + 1))
 struct SmoothSet {
     double *P, *ne, *c, *soft, *mot;
 };
 
 __host__ __device__ inline SmoothSet smooth_set(double *base, size_t n)
 {
-    return {base, base + 12 * n, base + 39 * n, base + 40 * n, base + 41 * n};
+    return {base + SMS_POSE * n, base + SMS_NE * n, base + SMS_PIX * n, base + SMS_SOFT * n, base + SMS_MOT * n};
+}
+
+// Entry e (0 <= e < SM_SET) of frame f in a state of n frames: the index from the allocation's start
+__host__ __device__ inline size_t smooth_set_at(int e, size_t f, size_t n)
+{
+    if (e < SMS_NE) return SMS_POSE * n + (SMS_NE - SMS_POSE) * f + (e - SMS_POSE);
+    if (e < SMS_PIX) return SMS_NE * n + (SMS_PIX - SMS_NE) * f + (e - SMS_NE);
+    if (e < SMS_MOT) return (size_t)e * n + f;   // pixel cost, soft slots: one double a frame each
+    return SMS_MOT * n + SM_MOT * f + (e - SMS_MOT);
 }
 
 struct SmoothBufs {
@@ -179,6 +192,30 @@ __device__ __forceinline__ double smooth_block_sum(double v, double *sh)
         __syncthreads();
     }
     return sh[0];
+}
+
+// A sequence's sums over a state, each in smooth_block_sum's fixed order and in every thread: the cost (pixel costs w + the
+// pairs' |m|^2), the pixel cost, the soft slots.  frame(f, c): what else the caller does with frame f and its pixel cost c.
+struct SmoothSums {
+    double cost, pix, soft;
+};
+
+template <class Frame>
+__device__ __forceinline__ SmoothSums smooth_sums(const SmoothSet &s, const SmoothSeq &q, double w, double *sh, Frame frame)
+{
+    double cost = 0, pix = 0, soft = 0;
+    for (int lf = (int)threadIdx.x; lf < q.n; lf += SM_WG) {
+        const int f = q.f0 + lf;
+        const double c = s.c[f];
+        frame(f, c);
+        soft += s.soft[f];
+        cost += c * w + (lf + 1 < q.n ? s.mot[SM_MOT * (size_t)f + 120] : 0.0);
+        pix += c;
+    }
+    cost = smooth_block_sum(cost, sh);
+    pix = smooth_block_sum(pix, sh);
+    soft = smooth_block_sum(soft, sh);
+    return {cost, pix, soft};
 }
 
 // Candidates of one frame and their data costs; ROBUST: under the Huber loss of threshold hk pixels (loc_corner), as every
@@ -479,22 +516,15 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_init(SmoothBufs b, double w)
         return;
     }
     const SmoothSet s = smooth_set(b.set[0], (size_t)b.n);
-    double cost = 0, pix = 0, corners = 0, ndata = 0, soft = 0;
-    for (int lf = tid; lf < q.n; lf += SM_WG) {
-        const int f = q.f0 + lf;
-        const double c = s.c[f];
+    double corners = 0, ndata = 0;
+    const SmoothSums sum = smooth_sums(s, q, w, sh, [&](int f, double c) {
         b.cseed[f] = c;
-        soft += s.soft[f];
-        cost += c * w + (lf + 1 < q.n ? s.mot[SM_MOT * (size_t)f + 120] : 0.0);
-        pix += c;
         corners += 4.0 * b.ntags[f];
         ndata += b.ntags[f] > 0 ? 1.0 : 0.0;
-    }
-    cost = smooth_block_sum(cost, sh);
-    pix = smooth_block_sum(pix, sh);
+    });
+    const double cost = sum.cost, pix = sum.pix, soft = sum.soft;
     corners = smooth_block_sum(corners, sh);
     ndata = smooth_block_sum(ndata, sh);
-    soft = smooth_block_sum(soft, sh);
     if (tid == 0) {
         const bool bad = !isfinite(cost);
         lm[SM_COST] = cost; lm[SM_COST0] = cost; lm[SM_PIX] = pix; lm[SM_PIX0] = pix; lm[SM_CORNERS] = corners; lm[SM_NDATA] = ndata;
@@ -505,11 +535,69 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_init(SmoothBufs b, double w)
     }
 }
 
+// The forward step both k_smooth_solve and k_smooth_cov take at a frame, S = S_f in LDS, lane 6 i + j its entry (i, j).
+// smooth_chol6: the right-looking Cholesky of S in place (every entry loses its products in the order k = 0, 1, ..., as
+// chol6_solve_tri_dev's do), 1 / diagonal in inv in every lane.  pivot(p, c): whether pivot p of column c passes; returns
+// whether all six did, the same LDS words in every lane, so one value in the whole wavefront.  No exit at a failed pivot:
+// the columns after it work on a spoilt block, which the caller, who then writes its flag and leaves, never reads.
+template <class Pivot>
+__device__ __forceinline__ bool smooth_chol6(double *S, int lane, int i, int j, double *inv, Pivot pivot)
+{
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+        const double p = S[7 * c];
+        ok &= pivot(p, c);
+        const double dc = sqrt(p);
+        inv[c] = 1.0 / dc;
+        __syncthreads();
+        if (lane < 36 && j == c) {
+            if (i == c) S[lane] = dc;
+            else if (i > c) S[lane] = S[lane] * inv[c];
+        }
+        __syncthreads();
+        if (lane < 36 && j > c && i >= j) S[lane] = S[lane] - S[6 * i + c] * S[6 * j + c];
+        __syncthreads();
+    }
+    return ok;
+}
+
+// smooth_couple: row `lane` of M_f = C_f L_f^-T from the factored S (pair: frame f has a successor; C: C_f, row-major),
+// then L, 1 / diag, M (and the solve's y, if any) into the frame's fac and M_f into Mp for the next frame: every load
+// ahead of the first store
+__device__ __forceinline__ void smooth_couple(const double *S, const double *inv, const double *y, const double *C, bool pair, int lane, int i,
+                                              int j, double *Mp, double *fac)
+{
+    double Mr[6] = {0, 0, 0, 0, 0, 0};
+    if (pair && lane < 6) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) {
+            double t = C[6 * lane + c];
+#pragma unroll
+            for (int k = 0; k < c; k++) t -= Mr[k] * S[6 * c + k];
+            Mr[c] = t * inv[c];
+        }
+    }
+    __syncthreads();
+    if (lane == 0) {
+#pragma unroll
+        for (int a = 0; a < 6; a++) {
+            fac[72 + a] = inv[a];
+            if (y) fac[78 + a] = y[a];
+        }
+    }
+    if (lane < 36) fac[lane] = i >= j ? S[lane] : 0.0;
+    if (pair && lane < 6) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) { Mp[6 * lane + c] = Mr[c]; fac[36 + 6 * lane + c] = Mr[c]; }
+    }
+    __syncthreads();
+}
+
 // (A + lambda diag(A)) delta = -g, A block tridiagonal: forward S_f = A_ff (damped) - M_{f-1} M_{f-1}^T = L_f L_f^T,
 // L_f y_f = -g_f - M_{f-1} y_{f-1}, M_f = C_f L_f^-T; back L_f^T x_f = y_f - M_f^T x_{f+1}.  Lane 6 i + j holds entry (i, j)
-// of the block on its way through the right-looking Cholesky (every entry loses its products in the order k = 0, 1, ...,
-// as chol6_solve_tri_dev's do); the triangular solves of six numbers run in every lane on the same LDS operands.  A pivot
-// that is not positive sets head[SMH_FAIL] and ends the kernel.
+// of the block on its way through smooth_chol6; the triangular solves of six numbers run in every lane on the same LDS
+// operands.  A pivot that is not positive sets head[SMH_FAIL] and ends the kernel.
 __global__ void __launch_bounds__(64) k_smooth_solve(SmoothBufs b, double w)
 {
     __shared__ double S[36], Mp[36], yv[6], rr[6], iv[6];
@@ -519,9 +607,11 @@ __global__ void __launch_bounds__(64) k_smooth_solve(SmoothBufs b, double w)
     const int lane = (int)threadIdx.x, n = q.n, i = lane / 6, j = lane % 6;
     const double lambda = lm[SM_LAMBDA];
     const SmoothSet s = smooth_set(b.set[0], (size_t)b.n);
-    // f: the frame counted from the sequence's first; the buffers are indexed by the call's frame q.f0 + f
+    // from here on at the sequence's first frame: f counts from it, and the addresses advance by constants
+    const double *nes = s.ne + 27 * (size_t)q.f0, *mots = s.mot + SM_MOT * (size_t)q.f0;
+    double *facs = b.fac + SM_FAC * (size_t)q.f0, *delta = b.delta + 6 * (size_t)q.f0;
     for (int f = 0; f < n; f++) {
-        const double *ne = s.ne + 27 * (size_t)(q.f0 + f), *mot = s.mot + SM_MOT * (size_t)(q.f0 + f), *motp = mot - SM_MOT;
+        const double *ne = nes + 27 * (size_t)f, *mot = mots + SM_MOT * (size_t)f, *motp = mot - SM_MOT;
         double v = 0;
         if (lane < 36) {
             v = ne[i >= j ? TRI(i, j) : TRI(j, i)] * w;
@@ -544,23 +634,9 @@ __global__ void __launch_bounds__(64) k_smooth_solve(SmoothBufs b, double w)
         else if (lane < 42) rr[lane - 36] = v;
         __syncthreads();
         double inv[6];
-#pragma unroll
-        for (int c = 0; c < 6; c++) {
-            const double p = S[7 * c];
-            if (!(p > 0)) {  // the same LDS word in every lane: the whole wavefront leaves
-                if (lane == 0) b.head[SMH__N * q.k + SMH_FAIL] = 1;
-                return;
-            }
-            const double dc = sqrt(p);
-            inv[c] = 1.0 / dc;
-            __syncthreads();
-            if (lane < 36 && j == c) {
-                if (i == c) S[lane] = dc;
-                else if (i > c) S[lane] = S[lane] * inv[c];
-            }
-            __syncthreads();
-            if (lane < 36 && j > c && i >= j) S[lane] = S[lane] - S[6 * i + c] * S[6 * j + c];
-            __syncthreads();
+        if (!smooth_chol6(S, lane, i, j, inv, [](double p, int) { return p > 0; })) {
+            if (lane == 0) b.head[SMH__N * q.k + SMH_FAIL] = 1;
+            return;
         }
         double y[6];
 #pragma unroll
@@ -570,33 +646,16 @@ __global__ void __launch_bounds__(64) k_smooth_solve(SmoothBufs b, double w)
             for (int k = 0; k < a; k++) t -= S[6 * a + k] * y[k];
             y[a] = t * inv[a];
         }
-        double Mr[6] = {0, 0, 0, 0, 0, 0};
-        if (f + 1 < n && lane < 6) {  // row `lane` of M_f = C_f L_f^-T
+        if (lane == 0) {  // read again only at the top of the next frame, after smooth_couple's barriers
 #pragma unroll
-            for (int c = 0; c < 6; c++) {
-                double t = mot[72 + 6 * lane + c];
-#pragma unroll
-                for (int k = 0; k < c; k++) t -= Mr[k] * S[6 * c + k];
-                Mr[c] = t * inv[c];
-            }
+            for (int a = 0; a < 6; a++) yv[a] = y[a];
         }
-        __syncthreads();
-        double *fac = b.fac + SM_FAC * (size_t)(q.f0 + f);
-        if (lane == 0) {
-#pragma unroll
-            for (int a = 0; a < 6; a++) { yv[a] = y[a]; fac[72 + a] = inv[a]; fac[78 + a] = y[a]; }
-        }
-        if (lane < 36) fac[lane] = i >= j ? S[lane] : 0.0;
-        if (f + 1 < n && lane < 6) {
-#pragma unroll
-            for (int c = 0; c < 6; c++) { Mp[6 * lane + c] = Mr[c]; fac[36 + 6 * lane + c] = Mr[c]; }
-        }
-        __syncthreads();
+        smooth_couple(S, inv, y, mot + 72, f + 1 < n, lane, i, j, Mp, facs + SM_FAC * (size_t)f);
     }
     __threadfence();  // fac: written by some lanes, read by others below
     double x[6] = {0, 0, 0, 0, 0, 0};
     for (int f = n - 1; f >= 0; f--) {
-        const double *fac = b.fac + SM_FAC * (size_t)(q.f0 + f);   // written above by this wavefront
+        const double *fac = facs + SM_FAC * (size_t)f;   // written above by this wavefront
         __syncthreads();
         if (lane < 36) { S[lane] = fac[lane]; Mp[lane] = f + 1 < n ? fac[36 + lane] : 0.0; }
         if (lane < 6) { iv[lane] = fac[72 + lane]; yv[lane] = fac[78 + lane]; }
@@ -622,7 +681,7 @@ __global__ void __launch_bounds__(64) k_smooth_solve(SmoothBufs b, double w)
         for (int a = 0; a < 6; a++) x[a] = xn[a];
         if (lane == 0) {
 #pragma unroll
-            for (int a = 0; a < 6; a++) b.delta[6 * (size_t)(q.f0 + f) + a] = x[a];
+            for (int a = 0; a < 6; a++) delta[6 * (size_t)f + a] = x[a];
         }
     }
 }
@@ -646,18 +705,8 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_decide(SmoothBufs b, double w)
         if (tid == 0) { lm[SM_ITERS] += 1.0; lm[SM_LAMBDA] *= 10.0; lm[SM_TAKE] = 0.0; head[SMH_FAIL] = 0; }
         return;
     }
-    const SmoothSet t = smooth_set(b.set[1], (size_t)b.n);
-    double cn = 0, pix = 0, soft = 0;
-    for (int lf = tid; lf < q.n; lf += SM_WG) {
-        const int f = q.f0 + lf;
-        const double c = t.c[f];
-        soft += t.soft[f];
-        cn += c * w + (lf + 1 < q.n ? t.mot[SM_MOT * (size_t)f + 120] : 0.0);
-        pix += c;
-    }
-    cn = smooth_block_sum(cn, sh);
-    pix = smooth_block_sum(pix, sh);
-    soft = smooth_block_sum(soft, sh);
+    const SmoothSums sum = smooth_sums(smooth_set(b.set[1], (size_t)b.n), q, w, sh, [](int, double) {});
+    const double cn = sum.cost, pix = sum.pix, soft = sum.soft;
     const bool take = cn < cost;
     if (tid == 0) {
         lm[SM_ITERS] += 1.0;
@@ -683,7 +732,7 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_commit(SmoothBufs b)
     const int e = (int)threadIdx.x;
     for (size_t f = blockIdx.x; f < n; f += gridDim.x) {
         if (e >= SM_SET || b.lm[SM__N * smooth_seq_of_uniform(b, (int)f).k + SM_TAKE] == 0.0) continue;
-        const size_t at = e < 12 ? 12 * f + e : e < 39 ? 12 * n + 27 * f + (e - 12) : e < 41 ? (size_t)e * n + f : 41 * n + SM_MOT * f + (e - 41);
+        const size_t at = smooth_set_at(e, f, n);
         b.set[0][at] = b.set[1][at];
     }
 }
@@ -763,6 +812,7 @@ __global__ void __launch_bounds__(64) k_smooth_cov(SmoothBufs b, double w, PoseC
         h = s.ne[tri];
         if (n > 1) { qn = s.mot[lane]; cc = s.mot[72 + lane]; }
     }
+#pragma clang loop unroll(disable)   // nor peeled: one copy of the frame's body, not a second one for f = 0
     for (int f = 0; f < n; f++) {
         double v = 0;
         if (lane < 36) {
@@ -788,46 +838,11 @@ __global__ void __launch_bounds__(64) k_smooth_cov(SmoothBufs b, double w, PoseC
         }
         __syncthreads();
         double inv[6];
-#pragma unroll
-        for (int c = 0; c < 6; c++) {
-            const double p = S[7 * c];
-            if (!(p > 0 && p > POSE_COV_PIVOT_TOL * dg[c])) {  // the same LDS words in every lane: the whole wavefront leaves
-                if (lane == 0) lm[SM_COV] = 2.0;
-                return;
-            }
-            const double dc = sqrt(p);
-            inv[c] = 1.0 / dc;
-            __syncthreads();
-            if (lane < 36 && j == c) {
-                if (i == c) S[lane] = dc;
-                else if (i > c) S[lane] = S[lane] * inv[c];
-            }
-            __syncthreads();
-            if (lane < 36 && j > c && i >= j) S[lane] = S[lane] - S[6 * i + c] * S[6 * j + c];
-            __syncthreads();
+        if (!smooth_chol6(S, lane, i, j, inv, [&](double p, int c) { return p > 0 && p > POSE_COV_PIVOT_TOL * dg[c]; })) {
+            if (lane == 0) lm[SM_COV] = 2.0;
+            return;
         }
-        double Mr[6] = {0, 0, 0, 0, 0, 0};
-        if (f + 1 < n && lane < 6) {  // row `lane` of M_f = C_f L_f^-T
-#pragma unroll
-            for (int c = 0; c < 6; c++) {
-                double t = Cs[6 * lane + c];
-#pragma unroll
-                for (int k = 0; k < c; k++) t -= Mr[k] * S[6 * c + k];
-                Mr[c] = t * inv[c];
-            }
-        }
-        __syncthreads();
-        double *fac = facs + SM_FAC * (size_t)f;
-        if (lane < 36) fac[lane] = i >= j ? S[lane] : 0.0;
-        if (lane == 0) {
-#pragma unroll
-            for (int a = 0; a < 6; a++) fac[72 + a] = inv[a];
-        }
-        if (f + 1 < n && lane < 6) {
-#pragma unroll
-            for (int c = 0; c < 6; c++) { Mp[6 * lane + c] = Mr[c]; fac[36 + 6 * lane + c] = Mr[c]; }
-        }
-        __syncthreads();
+        smooth_couple(S, inv, nullptr, Cs, f + 1 < n, lane, i, j, Mp, facs + SM_FAC * (size_t)f);
     }
     __threadfence();  // fac: written by some lanes, read by others below
     if (lane == 0) lm[SM_COV] = 0.0;

@@ -184,8 +184,8 @@ def failure_cases():
             "nonfinite": (obs[1:3], rec, nonfinite, HOLES_SIGMAS, 4, SR.NON_FINITE, 0)}
 
 
-def run(obs, rec, seed, dist, sigmas, reverse=False, max_iters=MAX_ITERS):
-    return SR.smooth(obs, rec, K, dist, TAG, seed, *sigmas, max_iters, reverse=reverse)
+def run(obs, rec, seed, dist, sigmas, reverse=False, max_iters=MAX_ITERS, huber=0.0):
+    return SR.smooth(obs, rec, K, dist, TAG, seed, *sigmas, max_iters, reverse=reverse, huber_px=huber)
 
 
 def pos_err(T, truth):

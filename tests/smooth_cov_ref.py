@@ -6,7 +6,7 @@ sigma_rot and sigma_trans.  So the covariance of the stacked left updates (w, v)
 block-tridiagonal matrix of smooth_ref.Problem.blocks at the returned poses: no sigma^2 factor, no estimate from the
 residuals.  A frame's marginal is the diagonal block Sigma_ff of A^-1 (the other frames are not held fixed).
 
-Block Cholesky as smooth_ref.tridiag_solve with lam = 0: S_f = D_f - M_{f-1} M_{f-1}^T = L_f L_f^T, M_f = C_f L_f^-T, then back
+Block Cholesky by smooth_ref.block_factor, the forward pass of smooth_ref.tridiag_solve, with lam = 0 and no right-hand side: S_f = D_f - M_{f-1} M_{f-1}^T = L_f L_f^T, M_f = C_f L_f^-T, then back
 
     Sigma_{n-1} = L_{n-1}^-T L_{n-1}^-1
     Sigma_f     = L_f^-T (I + M_f^T Sigma_{f+1} M_f) L_f^-1        f = n - 2 ... 0
@@ -30,41 +30,9 @@ import smooth_ref as SR
 from aprilslam_amd._lib import POSE_COV_DTYPE
 
 
-def chol6_checked(S, diag):
-    """smooth_ref.chol6 with the covariance's pivot rule against diag (the undamped D_f's diagonal) -> 1 / diagonal or None"""
-    inv = np.zeros(6)
-    for j in range(6):
-        p = S[j, j]
-        if not (p > 0 and p > PC.PIVOT_TOL * diag[j]):
-            return None
-        S[j, j] = np.sqrt(p)
-        inv[j] = 1.0 / S[j, j]
-        S[j + 1:, j] = S[j + 1:, j] * inv[j]
-        for c in range(j + 1, 6):
-            S[c:, c] = S[c:, c] - S[c:, j] * S[c, j]
-    return inv
-
-
-def factor(D, C):
-    """(L, 1 / diag, M) of the undamped block Cholesky, or None: A is not positive definite"""
-    n = len(D)
-    L, inv, M = np.zeros((n, 6, 6)), np.zeros((n, 6)), np.zeros((n, 6, 6))
-    for f in range(n):
-        S = np.array(D[f], dtype=np.float64)
-        if f:
-            for k in range(6):
-                S = S - np.outer(M[f - 1][:, k], M[f - 1][:, k])
-        iv = chol6_checked(S, np.diag(D[f]))
-        if iv is None:
-            return None
-        L[f], inv[f] = np.tril(S), iv
-        if f + 1 < n:
-            for c in range(6):
-                s = C[f][:, c].copy()
-                for k in range(c):
-                    s = s - M[f][:, k] * L[f, c, k]
-                M[f][:, c] = s * iv[c]
-    return L, inv, M
+def pivot_rule(p, d):
+    """the covariance's pivot rule against d, the undamped D_f's diagonal entry (pose_cov_ref.positive_definite's)"""
+    return p > 0 and p > PC.PIVOT_TOL * d
 
 
 def back_solve(L, iv, b):
@@ -84,10 +52,10 @@ def mirror_lower(Y):
 
 def marginals(D, C):
     """(n, 6, 6) diagonal blocks of A^-1 by the recursion, or None: A is not positive definite"""
-    fac = factor(D, C)
+    fac = SR.block_factor(D, C, pivot=pivot_rule)
     if fac is None:
         return None
-    L, inv, M = fac
+    L, inv, M, _ = fac
     n = len(D)
     Sig = np.zeros((n, 6, 6))
     for f in range(n - 1, -1, -1):
@@ -115,9 +83,10 @@ def to_record_convention(Sigma, R):
     return mirror_lower(Cv)
 
 
-def problem_blocks(obs, tag_map, K, dist, tag_size, poses, sigma_px, sigma_rot, sigma_trans):
-    """(problem, camera<-world poses, D, C) relinearised at the poses of a smooth output"""
-    pb = SR.Problem(np.asarray(obs), tag_map, K, dist, tag_size, sigma_px, sigma_rot, sigma_trans)
+def problem_blocks(obs, tag_map, K, dist, tag_size, poses, sigma_px, sigma_rot, sigma_trans, huber_px=0.0):
+    """(problem, camera<-world poses, D, C) relinearised at the poses of a smooth output (huber_px > 0: the weighted normal
+    equations, a down-weighted corner contributing wgt of its information)"""
+    pb = SR.Problem(np.asarray(obs), tag_map, K, dist, tag_size, sigma_px, sigma_rot, sigma_trans, huber_px=huber_px)
     P = [SR.pose_of_seed(p) for p in poses]
     D, C, _ = pb.blocks(pb.linearise(P))
     return pb, P, D, C
@@ -132,13 +101,13 @@ def records(n, cov, sigma_px, dof, status):
     return out
 
 
-def smooth_cov(obs, tag_map, K, dist, tag_size, poses, result, sigma_px, sigma_rot, sigma_trans):
+def smooth_cov(obs, tag_map, K, dist, tag_size, poses, result, sigma_px, sigma_rot, sigma_trans, huber_px=0.0):
     """the covariance records of the poses and result record of any smooth output (the statement's or the device's)
     -> (n_frames,) POSE_COV_DTYPE"""
     n = len(poses)
     if int(result["status"]) != SR.OK:
         return records(n, 0.0, sigma_px, 0, PC.STATUS_NO_POSE)
-    pb, P, D, C = problem_blocks(obs, tag_map, K, dist, tag_size, poses, sigma_px, sigma_rot, sigma_trans)
+    pb, P, D, C = problem_blocks(obs, tag_map, K, dist, tag_size, poses, sigma_px, sigma_rot, sigma_trans, huber_px)
     dof = 8 * int(pb.n_tags.sum()) - 6
     Sig = marginals(D, C) if np.all(np.isfinite(D)) and np.all(np.isfinite(C)) else None
     if Sig is None:
@@ -146,9 +115,9 @@ def smooth_cov(obs, tag_map, K, dist, tag_size, poses, result, sigma_px, sigma_r
     return records(n, np.stack([to_record_convention(Sig[f], P[f][0]) for f in range(n)]), sigma_px, dof, PC.STATUS_OK)
 
 
-def dense_marginals(obs, tag_map, K, dist, tag_size, poses, sigma_px, sigma_rot, sigma_trans):
+def dense_marginals(obs, tag_map, K, dist, tag_size, poses, sigma_px, sigma_rot, sigma_trans, huber_px=0.0):
     """the independent second route: (covariances (n, 6, 6) from np.linalg.inv of the assembled matrix, that matrix)"""
-    pb, P, D, C = problem_blocks(obs, tag_map, K, dist, tag_size, poses, sigma_px, sigma_rot, sigma_trans)
+    pb, P, D, C = problem_blocks(obs, tag_map, K, dist, tag_size, poses, sigma_px, sigma_rot, sigma_trans, huber_px)
     A = SR.dense(D, C)
     Ai = np.linalg.inv(A)
     out = np.zeros((len(poses), 6, 6))

@@ -29,11 +29,26 @@ consecutive posed frames, divided by the gap in frame steps; ties go to A, the b
 (tie: A).  A frame without a seed pose takes the chosen pose of the nearest earlier posed frame, the leading ones the first
 posed frame's.  Without any posed frame nothing is solved.
 
+Robust corner loss (huber_px = k > 0: asl_smooth_robust_sequences_*, k_smooth_cand<true> and k_smooth_lin<true> over
+loc_corner<NE, true> of k_localize.inc): every taking-part corner's pixel residual r = (r0, r1) goes through a Huber loss on
+the raw residual, before sigma_px.  With e = r0^2 + r1^2, s = sqrt(e) (corner_terms):
+
+    s <= k   rho = e                 wgt = 1          (the plain term)
+    s >  k   rho = 2 k s - k^2       wgt = k / s
+    z <= 1e-9   rho = 1e12, nothing added to H and g
+
+A frame's data cost is sum rho, its H = sum wgt J^T J and g = sum wgt J^T r, J the localisation's 2x6 rows: iteratively
+reweighted Gauss-Newton, no second-order term.  The robust cost stands wherever the squared one does: the chain's data
+costs, the cost after the chain, every trial and the accept rule, cost_seed and cost; rms_px and rms_seed_px are
+sqrt(sum rho / corners).  A slot is "soft" at a state if at least one of its four corners has wgt < 1 there; the count
+belongs to the linearisation a trial commits, as the frame's pixel cost does.  huber_px = 0 is the plain problem, through
+localize_ref.linearise / corner_costs, with no soft slot.  Corner sums run in slot order, as the device's lanes hold them.
+
 Output per frame (asl_cam_pose): T world<-camera, rms_px / rms_seed_px the frame's own corner RMS at the end / after the
-chain, n_tags its taking-part slots, n_rejected 0, seed_slot the seed's (+256 if the chain chose B; -1 for a filled frame),
+chain, n_tags its taking-part slots, n_rejected its soft slots at the returned poses (0 for the plain problem), seed_slot the seed's (+256 if the chain chose B; -1 for a filled frame),
 status 0 solved with data, 6 solved and carried by the motion prior alone, 4 in a solve that failed, 1 nothing to solve
 (T the identity).  One asl_smooth_result: total cost after the chain and at the end, the corner RMS of both over all
-frames, frames with data, frames filled, frames where B was chosen, trials run, status 0 ok / 1 no posed frame / 2 never
+frames, frames with data, frames filled, frames where B was chosen, trials run, n_soft the sum of n_rejected, status 0 ok / 1 no posed frame / 2 never
 positive definite / 3 non-finite (the cost after the chain).  Test infrastructure, as localize_ref.py is.
 """
 import numpy as np
@@ -88,13 +103,19 @@ def update(P, d):
     return dR @ P[0], dR @ P[1] + d[3:]
 
 
-def chol6(S):
-    """right-looking Cholesky of the lower triangle of S in place -> 1 / diagonal, or None: the products leave every entry
-    in the order k = 0, 1, ... (chol6_solve_tri_dev's), one lane per entry on the device"""
+def positive(p, d):
+    """the solve's pivot rule (d: the undamped diagonal entry of the pivot's column, for smooth_cov_ref's rule)"""
+    return p > 0
+
+
+def chol6(S, diag, pivot=positive):
+    """right-looking Cholesky of the lower triangle of S in place -> 1 / diagonal, or None at the first pivot that fails
+    pivot(p, diag[j]): the products leave every entry in the order k = 0, 1, ... (chol6_solve_tri_dev's), one lane per entry
+    on the device"""
     inv = np.zeros(6)
     for j in range(6):
         p = S[j, j]
-        if not p > 0:
+        if not pivot(p, diag[j]):
             return None
         S[j, j] = np.sqrt(p)
         inv[j] = 1.0 / S[j, j]
@@ -104,21 +125,22 @@ def chol6(S):
     return inv
 
 
-def tridiag_solve(D, C, b, lam):
-    """x of (A + lam diag(A)) x = b, A block tridiagonal: D (n, 6, 6) its diagonal blocks, C (n - 1, 6, 6) = A[f+1][f];
-    None if a diagonal block is not positive definite.  Forward: S_f = D_f (damped) - M_{f-1} M_{f-1}^T = L_f L_f^T,
-    L_f y_f = b_f - M_{f-1} y_{f-1}, M_f = C_f L_f^-T; back: L_f^T x_f = y_f - M_f^T x_{f+1}."""
+def block_factor(D, C, lam=0.0, b=None, pivot=positive):
+    """the forward pass over A + lam diag(A), A block tridiagonal: D (n, 6, 6) its diagonal blocks, C (n - 1, 6, 6) = A[f+1][f].
+    S_f = D_f (damped) - M_{f-1} M_{f-1}^T = L_f L_f^T, M_f = C_f L_f^-T and, with a right-hand side b,
+    L_f y_f = b_f - M_{f-1} y_{f-1} -> (L, 1 / diag, M, y), or None if a pivot fails (smooth_cov_ref's rule sees D_f's diagonal)"""
     n = len(D)
-    L, inv, M, y, x = np.zeros((n, 6, 6)), np.zeros((n, 6)), np.zeros((n, 6, 6)), np.zeros((n, 6)), np.zeros((n, 6))
+    L, inv, M, y = np.zeros((n, 6, 6)), np.zeros((n, 6)), np.zeros((n, 6, 6)), np.zeros((n, 6))
     for f in range(n):
         S = np.array(D[f], dtype=np.float64)
-        S[np.diag_indices(6)] += lam * np.diag(D[f])
-        r = np.array(b[f], dtype=np.float64)
+        if lam != 0.0:
+            S[np.diag_indices(6)] += lam * np.diag(D[f])
+        r = np.zeros(6) if b is None else np.array(b[f], dtype=np.float64)
         if f:
             for k in range(6):
                 S = S - np.outer(M[f - 1][:, k], M[f - 1][:, k])
                 r = r - M[f - 1][:, k] * y[f - 1, k]
-        iv = chol6(S)
+        iv = chol6(S, np.diag(D[f]), pivot)
         if iv is None:
             return None
         L[f], inv[f] = np.tril(S), iv
@@ -133,6 +155,18 @@ def tridiag_solve(D, C, b, lam):
                 for k in range(c):
                     s = s - M[f][:, k] * L[f, c, k]
                 M[f][:, c] = s * iv[c]
+    return L, inv, M, y
+
+
+def tridiag_solve(D, C, b, lam):
+    """x of (A + lam diag(A)) x = b by block_factor, then back: L_f^T x_f = y_f - M_f^T x_{f+1}; None if a diagonal block is not
+    positive definite"""
+    fac = block_factor(D, C, lam, b)
+    if fac is None:
+        return None
+    L, inv, M, y = fac
+    n = len(D)
+    x = np.zeros((n, 6))
     for f in range(n - 1, -1, -1):
         r = y[f].copy()
         if f + 1 < n:
@@ -158,15 +192,40 @@ def dense(D, C):
     return A
 
 
-class Problem:
-    """the frames' corners (taking-part slots; reverse: accumulated in reversed slot order, a rounding perturbation) and the weights"""
+def corner_terms(cam, R, t, Xw, uv, k, jac=False):
+    """per corner of one frame at (R, t): (rho, wgt, over, ok[, J (m, 2, 6) and r (m, 2) of the ok corners])"""
+    P = Xw @ R.T + t
+    ok = P[:, 2] > LR.Z_MIN
+    rho, wgt, over = np.full(len(P), LR.BEHIND_COST), np.zeros(len(P)), np.zeros(len(P), dtype=bool)
+    J = r = None
+    if ok.any():
+        p = P[ok]
+        if jac:
+            q, Jp = LR.project(cam, p, jac=True)
+            J = np.concatenate([Jp @ LR.neg_skew(p), Jp], axis=2)
+        else:
+            q = LR.project(cam, p)
+        r = q - uv[ok]
+        e = r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1]
+        s = np.sqrt(e)
+        o = s > k
+        safe = np.where(o, s, 1.0)
+        wgt[ok] = np.where(o, k / safe, 1.0)
+        rho[ok] = np.where(o, 2.0 * k * s - k * k, e)
+        over[ok] = o
+    return (rho, wgt, over, ok, J, r) if jac else (rho, wgt, over, ok)
 
-    def __init__(self, obs, tag_map, K, dist, tag_size, sigma_px, sigma_rot, sigma_trans, reverse=False):
+
+class Problem:
+    """the frames' corners (taking-part slots; reverse: accumulated in reversed slot order, a rounding perturbation), the weights
+    and the Huber threshold k = huber_px (0: the plain problem)"""
+
+    def __init__(self, obs, tag_map, K, dist, tag_size, sigma_px, sigma_rot, sigma_trans, reverse=False, huber_px=0.0):
         self.cam = LR.camera(K, dist)
         self.model = LR.OneCamera(self.cam)
         self.obs, self.tag_map, self.tag_size = obs, tag_map, tag_size
         self.w = 1.0 / (sigma_px * sigma_px)
-        self.sr, self.st = float(sigma_rot), float(sigma_trans)
+        self.sr, self.st, self.k = float(sigma_rot), float(sigma_trans), float(huber_px)
         self.n = len(obs)
         self.part, self.pts = [], []
         for rows in obs:
@@ -177,23 +236,40 @@ class Problem:
         self.n_tags = np.array([len(p) for p in self.part], dtype=np.int64)
 
     def data_cost(self, f, P):
-        """the frame's squared pixel error at P (not yet weighted)"""
+        """the frame's pixel cost at P: squared, or sum rho (not yet weighted by sigma_px)"""
         if self.pts[f] is None:
             return 0.0
-        return float(LR.corner_costs(self.cam, P[0], P[1], *self.pts[f]).sum())
+        if self.k == 0.0:
+            return float(LR.corner_costs(self.cam, P[0], P[1], *self.pts[f]).sum())
+        return float(corner_terms(self.cam, P[0], P[1], *self.pts[f], self.k)[0].sum())
+
+    def frame(self, f, P):
+        """the weighted path: (cost, H, g, soft slots, wgt per corner, |r| per corner (nan behind the camera)) of frame f at P = (R, t)"""
+        rho, wgt, over, ok, J, r = corner_terms(self.cam, P[0], P[1], *self.pts[f], self.k, jac=True)
+        H, g = np.zeros((6, 6)), np.zeros(6)
+        s = np.full(len(rho), np.nan)
+        if ok.any():
+            w = wgt[ok]
+            H = (w[:, None, None] * (J[:, 0, :, None] * J[:, 0, None, :] + J[:, 1, :, None] * J[:, 1, None, :])).sum(axis=0)
+            g = (w[:, None] * (J[:, 0, :] * r[:, 0:1] + J[:, 1, :] * r[:, 1:2])).sum(axis=0)
+            s[ok] = np.sqrt(r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1])
+        return float(rho.sum()), H, g, int(over.reshape(-1, 4).any(axis=1).sum()), wgt, s
 
     def motion_cost(self, Pa, Pb):
         m = motion_residual(Pa, Pb, self.sr, self.st)
         return float(m @ m)
 
     def linearise(self, P):
-        """everything a trial needs at the poses P: per frame the pixel cost c, H, g; per pair the motion blocks"""
+        """everything a trial needs at the poses P: per frame the pixel cost c, H, g and the soft slots; per pair the motion blocks"""
         n = self.n
         lin = {"c": np.zeros(n), "H": np.zeros((n, 6, 6)), "g": np.zeros((n, 6)), "mc": np.zeros(n), "QN": np.zeros((n, 6, 6)),
-               "QP": np.zeros((n, 6, 6)), "C": np.zeros((n, 6, 6)), "gN": np.zeros((n, 6)), "gP": np.zeros((n, 6))}
+               "QP": np.zeros((n, 6, 6)), "C": np.zeros((n, 6, 6)), "gN": np.zeros((n, 6)), "gP": np.zeros((n, 6)),
+               "soft": np.zeros(n, dtype=np.int64)}
         for f in range(n):
-            if self.pts[f] is not None:
+            if self.pts[f] is not None and self.k == 0.0:
                 lin["c"][f], lin["H"][f], lin["g"][f] = LR.linearise(self.cam, P[f][0], P[f][1], *self.pts[f])
+            elif self.pts[f] is not None:
+                lin["c"][f], lin["H"][f], lin["g"][f], lin["soft"][f] = self.frame(f, P[f])[:4]
             if f + 1 < n:
                 RD, tD = relative(P[f], P[f + 1])
                 m = np.concatenate([log_so3(RD) * (1.0 / self.sr), tD * (1.0 / self.st)])
@@ -282,11 +358,13 @@ def chain_total(d, tr, choice):
     return float(sum(d[k, choice[k]] + (tr[k, choice[k - 1], choice[k]] if k else 0.0) for k in range(len(d))))
 
 
-def smooth(obs, tag_map, K, dist, tag_size, seed, sigma_px, sigma_rot, sigma_trans, max_iters, reverse=False):
+def smooth(obs, tag_map, K, dist, tag_size, seed, sigma_px, sigma_rot, sigma_trans, max_iters, reverse=False, huber_px=0.0):
     """obs (n_frames, max_tags) asl_obs records, tag_map (n_ids,) asl_map_tag records, seed (n_frames,) asl_cam_pose ->
-    ((n_frames,) CAM_POSE_DTYPE, SMOOTH_RESULT_DTYPE record, trace); trace: "posed", "d", "tr", "choice" of the chain"""
+    ((n_frames,) CAM_POSE_DTYPE, SMOOTH_RESULT_DTYPE record, trace); trace: "posed", "d", "tr", "choice" of the chain, "lins":
+    (poses, linearisation) of the chain's poses and of every trial computed (accepted or not), "P": the camera<-world poses
+    returned, "problem": the Problem"""
     obs = np.asarray(obs)
-    pb = Problem(obs, tag_map, K, dist, tag_size, sigma_px, sigma_rot, sigma_trans, reverse)
+    pb = Problem(obs, tag_map, K, dist, tag_size, sigma_px, sigma_rot, sigma_trans, reverse, huber_px)
     n = pb.n
     out = np.zeros(n, dtype=CAM_POSE_DTYPE)
     out["T"] = np.eye(4)
@@ -295,7 +373,7 @@ def smooth(obs, tag_map, K, dist, tag_size, seed, sigma_px, sigma_rot, sigma_tra
     res = np.zeros((), dtype=SMOOTH_RESULT_DTYPE)
     cand = candidates(pb, seed)
     posed, d, tr = chain_costs(pb, cand)
-    trace = {"posed": posed, "d": d, "tr": tr, "choice": np.zeros(0, dtype=np.int64)}
+    trace = {"posed": posed, "d": d, "tr": tr, "choice": np.zeros(0, dtype=np.int64), "lins": [], "P": None, "problem": pb}
     if not posed:
         res["status"] = NO_POSED_FRAME
         return out, res, trace
@@ -315,6 +393,7 @@ def smooth(obs, tag_map, K, dist, tag_size, seed, sigma_px, sigma_rot, sigma_tra
     res["n_flipped"] = int(choice.sum())
 
     lin = pb.linearise(P)
+    trace["lins"].append((P, lin))
     corners = 4.0 * float(pb.n_tags.sum())
 
     def rms(c, k):
@@ -336,6 +415,7 @@ def smooth(obs, tag_map, K, dist, tag_size, seed, sigma_px, sigma_rot, sigma_tra
             solved = True
             Pn = [update(P[f], delta[f]) for f in range(n)]
             ln = pb.linearise(Pn)
+            trace["lins"].append((Pn, ln))
             if ln["cost"] < lin["cost"]:
                 stop = lin["cost"] - ln["cost"] < REL_STOP * lin["cost"]
                 P, lin = Pn, ln
@@ -352,6 +432,9 @@ def smooth(obs, tag_map, K, dist, tag_size, seed, sigma_px, sigma_rot, sigma_tra
         T[:3, 3] = -(P[f][0].T @ P[f][1])
         out["T"][f] = T
     out["rms_px"] = [rms(c, 4.0 * k) for c, k in zip(lin["c"], pb.n_tags)]
+    out["n_rejected"] = lin["soft"]
     out["status"] = FRAME_FAILED if status != OK else np.where(pb.n_tags > 0, FRAME_DATA, FRAME_PRIOR)
     res["cost"], res["rms_px"], res["iterations"], res["status"] = lin["cost"], rms(float(lin["c"].sum()), corners), iters, status
+    res["n_soft"] = int(lin["soft"].sum())
+    trace["P"] = P
     return out, res, trace

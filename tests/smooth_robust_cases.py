@@ -1,14 +1,13 @@
 """Inputs and recorded figures of the robust sequence-localisation tests (tests/test_smooth_robust_ref.py on the CPU,
 tests/test_gpu_smooth_robust.py on the device).  Every figure in recorded() and ROBUST_TOL was measured on the CPU with the
-NumPy statement (tests/smooth_robust_ref.py) -- never with the kernels; test_smooth_robust_ref.py measures them again and
+NumPy statement (tests/smooth_ref.py at huber_px > 0) -- never with the kernels; test_smooth_robust_ref.py measures them again and
 requires the recorded figures to still hold, so the GPU tests can use them without recomputing."""
-import collections
 import functools
 
 import numpy as np
 
 import smooth_cases as SC
-import smooth_robust_ref as RR
+import smooth_seq_cases as SQ
 
 SHAPE_HUBER = 0.6
 SHAPE_MOVE = (8.0, -6.0)            # pixels: corner 0 of slot 0 of every third frame
@@ -35,8 +34,8 @@ def recorded():
     """the statements' figures on the scene, position RMSE against the truth in scene units, rounded up to 4 significant digits
     scene_rmse_seed: the per-frame localisation of the corrupted block (the seeds; two of them are hundreds of units off)
     scene_rmse_plain: smooth_ref on the corrupted block from those seeds at SCENE_ITERS trials, rounded DOWN (a lower bound)
-    scene_rmse_robust: smooth_robust_ref at SCENE_HUBER from the same seeds (largest single error 1.09)
-    clean_rmse_robust: smooth_robust_ref at SCENE_HUBER on the uncorrupted noise(); smooth_ref gives 0.1380683 there, this
+    scene_rmse_robust: smooth_ref at SCENE_HUBER from the same seeds (largest single error 1.09)
+    clean_rmse_robust: smooth_ref at SCENE_HUBER on the uncorrupted noise(); the plain problem gives 0.1380683 there, this
       0.1380686 (one slot of 160 is soft)
     scene_trials / scene_soft: the robust statement's trials (all of SCENE_ITERS: the linear tail converges slowly; the clean
       run stops after 5) and n_soft on the scene: 10 soft slots in the frames 5, 11, 17, 29, 32, 34, 35 -- the five corrupted
@@ -81,23 +80,11 @@ def scene(corrupt=True):
     return obs, rec, SC.seeds_of(obs, rec), truth
 
 
-Batch = collections.namedtuple("Batch", "obs rec seed dist seq_start sigmas huber max_iters")
-
-
-def join(parts, rec, dist, sigmas, huber, max_iters):
-    start = np.concatenate([[0], np.cumsum([len(o) for o, _ in parts])]).astype(np.int32)
-    return Batch(np.concatenate([o for o, _ in parts]), rec, np.concatenate([s for _, s in parts]), dist, start, sigmas, huber, max_iters)
-
-
-def ranges(batch):
-    return [(int(a), int(b)) for a, b in zip(batch.seq_start[:-1], batch.seq_start[1:])]
-
-
 @functools.lru_cache(maxsize=None)
 def ragged():
     """shape(n, 4, 0) for n in 1, 2, 3, 5, 65 end to end: 76 frames, 5 sequences"""
     cases = [shape(n, 4, 0) for n in (1, 2, 3, 5, 65)]
-    return join([(c[0], c[2]) for c in cases], cases[0][1], None, SC.SHAPE_SIGMAS, SHAPE_HUBER, SC.COMPARE_ITERS)
+    return SQ.join([(c[0], c[2]) for c in cases], cases[0][1], None, SC.SHAPE_SIGMAS, SC.COMPARE_ITERS, SHAPE_HUBER)
 
 
 MIXED_STATUS = [0, 0, 2, 3]
@@ -110,11 +97,11 @@ def mixed():
     smooth_cases.failure_cases() (behind: never positive definite; nonfinite: no trial): result statuses MIXED_STATUS"""
     clean, dirty, fc = SC.shape(5, 4, 0), shape(5, 4, 0), SC.failure_cases()
     parts = [(clean[0], clean[2]), (dirty[0], dirty[2]), (fc["behind"][0], fc["behind"][2]), (fc["nonfinite"][0], fc["nonfinite"][2])]
-    return join(parts, clean[1], None, SC.SHAPE_SIGMAS, SHAPE_HUBER, SC.COMPARE_ITERS)
+    return SQ.join(parts, clean[1], None, SC.SHAPE_SIGMAS, SC.COMPARE_ITERS, SHAPE_HUBER)
 
 
 def run(obs, rec, seed, dist, sigmas, huber, max_iters, reverse=False):
-    return RR.smooth(obs, rec, SC.K, dist, SC.TAG, seed, *sigmas, huber, max_iters, reverse=reverse)
+    return SC.run(obs, rec, seed, dist, sigmas, reverse, max_iters, huber)
 
 
 def all_cases():
@@ -134,9 +121,7 @@ def statement(name):
 @functools.lru_cache(maxsize=None)
 def batch_statement(which, k):
     """the robust statement's (poses, result, trace) of sequence k of ragged() / mixed() alone"""
-    b = ragged() if which == "ragged" else mixed()
-    a0, a1 = ranges(b)[k]
-    return run(b.obs[a0:a1], b.rec, b.seed[a0:a1], b.dist, b.sigmas, b.huber, b.max_iters)
+    return SQ.statement(ragged() if which == "ragged" else mixed(), k)
 
 
 def rmse(T, truth):

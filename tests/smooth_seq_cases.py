@@ -9,7 +9,7 @@ import numpy as np
 
 import smooth_cases as SC
 
-Batch = collections.namedtuple("Batch", "obs rec seed dist seq_start sigmas max_iters")
+Batch = collections.namedtuple("Batch", "obs rec seed dist seq_start sigmas max_iters huber")    # huber: 0 for the plain batches
 
 RAGGED_LENGTHS = (1, 2, 3, 5, 64, 65, 130)
 STOP_APART_CUTS = ((0, 40), (13, 14), (5, 7), (0, 13), (14, 40))
@@ -22,10 +22,10 @@ FAILURES_COV_STATUS = [0, 1, 1, 1, 0]
 SHORT_PATTERN = (1, 2, 3, 5)
 
 
-def join(parts, rec, dist, sigmas, max_iters):
+def join(parts, rec, dist, sigmas, max_iters, huber=0.0):
     """parts: [(obs, seed)] of one max_tags -> the sequences laid end to end"""
     start = np.concatenate([[0], np.cumsum([len(o) for o, _ in parts])]).astype(np.int32)
-    return Batch(np.concatenate([o for o, _ in parts]), rec, np.concatenate([s for _, s in parts]), dist, start, sigmas, max_iters)
+    return Batch(np.concatenate([o for o, _ in parts]), rec, np.concatenate([s for _, s in parts]), dist, start, sigmas, max_iters, huber)
 
 
 def ranges(batch):
@@ -110,4 +110,4 @@ def short_pattern():
 def statement(batch, k):
     """the statement's (poses, result, trace) of sequence k of a batch alone"""
     a, b = ranges(batch)[k]
-    return SC.run(batch.obs[a:b], batch.rec, batch.seed[a:b], batch.dist, batch.sigmas, max_iters=batch.max_iters)
+    return SC.run(batch.obs[a:b], batch.rec, batch.seed[a:b], batch.dist, batch.sigmas, max_iters=batch.max_iters, huber=batch.huber)

@@ -1,5 +1,5 @@
 """The robust (Huber) sequence localisation on the device (asl_smooth_robust_sequences_device / _batch: k_smooth_cand<true>,
-k_smooth_lin<true>, k_smooth.inc) against the NumPy statement (tests/smooth_robust_ref.py) on the cases and recorded figures
+k_smooth_lin<true>, k_smooth.inc) against the NumPy statement (tests/smooth_ref.py at huber_px > 0) on the cases and recorded figures
 of tests/smooth_robust_cases.py, and at huber_px 0 against the plain entry points, byte for byte."""
 import ctypes as C
 
@@ -8,8 +8,8 @@ import pytest
 
 import localize_cases as LC
 import smooth_cases as SC
+import smooth_cov_ref as SV
 import smooth_robust_cases as RC
-import smooth_robust_ref as RR
 import smooth_seq_cases as SQ
 import solver_checks as CK
 from aprilslam_amd import _lib, synth
@@ -179,7 +179,7 @@ def test_each_sequence_of_a_batch_is_the_call_alone(gpu_detector, which):
     b = RC.ragged() if which == "ragged" else RC.mixed()
     rc, poses, results, cov = host(gpu_detector, b.obs, b.seq_start, b.rec, b.dist, b.sigmas, b.huber, b.max_iters, b.seed)
     assert rc == 0
-    for k, (a0, a1) in enumerate(RC.ranges(b)):
+    for k, (a0, a1) in enumerate(SQ.ranges(b)):
         rc1, p1, r1, c1 = host(gpu_detector, b.obs[a0:a1], [0, a1 - a0], b.rec, b.dist, b.sigmas, b.huber, b.max_iters, b.seed[a0:a1])
         assert rc1 == 0 and poses[a0:a1].tobytes() == p1.tobytes() and results[k].tobytes() == r1[0].tobytes(), (which, k)
         assert cov[a0:a1].tobytes() == c1.tobytes(), (which, k)
@@ -191,7 +191,7 @@ def test_each_sequence_of_a_batch_is_the_call_alone(gpu_detector, which):
             assert np.array_equal(poses["status"][a0:a1], want["status"]) and np.array_equal(poses["n_rejected"][a0:a1], want["n_rejected"])
     if which == "mixed":
         assert results["status"].tolist() == RC.MIXED_STATUS and results["n_soft"][0] == 0 and results["n_soft"][1] >= 1
-        for (a0, a1), st in zip(RC.ranges(b), RC.MIXED_COV_STATUS):
+        for (a0, a1), st in zip(SQ.ranges(b), RC.MIXED_COV_STATUS):
             assert (cov["status"][a0:a1] == st).all()
     else:
         assert (results["status"] == 0).all() and (results["n_soft"] >= 1).all() and (cov["status"] == 0).all()
@@ -222,11 +222,11 @@ def test_covariance_is_the_weighted_matrix(gpu_detector, name):
     """d_cov against the robust statement's at the device's own poses, within test_gpu_smooth_cov.py's bar (600 eps kappa)"""
     obs, rec, seed, dist, sig, huber, iters = CASES[name]
     out, res, cov = device_case(gpu_detector, name)
-    want = RR.smooth_cov(obs, rec, SC.K, dist, SC.TAG, out, res, *sig, huber)
+    want = SV.smooth_cov(obs, rec, SC.K, dist, SC.TAG, out, res, *sig, huber)
     assert res["status"] == 0 and (want["status"] == 0).all()
     for k in ("status", "dof", "sigma_px"):
         assert np.array_equal(cov[k], want[k]), (name, k, cov[k], want[k])
-    _, A = RR.dense_marginals(obs, rec, SC.K, dist, SC.TAG, out, *sig, huber)
+    _, A = SV.dense_marginals(obs, rec, SC.K, dist, SC.TAG, out, *sig, huber)
     worst = 0.0
     for f in range(len(out)):
         s = np.sqrt(np.diag(want["cov"][f]))
