@@ -382,7 +382,7 @@ static int make_geom(asl_detector *d, int n_frames, int channels, int w, int h, 
     g->tw = g->sw / TILESZ; g->th = g->sh / TILESZ;
     g->nframes = n_frames; g->frame_pitch = frame_pitch;
     g->npix = (size_t)g->sw * g->sh;
-    if (g->npix >= (1u << 24)) return fail(ASL_EINVAL, "decimated frame has %zu pixels; the cluster key holds 2^24", g->npix);
+    if (g->npix >= (1u << CLUSTER_LABEL_BITS)) return fail(ASL_EINVAL, "decimated frame has %zu pixels; the cluster key holds 2^24", g->npix);
     return ASL_OK;
 }
 

@@ -20,10 +20,13 @@ __device__ __forceinline__ unsigned long long hash64(unsigned long long k)
     return k;
 }
 
+#define CLUSTER_LABEL_BITS 24 /* a label is a pixel index of the decimated frame: make_geom refuses frames of 2^24 pixels or more */
+static_assert(2 * CLUSTER_LABEL_BITS <= 48, "cluster key: two labels below the frame number");
+
 __device__ __forceinline__ unsigned long long cluster_key(int fr, unsigned int a, unsigned int b)
 {
     unsigned int hi = a > b ? a : b, lo = a > b ? b : a;
-    return ((unsigned long long)fr << 48) | ((unsigned long long)hi << 24) | lo;
+    return ((unsigned long long)fr << 48) | ((unsigned long long)hi << CLUSTER_LABEL_BITS) | lo;
 }
 
 // insert-or-find; returns slot or -1 on overflow

@@ -13,7 +13,10 @@
 //   k_seg_roots   tile-local roots -> global roots, sizes summed
 //   k_seg_points  one wavefront per 64x63 pixel tile, lane = row, four tiles per workgroup: labels of the runs are
 //                 fetched once per run into LDS, runs of small components are deleted from the masks, the four
-//                 boundary-site masks are shifts and ANDs, and only pixels that emit a point are visited.
+//                 boundary-site masks are shifts and ANDs, and only pixels that emit a point are visited.  Its body is a
+//                 sequence of named steps (segp_*); what lives where in its LDS, and until which barrier, is the plan
+//                 table beside SegpStore; its packed words are stated once above that table, the rule for handing
+//                 tiles to the dense launch once above the kernel.
 // White is 8-connected, black 4-connected; only pixels with 1 <= x <= sw-2 initiate unions (upstream's row loops), so
 // pixel sw-1 never joins its left neighbour: all of that is in the join mask J of a word.
 // Mask layout: [frame][word column][row] (rows of one word column are contiguous: a wavefront's 32 / 64 rows are
@@ -256,6 +259,24 @@ __device__ __forceinline__ unsigned long long seg_threshold_tile(const uint8_t *
     return ((unsigned long long)(second ? hi1 : hi0) << 32) | (second ? lo1 : lo0);
 }
 
+// The links of a row's pixels to the row above, inside a tile (lane = (colour, row); Mp = the mask of the row above, 0 for
+// the tile's first row).  Every pair of touching runs gets at least one union; a stretch of vertically adjacent pixels is
+// one contact.  link[0] up, link[1] up-left, link[2] up-right; the diagonals are white's alone (isw).
+__device__ __forceinline__ void seg_links(unsigned long long M, unsigned long long Mp, unsigned long long J, bool isw, unsigned long long (&link)[3])
+{
+    const unsigned long long U = M & Mp & J;
+    link[0] = U & ~(U << 1);
+    link[1] = isw ? (M & J & (Mp << 1) & ~Mp) : 0ull;               // up-left, only where "up" does not already connect
+    link[2] = isw ? (M & J & (Mp >> 1) & ~(Mp & (J >> 1))) : 0ull;  // up-right, unless up connects and x+1 joins x above
+}
+
+// Run word of k_seg_tile's run list: row 5 | start column 6 | length - 1 (6 bits, the word's top field)
+static_assert(SEG_TH <= 32, "run word: row");
+__device__ __forceinline__ unsigned int seg_runw_pack(int row, int sx, int len) { return (unsigned int)row | ((unsigned int)sx << 5) | ((unsigned int)(len - 1) << 11); }
+__device__ __forceinline__ unsigned int seg_runw_row(unsigned int e) { return e & 31u; }
+__device__ __forceinline__ unsigned int seg_runw_col(unsigned int e) { return (e >> 5) & 63u; }
+__device__ __forceinline__ unsigned int seg_runw_len(unsigned int e) { return (e >> 11) + 1u; }
+
 // The common launch: threshold, masks out, and the components of the tile by union-find over RUN NUMBERS.  The runs of a
 // tile are numbered in the order (colour, row, column) -- a prefix sum over the lanes' run counts -- so the tables are as
 // long as the tile has runs (some eighty in a tile that a tag crosses), not 64 x 32 entries: 4.4 KB of LDS per wavefront,
@@ -272,7 +293,7 @@ __global__ void __launch_bounds__(64 * SEG_TILE_WAVES) k_seg_tile(const uint8_t 
 {
     // every wavefront of the workgroup has its own tile and its own slice of the tables (nothing is shared: no barrier)
     __shared__ unsigned int Ls[SEG_TILE_WAVES][SEG_CAP];          // per run: low 16 bits parent, high 16 bits (roots) pixel count
-    __shared__ unsigned int WLs[SEG_TILE_WAVES][SEG_CAP];         // links (a | b << 16), then the runs: row (5) | column (6) << 5 | (length - 1) << 11
+    __shared__ unsigned int WLs[SEG_TILE_WAVES][SEG_CAP];         // links (a | b << 16), then the runs (run words: seg_runw_pack)
     __shared__ unsigned long long RMKs[SEG_TILE_WAVES][SEG_TH];   // per row: the run starts that are roots (both colours)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     unsigned int *const L = Ls[wave], *const WL = WLs[wave];
@@ -310,12 +331,8 @@ __global__ void __launch_bounds__(64 * SEG_TILE_WAVES) k_seg_tile(const uint8_t 
     const unsigned long long S = seg_starts(M, J);
     unsigned long long Mp = __shfl_up(M, 1), Sp = __shfl_up(S, 1);
     if (r == 0) { Mp = 0; Sp = 0; }  // the row above belongs to another tile: k_seg_border
-    // every pair of touching runs gets at least one union; a stretch of vertically adjacent pixels is one contact
-    const unsigned long long U = M & Mp & J;
     unsigned long long link[3];
-    link[0] = U & ~(U << 1);
-    link[1] = isw ? (M & J & (Mp << 1) & ~Mp) : 0ull;               // up-left, only where "up" does not already connect
-    link[2] = isw ? (M & J & (Mp >> 1) & ~(Mp & (J >> 1))) : 0ull;  // up-right, unless up connects and x+1 joins x above
+    seg_links(M, Mp, J, isw, link);
     const unsigned int nlinks_lane = (unsigned int)(__popcll(link[0]) + __popcll(link[1]) + __popcll(link[2])), nruns_lane = (unsigned int)__popcll(S);
     // inclusive prefix sums; at most 64 x 96 links and 64 x 32 runs: both fit 16 bits
     const unsigned int incl = wave_scan<false>(nlinks_lane | (nruns_lane << 16), 0u, [](unsigned int a, unsigned int b) { return a + b; });
@@ -365,7 +382,7 @@ __global__ void __launch_bounds__(64 * SEG_TILE_WAVES) k_seg_tile(const uint8_t 
         while (m) {
             const int sx = __ffsll((long long)m) - 1;
             m &= m - 1;
-            WL[j++] = (unsigned int)r | ((unsigned int)sx << 5) | ((unsigned int)(seg_run_len(M, J, sx) - 1) << 11);
+            WL[j++] = seg_runw_pack(r, sx, seg_run_len(M, J, sx));
         }
     }
     seg_wave_sync();
@@ -379,13 +396,14 @@ __global__ void __launch_bounds__(64 * SEG_TILE_WAVES) k_seg_tile(const uint8_t 
         unsigned int r0 = i0, r1 = i1;
         seg_lds_find2(L, r0, r1);
         const unsigned int f0 = WL[r0], f1 = WL[r1];  // where the roots start
-        atomicAdd(&L[r0], ((e0 >> 11) + 1u) << 16);
-        if (two) atomicAdd(&L[r1], ((e1 >> 11) + 1u) << 16);
+        atomicAdd(&L[r0], seg_runw_len(e0) << 16);
+        if (two) atomicAdd(&L[r1], seg_runw_len(e1) << 16);
         // i is not a root: nobody adds to it, and finds passing through see an ancestor either way
-        if (r0 != i0) L[i0] = r0; else atomicOr(&RMK[e0 & 31u], 1ull << ((e0 >> 5) & 63u));
-        if (two) { if (r1 != i1) L[i1] = r1; else atomicOr(&RMK[e1 & 31u], 1ull << ((e1 >> 5) & 63u)); }
-        P[(size_t)(y0 + (int)(e0 & 31u)) * sw + x0 + (int)((e0 >> 5) & 63u)] = (unsigned int)((y0 + (int)(f0 & 31u)) * sw + x0 + (int)((f0 >> 5) & 63u));
-        if (two) P[(size_t)(y0 + (int)(e1 & 31u)) * sw + x0 + (int)((e1 >> 5) & 63u)] = (unsigned int)((y0 + (int)(f1 & 31u)) * sw + x0 + (int)((f1 >> 5) & 63u));
+        if (r0 != i0) L[i0] = r0; else atomicOr(&RMK[seg_runw_row(e0)], 1ull << seg_runw_col(e0));
+        if (two) { if (r1 != i1) L[i1] = r1; else atomicOr(&RMK[seg_runw_row(e1)], 1ull << seg_runw_col(e1)); }
+        auto pix = [&](unsigned int e) { return (unsigned int)((y0 + (int)seg_runw_row(e)) * sw + x0 + (int)seg_runw_col(e)); };  // frame index of a run word's start
+        P[pix(e0)] = pix(f0);
+        if (two) P[pix(e1)] = pix(f1);
     }
     seg_wave_sync();
     PHASE(10);
@@ -439,11 +457,8 @@ __global__ void __launch_bounds__(64) k_seg_tile_dense(Geom g, int nwx, int ntil
         seg_wave_sync();
         const unsigned int rbase = (unsigned int)(r * SEG_LW);
         {
-            const unsigned long long U = M & Mp & J;
             unsigned long long link[3];
-            link[0] = U & ~(U << 1);
-            link[1] = isw ? (M & J & (Mp << 1) & ~Mp) : 0ull;
-            link[2] = isw ? (M & J & (Mp >> 1) & ~(Mp & (J >> 1))) : 0ull;
+            seg_links(M, Mp, J, isw, link);
             bool bad = false;
 #pragma unroll
             for (int t = 0; t < 3; t++) {
@@ -668,7 +683,7 @@ __global__ void __launch_bounds__(256) k_seg_roots(const unsigned long long *__r
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// S4 on masks.  Parked point word: lx (6) | ly (6) | site (2) | pixel is black (1) | wavefront (2) | tile-table slot (8)
+// S4 on masks: the point pass, k_seg_points (K7).
 #define SEGP_NSLOT 256          /* slots of the workgroup's cluster table; the last one = "table full": the point probes the global table itself */
 #define SEGP_NW 4               /* word columns (wavefronts) of a common-launch workgroup */
 #define SEGP_RUNCAP 2048        /* runs a common-launch workgroup stages (4 tiles) */
@@ -676,274 +691,409 @@ __global__ void __launch_bounds__(256) k_seg_roots(const unsigned long long *__r
 #define SEGP_PCAP 4096          /* points a common-launch workgroup parks (4 tiles) */
 #define SEGP_PCAP_DENSE 8192    /* the maximum of half a tile: 32 rows x 64 pixels x 4 sites */
 
-// A tile is one word column x 63 emitting rows, one wavefront, lane = row.  The common launch (NW = 4, NHALF = 1) puts
-// four horizontally adjacent tiles in a workgroup that shares the run table, the cluster table and the parking space
-// (a dense tile borrows from its sparse neighbours; a cluster that spans the tiles costs one global probe, not four); a
-// workgroup that still runs out of space puts its tiles on the dense-tile list, which the second launch (NW = 1, full
-// capacities, a tile emitted in NHALF = 2 halves of rows) works off.
-template <int PCAP, int RUNCAP, int NW, int NHALF>
-__global__ void __launch_bounds__(64 * NW) k_seg_points(const unsigned long long *__restrict__ wmask, const unsigned long long *__restrict__ bmask,
-                                                        Geom g, int nwx, const unsigned int *__restrict__ labels, const unsigned int *__restrict__ sizes,
-                                                        unsigned long long *keys, unsigned int *counts, unsigned int hmask,
-                                                        unsigned long long *stage_rec, unsigned int *stage_pos, unsigned int *frame_cursor,
-                                                        unsigned int stage_cap, unsigned int *dense_tiles, int tiles_y, long long *counters)
+// ---- Packed words.  Each of the four formats is stated here and nowhere else (fields from bit 0 up); the asserts hold
+// every field against the largest value it must carry.
+constexpr bool segp_fits(long long largest, int bits) { return largest < (1ll << bits); }
+
+// Run entry (RT before the labels replace it): start bit 6 | row 6 | kind 2 | tile (wavefront) 2.  An own run starts at
+// its start bit of the tile's word; the left neighbour pixel x0-1 carries the start bit of its run in the word on the left,
+// the right neighbour pixel x0+64 is bit 0 of the word on the right and starts its run there.
+enum : unsigned int { SEGP_RUN_OWN = 0u, SEGP_RUN_LEFT = 1u, SEGP_RUN_RIGHT = 2u };
+#define SEGP_RUN_NONE 0xFFFFFFFFu /* no entry (past the end of the list) */
+static_assert(segp_fits(SEGP_NW - 1, 2), "run entry: tile");
+static_assert(segp_fits(SEG_PH, 6), "row (here and in the item and the parked point): a tile stages rows 0 .. SEG_PH");
+__device__ __forceinline__ unsigned int segp_run_tag(int row, int wave) { return ((unsigned int)row << 6) | ((unsigned int)wave << 14); }
+__device__ __forceinline__ unsigned int segp_run_pack(unsigned int tag, unsigned int kind, int sx) { return tag | (kind << 12) | (unsigned int)sx; }
+__device__ __forceinline__ int segp_run_sx(unsigned int e) { return (int)(e & 63u); }
+__device__ __forceinline__ int segp_run_row(unsigned int e) { return (int)((e >> 6) & 63u); }
+__device__ __forceinline__ unsigned int segp_run_kind(unsigned int e) { return (e >> 12) & 3u; }
+__device__ __forceinline__ int segp_run_wave(unsigned int e) { return (int)((e >> 14) & 3u); }
+// x of the entry's run start relative to its own tile's x0
+__device__ __forceinline__ int segp_run_dx(unsigned int e)
 {
-    constexpr bool DENSE = NHALF > 1;
-    constexpr int NSLOT = SEGP_NSLOT, NT = 64 * NW;
-    __shared__ unsigned int RT[RUNCAP];                        // run list, then run labels (bit 31: component too small)
-    __shared__ unsigned long long ROWS[NT];                    // per (tile, row): run starts of both colours
-    __shared__ unsigned int ROWB[NT];                          // per (tile, row): first table entry | own runs << 13 | has left neighbour << 20
-    // the workgroup's own cluster table: key while the points are grouped, then (global slot, base position) in its place;
-    // BC counts the points of a slot, is zeroed once the base is known and then hands out positions
-    __shared__ unsigned long long BK[NSLOT];
-    __shared__ unsigned int BC[NSLOT];
-    __shared__ __attribute__((aligned(8))) unsigned int PT[PCAP];
+    const unsigned int kind = segp_run_kind(e);
+    return (kind == SEGP_RUN_LEFT ? -64 : (kind == SEGP_RUN_RIGHT ? 64 : 0)) + segp_run_sx(e);
+}
+
+// Run label (RT once the labels are in): global root 31 | component too small 1.  A root is a pixel index of the
+// decimated frame, below 2^CLUSTER_LABEL_BITS (make_geom): two of them and the frame number make a cluster key.
+#define SEGP_SMALL 0x80000000u
+static_assert(CLUSTER_LABEL_BITS <= 31, "run label: the root and the too-small bit share a word");
+__device__ __forceinline__ unsigned int segp_label(unsigned int w) { return w & 0x7FFFFFFFu; }
+
+// ROWB, per (tile, row): first entry of the row in RT 13 | own runs 7 | has a left neighbour pixel 1.  The row's entries are
+// its own runs in the order of their start bits, then the left neighbour pixel, then the right one.
+static_assert(segp_fits(SEGP_RUNCAP_DENSE, 13) && segp_fits(SEGP_RUNCAP, 13), "ROWB: first entry (at most the table's size)");
+static_assert(segp_fits(64, 7), "ROWB: own runs of a 64-pixel row");
+static_assert(SEGP_RUNCAP_DENSE >= 64 * (64 + 2), "the dense launch stages every run a tile can have");
+__device__ __forceinline__ unsigned int segp_rowb_pack(int base, int nown, bool havel) { return (unsigned int)base | ((unsigned int)nown << 13) | (havel ? 1u << 20 : 0u); }
+__device__ __forceinline__ int segp_rowb_base(unsigned int rb) { return (int)(rb & 0x1FFFu); }
+__device__ __forceinline__ int segp_rowb_own(unsigned int rb) { return (int)((rb >> 13) & 0x7Fu); }
+__device__ __forceinline__ int segp_rowb_left(unsigned int rb) { return (int)((rb >> 20) & 1u); }
+
+// The one run lookup: index into RT of the run that holds pixel xx = -1 .. 64 of a row, from the row's ROWB word and
+// its run starts S (ROWS).  Pixel xx must belong to a run that was staged.
+__device__ __forceinline__ int segp_run_index(unsigned int rb, unsigned long long S, int xx)
+{
+    const int b = segp_rowb_base(rb), no = segp_rowb_own(rb);
+    if (xx < 0) return b + no;
+    if (xx > 63) return b + no + segp_rowb_left(rb);
+    return b + __popcll(S & seg_upto(xx)) - 1;
+}
+
+// Item (PT while the emitting pixels are listed): lx 6 | row 6 | wavefront 2 | sites 4 | pixel is black 1 | index of
+// its first point 13.  Row and wavefront together are the pixel's (tile, row) index into ROWS / ROWB.
+static_assert(segp_fits(SEGP_PCAP_DENSE - 1, 13) && segp_fits(SEGP_PCAP - 1, 13), "item: first point (an item is stored only if it is below PCAP)");
+__device__ __forceinline__ unsigned int segp_item_tag(int row, int wave) { return ((unsigned int)row << 6) | ((unsigned int)wave << 12); }
+__device__ __forceinline__ unsigned int segp_item_pack(unsigned int tag, int lx, unsigned int sites, unsigned int black, unsigned int first)
+{
+    return (unsigned int)lx | tag | (sites << 14) | (black << 18) | (first << 19);
+}
+__device__ __forceinline__ int segp_item_lx(unsigned int e) { return (int)(e & 63u); }
+__device__ __forceinline__ int segp_item_trow(unsigned int e) { return (int)((e >> 6) & 255u); }
+__device__ __forceinline__ unsigned int segp_item_sites(unsigned int e) { return (e >> 14) & 15u; }
+__device__ __forceinline__ unsigned int segp_item_first(unsigned int e) { return e >> 19; }
+
+// Parked point (PT once the points are grouped): lx 6 | ly 6 | site 2 | pixel is black 1 | wavefront 2 | slot of the
+// workgroup's cluster table 8.  Sites: 0 (1,0), 1 (0,1), 2 (-1,1), 3 (1,1).
+static_assert(segp_fits(SEGP_NSLOT - 1, 8), "parked point: table slot");
+__device__ __forceinline__ unsigned int segp_point_of_item(unsigned int e) { return (e & 0xFFFu) | (((e >> 18) & 1u) << 14) | (((e >> 12) & 3u) << 15); }  // all but site and slot
+__device__ __forceinline__ unsigned int segp_point_pack(unsigned int of_item, unsigned int site, unsigned int slot) { return of_item | (site << 12) | (slot << 17); }
+__device__ __forceinline__ int segp_point_lx(unsigned int w) { return (int)(w & 63u); }
+__device__ __forceinline__ int segp_point_ly(unsigned int w) { return (int)((w >> 6) & 63u); }
+__device__ __forceinline__ int segp_point_site(unsigned int w) { return (int)((w >> 12) & 3u); }
+__device__ __forceinline__ bool segp_point_black(unsigned int w) { return (w >> 14) & 1u; }
+__device__ __forceinline__ int segp_point_wave(unsigned int w) { return (int)((w >> 15) & 3u); }
+__device__ __forceinline__ unsigned int segp_point_slot(unsigned int w) { return w >> 17; }
+
+// The packed counter npts: items 16 | points 16, handed out together by one atomic per row.  Neither half can carry
+// into the other: the totals of a workgroup are bounded by its pixels.
+static_assert(segp_fits(SEGP_NW * SEG_PH * 64, 16), "npts: items of a common-launch workgroup (4 tiles x 63 rows x 64 pixels)");
+static_assert(segp_fits(SEGP_NW * SEG_PH * 64 * 4, 16), "npts: points of a common-launch workgroup (4 sites per pixel)");
+static_assert(SEGP_PCAP_DENSE >= 32 * 64 * 4, "the dense launch parks every point half a tile can have");
+
+// ---- Storage plan: the workgroup's LDS.  The kernel declares the arrays and builds one SegpStore of them at its top; the
+// steps reach them only through it.  "Free after" is the barrier that ends a life; nothing writes the same memory before it.
+//
+//   array   bytes: common  dense    life                written by                  read by                      free after
+//   ROWS           2048    512      run starts of       scan_runs                   group_park, emit's           the tile's end (dense: the barrier
+//   ROWB           1024    256      (tile, row)         scan_runs                   fallback                     opening the next tile)
+//   RT             8192    17408    1 run entries       list_runs                   label_runs                   label_runs itself: a thread replaces
+//                                                                                                                the entries it read, in place
+//                                   2 run labels        label_runs                  group_park, emit's fallback  the tile's end
+//   PT             16384   32768    1 SML: u64 per (tile, row) at PT[0, 2 NT), the starts of the runs too small; EFL: u32 per (tile, row) at
+//                                     PT[2 NT, 3 NT), bit 0 left / bit 1 right neighbour pixel too small
+//                                                       scan_runs (zero, behind     delete_small                 the barrier closing clear_tables
+//                                                       its barrier), label_runs                                 of the first half
+//                                                       (atomicOr, behind the
+//                                                       barrier closing list_runs)
+//                                   2 items             list_items                  group_park: a round's items  the barrier inside each round of
+//                                                                                   go to registers              group_park
+//                                   3 parked points     group_park, at or behind    emit                         the barrier opening the next half
+//                                                       the items of its round                                   or tile
+//   BK             2048    2048     1 cluster key       clear_tables (empty),       reserve                      reserve itself: the thread that read
+//   BC             1024    1024       point count       group_park (CAS, add)                                    slot i replaces it
+//                                   2 global slot |     reserve                     emit (BC: atomicAdd hands    the barrier opening the next half
+//                                     base << 32; next                              out the positions)           or tile
+//                                     position
+//   npts           4       4        items | points<<16  clear_tables (zero),        group_park                   the barrier opening the next half
+//                                                       list_items (atomicAdd)                                   or tile
+//   base           4       4        the frame cursor    reserve, before its barrier reserve, behind it           the same
+//   wtot           16      4        runs per tile       scan_runs, before its       scan_runs, behind it         the barrier opening the next tile
+//                                                       barrier
+//   sum            30744   54028
+//
+// The build reports 31000 B for the common launch (256 B more: the scratch of __syncthreads_or) and 54032 B for the dense
+// one (4 B of padding behind the scalars).
+template <int PCAP_, int RUNCAP_, int NW_, int NHALF_>
+struct SegpStore {
+    static constexpr int PCAP = PCAP_, RUNCAP = RUNCAP_, NW = NW_, NHALF = NHALF_, NT = 64 * NW_, NSLOT = SEGP_NSLOT;
+    static constexpr bool DENSE = NHALF_ > 1;
+    unsigned int *RT;          // [RUNCAP]
+    unsigned long long *ROWS;  // [NT]
+    unsigned int *ROWB;        // [NT]
+    unsigned long long *BK;    // [NSLOT]
+    unsigned int *BC;          // [NSLOT]
+    unsigned int *PT;          // [PCAP], 8-byte aligned
+    unsigned int *npts, *base, *wtot;  // two words and [NW]
+    __device__ __forceinline__ unsigned long long *SML() const { return reinterpret_cast<unsigned long long *>(PT); }
+    __device__ __forceinline__ unsigned int *EFL() const { return PT + 2 * NT; }
     static_assert(PCAP >= 3 * NT, "the small-run masks borrow the parking space");
-    unsigned long long *const SML = reinterpret_cast<unsigned long long *>(PT);  // per (tile, row): starts of the runs that are too small
-    unsigned int *const EFL = PT + 2 * NT;                                       // per (tile, row): bit 0 left neighbour pixel too small, bit 1 right
-    __shared__ unsigned int s_npts, s_base, s_wtot[NW];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int sw = g.sw, sh = g.sh;
-    const size_t per_frame = (size_t)nwx * sh;
-    PHASE_DECL();
-    const long long ndense = DENSE ? counters[CNT_DENSE_TILES] : 1;
-  for (long long work = DENSE ? blockIdx.x : 0; work < ndense; work += DENSE ? gridDim.x : 1) {
-    int wx, ty, fr;
-    if (DENSE) {
-        __syncthreads();
-        const unsigned int tile_id = dense_tiles[work];  // (frame * tiles_y + tile_y) * nwx + word column
-        wx = (int)(tile_id % (unsigned int)nwx);
-        ty = (int)((tile_id / (unsigned int)nwx) % (unsigned int)tiles_y);
-        fr = (int)(tile_id / (unsigned int)(nwx * tiles_y));
-    } else {
-        // frame-major grid: workgroups that run at the same time belong to different frames, so the per-frame cursor and
-        // the per-cluster counters are not hammered by thousands of waves at once (one address sustains ~90 atomics/us)
-        fr = blockIdx.x; ty = blockIdx.z; wx = (int)blockIdx.y * NW + wid;
-    }
-    const unsigned int my_tile_id = (unsigned int)((fr * tiles_y + ty) * nwx + wx);
-    const int x0 = wx * 64, y0 = ty * SEG_PH;
-    const int y = y0 + lane;  // lane = row; rows 0..62 emit, row 63 only serves as "the row below"
-    const bool rowok = y < sh && wx < nwx;
-    const unsigned long long *wm = wmask + (size_t)fr * per_frame, *bm = bmask + (size_t)fr * per_frame;
-    const unsigned int *lab = labels + (size_t)fr * g.npix, *siz = sizes + (size_t)fr * g.npix;
-    PHASE_INIT();
-    const size_t m0 = (size_t)wx * sh + y;
-    unsigned long long W = 0, B = 0;
-    bool wl = false, bl = false, wr = false, br = false;  // pixel x0-1 / x0+64 of this row
-    unsigned long long SL = 0;                            // run starts of the left neighbour pixel's colour in its word
-    if (rowok) {
-        W = wm[m0]; B = bm[m0];
-        if (wx > 0) {
+};
+constexpr size_t segp_lds_bytes(int pcap, int runcap, int nw) { return (size_t)64 * nw * (8 + 4) + SEGP_NSLOT * (8 + 4) + 4 * (size_t)runcap + 4 * (size_t)pcap + 4 * (2 + (size_t)nw); }
+static_assert(segp_lds_bytes(SEGP_PCAP, SEGP_RUNCAP, SEGP_NW) + 256 == 31000, "common launch: the plan and the LDS the build reports disagree");
+static_assert(segp_lds_bytes(SEGP_PCAP_DENSE, SEGP_RUNCAP_DENSE, 1) + 4 == 54032, "dense launch: the plan and the LDS the build reports disagree");
+
+// where the wavefront's tile lies
+struct SegpTile {
+    int fr, wx, x0, y0;
+    int xg0;          // x0 of the workgroup's first tile (the tile of wavefront w starts at xg0 + 64 w)
+    unsigned int id;  // (frame * tiles_y + tile_y) * nwx + word column, as the dense-tile list holds it
+};
+// what a lane holds of its row (lane = row of the tile)
+struct SegpRow {
+    unsigned long long W, B;  // the row's masks; segp_delete_small takes the runs of small components out
+    unsigned int nb;          // pixel x0-1 of the row is white 1 | black 2, pixel x0+64 white 4 | black 8 (the same deletion applies)
+    unsigned long long SL;    // run starts of the left neighbour pixel's colour in its word
+    __device__ __forceinline__ bool wl() const { return nb & 1u; }
+    __device__ __forceinline__ bool bl() const { return nb & 2u; }
+    __device__ __forceinline__ bool wr() const { return nb & 4u; }
+    __device__ __forceinline__ bool br() const { return nb & 8u; }
+    __device__ __forceinline__ bool havel() const { return nb & 3u; }
+    __device__ __forceinline__ bool haver() const { return nb & 12u; }
+};
+struct SegpRuns { unsigned long long Sall; int base, total; };  // the row's run starts (both colours), its first entry in RT, the workgroup's entries
+// the masks of the neighbours of pixel x, aligned to bit x, after the deletion: n = (x, y+1), sr = (x+1, y), nsr = (x+1, y+1), nsl = (x-1, y+1)
+struct SegpNbr { unsigned long long Wn, Bn, Wsr, Bsr, Wnsr, Bnsr, Wnsl, Bnsl; };
+// where the points go: the global cluster table and the per-frame staging rows
+struct SegpOut {
+    unsigned long long *keys;
+    unsigned int *counts, hmask;
+    unsigned long long *stage_rec;
+    unsigned int *stage_pos, *frame_cursor, stage_cap;
+    long long *counters;
+};
+// What a step tells the kernel body, which alone acts on it (the rule stands above k_seg_points)
+enum SegpStatus { SEGP_GO, SEGP_SKIP_HALF, SEGP_OVER_CAPACITY };
+
+// ---- The steps.  Each header says what the step reads and writes (SegpStore members, the lane's registers) and whether it
+// ends with a workgroup barrier.
+
+// Load: the masks of the lane's row and the pixels x0-1 and x0+64 beside it, from global memory.  No barrier.
+__device__ __forceinline__ SegpRow segp_load_row(const unsigned long long *wm, const unsigned long long *bm, const SegpTile &T, int y, int nwx, int sw, int sh)
+{
+    SegpRow R = {0ull, 0ull, 0u, 0ull};
+    if (y < sh && T.wx < nwx) {
+        const size_t m0 = (size_t)T.wx * sh + y;
+        R.W = wm[m0]; R.B = bm[m0];
+        if (T.wx > 0) {
             const unsigned long long Wl = wm[m0 - sh], Bl = bm[m0 - sh];
-            wl = Wl >> 63; bl = Bl >> 63;
-            if (wl || bl) SL = seg_starts(wl ? Wl : Bl, seg_join_mask(x0 - 64, sw));
+            R.nb = (unsigned int)(Wl >> 63) | ((unsigned int)(Bl >> 63) << 1);
+            if (R.havel()) R.SL = seg_starts(R.wl() ? Wl : Bl, seg_join_mask(T.x0 - 64, sw));
         }
-        if (wx + 1 < nwx) { wr = wm[m0 + sh] & 1ull; br = bm[m0 + sh] & 1ull; }
+        if (T.wx + 1 < nwx) R.nb |= (((unsigned int)wm[m0 + sh] & 1u) << 2) | (((unsigned int)bm[m0 + sh] & 1u) << 3);
     }
-    const bool tile_live = __ballot((W | B) != 0ull) != 0ull;
-    if (!DENSE) {
-        // most workgroups of a typical frame hold no contrast at all
-        if (!__syncthreads_or(tile_live ? 1 : 0)) return;
-    }
-    const unsigned long long J = seg_join_mask(x0, sw);
-    const unsigned long long Sall = seg_starts(W, J) | seg_starts(B, J);
-    const bool havel = wl || bl, haver = wr || br;
-    const int nown = __popcll(Sall);
-    const int cnt = tile_live ? nown + (havel ? 1 : 0) + (haver ? 1 : 0) : 0;  // a tile without contrast stages nothing
+    return R;
+}
+
+// Count and scan runs: every row's entries (own runs + neighbour pixels; none for a tile without contrast) are summed over
+// the rows and the tiles.  Writes wtot, then BARRIER, then ROWS, ROWB and zeroes SML / EFL; no barrier at the end (list_runs
+// closes with one).  SEGP_OVER_CAPACITY: the workgroup has more entries than RT holds.
+template <class ST>
+__device__ __forceinline__ SegpStatus segp_scan_runs(const ST &st, const SegpRow &R, unsigned long long J, bool tile_live, int tid, SegpRuns &Q)
+{
+    const int lane = tid & 63, wid = tid >> 6;
+    Q.Sall = seg_starts(R.W, J) | seg_starts(R.B, J);
+    const int nown = __popcll(Q.Sall);
+    const int cnt = tile_live ? nown + (R.havel() ? 1 : 0) + (R.haver() ? 1 : 0) : 0;
     int incl = cnt;  // inclusive prefix over the rows, then over the tiles
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
         int o = __shfl_up(incl, off);
         if (lane >= off) incl += o;
     }
-    if (lane == 63) s_wtot[wid] = (unsigned int)incl;
+    if (lane == 63) st.wtot[wid] = (unsigned int)incl;
     __syncthreads();
-    int base = incl - cnt, total = 0;
+    Q.base = incl - cnt; Q.total = 0;
 #pragma unroll
-    for (int w = 0; w < NW; w++) {
-        if (w < wid) base += (int)s_wtot[w];
-        total += (int)s_wtot[w];
+    for (int w = 0; w < ST::NW; w++) {
+        if (w < wid) Q.base += (int)st.wtot[w];
+        Q.total += (int)st.wtot[w];
     }
-    SML[tid] = 0ull;
-    EFL[tid] = 0u;
-    ROWS[tid] = Sall;
-    ROWB[tid] = (unsigned int)base | ((unsigned int)nown << 13) | (havel ? 1u << 20 : 0u);
-    if (total > RUNCAP) {  // only in the common launch (the dense one holds the maximum)
-        if (lane == 0 && tile_live) dense_tiles[atomicAdd((unsigned long long *)&counters[CNT_DENSE_TILES], 1ull)] = my_tile_id;
-        return;
-    }
-    // ---- run list: row << 6 | start bit, kind in bits 12-13 (0 own word, 1 left neighbour pixel, 2 right), tile in 14-15
+    st.SML()[tid] = 0ull;
+    st.EFL()[tid] = 0u;
+    st.ROWS[tid] = Q.Sall;
+    st.ROWB[tid] = segp_rowb_pack(Q.base, nown, R.havel());
+    return !ST::DENSE && Q.total > ST::RUNCAP ? SEGP_OVER_CAPACITY : SEGP_GO;  // the dense launch holds the maximum (asserted above)
+}
+
+// List runs: the row's lane writes its run entries to RT[base ..].  Ends with a BARRIER.
+template <class ST>
+__device__ __forceinline__ void segp_list_runs(const ST &st, const SegpRow &R, const SegpRuns &Q, bool tile_live, int tid)
+{
     if (tile_live) {
-        unsigned long long m = Sall;
-        int j = base;
-        const unsigned int tag = (unsigned int)(lane << 6) | ((unsigned int)wid << 14);
+        unsigned long long m = Q.Sall;
+        int j = Q.base;
+        const unsigned int tag = segp_run_tag(tid & 63, tid >> 6);
         while (m) {
             const int sx = __ffsll((long long)m) - 1;
             m &= m - 1;
-            RT[j++] = tag | (unsigned int)sx;
+            st.RT[j++] = segp_run_pack(tag, SEGP_RUN_OWN, sx);
         }
-        if (havel) RT[j++] = tag | (unsigned int)seg_start_of(SL, 63) | (1u << 12);
-        if (haver) RT[j++] = tag | (2u << 12);
+        if (R.havel()) st.RT[j++] = segp_run_pack(tag, SEGP_RUN_LEFT, seg_start_of(R.SL, 63));
+        if (R.haver()) st.RT[j++] = segp_run_pack(tag, SEGP_RUN_RIGHT, 0);
     }
     __syncthreads();
-    PHASE(32);
-    // ---- labels, one run per thread and step: run start -> tile-local root -> global root -> size (each level issued for
-    // four runs per thread before waiting)
-    for (int i0 = 0; i0 < total; i0 += 4 * NT) {
+}
+
+// Label runs, one run per thread and step: run start -> tile-local root -> global root -> size, from global memory (each
+// level issued for four runs per thread before waiting).  Reads RT (run entries) and replaces them by the labels; marks
+// the runs of components below MIN_COMPONENT in SML / EFL.  Ends with a BARRIER.
+template <class ST>
+__device__ __forceinline__ void segp_label_runs(const ST &st, const SegpTile &T, const unsigned int *lab, const unsigned int *siz, int sw, int total, int tid)
+{
+    for (int i0 = 0; i0 < total; i0 += 4 * ST::NT) {
         unsigned int e[4], l[4], s[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            const int i = i0 + u * NT + tid;
-            e[u] = i < total ? RT[i] : 0xFFFFFFFFu;
-            const int kind = (int)((e[u] >> 12) & 3u), ew = DENSE ? 0 : (int)((e[u] >> 14) & 3u);
-            const int ex0 = DENSE ? x0 : ((int)blockIdx.y * NW + ew) * 64;
-            const unsigned int p = (unsigned int)((y0 + (int)((e[u] >> 6) & 63u)) * sw + ex0 + (kind == 1 ? -64 : (kind == 2 ? 64 : 0)) + (int)(e[u] & 63u));
-            l[u] = e[u] != 0xFFFFFFFFu ? lab[p] : 0u;
+            const int i = i0 + u * ST::NT + tid;
+            e[u] = i < total ? st.RT[i] : SEGP_RUN_NONE;
+            const int ex0 = T.xg0 + (ST::DENSE ? 0 : segp_run_wave(e[u])) * 64;
+            const unsigned int p = (unsigned int)((T.y0 + segp_run_row(e[u])) * sw + ex0 + segp_run_dx(e[u]));
+            l[u] = e[u] != SEGP_RUN_NONE ? lab[p] : 0u;
         }
 #pragma unroll
-        for (int u = 0; u < 4; u++) l[u] = e[u] != 0xFFFFFFFFu ? lab[l[u]] : 0u;
+        for (int u = 0; u < 4; u++) l[u] = e[u] != SEGP_RUN_NONE ? lab[l[u]] : 0u;
 #pragma unroll
-        for (int u = 0; u < 4; u++) s[u] = e[u] != 0xFFFFFFFFu ? siz[l[u]] : MIN_COMPONENT;
+        for (int u = 0; u < 4; u++) s[u] = e[u] != SEGP_RUN_NONE ? siz[l[u]] : MIN_COMPONENT;
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            const int i = i0 + u * NT + tid;
-            if (e[u] == 0xFFFFFFFFu) continue;
+            const int i = i0 + u * ST::NT + tid;
+            if (e[u] == SEGP_RUN_NONE) continue;
             const bool small = s[u] < MIN_COMPONENT;
-            RT[i] = l[u] | (small ? 0x80000000u : 0u);
+            st.RT[i] = l[u] | (small ? SEGP_SMALL : 0u);
             if (small) {
-                const int row = (int)((e[u] >> 6) & 63u) + 64 * (int)((e[u] >> 14) & 3u), kind = (int)((e[u] >> 12) & 3u);
-                if (kind == 0) {
-                    const int sx = (int)(e[u] & 63u);
-                    atomicOr(reinterpret_cast<unsigned int *>(&SML[row]) + (sx >> 5), 1u << (sx & 31));
+                const int trow = segp_run_row(e[u]) + 64 * segp_run_wave(e[u]);
+                if (segp_run_kind(e[u]) == SEGP_RUN_OWN) {
+                    const int sx = segp_run_sx(e[u]);
+                    atomicOr(reinterpret_cast<unsigned int *>(&st.SML()[trow]) + (sx >> 5), 1u << (sx & 31));
                 } else
-                    atomicOr(&EFL[row], (unsigned int)kind);
+                    atomicOr(&st.EFL()[trow], segp_run_kind(e[u]));  // SEGP_RUN_LEFT = bit 0, SEGP_RUN_RIGHT = bit 1
             }
         }
     }
     __syncthreads();
-    PHASE(33);
-    // ---- a run of a component with fewer than 25 pixels behaves like "no contrast": delete it from the masks
-    {
-        unsigned long long m = SML[tid];
-        while (m) {
-            const int sx = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            const bool white = (W >> sx) & 1ull;
-            const int len = seg_run_len(white ? W : B, J, sx);
-            const unsigned long long bits = (len >= 64 ? ~0ull : ((1ull << len) - 1ull)) << sx;
-            if (white) W &= ~bits; else B &= ~bits;
-        }
-        const unsigned int ef = EFL[tid];
-        if (ef & 1u) { wl = false; bl = false; }
-        if (ef & 2u) { wr = false; br = false; }
+}
+
+// Delete small runs: a run of a component with fewer than 25 pixels behaves like "no contrast" and leaves the lane's masks
+// (R.W, R.B, the neighbour pixels).  Reads SML / EFL; returns the neighbours' masks the four sites are made of, taken after
+// the deletion (the row below is lane + 1).  No barrier.
+template <class ST>
+__device__ __forceinline__ SegpNbr segp_delete_small(const ST &st, SegpRow &R, unsigned long long J, int tid)
+{
+    unsigned long long m = st.SML()[tid];
+    while (m) {
+        const int sx = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const bool white = (R.W >> sx) & 1ull;
+        const int len = seg_run_len(white ? R.W : R.B, J, sx);
+        const unsigned long long bits = (len >= 64 ? ~0ull : ((1ull << len) - 1ull)) << sx;
+        if (white) R.W &= ~bits; else R.B &= ~bits;
     }
-    // the row below (lane + 1)
-    const unsigned long long Wn = __shfl_down(W, 1), Bn = __shfl_down(B, 1);
-    const int fl = (wl ? 1 : 0) | (bl ? 2 : 0) | (wr ? 4 : 0) | (br ? 8 : 0);
-    const int fln = __shfl_down(fl, 1);
+    const unsigned int ef = st.EFL()[tid];
+    if (ef & 1u) R.nb &= ~3u;
+    if (ef & 2u) R.nb &= ~12u;
+    SegpNbr N;
+    N.Wn = __shfl_down(R.W, 1); N.Bn = __shfl_down(R.B, 1);
+    const int fln = __shfl_down((int)R.nb, 1);
     const bool wln = fln & 1, bln = fln & 2, wrn = fln & 4, brn = fln & 8;
-    // label of pixel xx = -1 .. 64 of any (tile, row) of the workgroup, from the run table
-    auto label_at = [&](int trow, int xx) -> unsigned int {
-        const unsigned int rb = ROWB[trow];
-        const int b = (int)(rb & 0x1FFFu), no = (int)((rb >> 13) & 0x7Fu);
-        int j;
-        if (xx < 0) j = b + no;
-        else if (xx > 63) j = b + no + (int)((rb >> 20) & 1u);
-        else j = b + __popcll(ROWS[trow] & (~0ull >> (63 - xx))) - 1;
-        return RT[j] & 0x7FFFFFFFu;
-    };
-    // ---- the four boundary sites of pixel (x, y): (1,0) (0,1) (-1,1) (1,1); one white, one black
-    const unsigned long long Wsr = (W >> 1) | ((unsigned long long)wr << 63), Bsr = (B >> 1) | ((unsigned long long)br << 63);
-    const unsigned long long Wnsr = (Wn >> 1) | ((unsigned long long)wrn << 63), Bnsr = (Bn >> 1) | ((unsigned long long)brn << 63);
-    const unsigned long long Wnsl = (Wn << 1) | (unsigned long long)wln, Bnsl = (Bn << 1) | (unsigned long long)bln;
-#pragma unroll 1
-  for (int half = 0; half < NHALF; half++) {
-    const int rlo = NHALF == 1 ? 0 : half * 32, rhi = NHALF == 1 ? SEG_PH - 1 : min(half * 32 + 31, SEG_PH - 1);
-    if (half > 0) __syncthreads();
-    if (tid == 0) s_npts = 0;
-    for (int i = tid; i < NSLOT; i += NT) { BK[i] = HASH_EMPTY; BC[i] = 0; }
+    N.Wsr = (R.W >> 1) | ((unsigned long long)R.wr() << 63); N.Bsr = (R.B >> 1) | ((unsigned long long)R.br() << 63);
+    N.Wnsr = (N.Wn >> 1) | ((unsigned long long)wrn << 63); N.Bnsr = (N.Bn >> 1) | ((unsigned long long)brn << 63);
+    N.Wnsl = (N.Wn << 1) | (unsigned long long)wln; N.Bnsl = (N.Bn << 1) | (unsigned long long)bln;
+    return N;
+}
+
+// Site masks: E[k] bit x = pixel x of the row emits the point of site k (0 (1,0), 1 (0,1), 2 (-1,1), 3 (1,1): one pixel
+// white, the other black), for the emitting pixels V of this half.  Registers only.
+__device__ __forceinline__ void segp_site_masks(const SegpRow &R, const SegpNbr &N, unsigned long long V, int x0, unsigned long long (&E)[4])
+{
+    E[0] = ((R.W & N.Bsr) | (R.B & N.Wsr)) & V;
+    E[1] = ((R.W & N.Bn) | (R.B & N.Wn)) & V;
+    E[3] = ((R.W & N.Bnsr) | (R.B & N.Wnsr)) & V;
+    E[2] = ((R.W & N.Bnsl) | (R.B & N.Wnsl)) & V;
+    // the (-1,1) point of pixel x is the (1,1) point of pixel x-1: dropped when x-1 emitted it (x-1 >= 1)
+    unsigned long long cl = E[3] << 1;
+    if (x0 >= 64 && ((R.wl() && (N.Bn & 1ull)) || (R.bl() && (N.Wn & 1ull)))) cl |= 1ull;  // pixel x0-1 is an emitting pixel of the same row range
+    E[2] &= ~cl;
+}
+
+// Clear tables: empties BK / BC and zeroes npts for a half.  Ends with a BARRIER.
+template <class ST>
+__device__ __forceinline__ void segp_clear_tables(const ST &st, int tid)
+{
+    if (tid == 0) *st.npts = 0;
+    for (int i = tid; i < ST::NSLOT; i += ST::NT) { st.BK[i] = HASH_EMPTY; st.BC[i] = 0; }
     __syncthreads();
-    const unsigned long long V = (lane >= rlo && lane <= rhi && y >= 1 && y <= sh - 2) ? J : 0ull;  // emitting pixels: 1 <= x <= sw-2, 1 <= y <= sh-2
-    const unsigned long long E0 = ((W & Bsr) | (B & Wsr)) & V;
-    const unsigned long long E1 = ((W & Bn) | (B & Wn)) & V;
-    const unsigned long long E3 = ((W & Bnsr) | (B & Wnsr)) & V;
-    unsigned long long E2 = ((W & Bnsl) | (B & Wnsl)) & V;
-    {
-        // the (-1,1) point of pixel x is the (1,1) point of pixel x-1: dropped when x-1 emitted it (x-1 >= 1)
-        unsigned long long cl = E3 << 1;
-        if (x0 >= 64 && ((wl && (Bn & 1ull)) || (bl && (Wn & 1ull)))) cl |= 1ull;  // pixel x0-1 is an emitting pixel of the same row range
-        E2 &= ~cl;
+}
+
+// List items.  A row's lane only LISTS its emitting pixels (a short loop without a dependent memory access); the label
+// look-ups and the table probes are then done one pixel per thread, by all threads of the workgroup, however the pixels
+// are spread over the rows (a tag covers a third of a tile's rows and its payload rows hold most of the pixels).  The list
+// lives in the parking space itself: one packed counter (npts) hands out item and point indices together, so an item's
+// points are parked at or behind the item's own place, and the rounds of group_park run from the end of the list.
+// Reads the site masks and R.B; writes PT (items) and npts.  Ends with a BARRIER.
+template <class ST>
+__device__ __forceinline__ void segp_list_items(const ST &st, const SegpRow &R, const unsigned long long (&E)[4], int tid)
+{
+    const unsigned long long any = E[0] | E[1] | E[2] | E[3];
+    const unsigned int npts_lane = (unsigned int)(__popcll(E[0]) + __popcll(E[1]) + __popcll(E[2]) + __popcll(E[3]));
+    const unsigned int nitems_lane = (unsigned int)__popcll(any);
+    unsigned int ib = 0, pi = 0;
+    if (nitems_lane) {
+        const unsigned int old = atomicAdd(st.npts, nitems_lane | (npts_lane << 16));
+        ib = old & 0xFFFFu; pi = old >> 16;
     }
-    unsigned long long any = E0 | E1 | E2 | E3;
-    const unsigned int npts_lane = (unsigned int)(__popcll(E0) + __popcll(E1) + __popcll(E2) + __popcll(E3));
-    // ---- work list.  A row's lane only LISTS its emitting pixels (a short loop without a dependent memory access); the
-    // label look-ups and the table probes are then done one pixel per thread, by all threads of the workgroup, however the
-    // pixels are spread over the rows (a tag covers a third of a tile's rows and its payload rows hold most of the pixels).
-    // Item: lx (6) | row (6) | wavefront (2) | sites (4) | pixel is black (1) | index of its first point (13).  The list
-    // lives in the parking space itself: one packed counter hands out item and point indices together, so an item's points
-    // are parked at or behind the item's own place, and the rounds run from the end of the list.
-    {
-        const unsigned int nitems_lane = (unsigned int)__popcll(any);
-        unsigned int ib = 0, pi = 0;
-        if (nitems_lane) {
-            const unsigned int old = atomicAdd(&s_npts, nitems_lane | (npts_lane << 16));
-            ib = old & 0xFFFFu; pi = old >> 16;
-        }
-        const unsigned int rowtag = ((unsigned int)lane << 6) | ((unsigned int)wid << 12);
-        // the two 32-pixel halves of the word one after the other: every step of the walk is a 32-bit operation
+    const unsigned int rowtag = segp_item_tag(tid & 63, tid >> 6);
+    // the two 32-pixel halves of the word one after the other: every step of the walk is a 32-bit operation
 #pragma unroll
-        for (int hf = 0; hf < 2; hf++) {
-            unsigned int a = (unsigned int)(any >> (32 * hf));
-            const unsigned int e0 = (unsigned int)(E0 >> (32 * hf)), e1 = (unsigned int)(E1 >> (32 * hf)), e2 = (unsigned int)(E2 >> (32 * hf)),
-                               e3 = (unsigned int)(E3 >> (32 * hf)), bb = (unsigned int)(B >> (32 * hf));
-            while (a) {
-                const int b = __ffs((int)a) - 1;
-                a &= a - 1;
-                const unsigned int m = ((e0 >> b) & 1u) | (((e1 >> b) & 1u) << 1) | (((e2 >> b) & 1u) << 2) | (((e3 >> b) & 1u) << 3);
-                if (pi < (unsigned int)PCAP) PT[ib] = (unsigned int)(b + 32 * hf) | rowtag | (m << 14) | (((bb >> b) & 1u) << 18) | (pi << 19);
-                ib++;
-                pi += (unsigned int)__popc(m);
-            }
+    for (int hf = 0; hf < 2; hf++) {
+        unsigned int a = (unsigned int)(any >> (32 * hf));
+        const unsigned int e0 = (unsigned int)(E[0] >> (32 * hf)), e1 = (unsigned int)(E[1] >> (32 * hf)), e2 = (unsigned int)(E[2] >> (32 * hf)),
+                           e3 = (unsigned int)(E[3] >> (32 * hf)), bb = (unsigned int)(R.B >> (32 * hf));
+        while (a) {
+            const int b = __ffs((int)a) - 1;
+            a &= a - 1;
+            const unsigned int m = ((e0 >> b) & 1u) | (((e1 >> b) & 1u) << 1) | (((e2 >> b) & 1u) << 2) | (((e3 >> b) & 1u) << 3);
+            if (pi < (unsigned int)ST::PCAP) st.PT[ib] = segp_item_pack(rowtag, b + 32 * hf, m, (bb >> b) & 1u, pi);
+            ib++;
+            pi += (unsigned int)__popc(m);
         }
     }
     __syncthreads();
-    PHASE(37);
-    const unsigned int packed = s_npts;
-    const unsigned int nitems = packed & 0xFFFFu, npts = packed >> 16;
-    if (npts <= (unsigned int)PCAP && nitems > 0) {
+}
+
+// Group items and park points: one item per thread and round; the labels of the pixel and of its up to four partners come
+// from ROWB / ROWS / RT, every (pixel, partner label) pair is looked up or entered in BK, counted in BC, and the pixel's
+// points are parked in PT with the slot.  A round's items are in registers before the round's first point is parked (the
+// barrier inside the round).  npts = the half's points.  Ends with a BARRIER.  SEGP_OVER_CAPACITY: more points than PT
+// holds (nothing was parked); SEGP_SKIP_HALF: no points.
+template <class ST>
+__device__ __forceinline__ SegpStatus segp_group_park(const ST &st, int fr, int tid, unsigned int &npts)
+{
+    constexpr int NSLOT = ST::NSLOT;
+    const unsigned int packed = *st.npts;
+    const unsigned int nitems = packed & 0xFFFFu;
+    npts = packed >> 16;
+    if (npts <= (unsigned int)ST::PCAP && nitems > 0) {
 #pragma unroll 1
-        for (int rd = (int)((nitems - 1u) / (unsigned int)NT); rd >= 0; rd--) {
-            const unsigned int i = (unsigned int)rd * (unsigned int)NT + (unsigned int)tid;
+        for (int rd = (int)((nitems - 1u) / (unsigned int)ST::NT); rd >= 0; rd--) {
+            const unsigned int i = (unsigned int)rd * (unsigned int)ST::NT + (unsigned int)tid;
             const bool have = i < nitems;
-            const unsigned int e = have ? PT[i] : 0u;
+            const unsigned int e = have ? st.PT[i] : 0u;
             __syncthreads();  // every item of the round is in a register before the first point of the round is parked
             if (!have) continue;
-            const int lx = (int)(e & 63u), trow = (int)((e >> 6) & 255u);
-            unsigned int m = (e >> 14) & 15u, pidx = e >> 19;
-            // labels of the pixel and of its up to four partners: the two rows' tables first, then all run-table reads together
-            const unsigned int rb0 = ROWB[trow], rb1 = ROWB[trow + 1];
-            const unsigned long long S0 = ROWS[trow], S1 = ROWS[trow + 1];
-            const int b0 = (int)(rb0 & 0x1FFFu), n0 = (int)((rb0 >> 13) & 0x7Fu), b1 = (int)(rb1 & 0x1FFFu), n1 = (int)((rb1 >> 13) & 0x7Fu);
-            const unsigned long long upto = ~0ull >> (63 - lx);  // bits 0 .. lx
-            const int j0 = b0 + __popcll(S0 & upto) - 1;                                                 // (lx, row)
-            const int j00 = lx == 63 ? b0 + n0 + (int)((rb0 >> 20) & 1u) : b0 + __popcll(S0 & ((upto << 1) | 1ull)) - 1;   // (lx + 1, row)
-            const int j10 = b1 + __popcll(S1 & upto) - 1;                                                // (lx, row + 1)
-            const int j11 = lx == 0 ? b1 + n1 : b1 + __popcll(S1 & (upto >> 1)) - 1;                     // (lx - 1, row + 1)
-            const int j12 = lx == 63 ? b1 + n1 + (int)((rb1 >> 20) & 1u) : b1 + __popcll(S1 & ((upto << 1) | 1ull)) - 1;   // (lx + 1, row + 1)
-            const unsigned int rep0 = RT[j0] & 0x7FFFFFFFu;
+            const int lx = segp_item_lx(e), trow = segp_item_trow(e);
+            unsigned int m = segp_item_sites(e), pidx = segp_item_first(e);
+            // the two rows' tables first, then all run-table reads together
+            const unsigned int rb0 = st.ROWB[trow], rb1 = st.ROWB[trow + 1];
+            const unsigned long long S0 = st.ROWS[trow], S1 = st.ROWS[trow + 1];
+            const int j0 = segp_run_index(rb0, S0, lx);
+            const int j00 = segp_run_index(rb0, S0, lx + 1), j10 = segp_run_index(rb1, S1, lx);          // sites 0 (1,0) and 1 (0,1)
+            const int j11 = segp_run_index(rb1, S1, lx - 1), j12 = segp_run_index(rb1, S1, lx + 1);      // sites 2 (-1,1) and 3 (1,1)
+            const unsigned int rep0 = segp_label(st.RT[j0]);
             unsigned int rep1[4];
-            rep1[0] = RT[(m & 1u) ? j00 : j0] & 0x7FFFFFFFu;
-            rep1[1] = RT[(m & 2u) ? j10 : j0] & 0x7FFFFFFFu;
-            rep1[2] = RT[(m & 4u) ? j11 : j0] & 0x7FFFFFFFu;
-            rep1[3] = RT[(m & 8u) ? j12 : j0] & 0x7FFFFFFFu;
-            const unsigned int where = (e & 0xFFFu) | (((e >> 18) & 1u) << 14) | (((e >> 12) & 3u) << 15);
+            rep1[0] = segp_label(st.RT[(m & 1u) ? j00 : j0]);
+            rep1[1] = segp_label(st.RT[(m & 2u) ? j10 : j0]);
+            rep1[2] = segp_label(st.RT[(m & 4u) ? j11 : j0]);
+            rep1[3] = segp_label(st.RT[(m & 8u) ? j12 : j0]);
+            const unsigned int where = segp_point_of_item(e);
             while (m) {
                 // the lowest remaining site and every other remaining site with the same neighbour label
                 const unsigned int rr = (m & 1u) ? rep1[0] : ((m & 2u) ? rep1[1] : ((m & 4u) ? rep1[2] : rep1[3]));
                 const unsigned int grp = m & ((rep1[0] == rr ? 1u : 0u) | (rep1[1] == rr ? 2u : 0u) | (rep1[2] == rr ? 4u : 0u) | (rep1[3] == rr ? 8u : 0u));
                 m &= ~grp;
                 const unsigned int hi = rep0 > rr ? rep0 : rr, lo = rep0 > rr ? rr : rep0;
-                const unsigned long long key = ((unsigned long long)fr << 48) | ((unsigned long long)hi << 24) | lo;
+                const unsigned long long key = ((unsigned long long)fr << 48) | ((unsigned long long)hi << CLUSTER_LABEL_BITS) | lo;  // == cluster_key(fr, rep0, rr)
                 unsigned int h = hi ^ ((lo << 11) | (lo >> 21));
                 h ^= h >> 15;
                 h ^= h >> 7;
@@ -952,88 +1102,206 @@ __global__ void __launch_bounds__(64 * NW) k_seg_points(const unsigned long long
                 unsigned int slot = NSLOT - 1;  // "table full"
 #pragma unroll 1
                 for (int probe = 0; probe < NSLOT - 1; probe++) {
-                    unsigned long long cur = __hip_atomic_load(&BK[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    unsigned long long cur = __hip_atomic_load(&st.BK[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     if (cur == key) { slot = h; break; }
                     if (cur == HASH_EMPTY) {
-                        unsigned long long old = atomicCAS(&BK[h], HASH_EMPTY, key);
+                        unsigned long long old = atomicCAS(&st.BK[h], HASH_EMPTY, key);
                         if (old == HASH_EMPTY || old == key) { slot = h; break; }
                     }
                     h = h + 1 == (unsigned int)(NSLOT - 1) ? 0u : h + 1;
                 }
-                if (slot != (unsigned int)(NSLOT - 1)) atomicAdd(&BC[slot], (unsigned int)__popc(grp));
-                const unsigned int word = where | (slot << 17);
+                if (slot != (unsigned int)(NSLOT - 1)) atomicAdd(&st.BC[slot], (unsigned int)__popc(grp));
 #pragma unroll
-                for (int k = 0; k < 4; k++)
-                    if (grp & (1u << k)) PT[pidx++] = word | ((unsigned int)k << 12);
+                for (unsigned int k = 0; k < 4; k++)
+                    if (grp & (1u << k)) st.PT[pidx++] = segp_point_pack(where, k, slot);
             }
         }
     }
     __syncthreads();
-    PHASE(34);
-    if (npts > (unsigned int)PCAP) {
-        if (!DENSE) {  // more points than this launch parks: the dense launch takes the tiles
-            if (lane == 0 && tile_live) dense_tiles[atomicAdd((unsigned long long *)&counters[CNT_DENSE_TILES], 1ull)] = my_tile_id;
-            return;
-        }
-        if (tid == 0) atomicAdd((unsigned long long *)&counters[CNT_OVERFLOW_POINTS], 1ull);  // cannot happen: PCAP is the maximum of half a tile
-        continue;
-    }
-    if (npts == 0) continue;
-    // ---- one global table probe + one counted atomic per (workgroup, cluster), one cursor atomic per workgroup
-    for (int i = tid; i < NSLOT - 1; i += NT) {
-        const unsigned int c = BC[i];
+    if (npts > (unsigned int)ST::PCAP) return SEGP_OVER_CAPACITY;
+    return npts == 0 ? SEGP_SKIP_HALF : SEGP_GO;
+}
+
+// Reserve: one global table probe + one counted atomic per (workgroup, cluster) -- BK / BC change from (key, count) to
+// (global slot | base position << 32, 0) -- and one cursor atomic per workgroup (base).  Ends with a BARRIER.
+// SEGP_SKIP_HALF: the frame's staging rows are full (counted in CNT_OVERFLOW_POINTS: the host re-runs the batch).
+template <class ST>
+__device__ __forceinline__ SegpStatus segp_reserve(const ST &st, const SegpOut &out, int fr, unsigned int npts, int tid, unsigned int &tbase)
+{
+    for (int i = tid; i < ST::NSLOT - 1; i += ST::NT) {
+        const unsigned int c = st.BC[i];
         if (c) {
-            int gslot = hash_insert(keys, hmask, BK[i]);
+            int gslot = hash_insert(out.keys, out.hmask, st.BK[i]);
             unsigned int bg = 0xFFFFFFFFu, bb = 0u;
-            if (gslot < 0) atomicAdd((unsigned long long *)&counters[CNT_OVERFLOW_HASH], 1ull);
-            else { bg = (unsigned int)gslot; bb = atomicAdd(&counts[gslot], c); }
-            BK[i] = (unsigned long long)bg | ((unsigned long long)bb << 32);
-            BC[i] = 0u;
+            if (gslot < 0) atomicAdd((unsigned long long *)&out.counters[CNT_OVERFLOW_HASH], 1ull);
+            else { bg = (unsigned int)gslot; bb = atomicAdd(&out.counts[gslot], c); }
+            st.BK[i] = (unsigned long long)bg | ((unsigned long long)bb << 32);
+            st.BC[i] = 0u;
         }
     }
-    if (tid == NT - 1) {
-        unsigned int b = atomicAdd(&frame_cursor[fr], npts);
-        if (b + npts > stage_cap) { atomicAdd((unsigned long long *)&counters[CNT_OVERFLOW_POINTS], 1ull); b = 0xFFFFFFFFu; }
-        s_base = b;
+    if (tid == ST::NT - 1) {
+        unsigned int b = atomicAdd(&out.frame_cursor[fr], npts);
+        if (b + npts > out.stage_cap) { atomicAdd((unsigned long long *)&out.counters[CNT_OVERFLOW_POINTS], 1ull); b = 0xFFFFFFFFu; }
+        *st.base = b;
     }
     __syncthreads();
-    PHASE(35);
-    const unsigned int tbase = s_base;
-    if (tbase == 0xFFFFFFFFu) continue;
-    // ---- the parked points leave as dense, coalesced rows: (record | global slot << 36, position in the cluster)
-    uint2 *const srec = reinterpret_cast<uint2 *>(stage_rec) + ((size_t)fr * stage_cap + tbase);
-    unsigned int *const spos = stage_pos + ((size_t)fr * stage_cap + tbase);
-    for (unsigned int i = tid; i < npts; i += NT) {
-        const unsigned int w = PT[i];
-        const int lx = (int)(w & 63u), ly = (int)((w >> 6) & 63u), k = (int)((w >> 12) & 3u), pw = (int)((w >> 15) & 3u);
-        const bool black = (w >> 14) & 1u;
-        const unsigned int slot = w >> 17;
+    tbase = *st.base;
+    return tbase == 0xFFFFFFFFu ? SEGP_SKIP_HALF : SEGP_GO;
+}
+
+// Emit: the parked points leave as dense, coalesced rows: (record | global slot << 36, position in the cluster).  Reads PT
+// (parked points), BK / BC (global slot, base, next position); a point whose slot is "table full" finds its two labels
+// through the run lookup and probes the global table on its own.  No barrier.
+template <class ST>
+__device__ __forceinline__ void segp_emit(const ST &st, const SegpOut &out, const SegpTile &T, unsigned int npts, unsigned int tbase, int tid)
+{
+    uint2 *const srec = reinterpret_cast<uint2 *>(out.stage_rec) + ((size_t)T.fr * out.stage_cap + tbase);
+    unsigned int *const spos = out.stage_pos + ((size_t)T.fr * out.stage_cap + tbase);
+    for (unsigned int i = tid; i < npts; i += ST::NT) {
+        const unsigned int w = st.PT[i];
+        const int lx = segp_point_lx(w), ly = segp_point_ly(w), k = segp_point_site(w), pw = segp_point_wave(w);
+        const bool black = segp_point_black(w);
+        const unsigned int slot = segp_point_slot(w);
         const int dx = k == 0 ? 1 : (k == 1 ? 0 : (k == 2 ? -1 : 1)), dy = k == 0 ? 0 : 1;
-        const int px0 = DENSE ? x0 : ((int)blockIdx.y * NW + pw) * 64;
+        const int px0 = T.xg0 + (ST::DENSE ? 0 : pw) * 64;
         unsigned int gslot, pos;
-        if (slot == (unsigned int)(NSLOT - 1)) {  // the table was full: this point probes the global table on its own
-            int gs = hash_insert(keys, hmask, cluster_key(fr, label_at(pw * 64 + ly, lx), label_at(pw * 64 + ly + dy, lx + dx)));
+        if (slot == (unsigned int)(ST::NSLOT - 1)) {  // the table was full
+            const int t0 = pw * 64 + ly, t1 = t0 + dy;
+            const unsigned int a = segp_label(st.RT[segp_run_index(st.ROWB[t0], st.ROWS[t0], lx)]);
+            const unsigned int b = segp_label(st.RT[segp_run_index(st.ROWB[t1], st.ROWS[t1], lx + dx)]);
+            int gs = hash_insert(out.keys, out.hmask, cluster_key(T.fr, a, b));
             gslot = gs < 0 ? 0xFFFFFFFFu : (unsigned int)gs;
-            pos = gs < 0 ? 0u : atomicAdd(&counts[gs], 1u);
-            if (gs < 0) atomicAdd((unsigned long long *)&counters[CNT_OVERFLOW_HASH], 1ull);
+            pos = gs < 0 ? 0u : atomicAdd(&out.counts[gs], 1u);
+            if (gs < 0) atomicAdd((unsigned long long *)&out.counters[CNT_OVERFLOW_HASH], 1ull);
         } else {
-            const unsigned long long gb = BK[slot];
+            const unsigned long long gb = st.BK[slot];
             gslot = (unsigned int)gb;
-            pos = (unsigned int)(gb >> 32) + atomicAdd(&BC[slot], 1u);
+            pos = (unsigned int)(gb >> 32) + atomicAdd(&st.BC[slot], 1u);
         }
         const bool good = gslot != 0xFFFFFFFFu;  // table overflow: the place pass skips the record, the batch is re-run
         // == pack_point(2x+dx, 2y+dy, dx*d, dy*d) | gslot << POINT_BITS with d = +255 for a black pixel, -255 for a white one
         const unsigned int cpos = black ? 1u : 2u, cneg = 3u - cpos;
         const unsigned int cgx = dx == 0 ? 0u : (dx > 0 ? cpos : cneg), cgy = dy == 0 ? 0u : cpos;
         uint2 rec;
-        rec.x = good ? ((unsigned int)(2 * (px0 + lx) + dx) | ((unsigned int)(2 * (y0 + ly) + dy) << 16)) : 0xFFFFFFFFu;
+        rec.x = good ? ((unsigned int)(2 * (px0 + lx) + dx) | ((unsigned int)(2 * (T.y0 + ly) + dy) << 16)) : 0xFFFFFFFFu;
         rec.y = good ? (cgx | (cgy << 2) | (gslot << (POINT_BITS - 32))) : 0xFFFFFFFFu;
         srec[i] = rec;
         spos[i] = good ? pos : 0u;
     }
-    PHASE(36);
-  }  // halves
-  }  // tiles
+}
+
+// the wavefront's tile joins the list the dense launch works off
+__device__ __forceinline__ void segp_hand_over(unsigned int *dense_tiles, long long *counters, unsigned int tile_id)
+{
+    dense_tiles[atomicAdd((unsigned long long *)&counters[CNT_DENSE_TILES], 1ull)] = tile_id;
+}
+
+// A tile is one word column x 63 emitting rows, one wavefront, lane = row (row 63 only serves as "the row below").  The
+// common launch (NW = 4, NHALF = 1) puts four horizontally adjacent tiles in a workgroup that shares the run table, the
+// cluster table and the parking space (a dense tile borrows from its sparse neighbours; a cluster that spans the tiles
+// costs one global probe, not four); the dense launch (NW = 1, full capacities, a tile emitted in NHALF = 2 halves of rows)
+// works off the dense-tile list, one tile per workgroup and trip.
+//
+// The handover rule, stated here once and acted on only in this body.  A step that finds more runs than RUNCAP or more
+// points than PCAP answers SEGP_OVER_CAPACITY:
+//   common launch  every tile of the workgroup that has contrast goes on dense_tiles, and the workgroup ends;
+//   dense launch   cannot happen (RUNCAP and PCAP are the maxima of a tile and of half a tile, asserted above; the run
+//                  check is not even compiled); if points still overflow, CNT_OVERFLOW_POINTS counts it and the half is
+//                  skipped.
+// SEGP_SKIP_HALF (no points, or the frame's staging rows are full) goes on to the next half or tile.  Every exit passes
+// PHASE_FLUSH.
+template <int PCAP, int RUNCAP, int NW, int NHALF>
+__global__ void __launch_bounds__(64 * NW) k_seg_points(const unsigned long long *__restrict__ wmask, const unsigned long long *__restrict__ bmask,
+                                                        Geom g, int nwx, const unsigned int *__restrict__ labels, const unsigned int *__restrict__ sizes,
+                                                        unsigned long long *keys, unsigned int *counts, unsigned int hmask,
+                                                        unsigned long long *stage_rec, unsigned int *stage_pos, unsigned int *frame_cursor,
+                                                        unsigned int stage_cap, unsigned int *dense_tiles, int tiles_y, long long *counters)
+{
+    constexpr bool DENSE = NHALF > 1;
+    using ST = SegpStore<PCAP, RUNCAP, NW, NHALF>;
+    __shared__ unsigned int RT[RUNCAP];
+    __shared__ unsigned long long ROWS[ST::NT];
+    __shared__ unsigned int ROWB[ST::NT];
+    __shared__ unsigned long long BK[ST::NSLOT];
+    __shared__ unsigned int BC[ST::NSLOT];
+    __shared__ __attribute__((aligned(8))) unsigned int PT[PCAP];
+    __shared__ unsigned int s_npts, s_base, s_wtot[NW];
+    static_assert(sizeof RT + sizeof ROWS + sizeof ROWB + sizeof BK + sizeof BC + sizeof PT + sizeof s_npts + sizeof s_base + sizeof s_wtot == segp_lds_bytes(PCAP, RUNCAP, NW),
+                  "the arrays declared here are the plan's");
+    const ST st = {RT, ROWS, ROWB, BK, BC, PT, &s_npts, &s_base, s_wtot};
+    const SegpOut out = {keys, counts, hmask, stage_rec, stage_pos, frame_cursor, stage_cap, counters};
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int sw = g.sw, sh = g.sh;
+    const size_t per_frame = (size_t)nwx * sh;
+    PHASE_DECL();
+    const long long ndense = DENSE ? counters[CNT_DENSE_TILES] : 1;
+    for (long long work = DENSE ? blockIdx.x : 0; work < ndense; work += DENSE ? gridDim.x : 1) {
+        SegpTile T;
+        int ty;
+        if (DENSE) {
+            __syncthreads();  // the previous tile's last reads of the LDS are done
+            const unsigned int tile_id = dense_tiles[work];
+            T.wx = (int)(tile_id % (unsigned int)nwx);
+            ty = (int)((tile_id / (unsigned int)nwx) % (unsigned int)tiles_y);
+            T.fr = (int)(tile_id / (unsigned int)(nwx * tiles_y));
+        } else {
+            // frame-major grid: workgroups that run at the same time belong to different frames, so the per-frame cursor and
+            // the per-cluster counters are not hammered by thousands of waves at once (one address sustains ~90 atomics/us)
+            T.fr = blockIdx.x; ty = blockIdx.z; T.wx = (int)blockIdx.y * NW + wid;
+        }
+        T.id = (unsigned int)((T.fr * tiles_y + ty) * nwx + T.wx);
+        T.x0 = T.wx * 64; T.y0 = ty * SEG_PH;
+        T.xg0 = DENSE ? T.x0 : (int)blockIdx.y * NW * 64;
+        const int y = T.y0 + lane;
+        PHASE_INIT();
+        SegpRow R = segp_load_row(wmask + (size_t)T.fr * per_frame, bmask + (size_t)T.fr * per_frame, T, y, nwx, sw, sh);
+        const bool tile_live = __ballot((R.W | R.B) != 0ull) != 0ull;
+        if (!DENSE) {
+            // most workgroups of a typical frame hold no contrast at all
+            if (!__syncthreads_or(tile_live ? 1 : 0)) { PHASE_FLUSH(32); return; }
+        }
+        const unsigned long long J = seg_join_mask(T.x0, sw);
+        SegpRuns Q;
+        if (segp_scan_runs(st, R, J, tile_live, tid, Q) == SEGP_OVER_CAPACITY) {
+            if (lane == 0 && tile_live) segp_hand_over(dense_tiles, counters, T.id);
+            PHASE_FLUSH(32);
+            return;
+        }
+        segp_list_runs(st, R, Q, tile_live, tid);
+        PHASE(32);
+        segp_label_runs(st, T, labels + (size_t)T.fr * g.npix, sizes + (size_t)T.fr * g.npix, sw, Q.total, tid);
+        PHASE(33);
+        const SegpNbr N = segp_delete_small(st, R, J, tid);
+#pragma unroll 1
+        for (int half = 0; half < NHALF; half++) {
+            const int rlo = NHALF == 1 ? 0 : half * 32, rhi = NHALF == 1 ? SEG_PH - 1 : min(half * 32 + 31, SEG_PH - 1);
+            if (half > 0) __syncthreads();  // the previous half's emit has read PT, BK and BC
+            segp_clear_tables(st, tid);
+            const unsigned long long V = (lane >= rlo && lane <= rhi && y >= 1 && y <= sh - 2) ? J : 0ull;  // emitting pixels: 1 <= x <= sw-2, 1 <= y <= sh-2
+            unsigned long long E[4];
+            segp_site_masks(R, N, V, T.x0, E);
+            segp_list_items(st, R, E, tid);
+            PHASE(37);
+            unsigned int npts, tbase;
+            SegpStatus s = segp_group_park(st, T.fr, tid, npts);
+            PHASE(34);
+            if (s == SEGP_OVER_CAPACITY) {
+                if (!DENSE) {
+                    if (lane == 0 && tile_live) segp_hand_over(dense_tiles, counters, T.id);
+                    PHASE_FLUSH(32);
+                    return;
+                }
+                if (tid == 0) atomicAdd((unsigned long long *)&counters[CNT_OVERFLOW_POINTS], 1ull);
+                continue;
+            }
+            if (s == SEGP_SKIP_HALF) continue;
+            s = segp_reserve(st, out, T.fr, npts, tid, tbase);
+            PHASE(35);
+            if (s == SEGP_SKIP_HALF) continue;
+            segp_emit(st, out, T, npts, tbase, tid);
+            PHASE(36);
+        }
+    }
     PHASE_FLUSH(32);
 }
 
