@@ -53,6 +53,7 @@ EXPORTS = [
     "asl_localize_rig_frames_device", "asl_localize_rig_cov_frames_device", "asl_localize_rig_batch", "asl_localize_rig_cov_batch",
     "asl_map_frames_device", "asl_map_batch", "asl_smooth_frames_device", "asl_smooth_batch", "asl_smooth_cov_frames_device", "asl_smooth_cov_batch",
     "asl_smooth_sequences_device", "asl_smooth_sequences_batch", "asl_smooth_robust_sequences_device", "asl_smooth_robust_sequences_batch",
+    "asl_smooth_timed_sequences_device", "asl_smooth_timed_sequences_batch",
     "asl_debug_fetch", "asl_debug_refit", "asl_debug_dedup", "asl_debug_division_check", "asl_stage_times", "asl_set_profiling", "asl_debug_phase_cycles",
 ]
 
@@ -136,6 +137,8 @@ def load():
     robust = sigmas + [dbl] + solve[3:]                           # ..., sigma_trans, huber_px, max_iters, out, results
     L.asl_smooth_robust_sequences_device.argtypes = smooth + seqs + robust + [vp, vp]
     L.asl_smooth_robust_sequences_batch.argtypes = smooth + seqs + robust + [vp]
+    L.asl_smooth_timed_sequences_device.argtypes = smooth + [vp] + seqs + robust + [vp, vp]    # ..., seed, times, seq_start, ...
+    L.asl_smooth_timed_sequences_batch.argtypes = smooth + [dp] + seqs + robust + [vp]
     L.asl_debug_fetch.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.asl_debug_refit.argtypes = [vp, i32, vp, C.c_size_t]
     L.asl_debug_dedup.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, C.c_size_t]
@@ -525,7 +528,7 @@ class Detector:
                                             _ptr(result_ptr), _ptr(stream)))
 
     def smooth(self, obs, tag_map, K, dist, tag_size, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, seed=None,
-               with_cov=False, huber_px=0.0):
+               with_cov=False, huber_px=0.0, times=None):
         """asl_smooth_batch: host records obs (n_frames, max_tags) OBS_DTYPE of one camera's consecutive frames against tag_map
         -> ((n_frames,) CAM_POSE_DTYPE, world<-camera for EVERY frame, SMOOTH_RESULT_DTYPE record): the reprojection error of
         all frames (corner sigma sigma_px) plus a random-walk motion prior between consecutive frames (sigma_rot rad,
@@ -534,17 +537,22 @@ class Detector:
         with_cov: asl_smooth_cov_batch -> (poses, result, (n_frames,) POSE_COV_DTYPE), every pose's marginal covariance under
         the three sigmas (the same poses and result, byte for byte).
         huber_px > 0: asl_smooth_robust_sequences_batch with the one sequence -- a Huber loss of that many pixels on every
-        corner's residual; a frame's n_rejected and the result's n_soft count the slots it down-weighted.  0.0: the calls above."""
-        return self._smooth_host(obs, None, tag_map, K, dist, tag_size, (sigma_px, sigma_rot, sigma_trans), max_iters, seed, with_cov, huber_px)
+        corner's residual; a frame's n_rejected and the result's n_soft count the slots it down-weighted.  0.0: the calls above.
+        times: (n_frames,) float64, strictly increasing, any unit -- asl_smooth_timed_sequences_batch with the one sequence:
+        sigma_rot and sigma_trans are per unit of that time, a pair of frames dt apart is held by the prior / sqrt(dt).  Bad
+        times (not finite, not increasing) give result status 4, no error.  None: one frame step is one unit, the calls above."""
+        return self._smooth_host(obs, None, tag_map, K, dist, tag_size, (sigma_px, sigma_rot, sigma_trans), max_iters, seed, with_cov, huber_px,
+                                 times)
 
     def smooth_device(self, obs_ptr, n_frames, max_tags, map_ptr, n_ids, seed_ptr, out_ptr, result_ptr, K, dist, tag_size, sigma_px=1.0,
-                      sigma_rot=0.05, sigma_trans=0.5, max_iters=20, stream=0, cov_ptr=None, huber_px=0.0):
+                      sigma_rot=0.05, sigma_trans=0.5, max_iters=20, stream=0, cov_ptr=None, huber_px=0.0, times_ptr=None):
         """asl_smooth_frames_device: obs_ptr (n_frames x max_tags asl_obs), map_ptr (n_ids asl_map_tag), seed_ptr (n_frames
         asl_cam_pose, as localize_device wrote them), out_ptr (n_frames asl_cam_pose) and result_ptr (one asl_smooth_result)
         are device addresses; enqueued on `stream`, no wait.  cov_ptr not None (n_frames asl_pose_cov):
-        asl_smooth_cov_frames_device.  huber_px > 0: asl_smooth_robust_sequences_device with the one sequence."""
+        asl_smooth_cov_frames_device.  huber_px > 0: asl_smooth_robust_sequences_device with the one sequence.  times_ptr not
+        None (n_frames doubles on the device): asl_smooth_timed_sequences_device with the one sequence."""
         self._smooth_device((obs_ptr, map_ptr, seed_ptr, out_ptr, result_ptr), n_frames, max_tags, n_ids, None, K, dist, tag_size,
-                            (sigma_px, sigma_rot, sigma_trans), max_iters, stream, cov_ptr, huber_px)
+                            (sigma_px, sigma_rot, sigma_trans), max_iters, stream, cov_ptr, huber_px, times_ptr)
 
     @staticmethod
     def _seq_start(seq_start, n_frames):
@@ -558,26 +566,31 @@ class Detector:
         return ss, ss.ctypes.data_as(C.POINTER(C.c_int32)), len(ss) - 1
 
     def smooth_sequences(self, obs, seq_start, tag_map, K, dist, tag_size, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20,
-                         seed=None, with_cov=False, huber_px=0.0):
+                         seed=None, with_cov=False, huber_px=0.0, times=None):
         """asl_smooth_sequences_batch: smooth() for several sequences in one call, solved side by side.  obs (n_frames, max_tags)
         OBS_DTYPE holds the sequences end to end, sequence k the frames seq_start[k]:seq_start[k + 1] (n_seq + 1 offsets, from
         0 to n_frames) -> ((n_frames,) CAM_POSE_DTYPE, (n_seq,) SMOOTH_RESULT_DTYPE[, (n_frames,) POSE_COV_DTYPE]): for every
         sequence the bytes smooth() returns for its frames alone.  The map, the camera, the sigmas and max_iters are shared,
-        and so is huber_px (> 0: asl_smooth_robust_sequences_batch, as in smooth())."""
-        return self._smooth_host(obs, seq_start, tag_map, K, dist, tag_size, (sigma_px, sigma_rot, sigma_trans), max_iters, seed, with_cov, huber_px)
+        and so is huber_px (> 0: asl_smooth_robust_sequences_batch, as in smooth()).  times: (n_frames,) float64, every
+        sequence's own frame times end to end (asl_smooth_timed_sequences_batch, as in smooth()); they need to increase inside a
+        sequence only, and a sequence with bad times has result status 4 while the others are solved."""
+        return self._smooth_host(obs, seq_start, tag_map, K, dist, tag_size, (sigma_px, sigma_rot, sigma_trans), max_iters, seed, with_cov, huber_px,
+                                 times)
 
     def smooth_sequences_device(self, obs_ptr, n_frames, max_tags, map_ptr, n_ids, seed_ptr, seq_start, out_ptr, results_ptr, K, dist,
-                                tag_size, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, stream=0, cov_ptr=None, huber_px=0.0):
+                                tag_size, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, stream=0, cov_ptr=None, huber_px=0.0,
+                                times_ptr=None):
         """asl_smooth_sequences_device: smooth_device for several sequences; seq_start is a HOST array of n_seq + 1 offsets,
         results_ptr n_seq asl_smooth_result on the device, cov_ptr None or n_frames asl_pose_cov.  Enqueued on `stream`, no
-        wait; seq_start is read before this returns.  huber_px > 0: asl_smooth_robust_sequences_device."""
+        wait; seq_start is read before this returns.  huber_px > 0: asl_smooth_robust_sequences_device.  times_ptr not None
+        (n_frames doubles on the device): asl_smooth_timed_sequences_device."""
         self._smooth_device((obs_ptr, map_ptr, seed_ptr, out_ptr, results_ptr), n_frames, max_tags, n_ids, seq_start, K, dist, tag_size,
-                            (sigma_px, sigma_rot, sigma_trans), max_iters, stream, cov_ptr, huber_px)
+                            (sigma_px, sigma_rot, sigma_trans), max_iters, stream, cov_ptr, huber_px, times_ptr)
 
-    def _smooth_host(self, obs, seq_start, tag_map, K, dist, tag_size, sigmas, max_iters, seed, with_cov, huber_px=0.0):
+    def _smooth_host(self, obs, seq_start, tag_map, K, dist, tag_size, sigmas, max_iters, seed, with_cov, huber_px=0.0, times=None):
         """smooth (seq_start None: asl_smooth_batch / asl_smooth_cov_batch, whose n_frames bound is a sequence's) and
         smooth_sequences (asl_smooth_sequences_batch); huber_px other than 0.0: asl_smooth_robust_sequences_batch for both, the
-        one sequence [0, n] for smooth"""
+        one sequence [0, n] for smooth; times not None: asl_smooth_timed_sequences_batch for both, huber_px as it is"""
         o, m = _obs_records(obs), _map_records(tag_map)
         keep, Kp, dpp, nd = _camera(K, dist, square=True)
         n = o.shape[0]
@@ -586,34 +599,42 @@ class Detector:
             raise ValueError("seed must hold one pose per frame")
         out = np.zeros(n, dtype=CAM_POSE_DTYPE)
         cov = np.zeros(n, dtype=POSE_COV_DTYPE) if with_cov else None
-        robust = (float(huber_px),) if huber_px != 0.0 else ()
+        tm = None if times is None else np.ascontiguousarray(times, dtype=np.float64).ravel()
+        if tm is not None and len(tm) != n:
+            raise ValueError("times must hold one value per frame")
+        robust = (float(huber_px),) if huber_px != 0.0 or tm is not None else ()
+        timed = () if tm is None else (tm.ctypes.data_as(C.POINTER(C.c_double)),)
         if seq_start is None and not robust:
             fn, seqs, last = (self._L.asl_smooth_cov_batch, (), (_data(cov),)) if with_cov else (self._L.asl_smooth_batch, (), ())
         else:
             ss, ssp, n_seq = self._seq_start([0, n] if seq_start is None else seq_start, n)
-            fn = self._L.asl_smooth_robust_sequences_batch if robust else self._L.asl_smooth_sequences_batch
+            fn = (self._L.asl_smooth_timed_sequences_batch if timed else self._L.asl_smooth_robust_sequences_batch if robust
+                  else self._L.asl_smooth_sequences_batch)
             seqs, last = (ssp, n_seq), (_data(cov) if with_cov else None,)
         res = np.zeros(seqs[1] if seqs else (), dtype=SMOOTH_RESULT_DTYPE)
-        check(fn(self._h, _data(o), n, o.shape[1], _data(m), len(m), Kp, dpp, nd, float(tag_size), None if sd is None else sd.ctypes.data, *seqs,
+        check(fn(self._h, _data(o), n, o.shape[1], _data(m), len(m), Kp, dpp, nd, float(tag_size), None if sd is None else sd.ctypes.data, *timed, *seqs,
                  *map(float, sigmas), *robust, int(max_iters), _data(out), res.ctypes.data, *last))
         if seq_start is None and robust:
             res = res[0]
         return (out, res, cov) if with_cov else (out, res)
 
-    def _smooth_device(self, ptrs, n_frames, max_tags, n_ids, seq_start, K, dist, tag_size, sigmas, max_iters, stream, cov_ptr, huber_px=0.0):
+    def _smooth_device(self, ptrs, n_frames, max_tags, n_ids, seq_start, K, dist, tag_size, sigmas, max_iters, stream, cov_ptr, huber_px=0.0,
+                       times_ptr=None):
         """smooth_device (seq_start None: asl_smooth_frames_device / asl_smooth_cov_frames_device) and smooth_sequences_device
         (asl_smooth_sequences_device); ptrs: the addresses of obs, map, seed, out and result(s); huber_px other than 0.0:
-        asl_smooth_robust_sequences_device for both"""
+        asl_smooth_robust_sequences_device for both; times_ptr not None: asl_smooth_timed_sequences_device for both"""
         obs_ptr, map_ptr, seed_ptr, out_ptr, result_ptr = ptrs
         keep, Kp, dpp, nd = _camera(K, dist, square=True)
-        robust = (float(huber_px),) if huber_px != 0.0 else ()
+        timed = () if times_ptr is None else (_ptr(times_ptr),)
+        robust = (float(huber_px),) if huber_px != 0.0 or timed else ()
         if seq_start is None and not robust:
             fn, seqs, last = (self._L.asl_smooth_frames_device, (), ()) if cov_ptr is None else (self._L.asl_smooth_cov_frames_device, (), (_ptr(cov_ptr),))
         else:
             ss, ssp, n_seq = self._seq_start([0, int(n_frames)] if seq_start is None else seq_start, n_frames)
-            fn = self._L.asl_smooth_robust_sequences_device if robust else self._L.asl_smooth_sequences_device
+            fn = (self._L.asl_smooth_timed_sequences_device if timed else self._L.asl_smooth_robust_sequences_device if robust
+                  else self._L.asl_smooth_sequences_device)
             seqs, last = (ssp, n_seq), (_opt_ptr(cov_ptr),)
-        check(fn(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids), Kp, dpp, nd, float(tag_size), _ptr(seed_ptr), *seqs,
+        check(fn(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids), Kp, dpp, nd, float(tag_size), _ptr(seed_ptr), *timed, *seqs,
                  *map(float, sigmas), *robust, int(max_iters), _ptr(out_ptr), _ptr(result_ptr), *last, _ptr(stream)))
 
     def collect_view(self):

@@ -2,12 +2,22 @@
 // asl_smooth_batch): one camera<-world pose per frame of one camera's consecutive frames, minimising the reprojection
 // error of all mapped corners (/ sigma_px^2) plus |(Log(R_D) / sigma_rot, t_D / sigma_trans)|^2 between consecutive
 // frames, R_D = R_{f+1} R_f^T, t_D = t_{f+1} - R_D t_f.  tests/smooth_ref.py is the NumPy statement of the same
-// computation, operation order of the linear solve included.  float64, contraction off, no scratch.
+// computation, operation order of the linear solve included.  float64, contraction off, no scratch.  One frame step is one
+// unit of time unless the call gives the frames' times (below).
 // asl_smooth_robust_sequences_* (huber_px > 0): the same launches with k_smooth_cand<true> and k_smooth_lin<true>, which put every
 // corner's pixel residual through a Huber loss (loc_corner<NE, true>, k_localize.inc): its cost in every place the squared
 // one stands, its weight on J^T J and J^T r, and per frame the number of slots with a corner over the threshold, carried
 // with the state (SmoothSet.soft) as the pixel cost is.  tests/smooth_ref.py states it at huber_px > 0.  The plain calls run
 // the <false> instantiations: the code they ran before, the counts 0.
+// asl_smooth_timed_sequences_* (SmoothBufs.times, n doubles on the device): frame f is at time times[f], and sigma_rot and
+// sigma_trans are the random walk's per unit of that time.  The pair (f, f + 1) of a sequence, dt = times[f + 1] - times[f], has
+// m_f = (Log(R_D) w_rot, t_D w_trans), w_rot = (1 / sigma_rot) (1 / sqrt(dt)), w_trans = (1 / sigma_trans) (1 / sqrt(dt)), in
+// that operation order, so dt == 1 is the plain weight to the bit; k_smooth_lin's Jacobians, blocks and |m|^2 are built from
+// them, and the solve, the decide and the covariance read those blocks as they are.  The chain divides a transition cost by
+// times[f] - times[p] where the plain call divides by f - p.  Times of two sequences are unrelated.  A sequence with a time that
+// is not finite or a dt <= 0 is found by k_smooth_scan and solved as one without a posed frame, result status 4.  Every other
+// call leaves times NULL: a branch on the pointer, one value in the whole launch, ahead of each of the three places; no
+// instantiation of its own.  tests/smooth_timed_ref.py states it.
 //   seed chain   k_smooth_cand   one wavefront per frame: the seed's pose A and, for a frame of exactly one taking-part slot,
 //                                its mirrored planar minimum B (loc_candidate), both costed over the frame's corners
 //                k_smooth_scan   one wavefront a sequence: the nearest posed frame at or before every frame (wave_scan of a maximum)
@@ -43,7 +53,7 @@ struct SmoothResultRec {  // == asl_smooth_result, 64 bytes
 };
 
 enum { SM_COST = 0, SM_LAMBDA, SM_STOP, SM_ITERS, SM_STATUS, SM_COST0, SM_SOLVED, SM_PIX, SM_PIX0, SM_CORNERS, SM_NDATA, SM_TAKE, SM_COV, SM_SOFT, SM__N = 16 };
-enum { SMH_NPOSED = 0, SMH_FIRST, SMH_FAIL, SMH_NFLIP, SMH__N = 4 };
+enum { SMH_NPOSED = 0, SMH_FIRST, SMH_FAIL, SMH_NFLIP, SMH_BADT, SMH__N = 8 };   // SMH_BADT: the sequence's times are bad (status 4)
 #define SM_MOT 121                // per pair: QN 36, QP 36, C 36, gN 6, gP 6, |m|^2
 // One state's arrays, in doubles per frame from the start of the allocation: pose (R 9, t 3), packed normal equations
 // (21 + 6), pixel cost, soft slots, motion blocks.  smooth_set() and smooth_set_at() are the two readings of this layout.
@@ -78,6 +88,7 @@ struct SmoothBufs {
     double *lm, *cseed, *delta, *fac;
     double *set[2];                 // the current state and the trial
     int *seq, *fseq;                // n_seq > 1: the sequences' first frames (n_seq + 1) and every frame's sequence (k_smooth_seqs)
+    const double *times;            // the timed calls' frame times (n); NULL: frame f is at time f
     int n, n_seq;                   // lm and head: n_seq of each
 };
 
@@ -280,16 +291,21 @@ __global__ void __launch_bounds__(64) k_smooth_cand(const ObsRec *__restrict__ o
 }
 
 // A sequence's src[f]: the nearest posed frame of the sequence at or before f (-1: none), as a frame of the call; its head:
-// the number of posed frames and the first one
+// the number of posed frames and the first one.  Timed: a time that is not finite, or a pair of the sequence with
+// times[f + 1] - times[f] <= 0, makes it a sequence without a posed frame and sets SMH_BADT (k_smooth_init: status 4)
 __global__ void __launch_bounds__(64) k_smooth_scan(SmoothBufs b)
 {
     const int lane = (int)threadIdx.x;
     const SmoothSeq q = smooth_seq_uniform(b, (int)blockIdx.x);
     int *head = b.head + SMH__N * q.k;
-    int carry = -1, np = 0, first = -1;
+    int carry = -1, np = 0, first = -1, bad = 0;
     for (int base = 0; base < q.n; base += ASL_WAVE) {
         const int f = q.f0 + base + lane;
         const bool in = base + lane < q.n;
+        if (b.times && in) {  // one value in the whole wavefront: the plain calls skip it
+            const double t = b.times[f];
+            bad |= !isfinite(t) || (base + lane > 0 && !(t - b.times[f - 1] > 0)) ? 1 : 0;
+        }
         const int v = (in && b.posed[f]) ? f : -1;
         int s = wave_scan<false>(v, -1, [](int x, int y) { return x > y ? x : y; });
         s = s > carry ? s : carry;
@@ -299,10 +315,13 @@ __global__ void __launch_bounds__(64) k_smooth_scan(SmoothBufs b)
         const int mn = wave_scan<true>(v >= 0 ? v : 0x7fffffff, 0x7fffffff, [](int x, int y) { return x < y ? x : y; });
         if (first < 0 && mn != 0x7fffffff) first = mn;
     }
-    if (lane == 0) { head[SMH_NPOSED] = np; head[SMH_FIRST] = first; head[SMH_FAIL] = 0; head[SMH_NFLIP] = 0; }
+    bad = butterfly_sum<64>(bad) != 0;
+    if (bad) np = 0;   // nothing is solved: every kernel after this one treats the sequence as one without a posed frame
+    if (lane == 0) { head[SMH_NPOSED] = np; head[SMH_FIRST] = first; head[SMH_FAIL] = 0; head[SMH_NFLIP] = 0; head[SMH_BADT] = bad; }
 }
 
-// The four transition costs of a posed frame from its predecessor, over a gap of g frame steps divided by g
+// The four transition costs of a posed frame from its predecessor, over a gap of g frame steps (timed: of g = times[f] -
+// times[p]) divided by g
 __global__ void __launch_bounds__(64) k_smooth_trans(SmoothBufs b, double isr, double ist)
 {
     const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
@@ -310,7 +329,7 @@ __global__ void __launch_bounds__(64) k_smooth_trans(SmoothBufs b, double isr, d
     const int p = f > smooth_seq_of(b, f).f0 ? b.src[f - 1] : -1;
     double *tc = b.tcost + 4 * (size_t)f;
     if (p < 0) { tc[0] = 0; tc[1] = 0; tc[2] = 0; tc[3] = 0; return; }
-    const double gap = (double)(f - p);
+    const double gap = b.times ? b.times[f] - b.times[p] : (double)(f - p);
     double Pa[12], Pb[12], RD[9], tD[3], m[6];
     for (int a = 0; a < 2; a++)
         for (int c = 0; c < 2; c++) {
@@ -398,7 +417,8 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_fill(SmoothBufs b, const CamPo
 
 // Frame f of a state: its pose (trial: the current one stepped by delta), pixel cost, H and g, and the motion blocks of
 // the pair (f, f + 1) at the same state.  ROBUST: the cost is the Huber loss of threshold hk pixels, H and g are the sums
-// weighted by it (iteratively reweighted Gauss-Newton, no second-order term), and the state carries the frame's soft slots
+// weighted by it (iteratively reweighted Gauss-Newton, no second-order term), and the state carries the frame's soft slots.
+// Timed: the pair's weights are (isr, ist) / sqrt(times[f + 1] - times[f]), the random walk's over that time
 template <bool ROBUST>
 __global__ void __launch_bounds__(64) k_smooth_lin(const ObsRec *__restrict__ obs, int max_tags, const MapTagRec *__restrict__ map, int n_ids,
                                                    CamDev cam, SmoothBufs b, int trial, double isr, double ist, double hk)
@@ -448,6 +468,11 @@ __global__ void __launch_bounds__(64) k_smooth_lin(const ObsRec *__restrict__ ob
 #pragma unroll
         for (int k = 0; k < 6; k++) d[k] = b.delta[6 * (size_t)(f + 1) + k];
         smooth_update(Q, d);
+    }
+    if (b.times) {  // one value in the whole wavefront; a step of exactly 1 leaves both weights as they are
+        const double isd = 1.0 / sqrt(b.times[f + 1] - b.times[f]);
+        isr = isr * isd;
+        ist = ist * isd;
     }
     const double mm = smooth_residual(P, Q, isr, ist, RD, tD, mv);
     double *mot = out.mot + SM_MOT * (size_t)f;
@@ -512,7 +537,7 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_init(SmoothBufs b, double w)
     if (b.head[SMH__N * q.k + SMH_NPOSED] == 0) {
         if (tid < SM__N) lm[tid] = 0.0;
         __syncthreads();
-        if (tid == 0) { lm[SM_STOP] = 1.0; lm[SM_STATUS] = 1.0; }
+        if (tid == 0) { lm[SM_STOP] = 1.0; lm[SM_STATUS] = b.head[SMH__N * q.k + SMH_BADT] ? 4.0 : 1.0; }
         return;
     }
     const SmoothSet s = smooth_set(b.set[0], (size_t)b.n);

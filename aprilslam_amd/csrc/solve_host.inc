@@ -560,17 +560,18 @@ extern "C" int asl_map_batch(asl_detector *d, const asl_obs *obs, int n_frames, 
 #define SMOOTH_SEQS 65535         // sequences of one call
 #define SMOOTH_FRAMES 1048576     // frames of one call: the work buffers, about 3.6 KB a frame, stay under 4 GB
 
-// One smoothing call, whichever of the eight entry points made it, in their argument order.  The single-sequence forms leave
+// One smoothing call, whichever of the ten entry points made it, in their argument order.  The single-sequence forms leave
 // seq_start NULL, n_seq 1 and sequences false: the one sequence {0, n_frames}; seq_start is a host array of n_seq + 1
 // offsets in every form.  The plain forms leave cov NULL and with_cov false; the sequences forms set with_cov where cov is
 // given.  The host forms may leave seed NULL: the per-frame localisation of the same block.  obs, map, seed, out, result
 // and cov are all host or all device pointers.  huber_px: 0 from the six plain entry points (the squared corner loss and
-// its kernels), the robust pair's threshold in pixels otherwise.
+// its kernels), the robust and the timed pairs' threshold in pixels otherwise.  times: NULL from the eight entry points
+// without it (frame f is at time f), the timed pair's n_frames doubles otherwise, a host or a device array as the rest.
 struct SmoothCall {
     const void *obs; int n_frames, max_tags;
     const void *map; int n_ids;
     Camera cam;
-    const void *seed; const int32_t *seq_start; int n_seq;
+    const void *seed, *times; const int32_t *seq_start; int n_seq;
     double sigma_px, sigma_rot, sigma_trans, huber_px; int max_iters;
     void *out, *result, *cov;
     bool with_cov, sequences;
@@ -582,8 +583,8 @@ static bool smooth_overlap(const void *a, size_t a_bytes, const void *b, size_t 
     return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
-// Every refusal, before anything is written or enqueued.  device: the seed must be there, and the outputs apart from it
-// and from each other (host arrays are apart by contract).
+// Every refusal, before anything is written or enqueued.  device: the seed must be there, and the outputs apart from it,
+// from the times and from each other (host arrays are apart by contract).  The times' values are the device's to judge.
 static int check_smooth_call(const asl_detector *d, const SmoothCall &c, bool device)
 {
     if (!d) return fail(ASL_EINVAL, "NULL detector");
@@ -612,18 +613,21 @@ static int check_smooth_call(const asl_detector *d, const SmoothCall &c, bool de
     if (smooth_overlap(c.seed, poses, c.out, poses)) return fail(ASL_EINVAL, "d_out overlaps d_seed");
     if (c.with_cov && (smooth_overlap(c.cov, covs, c.out, poses) || smooth_overlap(c.cov, covs, c.seed, poses)))
         return fail(ASL_EINVAL, "d_cov overlaps d_out or d_seed");
+    const size_t times = sizeof(double) * (size_t)c.n_frames;
+    if (c.times && (smooth_overlap(c.times, times, c.out, poses) || (c.with_cov && smooth_overlap(c.times, times, c.cov, covs))))
+        return fail(ASL_EINVAL, "d_times overlaps d_out or d_cov");
     return ASL_OK;
 }
 
 // c's pointers are the device's but seq_start (host, not read for n_seq 1); everything is enqueued on st, nothing waits.
 // cov: NULL, or the frames' asl_pose_cov (two more launches).  n_seq > 1: k_smooth_seqs first, a launch per SM_SEQ_CHUNK
 // sequences, which carries the offsets to the device in its arguments.  huber_px > 0: the robust instantiations of the two
-// kernels that cost corners, the same launches otherwise.
+// kernels that cost corners, the same launches otherwise.  times: carried in SmoothBufs, the same launches.
 static int launch_smooth(asl_detector *d, const SmoothCall &c, hipStream_t st)
 {
     const size_t n = (size_t)c.n_frames, ns = (size_t)c.n_seq;
     SmoothBufs b{};
-    b.n = c.n_frames; b.n_seq = c.n_seq;
+    b.n = c.n_frames; b.n_seq = c.n_seq; b.times = (const double *)c.times;
     if (carve_ws(d->smooth_ws, [&](WsCarve &ws) {
             b.cand = ws.take<double>(24 * n); b.dcost = ws.take<double>(2 * n); b.tcost = ws.take<double>(4 * n);
             b.posed = ws.take<int>(n); b.ntags = ws.take<int>(n); b.src = ws.take<int>(n); b.back = ws.take<int>(n); b.choice = ws.take<int>(n);
@@ -682,18 +686,19 @@ static int launch_smooth(asl_detector *d, const SmoothCall &c, hipStream_t st)
     return ASL_OK;
 }
 
-static constexpr auto smooth_frames_device = frames_device<SmoothCall, check_smooth_call, launch_smooth>;   // the four device forms
+static constexpr auto smooth_frames_device = frames_device<SmoothCall, check_smooth_call, launch_smooth>;   // the five device forms
 
-// the four host forms; a seed not given is the per-frame localisation of the same block, gate 0
+// the five host forms; a seed not given is the per-frame localisation of the same block, gate 0; times are staged as a seed is
 static int smooth_batch(asl_detector *d, const SmoothCall &c)
 {
     if (int rc = check_smooth_call(d, c, false)) return rc;
     const size_t poses = sizeof(asl_cam_pose) * (size_t)c.n_frames;
     OutPiece o[] = {{c.result, sizeof(asl_smooth_result) * (size_t)c.n_seq}, {c.out, poses}, {nullptr, poses},
-                    {c.cov, c.cov ? sizeof(asl_pose_cov) * (size_t)c.n_frames : 0}};
+                    {c.cov, c.cov ? sizeof(asl_pose_cov) * (size_t)c.n_frames : 0}, {nullptr, c.times ? sizeof(double) * (size_t)c.n_frames : 0}};
     if (int rc = stage_host_call(d, "sequence localisation", o, c.obs, c.n_frames, c.max_tags, c.map, c.n_ids)) return rc;
     SmoothCall dc = c;
-    dc.obs = d->loc_obs.p; dc.map = d->loc_map.p; dc.result = o[0].dev; dc.out = o[1].dev; dc.seed = o[2].dev; dc.cov = o[3].dev;
+    dc.obs = d->loc_obs.p; dc.map = d->loc_map.p; dc.result = o[0].dev; dc.out = o[1].dev; dc.seed = o[2].dev; dc.cov = o[3].dev; dc.times = o[4].dev;
+    if (c.times) HIPCHK(hipMemcpy(o[4].dev, c.times, o[4].bytes, hipMemcpyHostToDevice));
     if (c.seed)
         HIPCHK(hipMemcpy(o[2].dev, c.seed, poses, hipMemcpyHostToDevice));
     else if (int rc = launch_localize(d, {dc.obs, 0, c.n_frames, c.max_tags, dc.map, c.n_ids, nullptr, c.cam, 0.0, 0.0, o[2].dev, nullptr, false}, nullptr))
@@ -706,7 +711,7 @@ extern "C" int asl_smooth_frames_device(asl_detector *d, const void *d_obs, int 
                                         const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed, double sigma_px,
                                         double sigma_rot, double sigma_trans, int max_iters, void *d_out, void *d_result, void *stream)
 {
-    return smooth_frames_device(d, {d_obs, n_frames, max_tags, d_map, n_ids, {K, dist, n_dist, tag_size}, d_seed, nullptr, 1,
+    return smooth_frames_device(d, {d_obs, n_frames, max_tags, d_map, n_ids, {K, dist, n_dist, tag_size}, d_seed, nullptr, nullptr, 1,
                                     sigma_px, sigma_rot, sigma_trans, 0.0, max_iters, d_out, d_result, nullptr, false, false}, stream);
 }
 
@@ -715,7 +720,7 @@ extern "C" int asl_smooth_cov_frames_device(asl_detector *d, const void *d_obs, 
                                             double sigma_px, double sigma_rot, double sigma_trans, int max_iters, void *d_out, void *d_result,
                                             void *d_cov, void *stream)
 {
-    return smooth_frames_device(d, {d_obs, n_frames, max_tags, d_map, n_ids, {K, dist, n_dist, tag_size}, d_seed, nullptr, 1,
+    return smooth_frames_device(d, {d_obs, n_frames, max_tags, d_map, n_ids, {K, dist, n_dist, tag_size}, d_seed, nullptr, nullptr, 1,
                                     sigma_px, sigma_rot, sigma_trans, 0.0, max_iters, d_out, d_result, d_cov, true, false}, stream);
 }
 
@@ -724,7 +729,7 @@ extern "C" int asl_smooth_sequences_device(asl_detector *d, const void *d_obs, i
                                            const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
                                            int max_iters, void *d_out, void *d_results, void *d_cov, void *stream)
 {
-    return smooth_frames_device(d, {d_obs, n_frames, max_tags, d_map, n_ids, {K, dist, n_dist, tag_size}, d_seed, seq_start, n_seq,
+    return smooth_frames_device(d, {d_obs, n_frames, max_tags, d_map, n_ids, {K, dist, n_dist, tag_size}, d_seed, nullptr, seq_start, n_seq,
                                     sigma_px, sigma_rot, sigma_trans, 0.0, max_iters, d_out, d_results, d_cov, d_cov != nullptr, true}, stream);
 }
 
@@ -732,7 +737,7 @@ extern "C" int asl_smooth_batch(asl_detector *d, const asl_obs *obs, int n_frame
                                 const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed, double sigma_px,
                                 double sigma_rot, double sigma_trans, int max_iters, asl_cam_pose *out, asl_smooth_result *result)
 {
-    return smooth_batch(d, {obs, n_frames, max_tags, map, n_ids, {K, dist, n_dist, tag_size}, seed, nullptr, 1,
+    return smooth_batch(d, {obs, n_frames, max_tags, map, n_ids, {K, dist, n_dist, tag_size}, seed, nullptr, nullptr, 1,
                             sigma_px, sigma_rot, sigma_trans, 0.0, max_iters, out, result, nullptr, false, false});
 }
 
@@ -741,7 +746,7 @@ extern "C" int asl_smooth_cov_batch(asl_detector *d, const asl_obs *obs, int n_f
                                     double sigma_rot, double sigma_trans, int max_iters, asl_cam_pose *out, asl_smooth_result *result,
                                     asl_pose_cov *cov)
 {
-    return smooth_batch(d, {obs, n_frames, max_tags, map, n_ids, {K, dist, n_dist, tag_size}, seed, nullptr, 1,
+    return smooth_batch(d, {obs, n_frames, max_tags, map, n_ids, {K, dist, n_dist, tag_size}, seed, nullptr, nullptr, 1,
                             sigma_px, sigma_rot, sigma_trans, 0.0, max_iters, out, result, cov, true, false});
 }
 
@@ -750,7 +755,7 @@ extern "C" int asl_smooth_sequences_batch(asl_detector *d, const asl_obs *obs, i
                                           const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
                                           int max_iters, asl_cam_pose *out, asl_smooth_result *results, asl_pose_cov *cov)
 {
-    return smooth_batch(d, {obs, n_frames, max_tags, map, n_ids, {K, dist, n_dist, tag_size}, seed, seq_start, n_seq,
+    return smooth_batch(d, {obs, n_frames, max_tags, map, n_ids, {K, dist, n_dist, tag_size}, seed, nullptr, seq_start, n_seq,
                             sigma_px, sigma_rot, sigma_trans, 0.0, max_iters, out, results, cov, cov != nullptr, true});
 }
 
@@ -759,7 +764,7 @@ extern "C" int asl_smooth_robust_sequences_device(asl_detector *d, const void *d
                                                   const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
                                                   double huber_px, int max_iters, void *d_out, void *d_results, void *d_cov, void *stream)
 {
-    return smooth_frames_device(d, {d_obs, n_frames, max_tags, d_map, n_ids, {K, dist, n_dist, tag_size}, d_seed, seq_start, n_seq,
+    return smooth_frames_device(d, {d_obs, n_frames, max_tags, d_map, n_ids, {K, dist, n_dist, tag_size}, d_seed, nullptr, seq_start, n_seq,
                                     sigma_px, sigma_rot, sigma_trans, huber_px, max_iters, d_out, d_results, d_cov, d_cov != nullptr, true}, stream);
 }
 
@@ -768,6 +773,26 @@ extern "C" int asl_smooth_robust_sequences_batch(asl_detector *d, const asl_obs 
                                                  const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
                                                  double huber_px, int max_iters, asl_cam_pose *out, asl_smooth_result *results, asl_pose_cov *cov)
 {
-    return smooth_batch(d, {obs, n_frames, max_tags, map, n_ids, {K, dist, n_dist, tag_size}, seed, seq_start, n_seq,
+    return smooth_batch(d, {obs, n_frames, max_tags, map, n_ids, {K, dist, n_dist, tag_size}, seed, nullptr, seq_start, n_seq,
                             sigma_px, sigma_rot, sigma_trans, huber_px, max_iters, out, results, cov, cov != nullptr, true});
+}
+
+extern "C" int asl_smooth_timed_sequences_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                                 const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed,
+                                                 const double *d_times, const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot,
+                                                 double sigma_trans, double huber, int max_iters, void *d_out, void *d_results, void *d_cov,
+                                                 void *stream)
+{
+    return smooth_frames_device(d, {d_obs, n_frames, max_tags, d_map, n_ids, {K, dist, n_dist, tag_size}, d_seed, d_times, seq_start, n_seq,
+                                    sigma_px, sigma_rot, sigma_trans, huber, max_iters, d_out, d_results, d_cov, d_cov != nullptr, true}, stream);
+}
+
+extern "C" int asl_smooth_timed_sequences_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                                const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed,
+                                                const double *times, const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot,
+                                                double sigma_trans, double huber, int max_iters, asl_cam_pose *out, asl_smooth_result *results,
+                                                asl_pose_cov *cov)
+{
+    return smooth_batch(d, {obs, n_frames, max_tags, map, n_ids, {K, dist, n_dist, tag_size}, seed, times, seq_start, n_seq,
+                            sigma_px, sigma_rot, sigma_trans, huber, max_iters, out, results, cov, cov != nullptr, true});
 }

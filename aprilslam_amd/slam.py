@@ -249,11 +249,12 @@ class SLAM:
 
     def localize_sequence(self, dets, poses, n_per_frame, **kw):
         """Camera poses of consecutive frames against tag_map(), solved together with a motion prior
-        (TagDetector.localize_sequence); like localize it leaves the graph, the window and my_pose() alone."""
+        (TagDetector.localize_sequence, whose keywords pass through: times=... for frames that are not evenly spaced); like
+        localize it leaves the graph, the window and my_pose() alone."""
         return self.detector.localize_sequence(dets, poses, n_per_frame, self.tag_map(), **kw)
 
     def localize_sequences(self, sequences, **kw):
-        """Several sequences of consecutive frames ((dets, poses, n_per_frame) triples) against tag_map(), solved side by side in
+        """Several sequences of consecutive frames ((dets, poses, n_per_frame) triples, or 4-tuples with frame times) against tag_map(), solved side by side in
         one call (TagDetector.localize_sequences) -> a list of smooth.SmoothResult; the graph, the window and my_pose() stay
         as they are."""
         return self.detector.localize_sequences(sequences, self.tag_map(), **kw)

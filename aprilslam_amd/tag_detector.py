@@ -218,7 +218,7 @@ class TagDetector:
                                            sigma_px=float(sigma_px) if with_cov else None)
 
     def localize_sequence(self, dets, poses, n_per_frame, tag_map, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20,
-                          max_tags=None, with_cov=False, huber_px=0.0):
+                          max_tags=None, with_cov=False, huber_px=0.0, times=None):
         """The structured arrays detect_host / collect return for one camera's CONSECUTIVE frames -> smooth.SmoothResult: a
         world<-camera pose for every frame, the frames solved together with a random-walk motion prior (sigma_rot rad and
         sigma_trans scene units per frame step) next to the corners (sigma_px).  Packs, localises every frame on its own
@@ -226,7 +226,10 @@ class TagDetector:
         carries every pose's covariance under the three sigmas (.cov, .cov_status, .pose_std()), the frames carried by the
         prior alone included.  huber_px > 0: a Huber loss of that many pixels on every corner's residual
         (asl_smooth_robust_sequences_batch), for a slipped corner or a slot with another tag's corners; the result's .n_soft
-        and .soft say which slots and frames it down-weighted.  Its linear tail needs more trials: raise max_iters."""
+        and .soft say which slots and frames it down-weighted.  Its linear tail needs more trials: raise max_iters.
+        times: one strictly increasing time per frame, any unit (asl_smooth_timed_sequences_batch): sigma_rot and sigma_trans
+        are then per unit of that time, so frames may be dropped or unevenly spaced; the result keeps them (.times) and
+        .pose_at(t) gives the pose between two frames.  Bad times: the result's status is 4, no error."""
         from .dist import pack_observations
         from .smooth import SmoothResult
         npf = np.asarray(n_per_frame, dtype=np.int64)
@@ -235,12 +238,14 @@ class TagDetector:
         det = self.detector._det
         seed = det.localize(obs, tag_map, self._K(), self._dist(), self.tag_size)
         got = det.smooth(obs, tag_map, self._K(), self._dist(), self.tag_size, sigma_px=sigma_px, sigma_rot=sigma_rot,
-                         sigma_trans=sigma_trans, max_iters=max_iters, seed=seed, with_cov=with_cov, huber_px=huber_px)
-        return SmoothResult(got[0], got[1], seed, got[2] if with_cov else None)
+                         sigma_trans=sigma_trans, max_iters=max_iters, seed=seed, with_cov=with_cov, huber_px=huber_px,
+                         times=times)
+        return SmoothResult(got[0], got[1], seed, got[2] if with_cov else None, times)
 
     def localize_sequences(self, sequences, tag_map, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, max_tags=None,
                            with_cov=False, huber_px=0.0):
-        """localize_sequence for several sequences in one call: `sequences` is a list of (dets, poses, n_per_frame) triples as
+        """localize_sequence for several sequences in one call: `sequences` is a list of (dets, poses, n_per_frame) triples (or
+        4-tuples with the sequence's frame times last; where some have them, a sequence without gets its frame indices) as
         detect_host / collect return them, each one camera's consecutive frames (different cameras, recordings, or the pieces
         of a recording cut where the camera was off) -> a list of smooth.SmoothResult, one per sequence, each what
         localize_sequence returns for it alone at the same max_tags.  Packs them end to end with one common max_tags,
@@ -256,11 +261,17 @@ class TagDetector:
         mt = int(max_tags) if max_tags is not None else max(1, min(256, max(int(n.max()) for n in npfs)))
         obs = np.concatenate([pack_observations(s[0], s[1], n, mt) for s, n in zip(sequences, npfs)])
         start = np.concatenate([[0], np.cumsum([len(n) for n in npfs])])
+        tms = [np.asarray(s[3], dtype=np.float64).ravel() if len(s) > 3 and s[3] is not None else None for s in sequences]
+        if any(t is not None and len(t) != len(n) for t, n in zip(tms, npfs)):
+            raise ValueError("a sequence's times must hold one value per frame")
+        timed = any(t is not None for t in tms)
+        times = np.concatenate([np.arange(len(n), dtype=np.float64) if t is None else t for t, n in zip(tms, npfs)]) if timed else None
         det = self.detector._det
         seed = det.localize(obs, tag_map, self._K(), self._dist(), self.tag_size)
         got = det.smooth_sequences(obs, start, tag_map, self._K(), self._dist(), self.tag_size, sigma_px=sigma_px, sigma_rot=sigma_rot,
-                                   sigma_trans=sigma_trans, max_iters=max_iters, seed=seed, with_cov=with_cov, huber_px=huber_px)
-        return [SmoothResult(got[0][a:b], got[1][k], seed[a:b], got[2][a:b] if with_cov else None)
+                                   sigma_trans=sigma_trans, max_iters=max_iters, seed=seed, with_cov=with_cov, huber_px=huber_px,
+                                   times=times)
+        return [SmoothResult(got[0][a:b], got[1][k], seed[a:b], got[2][a:b] if with_cov else None, tms[k])
                 for k, (a, b) in enumerate(zip(start[:-1], start[1:]))]
 
     # -- camera calibration from frames of a known target (asl_calibrate_batch) ------------------------------------------

@@ -405,7 +405,8 @@ typedef struct {
     int32_t n_flipped;             /* frames where the chain chose the mirrored candidate */
     int32_t iterations;            /* LM trials run */
     int32_t status;                /* 0 ok, 1 no frame with a seed pose (nothing solved), 2 never positive definite,
-                                      3 non-finite cost after the chain */
+                                      3 non-finite cost after the chain, 4 (asl_smooth_timed_sequences_*) the sequence's
+                                      times are bad: one not finite, or two consecutive ones that do not increase */
     int32_t n_soft;                /* asl_smooth_robust_sequences_*: taking-part slots, over all frames, with a corner over the
                                       threshold at the returned poses (the frames' n_rejected summed); 0 from the plain calls */
     int32_t reserved[2];
@@ -432,7 +433,8 @@ typedef struct {
    status 2 or 3; T is the chain's), 1 nothing to solve (T the identity).  d_result: one asl_smooth_result.
    ASL_EINVAL, nothing written: a NULL pointer; n_frames outside [1, 65535]; max_tags outside [1, 256]; n_dist not 0, 4 or 5,
    or n_dist > 0 with dist NULL; a non-finite K, tag_size or sigma; a sigma <= 0; max_iters outside [1, 100]; d_out
-   overlapping d_seed.  One sequence per call (several: asl_smooth_sequences_device), even frame spacing.  Deterministic:
+   overlapping d_seed.  One sequence per call (several: asl_smooth_sequences_device), one frame step one unit of time
+   (frame times: asl_smooth_timed_sequences_device).  Deterministic:
    the same input gives the same bytes.  tests/smooth_ref.py states the algorithm. */
 int asl_smooth_frames_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
                              const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed, double sigma_px,
@@ -524,6 +526,37 @@ int asl_smooth_robust_sequences_batch(asl_detector *det, const asl_obs *obs, int
                                       const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed,
                                       const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
                                       double huber_px, int max_iters, asl_cam_pose *out, asl_smooth_result *results, asl_pose_cov *cov);
+
+/* asl_smooth_robust_sequences_device with a time for every frame, for footage whose frames are not evenly spaced: dropped
+   frames, a camera pause, a variable frame rate.  d_times: n_frames doubles on the device, any unit, read in stream order
+   (no host wait); sigma_rot and sigma_trans are then the random walk's sigmas per unit of that time.  The pair (f, f + 1) of
+   a sequence, dt = d_times[f + 1] - d_times[f], has the motion residual (Log(R_D) w_rot, t_D w_trans) with
+   w_rot = (1 / sigma_rot) (1 / sqrt(dt)) and w_trans = (1 / sigma_trans) (1 / sqrt(dt)): its cost is the plain one divided by
+   dt, which is what marginalising dt - 1 evenly spaced frames without data out of the plain problem leaves.  The seed chain
+   divides the motion cost between a posed frame and its posed predecessor p by d_times[f] - d_times[p] where the plain call
+   divides by f - p.  Nothing else changes: the corner costs (huber as huber_px of the robust call, 0: squared), the linear
+   solve, the LM schedule, the fill, the outputs; d_cov is the inverse of the timed matrix.  Times of different sequences
+   are unrelated: no term links two sequences, so a later sequence may start at an earlier time.
+   d_times NULL is frame f at time f: d_out, d_results and d_cov are byte for byte what asl_smooth_robust_sequences_device
+   writes; so are they for times of unit spacing, d_times[f] = c + f with exact differences.
+   Bad times are found on the device, per sequence: a time that is not finite, or a dt <= 0 inside the sequence (a sequence
+   of one frame needs only a finite time).  That sequence's result has status 4 and is otherwise the result of status 1, its
+   frames have the records of status 1 (T the identity, seed_slot -1), its d_cov records status 1; the other sequences of
+   the call are what they are without it, so a sequence of a batch stays byte for byte what the call alone returns.
+   ASL_EINVAL, nothing written: whatever asl_smooth_robust_sequences_device refuses; d_times overlapping d_out or d_cov.
+   Nothing waits; deterministic: the same input gives the same bytes.  tests/smooth_timed_ref.py states the computation. */
+int asl_smooth_timed_sequences_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                      const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed,
+                                      const double *d_times, const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot,
+                                      double sigma_trans, double huber, int max_iters, void *d_out, void *d_results, void *d_cov,
+                                      void *stream);
+/* The same computation on host records, synchronous; times: a host array of n_frames doubles or NULL, copied to the device
+   as the seed is; bad times give status 4 here too, not ASL_EINVAL.  seed == NULL as in asl_smooth_sequences_batch. */
+int asl_smooth_timed_sequences_batch(asl_detector *det, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                     const double *K, const double *dist, int n_dist, double tag_size, const asl_cam_pose *seed,
+                                     const double *times, const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot,
+                                     double sigma_trans, double huber, int max_iters, asl_cam_pose *out, asl_smooth_result *results,
+                                     asl_pose_cov *cov);
 
 /* ---- before the detector: the image-formation step on the device (reference src/simulation/renderer.py:197-274:
    purple clear colour, one GL_LINEAR-textured quad per tag, BGR read-back).  One plane per visible tag and frame, in

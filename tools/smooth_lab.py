@@ -16,11 +16,18 @@ call out (a build that does not have it).  --huber K adds the robust call (asl_s
 K pixels) on the same input, alternating with the plain one: under "robust" its time, trials, ms per trial next to the plain
 call's, n_soft and the position RMSE against the truth next to the plain call's; with --sequences also the batched robust
 call.  --outliers N corrupts N taking-part slots first (--outlier-seed): half get one corner moved by 8 px, half the corners
-of another slot of their frame.
+of another slot of their frame.  --jitter J gives frame f the time f + J u_f, u_f uniform in (-0.5, 0.5) (J < 1; 0: unit spacing, the
+plain call's bytes) and adds the timed call (asl_smooth_timed_sequences_device) on the same input, alternating with the plain
+one: under "timed" its time, trials and position RMSE.  --gap LO:HI drops the frames [LO, HI) and adds three legs, again
+alternating: the timed call on the kept frames (their times as above), the naive call (the plain one on the kept frames, the
+gap taken for one frame step) and the plain call on all frames with the block emptied; under "gap" the time and trials of each,
+the position RMSE of each against the truth over the four frames next to the gap and over all kept frames, and the largest
+relative difference of a kept frame's T between the timed and the emptied solve (the same minimum without --jitter; with it the
+emptied solve, which has no times, is another problem).
 
     python tools/smooth_lab.py [--frames 1024] [--reps 20] [--max-tags 32] [--sigma-px 0.3] [--sigma-rot 0.01]
                                [--sigma-trans 0.05] [--max-iters 20] [--drop-every 0] [--cov] [--sequences S [--loop-only]]
-                               [--huber K] [--outliers N [--outlier-seed 1]]
+                               [--huber K] [--outliers N [--outlier-seed 1]] [--jitter J [--jitter-seed 1]] [--gap LO:HI]
 """
 import argparse
 import json
@@ -55,9 +62,17 @@ def main():
     ap.add_argument("--huber", type=float, default=0.0, help="also run the robust call with this Huber threshold in pixels")
     ap.add_argument("--outliers", type=int, default=0, help="corrupt N taking-part slots: half one corner moved by 8 px, half another slot's corners")
     ap.add_argument("--outlier-seed", type=int, default=1)
+    ap.add_argument("--jitter", type=float, default=None, help="irregular frame times f + J u, u uniform in (-0.5, 0.5): also run the timed call")
+    ap.add_argument("--jitter-seed", type=int, default=1)
+    ap.add_argument("--gap", default="", help="LO:HI: drop the frames [LO, HI); timed on the kept frames against naive and against the block emptied")
     a = ap.parse_args()
     if a.sequences and (a.sequences < 1 or a.frames % a.sequences):
         ap.error("--sequences must divide --frames")
+    if a.jitter is not None and not 0 <= a.jitter < 1:
+        ap.error("--jitter must be in [0, 1): the times have to increase")
+    gap = tuple(int(v) for v in a.gap.split(":")) if a.gap else None
+    if gap and not (len(gap) == 2 and 2 <= gap[0] < gap[1] <= a.frames - 2):
+        ap.error("--gap LO:HI needs 2 <= LO < HI <= frames - 2")
 
     import torch
 
@@ -159,7 +174,46 @@ def main():
                               d_outs[1][k * m:].data_ptr(), d_ress[1][64 * k:].data_ptr(), K, None, bench.TAG_INNER,
                               cov_ptr=d_covs[1][k * m:].data_ptr() if a.cov else None, **kw)
 
+    frame_times = np.arange(n, dtype=np.float64)
+    if a.jitter:
+        frame_times = frame_times + a.jitter * np.random.default_rng(a.jitter_seed).uniform(-0.5, 0.5, n)
+    d_times = torch.from_numpy(frame_times).to(dev)
+    d_out_t, d_res_t = torch.zeros_like(d_out), torch.zeros_like(d_res)
+
+    def smooth_timed():
+        det.smooth_device(d_obs.data_ptr(), n, mt, d_map.data_ptr(), len(rec), d_seed.data_ptr(), d_out_t.data_ptr(), d_res_t.data_ptr(), K, None,
+                          bench.TAG_INNER, times_ptr=d_times.data_ptr(), **kw)
+
+    if gap:   # the kept frames end to end, and all frames with the block emptied; each with the seeds of its own localisation
+        kept = np.array([f for f in range(n) if not gap[0] <= f < gap[1]])
+        obs_all = d_obs.cpu().numpy().view(_lib.OBS_DTYPE).reshape(n, mt)
+        emptied = obs_all.copy()
+        emptied["flags"][gap[0]:gap[1]] = 0
+        nk = len(kept)
+        g_obs = [torch.from_numpy(np.ascontiguousarray(o).view(np.uint8).reshape(len(o), mt, -1)).to(dev) for o in (obs_all[kept], emptied)]
+        g_seed = [torch.zeros((len(o), CAM_POSE_DTYPE.itemsize), dtype=torch.uint8, device=dev) for o in g_obs]
+        g_out = [torch.zeros((m_, CAM_POSE_DTYPE.itemsize), dtype=torch.uint8, device=dev) for m_ in (nk, nk, n)]
+        g_res = [torch.zeros_like(d_res) for _ in range(3)]
+        g_times = torch.from_numpy(np.ascontiguousarray(frame_times[kept])).to(dev)
+        torch.cuda.synchronize()
+        for o, sd in zip(g_obs, g_seed):
+            det.localize_device(o.data_ptr(), len(o), mt, d_map.data_ptr(), len(rec), sd.data_ptr(), K, None, bench.TAG_INNER, stream=stream.cuda_stream)
+
+        def gap_call(which, k, times_ptr=None):
+            det.smooth_device(g_obs[which].data_ptr(), len(g_obs[which]), mt, d_map.data_ptr(), len(rec), g_seed[which].data_ptr(), g_out[k].data_ptr(),
+                              g_res[k].data_ptr(), K, None, bench.TAG_INNER, times_ptr=times_ptr, **kw)
+
+        def gap_timed():
+            gap_call(0, 0, g_times.data_ptr())
+
+        def gap_naive():
+            gap_call(0, 1)
+
+        def gap_emptied():
+            gap_call(1, 2)
+
     legs = [localize, smooth] + ([smooth_cov] if a.cov else []) + ([smooth_robust] if a.huber > 0 else [])
+    legs += ([smooth_timed] if a.jitter is not None else []) + ([gap_timed, gap_naive, gap_emptied] if gap else [])
     seq_legs = ([] if a.loop_only else [batched]) + [loop] + ([batched_robust] if a.huber > 0 else []) if S else []
     first_seq_leg = len(legs)
     legs += seq_legs
@@ -230,6 +284,35 @@ def main():
                           "position_rmse_units": rmse_units(out_r, solved), "plain_position_rmse_units": rmse_units(out, solved),
                           "seed_position_rmse_units": rmse_units(seed, posed),
                           "after_same_frames": errors(out_r, posed & np.isin(out_r["status"], (0, 6)))}
+    leg_times = dict(zip([fn.__name__ for fn in legs], times))
+    if a.jitter is not None:
+        out_t = d_out_t.cpu().numpy().view(CAM_POSE_DTYPE).reshape(n)
+        res_t = d_res_t.cpu().numpy().view(_lib.SMOOTH_RESULT_DTYPE)[0]
+        solved = np.isin(out["status"], (0, 6)) & np.isin(out_t["status"], (0, 6))
+        tt = leg_times["smooth_timed"]
+        line["timed"] = {"jitter": a.jitter, "smooth_timed_ms_median": float(np.median(tt)), "smooth_timed_ms_min": float(np.min(tt)),
+                         "result": result(res_t), "same_bytes_as_plain": bool(torch.equal(d_out_t, d_out) and torch.equal(d_res_t, d_res)),
+                         "ms_per_trial": float(np.median(tt)) / max(1, int(res_t["iterations"])),
+                         "plain_ms_per_trial": float(np.median(times[1])) / max(1, int(res["iterations"])),
+                         "position_rmse_units": rmse_units(out_t, solved), "plain_position_rmse_units": rmse_units(out, solved)}
+    if gap:
+        near = [gap[0] - 2, gap[0] - 1, gap[1], gap[1] + 1]
+        at = {int(f): i for i, f in enumerate(kept)}
+        legs_out = {}
+        for k, name in enumerate(("timed", "naive", "emptied")):
+            po = g_out[k].cpu().numpy().view(CAM_POSE_DTYPE).reshape(-1)
+            rs = g_res[k].cpu().numpy().view(_lib.SMOOTH_RESULT_DTYPE)[0]
+            pos = (lambda f: po["T"][f][:3, 3]) if name == "emptied" else (lambda f: po["T"][at[f]][:3, 3])
+            tl = leg_times["gap_" + name]
+            legs_out[name] = {"frames": int(len(po)), "ms_median": float(np.median(tl)), "ms_min": float(np.min(tl)), "iterations": int(rs["iterations"]),
+                              "status": int(rs["status"]), "rmse_near_units": rms([np.linalg.norm(pos(f) - truths[f][:3, 3]) for f in near]),
+                              "rmse_kept_units": rms([np.linalg.norm(pos(int(f)) - truths[int(f)][:3, 3]) for f in kept])}
+        Tt = g_out[0].cpu().numpy().view(CAM_POSE_DTYPE).reshape(-1)["T"]
+        Te = g_out[2].cpu().numpy().view(CAM_POSE_DTYPE).reshape(-1)["T"][kept]
+        seed_near = rms([np.linalg.norm(seed["T"][f][:3, 3] - truths[f][:3, 3]) for f in near])
+        line["gap"] = dict(legs_out, lo=gap[0], hi=gap[1], jitter=a.jitter or 0.0, seed_rmse_near_units=seed_near,
+                           timed_over_emptied_ms=legs_out["timed"]["ms_median"] / legs_out["emptied"]["ms_median"],
+                           timed_against_emptied_rel=float(max(np.abs(x - y).max() / max(1.0, np.abs(y).max()) for x, y in zip(Tt, Te))))
     if S:
         t = dict(zip([fn.__name__ for fn in seq_legs], times[first_seq_leg:]))
         line["sequences"] = {"n_seq": S, "frames_each": m, "with_cov": bool(a.cov),
