@@ -28,7 +28,7 @@ CALIB_RESULT_DTYPE = np.dtype([("K", "<f8", (3, 3)), ("dist", "<f8", (5,)), ("st
                                ("status", "<i4")])  # asl_calib_result
 MAP_RESULT_DTYPE = np.dtype([("cost_seed", "<f8"), ("cost", "<f8"), ("rms_px", "<f8"), ("rms_seed_px", "<f8"),
                              ("n_frames_used", "<i4"), ("n_tags", "<i4"), ("n_obs", "<i4"), ("n_obs_dropped", "<i4"),
-                             ("iterations", "<i4"), ("world_id", "<i4"), ("status", "<i4"), ("reserved", "<i4")])  # asl_map_result
+                             ("iterations", "<i4"), ("world_id", "<i4"), ("status", "<i4"), ("n_soft", "<i4")])  # asl_map_result
 SMOOTH_RESULT_DTYPE = np.dtype([("cost_seed", "<f8"), ("cost", "<f8"), ("rms_px", "<f8"), ("rms_seed_px", "<f8"),
                                 ("n_frames_data", "<i4"), ("n_filled", "<i4"), ("n_flipped", "<i4"), ("iterations", "<i4"),
                                 ("status", "<i4"), ("n_soft", "<i4"), ("reserved", "<i4", (2,))])  # asl_smooth_result
@@ -51,7 +51,7 @@ EXPORTS = [
     "asl_localize_frames_device", "asl_localize_batch", "asl_localize_cov_frames_device", "asl_localize_cov_batch",
     "asl_pose_cov_device", "asl_solve_pnp_cov_batch", "asl_calibrate_frames_device", "asl_calibrate_batch",
     "asl_localize_rig_frames_device", "asl_localize_rig_cov_frames_device", "asl_localize_rig_batch", "asl_localize_rig_cov_batch",
-    "asl_map_frames_device", "asl_map_batch", "asl_smooth_frames_device", "asl_smooth_batch", "asl_smooth_cov_frames_device", "asl_smooth_cov_batch",
+    "asl_map_frames_device", "asl_map_batch", "asl_map_robust_frames_device", "asl_map_robust_batch", "asl_smooth_frames_device", "asl_smooth_batch", "asl_smooth_cov_frames_device", "asl_smooth_cov_batch",
     "asl_smooth_sequences_device", "asl_smooth_sequences_batch", "asl_smooth_robust_sequences_device", "asl_smooth_robust_sequences_batch",
     "asl_smooth_timed_sequences_device", "asl_smooth_timed_sequences_batch",
     "asl_debug_fetch", "asl_debug_refit", "asl_debug_dedup", "asl_debug_division_check", "asl_stage_times", "asl_set_profiling", "asl_debug_phase_cycles",
@@ -126,6 +126,9 @@ def load():
     mapping = [vp] + obs_block + [i32] + camera + [i32, i32, vp, vp, vp, vp]    # ..., n_ids, camera, world_id, max_iters, the four results
     L.asl_map_frames_device.argtypes = mapping + [vp]
     L.asl_map_batch.argtypes = mapping
+    mapping_robust = mapping[:10] + [dbl] + mapping[10:] + [vp]    # ..., world_id, huber_px, max_iters, the four results, slot_weight
+    L.asl_map_robust_frames_device.argtypes = mapping_robust + [vp]
+    L.asl_map_robust_batch.argtypes = mapping_robust
     smooth, seqs = [vp] + obs_block + tag_map + camera + [vp], [C.POINTER(C.c_int32), i32]    # ..., seed; seq_start, n_seq
     solve = sigmas + [i32, vp, vp]                                # ..., max_iters, out, result
     L.asl_smooth_frames_device.argtypes = smooth + solve + [vp]
@@ -504,25 +507,40 @@ class Detector:
                                                   float(tag_size), int(width), int(height), Kp, int(n_dist), int(flags), int(max_iters),
                                                   _ptr(result_ptr), _ptr(poses_ptr), _ptr(stream)))
 
-    def build_map(self, obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_std=True):
+    def build_map(self, obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_std=True, huber_px=0.0, with_slot_weight=False):
         """asl_map_batch: host records obs (n_frames, max_tags) OBS_DTYPE that see an unknown set of tags -> (MAP_RESULT_DTYPE
-        record, (n_ids,) MAP_TAG_DTYPE world<-tag map, (n_ids, 6) tag std or None, (n_frames,) CAM_POSE_DTYPE world<-camera)."""
+        record, (n_ids,) MAP_TAG_DTYPE world<-tag map, (n_ids, 6) tag std or None, (n_frames,) CAM_POSE_DTYPE world<-camera).
+        huber_px > 0 or with_slot_weight: asl_map_robust_batch -- a Huber loss of that many pixels on every corner residual of
+        the joint LM (0: the plain computation); the result's n_soft counts the down-weighted observations.
+        with_slot_weight: a fifth item, (n_frames, max_tags) doubles: a slot's smallest corner weight, 0 outside the solve."""
         o = _obs_records(obs)
         keep, Kp, dpp, nd = _camera(K, dist, square=True)
         res = np.zeros((), dtype=MAP_RESULT_DTYPE)
         tmap = np.zeros(max(int(n_ids), 1), dtype=MAP_TAG_DTYPE)
         std = np.zeros((max(int(n_ids), 1), 6), dtype=np.float64) if with_std else None
         poses = np.zeros(o.shape[0], dtype=CAM_POSE_DTYPE)
-        check(self._L.asl_map_batch(self._h, _data(o), o.shape[0], o.shape[1], int(n_ids), Kp, dpp, nd, float(tag_size), int(world_id), int(max_iters),
-                                    tmap.ctypes.data, std.ctypes.data if with_std else None, _data(poses), res.ctypes.data))
-        return res, tmap, std, poses
+        if not huber_px and not with_slot_weight:
+            check(self._L.asl_map_batch(self._h, _data(o), o.shape[0], o.shape[1], int(n_ids), Kp, dpp, nd, float(tag_size), int(world_id), int(max_iters),
+                                        tmap.ctypes.data, std.ctypes.data if with_std else None, _data(poses), res.ctypes.data))
+            return res, tmap, std, poses
+        weight = np.zeros(o.shape, dtype=np.float64) if with_slot_weight else None
+        check(self._L.asl_map_robust_batch(self._h, _data(o), o.shape[0], o.shape[1], int(n_ids), Kp, dpp, nd, float(tag_size), int(world_id),
+                                           float(huber_px), int(max_iters), tmap.ctypes.data, std.ctypes.data if with_std else None, _data(poses),
+                                           res.ctypes.data, weight.ctypes.data if with_slot_weight else None))
+        return (res, tmap, std, poses, weight) if with_slot_weight else (res, tmap, std, poses)
 
     def build_map_device(self, obs_ptr, n_frames, max_tags, n_ids, K, dist, tag_size, map_ptr, std_ptr, poses_ptr, result_ptr,
-                         world_id=-1, max_iters=30, stream=0):
+                         world_id=-1, max_iters=30, stream=0, huber_px=0.0, slot_weight_ptr=0):
         """asl_map_frames_device: obs_ptr (n_frames x max_tags asl_obs, e.g. from pack_observations_device), map_ptr (n_ids
         asl_map_tag, out), std_ptr (n_ids x 6 doubles or 0), poses_ptr (n_frames asl_cam_pose) and result_ptr (one
-        asl_map_result) are device addresses; enqueued on `stream` after one wait for the problem size."""
+        asl_map_result) are device addresses; enqueued on `stream` after one wait for the problem size.
+        huber_px > 0 or slot_weight_ptr (n_frames x max_tags doubles): asl_map_robust_frames_device."""
         keep, Kp, dpp, nd = _camera(K, dist, square=True)
+        if huber_px or slot_weight_ptr:
+            check(self._L.asl_map_robust_frames_device(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), int(n_ids), Kp, dpp, nd,
+                                                       float(tag_size), int(world_id), float(huber_px), int(max_iters), _ptr(map_ptr),
+                                                       _opt_ptr(std_ptr), _ptr(poses_ptr), _ptr(result_ptr), _opt_ptr(slot_weight_ptr), _ptr(stream)))
+            return
         check(self._L.asl_map_frames_device(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), int(n_ids), Kp, dpp, nd, float(tag_size),
                                             int(world_id), int(max_iters), _ptr(map_ptr), _opt_ptr(std_ptr), _ptr(poses_ptr),
                                             _ptr(result_ptr), _ptr(stream)))

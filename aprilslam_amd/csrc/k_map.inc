@@ -21,12 +21,19 @@
 //   reduce and factor an identity system;
 //   k_map_std       per tag parameter: diag of S^-1 = |L^-1 e_i|^2 by blocked forward substitution with the factor
 //   k_map_finish    one workgroup: the records.
+// The robust calls (asl_map_robust_*, huber_px = k > 0; tests/map_robust_ref.py) keep every seeding stage as it is and put
+// a Huber loss on each corner's raw residual in the LM alone: k_map_linearize<true> scales a corner's two rows by
+// sqrt(weight) and costs it 2 k s - k^2 beyond k, so gn_obs_block, the reduced system and the accept rule see a weighted
+// problem and the D blocks the std reads are weighted already.  After the LM
+//   k_map_soft      one workgroup: per observation the smallest corner weight at the committed poses; the number of soft
+//                   observations, the squared error and the number of the corners not over k, summed in a fixed order
+// which k_map_finish takes for n_soft, the slot weights and the std's variance factor.  huber_px = 0 runs the plain kernels.
 // No atomics: every sum has a fixed order (wave butterflies, per-thread loops in list order, k_gn_cost's fixed tree), so the
 // same input gives the same bytes; frames without taking-part slots change no list, no index and no sum.
 
 struct MapResultRec {  // == asl_map_result, 64 bytes
     double cost_seed, cost, rms_px, rms_seed_px;
-    int32_t n_frames_used, n_tags, n_obs, n_obs_dropped, iterations, world_id, status, reserved;
+    int32_t n_frames_used, n_tags, n_obs, n_obs_dropped, iterations, world_id, status, n_soft;
 };
 
 struct MapHead {  // the sizes the host reads once
@@ -522,9 +529,13 @@ __global__ void k_map_lm_init(const MapHead *head, double *lm, double *lm0)
 
 // k_gn_linearize with the k_pnp.inc camera model: one wavefront per observation, gn_obs_block with project_dev; a corner at
 // z <= 1e-9 costs 1e12 and adds no row.  Inactive observations cost 0 and leave their block alone (no list refers to it).
-// Nothing happens after the stop unless forced.
+// Nothing happens after the stop unless forced.  ROBUST: the Huber loss of threshold hk on the corner's residual length s
+// (both components come from the row's one projection): beyond hk the two rows are scaled by sqrt(hk / s) and the corner
+// costs 2 hk s - hk^2; a corner's cost is returned once, in its component-0 row.  <false> ignores hk.
+template <bool ROBUST>
 __global__ void __launch_bounds__(256) k_map_linearize(MapArgs a, const double *__restrict__ W, const double *__restrict__ G, int n_obs, CamDev cam,
-                                                       double *__restrict__ D, double *__restrict__ cost_obs, const double *__restrict__ lm, int force)
+                                                       double *__restrict__ D, double *__restrict__ cost_obs, const double *__restrict__ lm, int force,
+                                                       double hk)
 {
     const int lane = threadIdx.x & 63;
     const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -541,16 +552,72 @@ __global__ void __launch_bounds__(256) k_map_linearize(MapArgs a, const double *
         if (p[2] > LOC_Z_MIN) {
             double uv[2], Jp[6];
             project_dev(cam, p, uv, Jp);
-            res = uv[comp] - (double)o.corners[k];
+            if constexpr (ROBUST) {
+                const double r0 = uv[0] - (double)o.corners[k - comp], r1 = uv[1] - (double)o.corners[k - comp + 1];
+                const double e = r0 * r0 + r1 * r1, s = sqrt(e);
+                const bool over = s > hk;
+                const double sw = over ? sqrt(hk / s) : 1.0;
+                res = (comp ? r1 : r0) * sw;
 #pragma unroll
-            for (int r = 0; r < 3; r++) jp[r] = Jp[3 * comp + r];
-            add = res * res;
+                for (int r = 0; r < 3; r++) jp[r] = Jp[3 * comp + r] * sw;
+                if (comp == 0) add = over ? 2.0 * hk * s - hk * hk : e;
+            } else {
+                res = uv[comp] - (double)o.corners[k];
+#pragma unroll
+                for (int r = 0; r < 3; r++) jp[r] = Jp[3 * comp + r];
+                add = res * res;
+            }
         } else if (comp == 0)
             add = LOC_BEHIND_COST;
         return res;
     };
     const double c = gn_obs_block(W + 12 * (size_t)a.obs_cam[m], G + 12 * (size_t)a.obs_tag[m], cam.half, lane, row, D + (size_t)m * GN_DSTRIDE);
     if (lane == 0) cost_obs[m] = c;
+}
+
+// The robust call's look at the committed poses (a.W, a.G), one workgroup: wmin_obs[m] = the smallest of observation m's
+// four corner weights (0 for an inactive one); sums = {soft observations (a weight < 1), squared error of the corners not
+// over hk, their number}, a corner at z <= 1e-9 being one of them with its 1e12.  Per-thread sums in observation order,
+// then k_gn_cost's tree.
+enum { MAP_SOFT_N = 0, MAP_SOFT_COST, MAP_SOFT_IN, MAP_SOFT__N };
+__global__ void __launch_bounds__(256) k_map_soft(MapArgs a, int n_obs, CamDev cam, double hk, double *__restrict__ wmin_obs, double *__restrict__ sums)
+{
+    __shared__ double s_cost[256];
+    __shared__ int s_soft[256], s_in[256];
+    const int tid = threadIdx.x;
+    double cost = 0;
+    int n_soft = 0, n_in = 0;
+    for (int m = tid; m < n_obs; m += 256) {
+        double wm = 0.0;
+        if (a.obs_act[m]) {
+            wm = 1.0;
+            const ObsRec &o = a.obs[a.obs_slot[m]];
+            const double *Wc = a.W + 12 * (size_t)a.obs_cam[m], *Gj = a.G + 12 * (size_t)a.obs_tag[m];
+            for (int q = 0; q < 4; q++) {
+                const double ox = (q == 1 || q == 2) ? cam.half : -cam.half, oy = (q >= 2) ? cam.half : -cam.half;
+                double X[3], P[3], uv[2];
+#pragma unroll
+                for (int r = 0; r < 3; r++) X[r] = Gj[3 * r] * ox + Gj[3 * r + 1] * oy + Gj[9 + r];
+#pragma unroll
+                for (int r = 0; r < 3; r++) P[r] = Wc[3 * r] * X[0] + Wc[3 * r + 1] * X[1] + Wc[3 * r + 2] * X[2] + Wc[9 + r];
+                if (!(P[2] > LOC_Z_MIN)) { cost += LOC_BEHIND_COST; n_in++; continue; }
+                project_dev(cam, P, uv, nullptr);
+                const double r0 = uv[0] - (double)o.corners[2 * q], r1 = uv[1] - (double)o.corners[2 * q + 1];
+                const double e = r0 * r0 + r1 * r1, s = sqrt(e);
+                if (s > hk) wm = fmin(wm, hk / s);
+                else { cost += e; n_in++; }
+            }
+            n_soft += wm < 1.0;
+        }
+        wmin_obs[m] = wm;
+    }
+    s_cost[tid] = cost; s_soft[tid] = n_soft; s_in[tid] = n_in;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (tid < st) { s_cost[tid] += s_cost[tid + st]; s_soft[tid] += s_soft[tid + st]; s_in[tid] += s_in[tid + st]; }
+        __syncthreads();
+    }
+    if (tid == 0) { sums[MAP_SOFT_N] = s_soft[0]; sums[MAP_SOFT_COST] = s_cost[0]; sums[MAP_SOFT_IN] = s_in[0]; }
 }
 
 // accept / reject the trial, count it, stop on a small accepted decrease or a failed factorisation
@@ -612,11 +679,13 @@ __global__ void __launch_bounds__(256) k_map_std(const double *__restrict__ S, c
     if (tid == 0) var[i] = red[0];
 }
 
-// ---- the records: one workgroup.  nothing: no world tag (sizes only, no stage after the gather ran)
+// ---- the records: one workgroup.  nothing: no world tag (sizes only, no stage after the gather ran).  wmin_obs and soft
+// (k_map_soft's; NULL in a plain call): n_soft, the slot weights and the variance factor over the corners not over the
+// threshold; a plain call has n_soft 0, weight 1 for the slots in the solve and cost / dof.  slot_weight may be NULL.
 __global__ void __launch_bounds__(MAP_WG) k_map_finish(MapArgs a, int n_cams, int n_tags, int n_obs, int wt, int nothing, const double *lm,
                                                        const double *cost_obs, const double *seed_obs, const double *var, const int *var_fail,
-                                                       MapTagRec *map,
-                                                       double *tag_std, CamPoseRec *poses, MapResultRec *res)
+                                                       const double *wmin_obs, const double *soft, MapTagRec *map,
+                                                       double *tag_std, CamPoseRec *poses, MapResultRec *res, double *slot_weight)
 {
     __shared__ int s_part[MAP_WG + 1];
     const int tid = threadIdx.x;
@@ -628,7 +697,11 @@ __global__ void __launch_bounds__(MAP_WG) k_map_finish(MapArgs a, int n_cams, in
     const double cost = nothing ? 0.0 : lm[GN_LM_COST], cost0 = nothing ? 0.0 : lm[GN_LM_COST0];
     if (status == 0 && !isfinite(cost)) status = 3;
     const int dof = 8 * n_act - 6 * n_used - 6 * (n_mapped - 1);
-    const double s2 = dof > 0 ? cost / dof : 0.0;
+    double s2 = dof > 0 ? cost / dof : 0.0;
+    if (soft) {
+        const int dof_in = 2 * (int)soft[MAP_SOFT_IN] - 6 * n_used - 6 * (n_mapped - 1);
+        s2 = dof_in > 0 ? soft[MAP_SOFT_COST] / dof_in : 0.0;
+    }
     const bool std_ok = var && !(var_fail && *var_fail);  // an undamped system that is not positive definite gives no std
     for (int f = tid; f < a.n_frames; f += MAP_WG) {
         CamPoseRec *o = poses + f;
@@ -670,6 +743,11 @@ __global__ void __launch_bounds__(MAP_WG) k_map_finish(MapArgs a, int n_cams, in
         if (tag_std)
             for (int k = 0; k < 6; k++) tag_std[6 * (size_t)i + k] = (ok && j != wt && std_ok) ? sqrt(s2 * var[6 * j + k]) : 0.0;
     }
+    if (slot_weight)
+        for (size_t k = tid; k < (size_t)a.n_frames * a.max_tags; k += MAP_WG) {
+            const int m = nothing ? -1 : a.slot_obs[k];
+            slot_weight[k] = (m >= 0 && status == 0 && a.obs_act[m]) ? (wmin_obs ? wmin_obs[m] : 1.0) : 0.0;
+        }
     if (tid == 0) {
         MapResultRec r;
         r.cost_seed = cost0; r.cost = cost;
@@ -682,7 +760,7 @@ __global__ void __launch_bounds__(MAP_WG) k_map_finish(MapArgs a, int n_cams, in
         r.iterations = nothing ? 0 : (int)lm[MAP_LM_ITERS];
         r.world_id = a.head->world_id;
         r.status = status;
-        r.reserved = 0;
+        r.n_soft = (soft && status == 0) ? (int)soft[MAP_SOFT_N] : 0;
         *res = r;
     }
 }

@@ -401,13 +401,14 @@ extern "C" int asl_calibrate_batch(asl_detector *d, const asl_obs *obs, int n_fr
 
 // ---- mapping (k_map.inc)
 
-// One map call, in the entry points' argument order.  tag_std may be NULL: no std asked for.  obs, map, tag_std, poses and
-// result are all host (asl_map_batch) or all device pointers (asl_map_frames_device); no field is left empty by either.
+// One map call, in the robust entry points' argument order; the plain ones give huber_px 0 and no slot_weight.  tag_std
+// and slot_weight may be NULL: not asked for.  obs, map, tag_std, poses, result and slot_weight are all host (asl_map_batch,
+// asl_map_robust_batch) or all device pointers (asl_map_frames_device, asl_map_robust_frames_device).
 struct MapCall {
     const void *obs; int n_frames, max_tags, n_ids;
     Camera cam;
-    int world_id, max_iters;
-    void *map, *tag_std, *poses, *result;
+    int world_id; double huber_px; int max_iters;
+    void *map, *tag_std, *poses, *result, *slot_weight;
 };
 
 // every refusal that needs no look at the block, before anything is written or enqueued; the same for both forms
@@ -419,6 +420,7 @@ static int check_map_call(const asl_detector *d, const MapCall &c, bool)
     if (int rc = check_obs_args(c.max_tags, c.n_ids, c.cam)) return rc;
     if (c.world_id < -1 || c.world_id >= c.n_ids) return fail(ASL_EINVAL, "world_id must be -1 or in [0, n_ids) (got %d)", c.world_id);
     if (c.max_iters < 1 || c.max_iters > MAP_MAX_ITERS) return fail(ASL_EINVAL, "max_iters must be in [1, %d] (got %d)", MAP_MAX_ITERS, c.max_iters);
+    if (!(c.huber_px >= 0) || !std::isfinite(c.huber_px)) return fail(ASL_EINVAL, "huber_px must be >= 0 and finite (got %g)", c.huber_px);
     return ASL_OK;
 }
 
@@ -449,8 +451,8 @@ static int launch_map(asl_detector *d, const MapCall &c, hipStream_t st)
     const int NC = h.n_cams, NT = h.n_tags, NM = h.n_obs, WT = h.world_tag;
     auto finish_nothing = [&]() {
         hipLaunchKernelGGL(k_map_finish, dim3(1), dim3(MAP_WG), 0, st, a, NC, NT, NM, WT, 1, (const double *)nullptr, (const double *)nullptr,
-                           (const double *)nullptr, (const double *)nullptr, (const int *)nullptr, (MapTagRec *)c.map, (double *)c.tag_std, (CamPoseRec *)c.poses,
-                           (MapResultRec *)c.result);
+                           (const double *)nullptr, (const double *)nullptr, (const int *)nullptr, (const double *)nullptr, (const double *)nullptr,
+                           (MapTagRec *)c.map, (double *)c.tag_std, (CamPoseRec *)c.poses, (MapResultRec *)c.result, (double *)c.slot_weight);
         HIPCHK(hipGetLastError());
         return ASL_OK;
     };
@@ -462,16 +464,18 @@ static int launch_map(asl_detector *d, const MapCall &c, hipStream_t st)
         return ASL_OK;
     }
 
-    // the problem-sized part: the LM's buffers (gn_lm_carve), the seed costs, the std; the reduced system reads the LM's
-    // copies of the list offsets (k_map_park empties them after the stop)
+    // the problem-sized part: the LM's buffers (gn_lm_carve), the seed costs, the std, the robust call's weights and sums;
+    // the reduced system reads the LM's copies of the list offsets (k_map_park empties them after the stop)
     const int n = 6 * NT;
     const size_t nc = (size_t)NC, nt = (size_t)NT, nm = (size_t)NM;
     GnSystem sys = {nullptr, nullptr, a.cam_obs, nullptr, a.tag_obs, a.obs_cam, a.obs_tag, nullptr, NC, NT, WT};
     GnLmBufs b;
-    double *seed_obs, *var;
+    const bool robust = c.huber_px > 0;  // 0: the plain kernels
+    double *seed_obs, *var, *wmin_obs = nullptr, *soft = nullptr;
     if (carve_ws(d->map_lm, [&](WsCarve &w) {
             b = gn_lm_carve(w, sys, NM, 2 * MAP_LM__N);
             seed_obs = w.take<double>(nm); var = w.take<double>(n); sys.cam_ptr = w.take<int>(nc + 1); sys.tag_ptr = w.take<int>(nt + 1);
+            if (robust) { wmin_obs = w.take<double>(nm); soft = w.take<double>(MAP_SOFT__N); }
         }))
         return fail(ASL_ENOMEM, "map workspace allocation failed");
     a.obs_of = sys.obs_of;
@@ -498,7 +502,8 @@ static int launch_map(asl_detector *d, const MapCall &c, hipStream_t st)
 
     range_push("map: LM");
     auto lin = [&](const double *W, const double *G, double *D, int force) {
-        hipLaunchKernelGGL(k_map_linearize, dim3((NM + 3) / 4), dim3(256), 0, st, a, W, G, NM, cam, D, b.cost_obs, lm, force);
+        const auto kernel = robust ? k_map_linearize<true> : k_map_linearize<false>;
+        hipLaunchKernelGGL(kernel, dim3((NM + 3) / 4), dim3(256), 0, st, a, W, G, NM, cam, D, b.cost_obs, lm, force, c.huber_px);
     };
     auto decide = [&]() { hipLaunchKernelGGL(k_map_decide, dim3(1), dim3(1), 0, st, lm, b.flag); };
     auto park = [&]() {
@@ -510,6 +515,7 @@ static int launch_map(asl_detector *d, const MapCall &c, hipStream_t st)
     if (rc) return rc;
     // the final state's per-observation costs (and its blocks again, for the std)
     lin(a.W, a.G, sys.D, 1);
+    if (robust) hipLaunchKernelGGL(k_map_soft, dim3(1), dim3(256), 0, st, a, NM, cam, c.huber_px, wmin_obs, soft);
     range_pop();
     if (c.tag_std) {
         GnSystem full = sys;  // undamped, over every active observation
@@ -520,7 +526,8 @@ static int launch_map(asl_detector *d, const MapCall &c, hipStream_t st)
         hipLaunchKernelGGL(k_map_std, dim3(n), dim3(256), (size_t)n * sizeof(double), st, sys.S, sys.Linv, n, var);
     }
     hipLaunchKernelGGL(k_map_finish, dim3(1), wg, 0, st, a, NC, NT, NM, WT, 0, lm, b.cost_obs, seed_obs, c.tag_std ? var : nullptr, b.flag + 1,
-                       (MapTagRec *)c.map, (double *)c.tag_std, (CamPoseRec *)c.poses, (MapResultRec *)c.result);
+                       (const double *)wmin_obs, (const double *)soft, (MapTagRec *)c.map, (double *)c.tag_std, (CamPoseRec *)c.poses,
+                       (MapResultRec *)c.result, (double *)c.slot_weight);
     HIPCHK(hipGetLastError());
     return ASL_OK;
 }
@@ -532,10 +539,11 @@ static int map_batch(asl_detector *d, const MapCall &c)
     if (int rc = check_map_call(d, c, false)) return rc;
     const size_t ni = (size_t)c.n_ids;
     OutPiece o[] = {{c.result, sizeof(asl_map_result)}, {c.map, sizeof(asl_map_tag) * ni}, {c.tag_std, c.tag_std ? sizeof(double) * 6 * ni : 0},
-                    {c.poses, sizeof(asl_cam_pose) * (size_t)c.n_frames}};
+                    {c.poses, sizeof(asl_cam_pose) * (size_t)c.n_frames},
+                    {c.slot_weight, c.slot_weight ? sizeof(double) * (size_t)c.n_frames * (size_t)c.max_tags : 0}};
     if (int rc = stage_host_call(d, "map", o, c.obs, c.n_frames, c.max_tags, nullptr, c.n_ids)) return rc;
     MapCall dc = c;
-    dc.obs = d->loc_obs.p; dc.result = o[0].dev; dc.map = o[1].dev; dc.tag_std = o[2].dev; dc.poses = o[3].dev;
+    dc.obs = d->loc_obs.p; dc.result = o[0].dev; dc.map = o[1].dev; dc.tag_std = o[2].dev; dc.poses = o[3].dev; dc.slot_weight = o[4].dev;
     if (int rc = launch_map(d, dc, nullptr)) return rc;
     return fetch_out(o);
 }
@@ -544,14 +552,30 @@ extern "C" int asl_map_frames_device(asl_detector *d, const void *d_obs, int n_f
                                      int n_dist, double tag_size, int world_id, int max_iters, void *d_map, void *d_tag_std, void *d_poses,
                                      void *d_result, void *stream)
 {
-    return map_frames_device(d, {d_obs, n_frames, max_tags, n_ids, {K, dist, n_dist, tag_size}, world_id, max_iters, d_map, d_tag_std, d_poses, d_result}, stream);
+    return map_frames_device(d, {d_obs, n_frames, max_tags, n_ids, {K, dist, n_dist, tag_size}, world_id, 0.0, max_iters, d_map, d_tag_std, d_poses, d_result, nullptr}, stream);
 }
 
 extern "C" int asl_map_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, int n_ids, const double *K, const double *dist,
                              int n_dist, double tag_size, int world_id, int max_iters, asl_map_tag *map, double *tag_std, asl_cam_pose *poses,
                              asl_map_result *result)
 {
-    return map_batch(d, {obs, n_frames, max_tags, n_ids, {K, dist, n_dist, tag_size}, world_id, max_iters, map, tag_std, poses, result});
+    return map_batch(d, {obs, n_frames, max_tags, n_ids, {K, dist, n_dist, tag_size}, world_id, 0.0, max_iters, map, tag_std, poses, result, nullptr});
+}
+
+extern "C" int asl_map_robust_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, int n_ids, const double *K,
+                                            const double *dist, int n_dist, double tag_size, int world_id, double huber_px, int max_iters,
+                                            void *d_map, void *d_tag_std, void *d_poses, void *d_result, void *d_slot_weight, void *stream)
+{
+    return map_frames_device(d, {d_obs, n_frames, max_tags, n_ids, {K, dist, n_dist, tag_size}, world_id, huber_px, max_iters, d_map, d_tag_std, d_poses,
+                                 d_result, d_slot_weight}, stream);
+}
+
+extern "C" int asl_map_robust_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, int n_ids, const double *K, const double *dist,
+                                    int n_dist, double tag_size, int world_id, double huber_px, int max_iters, asl_map_tag *map, double *tag_std,
+                                    asl_cam_pose *poses, asl_map_result *result, double *slot_weight)
+{
+    return map_batch(d, {obs, n_frames, max_tags, n_ids, {K, dist, n_dist, tag_size}, world_id, huber_px, max_iters, map, tag_std, poses, result,
+                         slot_weight});
 }
 
 // ---- sequence localisation with a motion prior (k_smooth.inc)

@@ -3,7 +3,8 @@
 Frames that see an unknown set of tags give the tags' world<-tag poses (the world tag at the identity), every frame's
 camera pose and a per-tag standard deviation; the map is the asl_map_tag block localisation reads (localize.TagMap).
 
-    MapResult           the records of one solve, with .tag_map, .tag_std, .camera_poses, .frame_status
+    MapResult           the records of one solve, with .tag_map, .tag_std, .camera_poses, .frame_status and, from a solve
+                        with a robust loss (huber_px), .n_soft, .slot_weight and .soft_slots()
     MAP_RESULT_DTYPE    asl_map_result
 """
 import numpy as np
@@ -20,13 +21,16 @@ __all__ = ["MapResult", "MAP_RESULT_DTYPE", "STATUS_OK", "STATUS_NOTHING", "STAT
 
 class MapResult:
     """One map solve: result (MAP_RESULT_DTYPE record), map (n_ids,) MAP_TAG_DTYPE, std (n_ids, 6) or None, poses
-    (n_frames,) CAM_POSE_DTYPE."""
+    (n_frames,) CAM_POSE_DTYPE; slot_weight (n_frames, max_tags) doubles or None (not computed) with slot_ids, the
+    (n_frames, max_tags) ids of the observation block the weights belong to."""
 
-    def __init__(self, result, map_records, tag_std, poses):
+    def __init__(self, result, map_records, tag_std, poses, slot_weight=None, slot_ids=None):
         self.result = np.asarray(result, dtype=MAP_RESULT_DTYPE).reshape(())
         self.records = map_records
         self.std = tag_std
         self.poses = poses
+        self.slot_weight = slot_weight
+        self.slot_ids = slot_ids
 
     @property
     def status(self):
@@ -43,6 +47,20 @@ class MapResult:
     @property
     def rms_px(self):
         return float(self.result["rms_px"])
+
+    @property
+    def n_soft(self):
+        """observations in the solve that the robust loss down-weighted (0 from a plain solve)"""
+        return int(self.result["n_soft"])
+
+    def soft_slots(self):
+        """[(frame, slot, id, weight)] of every slot with a weight in (0, 1): the observations the robust loss
+        down-weighted, in (frame, slot) order; id is -1 without slot_ids"""
+        if self.slot_weight is None:
+            raise ValueError("the slot weights were not computed (build_map(..., huber_px=k))")
+        w = np.asarray(self.slot_weight)
+        return [(int(f), int(s), int(self.slot_ids[f, s]) if self.slot_ids is not None else -1, float(w[f, s]))
+                for f, s in np.argwhere((w > 0) & (w < 1))]
 
     @property
     def tag_map(self):

@@ -362,7 +362,8 @@ typedef struct {
     int32_t world_id;
     int32_t status;                /* 0 ok, 1 nothing to solve (no world tag in a used frame, or no observation left),
                                       2 reduced system not positive definite, 3 non-finite */
-    int32_t reserved;
+    int32_t n_soft;                /* asl_map_robust_*: observations in the solve with a corner over the Huber threshold at the
+                                      returned poses; 0 from the plain calls */
 } asl_map_result;                  /* 64 bytes */
 
 /* Map from d_obs (n_frames x max_tags records as asl_pack_observations_device writes them), device pointers.  A slot takes
@@ -393,6 +394,42 @@ int asl_map_frames_device(asl_detector *det, const void *d_obs, int n_frames, in
 int asl_map_batch(asl_detector *det, const asl_obs *obs, int n_frames, int max_tags, int n_ids, const double *K,
                   const double *dist, int n_dist, double tag_size, int world_id, int max_iters, asl_map_tag *map,
                   double *tag_std, asl_cam_pose *poses, asl_map_result *result);
+
+/* asl_map_frames_device with a robust (Huber) loss on every corner's pixel residual in the joint LM, for surveys where a
+   corner slips or a slot carries another tag's corners (a mis-decoded id): under the squared loss one such slot in hundreds
+   bends the whole map, and everything that later takes the map as exact with it.  The seed (gather, chain, reseed sweeps,
+   gauge, flip test, behind-camera test) is the plain call's, with squared costs, bit for bit.  map_huber_px is the
+   threshold every other layer calls huber_px: huber_px = k > 0, in pixels, on the raw residual r = (r0, r1) of a corner, s = |r|: s <= k costs s^2 with weight 1 (the plain term); s > k costs
+   2 k s - k^2 with weight k / s; a corner at z <= 1e-9 costs 1e12, adds nothing and is never over, as before.  The corner
+   adds weight J^T J and weight J^T r to the normal equations (iteratively reweighted Gauss-Newton, no second-order term of
+   the loss).  The robust cost stands wherever the LM's squared one does: cost_seed and cost, every trial, the accept rule and
+   the 1e-12 stop.  rms_px and rms_seed_px, per frame and in the result, are sqrt(sum of the corner costs / corners): the
+   plain RMS whenever no corner is over the threshold.  Damping, the lambda schedule, statuses, max_iters and which frames,
+   tags and observations are in the solve are those of the plain call; a frame's n_rejected keeps its meaning (nothing is
+   removed: a bad observation is down-weighted).
+   The result's n_soft is the number of observations in the solve with at least one corner of weight < 1 at the returned
+   poses ("soft").  d_slot_weight (NULL: skipped): n_frames x max_tags doubles, for a slot in the solve the smallest of its
+   four corner weights at the returned poses, in (0, 1]; 0 for every other slot, and for every slot, with n_soft 0, when the
+   result's status is not 0.  The slots with a weight below 1 are the observations to look at.
+   d_tag_std: the diagonal comes from the weighted undamped system at the solution, and the variance factor from the
+   corners that are not over k: sigma^2 = sum of their s^2 / (2 n_in - 6 frames - 6 (tags - 1)), n_in their number (a corner
+   at z <= 1e-9 is one of them, with its 1e12), 0 if that denominator is <= 0.  With cost / dof the linear tail of one swapped
+   slot inflated every tag's std several times over; the inlier factor does not, and is biased slightly low by the truncation
+   at k.
+   The loss cannot repair a seed that leaves a tag in a wrong basin (the slot that seeds a frame carrying another tag's
+   corners and PnP pose), nor a block too small to out-vote a bad slot (four frames of four tags); a k near the corner noise
+   makes many slots soft (at 2 sigma about a third of them).  The linear tail may need more trials than the quadratic one:
+   raise max_iters.  huber_px == 0 is the plain computation, run by the plain kernels: d_map, d_tag_std, d_poses and
+   d_result are byte for byte what asl_map_frames_device writes, n_soft 0, the slot weights 1 for the slots in the solve.
+   ASL_EINVAL, nothing written: whatever asl_map_frames_device refuses; huber_px < 0 or not finite.  The host waits once, as
+   in the plain call; deterministic: the same input gives the same bytes.  tests/map_robust_ref.py states the computation. */
+int asl_map_robust_frames_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, int n_ids, const double *K,
+                                 const double *dist, int n_dist, double tag_size, int world_id, double map_huber_px, int max_iters,
+                                 void *d_map, void *d_tag_std, void *d_poses, void *d_result, void *d_slot_weight, void *stream);
+/* The same computation on host records, synchronous; slot_weight may be NULL. */
+int asl_map_robust_batch(asl_detector *det, const asl_obs *obs, int n_frames, int max_tags, int n_ids, const double *K,
+                         const double *dist, int n_dist, double tag_size, int world_id, double map_huber_px, int max_iters,
+                         asl_map_tag *map, double *tag_std, asl_cam_pose *poses, asl_map_result *result, double *slot_weight);
 
 /* ---- sequence localisation: the camera poses of one camera's consecutive frames against a fixed map, solved together
    under a random-walk motion prior, so that EVERY frame gets a pose: frames without a mapped tag are carried by their

@@ -3,6 +3,13 @@
 observations, and the map and camera errors against the truth in the world-tag gauge.
 
     python tools/map_lab.py [--frames 1024] [--reps 10] [--out results.json]
+
+With --huber K the robust solve (asl_map_robust_frames_device, huber_px = K) is measured against the plain one on the bench
+scene alone: --outliers N slots, spread over the frames, are given their neighbour slot's corners (a mis-decoded id); the
+plain and the robust leg alternate, rep by rep, and each reports its map errors against the truth, its trials, its median
+total ms and ms per trial, and the robust leg its soft slots.
+
+    python tools/map_lab.py --huber 1.0 --outliers 8 [--iters 60]
 """
 import argparse
 import json
@@ -58,6 +65,68 @@ def time_device(det, obs, n_ids, K, reps):
     return float(np.median(ms)), res, tmap, poses
 
 
+def with_outliers(obs, n):
+    """n slots, evenly spread over the frames, carry the next slot's corners; the slots changed"""
+    out, slots = obs.copy(), []
+    F, S = obs.shape
+    for k in range(n):
+        f = (2 * k + 1) * F // (2 * n)
+        s = next(s for s in range((3 * k) % (S - 1), S - 1) if obs["id"][f, s] >= 0 and obs["id"][f, s + 1] >= 0)
+        out["corners"][f, s] = obs["corners"][f, s + 1]
+        slots.append((f, s))
+    return out, slots
+
+
+def robust_lab(det, a):
+    """the plain and the robust leg on the bench scene, alternating"""
+    import torch
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(7)
+    K, tags, cams, clean = scene_block(a.frames, 20, 0.3, rng)
+    obs, bad = with_outliers(clean, a.outliers) if a.outliers else (clean, [])
+    n_ids = 1 + max(t["id"] for t in tags)
+    n, mt = obs.shape
+    d_obs = torch.from_numpy(np.ascontiguousarray(obs).view(np.uint8).reshape(n, -1)).to(dev)
+    d_map = torch.empty((n_ids, _lib.MAP_TAG_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    d_std = torch.empty((n_ids, 6), dtype=torch.float64, device=dev)
+    d_poses = torch.empty((n, _lib.CAM_POSE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    d_res = torch.empty((64,), dtype=torch.uint8, device=dev)
+    d_w = torch.empty((n, mt), dtype=torch.float64, device=dev)
+    s = torch.cuda.Stream(dev)
+    legs = {"plain": dict(), "robust": dict(huber_px=a.huber, slot_weight_ptr=d_w.data_ptr())}
+    ms = {k: [] for k in legs}
+    out = {}
+    for r in range(a.reps + 2):
+        for leg, kw in legs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(s)
+            det.build_map_device(d_obs.data_ptr(), n, mt, n_ids, K, None, LC.TAG_INNER, d_map.data_ptr(), d_std.data_ptr(), d_poses.data_ptr(),
+                                 d_res.data_ptr(), max_iters=a.iters, stream=s.cuda_stream, **kw)
+            e1.record(s)
+            s.synchronize()
+            if r >= 2:
+                ms[leg].append(e0.elapsed_time(e1))
+            if r == a.reps + 1:
+                res = d_res.cpu().numpy().view(_lib.MAP_RESULT_DTYPE).reshape(())
+                tmap = d_map.cpu().numpy().view(_lib.MAP_TAG_DTYPE).reshape(n_ids)
+                poses = d_poses.cpu().numpy().view(_lib.CAM_POSE_DTYPE).reshape(n)
+                et, er, ec = MC.map_errors(tmap, poses, tags, cams, int(res["world_id"]))
+                out[leg] = dict(status=int(res["status"]), trials=int(res["iterations"]), max_iters=a.iters, rms_px=float(res["rms_px"]),
+                                tag_err=et, tag_rot_err=er, cam_err=ec, max_std=float(d_std.max().item()), n_soft=int(res["n_soft"]))
+                if leg == "robust":
+                    w = d_w.cpu().numpy()
+                    soft = {(int(f), int(sl)) for f, sl in np.argwhere((w > 0) & (w < 1))}
+                    out[leg].update(outliers_soft=len(soft & set(bad)), clean_soft=len(soft - set(bad)))
+    for leg in legs:
+        out[leg]["ms"] = float(np.median(ms[leg]))
+        out[leg]["ms_spread"] = [float(min(ms[leg])), float(max(ms[leg]))]
+        out[leg]["ms_per_trial"] = out[leg]["ms"] / max(1, out[leg]["trials"])    # the seed's share included
+        out[leg]["ms_per_enqueued_trial"] = out[leg]["ms"] / a.iters               # after the stop a trial is an identity system
+    r = dict(frames=n, obs=int((obs["id"] >= 0).sum()), huber_px=a.huber, outliers=len(bad), **out)
+    print("robust_lab", json.dumps(r), flush=True)
+    return r
+
+
 def time_host(det, obs, K, iters):
     t0 = time.perf_counter()
     frames = [[(int(o["id"]), MR.rec4(o["T"]), o["corners"].astype(np.float64).reshape(4, 2)) for o in fr if o["flags"] & 1 and o["id"] >= 0]
@@ -106,8 +175,17 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--huber", type=float, default=0.0, help="huber_px of the robust leg; > 0 runs the plain / robust comparison alone")
+    ap.add_argument("--outliers", type=int, default=0, help="slots given their neighbour slot's corners")
     a = ap.parse_args()
     det = _lib.Detector("tagStandard41h12", id_limit=0)
+    if a.huber > 0:
+        r = robust_lab(det, a)
+        det.close()
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(r, f, indent=1)
+        return
     rng = np.random.default_rng(7)
     out = {}
     for name, ntags, nf in (("bench_20", 20, a.frames), ("scene_200", 200, min(a.frames, 256))):
