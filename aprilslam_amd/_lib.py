@@ -54,6 +54,7 @@ EXPORTS = [
     "asl_map_frames_device", "asl_map_batch", "asl_map_robust_frames_device", "asl_map_robust_batch", "asl_smooth_frames_device", "asl_smooth_batch", "asl_smooth_cov_frames_device", "asl_smooth_cov_batch",
     "asl_smooth_sequences_device", "asl_smooth_sequences_batch", "asl_smooth_robust_sequences_device", "asl_smooth_robust_sequences_batch",
     "asl_smooth_timed_sequences_device", "asl_smooth_timed_sequences_batch",
+    "asl_smooth_rig_sequences_device", "asl_smooth_rig_sequences_batch",
     "asl_debug_fetch", "asl_debug_refit", "asl_debug_dedup", "asl_debug_division_check", "asl_stage_times", "asl_set_profiling", "asl_debug_phase_cycles",
 ]
 
@@ -142,6 +143,9 @@ def load():
     L.asl_smooth_robust_sequences_batch.argtypes = smooth + seqs + robust + [vp]
     L.asl_smooth_timed_sequences_device.argtypes = smooth + [vp] + seqs + robust + [vp, vp]    # ..., seed, times, seq_start, ...
     L.asl_smooth_timed_sequences_batch.argtypes = smooth + [dp] + seqs + robust + [vp]
+    smooth_rig = rig[:8] + [dbl, vp]                              # detector, obs, n_cams, n_frames, max_tags, map, n_ids, rig, tag_size, seed
+    L.asl_smooth_rig_sequences_device.argtypes = smooth_rig + [vp] + seqs + robust + [vp, vp]    # ..., seed, frame_times, seq_start, ...
+    L.asl_smooth_rig_sequences_batch.argtypes = smooth_rig + [dp] + seqs + robust + [vp]
     L.asl_debug_fetch.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.asl_debug_refit.argtypes = [vp, i32, vp, C.c_size_t]
     L.asl_debug_dedup.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, C.c_size_t]
@@ -654,6 +658,53 @@ class Detector:
             seqs, last = (ssp, n_seq), (_opt_ptr(cov_ptr),)
         check(fn(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids), Kp, dpp, nd, float(tag_size), _ptr(seed_ptr), *timed, *seqs,
                  *map(float, sigmas), *robust, int(max_iters), _ptr(out_ptr), _ptr(result_ptr), *last, _ptr(stream)))
+
+    def smooth_rig(self, obs, tag_map, rig, tag_size, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, seed=None, seq_start=None,
+                   times=None, huber_px=0.0, with_cov=False):
+        """asl_smooth_rig_sequences_batch: smooth_sequences() for a rig.  Host records obs (n_cams, n_frames, max_tags) OBS_DTYPE,
+        camera-major, of the rig's consecutive frames against tag_map and the camera table rig ((n_cams,) RIG_CAMERA_DTYPE, or a
+        rig.Rig) -> ((n_frames,) CAM_POSE_DTYPE, world<-rig for EVERY frame, SMOOTH_RESULT_DTYPE record[, (n_frames,)
+        POSE_COV_DTYPE with with_cov]).  seed: (n_frames,) CAM_POSE_DTYPE as localize_rig() returns them for the same obs; None:
+        that localisation runs first.  seq_start: None (one sequence, one result record), or n_seq + 1 offsets from 0 to
+        n_frames -> (n_seq,) result records.  times, huber_px: as in smooth()."""
+        o = np.ascontiguousarray(obs, dtype=OBS_DTYPE)
+        if o.ndim != 3:
+            raise ValueError("obs must be (n_cams, n_frames, max_tags) asl_obs records")
+        m, r = _map_records(tag_map), _rig_records(rig)
+        if len(r) != o.shape[0]:
+            raise ValueError("the rig has %d cameras, obs has %d" % (len(r), o.shape[0]))
+        n = o.shape[1]
+        sd = None if seed is None else np.ascontiguousarray(seed, dtype=CAM_POSE_DTYPE).ravel()
+        if sd is not None and len(sd) != n:
+            raise ValueError("seed must hold one pose per frame")
+        tm = None if times is None else np.ascontiguousarray(times, dtype=np.float64).ravel()
+        if tm is not None and len(tm) != n:
+            raise ValueError("times must hold one value per frame")
+        ss, ssp, n_seq = self._seq_start([0, n] if seq_start is None else seq_start, n)
+        out = np.zeros(n, dtype=CAM_POSE_DTYPE)
+        res = np.zeros(max(n_seq, 0), dtype=SMOOTH_RESULT_DTYPE)
+        cov = np.zeros(n, dtype=POSE_COV_DTYPE) if with_cov else None
+        check(self._L.asl_smooth_rig_sequences_batch(self._h, _data(o), o.shape[0], n, o.shape[2], _data(m), len(m), _data(r), float(tag_size),
+                                                     None if sd is None else sd.ctypes.data, None if tm is None else tm.ctypes.data_as(_DP), ssp, n_seq,
+                                                     float(sigma_px), float(sigma_rot), float(sigma_trans), float(huber_px), int(max_iters),
+                                                     _data(out), _data(res), _data(cov) if with_cov else None))
+        if seq_start is None:
+            res = res[0]
+        return (out, res, cov) if with_cov else (out, res)
+
+    def smooth_rig_device(self, obs_ptr, n_cams, n_frames, max_tags, map_ptr, n_ids, rig_ptr, seed_ptr, out_ptr, results_ptr, tag_size,
+                          sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, seq_start=None, stream=0, times_ptr=None, huber_px=0.0,
+                          cov_ptr=None):
+        """asl_smooth_rig_sequences_device: obs_ptr (n_cams x n_frames x max_tags asl_obs, camera-major), map_ptr (n_ids
+        asl_map_tag), rig_ptr (n_cams asl_rig_camera, complete when the call is made), seed_ptr (n_frames asl_cam_pose, as
+        localize_rig_device wrote them), out_ptr (n_frames asl_cam_pose) and results_ptr (n_seq asl_smooth_result) are device
+        addresses; seq_start: None (the one sequence) or a HOST array of n_seq + 1 offsets; times_ptr: None or n_frames doubles
+        on the device; cov_ptr: None or n_frames asl_pose_cov.  Enqueued on `stream` after the table's check."""
+        ss, ssp, n_seq = self._seq_start([0, int(n_frames)] if seq_start is None else seq_start, n_frames)
+        check(self._L.asl_smooth_rig_sequences_device(self._h, _ptr(obs_ptr), int(n_cams), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids),
+                                                      _opt_ptr(rig_ptr), float(tag_size), _ptr(seed_ptr), _opt_ptr(times_ptr), ssp, n_seq,
+                                                      float(sigma_px), float(sigma_rot), float(sigma_trans), float(huber_px), int(max_iters),
+                                                      _ptr(out_ptr), _ptr(results_ptr), _opt_ptr(cov_ptr), _ptr(stream)))
 
     def collect_view(self):
         """Wait for the submitted batch; (dets, poses or None, n_per_frame) as numpy VIEWS of the detector's page-locked result

@@ -110,6 +110,13 @@ struct LocOneCam {
     }
     // the solved pose (R, t) that slot s's PnP pose To and map tag M propose (loc_candidate)
     __device__ __forceinline__ void candidate(int, const double *To, const double *M, bool mirror, double *R, double *t) const;
+    // camera<-world of slot s's camera at the solved pose (R, t): the pose itself
+    __device__ __forceinline__ void camera_pose(int, const double *R, const double *t, double *Rc, double *tc) const
+    {
+#pragma unroll
+        for (int i = 0; i < 9; i++) Rc[i] = R[i];
+        tc[0] = t[0]; tc[1] = t[1]; tc[2] = t[2];
+    }
 };
 
 // LDS of one frame (dynamic): world corners double[3 * n4], slot area double[max_tags], image corners float[2 * n4],
@@ -243,9 +250,10 @@ __device__ __forceinline__ int loc_best_candidate(const int (&sel)[K], int nsel,
 
 // Total cost over the active corners (state == 1) of the model's slots, identical in every lane; with NE also the normal
 // equations in ne.
-// ROBUST (LocOneCam only): every corner through the Huber loss of threshold hk (loc_corner), and *soft the number of active
+// ROBUST: every corner through the Huber loss of threshold hk (the model's corner<NE, true>), and *soft the number of active
 // slots with a corner over it.  A slot's corners are four neighbouring lanes of one round of the loop (64 is a multiple of 4),
-// so the slot's OR is two quad exchanges; every lane takes every round, for the exchanges to read live lanes.
+// a rig's global slots as one camera's, so the slot's OR is two quad exchanges; every lane takes every round, for the
+// exchanges to read live lanes.
 template <bool NE, bool ROBUST = false, class Model>
 __device__ __forceinline__ double loc_pass(const Model &m, const double *R, const double *t, const LocLds &L, int lane, double *ne,
                                            [[maybe_unused]] double hk = 0.0, [[maybe_unused]] int *soft = nullptr)

@@ -39,8 +39,11 @@ __device__ __forceinline__ int rig_cam_of(int g, unsigned int magic) { return (i
 // loc_corner for a corner of the camera whose LDS record is cl: squared pixel error at rig point P_r = R X + t, with NE
 // its two Jacobian rows J_proj Re [-[P_r]x | I] added to acc (JtJ packed lower triangle 21, Jt r 6).  The mounting is read
 // from LDS where it is used: a per-camera choice among register copies would be a run-time-indexed array, i.e. scratch.
-template <bool NE>
-__device__ __forceinline__ double rig_corner(const double *cl, const double *R, const double *t, const double *X, double iu, double iv, double *acc)
+// ROBUST (the rig sequence solve's Huber loss, k_smooth.inc): loc_corner<NE, true>'s rho, wgt and *over on the same
+// residual, the weight on the same 27 sums; every other caller leaves it false and gets the code above alone.
+template <bool NE, bool ROBUST = false>
+__device__ __forceinline__ double rig_corner(const double *cl, const double *R, const double *t, const double *X, double iu, double iv, double *acc,
+                                             double hk = 0.0, bool *over = nullptr)
 {
     const double *Re = cl + 9, *te = cl + 18;
     double Pr[3], P[3], uv[2], Jp[6];
@@ -54,6 +57,14 @@ __device__ __forceinline__ double rig_corner(const double *cl, const double *R, 
     c.half = 0; c.both_minima = 0; c.pad = 0;
     project_dev(c, P, uv, NE ? Jp : nullptr);
     const double r0 = uv[0] - iu, r1 = uv[1] - iv;
+    [[maybe_unused]] double wgt = 1.0, rho = 0.0;
+    if constexpr (ROBUST) {
+        const double e = r0 * r0 + r1 * r1, s = sqrt(e);
+        const bool o = s > hk;
+        wgt = o ? hk / s : 1.0;
+        rho = o ? 2.0 * hk * s - hk * hk : e;
+        *over = o;
+    }
     if constexpr (NE) {
         double Jr[6];  // J_proj Re
 #pragma unroll
@@ -72,12 +83,17 @@ __device__ __forceinline__ double rig_corner(const double *cl, const double *R, 
         }
 #pragma unroll
         for (int a = 0; a < 6; a++) {
-            acc[21 + a] += J0[a] * r0 + J1[a] * r1;
+            if constexpr (ROBUST) acc[21 + a] += wgt * (J0[a] * r0 + J1[a] * r1);
+            else acc[21 + a] += J0[a] * r0 + J1[a] * r1;
 #pragma unroll
-            for (int b = 0; b <= a; b++) acc[TRI(a, b)] += J0[a] * J0[b] + J1[a] * J1[b];
+            for (int b = 0; b <= a; b++) {
+                if constexpr (ROBUST) acc[TRI(a, b)] += wgt * (J0[a] * J0[b] + J1[a] * J1[b]);
+                else acc[TRI(a, b)] += J0[a] * J0[b] + J1[a] * J1[b];
+            }
         }
     }
-    return r0 * r0 + r1 * r1;
+    if constexpr (ROBUST) return rho;
+    else return r0 * r0 + r1 * r1;
 }
 
 // The slot model of a rig: global slot g is slot g % max_tags of camera g / max_tags in the camera-major block, its corners
@@ -94,10 +110,11 @@ struct LocRig {
         const int c = rig_cam_of(g, magic);
         return obs + ((size_t)c * n_frames + frame) * max_tags + (g - c * max_tags);
     }
-    template <bool NE>
-    __device__ __forceinline__ double corner(int g, const double *R, const double *t, const double *X, double iu, double iv, double *acc) const
+    template <bool NE, bool ROBUST = false>
+    __device__ __forceinline__ double corner(int g, const double *R, const double *t, const double *X, double iu, double iv, double *acc,
+                                             double hk = 0.0, bool *over = nullptr) const
     {
-        return rig_corner<NE>(cam_of(g), R, t, X, iu, iv, acc);
+        return rig_corner<NE, ROBUST>(cam_of(g), R, t, X, iu, iv, acc, hk, over);
     }
     // slot g's camera<-world candidate (loc_candidate) through its camera's mounting: rig<-world = inv(E) of it,
     // Re^T Rk, Re^T (tk - te)
@@ -114,19 +131,23 @@ struct LocRig {
             t[i] = Re[i] * dk[0] + Re[3 + i] * dk[1] + Re[6 + i] * dk[2];
         }
     }
+    // camera<-world of slot g's camera at the solved pose rig<-world = (R, t): E of it, Re R, Re t + te
+    __device__ __forceinline__ void camera_pose(int g, const double *R, const double *t, double *Rc, double *tc) const
+    {
+        const double *Re = cam_of(g) + 9, *te = cam_of(g) + 18;
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) Rc[3 * i + k] = Re[3 * i] * R[k] + Re[3 * i + 1] * R[3 + k] + Re[3 * i + 2] * R[6 + k];
+            tc[i] = Re[3 * i] * t[0] + Re[3 * i + 1] * t[1] + Re[3 * i + 2] * t[2] + te[i];
+        }
+    }
 };
 
-// One wavefront per frame; COV: also the first-order covariance of the world<-rig pose written (asl_pose_cov) into cov[frame]
-template <bool COV>
-__global__ void __launch_bounds__(64) k_localize_rig(const ObsRec *__restrict__ obs, int n_cams, int max_tags, const MapTagRec *__restrict__ map,
-                                                     int n_ids, const RigCamRec *__restrict__ rig, double half, double gate,
-                                                     CamPoseRec *__restrict__ out, PoseCovRec *__restrict__ cov, double sigma_px)
+// The camera table of a rig into LDS, by one wavefront: entry i of camera c (the lens coefficients past n_dist are zero
+// whatever the record holds).  The caller's next barrier (loc_gather's) publishes it.
+__device__ __forceinline__ void rig_fill_cams(double *cams, const RigCamRec *__restrict__ rig, int n_cams, int lane)
 {
-    extern __shared__ double s_dyn[];
-    const int lane = threadIdx.x;
-    double *cams = s_dyn;
-
-    // the camera table: entry i of camera c (the lens coefficients past n_dist are zero whatever the record holds)
     for (int i = lane; i < RIG_CAM_DOUBLES * n_cams; i += ASL_WAVE) {
         const int c = i / RIG_CAM_DOUBLES, e = i - c * RIG_CAM_DOUBLES;
         const RigCamRec *rc = rig + c;
@@ -141,6 +162,19 @@ __global__ void __launch_bounds__(64) k_localize_rig(const ObsRec *__restrict__ 
             v = rc->E[4 * (e - 18) + 3];
         cams[i] = v;
     }
+}
+
+// One wavefront per frame; COV: also the first-order covariance of the world<-rig pose written (asl_pose_cov) into cov[frame]
+template <bool COV>
+__global__ void __launch_bounds__(64) k_localize_rig(const ObsRec *__restrict__ obs, int n_cams, int max_tags, const MapTagRec *__restrict__ map,
+                                                     int n_ids, const RigCamRec *__restrict__ rig, double half, double gate,
+                                                     CamPoseRec *__restrict__ out, PoseCovRec *__restrict__ cov, double sigma_px)
+{
+    extern __shared__ double s_dyn[];
+    const int lane = threadIdx.x;
+    double *cams = s_dyn;
+
+    rig_fill_cams(cams, rig, n_cams, lane);
 
     const LocRig m{cams, obs, 65536u / (unsigned int)max_tags + 1u, n_cams, max_tags, (int)gridDim.x, (int)blockIdx.x};
     loc_solve_frame<COV>(m, loc_lds(s_dyn + RIG_CAM_DOUBLES * n_cams, m.nslots()), map, n_ids, half, gate, out + blockIdx.x,

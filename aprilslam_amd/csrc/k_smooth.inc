@@ -18,6 +18,11 @@
 // is not finite or a dt <= 0 is found by k_smooth_scan and solved as one without a posed frame, result status 4.  Every other
 // call leaves times NULL: a branch on the pointer, one value in the whole launch, ahead of each of the three places; no
 // instantiation of its own.  tests/smooth_timed_ref.py states it.
+// asl_smooth_rig_sequences_* (a rig, k_rig.inc): the pose solved for is rig<-world, a frame's slots are the n_cams * max_tags
+// global slots of the camera-major block.  Only the two kernels that cost corners look at a camera, and their bodies are
+// written once over a slot model (smooth_cand_frame, smooth_lin_frame; loc_solve_frame does the same for the localisation):
+// k_smooth_cand / k_smooth_lin are set-up, LocOneCam and one call, k_smooth_rig_cand / k_smooth_rig_lin the camera table to
+// LDS, LocRig and the same call.  Every other kernel below runs as it is.  tests/smooth_rig_ref.py states it.
 //   seed chain   k_smooth_cand   one wavefront per frame: the seed's pose A and, for a frame of exactly one taking-part slot,
 //                                its mirrored planar minimum B (loc_candidate), both costed over the frame's corners
 //                k_smooth_scan   one wavefront a sequence: the nearest posed frame at or before every frame (wave_scan of a maximum)
@@ -229,18 +234,17 @@ __device__ __forceinline__ SmoothSums smooth_sums(const SmoothSet &s, const Smoo
     return {cost, pix, soft};
 }
 
-// Candidates of one frame and their data costs; ROBUST: under the Huber loss of threshold hk pixels (loc_corner), as every
-// later cost of the call is
-template <bool ROBUST>
-__global__ void __launch_bounds__(64) k_smooth_cand(const ObsRec *__restrict__ obs, int max_tags, const MapTagRec *__restrict__ map, int n_ids,
-                                                    CamDev cam, const CamPoseRec *__restrict__ seed, double w, SmoothBufs b, double hk)
+// Candidates of frame f and their data costs over the slots of model m, by one wavefront; ROBUST: under the Huber loss of
+// threshold hk pixels (the model's corner), as every later cost of the call is.  Written once for k_smooth_cand (LocOneCam)
+// and k_smooth_rig_cand (LocRig), as loc_solve_frame is for the localisation.  Pose A is the seed's body<-world (the
+// camera's, or the rig's).  B, for a frame of exactly one taking-part slot over the whole model: that slot's camera<-tag =
+// (camera<-world of its camera at A) map[id], mirrored and taken back through inv(map[id]) and the model's candidate().
+template <bool ROBUST, class Model>
+__device__ __forceinline__ void smooth_cand_frame(const Model &m, const LocLds &L, const MapTagRec *__restrict__ map, int n_ids, double half,
+                                                  const CamPoseRec *__restrict__ seed, double w, const SmoothBufs &b, double hk, int f, int lane)
 {
-    extern __shared__ double s_dyn[];
-    const int lane = (int)threadIdx.x, f = (int)blockIdx.x;
-    const LocLds L = loc_lds(s_dyn, max_tags);
-    const ObsRec *fo = obs + (size_t)f * max_tags;
-    const LocOneCam m{cam, fo, max_tags};
-    const int npart = loc_gather([&](int s) { return fo + s; }, max_tags, map, n_ids, cam.half, [](int) { return false; }, L, lane);
+    const int n = m.nslots();
+    const int npart = loc_gather([&](int s) { return m.rec(s); }, n, map, n_ids, half, [](int) { return false; }, L, lane);
     const bool posed = seed[f].status == 0;
     if (lane == 0) { b.ntags[f] = npart; b.posed[f] = posed ? 1 : 0; }
     if (!posed) return;
@@ -263,20 +267,21 @@ __global__ void __launch_bounds__(64) k_smooth_cand(const ObsRec *__restrict__ o
     const bool has_b = npart == 1;
     if (has_b) {  // the one taking-part slot: the only term of the sum
         int ls = 0;
-        for (int s = lane; s < max_tags; s += ASL_WAVE)
+        for (int s = lane; s < n; s += ASL_WAVE)
             if (L.state[s] == 1) ls += s;
         const int s1 = butterfly_sum<64>(ls);
-        const double *Mp = map[fo[s1].id].T;
-        double M[12], To[12];
+        const double *Mp = map[m.rec(s1)->id].T;
+        double M[12], To[12], Rc[9], tc[3];
 #pragma unroll
         for (int k = 0; k < 12; k++) M[k] = Mp[k];
+        m.camera_pose(s1, RA, tA, Rc, tc);
 #pragma unroll
-        for (int i = 0; i < 3; i++) {  // camera<-tag = A map[id]
+        for (int i = 0; i < 3; i++) {  // camera<-tag = (camera<-world) map[id]
 #pragma unroll
             for (int j = 0; j < 4; j++)
-                To[4 * i + j] = RA[3 * i] * M[j] + RA[3 * i + 1] * M[4 + j] + RA[3 * i + 2] * M[8 + j] + (j == 3 ? tA[i] : 0.0);
+                To[4 * i + j] = Rc[3 * i] * M[j] + Rc[3 * i + 1] * M[4 + j] + Rc[3 * i + 2] * M[8 + j] + (j == 3 ? tc[i] : 0.0);
         }
-        loc_candidate(To, M, true, RB, tB);
+        m.candidate(s1, To, M, true, RB, tB);
         dB = data_cost(RB, tB) * w;
     }
     if (lane == 0) {
@@ -288,6 +293,32 @@ __global__ void __launch_bounds__(64) k_smooth_cand(const ObsRec *__restrict__ o
         b.dcost[2 * f] = dA;
         b.dcost[2 * f + 1] = dB;
     }
+}
+
+// One camera: one wavefront per frame, the frame's max_tags records
+template <bool ROBUST>
+__global__ void __launch_bounds__(64) k_smooth_cand(const ObsRec *__restrict__ obs, int max_tags, const MapTagRec *__restrict__ map, int n_ids,
+                                                    CamDev cam, const CamPoseRec *__restrict__ seed, double w, SmoothBufs b, double hk)
+{
+    extern __shared__ double s_dyn[];
+    const int f = (int)blockIdx.x;
+    const LocOneCam m{cam, obs + (size_t)f * max_tags, max_tags};
+    smooth_cand_frame<ROBUST>(m, loc_lds(s_dyn, max_tags), map, n_ids, cam.half, seed, w, b, hk, f, (int)threadIdx.x);
+}
+
+// A rig (asl_smooth_rig_sequences_*): one wavefront per frame over its n_cams * max_tags global slots in the camera-major
+// block obs[n_cams][n_frames][max_tags], n_frames the frames of the whole call; the camera table to LDS first, as
+// k_localize_rig fills it; dynamic LDS rig_lds_bytes(n_cams, max_tags).  seed and the poses solved for are the rig's.
+template <bool ROBUST>
+__global__ void __launch_bounds__(64) k_smooth_rig_cand(const ObsRec *__restrict__ obs, int n_cams, int n_frames, int max_tags,
+                                                        const MapTagRec *__restrict__ map, int n_ids, const RigCamRec *__restrict__ rig, double half,
+                                                        const CamPoseRec *__restrict__ seed, double w, SmoothBufs b, double hk)
+{
+    extern __shared__ double s_dyn[];
+    const int lane = (int)threadIdx.x, f = (int)blockIdx.x;
+    rig_fill_cams(s_dyn, rig, n_cams, lane);
+    const LocRig m{s_dyn, obs, 65536u / (unsigned int)max_tags + 1u, n_cams, max_tags, n_frames, f};
+    smooth_cand_frame<ROBUST>(m, loc_lds(s_dyn + RIG_CAM_DOUBLES * n_cams, m.nslots()), map, n_ids, half, seed, w, b, hk, f, lane);
 }
 
 // A sequence's src[f]: the nearest posed frame of the sequence at or before f (-1: none), as a frame of the call; its head:
@@ -418,18 +449,28 @@ __global__ void __launch_bounds__(SM_WG) k_smooth_fill(SmoothBufs b, const CamPo
 // Frame f of a state: its pose (trial: the current one stepped by delta), pixel cost, H and g, and the motion blocks of
 // the pair (f, f + 1) at the same state.  ROBUST: the cost is the Huber loss of threshold hk pixels, H and g are the sums
 // weighted by it (iteratively reweighted Gauss-Newton, no second-order term), and the state carries the frame's soft slots.
-// Timed: the pair's weights are (isr, ist) / sqrt(times[f + 1] - times[f]), the random walk's over that time
-template <bool ROBUST>
-__global__ void __launch_bounds__(64) k_smooth_lin(const ObsRec *__restrict__ obs, int max_tags, const MapTagRec *__restrict__ map, int n_ids,
-                                                   CamDev cam, SmoothBufs b, int trial, double isr, double ist, double hk)
+// Timed: the pair's weights are (isr, ist) / sqrt(times[f + 1] - times[f]), the random walk's over that time.
+// The body is written once over a slot model, as smooth_cand_frame is: smooth_lin_runs says whether the frame's wavefront
+// has work (before any set-up), smooth_lin_frame does it; SmoothLinLds is the kernel's static LDS.
+struct SmoothLinLds {
+    double RD[9], tD[3], m[6], B[36], Ad[36], Jn[36], Jp[36];
+};
+
+__device__ __forceinline__ bool smooth_lin_runs(const SmoothBufs &b, int f, int trial, SmoothSeq &q)
 {
-    extern __shared__ double s_dyn[];
-    __shared__ double s_RD[9], s_tD[3], s_m[6], s_B[36], s_Ad[36], s_Jn[36], s_Jp[36];
-    const int lane = (int)threadIdx.x, f = (int)blockIdx.x, n = b.n;
-    const SmoothSeq q = smooth_seq_of_uniform(b, f);
+    q = smooth_seq_of_uniform(b, f);
     const int *head = b.head + SMH__N * q.k;
-    if (head[SMH_NPOSED] == 0) return;
-    if (trial && (b.lm[SM__N * q.k + SM_STOP] != 0.0 || head[SMH_FAIL])) return;
+    if (head[SMH_NPOSED] == 0) return false;
+    if (trial && (b.lm[SM__N * q.k + SM_STOP] != 0.0 || head[SMH_FAIL])) return false;
+    return true;
+}
+
+template <bool ROBUST, class Model>
+__device__ __forceinline__ void smooth_lin_frame(const Model &m, const LocLds &L, SmoothLinLds &sh, const MapTagRec *__restrict__ map, int n_ids,
+                                                 double half, const SmoothBufs &b, const SmoothSeq &q, int trial, double isr, double ist, double hk,
+                                                 int f, int lane)
+{
+    const int n = b.n;
     const SmoothSet in = smooth_set(b.set[0], (size_t)n), out = smooth_set(b.set[trial], (size_t)n);
     double P[12];
 #pragma unroll
@@ -440,10 +481,7 @@ __global__ void __launch_bounds__(64) k_smooth_lin(const ObsRec *__restrict__ ob
         for (int k = 0; k < 6; k++) d[k] = b.delta[6 * (size_t)f + k];
         smooth_update(P, d);
     }
-    const LocLds L = loc_lds(s_dyn, max_tags);
-    const ObsRec *fo = obs + (size_t)f * max_tags;
-    const LocOneCam m{cam, fo, max_tags};
-    loc_gather([&](int s) { return fo + s; }, max_tags, map, n_ids, cam.half, [](int) { return false; }, L, lane);
+    loc_gather([&](int s) { return m.rec(s); }, m.nslots(), map, n_ids, half, [](int) { return false; }, L, lane);
     double ne[27], c;
     [[maybe_unused]] int soft;
     if constexpr (ROBUST) c = loc_pass<true, true>(m, P, P + 9, L, lane, ne, hk, &soft);
@@ -478,11 +516,11 @@ __global__ void __launch_bounds__(64) k_smooth_lin(const ObsRec *__restrict__ ob
     double *mot = out.mot + SM_MOT * (size_t)f;
     if (lane == 0) {
 #pragma unroll
-        for (int k = 0; k < 9; k++) s_RD[k] = RD[k];
+        for (int k = 0; k < 9; k++) sh.RD[k] = RD[k];
 #pragma unroll
-        for (int k = 0; k < 3; k++) s_tD[k] = tD[k];
+        for (int k = 0; k < 3; k++) sh.tD[k] = tD[k];
 #pragma unroll
-        for (int k = 0; k < 6; k++) s_m[k] = mv[k];
+        for (int k = 0; k < 6; k++) sh.m[k] = mv[k];
         mot[120] = mm;
     }
     __syncthreads();
@@ -490,30 +528,30 @@ __global__ void __launch_bounds__(64) k_smooth_lin(const ObsRec *__restrict__ ob
     if (lane < 36) {  // B = [[I, 0], [-[t_D]x, I]], Ad = [[R_D, 0], [[t_D]x R_D, R_D]]
         double bv = i == j ? 1.0 : 0.0, av = 0.0;
         if (i >= 3 && j < 3) {
-            bv = -smooth_skew(s_tD, i - 3, j);
-            av = smooth_skew(s_tD, i - 3, 0) * s_RD[j] + smooth_skew(s_tD, i - 3, 1) * s_RD[3 + j] + smooth_skew(s_tD, i - 3, 2) * s_RD[6 + j];
+            bv = -smooth_skew(sh.tD, i - 3, j);
+            av = smooth_skew(sh.tD, i - 3, 0) * sh.RD[j] + smooth_skew(sh.tD, i - 3, 1) * sh.RD[3 + j] + smooth_skew(sh.tD, i - 3, 2) * sh.RD[6 + j];
         } else if (i < 3 && j < 3)
-            av = s_RD[3 * i + j];
+            av = sh.RD[3 * i + j];
         else if (i >= 3 && j >= 3)
-            av = s_RD[3 * (i - 3) + j - 3];
-        s_B[lane] = bv;
-        s_Ad[lane] = av;
+            av = sh.RD[3 * (i - 3) + j - 3];
+        sh.B[lane] = bv;
+        sh.Ad[lane] = av;
     }
     __syncthreads();
     if (lane < 36) {  // Jn = W B, Jp = -W B Ad
         const double wi = i < 3 ? isr : ist;
         double s = 0;
-        for (int k = 0; k < 6; k++) s += s_B[6 * i + k] * s_Ad[6 * k + j];
-        s_Jn[lane] = wi * s_B[lane];
-        s_Jp[lane] = -(wi * s);
+        for (int k = 0; k < 6; k++) s += sh.B[6 * i + k] * sh.Ad[6 * k + j];
+        sh.Jn[lane] = wi * sh.B[lane];
+        sh.Jp[lane] = -(wi * s);
     }
     __syncthreads();
     if (lane < 36) {
         double qn = 0, qp = 0, cc = 0;
         for (int k = 0; k < 6; k++) {
-            qn += s_Jp[6 * k + i] * s_Jp[6 * k + j];
-            qp += s_Jn[6 * k + i] * s_Jn[6 * k + j];
-            cc += s_Jn[6 * k + i] * s_Jp[6 * k + j];
+            qn += sh.Jp[6 * k + i] * sh.Jp[6 * k + j];
+            qp += sh.Jn[6 * k + i] * sh.Jn[6 * k + j];
+            cc += sh.Jn[6 * k + i] * sh.Jp[6 * k + j];
         }
         mot[lane] = qn;
         mot[36 + lane] = qp;
@@ -521,10 +559,39 @@ __global__ void __launch_bounds__(64) k_smooth_lin(const ObsRec *__restrict__ ob
     }
     if (lane < 6) {
         double gn = 0, gp = 0;
-        for (int k = 0; k < 6; k++) { gn += s_Jp[6 * k + lane] * s_m[k]; gp += s_Jn[6 * k + lane] * s_m[k]; }
+        for (int k = 0; k < 6; k++) { gn += sh.Jp[6 * k + lane] * sh.m[k]; gp += sh.Jn[6 * k + lane] * sh.m[k]; }
         mot[108 + lane] = gn;
         mot[114 + lane] = gp;
     }
+}
+
+template <bool ROBUST>
+__global__ void __launch_bounds__(64) k_smooth_lin(const ObsRec *__restrict__ obs, int max_tags, const MapTagRec *__restrict__ map, int n_ids,
+                                                   CamDev cam, SmoothBufs b, int trial, double isr, double ist, double hk)
+{
+    extern __shared__ double s_dyn[];
+    __shared__ SmoothLinLds s_lin;
+    const int f = (int)blockIdx.x;
+    SmoothSeq q;
+    if (!smooth_lin_runs(b, f, trial, q)) return;
+    const LocOneCam m{cam, obs + (size_t)f * max_tags, max_tags};
+    smooth_lin_frame<ROBUST>(m, loc_lds(s_dyn, max_tags), s_lin, map, n_ids, cam.half, b, q, trial, isr, ist, hk, f, (int)threadIdx.x);
+}
+
+// The rig's, set up as k_smooth_rig_cand
+template <bool ROBUST>
+__global__ void __launch_bounds__(64) k_smooth_rig_lin(const ObsRec *__restrict__ obs, int n_cams, int n_frames, int max_tags,
+                                                       const MapTagRec *__restrict__ map, int n_ids, const RigCamRec *__restrict__ rig, double half,
+                                                       SmoothBufs b, int trial, double isr, double ist, double hk)
+{
+    extern __shared__ double s_dyn[];
+    __shared__ SmoothLinLds s_lin;
+    const int lane = (int)threadIdx.x, f = (int)blockIdx.x;
+    SmoothSeq q;
+    if (!smooth_lin_runs(b, f, trial, q)) return;
+    rig_fill_cams(s_dyn, rig, n_cams, lane);
+    const LocRig m{s_dyn, obs, 65536u / (unsigned int)max_tags + 1u, n_cams, max_tags, n_frames, f};
+    smooth_lin_frame<ROBUST>(m, loc_lds(s_dyn + RIG_CAM_DOUBLES * n_cams, m.nslots()), s_lin, map, n_ids, half, b, q, trial, isr, ist, hk, f, lane);
 }
 
 // After the chain's linearisation: the LM state, the seed costs

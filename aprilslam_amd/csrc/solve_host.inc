@@ -584,13 +584,16 @@ extern "C" int asl_map_robust_batch(asl_detector *d, const asl_obs *obs, int n_f
 #define SMOOTH_SEQS 65535         // sequences of one call
 #define SMOOTH_FRAMES 1048576     // frames of one call: the work buffers, about 3.6 KB a frame, stay under 4 GB
 
-// One smoothing call, whichever of the ten entry points made it, in their argument order.  The single-sequence forms leave
+// One smoothing call, whichever of the twelve entry points made it, in their argument order (n_cams and rig, which only the
+// rig pair gives, stand last: the ten single-camera forms leave them 0 and NULL).  The single-sequence forms leave
 // seq_start NULL, n_seq 1 and sequences false: the one sequence {0, n_frames}; seq_start is a host array of n_seq + 1
 // offsets in every form.  The plain forms leave cov NULL and with_cov false; the sequences forms set with_cov where cov is
 // given.  The host forms may leave seed NULL: the per-frame localisation of the same block.  obs, map, seed, out, result
 // and cov are all host or all device pointers.  huber_px: 0 from the six plain entry points (the squared corner loss and
 // its kernels), the robust and the timed pairs' threshold in pixels otherwise.  times: NULL from the eight entry points
 // without it (frame f is at time f), the timed pair's n_frames doubles otherwise, a host or a device array as the rest.
+// The rig pair (asl_smooth_rig_sequences_*) gives n_cams and the camera table, host or device as the rest, as LocCall
+// carries them, and leaves cam's K and dist NULL, n_dist 0; obs is then the camera-major block of n_cams * n_frames rows.
 struct SmoothCall {
     const void *obs; int n_frames, max_tags;
     const void *map; int n_ids;
@@ -599,7 +602,10 @@ struct SmoothCall {
     double sigma_px, sigma_rot, sigma_trans, huber_px; int max_iters;
     void *out, *result, *cov;
     bool with_cov, sequences;
+    int n_cams; const void *rig;
 };
+
+static bool is_rig(const SmoothCall &c) { return c.n_cams || c.rig; }
 
 static bool smooth_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
 {
@@ -609,10 +615,13 @@ static bool smooth_overlap(const void *a, size_t a_bytes, const void *b, size_t 
 
 // Every refusal, before anything is written or enqueued.  device: the seed must be there, and the outputs apart from it,
 // from the times and from each other (host arrays are apart by contract).  The times' values are the device's to judge.
+// A rig's table is checked last, as check_localize_call checks it: where it is, or (device) in a copy read back.
 static int check_smooth_call(const asl_detector *d, const SmoothCall &c, bool device)
 {
+    const bool rig = is_rig(c);
     if (!d) return fail(ASL_EINVAL, "NULL detector");
-    if (!c.obs || !c.map || !c.cam.K || !c.out || !c.result || (c.sequences && !c.seq_start)) return fail(ASL_EINVAL, "NULL argument");
+    if (!c.obs || !c.map || !(rig ? c.rig : (const void *)c.cam.K) || !c.out || !c.result || (c.sequences && !c.seq_start))
+        return fail(ASL_EINVAL, "NULL argument");
     const int most = c.sequences ? SMOOTH_FRAMES : SMOOTH_SEQ_FRAMES;
     if (c.n_frames < 1 || c.n_frames > most) return fail(ASL_EINVAL, "n_frames must be in [1, %d] (got %d)", most, c.n_frames);
     if (c.sequences) {
@@ -624,15 +633,18 @@ static int check_smooth_call(const asl_detector *d, const SmoothCall &c, bool de
             if (len < 1 || len > SMOOTH_SEQ_FRAMES) return fail(ASL_EINVAL, "sequence %d must have 1 to %d frames (got %lld)", k, SMOOTH_SEQ_FRAMES, (long long)len);
         }
     }
+    if (rig && (c.n_cams < 1 || c.n_cams > RIG_MAX_CAMS)) return fail(ASL_EINVAL, "n_cams must be in [1, %d] (got %d)", RIG_MAX_CAMS, c.n_cams);
     if (int rc = check_obs_args(c.max_tags, c.n_ids, c.cam)) return rc;
-    for (int k = 0; k < 9; k++)
+    if (rig && c.n_cams * c.max_tags > RIG_MAX_SLOTS)
+        return fail(ASL_EINVAL, "n_cams * max_tags must be <= %d (got %d x %d)", RIG_MAX_SLOTS, c.n_cams, c.max_tags);
+    for (int k = 0; !rig && k < 9; k++)
         if (!std::isfinite(c.cam.K[k])) return fail(ASL_EINVAL, "K is not finite");
     for (double s : {c.sigma_px, c.sigma_rot, c.sigma_trans})
         if (!(s > 0) || !std::isfinite(s)) return fail(ASL_EINVAL, "sigma_px, sigma_rot and sigma_trans must be positive and finite (got %g)", s);
     if (!(c.huber_px >= 0) || !std::isfinite(c.huber_px)) return fail(ASL_EINVAL, "huber_px must be finite and not negative (got %g)", c.huber_px);
     if (c.max_iters < 1 || c.max_iters > 100) return fail(ASL_EINVAL, "max_iters must be in [1, 100] (got %d)", c.max_iters);
     if ((device && !c.seed) || (c.with_cov && !c.cov)) return fail(ASL_EINVAL, "NULL argument");
-    if (!device) return ASL_OK;
+    if (!device) return rig ? check_rig_table((const asl_rig_camera *)c.rig, c.n_cams) : ASL_OK;
     const size_t poses = sizeof(asl_cam_pose) * (size_t)c.n_frames, covs = sizeof(asl_pose_cov) * (size_t)c.n_frames;
     if (smooth_overlap(c.seed, poses, c.out, poses)) return fail(ASL_EINVAL, "d_out overlaps d_seed");
     if (c.with_cov && (smooth_overlap(c.cov, covs, c.out, poses) || smooth_overlap(c.cov, covs, c.seed, poses)))
@@ -640,13 +652,18 @@ static int check_smooth_call(const asl_detector *d, const SmoothCall &c, bool de
     const size_t times = sizeof(double) * (size_t)c.n_frames;
     if (c.times && (smooth_overlap(c.times, times, c.out, poses) || (c.with_cov && smooth_overlap(c.times, times, c.cov, covs))))
         return fail(ASL_EINVAL, "d_times overlaps d_out or d_cov");
-    return ASL_OK;
+    if (!rig) return ASL_OK;
+    asl_rig_camera tab[RIG_MAX_CAMS];
+    HIPCHK(hipSetDevice(d->device));
+    HIPCHK(hipMemcpy(tab, c.rig, sizeof(asl_rig_camera) * (size_t)c.n_cams, hipMemcpyDeviceToHost));
+    return check_rig_table(tab, c.n_cams);
 }
 
 // c's pointers are the device's but seq_start (host, not read for n_seq 1); everything is enqueued on st, nothing waits.
 // cov: NULL, or the frames' asl_pose_cov (two more launches).  n_seq > 1: k_smooth_seqs first, a launch per SM_SEQ_CHUNK
 // sequences, which carries the offsets to the device in its arguments.  huber_px > 0: the robust instantiations of the two
-// kernels that cost corners, the same launches otherwise.  times: carried in SmoothBufs, the same launches.
+// kernels that cost corners, the same launches otherwise.  times: carried in SmoothBufs, the same launches.  A rig: those two
+// kernels are k_smooth_rig_cand and k_smooth_rig_lin over the camera-major block, with the rig's LDS; nothing else differs.
 static int launch_smooth(asl_detector *d, const SmoothCall &c, hipStream_t st)
 {
     const size_t n = (size_t)c.n_frames, ns = (size_t)c.n_seq;
@@ -661,12 +678,15 @@ static int launch_smooth(asl_detector *d, const SmoothCall &c, hipStream_t st)
             if (c.n_seq > 1) { b.seq = ws.take<int>(ns + 1); b.fseq = ws.take<int>(n); }
         }))
         return fail(ASL_ENOMEM, "sequence localisation workspace allocation failed");
-    const CamDev cam = make_cam(d, c.cam);
+    static const double no_K[9] = {};
+    const bool rig = is_rig(c);
+    const CamDev cam = make_cam(d, rig ? no_K : c.cam.K, c.cam.dist, c.cam.n_dist, c.cam.tag_size);   // a rig: for its half alone
     const ObsRec *obs = (const ObsRec *)c.obs;
     const MapTagRec *map = (const MapTagRec *)c.map;
+    const RigCamRec *tab = (const RigCamRec *)c.rig;
     const CamPoseRec *seed = (const CamPoseRec *)c.seed;
     const double w = 1.0 / (c.sigma_px * c.sigma_px), isr = 1.0 / c.sigma_rot, ist = 1.0 / c.sigma_trans;
-    const size_t lds = loc_lds_bytes(c.max_tags);
+    const size_t lds = rig ? rig_lds_bytes(c.n_cams, c.max_tags) : loc_lds_bytes(c.max_tags);
     const dim3 frames((unsigned int)c.n_frames), wave(ASL_WAVE), seqs((unsigned int)c.n_seq), wg(SM_WG), per_thread((unsigned int)((n + SM_WG - 1) / SM_WG));
 
     static_assert(SM_SET <= SM_WG, "k_smooth_commit: a thread an entry of a frame");
@@ -683,18 +703,30 @@ static int launch_smooth(asl_detector *d, const SmoothCall &c, hipStream_t st)
     const bool robust = c.huber_px > 0;
     const auto cand = robust ? k_smooth_cand<true> : k_smooth_cand<false>;
     const auto lin = robust ? k_smooth_lin<true> : k_smooth_lin<false>;
-    hipLaunchKernelGGL(cand, frames, wave, lds, st, obs, c.max_tags, map, c.n_ids, cam, seed, w, b, c.huber_px);
+    const auto rig_cand = robust ? k_smooth_rig_cand<true> : k_smooth_rig_cand<false>;
+    const auto rig_lin = robust ? k_smooth_rig_lin<true> : k_smooth_rig_lin<false>;
+    const auto linearise = [&](int trial) {
+        if (rig)
+            hipLaunchKernelGGL(rig_lin, frames, wave, lds, st, obs, c.n_cams, c.n_frames, c.max_tags, map, c.n_ids, tab, cam.half, b, trial, isr, ist,
+                               c.huber_px);
+        else
+            hipLaunchKernelGGL(lin, frames, wave, lds, st, obs, c.max_tags, map, c.n_ids, cam, b, trial, isr, ist, c.huber_px);
+    };
+    if (rig)
+        hipLaunchKernelGGL(rig_cand, frames, wave, lds, st, obs, c.n_cams, c.n_frames, c.max_tags, map, c.n_ids, tab, cam.half, seed, w, b, c.huber_px);
+    else
+        hipLaunchKernelGGL(cand, frames, wave, lds, st, obs, c.max_tags, map, c.n_ids, cam, seed, w, b, c.huber_px);
     hipLaunchKernelGGL(k_smooth_scan, seqs, wave, 0, st, b);
     hipLaunchKernelGGL(k_smooth_trans, dim3((unsigned int)((n + ASL_WAVE - 1) / ASL_WAVE)), wave, 0, st, b, isr, ist);
     hipLaunchKernelGGL(k_smooth_dp, seqs, wave, 0, st, b);
     hipLaunchKernelGGL(k_smooth_fill, per_thread, wg, 0, st, b, seed);
-    hipLaunchKernelGGL(lin, frames, wave, lds, st, obs, c.max_tags, map, c.n_ids, cam, b, 0, isr, ist, c.huber_px);
+    linearise(0);
     hipLaunchKernelGGL(k_smooth_init, seqs, wg, 0, st, b, w);
     range_pop();
     range_push("smooth: LM");
     for (int it = 0; it < c.max_iters; it++) {
         hipLaunchKernelGGL(k_smooth_solve, seqs, wave, 0, st, b, w);
-        hipLaunchKernelGGL(lin, frames, wave, lds, st, obs, c.max_tags, map, c.n_ids, cam, b, 1, isr, ist, c.huber_px);
+        linearise(1);
         hipLaunchKernelGGL(k_smooth_decide, seqs, wg, 0, st, b, w);
         hipLaunchKernelGGL(k_smooth_commit, commit_blocks, wg, 0, st, b);
     }
@@ -710,22 +742,27 @@ static int launch_smooth(asl_detector *d, const SmoothCall &c, hipStream_t st)
     return ASL_OK;
 }
 
-static constexpr auto smooth_frames_device = frames_device<SmoothCall, check_smooth_call, launch_smooth>;   // the five device forms
+static constexpr auto smooth_frames_device = frames_device<SmoothCall, check_smooth_call, launch_smooth>;   // the six device forms
 
-// the five host forms; a seed not given is the per-frame localisation of the same block, gate 0; times are staged as a seed is
+// the six host forms; a seed not given is the per-frame localisation of the same block (a rig: the rig localisation), gate 0;
+// times and a rig's table are staged as a seed is
 static int smooth_batch(asl_detector *d, const SmoothCall &c)
 {
     if (int rc = check_smooth_call(d, c, false)) return rc;
     const size_t poses = sizeof(asl_cam_pose) * (size_t)c.n_frames;
     OutPiece o[] = {{c.result, sizeof(asl_smooth_result) * (size_t)c.n_seq}, {c.out, poses}, {nullptr, poses},
-                    {c.cov, c.cov ? sizeof(asl_pose_cov) * (size_t)c.n_frames : 0}, {nullptr, c.times ? sizeof(double) * (size_t)c.n_frames : 0}};
-    if (int rc = stage_host_call(d, "sequence localisation", o, c.obs, c.n_frames, c.max_tags, c.map, c.n_ids)) return rc;
+                    {c.cov, c.cov ? sizeof(asl_pose_cov) * (size_t)c.n_frames : 0}, {nullptr, c.times ? sizeof(double) * (size_t)c.n_frames : 0},
+                    {nullptr, sizeof(asl_rig_camera) * (size_t)c.n_cams}};
+    const bool rig = is_rig(c);
+    if (int rc = stage_host_call(d, "sequence localisation", o, c.obs, (rig ? c.n_cams : 1) * c.n_frames, c.max_tags, c.map, c.n_ids)) return rc;
     SmoothCall dc = c;
     dc.obs = d->loc_obs.p; dc.map = d->loc_map.p; dc.result = o[0].dev; dc.out = o[1].dev; dc.seed = o[2].dev; dc.cov = o[3].dev; dc.times = o[4].dev;
+    dc.rig = o[5].dev;
     if (c.times) HIPCHK(hipMemcpy(o[4].dev, c.times, o[4].bytes, hipMemcpyHostToDevice));
+    if (rig) HIPCHK(hipMemcpy(o[5].dev, c.rig, o[5].bytes, hipMemcpyHostToDevice));
     if (c.seed)
         HIPCHK(hipMemcpy(o[2].dev, c.seed, poses, hipMemcpyHostToDevice));
-    else if (int rc = launch_localize(d, {dc.obs, 0, c.n_frames, c.max_tags, dc.map, c.n_ids, nullptr, c.cam, 0.0, 0.0, o[2].dev, nullptr, false}, nullptr))
+    else if (int rc = launch_localize(d, {dc.obs, c.n_cams, c.n_frames, c.max_tags, dc.map, c.n_ids, dc.rig, c.cam, 0.0, 0.0, o[2].dev, nullptr, false}, nullptr))
         return rc;
     if (int rc = launch_smooth(d, dc, nullptr)) return rc;
     return fetch_out(o);
@@ -819,4 +856,24 @@ extern "C" int asl_smooth_timed_sequences_batch(asl_detector *d, const asl_obs *
 {
     return smooth_batch(d, {obs, n_frames, max_tags, map, n_ids, {K, dist, n_dist, tag_size}, seed, times, seq_start, n_seq,
                             sigma_px, sigma_rot, sigma_trans, huber, max_iters, out, results, cov, cov != nullptr, true});
+}
+
+extern "C" int asl_smooth_rig_sequences_device(asl_detector *d, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map,
+                                               int n_ids, const void *d_rig, double tag_size, const void *d_seed, const double *d_frame_times,
+                                               const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
+                                               double rig_huber_px, int max_iters, void *d_out, void *d_results, void *d_cov, void *stream)
+{
+    return smooth_frames_device(d, {d_obs, n_frames, max_tags, d_map, n_ids, {nullptr, nullptr, 0, tag_size}, d_seed, d_frame_times, seq_start, n_seq,
+                                    sigma_px, sigma_rot, sigma_trans, rig_huber_px, max_iters, d_out, d_results, d_cov, d_cov != nullptr, true,
+                                    n_cams, d_rig}, stream);
+}
+
+extern "C" int asl_smooth_rig_sequences_batch(asl_detector *d, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_map_tag *map,
+                                              int n_ids, const asl_rig_camera *rig, double tag_size, const asl_cam_pose *seed,
+                                              const double *frame_times, const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot,
+                                              double sigma_trans, double rig_huber_px, int max_iters, asl_cam_pose *out, asl_smooth_result *results,
+                                              asl_pose_cov *cov)
+{
+    return smooth_batch(d, {obs, n_frames, max_tags, map, n_ids, {nullptr, nullptr, 0, tag_size}, seed, frame_times, seq_start, n_seq,
+                            sigma_px, sigma_rot, sigma_trans, rig_huber_px, max_iters, out, results, cov, cov != nullptr, true, n_cams, rig});
 }

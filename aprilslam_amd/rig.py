@@ -7,11 +7,17 @@ mounting.  A frame index is one instant for all cameras.
 
     RigCamera       one camera: K, dist (0, 4 or 5 coefficients), T_cam_rig = camera<-rig 4x4 (the mounting)
     Rig             the cameras in block order; as_records() -> RIG_CAMERA_DTYPE (asl_rig_camera), save / load,
-                    localize(), from_camera_poses()
+                    localize(), localize_sequence() / localize_sequences(), from_camera_poses()
+
+Consecutive frames of the rig solved together under a random-walk motion prior (asl_smooth_rig_sequences_batch, k_smooth.inc):
+Rig.localize_sequence and Rig.localize_sequences return smooth.SmoothResult, its poses the rig's (world<-rig).  A frame in
+which no camera sees a mapped tag is carried by its neighbours, a frame whose only tag is one small tag in one camera is
+kept out of its mirrored planar minimum by them, and corner noise is averaged over the sequence.
 """
 import numpy as np
 
 from ._lib import CAM_POSE_DTYPE, OBS_DTYPE, RIG_CAMERA_DTYPE
+from .smooth import SmoothResult
 
 MAX_CAMERAS = 16
 MAX_SLOTS = 256          # n_cams * max_tags
@@ -98,6 +104,35 @@ class Rig:
         if o.shape[0] * o.shape[2] > MAX_SLOTS:
             raise ValueError("n_cams * max_tags must be <= %d" % MAX_SLOTS)
         return det.localize_rig(o, tag_map, self.as_records(), tag_size, max_tag_rms_px, float(sigma_px) if with_cov else None)
+
+    def _block(self, obs):
+        o = np.asarray(obs)
+        if o.dtype != OBS_DTYPE or o.ndim != 3 or o.shape[0] != len(self.cameras):
+            raise ValueError("obs must be (%d, n_frames, max_tags) asl_obs records" % len(self.cameras))
+        if o.shape[0] * o.shape[2] > MAX_SLOTS:
+            raise ValueError("n_cams * max_tags must be <= %d" % MAX_SLOTS)
+        return o
+
+    def localize_sequence(self, det, obs, tag_map, tag_size, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, seed=None,
+                          times=None, huber_px=0.0, with_cov=False):
+        """The rig's consecutive frames solved together (Detector.smooth_rig): obs (n_cams, n_frames, max_tags) OBS_DTYPE,
+        camera-major -> smooth.SmoothResult with world<-rig for EVERY frame.  seed: localize() of the same obs (None: it runs
+        first, and is not kept); times, huber_px, with_cov: as Detector.smooth."""
+        r = det.smooth_rig(self._block(obs), tag_map, self.as_records(), tag_size, sigma_px, sigma_rot, sigma_trans, max_iters, seed, None, times,
+                           huber_px, with_cov)
+        return SmoothResult(r[0], r[1], seed=seed, cov=r[2] if with_cov else None, times=times)
+
+    def localize_sequences(self, det, obs, seq_start, tag_map, tag_size, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, seed=None,
+                           times=None, huber_px=0.0, with_cov=False):
+        """Several sequences of the rig in one call, solved side by side: sequence k is the frames seq_start[k]:seq_start[k + 1]
+        of obs (n_seq + 1 offsets from 0 to n_frames) -> [smooth.SmoothResult], each what localize_sequence returns for its
+        frames alone."""
+        r = det.smooth_rig(self._block(obs), tag_map, self.as_records(), tag_size, sigma_px, sigma_rot, sigma_trans, max_iters, seed, seq_start, times,
+                           huber_px, with_cov)
+        ss = np.asarray(seq_start, dtype=np.int64).ravel()
+        tm = None if times is None else np.asarray(times, dtype=np.float64).ravel()
+        return [SmoothResult(r[0][a:b], r[1][k], seed=None if seed is None else np.asarray(seed)[a:b], cov=r[2][a:b] if with_cov else None,
+                             times=None if tm is None else tm[a:b]) for k, (a, b) in enumerate(zip(ss[:-1], ss[1:]))]
 
     @classmethod
     def from_camera_poses(cls, cams, poses_by_cam):

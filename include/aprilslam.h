@@ -595,6 +595,45 @@ int asl_smooth_timed_sequences_batch(asl_detector *det, const asl_obs *obs, int 
                                      double sigma_trans, double huber, int max_iters, asl_cam_pose *out, asl_smooth_result *results,
                                      asl_pose_cov *cov);
 
+/* Sequence localisation for a rig: asl_smooth_timed_sequences_device over the cameras of asl_localize_rig_frames_device.
+   One pose rig<-world per frame of the rig's consecutive frames, minimising the reprojection error of all mapped corners of
+   all cameras (/ sigma_px^2; a corner X of camera c contributes project_c(E_c (rig<-world) X) - pixel, through a Huber loss
+   of rig_huber_px pixels as in asl_smooth_robust_sequences_device, 0: squared) plus the random-walk motion prior between
+   consecutive rig poses.  Everything between frames -- the seed chain's dynamic programme, the fill of unposed frames, the
+   block-tridiagonal solve, the LM schedule, the stop rule, several sequences side by side, the frame times and the
+   covariance -- is that of the single-camera calls.
+   d_obs: n_cams x n_frames x max_tags records, camera-major as for asl_localize_rig_frames_device, n_frames the frames of
+   the whole call (all sequences end to end); a frame's records are its global slots g = c * max_tags + s.  d_rig: n_cams
+   asl_rig_camera in device memory, read back and checked before anything is enqueued (the one synchronous step), so it
+   must be complete when the call is made.  tag_size is one value for the rig.  d_seed: one asl_cam_pose per frame, what
+   asl_localize_rig_frames_device wrote for the same block (T = world<-rig; status 0: posed).  d_frame_times: NULL (frame f
+   is at time f), or n_frames doubles on the device as d_times of asl_smooth_timed_sequences_device.  seq_start, n_seq: as
+   asl_smooth_sequences_device; one sequence is n_seq = 1 with seq_start = {0, n_frames}.
+   Seed chain: candidate A is the seed's rig<-world.  B exists for a frame with exactly one taking-part global slot over
+   all cameras and goes through that slot's camera c: camera_c<-tag = E_c A map[id], its mirrored planar minimum, taken back
+   through inv(map[id]) and inv(E_c).
+   d_out: one asl_cam_pose per frame with T = world<-rig; n_tags counts taking-part global slots, n_rejected the soft ones,
+   rms_px / rms_seed_px are over the corners of all cameras, seed_slot is the seed's global slot (+256 where the chain chose
+   B, -1 for a filled frame), status as in asl_smooth_frames_device (0 data, 6 no mapped tag in any camera, carried by the
+   prior, 4 failed solve, 1 nothing to solve).  d_results: n_seq asl_smooth_result.  d_cov: NULL, or one asl_pose_cov per
+   frame of the world<-rig pose, as asl_smooth_cov_frames_device; the mountings and the map are taken as exact.  A rig of one
+   camera with E = identity solves the single-camera problem (the same numbers to rounding, not the same bytes).
+   ASL_EINVAL, nothing written or enqueued: whatever asl_smooth_timed_sequences_device refuses of the arguments both have;
+   d_rig NULL; n_cams outside [1, 16]; n_cams * max_tags > 256; a camera with n_dist not 0 / 4 / 5, a non-finite K or E or
+   an E whose rotation part is not orthonormal to 1e-6.  Deterministic: the same input gives the same bytes.
+   tests/smooth_rig_ref.py states the computation. */
+int asl_smooth_rig_sequences_device(asl_detector *det, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map,
+                                    int n_ids, const void *d_rig, double tag_size, const void *d_seed, const double *d_frame_times,
+                                    const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
+                                    double rig_huber_px, int max_iters, void *d_out, void *d_results, void *d_cov, void *stream);
+/* The same computation on host records, synchronous; frame_times, seed and cov may be NULL.  seed == NULL: the rig
+   localisation of all frames (asl_localize_rig_batch, max_tag_rms_px 0) runs first, as asl_smooth_batch does for one camera. */
+int asl_smooth_rig_sequences_batch(asl_detector *det, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_map_tag *map,
+                                   int n_ids, const asl_rig_camera *rig, double tag_size, const asl_cam_pose *seed,
+                                   const double *frame_times, const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot,
+                                   double sigma_trans, double rig_huber_px, int max_iters, asl_cam_pose *out, asl_smooth_result *results,
+                                   asl_pose_cov *cov);
+
 /* ---- before the detector: the image-formation step on the device (reference src/simulation/renderer.py:197-274:
    purple clear colour, one GL_LINEAR-textured quad per tag, BGR read-back).  One plane per visible tag and frame, in
    painter's order (far to near); a plane with tex < 0 ends a frame's list. */

@@ -1,0 +1,137 @@
+"""The NumPy statement of the rig sequence localisation (tests/smooth_rig_ref.py) and the ABI of asl_smooth_rig_sequences_*: the
+statement reduces to smooth_ref.smooth for one camera at E = I, the figures and DEVICE_TOL recorded in smooth_rig_cases.py
+still hold, include/aprilslam.h declares the two entry points with the argument names of the issue, the library exports
+them, the ctypes argument lists agree, the Python surface has its keywords, and the host entry point refuses a NULL detector
+before it touches a device.  No GPU."""
+import ctypes as C
+import inspect
+
+import numpy as np
+import pytest
+
+import smooth_cases as SC
+import smooth_ref as SR
+import smooth_rig_cases as GC
+import smooth_rig_ref as SRR
+from aprilslam_amd import _lib
+from aprilslam_amd.rig import Rig, RigCamera
+from aprilslam_amd.smooth import SmoothResult
+from test_smooth_cov_abi import prototype
+
+DEVICE = ["det", "d_obs", "n_cams", "n_frames", "max_tags", "d_map", "n_ids", "d_rig", "tag_size", "d_seed", "d_frame_times", "seq_start", "n_seq",
+          "sigma_px", "sigma_rot", "sigma_trans", "rig_huber_px", "max_iters", "d_out", "d_results", "d_cov", "stream"]
+BATCH = ["det", "obs", "n_cams", "n_frames", "max_tags", "map", "n_ids", "rig", "tag_size", "seed", "frame_times", "seq_start", "n_seq",
+         "sigma_px", "sigma_rot", "sigma_trans", "rig_huber_px", "max_iters", "out", "results", "cov"]
+
+
+@pytest.mark.parametrize("shape", SC.SHAPES, ids=lambda s: "%d_%d_%d" % s)
+@pytest.mark.parametrize("huber", [0.0, GC.HUBER_PX])
+def test_one_camera_at_identity_is_the_single_camera_statement(shape, huber):
+    obs, rec, seed, dist = SC.shape(*shape)
+    solo = Rig([RigCamera(SC.K, dist, np.eye(4))])
+    want = SR.smooth(obs, rec, SC.K, dist, SC.TAG, seed, *SC.SHAPE_SIGMAS, SC.COMPARE_ITERS, huber_px=huber)
+    got = SRR.smooth(obs[None], rec, solo, SC.TAG, seed, *SC.SHAPE_SIGMAS, SC.COMPARE_ITERS, huber_px=huber)
+    for name in want[0].dtype.names:
+        assert np.array_equal(got[0][name], want[0][name]), name
+    for name in want[1].dtype.names:
+        assert np.array_equal(got[1][name], want[1][name]), name
+    assert int(want[1]["status"]) == SR.OK and int(want[1]["iterations"]) == SC.COMPARE_ITERS
+
+
+def test_recorded_figures_still_hold():
+    fig, rec = GC.figures(lambda name, huber: GC.statement(name, huber)[0]), GC.recorded()
+    print(fig)
+    assert sorted(fig) == sorted(rec)
+    for k, v in fig.items():
+        assert v <= rec[k] and v > rec[k] * (1 - 2e-3), (k, v, rec[k])       # rounded up to 4 digits: within 1e-3 below
+    # what the figures mean
+    assert fig["noise_rmse_smooth"] < 0.25 * fig["noise_rmse_frame"]
+    assert fig["outlier_rmse_huber"] < 2 * fig["noise_rmse_smooth"] < fig["outlier_rmse_plain"]
+    assert fig["holes_mid_err"] < 1e-4 < fig["holes_end_err"]
+    poses, res, trace = GC.statement("holes")
+    assert poses["status"].tolist() == [6, 0, 0, 6, 0, 0, 6] and int(res["n_filled"]) == 3 and int(res["status"]) == SR.OK
+    assert poses["n_tags"][1:5].tolist() == [4, 4, 0, 4] and poses["n_tags"][5] == 8                  # camera 1 back in frame 5
+    poses, res, _ = GC.statement("flip")
+    frames = GC.flip()[5]
+    assert int(res["n_flipped"]) == len(frames) and all(poses["seed_slot"][f] == 1 + SR.FLIPPED for f in frames)   # global slot 1: camera 1
+    mirrored_off = max(GC.LC.rot_err(GC.flip()[3]["T"][f], GC.flip()[4][f]) for f in frames)
+    assert mirrored_off > 100 * GC.flip_errors(poses["T"])[0]
+    poses, res, _ = GC.statement("no_posed")
+    assert int(res["status"]) == SR.NO_POSED_FRAME and (poses["status"] == SR.FRAME_NOTHING).all()
+    poses, res, _ = GC.statement("outliers", GC.HUBER_PX)
+    assert poses["n_rejected"][GC.OUTLIER_SLIP[1]] >= 1 and poses["n_rejected"][GC.OUTLIER_SWAP[1]] >= 1 and int(res["n_soft"]) >= 2
+    assert int(GC.statement("outliers")[1]["n_soft"]) == 0
+
+
+def test_device_tol_is_the_measured_one():
+    worst = max((GC.reversal_error(c[0], h), c[0], h) for c in GC.all_cases() for h in (0.0, GC.HUBER_PX))
+    print(worst)
+    assert worst[0] <= GC.DEVICE_TOL_MEASURED and worst[0] > 0.5 * GC.DEVICE_TOL_MEASURED, worst
+    assert GC.DEVICE_TOL == max(10 * GC.DEVICE_TOL_MEASURED, 1e-9)
+
+
+def test_cases_are_what_the_issue_says():
+    assert [s[:2] for s in GC.SHAPES] == [(2, 1), (2, 3), (3, 5), (16, 16)] and sorted(s[2] for s in GC.SHAPES) == [1, 2, 64, 65]
+    assert GC.from_rig_cases("slots_256")[0].shape[::2] == (8, 32)
+    rig = GC.from_rig_cases("mixed_models")[2].as_records()
+    assert rig["n_dist"].tolist() == [0, 5] and rig["K"][0][0, 0] != rig["K"][1][0, 0]
+    obs = GC.flip()[0]
+    assert not (obs["flags"][0] & 1).any() and (obs["flags"][1] & 1).all()
+    E1 = GC.PAIR.cameras[1].T_cam_rig
+    assert np.abs(E1[:3, :3] - np.eye(3)).max() > 0.05 and np.abs(E1[:3, 3]).max() > 1.0        # turned and offset
+    assert np.diff(GC.SEQ_START).tolist() == [1, 2, 65]
+    t = GC.gap()[4]
+    assert np.diff(t).tolist() == [1, 1, 1, 6, 1, 1, 1, 1]
+    assert GC.COMPARE_ITERS == SC.COMPARE_ITERS
+
+
+def test_header_prototypes():
+    dev, host = prototype("asl_smooth_rig_sequences_device"), prototype("asl_smooth_rig_sequences_batch")
+    assert dev == DEVICE and len(dev) == 22
+    assert host == BATCH and len(host) == 21
+
+
+def test_exports_and_argtypes():
+    L = _lib.load()
+    for name in ("asl_smooth_rig_sequences_device", "asl_smooth_rig_sequences_batch"):
+        assert name in _lib.EXPORTS and hasattr(L, name)
+    vp, i32, dbl = C.c_void_p, C.c_int, C.c_double
+    head = [vp, vp, i32, i32, i32, vp, i32, vp, dbl, vp]
+    tail = [C.POINTER(C.c_int32), i32, dbl, dbl, dbl, dbl, i32, vp, vp, vp]
+    assert L.asl_smooth_rig_sequences_device.argtypes == head + [vp] + tail + [vp] and len(L.asl_smooth_rig_sequences_device.argtypes) == len(DEVICE)
+    assert L.asl_smooth_rig_sequences_batch.argtypes == head + [C.POINTER(dbl)] + tail and len(L.asl_smooth_rig_sequences_batch.argtypes) == len(BATCH)
+
+
+def test_python_surface_has_its_keywords():
+    want = {"sigma_px": 1.0, "sigma_rot": 0.05, "sigma_trans": 0.5, "max_iters": 20, "seed": None, "seq_start": None, "times": None,
+            "huber_px": 0.0, "with_cov": False}
+    p = inspect.signature(_lib.Detector.smooth_rig).parameters
+    assert list(p)[:5] == ["self", "obs", "tag_map", "rig", "tag_size"] and list(p)[5:] == list(want)
+    assert {k: p[k].default for k in want} == want
+    p = inspect.signature(_lib.Detector.smooth_rig_device).parameters
+    assert p["times_ptr"].default is None and p["cov_ptr"].default is None and p["huber_px"].default == 0.0 and p["seq_start"].default is None
+    for fn, lead in ((Rig.localize_sequence, ["self", "det", "obs", "tag_map", "tag_size"]),
+                     (Rig.localize_sequences, ["self", "det", "obs", "seq_start", "tag_map", "tag_size"])):
+        p = inspect.signature(fn).parameters
+        assert list(p)[:len(lead)] == lead
+        assert {k: p[k].default for k in want if k != "seq_start"} == {k: v for k, v in want.items() if k != "seq_start"}
+    assert "SmoothResult" in Rig.localize_sequence.__doc__ and SmoothResult.__init__ is not None
+
+
+def test_null_detector_is_refused():
+    L = _lib.load()
+    obs, rec, rig, seed = GC.shape(2, 3, 2)
+    n_cams, n, mt = obs.shape
+    obs, seed, tab = np.ascontiguousarray(obs), np.ascontiguousarray(seed), rig.as_records()
+    out = np.full(n * _lib.CAM_POSE_DTYPE.itemsize, 0xAB, dtype=np.uint8)
+    res = np.full(64, 0xAB, dtype=np.uint8)
+    cov = np.full(n * _lib.POSE_COV_DTYPE.itemsize, 0xAB, dtype=np.uint8)
+    start = np.array([0, n], dtype=np.int32)
+    sp = start.ctypes.data_as(C.POINTER(C.c_int32))
+    rc = L.asl_smooth_rig_sequences_batch(None, obs.ctypes.data, n_cams, n, mt, rec.ctypes.data, len(rec), tab.ctypes.data, GC.TAG, seed.ctypes.data,
+                                          None, sp, 1, *GC.SHAPE_SIGMAS, 0.0, GC.COMPARE_ITERS, out.ctypes.data, res.ctypes.data, cov.ctypes.data)
+    assert rc == -1 and b"detector" in L.asl_last_error()
+    assert (out == 0xAB).all() and (res == 0xAB).all() and (cov == 0xAB).all()
+    rc = L.asl_smooth_rig_sequences_device(None, 256, n_cams, n, mt, 256, len(rec), 256, GC.TAG, 256, None, sp, 1, *GC.SHAPE_SIGMAS, 0.0,
+                                           GC.COMPARE_ITERS, 256, 256, None, None)
+    assert rc == -1 and b"detector" in L.asl_last_error()

@@ -23,11 +23,16 @@ alternating: the timed call on the kept frames (their times as above), the naive
 gap taken for one frame step) and the plain call on all frames with the block emptied; under "gap" the time and trials of each,
 the position RMSE of each against the truth over the four frames next to the gap and over all kept frames, and the largest
 relative difference of a kept frame's T between the timed and the emptied solve (the same minimum without --jitter; with it the
-emptied solve, which has no times, is another problem).
+emptied solve, which has no times, is another problem).  --rig C runs the rig solve instead (asl_smooth_rig_sequences_device): C cameras
+side by side on one rig (mountings fanned over 6 degrees of yaw and 2 units), the rig moved along the bench trajectory, every
+camera's records from exact projections of the bench scene plus --rig-noise px of corner noise (no rendering: the rig solve
+starts from asl_obs blocks); under "rig" the kernel time of the rig localisation and of the rig solve, alternating, and the
+rig-smoothed against the per-frame rig position error.
 
     python tools/smooth_lab.py [--frames 1024] [--reps 20] [--max-tags 32] [--sigma-px 0.3] [--sigma-rot 0.01]
                                [--sigma-trans 0.05] [--max-iters 20] [--drop-every 0] [--cov] [--sequences S [--loop-only]]
                                [--huber K] [--outliers N [--outlier-seed 1]] [--jitter J [--jitter-seed 1]] [--gap LO:HI]
+    python tools/smooth_lab.py --rig C [--frames 1024] [--max-tags 2] [--rig-noise 0.3] [--huber K] [--cov] [the sigmas, --max-iters, --reps]
 """
 import argparse
 import json
@@ -43,6 +48,87 @@ sys.path.insert(0, ROOT)
 def rot_err(Ta, Tb):
     R = Ta[:3, :3] @ Tb[:3, :3].T
     return float(np.arccos(np.clip((np.trace(R) - 1) / 2, -1, 1)))
+
+
+def rig_leg(a):
+    """--rig C: one JSON line of the rig solve on a synthetic block"""
+    import torch
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import localize_cases as LC
+    import rig_cases as RC
+    from aprilslam_amd import _lib
+    from aprilslam_amd.localize import CAM_POSE_DTYPE, POSE_COV_DTYPE, TagMap
+    from aprilslam_amd.rig import Rig, RigCamera
+
+    dev = torch.device("cuda:0")
+    n, mt, nc = a.frames, a.max_tags, a.rig
+    step = 1.0 / max(1, nc - 1)
+    rig = Rig([RigCamera(RC.K45, None, RC.mounting(-3.0 + 6.0 * step * c, (-1.0 + 2.0 * step * c, 0.0, 0.0))) for c in range(nc)])
+    tm = TagMap.from_scene(LC.bench_scene())
+    rec = tm.as_records()
+    truths = [LC.world_from_camera(p, r) for p, r in LC.trajectory(n)]
+    obs = RC.exact_block(tm, rig, truths, LC.TAG_INNER, mt)
+    rng = np.random.default_rng(1)
+    obs["corners"] = (obs["corners"].astype(np.float64) + rng.normal(0.0, a.rig_noise, obs["corners"].shape)).astype(np.float32)
+    det = _lib.Detector("tagStandard41h12", id_limit=0)
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1)).to(dev)  # noqa: E731
+    d_obs, d_map, d_rig = up(obs), up(rec), up(rig.as_records())
+    d_seed, d_out = (torch.zeros(n * CAM_POSE_DTYPE.itemsize, dtype=torch.uint8, device=dev) for _ in range(2))
+    d_res = torch.zeros(_lib.SMOOTH_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    d_cov = torch.zeros(n * POSE_COV_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.Stream(dev)
+    torch.cuda.synchronize()
+
+    def localize_rig():
+        det.localize_rig_device(d_obs.data_ptr(), nc, n, mt, d_map.data_ptr(), len(rec), d_rig.data_ptr(), d_seed.data_ptr(), LC.TAG_INNER,
+                                stream=stream.cuda_stream)
+
+    def smooth_rig():
+        det.smooth_rig_device(d_obs.data_ptr(), nc, n, mt, d_map.data_ptr(), len(rec), d_rig.data_ptr(), d_seed.data_ptr(), d_out.data_ptr(),
+                              d_res.data_ptr(), LC.TAG_INNER, sigma_px=a.sigma_px, sigma_rot=a.sigma_rot, sigma_trans=a.sigma_trans,
+                              max_iters=a.max_iters, stream=stream.cuda_stream, huber_px=a.huber, cov_ptr=d_cov.data_ptr() if a.cov else None)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    legs = [localize_rig, smooth_rig]
+    with torch.cuda.stream(stream):
+        for _ in range(a.warmup):
+            for fn in legs:
+                fn()
+        times = [[] for _ in legs]
+        for _ in range(a.reps):
+            for k, fn in enumerate(legs):
+                times[k].append(timed(fn))
+    stream.synchronize()
+    seed = d_seed.cpu().numpy().view(CAM_POSE_DTYPE)
+    out = d_out.cpu().numpy().view(CAM_POSE_DTYPE)
+    res = d_res.cpu().numpy().view(_lib.SMOOTH_RESULT_DTYPE)[0]
+    tr = np.array(truths)
+
+    def rmse(poses, keep):
+        return float(np.sqrt(np.mean(np.sum((poses["T"][keep][:, :3, 3] - tr[keep][:, :3, 3]) ** 2, axis=1)))) if keep.any() else None
+
+    posed = seed["status"] == 0
+    solved = np.isin(out["status"], (0, 6))
+    print(json.dumps({
+        "metric": "asl_smooth_rig_sequences_device", "cameras": nc, "frames": n, "max_tags": mt, "corner_noise_px": a.rig_noise,
+        "sigma_px": a.sigma_px, "sigma_rot": a.sigma_rot, "sigma_trans": a.sigma_trans, "max_iters": a.max_iters, "huber_px": a.huber,
+        "with_cov": bool(a.cov), "reps": a.reps, "slots_per_frame_mean": float(out["n_tags"].mean()),
+        "smooth_rig_ms_median": float(np.median(times[1])), "smooth_rig_ms_min": float(np.min(times[1])),
+        "localize_rig_ms_median": float(np.median(times[0])), "localize_rig_ms_min": float(np.min(times[0])),
+        "ms_per_trial": float(np.median(times[1])) / max(1, int(res["iterations"])),
+        "result": {k: (float(res[k]) if res[k].dtype.kind == "f" else int(res[k])) for k in res.dtype.names if k != "reserved"},
+        "per_frame_position_rmse_units": rmse(seed, posed), "smoothed_position_rmse_units_same_frames": rmse(out, posed & solved),
+        "smoothed_position_rmse_units_all_frames": rmse(out, solved), "frames_without_seed": int((~posed).sum()),
+        "note": "world<-rig against the poses the block was projected from; per-frame = asl_localize_rig_frames_device (the seed)"}))
+    det.close()
 
 
 def main():
@@ -65,7 +151,13 @@ def main():
     ap.add_argument("--jitter", type=float, default=None, help="irregular frame times f + J u, u uniform in (-0.5, 0.5): also run the timed call")
     ap.add_argument("--jitter-seed", type=int, default=1)
     ap.add_argument("--gap", default="", help="LO:HI: drop the frames [LO, HI); timed on the kept frames against naive and against the block emptied")
+    ap.add_argument("--rig", type=int, default=0, help="C: the rig solve of C cameras on a synthetic block instead (see the module docstring)")
+    ap.add_argument("--rig-noise", type=float, default=0.3, help="with --rig: corner noise in pixels")
     a = ap.parse_args()
+    if a.rig:
+        if not 1 <= a.rig <= 16 or a.rig * a.max_tags > 256:
+            ap.error("--rig C needs 1 <= C <= 16 and C * max-tags <= 256")
+        return rig_leg(a)
     if a.sequences and (a.sequences < 1 or a.frames % a.sequences):
         ap.error("--sequences must divide --frames")
     if a.jitter is not None and not 0 <= a.jitter < 1:
