@@ -24,6 +24,7 @@
 #include "k_cluster.inc"
 #include "k_seg.inc"
 #include "k_quad.inc"
+#include "k_refine.inc"
 #include "k_decode.inc"
 #include "k_pnp.inc"
 #include "k_dedup.inc"

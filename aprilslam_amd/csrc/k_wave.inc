@@ -1,4 +1,5 @@
-// Cross-lane primitives of the kernels: DPP moves, lane exchanges, readlane, the wave scan and reduction, butterfly sums.
+// Cross-lane primitives of the kernels: DPP moves, lane exchanges, readlane, the wave scan and reduction, the maximum,
+// minimum and owner of a group of 8 lanes, butterfly sums.
 // They need neither LDS nor an address register: ds_bpermute does the same in ~100 cycles of latency per exchange, and a
 // sorting network or a reduction is a chain of such exchanges.
 // lane_xor<J>: value of lane (l ^ J) for a compile-time J, 32- or 64-bit.
@@ -17,6 +18,7 @@
 #define QUAD_ROT1 0x39 /* quad_perm [1,2,3,0]: value of lane l + 1 */
 #define QUAD_ROT2 0x4E /* quad_perm [2,3,0,1]: value of lane l + 2 */
 #define QUAD_ROT3 0x93 /* quad_perm [3,0,1,2]: value of lane l + 3 */
+#define ROW_HALF_MIRROR 0x141 /* row_half_mirror: lane i of each 8 takes the value of lane 7 - i, in the group's other quad */
 
 // One DPP move of a 32- or 64-bit value (a 64-bit value moves as two dwords): lanes whose source lies outside the row, or
 // whose row or bank is masked, receive `old`.
@@ -94,6 +96,27 @@ __device__ __forceinline__ T wave_scan(T v, T ident, Op op)
     v = op(v, dpp_mov<0x143, 0xc>(ident, v));  // row_bcast:31 into rows 2 and 3 -> lane 63 holds the whole wave's result
     if constexpr (REDUCE) return readlane(v, 63);
     else return v;
+}
+
+// Groups of 8 lanes (k_homography: one quad per group).  Maximum resp. minimum over the group, in all 8 lanes: the other
+// lanes of the quad through xor 1 and xor 2, the other quad through the half-row mirror.
+__device__ __forceinline__ double grp8_max(double v)
+{
+    v = fmax(v, dpp_mov<QUAD_XOR1>(0.0, v));
+    v = fmax(v, dpp_mov<QUAD_XOR2>(0.0, v));
+    return fmax(v, dpp_mov<ROW_HALF_MIRROR>(0.0, v));
+}
+__device__ __forceinline__ int grp8_min(int v)
+{
+    v = min(v, dpp_mov<QUAD_XOR1>(0, v));
+    v = min(v, dpp_mov<QUAD_XOR2>(0, v));
+    return min(v, dpp_mov<ROW_HALF_MIRROR>(0, v));
+}
+// the lane of the group for which `mine` holds (exactly one per group), in all 8 lanes
+__device__ __forceinline__ int grp8_owner(bool mine, int lane)
+{
+    const unsigned long long m = __ballot(mine);
+    return (lane & ~7) + (__ffs((int)((m >> (lane & ~7)) & 0xFFull)) - 1);
 }
 
 // sum of a double or an int over each aligned group of LANES lanes, in every lane of the group: the exchanges with

@@ -145,6 +145,19 @@ def quad_maxima(dec, pts, fam, decimate_f):
     return out[:n]
 
 
+def refine_edges(gray, p, reversed_border, decimate_f):
+    """S6 alone (aso_refine_edges) on one quad: p (4, 2) corners in full-resolution pixels (a fit_quads corner c at
+    decimate f is (c - 0.5) f + 0.5); returns the refined corners."""
+    gray = np.ascontiguousarray(gray, dtype=np.uint8)
+    h, w = gray.shape
+    q = AsoQuad()
+    for i in range(4):
+        q.p[i][0], q.p[i][1] = float(p[i][0]), float(p[i][1])
+    q.reversed_border = int(reversed_border)
+    lib().aso_refine_edges(_u8(gray), w, h, w, decimate_f, C.byref(q))
+    return np.array([[q.p[i][0], q.p[i][1]] for i in range(4)])
+
+
 def _dets(arr, n):
     return [dict(id=d.id, hamming=d.hamming, margin=d.margin, center=np.array(list(d.center)),
                  corners=np.array([[d.corners[i][0], d.corners[i][1]] for i in range(4)])) for d in arr[:n]]
