@@ -55,8 +55,23 @@ EXPORTS = [
     "asl_smooth_sequences_device", "asl_smooth_sequences_batch", "asl_smooth_robust_sequences_device", "asl_smooth_robust_sequences_batch",
     "asl_smooth_timed_sequences_device", "asl_smooth_timed_sequences_batch",
     "asl_smooth_rig_sequences_device", "asl_smooth_rig_sequences_batch",
-    "asl_debug_fetch", "asl_debug_refit", "asl_debug_dedup", "asl_debug_division_check", "asl_stage_times", "asl_set_profiling", "asl_debug_phase_cycles",
+    "asl_debug_fetch", "asl_debug_refit", "asl_debug_dedup", "asl_debug_gn_cholesky", "asl_debug_gn_step", "asl_debug_division_check", "asl_stage_times", "asl_set_profiling", "asl_debug_phase_cycles",
 ]
+
+
+
+class DebugSpan(C.Structure):    # asl_debug_span: room for n doubles at p; p NULL: not wanted
+    _fields_ = [("p", C.POINTER(C.c_double)), ("n", C.c_size_t)]
+
+
+# asl_debug_gn_step's items in the header's order (ASL_GN_STEP_*), with the shape of each for (P cameras, L tags, M observations)
+GN_STEP_ITEMS = ("D", "cost_obs", "cost", "Hinv", "gc", "Tfj", "S", "rhs", "dG", "Wn", "Gn")
+
+
+def gn_step_shapes(P, L, M):
+    return dict(D=(M, 12, 13), cost_obs=(M,), cost=(1,), Hinv=(P, 6, 6), gc=(P, 6), Tfj=(M, 6, 6), S=(6 * L, 6 * L), rhs=(6 * L,),
+                dG=(L, 6), Wn=(P, 12), Gn=(L, 12))
+
 
 _lib = None
 
@@ -149,6 +164,9 @@ def load():
     L.asl_debug_fetch.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.asl_debug_refit.argtypes = [vp, i32, vp, C.c_size_t]
     L.asl_debug_dedup.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, C.c_size_t]
+    L.asl_debug_gn_cholesky.argtypes = [vp, dp, dp, i32, dp, C.c_size_t, dp, dp, dp, C.c_size_t, dp, C.c_size_t, C.POINTER(C.c_int32)]
+    L.asl_debug_gn_step.argtypes = [vp, i32, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, dp, C.c_double, i32, dp, dp,
+                                    C.c_double, C.POINTER(DebugSpan), i32, C.POINTER(C.c_int32)]
     L.asl_debug_division_check.argtypes = [vp, i32, vp, C.c_size_t]
     L.asl_stage_times.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32, C.POINTER(i32)]
     L.asl_set_profiling.argtypes = [vp, i32]
@@ -821,6 +839,45 @@ class Detector:
         check(self._L.asl_debug_dedup(self._h, d.ctypes.data, k.ctypes.data, len(d), int(n_frames), int(cap_per_frame), out.ctypes.data,
                                       len(out), npf.ctypes.data, cnt.ctypes.data, len(cnt)))
         return out[:int(cnt[0])], npf, cnt
+
+    def debug_gn_cholesky(self, A, b):
+        """asl_debug_gn_cholesky: the back-end's blocked Cholesky, back substitution and diag(A^-1) on a dense symmetric A
+        (n x n, n = 6 x tags) and right-hand side b -> dict(L, y, x, Linv (blocks, 48, 48), var, fail)."""
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        n = A.shape[0]
+        if A.shape != (n, n) or b.shape != (n,):
+            raise ValueError("A must be square and b of its size")
+        nblk = (n + 47) // 48
+        L, y, x, var, Linv = np.zeros((n, n)), np.zeros(n), np.zeros(n), np.zeros(n), np.zeros((max(nblk, 1), 48, 48))
+        flag = C.c_int32(-1)
+        ptr = lambda a: a.ctypes.data_as(_DP)
+        check(self._L.asl_debug_gn_cholesky(self._h, ptr(A), ptr(b), n, ptr(L), L.size, ptr(y), ptr(x), ptr(var), n, ptr(Linv), Linv.size,
+                                            C.byref(flag)))
+        return dict(L=L, y=y, x=x, Linv=Linv, var=var, fail=int(flag.value))
+
+    def debug_gn_step(self, cam_T, tag_T, obs_cam, obs_tag, obs_corners, K, tag_size, fixed_tag, lam, want=GN_STEP_ITEMS):
+        """asl_debug_gn_step: one damped step of gn_solve's problem at damping lam, stage by stage -> dict of the items in
+        `want` (GN_STEP_ITEMS; shapes: gn_step_shapes) and `fail`.  The poses are not changed."""
+        cam = np.ascontiguousarray(cam_T, dtype=np.float64).reshape(-1, 16)
+        tag = np.ascontiguousarray(tag_T, dtype=np.float64).reshape(-1, 16)
+        oc = np.ascontiguousarray(obs_cam, dtype=np.int32)
+        ot = np.ascontiguousarray(obs_tag, dtype=np.int32)
+        corners = np.ascontiguousarray(obs_corners, dtype=np.float64).reshape(-1, 8)
+        Kc = np.ascontiguousarray(K, dtype=np.float64)
+        shapes = gn_step_shapes(cam.shape[0], tag.shape[0], len(oc))
+        res = {k: np.zeros(shapes[k]) for k in want}
+        spans = (DebugSpan * len(GN_STEP_ITEMS))()
+        for i, k in enumerate(GN_STEP_ITEMS):
+            if k in res:
+                spans[i].p, spans[i].n = res[k].ctypes.data_as(_DP), res[k].size
+        flag = C.c_int32(-1)
+        ip = C.POINTER(C.c_int32)
+        check(self._L.asl_debug_gn_step(self._h, cam.shape[0], tag.shape[0], len(oc), oc.ctypes.data_as(ip), ot.ctypes.data_as(ip),
+                                        corners.ctypes.data_as(_DP), Kc.ctypes.data_as(_DP), float(tag_size), int(fixed_tag),
+                                        cam.ctypes.data_as(_DP), tag.ctypes.data_as(_DP), float(lam), spans, len(spans), C.byref(flag)))
+        res["fail"] = int(flag.value)
+        return res
 
     def debug_division_check(self, exponent_limit=100):
         """(pairs, mismatches) of div_by(a, recip_of(d)) against a / d on the device, exponents within +-exponent_limit."""

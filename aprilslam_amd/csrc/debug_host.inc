@@ -1,6 +1,6 @@
 // Host side of the diagnostics (device side: k_seg_debug_* in k_seg.inc, k_div_check below): asl_debug_fetch, the quad-fit
-// refit, the de-duplication of given records, the division check and the phase counters; each checks the room it may write
-// into before it writes anything.
+// refit, the de-duplication of given records, the pose-graph back-end's factorisation and single step, the division check
+// and the phase counters; each checks the room it may write into before it writes anything.
 
 // asl_debug_division_check: div_by(a, recip_of(d)) (asl_common.h) against a / d, as compiled into this library: log-uniform
 // magnitudes with exponents within +-lim, both signs, a = 0 now and then
@@ -227,6 +227,96 @@ extern "C" int asl_debug_dedup(asl_detector *d, const asl_detection *dets, const
     if (nkeep) HIPCHK(hipMemcpy(out, d_out.p, (size_t)nkeep * sizeof(DetOut), hipMemcpyDeviceToHost));
     for (size_t f = 0; f < B; f++) n_per_frame[f] = (int)h_nkeep[f];
     counters[0] = nkeep; counters[1] = h_cnt[CNT_OVERFLOW_DETS]; counters[2] = h_cnt[CNT_DEDUP_LIMIT];
+    return ASL_OK;
+}
+
+// The pose-graph back-end's dense linear algebra alone on the caller's matrix: gn_factor, the back substitution and k_map_std
+// as asl_gn_solve and the map solver enqueue them (gn_host.inc, launch_map), in device buffers of this call's own.
+extern "C" int asl_debug_gn_cholesky(asl_detector *d, const double *A, const double *b, int n, double *L, size_t n_L, double *y, double *x,
+                                     double *var, size_t n_vec, double *Linv, size_t n_Linv, int32_t *fail_flag)
+{
+    if (!d || !A || !b || !L || !y || !x || !var || !Linv || !fail_flag) return fail(ASL_EINVAL, "NULL argument");
+    if (n < 6 || n > 6000 || n % 6) return fail(ASL_EINVAL, "n must be 6 times a tag count in [1, 1000] (got %d)", n);
+    const size_t N = (size_t)n, nblk = (N + GN_NB - 1) / GN_NB, nli = nblk * GN_NB * GN_NB;
+    if (n_L < N * N) return fail(ASL_EINVAL, "L too small: need %zu values (got %zu)", N * N, n_L);
+    if (n_vec < N) return fail(ASL_EINVAL, "y, x and var too small: need %zu values each (got %zu)", N, n_vec);
+    if (n_Linv < nli) return fail(ASL_EINVAL, "Linv too small: need %zu values (got %zu)", nli, n_Linv);
+    if (d->pending) return fail(ASL_EINVAL, "a batch is in flight on this detector");
+    HIPCHK(hipSetDevice(d->device));
+    DevBuf<double> d_S, d_x, d_Linv, d_var;
+    DevBuf<int> d_flag;
+    if (d_S.ensure((N + 1) * N) || d_x.ensure(N) || d_Linv.ensure(nli) || d_var.ensure(N) || d_flag.ensure(1))
+        return fail(ASL_ENOMEM, "debug buffer allocation failed (n = %d)", n);
+    HIPCHK(hipMemcpy(d_S.p, A, N * N * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_S.p + N * N, b, N * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_flag.p, 0, sizeof(int)));
+    gn_factor(d_S.p, d_Linv.p, n, d_flag.p, nullptr);
+    gn_trisolve(d_S.p, d_Linv.p, d_x.p, n, nullptr);
+    hipLaunchKernelGGL(k_map_std, dim3(n), dim3(256), N * sizeof(double), nullptr, d_S.p, d_Linv.p, n, d_var.p);
+    HIPCHK(hipGetLastError());
+    int flag = 0;
+    HIPCHK(hipMemcpy(&flag, d_flag.p, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(L, d_S.p, N * N * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < N; r++)
+        for (size_t c = r + 1; c < N; c++) L[r * N + c] = 0.0;  // the factorisation leaves A's upper triangle there
+    HIPCHK(hipMemcpy(y, d_S.p + N * N, N * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(x, d_x.p, N * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(var, d_var.p, N * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(Linv, d_Linv.p, nli * sizeof(double), hipMemcpyDeviceToHost));
+    *fail_flag = flag;
+    return ASL_OK;
+}
+
+// One damped step of asl_gn_solve's problem, stage by stage: the linearisation and its cost, gn_eliminate, gn_factor and
+// gn_step as gn_factor_step runs them, S and rhs read back between the first two.  A workspace of this call's own.
+extern "C" int asl_debug_gn_step(asl_detector *d, int n_cams, int n_tags, int n_obs, const int32_t *obs_cam, const int32_t *obs_tag,
+                                 const double *obs_corners, const double *K, double tag_size, int fixed_tag, const double *cam_T,
+                                 const double *tag_T, double lambda, const asl_debug_span *out, int n_out, int32_t *fail_flag)
+{
+    GnHostProblem h;
+    if (int rc = gn_host_problem(d, n_cams, n_tags, n_obs, obs_cam, obs_tag, obs_corners, K, fixed_tag, cam_T, tag_T, h)) return rc;
+    if (!out) return fail(ASL_EINVAL, "NULL argument");
+    if (!(lambda >= 0) || !std::isfinite(lambda)) return fail(ASL_EINVAL, "lambda must be >= 0 and finite (got %g)", lambda);
+    if (n_out != ASL_GN_STEP__N) return fail(ASL_EINVAL, "out must have %d entries (got %d)", ASL_GN_STEP__N, n_out);
+    const size_t nc = (size_t)n_cams, nt = (size_t)n_tags, nm = (size_t)n_obs, n = 6 * nt;
+    const size_t need[ASL_GN_STEP__N] = {GN_DSTRIDE * nm, nm, 1, 36 * nc, 6 * nc, 36 * nm, n * n, n, n, 12 * nc, 12 * nt};
+    for (int i = 0; i < ASL_GN_STEP__N; i++)
+        if (out[i].p && out[i].n < need[i]) return fail(ASL_EINVAL, "out[%d] too small: need %zu values (got %zu)", i, need[i], out[i].n);
+    if (d->pending) return fail(ASL_EINVAL, "a batch is in flight on this detector");
+    HIPCHK(hipSetDevice(d->device));
+    DevBuf<uint8_t> ws;
+    GnDevProblem p;
+    if (int rc = gn_stage_problem(ws, h, n_cams, n_tags, n_obs, obs_cam, obs_tag, obs_corners, fixed_tag, nullptr, p)) return rc;
+    const GnSystem &sys = p.sys;
+    double lm_init[GN_LM__N] = {0, 0, lambda, 0, 0, 0, 0, 0};
+    HIPCHK(hipMemcpy(p.b.lm, lm_init, sizeof lm_init, hipMemcpyHostToDevice));
+    const CamDev cam = make_cam(d, K, nullptr, 0, tag_size);
+    gn_launch_linearize(p, cam, n_obs, p.Wc, p.Gc, sys.D, nullptr);
+    hipLaunchKernelGGL(k_gn_cost, dim3(1), dim3(256), 0, nullptr, p.b.cost_obs, n_obs, p.b.lm + GN_LM_COST);
+    if (int rc = gn_eliminate(sys, p.b.lm, nullptr)) return rc;
+    HIPCHK(hipGetLastError());
+    auto fetch = [&](int item, const double *src) {
+        return out[item].p ? hipMemcpy(out[item].p, src, need[item] * sizeof(double), hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    HIPCHK(fetch(ASL_GN_STEP_S, sys.S));
+    HIPCHK(fetch(ASL_GN_STEP_RHS, sys.rhs));
+    gn_factor(sys.S, sys.Linv, (int)n, p.b.flag, nullptr);
+    gn_step(sys, nullptr, p.Wc, p.Gc, p.b.Wn, p.b.Gn);
+    HIPCHK(hipGetLastError());
+    HIPCHK(fetch(ASL_GN_STEP_D, sys.D));
+    HIPCHK(fetch(ASL_GN_STEP_COST_OBS, p.b.cost_obs));
+    HIPCHK(fetch(ASL_GN_STEP_COST, p.b.lm + GN_LM_COST));
+    HIPCHK(fetch(ASL_GN_STEP_HINV, sys.Hinv));
+    HIPCHK(fetch(ASL_GN_STEP_GC, sys.gc));
+    HIPCHK(fetch(ASL_GN_STEP_TFJ, sys.Tfj));
+    HIPCHK(fetch(ASL_GN_STEP_DG, sys.rhs));
+    HIPCHK(fetch(ASL_GN_STEP_WN, p.b.Wn));
+    HIPCHK(fetch(ASL_GN_STEP_GN, p.b.Gn));
+    if (fail_flag) {
+        int flag = 0;
+        HIPCHK(hipMemcpy(&flag, p.b.flag, sizeof(int), hipMemcpyDeviceToHost));
+        *fail_flag = flag;
+    }
     return ASL_OK;
 }
 

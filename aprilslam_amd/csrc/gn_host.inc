@@ -9,30 +9,56 @@ struct GnSystem {
     double *Hinv, *gc, *Tfj, *S, *rhs, *Linv;
 };
 
-// Enqueued on st: the cameras eliminated and the Schur complement over the tags (damping: lm[GN_LM_LAMBDA]), its blocked
-// Cholesky with the right-hand side carried as row n (fail set if it is not positive definite); with Wn, also the step:
-// the triangular solves and the trial poses (Wn, Gn) from (W, G)
-static int gn_factor_step(const GnSystem &g, const double *lm, int *fail_flag, hipStream_t st, const double *W = nullptr,
-                          const double *G = nullptr, double *Wn = nullptr, double *Gn = nullptr)
+// The three pieces of one damped step, each enqueued on st; gn_factor_step calls them in order, and a diagnostic
+// (debug_host.inc) may read S between the first two or hand gn_factor a matrix of its own.
+// Eliminate: the cameras reduced out (damping: lm[GN_LM_LAMBDA]), the Schur complement S over the tags and its right-hand
+// side, which is copied into row n of S
+static int gn_eliminate(const GnSystem &g, const double *lm, hipStream_t st)
 {
     const int n = 6 * g.n_tags;
     hipLaunchKernelGGL(k_gn_reduce_cam, dim3(g.n_cams), dim3(64), 0, st, g.D, g.cam_ptr, g.cam_obs, g.n_cams, lm, g.Hinv, g.gc, g.Tfj);
     hipLaunchKernelGGL(k_gn_schur, dim3(g.n_tags, g.n_tags), dim3(64), 0, st, g.D, g.Tfj, g.Hinv, g.gc, g.tag_ptr, g.tag_obs, g.obs_cam,
                        g.obs_of, g.n_cams, g.n_tags, g.fixed_tag, lm, g.S, g.rhs);
     HIPCHK(hipMemcpyAsync(g.S + (size_t)n * n, g.rhs, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+    return ASL_OK;
+}
+
+// Factor: the blocked Cholesky of S ((n + 1) x n, row n the right-hand side, which leaves as L^-1 b) in place, the inverses
+// of the diagonal blocks into Linv; fail_flag set if S is not positive definite
+static void gn_factor(double *S, double *Linv, int n, int *fail_flag, hipStream_t st)
+{
     for (int k0 = 0; k0 < n; k0 += GN_NB) {
         const int nb = std::min(GN_NB, n - k0), rem = n + 1 - k0 - nb;  // rows below the block, including row n
-        hipLaunchKernelGGL(k_gn_chol_diag, dim3(1), dim3(64), 0, st, g.S, n, k0, nb, fail_flag, g.Linv);
-        hipLaunchKernelGGL(k_gn_chol_panel, dim3((rem + 15) / 16), dim3(256), 0, st, g.S, n, n + 1, k0, nb);
+        hipLaunchKernelGGL(k_gn_chol_diag, dim3(1), dim3(64), 0, st, S, n, k0, nb, fail_flag, Linv);
+        hipLaunchKernelGGL(k_gn_chol_panel, dim3((rem + 15) / 16), dim3(256), 0, st, S, n, n + 1, k0, nb);
         if (rem > 1) {
             const unsigned int tiles = (unsigned int)((rem + GN_NB - 1) / GN_NB);
-            hipLaunchKernelGGL(k_gn_chol_update, dim3(tiles, tiles), dim3(256), 0, st, g.S, n, n + 1, k0, nb);
+            hipLaunchKernelGGL(k_gn_chol_update, dim3(tiles, tiles), dim3(256), 0, st, S, n, n + 1, k0, nb);
         }
     }
-    if (!Wn) return ASL_OK;
-    hipLaunchKernelGGL(k_gn_trisolve, dim3(1), dim3(GN_TRI_THREADS), (size_t)n * sizeof(double), st, g.S, g.Linv, g.rhs, n);
+}
+
+// the back substitution L^T x = (row n of S) into x (n doubles)
+static void gn_trisolve(const double *S, const double *Linv, double *x, int n, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_gn_trisolve, dim3(1), dim3(GN_TRI_THREADS), (size_t)n * sizeof(double), st, S, Linv, x, n);
+}
+
+// Step: the back substitution (the tag steps, into g.rhs), the camera steps and the trial poses (Wn, Gn) from (W, G)
+static void gn_step(const GnSystem &g, hipStream_t st, const double *W, const double *G, double *Wn, double *Gn)
+{
+    gn_trisolve(g.S, g.Linv, g.rhs, 6 * g.n_tags, st);
     hipLaunchKernelGGL(k_gn_update, dim3((g.n_cams + g.n_tags + 63) / 64), dim3(64), 0, st, g.D, g.Hinv, g.gc, g.cam_ptr, g.cam_obs,
                        g.obs_tag, g.rhs, g.n_cams, g.n_tags, W, G, Wn, Gn);
+}
+
+// Enqueued on st: eliminate and factor (fail set if the reduced system is not positive definite); with Wn, also the step
+static int gn_factor_step(const GnSystem &g, const double *lm, int *fail_flag, hipStream_t st, const double *W = nullptr,
+                          const double *G = nullptr, double *Wn = nullptr, double *Gn = nullptr)
+{
+    if (int rc = gn_eliminate(g, lm, st)) return rc;
+    gn_factor(g.S, g.Linv, 6 * g.n_tags, fail_flag, st);
+    if (Wn) gn_step(g, st, W, G, Wn, Gn);
     return ASL_OK;
 }
 
@@ -108,47 +134,91 @@ static void gn_unpack(const double *P12, double *T)
     T[12] = 0; T[13] = 0; T[14] = 0; T[15] = 1;
 }
 
+// A pose-graph problem as the ABI states it, checked and put into the kernels' form on the host: the CSR lists by camera
+// and by tag (observation order kept), the (camera, tag) -> observation table, the poses packed (W camera<-world, G)
+struct GnHostProblem {
+    std::vector<int> cam_ptr, tag_ptr, cam_obs, tag_obs, obs_of;
+    std::vector<double> W, G;
+};
+
+static int gn_host_problem(const asl_detector *d, int n_cams, int n_tags, int n_obs, const int32_t *obs_cam, const int32_t *obs_tag,
+                           const double *obs_corners, const double *K, int fixed_tag, const double *cam_T, const double *tag_T,
+                           GnHostProblem &h)
+{
+    if (!d || !obs_cam || !obs_tag || !obs_corners || !K || !cam_T || !tag_T) return fail(ASL_EINVAL, "NULL argument");
+    if (n_cams <= 0 || n_tags <= 0 || n_obs <= 0) return fail(ASL_EINVAL, "empty problem");
+    if (fixed_tag < 0 || fixed_tag >= n_tags) return fail(ASL_EINVAL, "fixed_tag out of range");
+    if ((long long)n_tags * 6 > 6000) return fail(ASL_EINVAL, "more than 1000 tags: the dense reduced system is not meant for that");
+    h.cam_ptr.assign(n_cams + 1, 0); h.tag_ptr.assign(n_tags + 1, 0); h.cam_obs.resize(n_obs); h.tag_obs.resize(n_obs);
+    h.obs_of.assign((size_t)n_cams * n_tags, -1);
+    for (int m = 0; m < n_obs; m++) {
+        int f = obs_cam[m], j = obs_tag[m];
+        if (f < 0 || f >= n_cams || j < 0 || j >= n_tags) return fail(ASL_EINVAL, "observation %d references camera %d / tag %d", m, f, j);
+        if (h.obs_of[(size_t)f * n_tags + j] >= 0) return fail(ASL_EINVAL, "camera %d observes tag %d twice", f, j);
+        h.obs_of[(size_t)f * n_tags + j] = m;
+        h.cam_ptr[f + 1]++; h.tag_ptr[j + 1]++;
+    }
+    for (int f = 0; f < n_cams; f++) h.cam_ptr[f + 1] += h.cam_ptr[f];
+    for (int j = 0; j < n_tags; j++) h.tag_ptr[j + 1] += h.tag_ptr[j];
+    {
+        std::vector<int> cf(h.cam_ptr.begin(), h.cam_ptr.end() - 1), tf(h.tag_ptr.begin(), h.tag_ptr.end() - 1);
+        for (int m = 0; m < n_obs; m++) { h.cam_obs[cf[obs_cam[m]]++] = m; h.tag_obs[tf[obs_tag[m]]++] = m; }
+    }
+    h.W.resize((size_t)12 * n_cams); h.G.resize((size_t)12 * n_tags);
+    for (int f = 0; f < n_cams; f++) gn_rigid_inverse(cam_T + 16 * (size_t)f, &h.W[12 * (size_t)f]);
+    for (int j = 0; j < n_tags; j++) gn_pack(tag_T + 16 * (size_t)j, &h.G[12 * (size_t)j]);
+    return ASL_OK;
+}
+
+// The problem on the device, in one workspace: the inputs (poses, corners, observation lists and their CSR) and the LM's
+// buffers; the uploads are enqueued on st and the LM's failure flag cleared
+struct GnDevProblem {
+    GnSystem sys{};
+    double *Wc, *Gc, *corners;
+    GnLmBufs b;
+};
+
+static int gn_stage_problem(DevBuf<uint8_t> &ws, const GnHostProblem &h, int n_cams, int n_tags, int n_obs, const int32_t *obs_cam,
+                            const int32_t *obs_tag, const double *obs_corners, int fixed_tag, hipStream_t st, GnDevProblem &p)
+{
+    GnSystem &sys = p.sys;
+    sys.n_cams = n_cams; sys.n_tags = n_tags; sys.fixed_tag = fixed_tag;
+    if (carve_ws(ws, [&](WsCarve &c) {
+            p.Wc = c.take<double>(h.W.size()); p.Gc = c.take<double>(h.G.size()); p.corners = c.take<double>((size_t)8 * n_obs);
+            sys.obs_cam = c.take<int>(n_obs); sys.obs_tag = c.take<int>(n_obs); sys.cam_ptr = c.take<int>(h.cam_ptr.size());
+            sys.cam_obs = c.take<int>(n_obs); sys.tag_ptr = c.take<int>(h.tag_ptr.size()); sys.tag_obs = c.take<int>(n_obs);
+            p.b = gn_lm_carve(c, sys, n_obs, GN_LM__N);
+        }))
+        return fail(ASL_ENOMEM, "Gauss-Newton workspace allocation failed");
+    HIPCHK(hipMemcpyAsync(p.Wc, h.W.data(), h.W.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(p.Gc, h.G.data(), h.G.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(p.corners, obs_corners, (size_t)8 * n_obs * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sys.obs_cam, obs_cam, (size_t)n_obs * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sys.obs_tag, obs_tag, (size_t)n_obs * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sys.cam_ptr, h.cam_ptr.data(), h.cam_ptr.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sys.cam_obs, h.cam_obs.data(), h.cam_obs.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sys.tag_ptr, h.tag_ptr.data(), h.tag_ptr.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sys.tag_obs, h.tag_obs.data(), h.tag_obs.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sys.obs_of, h.obs_of.data(), h.obs_of.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(p.b.flag, 0, 4, st));
+    return ASL_OK;
+}
+
+static void gn_launch_linearize(const GnDevProblem &p, const CamDev &cam, int n_obs, const double *Wp, const double *Gp, double *Dp,
+                                hipStream_t st)
+{
+    hipLaunchKernelGGL(k_gn_linearize, dim3((n_obs + 3) / 4), dim3(256), 0, st, Wp, Gp, p.sys.obs_cam, p.sys.obs_tag, p.corners, n_obs, cam, Dp,
+                       p.b.cost_obs);
+}
+
 extern "C" int asl_gn_solve(asl_detector *d, int n_cams, int n_tags, int n_obs, const int32_t *obs_cam, const int32_t *obs_tag,
                             const double *obs_corners, const double *K, double tag_size, int fixed_tag, double *cam_T,
                             double *tag_T, int iters, double *stats)
 {
-    if (!d || !obs_cam || !obs_tag || !obs_corners || !K || !cam_T || !tag_T) return fail(ASL_EINVAL, "NULL argument");
-    if (n_cams <= 0 || n_tags <= 0 || n_obs <= 0 || iters < 0) return fail(ASL_EINVAL, "empty problem");
-    if (fixed_tag < 0 || fixed_tag >= n_tags) return fail(ASL_EINVAL, "fixed_tag out of range");
-    if ((long long)n_tags * 6 > 6000) return fail(ASL_EINVAL, "more than 1000 tags: the dense reduced system is not meant for that");
+    GnHostProblem h;
+    if (int rc = gn_host_problem(d, n_cams, n_tags, n_obs, obs_cam, obs_tag, obs_corners, K, fixed_tag, cam_T, tag_T, h)) return rc;
+    if (iters < 0) return fail(ASL_EINVAL, "iters must be >= 0 (got %d)", iters);
     HIPCHK(hipSetDevice(d->device));
-
-    // CSR lists by camera and by tag (observation order kept), and the (camera, tag) -> observation table
-    std::vector<int> cam_ptr(n_cams + 1, 0), tag_ptr(n_tags + 1, 0), cam_obs(n_obs), tag_obs(n_obs), obs_of((size_t)n_cams * n_tags, -1);
-    for (int m = 0; m < n_obs; m++) {
-        int f = obs_cam[m], j = obs_tag[m];
-        if (f < 0 || f >= n_cams || j < 0 || j >= n_tags) return fail(ASL_EINVAL, "observation %d references camera %d / tag %d", m, f, j);
-        if (obs_of[(size_t)f * n_tags + j] >= 0) return fail(ASL_EINVAL, "camera %d observes tag %d twice", f, j);
-        obs_of[(size_t)f * n_tags + j] = m;
-        cam_ptr[f + 1]++; tag_ptr[j + 1]++;
-    }
-    for (int f = 0; f < n_cams; f++) cam_ptr[f + 1] += cam_ptr[f];
-    for (int j = 0; j < n_tags; j++) tag_ptr[j + 1] += tag_ptr[j];
-    {
-        std::vector<int> cf(cam_ptr.begin(), cam_ptr.end() - 1), tf(tag_ptr.begin(), tag_ptr.end() - 1);
-        for (int m = 0; m < n_obs; m++) { cam_obs[cf[obs_cam[m]]++] = m; tag_obs[tf[obs_tag[m]]++] = m; }
-    }
-    std::vector<double> W((size_t)12 * n_cams), G((size_t)12 * n_tags);
-    for (int f = 0; f < n_cams; f++) gn_rigid_inverse(cam_T + 16 * (size_t)f, &W[12 * (size_t)f]);
-    for (int j = 0; j < n_tags; j++) gn_pack(tag_T + 16 * (size_t)j, &G[12 * (size_t)j]);
-
-    // one workspace: the inputs (poses, corners, observation lists and their CSR) and the LM's buffers
-    GnSystem sys{};
-    sys.n_cams = n_cams; sys.n_tags = n_tags; sys.fixed_tag = fixed_tag;
-    double *Wc, *Gc, *corners;
-    GnLmBufs b;
-    if (carve_ws(d->gn_ws, [&](WsCarve &c) {
-            Wc = c.take<double>(W.size()); Gc = c.take<double>(G.size()); corners = c.take<double>((size_t)8 * n_obs);
-            sys.obs_cam = c.take<int>(n_obs); sys.obs_tag = c.take<int>(n_obs); sys.cam_ptr = c.take<int>(cam_ptr.size());
-            sys.cam_obs = c.take<int>(n_obs); sys.tag_ptr = c.take<int>(tag_ptr.size()); sys.tag_obs = c.take<int>(n_obs);
-            b = gn_lm_carve(c, sys, n_obs, GN_LM__N);
-        }))
-        return fail(ASL_ENOMEM, "Gauss-Newton workspace allocation failed");
     // a stream of its own, at the highest priority: the solve is a chain of small launches and read-backs, and behind a
     // detector batch on a shared queue every one of them would wait for the whole batch
     if (!d->aux_stream) {
@@ -157,22 +227,15 @@ extern "C" int asl_gn_solve(asl_detector *d, int n_cams, int n_tags, int n_obs, 
         HIPCHK(hipStreamCreateWithPriority(&d->aux_stream, hipStreamNonBlocking, hi));
     }
     hipStream_t st = d->aux_stream;
-    HIPCHK(hipMemcpyAsync(Wc, W.data(), W.size() * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(Gc, G.data(), G.size() * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(corners, obs_corners, (size_t)8 * n_obs * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sys.obs_cam, obs_cam, (size_t)n_obs * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sys.obs_tag, obs_tag, (size_t)n_obs * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sys.cam_ptr, cam_ptr.data(), cam_ptr.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sys.cam_obs, cam_obs.data(), cam_obs.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sys.tag_ptr, tag_ptr.data(), tag_ptr.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sys.tag_obs, tag_obs.data(), tag_obs.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sys.obs_of, obs_of.data(), obs_of.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(b.flag, 0, 4, st));
+    GnDevProblem p;
+    if (int rc = gn_stage_problem(d->gn_ws, h, n_cams, n_tags, n_obs, obs_cam, obs_tag, obs_corners, fixed_tag, st, p)) return rc;
+    const GnSystem &sys = p.sys;
+    const GnLmBufs &b = p.b;
+    double *Wc = p.Wc, *Gc = p.Gc;
+    std::vector<double> &W = h.W, &G = h.G;
 
     const CamDev cam = make_cam(d, K, nullptr, 0, tag_size);
-    auto lin = [&](const double *Wp, const double *Gp, double *Dp, int) {
-        hipLaunchKernelGGL(k_gn_linearize, dim3((n_obs + 3) / 4), dim3(256), 0, st, Wp, Gp, sys.obs_cam, sys.obs_tag, corners, n_obs, cam, Dp, b.cost_obs);
-    };
+    auto lin = [&](const double *Wp, const double *Gp, double *Dp, int) { gn_launch_linearize(p, cam, n_obs, Wp, Gp, Dp, st); };
     auto decide = [&]() { hipLaunchKernelGGL(k_gn_decide, dim3(1), dim3(1), 0, st, b.lm); };
     // The whole solve is enqueued at once: cost, lambda and the accept / reject decision live in device memory (b.lm), an
     // accepted trial is copied over the current state, and the host waits exactly once, at the end.

@@ -685,7 +685,8 @@ int asl_rectify_u8(asl_detector *det, const uint8_t *src, int channels, int w, i
 /* ---- introspection and diagnostics.  asl_debug_fetch, asl_stage_times and the counters (item 5) describe the LAST batch
    the detector ran.  asl_detect_batch_u8 and asl_detect_batch_pose_u8 run a call of 128 frames or more as consecutive
    batches of 64 frames, so after such a call that is the call's last chunk (frames 128..149 of a 150-frame call), not the
-   whole call.  asl_debug_fetch, asl_debug_refit, asl_debug_dedup, asl_debug_division_check and asl_debug_phase_cycles are told the room
+   whole call.  asl_debug_fetch, asl_debug_refit, asl_debug_dedup, asl_debug_gn_cholesky, asl_debug_gn_step, asl_debug_division_check and
+   asl_debug_phase_cycles are told the room
    they may write into and return ASL_EINVAL, writing nothing, when it is too small; asl_stage_times fills at most max_n. */
 
 /* Copy an intermediate buffer of the last batch to host, for the parity tests.
@@ -724,6 +725,37 @@ int asl_debug_refit(asl_detector *det, int reps, int64_t *out, size_t n_out);
    of range, max_out < n, n_counters < 3, a batch pending. */
 int asl_debug_dedup(asl_detector *det, const asl_detection *dets, const uint64_t *keys, int n, int n_frames, int cap_per_frame,
                     asl_detection *out, int max_out, int *n_per_frame, int64_t *counters, size_t n_counters);
+/* Diagnostic: the dense linear algebra of the pose-graph back-end alone, on a matrix of the caller's: the blocked Cholesky
+   (48-column blocks), the back substitution and the diag(A^-1) pass, launched as asl_gn_solve and asl_map_* launch them.
+   A is n x n row-major, symmetric (the lower triangle is read), b has n values, n = 6 x tags with 1 <= tags <= 1000.
+   L (n_L >= n * n): the factor, upper triangle zero;  y, x, var (n_vec >= n each): L^-1 b (the right-hand side rides through
+   the factorisation as row n), the solution of A x = b, and diag(A^-1);  Linv (n_Linv >= ceil(n / 48) * 48 * 48): the
+   inverses of the factor's diagonal blocks, 48 x 48 row-major each, a partial last block padded with the identity;
+   *fail_flag: 1 if A is not positive definite (the call still returns ASL_OK: the other outputs are then meaningless).
+   Synchronous, in device buffers of its own.  ASL_EINVAL, nothing written: a NULL pointer, n not such a size, an output
+   too small, a batch pending. */
+int asl_debug_gn_cholesky(asl_detector *det, const double *A, const double *b, int n, double *L, size_t n_L, double *y, double *x,
+                          double *var, size_t n_vec, double *Linv, size_t n_Linv, int32_t *fail_flag);
+/* Diagnostic: one damped step of asl_gn_solve's problem (its arguments and checks; cam_T and tag_T are only read), with the
+   damping lambda (>= 0) given: the linearisation and its cost, the cameras eliminated, the reduced system factored, the
+   step and the trial poses, through the launches a solve uses.  out has ASL_GN_STEP__N entries, one per item below; an
+   entry {p, n} names room for n doubles at p, p NULL: not wanted.  Item (doubles needed):
+     D (n_obs * 156) the 12 x 13 blocks [J^T J | J^T r] per observation;  COST_OBS (n_obs), COST (1) their costs and the sum;
+     HINV (n_cams * 36), GC (n_cams * 6) the damped camera blocks inverted and the camera gradients;  TFJ (n_obs * 36)
+     H_cc^-1 W_fj per observation;  S (n * n, n = 6 n_tags), RHS (n) the reduced system before it is factored;
+     DG (n) the tag steps;  WN (n_cams * 12), GN (n_tags * 12) the trial poses camera<-world and world<-tag, R row-major then t.
+   *fail_flag (may be NULL): 1 if the reduced system was not positive definite.  Synchronous, in a workspace of its own.
+   ASL_EINVAL, nothing written: asl_gn_solve's refusals, out NULL, n_out != ASL_GN_STEP__N, lambda negative or not finite,
+   an entry too small, a batch pending. */
+typedef struct {
+    double *p;
+    size_t n;
+} asl_debug_span;
+enum { ASL_GN_STEP_D = 0, ASL_GN_STEP_COST_OBS, ASL_GN_STEP_COST, ASL_GN_STEP_HINV, ASL_GN_STEP_GC, ASL_GN_STEP_TFJ, ASL_GN_STEP_S,
+       ASL_GN_STEP_RHS, ASL_GN_STEP_DG, ASL_GN_STEP_WN, ASL_GN_STEP_GN, ASL_GN_STEP__N };
+int asl_debug_gn_step(asl_detector *det, int n_cams, int n_tags, int n_obs, const int32_t *obs_cam, const int32_t *obs_tag,
+                      const double *obs_corners, const double *K, double tag_size, int fixed_tag, const double *cam_T,
+                      const double *tag_T, double lambda, const asl_debug_span *out, int n_out, int32_t *fail_flag);
 /* Diagnostic: the shared-reciprocal division of the line fits (asl_common.h) against the compiler's on 2^29 random operand
    pairs with exponents within +-exponent_limit (in [1, 900]).  out (n_out >= 2) = {pairs, mismatches}. */
 int asl_debug_division_check(asl_detector *det, int exponent_limit, int64_t *out, size_t n_out);

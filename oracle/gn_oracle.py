@@ -78,8 +78,8 @@ def linearize(W, G, obs_cam, obs_tag, obs_corners, K, tag_size):
     return float((r * r).sum()), r, Jc, Jt
 
 
-def lm_step(W, G, obs_cam, obs_tag, obs_corners, K, tag_size, fixed_tag, lam):
-    """One damped Gauss-Newton step via the camera Schur complement.  Returns (cost, dW, dG)."""
+def _reduce(W, G, obs_cam, obs_tag, obs_corners, K, tag_size, fixed_tag, lam):
+    """reduced_system's (S, b, keep) and what lm_step goes on with: (cost, Hinv, gc, Wb, seen)"""
     P, L = len(W), len(G)
     oc = np.asarray(obs_cam, dtype=np.int64); ot = np.asarray(obs_tag, dtype=np.int64)
     cost, r, Jc, Jt = linearize(W, G, oc, ot, obs_corners, K, tag_size)
@@ -114,6 +114,22 @@ def lm_step(W, G, obs_cam, obs_tag, obs_corners, K, tag_size, fixed_tag, lam):
     keep[6 * fixed_tag:6 * fixed_tag + 6] = False
     unseen = ~np.any(Hll.reshape(L, 36) != 0, axis=1)
     keep[np.repeat(unseen, 6)] = False
+    return S, b, keep, (cost, Hinv, gc, Wb, seen)
+
+
+def reduced_system(W, G, obs_cam, obs_tag, obs_corners, K, tag_size, fixed_tag, lam):
+    """The damped system with the cameras eliminated (their Schur complement): (S, b, keep) -- S (6L, 6L) and b over every
+    tag parameter, keep the rows that are solved: not the fixed tag's, not an unobserved tag's (S is not the identity there,
+    those rows are left out of the solve)."""
+    return _reduce(W, G, obs_cam, obs_tag, obs_corners, K, tag_size, fixed_tag, lam)[:3]
+
+
+def lm_step(W, G, obs_cam, obs_tag, obs_corners, K, tag_size, fixed_tag, lam):
+    """One damped Gauss-Newton step via the camera Schur complement.  Returns (cost, dW, dG)."""
+    P, L = len(W), len(G)
+    ot = np.asarray(obs_tag, dtype=np.int64)
+    S, b, keep, (cost, Hinv, gc, Wb, seen) = _reduce(W, G, obs_cam, obs_tag, obs_corners, K, tag_size, fixed_tag, lam)
+    n = 6 * L
     xl = np.zeros(n)
     xl[keep] = np.linalg.solve(S[np.ix_(keep, keep)], b[keep])
     dG = xl.reshape(L, 6)

@@ -274,3 +274,123 @@ def test_localize_and_rig(block):
               ("camera 0: K is not finite", dict(rig=table(K=KNAN))), ("camera 0: E is not finite", dict(rig=table(E=np.full((3, 4), np.inf))))],
         [(cams % 17, dict(n_cams=17, max_tags=0)), (MAX_TAGS % 0, dict(max_tags=0, rig=table(K=KNAN))), (slots, dict(n_cams=2, max_tags=129, gate=-1.0)),
          (gate, dict(gate=-1.0, rig=table(n_dist=3))), ("camera 0: n_dist must be 0, 4 or 5 (got 3)", dict(rig=table(n_dist=3, K=KNAN)))])
+
+
+# ---- the pose-graph back-end: asl_gn_solve and its two diagnostics (csrc/gn_host.inc, debug_host.inc) -----------------------
+
+def gn_problem_args():
+    """a small good problem (2 tags, 6 cameras) as asl_gn_solve's arguments, and fresh copies of the arrays it may write"""
+    from gn_cases import problem_case
+    c = problem_case(2, 0, 1e-3)
+    oc, ot = np.ascontiguousarray(c["obs_cam"], dtype=np.int32), np.ascontiguousarray(c["obs_tag"], dtype=np.int32)
+    KEEP.extend([oc, ot])
+    base = dict(d=None, n_cams=len(c["cam0"]), n_tags=2, n_obs=len(oc), obs_cam=oc.ctypes.data_as(IP), obs_tag=ot.ctypes.data_as(IP),
+                corners=dptr(c["obs_corners"].reshape(-1, 8)), K=dptr(c["K"]), tag_size=10.0, fixed_tag=0)
+    return c, oc, ot, base
+
+
+GN_EMPTY, GN_FIXED = "empty problem", "fixed_tag out of range"
+GN_TAGS = "more than 1000 tags: the dense reduced system is not meant for that"
+
+
+def gn_list_faults(oc, ot, n_cams):
+    """observation lists with one fault each: a camera or a tag out of range on either side, a (camera, tag) pair twice"""
+    def ints(a, i, v):
+        a = a.copy()
+        a[i] = v
+        KEEP.append(a)
+        return a.ctypes.data_as(IP)
+    ref = "observation %d references camera %d / tag %d"
+    twice = ot.copy()
+    first = int(np.flatnonzero(oc == oc[0])[1])    # camera oc[0]'s second observation: make it its first tag again
+    return [(ref % (1, n_cams, ot[1]), dict(obs_cam=ints(oc, 1, n_cams))), (ref % (0, -1, ot[0]), dict(obs_cam=ints(oc, 0, -1))),
+            (ref % (2, oc[2], 2), dict(obs_tag=ints(ot, 2, 2))), (ref % (2, oc[2], -1), dict(obs_tag=ints(ot, 2, -1))),
+            ("camera %d observes tag %d twice" % (oc[0], ot[0]), dict(obs_tag=ints(twice, first, ot[0])))]
+
+
+def test_gn_solve(block):
+    """every ASL_EINVAL of asl_gn_solve, each followed by a good call on the same detector that still succeeds; the refusal of a
+    reduced system that is not positive definite (here: a focal length that is not a number) comes after the solve and leaves
+    the poses as they were"""
+    c, oc, ot, base = gn_problem_args()
+    cam_T, tag_T, stats = np.array(c["cam0"]), np.array(c["tag0"]), np.zeros(3)
+    base.update(d=block.h, cam_T=cam_T.ctypes.data_as(DP), tag_T=tag_T.ctypes.data_as(DP), iters=2, stats=stats.ctypes.data_as(DP))
+    form = Form("asl_gn_solve", "d n_cams n_tags n_obs obs_cam obs_tag corners K tag_size fixed_tag cam_T tag_T iters stats", base,
+                [cam_T, tag_T, stats])
+    single = [(NULL_ARG, dict(d=None)), (NULL_ARG, dict(obs_cam=None)), (NULL_ARG, dict(obs_tag=None)), (NULL_ARG, dict(corners=None)),
+              (NULL_ARG, dict(K=None)), (NULL_ARG, dict(cam_T=None)), (NULL_ARG, dict(tag_T=None)),
+              (GN_EMPTY, dict(n_cams=0)), (GN_EMPTY, dict(n_tags=0)), (GN_EMPTY, dict(n_obs=0)), ("iters must be >= 0 (got -1)", dict(iters=-1)),
+              (GN_FIXED, dict(fixed_tag=-1)), (GN_FIXED, dict(fixed_tag=2)), (GN_TAGS, dict(n_tags=1001))] + gn_list_faults(oc, ot, base["n_cams"])
+    pairs = [(NULL_ARG, dict(K=None, n_obs=0)), (GN_EMPTY, dict(n_obs=0, fixed_tag=5)), (GN_FIXED, dict(fixed_tag=5, iters=-1)),
+             (GN_TAGS, dict(n_tags=1001, iters=-1))]
+
+    def good():
+        cam_T[:], tag_T[:] = c["cam0"], c["tag0"]
+        assert form() == 0, _lib.load().asl_last_error()
+        assert stats[1] < stats[0] and stats[2] >= 1
+        return cam_T.copy(), tag_T.copy(), stats.copy()
+    first = good()
+    for message, changes in single + pairs:
+        form.fill()
+        form.refuses(message, **changes)
+        assert form.untouched(), (message, changes)
+        again = good()
+        assert all(np.array_equal(a, b) for a, b in zip(first, again)), (message, changes)
+    # not positive definite: with a focal length that is not a number the factorisation meets a pivot that is not one either;
+    # no trial is accepted and the poses come back as they were
+    cam_T[:], tag_T[:] = c["cam0"], c["tag0"]
+    form.refuses("reduced system not positive definite (under-constrained problem?)", K=dptr(KNAN))
+    assert stats[2] == 0 and np.array_equal(tag_T, c["tag0"]) and np.abs(cam_T - c["cam0"]).max() <= 1e-12
+    good()
+
+
+def test_debug_gn_cholesky(block):
+    from gn_cases import dense_case
+    c = dense_case(2)
+    n, A, b = c["n"], c["A"], c["b"]
+    L, y, x, var, Linv, flag = np.zeros((n, n)), np.zeros(n), np.zeros(n), np.zeros(n), np.zeros((1, 48, 48)), np.zeros(1, dtype=np.int32)
+    outs = [L, y, x, var, Linv, flag]
+    base = dict(d=block.h, A=dptr(A), b=dptr(b), n=n, L=L.ctypes.data_as(DP), n_L=L.size, y=y.ctypes.data_as(DP), x=x.ctypes.data_as(DP),
+                var=var.ctypes.data_as(DP), n_vec=n, Linv=Linv.ctypes.data_as(DP), n_Linv=Linv.size, flag=flag.ctypes.data_as(IP))
+    form = Form("asl_debug_gn_cholesky", "d A b n L n_L y x var n_vec Linv n_Linv flag", base, outs)
+    size = "n must be 6 times a tag count in [1, 1000] (got %d)"
+    single = [(NULL_ARG, {k: None}) for k in ("d", "A", "b", "L", "y", "x", "var", "Linv", "flag")]
+    single += [(size % 13, dict(n=13)), (size % 0, dict(n=0)), (size % -6, dict(n=-6)), (size % 6006, dict(n=6006)),
+               ("L too small: need 144 values (got 143)", dict(n_L=143)), ("y, x and var too small: need 12 values each (got 11)", dict(n_vec=11)),
+               ("Linv too small: need 2304 values (got 2303)", dict(n_Linv=2303)),
+               ("Linv too small: need 4608 values (got 2304)", dict(n=54, n_L=54 * 54, n_vec=54))]    # a second block needs its own room
+    pairs = [(NULL_ARG, dict(A=None, n=13)), (size % 13, dict(n=13, n_L=0)), ("L too small: need 144 values (got 0)", dict(n_L=0, n_vec=0))]
+    run(form, single, pairs)
+    assert form() == 0 and flag[0] == 0 and np.abs(L @ L.T - A).max() <= 1e-12 * np.abs(A).max()
+
+
+def test_debug_gn_step(block):
+    c, oc, ot, base = gn_problem_args()
+    P, M = base["n_cams"], len(oc)
+    shapes = _lib.gn_step_shapes(P, 2, M)
+    bufs = {k: np.zeros(shapes[k]) for k in _lib.GN_STEP_ITEMS}
+    flag = np.zeros(1, dtype=np.int32)
+
+    def spans(short=None, skip=()):
+        s = (_lib.DebugSpan * len(_lib.GN_STEP_ITEMS))()
+        for i, k in enumerate(_lib.GN_STEP_ITEMS):
+            if k not in skip:
+                s[i].p, s[i].n = bufs[k].ctypes.data_as(DP), bufs[k].size - (1 if k == short else 0)
+        KEEP.append(s)
+        return s
+    base.update(d=block.h, cam_T=dptr(c["cam0"]), tag_T=dptr(c["tag0"]), lam=1e-3, out=spans(), n_out=len(_lib.GN_STEP_ITEMS),
+                flag=flag.ctypes.data_as(IP))
+    form = Form("asl_debug_gn_step", "d n_cams n_tags n_obs obs_cam obs_tag corners K tag_size fixed_tag cam_T tag_T lam out n_out flag", base,
+                list(bufs.values()) + [flag])
+    lam = "lambda must be >= 0 and finite (got %s)"
+    single = [(NULL_ARG, {k: None}) for k in ("d", "obs_cam", "obs_tag", "corners", "K", "cam_T", "tag_T", "out")]
+    single += [(GN_EMPTY, dict(n_cams=0)), (GN_EMPTY, dict(n_tags=0)), (GN_EMPTY, dict(n_obs=0)), (GN_FIXED, dict(fixed_tag=-1)),
+               (GN_FIXED, dict(fixed_tag=2)), (GN_TAGS, dict(n_tags=1001)), (lam % "-1", dict(lam=-1.0)), (lam % "nan", dict(lam=float("nan"))),
+               (lam % "inf", dict(lam=float("inf"))), ("out must have 11 entries (got 10)", dict(n_out=10))] + gn_list_faults(oc, ot, P)
+    need = dict(zip(_lib.GN_STEP_ITEMS, (156 * M, M, 1, 36 * P, 6 * P, 36 * M, 144, 12, 12, 12 * P, 24)))
+    single += [("out[%d] too small: need %d values (got %d)" % (i, need[k], need[k] - 1), dict(out=spans(short=k))) for i, k in enumerate(_lib.GN_STEP_ITEMS)]
+    pairs = [(GN_EMPTY, dict(n_obs=0, lam=-1.0)), (lam % "-1", dict(lam=-1.0, n_out=3)), ("out must have 11 entries (got 3)", dict(n_out=3, out=spans(short="S")))]
+    run(form, single, pairs)
+    # the flag and every item are optional
+    assert form(flag=None, out=spans(skip=_lib.GN_STEP_ITEMS)) == 0 and form.untouched()
+    assert form() == 0 and flag[0] == 0 and bufs["dG"][1].any() and not bufs["dG"][0].any()
