@@ -51,7 +51,7 @@ EXPORTS = [
     "asl_localize_frames_device", "asl_localize_batch", "asl_localize_cov_frames_device", "asl_localize_cov_batch",
     "asl_pose_cov_device", "asl_solve_pnp_cov_batch", "asl_calibrate_frames_device", "asl_calibrate_batch",
     "asl_localize_rig_frames_device", "asl_localize_rig_cov_frames_device", "asl_localize_rig_batch", "asl_localize_rig_cov_batch",
-    "asl_map_frames_device", "asl_map_batch", "asl_map_robust_frames_device", "asl_map_robust_batch", "asl_smooth_frames_device", "asl_smooth_batch", "asl_smooth_cov_frames_device", "asl_smooth_cov_batch",
+    "asl_map_frames_device", "asl_map_batch", "asl_map_robust_frames_device", "asl_map_robust_batch", "asl_map_rig_frames_device", "asl_map_rig_batch", "asl_smooth_frames_device", "asl_smooth_batch", "asl_smooth_cov_frames_device", "asl_smooth_cov_batch",
     "asl_smooth_sequences_device", "asl_smooth_sequences_batch", "asl_smooth_robust_sequences_device", "asl_smooth_robust_sequences_batch",
     "asl_smooth_timed_sequences_device", "asl_smooth_timed_sequences_batch",
     "asl_smooth_rig_sequences_device", "asl_smooth_rig_sequences_batch",
@@ -145,6 +145,9 @@ def load():
     mapping_robust = mapping[:10] + [dbl] + mapping[10:] + [vp]    # ..., world_id, huber_px, max_iters, the four results, slot_weight
     L.asl_map_robust_frames_device.argtypes = mapping_robust + [vp]
     L.asl_map_robust_batch.argtypes = mapping_robust
+    mapping_rig = [vp, vp, i32, i32, i32, i32, vp, dbl] + mapping_robust[9:]    # detector, obs, n_cams, n_frames, max_tags, n_ids, rig, tag_size, world_id, ...
+    L.asl_map_rig_frames_device.argtypes = mapping_rig + [vp]
+    L.asl_map_rig_batch.argtypes = mapping_rig
     smooth, seqs = [vp] + obs_block + tag_map + camera + [vp], [C.POINTER(C.c_int32), i32]    # ..., seed; seq_start, n_seq
     solve = sigmas + [i32, vp, vp]                                # ..., max_iters, out, result
     L.asl_smooth_frames_device.argtypes = smooth + solve + [vp]
@@ -566,6 +569,35 @@ class Detector:
         check(self._L.asl_map_frames_device(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), int(n_ids), Kp, dpp, nd, float(tag_size),
                                             int(world_id), int(max_iters), _ptr(map_ptr), _opt_ptr(std_ptr), _ptr(poses_ptr),
                                             _ptr(result_ptr), _ptr(stream)))
+
+    def build_map_rig(self, obs, n_ids, rig, tag_size, world_id=-1, max_iters=30, with_std=True, huber_px=0.0, with_slot_weight=False):
+        """asl_map_rig_batch: host records obs (n_cams, n_frames, max_tags) OBS_DTYPE, camera-major, of a rig whose camera table
+        is rig ((n_cams,) RIG_CAMERA_DTYPE, or a rig.Rig) -> build_map's items with poses = world<-rig per frame; huber_px as
+        there (0: the squared loss).  with_slot_weight: a fifth item, (n_cams, n_frames, max_tags) doubles."""
+        o = np.ascontiguousarray(obs, dtype=OBS_DTYPE)
+        if o.ndim != 3:
+            raise ValueError("obs must be (n_cams, n_frames, max_tags) asl_obs records")
+        r = _rig_records(rig)
+        if len(r) != o.shape[0]:
+            raise ValueError("the rig has %d cameras, obs has %d" % (len(r), o.shape[0]))
+        res = np.zeros((), dtype=MAP_RESULT_DTYPE)
+        tmap = np.zeros(max(int(n_ids), 1), dtype=MAP_TAG_DTYPE)
+        std = np.zeros((max(int(n_ids), 1), 6), dtype=np.float64) if with_std else None
+        poses = np.zeros(o.shape[1], dtype=CAM_POSE_DTYPE)
+        weight = np.zeros(o.shape, dtype=np.float64) if with_slot_weight else None
+        check(self._L.asl_map_rig_batch(self._h, _data(o), o.shape[0], o.shape[1], o.shape[2], int(n_ids), _data(r), float(tag_size), int(world_id),
+                                        float(huber_px), int(max_iters), tmap.ctypes.data, std.ctypes.data if with_std else None, _data(poses),
+                                        res.ctypes.data, weight.ctypes.data if with_slot_weight else None))
+        return (res, tmap, std, poses, weight) if with_slot_weight else (res, tmap, std, poses)
+
+    def build_map_rig_device(self, obs_ptr, n_cams, n_frames, max_tags, n_ids, rig_ptr, tag_size, map_ptr, std_ptr, poses_ptr, result_ptr,
+                             world_id=-1, max_iters=30, stream=0, huber_px=0.0, slot_weight_ptr=0):
+        """asl_map_rig_frames_device: obs_ptr (n_cams x n_frames x max_tags asl_obs, camera-major), rig_ptr (n_cams asl_rig_camera,
+        complete when the call is made) and the outputs of build_map_device (slot_weight_ptr: n_cams x n_frames x max_tags
+        doubles or 0) are device addresses; enqueued on `stream` after one wait for the problem size."""
+        check(self._L.asl_map_rig_frames_device(self._h, _ptr(obs_ptr), int(n_cams), int(n_frames), int(max_tags), int(n_ids), _ptr(rig_ptr),
+                                                float(tag_size), int(world_id), float(huber_px), int(max_iters), _ptr(map_ptr), _opt_ptr(std_ptr),
+                                                _ptr(poses_ptr), _ptr(result_ptr), _opt_ptr(slot_weight_ptr), _ptr(stream)))
 
     def smooth(self, obs, tag_map, K, dist, tag_size, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, seed=None,
                with_cov=False, huber_px=0.0, times=None):

@@ -1,11 +1,11 @@
 // Tag-map reconstruction from a batch of frames (asl_map_frames_device / asl_map_batch): world<-tag poses of every tag
 // the frames see, each frame's camera pose and a per-tag std, from the asl_obs block alone.  float64 throughout;
 // tests/map_ref.py is the NumPy statement of the same computation.
-//   k_map_gather    one workgroup: taking-part slots, used frames (>= 2 slots) -> cameras, ids seen -> tags (ascending),
-//                   observations in (frame, slot) order, the world tag; the host reads the sizes (its one wait)
-//   k_map_table     the (camera, tag) -> observation table k_gn_schur reads
-//   k_map_csr       one workgroup: the per-camera and per-tag lists of the active observations (in observation order,
-//                   tag lists in camera order), inactive entries of the table cleared; run after each stage that drops
+//   k_map_gather    one workgroup: taking-part slots, used frames (>= 2 slots of distinct ids) -> cameras, ids seen -> tags
+//                   (ascending), observations in (frame, slot) order, the world tag; the host reads the sizes (its one wait)
+//   k_map_csr       one workgroup: the (camera, tag) -> first active observation table k_gn_schur reads, each pair's chain
+//                   of later ones, and the per-camera and per-tag lists of the active observations (in observation
+//                   order); run after each stage that drops
 //   k_map_chain     one workgroup: breadth-first rounds from the world tag (cameras, then tags, each half reading the state
 //                   the previous one left) -- map_init.chain_initial_map without its dependence on frame order
 //   k_map_sweep_cam per camera (one wavefront): reseed_poses' camera half -- k_localize.inc's slot gather, top-8 choice,
@@ -28,6 +28,15 @@
 //   k_map_soft      one workgroup: per observation the smallest corner weight at the committed poses; the number of soft
 //                   observations, the squared error and the number of the corners not over k, summed in a fixed order
 // which k_map_finish takes for n_soft, the slot weights and the std's variance factor.  huber_px = 0 runs the plain kernels.
+// A camera rig (asl_map_rig_*, tests/map_rig_ref.py): the block is camera-major, obs[n_rig][n_frames][max_tags], the
+// "cameras" of the joint problem are the used rig frames with W = rig<-world, and an observation is a VIEW, a taking-part
+// slot of one rig camera, in (frame, camera, slot) order.  The kernels are written once over the view's camera
+// (map_view<RIG>): one camera is the call's model and W itself, a rig the table's entry (a.cams, k_rig.inc's layout, read
+// where it is used) and E_c W.  A (frame, tag) pair may have several views; the seeding, k_map_soft, the behind test and
+// the records work on the view lists (a.tag_ptr / a.tag_obs), the reduced system on the pair lists (a.cam_*, a.ptag_*,
+// a.obs_of), which hold the pair's first active view.  12 x 13 blocks of views of one pair are additive, so after each
+// linearisation k_map_fold adds the later views' blocks to the first one's, in view order (a.obs_next).  With one camera
+// every pair has one view, the two sets of lists are equal and nothing is folded.
 // No atomics: every sum has a fixed order (wave butterflies, per-thread loops in list order, k_gn_cost's fixed tree), so the
 // same input gives the same bytes; frames without taking-part slots change no list, no index and no sum.
 
@@ -51,14 +60,18 @@ enum { MAP_LM_STOP = GN_LM__N, MAP_LM_ITERS, MAP_LM_STATUS, MAP_LM__N = 16 };
 struct MapArgs {
     const ObsRec *obs;
     int n_frames, max_tags, n_ids, world_req;
+    int n_rig;                                              // cameras a frame has: 1, or the rig's
+    const double *cams;                                     // a rig: RIG_CAM_DOUBLES per camera (k_rig.inc's layout)
     MapHead *head;
-    int *seen, *id_tag, *tag_id, *tmp;                      // per id (n_ids + 1)
-    int *fr_npart, *fr_cam, *fr_obs0;                       // per frame (+1)
+    int *seen, *id_tag, *tag_id, *tmp, *tmp2;               // per id (n_ids + 1)
+    int *fr_npart, *fr_ndist, *fr_cam, *fr_obs0;            // per frame (+1): taking-part slots, distinct ids among them
     int *cam_frame, *cam_ptr0, *cam_state, *cam_seed;       // per camera (<= n_frames, +1)
     int *tag_state;                                         // per tag (<= n_ids)
-    int *slot_obs;                                          // per slot
-    int *obs_slot, *obs_cam, *obs_tag, *obs_act;            // per observation (<= n_frames * max_tags)
-    int *cam_ptr, *cam_obs, *tag_ptr, *tag_obs, *obs_of;    // active lists, (camera, tag) table
+    int *slot_obs;                                          // per slot of the block
+    int *obs_slot, *obs_cam, *obs_tag, *obs_act;            // per observation (<= n_rig * n_frames * max_tags); obs_slot: in the block
+    int *tag_ptr, *tag_obs;                                 // every active observation by tag
+    int *cam_ptr, *cam_obs, *ptag_ptr, *ptag_obs, *obs_of;  // the first active one of each (camera, tag) pair: lists and table
+    int *obs_next;                                          // the pair's next active observation, -1 at the end
     double *W, *G;                                          // camera<-world, world<-tag: R row-major (9), t (3)
 };
 
@@ -108,6 +121,35 @@ __device__ __forceinline__ void map_obs_pose(const ObsRec &o, bool mirror, doubl
     A[9] = t[0]; A[10] = t[1]; A[11] = t[2];
 }
 
+// the rig camera of observation m (0 with one camera), and its entry of the rig's table
+__device__ __forceinline__ int map_view_rig_cam(const MapArgs &a, int m) { return a.obs_slot[m] / (a.n_frames * a.max_tags); }
+__device__ __forceinline__ const double *map_view_entry(const MapArgs &a, int m) { return a.cams + RIG_CAM_DOUBLES * map_view_rig_cam(a, m); }
+
+// The camera of observation m: its model cv and its pose Wv = camera<-world where the frame's pose is W.  One camera: the
+// call's model and W itself; a rig: the table's entry and E_c W (W = rig<-world).
+template <bool RIG>
+__device__ __forceinline__ void map_view(const MapArgs &a, const CamDev &cam, int m, const double *W, CamDev &cv, double *Wv)
+{
+    cv = cam;
+    if constexpr (RIG) {
+        const double *cl = map_view_entry(a, m);
+        cv.fx = cl[0]; cv.fy = cl[1]; cv.cx = cl[2]; cv.cy = cl[3]; cv.k1 = cl[4]; cv.k2 = cl[5]; cv.p1 = cl[6]; cv.p2 = cl[7]; cv.k3 = cl[8];
+        double Wr[12];
+#pragma unroll
+        for (int i = 0; i < 12; i++) Wr[i] = W[i];
+        pk_mul(cl + 9, Wr, Wv);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 12; i++) Wv[i] = W[i];
+    }
+}
+
+// a rig's table in k_rig.inc's layout, into a.cams: one wavefront
+__global__ void __launch_bounds__(64) k_map_rig_table(double *cams, const RigCamRec *__restrict__ rig, int n_cams)
+{
+    rig_fill_cams(cams, rig, n_cams, (int)threadIdx.x);
+}
+
 // exclusive prefix sum of cnt(i), i < n, by the MAP_WG threads (contiguous chunks, then the chunks in order) into out[0..n]
 // (if out); returns the total in every thread
 template <class Cnt>
@@ -139,38 +181,46 @@ __device__ __forceinline__ int map_scan(int n, Cnt cnt, int *s_part, int *out)
 __global__ void __launch_bounds__(MAP_WG) k_map_gather(MapArgs a)
 {
     __shared__ int s_part[MAP_WG + 1];
-    const int tid = threadIdx.x, S = a.max_tags;
+    const int tid = threadIdx.x, S = a.max_tags, NR = a.n_rig;
+    auto slot = [&](int r, int f, int s) { return ((size_t)r * a.n_frames + f) * S + s; };  // the block is camera-major
     for (int i = tid; i < a.n_ids; i += MAP_WG) a.seen[i] = 0;
     for (int f = tid; f < a.n_frames; f += MAP_WG) {
-        const ObsRec *fo = a.obs + (size_t)f * S;
-        int np = 0;
-        for (int s = 0; s < S; s++) {
-            const int id = fo[s].id;
-            bool p = (fo[s].flags & 1) && id >= 0 && id < a.n_ids;
-            for (int s2 = 0; p && s2 < s; s2++)  // a repeated id takes part once, in its first slot
-                if ((fo[s2].flags & 1) && fo[s2].id == id) p = false;
-            a.slot_obs[(size_t)f * S + s] = p ? 1 : -1;
-            np += p;
+        int np = 0, nd = 0;
+        for (int r = 0; r < NR; r++) {
+            const ObsRec *fo = a.obs + slot(r, f, 0);
+            for (int s = 0; s < S; s++) {
+                const int id = fo[s].id;
+                bool p = (fo[s].flags & 1) && id >= 0 && id < a.n_ids;
+                for (int s2 = 0; p && s2 < s; s2++)  // a repeated id takes part once per camera, in its first slot
+                    if ((fo[s2].flags & 1) && fo[s2].id == id) p = false;
+                a.slot_obs[slot(r, f, s)] = p ? 1 : -1;
+                np += p;
+                bool first = p;  // the frame's first view of the id: no earlier camera has one
+                for (int k2 = 0; first && k2 < r * S; k2++)
+                    if (a.slot_obs[slot(k2 / S, f, k2 % S)] == 1 && a.obs[slot(k2 / S, f, k2 % S)].id == id) first = false;
+                nd += first;
+            }
         }
         a.fr_npart[f] = np;
+        a.fr_ndist[f] = nd;
     }
     __syncthreads();
     for (int f = tid; f < a.n_frames; f += MAP_WG) {
-        if (a.fr_npart[f] < 2) continue;
-        for (int s = 0; s < S; s++)
-            if (a.slot_obs[(size_t)f * S + s] == 1) a.seen[a.obs[(size_t)f * S + s].id] = 1;  // every writer stores the same 1
+        if (a.fr_ndist[f] < 2) continue;
+        for (int k = 0; k < NR * S; k++)
+            if (a.slot_obs[slot(k / S, f, k % S)] == 1) a.seen[a.obs[slot(k / S, f, k % S)].id] = 1;  // every writer stores the same 1
     }
     __syncthreads();
-    const int n_cams = map_scan(a.n_frames, [&](int f) { return a.fr_npart[f] >= 2 ? 1 : 0; }, s_part, a.fr_cam);
-    const int n_obs = map_scan(a.n_frames, [&](int f) { return a.fr_npart[f] >= 2 ? a.fr_npart[f] : 0; }, s_part, a.fr_obs0);
+    const int n_cams = map_scan(a.n_frames, [&](int f) { return a.fr_ndist[f] >= 2 ? 1 : 0; }, s_part, a.fr_cam);
+    const int n_obs = map_scan(a.n_frames, [&](int f) { return a.fr_ndist[f] >= 2 ? a.fr_npart[f] : 0; }, s_part, a.fr_obs0);
     const int n_tags = map_scan(a.n_ids, [&](int i) { return a.seen[i]; }, s_part, a.id_tag);
     for (int f = tid; f < a.n_frames; f += MAP_WG) {
-        const bool used = a.fr_npart[f] >= 2;
+        const bool used = a.fr_ndist[f] >= 2;
         const int c = a.fr_cam[f];
         int m = a.fr_obs0[f];
         if (used) { a.cam_frame[c] = f; a.cam_ptr0[c] = m; }
-        for (int s = 0; s < S; s++) {
-            const size_t k = (size_t)f * S + s;
+        for (int g = 0; g < NR * S; g++) {  // (camera, slot) order
+            const size_t k = slot(g / S, f, g % S);
             if (used && a.slot_obs[k] == 1) {
                 a.obs_slot[m] = (int)k; a.obs_cam[m] = c; a.obs_tag[m] = a.id_tag[a.obs[k].id]; a.obs_act[m] = 1;
                 a.slot_obs[k] = m++;
@@ -191,52 +241,70 @@ __global__ void __launch_bounds__(MAP_WG) k_map_gather(MapArgs a)
     }
 }
 
-__global__ void __launch_bounds__(256) k_map_table(MapArgs a, int n_obs, int n_tags)
-{
-    const int m = blockIdx.x * 256 + threadIdx.x;
-    if (m < n_obs) a.obs_of[(size_t)a.obs_cam[m] * n_tags + a.obs_tag[m]] = m;
-}
-
-// ---- active lists: one workgroup
+// ---- active lists: one workgroup.  The table entry of a (camera, tag) pair is its first active observation, and obs_next
+// chains the pair's later ones in observation order (one camera: there are none).  The tag lists walk the table in camera
+// order and each chain, which is observation order.
 __global__ void __launch_bounds__(MAP_WG) k_map_csr(MapArgs a, int n_cams, int n_tags)
 {
     __shared__ int s_part[MAP_WG + 1];
     const int tid = threadIdx.x;
+    for (size_t i = tid; i < (size_t)n_cams * n_tags; i += MAP_WG) a.obs_of[i] = -1;
+    __syncthreads();
+    for (int c = tid; c < n_cams; c += MAP_WG)
+        for (int m = a.cam_ptr0[c]; m < a.cam_ptr0[c + 1]; m++) {
+            a.obs_next[m] = -1;
+            if (!a.obs_act[m]) continue;
+            int *e = a.obs_of + (size_t)c * n_tags + a.obs_tag[m];
+            if (*e < 0) { *e = m; continue; }
+            int p = *e;
+            while (a.obs_next[p] >= 0) p = a.obs_next[p];
+            a.obs_next[p] = m;
+        }
+    __syncthreads();
+    // one camera: a pair has one view, every active observation is its pair's first, and no chain is followed (the tag
+    // loops below are a few threads walking every camera: a dependent load per entry would double their time)
+    const bool chains = a.n_rig > 1;
+    auto first = [&](int m) { return a.obs_act[m] && (!chains || a.obs_of[(size_t)a.obs_cam[m] * n_tags + a.obs_tag[m]] == m); };
+    auto next = [&](int m) { return chains ? a.obs_next[m] : -1; };
     auto cam_cnt = [&](int c) {
         int k = 0;
-        for (int m = a.cam_ptr0[c]; m < a.cam_ptr0[c + 1]; m++) k += a.obs_act[m];
+        for (int m = a.cam_ptr0[c]; m < a.cam_ptr0[c + 1]; m++) k += first(m);
         return k;
     };
-    const int n_act = map_scan(n_cams, cam_cnt, s_part, a.cam_ptr);
+    map_scan(n_cams, cam_cnt, s_part, a.cam_ptr);
     for (int c = tid; c < n_cams; c += MAP_WG) {
         int o = a.cam_ptr[c];
         for (int m = a.cam_ptr0[c]; m < a.cam_ptr0[c + 1]; m++)
-            if (a.obs_act[m]) a.cam_obs[o++] = m;
+            if (first(m)) a.cam_obs[o++] = m;
     }
     for (int j = tid; j < n_tags; j += MAP_WG) {
-        int k = 0;
+        int k = 0, kp = 0;
         for (int c = 0; c < n_cams; c++) {
-            int *e = a.obs_of + (size_t)c * n_tags + j;
-            const int m = *e;
-            if (m < 0) continue;
-            if (a.obs_act[m]) k++;
-            else *e = -1;
+            int m = a.obs_of[(size_t)c * n_tags + j];
+            kp += m >= 0;
+            for (; m >= 0; m = next(m)) k++;
         }
         a.tmp[j] = k;
+        a.tmp2[j] = kp;
     }
     __syncthreads();
-    map_scan(n_tags, [&](int j) { return a.tmp[j]; }, s_part, a.tag_ptr);
+    const int n_act = map_scan(n_tags, [&](int j) { return a.tmp[j]; }, s_part, a.tag_ptr);
+    map_scan(n_tags, [&](int j) { return a.tmp2[j]; }, s_part, a.ptag_ptr);
     for (int j = tid; j < n_tags; j += MAP_WG) {
-        int o = a.tag_ptr[j];
+        int o = a.tag_ptr[j], op = a.ptag_ptr[j];
         for (int c = 0; c < n_cams; c++) {
-            const int m = a.obs_of[(size_t)c * n_tags + j];
-            if (m >= 0) a.tag_obs[o++] = m;
+            int m = a.obs_of[(size_t)c * n_tags + j];
+            if (m >= 0) a.ptag_obs[op++] = m;
+            for (; m >= 0; m = next(m)) a.tag_obs[o++] = m;
         }
     }
     if (tid == 0) a.head->n_act = n_act;
 }
 
-// ---- breadth-first initial map: one workgroup
+// ---- breadth-first initial map: one workgroup.  A rig: a view's PnP pose is its own camera's, so the frame's pose is
+// inv(E_c) T_obs inv(G) and the tag's inv(E_c W) T_obs (LocRig::candidate, camera_pose); the frame half walks the views in
+// (camera, slot) order, so a tie of area and tag keeps the lower camera, the tag half in observation order.
+template <bool RIG>
 __global__ void __launch_bounds__(MAP_WG) k_map_chain(MapArgs a, int n_cams, int n_tags, int n_obs, int wt)
 {
     __shared__ int s_changed;
@@ -262,9 +330,15 @@ __global__ void __launch_bounds__(MAP_WG) k_map_chain(MapArgs a, int n_cams, int
             double To[12], Gi[12];
             map_obs_pose(a.obs[a.obs_slot[bm]], false, To);
             pk_inv(a.G + 12 * (size_t)bt, Gi);
-            pk_mul(To, Gi, a.W + 12 * (size_t)c);
+            if constexpr (RIG) {
+                double Ei[12], Tc[12];
+                pk_inv(map_view_entry(a, bm) + 9, Ei);
+                pk_mul(To, Gi, Tc);
+                pk_mul(Ei, Tc, a.W + 12 * (size_t)c);
+            } else
+                pk_mul(To, Gi, a.W + 12 * (size_t)c);
             a.cam_state[c] = 1;
-            a.cam_seed[c] = a.obs_slot[bm] % S;
+            a.cam_seed[c] = map_view_rig_cam(a, bm) * S + a.obs_slot[bm] % S;  // the frame's global slot
             s_changed = 1;
         }
         __syncthreads();
@@ -272,7 +346,7 @@ __global__ void __launch_bounds__(MAP_WG) k_map_chain(MapArgs a, int n_cams, int
             if (a.tag_state[j]) continue;
             double ba = -1.0;
             int bm = -1;
-            for (int o = a.tag_ptr[j]; o < a.tag_ptr[j + 1]; o++) {  // camera order: a tie keeps the lower camera
+            for (int o = a.tag_ptr[j]; o < a.tag_ptr[j + 1]; o++) {  // observation order: a tie keeps the lower camera
                 const int m = a.tag_obs[o];
                 const ObsRec &r = a.obs[a.obs_slot[m]];
                 if (!(r.flags & 2) || !a.cam_state[a.obs_cam[m]]) continue;
@@ -280,9 +354,11 @@ __global__ void __launch_bounds__(MAP_WG) k_map_chain(MapArgs a, int n_cams, int
                 if (ar > ba) { ba = ar; bm = m; }
             }
             if (bm < 0) continue;
-            double To[12], Wi[12];
+            double To[12], Wv[12], Wi[12];
+            CamDev unused{};
             map_obs_pose(a.obs[a.obs_slot[bm]], false, To);
-            pk_inv(a.W + 12 * (size_t)a.obs_cam[bm], Wi);
+            map_view<RIG>(a, unused, bm, a.W + 12 * (size_t)a.obs_cam[bm], unused, Wv);
+            pk_inv(Wv, Wi);
             pk_mul(Wi, To, a.G + 12 * (size_t)j);
             a.tag_state[j] = 1;
             s_changed = 1;
@@ -295,18 +371,26 @@ __global__ void __launch_bounds__(MAP_WG) k_map_chain(MapArgs a, int n_cams, int
     for (int m = tid; m < n_obs; m += MAP_WG) a.obs_act[m] = a.cam_state[a.obs_cam[m]] == 1 && a.tag_state[a.obs_tag[m]] == 1;
 }
 
-// ---- reseed, camera half: one wavefront per camera, k_localize.inc's layout and functions
+// ---- reseed, camera half: one wavefront per camera, k_localize.inc's layout and functions over the frame's slots: one
+// camera's max_tags (LocOneCam), or the rig's n_rig * max_tags global slots (LocRig, its table read from a.cams)
+template <bool RIG>
 __global__ void __launch_bounds__(64) k_map_sweep_cam(MapArgs a, CamDev cam)
 {
     extern __shared__ double s_dyn[];
-    const int c = blockIdx.x, lane = threadIdx.x, S = a.max_tags, n4 = 4 * S;
+    const int c = blockIdx.x, lane = threadIdx.x, S = RIG ? a.n_rig * a.max_tags : a.max_tags;
     if (a.cam_state[c] != 1) return;
     const LocLds L = loc_lds(s_dyn, S);
     const int f = a.cam_frame[c];
-    const ObsRec *fo = a.obs + (size_t)f * S;
+    const LocRig rig{a.cams, a.obs, 65536u / (unsigned int)a.max_tags + 1u, a.n_rig, a.max_tags, a.n_frames, f};
+    const LocOneCam one{cam, a.obs + (size_t)f * a.max_tags, a.max_tags};
+    auto rec = [&](int s) {
+        if constexpr (RIG) return rig.rec(s);
+        else return one.rec(s);
+    };
     int npart = 0;
     for (int s = lane; s < S; s += ASL_WAVE) {
-        const int m = a.slot_obs[(size_t)f * S + s];
+        const ObsRec *fo = rec(s);
+        const int m = a.slot_obs[fo - a.obs];
         const bool part = m >= 0 && a.obs_act[m];
         L.state[s] = part ? 1 : 0;
         L.area[s] = -1.0;
@@ -314,13 +398,16 @@ __global__ void __launch_bounds__(64) k_map_sweep_cam(MapArgs a, CamDev cam)
         npart++;
         double M[12];
         pk_to34(a.G + 12 * (size_t)a.obs_tag[m], M);
-        loc_gather_slot(L, s, M, cam.half, fo[s].corners);
-        if (fo[s].flags & 2) L.area[s] = loc_area(fo[s].corners);
+        loc_gather_slot(L, s, M, cam.half, fo->corners);
+        if (fo->flags & 2) L.area[s] = loc_area(fo->corners);
     }
     __syncthreads();
     npart = butterfly_sum<64>(npart);
     if (npart == 0) return;
-    auto score = [&](const double *P) { return loc_pass<false>(cam, P, P + 9, L, n4, lane, nullptr); };
+    auto score = [&](const double *P) {
+        if constexpr (RIG) return loc_pass<false>(rig, P, P + 9, L, lane, nullptr);
+        else return loc_pass<false>(one, P, P + 9, L, lane, nullptr);
+    };
     double P[12];
     const double *Wc = a.W + 12 * (size_t)c;
 #pragma unroll
@@ -329,11 +416,15 @@ __global__ void __launch_bounds__(64) k_map_sweep_cam(MapArgs a, CamDev cam)
     int sel[MAP_MAX_CAND];
     const int nsel = loc_top_k(S, lane, [&](int s) { return L.area[s]; }, sel);
     auto make = [&](int s) {
+        const ObsRec *fo = rec(s);
         double To[12], M[12];
-        pk_to34(a.G + 12 * (size_t)a.obs_tag[a.slot_obs[(size_t)f * S + s]], M);
+        pk_to34(a.G + 12 * (size_t)a.obs_tag[a.slot_obs[fo - a.obs]], M);
 #pragma unroll
-        for (int i = 0; i < 12; i++) To[i] = fo[s].T[i];
-        return [=](bool mirror, double *C) { loc_candidate(To, M, mirror, C, C + 9); };
+        for (int i = 0; i < 12; i++) To[i] = fo->T[i];
+        return [=](bool mirror, double *C) {
+            if constexpr (RIG) rig.candidate(s, To, M, mirror, C, C + 9);
+            else loc_candidate(To, M, mirror, C, C + 9);
+        };
     };
     loc_best_candidate(sel, nsel, make, score, best, P);
     if (lane == 0) {
@@ -345,8 +436,8 @@ __global__ void __launch_bounds__(64) k_map_sweep_cam(MapArgs a, CamDev cam)
 
 // Total corner cost of world<-tag (R, t) over the tag's observations b..e of the active list, the cameras held; with NE
 // also the normal equations of the left update of the tag (packed lower triangle 21, then J^T r 6), identical in every lane.
-template <bool NE>
-__device__ __forceinline__ double map_tag_pass(const MapArgs &a, const CamDev &c, const double *R, const double *t, int b, int e, int lane,
+template <bool NE, bool RIG>
+__device__ __forceinline__ double map_tag_pass(const MapArgs &a, const CamDev &cam, const double *R, const double *t, int b, int e, int lane,
                                                double *ne)
 {
     double cost = 0, acc[27];
@@ -354,7 +445,9 @@ __device__ __forceinline__ double map_tag_pass(const MapArgs &a, const CamDev &c
     for (int i = 0; i < 27; i++) acc[i] = 0;
     for (int k = lane; k < 4 * (e - b); k += ASL_WAVE) {
         const int m = a.tag_obs[b + (k >> 2)], q = k & 3;
-        const double *Wc = a.W + 12 * (size_t)a.obs_cam[m];
+        CamDev c;
+        double Wc[12];
+        map_view<RIG>(a, cam, m, a.W + 12 * (size_t)a.obs_cam[m], c, Wc);
         const ObsRec &o = a.obs[a.obs_slot[m]];
         const double ox = (q == 1 || q == 2) ? c.half : -c.half, oy = (q >= 2) ? c.half : -c.half;
         double X[3], P[3], uv[2], Jp[6];
@@ -393,19 +486,20 @@ __device__ __forceinline__ double map_tag_pass(const MapArgs &a, const CamDev &c
 }
 
 // ---- reseed, tag half: one wavefront per tag, the cameras held
+template <bool RIG>
 __global__ void __launch_bounds__(64) k_map_sweep_tag(MapArgs a, CamDev cam)
 {
     const int j = blockIdx.x, lane = threadIdx.x;
     if (a.tag_state[j] != 1) return;
     const int b = a.tag_ptr[j], e = a.tag_ptr[j + 1], n = e - b;
     if (n == 0) return;
-    auto score = [&](const double *P) { return map_tag_pass<false>(a, cam, P, P + 9, b, e, lane, nullptr); };
+    auto score = [&](const double *P) { return map_tag_pass<false, RIG>(a, cam, P, P + 9, b, e, lane, nullptr); };
     double P[12];
     const double *Gj = a.G + 12 * (size_t)j;
 #pragma unroll
     for (int i = 0; i < 12; i++) P[i] = Gj[i];
     double best = score(P);  // the current pose is candidate 0
-    // the <= 8 seeding observations of largest area (ties: lower list position = lower camera)
+    // the <= 8 seeding observations of largest area (ties: lower list position = observation order)
     int sel[MAP_MAX_CAND];
     const int nsel = loc_top_k(n, lane, [&](int o) {
         const ObsRec &rec = a.obs[a.obs_slot[a.tag_obs[b + o]]];
@@ -413,8 +507,10 @@ __global__ void __launch_bounds__(64) k_map_sweep_tag(MapArgs a, CamDev cam)
     }, sel);
     auto make = [&](int o) {
         const int m = a.tag_obs[b + o];
-        double Wi[12];
-        pk_inv(a.W + 12 * (size_t)a.obs_cam[m], Wi);
+        double Wv[12], Wi[12];
+        CamDev unused;
+        map_view<RIG>(a, cam, m, a.W + 12 * (size_t)a.obs_cam[m], unused, Wv);
+        pk_inv(Wv, Wi);
         const ObsRec *rec = a.obs + a.obs_slot[m];
         return [=](bool mirror, double *C) {
             double To[12];
@@ -454,6 +550,7 @@ __global__ void __launch_bounds__(MAP_WG) k_map_gauge(MapArgs a, int n_cams, int
 }
 
 // ---- flip test: one wavefront per tag
+template <bool RIG>
 __global__ void __launch_bounds__(64) k_map_flip(MapArgs a, CamDev cam, int wt)
 {
     const int j = blockIdx.x, lane = threadIdx.x;
@@ -462,7 +559,7 @@ __global__ void __launch_bounds__(64) k_map_flip(MapArgs a, CamDev cam, int wt)
     if (n == 0) return;
     double G0[12], R0[9], t0[3], R1[9], t1[3];
     for (int i = 0; i < 12; i++) G0[i] = a.G[12 * (size_t)j + i];
-    // the view where the tag is largest (ties: lower camera)
+    // the view where the tag is largest (ties: lower list position)
     double ba = -1.0;
     int bo = 0x7fffffff;
     for (int o = lane; o < n; o += ASL_WAVE) {
@@ -471,7 +568,12 @@ __global__ void __launch_bounds__(64) k_map_flip(MapArgs a, CamDev cam, int wt)
     }
     argmax_step<1>(ba, bo); argmax_step<2>(ba, bo); argmax_step<4>(ba, bo);
     argmax_step<8>(ba, bo); argmax_step<16>(ba, bo); argmax_step<32>(ba, bo);
-    const double *Wb = a.W + 12 * (size_t)a.obs_cam[a.tag_obs[b + bo]];
+    double Wb[12];
+    {
+        const int mb = a.tag_obs[b + bo];
+        CamDev unused;
+        map_view<RIG>(a, cam, mb, a.W + 12 * (size_t)a.obs_cam[mb], unused, Wb);
+    }
     double CT[12], CT34[12], I34[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, Mr[12], Wi[12], Gm[12];
     pk_mul(Wb, G0, CT);
     pk_to34(CT, CT34);
@@ -481,7 +583,7 @@ __global__ void __launch_bounds__(64) k_map_flip(MapArgs a, CamDev cam, int wt)
     for (int i = 0; i < 9; i++) { R0[i] = G0[i]; R1[i] = Gm[i]; }
     for (int i = 0; i < 3; i++) { t0[i] = G0[9 + i]; t1[i] = Gm[9 + i]; }
     auto pass = [&](const double *R, const double *t, auto ne_tag, double *ne) {
-        return map_tag_pass<decltype(ne_tag)::value>(a, cam, R, t, b, e, lane, ne);
+        return map_tag_pass<decltype(ne_tag)::value, RIG>(a, cam, R, t, b, e, lane, ne);
     };
     const double c0 = pose_lm(pass, R0, t0);
     const double c1 = pose_lm(pass, R1, t1);
@@ -493,15 +595,18 @@ __global__ void __launch_bounds__(64) k_map_flip(MapArgs a, CamDev cam, int wt)
     }
 }
 
-// ---- behind the camera: one thread per camera
+// ---- behind the camera: one thread per camera.  A rig's frame stays with >= 2 distinct tags among its active views.
+template <bool RIG>
 __global__ void __launch_bounds__(64) k_map_behind(MapArgs a, int n_cams, double half)
 {
     const int c = blockIdx.x * 64 + threadIdx.x;
     if (c >= n_cams || a.cam_state[c] != 1) return;
-    const double *Wc = a.W + 12 * (size_t)c;
     int k = 0;
     for (int m = a.cam_ptr0[c]; m < a.cam_ptr0[c + 1]; m++) {
         if (!a.obs_act[m]) continue;
+        double Wc[12];
+        CamDev unused{};
+        map_view<RIG>(a, unused, m, a.W + 12 * (size_t)c, unused, Wc);
         const double *Gj = a.G + 12 * (size_t)a.obs_tag[m];
         bool ok = true;
         for (int q = 0; q < 4; q++) {
@@ -512,6 +617,9 @@ __global__ void __launch_bounds__(64) k_map_behind(MapArgs a, int n_cams, double
             ok = ok && z > MAP_BEHIND_MARGIN;
         }
         a.obs_act[m] = ok;
+        if constexpr (RIG)  // an earlier active view of the same tag: counted already
+            for (int m2 = a.cam_ptr0[c]; ok && m2 < m; m2++)
+                if (a.obs_act[m2] && a.obs_tag[m2] == a.obs_tag[m]) ok = false;
         k += ok;
     }
     if (k < 2) {
@@ -532,7 +640,10 @@ __global__ void k_map_lm_init(const MapHead *head, double *lm, double *lm0)
 // Nothing happens after the stop unless forced.  ROBUST: the Huber loss of threshold hk on the corner's residual length s
 // (both components come from the row's one projection): beyond hk the two rows are scaled by sqrt(hk / s) and the corner
 // costs 2 hk s - hk^2; a corner's cost is returned once, in its component-0 row.  <false> ignores hk.
-template <bool ROBUST>
+// RIG: gn_obs_block gets W = rig<-world, so its p is the rig-frame point; the row applies the view's mounting, projects with
+// the view's camera and returns jp = J_proj Re_c, for which the camera block [-[p]x | I] and the tag block are the rig's
+// (rig_corner's derivation).
+template <bool ROBUST, bool RIG>
 __global__ void __launch_bounds__(256) k_map_linearize(MapArgs a, const double *__restrict__ W, const double *__restrict__ G, int n_obs, CamDev cam,
                                                        double *__restrict__ D, double *__restrict__ cost_obs, const double *__restrict__ lm, int force,
                                                        double hk)
@@ -545,13 +656,33 @@ __global__ void __launch_bounds__(256) k_map_linearize(MapArgs a, const double *
         return;
     }
     const ObsRec &o = a.obs[a.obs_slot[m]];
-    auto row = [&](int k, const double *p, double *jp, double &add) {
+    auto row = [&](int k, const double *pf, double *jp, double &add) {
         const int comp = k & 1;
         double res = 0;
         jp[0] = 0; jp[1] = 0; jp[2] = 0; add = 0;
+        CamDev cv = cam;
+        double p[3] = {pf[0], pf[1], pf[2]};
+        [[maybe_unused]] const double *Re = nullptr;
+        if constexpr (RIG) {
+            const double *cl = map_view_entry(a, m), *te = cl + 18;
+            Re = cl + 9;
+            cv.fx = cl[0]; cv.fy = cl[1]; cv.cx = cl[2]; cv.cy = cl[3]; cv.k1 = cl[4]; cv.k2 = cl[5]; cv.p1 = cl[6]; cv.p2 = cl[7]; cv.k3 = cl[8];
+#pragma unroll
+            for (int r = 0; r < 3; r++) p[r] = Re[3 * r] * pf[0] + Re[3 * r + 1] * pf[1] + Re[3 * r + 2] * pf[2] + te[r];
+        }
         if (p[2] > LOC_Z_MIN) {
             double uv[2], Jp[6];
-            project_dev(cam, p, uv, Jp);
+            project_dev(cv, p, uv, Jp);
+            if constexpr (RIG) {  // J_proj Re, both rows
+                double Jr[6];
+#pragma unroll
+                for (int r = 0; r < 3; r++) {
+                    Jr[r] = Jp[0] * Re[r] + Jp[1] * Re[3 + r] + Jp[2] * Re[6 + r];
+                    Jr[3 + r] = Jp[3] * Re[r] + Jp[4] * Re[3 + r] + Jp[5] * Re[6 + r];
+                }
+#pragma unroll
+                for (int r = 0; r < 6; r++) Jp[r] = Jr[r];
+            }
             if constexpr (ROBUST) {
                 const double r0 = uv[0] - (double)o.corners[k - comp], r1 = uv[1] - (double)o.corners[k - comp + 1];
                 const double e = r0 * r0 + r1 * r1, s = sqrt(e);
@@ -575,12 +706,26 @@ __global__ void __launch_bounds__(256) k_map_linearize(MapArgs a, const double *
     if (lane == 0) cost_obs[m] = c;
 }
 
+// A rig's pairs with several views: the blocks of the pair's later active views added to its first one's (the one the
+// lists and the table hold), in view order; one thread per entry of the block.  Under k_map_linearize's own condition, so
+// that a block is folded once per linearisation.
+__global__ void __launch_bounds__(256) k_map_fold(MapArgs a, int n_obs, int n_tags, double *__restrict__ D, const double *__restrict__ lm, int force)
+{
+    const int m = blockIdx.x, e = threadIdx.x;
+    if (e >= GN_DSTRIDE || m >= n_obs || (!force && lm[MAP_LM_STOP] != 0.0)) return;
+    if (!a.obs_act[m] || a.obs_of[(size_t)a.obs_cam[m] * n_tags + a.obs_tag[m]] != m || a.obs_next[m] < 0) return;
+    double acc = D[(size_t)m * GN_DSTRIDE + e];
+    for (int m2 = a.obs_next[m]; m2 >= 0; m2 = a.obs_next[m2]) acc += D[(size_t)m2 * GN_DSTRIDE + e];
+    D[(size_t)m * GN_DSTRIDE + e] = acc;
+}
+
 // The robust call's look at the committed poses (a.W, a.G), one workgroup: wmin_obs[m] = the smallest of observation m's
 // four corner weights (0 for an inactive one); sums = {soft observations (a weight < 1), squared error of the corners not
 // over hk, their number}, a corner at z <= 1e-9 being one of them with its 1e12.  Per-thread sums in observation order,
 // then k_gn_cost's tree.
 enum { MAP_SOFT_N = 0, MAP_SOFT_COST, MAP_SOFT_IN, MAP_SOFT__N };
-__global__ void __launch_bounds__(256) k_map_soft(MapArgs a, int n_obs, CamDev cam, double hk, double *__restrict__ wmin_obs, double *__restrict__ sums)
+template <bool RIG>
+__global__ void __launch_bounds__(256) k_map_soft(MapArgs a, int n_obs, CamDev cam0, double hk, double *__restrict__ wmin_obs, double *__restrict__ sums)
 {
     __shared__ double s_cost[256];
     __shared__ int s_soft[256], s_in[256];
@@ -592,7 +737,10 @@ __global__ void __launch_bounds__(256) k_map_soft(MapArgs a, int n_obs, CamDev c
         if (a.obs_act[m]) {
             wm = 1.0;
             const ObsRec &o = a.obs[a.obs_slot[m]];
-            const double *Wc = a.W + 12 * (size_t)a.obs_cam[m], *Gj = a.G + 12 * (size_t)a.obs_tag[m];
+            const double *Gj = a.G + 12 * (size_t)a.obs_tag[m];
+            CamDev cam;
+            double Wc[12];
+            map_view<RIG>(a, cam0, m, a.W + 12 * (size_t)a.obs_cam[m], cam, Wc);
             for (int q = 0; q < 4; q++) {
                 const double ox = (q == 1 || q == 2) ? cam.half : -cam.half, oy = (q >= 2) ? cam.half : -cam.half;
                 double X[3], P[3], uv[2];
@@ -706,10 +854,11 @@ __global__ void __launch_bounds__(MAP_WG) k_map_finish(MapArgs a, int n_cams, in
     for (int f = tid; f < a.n_frames; f += MAP_WG) {
         CamPoseRec *o = poses + f;
         const int np = a.fr_npart[f];
+        const bool used = a.fr_ndist[f] >= 2;
         int st = 1, na = 0, seed = -1;
         double T[12], rms = 0, rms0 = 0;
         pk_eye(T);
-        if (np >= 2) {
+        if (used) {
             const int c = a.fr_cam[f];
             st = nothing ? 5 : (a.cam_state[c] == 1 ? (status == 0 ? 0 : 4) : a.cam_state[c] == 3 ? 3 : 5);
             seed = nothing ? -1 : a.cam_seed[c];
@@ -727,7 +876,7 @@ __global__ void __launch_bounds__(MAP_WG) k_map_finish(MapArgs a, int n_cams, in
         o->T[12] = 0; o->T[13] = 0; o->T[14] = 0; o->T[15] = 1;
         o->rms_px = rms; o->rms_seed_px = rms0;
         o->n_tags = na;
-        o->n_rejected = np >= 2 ? np - na : 0;
+        o->n_rejected = used ? np - na : 0;
         o->status = st;
         o->seed_slot = seed;
     }
@@ -744,7 +893,7 @@ __global__ void __launch_bounds__(MAP_WG) k_map_finish(MapArgs a, int n_cams, in
             for (int k = 0; k < 6; k++) tag_std[6 * (size_t)i + k] = (ok && j != wt && std_ok) ? sqrt(s2 * var[6 * j + k]) : 0.0;
     }
     if (slot_weight)
-        for (size_t k = tid; k < (size_t)a.n_frames * a.max_tags; k += MAP_WG) {
+        for (size_t k = tid; k < (size_t)a.n_rig * a.n_frames * a.max_tags; k += MAP_WG) {
             const int m = nothing ? -1 : a.slot_obs[k];
             slot_weight[k] = (m >= 0 && status == 0 && a.obs_act[m]) ? (wmin_obs ? wmin_obs[m] : 1.0) : 0.0;
         }

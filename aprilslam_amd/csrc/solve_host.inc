@@ -402,47 +402,69 @@ extern "C" int asl_calibrate_batch(asl_detector *d, const asl_obs *obs, int n_fr
 // ---- mapping (k_map.inc)
 
 // One map call, in the robust entry points' argument order; the plain ones give huber_px 0 and no slot_weight.  tag_std
-// and slot_weight may be NULL: not asked for.  obs, map, tag_std, poses, result and slot_weight are all host (asl_map_batch,
-// asl_map_robust_batch) or all device pointers (asl_map_frames_device, asl_map_robust_frames_device).
+// and slot_weight may be NULL: not asked for.  The single-camera forms leave n_cams 0 and rig NULL; the rig forms
+// (asl_map_rig_*) give n_cams and the table and leave cam's K and dist NULL, n_dist 0; their block is camera-major and their
+// slot weights n_cams x n_frames x max_tags.  obs, rig, map, tag_std, poses, result and slot_weight are all host (*_batch) or
+// all device pointers (*_frames_device).
 struct MapCall {
-    const void *obs; int n_frames, max_tags, n_ids;
-    Camera cam;
+    const void *obs; int n_cams, n_frames, max_tags, n_ids;
+    const void *rig; Camera cam;
     int world_id; double huber_px; int max_iters;
     void *map, *tag_std, *poses, *result, *slot_weight;
 };
 
-// every refusal that needs no look at the block, before anything is written or enqueued; the same for both forms
-static int check_map_call(const asl_detector *d, const MapCall &c, bool)
+static bool is_rig(const MapCall &c) { return c.n_cams || c.rig; }
+
+// every refusal that needs no look at the block, before anything is written or enqueued; the same for both forms, but that
+// a rig's table, checked last, is read back first where the pointers are the device's (check_localize_call's rule)
+static int check_map_call(const asl_detector *d, const MapCall &c, bool device)
 {
+    const bool rig = is_rig(c);
     if (!d) return fail(ASL_EINVAL, "NULL detector");
-    if (!c.obs || !c.cam.K || !c.map || !c.poses || !c.result) return fail(ASL_EINVAL, "NULL argument");
+    if (!c.obs || !(rig ? c.rig : (const void *)c.cam.K) || !c.map || !c.poses || !c.result) return fail(ASL_EINVAL, "NULL argument");
     if (c.n_frames < 1) return fail(ASL_EINVAL, "n_frames must be >= 1 (got %d)", c.n_frames);
+    if (rig && (c.n_cams < 1 || c.n_cams > RIG_MAX_CAMS)) return fail(ASL_EINVAL, "n_cams must be in [1, %d] (got %d)", RIG_MAX_CAMS, c.n_cams);
     if (int rc = check_obs_args(c.max_tags, c.n_ids, c.cam)) return rc;
+    if (rig && c.n_cams * c.max_tags > RIG_MAX_SLOTS)
+        return fail(ASL_EINVAL, "n_cams * max_tags must be <= %d (got %d x %d)", RIG_MAX_SLOTS, c.n_cams, c.max_tags);
     if (c.world_id < -1 || c.world_id >= c.n_ids) return fail(ASL_EINVAL, "world_id must be -1 or in [0, n_ids) (got %d)", c.world_id);
     if (c.max_iters < 1 || c.max_iters > MAP_MAX_ITERS) return fail(ASL_EINVAL, "max_iters must be in [1, %d] (got %d)", MAP_MAX_ITERS, c.max_iters);
     if (!(c.huber_px >= 0) || !std::isfinite(c.huber_px)) return fail(ASL_EINVAL, "huber_px must be >= 0 and finite (got %g)", c.huber_px);
-    return ASL_OK;
+    if (!rig) return ASL_OK;
+    asl_rig_camera tab[RIG_MAX_CAMS];
+    if (device) {
+        HIPCHK(hipSetDevice(d->device));
+        HIPCHK(hipMemcpy(tab, c.rig, sizeof(asl_rig_camera) * (size_t)c.n_cams, hipMemcpyDeviceToHost));
+    }
+    return check_rig_table(device ? tab : (const asl_rig_camera *)c.rig, c.n_cams);
 }
 
-// c's pointers are the device's
-static int launch_map(asl_detector *d, const MapCall &c, hipStream_t st)
+// c's pointers are the device's; RIG: the kernels' view model (k_map.inc)
+template <bool RIG>
+static int launch_map_views(asl_detector *d, const MapCall &c, hipStream_t st)
 {
-    const size_t nf = (size_t)c.n_frames, ni = (size_t)c.n_ids, nsl = nf * (size_t)c.max_tags;
+    const size_t nf = (size_t)c.n_frames, ni = (size_t)c.n_ids, nsl = (RIG ? (size_t)c.n_cams : 1) * nf * (size_t)c.max_tags;
     MapArgs a{};
     int *per_id, *per_frame, *per_cam, *per_obs, *csr;  // the grouped int arrays, one piece per group
+    double *cams;
     if (carve_ws(d->map_ws, [&](WsCarve &w) {
-            a.head = w.take<MapHead>(1); per_id = w.take<int>(4 * (ni + 1)); per_frame = w.take<int>(3 * (nf + 1));
-            per_cam = w.take<int>(4 * (nf + 1)); a.tag_state = w.take<int>(ni + 1); a.slot_obs = w.take<int>(nsl); per_obs = w.take<int>(4 * nsl);
-            csr = w.take<int>(2 * nsl + nf + ni + 2); a.W = w.take<double>(12 * nf); a.G = w.take<double>(12 * ni);
+            a.head = w.take<MapHead>(1); per_id = w.take<int>(5 * (ni + 1)); per_frame = w.take<int>(4 * (nf + 1));
+            per_cam = w.take<int>(4 * (nf + 1)); a.tag_state = w.take<int>(ni + 1); a.slot_obs = w.take<int>(nsl); per_obs = w.take<int>(5 * nsl);
+            csr = w.take<int>(3 * nsl + nf + 2 * ni + 3); a.W = w.take<double>(12 * nf); a.G = w.take<double>(12 * ni);
+            cams = w.take<double>(RIG_CAM_DOUBLES * RIG_MAX_CAMS);
         }))
         return fail(ASL_ENOMEM, "map workspace allocation failed");
     a.obs = (const ObsRec *)c.obs; a.n_frames = c.n_frames; a.max_tags = c.max_tags; a.n_ids = c.n_ids; a.world_req = c.world_id;
-    a.seen = per_id; a.id_tag = per_id + (ni + 1); a.tag_id = per_id + 2 * (ni + 1); a.tmp = per_id + 3 * (ni + 1);
-    a.fr_npart = per_frame; a.fr_cam = per_frame + (nf + 1); a.fr_obs0 = per_frame + 2 * (nf + 1);
+    a.n_rig = RIG ? c.n_cams : 1; a.cams = RIG ? cams : nullptr;
+    a.seen = per_id; a.id_tag = per_id + (ni + 1); a.tag_id = per_id + 2 * (ni + 1); a.tmp = per_id + 3 * (ni + 1); a.tmp2 = per_id + 4 * (ni + 1);
+    a.fr_npart = per_frame; a.fr_cam = per_frame + (nf + 1); a.fr_obs0 = per_frame + 2 * (nf + 1); a.fr_ndist = per_frame + 3 * (nf + 1);
     a.cam_frame = per_cam; a.cam_ptr0 = per_cam + (nf + 1); a.cam_state = per_cam + 2 * (nf + 1); a.cam_seed = per_cam + 3 * (nf + 1);
-    a.obs_slot = per_obs; a.obs_cam = per_obs + nsl; a.obs_tag = per_obs + 2 * nsl; a.obs_act = per_obs + 3 * nsl;
-    a.cam_obs = csr; a.tag_obs = csr + nsl; a.cam_ptr = csr + 2 * nsl; a.tag_ptr = csr + 2 * nsl + nf + 1;
-    const CamDev cam = make_cam(d, c.cam);
+    a.obs_slot = per_obs; a.obs_cam = per_obs + nsl; a.obs_tag = per_obs + 2 * nsl; a.obs_act = per_obs + 3 * nsl; a.obs_next = per_obs + 4 * nsl;
+    a.cam_obs = csr; a.tag_obs = csr + nsl; a.ptag_obs = csr + 2 * nsl; a.cam_ptr = csr + 3 * nsl; a.tag_ptr = a.cam_ptr + nf + 1;
+    a.ptag_ptr = a.tag_ptr + ni + 1;
+    static const double no_K[9] = {};
+    const CamDev cam = make_cam(d, RIG ? no_K : c.cam.K, c.cam.dist, c.cam.n_dist, c.cam.tag_size);   // a rig: for its half alone
+    if (RIG) hipLaunchKernelGGL(k_map_rig_table, dim3(1), dim3(ASL_WAVE), 0, st, cams, (const RigCamRec *)c.rig, c.n_cams);
 
     hipLaunchKernelGGL(k_map_gather, dim3(1), dim3(MAP_WG), 0, st, a);
     MapHead h;
@@ -468,7 +490,7 @@ static int launch_map(asl_detector *d, const MapCall &c, hipStream_t st)
     // the reduced system reads the LM's copies of the list offsets (k_map_park empties them after the stop)
     const int n = 6 * NT;
     const size_t nc = (size_t)NC, nt = (size_t)NT, nm = (size_t)NM;
-    GnSystem sys = {nullptr, nullptr, a.cam_obs, nullptr, a.tag_obs, a.obs_cam, a.obs_tag, nullptr, NC, NT, WT};
+    GnSystem sys = {nullptr, nullptr, a.cam_obs, nullptr, a.ptag_obs, a.obs_cam, a.obs_tag, nullptr, NC, NT, WT};  // the pair lists
     GnLmBufs b;
     const bool robust = c.huber_px > 0;  // 0: the plain kernels
     double *seed_obs, *var, *wmin_obs = nullptr, *soft = nullptr;
@@ -483,18 +505,16 @@ static int launch_map(asl_detector *d, const MapCall &c, hipStream_t st)
     const dim3 wg(MAP_WG);
 
     range_push("map: seed");
-    HIPCHK(hipMemsetAsync(a.obs_of, 0xff, 4 * nc * nt, st));
-    hipLaunchKernelGGL(k_map_table, dim3((NM + 255) / 256), dim3(256), 0, st, a, NM, NT);
     hipLaunchKernelGGL(k_map_csr, dim3(1), wg, 0, st, a, NC, NT);
-    hipLaunchKernelGGL(k_map_chain, dim3(1), wg, 0, st, a, NC, NT, NM, WT);
+    hipLaunchKernelGGL(k_map_chain<RIG>, dim3(1), wg, 0, st, a, NC, NT, NM, WT);
     hipLaunchKernelGGL(k_map_csr, dim3(1), wg, 0, st, a, NC, NT);
     for (int sw = 0; sw < 2; sw++) {
-        hipLaunchKernelGGL(k_map_sweep_cam, dim3(NC), dim3(ASL_WAVE), loc_lds_bytes(c.max_tags), st, a, cam);
-        hipLaunchKernelGGL(k_map_sweep_tag, dim3(NT), dim3(ASL_WAVE), 0, st, a, cam);
+        hipLaunchKernelGGL(k_map_sweep_cam<RIG>, dim3(NC), dim3(ASL_WAVE), loc_lds_bytes(a.n_rig * c.max_tags), st, a, cam);
+        hipLaunchKernelGGL(k_map_sweep_tag<RIG>, dim3(NT), dim3(ASL_WAVE), 0, st, a, cam);
     }
     hipLaunchKernelGGL(k_map_gauge, dim3(1), wg, 0, st, a, NC, NT, WT);
-    hipLaunchKernelGGL(k_map_flip, dim3(NT), dim3(ASL_WAVE), 0, st, a, cam, WT);
-    hipLaunchKernelGGL(k_map_behind, dim3((NC + 63) / 64), dim3(64), 0, st, a, NC, cam.half);
+    hipLaunchKernelGGL(k_map_flip<RIG>, dim3(NT), dim3(ASL_WAVE), 0, st, a, cam, WT);
+    hipLaunchKernelGGL(k_map_behind<RIG>, dim3((NC + 63) / 64), dim3(64), 0, st, a, NC, cam.half);
     hipLaunchKernelGGL(k_map_csr, dim3(1), wg, 0, st, a, NC, NT);
     hipLaunchKernelGGL(k_map_lm_init, dim3(1), dim3(1), 0, st, (const MapHead *)a.head, lm, lm0);
     HIPCHK(hipMemsetAsync(b.flag, 0, 8, st));
@@ -502,25 +522,26 @@ static int launch_map(asl_detector *d, const MapCall &c, hipStream_t st)
 
     range_push("map: LM");
     auto lin = [&](const double *W, const double *G, double *D, int force) {
-        const auto kernel = robust ? k_map_linearize<true> : k_map_linearize<false>;
+        const auto kernel = robust ? k_map_linearize<true, RIG> : k_map_linearize<false, RIG>;
         hipLaunchKernelGGL(kernel, dim3((NM + 3) / 4), dim3(256), 0, st, a, W, G, NM, cam, D, b.cost_obs, lm, force, c.huber_px);
+        if (RIG) hipLaunchKernelGGL(k_map_fold, dim3(NM), dim3(256), 0, st, a, NM, NT, D, (const double *)lm, force);
     };
     auto decide = [&]() { hipLaunchKernelGGL(k_map_decide, dim3(1), dim3(1), 0, st, lm, b.flag); };
     auto park = [&]() {
         hipLaunchKernelGGL(k_map_park, dim3((NC + NT + 2 + 255) / 256), dim3(256), 0, st, lm, sys.cam_ptr, NC, sys.tag_ptr, NT);
     };
     HIPCHK(hipMemcpyAsync(sys.cam_ptr, a.cam_ptr, 4 * (nc + 1), hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(sys.tag_ptr, a.tag_ptr, 4 * (nt + 1), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(sys.tag_ptr, a.ptag_ptr, 4 * (nt + 1), hipMemcpyDeviceToDevice, st));
     int rc = gn_lm_run(sys, b, a.W, a.G, NM, c.max_iters, seed_obs, lin, decide, park, st);
     if (rc) return rc;
     // the final state's per-observation costs (and its blocks again, for the std)
     lin(a.W, a.G, sys.D, 1);
-    if (robust) hipLaunchKernelGGL(k_map_soft, dim3(1), dim3(256), 0, st, a, NM, cam, c.huber_px, wmin_obs, soft);
+    if (robust) hipLaunchKernelGGL(k_map_soft<RIG>, dim3(1), dim3(256), 0, st, a, NM, cam, c.huber_px, wmin_obs, soft);
     range_pop();
     if (c.tag_std) {
         GnSystem full = sys;  // undamped, over every active observation
         full.cam_ptr = a.cam_ptr;
-        full.tag_ptr = a.tag_ptr;
+        full.tag_ptr = a.ptag_ptr;
         rc = gn_factor_step(full, lm0, b.flag + 1, st);
         if (rc) return rc;
         hipLaunchKernelGGL(k_map_std, dim3(n), dim3(256), (size_t)n * sizeof(double), st, sys.S, sys.Linv, n, var);
@@ -532,18 +553,27 @@ static int launch_map(asl_detector *d, const MapCall &c, hipStream_t st)
     return ASL_OK;
 }
 
+static int launch_map(asl_detector *d, const MapCall &c, hipStream_t st)
+{
+    return is_rig(c) ? launch_map_views<true>(d, c, st) : launch_map_views<false>(d, c, st);
+}
+
 static constexpr auto map_frames_device = frames_device<MapCall, check_map_call, launch_map>;
 
+// the host forms; a rig's table is staged in solve_out too
 static int map_batch(asl_detector *d, const MapCall &c)
 {
     if (int rc = check_map_call(d, c, false)) return rc;
-    const size_t ni = (size_t)c.n_ids;
+    const bool rig = is_rig(c);
+    const size_t ni = (size_t)c.n_ids, rows = (size_t)(rig ? c.n_cams : 1) * (size_t)c.n_frames, rig_bytes = sizeof(asl_rig_camera) * (size_t)c.n_cams;
     OutPiece o[] = {{c.result, sizeof(asl_map_result)}, {c.map, sizeof(asl_map_tag) * ni}, {c.tag_std, c.tag_std ? sizeof(double) * 6 * ni : 0},
                     {c.poses, sizeof(asl_cam_pose) * (size_t)c.n_frames},
-                    {c.slot_weight, c.slot_weight ? sizeof(double) * (size_t)c.n_frames * (size_t)c.max_tags : 0}};
-    if (int rc = stage_host_call(d, "map", o, c.obs, c.n_frames, c.max_tags, nullptr, c.n_ids)) return rc;
+                    {c.slot_weight, c.slot_weight ? sizeof(double) * rows * (size_t)c.max_tags : 0}, {nullptr, rig_bytes}};
+    if (int rc = stage_host_call(d, rig ? "rig map" : "map", o, c.obs, (int)rows, c.max_tags, nullptr, c.n_ids)) return rc;
+    if (rig) HIPCHK(hipMemcpy(o[5].dev, c.rig, rig_bytes, hipMemcpyHostToDevice));
     MapCall dc = c;
     dc.obs = d->loc_obs.p; dc.result = o[0].dev; dc.map = o[1].dev; dc.tag_std = o[2].dev; dc.poses = o[3].dev; dc.slot_weight = o[4].dev;
+    dc.rig = o[5].dev;
     if (int rc = launch_map(d, dc, nullptr)) return rc;
     return fetch_out(o);
 }
@@ -552,21 +582,21 @@ extern "C" int asl_map_frames_device(asl_detector *d, const void *d_obs, int n_f
                                      int n_dist, double tag_size, int world_id, int max_iters, void *d_map, void *d_tag_std, void *d_poses,
                                      void *d_result, void *stream)
 {
-    return map_frames_device(d, {d_obs, n_frames, max_tags, n_ids, {K, dist, n_dist, tag_size}, world_id, 0.0, max_iters, d_map, d_tag_std, d_poses, d_result, nullptr}, stream);
+    return map_frames_device(d, {d_obs, 0, n_frames, max_tags, n_ids, nullptr, {K, dist, n_dist, tag_size}, world_id, 0.0, max_iters, d_map, d_tag_std, d_poses, d_result, nullptr}, stream);
 }
 
 extern "C" int asl_map_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, int n_ids, const double *K, const double *dist,
                              int n_dist, double tag_size, int world_id, int max_iters, asl_map_tag *map, double *tag_std, asl_cam_pose *poses,
                              asl_map_result *result)
 {
-    return map_batch(d, {obs, n_frames, max_tags, n_ids, {K, dist, n_dist, tag_size}, world_id, 0.0, max_iters, map, tag_std, poses, result, nullptr});
+    return map_batch(d, {obs, 0, n_frames, max_tags, n_ids, nullptr, {K, dist, n_dist, tag_size}, world_id, 0.0, max_iters, map, tag_std, poses, result, nullptr});
 }
 
 extern "C" int asl_map_robust_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, int n_ids, const double *K,
                                             const double *dist, int n_dist, double tag_size, int world_id, double huber_px, int max_iters,
                                             void *d_map, void *d_tag_std, void *d_poses, void *d_result, void *d_slot_weight, void *stream)
 {
-    return map_frames_device(d, {d_obs, n_frames, max_tags, n_ids, {K, dist, n_dist, tag_size}, world_id, huber_px, max_iters, d_map, d_tag_std, d_poses,
+    return map_frames_device(d, {d_obs, 0, n_frames, max_tags, n_ids, nullptr, {K, dist, n_dist, tag_size}, world_id, huber_px, max_iters, d_map, d_tag_std, d_poses,
                                  d_result, d_slot_weight}, stream);
 }
 
@@ -574,8 +604,24 @@ extern "C" int asl_map_robust_batch(asl_detector *d, const asl_obs *obs, int n_f
                                     int n_dist, double tag_size, int world_id, double huber_px, int max_iters, asl_map_tag *map, double *tag_std,
                                     asl_cam_pose *poses, asl_map_result *result, double *slot_weight)
 {
-    return map_batch(d, {obs, n_frames, max_tags, n_ids, {K, dist, n_dist, tag_size}, world_id, huber_px, max_iters, map, tag_std, poses, result,
+    return map_batch(d, {obs, 0, n_frames, max_tags, n_ids, nullptr, {K, dist, n_dist, tag_size}, world_id, huber_px, max_iters, map, tag_std, poses, result,
                          slot_weight});
+}
+
+extern "C" int asl_map_rig_frames_device(asl_detector *d, const void *d_obs, int n_cams, int n_frames, int max_tags, int n_ids, const void *d_rig,
+                                         double tag_size, int world_id, double rig_huber_px, int max_iters, void *d_map, void *d_tag_std,
+                                         void *d_poses, void *d_result, void *d_slot_weight, void *stream)
+{
+    return map_frames_device(d, {d_obs, n_cams, n_frames, max_tags, n_ids, d_rig, {nullptr, nullptr, 0, tag_size}, world_id, rig_huber_px, max_iters,
+                                 d_map, d_tag_std, d_poses, d_result, d_slot_weight}, stream);
+}
+
+extern "C" int asl_map_rig_batch(asl_detector *d, const asl_obs *obs, int n_cams, int n_frames, int max_tags, int n_ids, const asl_rig_camera *rig,
+                                 double tag_size, int world_id, double rig_huber_px, int max_iters, asl_map_tag *map, double *tag_std,
+                                 asl_cam_pose *poses, asl_map_result *result, double *slot_weight)
+{
+    return map_batch(d, {obs, n_cams, n_frames, max_tags, n_ids, rig, {nullptr, nullptr, 0, tag_size}, world_id, rig_huber_px, max_iters, map, tag_std,
+                         poses, result, slot_weight});
 }
 
 // ---- sequence localisation with a motion prior (k_smooth.inc)

@@ -22,7 +22,8 @@ __all__ = ["MapResult", "MAP_RESULT_DTYPE", "STATUS_OK", "STATUS_NOTHING", "STAT
 class MapResult:
     """One map solve: result (MAP_RESULT_DTYPE record), map (n_ids,) MAP_TAG_DTYPE, std (n_ids, 6) or None, poses
     (n_frames,) CAM_POSE_DTYPE; slot_weight (n_frames, max_tags) doubles or None (not computed) with slot_ids, the
-    (n_frames, max_tags) ids of the observation block the weights belong to."""
+    (n_frames, max_tags) ids of the observation block the weights belong to.  From a rig (Rig.build_map) the poses are the
+    rig's (world<-rig) and slot_weight / slot_ids are (n_cams, n_frames, max_tags)."""
 
     def __init__(self, result, map_records, tag_std, poses, slot_weight=None, slot_ids=None):
         self.result = np.asarray(result, dtype=MAP_RESULT_DTYPE).reshape(())
@@ -55,12 +56,13 @@ class MapResult:
 
     def soft_slots(self):
         """[(frame, slot, id, weight)] of every slot with a weight in (0, 1): the observations the robust loss
-        down-weighted, in (frame, slot) order; id is -1 without slot_ids"""
+        down-weighted, in (frame, slot) order; id is -1 without slot_ids.  A rig's solve (Rig.build_map) has a weight
+        block (n_cams, n_frames, max_tags) and gives [(camera, frame, slot, id, weight)] in (camera, frame, slot) order."""
         if self.slot_weight is None:
             raise ValueError("the slot weights were not computed (build_map(..., huber_px=k))")
         w = np.asarray(self.slot_weight)
-        return [(int(f), int(s), int(self.slot_ids[f, s]) if self.slot_ids is not None else -1, float(w[f, s]))
-                for f, s in np.argwhere((w > 0) & (w < 1))]
+        return [tuple(int(i) for i in k) + (int(self.slot_ids[tuple(k)]) if self.slot_ids is not None else -1, float(w[tuple(k)]))
+                for k in np.argwhere((w > 0) & (w < 1))]
 
     @property
     def tag_map(self):
@@ -76,7 +78,7 @@ class MapResult:
 
     @property
     def camera_poses(self):
-        """(n_frames, 4, 4) world<-camera; the identity where frame_status is not 0 or 4"""
+        """(n_frames, 4, 4) world<-camera (a rig's solve: world<-rig); the identity where frame_status is not 0 or 4"""
         return np.array(self.poses["T"])
 
     @property

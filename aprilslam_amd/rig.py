@@ -7,7 +7,7 @@ mounting.  A frame index is one instant for all cameras.
 
     RigCamera       one camera: K, dist (0, 4 or 5 coefficients), T_cam_rig = camera<-rig 4x4 (the mounting)
     Rig             the cameras in block order; as_records() -> RIG_CAMERA_DTYPE (asl_rig_camera), save / load,
-                    localize(), localize_sequence() / localize_sequences(), from_camera_poses()
+                    localize(), localize_sequence() / localize_sequences(), build_map(), from_camera_poses()
 
 Consecutive frames of the rig solved together under a random-walk motion prior (asl_smooth_rig_sequences_batch, k_smooth.inc):
 Rig.localize_sequence and Rig.localize_sequences return smooth.SmoothResult, its poses the rig's (world<-rig).  A frame in
@@ -104,6 +104,19 @@ class Rig:
         if o.shape[0] * o.shape[2] > MAX_SLOTS:
             raise ValueError("n_cams * max_tags must be <= %d" % MAX_SLOTS)
         return det.localize_rig(o, tag_map, self.as_records(), tag_size, max_tag_rms_px, float(sigma_px) if with_cov else None)
+
+    def build_map(self, det, obs, n_ids, tag_size, world_id=-1, max_iters=30, with_std=True, huber_px=0.0):
+        """The tag map from the rig's own frames (Detector.build_map_rig, asl_map_rig_batch): obs (n_cams, n_frames, max_tags)
+        OBS_DTYPE, camera-major, of tags with ids below n_ids at unknown poses -> mapping.MapResult: the world<-tag map (the
+        world tag world_id, default the lowest id seen, at the identity), the per-tag std and one pose per frame,
+        camera_poses = world<-rig.  Every camera's views enter one solve through the mountings, which are taken as exact, so
+        tags that no single camera sees together share one map.  huber_px > 0: a Huber loss of that many pixels on every
+        corner residual; the result's soft_slots() are then (camera, frame, slot, id, weight)."""
+        from .mapping import MapResult
+        o = self._block(obs)
+        out = det.build_map_rig(o, n_ids, self.as_records(), tag_size, world_id=world_id, max_iters=max_iters, with_std=with_std,
+                                huber_px=huber_px, with_slot_weight=bool(huber_px))
+        return MapResult(*out, slot_ids=o["id"] if huber_px else None)
 
     def _block(self, obs):
         o = np.asarray(obs)

@@ -431,6 +431,35 @@ int asl_map_robust_batch(asl_detector *det, const asl_obs *obs, int n_frames, in
                          const double *dist, int n_dist, double tag_size, int world_id, double map_huber_px, int max_iters,
                          asl_map_tag *map, double *tag_std, asl_cam_pose *poses, asl_map_result *result, double *slot_weight);
 
+/* Tag-map reconstruction from the frames of a camera rig: asl_map_robust_frames_device with the camera-major block
+   d_obs[n_cams][n_frames][max_tags] and the asl_rig_camera table of asl_localize_rig_frames_device (n_cams records, complete
+   when the call is made) in place of one camera's model.  A frame index is one instant for all cameras, the mountings are
+   taken as exact and the rig has one tag_size.  Tags that no single camera ever sees together come into one map and one
+   gauge through the rig's poses.  tests/map_rig_ref.py states the computation:
+   a view is a taking-part slot of one camera (flags & 1, 0 <= id < n_ids; a repeated id takes part once per camera, in that
+   camera's first slot; the same id in two cameras of a frame is two views), in (frame, camera, slot) order.  A frame is used
+   if its views hold >= 2 distinct ids.  The camera pose of a view is E_c (rig<-world): the seed's stages are the plain
+   call's over views, a view's PnP pose going through its camera's mounting (the rig from a view: inv(E_c) T_obs inv(G); the
+   tag from a view: inv(E_c W) T_obs), every corner costed by its own camera's model, areas in pixels as they are.  The
+   behind-camera test drops a frame left with < 2 distinct tags among its views.  The joint LM has 6 unknowns per used frame
+   (rig<-world) and per mapped tag but the world tag; all views of a (frame, tag) pair enter it.  rig_huber_px is the
+   threshold every other layer calls huber_px, with asl_map_robust_frames_device's meaning, per view; 0: the squared loss.
+   d_poses: T = world<-rig, n_tags the frame's views in the solve, n_rejected its other taking-part slots, seed_slot the
+   seeding view as the frame's global slot camera * max_tags + slot; the result's n_obs, n_obs_dropped and n_soft count
+   views, and the std's degrees of freedom are 8 views - 6 frames - 6 (tags - 1).  d_slot_weight (NULL: skipped):
+   n_cams x n_frames x max_tags doubles, camera-major like the block.
+   ASL_EINVAL, nothing written: whatever asl_map_robust_frames_device refuses; d_rig NULL; n_cams outside [1, 16];
+   n_cams * max_tags > 256; a camera with n_dist not 0, 4 or 5, a non-finite K, dist or E, or an E whose rotation is not
+   orthonormal to 1e-6 (the table is read back and checked before anything is enqueued).  Deterministic: the same input
+   gives the same bytes. */
+int asl_map_rig_frames_device(asl_detector *det, const void *d_obs, int n_cams, int n_frames, int max_tags, int n_ids,
+                              const void *d_rig, double tag_size, int world_id, double rig_huber_px, int max_iters, void *d_map,
+                              void *d_tag_std, void *d_poses, void *d_result, void *d_slot_weight, void *stream);
+/* The same computation on host records, synchronous; tag_std and slot_weight may be NULL. */
+int asl_map_rig_batch(asl_detector *det, const asl_obs *obs, int n_cams, int n_frames, int max_tags, int n_ids,
+                      const asl_rig_camera *rig, double tag_size, int world_id, double rig_huber_px, int max_iters,
+                      asl_map_tag *map, double *tag_std, asl_cam_pose *poses, asl_map_result *result, double *slot_weight);
+
 /* ---- sequence localisation: the camera poses of one camera's consecutive frames against a fixed map, solved together
    under a random-walk motion prior, so that EVERY frame gets a pose: frames without a mapped tag are carried by their
    neighbours, a single-tag frame cannot end in its mirrored planar minimum alone, and corner noise is averaged. */

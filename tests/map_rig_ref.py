@@ -1,0 +1,478 @@
+"""NumPy statement of the tag-map reconstruction from a camera rig's frames (asl_map_rig_frames_device / asl_map_rig_batch,
+aprilslam_amd/csrc/k_map.inc): map_ref.py / map_robust_ref.py over the camera table of rig_ref.RigModel.  Test
+infrastructure; what is not named here is map_ref's and map_robust_ref's.
+
+  block    obs (n_cams, n_frames, max_tags), camera-major; camera c has its model and its mounting E_c = camera_c<-rig (exact);
+           a frame index is one instant for all cameras; one tag_size.
+  view     a taking-part slot (camera c, frame f, slot s): flags & 1, 0 <= id < n_ids, and no earlier slot of the SAME camera's
+           frame took part with the id.  The same id in two cameras of a frame is two views.  Views are ordered (frame,
+           camera, slot).  A frame is used if its views hold >= 2 distinct ids (else status 1); the cameras of the joint
+           problem are the used frames, with W = rig<-world; tags are the ids seen, ascending.
+  pose     the camera pose of a view is E_c W.  The rig from a view: W = inv(E_c) T_obs inv(G); the tag from a view:
+           G = inv(E_c W) T_obs.  Every corner is costed by its own camera's model; areas are pixels as they are.
+  seeding  chain, sweeps x 2, gauge, flip and behind are map_ref's stages over views.  Chain ties: frame half (area desc, tag
+           asc, camera asc), tag half (area desc, view order).  Sweep top-8: frame half over the frame's global slots
+           g = c * max_tags + s, tag half over the list position.  Behind: a frame left with < 2 distinct tags among its
+           active views is dropped with all of them (status 3).
+  LM       6 unknowns per used frame (rig<-world) and per mapped tag but the world tag.  With p = W q the rig-frame corner,
+           the residual of a view is project_c(Re_c p + te_c) - uv and its rows are jp [-[p]x | I] and (jp R_W) [-[q]x | I]
+           with jp = J_proj Re_c.  Every view gives a 12 x 13 block [J^T J | J^T r]; the blocks of the views of one (frame,
+           tag) pair are added into the pair's first active view's in view order, and the normal equations are assembled
+           from the pairs.  The cost is per view.  huber_px = k > 0: map_robust_ref's rule on each view's raw residual.
+  std      map_robust_ref's, with dof 8 views - 6 frames - 6 (tags - 1) (k > 0: 2 n_in - ...).
+  records  per frame T = world<-rig, n_tags = active views, n_rejected = taking-part - active, seed_slot = the chain's view
+           as a global slot; the result's n_obs counts views; slot_weight is (n_cams, n_frames, max_tags).
+
+reverse (a rounding perturbation for the tests): the LM's sums run over the views in reversed order.
+trace (a dict, optional) receives "margin" (map_robust_ref's), "flipped", "views" and "pairs" (the LM's counts) and
+"decreases", the relative cost decrease of every accepted trial.
+"""
+import numpy as np
+from scipy.linalg import solve_triangular
+
+import localize_ref as LR
+import rig_ref
+from aprilslam_amd._lib import CAM_POSE_DTYPE, MAP_RESULT_DTYPE, MAP_TAG_DTYPE
+from map_ref import BEHIND_MARGIN, MAX_CAND, MAX_MAP_TAGS, SWEEPS, gn_oracle, inv, mirror4, obj3, rec4
+
+
+def mountings(table):
+    """(n_cams, 4, 4) camera<-rig"""
+    E = np.tile(np.eye(4), (len(table), 1, 1))
+    for c, (_, Re, te) in enumerate(table):
+        E[c, :3, :3], E[c, :3, 3] = Re, te
+    return E
+
+
+def project_views(table, pc, P, jac=False):
+    """the points P (n, 3), each in the frame of its camera pc (n,): (uv (n, 2), J (n, 2, 3), in front (n,)); rows with
+    z <= Z_MIN come back as zeros"""
+    ok = P[:, 2] > LR.Z_MIN
+    uv, J = np.zeros((len(P), 2)), np.zeros((len(P), 2, 3))
+    for c, (cam, _, _) in enumerate(table):
+        m = ok & (pc == c)
+        if not m.any():
+            continue
+        if jac:
+            uv[m], J[m] = LR.project(cam, P[m], jac=True)
+        else:
+            uv[m] = LR.project(cam, P[m])
+    return uv, J, ok
+
+
+def corner_terms(table, vc, Wv, G, uv, h, k):
+    """per corner of n views (vc (n,) their cameras, Wv (n, 4, 4) camera<-world, G (n, 4, 4) world<-tag, uv (n, 4, 2)):
+    (cost, weight, over, s, in front), each (n, 4); k = 0: the squared loss"""
+    Xw = np.einsum('nij,kj->nki', G[:, :3, :3], obj3(h)) + G[:, None, :3, 3]
+    P = (np.einsum('nij,nkj->nki', Wv[:, :3, :3], Xw) + Wv[:, None, :3, 3]).reshape(-1, 3)
+    pr, _, ok = project_views(table, np.repeat(vc, 4), P)
+    r = (pr - uv.reshape(-1, 2)) * ok[:, None]
+    e = r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1]
+    s = np.sqrt(e)
+    over = ok & (s > k) if k > 0 else np.zeros(len(P), dtype=bool)
+    w = np.ones(len(P))
+    w[over] = k / s[over]
+    rho = np.where(over, 2.0 * k * s - k * k, e)
+    rho[~ok] = LR.BEHIND_COST
+    sh = (len(vc), 4)
+    return rho.reshape(sh), w.reshape(sh), over.reshape(sh), s.reshape(sh), ok.reshape(sh)
+
+
+def view_costs(table, vc, Wv, G, uv, h, k=0.0):
+    """(n,) cost of each view"""
+    return corner_terms(table, vc, Wv, G, uv, h, k)[0].sum(axis=1)
+
+
+def margin(s, ok, k):
+    return float(np.abs(s[ok] - k).min()) if ok.any() else np.inf
+
+
+def tag_lm(table, vcs, G, Wvs, uvs, h):
+    """map_ref.tag_lm with every view's own camera: pose-only LM of world<-tag G, the view cameras Wvs (camera<-world) held"""
+    X = obj3(h)
+    Wa, uva, pc = np.stack(Wvs), np.stack(uvs), np.repeat(np.asarray(vcs), 4)
+    n = len(Wa)
+
+    def lin(R, t, want):
+        Xw = X @ R.T + t
+        P = (np.einsum('nij,kj->nki', Wa[:, :3, :3], Xw) + Wa[:, None, :3, 3]).reshape(-1, 3)
+        pr, Jp, ok = project_views(table, pc, P, jac=want)
+        r = (pr - uva.reshape(-1, 2))[ok]
+        cost = LR.BEHIND_COST * float((~ok).sum()) + float((r * r).sum())
+        if not want:
+            return cost, None, None
+        H, g = np.zeros((6, 6)), np.zeros(6)
+        if ok.any():
+            a = np.einsum('nri,nij->nrj', Jp[ok], np.repeat(Wa[:, :3, :3], 4, axis=0)[ok])    # d uv / d Xw
+            Xq = np.tile(Xw, (n, 1))[ok]
+            J = np.concatenate([np.cross(Xq[:, None, :], a), a], axis=2).reshape(-1, 6)
+            H = J.T @ J
+            g = J.T @ r.reshape(-1)
+        return cost, H, g
+
+    R, t, cost = LR.lm(lin, G[:3, :3], G[:3, 3])
+    out = G.copy()
+    out[:3, :3], out[:3, 3] = R, t
+    return out, cost
+
+
+def view_blocks(table, W, G, oc, ot, ovc, uv, h, k=0.0, trace=None):
+    """per view (frame oc, tag ot, camera ovc; W (NC, 4, 4) rig<-world, G (NT, 4, 4)): its cost (M,) and its 12 x 13 block
+    [J^T J | J^T r] (M, 12, 13), J = [frame | tag], the rows weighted under the loss"""
+    X = obj3(h)
+    M = len(oc)
+    q = np.einsum('mij,kj->mki', G[ot][:, :3, :3], X) + G[ot][:, None, :3, 3]                 # (M, 4, 3) world
+    p = np.einsum('mij,mkj->mki', W[oc][:, :3, :3], q) + W[oc][:, None, :3, 3]                 # (M, 4, 3) rig
+    Re = np.stack([table[c][1] for c in ovc]) if M else np.zeros((0, 3, 3))
+    te = np.stack([table[c][2] for c in ovc]) if M else np.zeros((0, 3))
+    P = np.einsum('mij,mkj->mki', Re, p) + te[:, None, :]                                      # (M, 4, 3) camera
+    pr, Jp, ok = project_views(table, np.repeat(ovc, 4), P.reshape(-1, 3), jac=True)
+    r = (pr - uv.reshape(-1, 2)) * ok[:, None]
+    e = r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1]
+    s = np.sqrt(e)
+    over = ok & (s > k) if k > 0 else np.zeros(len(s), dtype=bool)
+    w = np.ones(len(s))
+    w[over] = k / s[over]
+    rho = np.where(over, 2.0 * k * s - k * k, e)
+    rho[~ok] = LR.BEHIND_COST
+    if trace is not None and k > 0:
+        trace["margin"] = min(trace.get("margin", np.inf), margin(s, ok, k))
+    sw = np.sqrt(w)
+    jp = np.einsum('nri,nij->nrj', Jp, np.repeat(Re, 4, axis=0)) * (ok * sw)[:, None, None]   # J_proj Re
+    r = r * sw[:, None]
+    pf, qf = p.reshape(-1, 3), q.reshape(-1, 3)
+    Jc = np.concatenate([np.cross(pf[:, None, :], jp), jp], axis=2)                            # jp [-[p]x | I]
+    a = np.einsum('nri,nij->nrj', jp, np.repeat(W[oc][:, :3, :3], 4, axis=0))
+    Jt = np.concatenate([np.cross(qf[:, None, :], a), a], axis=2)
+    J = np.concatenate([Jc.reshape(M, 8, 6), Jt.reshape(M, 8, 6), r.reshape(M, 8, 1)], axis=2)  # (M, 8, 13)
+    return rho.reshape(M, 4).sum(axis=1), np.einsum('mri,mrj->mij', J[:, :, :12], J)
+
+
+def fold_pairs(B, oc, ot):
+    """the blocks of the views of one (frame, tag) pair added into the pair's first view's, in the order given:
+    (blocks (P, 12, 13), indices (P,) of the first views)"""
+    first, heads = {}, []
+    out = []
+    for m in range(len(oc)):
+        key = (int(oc[m]), int(ot[m]))
+        if key in first:
+            out[first[key]] = out[first[key]] + B[m]
+        else:
+            first[key] = len(heads)
+            heads.append(m)
+            out.append(B[m].copy())
+    return (np.stack(out) if out else np.zeros((0, 12, 13))), np.array(heads, dtype=np.int64)
+
+
+def assemble(B, oc, ot, cam_col, tag_col, n_par):
+    """H, g from the blocks B of observations (frame oc, tag ot): cam_col[c] / tag_col[j] = first column or -1 (held)"""
+    ccol, tcol = cam_col[oc], tag_col[ot]
+    H, g = np.zeros((n_par, n_par)), np.zeros(n_par)
+    i6 = np.arange(6)
+
+    def add(rc, cc, blk, sel):
+        if sel.any():
+            np.add.at(H, (rc[sel][:, None, None] + i6[None, :, None], cc[sel][:, None, None] + i6[None, None, :]), blk[sel])
+
+    cm, tm = ccol >= 0, tcol >= 0
+    add(ccol, ccol, B[:, :6, :6], cm)
+    add(tcol, tcol, B[:, 6:12, 6:12], tm)
+    add(ccol, tcol, B[:, :6, 6:12], cm & tm)
+    add(tcol, ccol, B[:, 6:12, :6], cm & tm)
+    if cm.any():
+        np.add.at(g, ccol[cm][:, None] + i6, B[:, :6, 12][cm])
+    if tm.any():
+        np.add.at(g, tcol[tm][:, None] + i6, B[:, 6:12, 12][tm])
+    return H, g
+
+
+def joint_linearise(table, W, G, oc, ot, ovc, uv, h, cam_col, tag_col, n_par, k=0.0, trace=None, fold=True):
+    """(cost, H, g) of the joint problem over the views given; fold False: every view its own observation"""
+    cost_v, B = view_blocks(table, W, G, oc, ot, ovc, uv, h, k, trace)
+    if fold:
+        B, heads = fold_pairs(B, oc, ot)
+        oc, ot = oc[heads], ot[heads]
+        if trace is not None:
+            trace["views"], trace["pairs"] = len(cost_v), len(heads)
+    H, g = assemble(B, oc, ot, cam_col, tag_col, n_par)
+    return float(cost_v.sum()), H, g
+
+
+def map_frames(obs, n_ids, rig, tag_size, world_id=-1, huber_px=0.0, max_iters=30, with_std=True, trace=None, reverse=False):
+    """(result MAP_RESULT_DTYPE record, map (n_ids,) MAP_TAG_DTYPE, tag_std (n_ids, 6), poses (n_frames,) CAM_POSE_DTYPE with
+    T = world<-rig, slot_weight (n_cams, n_frames, max_tags))"""
+    k = float(huber_px)
+    if not (k >= 0 and np.isfinite(k)):
+        raise ValueError("huber_px must be >= 0 and finite")
+    obs = np.asarray(obs)
+    C, F, S = obs.shape
+    table = rig_ref.rig_table(rig)
+    assert len(table) == C
+    E = mountings(table)
+    h = LR.half_size(tag_size)
+    res = np.zeros((), dtype=MAP_RESULT_DTYPE)
+    out_map = np.zeros(n_ids, dtype=MAP_TAG_DTYPE)
+    tag_std = np.zeros((n_ids, 6))
+    poses = np.zeros(F, dtype=CAM_POSE_DTYPE)
+    poses["T"] = np.eye(4)
+    poses["seed_slot"] = -1
+    poses["status"] = 1
+    slot_weight = np.zeros((C, F, S))
+
+    # gather
+    part = np.zeros((C, F, S), dtype=bool)
+    for c in range(C):
+        for f in range(F):
+            seen = set()
+            for s in range(S):
+                i, fl = int(obs["id"][c, f, s]), int(obs["flags"][c, f, s])
+                if (fl & 1) and 0 <= i < n_ids and i not in seen:
+                    part[c, f, s] = True
+                    seen.add(i)
+    npart = part.sum(axis=(0, 2))
+    ndist = [len({int(i) for i in obs["id"][:, f][part[:, f]]}) for f in range(F)]
+    frames = [f for f in range(F) if ndist[f] >= 2]
+    ids = sorted({int(i) for f in frames for i in obs["id"][:, f][part[:, f]]})
+    tag_of = {i: j for j, i in enumerate(ids)}
+    ob = [(n, tag_of[int(obs["id"][c, f, s])], f, c, s) for n, f in enumerate(frames) for c in range(C) for s in range(S) if part[c, f, s]]
+    oc = np.array([o[0] for o in ob], dtype=np.int64)
+    ot = np.array([o[1] for o in ob], dtype=np.int64)
+    ofr = np.array([o[2] for o in ob], dtype=np.int64)
+    ovc = np.array([o[3] for o in ob], dtype=np.int64)
+    osl = np.array([o[4] for o in ob], dtype=np.int64)
+    M, NC, NT = len(ob), len(frames), len(ids)
+    if world_id < 0:
+        world_id = ids[0] if ids else -1
+    res["world_id"] = world_id
+    res["n_obs_dropped"] = M
+    if world_id not in tag_of:
+        res["status"] = 1
+        for f in frames:
+            poses["status"][f] = 5
+            poses["n_rejected"][f] = npart[f]
+        return res, out_map, tag_std, poses, slot_weight
+    if NT > MAX_MAP_TAGS:
+        raise ValueError("more than %d tags" % MAX_MAP_TAGS)
+    wt = tag_of[world_id]
+    rec = [obs[c, f, s] for c, f, s in zip(ovc, ofr, osl)]
+    uv = np.stack([r["corners"].astype(np.float64).reshape(4, 2) for r in rec]) if M else np.zeros((0, 4, 2))
+    To = [rec4(r["T"]) for r in rec]
+    seedable = np.array([bool(r["flags"] & 2) for r in rec], dtype=bool)
+    area = np.array([LR.corner_area(r["corners"]) for r in rec])
+    by_cam = [np.flatnonzero(oc == c) for c in range(NC)]
+    by_tag = [np.flatnonzero(ot == j) for j in range(NT)]
+    Ev, Evi = E[ovc] if M else np.zeros((0, 4, 4)), np.array([inv(E[c]) for c in ovc]) if M else np.zeros((0, 4, 4))
+
+    def Wview(Wx, ms):
+        """camera<-world of the views ms"""
+        return Ev[ms] @ Wx[oc[ms]]
+
+    # chain
+    W = np.tile(np.eye(4), (NC, 1, 1))
+    G = np.tile(np.eye(4), (NT, 1, 1))
+    cplaced = np.zeros(NC, dtype=bool)
+    tplaced = np.zeros(NT, dtype=bool)
+    tplaced[wt] = True
+    seed_slot = np.full(NC, -1)
+    changed = True
+    while changed:
+        changed = False
+        for c in range(NC):
+            if cplaced[c]:
+                continue
+            cand = [m for m in by_cam[c] if seedable[m] and tplaced[ot[m]]]
+            if cand:
+                m = min(cand, key=lambda m: (-area[m], ot[m], ovc[m]))
+                W[c] = Evi[m] @ (To[m] @ inv(G[ot[m]]))
+                cplaced[c] = True
+                seed_slot[c] = ovc[m] * S + osl[m]
+                changed = True
+        for j in range(NT):
+            if tplaced[j]:
+                continue
+            cand = [m for m in by_tag[j] if seedable[m] and cplaced[oc[m]]]
+            if cand:
+                m = min(cand, key=lambda m: (-area[m], m))
+                G[j] = inv(Ev[m] @ W[oc[m]]) @ To[m]
+                tplaced[j] = True
+                changed = True
+    act = cplaced[oc] & tplaced[ot] if M else np.zeros(0, dtype=bool)
+
+    # sweeps
+    for _ in range(SWEEPS):
+        Wn = W.copy()
+        for c in range(NC):
+            ms = [m for m in by_cam[c] if act[m]]
+            if not cplaced[c] or not ms:
+                continue
+            cands = [W[c]]
+            sm = [m for m in ms if seedable[m]]
+            for kk in LR.top_k([area[m] for m in sm], MAX_CAND):
+                m = sm[kk]
+                cands += [Evi[m] @ (To[m] @ inv(G[ot[m]])), Evi[m] @ (mirror4(To[m]) @ inv(G[ot[m]]))]
+            Gm, uvm = G[ot[ms]], uv[ms]
+            costs = [float(view_costs(table, ovc[ms], Ev[ms] @ Tc[None], Gm, uvm, h).sum()) for Tc in cands]
+            Wn[c] = cands[int(np.argmin(costs))]
+        W = Wn
+        Gn = G.copy()
+        for j in range(NT):
+            ms = [m for m in by_tag[j] if act[m]]
+            if not tplaced[j] or not ms:
+                continue
+            cands = [G[j]]
+            sm = [m for m in ms if seedable[m]]
+            for kk in LR.top_k([area[m] for m in sm], MAX_CAND):
+                m = sm[kk]
+                Wi = inv(Ev[m] @ W[oc[m]])
+                cands += [Wi @ To[m], Wi @ mirror4(To[m])]
+            Wm, uvm = Wview(W, ms), uv[ms]
+            costs = [float(view_costs(table, ovc[ms], Wm, np.broadcast_to(Tg, (len(ms), 4, 4)), uvm, h).sum()) for Tg in cands]
+            Gn[j] = cands[int(np.argmin(costs))]
+        G = Gn
+    Gw = G[wt].copy()
+    Mi = inv(Gw)
+    W = W @ Gw[None]
+    G = Mi[None] @ G
+    G[wt] = np.eye(4)
+
+    # flip test
+    for j in range(NT):
+        ms = [m for m in by_tag[j] if act[m]]
+        if j == wt or not ms:
+            continue
+        Ws, uvs = list(Wview(W, ms)), [uv[m] for m in ms]
+        T0, c0 = tag_lm(table, ovc[ms], G[j], Ws, uvs, h)
+        big = min(range(len(ms)), key=lambda kk: (-area[ms[kk]], kk))
+        Wb = Ws[big]
+        T1, c1 = tag_lm(table, ovc[ms], inv(Wb) @ mirror4(Wb @ G[j]), Ws, uvs, h)
+        G[j] = T1 if c1 < c0 else T0
+        if trace is not None and c1 < c0:
+            trace.setdefault("flipped", []).append(ids[j])
+
+    # behind the camera, dropped frames, mapped tags
+    X = obj3(h)
+    for m in range(M):
+        if act[m]:
+            Wv = Ev[m] @ W[oc[m]]
+            Pm = (X @ G[ot[m]][:3, :3].T + G[ot[m]][:3, 3]) @ Wv[:3, :3].T + Wv[:3, 3]
+            act[m] = bool((Pm[:, 2] > BEHIND_MARGIN).all())
+    cstat = np.where(cplaced, 0, 5)
+    for c in range(NC):
+        if cplaced[c] and len({int(ot[m]) for m in by_cam[c] if act[m]}) < 2:
+            cstat[c] = 3
+            act[by_cam[c]] = False
+    mapped = np.array([j == wt or act[by_tag[j]].any() for j in range(NT)], dtype=bool)
+    n_obs = int(act.sum())
+
+    # the joint LM
+    status = 0
+    cost0 = cost = 0.0
+    it = 0
+    n_soft = 0
+    cams_used = [c for c in range(NC) if cstat[c] == 0]
+    free_tags = [j for j in range(NT) if mapped[j] and j != wt]
+    if n_obs == 0:
+        status = 1
+    else:
+        cam_col = np.full(NC, -1)
+        tag_col = np.full(NT, -1)
+        for i, c in enumerate(cams_used):
+            cam_col[c] = 6 * i
+        for i, j in enumerate(free_tags):
+            tag_col[j] = 6 * (len(cams_used) + i)
+        npar = 6 * (len(cams_used) + len(free_tags))
+        a = np.flatnonzero(act)
+        if reverse:
+            a = a[::-1]
+
+        def lin(Wx, Gx):
+            return joint_linearise(table, Wx, Gx, oc[a], ot[a], ovc[a], uv[a], h, cam_col, tag_col, npar, k, trace)
+
+        allv = np.arange(M)
+        seed_obs = view_costs(table, ovc, Wview(W, allv), G[ot], uv, h, k)
+        cost, H, g = lin(W, G)
+        cost0 = cost
+        lam = 1e-3
+        while it < max_iters:
+            it += 1
+            A = H.copy()
+            A[np.diag_indices(npar)] += lam * np.maximum(np.diag(H), 1e-12)
+            try:
+                L = np.linalg.cholesky(A)
+            except np.linalg.LinAlgError:
+                status = 2
+                break
+            d = solve_triangular(L, solve_triangular(L, -g, lower=True), lower=True, trans='T')
+            Wn, Gn = W.copy(), G.copy()
+            for c in cams_used:
+                Wn[c] = gn_oracle.apply_update(W[c], d[cam_col[c]:cam_col[c] + 6])
+            for j in free_tags:
+                Gn[j] = gn_oracle.apply_update(G[j], d[tag_col[j]:tag_col[j] + 6])
+            cn, Hn, gn = lin(Wn, Gn)
+            if cn < cost:
+                stop = cost - cn < 1e-12 * cost
+                if trace is not None:
+                    trace.setdefault("decreases", []).append((cost - cn) / cost)
+                W, G, cost, H, g = Wn, Gn, cn, Hn, gn
+                lam = max(lam * 0.1, 1e-12)
+                if stop:
+                    break
+            else:
+                lam *= 10
+        if status == 0 and not np.isfinite(cost):
+            status = 3
+        if k > 0:
+            rho, w, over, s, ok = corner_terms(table, ovc, Wview(W, allv), G[ot], uv, h, k)
+        if status == 0 and k > 0:
+            wmin = w.min(axis=1)
+            n_soft = int((over.any(axis=1) & act).sum())
+            slot_weight[ovc[act], ofr[act], osl[act]] = wmin[act]
+            if trace is not None:
+                trace["margin"] = min(trace.get("margin", np.inf), margin(s[act], ok[act], k))
+        elif status == 0:
+            slot_weight[ovc[act], ofr[act], osl[act]] = 1.0
+        if status == 0 and with_std:
+            if k > 0:
+                inl = ~over[act]
+                n_in = int(inl.sum())
+                dof = 2 * n_in - 6 * len(cams_used) - 6 * len(free_tags)
+                s2 = float(np.where(ok[act], s[act] * s[act], LR.BEHIND_COST)[inl].sum()) / dof if dof > 0 else 0.0
+            else:
+                dof = 8 * n_obs - 6 * len(cams_used) - 6 * len(free_tags)
+                s2 = cost / dof if dof > 0 else 0.0
+            Li = solve_triangular(np.linalg.cholesky(H), np.eye(npar), lower=True)    # diag(H^-1)_i = |L^-1 e_i|^2
+            Hid = (Li * Li).sum(axis=0)
+            for j in free_tags:
+                tag_std[ids[j]] = np.sqrt(s2 * Hid[tag_col[j]:tag_col[j] + 6])
+        fin = view_costs(table, ovc, Wview(W, allv), G[ot], uv, h, k)
+
+    # records
+    for c, f in enumerate(frames):
+        na = int(act[by_cam[c]].sum())
+        st = int(cstat[c])
+        if st == 0 and status != 0:
+            st = 4
+        poses["status"][f] = st
+        poses["seed_slot"][f] = seed_slot[c]
+        poses["n_tags"][f] = na if st in (0, 4) else 0
+        poses["n_rejected"][f] = npart[f] - (na if st in (0, 4) else 0)
+        if st in (0, 4):
+            poses["T"][f] = inv(W[c])
+            if na and n_obs:
+                poses["rms_px"][f] = np.sqrt(sum(fin[m] for m in by_cam[c] if act[m]) / (4.0 * na))
+                poses["rms_seed_px"][f] = np.sqrt(sum(seed_obs[m] for m in by_cam[c] if act[m]) / (4.0 * na))
+    for j in range(NT):
+        if mapped[j] and status == 0:
+            out_map["T"][ids[j]] = G[j][:3].ravel()
+            out_map["valid"][ids[j]] = 1
+    res["cost_seed"], res["cost"] = cost0, cost
+    if n_obs:
+        res["rms_px"], res["rms_seed_px"] = np.sqrt(cost / (4.0 * n_obs)), np.sqrt(cost0 / (4.0 * n_obs))
+    res["n_frames_used"] = len(cams_used) if status == 0 else 0
+    res["n_tags"] = int(mapped.sum()) if status == 0 else 0
+    res["n_obs"] = n_obs
+    res["n_obs_dropped"] = M - n_obs
+    res["iterations"] = it
+    res["status"] = status
+    res["n_soft"] = n_soft
+    return res, out_map, tag_std, poses, slot_weight

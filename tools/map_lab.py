@@ -10,6 +10,12 @@ plain and the robust leg alternate, rep by rep, and each reports its map errors 
 total ms and ms per trial, and the robust leg its soft slots.
 
     python tools/map_lab.py --huber 1.0 --outliers 8 [--iters 60]
+
+With --rig C the rig solve (asl_map_rig_frames_device) of a ring of C cameras (smooth_rig_cases.ring) along the bench trajectory
+is measured against the single-camera solve of the ring's camera 0 on the same frames, the two legs alternating rep by rep:
+views, pairs, trials, median ms and the map errors against the truth.
+
+    python tools/map_lab.py --rig 2 [--frames 256] [--huber 1.0]
 """
 import argparse
 import json
@@ -127,6 +133,60 @@ def robust_lab(det, a):
     return r
 
 
+def rig_lab(det, a):
+    """the rig leg and the single-camera leg (the rig's camera 0) on the bench scene, alternating"""
+    import torch
+    import map_rig_cases as GC
+    import rig_cases as RC
+    import smooth_rig_cases as SRC
+    dev = torch.device("cuda:0")
+    rig = SRC.ring(a.rig) if a.rig > 1 else GC.Rig([GC.RigCamera(RC.K45, None, np.eye(4))])
+    mt = min(24, 256 // a.rig)
+    poses = GC.bench_poses(a.frames, a.frames)
+    obs = GC.add_noise(RC.exact_block(GC.scene(), rig, poses, GC.TAG, mt, pnp_seed=None), 0.3, 7)
+    nc, n, _ = obs.shape
+    n_ids = GC.N_IDS
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1)).to(dev)
+    d_obs, d_one, d_rig = up(obs), up(obs[0]), up(rig.as_records())
+    d_map = torch.empty((n_ids, _lib.MAP_TAG_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    d_std = torch.empty((n_ids, 6), dtype=torch.float64, device=dev)
+    d_poses = torch.empty((n, _lib.CAM_POSE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    d_res = torch.empty((64,), dtype=torch.uint8, device=dev)
+    s = torch.cuda.Stream(dev)
+    cam0 = rig.cameras[0]
+    outs = (d_map.data_ptr(), d_std.data_ptr(), d_poses.data_ptr(), d_res.data_ptr())
+    legs = {"rig": lambda: det.build_map_rig_device(d_obs.data_ptr(), nc, n, mt, n_ids, d_rig.data_ptr(), GC.TAG, *outs, max_iters=a.iters,
+                                                    stream=s.cuda_stream, huber_px=a.huber),
+            "camera0": lambda: det.build_map_device(d_one.data_ptr(), n, mt, n_ids, cam0.K, None, GC.TAG, *outs, max_iters=a.iters,
+                                                    stream=s.cuda_stream, huber_px=a.huber)}
+    ms = {k: [] for k in legs}
+    out = {}
+    for r in range(a.reps + 2):
+        for leg, call in legs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(s)
+            call()
+            e1.record(s)
+            s.synchronize()
+            if r >= 2:
+                ms[leg].append(e0.elapsed_time(e1))
+            if r == a.reps + 1:
+                res = d_res.cpu().numpy().view(_lib.MAP_RESULT_DTYPE).reshape(())
+                tmap = d_map.cpu().numpy().view(_lib.MAP_TAG_DTYPE).reshape(n_ids)
+                pr = d_poses.cpu().numpy().view(_lib.CAM_POSE_DTYPE).reshape(n)
+                truth = poses if leg == "rig" else [T @ np.linalg.inv(cam0.T_cam_rig) for T in poses]
+                et, er, ec = GC.truth_errors((res, tmap, None, pr), truth)
+                out[leg] = dict(status=int(res["status"]), tags=int(res["n_tags"]), views=int(res["n_obs"]), trials=int(res["iterations"]),
+                                rms_px=float(res["rms_px"]), tag_err=et, tag_rot_err=er, pose_err=ec, n_soft=int(res["n_soft"]))
+    for leg in legs:
+        out[leg]["ms"] = float(np.median(ms[leg]))
+        out[leg]["ms_spread"] = [float(min(ms[leg])), float(max(ms[leg]))]
+    views, pairs = GC.view_counts(obs)
+    r = dict(cameras=nc, frames=n, max_tags=mt, views=views, pairs=pairs, huber_px=a.huber, max_iters=a.iters, **out)
+    print("rig_lab", json.dumps(r), flush=True)
+    return r
+
+
 def time_host(det, obs, K, iters):
     t0 = time.perf_counter()
     frames = [[(int(o["id"]), MR.rec4(o["T"]), o["corners"].astype(np.float64).reshape(4, 2)) for o in fr if o["flags"] & 1 and o["id"] >= 0]
@@ -177,8 +237,16 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--huber", type=float, default=0.0, help="huber_px of the robust leg; > 0 runs the plain / robust comparison alone")
     ap.add_argument("--outliers", type=int, default=0, help="slots given their neighbour slot's corners")
+    ap.add_argument("--rig", type=int, default=0, help="cameras of the rig; > 0 runs the rig / single-camera comparison alone")
     a = ap.parse_args()
     det = _lib.Detector("tagStandard41h12", id_limit=0)
+    if a.rig > 0:
+        r = rig_lab(det, a)
+        det.close()
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(r, f, indent=1)
+        return
     if a.huber > 0:
         r = robust_lab(det, a)
         det.close()
