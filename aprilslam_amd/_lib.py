@@ -20,7 +20,7 @@ assert OBS_DTYPE.itemsize == 136
 DET_DTYPE = np.dtype([("id", "<i4"), ("hamming", "<i4"), ("margin", "<f4"), ("frame", "<i4"),
                       ("center", "<f8", (2,)), ("corners", "<f8", (4, 2))])
 POSE_DTYPE = np.dtype([("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)), ("T", "<f8", (4, 4)), ("ok", "<i4"), ("reserved", "<i4")])
-MAP_TAG_DTYPE = np.dtype([("T", "<f8", (12,)), ("valid", "<i4"), ("reserved", "<i4")])  # asl_map_tag
+MAP_TAG_DTYPE = np.dtype([("T", "<f8", (12,)), ("valid", "<i4"), ("size", "<f4")])  # asl_map_tag; size 0: the call's tag_size
 CAM_POSE_DTYPE = np.dtype([("T", "<f8", (4, 4)), ("rms_px", "<f8"), ("rms_seed_px", "<f8"), ("n_tags", "<i4"), ("n_rejected", "<i4"),
                            ("status", "<i4"), ("seed_slot", "<i4")])  # asl_cam_pose
 CALIB_RESULT_DTYPE = np.dtype([("K", "<f8", (3, 3)), ("dist", "<f8", (5,)), ("std", "<f8", (9,)), ("rms_px", "<f8"),
@@ -424,7 +424,8 @@ class Detector:
         """asl_localize_batch: host records obs (n_frames, max_tags) OBS_DTYPE (e.g. dist.pack_observations) against
         tag_map (n_ids,) MAP_TAG_DTYPE (or a localize.TagMap) -> (n_frames,) CAM_POSE_DTYPE, world<-camera per frame.
         sigma_px not None: asl_localize_cov_batch -> (poses, (n_frames,) POSE_COV_DTYPE), the covariance scaled by that
-        corner sigma, or by the solve's own estimate for 0."""
+        corner sigma, or by the solve's own estimate for 0.
+        tag_size is the size of the map entries whose size is 0; an entry with a size of its own (TagMap.set_size) is solved at it."""
         o, m = _obs_records(obs), _map_records(tag_map)
         keep, Kp, dpp, nd = _camera(K, dist, square=True)
         out = np.zeros(o.shape[0], dtype=CAM_POSE_DTYPE)
@@ -451,7 +452,8 @@ class Detector:
     def localize_rig(self, obs, tag_map, rig, tag_size, max_tag_rms_px=0.0, sigma_px=None):
         """asl_localize_rig_batch: host records obs (n_cams, n_frames, max_tags) OBS_DTYPE, camera-major, against tag_map and
         the camera table rig ((n_cams,) RIG_CAMERA_DTYPE, or a rig.Rig) -> (n_frames,) CAM_POSE_DTYPE, world<-rig per frame.
-        sigma_px not None: asl_localize_rig_cov_batch -> (poses, (n_frames,) POSE_COV_DTYPE), as localize."""
+        sigma_px not None: asl_localize_rig_cov_batch -> (poses, (n_frames,) POSE_COV_DTYPE), as localize.
+        tag_size is the size of the map entries whose size is 0, as in localize."""
         o = np.ascontiguousarray(obs, dtype=OBS_DTYPE)
         if o.ndim != 3:
             raise ValueError("obs must be (n_cams, n_frames, max_tags) asl_obs records")
@@ -513,7 +515,8 @@ class Detector:
 
     def calibrate(self, obs, tag_map, tag_size, width, height, K_init=None, n_dist=5, flags=0, max_iters=30):
         """asl_calibrate_batch: host records obs (n_frames, max_tags) OBS_DTYPE of a target whose tag poses tag_map
-        ((n_ids,) MAP_TAG_DTYPE or a localize.TagMap) gives -> (CALIB_RESULT_DTYPE record, (n_frames,) CAM_POSE_DTYPE)."""
+        ((n_ids,) MAP_TAG_DTYPE or a localize.TagMap) gives -> (CALIB_RESULT_DTYPE record, (n_frames,) CAM_POSE_DTYPE).
+        tag_size is the size of the map entries whose size is 0: a target may mix tags of several sizes (TagMap.set_size)."""
         o, m = _obs_records(obs), _map_records(tag_map)
         keep, Kp = self._calib_args(K_init, n_dist)
         res = np.zeros((), dtype=CALIB_RESULT_DTYPE)
@@ -612,7 +615,8 @@ class Detector:
         corner's residual; a frame's n_rejected and the result's n_soft count the slots it down-weighted.  0.0: the calls above.
         times: (n_frames,) float64, strictly increasing, any unit -- asl_smooth_timed_sequences_batch with the one sequence:
         sigma_rot and sigma_trans are per unit of that time, a pair of frames dt apart is held by the prior / sqrt(dt).  Bad
-        times (not finite, not increasing) give result status 4, no error.  None: one frame step is one unit, the calls above."""
+        times (not finite, not increasing) give result status 4, no error.  None: one frame step is one unit, the calls above.
+        tag_size is the size of the map entries whose size is 0, as in localize; so it is in smooth_sequences and smooth_rig."""
         return self._smooth_host(obs, None, tag_map, K, dist, tag_size, (sigma_px, sigma_rot, sigma_trans), max_iters, seed, with_cov, huber_px,
                                  times)
 

@@ -292,7 +292,8 @@ __global__ void __launch_bounds__(64) k_calib_init(CalibArgs a)
     int npart = 0;
     for (int k = lane; k < a.max_tags; k += ASL_WAVE) {
         const int id = fo[k].id, fl = fo[k].flags;
-        if (!((fl & 1) && id >= 0 && id < a.n_ids && a.map[id].valid)) continue;
+        double hs = a.half;
+        if (!((fl & 1) && id >= 0 && id < a.n_ids && map_tag_half(a.map[id], hs))) continue;
         npart++;
         if (a.has_init) continue;
         float cf[8];
@@ -395,7 +396,9 @@ __global__ void __launch_bounds__(64) k_calib_seed(CalibArgs a)
     auto make = [&](int k) {
         double H[9], To[12], M[12];
         cal_square_h(fo[k].corners, th[2], th[3], s, H);
-        cal_planar_pose(H, th[0], th[1], s, a.half, To);
+        double hs = a.half;
+        map_tag_half(a.map[fo[k].id], hs);  // the slot's own half
+        cal_planar_pose(H, th[0], th[1], s, hs, To);
         const double *Mp = a.map[fo[k].id].T;
 #pragma unroll
         for (int i = 0; i < 12; i++) M[i] = Mp[i];

@@ -3,8 +3,10 @@
 // (corner c = 4 * slot + q on lane c % 64); every pass over the corners ends in a butterfly sum over the wave
 // (butterfly_sum, k_wave.inc: every lane then holds the same bits), so the small serial parts (candidate choice, 6x6
 // Cholesky, the step) run redundantly in all lanes on identical inputs, without a broadcast.
-//   gather  taking-part slots (flags & 1, mapped id) -> world corners (LDS, double) and image corners (LDS, float32 as packed)
-//   seed    <= 8 seeding slots (flags & 2) of largest corner area; each slot's PnP pose and its mirrored planar minimum,
+//   gather  taking-part slots (flags & 1, mapped id) -> world corners (LDS, double) and image corners (LDS, float32 as packed);
+//           a map entry with a size of its own has its corners at that size, the others at the call's tag_size (map_tag_half)
+//   seed    <= 8 seeding slots (flags & 2) of largest corner area; each slot's PnP pose (solved at the call's tag_size: a
+//           sized slot's translation times h_id / half, which is its pose at its own size) and its mirrored planar minimum,
 //           composed with the map, scored over ALL taking-part corners: reseed_poses' camera half with the tags held fixed
 //   refine  Levenberg-Marquardt on camera<-world, T <- [Rod(w) | v] T, 10 trial steps at most
 //   gate    optional: while the slot of largest own 4-corner RMS exceeds max_tag_rms_px it is dropped and the solve runs
@@ -20,8 +22,19 @@
 
 struct MapTagRec {  // == asl_map_tag, 104 bytes
     double T[12];   // rows 0..2 of world<-tag
-    int32_t valid, reserved;
+    int32_t valid;
+    float size;     // the tag's own side; 0: the call's tag_size
 };
+
+// The half side of map entry e, the one rule of every solver that takes a map.  hid comes in as the call's half and stays
+// that for size 0; a size of its own makes it (double)(size * 0.5f) (halving a float32 is exact: the float32 half the PnP
+// would form).  False for an entry that does not take part: valid == 0, or a size that is negative or not finite.
+__device__ __forceinline__ bool map_tag_half(const MapTagRec &e, double &hid)
+{
+    const float sz = e.size;
+    if (sz > 0.0f) hid = (double)(sz * 0.5f);
+    return e.valid && sz >= 0.0f && sz < INFINITY;
+}
 
 struct CamPoseRec {  // == asl_cam_pose, 160 bytes
     double T[16];
@@ -164,8 +177,8 @@ __device__ __forceinline__ void loc_gather_slot(const LocLds &L, int s, const do
 }
 
 // Gather of one frame's n slots against the map, slot s being the record rec(s): state 1 for a taking-part slot
-// (flags & 1, mapped id), its area if seeds(flags), else -1.  Returns the number of taking-part slots and, with nseed,
-// sets the number of seeding ones, both identical in every lane.
+// (flags & 1, mapped id: map_tag_half), its corners at the slot's own half, its area if seeds(flags), else -1.  Returns
+// the number of taking-part slots and, with nseed, sets the number of seeding ones, both identical in every lane.
 template <class Rec, class Seeds>
 __device__ __forceinline__ int loc_gather(Rec rec, int n, const MapTagRec *map, int n_ids, double half, Seeds seeds, const LocLds &L, int lane,
                                           int *nseed = nullptr)
@@ -174,7 +187,8 @@ __device__ __forceinline__ int loc_gather(Rec rec, int n, const MapTagRec *map, 
     for (int s = lane; s < n; s += ASL_WAVE) {
         const ObsRec *r = rec(s);
         const int id = r->id, fl = r->flags;
-        const bool part = (fl & 1) && id >= 0 && id < n_ids && map[id].valid;
+        double hs = half;
+        const bool part = (fl & 1) && id >= 0 && id < n_ids && map_tag_half(map[id], hs);
         L.state[s] = part ? 1 : 0;
         L.area[s] = -1.0;
         if (!part) continue;
@@ -182,7 +196,7 @@ __device__ __forceinline__ int loc_gather(Rec rec, int n, const MapTagRec *map, 
         float cf[8];
 #pragma unroll
         for (int k = 0; k < 8; k++) cf[k] = r->corners[k];
-        loc_gather_slot(L, s, map[id].T, half, cf);
+        loc_gather_slot(L, s, map[id].T, hs, cf);
         if (seeds(fl)) {
             ns++;
             L.area[s] = loc_area(cf);
@@ -420,6 +434,13 @@ __device__ __forceinline__ void loc_solve_frame(const Model &m, const LocLds &L,
         const double *Mp = map[fo->id].T;
 #pragma unroll
         for (int k = 0; k < 12; k++) { To[k] = fo->T[k]; M[k] = Mp[k]; }
+        // a sized tag: the PnP solved it at the call's half, so the rotation holds and the translation is short by
+        // half / h_id (object and translation scaled together leave every ray where it is, under any lens)
+        const float sz = map[fo->id].size;
+        if (sz > 0.0f) {
+            const double k = (double)(sz * 0.5f) / half;
+            To[3] *= k; To[7] *= k; To[11] *= k;
+        }
         for (int mi = 0; mi < 2; mi++) {
             double Rc[9], tc[3];
             m.candidate(s, To, M, mi == 1, Rc, tc);

@@ -888,7 +888,7 @@ __global__ void __launch_bounds__(MAP_WG) k_map_finish(MapArgs a, int n_cams, in
         if (ok) pk_to34(a.G + 12 * (size_t)j, T);
         for (int k = 0; k < 12; k++) r->T[k] = ok ? T[k] : 0.0;
         r->valid = ok ? 1 : 0;
-        r->reserved = 0;
+        r->size = 0.0f;
         if (tag_std)
             for (int k = 0; k < 6; k++) tag_std[6 * (size_t)i + k] = (ok && j != wt && std_ok) ? sqrt(s2 * var[6 * j + k]) : 0.0;
     }

@@ -5,7 +5,8 @@ A frame that sees n mapped tags gives 8n pixel residuals for the 6 unknowns of i
 any one tag's planar PnP.  The map may come from SLAM.optimize() (SLAM.tag_map()), from a survey or from a synthetic
 scene (TagMap.from_scene).
 
-    TagMap          ids -> world<-tag 4x4, as the asl_map_tag records the library reads (indexed by id)
+    TagMap          ids -> world<-tag 4x4 and, optionally, the tag's own side length, as the asl_map_tag records the
+                    library reads (indexed by id)
     CAM_POSE_DTYPE  one asl_cam_pose per frame: world<-camera T, rms_px, rms_seed_px, n_tags, n_rejected, status, seed_slot
     POSE_COV_DTYPE  one asl_pose_cov per pose: cov 6x6 (rx ry rz | px py pz), sigma_px, dof, status; pose_std reads it
 """
@@ -31,12 +32,16 @@ def pose_std(cov):
 
 class TagMap:
     """World<-tag poses by tag id.  The tag frame is the one the per-tag PnP reports (camera<-tag): corners at (+-h, +-h, 0)
-    in the order lb, rb, rt, lt."""
+    in the order lb, rb, rt, lt.  h is half the call's tag_size, or half the tag's own size where one is set (set_size):
+    every solver that takes a map honours it."""
 
-    def __init__(self, poses=None):
+    def __init__(self, poses=None, sizes=None):
         self.poses = {}
+        self.sizes = {}
         for tag_id, T in (poses or {}).items():
             self[tag_id] = T
+        for tag_id, size in (sizes or {}).items():
+            self.set_size(tag_id, size)
 
     def __setitem__(self, tag_id, T):
         tag_id = int(tag_id)
@@ -51,6 +56,37 @@ class TagMap:
 
     def __getitem__(self, tag_id):
         return self.poses[int(tag_id)]
+
+    def set_size(self, tag_id, size):
+        """The side of tag tag_id, in the units and with the meaning of the solvers' tag_size (between the corner points
+        the detector reports), kept as float32 like the record's field.  0 clears it: the tag then has the call's tag_size."""
+        tag_id = int(tag_id)
+        if tag_id not in self.poses:
+            raise KeyError("tag %d has no pose in this map" % tag_id)
+        size = float(np.float32(size))
+        if not (np.isfinite(size) and size >= 0):
+            raise ValueError("a tag size is finite and non-negative (0: the call's tag_size)")
+        if size == 0:
+            self.sizes.pop(tag_id, None)
+        else:
+            self.sizes[tag_id] = size
+
+    def size(self, tag_id):
+        """The tag's own side, 0.0 if none is set (the tag has the call's tag_size)."""
+        return self.sizes.get(int(tag_id), 0.0)
+
+    def tag_pose(self, tag_id, T_cam_tag, tag_size):
+        """camera<-tag (4x4) of tag tag_id from the pose T_cam_tag that the per-tag PnP gave at tag_size (get_pose, or a
+        record's T).  For a tag with a size of its own the rotation holds and the translation is multiplied by
+        k = float32(size / 2) / float32(tag_size / 2): object and translation scaled together leave every ray where it
+        is, under any lens.  A tag without a size comes back unchanged."""
+        T = np.array(T_cam_tag, dtype=np.float64)
+        if T.shape == (3, 4):
+            T = np.vstack([T, [0.0, 0.0, 0.0, 1.0]])
+        size = self.size(tag_id)
+        if size > 0:
+            T[:3, 3] *= float(np.float32(size) * np.float32(0.5)) / float(np.float32(tag_size / 2))
+        return T
 
     def __contains__(self, tag_id):
         return int(tag_id) in self.poses
@@ -97,30 +133,38 @@ class TagMap:
         return cls(poses)
 
     def save(self, path):
-        """Write the map to an .npz file: ids (n,) and T (n, 4, 4) world<-tag, in ascending id order."""
+        """Write the map to an .npz file: ids (n,), T (n, 4, 4) world<-tag and sizes (n,) float32 (0: none), in ascending
+        id order."""
         ids = self.ids()
         T = np.array([self.poses[i] for i in ids], dtype=np.float64).reshape(-1, 4, 4)
-        np.savez(path, ids=np.array(ids, dtype=np.int64), T=T)
+        sizes = np.array([self.size(i) for i in ids], dtype=np.float32)
+        np.savez(path, ids=np.array(ids, dtype=np.int64), T=T, sizes=sizes)
 
     @classmethod
     def load(cls, path):
-        """The map TagMap.save wrote."""
+        """The map TagMap.save wrote; a file without sizes (written before tags had them) gives sizes of 0."""
         with np.load(path) as z:
             ids, T = z["ids"], z["T"]
             if ids.ndim != 1 or T.shape != (len(ids), 4, 4):
                 raise ValueError("%s is not a saved TagMap (ids (n,), T (n, 4, 4))" % path)
-            return cls({int(i): T[k] for k, i in enumerate(ids)})
+            sizes = z["sizes"] if "sizes" in z.files else np.zeros(len(ids), dtype=np.float32)
+            if sizes.shape != (len(ids),):
+                raise ValueError("%s: sizes must be (n,) like ids" % path)
+            return cls({int(i): T[k] for k, i in enumerate(ids)}, {int(i): sizes[k] for k, i in enumerate(ids)})
 
     @classmethod
     def from_records(cls, rec):
-        """The valid entries of an (n_ids,) MAP_TAG_DTYPE block (e.g. asl_map_frames_device's output)."""
+        """The valid entries of an (n_ids,) MAP_TAG_DTYPE block (e.g. asl_map_frames_device's output), with their sizes.
+        An entry with a negative or non-finite size counts as not valid, as in the solvers."""
         rec = np.asarray(rec, dtype=MAP_TAG_DTYPE).ravel()
-        return cls({int(i): rec["T"][i].reshape(3, 4) for i in np.flatnonzero(rec["valid"])})
+        ok = (rec["valid"] != 0) & np.isfinite(rec["size"]) & (rec["size"] >= 0)
+        return cls({int(i): rec["T"][i].reshape(3, 4) for i in np.flatnonzero(ok)}, {int(i): rec["size"][i] for i in np.flatnonzero(ok)})
 
     def as_records(self):
-        """(n_ids,) MAP_TAG_DTYPE, indexed by id; ids without a pose have valid = 0"""
+        """(n_ids,) MAP_TAG_DTYPE, indexed by id; ids without a pose have valid = 0, tags without a size have size = 0"""
         rec = np.zeros(max(self.n_ids, 1), dtype=MAP_TAG_DTYPE)
         for tag_id, T in self.poses.items():
             rec["T"][tag_id] = T[:3].ravel()
             rec["valid"][tag_id] = 1
+            rec["size"][tag_id] = self.size(tag_id)
         return rec

@@ -97,7 +97,8 @@ class Rig:
     def localize(self, det, obs, tag_map, tag_size, max_tag_rms_px=0.0, with_cov=False, sigma_px=0.0):
         """obs (n_cams, n_frames, max_tags) OBS_DTYPE, camera-major, against tag_map (a localize.TagMap or MAP_TAG_DTYPE
         records) on det (a _lib.Detector) -> (n_frames,) CAM_POSE_DTYPE with T = world<-rig; with_cov: (poses, (n_frames,)
-        POSE_COV_DTYPE), scaled by sigma_px or, for 0, by the solve's own estimate."""
+        POSE_COV_DTYPE), scaled by sigma_px or, for 0, by the solve's own estimate.  tag_size is the size of the map entries
+        that have none of their own (TagMap.set_size), here and in localize_sequence / localize_sequences."""
         o = np.asarray(obs)
         if o.dtype != OBS_DTYPE or o.ndim != 3 or o.shape[0] != len(self.cameras):
             raise ValueError("obs must be (%d, n_frames, max_tags) asl_obs records" % len(self.cameras))

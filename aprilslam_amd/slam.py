@@ -244,7 +244,8 @@ class SLAM:
     def localize(self, detections, max_tag_rms_px=0.0, with_cov=False, sigma_px=0.0):
         """Camera pose of one frame from all its mapped tags at once (TagDetector.localize against tag_map()).  Leaves
         estimated_pose, the graph and the window alone; my_pose() stays the reference's estimator.  with_cov / sigma_px:
-        the pose's covariance as TagDetector.localize reports it (the graph's tags taken as exact)."""
+        the pose's covariance as TagDetector.localize reports it (the graph's tags taken as exact).  tag_map() carries no
+        sizes (the graph has one tag_size); a map with sizes goes through TagDetector.localize."""
         return self.detector.localize(detections, self.tag_map(), max_tag_rms_px=max_tag_rms_px, with_cov=with_cov, sigma_px=sigma_px)
 
     def localize_sequence(self, dets, poses, n_per_frame, **kw):

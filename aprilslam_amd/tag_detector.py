@@ -172,7 +172,9 @@ class TagDetector:
         submission are reused; detections without one get their PnP first (one launch).  max_tag_rms_px > 0 drops tags
         whose own corner RMS exceeds it (moved or mis-identified tags) and solves again.  with_cov adds "cov" (6x6,
         rotation about the world axes | camera position, zeros unless "cov_status" is 0) and "sigma_px", the corner sigma
-        that scaled it: the given one, or for 0 the solve's own estimate (localize.pose_std reads the std off it)."""
+        that scaled it: the given one, or for 0 the solve's own estimate (localize.pose_std reads the std off it).
+        A tag with a size of its own in tag_map (TagMap.set_size) is solved at it, here and in localize_batch /
+        localize_sequence / localize_sequences; this detector's tag_size is the size of the others."""
         dets = list(detections)
         if len(dets) > 256:
             raise ValueError("at most 256 detections per frame")
@@ -279,7 +281,8 @@ class TagDetector:
         """Host frames ((n, H, W, 3) BGR or (n, H, W) gray uint8, or a list of them) that see the target tag_map (a
         localize.TagMap, e.g. TagMap.grid) -> calibrate.CalibrationResult: K, dist (n_dist coefficients), std, per-frame
         poses.  Detect, pack (asl_obs records) and calibrate; this detector's own camera model is not used.  Pass the
-        result's camera_params to a TagDetector afterwards."""
+        result's camera_params to a TagDetector afterwards.  The target may mix tag sizes (TagMap.set_size); this detector's
+        tag_size is the size of the tags that have none of their own."""
         from .calibrate import CalibrationResult
         from .dist import pack_observations
         if self.rectify:

@@ -201,8 +201,16 @@ int asl_graph_picks_device(asl_detector *det, const void *d_obs, int world, int 
 typedef struct {
     double T[12];    /* world<-tag, rows 0..2 of the 4x4 (the tag frame of asl_pose: corners (+-h, +-h, 0), lb rb rt lt) */
     int32_t valid;   /* 0: no pose for this id */
-    int32_t reserved;
+    float size;      /* the side of this tag, in the units and with the meaning of tag_size (between the corner points the
+                        detector reports).  0: the call's tag_size (every map asl_map_* writes).  > 0 and finite: this tag's
+                        own side; its corners are (+-h_id, +-h_id, 0) with h_id = size * 0.5f.  Negative or not finite: the
+                        entry counts as valid = 0 */
 } asl_map_tag;       /* indexed by tag id; 104 bytes */
+
+/* Every entry point below that takes d_map / map honours the entries' sizes: localisation, the rig forms, their covariances,
+   calibration and the sequence solves.  Their tag_size is the size of the entries whose size is 0.  The per-tag PnP poses in
+   the records (asl_obs.T) are taken as solved at tag_size: the seed of a sized tag uses that pose with its translation
+   times size / tag_size (object and translation scaled together leave every ray where it is, under any lens). */
 
 typedef struct {
     double T[16];        /* world<-camera, row-major (the convention of asl_gn_solve's cam_T) */
@@ -216,7 +224,7 @@ typedef struct {
 
 /* One camera pose per frame of d_obs (n_frames x max_tags records as asl_pack_observations_device writes them), device
    pointers, asynchronous on `stream`.  A slot takes part if flags & 1 and its id has a valid map entry (id < n_ids); its
-   4 corners are residuals against the map tag's corners.  The seed is the best, over all taking-part corners, of the
+   4 corners are residuals against the map tag's corners (tag_size is the size of the entries whose size is 0).  The seed is the best, over all taking-part corners, of the
    poses that the PnP of the <= 8 largest slots with flags & 2 imply through the map, each also in its mirrored planar
    minimum; Levenberg-Marquardt on the 6 pose parameters refines it (K 9 doubles row-major, dist n_dist = 0, 4 or 5
    coefficients, as asl_solve_pnp_batch).  max_tag_rms_px > 0 is an outlier gate: while the slot of largest own corner RMS
@@ -281,7 +289,8 @@ typedef struct {
    slots g = c * max_tags + s, and gather, seed, refinement and gate are those of asl_localize_frames_device over global
    slots: the seeds are the <= 8 global slots with flags & 2 of largest corner area -- in pixels squared as they are, so
    cameras of different focal length are not put on one scale -- and a seed of camera c implies the rig pose
-   inv(E_c) T_obs inv(map[id]), scored over the taking-part corners of all cameras.  tag_size is one value for the rig.
+   inv(E_c) T_obs inv(map[id]), scored over the taking-part corners of all cameras.  tag_size is one value for the rig
+   (the size of the map entries whose size is 0).
    d_out: one asl_cam_pose per frame with T = world<-rig; n_tags / n_rejected count global slots, status 1: no mapped tag
    in any camera, 2: no slot with a successful PnP, seed_slot the global slot of the winner (+256 if mirrored).  A rig of
    one camera with E = identity is asl_localize_frames_device.
@@ -331,7 +340,8 @@ typedef struct {
 } asl_calib_result;       /* 216 bytes */
 
 /* Calibrate from d_obs (n_frames x max_tags records as asl_pack_observations_device writes them; only flags & 1, id and
-   corners are read -- the PnP pose in the record was computed with some other K) against d_map (n_ids asl_map_tag).
+   corners are read -- the PnP pose in the record was computed with some other K) against d_map (n_ids asl_map_tag;
+   tag_size is the size of the entries whose size is 0, and a sized tag's planar pose is formed at its own half).
    A frame takes part with >= 2 mapped slots.  Without K_init the principal point starts at (width / 2, height / 2) and
    the focal lengths come in closed form from every tag's homography (Zhang's constraints, least squares); each frame is
    seeded with that K0 and no distortion (planar pose of its <= 8 largest tags and their mirrored minima, scored over all
@@ -479,7 +489,7 @@ typedef struct {
 } asl_smooth_result;               /* 64 bytes */
 
 /* Smooth d_obs (n_frames x max_tags records of consecutive frames, as asl_pack_observations_device writes them) against
-   d_map (n_ids asl_map_tag) from d_seed (n_frames asl_cam_pose, what asl_localize_frames_device wrote for the same obs, map
+   d_map (n_ids asl_map_tag; tag_size is the size of the entries whose size is 0) from d_seed (n_frames asl_cam_pose, what asl_localize_frames_device wrote for the same obs, map
    and camera; status 0: the frame has a pose); device pointers, everything enqueued on `stream`, no host wait (the detector
    owns the work buffers: the first call at a larger n_frames allocates, which synchronises the device).  Unknowns:
    camera<-world (R_f, t_f) of every frame, left update as the localisation.  Minimised:
