@@ -45,7 +45,7 @@ RIG_CAMERA_DTYPE = np.dtype([("K", "<f8", (3, 3)), ("dist", "<f8", (5,)), ("E", 
 assert RIG_CAMERA_DTYPE.itemsize == 216
 
 EXPORTS = [
-    "asl_detector_create", "asl_detector_destroy", "asl_detector_set_id_limit", "asl_detector_set_pnp_both_minima", "asl_detector_set_quad_sigma", "asl_blur_taps", "asl_last_error", "asl_version", "asl_detect_gray_u8",
+    "asl_detector_create", "asl_family_check", "asl_detector_create_family", "asl_detector_destroy", "asl_detector_set_id_limit", "asl_detector_set_pnp_both_minima", "asl_detector_set_quad_sigma", "asl_blur_taps", "asl_last_error", "asl_version", "asl_detect_gray_u8",
     "asl_detect_bgr_u8", "asl_detect_batch_u8", "asl_detect_batch_pose_u8", "asl_detect_batch_device", "asl_submit_batch_device", "asl_collect_batch", "asl_collect_batch_view", "asl_solve_pnp_batch", "asl_gn_solve", "asl_pack_observations_device", "asl_graph_frames_device", "asl_graph_picks_device", "asl_render_frames_device",
     "asl_rectify_frames_device", "asl_rectify_u8",
     "asl_localize_frames_device", "asl_localize_batch", "asl_localize_cov_frames_device", "asl_localize_cov_batch",
@@ -58,6 +58,32 @@ EXPORTS = [
     "asl_debug_fetch", "asl_debug_refit", "asl_debug_dedup", "asl_debug_gn_cholesky", "asl_debug_gn_step", "asl_debug_division_check", "asl_stage_times", "asl_set_profiling", "asl_debug_phase_cycles",
 ]
 
+
+
+BUILTIN_FAMILY = "tagStandard41h12"  # asl_detector_create's one name; every other family goes in as a table
+
+
+class AslFamily(C.Structure):    # asl_family
+    _fields_ = [("nbits", C.c_int32), ("width_at_border", C.c_int32), ("total_width", C.c_int32), ("reversed_border", C.c_int32),
+                ("ncodes", C.c_int32), ("reserved", C.c_int32), ("bit_x", C.POINTER(C.c_int32)), ("bit_y", C.POINTER(C.c_int32)),
+                ("codes", C.POINTER(C.c_uint64))]
+
+
+class FamilyTable:
+    """An asl_family over a TagFamily (families.py), with the arrays it points into kept alive."""
+
+    def __init__(self, fam):
+        self.bit_x = np.ascontiguousarray(fam.bit_x, dtype=np.int32)
+        self.bit_y = np.ascontiguousarray(fam.bit_y, dtype=np.int32)
+        self.codes = np.ascontiguousarray(fam.codes, dtype=np.uint64)
+        self.c = AslFamily(int(fam.nbits), int(fam.width_at_border), int(fam.total_width), int(bool(fam.reversed_border)),
+                           int(self.codes.shape[0]), 0, self.bit_x.ctypes.data_as(C.POINTER(C.c_int32)),
+                           self.bit_y.ctypes.data_as(C.POINTER(C.c_int32)), self.codes.ctypes.data_as(C.POINTER(C.c_uint64)))
+
+
+def family_check(fam):
+    """asl_family_check on a TagFamily: raises AslError naming the field the detector cannot take.  No GPU needed."""
+    check(load().asl_family_check(C.byref(FamilyTable(fam).c)))
 
 
 class DebugSpan(C.Structure):    # asl_debug_span: room for n doubles at p; p NULL: not wanted
@@ -96,6 +122,8 @@ def load():
     L.asl_last_error.restype = C.c_char_p
     L.asl_version.restype = C.c_char_p
     L.asl_detector_create.argtypes = [C.c_char_p, i32, i32, C.c_float, C.c_float, i32, i32, C.POINTER(vp)]
+    L.asl_family_check.argtypes = [C.POINTER(AslFamily)]
+    L.asl_detector_create_family.argtypes = [C.POINTER(AslFamily), i32, i32, C.c_float, C.c_float, i32, i32, C.POINTER(vp)]
     L.asl_detector_destroy.argtypes = [vp]
     L.asl_detector_destroy.restype = None
     L.asl_detector_set_id_limit.argtypes = [vp, i32]
@@ -250,13 +278,25 @@ class Detector:
 
     def __init__(self, family="tagStandard41h12", threads=1, maxhamming=1, decimate=2.0, blur=0.0, refine_edges=True,
                  device=0, id_limit=None):
-        """id_limit: None = the ids the reference pins (0..4); 0 = the whole (build-defined) table; n = ids 0..n-1."""
+        """family: the built-in name, the name of a family registered with families.register / families.load, or a
+        TagFamily.  id_limit: None = the built-in family's ids the reference pins (0..4), every id of any other family;
+        0 = the whole table; n = ids 0..n-1."""
         L = load()
         self._L = L
         self._h = C.c_void_p()
         self._outbuf = self._posebuf = None  # detection / pose results kept across calls (_result_buffers)
-        check(L.asl_detector_create(family.encode(), int(threads), int(maxhamming), float(decimate), float(blur),
-                                    1 if refine_edges else 0, int(device), C.byref(self._h)))
+        rest = (int(threads), int(maxhamming), float(decimate), float(blur), 1 if refine_edges else 0, int(device), C.byref(self._h))
+        table = None
+        if not isinstance(family, str):
+            table = FamilyTable(family)
+        elif family != BUILTIN_FAMILY:
+            from . import families
+            if families.is_registered(family):
+                table = FamilyTable(families.get_family(family))
+        if table is None:
+            check(L.asl_detector_create(family.encode(), *rest))  # refuses an unknown name
+        else:
+            check(L.asl_detector_create_family(C.byref(table.c), *rest))  # the detector keeps its own copy of the table
         self.device = int(device)
         if id_limit is not None:
             check(L.asl_detector_set_id_limit(self._h, int(id_limit)))

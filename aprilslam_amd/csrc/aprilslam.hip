@@ -91,6 +91,7 @@ struct asl_detector {
     int pnp_both_minima = 0;
     BlurTaps blur{};  // asl_detector_set_quad_sigma; r = 0: off
     FamilyDev fam;
+    std::vector<unsigned long long> host_codes;  // the family's whole table, the detector's own copy: the index and the id limit read it
     DevBuf<unsigned long long> codes;        // the family's code book (FamilyDev::codes)
     DevBuf<unsigned short> idx_start;        // code-book index of the family (FamilyDev), rebuilt when the id limit changes
     DevBuf<unsigned long long> idx_entries;
@@ -198,22 +199,79 @@ static int build_code_index(asl_detector *d)
         std::vector<unsigned int> bucket(f.ncodes);
         unsigned short *st = start.data() + (size_t)c * (IDX_BUCKETS + 1);
         for (int i = 0; i < f.ncodes; i++) {
-            bucket[i] = idx_bucket((kTag41h12Codes[i] >> lo) & ((1ull << w) - 1ull), w);
+            bucket[i] = idx_bucket((d->host_codes[i] >> lo) & ((1ull << w) - 1ull), w);
             st[bucket[i] + 1]++;
         }
         for (int b = 0; b < IDX_BUCKETS; b++) st[b + 1] = (unsigned short)(st[b + 1] + st[b]);
         std::vector<unsigned short> fill(st, st + IDX_BUCKETS);
         for (int i = 0; i < f.ncodes; i++)  // ids ascending inside a bucket
-            entries[(size_t)c * f.ncodes + fill[bucket[i]]++] = ((unsigned long long)i << 48) | kTag41h12Codes[i];
+            entries[(size_t)c * f.ncodes + fill[bucket[i]]++] = ((unsigned long long)i << 48) | d->host_codes[i];
         lo += w;
     }
     for (int c = nch; c < IDX_MAX_CHUNKS; c++) { f.idx_lo[c] = 0; f.idx_w[c] = 1; }
-    if (d->idx_start.ensure(start.size()) || d->idx_entries.ensure((size_t)IDX_MAX_CHUNKS * kTag41h12NCodes)) return -1;
+    if (d->idx_start.ensure(start.size()) || d->idx_entries.ensure((size_t)IDX_MAX_CHUNKS * d->host_codes.size())) return -1;
     if (hipMemcpy(d->idx_start.p, start.data(), start.size() * sizeof(unsigned short), hipMemcpyHostToDevice) != hipSuccess) return -1;
     if (hipMemcpy(d->idx_entries.p, entries.data(), entries.size() * sizeof(unsigned long long), hipMemcpyHostToDevice) != hipSuccess) return -1;
     f.idx_start = d->idx_start.p; f.idx_entries = d->idx_entries.p; f.idx_nch = nch;
     return 0;
 }
+
+// What k_decode and the quad fit assume of a family (k_decode.inc: the storage plan's capacities, rotate90_dev, the packed
+// match).  A table that fails here would decode silently wrong, so it never reaches a detector.
+extern "C" int asl_family_check(const asl_family *f)
+{
+    if (!f) return fail(ASL_EINVAL, "family is NULL");
+    const int nbits = f->nbits, wb = f->width_at_border, tw = f->total_width;
+    if (nbits < 1 || nbits > 63) return fail(ASL_EINVAL, "nbits must be in [1, 63] (got %d)", nbits);
+    if (nbits % 4 > 1) return fail(ASL_EINVAL, "nbits %% 4 must be 0 or 1 (got nbits = %d): the rotation search handles nothing else", nbits);
+    if (wb < 2 || wb > 8) return fail(ASL_EINVAL, "width_at_border must be in [2, 8] (got %d)", wb);
+    if (tw > DEC_GRID_CAP || tw < wb || (tw - wb) % 2 != 0)
+        return fail(ASL_EINVAL, "total_width must be in [width_at_border, %d] and differ from width_at_border by an even number (got %d, width_at_border %d)",
+                    DEC_GRID_CAP, tw, wb);
+    if (f->ncodes < 1 || f->ncodes > 65535) return fail(ASL_EINVAL, "ncodes must be in [1, 65535] (got %d)", f->ncodes);
+    if (!f->bit_x) return fail(ASL_EINVAL, "bit_x is NULL");
+    if (!f->bit_y) return fail(ASL_EINVAL, "bit_y is NULL");
+    if (!f->codes) return fail(ASL_EINVAL, "codes is NULL");
+    std::vector<std::pair<uint64_t, int>> sorted((size_t)f->ncodes);
+    for (int i = 0; i < f->ncodes; i++) {
+        if (f->codes[i] >> nbits) return fail(ASL_EINVAL, "codes[%d] has bits at or above nbits (%d)", i, nbits);
+        sorted[(size_t)i] = {f->codes[i], i};
+    }
+    std::sort(sorted.begin(), sorted.end());
+    for (int i = 1; i < f->ncodes; i++)
+        if (sorted[(size_t)i].first == sorted[(size_t)i - 1].first)
+            return fail(ASL_EINVAL, "codes[%d] is a duplicate of codes[%d]", sorted[(size_t)i].second, sorted[(size_t)i - 1].second);
+    const int off = (tw - wb) / 2;
+    int owner[DEC_GRID_CAP * DEC_GRID_CAP];
+    for (int &o : owner) o = -1;
+    for (int i = 0; i < nbits; i++) {
+        const int x = f->bit_x[i], y = f->bit_y[i];
+        if (x < -off || y < -off || x >= wb + off || y >= wb + off)
+            return fail(ASL_EINVAL, "bit %d at (%d, %d) is outside the total_width grid", i, x, y);
+        const bool in_border = x >= 0 && y >= 0 && x < wb && y < wb, in_outer = x >= -1 && y >= -1 && x <= wb && y <= wb;
+        if (in_border && (x == 0 || y == 0 || x == wb - 1 || y == wb - 1))
+            return fail(ASL_EINVAL, "bit %d at (%d, %d) is on the border ring", i, x, y);
+        if (!in_border && in_outer)
+            return fail(ASL_EINVAL, "bit %d at (%d, %d) is on the ring just outside the border", i, x, y);
+        int &o = owner[(y + off) * tw + (x + off)];
+        if (o >= 0) return fail(ASL_EINVAL, "bit %d and bit %d share the cell (%d, %d)", o, i, x, y);
+        o = i;
+    }
+    const int q = nbits / 4;
+    for (int i = 0; i + q < 4 * q; i++)
+        if (f->bit_x[i + q] != wb - 1 - f->bit_y[i] || f->bit_y[i + q] != f->bit_x[i])
+            return fail(ASL_EINVAL, "the layout does not turn with the code: bit %d must be at (%d, %d), the quarter turn of bit %d", i + q,
+                        wb - 1 - f->bit_y[i], f->bit_x[i], i);
+    if (nbits % 4 == 1 && (wb % 2 == 0 || f->bit_x[nbits - 1] != (wb - 1) / 2 || f->bit_y[nbits - 1] != (wb - 1) / 2))
+        return fail(ASL_EINVAL, "the layout does not turn with the code: the last bit must be at the centre cell");
+    return ASL_OK;
+}
+
+static int detector_create(const asl_family *family, int default_ids, int maxhamming, float decimate, float blur, int refine_edges,
+                           int device, asl_detector **out);
+
+static const asl_family kTag41h12Family = {kTag41h12NBits, kTag41h12WidthAtBorder, kTag41h12TotalWidth, 1, kTag41h12NCodes, 0,
+                                           kTag41h12BitX, kTag41h12BitY, reinterpret_cast<const uint64_t *>(kTag41h12Codes)};
 
 extern "C" int asl_detector_create(const char *family, int nthreads, int maxhamming, float decimate, float blur,
                                    int refine_edges, int device, asl_detector **out)
@@ -223,6 +281,23 @@ extern "C" int asl_detector_create(const char *family, int nthreads, int maxhamm
     *out = nullptr;
     if (!family || strcmp(family, "tagStandard41h12") != 0)
         return fail(ASL_EINVAL, "unknown tag family '%s' (supported: tagStandard41h12)", family ? family : "(null)");
+    // ids the reference's own tag images pin; asl_detector_set_id_limit opens the rest
+    return detector_create(&kTag41h12Family, kTag41h12PinnedIds, maxhamming, decimate, blur, refine_edges, device, out);
+}
+
+extern "C" int asl_detector_create_family(const asl_family *fam, int nthreads, int maxhamming, float decimate, float blur,
+                                          int refine_edges, int device, asl_detector **out)
+{
+    (void)nthreads;
+    if (!out) return fail(ASL_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (int rc = asl_family_check(fam)) return rc;
+    return detector_create(fam, fam->ncodes, maxhamming, decimate, blur, refine_edges, device, out);  // the caller's table: all of its ids
+}
+
+static int detector_create(const asl_family *family, int default_ids, int maxhamming, float decimate, float blur, int refine_edges,
+                           int device, asl_detector **out)
+{
     if (!(decimate >= 1.0f) || decimate != std::floor(decimate) || decimate > 8.0f)
         return fail(ASL_EINVAL, "decimate must be an integer value in [1, 8] (got %g)", (double)decimate);
     if (blur != 0.0f) return fail(ASL_EINVAL, "blur must be 0 here: set quad_sigma with asl_detector_set_quad_sigma");
@@ -238,14 +313,15 @@ extern "C" int asl_detector_create(const char *family, int nthreads, int maxhamm
     d->decimate = (int)decimate;
     d->refine = refine_edges ? 1 : 0;
     memset(&d->fam, 0, sizeof d->fam);
-    d->fam.nbits = kTag41h12NBits;
-    d->fam.width_at_border = kTag41h12WidthAtBorder;
-    d->fam.total_width = kTag41h12TotalWidth;
-    d->fam.reversed_border = 1;
-    d->fam.ncodes = kTag41h12PinnedIds;  // ids the reference's own tag images pin; asl_detector_set_id_limit opens the rest
-    for (int i = 0; i < kTag41h12NBits; i++) { d->fam.bit_x[i] = kTag41h12BitX[i]; d->fam.bit_y[i] = kTag41h12BitY[i]; }
-    if (d->codes.ensure(kTag41h12NCodes)) return fail(ASL_ENOMEM, "hipMalloc(code book) failed");
-    if (hipMemcpy(d->codes.p, kTag41h12Codes, sizeof(unsigned long long) * kTag41h12NCodes, hipMemcpyHostToDevice) != hipSuccess)
+    d->fam.nbits = family->nbits;
+    d->fam.width_at_border = family->width_at_border;
+    d->fam.total_width = family->total_width;
+    d->fam.reversed_border = family->reversed_border ? 1 : 0;
+    d->fam.ncodes = default_ids;
+    for (int i = 0; i < family->nbits; i++) { d->fam.bit_x[i] = family->bit_x[i]; d->fam.bit_y[i] = family->bit_y[i]; }
+    d->host_codes.assign(family->codes, family->codes + family->ncodes);
+    if (d->codes.ensure(d->host_codes.size())) return fail(ASL_ENOMEM, "hipMalloc(code book) failed");
+    if (hipMemcpy(d->codes.p, d->host_codes.data(), sizeof(unsigned long long) * d->host_codes.size(), hipMemcpyHostToDevice) != hipSuccess)
         return fail(ASL_EDEVICE, "hipMemcpy(code book) failed");
     d->fam.codes = d->codes.p;
     if (build_code_index(d.get())) return fail(ASL_ENOMEM, "code-book index allocation failed");
@@ -269,9 +345,10 @@ extern "C" void asl_detector_destroy(asl_detector *d)
 extern "C" int asl_detector_set_id_limit(asl_detector *d, int n_ids)
 {
     if (!d) return fail(ASL_EINVAL, "detector is NULL");
-    if (n_ids > kTag41h12NCodes) return fail(ASL_EINVAL, "the code table holds %d ids (asked for %d)", kTag41h12NCodes, n_ids);
+    const int table_ids = (int)d->host_codes.size();
+    if (n_ids > table_ids) return fail(ASL_EINVAL, "the code table holds %d ids (asked for %d)", table_ids, n_ids);
     if (d->pending) return fail(ASL_EINVAL, "a batch is in flight on this detector");
-    d->fam.ncodes = n_ids <= 0 ? kTag41h12NCodes : n_ids;
+    d->fam.ncodes = n_ids <= 0 ? table_ids : n_ids;
     HIPCHK(hipSetDevice(d->device));
     if (build_code_index(d)) return fail(ASL_ENOMEM, "code-book index allocation failed");
     return ASL_OK;

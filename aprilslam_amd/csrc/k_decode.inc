@@ -55,20 +55,21 @@ __device__ __forceinline__ unsigned long long rotate90_dev(unsigned long long w,
 
 // ---- Storage plan of k_decode: the workgroup's LDS, one wavefront.  The kernel holds one DecodeStore; the steps reach it
 // only through their argument.  Nothing shares memory.  The capacities are what the store assumes of a family:
-#define DEC_BORDER_CAP 40 /* border samples, 8 patterns of width_at_border each: 8 * width_at_border <= 40 (more are not sampled) */
+#define DEC_BORDER_CAP 64 /* border samples, 8 patterns of width_at_border each, one lane each: width_at_border <= 8 */
 #define DEC_GRID_CAP 16   /* cells along a side of the payload grid: total_width <= 16 */
 #define DEC_BITS_CAP 64   /* payload bits, one lane each: nbits <= 64 */
+// A family beyond these is refused when the detector is made (asl_family_check), never truncated here.
 // Barriers of a quad: L opens it (loop top), A follows H, B the border samples, C the gray models, D the payload values,
 // E (inside decode_scores) the two lists.
 //
 //   member      bytes   holds                          written by                     read by                       free after
-//   smpxy       640     tag-frame coordinates of the   tag_sites, once per            border_samples,               never: constant for the
+//   smpxy       1024    tag-frame coordinates of the   tag_sites, once per            border_samples,               never: constant for the
 //   bitxy       1024    border samples / payload bits  workgroup, ahead of the        payload_values                workgroup's life
 //                                                      first L
 //   H           72      the quad's homography          the body: lanes 0-8            border_samples,               L of the next quad
 //                                                                                     payload_values (behind A),
 //                                                                                     emit
-//   smp         1280    border rows (x, y, gray, 1),   border_samples: the sample's   gray_models: lanes 0-17       L of the next quad
+//   smp         2048    border rows (x, y, gray, 1),   border_samples: the sample's   gray_models: lanes 0-17       L of the next quad
 //                       zeros for a sample outside     lane                           (behind B)
 //   white,      240     the two gray models            gray_models: lanes 0 and 1     payload_values (behind C)     L of the next quad
 //   black
@@ -78,7 +79,7 @@ __device__ __forceinline__ unsigned long long rotate90_dev(unsigned long long w,
 //                       threshold, 0 where unknown     payload_values: a bit's lane
 //   list        1024    the white and the negated      scores: a bit's lane           scores: lanes 0 and 1         L of the next quad
 //                       black values, in bit order                                    (behind E)
-//   sum         6332    + 4 of padding = 6336, what the build reports
+//   sum         7484    + 4 of padding = 7488, what the build reports
 //
 // The three early `continue`s of the body, and why every lane of the wavefront takes them together: (1) slot 9 of the
 // quad's record is 0 -- one global word, read by every lane; (2) ok is 0 -- one LDS word, read by every lane behind C;
@@ -95,7 +96,7 @@ struct alignas(16) DecodeStore {  // the rows of smp, smpxy and bitxy start on 1
     GrayModel black;
     int ok;
 };
-static_assert(sizeof(DecodeStore) == 6336, "k_decode: the plan and the LDS allocation disagree");
+static_assert(sizeof(DecodeStore) == 7488, "k_decode: the plan and the LDS allocation disagree");
 
 // where a lane's payload bit sits: values[at], cell (x, y) of the grid
 struct DecodeCell { int at, x, y; };
@@ -111,7 +112,7 @@ struct UMin { __device__ __forceinline__ unsigned int operator()(unsigned int a,
 __device__ __forceinline__ void decode_tag_sites(DecodeStore &st, const FamilyDev &fam, int lane)
 {
     const int wb = fam.width_at_border;
-    if (lane < 8 * wb && lane < DEC_BORDER_CAP) {
+    if (lane < 8 * wb) {
         int pi = lane / wb, i = lane % wb;
         double p0, p1, p2, p3;
         switch (pi) {
@@ -142,7 +143,7 @@ __device__ __forceinline__ void decode_tag_sites(DecodeStore &st, const FamilyDe
 template <int CH>
 __device__ __forceinline__ void decode_border_samples(DecodeStore &st, const uint8_t *frame, const Geom &g, const FamilyDev &fam, int lane)
 {
-    if (lane < 8 * fam.width_at_border && lane < DEC_BORDER_CAP) {
+    if (lane < 8 * fam.width_at_border) {
         const double tagx = st.smpxy[lane][0], tagy = st.smpxy[lane][1];
         double px, py;
         hproject_dev(st.H, tagx, tagy, &px, &py);
@@ -155,10 +156,10 @@ __device__ __forceinline__ void decode_border_samples(DecodeStore &st, const uin
 
 // Gray models of the white and the black border.  Upstream adds the samples one by one into 9 running sums per model;
 // here lane a (0..8: white, 9..17: black) owns one sum and walks the samples in the same order, so every sum sees the
-// same additions -- 40 steps of a wavefront instead of 40 x 9 of a single lane.  The sum's term is u*v with u, v picked
-// from the sample's (x, y, gray, 1) row (x*1 and 1*1 are exact).  Both models are then solved at once: lane 0 solves
-// white, lane 1 black (every lane runs the same code on its copy), and lane 0 compares them at the tag's centre for the
-// polarity.  Reads smp; writes white, black, ok.
+// same additions -- 4 x width_at_border steps of a wavefront instead of 8 x width_at_border x 9 of a single lane.  The
+// sum's term is u*v with u, v picked from the sample's (x, y, gray, 1) row (x*1 and 1*1 are exact).  Both models are
+// then solved at once: lane 0 solves white, lane 1 black (every lane runs the same code on its copy), and lane 0
+// compares them at the tag's centre for the polarity.  Reads smp; writes white, black, ok.
 __device__ __forceinline__ void decode_gray_models(DecodeStore &st, const FamilyDev &fam, int lane)
 {
     const int wb = fam.width_at_border, nsmp = 8 * wb;
@@ -168,10 +169,8 @@ __device__ __forceinline__ void decode_gray_models(DecodeStore &st, const Family
     double acc = 0;
     if (lane < 18) {
         // patterns alternate white, black: a model's lanes visit only their own patterns (half the samples), in order
-        const int ns = nsmp < DEC_BORDER_CAP ? nsmp : DEC_BORDER_CAP;
-        for (int p0 = m * wb; p0 < ns; p0 += 2 * wb) {
-            const int pe = p0 + wb < ns ? p0 + wb : ns;
-            for (int smp = p0; smp < pe; smp++) {
+        for (int p0 = m * wb; p0 < nsmp; p0 += 2 * wb) {
+            for (int smp = p0; smp < p0 + wb; smp++) {
                 const double u = st.smp[smp][ku], v = st.smp[smp][kv];
                 acc += u * v;
             }

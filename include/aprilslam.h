@@ -69,10 +69,44 @@ typedef struct {
 int asl_detector_create(const char *family, int nthreads, int maxhamming, float decimate, float blur,
                         int refine_edges, int device, asl_detector **out);
 void asl_detector_destroy(asl_detector *det);
-/* Which ids the decoder may return.  Only ids 0..4 of tagStandard41h12 are pinned by the reference (its
+
+/* A tag family as data: the fields of upstream's apriltag_family_t that the detector reads.  Whoever has upstream's
+   detector installed owns the real tables (its generated tagXXhYY.c files); this is how they are handed in.
+   bit_x / bit_y follow upstream's convention: cell (0, 0) is the corner cell of the border, the border square spans
+   cells 0..width_at_border-1, and a reversed-border family puts payload cells outside it (negative coordinates).
+   codes[id] holds bit 0 of the family in the most significant of its nbits. */
+typedef struct {
+    int32_t nbits, width_at_border, total_width, reversed_border, ncodes, reserved;
+    const int32_t *bit_x, *bit_y; /* nbits each */
+    const uint64_t *codes;        /* ncodes */
+} asl_family;
+
+/* Whether the detector can decode `fam` exactly.  A pure host function: no GPU, no detector.  ASL_EINVAL, with
+   asl_last_error() naming the field, for
+     - nbits outside 1..63, or nbits % 4 not 0 or 1 (the rotation search handles nothing else);
+     - width_at_border outside 2..8 (the 8 * width_at_border border samples are one per lane of a wavefront);
+     - total_width above 16, below width_at_border, or total_width - width_at_border odd;
+     - ncodes outside 1..65535 (the match packs the id into 16 bits);
+     - a NULL array; a code with bits at or above nbits; a duplicate code;
+     - a bit cell outside the total_width grid, on the border ring, on the ring of opposite colour just outside it,
+       or shared by two bits;
+     - a layout that does not turn with the code: bit i + nbits/4 must sit at (width_at_border - 1 - y_i, x_i), and
+       with nbits % 4 == 1 the last bit at the centre cell.
+   The minimum Hamming distance of the table is not checked: it is the owner's, and so is maxhamming. */
+int asl_family_check(const asl_family *fam);
+/* asl_detector_create for a caller's table (the other arguments as there).  The family must pass asl_family_check.
+   The detector copies everything it needs: the caller's arrays may go away after the call.  The table is the caller's
+   truth, so the new detector decodes all of its ids; asl_detector_set_id_limit narrows that, bounded by fam->ncodes.
+   One detector decodes one family (a detection carries no family field): use one detector per family. */
+int asl_detector_create_family(const asl_family *fam, int nthreads, int maxhamming, float decimate, float blur,
+                               int refine_edges, int device, asl_detector **out);
+
+/* Which ids the decoder may return, ASL_EINVAL beyond the detector's table.  For a detector made with
+   asl_detector_create: only ids 0..4 of tagStandard41h12 are pinned by the reference (its
    assets/tags/tag{0..4}.png); upstream's 2115-entry code table is not in the reference tree, so the other
-   entries of this library's table are build-defined and would mislabel a physical tag with id >= 5.  A new
-   detector therefore decodes ids 0..4 only.  n_ids <= 0 opens the whole table (synthetic scenes rendered from
+   entries of this library's built-in table are build-defined and would mislabel a physical tag with id >= 5.  Such a
+   detector therefore decodes ids 0..4 only until told otherwise; to decode printed tags with id >= 5, hand upstream's
+   own table to asl_detector_create_family.  n_ids <= 0 opens the whole table (synthetic scenes rendered from
    the same table), n_ids > 0 keeps ids 0..n_ids-1. */
 int asl_detector_set_id_limit(asl_detector *det, int n_ids);
 /* A planar tag has two poses that reproject almost equally well.  cv2.solvePnP(ITERATIVE), which the reference calls
