@@ -45,7 +45,7 @@ RIG_CAMERA_DTYPE = np.dtype([("K", "<f8", (3, 3)), ("dist", "<f8", (5,)), ("E", 
 assert RIG_CAMERA_DTYPE.itemsize == 216
 
 EXPORTS = [
-    "asl_detector_create", "asl_family_check", "asl_detector_create_family", "asl_detector_destroy", "asl_detector_set_id_limit", "asl_detector_set_pnp_both_minima", "asl_detector_set_quad_sigma", "asl_blur_taps", "asl_last_error", "asl_version", "asl_detect_gray_u8",
+    "asl_detector_create", "asl_family_check", "asl_detector_create_family", "asl_families_check", "asl_detector_create_families", "asl_detector_family_of", "asl_detector_destroy", "asl_detector_set_id_limit", "asl_detector_set_pnp_both_minima", "asl_detector_set_quad_sigma", "asl_blur_taps", "asl_last_error", "asl_version", "asl_detect_gray_u8",
     "asl_detect_bgr_u8", "asl_detect_batch_u8", "asl_detect_batch_pose_u8", "asl_detect_batch_device", "asl_submit_batch_device", "asl_collect_batch", "asl_collect_batch_view", "asl_solve_pnp_batch", "asl_gn_solve", "asl_pack_observations_device", "asl_graph_frames_device", "asl_graph_picks_device", "asl_render_frames_device",
     "asl_rectify_frames_device", "asl_rectify_u8",
     "asl_localize_frames_device", "asl_localize_batch", "asl_localize_cov_frames_device", "asl_localize_cov_batch",
@@ -60,6 +60,7 @@ EXPORTS = [
 
 
 
+MAX_FAMILIES = 4  # ASL_MAX_FAMILIES
 BUILTIN_FAMILY = "tagStandard41h12"  # asl_detector_create's one name; every other family goes in as a table
 
 
@@ -84,6 +85,43 @@ class FamilyTable:
 def family_check(fam):
     """asl_family_check on a TagFamily: raises AslError naming the field the detector cannot take.  No GPU needed."""
     check(load().asl_family_check(C.byref(FamilyTable(fam).c)))
+
+
+def _tag_family(family):
+    """A TagFamily of a TagFamily or a registered (or the built-in) name."""
+    if not isinstance(family, str):
+        return family
+    from . import families
+    if family != BUILTIN_FAMILY and not families.is_registered(family):
+        raise AslError("unknown tag family '%s'" % family)
+    return families.get_family(family)
+
+
+class FamilySet:
+    """What asl_families_check / asl_detector_create_families take: an asl_family array over TagFamily objects or names,
+    with their id bases.  id_base None: the cumulative bases 0, n0, n0 + n1, ..."""
+
+    def __init__(self, fams, id_base=None):
+        self.families = tuple(_tag_family(f) for f in fams)
+        self.tables = [FamilyTable(f) for f in self.families]
+        if id_base is None:
+            id_base = np.cumsum([0] + [len(t.codes) for t in self.tables[:-1]]) if self.tables else []
+        if len(id_base) != len(self.tables):
+            raise ValueError("one id_base per family")
+        self.id_base = np.ascontiguousarray(id_base, dtype=np.int32)
+        self.c = (AslFamily * max(len(self.tables), 1))(*[t.c for t in self.tables])
+        self.n = len(self.tables)
+
+    @property
+    def id_base_p(self):
+        return self.id_base.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def families_check(fams, id_base=None):
+    """asl_families_check on a list of TagFamily objects / names: raises AslError naming the family's index and the field.
+    No GPU needed."""
+    fs = FamilySet(fams, id_base)
+    check(load().asl_families_check(fs.c, fs.id_base_p, fs.n))
 
 
 class DebugSpan(C.Structure):    # asl_debug_span: room for n doubles at p; p NULL: not wanted
@@ -124,6 +162,9 @@ def load():
     L.asl_detector_create.argtypes = [C.c_char_p, i32, i32, C.c_float, C.c_float, i32, i32, C.POINTER(vp)]
     L.asl_family_check.argtypes = [C.POINTER(AslFamily)]
     L.asl_detector_create_family.argtypes = [C.POINTER(AslFamily), i32, i32, C.c_float, C.c_float, i32, i32, C.POINTER(vp)]
+    L.asl_families_check.argtypes = [C.POINTER(AslFamily), C.POINTER(C.c_int32), i32]
+    L.asl_detector_create_families.argtypes = [C.POINTER(AslFamily), C.POINTER(C.c_int32), i32, i32, i32, C.c_float, C.c_float, i32, i32, C.POINTER(vp)]
+    L.asl_detector_family_of.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.asl_detector_destroy.argtypes = [vp]
     L.asl_detector_destroy.restype = None
     L.asl_detector_set_id_limit.argtypes = [vp, i32]
@@ -277,16 +318,29 @@ class Detector:
     """Owns one asl_detector (one GPU workspace).  Not re-entrant."""
 
     def __init__(self, family="tagStandard41h12", threads=1, maxhamming=1, decimate=2.0, blur=0.0, refine_edges=True,
-                 device=0, id_limit=None):
+                 device=0, id_limit=None, id_base=None):
         """family: the built-in name, the name of a family registered with families.register / families.load, or a
-        TagFamily.  id_limit: None = the built-in family's ids the reference pins (0..4), every id of any other family;
-        0 = the whole table; n = ids 0..n-1."""
+        TagFamily; or a list / tuple of those, for one detector that decodes several families in one pass and reports a
+        tag with local id k of family i as id_base[i] + k (id_base None: the cumulative bases 0, n0, n0 + n1, ...); the
+        built-in name in a list stands for its whole table.
+        id_limit (one family only): None = the built-in family's ids the reference pins (0..4), every id of any other
+        family; 0 = the whole table; n = ids 0..n-1."""
         L = load()
         self._L = L
         self._h = C.c_void_p()
         self._outbuf = self._posebuf = None  # detection / pose results kept across calls (_result_buffers)
         rest = (int(threads), int(maxhamming), float(decimate), float(blur), 1 if refine_edges else 0, int(device), C.byref(self._h))
         table = None
+        if isinstance(family, (list, tuple)):
+            fs = FamilySet(family, id_base)
+            check(L.asl_detector_create_families(fs.c, fs.id_base_p, fs.n, *rest))  # the detector keeps its own copy of the tables
+            self.families, self.id_base = fs.families, tuple(int(b) for b in fs.id_base)
+            self.device = int(device)
+            if id_limit is not None:
+                check(L.asl_detector_set_id_limit(self._h, int(id_limit)))
+            return
+        if id_base is not None:
+            raise ValueError("id_base goes with a list of families")
         if not isinstance(family, str):
             table = FamilyTable(family)
         elif family != BUILTIN_FAMILY:
@@ -297,9 +351,16 @@ class Detector:
             check(L.asl_detector_create(family.encode(), *rest))  # refuses an unknown name
         else:
             check(L.asl_detector_create_family(C.byref(table.c), *rest))  # the detector keeps its own copy of the table
+        self.families, self.id_base = (_tag_family(family),), (0,)
         self.device = int(device)
         if id_limit is not None:
             check(L.asl_detector_set_id_limit(self._h, int(id_limit)))
+
+    def family_of(self, id):
+        """asl_detector_family_of: (index into the detector's families, the id inside that family) of a reported id."""
+        fi, k = C.c_int(), C.c_int()
+        check(self._L.asl_detector_family_of(self._h, int(id), C.byref(fi), C.byref(k)))
+        return fi.value, k.value
 
     def set_pnp_both_minima(self, enabled):
         """asl_detector_set_pnp_both_minima: off = the reference's (cv2's) single minimum, on = the better of the two planar poses"""

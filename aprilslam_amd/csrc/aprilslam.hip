@@ -83,6 +83,8 @@ static int fail(int code, const char *fmt, ...)
 
 #define MAX_STAGES 24
 
+static_assert(FAM_MAX == ASL_MAX_FAMILIES, "asl_common.h and aprilslam.h disagree on the families a detector holds");
+
 struct asl_detector {
     int device = 0;
     int maxhamming = 1;
@@ -90,11 +92,17 @@ struct asl_detector {
     int refine = 1;
     int pnp_both_minima = 0;
     BlurTaps blur{};  // asl_detector_set_quad_sigma; r = 0: off
-    FamilyDev fam;
-    std::vector<unsigned long long> host_codes;  // the family's whole table, the detector's own copy: the index and the id limit read it
-    DevBuf<unsigned long long> codes;        // the family's code book (FamilyDev::codes)
-    DevBuf<unsigned short> idx_start;        // code-book index of the family (FamilyDev), rebuilt when the id limit changes
-    DevBuf<unsigned long long> idx_entries;
+    struct Family {
+        FamilyDev dev;
+        int id_base = 0;                             // a tag with local id k is reported as id_base + k (0 for a one-family detector)
+        std::vector<unsigned long long> host_codes;  // the family's whole table, the detector's own copy: the index and the id limit read it
+        DevBuf<unsigned long long> codes;        // the family's code book (FamilyDev::codes)
+        DevBuf<unsigned short> idx_start;        // code-book index of the family (FamilyDev), rebuilt when the id limit changes
+        DevBuf<unsigned long long> idx_entries;
+    };
+    Family fams[ASL_MAX_FAMILIES];
+    int nfam = 1;
+    DevBuf<FamilyTabDev> fam_tab;  // what k_decode_multi reads, where it is the decoder (decodes_multi, upload_family_table)
 
     // capacities (grow on overflow)
     unsigned int hash_slots_per_frame = 1024;
@@ -183,9 +191,9 @@ extern "C" const char *asl_version(void) { return kVersion; }
 
 // Code-book index for k_decode (asl_common.h: FamilyDev): maxhamming + 1 chunks of the code bits; a family wider than 48 bits
 // or with more than 65535 ids keeps idx_nch = 0 and is searched as a whole.
-static int build_code_index(asl_detector *d)
+static int build_code_index(asl_detector *d, asl_detector::Family &slot)
 {
-    FamilyDev &f = d->fam;
+    FamilyDev &f = slot.dev;
     f.idx_nch = 0; f.idx_start = nullptr; f.idx_entries = nullptr;
     const int nch = d->maxhamming + 1;
     if (f.nbits > 48 || f.ncodes > 65535 || nch > IDX_MAX_CHUNKS) return 0;
@@ -199,20 +207,20 @@ static int build_code_index(asl_detector *d)
         std::vector<unsigned int> bucket(f.ncodes);
         unsigned short *st = start.data() + (size_t)c * (IDX_BUCKETS + 1);
         for (int i = 0; i < f.ncodes; i++) {
-            bucket[i] = idx_bucket((d->host_codes[i] >> lo) & ((1ull << w) - 1ull), w);
+            bucket[i] = idx_bucket((slot.host_codes[i] >> lo) & ((1ull << w) - 1ull), w);
             st[bucket[i] + 1]++;
         }
         for (int b = 0; b < IDX_BUCKETS; b++) st[b + 1] = (unsigned short)(st[b + 1] + st[b]);
         std::vector<unsigned short> fill(st, st + IDX_BUCKETS);
         for (int i = 0; i < f.ncodes; i++)  // ids ascending inside a bucket
-            entries[(size_t)c * f.ncodes + fill[bucket[i]]++] = ((unsigned long long)i << 48) | d->host_codes[i];
+            entries[(size_t)c * f.ncodes + fill[bucket[i]]++] = ((unsigned long long)i << 48) | slot.host_codes[i];
         lo += w;
     }
     for (int c = nch; c < IDX_MAX_CHUNKS; c++) { f.idx_lo[c] = 0; f.idx_w[c] = 1; }
-    if (d->idx_start.ensure(start.size()) || d->idx_entries.ensure((size_t)IDX_MAX_CHUNKS * d->host_codes.size())) return -1;
-    if (hipMemcpy(d->idx_start.p, start.data(), start.size() * sizeof(unsigned short), hipMemcpyHostToDevice) != hipSuccess) return -1;
-    if (hipMemcpy(d->idx_entries.p, entries.data(), entries.size() * sizeof(unsigned long long), hipMemcpyHostToDevice) != hipSuccess) return -1;
-    f.idx_start = d->idx_start.p; f.idx_entries = d->idx_entries.p; f.idx_nch = nch;
+    if (slot.idx_start.ensure(start.size()) || slot.idx_entries.ensure((size_t)IDX_MAX_CHUNKS * slot.host_codes.size())) return -1;
+    if (hipMemcpy(slot.idx_start.p, start.data(), start.size() * sizeof(unsigned short), hipMemcpyHostToDevice) != hipSuccess) return -1;
+    if (hipMemcpy(slot.idx_entries.p, entries.data(), entries.size() * sizeof(unsigned long long), hipMemcpyHostToDevice) != hipSuccess) return -1;
+    f.idx_start = slot.idx_start.p; f.idx_entries = slot.idx_entries.p; f.idx_nch = nch;
     return 0;
 }
 
@@ -267,8 +275,34 @@ extern "C" int asl_family_check(const asl_family *f)
     return ASL_OK;
 }
 
-static int detector_create(const asl_family *family, int default_ids, int maxhamming, float decimate, float blur, int refine_edges,
-                           int device, asl_detector **out);
+// What a detector of several families assumes on top of asl_family_check of each: global ids id_base[i] + k that fit the
+// 16 bits the de-duplication key gives an id (k_dedup.inc) and name one family each.
+extern "C" int asl_families_check(const asl_family *fams, const int32_t *id_base, int n_fams)
+{
+    if (n_fams < 1 || n_fams > ASL_MAX_FAMILIES) return fail(ASL_EINVAL, "n_fams must be in [1, %d] (got %d)", ASL_MAX_FAMILIES, n_fams);
+    if (!fams) return fail(ASL_EINVAL, "fams is NULL");
+    if (!id_base) return fail(ASL_EINVAL, "id_base is NULL");
+    for (int i = 0; i < n_fams; i++) {
+        if (asl_family_check(&fams[i])) {
+            const std::string why = g_err;
+            return fail(ASL_EINVAL, "family %d: %s", i, why.c_str());
+        }
+        if (id_base[i] < 0) return fail(ASL_EINVAL, "family %d: id_base must not be negative (got %d)", i, (int)id_base[i]);
+        const long long end = (long long)id_base[i] + fams[i].ncodes;
+        if (end > 65536)
+            return fail(ASL_EINVAL, "family %d: id_base + ncodes must not exceed 65536, an id has 16 bits in the de-duplication key (got %d + %d)", i,
+                        (int)id_base[i], (int)fams[i].ncodes);
+    }
+    for (int i = 1; i < n_fams; i++)
+        for (int j = 0; j < i; j++)
+            if (id_base[i] < id_base[j] + fams[j].ncodes && id_base[j] < id_base[i] + fams[i].ncodes)
+                return fail(ASL_EINVAL, "family %d: id_base range [%d, %d) overlaps that of family %d, [%d, %d)", i, (int)id_base[i],
+                            (int)(id_base[i] + fams[i].ncodes), j, (int)id_base[j], (int)(id_base[j] + fams[j].ncodes));
+    return ASL_OK;
+}
+
+static int detector_create(const asl_family *fams, const int32_t *id_base, int n_fams, int default_ids, int maxhamming, float decimate, float blur,
+                           int refine_edges, int device, asl_detector **out);
 
 static const asl_family kTag41h12Family = {kTag41h12NBits, kTag41h12WidthAtBorder, kTag41h12TotalWidth, 1, kTag41h12NCodes, 0,
                                            kTag41h12BitX, kTag41h12BitY, reinterpret_cast<const uint64_t *>(kTag41h12Codes)};
@@ -282,7 +316,8 @@ extern "C" int asl_detector_create(const char *family, int nthreads, int maxhamm
     if (!family || strcmp(family, "tagStandard41h12") != 0)
         return fail(ASL_EINVAL, "unknown tag family '%s' (supported: tagStandard41h12)", family ? family : "(null)");
     // ids the reference's own tag images pin; asl_detector_set_id_limit opens the rest
-    return detector_create(&kTag41h12Family, kTag41h12PinnedIds, maxhamming, decimate, blur, refine_edges, device, out);
+    const int32_t base = 0;
+    return detector_create(&kTag41h12Family, &base, 1, kTag41h12PinnedIds, maxhamming, decimate, blur, refine_edges, device, out);
 }
 
 extern "C" int asl_detector_create_family(const asl_family *fam, int nthreads, int maxhamming, float decimate, float blur,
@@ -292,11 +327,47 @@ extern "C" int asl_detector_create_family(const asl_family *fam, int nthreads, i
     if (!out) return fail(ASL_EINVAL, "out is NULL");
     *out = nullptr;
     if (int rc = asl_family_check(fam)) return rc;
-    return detector_create(fam, fam->ncodes, maxhamming, decimate, blur, refine_edges, device, out);  // the caller's table: all of its ids
+    const int32_t base = 0;
+    return detector_create(fam, &base, 1, 0, maxhamming, decimate, blur, refine_edges, device, out);  // the caller's table: all of its ids
 }
 
-static int detector_create(const asl_family *family, int default_ids, int maxhamming, float decimate, float blur, int refine_edges,
-                           int device, asl_detector **out)
+extern "C" int asl_detector_create_families(const asl_family *fams, const int32_t *id_base, int n_fams, int nthreads, int maxhamming, float decimate,
+                                            float blur, int refine_edges, int device, asl_detector **out)
+{
+    (void)nthreads;
+    if (!out) return fail(ASL_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (int rc = asl_families_check(fams, id_base, n_fams)) return rc;
+    return detector_create(fams, id_base, n_fams, 0, maxhamming, decimate, blur, refine_edges, device, out);
+}
+
+// k_decode serves one family whose ids are reported as they are; k_decode_multi every other detector (several families, or
+// one made by asl_detector_create_families with an id_base of its own).
+static bool decodes_multi(const asl_detector *d) { return d->nfam > 1 || d->fams[0].id_base != 0; }
+
+// The table k_decode_multi reads: the families' device records as they stand (code books and indices included).
+static int upload_family_table(asl_detector *d)
+{
+    if (!decodes_multi(d)) return 0;
+    FamilyTabDev tab;
+    memset(&tab, 0, sizeof tab);
+    tab.n = d->nfam;
+    int k = 0;
+    for (int i = 0; i < d->nfam; i++) {
+        tab.fam[i] = d->fams[i].dev;
+        tab.id_base[i] = d->fams[i].id_base;
+        bool first = true;  // of its border width
+        for (int j = 0; j < i; j++) first = first && d->fams[j].dev.width_at_border != d->fams[i].dev.width_at_border;
+        for (int j = i; first && j < d->nfam; j++)
+            if (d->fams[j].dev.width_at_border == d->fams[i].dev.width_at_border) tab.order[k++] = j;
+    }
+    if (d->fam_tab.ensure(1)) return -1;
+    return hipMemcpy(d->fam_tab.p, &tab, sizeof tab, hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+}
+
+// default_ids: the ids a one-family detector decodes until asl_detector_set_id_limit says otherwise; 0: every id of every table
+static int detector_create(const asl_family *fams, const int32_t *id_base, int n_fams, int default_ids, int maxhamming, float decimate, float blur,
+                           int refine_edges, int device, asl_detector **out)
 {
     if (!(decimate >= 1.0f) || decimate != std::floor(decimate) || decimate > 8.0f)
         return fail(ASL_EINVAL, "decimate must be an integer value in [1, 8] (got %g)", (double)decimate);
@@ -312,19 +383,27 @@ static int detector_create(const asl_family *family, int default_ids, int maxham
     d->maxhamming = maxhamming;
     d->decimate = (int)decimate;
     d->refine = refine_edges ? 1 : 0;
-    memset(&d->fam, 0, sizeof d->fam);
-    d->fam.nbits = family->nbits;
-    d->fam.width_at_border = family->width_at_border;
-    d->fam.total_width = family->total_width;
-    d->fam.reversed_border = family->reversed_border ? 1 : 0;
-    d->fam.ncodes = default_ids;
-    for (int i = 0; i < family->nbits; i++) { d->fam.bit_x[i] = family->bit_x[i]; d->fam.bit_y[i] = family->bit_y[i]; }
-    d->host_codes.assign(family->codes, family->codes + family->ncodes);
-    if (d->codes.ensure(d->host_codes.size())) return fail(ASL_ENOMEM, "hipMalloc(code book) failed");
-    if (hipMemcpy(d->codes.p, d->host_codes.data(), sizeof(unsigned long long) * d->host_codes.size(), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(ASL_EDEVICE, "hipMemcpy(code book) failed");
-    d->fam.codes = d->codes.p;
-    if (build_code_index(d.get())) return fail(ASL_ENOMEM, "code-book index allocation failed");
+    d->nfam = n_fams;
+    for (int fi = 0; fi < n_fams; fi++) {
+        const asl_family *family = &fams[fi];
+        asl_detector::Family &slot = d->fams[fi];
+        FamilyDev &f = slot.dev;
+        memset(&f, 0, sizeof f);
+        f.nbits = family->nbits;
+        f.width_at_border = family->width_at_border;
+        f.total_width = family->total_width;
+        f.reversed_border = family->reversed_border ? 1 : 0;
+        f.ncodes = default_ids > 0 ? default_ids : family->ncodes;
+        for (int i = 0; i < family->nbits; i++) { f.bit_x[i] = family->bit_x[i]; f.bit_y[i] = family->bit_y[i]; }
+        slot.id_base = id_base[fi];
+        slot.host_codes.assign(family->codes, family->codes + family->ncodes);
+        if (slot.codes.ensure(slot.host_codes.size())) return fail(ASL_ENOMEM, "hipMalloc(code book) failed");
+        if (hipMemcpy(slot.codes.p, slot.host_codes.data(), sizeof(unsigned long long) * slot.host_codes.size(), hipMemcpyHostToDevice) != hipSuccess)
+            return fail(ASL_EDEVICE, "hipMemcpy(code book) failed");
+        f.codes = slot.codes.p;
+        if (build_code_index(d.get(), slot)) return fail(ASL_ENOMEM, "code-book index allocation failed");
+    }
+    if (upload_family_table(d.get())) return fail(ASL_ENOMEM, "family table allocation failed");
     if (d->wtab.ensure(WEIGHT_TABLE_N)) return fail(ASL_ENOMEM, "hipMalloc(weight table) failed");
     hipLaunchKernelGGL(k_weight_table, dim3((WEIGHT_TABLE_N + 255) / 256), dim3(256), 0, 0, d->wtab.p);
     if (hipDeviceSynchronize() != hipSuccess) return fail(ASL_EDEVICE, "weight table kernel failed");
@@ -345,13 +424,28 @@ extern "C" void asl_detector_destroy(asl_detector *d)
 extern "C" int asl_detector_set_id_limit(asl_detector *d, int n_ids)
 {
     if (!d) return fail(ASL_EINVAL, "detector is NULL");
-    const int table_ids = (int)d->host_codes.size();
+    if (d->nfam > 1) return fail(ASL_EINVAL, "a detector of %d families decodes every id of its tables: the id limit is for one family", d->nfam);
+    const int table_ids = (int)d->fams[0].host_codes.size();
     if (n_ids > table_ids) return fail(ASL_EINVAL, "the code table holds %d ids (asked for %d)", table_ids, n_ids);
     if (d->pending) return fail(ASL_EINVAL, "a batch is in flight on this detector");
-    d->fam.ncodes = n_ids <= 0 ? table_ids : n_ids;
+    d->fams[0].dev.ncodes = n_ids <= 0 ? table_ids : n_ids;
     HIPCHK(hipSetDevice(d->device));
-    if (build_code_index(d)) return fail(ASL_ENOMEM, "code-book index allocation failed");
+    if (build_code_index(d, d->fams[0]) || upload_family_table(d)) return fail(ASL_ENOMEM, "code-book index allocation failed");
     return ASL_OK;
+}
+
+extern "C" int asl_detector_family_of(const asl_detector *d, int id, int *family_index, int *local_id)
+{
+    if (!d) return fail(ASL_EINVAL, "detector is NULL");
+    if (!family_index || !local_id) return fail(ASL_EINVAL, "family_index or local_id is NULL");
+    for (int i = 0; i < d->nfam; i++) {
+        const int base = d->fams[i].id_base;
+        if (id >= base && id - base < (int)d->fams[i].host_codes.size()) {
+            *family_index = i; *local_id = id - base;
+            return ASL_OK;
+        }
+    }
+    return fail(ASL_EINVAL, "id %d is in no family's range", id);
 }
 
 // The taps of tests/blur_ref.py: ksz = int(4 * |sigma|) in float32, made odd; floor(255 * normalised Gaussian) in double.
@@ -553,7 +647,20 @@ static void launch_dedup(const S8Buffers &b, unsigned int B, int with_pose, hipS
 }
 
 // tag width in decimated pixels, at least 3 (the quad fit and its finish)
-static int tag_width(const asl_detector *d, const Geom &g) { return std::max(3, d->fam.width_at_border / g.f); }
+static int tag_width(const asl_detector *d, const Geom &g)
+{
+    int w = std::max(3, d->fams[0].dev.width_at_border / g.f);
+    for (int i = 1; i < d->nfam; i++) w = std::min(w, std::max(3, d->fams[i].dev.width_at_border / g.f));  // upstream: the smallest of the families'
+    return w;
+}
+
+// which border polarities the families want: bit 0 normal, bit 1 reversed (k_refine's selection, the quad fit's two wants)
+static int wanted_polarities(const asl_detector *d)
+{
+    int m = 0;
+    for (int i = 0; i < d->nfam; i++) m |= d->fams[i].dev.reversed_border ? 2 : 1;
+    return m;
+}
 
 // Quad fit of one size class (k_quad.inc): grid-stride kernels over the class's device-side cluster list -- many more
 // workgroups than fit on the chip, so the heavy-tailed per-cluster costs balance out (workgroups without work leave at once).
@@ -561,7 +668,7 @@ static int tag_width(const asl_detector *d, const Geom &g) { return std::max(3, 
 template <int BLOCK, int CAP>
 static void launch_fit(asl_detector *d, const Geom &g, int cls, unsigned int grid, hipStream_t st)
 {
-    const int want_rev = d->fam.reversed_border ? 1 : 0, want_norm = d->fam.reversed_border ? 0 : 1;
+    const int want_rev = (wanted_polarities(d) >> 1) & 1, want_norm = wanted_polarities(d) & 1;
     hipLaunchKernelGGL((k_fit_quads<BLOCK, CAP / BLOCK>), dim3(grid), dim3(BLOCK), CAP > 0 ? QUAD_LDS_BYTES(CAP) : 0, st, d->clusters.p,
                        d->class_lists.p + (size_t)cls * d->max_clusters, d->counters.p, cls, d->max_clusters, CAP, d->points.p, d->qgray, g,
                        tag_width(d, g), want_rev, want_norm, d->scratch.p, d->quads.p, d->wtab.p, d->side_mom.p);
@@ -681,13 +788,17 @@ static int enqueue_detect(asl_detector *d, const uint8_t *d_frames, const Geom &
     unsigned int dgrid = std::min<unsigned int>(d->max_clusters, std::max<unsigned int>(8192u, 64u * B));
     STAGE("k_refine");
     hipLaunchKernelGGL((g.channels == 1 ? k_refine<1> : k_refine<3>), dim3(dgrid), dim3(64), 0, st, d->quads.p, d->counters.p, d->max_clusters, d_frames, g,
-                       d->fam.reversed_border ? 1 : 0, d->refine, d->quadH.p, d->quad_list.p, d->side_mom.p);
+                       wanted_polarities(d), d->refine, d->quadH.p, d->quad_list.p, d->side_mom.p);
     STAGE("k_homography");
     hipLaunchKernelGGL(k_homography, dim3(std::min<unsigned int>((d->max_clusters + 31) / 32, 2048u)), dim3(256), 0, st, d->quadH.p, d->counters.p, d->max_clusters,
                        d->quad_list.p, d->side_mom.p);
     STAGE("k_decode");
-    hipLaunchKernelGGL((g.channels == 1 ? k_decode<1> : k_decode<3>), dim3(dgrid), dim3(64), 0, st, d->quads.p, d->quadH.p, d->counters.p, d->max_clusters, d_frames, g, d->fam,
-                       d->maxhamming, d->dets.p, d->max_dets, d->counters.p, d->quad_list.p);
+    if (!decodes_multi(d))
+        hipLaunchKernelGGL((g.channels == 1 ? k_decode<1> : k_decode<3>), dim3(dgrid), dim3(64), 0, st, d->quads.p, d->quadH.p, d->counters.p, d->max_clusters, d_frames, g,
+                           d->fams[0].dev, d->maxhamming, d->dets.p, d->max_dets, d->counters.p, d->quad_list.p);
+    else
+        hipLaunchKernelGGL((g.channels == 1 ? k_decode_multi<1> : k_decode_multi<3>), dim3(dgrid), dim3(64), 0, st, d->quads.p, d->quadH.p, d->counters.p, d->max_clusters,
+                           d_frames, g, d->fam_tab.p, d->maxhamming, d->dets.p, d->max_dets, d->counters.p, d->quad_list.p);
 
     range_pop();
     range_push("S9 PnP, S8 de-duplication");

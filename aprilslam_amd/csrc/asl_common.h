@@ -140,6 +140,16 @@ struct FamilyDev {
     const unsigned short *idx_start;              // [chunk][IDX_BUCKETS + 1]: first entry of every bucket
     const unsigned long long *idx_entries;        // [chunk][ncodes]: id << 48 | code, by bucket, ids ascending
 };
+// The families of a detector that holds more than one (k_decode_multi reads it from device memory).  A tag with local id k
+// of family i is reported as id_base[i] + k.  order: the table's indices with the families of one border width next to
+// each other (widths in the order of their first family, table order inside a width), so that a quad's border is
+// sampled once per width.
+#define FAM_MAX 4  // ASL_MAX_FAMILIES
+struct FamilyTabDev {
+    FamilyDev fam[FAM_MAX];
+    int id_base[FAM_MAX], order[FAM_MAX];
+    int n, pad;
+};
 __host__ __device__ __forceinline__ unsigned int idx_bucket(unsigned long long chunk_value, int width)
 {
     return width <= IDX_BUCKET_BITS ? (unsigned int)chunk_value : (unsigned int)((chunk_value * 0x9E3779B97F4A7C15ull) >> (64 - IDX_BUCKET_BITS));

@@ -98,6 +98,16 @@ struct alignas(16) DecodeStore {  // the rows of smp, smpxy and bitxy start on 1
 };
 static_assert(sizeof(DecodeStore) == 7488, "k_decode: the plan and the LDS allocation disagree");
 
+// Where a lane's border sample and its payload bit sit.  The steps ask a `Sites` instead of a table, so that k_decode_multi
+// (below) can keep its families' sites in another form; the steps are templates over the store for the same reason.
+// k_decode's Sites: the two tables of its store, the bit's cell from the family in the kernel's arguments.
+struct DecodeSites {
+    const DecodeStore &st;
+    __device__ __forceinline__ void sample(int lane, double *tagx, double *tagy) const { *tagx = st.smpxy[lane][0]; *tagy = st.smpxy[lane][1]; }
+    __device__ __forceinline__ void bit_cell(const FamilyDev &fam, int lane, int *bitx, int *bity) const { *bitx = fam.bit_x[lane]; *bity = fam.bit_y[lane]; }
+    __device__ __forceinline__ void bit(int lane, double *tagx, double *tagy) const { *tagx = st.bitxy[lane][0]; *tagy = st.bitxy[lane][1]; }
+};
+
 // where a lane's payload bit sits: values[at], cell (x, y) of the grid
 struct DecodeCell { int at, x, y; };
 struct DecodeScores { float white_score, black_score, white_count, black_count; };
@@ -140,11 +150,12 @@ __device__ __forceinline__ void decode_tag_sites(DecodeStore &st, const FamilyDe
 // Border samples, 8 patterns x width_at_border: a lane projects its sample and reads its pixel.  A sample outside the
 // frame is left out of the sums upstream: here its row is all zeros, so that each of its terms is +0.0 and leaves a sum
 // that started at +0.0 exactly as it is (no flag to read in decode_gray_models).  Reads H, smpxy; writes smp.
-template <int CH>
-__device__ __forceinline__ void decode_border_samples(DecodeStore &st, const uint8_t *frame, const Geom &g, const FamilyDev &fam, int lane)
+template <int CH, class Store, class Sites>
+__device__ __forceinline__ void decode_border_samples(Store &st, const Sites &sites, const uint8_t *frame, const Geom &g, const FamilyDev &fam, int lane)
 {
     if (lane < 8 * fam.width_at_border) {
-        const double tagx = st.smpxy[lane][0], tagy = st.smpxy[lane][1];
+        double tagx, tagy;
+        sites.sample(lane, &tagx, &tagy);
         double px, py;
         hproject_dev(st.H, tagx, tagy, &px, &py);
         int ix = (int)px, iy = (int)py;
@@ -160,7 +171,8 @@ __device__ __forceinline__ void decode_border_samples(DecodeStore &st, const uin
 // sum's term is u*v with u, v picked from the sample's (x, y, gray, 1) row (x*1 and 1*1 are exact).  Both models are
 // then solved at once: lane 0 solves white, lane 1 black (every lane runs the same code on its copy), and lane 0
 // compares them at the tag's centre for the polarity.  Reads smp; writes white, black, ok.
-__device__ __forceinline__ void decode_gray_models(DecodeStore &st, const FamilyDev &fam, int lane)
+template <class Store>
+__device__ __forceinline__ void decode_gray_models(Store &st, const FamilyDev &fam, int lane)
 {
     const int wb = fam.width_at_border, nsmp = 8 * wb;
     const int a = lane % 9, m = lane / 9;
@@ -197,17 +209,19 @@ __device__ __forceinline__ void decode_gray_models(DecodeStore &st, const Family
 // Payload bits: a bit's lane projects its cell's centre, interpolates the gray value there and stores it minus the
 // threshold between the two models; a cell whose four pixels are not all inside the frame keeps its 0.  Reads H, bitxy,
 // white, black; writes values (one cell per lane).  Returns where the lane's bit sits.
-template <int CH>
-__device__ __forceinline__ DecodeCell decode_payload_values(DecodeStore &st, const uint8_t *frame, const Geom &g, const FamilyDev &fam, int lane)
+template <int CH, class Store, class Sites>
+__device__ __forceinline__ DecodeCell decode_payload_values(Store &st, const Sites &sites, const uint8_t *frame, const Geom &g, const FamilyDev &fam, int lane)
 {
     const int wb = fam.width_at_border, tw = fam.total_width;
     int min_coord = (wb - tw) / 2;
     DecodeCell c = {0, 0, 0};
     if (lane < fam.nbits) {
-        int bitx = fam.bit_x[lane], bity = fam.bit_y[lane];
+        int bitx, bity;
+        sites.bit_cell(fam, lane, &bitx, &bity);
         c.x = bitx - min_coord; c.y = bity - min_coord;
         c.at = tw * c.y + c.x;
-        const double tagx = st.bitxy[lane][0], tagy = st.bitxy[lane][1];
+        double tagx, tagy;
+        sites.bit(lane, &tagx, &tagy);
         double px, py;
         hproject_dev(st.H, tagx, tagy, &px, &py);
         double v = value_for_pixel_dev<CH>(frame, g, px, py);
@@ -222,7 +236,8 @@ __device__ __forceinline__ DecodeCell decode_payload_values(DecodeStore &st, con
 // Sharpening (upstream: the whole grid through a 3x3 Laplacian, then value + 0.25 * Laplacian): only the payload cells are
 // read afterwards, so each bit's lane sharpens its own cell -- the same five terms in the same order.  No second grid,
 // no pass over the 81 cells (two rounds with an integer division each), two barriers fewer.  Reads values.
-__device__ __forceinline__ double decode_sharpen(const DecodeStore &st, const FamilyDev &fam, const DecodeCell &c, int lane)
+template <class Store>
+__device__ __forceinline__ double decode_sharpen(const Store &st, const FamilyDev &fam, const DecodeCell &c, int lane)
 {
     const int tw = fam.total_width;
     double sharp_v = 0.0;
@@ -243,7 +258,8 @@ __device__ __forceinline__ double decode_sharpen(const DecodeStore &st, const Fa
 // chains, so lane 0 adds the white values in bit order and lane 1 the negated black ones, from two compacted lists --
 // ~20 steps of one add instead of 41 steps of compare, two conversions, add and select by every lane.  The code word is
 // the ballot of "white".  Writes list, barrier E, reads list.
-__device__ __forceinline__ DecodeScores decode_scores(DecodeStore &st, const FamilyDev &fam, double sharp_v, int lane, unsigned long long *rcode)
+template <class Store>
+__device__ __forceinline__ DecodeScores decode_scores(Store &st, const FamilyDev &fam, double sharp_v, int lane, unsigned long long *rcode)
 {
     const bool isbit = lane < fam.nbits;
     const double v = isbit ? sharp_v : 0.0;
@@ -321,7 +337,8 @@ __device__ __forceinline__ DecodeMatch decode_lookup_book(const FamilyDev &fam, 
 
 // The detection record: lane 0 takes a slot, turns H by the match's rotation and projects the centre and the corners.
 // Reads H.
-__device__ __forceinline__ void decode_emit(const DecodeStore &st, const DecodeMatch &m, float margin, int fr, unsigned long long qkey, DetRec *dets,
+template <class Store>
+__device__ __forceinline__ void decode_emit(const Store &st, const DecodeMatch &m, float margin, int fr, unsigned long long qkey, DetRec *dets,
                                             unsigned int max_dets, long long *wcounters, int lane)
 {
     if (lane == 0) {
@@ -361,6 +378,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) k_
     const unsigned int nq = tail_quad_count(counters, max_clusters);
 
     decode_tag_sites(st, fam, lane);
+    const DecodeSites sites{st};
     for (unsigned int qi = blockIdx.x; qi < nq; qi += gridDim.x) {
         __syncthreads();  // L
         PHASE_INIT();
@@ -372,14 +390,14 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) k_
         if (lane < 9) st.H[lane] = Hin[10 * (size_t)ci + lane];
         __syncthreads();  // A
         PHASE(18);
-        decode_border_samples<CH>(st, frame, g, fam, lane);
+        decode_border_samples<CH>(st, sites, frame, g, fam, lane);
         __syncthreads();  // B
         decode_gray_models(st, fam, lane);
         for (int i = lane; i < fam.total_width * fam.total_width; i += 64) st.values[i] = 0;
         __syncthreads();  // C
         if (!st.ok) continue;  // (2) the border's polarity is not the family's
         PHASE(19);
-        const DecodeCell cell = decode_payload_values<CH>(st, frame, g, fam, lane);
+        const DecodeCell cell = decode_payload_values<CH>(st, sites, frame, g, fam, lane);
         __syncthreads();  // D
         const double sharp_v = decode_sharpen(st, fam, cell, lane);
         PHASE(20);
@@ -393,4 +411,147 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) k_
         PHASE(23);
     }
     PHASE_FLUSH(16);
+}
+
+// ---- Several families in one detector: k_decode_multi, launched in place of k_decode when the detector holds more than
+// one family.  One wavefront per quad, the steps above, the families of the table (FamilyTabDev, device memory) in a loop
+// inside the quad: a quad is decoded against every family of its polarity and every family that accepts it yields a
+// detection of its own, with id = id_base + local id (upstream's loop over its family list; no arbitration between
+// families).  H is loaded once per quad; the border samples and the two gray models are taken once per border width --
+// they depend on the family through width_at_border alone, and every candidate has the quad's polarity, so `ok` is a
+// property of (quad, width) as well -- and the families of that width, next to each other in the table's `order`, read them.
+//
+// Storage plan: DecodeStore's per-quad members unchanged (same writers, readers and barriers); the tag sites in another
+// form, because two 1 KB tables of doubles per family would be 8 KB for four.  Every site coordinate is
+// 2 * ((n + 0.5) / width_at_border - 0.5) for an integer cell n along one axis: -1 .. width_at_border for the border
+// patterns, the bit's cell for the payload, in all -8 .. 15 under asl_family_check's limits (total_width <= 16,
+// width_at_border >= 2).  So a family keeps that one axis as doubles, computed by the expression decode_tag_sites uses
+// (the same bits), and two cells per lane as bytes.
+//
+//   member      bytes   holds                              written by                    read by                      free after
+//   axis        768     per family: the coordinate of      multi_tag_sites, once per     MultiSites (border_samples,  never
+//                       cell n at [n + 8]                   workgroup, ahead of the       payload_values)
+//   smpn        512     per family: the cells (x, y) of    first L
+//                       lane's border sample
+//   bitn        512     per family: the cells of lane's
+//                       payload bit
+//   H, smp, white, black, ok, values, list: 5436, as in DecodeStore, "next quad" reading "next width" for smp, white,
+//                       black and ok, and "next family" for values and list
+//   sum         7228    + 4 of padding = 7232, what the build reports: as many workgroups on a CU as k_decode's 7488
+//
+// Barriers: L, A per quad; B (border samples) and the gray models per width; C, D, E per family.  C also separates a
+// family's zeroing of `values` from the cells the lanes then write; the zeroing itself comes behind E of the family
+// before, whose last read of `values` (sharpen) is ahead of that E.  `list` of the family before is read behind its E
+// by lanes 0 and 1, which reach this family's C and D only afterwards; this family writes it behind D.  A new width
+// writes smp behind C of the family before (its readers, the model lanes, are ahead of that C), and white, black and
+// ok behind B, which every lane reaches after its read of ok and of the models (payload_values, ahead of D).
+//
+// Early exits, all taken by the whole wavefront: (1) as in k_decode; inside the family loop a `continue` goes on to the
+// next family, where every path meets barrier C (or B then C) again, so the test must be uniform: (4) the family's
+// polarity against the quad's -- a word of the table and a word of the quad's record, each read by every lane from
+// global memory that nothing writes during the kernel; (2) ok, one LDS word behind C; (3) the reduction and the two
+// broadcasts, as in k_decode.  The loop's bounds and `order` are table words.  The width test that decides between
+// B-then-C and C alone compares a table word with a value every lane derived from table words.
+#define DEC_AXIS_LO 8   /* axis[f][n + DEC_AXIS_LO], n = -8 .. 15 */
+#define DEC_AXIS_N 24
+struct alignas(16) MultiStore {
+    double smp[DEC_BORDER_CAP][4];
+    double values[DEC_GRID_CAP * DEC_GRID_CAP];
+    double list[2][DEC_BITS_CAP];
+    double axis[FAM_MAX][DEC_AXIS_N];
+    GrayModel white;
+    double H[9];
+    GrayModel black;
+    signed char smpn[FAM_MAX][DEC_BORDER_CAP][2], bitn[FAM_MAX][DEC_BITS_CAP][2];
+    int ok;
+};
+static_assert(sizeof(MultiStore) == 7232, "k_decode_multi: the plan and the LDS allocation disagree");
+static_assert(DEC_GRID_CAP - 1 < DEC_AXIS_N - DEC_AXIS_LO && (DEC_GRID_CAP - 2) / 2 <= DEC_AXIS_LO, "k_decode_multi: a cell asl_family_check admits is off the axis");
+
+struct MultiSites {
+    const MultiStore &st;
+    int f;
+    __device__ __forceinline__ void sample(int lane, double *tagx, double *tagy) const
+    {
+        *tagx = st.axis[f][st.smpn[f][lane][0] + DEC_AXIS_LO]; *tagy = st.axis[f][st.smpn[f][lane][1] + DEC_AXIS_LO];
+    }
+    __device__ __forceinline__ void bit_cell(const FamilyDev &, int lane, int *bitx, int *bity) const { *bitx = st.bitn[f][lane][0]; *bity = st.bitn[f][lane][1]; }
+    __device__ __forceinline__ void bit(int lane, double *tagx, double *tagy) const
+    {
+        *tagx = st.axis[f][st.bitn[f][lane][0] + DEC_AXIS_LO]; *tagy = st.axis[f][st.bitn[f][lane][1] + DEC_AXIS_LO];
+    }
+};
+
+// decode_tag_sites for every family of the table.  Writes axis, smpn, bitn.
+__device__ __forceinline__ void decode_multi_tag_sites(MultiStore &st, const FamilyTabDev *tab, int nf, int lane)
+{
+    for (int f = 0; f < nf; f++) {
+        const int wb = tab->fam[f].width_at_border, nbits = tab->fam[f].nbits;
+        if (lane < DEC_AXIS_N) {
+            double tag01 = ((lane - DEC_AXIS_LO) + 0.5) / wb;
+            st.axis[f][lane] = 2 * (tag01 - 0.5);
+        }
+        if (lane < 8 * wb) {
+            const int pi = lane / wb, i = lane % wb;
+            const int across = (pi & 3) == 0 ? -1 : ((pi & 3) == 1 ? 0 : ((pi & 3) == 2 ? wb : wb - 1));  // the pattern's line
+            st.smpn[f][lane][0] = (signed char)(pi < 4 ? across : i);
+            st.smpn[f][lane][1] = (signed char)(pi < 4 ? i : across);
+        }
+        if (lane < nbits) {
+            st.bitn[f][lane][0] = (signed char)tab->fam[f].bit_x[lane];
+            st.bitn[f][lane][1] = (signed char)tab->fam[f].bit_y[lane];
+        }
+    }
+}
+
+template <int CH>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) k_decode_multi(const QuadRec *__restrict__ quads, const double *__restrict__ Hin,
+                                               const long long *__restrict__ counters, unsigned int max_clusters,
+                                               const uint8_t *__restrict__ frames, Geom g, const FamilyTabDev *__restrict__ tab, int maxhamming,
+                                               DetRec *dets, unsigned int max_dets, long long *wcounters, const unsigned int *__restrict__ quad_list)
+{
+    __shared__ MultiStore st;
+    const int lane = threadIdx.x;
+    const unsigned int nq = tail_quad_count(counters, max_clusters);
+    const int nf = min(tab->n, FAM_MAX);
+
+    decode_multi_tag_sites(st, tab, nf, lane);
+    for (unsigned int qi = blockIdx.x; qi < nq; qi += gridDim.x) {
+        __syncthreads();  // L
+        const unsigned int ci = quad_list[qi];
+        if (Hin[10 * (size_t)ci + 9] == 0.0) continue;  // (1) no quad, a polarity no family has, or singular homography
+        const unsigned long long qkey = quads[ci].key;
+        const int q_reversed = quads[ci].reversed_border;
+        const int fr = (int)(qkey >> 48);
+        const uint8_t *frame = frames + (size_t)fr * g.frame_pitch;
+        if (lane < 9) st.H[lane] = Hin[10 * (size_t)ci + lane];
+        __syncthreads();  // A
+        int models_wb = 0;  // the border width the gray models in the store were fitted at
+#pragma unroll 1
+        for (int k = 0; k < nf; k++) {
+            const int f = tab->order[k] & (FAM_MAX - 1);
+            const FamilyDev &fam = tab->fam[f];
+            if (fam.reversed_border != q_reversed) continue;  // (4) not a candidate for this quad
+            const MultiSites sites{st, f};
+            if (fam.width_at_border != models_wb) {
+                models_wb = fam.width_at_border;
+                decode_border_samples<CH>(st, sites, frame, g, fam, lane);
+                __syncthreads();  // B
+                decode_gray_models(st, fam, lane);
+            }
+            for (int i = lane; i < fam.total_width * fam.total_width; i += 64) st.values[i] = 0;
+            __syncthreads();  // C
+            if (!st.ok) continue;  // (2) the border's polarity at this width is not the quad's
+            const DecodeCell cell = decode_payload_values<CH>(st, sites, frame, g, fam, lane);
+            __syncthreads();  // D
+            const double sharp_v = decode_sharpen(st, fam, cell, lane);
+            unsigned long long rcode;
+            const DecodeScores sc = decode_scores(st, fam, sharp_v, lane, &rcode);
+            DecodeMatch m = fam.idx_nch > 0 ? decode_lookup_index(fam, rcode, maxhamming, lane) : decode_lookup_book(fam, rcode, maxhamming, lane);
+            const float margin = fminf(sc.white_score / sc.white_count, sc.black_score / sc.black_count);
+            if (!(margin >= 0) || m.hamming >= 255) continue;  // (3) no detection in this family
+            m.id += tab->id_base[f];
+            decode_emit(st, m, margin, fr, qkey, dets, max_dets, wcounters, lane);
+        }
+    }
 }

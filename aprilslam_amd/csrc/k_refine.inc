@@ -281,7 +281,7 @@ __device__ __forceinline__ void refine_hand_over(const RefineStore &st, double *
 // same for every lane; the loop-top barrier L keeps the next quad's writes behind this quad's last reads.
 template <int CH>
 __global__ void __launch_bounds__(64) k_refine(const QuadRec *__restrict__ quads, const long long *__restrict__ counters,
-                                               unsigned int max_clusters, const uint8_t *__restrict__ frames, Geom g, int fam_reversed,
+                                               unsigned int max_clusters, const uint8_t *__restrict__ frames, Geom g, int want_polarity /* bit 0: normal, bit 1: reversed */,
                                                int refine, double *__restrict__ Hout /* 10 doubles per cluster: the four corners, 0.25 / 0.5 */,
                                                const unsigned int *__restrict__ quad_list, double *__restrict__ edge_mom /* 4 x 6 per cluster */)
 {
@@ -299,7 +299,7 @@ __global__ void __launch_bounds__(64) k_refine(const QuadRec *__restrict__ quads
         const int q_valid = qp->valid, q_reversed = qp->reversed_border;
         if (lane == 0) Hout[10 * (size_t)ci + 9] = 0.0;
         if (!q_valid) continue;
-        if (fam_reversed != q_reversed) continue;
+        if (!((want_polarity >> (q_reversed ? 1 : 0)) & 1)) continue;
         const uint8_t *frame = frames + (size_t)(int)(qp->key >> 48) * g.frame_pitch;
         refine_load_corners(st, qp, g, lane);
         __syncthreads();  // A

@@ -67,7 +67,8 @@ class SLAM:
     (slam_graph.py:72-76 `update_world` is a stub, docs/api/core/SLAM.md:255-260).  It also keeps up to `keyframes`
     keyframes (every `keyframe_every`-th frame) of the whole run: when a tag comes back into view after it has been out
     of the window (a loop closure), `optimize_global()` re-solves the map over the keyframes and the window.
-    With window = 0 every method behaves exactly like the reference's."""
+    With window = 0 every method behaves exactly like the reference's.
+    tag_type may be a list of registered family names: one detector for all of them, global tag ids (TagDetector)."""
 
     def __init__(self, logger, camera_params, tag_type="tagStandard41h12", tag_size=0.06, detector=None,
                  visualizer=None, device=0, window=0, keyframes=64, keyframe_every=None):

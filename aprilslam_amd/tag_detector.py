@@ -30,7 +30,9 @@ class TagDetector:
 
     def __init__(self, camera_params, tag_type="tagStandard41h12", tag_size=0.06, device=0, id_limit=None, quad_sigma=0.0,
                  rectify=False, rectified_K=None):
-        """quad_sigma: the detector's blur (> 0) or sharpening (< 0) of the decimated image; the reference leaves it 0.
+        """tag_type: a family's name, or a list of registered names (one detector for all; ids are then global and the
+        detections carry 'family' and 'local_id', see apriltag).
+        quad_sigma: the detector's blur (> 0) or sharpening (< 0) of the decimated image; the reference leaves it 0.
         rectify: take every frame through the lens rectification first (asl_rectify_u8 / asl_rectify_frames_device with
         camera_params as the source camera), into a buffer this detector owns, and detect on the gray result -- for a lens
         strong enough to bend a tag's edges.  DETECTIONS ARE THEN IN RECTIFIED PIXELS (rectify.distort_points takes them back
@@ -64,9 +66,10 @@ class TagDetector:
         # the one get_pose() does on its own (float32-rounded corners -> asl_solve_pnp_batch), bit for bit
         dets, poses, _ = self.detector._det.detect_host(np.ascontiguousarray(a), K=self._K(), dist=self._dist(),
                                                         tag_size=self.tag_size)
-        out = [{"hamming": int(d["hamming"]), "margin": float(d["margin"]), "id": int(d["id"]),
-                "center": np.array(d["center"]), "lb-rb-rt-lt": np.array(d["corners"]),
-                "_pose": (np.array(d["corners"]), self._pose_key(), bool(p["ok"]), np.array(p["rvec"]), np.array(p["tvec"]))}
+        out = [dict({"hamming": int(d["hamming"]), "margin": float(d["margin"]), "id": int(d["id"]),
+                     "center": np.array(d["center"]), "lb-rb-rt-lt": np.array(d["corners"]),
+                     "_pose": (np.array(d["corners"]), self._pose_key(), bool(p["ok"]), np.array(p["rvec"]), np.array(p["tvec"]))},
+                    **self.detector.family_keys(int(d["id"])))  # a list of families: 'family' and 'local_id' as well
                for d, p in zip(dets, poses)]
         return sorted(out, key=lambda d: d['id'])
 

@@ -97,9 +97,33 @@ int asl_family_check(const asl_family *fam);
 /* asl_detector_create for a caller's table (the other arguments as there).  The family must pass asl_family_check.
    The detector copies everything it needs: the caller's arrays may go away after the call.  The table is the caller's
    truth, so the new detector decodes all of its ids; asl_detector_set_id_limit narrows that, bounded by fam->ncodes.
-   One detector decodes one family (a detection carries no family field): use one detector per family. */
+   A detection carries no family field: a detector of several families (asl_detector_create_families) tells them apart
+   by id ranges. */
 int asl_detector_create_family(const asl_family *fam, int nthreads, int maxhamming, float decimate, float blur,
                                int refine_edges, int device, asl_detector **out);
+
+/* Several families in one detector, decoded in one pass.  A tag with local id k of family i is reported as
+   id_base[i] + k: asl_detection, asl_pose and asl_obs are what they are for one family, and the de-duplication, the
+   (frame, id) order, asl_pack_observations_device, tag maps and every solver work on that global id.  Upstream's
+   semantics: the quad fit's minimum tag width is the smallest of the families' max(3, width_at_border / decimate); both
+   border polarities are wanted if the families' reversed_border differ; a quad is decoded against every family of its
+   polarity, and every family that accepts it yields a detection of its own (two families that both accept a quad give
+   two detections with different ids; there is no arbitration between families).  maxhamming is one value for all. */
+#define ASL_MAX_FAMILIES 4
+/* Whether asl_detector_create_families takes the set.  A pure host function, like asl_family_check.  ASL_EINVAL, with
+   asl_last_error() naming the family's index and the field, for n_fams outside 1..ASL_MAX_FAMILIES, a NULL array, a
+   family asl_family_check refuses, a negative id_base, two id ranges [id_base[i], id_base[i] + ncodes_i) that overlap,
+   and a range that ends above 65536 (the de-duplication key holds the id in 16 bits). */
+int asl_families_check(const asl_family *fams, const int32_t *id_base, int n_fams);
+/* The other arguments as in asl_detector_create_family; the set must pass asl_families_check.  The detector copies what
+   it needs and decodes every id of every table: asl_detector_set_id_limit on a detector of more than one family is
+   ASL_EINVAL.  Everything else works as on a one-family detector (the fused PnP with its one tag_size: families printed
+   at different sizes are what the per-tag sizes of a tag map are for). */
+int asl_detector_create_families(const asl_family *fams, const int32_t *id_base, int n_fams, int nthreads, int maxhamming,
+                                 float decimate, float blur, int refine_edges, int device, asl_detector **out);
+/* Which family a reported id belongs to, and its id there.  A host function.  ASL_EINVAL for an id in no family's
+   range; a one-family detector answers (0, id) for the ids of its table. */
+int asl_detector_family_of(const asl_detector *det, int id, int *family_index, int *local_id);
 
 /* Which ids the decoder may return, ASL_EINVAL beyond the detector's table.  For a detector made with
    asl_detector_create: only ids 0..4 of tagStandard41h12 are pinned by the reference (its
