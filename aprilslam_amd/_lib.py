@@ -51,7 +51,8 @@ EXPORTS = [
     "asl_localize_frames_device", "asl_localize_batch", "asl_localize_cov_frames_device", "asl_localize_cov_batch",
     "asl_pose_cov_device", "asl_solve_pnp_cov_batch", "asl_calibrate_frames_device", "asl_calibrate_batch",
     "asl_localize_rig_frames_device", "asl_localize_rig_cov_frames_device", "asl_localize_rig_batch", "asl_localize_rig_cov_batch",
-    "asl_map_frames_device", "asl_map_batch", "asl_map_robust_frames_device", "asl_map_robust_batch", "asl_map_rig_frames_device", "asl_map_rig_batch", "asl_smooth_frames_device", "asl_smooth_batch", "asl_smooth_cov_frames_device", "asl_smooth_cov_batch",
+    "asl_map_frames_device", "asl_map_batch", "asl_map_robust_frames_device", "asl_map_robust_batch", "asl_map_rig_frames_device", "asl_map_rig_batch", "asl_map_sized_frames_device", "asl_map_sized_batch",
+    "asl_map_rig_sized_frames_device", "asl_map_rig_sized_batch", "asl_smooth_frames_device", "asl_smooth_batch", "asl_smooth_cov_frames_device", "asl_smooth_cov_batch",
     "asl_smooth_sequences_device", "asl_smooth_sequences_batch", "asl_smooth_robust_sequences_device", "asl_smooth_robust_sequences_batch",
     "asl_smooth_timed_sequences_device", "asl_smooth_timed_sequences_batch",
     "asl_smooth_rig_sequences_device", "asl_smooth_rig_sequences_batch",
@@ -217,6 +218,11 @@ def load():
     mapping_rig = [vp, vp, i32, i32, i32, i32, vp, dbl] + mapping_robust[9:]    # detector, obs, n_cams, n_frames, max_tags, n_ids, rig, tag_size, world_id, ...
     L.asl_map_rig_frames_device.argtypes = mapping_rig + [vp]
     L.asl_map_rig_batch.argtypes = mapping_rig
+    fp = C.POINTER(C.c_float)                                     # tag_sizes, after tag_size: a host array in the device forms too
+    L.asl_map_sized_frames_device.argtypes = mapping_robust[:9] + [fp] + mapping_robust[9:] + [vp]
+    L.asl_map_sized_batch.argtypes = mapping_robust[:9] + [fp] + mapping_robust[9:]
+    L.asl_map_rig_sized_frames_device.argtypes = mapping_rig[:8] + [fp] + mapping_rig[8:] + [vp]
+    L.asl_map_rig_sized_batch.argtypes = mapping_rig[:8] + [fp] + mapping_rig[8:]
     smooth, seqs = [vp] + obs_block + tag_map + camera + [vp], [C.POINTER(C.c_int32), i32]    # ..., seed; seq_start, n_seq
     solve = sigmas + [i32, vp, vp]                                # ..., max_iters, out, result
     L.asl_smooth_frames_device.argtypes = smooth + solve + [vp]
@@ -305,6 +311,24 @@ def _map_records(tag_map):
     if hasattr(tag_map, "as_records"):
         tag_map = tag_map.as_records()
     return np.ascontiguousarray(tag_map, dtype=MAP_TAG_DTYPE).ravel()
+
+
+def _size_table(tag_sizes, n_ids):
+    """(n_ids,) float32 table of the sized map calls from a {id: size} dict (ids >= n_ids are ignored, ids not named are 0:
+    the call's tag_size) or an array of n_ids sizes; the library refuses negative and non-finite entries"""
+    n = max(int(n_ids), 1)
+    if isinstance(tag_sizes, dict):
+        table = np.zeros(n, dtype=np.float32)
+        for i, size in tag_sizes.items():
+            if int(i) < 0:
+                raise ValueError("tag_sizes: tag id %d is negative" % int(i))
+            if int(i) < n:
+                table[int(i)] = size
+        return table
+    table = np.ascontiguousarray(tag_sizes, dtype=np.float32).ravel()
+    if len(table) != n:
+        raise ValueError("tag_sizes must be a {id: size} dict or an array of n_ids = %d sizes (got %d)" % (n, len(table)))
+    return table
 
 
 def _rig_records(rig):
@@ -636,18 +660,29 @@ class Detector:
                                                   float(tag_size), int(width), int(height), Kp, int(n_dist), int(flags), int(max_iters),
                                                   _ptr(result_ptr), _ptr(poses_ptr), _ptr(stream)))
 
-    def build_map(self, obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_std=True, huber_px=0.0, with_slot_weight=False):
+    def build_map(self, obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_std=True, huber_px=0.0, with_slot_weight=False,
+                  tag_sizes=None):
         """asl_map_batch: host records obs (n_frames, max_tags) OBS_DTYPE that see an unknown set of tags -> (MAP_RESULT_DTYPE
         record, (n_ids,) MAP_TAG_DTYPE world<-tag map, (n_ids, 6) tag std or None, (n_frames,) CAM_POSE_DTYPE world<-camera).
         huber_px > 0 or with_slot_weight: asl_map_robust_batch -- a Huber loss of that many pixels on every corner residual of
         the joint LM (0: the plain computation); the result's n_soft counts the down-weighted observations.
-        with_slot_weight: a fifth item, (n_frames, max_tags) doubles: a slot's smallest corner weight, 0 outside the solve."""
+        with_slot_weight: a fifth item, (n_frames, max_tags) doubles: a slot's smallest corner weight, 0 outside the solve.
+        tag_sizes ({id: size} or n_ids sizes; 0: tag_size): asl_map_sized_batch -- tags of different known sizes, each solved
+        at its own and returned with it in the map's size field."""
         o = _obs_records(obs)
         keep, Kp, dpp, nd = _camera(K, dist, square=True)
         res = np.zeros((), dtype=MAP_RESULT_DTYPE)
         tmap = np.zeros(max(int(n_ids), 1), dtype=MAP_TAG_DTYPE)
         std = np.zeros((max(int(n_ids), 1), 6), dtype=np.float64) if with_std else None
         poses = np.zeros(o.shape[0], dtype=CAM_POSE_DTYPE)
+        if tag_sizes is not None:
+            table = _size_table(tag_sizes, n_ids)
+            weight = np.zeros(o.shape, dtype=np.float64) if with_slot_weight else None
+            check(self._L.asl_map_sized_batch(self._h, _data(o), o.shape[0], o.shape[1], int(n_ids), Kp, dpp, nd, float(tag_size),
+                                              table.ctypes.data_as(C.POINTER(C.c_float)), int(world_id), float(huber_px), int(max_iters),
+                                              tmap.ctypes.data, std.ctypes.data if with_std else None, _data(poses), res.ctypes.data,
+                                              weight.ctypes.data if with_slot_weight else None))
+            return (res, tmap, std, poses, weight) if with_slot_weight else (res, tmap, std, poses)
         if not huber_px and not with_slot_weight:
             check(self._L.asl_map_batch(self._h, _data(o), o.shape[0], o.shape[1], int(n_ids), Kp, dpp, nd, float(tag_size), int(world_id), int(max_iters),
                                         tmap.ctypes.data, std.ctypes.data if with_std else None, _data(poses), res.ctypes.data))
@@ -659,12 +694,20 @@ class Detector:
         return (res, tmap, std, poses, weight) if with_slot_weight else (res, tmap, std, poses)
 
     def build_map_device(self, obs_ptr, n_frames, max_tags, n_ids, K, dist, tag_size, map_ptr, std_ptr, poses_ptr, result_ptr,
-                         world_id=-1, max_iters=30, stream=0, huber_px=0.0, slot_weight_ptr=0):
+                         world_id=-1, max_iters=30, stream=0, huber_px=0.0, slot_weight_ptr=0, tag_sizes=None):
         """asl_map_frames_device: obs_ptr (n_frames x max_tags asl_obs, e.g. from pack_observations_device), map_ptr (n_ids
         asl_map_tag, out), std_ptr (n_ids x 6 doubles or 0), poses_ptr (n_frames asl_cam_pose) and result_ptr (one
         asl_map_result) are device addresses; enqueued on `stream` after one wait for the problem size.
-        huber_px > 0 or slot_weight_ptr (n_frames x max_tags doubles): asl_map_robust_frames_device."""
+        huber_px > 0 or slot_weight_ptr (n_frames x max_tags doubles): asl_map_robust_frames_device.
+        tag_sizes ({id: size} or n_ids sizes, on the host): asl_map_sized_frames_device."""
         keep, Kp, dpp, nd = _camera(K, dist, square=True)
+        if tag_sizes is not None:
+            table = _size_table(tag_sizes, n_ids)
+            check(self._L.asl_map_sized_frames_device(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), int(n_ids), Kp, dpp, nd,
+                                                      float(tag_size), table.ctypes.data_as(C.POINTER(C.c_float)), int(world_id),
+                                                      float(huber_px), int(max_iters), _ptr(map_ptr), _opt_ptr(std_ptr), _ptr(poses_ptr),
+                                                      _ptr(result_ptr), _opt_ptr(slot_weight_ptr), _ptr(stream)))
+            return
         if huber_px or slot_weight_ptr:
             check(self._L.asl_map_robust_frames_device(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), int(n_ids), Kp, dpp, nd,
                                                        float(tag_size), int(world_id), float(huber_px), int(max_iters), _ptr(map_ptr),
@@ -674,10 +717,12 @@ class Detector:
                                             int(world_id), int(max_iters), _ptr(map_ptr), _opt_ptr(std_ptr), _ptr(poses_ptr),
                                             _ptr(result_ptr), _ptr(stream)))
 
-    def build_map_rig(self, obs, n_ids, rig, tag_size, world_id=-1, max_iters=30, with_std=True, huber_px=0.0, with_slot_weight=False):
+    def build_map_rig(self, obs, n_ids, rig, tag_size, world_id=-1, max_iters=30, with_std=True, huber_px=0.0, with_slot_weight=False,
+                      tag_sizes=None):
         """asl_map_rig_batch: host records obs (n_cams, n_frames, max_tags) OBS_DTYPE, camera-major, of a rig whose camera table
         is rig ((n_cams,) RIG_CAMERA_DTYPE, or a rig.Rig) -> build_map's items with poses = world<-rig per frame; huber_px as
-        there (0: the squared loss).  with_slot_weight: a fifth item, (n_cams, n_frames, max_tags) doubles."""
+        there (0: the squared loss).  with_slot_weight: a fifth item, (n_cams, n_frames, max_tags) doubles.  tag_sizes as
+        there: asl_map_rig_sized_batch."""
         o = np.ascontiguousarray(obs, dtype=OBS_DTYPE)
         if o.ndim != 3:
             raise ValueError("obs must be (n_cams, n_frames, max_tags) asl_obs records")
@@ -689,16 +734,31 @@ class Detector:
         std = np.zeros((max(int(n_ids), 1), 6), dtype=np.float64) if with_std else None
         poses = np.zeros(o.shape[1], dtype=CAM_POSE_DTYPE)
         weight = np.zeros(o.shape, dtype=np.float64) if with_slot_weight else None
+        if tag_sizes is not None:
+            table = _size_table(tag_sizes, n_ids)
+            check(self._L.asl_map_rig_sized_batch(self._h, _data(o), o.shape[0], o.shape[1], o.shape[2], int(n_ids), _data(r), float(tag_size),
+                                                  table.ctypes.data_as(C.POINTER(C.c_float)), int(world_id), float(huber_px), int(max_iters),
+                                                  tmap.ctypes.data, std.ctypes.data if with_std else None, _data(poses), res.ctypes.data,
+                                                  weight.ctypes.data if with_slot_weight else None))
+            return (res, tmap, std, poses, weight) if with_slot_weight else (res, tmap, std, poses)
         check(self._L.asl_map_rig_batch(self._h, _data(o), o.shape[0], o.shape[1], o.shape[2], int(n_ids), _data(r), float(tag_size), int(world_id),
                                         float(huber_px), int(max_iters), tmap.ctypes.data, std.ctypes.data if with_std else None, _data(poses),
                                         res.ctypes.data, weight.ctypes.data if with_slot_weight else None))
         return (res, tmap, std, poses, weight) if with_slot_weight else (res, tmap, std, poses)
 
     def build_map_rig_device(self, obs_ptr, n_cams, n_frames, max_tags, n_ids, rig_ptr, tag_size, map_ptr, std_ptr, poses_ptr, result_ptr,
-                             world_id=-1, max_iters=30, stream=0, huber_px=0.0, slot_weight_ptr=0):
+                             world_id=-1, max_iters=30, stream=0, huber_px=0.0, slot_weight_ptr=0, tag_sizes=None):
         """asl_map_rig_frames_device: obs_ptr (n_cams x n_frames x max_tags asl_obs, camera-major), rig_ptr (n_cams asl_rig_camera,
         complete when the call is made) and the outputs of build_map_device (slot_weight_ptr: n_cams x n_frames x max_tags
-        doubles or 0) are device addresses; enqueued on `stream` after one wait for the problem size."""
+        doubles or 0) are device addresses; enqueued on `stream` after one wait for the problem size.  tag_sizes ({id: size} or
+        n_ids sizes, on the host): asl_map_rig_sized_frames_device."""
+        if tag_sizes is not None:
+            table = _size_table(tag_sizes, n_ids)
+            check(self._L.asl_map_rig_sized_frames_device(self._h, _ptr(obs_ptr), int(n_cams), int(n_frames), int(max_tags), int(n_ids),
+                                                          _ptr(rig_ptr), float(tag_size), table.ctypes.data_as(C.POINTER(C.c_float)),
+                                                          int(world_id), float(huber_px), int(max_iters), _ptr(map_ptr), _opt_ptr(std_ptr),
+                                                          _ptr(poses_ptr), _ptr(result_ptr), _opt_ptr(slot_weight_ptr), _ptr(stream)))
+            return
         check(self._L.asl_map_rig_frames_device(self._h, _ptr(obs_ptr), int(n_cams), int(n_frames), int(max_tags), int(n_ids), _ptr(rig_ptr),
                                                 float(tag_size), int(world_id), float(huber_px), int(max_iters), _ptr(map_ptr), _opt_ptr(std_ptr),
                                                 _ptr(poses_ptr), _ptr(result_ptr), _opt_ptr(slot_weight_ptr), _ptr(stream)))

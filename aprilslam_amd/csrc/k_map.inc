@@ -37,6 +37,10 @@
 // a.obs_of), which hold the pair's first active view.  12 x 13 blocks of views of one pair are additive, so after each
 // linearisation k_map_fold adds the later views' blocks to the first one's, in view order (a.obs_next).  With one camera
 // every pair has one view, the two sets of lists are equal and nothing is folded.
+// Tags of different sizes (asl_map_*sized*, tests/map_sized_ref.py): the caller's per-id table (a.sizes; all 0 in every
+// other call) gives each tag its half side (a.tag_half, k_map_gather; map_tag_half's rule), which every pass that forms a
+// tag's corners reads in place of the call's, and a sized tag's PnP translation is multiplied by h / half wherever a
+// record proposes a pose (map_seed_scale: the chain, both sweeps' candidates).  Sizes are given, never solved for.
 // No atomics: every sum has a fixed order (wave butterflies, per-thread loops in list order, k_gn_cost's fixed tree), so the
 // same input gives the same bytes; frames without taking-part slots change no list, no index and no sum.
 
@@ -73,6 +77,8 @@ struct MapArgs {
     int *cam_ptr, *cam_obs, *ptag_ptr, *ptag_obs, *obs_of;  // the first active one of each (camera, tag) pair: lists and table
     int *obs_next;                                          // the pair's next active observation, -1 at the end
     double *W, *G;                                          // camera<-world, world<-tag: R row-major (9), t (3)
+    const float *sizes;                                     // per id: the tag's own side, 0: the call's tag_size (all 0 without a table)
+    double *tag_half;                                       // per tag: its half side (k_map_gather); the call's half for size 0
 };
 
 // ---- small helpers on 12-double poses
@@ -109,15 +115,26 @@ __device__ __forceinline__ void pk_to34(const double *A, double *T)
     for (int r = 0; r < 3; r++) { T[4 * r] = A[3 * r]; T[4 * r + 1] = A[3 * r + 1]; T[4 * r + 2] = A[3 * r + 2]; T[4 * r + 3] = A[9 + r]; }
 }
 
-// camera<-tag of a slot's PnP pose, or its mirrored planar minimum (loc_candidate against the identity)
-__device__ __forceinline__ void map_obs_pose(const ObsRec &o, bool mirror, double *A)
+// What a record's PnP pose, solved at the call's half, is for a tag of half side h: the rotation holds and the translation
+// is short by half / h (k_localize.inc: loc_solve_frame).  1 exactly for a tag without a size, which takes the unscaled path.
+__device__ __forceinline__ double map_seed_scale(double h, double half) { return h == half ? 1.0 : h / half; }
+
+__device__ __forceinline__ void map_scale_obs(double *To, double k)
+{
+    if (k != 1.0) { To[3] *= k; To[7] *= k; To[11] *= k; }
+}
+
+// camera<-tag of a slot's PnP pose with its translation times k (map_seed_scale), or the mirrored planar minimum of that
+// (loc_candidate against the identity)
+__device__ __forceinline__ void map_obs_pose(const ObsRec &o, double k, bool mirror, double *A)
 {
     double To[12], I34[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, R[9], t[3];
 #pragma unroll
-    for (int k = 0; k < 12; k++) To[k] = o.T[k];
+    for (int i = 0; i < 12; i++) To[i] = o.T[i];
+    map_scale_obs(To, k);
     loc_candidate(To, I34, mirror, R, t);
 #pragma unroll
-    for (int k = 0; k < 9; k++) A[k] = R[k];
+    for (int i = 0; i < 9; i++) A[i] = R[i];
     A[9] = t[0]; A[10] = t[1]; A[11] = t[2];
 }
 
@@ -177,8 +194,8 @@ __device__ __forceinline__ int map_scan(int n, Cnt cnt, int *s_part, int *out)
     return total;
 }
 
-// ---- gather: one workgroup
-__global__ void __launch_bounds__(MAP_WG) k_map_gather(MapArgs a)
+// ---- gather: one workgroup.  half: the call's; a tag's own is map_tag_half's (double)(size * 0.5f)
+__global__ void __launch_bounds__(MAP_WG) k_map_gather(MapArgs a, double half)
 {
     __shared__ int s_part[MAP_WG + 1];
     const int tid = threadIdx.x, S = a.max_tags, NR = a.n_rig;
@@ -229,7 +246,11 @@ __global__ void __launch_bounds__(MAP_WG) k_map_gather(MapArgs a)
         }
     }
     for (int i = tid; i < a.n_ids; i += MAP_WG)
-        if (a.seen[i]) a.tag_id[a.id_tag[i]] = i;
+        if (a.seen[i]) {
+            const float sz = a.sizes[i];
+            a.tag_id[a.id_tag[i]] = i;
+            a.tag_half[a.id_tag[i]] = sz > 0.0f ? (double)(sz * 0.5f) : half;
+        }
     __syncthreads();
     if (tid == 0) {
         a.cam_ptr0[n_cams] = n_obs;
@@ -305,7 +326,7 @@ __global__ void __launch_bounds__(MAP_WG) k_map_csr(MapArgs a, int n_cams, int n
 // inv(E_c) T_obs inv(G) and the tag's inv(E_c W) T_obs (LocRig::candidate, camera_pose); the frame half walks the views in
 // (camera, slot) order, so a tie of area and tag keeps the lower camera, the tag half in observation order.
 template <bool RIG>
-__global__ void __launch_bounds__(MAP_WG) k_map_chain(MapArgs a, int n_cams, int n_tags, int n_obs, int wt)
+__global__ void __launch_bounds__(MAP_WG) k_map_chain(MapArgs a, int n_cams, int n_tags, int n_obs, int wt, double half)
 {
     __shared__ int s_changed;
     const int tid = threadIdx.x, S = a.max_tags;
@@ -328,7 +349,7 @@ __global__ void __launch_bounds__(MAP_WG) k_map_chain(MapArgs a, int n_cams, int
             }
             if (bm < 0) continue;
             double To[12], Gi[12];
-            map_obs_pose(a.obs[a.obs_slot[bm]], false, To);
+            map_obs_pose(a.obs[a.obs_slot[bm]], map_seed_scale(a.tag_half[bt], half), false, To);
             pk_inv(a.G + 12 * (size_t)bt, Gi);
             if constexpr (RIG) {
                 double Ei[12], Tc[12];
@@ -356,7 +377,7 @@ __global__ void __launch_bounds__(MAP_WG) k_map_chain(MapArgs a, int n_cams, int
             if (bm < 0) continue;
             double To[12], Wv[12], Wi[12];
             CamDev unused{};
-            map_obs_pose(a.obs[a.obs_slot[bm]], false, To);
+            map_obs_pose(a.obs[a.obs_slot[bm]], map_seed_scale(a.tag_half[j], half), false, To);
             map_view<RIG>(a, unused, bm, a.W + 12 * (size_t)a.obs_cam[bm], unused, Wv);
             pk_inv(Wv, Wi);
             pk_mul(Wi, To, a.G + 12 * (size_t)j);
@@ -398,7 +419,7 @@ __global__ void __launch_bounds__(64) k_map_sweep_cam(MapArgs a, CamDev cam)
         npart++;
         double M[12];
         pk_to34(a.G + 12 * (size_t)a.obs_tag[m], M);
-        loc_gather_slot(L, s, M, cam.half, fo->corners);
+        loc_gather_slot(L, s, M, a.tag_half[a.obs_tag[m]], fo->corners);
         if (fo->flags & 2) L.area[s] = loc_area(fo->corners);
     }
     __syncthreads();
@@ -418,9 +439,11 @@ __global__ void __launch_bounds__(64) k_map_sweep_cam(MapArgs a, CamDev cam)
     auto make = [&](int s) {
         const ObsRec *fo = rec(s);
         double To[12], M[12];
-        pk_to34(a.G + 12 * (size_t)a.obs_tag[a.slot_obs[fo - a.obs]], M);
+        const int j = a.obs_tag[a.slot_obs[fo - a.obs]];
+        pk_to34(a.G + 12 * (size_t)j, M);
 #pragma unroll
         for (int i = 0; i < 12; i++) To[i] = fo->T[i];
+        map_scale_obs(To, map_seed_scale(a.tag_half[j], cam.half));
         return [=](bool mirror, double *C) {
             if constexpr (RIG) rig.candidate(s, To, M, mirror, C, C + 9);
             else loc_candidate(To, M, mirror, C, C + 9);
@@ -434,11 +457,11 @@ __global__ void __launch_bounds__(64) k_map_sweep_cam(MapArgs a, CamDev cam)
     }
 }
 
-// Total corner cost of world<-tag (R, t) over the tag's observations b..e of the active list, the cameras held; with NE
-// also the normal equations of the left update of the tag (packed lower triangle 21, then J^T r 6), identical in every lane.
+// Total corner cost of world<-tag (R, t), a tag of half side h, over its observations b..e of the active list, the cameras
+// held; with NE also the normal equations of the left update of the tag (packed lower triangle 21, then J^T r 6), identical in every lane.
 template <bool NE, bool RIG>
-__device__ __forceinline__ double map_tag_pass(const MapArgs &a, const CamDev &cam, const double *R, const double *t, int b, int e, int lane,
-                                               double *ne)
+__device__ __forceinline__ double map_tag_pass(const MapArgs &a, const CamDev &cam, double h, const double *R, const double *t, int b, int e,
+                                               int lane, double *ne)
 {
     double cost = 0, acc[27];
 #pragma unroll
@@ -449,7 +472,7 @@ __device__ __forceinline__ double map_tag_pass(const MapArgs &a, const CamDev &c
         double Wc[12];
         map_view<RIG>(a, cam, m, a.W + 12 * (size_t)a.obs_cam[m], c, Wc);
         const ObsRec &o = a.obs[a.obs_slot[m]];
-        const double ox = (q == 1 || q == 2) ? c.half : -c.half, oy = (q >= 2) ? c.half : -c.half;
+        const double ox = (q == 1 || q == 2) ? h : -h, oy = (q >= 2) ? h : -h;
         double X[3], P[3], uv[2], Jp[6];
 #pragma unroll
         for (int r = 0; r < 3; r++) X[r] = R[3 * r] * ox + R[3 * r + 1] * oy + t[r];
@@ -493,7 +516,8 @@ __global__ void __launch_bounds__(64) k_map_sweep_tag(MapArgs a, CamDev cam)
     if (a.tag_state[j] != 1) return;
     const int b = a.tag_ptr[j], e = a.tag_ptr[j + 1], n = e - b;
     if (n == 0) return;
-    auto score = [&](const double *P) { return map_tag_pass<false, RIG>(a, cam, P, P + 9, b, e, lane, nullptr); };
+    const double h = a.tag_half[j], ks = map_seed_scale(h, cam.half);
+    auto score = [&](const double *P) { return map_tag_pass<false, RIG>(a, cam, h, P, P + 9, b, e, lane, nullptr); };
     double P[12];
     const double *Gj = a.G + 12 * (size_t)j;
 #pragma unroll
@@ -514,7 +538,7 @@ __global__ void __launch_bounds__(64) k_map_sweep_tag(MapArgs a, CamDev cam)
         const ObsRec *rec = a.obs + a.obs_slot[m];
         return [=](bool mirror, double *C) {
             double To[12];
-            map_obs_pose(*rec, mirror, To);
+            map_obs_pose(*rec, ks, mirror, To);
             pk_mul(Wi, To, C);
         };
     };
@@ -557,6 +581,7 @@ __global__ void __launch_bounds__(64) k_map_flip(MapArgs a, CamDev cam, int wt)
     if (j == wt || a.tag_state[j] != 1) return;
     const int b = a.tag_ptr[j], e = a.tag_ptr[j + 1], n = e - b;
     if (n == 0) return;
+    const double h = a.tag_half[j];
     double G0[12], R0[9], t0[3], R1[9], t1[3];
     for (int i = 0; i < 12; i++) G0[i] = a.G[12 * (size_t)j + i];
     // the view where the tag is largest (ties: lower list position)
@@ -583,7 +608,7 @@ __global__ void __launch_bounds__(64) k_map_flip(MapArgs a, CamDev cam, int wt)
     for (int i = 0; i < 9; i++) { R0[i] = G0[i]; R1[i] = Gm[i]; }
     for (int i = 0; i < 3; i++) { t0[i] = G0[9 + i]; t1[i] = Gm[9 + i]; }
     auto pass = [&](const double *R, const double *t, auto ne_tag, double *ne) {
-        return map_tag_pass<decltype(ne_tag)::value, RIG>(a, cam, R, t, b, e, lane, ne);
+        return map_tag_pass<decltype(ne_tag)::value, RIG>(a, cam, h, R, t, b, e, lane, ne);
     };
     const double c0 = pose_lm(pass, R0, t0);
     const double c1 = pose_lm(pass, R1, t1);
@@ -597,7 +622,7 @@ __global__ void __launch_bounds__(64) k_map_flip(MapArgs a, CamDev cam, int wt)
 
 // ---- behind the camera: one thread per camera.  A rig's frame stays with >= 2 distinct tags among its active views.
 template <bool RIG>
-__global__ void __launch_bounds__(64) k_map_behind(MapArgs a, int n_cams, double half)
+__global__ void __launch_bounds__(64) k_map_behind(MapArgs a, int n_cams)
 {
     const int c = blockIdx.x * 64 + threadIdx.x;
     if (c >= n_cams || a.cam_state[c] != 1) return;
@@ -608,6 +633,7 @@ __global__ void __launch_bounds__(64) k_map_behind(MapArgs a, int n_cams, double
         CamDev unused{};
         map_view<RIG>(a, unused, m, a.W + 12 * (size_t)c, unused, Wc);
         const double *Gj = a.G + 12 * (size_t)a.obs_tag[m];
+        const double half = a.tag_half[a.obs_tag[m]];
         bool ok = true;
         for (int q = 0; q < 4; q++) {
             const double ox = (q == 1 || q == 2) ? half : -half, oy = (q >= 2) ? half : -half;
@@ -702,7 +728,7 @@ __global__ void __launch_bounds__(256) k_map_linearize(MapArgs a, const double *
             add = LOC_BEHIND_COST;
         return res;
     };
-    const double c = gn_obs_block(W + 12 * (size_t)a.obs_cam[m], G + 12 * (size_t)a.obs_tag[m], cam.half, lane, row, D + (size_t)m * GN_DSTRIDE);
+    const double c = gn_obs_block(W + 12 * (size_t)a.obs_cam[m], G + 12 * (size_t)a.obs_tag[m], a.tag_half[a.obs_tag[m]], lane, row, D + (size_t)m * GN_DSTRIDE);
     if (lane == 0) cost_obs[m] = c;
 }
 
@@ -738,11 +764,12 @@ __global__ void __launch_bounds__(256) k_map_soft(MapArgs a, int n_obs, CamDev c
             wm = 1.0;
             const ObsRec &o = a.obs[a.obs_slot[m]];
             const double *Gj = a.G + 12 * (size_t)a.obs_tag[m];
+            const double h = a.tag_half[a.obs_tag[m]];
             CamDev cam;
             double Wc[12];
             map_view<RIG>(a, cam0, m, a.W + 12 * (size_t)a.obs_cam[m], cam, Wc);
             for (int q = 0; q < 4; q++) {
-                const double ox = (q == 1 || q == 2) ? cam.half : -cam.half, oy = (q >= 2) ? cam.half : -cam.half;
+                const double ox = (q == 1 || q == 2) ? h : -h, oy = (q >= 2) ? h : -h;
                 double X[3], P[3], uv[2];
 #pragma unroll
                 for (int r = 0; r < 3; r++) X[r] = Gj[3 * r] * ox + Gj[3 * r + 1] * oy + Gj[9 + r];
@@ -888,7 +915,7 @@ __global__ void __launch_bounds__(MAP_WG) k_map_finish(MapArgs a, int n_cams, in
         if (ok) pk_to34(a.G + 12 * (size_t)j, T);
         for (int k = 0; k < 12; k++) r->T[k] = ok ? T[k] : 0.0;
         r->valid = ok ? 1 : 0;
-        r->size = 0.0f;
+        r->size = ok ? a.sizes[i] : 0.0f;
         if (tag_std)
             for (int k = 0; k < 6; k++) tag_std[6 * (size_t)i + k] = (ok && j != wt && std_ok) ? sqrt(s2 * var[6 * j + k]) : 0.0;
     }

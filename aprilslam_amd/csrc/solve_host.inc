@@ -405,10 +405,11 @@ extern "C" int asl_calibrate_batch(asl_detector *d, const asl_obs *obs, int n_fr
 // and slot_weight may be NULL: not asked for.  The single-camera forms leave n_cams 0 and rig NULL; the rig forms
 // (asl_map_rig_*) give n_cams and the table and leave cam's K and dist NULL, n_dist 0; their block is camera-major and their
 // slot weights n_cams x n_frames x max_tags.  obs, rig, map, tag_std, poses, result and slot_weight are all host (*_batch) or
-// all device pointers (*_frames_device).
+// all device pointers (*_frames_device).  tag_sizes (the sized forms; NULL: no table) is a host array of n_ids in both,
+// like K and dist: the side of each id, 0 for the call's tag_size.
 struct MapCall {
     const void *obs; int n_cams, n_frames, max_tags, n_ids;
-    const void *rig; Camera cam;
+    const void *rig; Camera cam; const float *tag_sizes;
     int world_id; double huber_px; int max_iters;
     void *map, *tag_std, *poses, *result, *slot_weight;
 };
@@ -430,6 +431,9 @@ static int check_map_call(const asl_detector *d, const MapCall &c, bool device)
     if (c.world_id < -1 || c.world_id >= c.n_ids) return fail(ASL_EINVAL, "world_id must be -1 or in [0, n_ids) (got %d)", c.world_id);
     if (c.max_iters < 1 || c.max_iters > MAP_MAX_ITERS) return fail(ASL_EINVAL, "max_iters must be in [1, %d] (got %d)", MAP_MAX_ITERS, c.max_iters);
     if (!(c.huber_px >= 0) || !std::isfinite(c.huber_px)) return fail(ASL_EINVAL, "huber_px must be >= 0 and finite (got %g)", c.huber_px);
+    for (int i = 0; c.tag_sizes && i < c.n_ids; i++)
+        if (!(c.tag_sizes[i] >= 0) || !std::isfinite(c.tag_sizes[i]))
+            return fail(ASL_EINVAL, "tag_sizes[%d] must be 0 or positive and finite (got %g)", i, (double)c.tag_sizes[i]);
     if (!rig) return ASL_OK;
     asl_rig_camera tab[RIG_MAX_CAMS];
     if (device) {
@@ -447,15 +451,16 @@ static int launch_map_views(asl_detector *d, const MapCall &c, hipStream_t st)
     MapArgs a{};
     int *per_id, *per_frame, *per_cam, *per_obs, *csr;  // the grouped int arrays, one piece per group
     double *cams;
+    float *sizes;
     if (carve_ws(d->map_ws, [&](WsCarve &w) {
             a.head = w.take<MapHead>(1); per_id = w.take<int>(5 * (ni + 1)); per_frame = w.take<int>(4 * (nf + 1));
             per_cam = w.take<int>(4 * (nf + 1)); a.tag_state = w.take<int>(ni + 1); a.slot_obs = w.take<int>(nsl); per_obs = w.take<int>(5 * nsl);
             csr = w.take<int>(3 * nsl + nf + 2 * ni + 3); a.W = w.take<double>(12 * nf); a.G = w.take<double>(12 * ni);
-            cams = w.take<double>(RIG_CAM_DOUBLES * RIG_MAX_CAMS);
+            cams = w.take<double>(RIG_CAM_DOUBLES * RIG_MAX_CAMS); a.tag_half = w.take<double>(ni); sizes = w.take<float>(ni);
         }))
         return fail(ASL_ENOMEM, "map workspace allocation failed");
     a.obs = (const ObsRec *)c.obs; a.n_frames = c.n_frames; a.max_tags = c.max_tags; a.n_ids = c.n_ids; a.world_req = c.world_id;
-    a.n_rig = RIG ? c.n_cams : 1; a.cams = RIG ? cams : nullptr;
+    a.n_rig = RIG ? c.n_cams : 1; a.cams = RIG ? cams : nullptr; a.sizes = sizes;
     a.seen = per_id; a.id_tag = per_id + (ni + 1); a.tag_id = per_id + 2 * (ni + 1); a.tmp = per_id + 3 * (ni + 1); a.tmp2 = per_id + 4 * (ni + 1);
     a.fr_npart = per_frame; a.fr_cam = per_frame + (nf + 1); a.fr_obs0 = per_frame + 2 * (nf + 1); a.fr_ndist = per_frame + 3 * (nf + 1);
     a.cam_frame = per_cam; a.cam_ptr0 = per_cam + (nf + 1); a.cam_state = per_cam + 2 * (nf + 1); a.cam_seed = per_cam + 3 * (nf + 1);
@@ -466,7 +471,10 @@ static int launch_map_views(asl_detector *d, const MapCall &c, hipStream_t st)
     const CamDev cam = make_cam(d, RIG ? no_K : c.cam.K, c.cam.dist, c.cam.n_dist, c.cam.tag_size);   // a rig: for its half alone
     if (RIG) hipLaunchKernelGGL(k_map_rig_table, dim3(1), dim3(ASL_WAVE), 0, st, cams, (const RigCamRec *)c.rig, c.n_cams);
 
-    hipLaunchKernelGGL(k_map_gather, dim3(1), dim3(MAP_WG), 0, st, a);
+    // the per-id sizes: the caller's table or, without one, zeros (read before the wait below returns)
+    if (c.tag_sizes) HIPCHK(hipMemcpyAsync(sizes, c.tag_sizes, sizeof(float) * ni, hipMemcpyHostToDevice, st));
+    else HIPCHK(hipMemsetAsync(sizes, 0, sizeof(float) * ni, st));
+    hipLaunchKernelGGL(k_map_gather, dim3(1), dim3(MAP_WG), 0, st, a, cam.half);
     MapHead h;
     HIPCHK(hipMemcpyAsync(&h, a.head, sizeof h, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));  // the one wait before the end: the reduced system is sized by the tags seen
@@ -506,7 +514,7 @@ static int launch_map_views(asl_detector *d, const MapCall &c, hipStream_t st)
 
     range_push("map: seed");
     hipLaunchKernelGGL(k_map_csr, dim3(1), wg, 0, st, a, NC, NT);
-    hipLaunchKernelGGL(k_map_chain<RIG>, dim3(1), wg, 0, st, a, NC, NT, NM, WT);
+    hipLaunchKernelGGL(k_map_chain<RIG>, dim3(1), wg, 0, st, a, NC, NT, NM, WT, cam.half);
     hipLaunchKernelGGL(k_map_csr, dim3(1), wg, 0, st, a, NC, NT);
     for (int sw = 0; sw < 2; sw++) {
         hipLaunchKernelGGL(k_map_sweep_cam<RIG>, dim3(NC), dim3(ASL_WAVE), loc_lds_bytes(a.n_rig * c.max_tags), st, a, cam);
@@ -514,7 +522,7 @@ static int launch_map_views(asl_detector *d, const MapCall &c, hipStream_t st)
     }
     hipLaunchKernelGGL(k_map_gauge, dim3(1), wg, 0, st, a, NC, NT, WT);
     hipLaunchKernelGGL(k_map_flip<RIG>, dim3(NT), dim3(ASL_WAVE), 0, st, a, cam, WT);
-    hipLaunchKernelGGL(k_map_behind<RIG>, dim3((NC + 63) / 64), dim3(64), 0, st, a, NC, cam.half);
+    hipLaunchKernelGGL(k_map_behind<RIG>, dim3((NC + 63) / 64), dim3(64), 0, st, a, NC);
     hipLaunchKernelGGL(k_map_csr, dim3(1), wg, 0, st, a, NC, NT);
     hipLaunchKernelGGL(k_map_lm_init, dim3(1), dim3(1), 0, st, (const MapHead *)a.head, lm, lm0);
     HIPCHK(hipMemsetAsync(b.flag, 0, 8, st));
@@ -582,21 +590,21 @@ extern "C" int asl_map_frames_device(asl_detector *d, const void *d_obs, int n_f
                                      int n_dist, double tag_size, int world_id, int max_iters, void *d_map, void *d_tag_std, void *d_poses,
                                      void *d_result, void *stream)
 {
-    return map_frames_device(d, {d_obs, 0, n_frames, max_tags, n_ids, nullptr, {K, dist, n_dist, tag_size}, world_id, 0.0, max_iters, d_map, d_tag_std, d_poses, d_result, nullptr}, stream);
+    return map_frames_device(d, {d_obs, 0, n_frames, max_tags, n_ids, nullptr, {K, dist, n_dist, tag_size}, nullptr, world_id, 0.0, max_iters, d_map, d_tag_std, d_poses, d_result, nullptr}, stream);
 }
 
 extern "C" int asl_map_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, int n_ids, const double *K, const double *dist,
                              int n_dist, double tag_size, int world_id, int max_iters, asl_map_tag *map, double *tag_std, asl_cam_pose *poses,
                              asl_map_result *result)
 {
-    return map_batch(d, {obs, 0, n_frames, max_tags, n_ids, nullptr, {K, dist, n_dist, tag_size}, world_id, 0.0, max_iters, map, tag_std, poses, result, nullptr});
+    return map_batch(d, {obs, 0, n_frames, max_tags, n_ids, nullptr, {K, dist, n_dist, tag_size}, nullptr, world_id, 0.0, max_iters, map, tag_std, poses, result, nullptr});
 }
 
 extern "C" int asl_map_robust_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, int n_ids, const double *K,
                                             const double *dist, int n_dist, double tag_size, int world_id, double huber_px, int max_iters,
                                             void *d_map, void *d_tag_std, void *d_poses, void *d_result, void *d_slot_weight, void *stream)
 {
-    return map_frames_device(d, {d_obs, 0, n_frames, max_tags, n_ids, nullptr, {K, dist, n_dist, tag_size}, world_id, huber_px, max_iters, d_map, d_tag_std, d_poses,
+    return map_frames_device(d, {d_obs, 0, n_frames, max_tags, n_ids, nullptr, {K, dist, n_dist, tag_size}, nullptr, world_id, huber_px, max_iters, d_map, d_tag_std, d_poses,
                                  d_result, d_slot_weight}, stream);
 }
 
@@ -604,7 +612,7 @@ extern "C" int asl_map_robust_batch(asl_detector *d, const asl_obs *obs, int n_f
                                     int n_dist, double tag_size, int world_id, double huber_px, int max_iters, asl_map_tag *map, double *tag_std,
                                     asl_cam_pose *poses, asl_map_result *result, double *slot_weight)
 {
-    return map_batch(d, {obs, 0, n_frames, max_tags, n_ids, nullptr, {K, dist, n_dist, tag_size}, world_id, huber_px, max_iters, map, tag_std, poses, result,
+    return map_batch(d, {obs, 0, n_frames, max_tags, n_ids, nullptr, {K, dist, n_dist, tag_size}, nullptr, world_id, huber_px, max_iters, map, tag_std, poses, result,
                          slot_weight});
 }
 
@@ -612,7 +620,7 @@ extern "C" int asl_map_rig_frames_device(asl_detector *d, const void *d_obs, int
                                          double tag_size, int world_id, double rig_huber_px, int max_iters, void *d_map, void *d_tag_std,
                                          void *d_poses, void *d_result, void *d_slot_weight, void *stream)
 {
-    return map_frames_device(d, {d_obs, n_cams, n_frames, max_tags, n_ids, d_rig, {nullptr, nullptr, 0, tag_size}, world_id, rig_huber_px, max_iters,
+    return map_frames_device(d, {d_obs, n_cams, n_frames, max_tags, n_ids, d_rig, {nullptr, nullptr, 0, tag_size}, nullptr, world_id, rig_huber_px, max_iters,
                                  d_map, d_tag_std, d_poses, d_result, d_slot_weight}, stream);
 }
 
@@ -620,8 +628,44 @@ extern "C" int asl_map_rig_batch(asl_detector *d, const asl_obs *obs, int n_cams
                                  double tag_size, int world_id, double rig_huber_px, int max_iters, asl_map_tag *map, double *tag_std,
                                  asl_cam_pose *poses, asl_map_result *result, double *slot_weight)
 {
-    return map_batch(d, {obs, n_cams, n_frames, max_tags, n_ids, rig, {nullptr, nullptr, 0, tag_size}, world_id, rig_huber_px, max_iters, map, tag_std,
+    return map_batch(d, {obs, n_cams, n_frames, max_tags, n_ids, rig, {nullptr, nullptr, 0, tag_size}, nullptr, world_id, rig_huber_px, max_iters, map, tag_std,
                          poses, result, slot_weight});
+}
+
+// The sized forms: the robust and the rig argument lists with the per-id size table after tag_size.
+extern "C" int asl_map_sized_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, int n_ids, const double *K,
+                                           const double *dist, int n_dist, double tag_size, const float *tag_sizes, int world_id,
+                                           double sized_huber_px, int max_iters, void *d_map, void *d_tag_std, void *d_poses, void *d_result,
+                                           void *d_slot_weight, void *stream)
+{
+    return map_frames_device(d, {d_obs, 0, n_frames, max_tags, n_ids, nullptr, {K, dist, n_dist, tag_size}, tag_sizes, world_id, sized_huber_px, max_iters,
+                                 d_map, d_tag_std, d_poses, d_result, d_slot_weight}, stream);
+}
+
+extern "C" int asl_map_sized_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, int n_ids, const double *K, const double *dist,
+                                   int n_dist, double tag_size, const float *tag_sizes, int world_id, double sized_huber_px, int max_iters,
+                                   asl_map_tag *map, double *tag_std, asl_cam_pose *poses, asl_map_result *result, double *slot_weight)
+{
+    return map_batch(d, {obs, 0, n_frames, max_tags, n_ids, nullptr, {K, dist, n_dist, tag_size}, tag_sizes, world_id, sized_huber_px, max_iters, map,
+                         tag_std, poses, result, slot_weight});
+}
+
+extern "C" int asl_map_rig_sized_frames_device(asl_detector *d, const void *d_obs, int n_cams, int n_frames, int max_tags, int n_ids,
+                                               const void *d_rig, double tag_size, const float *tag_sizes, int world_id, double sized_huber_px,
+                                               int max_iters, void *d_map, void *d_tag_std, void *d_poses, void *d_result, void *d_slot_weight,
+                                               void *stream)
+{
+    return map_frames_device(d, {d_obs, n_cams, n_frames, max_tags, n_ids, d_rig, {nullptr, nullptr, 0, tag_size}, tag_sizes, world_id, sized_huber_px,
+                                 max_iters, d_map, d_tag_std, d_poses, d_result, d_slot_weight}, stream);
+}
+
+extern "C" int asl_map_rig_sized_batch(asl_detector *d, const asl_obs *obs, int n_cams, int n_frames, int max_tags, int n_ids,
+                                       const asl_rig_camera *rig, double tag_size, const float *tag_sizes, int world_id, double sized_huber_px,
+                                       int max_iters, asl_map_tag *map, double *tag_std, asl_cam_pose *poses, asl_map_result *result,
+                                       double *slot_weight)
+{
+    return map_batch(d, {obs, n_cams, n_frames, max_tags, n_ids, rig, {nullptr, nullptr, 0, tag_size}, tag_sizes, world_id, sized_huber_px, max_iters, map,
+                         tag_std, poses, result, slot_weight});
 }
 
 // ---- sequence localisation with a motion prior (k_smooth.inc)

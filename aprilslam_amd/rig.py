@@ -7,7 +7,7 @@ mounting.  A frame index is one instant for all cameras.
 
     RigCamera       one camera: K, dist (0, 4 or 5 coefficients), T_cam_rig = camera<-rig 4x4 (the mounting)
     Rig             the cameras in block order; as_records() -> RIG_CAMERA_DTYPE (asl_rig_camera), save / load,
-                    localize(), localize_sequence() / localize_sequences(), build_map(), from_camera_poses()
+                    localize(), localize_sequence() / localize_sequences(), build_map() / build_map_sized(), from_camera_poses()
 
 Consecutive frames of the rig solved together under a random-walk motion prior (asl_smooth_rig_sequences_batch, k_smooth.inc):
 Rig.localize_sequence and Rig.localize_sequences return smooth.SmoothResult, its poses the rig's (world<-rig).  A frame in
@@ -112,11 +112,18 @@ class Rig:
         world tag world_id, default the lowest id seen, at the identity), the per-tag std and one pose per frame,
         camera_poses = world<-rig.  Every camera's views enter one solve through the mountings, which are taken as exact, so
         tags that no single camera sees together share one map.  huber_px > 0: a Huber loss of that many pixels on every
-        corner residual; the result's soft_slots() are then (camera, frame, slot, id, weight)."""
+        corner residual; the result's soft_slots() are then (camera, frame, slot, id, weight).  Tags of different known
+        sizes: build_map_sized."""
+        return self.build_map_sized(det, obs, n_ids, tag_size, None, world_id=world_id, max_iters=max_iters, with_std=with_std, huber_px=huber_px)
+
+    def build_map_sized(self, det, obs, n_ids, tag_size, tag_sizes, world_id=-1, max_iters=30, with_std=True, huber_px=0.0):
+        """build_map for tags of different known sizes (asl_map_rig_sized_batch): tag_sizes is a {id: size} dict or an array of
+        n_ids sizes, 0 or an id not named standing for tag_size (None: build_map itself).  Every tag is solved at its own
+        size and the result's tag_map carries the sizes, so that localize() and localize_sequences() against it honour them."""
         from .mapping import MapResult
         o = self._block(obs)
         out = det.build_map_rig(o, n_ids, self.as_records(), tag_size, world_id=world_id, max_iters=max_iters, with_std=with_std,
-                                huber_px=huber_px, with_slot_weight=bool(huber_px))
+                                huber_px=huber_px, with_slot_weight=bool(huber_px), tag_sizes=tag_sizes)
         return MapResult(*out, slot_ids=o["id"] if huber_px else None)
 
     def _block(self, obs):

@@ -302,13 +302,16 @@ class TagDetector:
                                                 max_iters=max_iters)
         return CalibrationResult(res, cam, n_dist)
 
-    def build_map(self, frames, world_id=None, max_iters=30, with_std=True, huber_px=0.0):
+    def build_map(self, frames, world_id=None, max_iters=30, with_std=True, huber_px=0.0, tag_sizes=None):
         """Host frames ((n, H, W, 3) BGR or (n, H, W) gray uint8, or a list of them) that see an unknown set of tags ->
         mapping.MapResult: the tags' world<-tag poses (tag_map, world tag world_id, default the lowest id seen), every
         frame's camera pose and a per-tag std.  Detect with this detector's camera model and tag size, pack (asl_obs
         records) and map (asl_map_batch).  huber_px > 0: a Huber loss of that many pixels on every corner residual of
         the joint solve (asl_map_robust_batch), so that a slipped corner or a mis-decoded id is down-weighted instead
-        of bending the map; the result then has n_soft, slot_weight and soft_slots()."""
+        of bending the map; the result then has n_soft, slot_weight and soft_slots().  tag_sizes ({id: size}, or an
+        array indexed by id that covers every id seen): tags whose side is not the detector's tag_size (0, or an id
+        not named: tag_size), each solved at its own (asl_map_sized_batch); result.tag_map carries the sizes, so that
+        localize() and localize_sequence() against it, or against the file tag_map.save() writes, honour them."""
         from .dist import pack_observations
         from .mapping import MapResult
         if self.camera_matrix is None:
@@ -325,8 +328,14 @@ class TagDetector:
         mt = max(1, min(256, int(npf.max()) if len(npf) else 1))
         obs = pack_observations(dets, poses, npf, mt)
         n_ids = int(max(1, obs["id"].max() + 1 if obs.size else 1))
+        if tag_sizes is not None and not isinstance(tag_sizes, dict):
+            table = np.asarray(tag_sizes, dtype=np.float32).ravel()
+            if len(table) < n_ids:
+                raise ValueError("tag_sizes has %d entries; the frames hold ids up to %d" % (len(table), n_ids - 1))
+            tag_sizes = table[:n_ids]
         out = self.detector._det.build_map(obs, n_ids, self._K(), dist, self.tag_size, world_id=-1 if world_id is None else int(world_id),
-                                           max_iters=max_iters, with_std=with_std, huber_px=huber_px, with_slot_weight=bool(huber_px))
+                                           max_iters=max_iters, with_std=with_std, huber_px=huber_px, with_slot_weight=bool(huber_px),
+                                           tag_sizes=tag_sizes)
         return MapResult(*out, slot_ids=obs["id"] if huber_px else None)
 
     def detect_batch_device(self, data_ptr, n_frames, channels, width, height, with_pose=True, stream=0, **kw):

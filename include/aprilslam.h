@@ -528,6 +528,50 @@ int asl_map_rig_batch(asl_detector *det, const asl_obs *obs, int n_cams, int n_f
                       const asl_rig_camera *rig, double tag_size, int world_id, double rig_huber_px, int max_iters,
                       asl_map_tag *map, double *tag_std, asl_cam_pose *poses, asl_map_result *result, double *slot_weight);
 
+/* Tag-map reconstruction for tags of different KNOWN sizes (large tags for far views, nested landing pads, two print
+   sizes in one survey): asl_map_robust_frames_device / asl_map_rig_frames_device with the side of every tag id stated by
+   the caller.  The poses are the unknowns; sizes are given, never estimated.  tag_sizes: n_ids float32 values, a HOST
+   array in the device forms too, like K and dist, read before the call returns; NULL: no table, the call is then the
+   robust / rig call to the byte.  The rule is the one of every solver that takes an asl_map_tag.size:
+     tag_sizes[id] == 0            the tag has the call's tag_size: h = float32(tag_size / 2), as in the other map calls
+     tag_sizes[id] > 0, finite     the tag's own side: h_id = (double)(tag_sizes[id] * 0.5f)
+     negative or not finite        ASL_EINVAL naming the id, nothing written or enqueued (a map entry with such a size is
+                                   an unmapped id to the localisation; here the table is the caller's own input)
+   The sizes enter in two places.  Corners: every pass that forms a tag's corners (+-h, +-h, 0) uses that tag's h: the
+   reseed sweeps of frames and of tags, the flip test with its pose-only LM, the behind-camera test, the joint LM's
+   linearisation and costs (seed, every trial, final, per frame) and the robust call's weights.  Seeds: a record's PnP
+   pose T was solved at the call's tag_size, so for a sized tag it has the right rotation and a translation short by
+   tag_size / size; wherever T proposes a pose (the chain's frame and tag halves, the sweeps' candidates) a sized tag's
+   translation is first multiplied by k = h_id / h, and the mirrored planar minimum is formed after that.  A tag without
+   a size takes the unscaled path.  The flip test's mirror comes from the current map pose, not from T.  Everything else
+   is the robust / rig call's: the slots that take part, the used frames, the world tag and the gauge, statuses, the
+   lambda schedule and the stop rule, the Huber terms (sized_huber_px is the threshold every other layer calls huber_px;
+   0: the squared loss), the std's degrees of freedom, determinism.
+   d_map[id].size is tag_sizes[id] for every mapped id (0 where the table has 0) and unmapped ids stay all-zero, so the
+   block goes to asl_localize_* / asl_smooth_* / asl_calibrate_* as it is, with the same tag_size.  Ids that no used frame
+   sees may have any valid entry.  An all-zero table gives every output of the robust / rig call byte for byte; a table
+   whose every entry equals a float32 tag_size gives the same bytes but for d_map[].size.
+   tests/map_sized_ref.py states the computation. */
+int asl_map_sized_frames_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, int n_ids, const double *K,
+                                const double *dist, int n_dist, double tag_size, const float *tag_sizes, int world_id,
+                                double sized_huber_px, int max_iters, void *d_map, void *d_tag_std, void *d_poses, void *d_result,
+                                void *d_slot_weight, void *stream);
+/* The same computation on host records, synchronous; tag_std and slot_weight may be NULL. */
+int asl_map_sized_batch(asl_detector *det, const asl_obs *obs, int n_frames, int max_tags, int n_ids, const double *K,
+                        const double *dist, int n_dist, double tag_size, const float *tag_sizes, int world_id,
+                        double sized_huber_px, int max_iters, asl_map_tag *map, double *tag_std, asl_cam_pose *poses,
+                        asl_map_result *result, double *slot_weight);
+/* The rig forms: asl_map_rig_frames_device / asl_map_rig_batch with the same table and rule; a tag has one size, whichever
+   camera views it. */
+int asl_map_rig_sized_frames_device(asl_detector *det, const void *d_obs, int n_cams, int n_frames, int max_tags, int n_ids,
+                                    const void *d_rig, double tag_size, const float *tag_sizes, int world_id, double sized_huber_px,
+                                    int max_iters, void *d_map, void *d_tag_std, void *d_poses, void *d_result, void *d_slot_weight,
+                                    void *stream);
+int asl_map_rig_sized_batch(asl_detector *det, const asl_obs *obs, int n_cams, int n_frames, int max_tags, int n_ids,
+                            const asl_rig_camera *rig, double tag_size, const float *tag_sizes, int world_id, double sized_huber_px,
+                            int max_iters, asl_map_tag *map, double *tag_std, asl_cam_pose *poses, asl_map_result *result,
+                            double *slot_weight);
+
 /* ---- sequence localisation: the camera poses of one camera's consecutive frames against a fixed map, solved together
    under a random-walk motion prior, so that EVERY frame gets a pose: frames without a mapped tag are carried by their
    neighbours, a single-tag frame cannot end in its mirrored planar minimum alone, and corner noise is averaged. */
