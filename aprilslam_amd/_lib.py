@@ -671,27 +671,8 @@ class Detector:
         at its own and returned with it in the map's size field."""
         o = _obs_records(obs)
         keep, Kp, dpp, nd = _camera(K, dist, square=True)
-        res = np.zeros((), dtype=MAP_RESULT_DTYPE)
-        tmap = np.zeros(max(int(n_ids), 1), dtype=MAP_TAG_DTYPE)
-        std = np.zeros((max(int(n_ids), 1), 6), dtype=np.float64) if with_std else None
-        poses = np.zeros(o.shape[0], dtype=CAM_POSE_DTYPE)
-        if tag_sizes is not None:
-            table = _size_table(tag_sizes, n_ids)
-            weight = np.zeros(o.shape, dtype=np.float64) if with_slot_weight else None
-            check(self._L.asl_map_sized_batch(self._h, _data(o), o.shape[0], o.shape[1], int(n_ids), Kp, dpp, nd, float(tag_size),
-                                              table.ctypes.data_as(C.POINTER(C.c_float)), int(world_id), float(huber_px), int(max_iters),
-                                              tmap.ctypes.data, std.ctypes.data if with_std else None, _data(poses), res.ctypes.data,
-                                              weight.ctypes.data if with_slot_weight else None))
-            return (res, tmap, std, poses, weight) if with_slot_weight else (res, tmap, std, poses)
-        if not huber_px and not with_slot_weight:
-            check(self._L.asl_map_batch(self._h, _data(o), o.shape[0], o.shape[1], int(n_ids), Kp, dpp, nd, float(tag_size), int(world_id), int(max_iters),
-                                        tmap.ctypes.data, std.ctypes.data if with_std else None, _data(poses), res.ctypes.data))
-            return res, tmap, std, poses
-        weight = np.zeros(o.shape, dtype=np.float64) if with_slot_weight else None
-        check(self._L.asl_map_robust_batch(self._h, _data(o), o.shape[0], o.shape[1], int(n_ids), Kp, dpp, nd, float(tag_size), int(world_id),
-                                           float(huber_px), int(max_iters), tmap.ctypes.data, std.ctypes.data if with_std else None, _data(poses),
-                                           res.ctypes.data, weight.ctypes.data if with_slot_weight else None))
-        return (res, tmap, std, poses, weight) if with_slot_weight else (res, tmap, std, poses)
+        return self._map_host(o, o.shape[0], n_ids, [o.shape[0], o.shape[1]], [Kp, dpp, nd], False, tag_size, tag_sizes, world_id, huber_px,
+                              max_iters, with_std, with_slot_weight)
 
     def build_map_device(self, obs_ptr, n_frames, max_tags, n_ids, K, dist, tag_size, map_ptr, std_ptr, poses_ptr, result_ptr,
                          world_id=-1, max_iters=30, stream=0, huber_px=0.0, slot_weight_ptr=0, tag_sizes=None):
@@ -701,21 +682,8 @@ class Detector:
         huber_px > 0 or slot_weight_ptr (n_frames x max_tags doubles): asl_map_robust_frames_device.
         tag_sizes ({id: size} or n_ids sizes, on the host): asl_map_sized_frames_device."""
         keep, Kp, dpp, nd = _camera(K, dist, square=True)
-        if tag_sizes is not None:
-            table = _size_table(tag_sizes, n_ids)
-            check(self._L.asl_map_sized_frames_device(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), int(n_ids), Kp, dpp, nd,
-                                                      float(tag_size), table.ctypes.data_as(C.POINTER(C.c_float)), int(world_id),
-                                                      float(huber_px), int(max_iters), _ptr(map_ptr), _opt_ptr(std_ptr), _ptr(poses_ptr),
-                                                      _ptr(result_ptr), _opt_ptr(slot_weight_ptr), _ptr(stream)))
-            return
-        if huber_px or slot_weight_ptr:
-            check(self._L.asl_map_robust_frames_device(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), int(n_ids), Kp, dpp, nd,
-                                                       float(tag_size), int(world_id), float(huber_px), int(max_iters), _ptr(map_ptr),
-                                                       _opt_ptr(std_ptr), _ptr(poses_ptr), _ptr(result_ptr), _opt_ptr(slot_weight_ptr), _ptr(stream)))
-            return
-        check(self._L.asl_map_frames_device(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), int(n_ids), Kp, dpp, nd, float(tag_size),
-                                            int(world_id), int(max_iters), _ptr(map_ptr), _opt_ptr(std_ptr), _ptr(poses_ptr),
-                                            _ptr(result_ptr), _ptr(stream)))
+        self._map_call(True, obs_ptr, [int(n_frames), int(max_tags)], n_ids, [Kp, dpp, nd], False, tag_size, tag_sizes, world_id, huber_px, max_iters,
+                       (map_ptr, std_ptr, poses_ptr, result_ptr), slot_weight_ptr, stream)
 
     def build_map_rig(self, obs, n_ids, rig, tag_size, world_id=-1, max_iters=30, with_std=True, huber_px=0.0, with_slot_weight=False,
                       tag_sizes=None):
@@ -729,22 +697,8 @@ class Detector:
         r = _rig_records(rig)
         if len(r) != o.shape[0]:
             raise ValueError("the rig has %d cameras, obs has %d" % (len(r), o.shape[0]))
-        res = np.zeros((), dtype=MAP_RESULT_DTYPE)
-        tmap = np.zeros(max(int(n_ids), 1), dtype=MAP_TAG_DTYPE)
-        std = np.zeros((max(int(n_ids), 1), 6), dtype=np.float64) if with_std else None
-        poses = np.zeros(o.shape[1], dtype=CAM_POSE_DTYPE)
-        weight = np.zeros(o.shape, dtype=np.float64) if with_slot_weight else None
-        if tag_sizes is not None:
-            table = _size_table(tag_sizes, n_ids)
-            check(self._L.asl_map_rig_sized_batch(self._h, _data(o), o.shape[0], o.shape[1], o.shape[2], int(n_ids), _data(r), float(tag_size),
-                                                  table.ctypes.data_as(C.POINTER(C.c_float)), int(world_id), float(huber_px), int(max_iters),
-                                                  tmap.ctypes.data, std.ctypes.data if with_std else None, _data(poses), res.ctypes.data,
-                                                  weight.ctypes.data if with_slot_weight else None))
-            return (res, tmap, std, poses, weight) if with_slot_weight else (res, tmap, std, poses)
-        check(self._L.asl_map_rig_batch(self._h, _data(o), o.shape[0], o.shape[1], o.shape[2], int(n_ids), _data(r), float(tag_size), int(world_id),
-                                        float(huber_px), int(max_iters), tmap.ctypes.data, std.ctypes.data if with_std else None, _data(poses),
-                                        res.ctypes.data, weight.ctypes.data if with_slot_weight else None))
-        return (res, tmap, std, poses, weight) if with_slot_weight else (res, tmap, std, poses)
+        return self._map_host(o, o.shape[1], n_ids, list(o.shape), [_data(r)], True, tag_size, tag_sizes, world_id, huber_px, max_iters, with_std,
+                              with_slot_weight)
 
     def build_map_rig_device(self, obs_ptr, n_cams, n_frames, max_tags, n_ids, rig_ptr, tag_size, map_ptr, std_ptr, poses_ptr, result_ptr,
                              world_id=-1, max_iters=30, stream=0, huber_px=0.0, slot_weight_ptr=0, tag_sizes=None):
@@ -752,16 +706,46 @@ class Detector:
         complete when the call is made) and the outputs of build_map_device (slot_weight_ptr: n_cams x n_frames x max_tags
         doubles or 0) are device addresses; enqueued on `stream` after one wait for the problem size.  tag_sizes ({id: size} or
         n_ids sizes, on the host): asl_map_rig_sized_frames_device."""
-        if tag_sizes is not None:
-            table = _size_table(tag_sizes, n_ids)
-            check(self._L.asl_map_rig_sized_frames_device(self._h, _ptr(obs_ptr), int(n_cams), int(n_frames), int(max_tags), int(n_ids),
-                                                          _ptr(rig_ptr), float(tag_size), table.ctypes.data_as(C.POINTER(C.c_float)),
-                                                          int(world_id), float(huber_px), int(max_iters), _ptr(map_ptr), _opt_ptr(std_ptr),
-                                                          _ptr(poses_ptr), _ptr(result_ptr), _opt_ptr(slot_weight_ptr), _ptr(stream)))
-            return
-        check(self._L.asl_map_rig_frames_device(self._h, _ptr(obs_ptr), int(n_cams), int(n_frames), int(max_tags), int(n_ids), _ptr(rig_ptr),
-                                                float(tag_size), int(world_id), float(huber_px), int(max_iters), _ptr(map_ptr), _opt_ptr(std_ptr),
-                                                _ptr(poses_ptr), _ptr(result_ptr), _opt_ptr(slot_weight_ptr), _ptr(stream)))
+        self._map_call(True, obs_ptr, [int(n_cams), int(n_frames), int(max_tags)], n_ids, [rig_ptr], True, tag_size, tag_sizes, world_id, huber_px,
+                       max_iters, (map_ptr, std_ptr, poses_ptr, result_ptr), slot_weight_ptr, stream)
+
+    def _map_host(self, o, n_frames, n_ids, dims, model, rig, tag_size, tag_sizes, world_id, huber_px, max_iters, with_std, with_slot_weight):
+        """the host form of _map_call on the block o: the outputs allocated, build_map's items back"""
+        res = np.zeros((), dtype=MAP_RESULT_DTYPE)
+        tmap = np.zeros(max(int(n_ids), 1), dtype=MAP_TAG_DTYPE)
+        std = np.zeros((max(int(n_ids), 1), 6), dtype=np.float64) if with_std else None
+        poses = np.zeros(n_frames, dtype=CAM_POSE_DTYPE)
+        weight = np.zeros(o.shape, dtype=np.float64) if with_slot_weight else None
+        self._map_call(False, _data(o), dims, n_ids, model, rig, tag_size, tag_sizes, world_id, huber_px, max_iters,
+                       (tmap.ctypes.data, std.ctypes.data if with_std else None, _data(poses), res.ctypes.data),
+                       weight.ctypes.data if with_slot_weight else None)
+        return (res, tmap, std, poses, weight) if with_slot_weight else (res, tmap, std, poses)
+
+    def _map_call(self, device, obs, dims, n_ids, model, rig, tag_size, tag_sizes, world_id, huber_px, max_iters, outs, weight, stream=0):
+        """The one tag-map call.  Its entry point, _batch or (device) _frames_device, whose addresses are then the device's:
+
+            rig  tag_sizes  huber_px or weight   entry
+            no   no         no                   asl_map            (no huber_px, no slot weights in its list)
+            no   no         yes                  asl_map_robust
+            no   yes        any                  asl_map_sized      (tag_sizes after tag_size)
+            yes  no         any                  asl_map_rig
+            yes  yes        any                  asl_map_rig_sized  (tag_sizes after tag_size)
+
+        dims: the block's extents; model: K, dist, n_dist or [the rig table's address]; outs: map, std (optional), poses, result."""
+        sized = tag_sizes is not None
+        robust = bool(rig or sized or huber_px or (weight if device else weight is not None))
+        table = _size_table(tag_sizes, n_ids) if sized else None
+        req, opt = (_ptr, _opt_ptr) if device else (lambda p: p, lambda p: p)
+        args = [self._h, req(obs)] + dims + [int(n_ids)] + ([req(model[0])] if rig else model) + [float(tag_size)]
+        if sized:
+            args.append(table.ctypes.data_as(C.POINTER(C.c_float)))
+        args += [int(world_id)] + ([float(huber_px)] if robust else []) + [int(max_iters), req(outs[0]), opt(outs[1]), req(outs[2]), req(outs[3])]
+        if robust:
+            args.append(opt(weight))
+        if device:
+            args.append(_ptr(stream))
+        name = "asl_map" + ("_rig" if rig else "") + ("_sized" if sized else "" if rig or not robust else "_robust")
+        check(getattr(self._L, name + ("_frames_device" if device else "_batch"))(*args))
 
     def smooth(self, obs, tag_map, K, dist, tag_size, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, seed=None,
                with_cov=False, huber_px=0.0, times=None):

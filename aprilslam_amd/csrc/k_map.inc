@@ -21,14 +21,14 @@
 //   reduce and factor an identity system;
 //   k_map_std       per tag parameter: diag of S^-1 = |L^-1 e_i|^2 by blocked forward substitution with the factor
 //   k_map_finish    one workgroup: the records.
-// The robust calls (asl_map_robust_*, huber_px = k > 0; tests/map_robust_ref.py) keep every seeding stage as it is and put
+// The robust calls (asl_map_robust_*, huber_px = k > 0; tests/map_ref.py "loss") keep every seeding stage as it is and put
 // a Huber loss on each corner's raw residual in the LM alone: k_map_linearize<true> scales a corner's two rows by
 // sqrt(weight) and costs it 2 k s - k^2 beyond k, so gn_obs_block, the reduced system and the accept rule see a weighted
 // problem and the D blocks the std reads are weighted already.  After the LM
 //   k_map_soft      one workgroup: per observation the smallest corner weight at the committed poses; the number of soft
 //                   observations, the squared error and the number of the corners not over k, summed in a fixed order
 // which k_map_finish takes for n_soft, the slot weights and the std's variance factor.  huber_px = 0 runs the plain kernels.
-// A camera rig (asl_map_rig_*, tests/map_rig_ref.py): the block is camera-major, obs[n_rig][n_frames][max_tags], the
+// A camera rig (asl_map_rig_*, tests/map_ref.py "block"): the block is camera-major, obs[n_rig][n_frames][max_tags], the
 // "cameras" of the joint problem are the used rig frames with W = rig<-world, and an observation is a VIEW, a taking-part
 // slot of one rig camera, in (frame, camera, slot) order.  The kernels are written once over the view's camera
 // (map_view<RIG>): one camera is the call's model and W itself, a rig the table's entry (a.cams, k_rig.inc's layout, read
@@ -37,7 +37,7 @@
 // a.obs_of), which hold the pair's first active view.  12 x 13 blocks of views of one pair are additive, so after each
 // linearisation k_map_fold adds the later views' blocks to the first one's, in view order (a.obs_next).  With one camera
 // every pair has one view, the two sets of lists are equal and nothing is folded.
-// Tags of different sizes (asl_map_*sized*, tests/map_sized_ref.py): the caller's per-id table (a.sizes; all 0 in every
+// Tags of different sizes (asl_map_*sized*, tests/map_ref.py "sizes"): the caller's per-id table (a.sizes; all 0 in every
 // other call) gives each tag its half side (a.tag_half, k_map_gather; map_tag_half's rule), which every pass that forms a
 // tag's corners reads in place of the call's, and a sized tag's PnP translation is multiplied by h / half wherever a
 // record proposes a pose (map_seed_scale: the chain, both sweeps' candidates).  Sizes are given, never solved for.

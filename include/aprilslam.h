@@ -490,7 +490,7 @@ int asl_map_batch(asl_detector *det, const asl_obs *obs, int n_frames, int max_t
    raise max_iters.  huber_px == 0 is the plain computation, run by the plain kernels: d_map, d_tag_std, d_poses and
    d_result are byte for byte what asl_map_frames_device writes, n_soft 0, the slot weights 1 for the slots in the solve.
    ASL_EINVAL, nothing written: whatever asl_map_frames_device refuses; huber_px < 0 or not finite.  The host waits once, as
-   in the plain call; deterministic: the same input gives the same bytes.  tests/map_robust_ref.py states the computation. */
+   in the plain call; deterministic: the same input gives the same bytes.  tests/map_ref.py states the computation. */
 int asl_map_robust_frames_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, int n_ids, const double *K,
                                  const double *dist, int n_dist, double tag_size, int world_id, double map_huber_px, int max_iters,
                                  void *d_map, void *d_tag_std, void *d_poses, void *d_result, void *d_slot_weight, void *stream);
@@ -503,7 +503,7 @@ int asl_map_robust_batch(asl_detector *det, const asl_obs *obs, int n_frames, in
    d_obs[n_cams][n_frames][max_tags] and the asl_rig_camera table of asl_localize_rig_frames_device (n_cams records, complete
    when the call is made) in place of one camera's model.  A frame index is one instant for all cameras, the mountings are
    taken as exact and the rig has one tag_size.  Tags that no single camera ever sees together come into one map and one
-   gauge through the rig's poses.  tests/map_rig_ref.py states the computation:
+   gauge through the rig's poses.  tests/map_ref.py states the computation:
    a view is a taking-part slot of one camera (flags & 1, 0 <= id < n_ids; a repeated id takes part once per camera, in that
    camera's first slot; the same id in two cameras of a frame is two views), in (frame, camera, slot) order.  A frame is used
    if its views hold >= 2 distinct ids.  The camera pose of a view is E_c (rig<-world): the seed's stages are the plain
@@ -551,7 +551,7 @@ int asl_map_rig_batch(asl_detector *det, const asl_obs *obs, int n_cams, int n_f
    block goes to asl_localize_* / asl_smooth_* / asl_calibrate_* as it is, with the same tag_size.  Ids that no used frame
    sees may have any valid entry.  An all-zero table gives every output of the robust / rig call byte for byte; a table
    whose every entry equals a float32 tag_size gives the same bytes but for d_map[].size.
-   tests/map_sized_ref.py states the computation. */
+   tests/map_ref.py states the computation. */
 int asl_map_sized_frames_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, int n_ids, const double *K,
                                 const double *dist, int n_dist, double tag_size, const float *tag_sizes, int world_id,
                                 double sized_huber_px, int max_iters, void *d_map, void *d_tag_std, void *d_poses, void *d_result,

@@ -79,8 +79,8 @@ def flip_case(K=None):
     W = [MR.inv(c) for c in gc]
     views = [(MR.LR.corner_area(obs["corners"][f, s]), f, s) for f, s in zip(*np.nonzero(obs["id"] == FLIP_TAG))]
     _, b, _ = max(views, key=lambda v: (v[0], -v[1]))
-    cam = MR.LR.camera(K, None)
-    G2, _ = MR.tag_lm(cam, MR.inv(W[b]) @ MR.mirror4(W[b] @ gt[FLIP_TAG]), [W[f] for _, f, _ in views],
+    table = MR.rig_ref.rig_table(MR.one_camera(K, None))
+    G2, _ = MR.tag_lm(table, [0] * len(views), MR.inv(W[b]) @ MR.mirror4(W[b] @ gt[FLIP_TAG]), [W[f] for _, f, _ in views],
                       [obs["corners"][f, s].astype(np.float64).reshape(4, 2) for _, f, s in views], MR.LR.half_size(LC.TAG_INNER))
     out = obs.copy()
     for _, f, s in views:

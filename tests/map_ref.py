@@ -1,32 +1,81 @@
-"""NumPy statement of the tag-map reconstruction (asl_map_frames_device / asl_map_batch, aprilslam_amd/csrc/k_map.inc):
-the same gather, breadth-first initial map, reseed sweeps, flip test, behind-camera test and joint Levenberg-Marquardt,
-on the host.  Test infrastructure, as tests/localize_ref.py is for the localisation.
+"""NumPy statement of the tag-map reconstruction (every asl_map_* entry point, aprilslam_amd/csrc/k_map.inc): the same gather,
+breadth-first initial map, reseed sweeps, flip test, behind-camera test and joint Levenberg-Marquardt, on the host.  The one
+place where the computation is stated; test infrastructure, as tests/localize_ref.py is for the localisation.
 
-  gather   a slot takes part if flags & 1, 0 <= id < n_ids and no earlier slot of the frame took part with the same id;
-           a frame is used with >= 2 taking-part slots (else status 1).  Cameras are the used frames in frame order,
-           tags the ids seen in used frames in ascending order, observations the taking-part slots of used frames in
-           (frame, slot) order.  world_id -1 picks the lowest id seen.
-  chain    the world tag sits at the identity; rounds of two halves until nothing changes.  (a) every unplaced camera
-           that sees a placed tag through a slot with flags & 2 takes camera<-world = T_obs inv(G) from the one of
-           largest corner area (ties: lower tag); (b) every unplaced tag seen through a flags & 2 slot of a placed camera
-           takes G = inv(W) T_obs from the camera where its area is largest (ties: lower camera).  Each half reads the
-           state the previous half left.  Cameras / tags never reached get status 5 / valid 0, their observations drop.
-  sweeps   twice: all cameras, then all tags (localize_ref's candidate and scoring rules): candidates are the current
-           pose, then, for the <= 8 seeding observations of largest area (ties: lower slot / lower camera) in their own
-           order, the pose the PnP pose implies and the one its mirrored planar minimum implies; the strictly lowest
-           total corner cost over every active observation wins.  Then the gauge: the world tag back at the identity.
-  flip     every other tag with an observation: its pose and its mirror (the mirrored planar minimum of the tag in the
-           view where it is largest, ties: lower camera) are each polished by pose-only LM (localize_ref.lm's schedule,
-           the cameras held, left update of world<-tag); the mirror replaces the pose only at a strictly lower cost.
-  behind   an observation with a corner at z <= 1e-6 in its camera leaves the solve; a camera left with fewer than
-           2 observations is dropped (status 3) with all of them; a tag left with none is not mapped.
-  LM       unknowns 6 per camera (camera<-world) and 6 per mapped tag but the world tag (world<-tag), left updates
-           R <- exp(w) R, t <- exp(w) t + v; residuals the k_pnp.inc camera model at the corners (+-h, +-h, 0); a corner
-           at z <= 1e-9 costs 1e12 and adds no row.  (H + lambda diag(max(H_ii, 1e-12))) d = -g, lambda0 = 1e-3,
-           x0.1 (floor 1e-12) after an accepted trial, x10 after a rejected one; max_iters trials at most, an accepted
-           trial of relative decrease below 1e-12 stops; a system that is not positive definite stops with status 2.
-  std      sigma^2 = cost / (8 n_obs - 6 frames - 6 (tags - 1)), std = sqrt(sigma^2 diag(H^-1)) of each tag's block of
-           the undamped normal matrix at the solution (w then v, world frame).
+map_rig_frames is the computation: a camera rig's frames, a half side per tag, squared or Huber loss.  map_frames is one camera:
+it builds the rig of that camera at the identity mounting, adds the leading axis, calls map_rig_frames and drops the axis
+from slot_weight.  With one camera, E = I and no size table every rule below reads as the single-camera one: a view is a
+slot, the rig is the camera, a pair has one view.
+
+  block    obs (n_cams, n_frames, max_tags), camera-major; camera c has its model and its mounting E_c = camera_c<-rig (exact);
+           a frame index is one instant for all cameras; one tag_size and an optional table tag_sizes (sizes, below).
+  gather   a view is a taking-part slot (camera c, frame f, slot s): flags & 1, 0 <= id < n_ids, and no earlier slot of the
+           SAME camera's frame took part with the id.  The same id in two cameras of a frame is two views.  Views are ordered
+           (frame, camera, slot).  A frame is used if its views hold >= 2 distinct ids (else status 1); the cameras of the
+           joint problem are the used frames in frame order, with W = rig<-world; tags are the ids seen in used frames,
+           ascending.  world_id -1 picks the lowest id seen.
+  pose     the camera pose of a view is E_c W.  The rig from a view: W = inv(E_c) T_obs inv(G); the tag from a view:
+           G = inv(E_c W) T_obs.  Every corner is costed by its own camera's model (the k_pnp.inc camera model at the corners
+           (+-h, +-h, 0)); areas are pixels as they are.
+  chain    the world tag sits at the identity; rounds of two halves until nothing changes.  (a) every unplaced frame that
+           sees a placed tag through a view with flags & 2 takes its W from the one of largest corner area (ties: lower tag,
+           then lower camera); (b) every unplaced tag seen through a flags & 2 view of a placed frame takes its G from the view
+           where its area is largest (ties: view order, which for one camera is the lower frame).  Each half reads the state
+           the previous half left.  Frames / tags never reached get status 5 / valid 0, their views drop.
+  sweeps   twice: all frames, then all tags (localize_ref's candidate and scoring rules): candidates are the current pose,
+           then, for the <= 8 seeding views of largest area (ties: frame half the lower global slot g = c * max_tags + s, tag
+           half the lower list position) in their own order, the pose the PnP pose implies and the one its mirrored planar
+           minimum implies; the strictly lowest total squared corner cost over every active view wins.  Then the gauge: the
+           world tag back at the identity.
+  flip     every other tag with a view: its pose and its mirror (the mirrored planar minimum of the tag in the view where it
+           is largest, ties: view order, formed from the map pose) are each polished by pose-only LM (localize_ref.lm's
+           schedule, the frames held, left update of world<-tag); the mirror replaces the pose only at a strictly lower cost.
+  behind   a view with a corner at z <= 1e-6 in its camera leaves the solve; a frame left with < 2 distinct tags among its
+           active views is dropped with all of them (status 3); a tag left with no view is not mapped.
+  LM       6 unknowns per used frame (rig<-world) and per mapped tag but the world tag (world<-tag), left updates
+           R <- exp(w) R, t <- exp(w) t + v.  With p = W q the rig-frame corner, the residual of a view is
+           project_c(Re_c p + te_c) - uv and its rows are jp [-[p]x | I] and (jp R_W) [-[q]x | I] with jp = J_proj Re_c; a
+           corner at z <= 1e-9 costs 1e12 and adds no row.  Every view gives a 12 x 13 block [J^T J | J^T r]; the blocks of the
+           views of one (frame, tag) pair are added into the pair's first active view's in view order, and the normal
+           equations are assembled from the pairs.  The cost is summed per view (four corners), then over the views.
+           (H + lambda diag(max(H_ii, 1e-12))) d = -g, lambda0 = 1e-3, x0.1 (floor 1e-12) after an accepted trial, x10 after a
+           rejected one; max_iters trials at most, an accepted trial of relative decrease below 1e-12 stops; a system that is
+           not positive definite stops with status 2.
+  loss     huber_px = k >= 0, in pixels, on every corner's raw residual r = (r0, r1), s = |r|.  k = 0 is the squared loss
+           inside the same functions: every corner costs s^2 with weight 1.  k > 0: s <= k costs s^2 with weight 1, s > k costs
+           2 k s - k^2 with weight k / s; a corner at z <= 1e-9 costs 1e12, adds no row and is never over.  The corner adds
+           weight J^T J and weight J^T r to the normal equations (iteratively reweighted Gauss-Newton, no second-order term of
+           the loss).  The seeding (chain, sweeps, gauge, flip, behind) keeps squared costs.  The robust cost stands wherever the
+           LM has a cost: cost_seed, cost, every trial, the accept rule and the 1e-12 stop, and the per-frame and result
+           rms_px / rms_seed_px, which are sqrt(sum of corner costs / corners).
+  soft     at the returned poses a view's weight is the smallest of its four corner weights, in (0, 1]; it is soft with a
+           weight < 1.  n_soft counts them; slot_weight (n_cams, n_frames, max_tags) holds the weights (1 for every view in
+           the solve at k = 0), 0 for every slot that is not in the solve, and for every slot (with n_soft 0) when the
+           status is not 0.
+  std      std = sqrt(sigma^2 diag(H^-1)) of each tag's block of the (weighted) undamped normal matrix at the solution (w then
+           v, world frame).  k = 0: sigma^2 = cost / (8 views - 6 frames - 6 (tags - 1)).  k > 0: sigma^2 = sum of s^2 over the
+           corners not over k / (2 n_in - 6 frames - 6 (tags - 1)), n_in their number (a corner at z <= 1e-9 is one of them,
+           with its 1e12); 0 if the denominator is <= 0.  The factor leaves the outliers' linear tails out, so one bad slot
+           does not inflate every tag's std; the truncation at k biases it slightly low.
+  sizes    tag_sizes, (n_ids,) float32 or None (all 0), by the rule of map_tag_half (sized_ref.py): 0: the tag has the call's
+           tag_size, half = float32(tag_size / 2); > 0 and finite: the tag's own side, h_id = float32(size) * float32(0.5);
+           negative or not finite: ValueError naming the id (the device: ASL_EINVAL, nothing written).  Every pass that
+           forms a tag's corners uses that tag's h: the sweeps' costs, the flip test's tag_lm, the behind test, the LM's
+           blocks and costs, the robust terms and the seed and final per-view costs.  corner_terms and view_blocks work row
+           by row; given the views' halves they run once per distinct half over that half's views, in view order, and put
+           the rows back where they were (by_half); with one half among the views that is one plain call.  A record's PnP
+           pose T was solved at tag_size; a sized tag's translation is multiplied by h_id / half before T proposes anything
+           (the chain's frame and tag halves, the sweeps' candidates plain and mirrored: the mirrored minimum is formed from
+           the scaled pose).  A tag without a size keeps T as it is.  map["size"] = the table's entry for every mapped id.
+  records  per frame T = world<-rig, n_tags = active views, n_rejected = taking-part - active, seed_slot = the chain's view
+           as a global slot; the result's n_obs counts views.
+
+reverse (a rounding perturbation for the tests): the LM's sums run over the views in reversed order.
+trace (a dict, optional) receives "ids"; "chain_frames" [(frame, id of the seeding view)] and "chain_tags" [id the chain
+placed]; "sweep_mirrored" [("frame", frame, id) or ("tag", id, id): the winning candidate was the mirrored pose of a view of
+that id]; "flipped" [id the flip test turned over]; "behind" [id of every view the behind test dropped]; "views" and "pairs"
+(the LM's counts); "decreases", the relative cost decrease of every accepted trial; and at k > 0 "margin", the smallest
+|s - k| over every corner of every linearisation and of the final weights.
 """
 import os
 import sys
@@ -35,7 +84,9 @@ import numpy as np
 from scipy.linalg import solve_triangular
 
 import localize_ref as LR
+import rig_ref
 from aprilslam_amd._lib import CAM_POSE_DTYPE, MAP_RESULT_DTYPE, MAP_TAG_DTYPE
+from aprilslam_amd.rig import Rig, RigCamera
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
 import gn_oracle  # noqa: E402
@@ -70,46 +121,128 @@ def obj3(h):
     return np.array([[-h, -h, 0.0], [h, -h, 0.0], [h, h, 0.0], [-h, h, 0.0]])
 
 
-def corner_costs_many(cam, Wc, Xw, uv):
-    """localize_ref.corner_costs of n observations at once: Wc (n, 4, 4) camera<-world, Xw (n, 4, 3) world corners,
-    uv (n, 4, 2) -> (n, 4) squared pixel errors (1e12 for a corner at z <= 1e-9)"""
-    P = np.einsum('nij,nkj->nki', Wc[:, :3, :3], Xw) + Wc[:, None, :3, 3]
-    Pf = P.reshape(-1, 3)
-    ok = Pf[:, 2] > LR.Z_MIN
-    e = np.full(len(Pf), LR.BEHIND_COST)
-    if ok.any():
-        r = LR.project(cam, Pf[ok]) - uv.reshape(-1, 2)[ok]
-        e[ok] = r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1]
-    return e.reshape(len(Wc), 4)
+def size_table(tag_sizes, n_ids):
+    """(n_ids,) float32; None: all zero.  A negative or non-finite entry is refused"""
+    if tag_sizes is None:
+        return np.zeros(n_ids, dtype=np.float32)
+    t = np.asarray(tag_sizes, dtype=np.float32)
+    if t.shape != (n_ids,):
+        raise ValueError("tag_sizes must hold n_ids = %d entries" % n_ids)
+    bad = np.flatnonzero(~(np.isfinite(t) & (t >= 0)))
+    if len(bad):
+        raise ValueError("tag_sizes[%d] must be 0 or positive and finite" % bad[0])
+    return t
 
 
-def obs_costs(cam, W, G, uv, h):
-    """obs_cost of n observations at once: W (n, 4, 4) camera<-world, G (n, 4, 4) world<-tag, uv (n, 4, 2) -> (n,)"""
-    Xw = np.einsum('nij,kj->nki', G[:, :3, :3], obj3(h)) + G[:, None, :3, 3]
-    return corner_costs_many(cam, W, Xw, uv).sum(axis=1)
+def tag_half(size, half):
+    """sized_ref.tag_half on a table entry"""
+    return float(np.float32(size) * np.float32(0.5)) if size > 0 else half
 
 
-def tag_lm(cam, G, Ws, uvs, h):
-    """pose-only LM of one world<-tag G with the cameras Ws (camera<-world) held; localize_ref.lm's schedule"""
+def scaled(T, size, h, half):
+    """a record's camera<-tag (4x4) as it is for a tag of half side h: sized_ref.tag_pose"""
+    if size > 0:
+        T[:3, 3] = T[:3, 3] * (h / half)
+    return T
+
+
+def by_half(fn, hv, n_out):
+    """fn(rows, h) -> n_out arrays with one row per view, run once per distinct half of hv (n,) over its views (rows: their
+    indices, ascending) and put back in place.  One half: fn's own result"""
+    hv = np.asarray(hv, dtype=np.float64)
+    halves = np.unique(hv)
+    if len(halves) <= 1:
+        return fn(np.arange(len(hv)), float(halves[0]) if len(halves) else 0.0)
+    out = None
+    for h in halves:
+        rows = np.flatnonzero(hv == h)
+        got = fn(rows, float(h))
+        if out is None:
+            out = [np.zeros((len(hv),) + g.shape[1:], dtype=g.dtype) for g in got]
+        for o, g in zip(out, got):
+            o[rows] = g
+    return tuple(out)
+
+
+def mountings(table):
+    """(n_cams, 4, 4) camera<-rig"""
+    E = np.tile(np.eye(4), (len(table), 1, 1))
+    for c, (_, Re, te) in enumerate(table):
+        E[c, :3, :3], E[c, :3, 3] = Re, te
+    return E
+
+
+def project_views(table, pc, P, jac=False):
+    """the points P (n, 3), each in the frame of its camera pc (n,): (uv (n, 2), J (n, 2, 3), in front (n,)); rows with
+    z <= Z_MIN come back as zeros"""
+    ok = P[:, 2] > LR.Z_MIN
+    uv, J = np.zeros((len(P), 2)), np.zeros((len(P), 2, 3))
+    for c, (cam, _, _) in enumerate(table):
+        m = ok & (pc == c)
+        if not m.any():
+            continue
+        if jac:
+            uv[m], J[m] = LR.project(cam, P[m], jac=True)
+        else:
+            uv[m] = LR.project(cam, P[m])
+    return uv, J, ok
+
+
+def loss_terms(r, ok, k):
+    """per corner, from the raw residuals r (n, 2), zero where not ok: (cost, weight, over, s); k = 0: the squared loss"""
+    e = r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1]
+    s = np.sqrt(e)
+    over = ok & (s > k) if k > 0 else np.zeros(len(s), dtype=bool)
+    w = np.ones(len(s))
+    w[over] = k / s[over]
+    rho = np.where(over, 2.0 * k * s - k * k, e)
+    rho[~ok] = LR.BEHIND_COST
+    return rho, w, over, s
+
+
+def corner_terms(table, vc, Wv, G, uv, hv, k=0.0):
+    """per corner of n views (vc (n,) their cameras, Wv (n, 4, 4) camera<-world, G (n, 4, 4) world<-tag, uv (n, 4, 2), hv their
+    half sides, (n,) or one for all): (cost, weight, over, s, in front), each (n, 4)"""
+    vc = np.asarray(vc)
+
+    def one(rows, h):
+        Xw = np.einsum('nij,kj->nki', G[rows][:, :3, :3], obj3(h)) + G[rows][:, None, :3, 3]
+        P = (np.einsum('nij,nkj->nki', Wv[rows][:, :3, :3], Xw) + Wv[rows][:, None, :3, 3]).reshape(-1, 3)
+        pr, _, ok = project_views(table, np.repeat(vc[rows], 4), P)
+        r = (pr - uv[rows].reshape(-1, 2)) * ok[:, None]
+        return tuple(x.reshape(len(rows), 4) for x in loss_terms(r, ok, k) + (ok,))
+
+    return by_half(one, np.broadcast_to(hv, len(vc)), 5)
+
+
+def view_costs(table, vc, Wv, G, uv, hv, k=0.0):
+    """(n,) cost of each view"""
+    return corner_terms(table, vc, Wv, G, uv, hv, k)[0].sum(axis=1)
+
+
+def margin(s, ok, k):
+    """smallest |s - k| over the corners in front"""
+    return float(np.abs(s[ok] - k).min()) if ok.any() else np.inf
+
+
+def tag_lm(table, vcs, G, Wvs, uvs, h):
+    """pose-only LM of one world<-tag G of half side h, the view cameras Wvs (camera<-world, of the table's cameras vcs) held;
+    localize_ref.lm's schedule"""
     X = obj3(h)
-
-    Wa = np.stack(Ws)
-    uva = np.stack(uvs)
+    Wa, uva, pc = np.stack(Wvs), np.stack(uvs), np.repeat(np.asarray(vcs), 4)
     n = len(Wa)
 
     def lin(R, t, want):
         Xw = X @ R.T + t
-        if not want:
-            return float(corner_costs_many(cam, Wa, np.broadcast_to(Xw, (n, 4, 3)), uva).sum()), None, None
         P = (np.einsum('nij,kj->nki', Wa[:, :3, :3], Xw) + Wa[:, None, :3, 3]).reshape(-1, 3)
-        ok = P[:, 2] > LR.Z_MIN
-        cost = LR.BEHIND_COST * float((~ok).sum())
+        pr, Jp, ok = project_views(table, pc, P, jac=want)
+        r = (pr - uva.reshape(-1, 2))[ok]
+        cost = LR.BEHIND_COST * float((~ok).sum()) + float((r * r).sum())
+        if not want:
+            return cost, None, None
         H, g = np.zeros((6, 6)), np.zeros(6)
         if ok.any():
-            pr, Jp = LR.project(cam, P[ok], jac=True)
-            r = pr - uva.reshape(-1, 2)[ok]
-            cost += float((r * r).sum())
-            a = np.einsum('nri,nij->nrj', Jp, np.repeat(Wa[:, :3, :3], 4, axis=0)[ok])    # (k, 2, 3): d uv / d Xw
+            a = np.einsum('nri,nij->nrj', Jp[ok], np.repeat(Wa[:, :3, :3], 4, axis=0)[ok])    # d uv / d Xw
             Xq = np.tile(Xw, (n, 1))[ok]
             J = np.concatenate([np.cross(Xq[:, None, :], a), a], axis=2).reshape(-1, 6)
             H = J.T @ J
@@ -122,31 +255,53 @@ def tag_lm(cam, G, Ws, uvs, h):
     return out, cost
 
 
-def _project_many(cam, P):
-    """(n, 2) pixels and (n, 2, 3) Jacobians; rows with z <= Z_MIN come back as zeros"""
-    ok = P[:, 2] > LR.Z_MIN
-    uv, J = np.zeros((len(P), 2)), np.zeros((len(P), 2, 3))
-    if ok.any():
-        uv[ok], J[ok] = LR.project(cam, P[ok], jac=True)
-    return uv, J, ok
+def view_blocks(table, W, G, oc, ot, ovc, uv, hv, k=0.0, trace=None):
+    """per view (frame oc, tag ot, camera ovc, half side hv (M,) or one for all; W (NC, 4, 4) rig<-world, G (NT, 4, 4)): its
+    cost (M,) and its 12 x 13 block [J^T J | J^T r] (M, 12, 13), J = [frame | tag], the rows weighted under the loss"""
+    def one(rows, h):
+        c, t, vc = oc[rows], ot[rows], ovc[rows]
+        M = len(rows)
+        q = np.einsum('mij,kj->mki', G[t][:, :3, :3], obj3(h)) + G[t][:, None, :3, 3]              # (M, 4, 3) world
+        p = np.einsum('mij,mkj->mki', W[c][:, :3, :3], q) + W[c][:, None, :3, 3]                   # (M, 4, 3) rig
+        Re = np.stack([table[x][1] for x in vc]) if M else np.zeros((0, 3, 3))
+        te = np.stack([table[x][2] for x in vc]) if M else np.zeros((0, 3))
+        P = np.einsum('mij,mkj->mki', Re, p) + te[:, None, :]                                      # (M, 4, 3) camera
+        pr, Jp, ok = project_views(table, np.repeat(vc, 4), P.reshape(-1, 3), jac=True)
+        r = (pr - uv[rows].reshape(-1, 2)) * ok[:, None]
+        rho, w, _, s = loss_terms(r, ok, k)
+        if trace is not None and k > 0:
+            trace["margin"] = min(trace.get("margin", np.inf), margin(s, ok, k))
+        sw = np.sqrt(w)
+        jp = np.einsum('nri,nij->nrj', Jp, np.repeat(Re, 4, axis=0)) * (ok * sw)[:, None, None]   # J_proj Re
+        r = r * sw[:, None]
+        pf, qf = p.reshape(-1, 3), q.reshape(-1, 3)
+        Jc = np.concatenate([np.cross(pf[:, None, :], jp), jp], axis=2)                            # jp [-[p]x | I]
+        a = np.einsum('nri,nij->nrj', jp, np.repeat(W[c][:, :3, :3], 4, axis=0))
+        Jt = np.concatenate([np.cross(qf[:, None, :], a), a], axis=2)
+        J = np.concatenate([Jc.reshape(M, 8, 6), Jt.reshape(M, 8, 6), r.reshape(M, 8, 1)], axis=2)  # (M, 8, 13)
+        return rho.reshape(M, 4).sum(axis=1), np.einsum('mri,mrj->mij', J[:, :, :12], J)
+
+    return by_half(one, np.broadcast_to(hv, len(oc)), 2)
 
 
-def joint_linearise(cam, W, G, oc, ot, uv, h, cam_col, tag_col, n_par):
-    """cost, H, g of the joint problem: cam_col[c] / tag_col[j] = first column or -1 (held)"""
-    X = obj3(h)
-    M = len(oc)
-    q = np.einsum('mij,kj->mki', G[ot][:, :3, :3], X) + G[ot][:, None, :3, 3]               # (M, 4, 3) world
-    P = np.einsum('mij,mkj->mki', W[oc][:, :3, :3], q) + W[oc][:, None, :3, 3]               # (M, 4, 3) camera
-    pr, Jp, ok = _project_many(cam, P.reshape(-1, 3))
-    r = (pr - uv.reshape(-1, 2)) * ok[:, None]
-    cost = float((r * r).sum()) + LR.BEHIND_COST * float((~ok).sum())
-    Jp = Jp * ok[:, None, None]
-    Pf, qf = P.reshape(-1, 3), q.reshape(-1, 3)
-    Jc = np.concatenate([np.cross(Pf[:, None, :], Jp), Jp], axis=2)                           # [P x jp | jp]
-    a = np.einsum('nri,nij->nrj', Jp, np.repeat(W[oc][:, :3, :3], 4, axis=0))
-    Jt = np.concatenate([np.cross(qf[:, None, :], a), a], axis=2)
-    # J^T J and J^T r block by block: per observation its 8 rows' camera / tag products, added into their columns
-    Jc, Jt, r8 = Jc.reshape(M, 8, 6), Jt.reshape(M, 8, 6), r.reshape(M, 8)
+def fold_pairs(B, oc, ot):
+    """the blocks of the views of one (frame, tag) pair added into the pair's first view's, in the order given:
+    (blocks (P, 12, 13), indices (P,) of the first views)"""
+    first, heads = {}, []
+    out = []
+    for m in range(len(oc)):
+        key = (int(oc[m]), int(ot[m]))
+        if key in first:
+            out[first[key]] = out[first[key]] + B[m]
+        else:
+            first[key] = len(heads)
+            heads.append(m)
+            out.append(B[m].copy())
+    return (np.stack(out) if out else np.zeros((0, 12, 13))), np.array(heads, dtype=np.int64)
+
+
+def assemble(B, oc, ot, cam_col, tag_col, n_par):
+    """H, g from the blocks B of observations (frame oc, tag ot): cam_col[c] / tag_col[j] = first column or -1 (held)"""
     ccol, tcol = cam_col[oc], tag_col[ot]
     H, g = np.zeros((n_par, n_par)), np.zeros(n_par)
     i6 = np.arange(6)
@@ -156,25 +311,61 @@ def joint_linearise(cam, W, G, oc, ot, uv, h, cam_col, tag_col, n_par):
             np.add.at(H, (rc[sel][:, None, None] + i6[None, :, None], cc[sel][:, None, None] + i6[None, None, :]), blk[sel])
 
     cm, tm = ccol >= 0, tcol >= 0
-    add(ccol, ccol, np.einsum('mri,mrj->mij', Jc, Jc), cm)
-    add(tcol, tcol, np.einsum('mri,mrj->mij', Jt, Jt), tm)
-    ct = np.einsum('mri,mrj->mij', Jc, Jt)
-    add(ccol, tcol, ct, cm & tm)
-    add(tcol, ccol, ct.transpose(0, 2, 1), cm & tm)
+    add(ccol, ccol, B[:, :6, :6], cm)
+    add(tcol, tcol, B[:, 6:12, 6:12], tm)
+    add(ccol, tcol, B[:, :6, 6:12], cm & tm)
+    add(tcol, ccol, B[:, 6:12, :6], cm & tm)
     if cm.any():
-        np.add.at(g, ccol[cm][:, None] + i6, np.einsum('mri,mr->mi', Jc, r8)[cm])
+        np.add.at(g, ccol[cm][:, None] + i6, B[:, :6, 12][cm])
     if tm.any():
-        np.add.at(g, tcol[tm][:, None] + i6, np.einsum('mri,mr->mi', Jt, r8)[tm])
-    return cost, H, g
+        np.add.at(g, tcol[tm][:, None] + i6, B[:, 6:12, 12][tm])
+    return H, g
 
 
-def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_std=True, trace=None):
-    """(result MAP_RESULT_DTYPE record, map (n_ids,) MAP_TAG_DTYPE, tag_std (n_ids, 6), poses (n_frames,) CAM_POSE_DTYPE);
-    trace (a dict, optional) receives the ids the flip test turned over ("flipped")"""
+def joint_linearise(table, W, G, oc, ot, ovc, uv, hv, cam_col, tag_col, n_par, k=0.0, trace=None, fold=True):
+    """(cost, H, g) of the joint problem over the views given; fold False: every view its own observation"""
+    cost_v, B = view_blocks(table, W, G, oc, ot, ovc, uv, hv, k, trace)
+    if fold:
+        B, heads = fold_pairs(B, oc, ot)
+        oc, ot = oc[heads], ot[heads]
+        if trace is not None:
+            trace["views"], trace["pairs"] = len(cost_v), len(heads)
+    H, g = assemble(B, oc, ot, cam_col, tag_col, n_par)
+    return float(cost_v.sum()), H, g
+
+
+def won(trace, what, key, costs, src):
+    """note a sweep whose winning candidate is a mirrored one: candidates 1, 2 / 3, 4 / ... are view k's plain and mirrored"""
+    best = int(np.argmin(costs))
+    if trace is not None and best > 0 and best % 2 == 0:
+        trace["sweep_mirrored"].append((what, key, src[(best - 1) // 2]))
+
+
+def one_camera(K, dist):
+    """the rig of one camera at the identity mounting"""
+    return Rig([RigCamera(K, dist, np.eye(4))])
+
+
+def map_frames(obs, n_ids, K, dist, tag_size, tag_sizes=None, world_id=-1, huber_px=0.0, max_iters=30, with_std=True, trace=None, reverse=False):
+    """one camera: obs (n_frames, max_tags) -> map_rig_frames' five of one_camera(K, dist), poses with T = world<-camera and
+    slot_weight (n_frames, max_tags)"""
+    out = map_rig_frames(np.asarray(obs)[None], n_ids, one_camera(K, dist), tag_size, tag_sizes, world_id, huber_px, max_iters, with_std, trace, reverse)
+    return out[:4] + (out[4][0],)
+
+
+def map_rig_frames(obs, n_ids, rig, tag_size, tag_sizes=None, world_id=-1, huber_px=0.0, max_iters=30, with_std=True, trace=None, reverse=False):
+    """(result MAP_RESULT_DTYPE record, map (n_ids,) MAP_TAG_DTYPE, tag_std (n_ids, 6), poses (n_frames,) CAM_POSE_DTYPE with
+    T = world<-rig, slot_weight (n_cams, n_frames, max_tags)); tag_sizes: (n_ids,) sizes, 0 for tag_size, or None"""
+    k = float(huber_px)
+    if not (k >= 0 and np.isfinite(k)):
+        raise ValueError("huber_px must be >= 0 and finite")
     obs = np.asarray(obs)
-    F, S = obs.shape
-    cam = LR.camera(K, dist)
-    h = LR.half_size(tag_size)
+    C, F, S = obs.shape
+    table = rig_ref.rig_table(rig)
+    assert len(table) == C
+    E = mountings(table)
+    half = LR.half_size(tag_size)
+    sizes = size_table(tag_sizes, n_ids)
     res = np.zeros((), dtype=MAP_RESULT_DTYPE)
     out_map = np.zeros(n_ids, dtype=MAP_TAG_DTYPE)
     tag_std = np.zeros((n_ids, 6))
@@ -182,25 +373,29 @@ def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_st
     poses["T"] = np.eye(4)
     poses["seed_slot"] = -1
     poses["status"] = 1
+    slot_weight = np.zeros((C, F, S))
 
     # gather
-    part = np.zeros((F, S), dtype=bool)
-    for f in range(F):
-        seen = set()
-        for s in range(S):
-            i, fl = int(obs["id"][f, s]), int(obs["flags"][f, s])
-            if (fl & 1) and 0 <= i < n_ids and i not in seen:
-                part[f, s] = True
-                seen.add(i)
-    npart = part.sum(axis=1)
-    frames = [f for f in range(F) if npart[f] >= 2]
-    ids = sorted({int(obs["id"][f, s]) for f in frames for s in range(S) if part[f, s]})
+    part = np.zeros((C, F, S), dtype=bool)
+    for c in range(C):
+        for f in range(F):
+            seen = set()
+            for s in range(S):
+                i, fl = int(obs["id"][c, f, s]), int(obs["flags"][c, f, s])
+                if (fl & 1) and 0 <= i < n_ids and i not in seen:
+                    part[c, f, s] = True
+                    seen.add(i)
+    npart = part.sum(axis=(0, 2))
+    ndist = [len({int(i) for i in obs["id"][:, f][part[:, f]]}) for f in range(F)]
+    frames = [f for f in range(F) if ndist[f] >= 2]
+    ids = sorted({int(i) for f in frames for i in obs["id"][:, f][part[:, f]]})
     tag_of = {i: j for j, i in enumerate(ids)}
-    ob = [(c, tag_of[int(obs["id"][f, s])], f, s) for c, f in enumerate(frames) for s in range(S) if part[f, s]]
+    ob = [(n, tag_of[int(obs["id"][c, f, s])], f, c, s) for n, f in enumerate(frames) for c in range(C) for s in range(S) if part[c, f, s]]
     oc = np.array([o[0] for o in ob], dtype=np.int64)
     ot = np.array([o[1] for o in ob], dtype=np.int64)
     ofr = np.array([o[2] for o in ob], dtype=np.int64)
-    osl = np.array([o[3] for o in ob], dtype=np.int64)
+    ovc = np.array([o[3] for o in ob], dtype=np.int64)
+    osl = np.array([o[4] for o in ob], dtype=np.int64)
     M, NC, NT = len(ob), len(frames), len(ids)
     if world_id < 0:
         world_id = ids[0] if ids else -1
@@ -211,16 +406,26 @@ def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_st
         for f in frames:
             poses["status"][f] = 5
             poses["n_rejected"][f] = npart[f]
-        return res, out_map, tag_std, poses
+        return res, out_map, tag_std, poses, slot_weight
     if NT > MAX_MAP_TAGS:
         raise ValueError("more than %d tags" % MAX_MAP_TAGS)
     wt = tag_of[world_id]
-    uv = np.stack([obs["corners"][f, s].astype(np.float64).reshape(4, 2) for f, s in zip(ofr, osl)]) if M else np.zeros((0, 4, 2))
-    To = [rec4(obs["T"][f, s]) for f, s in zip(ofr, osl)]
-    seedable = np.array([bool(obs["flags"][f, s] & 2) for f, s in zip(ofr, osl)], dtype=bool)
-    area = np.array([LR.corner_area(obs["corners"][f, s]) for f, s in zip(ofr, osl)])
+    ht = np.array([tag_half(sizes[i], half) for i in ids])             # per tag: its half side
+    hv = ht[ot]                                                        # per view
+    rec = [obs[c, f, s] for c, f, s in zip(ovc, ofr, osl)]
+    uv = np.stack([r["corners"].astype(np.float64).reshape(4, 2) for r in rec]) if M else np.zeros((0, 4, 2))
+    To = [scaled(rec4(r["T"]), sizes[ids[j]], ht[j], half) for r, j in zip(rec, ot)]
+    if trace is not None:
+        trace.update(ids=ids, chain_frames=[], chain_tags=[], sweep_mirrored=[])
+    seedable = np.array([bool(r["flags"] & 2) for r in rec], dtype=bool)
+    area = np.array([LR.corner_area(r["corners"]) for r in rec])
     by_cam = [np.flatnonzero(oc == c) for c in range(NC)]
     by_tag = [np.flatnonzero(ot == j) for j in range(NT)]
+    Ev, Evi = E[ovc] if M else np.zeros((0, 4, 4)), np.array([inv(E[c]) for c in ovc]) if M else np.zeros((0, 4, 4))
+
+    def Wview(Wx, ms):
+        """camera<-world of the views ms"""
+        return Ev[ms] @ Wx[oc[ms]]
 
     # chain
     W = np.tile(np.eye(4), (NC, 1, 1))
@@ -237,20 +442,24 @@ def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_st
                 continue
             cand = [m for m in by_cam[c] if seedable[m] and tplaced[ot[m]]]
             if cand:
-                m = min(cand, key=lambda m: (-area[m], ot[m]))
-                W[c] = To[m] @ inv(G[ot[m]])
+                m = min(cand, key=lambda m: (-area[m], ot[m], ovc[m]))
+                W[c] = Evi[m] @ (To[m] @ inv(G[ot[m]]))
                 cplaced[c] = True
-                seed_slot[c] = osl[m]
+                seed_slot[c] = ovc[m] * S + osl[m]
                 changed = True
+                if trace is not None:
+                    trace["chain_frames"].append((frames[c], ids[ot[m]]))
         for j in range(NT):
             if tplaced[j]:
                 continue
             cand = [m for m in by_tag[j] if seedable[m] and cplaced[oc[m]]]
             if cand:
-                m = min(cand, key=lambda m: (-area[m], oc[m]))
-                G[j] = inv(W[oc[m]]) @ To[m]
+                m = min(cand, key=lambda m: (-area[m], m))
+                G[j] = inv(Ev[m] @ W[oc[m]]) @ To[m]
                 tplaced[j] = True
                 changed = True
+                if trace is not None:
+                    trace["chain_tags"].append(ids[j])
     act = cplaced[oc] & tplaced[ot] if M else np.zeros(0, dtype=bool)
 
     # sweeps
@@ -260,14 +469,16 @@ def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_st
             ms = [m for m in by_cam[c] if act[m]]
             if not cplaced[c] or not ms:
                 continue
-            cands = [W[c]]
+            cands, src = [W[c]], []
             sm = [m for m in ms if seedable[m]]
-            for k in LR.top_k([area[m] for m in sm], MAX_CAND):
-                m = sm[k]
-                cands += [To[m] @ inv(G[ot[m]]), mirror4(To[m]) @ inv(G[ot[m]])]
+            for kk in LR.top_k([area[m] for m in sm], MAX_CAND):
+                m = sm[kk]
+                cands += [Evi[m] @ (To[m] @ inv(G[ot[m]])), Evi[m] @ (mirror4(To[m]) @ inv(G[ot[m]]))]
+                src.append(ids[ot[m]])
             Gm, uvm = G[ot[ms]], uv[ms]
-            costs = [float(obs_costs(cam, np.broadcast_to(Tc, (len(ms), 4, 4)), Gm, uvm, h).sum()) for Tc in cands]
+            costs = [float(view_costs(table, ovc[ms], Ev[ms] @ Tc[None], Gm, uvm, hv[ms]).sum()) for Tc in cands]
             Wn[c] = cands[int(np.argmin(costs))]
+            won(trace, "frame", frames[c], costs, src)
         W = Wn
         Gn = G.copy()
         for j in range(NT):
@@ -276,13 +487,14 @@ def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_st
                 continue
             cands = [G[j]]
             sm = [m for m in ms if seedable[m]]
-            for k in LR.top_k([area[m] for m in sm], MAX_CAND):
-                m = sm[k]
-                Wi = inv(W[oc[m]])
+            for kk in LR.top_k([area[m] for m in sm], MAX_CAND):
+                m = sm[kk]
+                Wi = inv(Ev[m] @ W[oc[m]])
                 cands += [Wi @ To[m], Wi @ mirror4(To[m])]
-            Wm, uvm = W[oc[ms]], uv[ms]
-            costs = [float(obs_costs(cam, Wm, np.broadcast_to(Tg, (len(ms), 4, 4)), uvm, h).sum()) for Tg in cands]
+            Wm, uvm = Wview(W, ms), uv[ms]
+            costs = [float(view_costs(table, ovc[ms], Wm, np.broadcast_to(Tg, (len(ms), 4, 4)), uvm, hv[ms]).sum()) for Tg in cands]
             Gn[j] = cands[int(np.argmin(costs))]
+            won(trace, "tag", ids[j], costs, [ids[j]] * (len(cands) // 2))
         G = Gn
     Gw = G[wt].copy()
     Mi = inv(Gw)
@@ -295,32 +507,36 @@ def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_st
         ms = [m for m in by_tag[j] if act[m]]
         if j == wt or not ms:
             continue
-        Ws, uvs = [W[oc[m]] for m in ms], [uv[m] for m in ms]
-        T0, c0 = tag_lm(cam, G[j], Ws, uvs, h)
-        big = min(range(len(ms)), key=lambda k: (-area[ms[k]], k))
+        Ws, uvs = list(Wview(W, ms)), [uv[m] for m in ms]
+        T0, c0 = tag_lm(table, ovc[ms], G[j], Ws, uvs, ht[j])
+        big = min(range(len(ms)), key=lambda kk: (-area[ms[kk]], kk))
         Wb = Ws[big]
-        T1, c1 = tag_lm(cam, inv(Wb) @ mirror4(Wb @ G[j]), Ws, uvs, h)
+        T1, c1 = tag_lm(table, ovc[ms], inv(Wb) @ mirror4(Wb @ G[j]), Ws, uvs, ht[j])
         G[j] = T1 if c1 < c0 else T0
         if trace is not None and c1 < c0:
             trace.setdefault("flipped", []).append(ids[j])
 
     # behind the camera, dropped frames, mapped tags
-    X = obj3(h)
     for m in range(M):
         if act[m]:
-            Pm = (X @ G[ot[m]][:3, :3].T + G[ot[m]][:3, 3]) @ W[oc[m]][:3, :3].T + W[oc[m]][:3, 3]
+            Wv = Ev[m] @ W[oc[m]]
+            Pm = (obj3(hv[m]) @ G[ot[m]][:3, :3].T + G[ot[m]][:3, 3]) @ Wv[:3, :3].T + Wv[:3, 3]
             act[m] = bool((Pm[:, 2] > BEHIND_MARGIN).all())
+            if trace is not None and not act[m]:
+                trace.setdefault("behind", []).append(ids[ot[m]])
     cstat = np.where(cplaced, 0, 5)
     for c in range(NC):
-        if cplaced[c] and act[by_cam[c]].sum() < 2:
+        if cplaced[c] and len({int(ot[m]) for m in by_cam[c] if act[m]}) < 2:
             cstat[c] = 3
             act[by_cam[c]] = False
     mapped = np.array([j == wt or act[by_tag[j]].any() for j in range(NT)], dtype=bool)
     n_obs = int(act.sum())
 
+    # the joint LM
     status = 0
     cost0 = cost = 0.0
     it = 0
+    n_soft = 0
     cams_used = [c for c in range(NC) if cstat[c] == 0]
     free_tags = [j for j in range(NT) if mapped[j] and j != wt]
     if n_obs == 0:
@@ -328,14 +544,21 @@ def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_st
     else:
         cam_col = np.full(NC, -1)
         tag_col = np.full(NT, -1)
-        for k, c in enumerate(cams_used):
-            cam_col[c] = 6 * k
-        for k, j in enumerate(free_tags):
-            tag_col[j] = 6 * (len(cams_used) + k)
+        for i, c in enumerate(cams_used):
+            cam_col[c] = 6 * i
+        for i, j in enumerate(free_tags):
+            tag_col[j] = 6 * (len(cams_used) + i)
         npar = 6 * (len(cams_used) + len(free_tags))
         a = np.flatnonzero(act)
-        seed_obs = obs_costs(cam, W[oc], G[ot], uv, h)
-        cost, H, g = joint_linearise(cam, W, G, oc[a], ot[a], uv[a], h, cam_col, tag_col, npar)
+        if reverse:
+            a = a[::-1]
+
+        def lin(Wx, Gx):
+            return joint_linearise(table, Wx, Gx, oc[a], ot[a], ovc[a], uv[a], hv[a], cam_col, tag_col, npar, k, trace)
+
+        allv = np.arange(M)
+        seed_obs = view_costs(table, ovc, Wview(W, allv), G[ot], uv, hv, k)
+        cost, H, g = lin(W, G)
         cost0 = cost
         lam = 1e-3
         while it < max_iters:
@@ -353,9 +576,11 @@ def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_st
                 Wn[c] = gn_oracle.apply_update(W[c], d[cam_col[c]:cam_col[c] + 6])
             for j in free_tags:
                 Gn[j] = gn_oracle.apply_update(G[j], d[tag_col[j]:tag_col[j] + 6])
-            cn, Hn, gn = joint_linearise(cam, Wn, Gn, oc[a], ot[a], uv[a], h, cam_col, tag_col, npar)
+            cn, Hn, gn = lin(Wn, Gn)
             if cn < cost:
                 stop = cost - cn < 1e-12 * cost
+                if trace is not None:
+                    trace.setdefault("decreases", []).append((cost - cn) / cost)
                 W, G, cost, H, g = Wn, Gn, cn, Hn, gn
                 lam = max(lam * 0.1, 1e-12)
                 if stop:
@@ -364,14 +589,30 @@ def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_st
                 lam *= 10
         if status == 0 and not np.isfinite(cost):
             status = 3
+        if k > 0:
+            rho, w, over, s, ok = corner_terms(table, ovc, Wview(W, allv), G[ot], uv, hv, k)
+        if status == 0 and k > 0:
+            wmin = w.min(axis=1)
+            n_soft = int((over.any(axis=1) & act).sum())
+            slot_weight[ovc[act], ofr[act], osl[act]] = wmin[act]
+            if trace is not None:
+                trace["margin"] = min(trace.get("margin", np.inf), margin(s[act], ok[act], k))
+        elif status == 0:
+            slot_weight[ovc[act], ofr[act], osl[act]] = 1.0
         if status == 0 and with_std:
-            dof = 8 * n_obs - 6 * len(cams_used) - 6 * len(free_tags)
-            s2 = cost / dof if dof > 0 else 0.0
+            if k > 0:
+                inl = ~over[act]
+                n_in = int(inl.sum())
+                dof = 2 * n_in - 6 * len(cams_used) - 6 * len(free_tags)
+                s2 = float(np.where(ok[act], s[act] * s[act], LR.BEHIND_COST)[inl].sum()) / dof if dof > 0 else 0.0
+            else:
+                dof = 8 * n_obs - 6 * len(cams_used) - 6 * len(free_tags)
+                s2 = cost / dof if dof > 0 else 0.0
             Li = solve_triangular(np.linalg.cholesky(H), np.eye(npar), lower=True)    # diag(H^-1)_i = |L^-1 e_i|^2
             Hid = (Li * Li).sum(axis=0)
             for j in free_tags:
                 tag_std[ids[j]] = np.sqrt(s2 * Hid[tag_col[j]:tag_col[j] + 6])
-        fin = obs_costs(cam, W[oc], G[ot], uv, h)
+        fin = view_costs(table, ovc, Wview(W, allv), G[ot], uv, hv, k)
 
     # records
     for c, f in enumerate(frames):
@@ -392,6 +633,7 @@ def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_st
         if mapped[j] and status == 0:
             out_map["T"][ids[j]] = G[j][:3].ravel()
             out_map["valid"][ids[j]] = 1
+            out_map["size"][ids[j]] = sizes[ids[j]]
     res["cost_seed"], res["cost"] = cost0, cost
     if n_obs:
         res["rms_px"], res["rms_seed_px"] = np.sqrt(cost / (4.0 * n_obs)), np.sqrt(cost0 / (4.0 * n_obs))
@@ -401,4 +643,5 @@ def map_frames(obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_st
     res["n_obs_dropped"] = M - n_obs
     res["iterations"] = it
     res["status"] = status
-    return res, out_map, tag_std, poses
+    res["n_soft"] = n_soft
+    return res, out_map, tag_std, poses, slot_weight

@@ -1,7 +1,7 @@
 """Inputs and recorded figures of the rig map-reconstruction tests (tests/test_map_rig_ref.py on the CPU,
 tests/test_gpu_map_rig.py on the device): camera-major asl_obs blocks (n_cams, n_frames, max_tags) of the bench scene seen by
 rigs with known mountings (rig_cases.exact_block with the true pose in every slot, as map_cases has it).  Every figure here
-was measured on the CPU with the NumPy statement (tests/map_rig_ref.py) -- never with the kernels; test_map_rig_ref.py
+was measured on the CPU with the NumPy statement (tests/map_ref.py) -- never with the kernels; test_map_rig_ref.py
 measures them again."""
 import functools
 
@@ -10,7 +10,6 @@ import numpy as np
 import localize_cases as LC
 import map_cases as MC
 import map_ref as MR
-import map_rig_ref as GR
 import rig_cases as RC
 import smooth_rig_cases as SRC
 from aprilslam_amd import _lib
@@ -139,7 +138,7 @@ def truth_errors(out, poses, world_id=None):
 
 
 def run(obs, rig, huber=0.0, max_iters=ITERS, reverse=False, trace=None, with_std=True, world_id=-1):
-    return GR.map_frames(obs, N_IDS, rig, TAG, world_id=world_id, huber_px=huber, max_iters=max_iters, trace=trace, reverse=reverse,
+    return MR.map_rig_frames(obs, N_IDS, rig, TAG, world_id=world_id, huber_px=huber, max_iters=max_iters, trace=trace, reverse=reverse,
                          with_std=with_std)
 
 

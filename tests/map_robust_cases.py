@@ -8,7 +8,6 @@ import numpy as np
 import localize_cases as LC
 import map_cases as MC
 import map_ref as MR
-import map_robust_ref as RR
 
 K = MC.K_bench()
 HUBER = 1.0
@@ -116,10 +115,10 @@ REPAIR_ROWS = ("slip", "swap", "swap3")
 
 @functools.lru_cache(maxsize=None)
 def statement(name, huber=HUBER, reverse=False, max_iters=ITERS):
-    """(outputs of map_robust_ref.map_frames, trace) of a repair case"""
+    """(outputs of map_ref.map_frames, trace) of a repair case"""
     obs, _, _, dist, _ = repair_cases()[name]
     trace = {}
-    out = RR.map_frames(obs, MC.N_IDS, K, dist, LC.TAG_INNER, huber_px=huber, max_iters=max_iters, trace=trace, reverse=reverse)
+    out = MR.map_frames(obs, MC.N_IDS, K, dist, LC.TAG_INNER, huber_px=huber, max_iters=max_iters, trace=trace, reverse=reverse)
     return out, trace
 
 
@@ -231,5 +230,5 @@ def compared_cases():
 
 
 def run(obs, dist, huber=HUBER, max_iters=ITERS, reverse=False, trace=None, with_std=True):
-    return RR.map_frames(obs, MC.N_IDS, K, dist, LC.TAG_INNER, huber_px=huber, max_iters=max_iters, trace=trace, reverse=reverse,
+    return MR.map_frames(obs, MC.N_IDS, K, dist, LC.TAG_INNER, huber_px=huber, max_iters=max_iters, trace=trace, reverse=reverse,
                          with_std=with_std)

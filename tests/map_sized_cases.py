@@ -1,7 +1,7 @@
 """Inputs and recorded figures of the sized tag-map reconstruction tests (tests/test_map_sized_ref.py on the CPU,
 tests/test_gpu_map_sized.py on the device): asl_obs blocks of scenes whose tags have different known sizes, built with
 sized_cases.block (exact projections at the true sizes, records as a PnP at the call's tag_size gives them), at most
-12 frames x 24 slots.  Every figure here was measured on the CPU with the NumPy statement (tests/map_sized_ref.py) -- never
+12 frames x 24 slots.  Every figure here was measured on the CPU with the NumPy statement (tests/map_ref.py) -- never
 with the kernels; test_map_sized_ref.py measures them again."""
 import functools
 
@@ -11,8 +11,6 @@ import localize_cases as LC
 import localize_ref as LR
 import map_ref as MR
 import map_rig_cases as GC
-import map_rig_ref as GR
-import map_sized_ref as ZM
 import rig_cases as RC
 import sized_cases as SC
 import smooth_rig_cases as SRC
@@ -99,12 +97,12 @@ def flip_case():
     obs, rig, t = build(sizes, SOLO, 6, 24, noise=0.0, poses=poses)
     obs = obs.copy()
     tm = sized_scene(sizes)
-    h, half = ZM.tag_half(t[FLIP_TAG], LR.half_size(TAG)), LR.half_size(TAG)
+    h, half = MR.tag_half(t[FLIP_TAG], LR.half_size(TAG)), LR.half_size(TAG)
     W = [MR.inv(T) for T in poses]
     views = [(LR.corner_area(obs["corners"][0, f, s]), f, s) for f, s in zip(*np.nonzero(obs["id"][0] == FLIP_TAG))]
     _, b, _ = max(views, key=lambda v: (v[0], -v[1]))
-    tab = GR.rig_ref.rig_table(rig)
-    G2, _ = GR.tag_lm(tab, [0] * len(views), MR.inv(W[b]) @ MR.mirror4(W[b] @ tm[FLIP_TAG]), [W[f] for _, f, _ in views],
+    tab = MR.rig_ref.rig_table(rig)
+    G2, _ = MR.tag_lm(tab, [0] * len(views), MR.inv(W[b]) @ MR.mirror4(W[b] @ tm[FLIP_TAG]), [W[f] for _, f, _ in views],
                       [obs["corners"][0, f, s].astype(np.float64).reshape(4, 2) for _, f, s in views], h)
     for _, f, s in views:
         T = (W[f] @ G2)[:3].copy()
@@ -195,7 +193,7 @@ def compared_cases():
 
 
 def run(obs, rig, t, huber=0.0, max_iters=ITERS, reverse=False, trace=None, world_id=-1):
-    return ZM.map_frames(obs, N_IDS, rig, TAG, t, world_id=world_id, huber_px=huber, max_iters=max_iters, trace=trace, reverse=reverse)
+    return MR.map_rig_frames(obs, N_IDS, rig, TAG, t, world_id=world_id, huber_px=huber, max_iters=max_iters, trace=trace, reverse=reverse)
 
 
 distance = GC.distance
@@ -221,7 +219,7 @@ def truth_bar():
     """(the statement's error on the equal-size scene of truth_case's geometry, the bar: ten times it): sized_cases.truth_bar's
     rule"""
     obs, t, gt, gp = truth_case(sized=False)
-    base = truth_err(ZM.map_frames(obs, 6, SC.one_camera(), TAG, t, max_iters=ITERS), gt, gp)
+    base = truth_err(MR.map_rig_frames(obs, 6, SC.one_camera(), TAG, t, max_iters=ITERS), gt, gp)
     return base, 10 * base
 
 

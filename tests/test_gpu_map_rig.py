@@ -1,5 +1,5 @@
 """Tag-map reconstruction from a camera rig's frames on the device (asl_map_rig_frames_device / asl_map_rig_batch, k_map.inc)
-against the NumPy statement (tests/map_rig_ref.py): every field of both entry points on the split, overlap and mixed-model
+against the NumPy statement (tests/map_ref.py): every field of both entry points on the split, overlap and mixed-model
 blocks and the edge shapes, with and without the Huber loss; one camera with E = I against asl_map_robust_frames_device;
 determinism; the slot weights; refusals; Rig.build_map and Rig.localize against the map it returns."""
 import ctypes as C

@@ -1,5 +1,5 @@
 """Robust tag-map reconstruction on the device (asl_map_robust_frames_device / asl_map_robust_batch, k_map.inc) against the
-NumPy statement (tests/map_robust_ref.py): every field on the repair cases and the small and edge shapes, in the host and
+NumPy statement (tests/map_ref.py): every field on the repair cases and the small and edge shapes, in the host and
 the device form; huber_px 0 through the new entry points against the plain ones, byte for byte; determinism; the repair
 against the truth; refusals; TagDetector.build_map(huber_px=)."""
 import ctypes as C

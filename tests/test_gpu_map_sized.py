@@ -1,5 +1,5 @@
 """Tag-map reconstruction for tags of different known sizes on the device (asl_map_sized_* / asl_map_rig_sized_*, k_map.inc)
-against the NumPy statement (tests/map_sized_ref.py): the truth on exact data, every field of the host and device forms on
+against the NumPy statement (tests/map_ref.py): the truth on exact data, every field of the host and device forms on
 the cases of tests/map_sized_cases.py (tests/test_map_sized_ref.py checks on the CPU what each is for), the bytes of the
 existing calls, refusals, the round trip through the localisation, and TagDetector.build_map(tag_sizes=)."""
 import ctypes as C

@@ -73,7 +73,7 @@ def test_calibration_matches_the_statement(gpu_detector, case):
 def test_map_matches_the_statement(gpu_detector, case):
     name, obs, n_ids, dist, w, kw, _ = case
     gr, gm, gs, gp = gpu_detector.build_map(obs, n_ids, E.K, dist, LC.TAG_INNER, world_id=w, **kw)
-    wr, wm, ws, wp = MR.map_frames(obs, n_ids, E.K, dist, LC.TAG_INNER, world_id=w, **kw)
+    wr, wm, ws, wp = MR.map_frames(obs, n_ids, E.K, dist, LC.TAG_INNER, world_id=w, **kw)[:4]
     same_ints(gr, wr, ("status", "n_frames_used", "n_tags", "n_obs", "n_obs_dropped", "world_id"))
     same_ints(gm, wm, ("valid",))
     same_ints(gp, wp, ("status", "n_tags", "n_rejected", "seed_slot"))

@@ -2,7 +2,7 @@
 map argument lists with n_cams after the block and the rig table in place of K, dist, n_dist, the library exports them, the
 ctypes argument lists agree, the records keep their sizes, the host entry point refuses a NULL detector before it touches a
 device, and the Python surface has the calls.  The header names the threshold `rig_huber_px` (its `double huber_px` and
-`double huber,` are counted by the sequence solver's ABI tests) and names tests/map_rig_ref.py.  No GPU."""
+`double huber,` are counted by the sequence solver's ABI tests) and names tests/map_ref.py.  No GPU."""
 import ctypes as C
 import inspect
 import os
@@ -26,7 +26,7 @@ def test_header_prototypes():
     want = robh[:2] + ["n_cams"] + robh[2:k] + ["rig"] + robh[k + 3:]
     assert righ == [w if w != "map_huber_px" else "rig_huber_px" for w in want], righ
     src = open(os.path.join(ROOT, "include", "aprilslam.h")).read()
-    assert "tests/map_rig_ref.py" in src
+    assert "tests/map_ref.py" in src
 
 
 def test_exports_and_argtypes():

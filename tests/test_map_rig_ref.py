@@ -1,5 +1,5 @@
-"""The NumPy statement of the rig tag-map reconstruction (tests/map_rig_ref.py): one camera at the identity against the
-single-camera statements, the LM's gradient with a mounting, the fold of a pair's views, the split, overlap and swapped-slot
+"""The NumPy statement of the tag-map reconstruction (tests/map_ref.py) on a camera rig: one camera at the identity against the
+single-camera front, the LM's gradient with a mounting, the fold of a pair's views, the split, overlap and swapped-slot
 cases with their recorded figures, and the measurements the device comparison (tests/test_gpu_map_rig.py) rests on."""
 import numpy as np
 import pytest
@@ -9,9 +9,7 @@ import localize_ref as LR
 import map_cases as MC
 import map_ref as MR
 import map_rig_cases as GC
-import map_rig_ref as GR
 import map_robust_cases as RBC
-import map_robust_ref as RR
 import rig_ref
 from aprilslam_amd.mapping import MapResult
 from aprilslam_amd.rig import Rig, RigCamera
@@ -26,8 +24,8 @@ def test_one_camera_at_the_identity_is_the_single_camera_statement(case):
     _, obs, dist, w = [c for c in MC.cpu_cases(K) if c[0] == case][0]
     solo = Rig([RigCamera(K, dist, np.eye(4))])
     for huber in (0.0, RBC.HUBER):
-        want = RR.map_frames(obs, MC.N_IDS, K, dist, LC.TAG_INNER, world_id=w, huber_px=huber)
-        got = GR.map_frames(obs[None], MC.N_IDS, solo, LC.TAG_INNER, world_id=w, huber_px=huber)
+        want = MR.map_frames(obs, MC.N_IDS, K, dist, LC.TAG_INNER, world_id=w, huber_px=huber)
+        got = MR.map_rig_frames(obs[None], MC.N_IDS, solo, LC.TAG_INNER, world_id=w, huber_px=huber)
         for k in INTS:
             assert got[0][k] == want[0][k], (case, huber, k)
         for k in ("status", "n_tags", "n_rejected", "seed_slot"):
@@ -38,7 +36,7 @@ def test_one_camera_at_the_identity_is_the_single_camera_statement(case):
         np.testing.assert_allclose(got[2], want[2], rtol=1e-6, atol=1e-12)
         if huber == 0.0 and w == -1:
             plain = MR.map_frames(obs, MC.N_IDS, K, dist, LC.TAG_INNER)
-            assert all(a.tobytes() == b.tobytes() for a, b in zip(plain, want[:4]))
+            assert all(a.tobytes() == b.tobytes() for a, b in zip(plain[:4], want[:4]))
 
 
 def small_problem():
@@ -50,8 +48,8 @@ def small_problem():
     ids = [0, 1, 2, 3]
     views = [(f, i, c, int(np.flatnonzero(obs["id"][c, f] == i)[0])) for f in range(3) for c in range(2) for i in ids if i in obs["id"][c, f]]
     rng = np.random.default_rng(2)
-    W = np.array([GR.gn_oracle.apply_update(MR.inv(T), rng.normal(size=6) * 0.01) for T in poses])
-    G = np.array([GR.gn_oracle.apply_update(tm[i], rng.normal(size=6) * 0.01) for i in ids])
+    W = np.array([MR.gn_oracle.apply_update(MR.inv(T), rng.normal(size=6) * 0.01) for T in poses])
+    G = np.array([MR.gn_oracle.apply_update(tm[i], rng.normal(size=6) * 0.01) for i in ids])
     oc = np.array([v[0] for v in views])
     ot = np.array([ids.index(v[1]) for v in views])
     ovc = np.array([v[2] for v in views])
@@ -64,12 +62,12 @@ def small_problem():
 def test_gradient_is_the_central_difference_of_half_the_cost(huber):
     table, W, G, oc, ot, ovc, uv, h = small_problem()
     cam_col, tag_col = 6 * np.arange(3), 18 + 6 * np.arange(4)
-    _, H, g = GR.joint_linearise(table, W, G, oc, ot, ovc, uv, h, cam_col, tag_col, 42, huber)
+    _, H, g = MR.joint_linearise(table, W, G, oc, ot, ovc, uv, h, cam_col, tag_col, 42, huber)
 
     def cost(x):
-        Wx = np.array([GR.gn_oracle.apply_update(W[c], x[6 * c:6 * c + 6]) for c in range(3)])
-        Gx = np.array([GR.gn_oracle.apply_update(G[j], x[18 + 6 * j:24 + 6 * j]) for j in range(4)])
-        return GR.joint_linearise(table, Wx, Gx, oc, ot, ovc, uv, h, cam_col, tag_col, 42, huber)[0]
+        Wx = np.array([MR.gn_oracle.apply_update(W[c], x[6 * c:6 * c + 6]) for c in range(3)])
+        Gx = np.array([MR.gn_oracle.apply_update(G[j], x[18 + 6 * j:24 + 6 * j]) for j in range(4)])
+        return MR.joint_linearise(table, Wx, Gx, oc, ot, ovc, uv, h, cam_col, tag_col, 42, huber)[0]
 
     num = np.zeros(42)
     for i in range(42):
@@ -83,9 +81,9 @@ def test_the_fold_leaves_the_normal_matrix_alone():
     table, W, G, oc, ot, ovc, uv, h = small_problem()
     cam_col, tag_col = 6 * np.arange(3), 18 + 6 * np.arange(4)
     tag_col[0] = -1                                              # a held tag, as the world tag is
-    ca, Ha, ga = GR.joint_linearise(table, W, G, oc, ot, ovc, uv, h, cam_col, tag_col, 42, fold=False)
+    ca, Ha, ga = MR.joint_linearise(table, W, G, oc, ot, ovc, uv, h, cam_col, tag_col, 42, fold=False)
     tr = {}
-    cb, Hb, gb = GR.joint_linearise(table, W, G, oc, ot, ovc, uv, h, cam_col, tag_col, 42, trace=tr, fold=True)
+    cb, Hb, gb = MR.joint_linearise(table, W, G, oc, ot, ovc, uv, h, cam_col, tag_col, 42, trace=tr, fold=True)
     assert tr["pairs"] < tr["views"] == len(oc) and ca == cb
     assert np.abs(Ha - Hb).max() <= 1e-12 * np.abs(Ha).max() and np.abs(ga - gb).max() <= 1e-12 * np.abs(ga).max()
 

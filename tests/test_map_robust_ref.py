@@ -1,4 +1,4 @@
-"""The NumPy statement of the robust tag-map reconstruction (tests/map_robust_ref.py): the plain computation at huber_px 0,
+"""The NumPy statement of the tag-map reconstruction (tests/map_ref.py) under the Huber loss: the plain computation at huber_px 0,
 the loss's gradient, the repair of corrupted slots against the plain solve, the std's variance factor, and the margins and
 tolerance the device comparison (tests/test_gpu_map_robust.py) rests on."""
 import numpy as np
@@ -8,7 +8,6 @@ import localize_cases as LC
 import map_cases as MC
 import map_ref as MR
 import map_robust_cases as RC
-import map_robust_ref as RR
 
 K = RC.K
 
@@ -16,8 +15,8 @@ K = RC.K
 @pytest.mark.parametrize("case", [c[0] for c in MC.cpu_cases(K)])
 def test_huber_0_is_the_plain_statement_byte_for_byte(case):
     name, obs, dist, w = [c for c in MC.cpu_cases(K) if c[0] == case][0]
-    want = MR.map_frames(obs, MC.N_IDS, K, dist, LC.TAG_INNER, world_id=w)
-    got = RR.map_frames(obs, MC.N_IDS, K, dist, LC.TAG_INNER, world_id=w, huber_px=0.0)
+    want = MR.map_frames(obs, MC.N_IDS, K, dist, LC.TAG_INNER, world_id=w)[:4]
+    got = MR.map_frames(obs, MC.N_IDS, K, dist, LC.TAG_INNER, world_id=w, huber_px=0.0)
     assert all(g.tobytes() == x.tobytes() for g, x in zip(got[:4], want))
     assert got[0]["n_soft"] == 0
     weight = got[4]
@@ -39,7 +38,7 @@ def test_gradient_of_half_the_robust_cost():
     """g is the central-difference gradient of half the robust cost at a point that is not the optimum, with corners on
     both sides of the threshold; H is symmetric"""
     obs, tags, cams, _, _ = RC.repair_cases()["small_slip"]
-    cam, h = MR.LR.camera(K, None), MR.LR.half_size(LC.TAG_INNER)
+    table, h = MR.rig_ref.rig_table(MR.one_camera(K, None)), MR.LR.half_size(LC.TAG_INNER)
     w = int(min(i for i in obs["id"].ravel() if i >= 0))
     gt_tags, gt_cams = MC.truth(tags, cams, w)
     ids = sorted(gt_tags)
@@ -52,16 +51,17 @@ def test_gradient_of_half_the_robust_cost():
     fs = [(f, s) for f in range(obs.shape[0]) for s in range(obs.shape[1]) if obs["id"][f, s] >= 0]
     oc = np.array([f for f, _ in fs])
     ot = np.array([ids.index(int(obs["id"][f, s])) for f, s in fs])
+    ovc = np.zeros(len(fs), dtype=np.int64)
     uv = np.stack([obs["corners"][f, s].astype(np.float64).reshape(4, 2) for f, s in fs])
     cam_col = 6 * np.arange(len(W))
     tag_col = np.array([-1 if i == w else 6 * (len(W) + ids.index(i) - (ids.index(i) > ids.index(w))) for i in ids])
     npar = 6 * (len(W) + len(ids) - 1)
-    over = RR.corner_terms(cam, W[oc], G[ot], uv, h, RC.HUBER)[2]
+    over = MR.corner_terms(table, ovc, W[oc], G[ot], uv, h, RC.HUBER)[2]
     assert 0 < over.sum() < over.size
 
     def cost(Wx, Gx):
-        return RR.robust_linearise(cam, Wx, Gx, oc, ot, uv, h, cam_col, tag_col, npar, RC.HUBER)[0]
-    _, H, g = RR.robust_linearise(cam, W, G, oc, ot, uv, h, cam_col, tag_col, npar, RC.HUBER)
+        return MR.joint_linearise(table, Wx, Gx, oc, ot, ovc, uv, h, cam_col, tag_col, npar, RC.HUBER)[0]
+    _, H, g = MR.joint_linearise(table, W, G, oc, ot, ovc, uv, h, cam_col, tag_col, npar, RC.HUBER)
     assert np.array_equal(H, H.T) or np.abs(H - H.T).max() <= 1e-12 * np.abs(H).max()
     num = np.zeros(npar)
     eps = 1e-6
@@ -176,5 +176,5 @@ def test_refusals_and_the_weights_of_a_failed_solve():
             RC.run(obs, dist, huber=bad)
     ids = {int(i) for i in obs["id"].ravel() if i >= 0}
     missing = next(i for i in range(MC.N_IDS) if i not in ids)
-    out = RR.map_frames(obs, MC.N_IDS, K, dist, LC.TAG_INNER, world_id=missing, huber_px=RC.HUBER)
+    out = MR.map_frames(obs, MC.N_IDS, K, dist, LC.TAG_INNER, world_id=missing, huber_px=RC.HUBER)
     assert out[0]["status"] == 1 and out[0]["n_soft"] == 0 and not out[4].any()

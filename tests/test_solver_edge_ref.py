@@ -83,7 +83,7 @@ def test_calibration_statement(case):
 @pytest.mark.parametrize("case", MAP, ids=[c[0] for c in MAP])
 def test_map_statement(case):
     name, obs, n_ids, dist, w, kw, ex = case
-    res, tmap, std, poses = MR.map_frames(obs, n_ids, E.K, dist, LC.TAG_INNER, world_id=w, **kw)
+    res, tmap, std, poses = MR.map_frames(obs, n_ids, E.K, dist, LC.TAG_INNER, world_id=w, **kw)[:4]
     assert res["status"] == 0 and res["n_obs_dropped"] == 0
     if "n_tags" in ex:
         assert res["n_tags"] == ex["n_tags"]
