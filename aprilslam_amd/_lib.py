@@ -762,8 +762,10 @@ class Detector:
         sigma_rot and sigma_trans are per unit of that time, a pair of frames dt apart is held by the prior / sqrt(dt).  Bad
         times (not finite, not increasing) give result status 4, no error.  None: one frame step is one unit, the calls above.
         tag_size is the size of the map entries whose size is 0, as in localize; so it is in smooth_sequences and smooth_rig."""
-        return self._smooth_host(obs, None, tag_map, K, dist, tag_size, (sigma_px, sigma_rot, sigma_trans), max_iters, seed, with_cov, huber_px,
-                                 times)
+        o = _obs_records(obs)
+        keep, Kp, dpp, nd = _camera(K, dist, square=True)
+        return self._smooth_host(o, [o.shape[0], o.shape[1]], tag_map, [Kp, dpp, nd], False, tag_size, seed, times, None,
+                                 (sigma_px, sigma_rot, sigma_trans), huber_px, max_iters, with_cov)
 
     def smooth_device(self, obs_ptr, n_frames, max_tags, map_ptr, n_ids, seed_ptr, out_ptr, result_ptr, K, dist, tag_size, sigma_px=1.0,
                       sigma_rot=0.05, sigma_trans=0.5, max_iters=20, stream=0, cov_ptr=None, huber_px=0.0, times_ptr=None):
@@ -772,8 +774,9 @@ class Detector:
         are device addresses; enqueued on `stream`, no wait.  cov_ptr not None (n_frames asl_pose_cov):
         asl_smooth_cov_frames_device.  huber_px > 0: asl_smooth_robust_sequences_device with the one sequence.  times_ptr not
         None (n_frames doubles on the device): asl_smooth_timed_sequences_device with the one sequence."""
-        self._smooth_device((obs_ptr, map_ptr, seed_ptr, out_ptr, result_ptr), n_frames, max_tags, n_ids, None, K, dist, tag_size,
-                            (sigma_px, sigma_rot, sigma_trans), max_iters, stream, cov_ptr, huber_px, times_ptr)
+        keep, Kp, dpp, nd = _camera(K, dist, square=True)
+        self._smooth_call(True, obs_ptr, [int(n_frames), int(max_tags)], map_ptr, n_ids, [Kp, dpp, nd], False, tag_size, seed_ptr, times_ptr, None,
+                          (sigma_px, sigma_rot, sigma_trans), huber_px, max_iters, (out_ptr, result_ptr, cov_ptr), cov_ptr is not None, stream)
 
     @staticmethod
     def _seq_start(seq_start, n_frames):
@@ -795,8 +798,10 @@ class Detector:
         and so is huber_px (> 0: asl_smooth_robust_sequences_batch, as in smooth()).  times: (n_frames,) float64, every
         sequence's own frame times end to end (asl_smooth_timed_sequences_batch, as in smooth()); they need to increase inside a
         sequence only, and a sequence with bad times has result status 4 while the others are solved."""
-        return self._smooth_host(obs, seq_start, tag_map, K, dist, tag_size, (sigma_px, sigma_rot, sigma_trans), max_iters, seed, with_cov, huber_px,
-                                 times)
+        o = _obs_records(obs)
+        keep, Kp, dpp, nd = _camera(K, dist, square=True)
+        return self._smooth_host(o, [o.shape[0], o.shape[1]], tag_map, [Kp, dpp, nd], False, tag_size, seed, times, seq_start,
+                                 (sigma_px, sigma_rot, sigma_trans), huber_px, max_iters, with_cov)
 
     def smooth_sequences_device(self, obs_ptr, n_frames, max_tags, map_ptr, n_ids, seed_ptr, seq_start, out_ptr, results_ptr, K, dist,
                                 tag_size, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, stream=0, cov_ptr=None, huber_px=0.0,
@@ -805,58 +810,9 @@ class Detector:
         results_ptr n_seq asl_smooth_result on the device, cov_ptr None or n_frames asl_pose_cov.  Enqueued on `stream`, no
         wait; seq_start is read before this returns.  huber_px > 0: asl_smooth_robust_sequences_device.  times_ptr not None
         (n_frames doubles on the device): asl_smooth_timed_sequences_device."""
-        self._smooth_device((obs_ptr, map_ptr, seed_ptr, out_ptr, results_ptr), n_frames, max_tags, n_ids, seq_start, K, dist, tag_size,
-                            (sigma_px, sigma_rot, sigma_trans), max_iters, stream, cov_ptr, huber_px, times_ptr)
-
-    def _smooth_host(self, obs, seq_start, tag_map, K, dist, tag_size, sigmas, max_iters, seed, with_cov, huber_px=0.0, times=None):
-        """smooth (seq_start None: asl_smooth_batch / asl_smooth_cov_batch, whose n_frames bound is a sequence's) and
-        smooth_sequences (asl_smooth_sequences_batch); huber_px other than 0.0: asl_smooth_robust_sequences_batch for both, the
-        one sequence [0, n] for smooth; times not None: asl_smooth_timed_sequences_batch for both, huber_px as it is"""
-        o, m = _obs_records(obs), _map_records(tag_map)
         keep, Kp, dpp, nd = _camera(K, dist, square=True)
-        n = o.shape[0]
-        sd = None if seed is None else np.ascontiguousarray(seed, dtype=CAM_POSE_DTYPE).ravel()
-        if sd is not None and len(sd) != n:
-            raise ValueError("seed must hold one pose per frame")
-        out = np.zeros(n, dtype=CAM_POSE_DTYPE)
-        cov = np.zeros(n, dtype=POSE_COV_DTYPE) if with_cov else None
-        tm = None if times is None else np.ascontiguousarray(times, dtype=np.float64).ravel()
-        if tm is not None and len(tm) != n:
-            raise ValueError("times must hold one value per frame")
-        robust = (float(huber_px),) if huber_px != 0.0 or tm is not None else ()
-        timed = () if tm is None else (tm.ctypes.data_as(C.POINTER(C.c_double)),)
-        if seq_start is None and not robust:
-            fn, seqs, last = (self._L.asl_smooth_cov_batch, (), (_data(cov),)) if with_cov else (self._L.asl_smooth_batch, (), ())
-        else:
-            ss, ssp, n_seq = self._seq_start([0, n] if seq_start is None else seq_start, n)
-            fn = (self._L.asl_smooth_timed_sequences_batch if timed else self._L.asl_smooth_robust_sequences_batch if robust
-                  else self._L.asl_smooth_sequences_batch)
-            seqs, last = (ssp, n_seq), (_data(cov) if with_cov else None,)
-        res = np.zeros(seqs[1] if seqs else (), dtype=SMOOTH_RESULT_DTYPE)
-        check(fn(self._h, _data(o), n, o.shape[1], _data(m), len(m), Kp, dpp, nd, float(tag_size), None if sd is None else sd.ctypes.data, *timed, *seqs,
-                 *map(float, sigmas), *robust, int(max_iters), _data(out), res.ctypes.data, *last))
-        if seq_start is None and robust:
-            res = res[0]
-        return (out, res, cov) if with_cov else (out, res)
-
-    def _smooth_device(self, ptrs, n_frames, max_tags, n_ids, seq_start, K, dist, tag_size, sigmas, max_iters, stream, cov_ptr, huber_px=0.0,
-                       times_ptr=None):
-        """smooth_device (seq_start None: asl_smooth_frames_device / asl_smooth_cov_frames_device) and smooth_sequences_device
-        (asl_smooth_sequences_device); ptrs: the addresses of obs, map, seed, out and result(s); huber_px other than 0.0:
-        asl_smooth_robust_sequences_device for both; times_ptr not None: asl_smooth_timed_sequences_device for both"""
-        obs_ptr, map_ptr, seed_ptr, out_ptr, result_ptr = ptrs
-        keep, Kp, dpp, nd = _camera(K, dist, square=True)
-        timed = () if times_ptr is None else (_ptr(times_ptr),)
-        robust = (float(huber_px),) if huber_px != 0.0 or timed else ()
-        if seq_start is None and not robust:
-            fn, seqs, last = (self._L.asl_smooth_frames_device, (), ()) if cov_ptr is None else (self._L.asl_smooth_cov_frames_device, (), (_ptr(cov_ptr),))
-        else:
-            ss, ssp, n_seq = self._seq_start([0, int(n_frames)] if seq_start is None else seq_start, n_frames)
-            fn = (self._L.asl_smooth_timed_sequences_device if timed else self._L.asl_smooth_robust_sequences_device if robust
-                  else self._L.asl_smooth_sequences_device)
-            seqs, last = (ssp, n_seq), (_opt_ptr(cov_ptr),)
-        check(fn(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids), Kp, dpp, nd, float(tag_size), _ptr(seed_ptr), *timed, *seqs,
-                 *map(float, sigmas), *robust, int(max_iters), _ptr(out_ptr), _ptr(result_ptr), *last, _ptr(stream)))
+        self._smooth_call(True, obs_ptr, [int(n_frames), int(max_tags)], map_ptr, n_ids, [Kp, dpp, nd], False, tag_size, seed_ptr, times_ptr, seq_start,
+                          (sigma_px, sigma_rot, sigma_trans), huber_px, max_iters, (out_ptr, results_ptr, cov_ptr), cov_ptr is not None, stream)
 
     def smooth_rig(self, obs, tag_map, rig, tag_size, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, seed=None, seq_start=None,
                    times=None, huber_px=0.0, with_cov=False):
@@ -869,27 +825,11 @@ class Detector:
         o = np.ascontiguousarray(obs, dtype=OBS_DTYPE)
         if o.ndim != 3:
             raise ValueError("obs must be (n_cams, n_frames, max_tags) asl_obs records")
-        m, r = _map_records(tag_map), _rig_records(rig)
+        r = _rig_records(rig)
         if len(r) != o.shape[0]:
             raise ValueError("the rig has %d cameras, obs has %d" % (len(r), o.shape[0]))
-        n = o.shape[1]
-        sd = None if seed is None else np.ascontiguousarray(seed, dtype=CAM_POSE_DTYPE).ravel()
-        if sd is not None and len(sd) != n:
-            raise ValueError("seed must hold one pose per frame")
-        tm = None if times is None else np.ascontiguousarray(times, dtype=np.float64).ravel()
-        if tm is not None and len(tm) != n:
-            raise ValueError("times must hold one value per frame")
-        ss, ssp, n_seq = self._seq_start([0, n] if seq_start is None else seq_start, n)
-        out = np.zeros(n, dtype=CAM_POSE_DTYPE)
-        res = np.zeros(max(n_seq, 0), dtype=SMOOTH_RESULT_DTYPE)
-        cov = np.zeros(n, dtype=POSE_COV_DTYPE) if with_cov else None
-        check(self._L.asl_smooth_rig_sequences_batch(self._h, _data(o), o.shape[0], n, o.shape[2], _data(m), len(m), _data(r), float(tag_size),
-                                                     None if sd is None else sd.ctypes.data, None if tm is None else tm.ctypes.data_as(_DP), ssp, n_seq,
-                                                     float(sigma_px), float(sigma_rot), float(sigma_trans), float(huber_px), int(max_iters),
-                                                     _data(out), _data(res), _data(cov) if with_cov else None))
-        if seq_start is None:
-            res = res[0]
-        return (out, res, cov) if with_cov else (out, res)
+        return self._smooth_host(o, list(o.shape), tag_map, [_data(r)], True, tag_size, seed, times, seq_start, (sigma_px, sigma_rot, sigma_trans),
+                                 huber_px, max_iters, with_cov)
 
     def smooth_rig_device(self, obs_ptr, n_cams, n_frames, max_tags, map_ptr, n_ids, rig_ptr, seed_ptr, out_ptr, results_ptr, tag_size,
                           sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, seq_start=None, stream=0, times_ptr=None, huber_px=0.0,
@@ -899,11 +839,61 @@ class Detector:
         localize_rig_device wrote them), out_ptr (n_frames asl_cam_pose) and results_ptr (n_seq asl_smooth_result) are device
         addresses; seq_start: None (the one sequence) or a HOST array of n_seq + 1 offsets; times_ptr: None or n_frames doubles
         on the device; cov_ptr: None or n_frames asl_pose_cov.  Enqueued on `stream` after the table's check."""
-        ss, ssp, n_seq = self._seq_start([0, int(n_frames)] if seq_start is None else seq_start, n_frames)
-        check(self._L.asl_smooth_rig_sequences_device(self._h, _ptr(obs_ptr), int(n_cams), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids),
-                                                      _opt_ptr(rig_ptr), float(tag_size), _ptr(seed_ptr), _opt_ptr(times_ptr), ssp, n_seq,
-                                                      float(sigma_px), float(sigma_rot), float(sigma_trans), float(huber_px), int(max_iters),
-                                                      _ptr(out_ptr), _ptr(results_ptr), _opt_ptr(cov_ptr), _ptr(stream)))
+        self._smooth_call(True, obs_ptr, [int(n_cams), int(n_frames), int(max_tags)], map_ptr, n_ids, [rig_ptr], True, tag_size, seed_ptr, times_ptr,
+                          seq_start, (sigma_px, sigma_rot, sigma_trans), huber_px, max_iters, (out_ptr, results_ptr, cov_ptr), cov_ptr is not None, stream)
+
+    def _smooth_host(self, o, dims, tag_map, model, rig, tag_size, seed, times, seq_start, sigmas, huber_px, max_iters, with_cov):
+        """the host form of _smooth_call on the block o: seed and times checked against its frames, the outputs allocated ->
+        (poses, result(s)[, cov]); one result record where seq_start is None"""
+        m = _map_records(tag_map)
+        n = dims[-2]
+        sd = None if seed is None else np.ascontiguousarray(seed, dtype=CAM_POSE_DTYPE).ravel()
+        if sd is not None and len(sd) != n:
+            raise ValueError("seed must hold one pose per frame")
+        tm = None if times is None else np.ascontiguousarray(times, dtype=np.float64).ravel()
+        if tm is not None and len(tm) != n:
+            raise ValueError("times must hold one value per frame")
+        out = np.zeros(n, dtype=CAM_POSE_DTYPE)
+        res = np.zeros(1 if seq_start is None else max(np.size(seq_start) - 1, 0), dtype=SMOOTH_RESULT_DTYPE)
+        cov = np.zeros(n, dtype=POSE_COV_DTYPE) if with_cov else None
+        n_seq = self._smooth_call(False, _data(o), dims, _data(m), len(m), model, rig, tag_size, None if sd is None else sd.ctypes.data,
+                                  None if tm is None else tm.ctypes.data_as(_DP), seq_start, sigmas, huber_px, max_iters,
+                                  (_data(out), res.ctypes.data, _data(cov) if with_cov else None), with_cov)
+        if seq_start is None:
+            res = res.reshape(()) if n_seq is None else res[0]
+        return (out, res, cov) if with_cov else (out, res)
+
+    def _smooth_call(self, device, obs, dims, tag_map, n_ids, model, rig, tag_size, seed, times, seq_start, sigmas, huber_px, max_iters, outs,
+                     with_cov, stream=0):
+        """The one sequence-localisation call.  Its entry point, _batch or (device) _frames_device for the first two rows and
+        _device for the others, whose addresses are then the device's:
+
+            rig  times  huber_px  seq_start  cov   entry
+            no   none   0         None       no    asl_smooth
+            no   none   0         None       yes   asl_smooth_cov
+            no   none   0         given      any   asl_smooth_sequences         (seq_start, n_seq after seed)
+            no   none   != 0      any        any   asl_smooth_robust_sequences  (huber_px after the sigmas; [0, n] for None)
+            no   given  any       any        any   asl_smooth_timed_sequences   (times after seed)
+            yes  any    any       any        any   asl_smooth_rig_sequences     (times, which may be NULL, after seed)
+
+        dims: the block's extents, n_frames the last but one; model: K, dist, n_dist or [the rig table's address]; outs: poses,
+        result(s), cov (NULL without with_cov).  Returns n_seq as the entry got it, None for the two entries without offsets."""
+        req, opt = (_ptr, _opt_ptr) if device else (lambda p: p, lambda p: p)
+        timed = bool(rig or times is not None)
+        robust = bool(timed or huber_px != 0.0)
+        plain = not robust and seq_start is None
+        ss, ssp, n_seq = self._seq_start([0, dims[-2]] if seq_start is None else seq_start, dims[-2])
+        args = [self._h, req(obs)] + dims + [req(tag_map), int(n_ids)] + ([opt(model[0])] if rig else model) + [float(tag_size), req(seed)]
+        args += ([opt(times)] if timed else []) + ([] if plain else [ssp, n_seq]) + [float(s) for s in sigmas]
+        args += ([float(huber_px)] if robust else []) + [int(max_iters), req(outs[0]), req(outs[1])] + ([opt(outs[2])] if with_cov or not plain else [])
+        if device:
+            args.append(_ptr(stream))
+        if plain:
+            name = "asl_smooth" + ("_cov" if with_cov else "") + ("_frames_device" if device else "_batch")
+        else:
+            name = "asl_smooth_%ssequences" % ("rig_" if rig else "timed_" if timed else "robust_" if robust else "") + ("_device" if device else "_batch")
+        check(getattr(self._L, name)(*args))
+        return None if plain else n_seq
 
     def collect_view(self):
         """Wait for the submitted batch; (dets, poses or None, n_per_frame) as numpy VIEWS of the detector's page-locked result

@@ -17,12 +17,12 @@
 // times[f] - times[p] where the plain call divides by f - p.  Times of two sequences are unrelated.  A sequence with a time that
 // is not finite or a dt <= 0 is found by k_smooth_scan and solved as one without a posed frame, result status 4.  Every other
 // call leaves times NULL: a branch on the pointer, one value in the whole launch, ahead of each of the three places; no
-// instantiation of its own.  tests/smooth_timed_ref.py states it.
+// instantiation of its own.  tests/smooth_ref.py states it (times).
 // asl_smooth_rig_sequences_* (a rig, k_rig.inc): the pose solved for is rig<-world, a frame's slots are the n_cams * max_tags
 // global slots of the camera-major block.  Only the two kernels that cost corners look at a camera, and their bodies are
 // written once over a slot model (smooth_cand_frame, smooth_lin_frame; loc_solve_frame does the same for the localisation):
 // k_smooth_cand / k_smooth_lin are set-up, LocOneCam and one call, k_smooth_rig_cand / k_smooth_rig_lin the camera table to
-// LDS, LocRig and the same call.  Every other kernel below runs as it is.  tests/smooth_rig_ref.py states it.
+// LDS, LocRig and the same call.  Every other kernel below runs as it is.  tests/smooth_ref.py states it (smooth_rig).
 //   seed chain   k_smooth_cand   one wavefront per frame: the seed's pose A and, for a frame of exactly one taking-part slot,
 //                                its mirrored planar minimum B (loc_candidate), both costed over the frame's corners
 //                k_smooth_scan   one wavefront a sequence: the nearest posed frame at or before every frame (wave_scan of a maximum)

@@ -693,7 +693,7 @@ int asl_smooth_sequences_batch(asl_detector *det, const asl_obs *obs, int n_fram
    where the clean one stopped after 5): raise max_iters.  huber_px == 0 is the plain computation: d_out, d_results and d_cov are byte for byte what
    asl_smooth_sequences_device writes, n_soft 0.
    ASL_EINVAL, nothing written: whatever asl_smooth_sequences_device refuses; huber_px < 0 or not finite.  Nothing waits;
-   deterministic: the same input gives the same bytes.  tests/smooth_robust_ref.py states the computation. */
+   deterministic: the same input gives the same bytes.  tests/smooth_ref.py states the computation (huber_px > 0). */
 int asl_smooth_robust_sequences_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
                                        const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed,
                                        const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,
@@ -722,7 +722,7 @@ int asl_smooth_robust_sequences_batch(asl_detector *det, const asl_obs *obs, int
    frames have the records of status 1 (T the identity, seed_slot -1), its d_cov records status 1; the other sequences of
    the call are what they are without it, so a sequence of a batch stays byte for byte what the call alone returns.
    ASL_EINVAL, nothing written: whatever asl_smooth_robust_sequences_device refuses; d_times overlapping d_out or d_cov.
-   Nothing waits; deterministic: the same input gives the same bytes.  tests/smooth_timed_ref.py states the computation. */
+   Nothing waits; deterministic: the same input gives the same bytes.  tests/smooth_ref.py states the computation (times). */
 int asl_smooth_timed_sequences_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
                                       const double *K, const double *dist, int n_dist, double tag_size, const void *d_seed,
                                       const double *d_times, const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot,
@@ -762,7 +762,7 @@ int asl_smooth_timed_sequences_batch(asl_detector *det, const asl_obs *obs, int 
    ASL_EINVAL, nothing written or enqueued: whatever asl_smooth_timed_sequences_device refuses of the arguments both have;
    d_rig NULL; n_cams outside [1, 16]; n_cams * max_tags > 256; a camera with n_dist not 0 / 4 / 5, a non-finite K or E or
    an E whose rotation part is not orthonormal to 1e-6.  Deterministic: the same input gives the same bytes.
-   tests/smooth_rig_ref.py states the computation. */
+   tests/smooth_ref.py states the computation (smooth_rig). */
 int asl_smooth_rig_sequences_device(asl_detector *det, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map,
                                     int n_ids, const void *d_rig, double tag_size, const void *d_seed, const double *d_frame_times,
                                     const int32_t *seq_start, int n_seq, double sigma_px, double sigma_rot, double sigma_trans,

@@ -264,7 +264,7 @@ def smooth_case():
     obs = noisy(exact, 0.2, 1203)
     seed = ZR.localize(exact, rec, K, None, TAG)
     with ZR.honoured(TAG):
-        seed = SC.mirror_seed(SR.Problem(obs, rec, K, None, TAG, *SMOOTH_SIGMAS), seed, (4,))
+        seed = SC.mirror_seed(SR.problem(obs, rec, K, None, TAG, *SMOOTH_SIGMAS), seed, (4,))
     return obs, rec, seed
 
 

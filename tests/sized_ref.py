@@ -34,8 +34,8 @@ import numpy as np
 import calib_ref as CR
 import localize_ref as LR
 import rig_ref as RR
-import smooth_rig_ref as SG
-import smooth_timed_ref as ST
+import smooth_cov_ref as SV
+import smooth_ref as SR
 
 
 def tag_half(tag_map, tag_id, tag_size):
@@ -173,18 +173,18 @@ def calibrate(obs, tag_map, tag_size, width, height, **kw):
 
 
 def smooth(obs, tag_map, K, dist, tag_size, seed, times, *args, **kw):
-    """smooth_timed_ref.smooth (times None: smooth_ref.smooth to the bit) over a sized map"""
+    """smooth_ref.smooth over a sized map"""
     with honoured(tag_size):
-        return ST.smooth(obs, tag_map, K, dist, tag_size, seed, times, *args, **kw)
+        return SR.smooth(obs, tag_map, K, dist, tag_size, seed, *args, times=times, **kw)
 
 
 def smooth_cov(obs, tag_map, K, dist, tag_size, poses, result, times, *args, **kw):
-    """smooth_timed_ref.smooth_cov over a sized map"""
+    """smooth_cov_ref.smooth_cov over a sized map"""
     with honoured(tag_size):
-        return ST.smooth_cov(obs, tag_map, K, dist, tag_size, poses, result, times, *args, **kw)
+        return SV.smooth_cov(obs, tag_map, K, dist, tag_size, poses, result, *args, times=times, **kw)
 
 
 def smooth_rig(obs, tag_map, rig, tag_size, seed, *args, **kw):
-    """smooth_rig_ref.smooth over a sized map"""
+    """smooth_ref.smooth_rig over a sized map"""
     with honoured(tag_size):
-        return SG.smooth(obs, tag_map, rig, tag_size, seed, *args, **kw)
+        return SR.smooth_rig(obs, tag_map, rig, tag_size, seed, *args, **kw)

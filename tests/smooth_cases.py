@@ -105,7 +105,7 @@ def flips(first=False):
     obs = np.stack([LC.exact_frame(FLIP_TAG, p, r, K, max_tags=1) for p, r in cams])
     seed = seeds_of(obs, rec)
     frames = (0,) if first else (3, 4, 9)
-    pb = SR.Problem(obs, rec, K, None, TAG, *FLIPS_SIGMAS)
+    pb = SR.problem(obs, rec, K, None, TAG, *FLIPS_SIGMAS)
     return obs, rec, mirror_seed(pb, seed, frames), truths(cams), frames
 
 
@@ -148,7 +148,7 @@ def shape(n, max_tags, n_dist):
         obs, exact = empty(obs, range(3, n, 7)), empty(exact, range(3, n, 7))
     seed = seeds_of(exact, rec, dist)
     if max_tags == 1 and n >= 5:
-        seed = mirror_seed(SR.Problem(obs, rec, K, dist, TAG, *SHAPE_SIGMAS), seed, (1, n - 3))
+        seed = mirror_seed(SR.problem(obs, rec, K, dist, TAG, *SHAPE_SIGMAS), seed, (1, n - 3))
     return obs, rec, seed, dist
 
 

@@ -69,7 +69,7 @@ def statement_cov(name):
     """the statement's covariance at the statement's own poses"""
     obs, rec, seed, dist, sig, iters = prior_only() if name == "prior_only" else case(name)
     poses, res = statement(name)
-    return SV.smooth_cov(obs, rec, SC.K, dist, SC.TAG, poses, res, *sig)
+    return SV.smooth_cov(obs, rec, SC.K, dist, SC.TAG, poses, res, *sig)[0]
 
 
 # ---- statistical consistency: sequences drawn from the prior itself
@@ -124,7 +124,7 @@ def nees_of_run(run):
     """(NEES_FRAMES,) e^T C^-1 e of the statement's smooth and covariance against the run's truth"""
     obs, rec, P = prior_walk(run)
     poses, res, _ = SC.run(obs, rec, SC.seeds_of(obs, rec), None, NEES_SIGMAS)
-    cov = SV.smooth_cov(obs, rec, SC.K, None, SC.TAG, poses, res, *NEES_SIGMAS)
+    cov = SV.smooth_cov(obs, rec, SC.K, None, SC.TAG, poses, res, *NEES_SIGMAS)[0]
     assert res["status"] == 0 and (cov["status"] == 0).all()
     out = np.zeros(len(P))
     for f, (R, t) in enumerate(P):

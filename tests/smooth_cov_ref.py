@@ -15,6 +15,9 @@ which is the selected inverse of a block-tridiagonal matrix (from A^-1 = L^-T L^
 a time).  The operations run in the kernel's order: T = Sigma_{f+1} M_f and X = I + M_f^T T summed over k = 0, 1, ...;
 L^T Z = X by columns, L^T Y^T = Z^T by rows; the lower triangle of Y, mirrored, is Sigma_f (the carry of the next step too).
 
+The blocks are those of the one smooth_ref.Problem, so frame times and a rig come with it: smooth_cov / problem_blocks are
+the single-camera front, smooth_rig_cov / rig_problem_blocks the rig's (T = world<-rig), over cov_records / blocks_at.
+
 The record is the project's asl_pose_cov of a world<-camera pose (pose_cov_ref.convention_map(R_f, t_f, True)):
 C_f = A_f Sigma_ff A_f^T, A_f = blockdiag(-R_f^T, -R_f^T); computed as R^T . R on every 3x3 block (the sign drops out), lower
 triangle mirrored, so it is symmetric to the bit.  sigma_px: the given one.  dof: 8 (taking-part slots of all frames) - 6 =
@@ -83,13 +86,22 @@ def to_record_convention(Sigma, R):
     return mirror_lower(Cv)
 
 
-def problem_blocks(obs, tag_map, K, dist, tag_size, poses, sigma_px, sigma_rot, sigma_trans, huber_px=0.0):
-    """(problem, camera<-world poses, D, C) relinearised at the poses of a smooth output (huber_px > 0: the weighted normal
-    equations, a down-weighted corner contributing wgt of its information)"""
-    pb = SR.Problem(np.asarray(obs), tag_map, K, dist, tag_size, sigma_px, sigma_rot, sigma_trans, huber_px=huber_px)
+def blocks_at(pb, poses):
+    """(problem, the poses solved for, D, C) of a smooth_ref.Problem relinearised at the poses of a smooth output (huber_px >
+    0: the weighted normal equations, a down-weighted corner contributing wgt of its information)"""
     P = [SR.pose_of_seed(p) for p in poses]
     D, C, _ = pb.blocks(pb.linearise(P))
     return pb, P, D, C
+
+
+def problem_blocks(obs, tag_map, K, dist, tag_size, poses, sigma_px, sigma_rot, sigma_trans, huber_px=0.0, times=None):
+    """blocks_at of one camera's problem"""
+    return blocks_at(SR.problem(obs, tag_map, K, dist, tag_size, sigma_px, sigma_rot, sigma_trans, times=times, huber_px=huber_px), poses)
+
+
+def rig_problem_blocks(obs, tag_map, rig, tag_size, poses, sigma_px, sigma_rot, sigma_trans, times=None, huber_px=0.0):
+    """blocks_at of a rig's problem"""
+    return blocks_at(SR.rig_problem(obs, tag_map, rig, tag_size, sigma_px, sigma_rot, sigma_trans, times=times, huber_px=huber_px), poses)
 
 
 def records(n, cov, sigma_px, dof, status):
@@ -101,18 +113,30 @@ def records(n, cov, sigma_px, dof, status):
     return out
 
 
-def smooth_cov(obs, tag_map, K, dist, tag_size, poses, result, sigma_px, sigma_rot, sigma_trans, huber_px=0.0):
-    """the covariance records of the poses and result record of any smooth output (the statement's or the device's)
-    -> (n_frames,) POSE_COV_DTYPE"""
+def cov_records(pb, poses, result, sigma_px):
+    """the covariance records of the poses and result record of any smooth output (the statement's or the device's) of the
+    smooth_ref.Problem pb -> ((n_frames,) POSE_COV_DTYPE, the assembled matrix A or None)"""
     n = len(poses)
     if int(result["status"]) != SR.OK:
-        return records(n, 0.0, sigma_px, 0, PC.STATUS_NO_POSE)
-    pb, P, D, C = problem_blocks(obs, tag_map, K, dist, tag_size, poses, sigma_px, sigma_rot, sigma_trans, huber_px)
+        return records(n, 0.0, sigma_px, 0, PC.STATUS_NO_POSE), None
+    _, P, D, C = blocks_at(pb, poses)
     dof = 8 * int(pb.n_tags.sum()) - 6
     Sig = marginals(D, C) if np.all(np.isfinite(D)) and np.all(np.isfinite(C)) else None
     if Sig is None:
-        return records(n, 0.0, sigma_px, dof, PC.STATUS_NOT_PD)
-    return records(n, np.stack([to_record_convention(Sig[f], P[f][0]) for f in range(n)]), sigma_px, dof, PC.STATUS_OK)
+        return records(n, 0.0, sigma_px, dof, PC.STATUS_NOT_PD), None
+    return records(n, np.stack([to_record_convention(Sig[f], P[f][0]) for f in range(n)]), sigma_px, dof, PC.STATUS_OK), SR.dense(D, C)
+
+
+def smooth_cov(obs, tag_map, K, dist, tag_size, poses, result, sigma_px, sigma_rot, sigma_trans, huber_px=0.0, times=None):
+    """cov_records of one camera's output, T = world<-camera"""
+    return cov_records(SR.problem(obs, tag_map, K, dist, tag_size, sigma_px, sigma_rot, sigma_trans, times=times, huber_px=huber_px),
+                       poses, result, sigma_px)
+
+
+def smooth_rig_cov(obs, tag_map, rig, tag_size, poses, result, sigma_px, sigma_rot, sigma_trans, times=None, huber_px=0.0):
+    """cov_records of a rig's output, T = world<-rig"""
+    return cov_records(SR.rig_problem(obs, tag_map, rig, tag_size, sigma_px, sigma_rot, sigma_trans, times=times, huber_px=huber_px),
+                       poses, result, sigma_px)
 
 
 def dense_marginals(obs, tag_map, K, dist, tag_size, poses, sigma_px, sigma_rot, sigma_trans, huber_px=0.0):

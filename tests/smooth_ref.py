@@ -1,16 +1,37 @@
-"""NumPy statement of the sequence localisation (asl_smooth_frames_device / asl_smooth_batch, aprilslam_amd/csrc/k_smooth.inc):
-one camera<-world pose (R_f, t_f) for EVERY frame of one camera's consecutive frames against a fixed tag map, minimising
+"""NumPy statement of the sequence localisation, the one every asl_smooth* entry point is compared with (k_smooth_cand and
+k_smooth_lin over LocOneCam, k_smooth_rig_cand and k_smooth_rig_lin over LocRig, aprilslam_amd/csrc/k_smooth.inc): one pose
+(R_f, t_f) for EVERY frame of a sequence of consecutive frames against a fixed tag map, minimising
 
     sum_f  |r_f|^2 / sigma_px^2   +   sum_f  |m_f|^2
 
+The one computation (Problem, candidates, chain_costs, solve, solve_sequences) runs over a slot model of localize_ref.py --
+localize_ref.OneCamera or rig_ref.RigModel -- and frames whose rows are the model's global slots.  smooth / smooth_sequences
+(one camera: the pose is camera<-world, obs (n_frames, max_tags)) and smooth_rig / smooth_rig_sequences (the pose is rig<-world,
+obs (n_cams, n_frames, max_tags) camera-major, a frame's slots g = c * max_tags + s in global-slot order, T = world<-rig) are
+its two fronts: argument order and frame_major only.  A rig of one camera at E = I gives the single-camera bytes: Re = I
+and te = 0 multiply and add exactly.
+
 r_f: the localisation's own pixel residuals of frame f (localize_ref: every taking-part slot, flags & 1, 0 <= id < n_ids,
-     map[id].valid, corners +-h through the camera model; a corner at z <= 1e-9 costs 1e12 and adds nothing to H and g; no gate)
+     map[id].valid, corners +-h through the camera model; a corner at z <= 1e-9 costs 1e12 and adds nothing to H and g; no gate).
+     Through the model: a world corner X of camera c (model K_c, dist_c, mounting E_c = camera_c<-rig = (Re, te); one camera:
+     E = I) has P_r = R X + t, P_c = Re P_r + te, r = project_c(P_c) - (iu, iv), J = J_proj_c(P_c) Re [-[P_r]x | I].
 m_f: the random-walk motion residual between frames f and f + 1: R_D = R_{f+1} R_f^T, t_D = t_{f+1} - R_D t_f,
-     m_f = (Log(R_D) / sigma_rot, t_D / sigma_trans).  Log through atan2(|a|, c), a = vee(R_D - R_D^T) / 2, c = (tr R_D - 1) / 2:
+     m_f = (Log(R_D) w_rot, t_D w_trans).  Log through atan2(|a|, c), a = vee(R_D - R_D^T) / 2, c = (tr R_D - 1) / 2:
      exact to rounding at small angles, meant for relative rotations well below pi.
 
+Frame times (asl_smooth_timed_sequences_*, SmoothBufs.times): frame f is at time times[f] (float64, any unit; None: f), and
+sigma_rot and sigma_trans are the random walk's sigmas per unit of that time.  With dt_f = times[f + 1] - times[f],
+
+    w_rot = (1 / sigma_rot) (1 / sqrt(dt_f)),    w_trans = (1 / sigma_trans) (1 / sqrt(dt_f))        (Problem.pair_weights)
+
+in that operation order, so that dt_f == 1 gives 1 / sigma to the bit.  |m_f|^2 is the unit-step cost divided by dt_f: what
+is left of dt_f unit steps of the walk when the frames between, which have no data, are marginalised out (the variances of
+a random walk add).  Bad times: a time that is not finite, or a dt_f <= 0 (a sequence of one frame needs only a finite
+time).  Nothing is solved: the result is that of status 1 (no posed frame) with status 4 (BAD_TIMES), the frames' records
+those of status 1.
+
 Left update of the localisation, R <- Rod(w) R, t <- Rod(w) t + v, delta = (w, v).  To first order in the relative rotation
-(J_l^-1 ~ I), with B = [[I, 0], [-[t_D]x, I]], Ad = [[R_D, 0], [[t_D]x R_D, R_D]], W = diag(1/sigma_rot x3, 1/sigma_trans x3):
+(J_l^-1 ~ I), with B = [[I, 0], [-[t_D]x, I]], Ad = [[R_D, 0], [[t_D]x R_D, R_D]], W = diag(w_rot x3, w_trans x3) of the pair:
 d m_f / d delta_{f+1} = W B = Jn and d m_f / d delta_f = -W B Ad = Jp.
 
 Normal matrix, block tridiagonal in 6x6 blocks, assembled in this order (w = 1 / sigma_px^2):
@@ -22,10 +43,12 @@ failed trial, x0.1 after an accepted one, at most max_iters trials, an accepted 
 cost before it ends the solve.
 
 Seed chain, before the LM: seed[f] is the frame's asl_cam_pose of the per-frame localisation (status 0: posed).  Candidate A
-is the seed's camera<-world; B, only for a frame with exactly one taking-part slot, the mirrored planar minimum through that
-slot's map tag (localize_ref.mirrored of camera<-tag = A map[id], taken back through inv(map[id])), else B = A.  A two-state
-dynamic programme over the posed frames in frame order minimises the candidates' data costs (/ sigma_px^2) plus |m|^2 between
-consecutive posed frames, divided by the gap in frame steps; ties go to A, the backtracking starts from the lower-cost state
+is the seed's pose (camera<-world; rig<-world of rig_ref.localize); B, only for a frame with exactly one taking-part global
+slot, the mirrored planar minimum through that slot's map tag and its camera c: camera_c<-tag = (E_c A) map[id], mirrored
+(localize_ref.mirrored), taken back through inv(map[id]) to camera_c<-world and through inv(E_c) (the model's pose()) to the
+pose solved for; else B = A.  A two-state dynamic programme over the posed frames in frame order minimises the candidates' data
+costs (/ sigma_px^2) plus the motion cost at the call's sigmas between a posed frame f and its posed predecessor p, divided by
+times[f] - times[p] (no times: the gap in frame steps); ties go to A, the backtracking starts from the lower-cost state
 (tie: A).  A frame without a seed pose takes the chosen pose of the nearest earlier posed frame, the leading ones the first
 posed frame's.  Without any posed frame nothing is solved.
 
@@ -44,23 +67,29 @@ sqrt(sum rho / corners).  A slot is "soft" at a state if at least one of its fou
 belongs to the linearisation a trial commits, as the frame's pixel cost does.  huber_px = 0 is the plain problem, through
 localize_ref.linearise / corner_costs, with no soft slot.  Corner sums run in slot order, as the device's lanes hold them.
 
-Output per frame (asl_cam_pose): T world<-camera, rms_px / rms_seed_px the frame's own corner RMS at the end / after the
-chain, n_tags its taking-part slots, n_rejected its soft slots at the returned poses (0 for the plain problem), seed_slot the seed's (+256 if the chain chose B; -1 for a filled frame),
+Output per frame (asl_cam_pose): T world<-camera (world<-rig), rms_px / rms_seed_px the frame's own corner RMS at the end / after the
+chain, n_tags its taking-part global slots, n_rejected its soft slots at the returned poses (0 for the plain problem), seed_slot the seed's (+256 if the chain chose B; -1 for a filled frame),
 status 0 solved with data, 6 solved and carried by the motion prior alone, 4 in a solve that failed, 1 nothing to solve
 (T the identity).  One asl_smooth_result: total cost after the chain and at the end, the corner RMS of both over all
 frames, frames with data, frames filled, frames where B was chosen, trials run, n_soft the sum of n_rejected, status 0 ok / 1 no posed frame / 2 never
-positive definite / 3 non-finite (the cost after the chain).  Test infrastructure, as localize_ref.py is.
+positive definite / 3 non-finite (the cost after the chain) / 4 bad times.
+
+pose_at: the pose at a time between two frames along the prior's own geodesic, a = (t - times[f]) / dt_f:
+R = Exp(a Log R_D) R_f, t = Exp(a Log R_D) t_f + a t_D -- to first order in the step rotation the walk's conditional mean
+between the two poses.  No extrapolation.  The covariance of the returned poses is smooth_cov_ref.py's, on this Problem's
+blocks.  Test infrastructure, as localize_ref.py is.
 """
 import numpy as np
 
 import localize_ref as LR
+import rig_ref as RR
 from aprilslam_amd._lib import CAM_POSE_DTYPE, SMOOTH_RESULT_DTYPE
 
 LAMBDA0 = 1e-3
 REL_STOP = 1e-12
 FLIPPED = 256
 FRAME_DATA, FRAME_NOTHING, FRAME_FAILED, FRAME_PRIOR = 0, 1, 4, 6
-OK, NO_POSED_FRAME, NOT_POSITIVE_DEFINITE, NON_FINITE = 0, 1, 2, 3
+OK, NO_POSED_FRAME, NOT_POSITIVE_DEFINITE, NON_FINITE, BAD_TIMES = 0, 1, 2, 3, 4
 
 
 def skew(t):
@@ -87,14 +116,14 @@ def motion_residual(Pa, Pb, sigma_rot, sigma_trans):
     return np.concatenate([log_so3(RD) * (1.0 / sigma_rot), tD * (1.0 / sigma_trans)])
 
 
-def motion_jacobians(RD, tD, sigma_rot, sigma_trans):
-    """(Jn = d m / d delta_{f+1}, Jp = d m / d delta_f)"""
+def motion_jacobians(RD, tD, w_rot, w_trans):
+    """(Jn = d m / d delta_{f+1}, Jp = d m / d delta_f) of m = (Log(R_D) w_rot, t_D w_trans)"""
     B, Ad = np.eye(6), np.zeros((6, 6))
     B[3:, :3] = -skew(tD)
     Ad[:3, :3] = RD
     Ad[3:, :3] = skew(tD) @ RD
     Ad[3:, 3:] = RD
-    w = np.array([1.0 / sigma_rot] * 3 + [1.0 / sigma_trans] * 3)
+    w = np.array([w_rot] * 3 + [w_trans] * 3)
     return w[:, None] * B, -(w[:, None] * (B @ Ad))
 
 
@@ -192,20 +221,38 @@ def dense(D, C):
     return A
 
 
-def corner_terms(cam, R, t, Xw, uv, k, jac=False):
-    """per corner of one frame at (R, t): (rho, wgt, over, ok[, J (m, 2, 6) and r (m, 2) of the ok corners])"""
-    P = Xw @ R.T + t
-    ok = P[:, 2] > LR.Z_MIN
-    rho, wgt, over = np.full(len(P), LR.BEHIND_COST), np.zeros(len(P)), np.zeros(len(P), dtype=bool)
-    J = r = None
-    if ok.any():
-        p = P[ok]
+def cameras(model):
+    """[(camera tuple, Re, te)] of a slot model: the rig's table; one camera stands at E = I"""
+    return getattr(model, "table", None) or [(model.cam, np.eye(3), np.zeros(3))]
+
+
+def corner_terms(model, R, t, Xw, uv, ci, k, jac=False):
+    """per corner of one frame at (R, t), ci its camera: (rho, wgt, over, ok[, J (m, 2, 6) and r (m, 2) of the ok corners, in
+    corner order])"""
+    Pr = Xw @ R.T + t
+    n = len(Pr)
+    ok = np.zeros(n, dtype=bool)
+    J, r = np.zeros((n, 2, 6)), np.zeros((n, 2))
+    for c, (cam, Re, te) in enumerate(cameras(model)):
+        m = ci == c
+        if not m.any():
+            continue
+        P = Pr[m] @ Re.T + te
+        okc = P[:, 2] > LR.Z_MIN
+        if not okc.any():
+            continue
+        idx = np.flatnonzero(m)[okc]
         if jac:
-            q, Jp = LR.project(cam, p, jac=True)
-            J = np.concatenate([Jp @ LR.neg_skew(p), Jp], axis=2)
+            q, Jp = LR.project(cam, P[okc], jac=True)
+            Jr = Jp @ Re
+            J[idx] = np.concatenate([Jr @ LR.neg_skew(Pr[idx]), Jr], axis=2)
         else:
-            q = LR.project(cam, p)
-        r = q - uv[ok]
+            q = LR.project(cam, P[okc])
+        r[idx] = q - uv[idx]
+        ok[idx] = True
+    rho, wgt, over = np.full(n, LR.BEHIND_COST), np.zeros(n), np.zeros(n, dtype=bool)
+    J, r = J[ok], r[ok]
+    if ok.any():
         e = r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1]
         s = np.sqrt(e)
         o = s > k
@@ -216,36 +263,42 @@ def corner_terms(cam, R, t, Xw, uv, k, jac=False):
     return (rho, wgt, over, ok, J, r) if jac else (rho, wgt, over, ok)
 
 
-class Problem:
-    """the frames' corners (taking-part slots; reverse: accumulated in reversed slot order, a rounding perturbation), the weights
-    and the Huber threshold k = huber_px (0: the plain problem)"""
+def bad_times(times):
+    """the status-4 rule of one sequence"""
+    t = np.asarray(times, dtype=np.float64)
+    return bool((~np.isfinite(t)).any() or (len(t) > 1 and not (np.diff(t) > 0).all()))
 
-    def __init__(self, obs, tag_map, K, dist, tag_size, sigma_px, sigma_rot, sigma_trans, reverse=False, huber_px=0.0):
-        self.cam = LR.camera(K, dist)
-        self.model = LR.OneCamera(self.cam)
-        self.obs, self.tag_map, self.tag_size = obs, tag_map, tag_size
+
+class Problem:
+    """the frames' corners over a slot model (frames (n_frames, max_tags) or (n_frames, n_cams, max_tags): a frame's rows are
+    its global slots; taking-part slots; reverse: accumulated in reversed slot order, a rounding perturbation), the weights,
+    the frame times (None: the frame indices) and the Huber threshold k = huber_px (0: the plain problem)"""
+
+    def __init__(self, model, frames, tag_map, tag_size, sigma_px, sigma_rot, sigma_trans, times=None, reverse=False, huber_px=0.0):
+        self.model, self.obs, self.tag_map, self.tag_size = model, frames, tag_map, tag_size
         self.w = 1.0 / (sigma_px * sigma_px)
         self.sr, self.st, self.k = float(sigma_rot), float(sigma_trans), float(huber_px)
-        self.n = len(obs)
+        self.n = len(frames)
         self.part, self.pts = [], []
-        for rows in obs:
+        for rows in frames:
             part = LR.gather(rows, tag_map)[1]
             self.part.append(part)
             order = part[::-1] if reverse else part
-            self.pts.append(LR.frame_points(self.model, rows, tag_map, tag_size, order)[:2] if part else None)
+            self.pts.append(LR.frame_points(model, rows, tag_map, tag_size, order) if part else None)
         self.n_tags = np.array([len(p) for p in self.part], dtype=np.int64)
+        self.times = np.arange(self.n, dtype=np.float64) if times is None else np.asarray(times, dtype=np.float64)
 
     def data_cost(self, f, P):
         """the frame's pixel cost at P: squared, or sum rho (not yet weighted by sigma_px)"""
         if self.pts[f] is None:
             return 0.0
         if self.k == 0.0:
-            return float(LR.corner_costs(self.cam, P[0], P[1], *self.pts[f]).sum())
-        return float(corner_terms(self.cam, P[0], P[1], *self.pts[f], self.k)[0].sum())
+            return float(self.model.costs(P[0], P[1], *self.pts[f]).sum())
+        return float(corner_terms(self.model, P[0], P[1], *self.pts[f], self.k)[0].sum())
 
     def frame(self, f, P):
         """the weighted path: (cost, H, g, soft slots, wgt per corner, |r| per corner (nan behind the camera)) of frame f at P = (R, t)"""
-        rho, wgt, over, ok, J, r = corner_terms(self.cam, P[0], P[1], *self.pts[f], self.k, jac=True)
+        rho, wgt, over, ok, J, r = corner_terms(self.model, P[0], P[1], *self.pts[f], self.k, jac=True)
         H, g = np.zeros((6, 6)), np.zeros(6)
         s = np.full(len(rho), np.nan)
         if ok.any():
@@ -256,8 +309,14 @@ class Problem:
         return float(rho.sum()), H, g, int(over.reshape(-1, 4).any(axis=1).sum()), wgt, s
 
     def motion_cost(self, Pa, Pb):
+        """|m|^2 at the call's sigmas, one unit of time apart (the chain divides it by the time between its two frames)"""
         m = motion_residual(Pa, Pb, self.sr, self.st)
         return float(m @ m)
+
+    def pair_weights(self, f):
+        """(w_rot, w_trans) of the pair (f, f + 1)"""
+        isd = 1.0 / np.sqrt(self.times[f + 1] - self.times[f])
+        return (1.0 / self.sr) * isd, (1.0 / self.st) * isd
 
     def linearise(self, P):
         """everything a trial needs at the poses P: per frame the pixel cost c, H, g and the soft slots; per pair the motion blocks"""
@@ -267,13 +326,14 @@ class Problem:
                "soft": np.zeros(n, dtype=np.int64)}
         for f in range(n):
             if self.pts[f] is not None and self.k == 0.0:
-                lin["c"][f], lin["H"][f], lin["g"][f] = LR.linearise(self.cam, P[f][0], P[f][1], *self.pts[f])
+                lin["c"][f], lin["H"][f], lin["g"][f] = self.model.linearise(P[f][0], P[f][1], *self.pts[f])
             elif self.pts[f] is not None:
                 lin["c"][f], lin["H"][f], lin["g"][f], lin["soft"][f] = self.frame(f, P[f])[:4]
             if f + 1 < n:
+                wr, wt = self.pair_weights(f)
                 RD, tD = relative(P[f], P[f + 1])
-                m = np.concatenate([log_so3(RD) * (1.0 / self.sr), tD * (1.0 / self.st)])
-                Jn, Jp = motion_jacobians(RD, tD, self.sr, self.st)
+                m = np.concatenate([log_so3(RD) * wr, tD * wt])
+                Jn, Jp = motion_jacobians(RD, tD, wr, wt)
                 lin["mc"][f] = m @ m
                 lin["QN"][f], lin["QP"][f], lin["C"][f] = Jp.T @ Jp, Jn.T @ Jn, Jn.T @ Jp
                 lin["gN"][f], lin["gP"][f] = Jp.T @ m, Jn.T @ m
@@ -292,14 +352,14 @@ class Problem:
 
 
 def pose_of_seed(rec):
-    """camera<-world of an asl_cam_pose's world<-camera T"""
+    """the pose solved for (camera<-world, rig<-world) of an asl_cam_pose's T, its inverse"""
     T = np.asarray(rec["T"], dtype=np.float64)
     R = T[:3, :3].T
     return R, -(R @ T[:3, 3])
 
 
 def candidates(pb, seed):
-    """per frame None (no seed pose) or (A, B, has_b)"""
+    """per frame None (no seed pose) or (A, B, has_b); B through the mounting of the one taking-part slot's camera"""
     out = []
     for f in range(pb.n):
         if seed["status"][f] != 0:
@@ -309,16 +369,22 @@ def candidates(pb, seed):
         if len(pb.part[f]) != 1:
             out.append((A, A, False))
             continue
-        M = pb.tag_map["T"][pb.obs[f]["id"][pb.part[f][0]]].reshape(3, 4)
-        Rm, tm = LR.mirrored(A[0] @ M[:, :3], A[0] @ M[:, 3] + A[1])     # camera<-tag = A map[id], mirrored
-        RB = Rm @ M[:, :3].T
-        out.append((A, (RB, tm - RB @ M[:, 3]), True))
+        g = pb.part[f][0]
+        c = pb.model.slot_camera(g, pb.obs.shape[-1])
+        _, Re, te = cameras(pb.model)[c]
+        M = pb.tag_map["T"][pb.obs[f].reshape(-1)["id"][g]].reshape(3, 4)
+        # camera_c<-world = E_c A.  Written as (A^T Re^T)^T so that Rc has the memory layout of A's R (a transposed view of
+        # the record's T): at E = I the products below then run on the operands the seed itself gives them
+        Rc, tc = (A[0].T @ Re.T).T, Re @ A[1] + te
+        Rm, tm = LR.mirrored(Rc @ M[:, :3], Rc @ M[:, 3] + tc)             # camera_c<-tag, mirrored
+        Rk = Rm @ M[:, :3].T
+        out.append((A, pb.model.pose(Rk, tm - Rk @ M[:, 3], c), True))
     return out
 
 
 def chain_costs(pb, cand):
     """(posed frames, data costs (n_posed, 2) weighted, transition costs (n_posed, 2, 2) [from, to] of each posed frame from its
-    predecessor, divided by the gap; the first one's are 0)"""
+    predecessor, divided by the time between the two; the first one's are 0)"""
     posed = [f for f in range(pb.n) if cand[f] is not None]
     d = np.zeros((len(posed), 2))
     tr = np.zeros((len(posed), 2, 2))
@@ -328,7 +394,7 @@ def chain_costs(pb, cand):
             for a in (0, 1):
                 if k:
                     p = posed[k - 1]
-                    tr[k, a, b] = pb.motion_cost(cand[p][a], cand[f][b]) / float(f - p)
+                    tr[k, a, b] = pb.motion_cost(cand[p][a], cand[f][b]) / (pb.times[f] - pb.times[p])
     return posed, d, tr
 
 
@@ -358,22 +424,26 @@ def chain_total(d, tr, choice):
     return float(sum(d[k, choice[k]] + (tr[k, choice[k - 1], choice[k]] if k else 0.0) for k in range(len(d))))
 
 
-def smooth(obs, tag_map, K, dist, tag_size, seed, sigma_px, sigma_rot, sigma_trans, max_iters, reverse=False, huber_px=0.0):
-    """obs (n_frames, max_tags) asl_obs records, tag_map (n_ids,) asl_map_tag records, seed (n_frames,) asl_cam_pose ->
+def solve(model, frames, tag_map, tag_size, seed, times, sigma_px, sigma_rot, sigma_trans, max_iters, reverse=False, huber_px=0.0):
+    """the solve of one sequence: frames as Problem takes them, seed (n_frames,) asl_cam_pose, times (n_frames,) or None ->
     ((n_frames,) CAM_POSE_DTYPE, SMOOTH_RESULT_DTYPE record, trace); trace: "posed", "d", "tr", "choice" of the chain, "lins":
-    (poses, linearisation) of the chain's poses and of every trial computed (accepted or not), "P": the camera<-world poses
-    returned, "problem": the Problem"""
-    obs = np.asarray(obs)
-    pb = Problem(obs, tag_map, K, dist, tag_size, sigma_px, sigma_rot, sigma_trans, reverse, huber_px)
-    n = pb.n
+    (poses, linearisation) of the chain's poses and of every trial computed (accepted or not), "P": the poses returned,
+    "problem": the Problem (None with bad times)"""
+    n = len(frames)
     out = np.zeros(n, dtype=CAM_POSE_DTYPE)
     out["T"] = np.eye(4)
     out["seed_slot"] = -1
     out["status"] = FRAME_NOTHING
     res = np.zeros((), dtype=SMOOTH_RESULT_DTYPE)
+    trace = {"posed": [], "d": np.zeros((0, 2)), "tr": np.zeros((0, 2, 2)), "choice": np.zeros(0, dtype=np.int64), "lins": [], "P": None,
+             "problem": None}
+    if times is not None and bad_times(times):
+        res["status"] = BAD_TIMES
+        return out, res, trace
+    pb = Problem(model, frames, tag_map, tag_size, sigma_px, sigma_rot, sigma_trans, times, reverse, huber_px)
     cand = candidates(pb, seed)
     posed, d, tr = chain_costs(pb, cand)
-    trace = {"posed": posed, "d": d, "tr": tr, "choice": np.zeros(0, dtype=np.int64), "lins": [], "P": None, "problem": pb}
+    trace.update(posed=posed, d=d, tr=tr, problem=pb)
     if not posed:
         res["status"] = NO_POSED_FRAME
         return out, res, trace
@@ -438,3 +508,85 @@ def smooth(obs, tag_map, K, dist, tag_size, seed, sigma_px, sigma_rot, sigma_tra
     res["n_soft"] = int(lin["soft"].sum())
     trace["P"] = P
     return out, res, trace
+
+
+def solve_sequences(model, frames, seq_start, tag_map, tag_size, seed, times, sigma_px, sigma_rot, sigma_trans, max_iters, huber_px=0.0):
+    """a call of several sequences: each alone on its own frames and times[a0:a1] -> ((n_frames,) poses, (n_seq,) results)"""
+    out, res = np.zeros(len(frames), dtype=CAM_POSE_DTYPE), np.zeros(len(seq_start) - 1, dtype=SMOOTH_RESULT_DTYPE)
+    for k, (a, b) in enumerate(zip(seq_start[:-1], seq_start[1:])):
+        out[a:b], res[k], _ = solve(model, frames[a:b], tag_map, tag_size, seed[a:b], None if times is None else times[a:b], sigma_px,
+                                    sigma_rot, sigma_trans, max_iters, huber_px=huber_px)
+    return out, res
+
+
+# ---- the two fronts: one camera, obs (n_frames, max_tags); a rig, obs (n_cams, n_frames, max_tags) camera-major
+
+def one_camera(obs, K, dist):
+    """(the slot model, the frames) of one camera's block"""
+    return LR.OneCamera(LR.camera(K, dist)), np.asarray(obs)
+
+
+def frame_major(obs):
+    """(n_cams, n_frames, max_tags) -> (n_frames, n_cams, max_tags): a frame's rows are its global slots, flattened"""
+    obs = np.asarray(obs)
+    assert obs.ndim == 3
+    return np.ascontiguousarray(np.swapaxes(obs, 0, 1))
+
+
+def rig_cameras(obs, rig):
+    """(the slot model, the frames) of a rig's block; rig: RIG_CAMERA_DTYPE records or a rig.Rig"""
+    model, frames = RR.RigModel(rig), frame_major(obs)
+    assert frames.shape[1] == len(model.table)
+    return model, frames
+
+
+def problem(obs, tag_map, K, dist, tag_size, sigma_px, sigma_rot, sigma_trans, **kw):
+    """the Problem of one camera's block (kw: times, reverse, huber_px)"""
+    return Problem(*one_camera(obs, K, dist), tag_map, tag_size, sigma_px, sigma_rot, sigma_trans, **kw)
+
+
+def rig_problem(obs, tag_map, rig, tag_size, sigma_px, sigma_rot, sigma_trans, **kw):
+    """the Problem of a rig's block (kw: times, reverse, huber_px)"""
+    return Problem(*rig_cameras(obs, rig), tag_map, tag_size, sigma_px, sigma_rot, sigma_trans, **kw)
+
+
+def smooth(obs, tag_map, K, dist, tag_size, seed, sigma_px, sigma_rot, sigma_trans, max_iters, reverse=False, huber_px=0.0, times=None):
+    """obs (n_frames, max_tags) asl_obs records, tag_map (n_ids,) asl_map_tag records, seed (n_frames,) asl_cam_pose of
+    localize_ref.localize -> solve's three, T = world<-camera"""
+    return solve(*one_camera(obs, K, dist), tag_map, tag_size, seed, times, sigma_px, sigma_rot, sigma_trans, max_iters, reverse, huber_px)
+
+
+def smooth_rig(obs, tag_map, rig, tag_size, seed, sigma_px, sigma_rot, sigma_trans, max_iters, times=None, reverse=False, huber_px=0.0):
+    """obs (n_cams, n_frames, max_tags) asl_obs records, seed (n_frames,) asl_cam_pose of rig_ref.localize -> solve's three,
+    T = world<-rig"""
+    return solve(*rig_cameras(obs, rig), tag_map, tag_size, seed, times, sigma_px, sigma_rot, sigma_trans, max_iters, reverse, huber_px)
+
+
+def smooth_sequences(obs, seq_start, tag_map, K, dist, tag_size, seed, sigma_px, sigma_rot, sigma_trans, max_iters, huber_px=0.0, times=None):
+    """smooth of every sequence obs[seq_start[k]:seq_start[k + 1]] alone -> solve_sequences' two"""
+    return solve_sequences(*one_camera(obs, K, dist), seq_start, tag_map, tag_size, seed, times, sigma_px, sigma_rot, sigma_trans, max_iters, huber_px)
+
+
+def smooth_rig_sequences(obs, seq_start, tag_map, rig, tag_size, seed, sigma_px, sigma_rot, sigma_trans, max_iters, times=None, huber_px=0.0):
+    """smooth_rig of every sequence obs[:, seq_start[k]:seq_start[k + 1]] alone -> solve_sequences' two"""
+    return solve_sequences(*rig_cameras(obs, rig), seq_start, tag_map, tag_size, seed, times, sigma_px, sigma_rot, sigma_trans, max_iters, huber_px)
+
+
+def pose_at(T, times, t):
+    """(4, 4) world<-camera at time t of the world<-camera poses T (n, 4, 4) at times (None: the frame indices)"""
+    T = np.asarray(T, dtype=np.float64).reshape(-1, 4, 4)
+    times = np.arange(len(T), dtype=np.float64) if times is None else np.asarray(times, dtype=np.float64)
+    if not (times[0] <= t <= times[-1]):
+        raise ValueError("no extrapolation")
+    f = int(np.searchsorted(times, t, side="right")) - 1
+    if f == len(T) - 1 or t == times[f]:
+        return T[f].copy()
+    Pa, Pb = pose_of_seed({"T": T[f]}), pose_of_seed({"T": T[f + 1]})
+    a = (t - times[f]) / (times[f + 1] - times[f])
+    RD, tD = relative(Pa, Pb)
+    E = LR.rodrigues(a * log_so3(RD))
+    R, tv = E @ Pa[0], E @ Pa[1] + a * tD
+    out = np.eye(4)
+    out[:3, :3], out[:3, 3] = R.T, -(R.T @ tv)
+    return out
+

@@ -1,7 +1,7 @@
 """Inputs and recorded bounds of the rig sequence-localisation tests (tests/test_smooth_rig_ref.py on the CPU,
 tests/test_gpu_smooth_rig.py on the device), built with rig_cases.exact_block / mounting and the smooth_cases helpers, seeded
 by rig_ref.localize.  Every figure in recorded() and DEVICE_TOL was measured on the CPU with the NumPy statement
-(tests/smooth_rig_ref.py) -- never with the kernels; test_smooth_rig_ref.py measures them again and requires the recorded
+(tests/smooth_ref.py) -- never with the kernels; test_smooth_rig_ref.py measures them again and requires the recorded
 figures to still hold, so the GPU tests can use them without recomputing."""
 import functools
 
@@ -11,7 +11,7 @@ import localize_cases as LC
 import rig_cases as RC
 import rig_ref as RR
 import smooth_cases as SC
-import smooth_rig_ref as SRR
+import smooth_ref as SR
 from aprilslam_amd.localize import TagMap
 from aprilslam_amd.rig import Rig, RigCamera
 
@@ -92,7 +92,7 @@ def seeds_of(obs, rec, rig):
 def mirror_seed(obs, rec, rig, seed, frames, sigmas):
     """the seeds of `frames` replaced by candidate B of the chain: their mirrored planar minima through the mounting"""
     out = seed.copy()
-    cand = SRR.candidates(SRR.RigProblem(SRR.frame_major(obs), rec, rig, None, TAG, *sigmas, None), seed)
+    cand = SR.candidates(SR.rig_problem(obs, rec, rig, TAG, *sigmas), seed)
     for f in frames:
         assert cand[f][2]
         R, t = cand[f][1]
@@ -238,7 +238,7 @@ def case(name):
 
 def run(name, reverse=False, huber=0.0, max_iters=None):
     _, obs, rec, rig, seed, sig, iters, times = case(name)
-    return SRR.smooth(obs, rec, rig, TAG, seed, *sig, max_iters or iters, times=times, reverse=reverse, huber_px=huber)
+    return SR.smooth_rig(obs, rec, rig, TAG, seed, *sig, max_iters or iters, times=times, reverse=reverse, huber_px=huber)
 
 
 def reversal_error(name, huber):

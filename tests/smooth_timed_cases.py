@@ -1,7 +1,7 @@
 """Inputs and recorded bounds of the tests of the sequence localisation with frame times (tests/test_smooth_timed_ref.py on the
 CPU, tests/test_gpu_smooth_timed.py on the device): the cases of tests/smooth_cases.py and tests/smooth_seq_cases.py with a time
 for every frame.  Every figure in recorded() and DEVICE_TOL was measured on the CPU with the NumPy statement
-(tests/smooth_timed_ref.py) -- never with the kernels; test_smooth_timed_ref.py measures them again and requires the recorded
+(tests/smooth_ref.py with times) -- never with the kernels; test_smooth_timed_ref.py measures them again and requires the recorded
 figures to still hold, so the GPU tests can use them without recomputing."""
 import functools
 
@@ -9,8 +9,8 @@ import numpy as np
 
 import localize_cases as LC
 import smooth_cases as SC
+import smooth_ref as SR
 import smooth_seq_cases as SQ
-import smooth_timed_ref as TR
 
 # Bound of the device's T against the statement's, built as smooth_cases.DEVICE_TOL is: ten times the largest rel_err between
 # the statement and the statement with every frame's corner sums accumulated in reversed slot order over all_cases() of this
@@ -74,7 +74,7 @@ def case(name):
 
 
 def run(obs, rec, seed, dist, times, sigmas, reverse=False, max_iters=SC.MAX_ITERS, huber=0.0):
-    return TR.smooth(obs, rec, SC.K, dist, SC.TAG, seed, times, *sigmas, max_iters, reverse=reverse, huber_px=huber)
+    return SR.smooth(obs, rec, SC.K, dist, SC.TAG, seed, *sigmas, max_iters, reverse=reverse, huber_px=huber, times=times)
 
 
 @functools.lru_cache(maxsize=None)

@@ -33,7 +33,7 @@ def test_device_matches_the_statement_at_its_own_poses(gpu_detector, name):
     out, res, cov = device(gpu_detector, name)
     plain_out, plain_res = gpu_detector.smooth(obs, rec, SC.K, dist, SC.TAG, *sig, max_iters=iters, seed=seed)
     assert out.tobytes() == plain_out.tobytes() and res.tobytes() == plain_res.tobytes()
-    want = SV.smooth_cov(obs, rec, SC.K, dist, SC.TAG, out, res, *sig)
+    want = SV.smooth_cov(obs, rec, SC.K, dist, SC.TAG, out, res, *sig)[0]
     assert res["status"] == 0 and (want["status"] == 0).all()
     for k in ("status", "dof", "sigma_px"):
         assert np.array_equal(cov[k], want[k]), (name, k, cov[k], want[k])
@@ -51,7 +51,7 @@ def test_device_matches_the_statement_at_its_own_poses(gpu_detector, name):
 def test_status_rules(gpu_detector, name):
     obs, rec, seed, dist, sig, iters = VC.prior_only() if name == "prior_only" else VC.case(name)
     out, res, cov = device(gpu_detector, name)
-    want = SV.smooth_cov(obs, rec, SC.K, dist, SC.TAG, out, res, *sig)
+    want = SV.smooth_cov(obs, rec, SC.K, dist, SC.TAG, out, res, *sig)[0]
     status = 2 if name == "prior_only" else 1
     assert (want["status"] == status).all() and (res["status"] == 0) == (name == "prior_only")
     for k in ("status", "dof", "sigma_px"):

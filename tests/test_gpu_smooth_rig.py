@@ -1,5 +1,5 @@
 """The rig sequence localisation on the device (asl_smooth_rig_sequences_device / _batch: k_smooth_rig_cand and k_smooth_rig_lin
-over LocRig in k_smooth.inc) against the NumPy statement (tests/smooth_rig_ref.py) on the cases and recorded figures of
+over LocRig in k_smooth.inc) against the NumPy statement (tests/smooth_ref.py) on the cases and recorded figures of
 tests/smooth_rig_cases.py; one camera at E = I against asl_smooth_timed_sequences_device; the identities that need no
 statement; the covariance; the refusals; the Python surface."""
 import ctypes as C
@@ -9,9 +9,9 @@ import pytest
 
 import localize_cases as LC
 import smooth_cases as SC
+import smooth_cov_ref as SV
 import smooth_ref as SR
 import smooth_rig_cases as GC
-import smooth_rig_ref as SRR
 import solver_checks as CK
 from aprilslam_amd import _lib
 from aprilslam_amd._lib import CAM_POSE_DTYPE, POSE_COV_DTYPE, SMOOTH_RESULT_DTYPE
@@ -122,7 +122,7 @@ def test_flip_goes_through_the_mounting(gpu_detector):
     """the chain's first decision on the device: B of a frame whose one slot is in camera 1, at COMPARE_ITERS against the statement"""
     _, obs, rec, rig, seed, sig, _, _ = GC.case("flip")
     rc, got, gres, _ = host(gpu_detector, obs, rec, rig, seed, sig, 0.0, GC.COMPARE_ITERS)
-    want, wres, _ = SRR.smooth(obs, rec, rig, GC.TAG, seed, *sig, GC.COMPARE_ITERS)
+    want, wres, _ = SR.smooth_rig(obs, rec, rig, GC.TAG, seed, *sig, GC.COMPARE_ITERS)
     assert rc == 0 and int(wres["n_flipped"]) == len(GC.FLIP_FRAMES)
     assert_same("flip at %d trials" % GC.COMPARE_ITERS, got, gres[0], want, wres)
 
@@ -184,7 +184,7 @@ def test_each_sequence_is_the_call_alone(gpu_detector):
             p1, r1, c1 = one.run(None, GC.SHAPE_SIGMAS, huber, GC.COMPARE_ITERS, fill=0xAB)
             ps, cs = CAM_POSE_DTYPE.itemsize, POSE_COV_DTYPE.itemsize
             assert p[a * ps:b * ps] == p1 and r[64 * k:64 * k + 64] == r1 and c[a * cs:b * cs] == c1, (huber, k)
-        want, wres = SRR.smooth_sequences(obs, start, rec, rig, GC.TAG, seed, *GC.SHAPE_SIGMAS, GC.COMPARE_ITERS, huber_px=huber)
+        want, wres = SR.smooth_rig_sequences(obs, start, rec, rig, GC.TAG, seed, *GC.SHAPE_SIGMAS, GC.COMPARE_ITERS, huber_px=huber)
         got, gres = np.frombuffer(p, dtype=CAM_POSE_DTYPE), np.frombuffer(r, dtype=SMOOTH_RESULT_DTYPE)
         for k, (a, b) in enumerate(zip(start[:-1], start[1:])):
             assert_same("three_sequences[%d] huber %g" % (k, huber), got[a:b], gres[k], want[a:b], wres[k])
@@ -220,7 +220,7 @@ def test_covariance_is_the_statements(gpu_detector, name, huber):
     """d_cov against smooth_cov_ref.marginals of the rig statement's blocks at the device's own poses (600 eps kappa)"""
     _, obs, rec, rig, seed, sig, iters, times = GC.case(name)
     out, res, cov = device_case(gpu_detector, name, huber)
-    want, A = SRR.smooth_cov(obs, rec, rig, GC.TAG, out, res, *sig, times=times, huber_px=huber)
+    want, A = SV.smooth_rig_cov(obs, rec, rig, GC.TAG, out, res, *sig, times=times, huber_px=huber)
     assert res["status"] == 0 and (want["status"] == 0).all()
     for key in ("status", "dof", "sigma_px"):
         assert np.array_equal(cov[key], want[key]), (name, key, cov[key], want[key])

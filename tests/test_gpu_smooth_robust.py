@@ -222,7 +222,7 @@ def test_covariance_is_the_weighted_matrix(gpu_detector, name):
     """d_cov against the robust statement's at the device's own poses, within test_gpu_smooth_cov.py's bar (600 eps kappa)"""
     obs, rec, seed, dist, sig, huber, iters = CASES[name]
     out, res, cov = device_case(gpu_detector, name)
-    want = SV.smooth_cov(obs, rec, SC.K, dist, SC.TAG, out, res, *sig, huber)
+    want = SV.smooth_cov(obs, rec, SC.K, dist, SC.TAG, out, res, *sig, huber)[0]
     assert res["status"] == 0 and (want["status"] == 0).all()
     for k in ("status", "dof", "sigma_px"):
         assert np.array_equal(cov[k], want[k]), (name, k, cov[k], want[k])

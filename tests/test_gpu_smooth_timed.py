@@ -1,5 +1,5 @@
 """The sequence localisation with frame times on the device (asl_smooth_timed_sequences_device / _batch: SmoothBufs.times in
-k_smooth.inc) against the NumPy statement (tests/smooth_timed_ref.py) on the cases and recorded figures of
+k_smooth.inc) against the NumPy statement (tests/smooth_ref.py) on the cases and recorded figures of
 tests/smooth_timed_cases.py, and without times or at unit spacing against the existing entry points, byte for byte."""
 import ctypes as C
 
@@ -8,9 +8,10 @@ import pytest
 
 import localize_cases as LC
 import smooth_cases as SC
+import smooth_cov_ref as SV
+import smooth_ref as SR
 import smooth_seq_cases as SQ
 import smooth_timed_cases as TC
-import smooth_timed_ref as TR
 import solver_checks as CK
 from aprilslam_amd import _lib, synth
 from aprilslam_amd._lib import CAM_POSE_DTYPE, POSE_COV_DTYPE, SMOOTH_RESULT_DTYPE
@@ -218,7 +219,7 @@ def test_bad_times_batch(gpu_detector):
     assert rc == 0 and results["status"].tolist() == TC.BAD_STATUS
     dv = OnDevice(gpu_detector, b.obs, b.rec, b.seed)
     assert dv.run(b.seq_start, b.dist, b.sigmas, 0.0, b.max_iters, times) == (poses.tobytes(), results.tobytes(), cov.tobytes())
-    want, wres = TR.smooth_sequences(b.obs, b.seq_start, b.rec, SC.K, b.dist, SC.TAG, b.seed, times, *b.sigmas, b.max_iters)
+    want, wres = SR.smooth_sequences(b.obs, b.seq_start, b.rec, SC.K, b.dist, SC.TAG, b.seed, *b.sigmas, b.max_iters, times=times)
     for k, (a0, a1) in enumerate(SQ.ranges(b)):
         rc1, p1, r1, c1 = host(gpu_detector, b.obs[a0:a1], [0, a1 - a0], b.rec, b.dist, b.sigmas, 0.0, b.max_iters, b.seed[a0:a1], times[a0:a1])
         assert rc1 == 0 and poses[a0:a1].tobytes() == p1.tobytes() and results[k].tobytes() == r1[0].tobytes(), k
@@ -267,7 +268,7 @@ def test_covariance_is_the_timed_matrix(gpu_detector, name):
     else:
         obs, rec, seed, dist, times, sig, iters = CASES[name]
         out, res, cov = device_case(gpu_detector, name)
-    want, A = TR.smooth_cov(obs, rec, SC.K, dist, SC.TAG, out, res, times, *sig)
+    want, A = SV.smooth_cov(obs, rec, SC.K, dist, SC.TAG, out, res, *sig, times=times)
     assert res["status"] == 0 and (want["status"] == 0).all()
     for key in ("status", "dof", "sigma_px"):
         assert np.array_equal(cov[key], want[key]), (name, key, cov[key], want[key])
@@ -381,7 +382,7 @@ def test_python_surface(gpu_detector):
     truth = LC.world_from_camera(*LC.trajectory(520)[2])
     mid = r.pose_at(2.0)
     print("pose_at(2.0): position error to the dropped frame's truth %.4g" % np.linalg.norm(mid[:3, 3] - truth[:3, 3]))
-    assert np.abs(mid - TR.pose_at(r.trajectory(), ft, 2.0)).max() <= 1e-14
+    assert np.abs(mid - SR.pose_at(r.trajectory(), ft, 2.0)).max() <= 1e-14
     with pytest.raises(ValueError):
         r.pose_at(4.5)
     badt = td.localize_sequence(dd, p, npf, tm, times=[0.0, 1.0, 1.0], **kw)

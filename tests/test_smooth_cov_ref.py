@@ -38,7 +38,7 @@ def test_one_frame_is_the_localisation_covariance(name):
     obs, rec, seed, dist, sig, iters = VC.case(name)
     poses, res = VC.statement(name)
     cov = VC.statement_cov(name)
-    pb = SR.Problem(obs, rec, SC.K, dist, SC.TAG, *sig)
+    pb = SR.problem(obs, rec, SC.K, dist, SC.TAG, *sig)
     R, t = SR.pose_of_seed(poses[0])
     Xw, uv, ci = LR.frame_points(pb.model, obs[0], rec, SC.TAG, pb.part[0])
     want, sigma, dof, status = LR.pose_cov(pb.model, R, t, Xw, uv, ci, sig[0])

@@ -42,7 +42,7 @@ def test_motion_jacobians_against_central_differences(angle, tol):
         Pa = random_pose(rng, 0.7, 2.0)
         dR, dt = random_pose(rng, angle, 0.4)
         Pb = (dR @ Pa[0], dR @ Pa[1] + dt)
-        Jn, Jp = SR.motion_jacobians(*SR.relative(Pa, Pb), sr, st)
+        Jn, Jp = SR.motion_jacobians(*SR.relative(Pa, Pb), 1.0 / sr, 1.0 / st)
         num_n, num_p = np.zeros((6, 6)), np.zeros((6, 6))
         for k in range(6):
             e = np.zeros(6)

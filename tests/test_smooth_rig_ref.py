@@ -1,5 +1,5 @@
-"""The NumPy statement of the rig sequence localisation (tests/smooth_rig_ref.py) and the ABI of asl_smooth_rig_sequences_*: the
-statement reduces to smooth_ref.smooth for one camera at E = I, the figures and DEVICE_TOL recorded in smooth_rig_cases.py
+"""The NumPy statement of the sequence localisation (tests/smooth_ref.py) over a rig and the ABI of asl_smooth_rig_sequences_*: the
+rig front reduces to the single-camera front for one camera at E = I, the figures and DEVICE_TOL recorded in smooth_rig_cases.py
 still hold, include/aprilslam.h declares the two entry points with the argument names of the issue, the library exports
 them, the ctypes argument lists agree, the Python surface has its keywords, and the host entry point refuses a NULL detector
 before it touches a device.  No GPU."""
@@ -12,7 +12,6 @@ import pytest
 import smooth_cases as SC
 import smooth_ref as SR
 import smooth_rig_cases as GC
-import smooth_rig_ref as SRR
 from aprilslam_amd import _lib
 from aprilslam_amd.rig import Rig, RigCamera
 from aprilslam_amd.smooth import SmoothResult
@@ -30,7 +29,7 @@ def test_one_camera_at_identity_is_the_single_camera_statement(shape, huber):
     obs, rec, seed, dist = SC.shape(*shape)
     solo = Rig([RigCamera(SC.K, dist, np.eye(4))])
     want = SR.smooth(obs, rec, SC.K, dist, SC.TAG, seed, *SC.SHAPE_SIGMAS, SC.COMPARE_ITERS, huber_px=huber)
-    got = SRR.smooth(obs[None], rec, solo, SC.TAG, seed, *SC.SHAPE_SIGMAS, SC.COMPARE_ITERS, huber_px=huber)
+    got = SR.smooth_rig(obs[None], rec, solo, SC.TAG, seed, *SC.SHAPE_SIGMAS, SC.COMPARE_ITERS, huber_px=huber)
     for name in want[0].dtype.names:
         assert np.array_equal(got[0][name], want[0][name]), name
     for name in want[1].dtype.names:

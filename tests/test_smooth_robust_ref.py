@@ -38,7 +38,7 @@ def test_plain_path_is_the_localisation_statement(name):
     for P, lin in trace["lins"]:
         assert not lin["soft"].any()
         for f in range(pb.n):
-            c, H, g = (0.0, np.zeros((6, 6)), np.zeros(6)) if pb.pts[f] is None else LR.linearise(pb.cam, P[f][0], P[f][1], *pb.pts[f])
+            c, H, g = (0.0, np.zeros((6, 6)), np.zeros(6)) if pb.pts[f] is None else LR.linearise(pb.model.cam, P[f][0], P[f][1], *pb.pts[f][:2])
             assert np.float64(c).tobytes() == lin["c"][f].tobytes() and H.tobytes() == lin["H"][f].tobytes() and g.tobytes() == lin["g"][f].tobytes()
 
 
@@ -61,7 +61,7 @@ def test_weighted_path_with_all_weights_one(name):
 
 
 def rho_sum(pb, f, P):
-    return float(SR.corner_terms(pb.cam, P[0], P[1], *pb.pts[f], pb.k)[0].sum())
+    return float(SR.corner_terms(pb.model, P[0], P[1], *pb.pts[f], pb.k)[0].sum())
 
 
 @pytest.mark.parametrize("name", ["shape3_4_0", "shape5_20_5", "shape1_1_0"])
@@ -78,10 +78,10 @@ def test_h_and_g_are_the_weighted_sums(name):
         assert (wgt < 1).any() == (soft > 0) and c == rho_sum(pb, f, P[f]) and c == lin["c"][f]
         assert np.array_equal(H, lin["H"][f]) and np.array_equal(g, lin["g"][f]) and soft == lin["soft"][f]
         # corner by corner
-        Xw, uv = pb.pts[f]
+        Xw, uv, ci = pb.pts[f]
         Hs, gs = np.zeros((6, 6)), np.zeros(6)
         for i in range(len(Xw)):
-            _, w1, _, ok, J, r = SR.corner_terms(pb.cam, P[f][0], P[f][1], Xw[i:i + 1], uv[i:i + 1], pb.k, jac=True)
+            _, w1, _, ok, J, r = SR.corner_terms(pb.model, P[f][0], P[f][1], Xw[i:i + 1], uv[i:i + 1], ci[i:i + 1], pb.k, jac=True)
             assert ok[0]
             over = s[i] > pb.k
             assert w1[0] == (pb.k / s[i] if over else 1.0) and wgt[i] == w1[0]
@@ -102,7 +102,7 @@ def test_loss_values():
     cam = (100.0, 100.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
     Xw = np.array([[0.0, 0.0, 1.0], [0.0, 0.0, 1.0], [0.0, 0.0, 1.0], [0.0, 0.0, -1.0]])
     uv = np.array([[0.3, 0.4], [3.0, 4.0], [0.6, 0.8], [0.0, 0.0]])       # |r| = 0.5, 5, 1 (at the threshold), behind
-    rho, wgt, over, ok = SR.corner_terms(cam, np.eye(3), np.zeros(3), Xw, uv, 1.0)
+    rho, wgt, over, ok = SR.corner_terms(LR.OneCamera(cam), np.eye(3), np.zeros(3), Xw, uv, np.zeros(4, dtype=np.int64), 1.0)
     assert ok.tolist() == [True, True, True, False] and over.tolist() == [False, True, False, False]
     assert abs(rho[0] - 0.25) <= 1e-15 and abs(rho[1] - 9.0) <= 1e-14 and abs(rho[2] - 1.0) <= 1e-15 and rho[3] == 1e12
     assert wgt[0] == 1.0 and abs(wgt[1] - 0.2) <= 1e-16 and wgt[2] == 1.0 and wgt[3] == 0.0
@@ -182,13 +182,13 @@ def test_robust_tolerance():
 def test_covariance_is_the_dense_inverse_of_the_weighted_matrix(name):
     _, obs, rec, seed, dist, sig, huber, iters = [c for c in RC.all_cases() if c[0] == name][0]
     out, res, _ = RC.statement(name)
-    cov = SV.smooth_cov(obs, rec, SC.K, dist, SC.TAG, out, res, *sig, huber)
+    cov = SV.smooth_cov(obs, rec, SC.K, dist, SC.TAG, out, res, *sig, huber)[0]
     pb = SV.problem_blocks(obs, rec, SC.K, dist, SC.TAG, out, *sig, huber)[0]
     assert (cov["status"] == 0).all() and (cov["dof"] == 8 * int(pb.n_tags.sum()) - 6).all() and (cov["sigma_px"] == sig[0]).all()
     dense, A = SV.dense_marginals(obs, rec, SC.K, dist, SC.TAG, out, *sig, huber)
     for f in range(len(out)):
         CK.assert_cov_close(cov["cov"][f], dense[f], A, (name, f))
     # a down-weighted corner gives less information: no frame is tighter than under the squared loss at the same poses
-    plain = SV.smooth_cov(obs, rec, SC.K, dist, SC.TAG, out, res, *sig)
+    plain = SV.smooth_cov(obs, rec, SC.K, dist, SC.TAG, out, res, *sig)[0]
     soft = np.flatnonzero(out["n_rejected"])
     assert len(soft) and (SV.position_std(cov["cov"])[soft] > SV.position_std(plain["cov"])[soft]).all()

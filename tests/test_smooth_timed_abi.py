@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 
 import smooth_cases as SC
+import smooth_ref as SR
 import smooth_timed_cases as TC
-import smooth_timed_ref as TR
 from aprilslam_amd import _lib
 from aprilslam_amd.smooth import STATUS_BAD_TIMES, SmoothResult
 from test_smooth_cov_abi import ROOT, prototype
@@ -41,7 +41,7 @@ def test_exports_and_argtypes():
     assert L.asl_smooth_timed_sequences_batch.argtypes == host[:11] + [C.POINTER(C.c_double)] + host[11:]
     assert len(L.asl_smooth_timed_sequences_device.argtypes) == len(prototype("asl_smooth_timed_sequences_device")) == 23
     assert len(L.asl_smooth_timed_sequences_batch.argtypes) == len(prototype("asl_smooth_timed_sequences_batch")) == 22
-    assert _lib.SMOOTH_RESULT_DTYPE.itemsize == 64 and STATUS_BAD_TIMES == TR.BAD_TIMES == 4
+    assert _lib.SMOOTH_RESULT_DTYPE.itemsize == 64 and STATUS_BAD_TIMES == SR.BAD_TIMES == 4
 
 
 def test_python_surface_has_the_argument():
@@ -96,13 +96,12 @@ def test_pose_at_on_hand_made_records():
     for f, t in enumerate(times):
         assert np.array_equal(r.pose_at(t), poses["T"][f])
     for t in (0.25, 0.6, 1.5, 2.49, 2.75):
-        got, want = r.pose_at(t), TR.pose_at(poses["T"], times, t)
+        got, want = r.pose_at(t), SR.pose_at(poses["T"], times, t)
         assert np.abs(got - want).max() <= 1e-14, t
         assert np.allclose(got[:3, :3] @ got[:3, :3].T, np.eye(3), atol=1e-14) and np.array_equal(got[3], [0, 0, 0, 1])
     # the geodesic: half way in time is half the step's rotation and, camera<-world, half its translation
     mid = r.pose_at(1.5)
     Ra, Rb, Rm = poses["T"][1][:3, :3].T, poses["T"][2][:3, :3].T, mid[:3, :3].T
-    import smooth_ref as SR
     assert np.allclose(SR.log_so3(Rm @ Ra.T), 0.5 * SR.log_so3(Rb @ Ra.T), atol=1e-14)
     for t in (-1e-9, 3.0 + 1e-9, float("nan"), float("inf")):
         with pytest.raises(ValueError):
@@ -110,7 +109,7 @@ def test_pose_at_on_hand_made_records():
     # without times the frame index is the time
     plain = SmoothResult(poses, result)
     assert plain.times is None and np.array_equal(plain.pose_at(2), poses["T"][2])
-    assert np.abs(plain.pose_at(1.25) - TR.pose_at(poses["T"], None, 1.25)).max() <= 1e-14
+    assert np.abs(plain.pose_at(1.25) - SR.pose_at(poses["T"], None, 1.25)).max() <= 1e-14
     with pytest.raises(ValueError):
         plain.pose_at(3.5)
     one = SmoothResult(poses[:1], result, times=[7.0])

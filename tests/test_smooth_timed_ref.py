@@ -1,5 +1,5 @@
-"""The NumPy statement of the sequence localisation with frame times (tests/smooth_timed_ref.py) against the plain statement
-(tests/smooth_ref.py) where the two must agree, and the figures recorded in tests/smooth_timed_cases.py measured again.  CPU only."""
+"""The NumPy statement of the sequence localisation (tests/smooth_ref.py) with frame times against the same statement without
+them where the two must agree, and the figures recorded in tests/smooth_timed_cases.py measured again.  CPU only."""
 import numpy as np
 import pytest
 
@@ -9,7 +9,6 @@ import smooth_cov_ref as SV
 import smooth_ref as SR
 import smooth_seq_cases as SQ
 import smooth_timed_cases as TC
-import smooth_timed_ref as TR
 
 PLAIN = {c[0]: c[1:] for c in SC.all_cases()}
 
@@ -106,10 +105,10 @@ def test_pose_at():
     k = TC.kept_frames()
     times = k.astype(np.float64)
     for i, f in enumerate(k):       # a frame's own time: that frame's pose
-        assert LC.rel_err(TR.pose_at(timed[0]["T"], times, float(f)), timed[0]["T"][i]) <= 1e-12
+        assert LC.rel_err(SR.pose_at(timed[0]["T"], times, float(f)), timed[0]["T"][i]) <= 1e-12
     rel = pos = truth_err = 0.0
     for f in range(*TC.GAP):        # the dropped frames' times: on the emptied-frames solve, to first order
-        T = TR.pose_at(timed[0]["T"], times, float(f))
+        T = SR.pose_at(timed[0]["T"], times, float(f))
         rel = max(rel, LC.rel_err(T, emptied[0]["T"][f]))
         pos = max(pos, float(np.linalg.norm(T[:3, 3] - emptied[0]["T"][f][:3, 3])))
         truth_err = max(truth_err, float(np.linalg.norm(T[:3, 3] - truth[f][:3, 3])))
@@ -119,15 +118,15 @@ def test_pose_at():
     assert rel <= 2 * r["pose_at_rel"] and pos <= 2 * r["pose_at_pos"] and pos <= 0.05 * truth_err
     assert 0.9 * r["pose_at_rel"] <= rel <= r["pose_at_rel"] and 0.9 * r["pose_at_pos"] <= pos <= r["pose_at_pos"]
     # between two neighbouring frames it stays between them; no extrapolation; without times the index is the time
-    mid = TR.pose_at(timed[0]["T"], times, 3.5)
+    mid = SR.pose_at(timed[0]["T"], times, 3.5)
     assert np.linalg.norm(mid[:3, 3] - 0.5 * (timed[0]["T"][3][:3, 3] + timed[0]["T"][4][:3, 3])) <= 1e-3
     assert np.allclose(mid[:3, :3] @ mid[:3, :3].T, np.eye(3), atol=1e-14)
     for t in (-0.5, 39.5, np.nan):
         with pytest.raises(ValueError):
-            TR.pose_at(timed[0]["T"], times, t)
-    assert np.array_equal(TR.pose_at(timed[0]["T"], None, 19.0), timed[0]["T"][19])
+            SR.pose_at(timed[0]["T"], times, t)
+    assert np.array_equal(SR.pose_at(timed[0]["T"], None, 19.0), timed[0]["T"][19])
     with pytest.raises(ValueError):
-        TR.pose_at(timed[0]["T"], None, 19.5)
+        SR.pose_at(timed[0]["T"], None, 19.5)
 
 
 def test_covariance_of_the_kept_frames():
@@ -136,8 +135,8 @@ def test_covariance_of_the_kept_frames():
     timed, _, emptied = TC.gap_statements()
     k = TC.kept_frames()
     s = TC.GAP_SIGMAS
-    ct, A = TR.smooth_cov(obs[k], rec, SC.K, None, SC.TAG, timed[0], timed[1], k.astype(np.float64), *s)
-    ce = SV.smooth_cov(TC.emptied_gap()[0], rec, SC.K, None, SC.TAG, emptied[0], emptied[1], *s)
+    ct, A = SV.smooth_cov(obs[k], rec, SC.K, None, SC.TAG, timed[0], timed[1], *s, times=k.astype(np.float64))
+    ce = SV.smooth_cov(TC.emptied_gap()[0], rec, SC.K, None, SC.TAG, emptied[0], emptied[1], *s)[0]
     assert (ct["status"] == 0).all() and (ce["status"] == 0).all() and A.shape == (120, 120)
     assert ct["dof"][0] == ce["dof"][0] == 8 * 4 * 20 - 6
     e = TC.scaled_cov_err(ct["cov"], ce["cov"][k])
@@ -155,7 +154,7 @@ def test_covariance_of_the_kept_frames():
         assert (np.abs(ct["cov"][f] - want) / np.outer(sd, sd)).max() <= 1e-8
     # the naive matrix holds the gap as tightly as one frame step, so it is surer of the frames next to it (more information
     # on one link of the chain can only shrink a marginal)
-    cn = SV.smooth_cov(obs[k], rec, SC.K, None, SC.TAG, timed[0], timed[1], *s)
+    cn = SV.smooth_cov(obs[k], rec, SC.K, None, SC.TAG, timed[0], timed[1], *s)[0]
     assert (SV.position_std(cn["cov"])[[9, 10]] < SV.position_std(ct["cov"])[[9, 10]]).all()
 
 
@@ -172,7 +171,7 @@ def test_gap_scene_rmses():
 
 def test_bad_times_are_status_4():
     b, times = TC.bad_times_batch()
-    out, res = TR.smooth_sequences(b.obs, b.seq_start, b.rec, SC.K, b.dist, SC.TAG, b.seed, times, *b.sigmas, b.max_iters)
+    out, res = SR.smooth_sequences(b.obs, b.seq_start, b.rec, SC.K, b.dist, SC.TAG, b.seed, *b.sigmas, b.max_iters, times=times)
     assert res["status"].tolist() == TC.BAD_STATUS
     nothing = SC.statement("all_empty")
     for k, (a0, a1) in enumerate(SQ.ranges(b)):
@@ -181,16 +180,16 @@ def test_bad_times_are_status_4():
             assert out[a0:a1].tobytes() == alone[0].tobytes() and res[k].tobytes() == alone[1].tobytes()
             assert out[a0:a1].tobytes() == TC.statement("shape5_4_0")[0].tobytes()
             continue
-        assert TR.bad_times(times[a0:a1])
+        assert SR.bad_times(times[a0:a1])
         want = nothing[1].copy()
-        want["status"] = TR.BAD_TIMES
+        want["status"] = SR.BAD_TIMES
         assert res[k].tobytes() == want.tobytes()                                  # a status-1 result but for the status
         assert out[a0:a1].tobytes() == nothing[0][:a1 - a0].tobytes()               # status-1 frames: T identity, seed_slot -1
-        cov, _ = TR.smooth_cov(b.obs[a0:a1], b.rec, SC.K, b.dist, SC.TAG, out[a0:a1], res[k], times[a0:a1], *b.sigmas)
+        cov, _ = SV.smooth_cov(b.obs[a0:a1], b.rec, SC.K, b.dist, SC.TAG, out[a0:a1], res[k], *b.sigmas, times=times[a0:a1])
         assert (cov["status"] == 1).all() and not cov["cov"].any() and (cov["dof"] == 0).all()
     # one frame needs only a finite time; infinities are not finite
-    assert not TR.bad_times([3.0]) and TR.bad_times([np.inf]) and TR.bad_times([0.0, np.inf]) and not TR.bad_times([-2.0, -1.0])
-    assert TR.bad_times([0.0, 0.0]) and TR.bad_times([1.0, 0.5]) and TR.bad_times([0.0, np.nan, 2.0])
+    assert not SR.bad_times([3.0]) and SR.bad_times([np.inf]) and SR.bad_times([0.0, np.inf]) and not SR.bad_times([-2.0, -1.0])
+    assert SR.bad_times([0.0, 0.0]) and SR.bad_times([1.0, 0.5]) and SR.bad_times([0.0, np.nan, 2.0])
 
 
 def test_ragged_times_restart_at_every_boundary():
