@@ -43,6 +43,9 @@ assert SMOOTH_RESULT_DTYPE.itemsize == 64
 assert POSE_COV_DTYPE.itemsize == 304
 RIG_CAMERA_DTYPE = np.dtype([("K", "<f8", (3, 3)), ("dist", "<f8", (5,)), ("E", "<f8", (3, 4)), ("n_dist", "<i4"), ("reserved", "<i4")])  # asl_rig_camera
 assert RIG_CAMERA_DTYPE.itemsize == 216
+TAG_FIT_DTYPE = np.dtype([("rms_px", "<f8"), ("rms_seed_px", "<f8"), ("n_views", "<i4"), ("n_rejected", "<i4"), ("status", "<i4"),
+                          ("seed_frame", "<i4"), ("seed_mirrored", "<i4"), ("reserved", "<i4")])  # asl_tag_fit
+assert TAG_FIT_DTYPE.itemsize == 40
 
 EXPORTS = [
     "asl_detector_create", "asl_family_check", "asl_detector_create_family", "asl_families_check", "asl_detector_create_families", "asl_detector_family_of", "asl_detector_destroy", "asl_detector_set_id_limit", "asl_detector_set_pnp_both_minima", "asl_detector_set_quad_sigma", "asl_blur_taps", "asl_last_error", "asl_version", "asl_detect_gray_u8",
@@ -56,6 +59,7 @@ EXPORTS = [
     "asl_smooth_sequences_device", "asl_smooth_sequences_batch", "asl_smooth_robust_sequences_device", "asl_smooth_robust_sequences_batch",
     "asl_smooth_timed_sequences_device", "asl_smooth_timed_sequences_batch",
     "asl_smooth_rig_sequences_device", "asl_smooth_rig_sequences_batch",
+    "asl_locate_tags_frames_device", "asl_locate_tags_batch",
     "asl_debug_fetch", "asl_debug_refit", "asl_debug_dedup", "asl_debug_gn_cholesky", "asl_debug_gn_step", "asl_debug_division_check", "asl_stage_times", "asl_set_profiling", "asl_debug_phase_cycles",
 ]
 
@@ -239,6 +243,9 @@ def load():
     smooth_rig = rig[:8] + [dbl, vp]                              # detector, obs, n_cams, n_frames, max_tags, map, n_ids, rig, tag_size, seed
     L.asl_smooth_rig_sequences_device.argtypes = smooth_rig + [vp] + seqs + robust + [vp, vp]    # ..., seed, frame_times, seq_start, ...
     L.asl_smooth_rig_sequences_batch.argtypes = smooth_rig + [dp] + seqs + robust + [vp]
+    locate = [vp] + obs_block + [vp] + tag_map + camera + [dbl, i32, dbl, vp, vp]    # ..., poses, map, n_ids, camera, gate, min_views, sigma_px, fit, cov
+    L.asl_locate_tags_frames_device.argtypes = locate + [vp]
+    L.asl_locate_tags_batch.argtypes = locate
     L.asl_debug_fetch.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.asl_debug_refit.argtypes = [vp, i32, vp, C.c_size_t]
     L.asl_debug_dedup.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, C.c_size_t]
@@ -606,6 +613,38 @@ class Detector:
             check(self._L.asl_localize_rig_frames_device(*args, _ptr(out_ptr), _ptr(stream)))
         else:
             check(self._L.asl_localize_rig_cov_frames_device(*args, float(sigma_px), _ptr(out_ptr), _ptr(cov_ptr), _ptr(stream)))
+
+    def locate_tags(self, obs, poses, map_records, K, dist, tag_size, max_view_rms_px=0.0, min_views=2, sigma_px=None):
+        """asl_locate_tags_batch: host records obs (n_frames, max_tags) OBS_DTYPE, their frames' poses (n_frames,)
+        CAM_POSE_DTYPE (world<-camera: what localize, smooth or build_map return) and a map block (n_ids,) MAP_TAG_DTYPE (or a
+        localize.TagMap) -> (the extended map, (n_ids,) TAG_FIT_DTYPE, (n_ids,) POSE_COV_DTYPE or None).  Every id whose
+        entry has valid == 0 (and a size that is 0, the call's tag_size, or the tag's own side) is solved from all its
+        views with the cameras held fixed; a located tag's entry gets its pose and valid = 1, every other entry keeps its
+        bytes.  The caller's array is not modified.  max_view_rms_px > 0: the outlier gate on single views.  sigma_px not
+        None: also the covariance of every located world<-tag, scaled by that corner sigma, or by the solve's own
+        estimate for 0."""
+        o, m = _obs_records(obs), _map_records(map_records).copy()
+        p = np.ascontiguousarray(poses, dtype=CAM_POSE_DTYPE).ravel()
+        if len(p) != o.shape[0]:
+            raise ValueError("one pose per frame: obs has %d frames, poses %d" % (o.shape[0], len(p)))
+        keep, Kp, dpp, nd = _camera(K, dist, square=True)
+        fit = np.zeros(len(m), dtype=TAG_FIT_DTYPE)
+        cov = np.zeros(len(m), dtype=POSE_COV_DTYPE) if sigma_px is not None else None
+        none = np.zeros(1, dtype=CAM_POSE_DTYPE)   # no frame: the block and the poses are never read, but must not be NULL
+        check(self._L.asl_locate_tags_batch(self._h, _data(o) or none.ctypes.data, o.shape[0], o.shape[1], _data(p) or none.ctypes.data, _data(m),
+                                            len(m), Kp, dpp, nd, float(tag_size), float(max_view_rms_px), int(min_views),
+                                            float(sigma_px or 0.0), _data(fit), None if cov is None else _data(cov)))
+        return m, fit, cov
+
+    def locate_tags_device(self, obs_ptr, n_frames, max_tags, poses_ptr, map_ptr, n_ids, fit_ptr, K, dist, tag_size, max_view_rms_px=0.0,
+                           min_views=2, stream=0, cov_ptr=None, sigma_px=0.0):
+        """asl_locate_tags_frames_device: obs_ptr (n_frames x max_tags asl_obs), poses_ptr (n_frames asl_cam_pose), map_ptr
+        (n_ids asl_map_tag, read and written in place), fit_ptr (n_ids asl_tag_fit) and cov_ptr (n_ids asl_pose_cov, or None)
+        are device addresses; enqueued on `stream`, no wait."""
+        keep, Kp, dpp, nd = _camera(K, dist, square=True)
+        check(self._L.asl_locate_tags_frames_device(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(poses_ptr), _ptr(map_ptr), int(n_ids),
+                                                    Kp, dpp, nd, float(tag_size), float(max_view_rms_px), int(min_views), float(sigma_px),
+                                                    _ptr(fit_ptr), _opt_ptr(cov_ptr), _ptr(stream)))
 
     def pose_cov(self, corners, T, K, dist, tag_size, sigma_px=0.0):
         """asl_solve_pnp_cov_batch: the covariance of the camera<-tag poses T (N, 4, 4) that solve_pnp returned for corners

@@ -38,6 +38,7 @@
 #include "k_calib.inc"
 #include "k_map.inc"
 #include "k_smooth.inc"
+#include "k_locate.inc"
 
 static thread_local std::string g_err;
 
@@ -142,6 +143,7 @@ struct asl_detector {
     DevBuf<uint8_t> cal_ws;  // calibration: per-frame workspace and state (k_calib.inc)
     DevBuf<uint8_t> map_ws, map_lm;  // map reconstruction (k_map.inc): sized by the input / by the problem
     DevBuf<uint8_t> smooth_ws;  // sequence localisation (k_smooth.inc): the chain's and the LM's buffers, sized by n_frames and n_seq
+    DevBuf<uint8_t> locate_ws;  // tag location (k_locate.inc): per-id marks, counts and offsets, the view list
     hipStream_t copy_stream = nullptr, host_stream = nullptr;  // host frames: transfers and the chunks' kernels (detect_host_frames)
     std::vector<hipEvent_t> copy_done;
     hipStream_t aux_stream = nullptr;  // highest priority, for the small latency-bound jobs next to a running batch (pose-graph LM)

@@ -249,6 +249,11 @@ class SLAM:
         sizes (the graph has one tag_size); a map with sizes goes through TagDetector.localize."""
         return self.detector.localize(detections, self.tag_map(), max_tag_rms_px=max_tag_rms_px, with_cov=with_cov, sigma_px=sigma_px)
 
+    def extend_map(self, frames_or_obs, **kw):
+        """Tags the graph does not have, located from frames that also see tags of tag_map() (TagDetector.extend_map, whose
+        keywords pass through) -> (locate.LocateResult, the frames' poses); the graph, the window and my_pose() stay as they are."""
+        return self.detector.extend_map(frames_or_obs, self.tag_map(), **kw)
+
     def localize_sequence(self, dets, poses, n_per_frame, **kw):
         """Camera poses of consecutive frames against tag_map(), solved together with a motion prior
         (TagDetector.localize_sequence, whose keywords pass through: times=... for frames that are not evenly spaced); like

@@ -338,6 +338,32 @@ class TagDetector:
                                            tag_sizes=tag_sizes)
         return MapResult(*out, slot_ids=obs["id"] if huber_px else None)
 
+    def extend_map(self, frames_or_obs, tag_map, tag_sizes=None, max_view_rms_px=0.0, min_views=2, sigma_px=None, max_tag_rms_px=0.0):
+        """Frames that see tags of tag_map (a localize.TagMap) and tags it does not have -> (locate.LocateResult, one
+        CAM_POSE_DTYPE record per frame): the frames are localised against the map and every unmapped tag is located from
+        the frames that got a pose, the cameras held fixed (asl_locate_tags_batch).  The known tags keep their poses.
+        frames_or_obs: host frames as build_map takes them, or an (n_frames, max_tags) OBS_DTYPE block.  tag_sizes
+        ({id: size}): unmapped tags whose side is not the detector's tag_size.  max_view_rms_px gates single views of a
+        tag, max_tag_rms_px the tags of a frame; sigma_px not None adds the located tags' covariances.  The frame poses
+        are taken as exact: this is not a joint refinement of cameras and new tags."""
+        from .dist import pack_observations
+        from .locate import extend_map
+        if self.camera_matrix is None:
+            raise ValueError("extend_map needs the detector's camera parameters")
+        a = frames_or_obs
+        if not (isinstance(a, np.ndarray) and a.dtype == _lib.OBS_DTYPE):
+            a = np.ascontiguousarray(np.stack(a) if isinstance(a, (list, tuple)) else a)
+            if a.ndim not in (3, 4) or a.dtype != np.uint8:
+                raise ValueError("frames must be (n, H, W[, 3]) uint8, or an OBS_DTYPE block")
+            if self.rectify:
+                a = np.stack([self._rectified_host(f) for f in a])
+            dets, poses, npf = self.detector._det.detect_host(a, channels=1 if a.ndim == 3 else None, K=self._K(), dist=self._dist(),
+                                                              tag_size=self.tag_size)
+            npf = np.asarray(npf, dtype=np.int64)
+            a = pack_observations(dets, poses, npf, max(1, min(256, int(npf.max()) if len(npf) else 1)))
+        return extend_map(self.detector._det, a, tag_map, self._K(), self._dist(), self.tag_size, tag_sizes=tag_sizes,
+                          max_view_rms_px=max_view_rms_px, min_views=min_views, sigma_px=sigma_px, max_tag_rms_px=max_tag_rms_px)
+
     def detect_batch_device(self, data_ptr, n_frames, channels, width, height, with_pose=True, stream=0, **kw):
         """Frames resident in HBM -> (dets, poses, n_per_frame) structured arrays (see _lib).  With rectify the frames are
         rectified on `stream` first, device to device, and the detections are in rectified pixels."""

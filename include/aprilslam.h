@@ -572,6 +572,57 @@ int asl_map_rig_sized_batch(asl_detector *det, const asl_obs *obs, int n_cams, i
                             int max_iters, asl_map_tag *map, double *tag_std, asl_cam_pose *poses, asl_map_result *result,
                             double *slot_weight);
 
+/* ---- extending a map: the world<-tag pose of tags the map does not have, from frames whose camera poses are known
+   (asl_localize_* against the tags the map does have, asl_smooth_*, or asl_map_*'s d_poses).  The dual of localisation:
+   each unmapped tag is solved on its own from all its views with the cameras held fixed, one wavefront per tag.  The
+   result is NOT the joint optimum of cameras and tags: the frame poses are taken as exact, exactly as localisation takes
+   the map as exact, and their uncertainty is not propagated.  The known entries of the map are never moved, so the gauge
+   and every pose the rest of a system relies on stay as they are. */
+typedef struct {
+    double rms_px;         /* final reprojection RMS (pixels per corner) over the views used */
+    double rms_seed_px;    /* the same of the winning first candidate, over every view */
+    int32_t n_views;       /* views in the final solve (status 2 and 3: the views found) */
+    int32_t n_rejected;    /* views dropped by the gate */
+    int32_t status;        /* 0 located, 1 not wanted, 2 fewer than min_views views, 3 no view with a PnP */
+    int32_t seed_frame;    /* frame of the winning first candidate, -1 if none */
+    int32_t seed_mirrored; /* 1: that candidate was the mirrored planar minimum */
+    int32_t reserved;
+} asl_tag_fit;             /* 40 bytes */
+
+/* d_obs: n_frames x max_tags records of one camera; d_poses: n_frames asl_cam_pose (T = world<-camera); d_map: n_ids
+   asl_map_tag, in and out; d_fit: n_ids asl_tag_fit; d_cov: n_ids asl_pose_cov or NULL.  Device pointers, asynchronous on
+   `stream`, no host wait.
+   Wanted: id i < n_ids whose entry has valid == 0 and a size that is >= 0 and finite.  size > 0 on such an entry is the
+   tag's own known side, 0 means tag_size (the rule of asl_map_tag.size), so no separate table of sizes is needed.  Valid
+   entries, and invalid ones with a negative or non-finite size, are not wanted: status 1.
+   Views: frame f takes part if d_poses[f].status is 0 or 6 (the sequence solve's prior-only frame) and rows 0..2 of its T
+   are finite; in such a frame the first slot with flags & 1 and id == i is the tag's view.  C_f = inv(T_f).  Fewer than
+   min_views (>= 1) views: status 2.
+   Cost: the 4 corners (+-h, +-h, 0) of every active view, project(C_f (G X_q)) - uv, G = world<-tag; a corner at
+   z <= 1e-9 costs 1e12.  Seed: the <= 8 active views with flags & 2 of largest corner area (ties: the earlier view), in
+   view order, each with G = inv(C_f) T_obs (a sized tag's PnP translation first times size / tag_size) and that pose's
+   mirrored planar minimum formed in the camera frame; the strictly lowest total cost over all active views wins.  No such
+   view, or every score NaN: status 3.  Refinement: Levenberg-Marquardt on the 6 parameters of G with localisation's fixed
+   schedule.  max_view_rms_px > 0 is an outlier gate: while the active view of largest own 4-corner RMS exceeds it, that
+   view is dropped (one at a time, at most 8, never the last) and the solve is seeded again, from the lowest-cost of the
+   current pose and the candidates of the views still active, and refined; 0 turns the gate off.
+   Output: a located tag's d_map[i].T is written and its valid set to 1, its size is kept; every other map entry keeps its
+   bytes, so the block is the extended map and goes to asl_localize_* / asl_smooth_* / asl_calibrate_* as it is.  d_cov[i]:
+   the covariance of world<-tag in the (r, d) convention above (the pose solved for itself, A = [I 0; -[p]x I]) over the
+   views of the final solve, dof = 8 n_views - 6, sigma_px given or 0 to estimate it from the cost; status 1 for an id not
+   located, 2 when J^T J is not positive definite.
+   ASL_EINVAL, before anything is written or enqueued: a NULL argument other than d_cov, n_frames < 0, max_tags outside
+   [1, 256], n_ids < 1, a bad camera, a negative or non-finite gate, min_views < 1, sigma_px < 0 or non-finite.
+   n_frames == 0 is ASL_OK: every wanted id gets status 2.  Deterministic: the same input gives the same bytes.
+   tests/locate_ref.py states the computation. */
+int asl_locate_tags_frames_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, const void *d_poses,
+                                  void *d_map, int n_ids, const double *K, const double *dist, int n_dist, double tag_size,
+                                  double max_view_rms_px, int min_views, double sigma_px, void *d_fit, void *d_cov, void *stream);
+/* The same computation on host records, synchronous; map is read and written in place, cov may be NULL. */
+int asl_locate_tags_batch(asl_detector *det, const asl_obs *obs, int n_frames, int max_tags, const asl_cam_pose *poses,
+                          asl_map_tag *map, int n_ids, const double *K, const double *dist, int n_dist, double tag_size,
+                          double max_view_rms_px, int min_views, double sigma_px, asl_tag_fit *fit, asl_pose_cov *cov);
+
 /* ---- sequence localisation: the camera poses of one camera's consecutive frames against a fixed map, solved together
    under a random-walk motion prior, so that EVERY frame gets a pose: frames without a mapped tag are carried by their
    neighbours, a single-tag frame cannot end in its mirrored planar minimum alone, and corner noise is averaged. */
