@@ -6,7 +6,8 @@ Input: n_frames x max_tags asl_obs records (only flags & 1, id and corners are r
 are known (asl_map_tag records indexed by id).  Unknowns: theta = (fx, fy, cx, cy, k1, k2, p1, p2, k3) -- the camera
 model of k_pnp.inc, the first 4 + n_dist of them -- and every used frame's camera<-world pose.
 
-  gather      a slot takes part if flags & 1, 0 <= id < n_ids and map[id].valid; a frame takes part with >= 2 such slots
+  gather      a slot takes part if flags & 1, 0 <= id < n_ids and map[id] is valid by localize_ref's size rule (tag_half);
+              its world corners are (+-h, +-h, 0) of its tag's own half side h; a frame takes part with >= 2 such slots
   closed form (no K_init) principal point = (width / 2, height / 2); every taking-part tag's homography from its square
               (+-1, +-1) (lb rb rt lt) to its corners, in the coordinates x' = (u - cx) / s, s = (width + height) / 2,
               closed-form square -> quad (Heckbert); Zhang's two constraints on its columns h1, h2 with
@@ -17,9 +18,9 @@ model of k_pnp.inc, the first 4 + n_dist of them -- and every used frame's camer
               unknown).  Status 2 if det M <= 1e-6 m trace M (m rows; with a fixed aspect ratio the 1x1 system <= 1e-6 m):
               fronto-parallel views inform only fx / fy, or if a or b is not above 1e-6 or not finite.  K_init replaces the whole step.
   seed        per frame, with K0 and no distortion: the <= 8 taking-part slots of largest corner area (ties: lower
-              slot), in slot order, each slot's planar pose from its homography under K0 and that pose's mirrored
-              minimum, composed with the map and scored over all of the frame's corners (localize_ref.seed_candidates'
-              rule: the strictly lowest wins); a winner that costs >= 1e12 (a corner behind the camera) drops the frame
+              slot), in slot order, each slot's planar pose from its homography under K0 at its tag's own half side (no
+              PnP pose is read, so nothing is scaled) and that pose's mirrored minimum, composed with the map and scored
+              over all of the frame's corners (localize_ref.seed_candidates' rule: the strictly lowest wins); a winner that costs >= 1e12 (a corner behind the camera) drops the frame
               (frame status 3); otherwise localize_ref.lm refines it.
   joint LM    theta (the free entries, in the order fx fy cx cy k1 k2 p1 p2 k3, fx dropped under FIX_ASPECT_RATIO,
               cx cy under FIX_PRINCIPAL_POINT, p1 p2 under ZERO_TANGENT_DIST) and 6 pose parameters per used frame,
@@ -63,11 +64,10 @@ def free_params(n_dist, flags):
 def gather(rows, tag_map, tag_size):
     """(taking-part slots, world corners (4n, 3), image corners (4n, 2))"""
     n_ids = len(tag_map)
-    part = [s for s, o in enumerate(rows) if (o["flags"] & 1) and 0 <= o["id"] < n_ids and tag_map["valid"][o["id"]]]
+    part = [s for s, o in enumerate(rows) if (o["flags"] & 1) and 0 <= o["id"] < n_ids and LR.tag_half(tag_map[o["id"]], tag_size)[0] is not None]
     if not part:
         return part, np.zeros((0, 3)), np.zeros((0, 2))
-    obj = LR.object_corners(tag_size)
-    Xw = np.concatenate([LR._world_corners(tag_map["T"][rows["id"][s]], obj) for s in part])
+    Xw = np.concatenate([LR._world_corners(tag_map["T"][i], LR.half_corners(LR.tag_half(tag_map[i], tag_size)[0])) for i in rows["id"][part]])
     uv = np.concatenate([rows["corners"][s].astype(np.float64).reshape(4, 2) for s in part])
     return part, Xw, uv
 
@@ -142,9 +142,10 @@ def seed_frame(rows, part, Xw, uv, tag_map, theta0, width, height, tag_size):
     """(R, t, seed cost after the pose-only LM, seed code) or None (every candidate had a corner behind the camera)"""
     fx, fy, cx, cy = theta0[:4]
     cam0 = (fx, fy, cx, cy, 0.0, 0.0, 0.0, 0.0, 0.0)
-    s, half = 0.5 * (width + height), LR.half_size(tag_size)
+    s = 0.5 * (width + height)
     best, best_cost = None, np.inf
     for k in [part[i] for i in LR.top_k([LR.corner_area(rows["corners"][k]) for k in part])]:
+        half = LR.tag_half(tag_map[rows["id"][k]], tag_size)[0]
         Ro, to = planar_pose(square_homography(rows["corners"][k], cx, cy, s), fx, fy, s, half)
         M = tag_map["T"][rows["id"][k]].reshape(3, 4)
         for m in (0, 1):

@@ -166,7 +166,7 @@ def run_parent(run):
 
 
 def run_sized(ZR, kind, a, times, sig, iters, kw):
-    """the sized fronts, whose spelling did not change"""
+    """the sized fronts of the recorded commit's sized_ref"""
     if kind == "sized_cam":
         out, res, trace = ZR.smooth(*a, times, *sig, iters, **kw)
         return out, res, None, trace
@@ -179,11 +179,12 @@ def run_sized(ZR, kind, a, times, sig, iters, kw):
 
 
 def run_one(run):
-    """the call through the one statement -> (poses, results, covariance or None, trace or None)"""
-    import sized_ref as ZR
+    """the call through the one statement -> (poses, results, covariance or None, trace or None); a sized run is the same call:
+    the statements honour sizes themselves"""
     import smooth_cov_ref as SV
     import smooth_ref as SR
     _, _, kind, args, kw = run
+    kind = kind[len("sized_"):] if kind.startswith("sized_") else kind
     kw = dict(kw)
     times = kw.pop("times", None)
     sig, iters = args[-2:]
@@ -196,10 +197,9 @@ def run_one(run):
     if kind == "cam_cov":
         out, res, _ = SR.smooth(*a, *sig, iters, times=times, **kw)
         return out, res, SV.smooth_cov(*a[:5], out, res, *sig, times=times, **kw)[0], None
-    if kind == "rig_cov":
-        out, res, _ = SR.smooth_rig(*a, *sig, iters, times=times, **kw)
-        return out, res, SV.smooth_rig_cov(*a[:4], out, res, *sig, times=times, **kw)[0], None
-    return run_sized(ZR, kind, a, times, sig, iters, kw)
+    assert kind == "rig_cov", kind
+    out, res, _ = SR.smooth_rig(*a, *sig, iters, times=times, **kw)
+    return out, res, SV.smooth_rig_cov(*a[:4], out, res, *sig, times=times, **kw)[0], None
 
 
 def fields(out):

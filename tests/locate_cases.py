@@ -98,7 +98,7 @@ def sized_view(tag, pos, rot, side, dist=None):
     """(corners (8,) float32, T (12,)) of `tag` seen at its own side, with the PnP pose a solve at TAG gives for it: the true
     camera<-tag with its translation divided by k = h_id / half (sized_cases.block)"""
     T = synth.camera_from_tag(tag["position"], tag["rotation"], pos, rot).copy()
-    h = float(np.float32(side) * np.float32(0.5))
+    h = LR.size_half(side, TAG)[0]
     obj = np.array([[-h, -h, 0.0], [h, -h, 0.0], [h, h, 0.0], [-h, h, 0.0]])
     uv = LR.project(LR.camera(K, dist), obj @ T[:3, :3].T + T[:3, 3])
     assert np.all(uv >= 0) and np.all(uv[:, 0] < LC.W) and np.all(uv[:, 1] < LC.H)

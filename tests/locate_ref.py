@@ -7,8 +7,8 @@ Inputs: obs (n_frames, max_tags) asl_obs records of one camera, poses (n_frames,
 block (n_ids,) asl_map_tag, the camera model, tag_size, max_view_rms_px, min_views, optionally sigma_px.
 
   wanted   id i is solved for if map[i].valid == 0 and its size is >= 0 and finite; size > 0 is the tag's own side, 0 the
-           call's tag_size (h = float32(size) * float32(0.5), or float32(tag_size / 2): map_tag_half's rule).  Valid
-           entries, and invalid ones with a bad size, get status 1.
+           call's tag_size (map_tag_half's rule on the size: localize_ref.size_half).  Valid entries, and invalid ones
+           with a bad size, get status 1.
   views    frame f takes part if poses[f].status is 0 or 6 and rows 0..2 of its T are finite; in such a frame the first
            slot with flags & 1 and id == i is the view.  C_f = inv(T_f) = camera<-world, formed from the record as
            (R^T, -R^T p).  Fewer than min_views views: status 2.
@@ -16,7 +16,8 @@ block (n_ids,) asl_map_tag, the camera model, tag_size, max_view_rms_px, min_vie
            z <= 1e-9 costs 1e12 and adds no row.  Left update G <- [Rod(w) | v] G in the world frame:
            J = J_proj R_f [-[X_w]x | I].
   seed     the <= 8 active views with flags & 2 of largest corner area (ties: lower list position), walked in list order,
-           plain before mirrored: G = inv(C_f) T_obs, a sized tag's PnP translation first times h_id / half, the mirror
+           plain before mirrored: G = inv(C_f) T_obs, a sized tag's PnP translation first times h_id / half
+           (localize_ref.seed_translation), the mirror
            formed in the camera frame.  The strictly lowest total cost over all active views wins.  No seeding view, or
            every score NaN: status 3.
   refine   localize_ref.lm: 10 trials, lambda0 = 1e-3, stop on a relative decrease below 1e-12.
@@ -37,18 +38,16 @@ import numpy as np
 
 import pose_cov_ref as PC
 from aprilslam_amd._lib import MAP_TAG_DTYPE, POSE_COV_DTYPE, TAG_FIT_DTYPE
-from localize_ref import BEHIND_COST, MAX_GATE_DROPS, MAX_SEED_SLOTS, Z_MIN, camera, corner_area, half_size, lm, mirrored, neg_skew, project, top_k
+from localize_ref import (BEHIND_COST, MAX_GATE_DROPS, MAX_SEED_SLOTS, Z_MIN, camera, corner_area, lm, mirrored, neg_skew, project, seed_translation,
+                          size_half, top_k)
 
 STATUS_LOCATED, STATUS_NOT_WANTED, STATUS_FEW_VIEWS, STATUS_NO_PNP = 0, 1, 2, 3
 FRAME_STATUSES = (0, 6)
 
 
 def wanted_half(entry, tag_size):
-    """(wanted, half side) of one map entry"""
-    sz = np.float32(entry["size"])
-    ok = entry["valid"] == 0 and bool(sz >= 0) and bool(np.isfinite(sz))
-    h = float(sz * np.float32(0.5)) if sz > 0 else half_size(tag_size)
-    return ok, h
+    """(half side, whether it is the tag's own) of a map entry that is wanted: not mapped, with a good size; else (None, False)"""
+    return size_half(entry["size"], tag_size) if entry["valid"] == 0 else (None, False)
 
 
 def frame_ok(pose):
@@ -81,8 +80,8 @@ def tag_corners(h):
 class TagViews:
     """the views of one tag: cameras (Rc (n, 3, 3), tc (n, 3)), image corners (n, 4, 2), the records' flags and PnP poses"""
 
-    def __init__(self, cam, obs, poses, views, h, half):
-        self.cam, self.h, self.half = cam, h, half
+    def __init__(self, cam, obs, poses, views, h, own, tag_size):
+        self.cam, self.h, self.own, self.tag_size = cam, h, own, tag_size
         self.views = views
         cams = [view_camera(poses[f]) for f, _ in views]
         self.Rc = np.array([c[0] for c in cams]).reshape(-1, 3, 3)
@@ -139,9 +138,7 @@ class TagViews:
         chosen = [seeds[k] for k in top_k([self.area[v] for v in seeds], MAX_SEED_SLOTS)]
         out = []
         for v in chosen:
-            Ro, to = self.To[v][:, :3], self.To[v][:, 3].copy()
-            if self.h != self.half:
-                to = to * (self.h / self.half)
+            Ro, to = self.To[v][:, :3], seed_translation(self.To[v][:, 3], self.h, self.own, self.tag_size)
             Wr = self.Rc[v].T                                                # inv(C_f)
             Wt = -(Wr @ self.tc[v])
             for m in (0, 1):
@@ -217,16 +214,15 @@ def locate_tags(obs, poses, map_records, K, dist, tag_size, max_view_rms_px=0.0,
         obs = obs[None]
     out = np.array(map_records, dtype=MAP_TAG_DTYPE).ravel().copy()
     cam = camera(K, dist)
-    half = half_size(tag_size)
     fits, covs = [], []
     for i in range(len(out)):
-        ok, h = wanted_half(out[i], tag_size)
-        if not ok:
+        h, own = wanted_half(out[i], tag_size)
+        if h is None:
             fit = np.zeros((), dtype=TAG_FIT_DTYPE)
             fit["status"], fit["seed_frame"] = STATUS_NOT_WANTED, -1
             Rt, tv, act = None, None, None
         else:
-            tv = TagViews(cam, obs, poses, views_of(obs, poses, i), h, half)
+            tv = TagViews(cam, obs, poses, views_of(obs, poses, i), h, own, tag_size)
             fit, Rt, act, trace = solve_tag(tv, float(max_view_rms_px), int(min_views))
             if traces is not None:
                 traces[i] = (tv, trace, Rt, act)

@@ -57,7 +57,7 @@ slot, the rig is the camera, a pair has one view.
            corners not over k / (2 n_in - 6 frames - 6 (tags - 1)), n_in their number (a corner at z <= 1e-9 is one of them,
            with its 1e12); 0 if the denominator is <= 0.  The factor leaves the outliers' linear tails out, so one bad slot
            does not inflate every tag's std; the truncation at k biases it slightly low.
-  sizes    tag_sizes, (n_ids,) float32 or None (all 0), by the rule of map_tag_half (sized_ref.py): 0: the tag has the call's
+  sizes    tag_sizes, (n_ids,) float32 or None (all 0), by the rule of map_tag_half (localize_ref.py): 0: the tag has the call's
            tag_size, half = float32(tag_size / 2); > 0 and finite: the tag's own side, h_id = float32(size) * float32(0.5);
            negative or not finite: ValueError naming the id (the device: ASL_EINVAL, nothing written).  Every pass that
            forms a tag's corners uses that tag's h: the sweeps' costs, the flip test's tag_lm, the behind test, the LM's
@@ -132,18 +132,6 @@ def size_table(tag_sizes, n_ids):
     if len(bad):
         raise ValueError("tag_sizes[%d] must be 0 or positive and finite" % bad[0])
     return t
-
-
-def tag_half(size, half):
-    """sized_ref.tag_half on a table entry"""
-    return float(np.float32(size) * np.float32(0.5)) if size > 0 else half
-
-
-def scaled(T, size, h, half):
-    """a record's camera<-tag (4x4) as it is for a tag of half side h: sized_ref.tag_pose"""
-    if size > 0:
-        T[:3, 3] = T[:3, 3] * (h / half)
-    return T
 
 
 def by_half(fn, hv, n_out):
@@ -364,7 +352,6 @@ def map_rig_frames(obs, n_ids, rig, tag_size, tag_sizes=None, world_id=-1, huber
     table = rig_ref.rig_table(rig)
     assert len(table) == C
     E = mountings(table)
-    half = LR.half_size(tag_size)
     sizes = size_table(tag_sizes, n_ids)
     res = np.zeros((), dtype=MAP_RESULT_DTYPE)
     out_map = np.zeros(n_ids, dtype=MAP_TAG_DTYPE)
@@ -410,11 +397,14 @@ def map_rig_frames(obs, n_ids, rig, tag_size, tag_sizes=None, world_id=-1, huber
     if NT > MAX_MAP_TAGS:
         raise ValueError("more than %d tags" % MAX_MAP_TAGS)
     wt = tag_of[world_id]
-    ht = np.array([tag_half(sizes[i], half) for i in ids])             # per tag: its half side
+    sized = [LR.size_half(sizes[i], tag_size) for i in ids]            # per tag: (its half side, whether its own)
+    ht = np.array([h for h, _ in sized])
     hv = ht[ot]                                                        # per view
     rec = [obs[c, f, s] for c, f, s in zip(ovc, ofr, osl)]
     uv = np.stack([r["corners"].astype(np.float64).reshape(4, 2) for r in rec]) if M else np.zeros((0, 4, 2))
-    To = [scaled(rec4(r["T"]), sizes[ids[j]], ht[j], half) for r, j in zip(rec, ot)]
+    To = [rec4(r["T"]) for r in rec]
+    for T, j in zip(To, ot):                                           # a record's camera<-tag as it is for its tag's half side
+        T[:3, 3] = LR.seed_translation(T[:3, 3], *sized[j], tag_size)
     if trace is not None:
         trace.update(ids=ids, chain_frames=[], chain_tags=[], sweep_mirrored=[])
     seedable = np.array([bool(r["flags"] & 2) for r in rec], dtype=bool)

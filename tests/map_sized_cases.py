@@ -97,7 +97,7 @@ def flip_case():
     obs, rig, t = build(sizes, SOLO, 6, 24, noise=0.0, poses=poses)
     obs = obs.copy()
     tm = sized_scene(sizes)
-    h, half = MR.tag_half(t[FLIP_TAG], LR.half_size(TAG)), LR.half_size(TAG)
+    h, half = LR.size_half(t[FLIP_TAG], TAG)[0], LR.half_size(TAG)
     W = [MR.inv(T) for T in poses]
     views = [(LR.corner_area(obs["corners"][0, f, s]), f, s) for f, s in zip(*np.nonzero(obs["id"][0] == FLIP_TAG))]
     _, b, _ = max(views, key=lambda v: (v[0], -v[1]))

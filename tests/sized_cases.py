@@ -1,7 +1,7 @@
 """Inputs of the sized-map tests (tests/test_sized_ref.py on the CPU, tests/test_gpu_sized.py on the device): tag maps
 whose entries carry their own size, asl_obs blocks from exact projections of those tags at their true sizes, and records
 whose PnP pose is what a PnP at the call's single tag_size gives for them: the true camera<-tag with its translation
-divided by k = h_id / half (sized_ref.py).  All from 4x4 matrices with localize_ref.project, as rig_cases.py."""
+divided by k = h_id / half (localize_ref.py).  All from 4x4 matrices with localize_ref.project, as rig_cases.py."""
 import functools
 
 import numpy as np
@@ -9,7 +9,7 @@ import numpy as np
 import localize_cases as LC
 import localize_ref as LR
 import rig_cases as RC
-import sized_ref as ZR
+import rig_ref as RR
 from aprilslam_amd import _lib, synth
 from aprilslam_amd.localize import TagMap
 from aprilslam_amd.rig import Rig, RigCamera
@@ -89,8 +89,8 @@ def block(tm, rig, poses, tag_size, max_tags, slot_ids=None, pnp_seed=1, image_s
                 if i < 0:
                     k += 1
                     continue
-                hid, own = ZR.tag_half(rec, i, tag_size)
-                obj = np.c_[ZR._object_corners(hid), np.zeros(4)]
+                hid, own = LR.tag_half(rec[i], tag_size)
+                obj = np.c_[LR.half_corners(hid), np.zeros(4)]
                 T = Tcw @ tm[i]
                 P = obj @ T[:3, :3].T + T[:3, 3]
                 uv = LR.project(cam, P) if np.all(P[:, 2] > 1e-3) else np.full((4, 2), -1.0)
@@ -157,7 +157,7 @@ def truth_bar():
     """(the statement's error against the truth on the equal-size scene of truth_case's geometry, the bar: ten times it for
     the different rounding path of a sized map).  Measured with the statement on the CPU, never with the kernels."""
     obs, rec, truths = truth_case(sized=False)
-    base = truth_err(ZR.localize(obs, rec, K, None, TAG), truths)
+    base = truth_err(LR.localize(obs, rec, K, None, TAG), truths)
     return base, 10 * base
 
 
@@ -262,9 +262,8 @@ def smooth_case():
     exact = block(tm, one_camera(), walk(12, 6), TAG, 3, slot_ids=ids)[0]
     rec = tm.as_records()
     obs = noisy(exact, 0.2, 1203)
-    seed = ZR.localize(exact, rec, K, None, TAG)
-    with ZR.honoured(TAG):
-        seed = SC.mirror_seed(SR.problem(obs, rec, K, None, TAG, *SMOOTH_SIGMAS), seed, (4,))
+    seed = LR.localize(exact, rec, K, None, TAG)
+    seed = SC.mirror_seed(SR.problem(obs, rec, K, None, TAG, *SMOOTH_SIGMAS), seed, (4,))
     return obs, rec, seed
 
 
@@ -277,7 +276,7 @@ def smooth_rig_case():
            [[48, 49, 50], [40, 42, 44], [47, 49, 50], [-1, -1, -1], [46, -1, 50], [-1, 43, -1], [40, 43, 46], [-1, -1, -1]]]
     exact = block(tm, rig, walk(8, 8), TAG, 3, slot_ids=ids)
     rec = tm.as_records()
-    return noisy(exact, 0.2, 803), rec, rig, ZR.localize_rig(exact, rec, rig, TAG)
+    return noisy(exact, 0.2, 803), rec, rig, RR.localize(exact, rec, rig, TAG)
 
 
 CALIB_FRAMES = 6      # the fewest frames of a board in calib_cases.cpu_cases (the fronto-parallel board)

@@ -1,6 +1,6 @@
 """Per-tag sizes in the tag map on the device: every solver that takes a map (localisation of one camera and of a rig, their
-covariances, calibration, the sequence solves) against the NumPy statement (tests/sized_ref.py) on the cases of
-tests/sized_cases.py, against the truth, and end to end on rendered frames.
+covariances, calibration, the sequence solves) against its NumPy statement (the size rule: tests/localize_ref.py) on the
+cases of tests/sized_cases.py, against the truth, and end to end on rendered frames.
 
 Bars, taken from the tests of the same comparison over equal-size maps: pose 1e-9 relative, rms 1e-6, counts, statuses and
 seeds identical or of equal score (test_gpu_localize.assert_same, test_gpu_rig); covariance per element 600 eps kappa
@@ -13,7 +13,8 @@ import localize_cases as LC
 import localize_ref as LR
 import rig_ref as RR
 import sized_cases as ZC
-import sized_ref as ZR
+import smooth_cov_ref as SV
+import smooth_ref as SR
 from aprilslam_amd import _lib, synth
 from aprilslam_amd.localize import CAM_POSE_DTYPE, POSE_COV_DTYPE, TagMap
 from solver_checks import assert_cov_close, dev_bytes, rel
@@ -47,8 +48,7 @@ def assert_loc_same(got, want, obs, rec, dist, tag_size=TAG, tol=1e-9, Kc=K):
         assert abs(g["rms_px"] - w["rms_px"]) <= 1e-6 * max(1.0, w["rms_px"])
         assert abs(g["rms_seed_px"] - w["rms_seed_px"]) <= 1e-6 * max(1.0, w["rms_seed_px"])
         if g["seed_slot"] != w["seed_slot"]:
-            with ZR.honoured(tag_size):
-                sc = LR.candidate_scores(LR.OneCamera(LR.camera(Kc, dist)), obs[f], rec, tag_size)
+            sc = LR.candidate_scores(LR.OneCamera(LR.camera(Kc, dist)), obs[f], rec, tag_size)
             assert g["seed_slot"] in sc and abs(sc[g["seed_slot"]] - sc[w["seed_slot"]]) <= 1e-9 * max(1.0, sc[w["seed_slot"]]), (f, g["seed_slot"], w["seed_slot"])
 
 
@@ -58,7 +58,7 @@ def assert_loc_cov(model, frames, rec, out, cov, traces, sigma_px):
         if g["status"] != 0:
             assert c["status"] == 1 and c["dof"] == 0 and c["sigma_px"] == sigma_px and not c["cov"].any(), f
             continue
-        Xw, uv, ci = ZR.frame_points(model, frames[f], rec, TAG, traces[f]["active"])
+        Xw, uv, ci = LR.frame_points(model, frames[f], rec, TAG, traces[f]["active"])
         R = g["T"][:3, :3].T
         t = -(R @ g["T"][:3, 3])
         ref, sig, dof, status = LR.pose_cov(model, R, t, Xw, uv, ci, sigma_px)
@@ -94,7 +94,7 @@ def test_localize_matches_the_statement(gpu_detector, max_tags):
     out, cov = gpu_detector.localize(obs, rec, K, dist, TAG, max_tag_rms_px=ZC.GATE, sigma_px=SIGMA)
     assert out.tobytes() == plain.tobytes()
     traces = []
-    want = ZR.localize(obs, rec, K, dist, TAG, ZC.GATE, traces=traces)
+    want = LR.localize(obs, rec, K, dist, TAG, ZC.GATE, traces=traces)
     print("max_tags %d: T rel_err per frame %s, seeds %s" % (max_tags, ["%.2g" % LC.rel_err(g["T"], w["T"]) for g, w in zip(out, want)],
                                                              out["seed_slot"].tolist()))
     assert_loc_same(out, want, obs, rec, dist)
@@ -110,7 +110,7 @@ def test_rig_matches_the_statement(gpu_detector):
     out, cov = rig.localize(gpu_detector, obs, rec, TAG, 0.0, with_cov=True, sigma_px=SIGMA)
     assert out.tobytes() == plain.tobytes()
     traces = []
-    want = ZR.localize_rig(obs, rec, rig, TAG, 0.0, traces=traces)
+    want = RR.localize(obs, rec, rig, TAG, 0.0, traces=traces)
     for f, (g, w) in enumerate(zip(out, want)):
         print("rig", f, "pose %.2e rms %.2e seed rms %.2e" % (LC.rel_err(g["T"], w["T"]), rel(g["rms_px"], w["rms_px"]), rel(g["rms_seed_px"], w["rms_seed_px"])))
         for field in ("status", "n_tags", "n_rejected", "seed_slot"):
@@ -150,7 +150,7 @@ def test_sequence_solve_matches_the_statement(gpu_detector, huber):
     """12 frames, max_tags 3: frames without a tag, frames of one sized tag alone (candidate B), one seed mirrored"""
     obs, rec, seed = ZC.smooth_case()
     got, gres = gpu_detector.smooth(obs, rec, K, None, TAG, *ZC.SMOOTH_SIGMAS, max_iters=ZC.SMOOTH_ITERS, seed=seed, huber_px=huber)
-    want, wres, _ = ZR.smooth(obs, rec, K, None, TAG, seed, None, *ZC.SMOOTH_SIGMAS, ZC.SMOOTH_ITERS, huber_px=huber)
+    want, wres, _ = SR.smooth(obs, rec, K, None, TAG, seed, *ZC.SMOOTH_SIGMAS, ZC.SMOOTH_ITERS, huber_px=huber)
     assert want["status"].tolist() == [0, 0, 6, 0, 0, 0, 6, 0, 0, 0, 0, 0] and wres["n_flipped"] >= 1
     assert (wres["n_soft"] > 0) == (huber > 0)
     assert_smooth_same("smooth huber %g" % huber, got, gres, want, wres)
@@ -161,7 +161,7 @@ def test_sequence_solve_with_covariance(gpu_detector):
     plain, pres = gpu_detector.smooth(obs, rec, K, None, TAG, *ZC.SMOOTH_SIGMAS, max_iters=ZC.SMOOTH_ITERS, seed=seed)
     out, res, cov = gpu_detector.smooth(obs, rec, K, None, TAG, *ZC.SMOOTH_SIGMAS, max_iters=ZC.SMOOTH_ITERS, seed=seed, with_cov=True)
     assert out.tobytes() == plain.tobytes() and res.tobytes() == pres.tobytes()
-    want, A = ZR.smooth_cov(obs, rec, K, None, TAG, out, res, None, *ZC.SMOOTH_SIGMAS)
+    want, A = SV.smooth_cov(obs, rec, K, None, TAG, out, res, *ZC.SMOOTH_SIGMAS)
     assert res["status"] == 0 and (want["status"] == 0).all()
     for k in ("status", "dof", "sigma_px"):
         assert np.array_equal(cov[k], want[k]), (k, cov[k], want[k])
@@ -173,7 +173,7 @@ def test_rig_sequence_solve_matches_the_statement(gpu_detector):
     """2 cameras x 8 frames"""
     obs, rec, rig, seed = ZC.smooth_rig_case()
     got, gres = gpu_detector.smooth_rig(obs, rec, rig, TAG, *ZC.SMOOTH_SIGMAS, max_iters=ZC.SMOOTH_ITERS, seed=seed)
-    want, wres, _ = ZR.smooth_rig(obs, rec, rig, TAG, seed, *ZC.SMOOTH_SIGMAS, ZC.SMOOTH_ITERS)
+    want, wres, _ = SR.smooth_rig(obs, rec, rig, TAG, seed, *ZC.SMOOTH_SIGMAS, ZC.SMOOTH_ITERS)
     assert want["status"].tolist() == [0, 0, 0, 6, 0, 0, 0, 0]
     assert_smooth_same("smooth rig", got, gres, want, wres)
 
@@ -182,9 +182,10 @@ def test_rig_sequence_solve_matches_the_statement(gpu_detector):
 def test_calibration_matches_the_statement(gpu_detector, n_dist):
     """a board of two tag sizes, 6 frames; the fields and bars of test_gpu_calibrate.assert_same at its 1e-9"""
     import calib_cases as CC
+    import calib_ref as CR
     obs, rec = ZC.calib_case(n_dist)
     got = gpu_detector.calibrate(obs, rec, TAG, CC.W, CC.H, n_dist=n_dist)
-    want = ZR.calibrate(obs, rec, TAG, CC.W, CC.H, n_dist=n_dist)
+    want = CR.calibrate(obs, rec, TAG, CC.W, CC.H, n_dist=n_dist)
     print("calibration n_dist %d: K %s rms %.3g" % (n_dist, got[0]["K"].ravel()[[0, 4, 2, 5]], got[0]["rms_px"]))
     assert want[0]["status"] == 0 and want[0]["rms_px"] < 1e-3        # the two sizes are honoured: exact corners fit
     (gr, gp), (wr, wp), tol = got, want, 1e-9
@@ -260,7 +261,7 @@ def test_bad_size_is_an_unmapped_entry(gpu_detector, bad):
     assert got[0]["status"][4] == 1 and got[0]["status"][0] == 0 and got[0]["n_tags"][0] == 1 and got[0]["status"][1] == 2
     devf = localize_device(gpu_detector, obs, a, dist, TAG, sigma_px=SIGMA)
     assert devf[0].tobytes() == got[0].tobytes() and devf[1].tobytes() == got[1].tobytes()
-    assert_loc_same(got[0], ZR.localize(obs, a, K, dist, TAG), obs, a, dist)
+    assert_loc_same(got[0], LR.localize(obs, a, K, dist, TAG), obs, a, dist)
     # the other solvers share the rule: the rig form and the sequence solve
     robs, rrec, rig = ZC.rig_case()
     a, b = rrec.copy(), rrec.copy()
@@ -294,7 +295,7 @@ def test_uniform_size_is_the_call_size_on_the_device(gpu_detector):
     print("uniform on the device: T rel_err %.3g, identical bytes: %s" % (worst, got.tobytes() == want.tobytes()))
     assert (got["status"] == 0).all() and (got["n_tags"] == 4).all() and np.array_equal(got["n_tags"], want["n_tags"])
     assert worst <= 1e-9, worst
-    assert_loc_same(got, ZR.localize(a, rec_a, K, None, s1), a, rec_a, None, tag_size=s1)
+    assert_loc_same(got, LR.localize(a, rec_a, K, None, s1), a, rec_a, None, tag_size=s1)
 
 
 # ---- 6: end to end on rendered frames
@@ -371,10 +372,10 @@ def test_end_to_end_with_two_tag_sizes():
     assert rec["size"].tolist() == [0, 7.5, 0, 7.5, 0] and not rec0["size"].any()
     assert (out["status"] == 0).all() and (out["n_tags"] >= 4).all() and (out0["n_tags"] >= 4).all()
     assert all(np.isin([1, 3], row["id"]).any() for row in obs)          # every frame sees a sized tag
-    want = ZR.localize(obs, rec, Kc, None, TAG)
+    want = LR.localize(obs, rec, Kc, None, TAG)
     assert_loc_same(out, want, obs, rec, None, tol=1e-7, Kc=Kc)
     (rot, tr), (rot0, tr0) = e2e_errors(out, cams), e2e_errors(out0, cams)
-    blind = e2e_errors(ZR.localize(obs, ZC.without_sizes(rec), Kc, None, TAG), cams)
+    blind = e2e_errors(LR.localize(obs, ZC.without_sizes(rec), Kc, None, TAG), cams)
     print("two sizes: rot %.3g rad, trans %.3g; common size: rot %.3g rad, trans %.3g; ratios %.3g %.3g; sizes dropped: rot %.3g trans %.3g"
           % (rot, tr, rot0, tr0, rot / rot0, tr / tr0, blind[0], blind[1]))
     assert rot <= E2E_MARGIN * rot0 and tr <= E2E_MARGIN * tr0, (rot, rot0, tr, tr0)

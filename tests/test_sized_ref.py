@@ -1,5 +1,5 @@
 """Per-tag sizes in the tag map on the CPU: the ABI field, TagMap's handling of sizes, and the NumPy statement
-(tests/sized_ref.py) against the existing statements, against the truth and against itself."""
+(the size rule of tests/localize_ref.py) against the truth and against itself."""
 import os
 import re
 
@@ -9,9 +9,7 @@ import pytest
 import localize_cases as LC
 import localize_ref as LR
 import rig_cases as RC
-import rig_ref as RR
 import sized_cases as ZC
-import sized_ref as ZR
 from aprilslam_amd import _lib
 from aprilslam_amd.localize import TagMap
 
@@ -77,42 +75,12 @@ def test_tag_pose_is_the_seed_rule():
     assert np.array_equal(tm.tag_pose(0, T, 10.0), T)
     S = tm.tag_pose(1, T[:3], 10.0)
     assert S.shape == (4, 4) and np.array_equal(S[:3, :3], T[:3, :3]) and np.array_equal(S[:3, 3], T[:3, 3] * 2.5)
-    assert np.array_equal(ZR.tag_pose(tm.as_records(), 1, T, 10.0), S[:3])
+    rec = tm.as_records()
+    for i in (0, 1):
+        assert np.array_equal(LR.seed_translation(T[:3, 3], *LR.tag_half(rec[i], 10.0), 10.0), tm.tag_pose(i, T, 10.0)[:3, 3])
 
 
-# ---- 3: with every size 0 the new statement is the existing one, byte for byte
-
-@pytest.mark.parametrize("case", ["exact", "mirrored", "gate", "slots", "dist5"])
-def test_no_sizes_is_localize_ref(case):
-    name, obs, rec, dist, gate = [c for c in LC.cpu_cases(ZC.K) if c[0] == case][0]
-    assert not rec["size"].any()
-    want, wcov = LR.localize(obs, rec, ZC.K, dist, LC.TAG_INNER, gate, sigma_px=ZC.SIGMA)
-    got, gcov = ZR.localize(obs, rec, ZC.K, dist, LC.TAG_INNER, gate, sigma_px=ZC.SIGMA)
-    assert got.tobytes() == want.tobytes() and gcov.tobytes() == wcov.tobytes()
-    assert LR.gather is not ZR.gather                    # the existing statement is back in place
-
-
-def test_no_sizes_is_rig_ref():
-    c = RC.case("back_to_back")
-    want = RR.localize(c["obs"], c["rec"], c["rig"], c["tag_size"], c["gate"], sigma_px=ZC.SIGMA)
-    got = ZR.localize_rig(c["obs"], c["rec"], c["rig"], c["tag_size"], c["gate"], sigma_px=ZC.SIGMA)
-    assert got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes()
-
-
-def test_no_sizes_is_smooth_ref_and_calib_ref():
-    import calib_cases as CC
-    import calib_ref as CR
-    import smooth_cases as SC
-    import smooth_ref as SR
-    obs, rec, seed, dist = SC.shape(5, 4, 0)
-    want = SR.smooth(obs, rec, SC.K, dist, SC.TAG, seed, *SC.SHAPE_SIGMAS, SC.COMPARE_ITERS)
-    got = ZR.smooth(obs, rec, SC.K, dist, SC.TAG, seed, None, *SC.SHAPE_SIGMAS, SC.COMPARE_ITERS)
-    assert got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes()
-    bd, brec, _ = CC.board_case(n=6, fronto=True)
-    want = CR.calibrate(bd, brec, LC.TAG_INNER, CC.W, CC.H, n_dist=0, max_iters=4)
-    got = ZR.calibrate(bd, brec, LC.TAG_INNER, CC.W, CC.H, n_dist=0, max_iters=4)
-    assert got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes()
-
+# ---- 3: with every size 0 the statements return what they returned before they honoured sizes: tests/test_localize_statement_golden.py
 
 # ---- 4: the truth
 
@@ -125,9 +93,9 @@ def test_statement_recovers_the_truth_on_a_mixed_size_scene():
     base, bar = ZC.truth_bar()
     obs, rec, truths = ZC.truth_case()
     assert rec["size"].tolist() == [0, 0, 0, 0, 0, 20.0] and obs.shape == (6, 4) and (obs["id"][:, 3] == 5).all()
-    got = ZR.localize(obs, rec, ZC.K, None, ZC.TAG)
+    got = LR.localize(obs, rec, ZC.K, None, ZC.TAG)
     err = ZC.truth_err(got, truths)
-    blind = ZC.truth_err(ZR.localize(obs, ZC.without_sizes(rec), ZC.K, None, ZC.TAG), truths)
+    blind = ZC.truth_err(LR.localize(obs, ZC.without_sizes(rec), ZC.K, None, ZC.TAG), truths)
     print("equal-size %.3g bar %.3g mixed %.3g sizes dropped %.3g (%.3g bars)" % (base, bar, err, blind, blind / bar))
     assert (got["status"] == 0).all() and (got["n_tags"] == 4).all()
     assert 0 < base < 1e-4                               # the equal-size scene itself is solved
@@ -144,7 +112,7 @@ def test_statement_on_the_kernel_cases_does_what_they_are_for():
     for mt in ZC.LOC_MAX_TAGS:
         obs, rec, dist, notes = ZC.loc_case(mt)
         traces = []
-        want = ZR.localize(obs, rec, ZC.K, dist, ZC.TAG, ZC.GATE, traces=traces)
+        want = LR.localize(obs, rec, ZC.K, dist, ZC.TAG, ZC.GATE, traces=traces)
         assert want["seed_slot"][1] in notes[1] and want["seed_slot"][2] - LR.MIRRORED in notes[2], (mt, want["seed_slot"])
         if mt >= 2:
             assert traces[3]["dropped"] == notes[3] and want["n_rejected"][3] == 1
@@ -165,7 +133,7 @@ def test_bad_sizes_are_unmapped_in_the_statement():
         a, b = rec.copy(), rec.copy()
         a["size"][1] = bad
         b["valid"][1] = 0
-        got, want = ZR.localize(obs, a, ZC.K, dist, ZC.TAG), ZR.localize(obs, b, ZC.K, dist, ZC.TAG)
+        got, want = LR.localize(obs, a, ZC.K, dist, ZC.TAG), LR.localize(obs, b, ZC.K, dist, ZC.TAG)
         assert got.tobytes() == want.tobytes() and got["n_tags"][0] == 1 and got["status"][1] == 2
 
 
@@ -175,8 +143,8 @@ def test_uniform_size_is_the_call_size():
     s1, s2 = 10.0, 25.0
     (a, rec_a), (b, rec_b) = ZC.uniform_case(s1, s2)
     assert (rec_a["size"] == s2).all() and not rec_b["size"].any()
-    got = ZR.localize(a, rec_a, ZC.K, None, s1)
-    want = ZR.localize(b, rec_b, ZC.K, None, s2)
+    got = LR.localize(a, rec_a, ZC.K, None, s1)
+    want = LR.localize(b, rec_b, ZC.K, None, s2)
     worst = max(LC.rel_err(g["T"], w["T"]) for g, w in zip(got, want))
     print("uniform: T rel_err %.3g" % worst)
     assert np.array_equal(got["seed_slot"], want["seed_slot"]) and (got["status"] == 0).all() and (got["n_tags"] == 4).all()

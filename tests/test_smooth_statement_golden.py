@@ -1,5 +1,5 @@
-"""The one NumPy statement of the sequence localisation (tests/smooth_ref.py, with tests/smooth_cov_ref.py and the fronts of
-tests/sized_ref.py over it) against what the statements it replaced (smooth_ref, its timed and rig copies, smooth_cov_ref)
+"""The one NumPy statement of the sequence localisation (tests/smooth_ref.py, with tests/smooth_cov_ref.py; per-tag sizes
+through tests/localize_ref.py) against what the statements it replaced (smooth_ref, its timed and rig copies, smooth_cov_ref)
 returned at the last commit that had them, recorded in tests/golden/smooth_statements.npz by
 tests/golden/make_smooth_statement_fixtures.py: the cases of the device comparisons and of the CPU statement tests, at their
 huber_px and max_iters, plain and reversed.  The recorder's runs() is the list of calls and its compare() the comparison:
