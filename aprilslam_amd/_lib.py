@@ -59,7 +59,7 @@ EXPORTS = [
     "asl_smooth_sequences_device", "asl_smooth_sequences_batch", "asl_smooth_robust_sequences_device", "asl_smooth_robust_sequences_batch",
     "asl_smooth_timed_sequences_device", "asl_smooth_timed_sequences_batch",
     "asl_smooth_rig_sequences_device", "asl_smooth_rig_sequences_batch",
-    "asl_locate_tags_frames_device", "asl_locate_tags_batch",
+    "asl_locate_tags_frames_device", "asl_locate_tags_batch", "asl_locate_tags_rig_frames_device", "asl_locate_tags_rig_batch",
     "asl_debug_fetch", "asl_debug_refit", "asl_debug_dedup", "asl_debug_gn_cholesky", "asl_debug_gn_step", "asl_debug_division_check", "asl_stage_times", "asl_set_profiling", "asl_debug_phase_cycles",
 ]
 
@@ -246,6 +246,9 @@ def load():
     locate = [vp] + obs_block + [vp] + tag_map + camera + [dbl, i32, dbl, vp, vp]    # ..., poses, map, n_ids, camera, gate, min_views, sigma_px, fit, cov
     L.asl_locate_tags_frames_device.argtypes = locate + [vp]
     L.asl_locate_tags_batch.argtypes = locate
+    locate_rig = [vp, vp, i32, i32, i32] + locate[4:7] + [vp, dbl] + locate[11:]    # detector, obs, n_cams, n_frames, max_tags, poses, map, n_ids, rig, tag_size, ...
+    L.asl_locate_tags_rig_frames_device.argtypes = locate_rig + [vp]
+    L.asl_locate_tags_rig_batch.argtypes = locate_rig
     L.asl_debug_fetch.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.asl_debug_refit.argtypes = [vp, i32, vp, C.c_size_t]
     L.asl_debug_dedup.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, C.c_size_t]
@@ -645,6 +648,39 @@ class Detector:
         check(self._L.asl_locate_tags_frames_device(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(poses_ptr), _ptr(map_ptr), int(n_ids),
                                                     Kp, dpp, nd, float(tag_size), float(max_view_rms_px), int(min_views), float(sigma_px),
                                                     _ptr(fit_ptr), _opt_ptr(cov_ptr), _ptr(stream)))
+
+    def locate_tags_rig(self, obs, poses, tag_map, rig, tag_size, max_view_rms_px=0.0, min_views=2, sigma_px=None):
+        """asl_locate_tags_rig_batch: locate_tags for a rig.  Host records obs (n_cams, n_frames, max_tags) OBS_DTYPE,
+        camera-major, the frames' poses (n_frames,) CAM_POSE_DTYPE with T = world<-rig (what localize_rig, smooth_rig or
+        build_map_rig return), a map block (or a localize.TagMap) and the camera table rig ((n_cams,) RIG_CAMERA_DTYPE, or a
+        rig.Rig) -> (the extended map, (n_ids,) TAG_FIT_DTYPE, (n_ids,) POSE_COV_DTYPE or None).  Every camera's view of a
+        tag in a frame is a view of its own, through that camera's model and mounting.  The caller's block is not modified."""
+        o = np.ascontiguousarray(obs, dtype=OBS_DTYPE)
+        if o.ndim != 3:
+            raise ValueError("obs must be (n_cams, n_frames, max_tags) asl_obs records")
+        m, r = _map_records(tag_map).copy(), _rig_records(rig)
+        if len(r) != o.shape[0]:
+            raise ValueError("the rig has %d cameras, obs has %d" % (len(r), o.shape[0]))
+        p = np.ascontiguousarray(poses, dtype=CAM_POSE_DTYPE).ravel()
+        if len(p) != o.shape[1]:
+            raise ValueError("one pose per frame: obs has %d frames, poses %d" % (o.shape[1], len(p)))
+        fit = np.zeros(len(m), dtype=TAG_FIT_DTYPE)
+        cov = np.zeros(len(m), dtype=POSE_COV_DTYPE) if sigma_px is not None else None
+        none = np.zeros(1, dtype=CAM_POSE_DTYPE)   # no frame: the block and the poses are never read, but must not be NULL
+        check(self._L.asl_locate_tags_rig_batch(self._h, _data(o) or none.ctypes.data, o.shape[0], o.shape[1], o.shape[2],
+                                                _data(p) or none.ctypes.data, _data(m), len(m), _data(r), float(tag_size), float(max_view_rms_px),
+                                                int(min_views), float(sigma_px or 0.0), _data(fit), None if cov is None else _data(cov)))
+        return m, fit, cov
+
+    def locate_tags_rig_device(self, obs_ptr, n_cams, n_frames, max_tags, poses_ptr, map_ptr, n_ids, rig_ptr, fit_ptr, tag_size,
+                               max_view_rms_px=0.0, min_views=2, stream=0, cov_ptr=None, sigma_px=0.0):
+        """asl_locate_tags_rig_frames_device: obs_ptr (n_cams x n_frames x max_tags asl_obs, camera-major), poses_ptr (n_frames
+        asl_cam_pose, world<-rig), map_ptr (n_ids asl_map_tag, read and written in place), rig_ptr (n_cams asl_rig_camera,
+        complete when the call is made), fit_ptr (n_ids asl_tag_fit) and cov_ptr (n_ids asl_pose_cov, or None) are device
+        addresses; enqueued on `stream`, no wait."""
+        check(self._L.asl_locate_tags_rig_frames_device(self._h, _ptr(obs_ptr), int(n_cams), int(n_frames), int(max_tags), _ptr(poses_ptr),
+                                                        _ptr(map_ptr), int(n_ids), _ptr(rig_ptr), float(tag_size), float(max_view_rms_px),
+                                                        int(min_views), float(sigma_px), _ptr(fit_ptr), _opt_ptr(cov_ptr), _ptr(stream)))
 
     def pose_cov(self, corners, T, K, dist, tag_size, sigma_px=0.0):
         """asl_solve_pnp_cov_batch: the covariance of the camera<-tag poses T (N, 4, 4) that solve_pnp returned for corners

@@ -4,14 +4,17 @@
 // optimum: the frame poses are taken as exact, as localisation takes the map as exact.
 //   wanted  id i is solved for if its map entry has valid == 0 and a size that is >= 0 and finite (> 0: the tag's own side,
 //           0: the call's tag_size; map_tag_half's rule).  Every other id gets status 1 and keeps its entry's bytes.
-//   views   frame f takes part if poses[f].status is 0 or 6 and rows 0..2 of its T are finite; the first slot of such a
-//           frame with flags & 1 and id == i is the tag's view there.  C_f = inv(T_f) = camera<-world.
+//   views   frame f takes part if poses[f].status is 0 or 6 and rows 0..2 of its T are finite; in such a frame every camera
+//           c of the camera-major block obs[n_cams][n_frames][max_tags] gives at most one view of the tag, its first slot
+//           with flags & 1 and id == i (one camera: n_cams = 1, the frame's view).  C = camera<-world of the view.
 //   mark    k_locate_mark, one thread per slot: seen[id] = 1 for a wanted id with a view (every writer stores the same 1)
-//   count   k_locate_count, one wavefront per seen id: the frames 64 at a time, lane = frame, ballot and popcount
+//   count   k_locate_count, one wavefront per seen id: the frames 64 at a time, lane = frame with its 0..n_cams views, a
+//           wave sum
 //   scan    k_locate_scan, one workgroup: ptr[n_ids + 1], the exclusive prefix of the counts (map_scan)
-//   solve   k_locate_solve, one wavefront per id: fills its segment of the view list with frame * max_tags + slot in frame
-//           order, then, corner 4 * view + q on lane % 64 and every sum a butterfly sum (the serial parts run redundantly
-//           in all lanes on identical inputs, as in k_localize.inc):
+//   solve   one wavefront per id: fills its segment of the view list with frame * (n_cams * max_tags) + camera * max_tags +
+//           slot in (frame, camera) order, each lane its frame's entries at the wave's exclusive prefix, then, corner
+//           4 * view + q on lane % 64 and every sum a butterfly sum (the serial parts run redundantly in all lanes on
+//           identical inputs, as in k_localize.inc):
 //     seed    the <= 8 active views with flags & 2 of largest corner area (ties: lower list position), in list order, plain
 //             before mirrored: G = inv(C_f) T_obs, a sized tag's PnP translation first times h_id / half, the mirror formed
 //             in the camera frame; the strictly lowest total cost over ALL active views wins
@@ -22,8 +25,15 @@
 //             can pull a tag into its mirrored minimum, and from there the LM does not come back.)
 //     cov     k_locate_solve<true>: one more linearisation at the pose written, lane c solves column c of
 //             sigma^2 (J^T J)^-1 in the (r, d) convention of world<-tag (pose_cov_column_dev<false>); dof = 8 n_views - 6
-// A view's C_f and corners are read from global memory in every pass (latency-bound scalar float64, not bytes).  No atomics,
+// A view's C and corners are read from global memory in every pass (latency-bound scalar float64, not bytes).  No atomics,
 // no host wait between the kernels: the same input gives the same bytes.  tests/locate_ref.py is the NumPy statement.
+// The solve is one body, locate_solve_tag, over a view model, as loc_solve_frame is over LocOne / LocRig:
+//   LocateOne  k_locate_solve: the frames' poses are world<-camera, C = inv(T_f), one CamDev in registers; no LDS
+//   LocateRig  k_locate_solve_rig (asl_locate_tags_rig_*): the poses are world<-rig and camera c is mounted at E_c =
+//              camera_c<-rig, C = E_c inv(T_f) = (Re R, Re t + te) formed where it is used; the camera table lies in LDS
+//              (rig_fill_cams, published by a barrier) and a view's CamDev is built from its record there, so that no
+//              per-camera choice becomes a run-time-indexed register array.  Seeding areas are pixels as they are.  A rig
+//              of one camera with E = I is LocateOne: Re = I multiplies exactly.  tests/locate_rig_ref.py is its statement.
 
 struct TagFitRec {  // == asl_tag_fit, 40 bytes
     double rms_px, rms_seed_px;
@@ -31,14 +41,15 @@ struct TagFitRec {  // == asl_tag_fit, 40 bytes
 };
 
 struct LocateArgs {
-    const ObsRec *obs;
-    int n_frames, max_tags;
+    const ObsRec *obs;  // [n_cams][n_frames][max_tags]; one camera: n_cams = 1
+    int n_cams, n_frames, max_tags;
     const CamPoseRec *poses;
     MapTagRec *map;  // in / out
     int n_ids;
     int *seen, *cnt;  // per id
     int *ptr;         // n_ids + 1
-    int *views;       // <= n_frames * max_tags: frame * max_tags + slot, by id, in frame order
+    int *views;       // <= n_cams * n_frames * max_tags: frame * (n_cams * max_tags) + camera * max_tags + slot, by id, in
+                      // (frame, camera) order
 };
 
 // Id wanted: valid == 0 and a size map_tag_half accepts; h: the tag's half side (comes in as the call's)
@@ -60,24 +71,48 @@ __device__ __forceinline__ bool locate_frame_ok(const CamPoseRec &p)
     return fin;
 }
 
-// the slot of id's view in frame f, -1 without one
-__device__ __forceinline__ int locate_view_slot(const LocateArgs &a, int f, int id)
+// the slot of id's view in camera c's records of frame f (a frame that takes part), -1 without one
+__device__ __forceinline__ int locate_view_slot(const LocateArgs &a, int f, int c, int id)
 {
-    if (!locate_frame_ok(a.poses[f])) return -1;
-    const ObsRec *fo = a.obs + (size_t)f * a.max_tags;
+    const ObsRec *fo = a.obs + ((size_t)c * a.n_frames + f) * a.max_tags;
     for (int s = 0; s < a.max_tags; s++)
         if ((fo[s].flags & 1) && fo[s].id == id) return s;
     return -1;
 }
 
+// The views of id in frame f, one per camera at most: their number, the cameras as a bit mask, camera c's slot in byte c of
+// (lo, hi) (a slot is below 256; two words chosen by a compare, not an array indexed by c)
+struct LocateFrameViews {
+    unsigned long long lo, hi;
+    unsigned int cams;
+    int n;
+    __device__ __forceinline__ int slot(int c) const { return (int)(((c < 8 ? lo : hi) >> (8 * (c & 7))) & 255ull); }
+};
+
+__device__ __forceinline__ LocateFrameViews locate_frame_views(const LocateArgs &a, int f, int id)
+{
+    LocateFrameViews v{0ull, 0ull, 0u, 0};
+    if (f >= a.n_frames || !locate_frame_ok(a.poses[f])) return v;
+    for (int c = 0; c < a.n_cams; c++) {
+        const int s = locate_view_slot(a, f, c, id);
+        if (s < 0) continue;
+        const unsigned long long b = (unsigned long long)s << (8 * (c & 7));
+        if (c < 8) v.lo |= b;
+        else v.hi |= b;
+        v.cams |= 1u << c;
+        v.n++;
+    }
+    return v;
+}
+
 __global__ void __launch_bounds__(256) k_locate_mark(LocateArgs a)
 {
     const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= (size_t)a.n_frames * (size_t)a.max_tags) return;
+    if (k >= (size_t)a.n_cams * (size_t)a.n_frames * (size_t)a.max_tags) return;
     const int id = a.obs[k].id;
     if (!(a.obs[k].flags & 1) || id < 0 || id >= a.n_ids) return;
     double h = 0;
-    if (!locate_wanted(a.map[id], h) || !locate_frame_ok(a.poses[k / (size_t)a.max_tags])) return;
+    if (!locate_wanted(a.map[id], h) || !locate_frame_ok(a.poses[(k / (size_t)a.max_tags) % (size_t)a.n_frames])) return;
     a.seen[id] = 1;
 }
 
@@ -87,8 +122,9 @@ __global__ void __launch_bounds__(64) k_locate_count(LocateArgs a)
     int n = 0;
     if (a.seen[i]) {
         for (int f0 = 0; f0 < a.n_frames; f0 += ASL_WAVE) {
-            const int f = f0 + lane;
-            n += __popcll(__ballot(f < a.n_frames && locate_view_slot(a, f, i) >= 0));
+            int tot;
+            wave_prefix_sum(locate_frame_views(a, f0 + lane, i).n, &tot);
+            n += tot;
         }
     }
     if (lane == 0) a.cnt[i] = n;
@@ -100,15 +136,56 @@ __global__ void __launch_bounds__(MAP_WG) k_locate_scan(LocateArgs a)
     map_scan(a.n_ids, [&](int i) { return a.cnt[i]; }, s_part, a.ptr);
 }
 
-// camera<-world of view entry e (R row-major 9, t 3): the inverse of the frame's world<-camera, formed from the record
-__device__ __forceinline__ void locate_view_cam(const LocateArgs &a, int e, double *C)
+// inv(T_f) of frame f (R row-major 9, t 3), formed from the record: camera<-world of one camera, rig<-world of a rig
+__device__ __forceinline__ void locate_frame_inv(const LocateArgs &a, int f, double *C)
 {
-    const double *T = a.poses[e / a.max_tags].T;
+    const double *T = a.poses[f].T;
     double W[12];
 #pragma unroll
     for (int r = 0; r < 3; r++) { W[3 * r] = T[4 * r]; W[3 * r + 1] = T[4 * r + 1]; W[3 * r + 2] = T[4 * r + 2]; W[9 + r] = T[4 * r + 3]; }
     pk_inv(W, C);
 }
+
+// A view entry taken apart: its frame, its record and (a rig) its camera's LDS record
+struct LocateView {
+    int frame;
+    const ObsRec *rec;
+    const double *cl;
+};
+
+// The view model of one camera: entry e is record e of the block, every view goes through the one CamDev
+struct LocateOne {
+    CamDev cam;
+    __device__ __forceinline__ LocateView view(const LocateArgs &a, int e) const { return {e / a.max_tags, a.obs + e, nullptr}; }
+    __device__ __forceinline__ void view_cam(const LocateArgs &a, const LocateView &v, double *C) const { locate_frame_inv(a, v.frame, C); }
+    __device__ __forceinline__ CamDev cam_of(const LocateView &) const { return cam; }
+};
+
+// The view model of a rig: entry e = f * (n_cams * max_tags) + g with the global slot g = c * max_tags + s of k_rig.inc,
+// the record obs[c][f][s], camera<-world C = E_c inv(T_f) (LocRig::camera_pose's formula) and the CamDev of camera c's LDS
+// record (rig_cam_dev)
+struct LocateRig {
+    const double *cams;  // LDS: RIG_CAM_DOUBLES per camera
+    unsigned int magic;
+    __device__ __forceinline__ LocateView view(const LocateArgs &a, int e) const
+    {
+        const int ns = a.n_cams * a.max_tags, f = e / ns, g = e - f * ns, c = rig_cam_of(g, magic);
+        return {f, a.obs + ((size_t)c * a.n_frames + f) * a.max_tags + (g - c * a.max_tags), cams + RIG_CAM_DOUBLES * c};
+    }
+    __device__ __forceinline__ void view_cam(const LocateArgs &a, const LocateView &v, double *C) const
+    {
+        const double *Re = v.cl + 9, *te = v.cl + 18;
+        double W[12];
+        locate_frame_inv(a, v.frame, W);
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) C[3 * i + k] = Re[3 * i] * W[k] + Re[3 * i + 1] * W[3 + k] + Re[3 * i + 2] * W[6 + k];
+            C[9 + i] = Re[3 * i] * W[9] + Re[3 * i + 1] * W[10] + Re[3 * i + 2] * W[11] + te[i];
+        }
+    }
+    __device__ __forceinline__ CamDev cam_of(const LocateView &v) const { return rig_cam_dev(v.cl); }
+};
 
 // Squared pixel error of corner q of a tag of half side h at world<-tag (R, t), seen through camera<-world C at cf; with NE
 // its rows of d uv / d (w, v) = J_proj R_C [-[X_w]x | I] are added to acc (map_tag_pass's formula)
@@ -166,8 +243,8 @@ struct LocateDrops {
 
 // Total corner cost of world<-tag (R, t) over the active views of the n at list offset b, identical in every lane; with NE
 // also the normal equations of the tag's left update (packed lower triangle 21, then J^T r 6)
-template <bool NE>
-__device__ __forceinline__ double locate_pass(const LocateArgs &a, const CamDev &cam, double h, int b, int n, const LocateDrops &drops,
+template <bool NE, class M>
+__device__ __forceinline__ double locate_pass(const M &m, const LocateArgs &a, double h, int b, int n, const LocateDrops &drops,
                                               const double *R, const double *t, int lane, double *ne)
 {
     double cost = 0, acc[27];
@@ -176,10 +253,10 @@ __device__ __forceinline__ double locate_pass(const LocateArgs &a, const CamDev 
     for (int k = lane; k < 4 * n; k += ASL_WAVE) {
         const int o = k >> 2;
         if (drops.has(o)) continue;
-        const int e = a.views[b + o];
+        const LocateView v = m.view(a, a.views[b + o]);
         double C[12];
-        locate_view_cam(a, e, C);
-        cost += locate_corner<NE>(cam, C, a.obs[e].corners, h, R, t, k & 3, acc);
+        m.view_cam(a, v, C);
+        cost += locate_corner<NE>(m.cam_of(v), C, v.rec->corners, h, R, t, k & 3, acc);
     }
     if constexpr (NE) {
 #pragma unroll
@@ -198,27 +275,29 @@ __device__ __forceinline__ void locate_write_none(TagFitRec *o, PoseCovRec *oc, 
     if (oc) loc_cov_write_none(oc, sigma_px, lane);
 }
 
-// One wavefront per id; COV: also cov[id], which the plain instantiation never touches
-template <bool COV>
-__global__ void __launch_bounds__(64) k_locate_solve(LocateArgs a, CamDev cam, double gate, int min_views, TagFitRec *__restrict__ fit,
-                                                     PoseCovRec *__restrict__ cov, double sigma_px)
+// One id's solve by one wavefront over the view model vm (LocateOne, LocateRig): the one copy of list fill, seed, refine,
+// gate and covariance.  half: the call's tag_size / 2.  COV: also *oc, which the plain instantiations never touch
+template <bool COV, class M>
+__device__ __forceinline__ void locate_solve_tag(const M &vm, const LocateArgs &a, int i, double half, double gate, int min_views, TagFitRec *o,
+                                                 PoseCovRec *oc, double sigma_px, int lane)
 {
-    const int i = blockIdx.x, lane = threadIdx.x;
-    TagFitRec *o = fit + i;
-    PoseCovRec *oc = COV ? cov + i : nullptr;
-    double h = cam.half;
+    double h = half;
     if (!locate_wanted(a.map[i], h)) { locate_write_none(o, oc, sigma_px, 1, 0, lane); return; }
 
-    // the view list of this id, in frame order, then visible to the whole wave
+    // the view list of this id, in (frame, camera) order, then visible to the whole wave
     const int b = a.ptr[i], cap = a.ptr[i + 1] - b;
     int n = 0;
     if (a.seen[i]) {
         for (int f0 = 0; f0 < a.n_frames; f0 += ASL_WAVE) {
-            const int f = f0 + lane, s = f < a.n_frames ? locate_view_slot(a, f, i) : -1;
-            const unsigned long long m = __ballot(s >= 0);
-            const int pos = n + __popcll(m & ((1ull << lane) - 1ull));
-            if (s >= 0 && pos < cap) a.views[b + pos] = f * a.max_tags + s;  // cap: what k_locate_count found
-            n += __popcll(m);
+            const int f = f0 + lane;
+            const LocateFrameViews fv = locate_frame_views(a, f, i);
+            int tot, pos = n + wave_prefix_sum(fv.n, &tot);
+            for (int c = 0; c < a.n_cams; c++) {
+                if (!((fv.cams >> c) & 1u)) continue;
+                if (pos < cap) a.views[b + pos] = (f * a.n_cams + c) * a.max_tags + fv.slot(c);  // cap: what k_locate_count found
+                pos++;
+            }
+            n += tot;
         }
         n = min(n, cap);
         // the list goes back through this CU's L1, which may hold a neighbouring id's part of a line from before the
@@ -229,14 +308,14 @@ __global__ void __launch_bounds__(64) k_locate_solve(LocateArgs a, CamDev cam, d
     }
     if (n < min_views) { locate_write_none(o, oc, sigma_px, 2, n, lane); return; }
 
-    const double ks = map_seed_scale(h, cam.half);
+    const double ks = map_seed_scale(h, half);
     LocateDrops drops;
 #pragma unroll
     for (int r = 0; r < LOC_MAX_GATE_DROPS; r++) drops.o[r] = -1;
     auto pass = [&](const double *R, const double *t, auto ne_tag, double *ne) {
-        return locate_pass<decltype(ne_tag)::value>(a, cam, h, b, n, drops, R, t, lane, ne);
+        return locate_pass<decltype(ne_tag)::value>(vm, a, h, b, n, drops, R, t, lane, ne);
     };
-    auto score = [&](const double *P) { return locate_pass<false>(a, cam, h, b, n, drops, P, P + 9, lane, nullptr); };
+    auto score = [&](const double *P) { return locate_pass<false>(vm, a, h, b, n, drops, P, P + 9, lane, nullptr); };
 
     double P[12], cost = 0, best = INFINITY, best_first = 0;
     int nused = n, nrej = 0, seed_frame = -1, seed_mirrored = 0;
@@ -247,8 +326,8 @@ __global__ void __launch_bounds__(64) k_locate_solve(LocateArgs a, CamDev cam, d
         int sel[LOC_MAX_SEEDS];
         const int nsel = loc_top_k(n, lane, [&](int v) {
             if (drops.has(v)) return -1.0;
-            const ObsRec &rec = a.obs[a.views[b + v]];
-            return (rec.flags & 2) ? loc_area(rec.corners) : -1.0;
+            const ObsRec *rec = vm.view(a, a.views[b + v]).rec;
+            return (rec->flags & 2) ? loc_area(rec->corners) : -1.0;
         }, sel);
         int won = -1, wm = 0, prev = -1;
         for (int j = 0; j < nsel; j++) {
@@ -257,13 +336,13 @@ __global__ void __launch_bounds__(64) k_locate_solve(LocateArgs a, CamDev cam, d
             for (int r = 0; r < LOC_MAX_SEEDS; r++)
                 if (sel[r] > prev && sel[r] < v) v = sel[r];
             prev = v;
-            const int e = a.views[b + v];
+            const LocateView sv = vm.view(a, a.views[b + v]);
             double C[12], Wi[12];
-            locate_view_cam(a, e, C);
+            vm.view_cam(a, sv, C);
             pk_inv(C, Wi);
             for (int m = 0; m < 2; m++) {
                 double A[12], G[12];
-                map_obs_pose(a.obs[e], ks, m == 1, A);
+                map_obs_pose(*sv.rec, ks, m == 1, A);
                 pk_mul(Wi, A, G);
                 const double c = score(G);
                 if (c < best) {
@@ -276,7 +355,7 @@ __global__ void __launch_bounds__(64) k_locate_solve(LocateArgs a, CamDev cam, d
         if (nrej == 0) {
             if (won < 0) { locate_write_none(o, oc, sigma_px, 3, n, lane); return; }  // no seeding view, or every score NaN
             best_first = best;
-            seed_frame = a.views[b + won] / a.max_tags;
+            seed_frame = vm.view(a, a.views[b + won]).frame;
             seed_mirrored = wm;
         }
 
@@ -289,11 +368,12 @@ __global__ void __launch_bounds__(64) k_locate_solve(LocateArgs a, CamDev cam, d
         int wv = 0x7fffffff;
         for (int v = lane; v < n; v += ASL_WAVE) {
             if (drops.has(v)) continue;
-            const int e = a.views[b + v];
+            const LocateView gv = vm.view(a, a.views[b + v]);
+            const CamDev cam = vm.cam_of(gv);
             double C[12], eq[4];
-            locate_view_cam(a, e, C);
+            vm.view_cam(a, gv, C);
 #pragma unroll
-            for (int q = 0; q < 4; q++) eq[q] = locate_corner<false>(cam, C, a.obs[e].corners, h, P, P + 9, q, nullptr);
+            for (int q = 0; q < 4; q++) eq[q] = locate_corner<false>(cam, C, gv.rec->corners, h, P, P + 9, q, nullptr);
             const double rms = sqrt(((eq[0] + eq[1]) + (eq[2] + eq[3])) / 4);
             if (rms > wr) { wr = rms; wv = v; }
         }
@@ -318,7 +398,7 @@ __global__ void __launch_bounds__(64) k_locate_solve(LocateArgs a, CamDev cam, d
     // the covariance at the pose just written, as loc_solve_frame<true> does: world<-tag is the pose solved for itself
     if constexpr (COV) {
         double ne[27], col[6], sig;
-        const double c1 = locate_pass<true>(a, cam, h, b, n, drops, P, P + 9, lane, ne);
+        const double c1 = locate_pass<true>(vm, a, h, b, n, drops, P, P + 9, lane, ne);
         const int dof = 8 * nused - 6;
         const double s2 = pose_cov_sigma2(sigma_px, c1, dof, &sig);
         const int c = lane < 6 ? lane : 5;
@@ -327,4 +407,26 @@ __global__ void __launch_bounds__(64) k_locate_solve(LocateArgs a, CamDev cam, d
         if (lane == 36) oc->sigma_px = sig;
         if (lane == 37) { oc->dof = dof; oc->status = pd ? 0 : 2; }
     }
+}
+
+// One wavefront per id, one camera; COV: also cov[id]
+template <bool COV>
+__global__ void __launch_bounds__(64) k_locate_solve(LocateArgs a, CamDev cam, double gate, int min_views, TagFitRec *__restrict__ fit,
+                                                     PoseCovRec *__restrict__ cov, double sigma_px)
+{
+    const int i = blockIdx.x;
+    locate_solve_tag<COV>(LocateOne{cam}, a, i, cam.half, gate, min_views, fit + i, COV ? cov + i : nullptr, sigma_px, (int)threadIdx.x);
+}
+
+// One wavefront per id, a rig: the camera table to LDS first, published by the barrier before the solve reads it
+template <bool COV>
+__global__ void __launch_bounds__(64) k_locate_solve_rig(LocateArgs a, const RigCamRec *__restrict__ rig, double half, double gate, int min_views,
+                                                         TagFitRec *__restrict__ fit, PoseCovRec *__restrict__ cov, double sigma_px)
+{
+    __shared__ double s_cams[RIG_MAX_CAMS * RIG_CAM_DOUBLES];
+    const int i = blockIdx.x, lane = threadIdx.x;
+    rig_fill_cams(s_cams, rig, a.n_cams, lane);
+    __syncthreads();
+    locate_solve_tag<COV>(LocateRig{s_cams, 65536u / (unsigned int)a.max_tags + 1u}, a, i, half, gate, min_views, fit + i, COV ? cov + i : nullptr,
+                          sigma_px, lane);
 }

@@ -36,6 +36,15 @@ __host__ __device__ constexpr size_t rig_lds_bytes(int n_cams, int max_tags)
 // less than g * max_tags / 65536 < 1 / max_tags, which no quotient's fraction part comes within of the next integer
 __device__ __forceinline__ int rig_cam_of(int g, unsigned int magic) { return (int)(((unsigned int)g * magic) >> 16); }
 
+// the projection model of the camera whose LDS record is cl
+__device__ __forceinline__ CamDev rig_cam_dev(const double *cl)
+{
+    CamDev c;
+    c.fx = cl[0]; c.fy = cl[1]; c.cx = cl[2]; c.cy = cl[3]; c.k1 = cl[4]; c.k2 = cl[5]; c.p1 = cl[6]; c.p2 = cl[7]; c.k3 = cl[8];
+    c.half = 0; c.both_minima = 0; c.pad = 0;
+    return c;
+}
+
 // loc_corner for a corner of the camera whose LDS record is cl: squared pixel error at rig point P_r = R X + t, with NE
 // its two Jacobian rows J_proj Re [-[P_r]x | I] added to acc (JtJ packed lower triangle 21, Jt r 6).  The mounting is read
 // from LDS where it is used: a per-camera choice among register copies would be a run-time-indexed array, i.e. scratch.
@@ -52,10 +61,7 @@ __device__ __forceinline__ double rig_corner(const double *cl, const double *R, 
 #pragma unroll
     for (int r = 0; r < 3; r++) P[r] = Re[3 * r] * Pr[0] + Re[3 * r + 1] * Pr[1] + Re[3 * r + 2] * Pr[2] + te[r];
     if (!(P[2] > LOC_Z_MIN)) return LOC_BEHIND_COST;
-    CamDev c;
-    c.fx = cl[0]; c.fy = cl[1]; c.cx = cl[2]; c.cy = cl[3]; c.k1 = cl[4]; c.k2 = cl[5]; c.p1 = cl[6]; c.p2 = cl[7]; c.k3 = cl[8];
-    c.half = 0; c.both_minima = 0; c.pad = 0;
-    project_dev(c, P, uv, NE ? Jp : nullptr);
+    project_dev(rig_cam_dev(cl), P, uv, NE ? Jp : nullptr);
     const double r0 = uv[0] - iu, r1 = uv[1] - iv;
     [[maybe_unused]] double wgt = 1.0, rho = 0.0;
     if constexpr (ROBUST) {

@@ -1,4 +1,4 @@
-// Cross-lane primitives of the kernels: DPP moves, lane exchanges, readlane, the wave scan and reduction, the maximum,
+// Cross-lane primitives of the kernels: DPP moves, lane exchanges, readlane, the wave scan, reduction and prefix sum, the maximum,
 // minimum and owner of a group of 8 lanes, butterfly sums.
 // They need neither LDS nor an address register: ds_bpermute does the same in ~100 cycles of latency per exchange, and a
 // sorting network or a reduction is a chain of such exchanges.
@@ -96,6 +96,15 @@ __device__ __forceinline__ T wave_scan(T v, T ident, Op op)
     v = op(v, dpp_mov<0x143, 0xc>(ident, v));  // row_bcast:31 into rows 2 and 3 -> lane 63 holds the whole wave's result
     if constexpr (REDUCE) return readlane(v, 63);
     else return v;
+}
+
+// Exclusive prefix sum of an int over the 64 lanes (lane l: v_0 + ... + v_{l-1}) and, in every lane, the wave's sum in
+// *total; all lanes must be active.
+__device__ __forceinline__ int wave_prefix_sum(int v, int *total)
+{
+    const int incl = wave_scan<false>(v, 0, [](int a, int b) { return a + b; });
+    *total = readlane(incl, 63);
+    return incl - v;
 }
 
 // Groups of 8 lanes (k_homography: one quad per group).  Maximum resp. minimum over the group, in all 8 lanes: the other

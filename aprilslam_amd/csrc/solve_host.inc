@@ -972,85 +972,133 @@ extern "C" int asl_smooth_rig_sequences_batch(asl_detector *d, const asl_obs *ob
 
 static_assert(sizeof(TagFitRec) == sizeof(asl_tag_fit) && sizeof(asl_tag_fit) == 40, "asl_tag_fit layout");
 
-// One locate call, in the entry points' argument order; cov may be NULL: not asked for.  obs, poses, map (in / out), fit
-// and cov are all host (asl_locate_tags_batch) or all device pointers (asl_locate_tags_frames_device).
+// One locate call, whichever of the four entry points made it, in their argument order; cov may be NULL: not asked for.
+// The single-camera forms leave n_cams 0 and rig NULL; the rig forms give n_cams and the table and leave cam's K and dist
+// NULL, n_dist 0.  obs, poses, map (in / out), rig, fit and cov are all host (*_batch) or all device pointers.
 struct LocateCall {
-    const void *obs; int n_frames, max_tags;
+    const void *obs; int n_cams, n_frames, max_tags;
     const void *poses;
     void *map; int n_ids;
-    Camera cam;
+    const void *rig; Camera cam;
     double gate; int min_views; double sigma_px;
     void *fit, *cov;
 };
 
-// every refusal, before anything is written or enqueued; the same for both forms
-static int check_locate_call(const asl_detector *d, const LocateCall &c, bool)
+static bool is_rig(const LocateCall &c) { return c.n_cams || c.rig; }
+
+// Every refusal, before anything is written or enqueued.  A rig's table is checked last, as check_localize_call does: where
+// it is, or (device) in a copy read back.
+static int check_locate_call(const asl_detector *d, const LocateCall &c, bool device)
 {
+    const bool rig = is_rig(c);
     if (!d) return fail(ASL_EINVAL, "NULL detector");
-    if (!c.obs || !c.poses || !c.map || !c.cam.K || !c.fit) return fail(ASL_EINVAL, "NULL argument");
+    if (!c.obs || !c.poses || !c.map || !(rig ? c.rig : (const void *)c.cam.K) || !c.fit) return fail(ASL_EINVAL, "NULL argument");
     if (c.n_frames < 0) return fail(ASL_EINVAL, "n_frames < 0");
+    if (rig && (c.n_cams < 1 || c.n_cams > RIG_MAX_CAMS)) return fail(ASL_EINVAL, "n_cams must be in [1, %d] (got %d)", RIG_MAX_CAMS, c.n_cams);
     if (int rc = check_obs_args(c.max_tags, c.n_ids, c.cam)) return rc;
+    if (rig && c.n_cams * c.max_tags > RIG_MAX_SLOTS)
+        return fail(ASL_EINVAL, "n_cams * max_tags must be <= %d (got %d x %d)", RIG_MAX_SLOTS, c.n_cams, c.max_tags);
+    if ((size_t)(rig ? c.n_cams : 1) * (size_t)c.n_frames * (size_t)c.max_tags > 0x7fffffffull)
+        return fail(ASL_EINVAL, "the block must hold fewer than 2^31 records (got %d x %d x %d)", rig ? c.n_cams : 1, c.n_frames, c.max_tags);
     if (!(c.gate >= 0) || !std::isfinite(c.gate)) return fail(ASL_EINVAL, "max_view_rms_px must be >= 0 (got %g)", c.gate);
     if (c.min_views < 1) return fail(ASL_EINVAL, "min_views must be >= 1 (got %d)", c.min_views);
-    return check_sigma_px(c.sigma_px);
+    if (int rc = check_sigma_px(c.sigma_px)) return rc;
+    if (!rig) return ASL_OK;
+    asl_rig_camera tab[RIG_MAX_CAMS];
+    if (device) {
+        HIPCHK(hipSetDevice(d->device));
+        HIPCHK(hipMemcpy(tab, c.rig, sizeof(asl_rig_camera) * (size_t)c.n_cams, hipMemcpyDeviceToHost));
+    }
+    return check_rig_table(device ? tab : (const asl_rig_camera *)c.rig, c.n_cams);
 }
 
-// c's pointers are the device's.  The workspace (per-id marks, counts and offsets, the view list) is carved from
-// d->locate_ws before the first launch; the four kernels follow each other on the stream without a host wait.
+// c's pointers are the device's.  The workspace (per-id marks, counts and offsets, the view list over every record of the
+// block) is carved from d->locate_ws before the first launch; the four kernels follow each other on the stream without a
+// host wait.  One camera is a block of n_cams = 1.
 static int launch_locate(asl_detector *d, const LocateCall &c, hipStream_t st)
 {
-    const size_t ni = (size_t)c.n_ids, nsl = (size_t)c.n_frames * (size_t)c.max_tags;
-    if (nsl > 0x7fffffffull) return fail(ASL_EINVAL, "n_frames * max_tags must be below 2^31 (got %d x %d)", c.n_frames, c.max_tags);
+    static const double no_K[9] = {};
+    const bool rig = is_rig(c);
+    const int n_cams = rig ? c.n_cams : 1;
+    const size_t ni = (size_t)c.n_ids, nsl = (size_t)n_cams * (size_t)c.n_frames * (size_t)c.max_tags;
     LocateArgs a{};
     if (carve_ws(d->locate_ws, [&](WsCarve &w) {
             a.seen = w.take<int>(ni); a.cnt = w.take<int>(ni); a.ptr = w.take<int>(ni + 1); a.views = w.take<int>(std::max<size_t>(nsl, 1));
         }))
         return fail(ASL_ENOMEM, "tag location workspace allocation failed");
-    a.obs = (const ObsRec *)c.obs; a.n_frames = c.n_frames; a.max_tags = c.max_tags; a.poses = (const CamPoseRec *)c.poses;
+    a.obs = (const ObsRec *)c.obs; a.n_cams = n_cams; a.n_frames = c.n_frames; a.max_tags = c.max_tags; a.poses = (const CamPoseRec *)c.poses;
     a.map = (MapTagRec *)c.map; a.n_ids = c.n_ids;
-    const CamDev cam = make_cam(d, c.cam);
+    const CamDev cam = make_cam(d, rig ? no_K : c.cam.K, c.cam.dist, c.cam.n_dist, c.cam.tag_size);   // a rig: for its half alone
+    const RigCamRec *tab = (const RigCamRec *)c.rig;
+    TagFitRec *fit = (TagFitRec *)c.fit;
+    PoseCovRec *cov = (PoseCovRec *)c.cov;
     const dim3 ids((unsigned int)c.n_ids), wave(ASL_WAVE);
     HIPCHK(hipMemsetAsync(a.seen, 0, sizeof(int) * ni, st));
     if (nsl) hipLaunchKernelGGL(k_locate_mark, dim3((unsigned int)((nsl + 255) / 256)), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_locate_count, ids, wave, 0, st, a);
     hipLaunchKernelGGL(k_locate_scan, dim3(1), dim3(MAP_WG), 0, st, a);
-    if (c.cov)
-        hipLaunchKernelGGL(k_locate_solve<true>, ids, wave, 0, st, a, cam, c.gate, c.min_views, (TagFitRec *)c.fit, (PoseCovRec *)c.cov, c.sigma_px);
+    if (!rig && cov)
+        hipLaunchKernelGGL(k_locate_solve<true>, ids, wave, 0, st, a, cam, c.gate, c.min_views, fit, cov, c.sigma_px);
+    else if (!rig)
+        hipLaunchKernelGGL(k_locate_solve<false>, ids, wave, 0, st, a, cam, c.gate, c.min_views, fit, cov, c.sigma_px);
+    else if (cov)
+        hipLaunchKernelGGL(k_locate_solve_rig<true>, ids, wave, 0, st, a, tab, cam.half, c.gate, c.min_views, fit, cov, c.sigma_px);
     else
-        hipLaunchKernelGGL(k_locate_solve<false>, ids, wave, 0, st, a, cam, c.gate, c.min_views, (TagFitRec *)c.fit, (PoseCovRec *)nullptr, c.sigma_px);
+        hipLaunchKernelGGL(k_locate_solve_rig<false>, ids, wave, 0, st, a, tab, cam.half, c.gate, c.min_views, fit, cov, c.sigma_px);
     HIPCHK(hipGetLastError());
     return ASL_OK;
 }
 
-// the host form: the map goes in and comes back through solve_out, the frame poses are staged there too
+// the host forms: the map goes in and comes back through solve_out, the frame poses and a rig's table are staged there too
 static int locate_batch(asl_detector *d, const LocateCall &c)
 {
     if (int rc = check_locate_call(d, c, false)) return rc;
-    const size_t ni = (size_t)c.n_ids, pose_bytes = sizeof(asl_cam_pose) * (size_t)c.n_frames;
+    const bool rig = is_rig(c);
+    const size_t ni = (size_t)c.n_ids, pose_bytes = sizeof(asl_cam_pose) * (size_t)c.n_frames, rig_bytes = sizeof(asl_rig_camera) * (size_t)c.n_cams;
     OutPiece o[] = {{c.map, sizeof(asl_map_tag) * ni}, {c.fit, sizeof(asl_tag_fit) * ni}, {c.cov, c.cov ? sizeof(asl_pose_cov) * ni : 0},
-                    {nullptr, pose_bytes}};
-    if (int rc = stage_host_call(d, "tag location", o, c.obs, c.n_frames, c.max_tags, nullptr, c.n_ids)) return rc;
+                    {nullptr, pose_bytes}, {nullptr, rig_bytes}};
+    if (int rc = stage_host_call(d, "tag location", o, c.obs, (rig ? c.n_cams : 1) * c.n_frames, c.max_tags, nullptr, c.n_ids)) return rc;
     HIPCHK(hipMemcpy(o[0].dev, c.map, o[0].bytes, hipMemcpyHostToDevice));
     if (pose_bytes) HIPCHK(hipMemcpy(o[3].dev, c.poses, pose_bytes, hipMemcpyHostToDevice));
+    if (rig) HIPCHK(hipMemcpy(o[4].dev, c.rig, rig_bytes, hipMemcpyHostToDevice));
     LocateCall dc = c;
     dc.obs = d->loc_obs.p ? (const void *)d->loc_obs.p : c.obs;  // no frame: never read, but not NULL
     dc.poses = o[3].dev ? o[3].dev : c.poses;
-    dc.map = o[0].dev; dc.fit = o[1].dev; dc.cov = o[2].dev;
+    dc.map = o[0].dev; dc.fit = o[1].dev; dc.cov = o[2].dev; dc.rig = o[4].dev;
     if (int rc = launch_locate(d, dc, nullptr)) return rc;
     return fetch_out(o);
 }
+
+static constexpr auto locate_frames_device = frames_device<LocateCall, check_locate_call, launch_locate>;   // the two device forms
 
 extern "C" int asl_locate_tags_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_poses, void *d_map,
                                              int n_ids, const double *K, const double *dist, int n_dist, double tag_size, double max_view_rms_px,
                                              int min_views, double sigma_px, void *d_fit, void *d_cov, void *stream)
 {
-    return frames_device<LocateCall, check_locate_call, launch_locate>(
-        d, {d_obs, n_frames, max_tags, d_poses, d_map, n_ids, {K, dist, n_dist, tag_size}, max_view_rms_px, min_views, sigma_px, d_fit, d_cov}, stream);
+    return locate_frames_device(
+        d, {d_obs, 0, n_frames, max_tags, d_poses, d_map, n_ids, nullptr, {K, dist, n_dist, tag_size}, max_view_rms_px, min_views, sigma_px, d_fit, d_cov},
+        stream);
 }
 
 extern "C" int asl_locate_tags_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_cam_pose *poses, asl_map_tag *map,
                                      int n_ids, const double *K, const double *dist, int n_dist, double tag_size, double max_view_rms_px,
                                      int min_views, double sigma_px, asl_tag_fit *fit, asl_pose_cov *cov)
 {
-    return locate_batch(d, {obs, n_frames, max_tags, poses, map, n_ids, {K, dist, n_dist, tag_size}, max_view_rms_px, min_views, sigma_px, fit, cov});
+    return locate_batch(d, {obs, 0, n_frames, max_tags, poses, map, n_ids, nullptr, {K, dist, n_dist, tag_size}, max_view_rms_px, min_views, sigma_px, fit, cov});
+}
+
+extern "C" int asl_locate_tags_rig_frames_device(asl_detector *d, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_poses,
+                                                 void *d_map, int n_ids, const void *d_rig, double tag_size, double max_view_rms_px, int min_views,
+                                                 double sigma_px, void *d_fit, void *d_cov, void *stream)
+{
+    return locate_frames_device(
+        d, {d_obs, n_cams, n_frames, max_tags, d_poses, d_map, n_ids, d_rig, {nullptr, nullptr, 0, tag_size}, max_view_rms_px, min_views, sigma_px, d_fit, d_cov},
+        stream);
+}
+
+extern "C" int asl_locate_tags_rig_batch(asl_detector *d, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_cam_pose *poses,
+                                         asl_map_tag *map, int n_ids, const asl_rig_camera *rig, double tag_size, double max_view_rms_px,
+                                         int min_views, double sigma_px, asl_tag_fit *fit, asl_pose_cov *cov)
+{
+    return locate_batch(d, {obs, n_cams, n_frames, max_tags, poses, map, n_ids, rig, {nullptr, nullptr, 0, tag_size}, max_view_rms_px, min_views, sigma_px, fit, cov});
 }

@@ -8,6 +8,8 @@ exact and their uncertainty is not propagated.
 
     LocateResult    the records of one call, with .tag_map, .located_ids, .status and .tag_std()
     extend_map      localise a block of frames against the map, then locate every tag the map does not have
+    wanted_records  the record block of such a call: the map grown to every id seen, the known sizes written in
+                    (rig.Rig.extend_map, the rig form over asl_locate_tags_rig_*, calls it too)
     TAG_FIT_DTYPE   one asl_tag_fit per id: rms_px, rms_seed_px, n_views, n_rejected, status, seed_frame, seed_mirrored
 """
 import numpy as np
@@ -17,7 +19,7 @@ from .localize import TagMap, pose_std
 
 STATUS_LOCATED, STATUS_NOT_WANTED, STATUS_FEW_VIEWS, STATUS_NO_PNP = 0, 1, 2, 3
 
-__all__ = ["LocateResult", "extend_map", "TAG_FIT_DTYPE", "STATUS_LOCATED", "STATUS_NOT_WANTED", "STATUS_FEW_VIEWS", "STATUS_NO_PNP"]
+__all__ = ["LocateResult", "extend_map", "wanted_records", "TAG_FIT_DTYPE", "STATUS_LOCATED", "STATUS_NOT_WANTED", "STATUS_FEW_VIEWS", "STATUS_NO_PNP"]
 
 
 class LocateResult:
@@ -62,6 +64,16 @@ def extend_map(det, obs, tag_map, K, dist, tag_size, tag_sizes=None, max_view_rm
     ({id: size}): the known side of unmapped tags that is not tag_size; it is written into their entries, which the located
     tags keep.  The entries the map had come back byte for byte."""
     o = _obs_records(obs)
+    rec = wanted_records(o, tag_map, tag_sizes)
+    poses = det.localize(o, rec, K, dist, tag_size, max_tag_rms_px=max_tag_rms_px)
+    out, fit, cov = det.locate_tags(o, poses, rec, K, dist, tag_size, max_view_rms_px=max_view_rms_px, min_views=min_views, sigma_px=sigma_px)
+    return LocateResult(out, fit, cov), poses
+
+
+def wanted_records(o, tag_map, tag_sizes=None):
+    """The record block extend_map (and rig.Rig.extend_map) hands to the solvers: a copy of tag_map's records, grown to
+    cover every id the asl_obs records o (any shape) see, with tag_sizes ({id: size}) written into the entries that have
+    no pose.  The entries the map had keep their bytes."""
     rec = _map_records(tag_map)
     seen = o["id"][(o["flags"] & 1) != 0]
     n_ids = max(len(rec), int(seen.max()) + 1 if seen.size else 1, 1)
@@ -77,6 +89,4 @@ def extend_map(det, obs, tag_map, K, dist, tag_size, tag_sizes=None, max_view_rm
             raise ValueError("a tag size is finite and non-negative (0: the call's tag_size)")
         if 0 <= i < n_ids and not rec["valid"][i]:
             rec["size"][i] = size   # an id without a pose: TagMap.set_size has no place for it
-    poses = det.localize(o, rec, K, dist, tag_size, max_tag_rms_px=max_tag_rms_px)
-    out, fit, cov = det.locate_tags(o, poses, rec, K, dist, tag_size, max_view_rms_px=max_view_rms_px, min_views=min_views, sigma_px=sigma_px)
-    return LocateResult(out, fit, cov), poses
+    return rec

@@ -7,7 +7,8 @@ mounting.  A frame index is one instant for all cameras.
 
     RigCamera       one camera: K, dist (0, 4 or 5 coefficients), T_cam_rig = camera<-rig 4x4 (the mounting)
     Rig             the cameras in block order; as_records() -> RIG_CAMERA_DTYPE (asl_rig_camera), save / load,
-                    localize(), localize_sequence() / localize_sequences(), build_map() / build_map_sized(), from_camera_poses()
+                    localize(), localize_sequence() / localize_sequences(), build_map() / build_map_sized(),
+                    locate_tags() / extend_map(), from_camera_poses()
 
 Consecutive frames of the rig solved together under a random-walk motion prior (asl_smooth_rig_sequences_batch, k_smooth.inc):
 Rig.localize_sequence and Rig.localize_sequences return smooth.SmoothResult, its poses the rig's (world<-rig).  A frame in
@@ -125,6 +126,28 @@ class Rig:
         out = det.build_map_rig(o, n_ids, self.as_records(), tag_size, world_id=world_id, max_iters=max_iters, with_std=with_std,
                                 huber_px=huber_px, with_slot_weight=bool(huber_px), tag_sizes=tag_sizes)
         return MapResult(*out, slot_ids=o["id"] if huber_px else None)
+
+    def locate_tags(self, det, obs, poses, tag_map, tag_size, max_view_rms_px=0.0, min_views=2, sigma_px=None):
+        """The tags the map does not have, located from the rig's posed frames (Detector.locate_tags_rig,
+        asl_locate_tags_rig_batch): obs (n_cams, n_frames, max_tags) OBS_DTYPE, camera-major, poses (n_frames,)
+        CAM_POSE_DTYPE with T = world<-rig (localize(), localize_sequence() or build_map()'s camera_poses) ->
+        locate.LocateResult.  Every camera's view of a tag is a view of its own through that camera's mounting, so a tag
+        that only a camera without a mapped tag in view sees is located too, and one two cameras see at the same instant
+        is solved from both.  The mountings and the poses are taken as exact."""
+        from .locate import LocateResult
+        return LocateResult(*det.locate_tags_rig(self._block(obs), poses, tag_map, self.as_records(), tag_size, max_view_rms_px=max_view_rms_px,
+                                                 min_views=min_views, sigma_px=sigma_px))
+
+    def extend_map(self, det, obs, tag_map, tag_size, tag_sizes=None, max_view_rms_px=0.0, min_views=2, sigma_px=None, max_tag_rms_px=0.0):
+        """locate.extend_map for the rig: the frames are localised against the map (localize(), gate max_tag_rms_px), then
+        every id the map does not have is located from the frames that got a pose (locate_tags(), gate max_view_rms_px) ->
+        (locate.LocateResult, (n_frames,) CAM_POSE_DTYPE world<-rig).  The record block grows to cover every id seen;
+        tag_sizes ({id: size}): the known side of unmapped tags that is not tag_size."""
+        from .locate import wanted_records
+        o = self._block(obs)
+        rec = wanted_records(o, tag_map, tag_sizes)
+        poses = self.localize(det, o, rec, tag_size, max_tag_rms_px=max_tag_rms_px)
+        return self.locate_tags(det, o, poses, rec, tag_size, max_view_rms_px=max_view_rms_px, min_views=min_views, sigma_px=sigma_px), poses
 
     def _block(self, obs):
         o = np.asarray(obs)

@@ -623,6 +623,39 @@ int asl_locate_tags_batch(asl_detector *det, const asl_obs *obs, int n_frames, i
                           asl_map_tag *map, int n_ids, const double *K, const double *dist, int n_dist, double tag_size,
                           double max_view_rms_px, int min_views, double sigma_px, asl_tag_fit *fit, asl_pose_cov *cov);
 
+/* The rig form: asl_locate_tags_* with the camera-major block d_obs[n_cams][n_frames][max_tags] and the camera table
+   d_rig (n_cams asl_rig_camera, complete when the call is made) of asl_localize_rig_* in place of K, dist, n_dist.  A tag
+   that only a camera without a mapped tag in view sees is located through the rig's pose; a tag two cameras see at one
+   instant is solved from both views.
+   Poses: d_poses holds n_frames records with T = world<-rig, what asl_localize_rig_*, asl_smooth_rig_* and asl_map_rig_*
+   write.  A frame takes part under the rule above (status 0 or 6, rows 0..2 finite).
+   Views: in a frame that takes part each camera c = 0..n_cams-1 gives at most one view of id i, its first slot with
+   flags & 1 and id == i; the same id in two cameras of a frame is two views (asl_map_rig_*'s rule).  View order is
+   (frame, camera).  The camera of a view is C = E_c inv(T_f) = (Re R, Re t + te) with inv(T_f) = (R, t) formed as above,
+   and every view is projected through its own camera's model.  min_views counts views: one frame seen by two cameras
+   satisfies min_views = 2.
+   Seed, refinement, gate with re-seeding, fit record and covariance are those above over this view list.  The seeds are
+   the <= 8 active views with flags & 2 of largest corner area; areas are pixels as they are, so cameras of different
+   focal length are not put on one scale (asl_localize_rig_*'s rule); ties go to the earlier view.  A candidate is
+   G = inv(C) T_obs, plain before mirrored, a sized tag's translation first times size / tag_size.  The gate drops single
+   views: a spoiled view in one camera leaves the other cameras' views of that frame in.  seed_frame is the frame of the
+   winning first view; reserved stays 0.  The covariance has dof = 8 n_views - 6; the mountings and the frame poses are
+   taken as exact.
+   ASL_EINVAL, before anything is written or enqueued: whatever asl_locate_tags_* refuses, d_rig NULL, n_cams outside
+   [1, 16], n_cams * max_tags > 256, n_cams * n_frames * max_tags >= 2^31, or a table with a bad n_dist, a non-finite
+   entry or an E whose rotation part is not a rotation; the device form reads the table back and checks it first.
+   n_frames == 0 is ASL_OK: every wanted id gets status 2.  Deterministic: the same input gives the same bytes.  A rig of
+   one camera with E = I is asl_locate_tags_* with that camera.  tests/locate_rig_ref.py states the computation. */
+int asl_locate_tags_rig_frames_device(asl_detector *det, const void *d_obs, int n_cams, int n_frames, int max_tags,
+                                      const void *d_poses, void *d_map, int n_ids, const void *d_rig, double tag_size,
+                                      double max_view_rms_px, int min_views, double sigma_px, void *d_fit, void *d_cov,
+                                      void *stream);
+/* The same computation on host records, synchronous; map is read and written in place, cov may be NULL. */
+int asl_locate_tags_rig_batch(asl_detector *det, const asl_obs *obs, int n_cams, int n_frames, int max_tags,
+                              const asl_cam_pose *poses, asl_map_tag *map, int n_ids, const asl_rig_camera *rig,
+                              double tag_size, double max_view_rms_px, int min_views, double sigma_px, asl_tag_fit *fit,
+                              asl_pose_cov *cov);
+
 /* ---- sequence localisation: the camera poses of one camera's consecutive frames against a fixed map, solved together
    under a random-walk motion prior, so that EVERY frame gets a pose: frames without a mapped tag are carried by their
    neighbours, a single-tag frame cannot end in its mirrored planar minimum alone, and corner noise is averaged. */
