@@ -47,10 +47,14 @@ TAG_FIT_DTYPE = np.dtype([("rms_px", "<f8"), ("rms_seed_px", "<f8"), ("n_views",
                           ("seed_frame", "<i4"), ("seed_mirrored", "<i4"), ("reserved", "<i4")])  # asl_tag_fit
 assert TAG_FIT_DTYPE.itemsize == 40
 
+RECTIFY_VIEW_DTYPE = np.dtype([("K", "<f8", (3, 3)), ("R", "<f8", (3, 3))])  # asl_rectify_view; R = source camera <- view
+assert RECTIFY_VIEW_DTYPE.itemsize == 144
+LENS_BROWN, LENS_FISHEYE, MAX_VIEWS = 0, 1, 16   # ASL_LENS_BROWN, ASL_LENS_FISHEYE, ASL_MAX_VIEWS
+LENS_MODELS = {"brown": LENS_BROWN, "fisheye": LENS_FISHEYE}
 EXPORTS = [
     "asl_detector_create", "asl_family_check", "asl_detector_create_family", "asl_families_check", "asl_detector_create_families", "asl_detector_family_of", "asl_detector_destroy", "asl_detector_set_id_limit", "asl_detector_set_pnp_both_minima", "asl_detector_set_quad_sigma", "asl_blur_taps", "asl_last_error", "asl_version", "asl_detect_gray_u8",
     "asl_detect_bgr_u8", "asl_detect_batch_u8", "asl_detect_batch_pose_u8", "asl_detect_batch_device", "asl_submit_batch_device", "asl_collect_batch", "asl_collect_batch_view", "asl_solve_pnp_batch", "asl_gn_solve", "asl_pack_observations_device", "asl_graph_frames_device", "asl_graph_picks_device", "asl_render_frames_device",
-    "asl_rectify_frames_device", "asl_rectify_u8",
+    "asl_rectify_frames_device", "asl_rectify_u8", "asl_rectify_views_device", "asl_rectify_views_u8",
     "asl_localize_frames_device", "asl_localize_batch", "asl_localize_cov_frames_device", "asl_localize_cov_batch",
     "asl_pose_cov_device", "asl_solve_pnp_cov_batch", "asl_calibrate_frames_device", "asl_calibrate_batch",
     "asl_localize_rig_frames_device", "asl_localize_rig_cov_frames_device", "asl_localize_rig_batch", "asl_localize_rig_cov_batch",
@@ -192,6 +196,9 @@ def load():
     L.asl_render_frames_device.argtypes = [vp, vp, i32, i32, i32, i32, C.c_size_t, vp, i32, vp, i32, i32, C.c_double, dp, dp, i32, vp]
     L.asl_rectify_frames_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.c_size_t, vp, i32, i32, i32, C.c_size_t, dp, dp, i32, dp, i32, vp]
     L.asl_rectify_u8.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, dp, dp, i32, dp, i32]
+    L.asl_rectify_views_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.c_size_t, vp, i32, i32, i32, C.c_size_t, dp, dp, i32, i32, vp, i32,
+                                           C.c_double, i32, vp]
+    L.asl_rectify_views_u8.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, C.c_size_t, dp, dp, i32, i32, vp, i32, C.c_double, i32]
     L.asl_pack_observations_device.argtypes = [vp, vp, i32, vp]
     L.asl_graph_frames_device.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp]
     L.asl_graph_picks_device.argtypes = [vp, vp, i32, i32, i32, vp, C.c_uint32, C.c_uint32, vp, i32, vp, vp]
@@ -304,6 +311,29 @@ def _camera(K, dist, square=False):
     if len(dc) not in (0, 4, 5):
         raise ValueError("dist must have 0, 4 or 5 coefficients")
     return (Kc, dc), Kc.ctypes.data_as(_DP), (dc.ctypes.data_as(_DP) if len(dc) else None), len(dc)
+
+
+def _lens(K, dist, model):
+    """_camera for a lens of either model: (arrays to keep alive, K pointer, dist pointer or None, n_dist, lens_model).
+    model: "brown" (0, 4 or 5 coefficients k1 k2 p1 p2 [k3]) or "fisheye" (0 or 4: k1 k2 k3 k4), or the ABI's number."""
+    m = LENS_MODELS.get(model, model)
+    if m not in (LENS_BROWN, LENS_FISHEYE):
+        raise ValueError("model must be 'brown' or 'fisheye'")
+    keep, Kp, dpp, nd = _camera(K, dist, square=True)
+    if m == LENS_FISHEYE and nd not in (0, 4):
+        raise ValueError("a fisheye lens has 0 or 4 coefficients (k1, k2, k3, k4)")
+    return keep, Kp, dpp, nd, m
+
+
+def rectify_view_records(views):
+    """[(K_new, R)] or RECTIFY_VIEW_DTYPE records -> contiguous (n_views,) RECTIFY_VIEW_DTYPE"""
+    if isinstance(views, np.ndarray) and views.dtype == RECTIFY_VIEW_DTYPE:
+        return np.ascontiguousarray(views).ravel()
+    rec = np.zeros(len(views), dtype=RECTIFY_VIEW_DTYPE)
+    for k, (K_new, R) in enumerate(views):
+        rec["K"][k] = np.asarray(K_new, dtype=np.float64).reshape(3, 3)
+        rec["R"][k] = np.eye(3) if R is None else np.asarray(R, dtype=np.float64).reshape(3, 3)
+    return rec
 
 
 def _obs_records(obs):
@@ -536,6 +566,40 @@ class Detector:
         out = np.empty((max(h_out, 0), max(w_out, 0)), dtype=np.uint8)
         check(self._L.asl_rectify_u8(self._h, a.ctypes.data, ch, w, h, w * ch, out.ctypes.data, w_out, h_out, w_out, Kp, dpp, nd,
                                      None if Kn is None else Kn.ctypes.data_as(_DP), int(fill)))
+        return out
+
+    def rectify_views_device(self, src_ptr, n_frames, channels, width, height, dst_ptr, K, dist, views, model="fisheye", width_out=None,
+                             height_out=None, theta_max=None, fill=0, stride=None, frame_pitch=None, stride_out=None, frame_pitch_out=None,
+                             stream=0):
+        """asl_rectify_views_device: n_frames gray / BGR frames of the camera (K, dist, model) at the device address src_ptr
+        -> the gray frames of the rotated pinholes `views` ([(K_new, R)], R = source camera <- view, or RECTIFY_VIEW_DTYPE
+        records) at dst_ptr, view-major: view v of frame i at dst_ptr + (v * n_frames + i) * frame_pitch_out.  theta_max
+        (radians, None = pi): fisheye rays further from the axis give `fill`.  Enqueued on `stream`, no wait."""
+        width_out, height_out = int(width_out or width), int(height_out or height)
+        stride = stride or width * channels
+        frame_pitch = frame_pitch or stride * height
+        stride_out = stride_out or width_out
+        frame_pitch_out = frame_pitch_out or stride_out * height_out
+        keep, Kp, dpp, nd, m = _lens(K, dist, model)
+        rec = rectify_view_records(views)
+        check(self._L.asl_rectify_views_device(self._h, _ptr(src_ptr), int(n_frames), int(channels), int(width), int(height), int(stride),
+                                               int(frame_pitch), _ptr(dst_ptr), width_out, height_out, int(stride_out), int(frame_pitch_out),
+                                               Kp, dpp, nd, m, _data(rec), len(rec), float(theta_max or 0.0), int(fill), _ptr(stream)))
+
+    def rectify_views(self, image, K, dist, views, model="fisheye", size=None, theta_max=None, fill=0):
+        """asl_rectify_views_u8: one host image, (H, W) gray or (H, W, 3) BGR uint8, of the camera (K, dist, model) -> the
+        (n_views, h_out, w_out) gray images of the rotated pinholes `views`; size = (w_out, h_out), default the source's."""
+        a = np.ascontiguousarray(image)
+        if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3):
+            raise ValueError("expected an (H, W) or (H, W, 3) uint8 image")
+        h, w = a.shape[:2]
+        ch = 1 if a.ndim == 2 else 3
+        w_out, h_out = (w, h) if size is None else (int(size[0]), int(size[1]))
+        keep, Kp, dpp, nd, m = _lens(K, dist, model)
+        rec = rectify_view_records(views)
+        out = np.empty((len(rec), max(h_out, 0), max(w_out, 0)), dtype=np.uint8)
+        check(self._L.asl_rectify_views_u8(self._h, a.ctypes.data, ch, w, h, w * ch, out.ctypes.data, w_out, h_out, w_out, max(w_out * h_out, 0),
+                                           Kp, dpp, nd, m, _data(rec), len(rec), float(theta_max or 0.0), int(fill)))
         return out
 
     def pack_observations_device(self, out_ptr, max_tags, stream=0):

@@ -1148,6 +1148,7 @@ struct RectifyCall {
     const void *src; int n_frames, channels, w, h, stride; size_t frame_pitch;
     void *dst; int w_out, h_out, stride_out; size_t frame_pitch_out;
     const double *K, *dist; int n_dist; const double *K_new; int fill;
+    int n_views = 1;  // asl_rectify_views_*: the destination holds n_views * n_frames frames
 };
 #define RECTIFY_MAX_DIM 16384  // the detector's own limit (make_geom); keeps every row offset and the launch grid in range
 
@@ -1175,7 +1176,7 @@ static int check_rectify_call(const asl_detector *d, const RectifyCall &c, bool 
     if (!(c.K[0] > 0) || !(c.K[4] > 0) || !(Kn[0] > 0) || !(Kn[4] > 0)) return fail(ASL_EINVAL, "K and K_new must have positive focal lengths");
     // the bytes the kernel may read / write: whole strides but for the last row of the last frame
     const size_t src_bytes = (size_t)(c.n_frames - 1) * c.frame_pitch + (size_t)(c.h - 1) * (size_t)c.stride + (size_t)c.w * (size_t)c.channels;
-    const size_t dst_bytes = (size_t)(c.n_frames - 1) * c.frame_pitch_out + (size_t)(c.h_out - 1) * (size_t)c.stride_out + (size_t)c.w_out;
+    const size_t dst_bytes = ((size_t)c.n_views * (size_t)c.n_frames - 1) * c.frame_pitch_out + (size_t)(c.h_out - 1) * (size_t)c.stride_out + (size_t)c.w_out;
     const uintptr_t s0 = (uintptr_t)c.src, d0 = (uintptr_t)c.dst;
     if (s0 < d0 + dst_bytes && d0 < s0 + src_bytes) return fail(ASL_EINVAL, "source and destination overlap");
     memset(cam, 0, sizeof *cam);
@@ -1231,6 +1232,108 @@ extern "C" int asl_rectify_u8(asl_detector *d, const uint8_t *src, int channels,
     c.dst = d->rect_dst.p; c.stride_out = w_out; c.frame_pitch_out = (size_t)w_out * (size_t)h_out;
     if (int rc = launch_rectify(c, cam, nullptr)) return rc;
     HIPCHK(hipMemcpy2D(dst, (size_t)stride_out, d->rect_dst.p, (size_t)w_out, (size_t)w_out, (size_t)h_out, hipMemcpyDeviceToHost));
+    return ASL_OK;
+}
+
+// ---- rectification into rotated pinhole views (k_rectify_views): check_rectify_call's checks and those of the lens
+// model, the view table and theta_max; the same staging buffers, so both calls are legal while a batch is pending.
+#define RECTIFY_ROTATION_TOL 1e-6  // rig.ORTHONORMAL_TOL
+static int check_rectify_views_call(const asl_detector *d, const RectifyCall &c, bool device, int lens_model, const asl_rectify_view *views,
+                                    double theta_max, RectifyLens *lens, RectifyViewTable *table)
+{
+    static_assert(sizeof(asl_rectify_view) == 144, "asl_rectify_view layout");
+    static_assert(RECTIFY_MAX_VIEWS == ASL_MAX_VIEWS && RECTIFY_LENS_BROWN == ASL_LENS_BROWN && RECTIFY_LENS_FISHEYE == ASL_LENS_FISHEYE, "header and kernel agree");
+    if (lens_model != ASL_LENS_BROWN && lens_model != ASL_LENS_FISHEYE) return fail(ASL_EINVAL, "lens_model must be ASL_LENS_BROWN (0) or ASL_LENS_FISHEYE (1), got %d", lens_model);
+    if (lens_model == ASL_LENS_FISHEYE && c.n_dist != 0 && c.n_dist != 4) return fail(ASL_EINVAL, "a fisheye lens has n_dist 0 or 4 (k1 k2 k3 k4), got %d", c.n_dist);
+    if (c.n_views < 1 || c.n_views > ASL_MAX_VIEWS) return fail(ASL_EINVAL, "n_views must be in 1..%d, got %d", ASL_MAX_VIEWS, c.n_views);
+    if (!views) return fail(ASL_EINVAL, "views is NULL");
+    if (!device && c.frame_pitch_out < (size_t)std::max(c.stride_out, 0) * (size_t)std::max(c.h_out, 0)) return fail(ASL_EINVAL, "view_pitch_out smaller than one output frame");
+    RectifyCam cam;
+    if (int rc = check_rectify_call(d, c, device, &cam)) return rc;
+    if (!std::isfinite(theta_max) || theta_max < 0 || theta_max > M_PI) return fail(ASL_EINVAL, "theta_max must be 0 (= pi) or in (0, pi]");
+    for (int v = 0; v < c.n_views; v++) {
+        const double *K = views[v].K, *R = views[v].R;
+        for (int k = 0; k < 9; k++)
+            if (!std::isfinite(K[k]) || !std::isfinite(R[k])) return fail(ASL_EINVAL, "view %d: K / R is not finite", v);
+        if (!(K[0] > 0) || !(K[4] > 0)) return fail(ASL_EINVAL, "view %d: K must have positive focal lengths", v);
+        double worst = 0;
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++)
+                worst = std::max(worst, std::fabs(R[3 * i] * R[3 * j] + R[3 * i + 1] * R[3 * j + 1] + R[3 * i + 2] * R[3 * j + 2] - (i == j ? 1.0 : 0.0)));
+        const double det3 = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+        if (worst > RECTIFY_ROTATION_TOL || !(det3 > 0)) return fail(ASL_EINVAL, "view %d: R is not a rotation", v);
+    }
+    memset(lens, 0, sizeof *lens);
+    memset(table, 0, sizeof *table);
+    lens->fx = c.K[0]; lens->fy = c.K[4]; lens->cx = c.K[2]; lens->cy = c.K[5];
+    for (int k = 0; k < c.n_dist; k++) lens->k[k] = c.dist[k];
+    lens->theta_max = theta_max == 0 ? M_PI : theta_max;
+    lens->fill = c.fill;
+    for (int v = 0; v < c.n_views; v++) {
+        RectifyView &o = table->v[v];
+        o.nfx = views[v].K[0]; o.nfy = views[v].K[4]; o.ncx = views[v].K[2]; o.ncy = views[v].K[5];
+        memcpy(o.R, views[v].R, sizeof o.R);
+    }
+    return ASL_OK;
+}
+
+template <int CH, int MODEL>
+static void launch_rectify_views_as(const RectifyCall &c, const dim3 &grid, int z0, const RectifyLens &lens, const RectifyViewTable &table, hipStream_t st)
+{
+    hipLaunchKernelGGL((k_rectify_views<CH, MODEL>), grid, dim3(64, 4), 0, st, (const uint8_t *)c.src, c.n_frames, c.w, c.h, c.stride, c.frame_pitch,
+                       (uint8_t *)c.dst, c.w_out, c.h_out, c.stride_out, c.frame_pitch_out, z0, lens, table);
+}
+
+// view * n_frames + frame along blockIdx.z, as many to a launch as the grid takes
+static int launch_rectify_views(const RectifyCall &c, int lens_model, const RectifyLens &lens, const RectifyViewTable &table, hipStream_t st)
+{
+    const dim3 tiles((c.w_out + RECTIFY_TW - 1) / RECTIFY_TW, (c.h_out + 4 * RECTIFY_TH - 1) / (4 * RECTIFY_TH));
+    const unsigned long long per_frame = 256ull * tiles.x * tiles.y;
+    const long long total = (long long)c.n_views * c.n_frames;
+    const long long step = (long long)std::max<unsigned long long>(1ull, std::min<unsigned long long>(65535ull, (1ull << 31) / per_frame));
+    if (total > 0x7fffffffLL) return fail(ASL_EINVAL, "n_views * n_frames does not fit");
+    for (long long z0 = 0; z0 < total; z0 += step) {
+        const dim3 grid(tiles.x, tiles.y, (unsigned int)std::min(step, total - z0));
+        const bool fish = lens_model == ASL_LENS_FISHEYE;
+        if (c.channels == 1 && !fish) launch_rectify_views_as<1, RECTIFY_LENS_BROWN>(c, grid, (int)z0, lens, table, st);
+        else if (c.channels == 1) launch_rectify_views_as<1, RECTIFY_LENS_FISHEYE>(c, grid, (int)z0, lens, table, st);
+        else if (!fish) launch_rectify_views_as<3, RECTIFY_LENS_BROWN>(c, grid, (int)z0, lens, table, st);
+        else launch_rectify_views_as<3, RECTIFY_LENS_FISHEYE>(c, grid, (int)z0, lens, table, st);
+        HIPCHK(hipGetLastError());
+    }
+    return ASL_OK;
+}
+
+extern "C" int asl_rectify_views_device(asl_detector *d, const void *d_src, int n_frames, int channels, int w, int h, int stride, size_t frame_pitch,
+                                        void *d_dst, int w_out, int h_out, int stride_out, size_t frame_pitch_out, const double *K, const double *dist,
+                                        int n_dist, int lens_model, const asl_rectify_view *views, int n_views, double theta_max, int fill, void *stream)
+{
+    const RectifyCall c{d_src, n_frames, channels, w, h, stride, frame_pitch, d_dst, w_out, h_out, stride_out, frame_pitch_out, K, dist, n_dist, nullptr, fill, n_views};
+    RectifyLens lens;
+    RectifyViewTable table;
+    if (int rc = check_rectify_views_call(d, c, true, lens_model, views, theta_max, &lens, &table)) return rc;
+    HIPCHK(hipSetDevice(d->device));
+    return launch_rectify_views(c, lens_model, lens, table, (hipStream_t)stream);
+}
+
+extern "C" int asl_rectify_views_u8(asl_detector *d, const uint8_t *src, int channels, int w, int h, int stride, uint8_t *dst, int w_out, int h_out,
+                                    int stride_out, size_t view_pitch_out, const double *K, const double *dist, int n_dist, int lens_model,
+                                    const asl_rectify_view *views, int n_views, double theta_max, int fill)
+{
+    RectifyCall c{src, 1, channels, w, h, stride, 0, dst, w_out, h_out, stride_out, view_pitch_out, K, dist, n_dist, nullptr, fill, n_views};
+    RectifyLens lens;
+    RectifyViewTable table;
+    if (int rc = check_rectify_views_call(d, c, false, lens_model, views, theta_max, &lens, &table)) return rc;
+    HIPCHK(hipSetDevice(d->device));
+    const size_t row = (size_t)w * (size_t)channels, view_bytes = (size_t)w_out * (size_t)h_out;
+    if (d->rect_src.ensure(row * (size_t)h) || d->rect_dst.ensure(view_bytes * (size_t)n_views)) return fail(ASL_ENOMEM, "rectification staging allocation failed");
+    // rows packed on the device; the padding of the caller's rows and views is neither read nor written
+    HIPCHK(hipMemcpy2D(d->rect_src.p, row, src, (size_t)stride, row, (size_t)h, hipMemcpyHostToDevice));
+    c.src = d->rect_src.p; c.stride = (int)row; c.frame_pitch = row * (size_t)h;
+    c.dst = d->rect_dst.p; c.stride_out = w_out; c.frame_pitch_out = view_bytes;
+    if (int rc = launch_rectify_views(c, lens_model, lens, table, nullptr)) return rc;
+    for (int v = 0; v < n_views; v++)
+        HIPCHK(hipMemcpy2D(dst + (size_t)v * view_pitch_out, (size_t)stride_out, d->rect_dst.p + (size_t)v * view_bytes, (size_t)w_out, (size_t)w_out, (size_t)h_out, hipMemcpyDeviceToHost));
     return ASL_OK;
 }
 

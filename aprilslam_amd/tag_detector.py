@@ -29,7 +29,7 @@ class TagDetector:
     """Handles AprilTag detection and pose estimation (GPU-backed)."""
 
     def __init__(self, camera_params, tag_type="tagStandard41h12", tag_size=0.06, device=0, id_limit=None, quad_sigma=0.0,
-                 rectify=False, rectified_K=None):
+                 rectify=False, rectified_K=None, lens_model="brown"):
         """tag_type: a family's name, or a list of registered names (one detector for all; ids are then global and the
         detections carry 'family' and 'local_id', see apriltag).
         quad_sigma: the detector's blur (> 0) or sharpening (< 0) of the decimated image; the reference leaves it 0.
@@ -37,7 +37,16 @@ class TagDetector:
         camera_params as the source camera), into a buffer this detector owns, and detect on the gray result -- for a lens
         strong enough to bend a tag's edges.  DETECTIONS ARE THEN IN RECTIFIED PIXELS (rectify.distort_points takes them back
         into the frame the camera delivered), and every pose call uses the pinhole rectified_K (default: the camera matrix)
-        with no distortion.  False, the default, is the path without the keyword."""
+        with no distortion.  False, the default, is the path without the keyword.
+        lens_model: "brown" (dist_coeffs k1 k2 p1 p2 [k3]) or "fisheye" (dist_coeffs k1 k2 k3 k4, the cv2.fisheye model).  A
+        fisheye needs rectify=True, since no solver takes that lens: the frames go through asl_rectify_views_u8 /
+        asl_rectify_views_device into the one view rectified_K with R the identity.  A field of view no single pinhole
+        holds takes several views: rectify.ViewSet."""
+        if lens_model not in ("brown", "fisheye"):
+            raise ValueError("lens_model must be 'brown' or 'fisheye'")
+        if lens_model == "fisheye" and not rectify:
+            raise ValueError("a fisheye lens needs rectify=True: no solver takes that lens")
+        self.lens_model = lens_model
         self.detector = apriltag(tag_type, blur=quad_sigma, device=device, id_limit=id_limit)
         self.tag_size = tag_size
         self.camera_matrix = camera_params['camera_matrix']
@@ -132,7 +141,10 @@ class TagDetector:
     def _lens(self):
         """the camera's own lens coefficients"""
         d = np.asarray(self.dist_coeffs, dtype=np.float64).ravel()
-        if len(d) not in (0, 4, 5):
+        if self.lens_model == "fisheye":
+            if len(d) not in (0, 4):
+                raise ValueError("a fisheye's dist_coeffs hold 0 or 4 values")
+        elif len(d) not in (0, 4, 5):
             raise ValueError("dist_coeffs must hold 0, 4 or 5 values")
         return d
 
@@ -145,7 +157,9 @@ class TagDetector:
         return np.zeros(0) if self.rectify else self._lens()
 
     def _rectified_host(self, image):
-        """one host image, gray or BGR -> its rectified gray image (asl_rectify_u8)"""
+        """one host image, gray or BGR -> its rectified gray image (asl_rectify_u8; a fisheye: asl_rectify_views_u8)"""
+        if self.lens_model == "fisheye":
+            return self.detector._det.rectify_views(image, self.camera_matrix, self._lens(), [(self.rectified_K, None)], model="fisheye")[0]
         return self.detector._det.rectify(image, self.camera_matrix, self._lens(), K_new=self.rectified_K)
 
     def get_poses(self, detections):
@@ -372,9 +386,13 @@ class TagDetector:
             need = int(n_frames) * int(width) * int(height)
             if self._rect_buf is None or self._rect_buf.numel() < need:
                 self._rect_buf = torch.empty(need, dtype=torch.uint8, device="cuda:%d" % self._device)
-            self.detector._det.rectify_frames_device(data_ptr, n_frames, channels, width, height, self._rect_buf.data_ptr(),
-                                                     self.camera_matrix, self._lens(), K_new=self.rectified_K,
-                                                     stride=kw.pop("stride", None), frame_pitch=kw.pop("frame_pitch", None), stream=stream)
+            pitches = dict(stride=kw.pop("stride", None), frame_pitch=kw.pop("frame_pitch", None), stream=stream)
+            if self.lens_model == "fisheye":
+                self.detector._det.rectify_views_device(data_ptr, n_frames, channels, width, height, self._rect_buf.data_ptr(), self.camera_matrix,
+                                                        self._lens(), [(self.rectified_K, None)], model="fisheye", **pitches)
+            else:
+                self.detector._det.rectify_frames_device(data_ptr, n_frames, channels, width, height, self._rect_buf.data_ptr(),
+                                                         self.camera_matrix, self._lens(), K_new=self.rectified_K, **pitches)
             data_ptr, channels = self._rect_buf.data_ptr(), 1
         K = self._K() if with_pose else None
         return self.detector._det.detect_device(data_ptr, n_frames, channels, width, height, stream=stream, K=K,

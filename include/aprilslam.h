@@ -907,6 +907,48 @@ int asl_rectify_u8(asl_detector *det, const uint8_t *src, int channels, int w, i
                    uint8_t *dst, int w_out, int h_out, int stride_out, const double *K, const double *dist,
                    int n_dist, const double *K_new, int fill);
 
+/* Rectification into rotated pinhole views: the way in for a lens no single pinhole holds, a 150-200 degree fisheye.  The
+   frame is rectified into n_views pinholes (K, R), each turned against the source camera (left, front and right at 90
+   degrees each, say); those are rigidly mounted pinhole cameras with exactly known mountings, camera<-rig = [R^T | 0] in
+   the source camera's frame, and every asl_*_rig_* solver takes their observations as they are.
+   Output pixel (x, y) of view (K', R), R = source camera <- view, 9 doubles row-major:
+     the view ray dv = ((x + 0.5 - cx') / fx', (y + 0.5 - cy') / fy', 1) and the source ray (X, Y, Z) = R dv, each
+     component r0*dv0 + r1*dv1 + r2*dv2 from left to right; then the lens (K, dist, lens_model) of the source:
+     ASL_LENS_BROWN, n_dist 0, 4 or 5 (k1 k2 p1 p2 [k3]): Z <= 0 gives `fill`; else xn = X / Z, yn = Y / Z and the closed
+       form of asl_rectify_frames_device.  With one view and R the identity this is asl_rectify_frames_device, byte for byte.
+     ASL_LENS_FISHEYE, n_dist 0 or 4 (k1 k2 k3 k4): the model of cv2.fisheye, carried past 90 degrees by the two-argument
+       arctangent: r = sqrt(X*X + Y*Y), theta = atan2(r, Z) in [0, pi]; theta > theta_max gives `fill`; t2 = theta*theta,
+       theta_d = theta (1 + t2 (k1 + t2 (k2 + t2 (k3 + t2 k4)))); s = theta_d / r (r == 0: s = 0);
+       u = fx (s X) + cx, v = fy (s Y) + cy.  A ray behind the camera (Z < 0) is an ordinary ray of this model.
+     then the outside test, the bilinear sample, the gray conversion and the rounding of asl_rectify_frames_device.
+   All in float64, and the arctangent is an argument reduction and a polynomial written out in the kernel
+   (tests/rectify_views_ref.py: atan2_pos), not the device library's, so the frames are byte-identical to that statement.
+   theta_max: 0 means pi; otherwise in (0, pi]; cut it where the lens's image circle ends.  Ignored for ASL_LENS_BROWN.
+   Layout: view v of frame i at d_dst + (v*n_frames + i)*frame_pitch_out -- view-major, so that the frames of one view are
+   a contiguous batch for asl_submit_batch_device, and the order of the rig observation block (camera-major).  `views` is
+   a host pointer, read before the call returns; asynchronous on `stream`.  Legal between submit and collect.
+   Views that overlap show a tag twice, from the same source pixels: the rig solvers take both slots, which are not
+   independent, so a covariance that counts both is somewhat optimistic.  Views that abut avoid it.
+   ASL_EINVAL, nothing written: everything asl_rectify_frames_device refuses (the destination range being that of all
+   views); lens_model not 0 or 1; ASL_LENS_FISHEYE with n_dist not 0 or 4; n_views outside 1..ASL_MAX_VIEWS or views
+   NULL; a view whose K is not finite or has fx or fy <= 0; a view whose R is not finite or not a rotation
+   (max |R R^T - I| > 1e-6 or det <= 0); theta_max not finite or outside [0, pi]. */
+#define ASL_LENS_BROWN 0
+#define ASL_LENS_FISHEYE 1
+#define ASL_MAX_VIEWS 16
+typedef struct { double K[9]; double R[9]; } asl_rectify_view;   /* 144 bytes; R = source<-view, row-major */
+int asl_rectify_views_device(asl_detector *det, const void *d_src, int n_frames, int channels, int w, int h,
+                             int stride, size_t frame_pitch, void *d_dst, int w_out, int h_out, int stride_out,
+                             size_t frame_pitch_out, const double *K, const double *dist, int n_dist, int lens_model,
+                             const asl_rectify_view *views /* host */, int n_views, double theta_max, int fill,
+                             void *stream);
+/* The same for one host image, synchronous: view v at dst + v*view_pitch_out (at least stride_out*h_out).  Only the
+   w_out bytes of each of the h_out rows of each view are written. */
+int asl_rectify_views_u8(asl_detector *det, const uint8_t *src, int channels, int w, int h, int stride,
+                         uint8_t *dst, int w_out, int h_out, int stride_out, size_t view_pitch_out, const double *K,
+                         const double *dist, int n_dist, int lens_model, const asl_rectify_view *views, int n_views,
+                         double theta_max, int fill);
+
 /* ---- introspection and diagnostics.  asl_debug_fetch, asl_stage_times and the counters (item 5) describe the LAST batch
    the detector ran.  asl_detect_batch_u8 and asl_detect_batch_pose_u8 run a call of 128 frames or more as consecutive
    batches of 64 frames, so after such a call that is the call's last chunk (frames 128..149 of a 150-frame call), not the
