@@ -1,1 +1,1 @@
-from .rig import Rig, RigCamera  # noqa: F401
+from .rig import Rig, RigCalibrationResult, RigCamera  # noqa: F401

@@ -43,6 +43,10 @@ assert SMOOTH_RESULT_DTYPE.itemsize == 64
 assert POSE_COV_DTYPE.itemsize == 304
 RIG_CAMERA_DTYPE = np.dtype([("K", "<f8", (3, 3)), ("dist", "<f8", (5,)), ("E", "<f8", (3, 4)), ("n_dist", "<i4"), ("reserved", "<i4")])  # asl_rig_camera
 assert RIG_CAMERA_DTYPE.itemsize == 216
+RIG_CALIB_RESULT_DTYPE = np.dtype([("rms_px", "<f8"), ("rms_init_px", "<f8"), ("sigma_px", "<f8"), ("n_frames_used", "<i4"), ("n_corners", "<i4"),
+                                   ("iterations", "<i4"), ("status", "<i4"), ("n_solved", "<i4"), ("reserved", "<i4"),
+                                   ("cam_status", "<i4", (16,)), ("cam_frames", "<i4", (16,))])  # asl_rig_calib_result
+assert RIG_CALIB_RESULT_DTYPE.itemsize == 176
 TAG_FIT_DTYPE = np.dtype([("rms_px", "<f8"), ("rms_seed_px", "<f8"), ("n_views", "<i4"), ("n_rejected", "<i4"), ("status", "<i4"),
                           ("seed_frame", "<i4"), ("seed_mirrored", "<i4"), ("reserved", "<i4")])  # asl_tag_fit
 assert TAG_FIT_DTYPE.itemsize == 40
@@ -58,6 +62,7 @@ EXPORTS = [
     "asl_localize_frames_device", "asl_localize_batch", "asl_localize_cov_frames_device", "asl_localize_cov_batch",
     "asl_pose_cov_device", "asl_solve_pnp_cov_batch", "asl_calibrate_frames_device", "asl_calibrate_batch",
     "asl_localize_rig_frames_device", "asl_localize_rig_cov_frames_device", "asl_localize_rig_batch", "asl_localize_rig_cov_batch",
+    "asl_calibrate_rig_frames_device", "asl_calibrate_rig_batch",
     "asl_map_frames_device", "asl_map_batch", "asl_map_robust_frames_device", "asl_map_robust_batch", "asl_map_rig_frames_device", "asl_map_rig_batch", "asl_map_sized_frames_device", "asl_map_sized_batch",
     "asl_map_rig_sized_frames_device", "asl_map_rig_sized_batch", "asl_smooth_frames_device", "asl_smooth_batch", "asl_smooth_cov_frames_device", "asl_smooth_cov_batch",
     "asl_smooth_sequences_device", "asl_smooth_sequences_batch", "asl_smooth_robust_sequences_device", "asl_smooth_robust_sequences_batch",
@@ -220,6 +225,9 @@ def load():
     calib = [vp] + obs_block + tag_map + [dbl, i32, i32, dp, i32, i32, i32, vp, vp]    # ..., tag_size, width, height, K_init, n_dist, flags, max_iters, the two results
     L.asl_calibrate_frames_device.argtypes = calib + [vp]
     L.asl_calibrate_batch.argtypes = calib
+    calib_rig = rig[:9] + [i32, dbl, vp, vp, vp, vp]              # ..., rig, tag_size, max_iters, sigma_px, rig_out, result, cov, poses
+    L.asl_calibrate_rig_frames_device.argtypes = calib_rig + [vp]
+    L.asl_calibrate_rig_batch.argtypes = calib_rig
     mapping = [vp] + obs_block + [i32] + camera + [i32, i32, vp, vp, vp, vp]    # ..., n_ids, camera, world_id, max_iters, the four results
     L.asl_map_frames_device.argtypes = mapping + [vp]
     L.asl_map_batch.argtypes = mapping
@@ -798,6 +806,36 @@ class Detector:
         check(self._L.asl_calibrate_frames_device(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids),
                                                   float(tag_size), int(width), int(height), Kp, int(n_dist), int(flags), int(max_iters),
                                                   _ptr(result_ptr), _ptr(poses_ptr), _ptr(stream)))
+
+    def calibrate_rig(self, obs, tag_map, rig, tag_size, max_iters=30, sigma_px=None):
+        """asl_calibrate_rig_batch: host records obs (n_cams, n_frames, max_tags) OBS_DTYPE, camera-major, against tag_map, with
+        rig ((n_cams,) RIG_CAMERA_DTYPE, or a rig.Rig) as the initial mountings -> ((n_cams,) RIG_CAMERA_DTYPE with the refined
+        mountings, RIG_CALIB_RESULT_DTYPE record, (n_cams,) POSE_COV_DTYPE of the mountings, (n_frames,) CAM_POSE_DTYPE
+        world<-rig).  Camera 0's mounting is the gauge and stays; sigma_px None or 0: the covariances are scaled by the
+        solve's own estimate.  Pass clean observations: the joint solve has no outlier gate."""
+        o = np.ascontiguousarray(obs, dtype=OBS_DTYPE)
+        if o.ndim != 3:
+            raise ValueError("obs must be (n_cams, n_frames, max_tags) asl_obs records")
+        m, r = _map_records(tag_map), _rig_records(rig)
+        if len(r) != o.shape[0]:
+            raise ValueError("the rig has %d cameras, obs has %d" % (len(r), o.shape[0]))
+        rig_out = np.zeros(len(r), dtype=RIG_CAMERA_DTYPE)
+        res = np.zeros((), dtype=RIG_CALIB_RESULT_DTYPE)
+        cov = np.zeros(len(r), dtype=POSE_COV_DTYPE)
+        poses = np.zeros(o.shape[1], dtype=CAM_POSE_DTYPE)
+        check(self._L.asl_calibrate_rig_batch(self._h, _data(o), o.shape[0], o.shape[1], o.shape[2], _data(m), len(m), _data(r), float(tag_size),
+                                              int(max_iters), float(sigma_px or 0.0), _data(rig_out), res.ctypes.data, _data(cov), _data(poses)))
+        return rig_out, res, cov, poses
+
+    def calibrate_rig_device(self, obs_ptr, n_cams, n_frames, max_tags, map_ptr, n_ids, rig_ptr, tag_size, rig_out_ptr, result_ptr, cov_ptr,
+                             poses_ptr, max_iters=30, sigma_px=0.0, stream=0):
+        """asl_calibrate_rig_frames_device: obs_ptr (n_cams x n_frames x max_tags asl_obs, camera-major), map_ptr (n_ids
+        asl_map_tag), rig_ptr (n_cams asl_rig_camera, complete when the call is made), rig_out_ptr (n_cams asl_rig_camera; may
+        be rig_ptr), result_ptr (one asl_rig_calib_result), cov_ptr (n_cams asl_pose_cov) and poses_ptr (n_frames asl_cam_pose)
+        are device addresses; the whole solve is enqueued on `stream`, no wait."""
+        check(self._L.asl_calibrate_rig_frames_device(self._h, _ptr(obs_ptr), int(n_cams), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids),
+                                                      _ptr(rig_ptr), float(tag_size), int(max_iters), float(sigma_px), _ptr(rig_out_ptr),
+                                                      _ptr(result_ptr), _ptr(cov_ptr), _ptr(poses_ptr), _ptr(stream)))
 
     def build_map(self, obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_std=True, huber_px=0.0, with_slot_weight=False,
                   tag_sizes=None):

@@ -36,6 +36,7 @@
 #include "k_posecov.inc"
 #include "k_rig.inc"
 #include "k_calib.inc"
+#include "k_rigcal.inc"
 #include "k_map.inc"
 #include "k_smooth.inc"
 #include "k_locate.inc"
@@ -141,6 +142,7 @@ struct asl_detector {
     DevBuf<uint8_t> solve_out;         // the *_batch solver entries: their results, until copied back
     DevBuf<uint8_t> rect_src, rect_dst;  // asl_rectify_u8: the host image's device copy and the result (no batch reads them)
     DevBuf<uint8_t> cal_ws;  // calibration: per-frame workspace and state (k_calib.inc)
+    DevBuf<uint8_t> rigcal_ws;  // rig mounting calibration: per-frame workspace, camera tables and state (k_rigcal.inc)
     DevBuf<uint8_t> map_ws, map_lm;  // map reconstruction (k_map.inc): sized by the input / by the problem
     DevBuf<uint8_t> smooth_ws;  // sequence localisation (k_smooth.inc): the chain's and the LM's buffers, sized by n_frames and n_seq
     DevBuf<uint8_t> locate_ws;  // tag location (k_locate.inc): per-id marks, counts and offsets, the view list

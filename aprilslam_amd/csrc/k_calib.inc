@@ -206,50 +206,62 @@ __device__ __forceinline__ void cal_linearise(const CamDev &c, bool fa, double r
     cal_chunk<NT, 3 * C, NTRI>(c, fa, ratio, R, t, L, n4, lane, Hf);
 }
 
-// Sum over the list of frames of rows[f * stride + e] for e < ne (<= 64), by a CAL_WG workgroup: CAL_CHUNKS contiguous chunks
-// of the list, each summed in order, then the chunks in order.  The result lands in out[0..ne) (LDS) for every thread.
+// Sum over the list of frames of rows[f * stride + e] for e < ne, by a CAL_WG workgroup: CAL_CHUNKS contiguous chunks of the
+// list, each summed in order, then the chunks in order, 64 entries of the row at a time.  The result lands in out (LDS) for
+// every thread: ne rounded up to a multiple of 64 entries (64 for ne = 0), zero past ne.
 __device__ __forceinline__ void cal_list_sum(const double *rows, int stride, int ne, const int *list, int n, double *s_part, double *out)
 {
-    const int e = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
     const int chunk = (n + CAL_CHUNKS - 1) / CAL_CHUNKS;
-    double acc = 0;
-    if (e < ne) {
-        const int k1 = min(n, (q + 1) * chunk);
-        for (int k = q * chunk; k < k1; k++) acc += rows[(size_t)list[k] * stride + e];
+    for (int e0 = 0; e0 < max(ne, 1); e0 += 64) {
+        const int e = e0 + lane;
+        double acc = 0;
+        if (e < ne) {
+            const int k1 = min(n, (q + 1) * chunk);
+            for (int k = q * chunk; k < k1; k++) acc += rows[(size_t)list[k] * stride + e];
+        }
+        s_part[q * 64 + lane] = acc;
+        __syncthreads();
+        if (threadIdx.x < 64) {
+            double s = 0;
+            for (int j = 0; j < CAL_CHUNKS; j++) s += s_part[j * 64 + threadIdx.x];
+            out[e0 + threadIdx.x] = s;
+        }
+        __syncthreads();
     }
-    s_part[q * 64 + e] = acc;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        double s = 0;
-        for (int j = 0; j < CAL_CHUNKS; j++) s += s_part[j * 64 + threadIdx.x];
-        out[threadIdx.x] = s;
-    }
-    __syncthreads();
 }
 
-// The frames whose fr status is 0 and that have >= 2 mapped slots, in frame order, into list; returns their count
-// (every thread); s_cnt: CAL_WG ints of LDS
-__device__ __forceinline__ int cal_make_list(const CalibArgs &a, int *s_cnt)
+// The frames f < n_frames for which take(f) holds, in frame order, into list, by a CAL_WG workgroup; returns their count
+// (every thread); s_cnt: CAL_WG ints of LDS, count: an int of device memory for the count to pass through
+template <class Take>
+__device__ __forceinline__ int cal_make_list_of(int n_frames, Take take, int *list, int *s_cnt, int *count)
 {
-    const int tid = threadIdx.x, per = (a.n_frames + CAL_WG - 1) / CAL_WG;
-    const int f0 = min(a.n_frames, tid * per), f1 = min(a.n_frames, f0 + per);
+    const int tid = threadIdx.x, per = (n_frames + CAL_WG - 1) / CAL_WG;
+    const int f0 = min(n_frames, tid * per), f1 = min(n_frames, f0 + per);
     int c = 0;
-    for (int f = f0; f < f1; f++) c += (a.fr[CAL_FR * f] == 0 && a.fr[CAL_FR * f + 1] >= 2);
+    for (int f = f0; f < f1; f++) c += take(f) ? 1 : 0;
     s_cnt[tid] = c;
     __syncthreads();
     if (tid == 0) {
         int run = 0;
         for (int i = 0; i < CAL_WG; i++) { const int v = s_cnt[i]; s_cnt[i] = run; run += v; }
-        a.st->n_take = run;  // scratch for the count; the callers copy it where it belongs
+        *count = run;
     }
     __syncthreads();
     int o = s_cnt[tid];
     for (int f = f0; f < f1; f++)
-        if (a.fr[CAL_FR * f] == 0 && a.fr[CAL_FR * f + 1] >= 2) a.list[o++] = f;
+        if (take(f)) list[o++] = f;
     __syncthreads();
-    const int n = a.st->n_take;
+    const int n = *count;
     __syncthreads();
     return n;
+}
+
+// The frames whose fr status is 0 and that have >= 2 mapped slots (n_take: scratch for the count; the callers copy it where
+// it belongs)
+__device__ __forceinline__ int cal_make_list(const CalibArgs &a, int *s_cnt)
+{
+    return cal_make_list_of(a.n_frames, [&](int f) { return a.fr[CAL_FR * f] == 0 && a.fr[CAL_FR * f + 1] >= 2; }, a.list, s_cnt, &a.st->n_take);
 }
 
 // Cholesky solve of the packed n x n system A x = b in LDS (one thread); false if A is not positive definite

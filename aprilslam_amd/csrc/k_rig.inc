@@ -50,7 +50,11 @@ __device__ __forceinline__ CamDev rig_cam_dev(const double *cl)
 // from LDS where it is used: a per-camera choice among register copies would be a run-time-indexed array, i.e. scratch.
 // ROBUST (the rig sequence solve's Huber loss, k_smooth.inc): loc_corner<NE, true>'s rho, wgt and *over on the same
 // residual, the weight on the same 27 sums; every other caller leaves it false and gets the code above alone.
-template <bool NE, bool ROBUST = false>
+// MOUNT (the mounting calibration, k_rigcal.inc; with NE): nothing is summed; acc receives the corner's rows themselves,
+// J0 J1 (6 + 6) as above, then the rows over the mounting's own left update (Re, te) <- (Rod(w) Re, Rod(w) te + v),
+// J_proj [-[P_c]x | I] (6 + 6), then the residual (2): RIG_ROWS doubles.  A corner behind the camera leaves acc as it was.
+#define RIG_ROWS 26
+template <bool NE, bool ROBUST = false, bool MOUNT = false>
 __device__ __forceinline__ double rig_corner(const double *cl, const double *R, const double *t, const double *X, double iu, double iv, double *acc,
                                              double hk = 0.0, bool *over = nullptr)
 {
@@ -87,14 +91,27 @@ __device__ __forceinline__ double rig_corner(const double *cl, const double *R, 
             J1[k] = Jr[3] * nPx[k] + Jr[4] * nPx[3 + k] + Jr[5] * nPx[6 + k];
             J1[3 + k] = Jr[3 + k];
         }
+        if constexpr (MOUNT) {
+            const double nPc[9] = {0, P[2], -P[1], -P[2], 0, P[0], P[1], -P[0], 0};  // -[P_c]x
 #pragma unroll
-        for (int a = 0; a < 6; a++) {
-            if constexpr (ROBUST) acc[21 + a] += wgt * (J0[a] * r0 + J1[a] * r1);
-            else acc[21 + a] += J0[a] * r0 + J1[a] * r1;
+            for (int k = 0; k < 3; k++) {
+                acc[k] = J0[k]; acc[3 + k] = J0[3 + k]; acc[6 + k] = J1[k]; acc[9 + k] = J1[3 + k];
+                acc[12 + k] = Jp[0] * nPc[k] + Jp[1] * nPc[3 + k] + Jp[2] * nPc[6 + k];
+                acc[15 + k] = Jp[k];
+                acc[18 + k] = Jp[3] * nPc[k] + Jp[4] * nPc[3 + k] + Jp[5] * nPc[6 + k];
+                acc[21 + k] = Jp[3 + k];
+            }
+            acc[24] = r0; acc[25] = r1;
+        } else {
 #pragma unroll
-            for (int b = 0; b <= a; b++) {
-                if constexpr (ROBUST) acc[TRI(a, b)] += wgt * (J0[a] * J0[b] + J1[a] * J1[b]);
-                else acc[TRI(a, b)] += J0[a] * J0[b] + J1[a] * J1[b];
+            for (int a = 0; a < 6; a++) {
+                if constexpr (ROBUST) acc[21 + a] += wgt * (J0[a] * r0 + J1[a] * r1);
+                else acc[21 + a] += J0[a] * r0 + J1[a] * r1;
+#pragma unroll
+                for (int b = 0; b <= a; b++) {
+                    if constexpr (ROBUST) acc[TRI(a, b)] += wgt * (J0[a] * J0[b] + J1[a] * J1[b]);
+                    else acc[TRI(a, b)] += J0[a] * J0[b] + J1[a] * J1[b];
+                }
             }
         }
     }

@@ -1,5 +1,5 @@
 // Host side of the device solvers on asl_obs blocks: localisation and rig localisation (kernels: k_localize.inc, k_rig.inc),
-// per-tag pose covariance (k_posecov.inc), calibration (k_calib.inc), mapping (k_map.inc), sequence smoothing
+// per-tag pose covariance (k_posecov.inc), calibration (k_calib.inc), rig mounting calibration (k_rigcal.inc), mapping (k_map.inc), sequence smoothing
 // (k_smooth.inc) and tag location (k_locate.inc).  Every solver has one call record, filled by its extern "C" entry points in their argument order, one
 // check_*_call with every refusal, one launch_* on device pointers, one device form and one host form.  The host forms
 // share stage_host_call (the block and the map in, the results carved from d->solve_out) and fetch_out (the results back).
@@ -397,6 +397,110 @@ extern "C" int asl_calibrate_batch(asl_detector *d, const asl_obs *obs, int n_fr
                                    asl_calib_result *result, asl_cam_pose *poses)
 {
     return calibrate_batch(d, {obs, n_frames, max_tags, map, n_ids, tag_size, width, height, K_init, n_dist, flags, max_iters, result, poses});
+}
+
+// ---- rig mounting calibration (k_rigcal.inc)
+
+static_assert(sizeof(RigCalResultRec) == sizeof(asl_rig_calib_result) && sizeof(asl_rig_calib_result) == 176, "asl_rig_calib_result layout");
+
+// One mounting calibration call, in the entry points' argument order.  obs, map, rig, rig_out, result, cov and poses are all
+// host (asl_calibrate_rig_batch) or all device pointers (asl_calibrate_rig_frames_device); rig_out may be rig.
+struct RigCalCall {
+    const void *obs; int n_cams, n_frames, max_tags;
+    const void *map; int n_ids;
+    const void *rig; double tag_size; int max_iters; double sigma_px;
+    void *rig_out, *result, *cov, *poses;
+};
+
+// every refusal, before anything is written or enqueued; the table last, as check_localize_call reads it
+static int check_rig_calibrate_call(const asl_detector *d, const RigCalCall &c, bool device)
+{
+    if (!d) return fail(ASL_EINVAL, "NULL detector");
+    if (!c.obs || !c.map || !c.rig || !c.rig_out || !c.result || !c.cov || !c.poses) return fail(ASL_EINVAL, "NULL argument");
+    if (c.n_cams < 2 || c.n_cams > RC_MAX_CAMS) return fail(ASL_EINVAL, "n_cams must be in [2, %d] (got %d)", RC_MAX_CAMS, c.n_cams);
+    if (c.n_frames < 1) return fail(ASL_EINVAL, "n_frames must be >= 1 (got %d)", c.n_frames);
+    if (int rc = check_obs_args(c.max_tags, c.n_ids, {nullptr, nullptr, 0, c.tag_size})) return rc;
+    if (c.n_cams * c.max_tags > RIG_MAX_SLOTS)
+        return fail(ASL_EINVAL, "n_cams * max_tags must be <= %d (got %d x %d)", RIG_MAX_SLOTS, c.n_cams, c.max_tags);
+    if (c.max_iters < 1) return fail(ASL_EINVAL, "max_iters must be >= 1 (got %d)", c.max_iters);
+    if (int rc = check_sigma_px(c.sigma_px)) return rc;
+    asl_rig_camera tab[RC_MAX_CAMS];
+    if (device) {
+        HIPCHK(hipSetDevice(d->device));
+        HIPCHK(hipMemcpy(tab, c.rig, sizeof(asl_rig_camera) * (size_t)c.n_cams, hipMemcpyDeviceToHost));
+    }
+    return check_rig_table(device ? tab : (const asl_rig_camera *)c.rig, c.n_cams);
+}
+
+// c's pointers are the device's.  The workspace: state, frame list and per-frame buffers, carved from d->rigcal_ws
+static int launch_rig_calibrate(asl_detector *d, const RigCalCall &c, hipStream_t st)
+{
+    const size_t nf = (size_t)c.n_frames;
+    const int ns = c.n_cams - 1;  // room for every camera but the reference to be solved
+    RigCalArgs a{};
+    a.hs = rc_hs(ns); a.sbs = rc_sb(ns); a.bks = rc_bk(ns);
+    if (carve_ws(d->rigcal_ws, [&](WsCarve &w) {
+            a.st = w.take<RigCalState>(1); a.list = w.take<int>(nf); a.fr = w.take<int>(RC_FR * nf);
+            a.camtab = w.take<double>(2 * (size_t)c.n_cams * RIG_CAM_DOUBLES); a.pose = w.take<double>(2 * 12 * nf);
+            a.H = w.take<double>(2 * (size_t)a.hs * nf); a.SB = w.take<double>((size_t)a.sbs * nf); a.back = w.take<double>((size_t)a.bks * nf);
+        }))
+        return fail(ASL_ENOMEM, "rig calibration workspace allocation failed");
+    a.obs = (const ObsRec *)c.obs; a.map = (const MapTagRec *)c.map;
+    a.rig = (const RigCamRec *)c.rig; a.rig_out = (RigCamRec *)c.rig_out;
+    a.res = (RigCalResultRec *)c.result; a.cov = (PoseCovRec *)c.cov; a.out = (CamPoseRec *)c.poses;
+    a.half = (double)(float)(c.tag_size / 2);  // object corners are float32, as in the PnP
+    a.sigma_px = c.sigma_px;
+    a.magic = 65536u / (unsigned int)c.max_tags + 1u;
+    a.n_cams = c.n_cams; a.n_frames = c.n_frames; a.max_tags = c.max_tags; a.n_ids = c.n_ids; a.max_iters = c.max_iters;
+    const dim3 frames((unsigned int)c.n_frames), wave(ASL_WAVE), wg(CAL_WG);
+    const size_t lds = rig_lds_bytes(c.n_cams, c.max_tags);
+    // the seed: asl_localize_rig_frames_device under the mountings as given, the gate off
+    hipLaunchKernelGGL(k_localize_rig<false>, frames, wave, lds, st, a.obs, c.n_cams, c.max_tags, a.map, c.n_ids, a.rig, a.half, 0.0, a.out,
+                       (PoseCovRec *)nullptr, 0.0);
+    hipLaunchKernelGGL(k_rigcal_init, frames, wave, 0, st, a);
+    hipLaunchKernelGGL(k_rigcal_connect, dim3(1), wg, 0, st, a);
+    hipLaunchKernelGGL(k_rigcal_first, frames, wave, lds, st, a);
+    hipLaunchKernelGGL(k_rigcal_start, dim3(1), wg, 0, st, a);
+    for (int it = 0; it < c.max_iters; it++) {
+        hipLaunchKernelGGL(k_rigcal_schur, frames, wave, 0, st, a, 0);
+        hipLaunchKernelGGL(k_rigcal_solve, dim3(1), wg, 0, st, a);
+        hipLaunchKernelGGL(k_rigcal_step, frames, wave, lds, st, a);
+        hipLaunchKernelGGL(k_rigcal_decide, dim3(1), wg, 0, st, a);
+    }
+    hipLaunchKernelGGL(k_rigcal_schur, frames, wave, 0, st, a, 1);
+    hipLaunchKernelGGL(k_rigcal_finish, dim3(1), wg, 0, st, a);
+    HIPCHK(hipGetLastError());
+    return ASL_OK;
+}
+
+static int rig_calibrate_batch(asl_detector *d, const RigCalCall &c)
+{
+    if (int rc = check_rig_calibrate_call(d, c, false)) return rc;
+    const size_t rig_bytes = sizeof(asl_rig_camera) * (size_t)c.n_cams;
+    OutPiece o[] = {{c.rig_out, rig_bytes}, {c.result, sizeof(asl_rig_calib_result)}, {c.cov, sizeof(asl_pose_cov) * (size_t)c.n_cams},
+                    {c.poses, sizeof(asl_cam_pose) * (size_t)c.n_frames}, {nullptr, rig_bytes}};
+    if (int rc = stage_host_call(d, "rig calibration", o, c.obs, c.n_cams * c.n_frames, c.max_tags, c.map, c.n_ids)) return rc;
+    HIPCHK(hipMemcpy(o[4].dev, c.rig, rig_bytes, hipMemcpyHostToDevice));
+    RigCalCall dc = c;
+    dc.obs = d->loc_obs.p; dc.map = d->loc_map.p; dc.rig = o[4].dev;
+    dc.rig_out = o[0].dev; dc.result = o[1].dev; dc.cov = o[2].dev; dc.poses = o[3].dev;
+    if (int rc = launch_rig_calibrate(d, dc, nullptr)) return rc;
+    return fetch_out(o);
+}
+
+extern "C" int asl_calibrate_rig_frames_device(asl_detector *d, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map,
+                                               int n_ids, const void *d_rig, double tag_size, int max_iters, double sigma_px, void *d_rig_out,
+                                               void *d_result, void *d_cov, void *d_poses, void *stream)
+{
+    return frames_device<RigCalCall, check_rig_calibrate_call, launch_rig_calibrate>(
+        d, {d_obs, n_cams, n_frames, max_tags, d_map, n_ids, d_rig, tag_size, max_iters, sigma_px, d_rig_out, d_result, d_cov, d_poses}, stream);
+}
+
+extern "C" int asl_calibrate_rig_batch(asl_detector *d, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                       const asl_rig_camera *rig, double tag_size, int max_iters, double sigma_px, asl_rig_camera *rig_out,
+                                       asl_rig_calib_result *result, asl_pose_cov *cov, asl_cam_pose *poses)
+{
+    return rig_calibrate_batch(d, {obs, n_cams, n_frames, max_tags, map, n_ids, rig, tag_size, max_iters, sigma_px, rig_out, result, cov, poses});
 }
 
 // ---- mapping (k_map.inc)

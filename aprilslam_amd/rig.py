@@ -8,7 +8,9 @@ mounting.  A frame index is one instant for all cameras.
     RigCamera       one camera: K, dist (0, 4 or 5 coefficients), T_cam_rig = camera<-rig 4x4 (the mounting)
     Rig             the cameras in block order; as_records() -> RIG_CAMERA_DTYPE (asl_rig_camera), save / load,
                     localize(), localize_sequence() / localize_sequences(), build_map() / build_map_sized(),
-                    locate_tags() / extend_map(), from_camera_poses()
+                    locate_tags() / extend_map(), from_camera_poses(), calibrate_mountings()
+    RigCalibrationResult   what calibrate_mountings returns: the refined Rig, the result record, the mountings' covariances
+                    and the frames' poses
 
 Consecutive frames of the rig solved together under a random-walk motion prior (asl_smooth_rig_sequences_batch, k_smooth.inc):
 Rig.localize_sequence and Rig.localize_sequences return smooth.SmoothResult, its poses the rig's (world<-rig).  A frame in
@@ -24,7 +26,9 @@ MAX_CAMERAS = 16
 MAX_SLOTS = 256          # n_cams * max_tags
 ORTHONORMAL_TOL = 1e-6
 
-__all__ = ["Rig", "RigCamera", "RIG_CAMERA_DTYPE", "MAX_CAMERAS", "MAX_SLOTS"]
+MAX_CALIBRATED_CAMERAS = 8   # calibrate_mountings
+
+__all__ = ["Rig", "RigCamera", "RigCalibrationResult", "RIG_CAMERA_DTYPE", "MAX_CAMERAS", "MAX_SLOTS", "MAX_CALIBRATED_CAMERAS"]
 
 
 def _transform(T, what):
@@ -178,13 +182,28 @@ class Rig:
         return [SmoothResult(r[0][a:b], r[1][k], seed=None if seed is None else np.asarray(seed)[a:b], cov=r[2][a:b] if with_cov else None,
                              times=None if tm is None else tm[a:b]) for k, (a, b) in enumerate(zip(ss[:-1], ss[1:]))]
 
+    def calibrate_mountings(self, det, obs, tag_map, tag_size, max_iters=30, sigma_px=None):
+        """The mountings refined jointly with one rig pose per frame (Detector.calibrate_rig, asl_calibrate_rig_batch), this
+        rig's mountings the initial ones: obs (n_cams, n_frames, max_tags) OBS_DTYPE, camera-major, of a known tag_map ->
+        RigCalibrationResult.  Camera 0's mounting is the gauge and stays; a camera that shares no frame with the cameras
+        connected to camera 0 is held (result["cam_status"] 2).  2 to MAX_CALIBRATED_CAMERAS cameras.  sigma_px None or 0: the
+        covariances are scaled by the solve's own estimate.  There is no outlier gate: pass clean observations.  The frames
+        outside the joint solve (poses status 5) are localised under this rig's mountings: result.rig.localize() re-localises them."""
+        if not 2 <= len(self.cameras) <= MAX_CALIBRATED_CAMERAS:
+            raise ValueError("calibrate_mountings takes a rig of 2 to %d cameras" % MAX_CALIBRATED_CAMERAS)
+        rec, res, cov, poses = det.calibrate_rig(self._block(obs), tag_map, self.as_records(), tag_size, max_iters=max_iters, sigma_px=sigma_px)
+        return RigCalibrationResult(Rig.from_records(rec), res, cov, poses)
+
     @classmethod
     def from_camera_poses(cls, cams, poses_by_cam):
         """The mounting from per-camera localisations of the same frames.  cams: (K, dist) per camera; poses_by_cam:
         per camera an (n_frames,) CAM_POSE_DTYPE array (Detector.localize on that camera's stream).  The rig frame is
         camera 0.  For every frame where camera 0 and camera c both have status 0, E_c(f) = inv(T_wc_c(f)) T_wc_0(f); E_c is
         the rotation nearest to the mean of the R (SVD, det +1) and the mean translation.  The mountings are not refined
-        jointly with anything: this is the average of what the single-camera solves imply."""
+        jointly with anything: this is the average of what the single-camera solves imply.  calibrate_mountings() refines
+        them jointly, seeded from this average.  Where each camera sees one small tag, a single frame's pose can sit in its
+        mirrored minimum and poison the average: each camera's poses from TagDetector.localize_sequence (Detector.smooth) are
+        then the better input."""
         poses = [np.asarray(p, dtype=CAM_POSE_DTYPE).ravel() for p in poses_by_cam]
         if len(cams) != len(poses) or not poses or any(len(p) != len(poses[0]) for p in poses):
             raise ValueError("one (K, dist) and one pose array of the same frames per camera")
@@ -203,3 +222,39 @@ class Rig:
             T[:3, :3], T[:3, 3] = R, E[:, :3, 3].mean(axis=0)
             out.append(RigCamera(K, dist, T))
         return cls(out)
+
+
+class RigCalibrationResult:
+    """What Rig.calibrate_mountings returns: rig (a new Rig with the refined mountings; the given one where result["status"] is
+    not 0), result (RIG_CALIB_RESULT_DTYPE record), cov ((n_cams,) POSE_COV_DTYPE of the mountings, status 1 for camera 0
+    and for held cameras) and poses ((n_frames,) CAM_POSE_DTYPE, world<-rig)."""
+
+    def __init__(self, rig, result, cov, poses):
+        self.rig, self.result, self.cov, self.poses = rig, result, cov, poses
+
+    @property
+    def ok(self):
+        return int(self.result["status"]) == 0
+
+    def mounting_std(self):
+        """(n_cams, 6): the square roots of the covariance diagonals (rx ry rz in radians, px py pz in map units) of every
+        camera's mounting; zeros for a camera without a covariance"""
+        return np.sqrt(np.array([np.diag(c) for c in self.cov["cov"]]))
+
+    def save(self, path):
+        """Write the result as two files: the rig (Rig.save) at path, the records beside it at path + ".records.npz"."""
+        self.rig.save(path)
+        np.savez(_records_path(path), result=self.result, cov=self.cov, poses=self.poses)
+
+    @classmethod
+    def load(cls, path):
+        """The result RigCalibrationResult.save wrote."""
+        from ._lib import POSE_COV_DTYPE, RIG_CALIB_RESULT_DTYPE
+        rig = Rig.load(path if str(path).endswith(".npz") else str(path) + ".npz")
+        with np.load(_records_path(path)) as z:
+            return cls(rig, z["result"].astype(RIG_CALIB_RESULT_DTYPE).reshape(()), z["cov"].astype(POSE_COV_DTYPE), z["poses"].astype(CAM_POSE_DTYPE))
+
+
+def _records_path(path):
+    p = str(path)
+    return (p[:-4] if p.endswith(".npz") else p) + ".records.npz"

@@ -418,6 +418,53 @@ int asl_calibrate_batch(asl_detector *det, const asl_obs *obs, int n_frames, int
                         double tag_size, int width, int height, const double *K_init, int n_dist, int flags, int max_iters,
                         asl_calib_result *result, asl_cam_pose *poses);
 
+/* ---- rig mounting calibration: the mountings E_c = camera_c<-rig of a rig's cameras, refined jointly with one rig pose
+   per frame from the frames of a known tag map that two or more cameras see.  Every rig solver takes the mountings as
+   exact; this is the call that produces them (Rig.from_camera_poses averages single-camera poses and refines nothing). */
+typedef struct {
+    double rms_px;          /* final, per corner, over the frames used */
+    double rms_init_px;     /* the same frames at their seed poses under the mountings as given */
+    double sigma_px;        /* the pixel sigma that scaled the covariances (given, or estimated) */
+    int32_t n_frames_used, n_corners, iterations;
+    int32_t status;         /* 0 ok, 1 nothing to solve (no solved camera, or too few corners), 3 solve failed */
+    int32_t n_solved, reserved;
+    int32_t cam_status[16]; /* 0 solved, 1 the reference camera, 2 held (not connected to it); 0 past n_cams */
+    int32_t cam_frames[16]; /* the used frames in which the camera has a taking-part slot */
+} asl_rig_calib_result;     /* 176 bytes */
+
+/* d_obs, d_map, tag_size as for asl_localize_rig_frames_device; d_rig: n_cams asl_rig_camera whose E are the INITIAL
+   mountings (read back and checked before anything is enqueued, the one synchronous step).  Every frame is first
+   localised under those mountings with the gate off (exactly what asl_localize_rig_frames_device writes).  mask(f) is the
+   set of cameras with a taking-part slot (flags & 1, a valid map entry) in a frame whose seed has status 0.  Starting from
+   {camera 0}, a frame with two or more cameras in its mask, one of them reached, reaches them all (n_cams - 1 sweeps).
+   Used frames: two or more cameras, all reached.  Solved cameras: the reached ones but camera 0, whose E is the gauge and
+   stays as given (it need not be the identity).  A camera that is not reached is held: its mounting cannot be observed,
+   and its E comes back byte for byte.
+   Levenberg-Marquardt then refines the solved mountings (left update E <- [Rod(w) | v] E) and every used frame's pose
+   together, each frame eliminating its pose block (Schur complement), the reduced system (<= 42 x 42) solved by Cholesky;
+   the schedule is asl_calibrate_frames_device's (lambda0 1e-3, x0.1 / x10, at most max_iters >= 1 trials, stop at a
+   relative decrease below 1e-12).  There is no outlier gate: pass clean observations.
+   d_rig_out: n_cams asl_rig_camera, K / dist / n_dist copied, E refined for the solved cameras; it may be d_rig.
+   d_result: one asl_rig_calib_result; with status 1 or 3 d_rig_out equals d_rig.
+   d_cov: n_cams asl_pose_cov of the pose E_c in the (r, d) convention above, from sigma^2 S^-1 of the undamped reduced
+   system at the solution (sigma_px == 0: sigma^2 = cost / dof, dof = 2 n_corners - 6 n_frames_used - 6 n_solved, which is
+   the dof written); status 1 (zeros, dof 0) for camera 0, for held cameras and whenever the result status is not 0.
+   Covariances between cameras are not reported.
+   d_poses: n_frames asl_cam_pose, world<-rig.  Used frames: the refined pose, status 0, rms_px final, rms_seed_px and
+   seed_slot of the seed, n_tags the taking-part slots.  Other frames: the seed's record, status 5 where the seed's was 0
+   (localised under the initial mountings, outside the joint solve: asl_localize_rig_* with d_rig_out re-localises them),
+   else its 1 or 2.  Result status 1: every frame is such a frame; 3: the used frames keep the seed's record, status 4.
+   n_cams in [2, 8], max_tags in [1, 256], n_cams * max_tags <= 256, n_frames >= 1; sigma_px < 0 or non-finite, a bad
+   table or a NULL pointer is ASL_EINVAL, and nothing is written or enqueued.  The whole solve is enqueued on `stream`
+   without a wait; deterministic: the same input gives the same bytes.  tests/rig_calib_ref.py states the algorithm. */
+int asl_calibrate_rig_frames_device(asl_detector *det, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map,
+                                    int n_ids, const void *d_rig, double tag_size, int max_iters, double sigma_px, void *d_rig_out,
+                                    void *d_result, void *d_cov, void *d_poses, void *stream);
+/* The same computation on host records, synchronous (the detector keeps the device copies and grows them on demand). */
+int asl_calibrate_rig_batch(asl_detector *det, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_map_tag *map,
+                            int n_ids, const asl_rig_camera *rig, double tag_size, int max_iters, double sigma_px,
+                            asl_rig_camera *rig_out, asl_rig_calib_result *result, asl_pose_cov *cov, asl_cam_pose *poses);
+
 /* ---- tag-map reconstruction: the world<-tag pose of every tag a batch of frames sees, every frame's camera pose and a
    per-tag std, from the asl_obs block alone (no map given).  The output is the asl_map_tag block
    asl_localize_frames_device reads. */
