@@ -61,6 +61,7 @@ EXPORTS = [
     "asl_rectify_frames_device", "asl_rectify_u8", "asl_rectify_views_device", "asl_rectify_views_u8",
     "asl_localize_frames_device", "asl_localize_batch", "asl_localize_cov_frames_device", "asl_localize_cov_batch",
     "asl_pose_cov_device", "asl_solve_pnp_cov_batch", "asl_calibrate_frames_device", "asl_calibrate_batch",
+    "asl_calibrate_lens_frames_device", "asl_calibrate_lens_batch",
     "asl_localize_rig_frames_device", "asl_localize_rig_cov_frames_device", "asl_localize_rig_batch", "asl_localize_rig_cov_batch",
     "asl_calibrate_rig_frames_device", "asl_calibrate_rig_batch",
     "asl_map_frames_device", "asl_map_batch", "asl_map_robust_frames_device", "asl_map_robust_batch", "asl_map_rig_frames_device", "asl_map_rig_batch", "asl_map_sized_frames_device", "asl_map_sized_batch",
@@ -225,6 +226,9 @@ def load():
     calib = [vp] + obs_block + tag_map + [dbl, i32, i32, dp, i32, i32, i32, vp, vp]    # ..., tag_size, width, height, K_init, n_dist, flags, max_iters, the two results
     L.asl_calibrate_frames_device.argtypes = calib + [vp]
     L.asl_calibrate_batch.argtypes = calib
+    calib_lens = calib[:10] + [i32] + calib[10:]                  # ..., K_init, lens_model, n_dist, ...
+    L.asl_calibrate_lens_frames_device.argtypes = calib_lens + [vp]
+    L.asl_calibrate_lens_batch.argtypes = calib_lens
     calib_rig = rig[:9] + [i32, dbl, vp, vp, vp, vp]              # ..., rig, tag_size, max_iters, sigma_px, rig_out, result, cov, poses
     L.asl_calibrate_rig_frames_device.argtypes = calib_rig + [vp]
     L.asl_calibrate_rig_batch.argtypes = calib_rig
@@ -775,37 +779,49 @@ class Detector:
                                           _ptr(stream)))
 
     @staticmethod
-    def _calib_args(K_init, n_dist):
-        if int(n_dist) not in (0, 4, 5):
+    def _calib_args(K_init, n_dist, model=None):
+        """(array to keep alive, K_init pointer or None, lens_model or None: the call without a lens)"""
+        m = None
+        if model is not None:
+            m = LENS_MODELS.get(model, model)
+            if m not in (LENS_BROWN, LENS_FISHEYE):
+                raise ValueError("model must be 'brown' or 'fisheye'")
+        if m == LENS_FISHEYE:
+            if int(n_dist) not in (0, 4):
+                raise ValueError("a fisheye lens has 0 or 4 coefficients (k1, k2, k3, k4)")
+        elif int(n_dist) not in (0, 4, 5):
             raise ValueError("n_dist must be 0, 4 or 5")
         if K_init is None:
-            return None, None
+            return None, None, m
         Kc = np.ascontiguousarray(K_init, dtype=np.float64)
         if Kc.shape != (3, 3):
             raise ValueError("K_init must be 3x3")
-        return Kc, Kc.ctypes.data_as(_DP)
+        return Kc, Kc.ctypes.data_as(_DP), m
 
-    def calibrate(self, obs, tag_map, tag_size, width, height, K_init=None, n_dist=5, flags=0, max_iters=30):
+    def calibrate(self, obs, tag_map, tag_size, width, height, K_init=None, n_dist=5, flags=0, max_iters=30, model=None):
         """asl_calibrate_batch: host records obs (n_frames, max_tags) OBS_DTYPE of a target whose tag poses tag_map
         ((n_ids,) MAP_TAG_DTYPE or a localize.TagMap) gives -> (CALIB_RESULT_DTYPE record, (n_frames,) CAM_POSE_DTYPE).
-        tag_size is the size of the map entries whose size is 0: a target may mix tags of several sizes (TagMap.set_size)."""
+        tag_size is the size of the map entries whose size is 0: a target may mix tags of several sizes (TagMap.set_size).
+        model: "brown" or "fisheye" (n_dist 0 or 4: dist = k1 k2 k3 k4, from the corners of the RAW frames), through
+        asl_calibrate_lens_batch; None is the call without a lens, the Brown model."""
         o, m = _obs_records(obs), _map_records(tag_map)
-        keep, Kp = self._calib_args(K_init, n_dist)
+        keep, Kp, lens = self._calib_args(K_init, n_dist, model)
         res = np.zeros((), dtype=CALIB_RESULT_DTYPE)
         poses = np.zeros(o.shape[0], dtype=CAM_POSE_DTYPE)
-        check(self._L.asl_calibrate_batch(self._h, _data(o), o.shape[0], o.shape[1], _data(m), len(m), float(tag_size), int(width), int(height), Kp,
-                                          int(n_dist), int(flags), int(max_iters), res.ctypes.data, _data(poses)))
+        head = (self._h, _data(o), o.shape[0], o.shape[1], _data(m), len(m), float(tag_size), int(width), int(height), Kp)
+        tail = (int(n_dist), int(flags), int(max_iters), res.ctypes.data, _data(poses))
+        check(self._L.asl_calibrate_batch(*head, *tail) if lens is None else self._L.asl_calibrate_lens_batch(*head, lens, *tail))
         return res, poses
 
     def calibrate_device(self, obs_ptr, n_frames, max_tags, map_ptr, n_ids, tag_size, width, height, result_ptr, poses_ptr,
-                         K_init=None, n_dist=5, flags=0, max_iters=30, stream=0):
+                         K_init=None, n_dist=5, flags=0, max_iters=30, stream=0, model=None):
         """asl_calibrate_frames_device: obs_ptr (n_frames x max_tags asl_obs), map_ptr (n_ids asl_map_tag), result_ptr (one
         asl_calib_result) and poses_ptr (n_frames asl_cam_pose) are device addresses; the whole solve is enqueued on
-        `stream`, no wait."""
-        keep, Kp = self._calib_args(K_init, n_dist)
-        check(self._L.asl_calibrate_frames_device(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids),
-                                                  float(tag_size), int(width), int(height), Kp, int(n_dist), int(flags), int(max_iters),
-                                                  _ptr(result_ptr), _ptr(poses_ptr), _ptr(stream)))
+        `stream`, no wait.  model as in calibrate (asl_calibrate_lens_frames_device)."""
+        keep, Kp, lens = self._calib_args(K_init, n_dist, model)
+        head = (self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids), float(tag_size), int(width), int(height), Kp)
+        tail = (int(n_dist), int(flags), int(max_iters), _ptr(result_ptr), _ptr(poses_ptr), _ptr(stream))
+        check(self._L.asl_calibrate_frames_device(*head, *tail) if lens is None else self._L.asl_calibrate_lens_frames_device(*head, lens, *tail))
 
     def calibrate_rig(self, obs, tag_map, rig, tag_size, max_iters=30, sigma_px=None):
         """asl_calibrate_rig_batch: host records obs (n_cams, n_frames, max_tags) OBS_DTYPE, camera-major, against tag_map, with

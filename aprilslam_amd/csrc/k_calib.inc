@@ -20,6 +20,19 @@
 // corners are butterfly sums over the wave (butterfly_sum, k_wave.inc), sums over frames run over the list of used frames in
 // contiguous chunks of a fixed count, then over the chunks in order: no atomics, the same bytes on every run, and frames
 // that do not take part change nothing.  Latency-bound like k_localize.inc: ~4 dependent launches per iteration.
+//
+// The lens is a compile-time parameter of the kernels that project (CAL_LENS_BROWN: the above, CamDev; CAL_LENS_FISHEYE:
+// FishDev, the cv2.fisheye model of k_rectify.inc, theta = (fx, fy, cx, cy, k1, k2, k3, k4); tests/calib_fisheye_ref.py is
+// its statement).  A fisheye has no closed-form focal length and no pinhole planar pose, so its K0 and seeds come from a
+// focal ladder; k_calib_seed is replaced by three launches:
+//   k_calib_fish_seed  one wavefront per (frame, rung): the frame seeded under the equidistant (f_j, f_j, centre) -- the
+//                      <= 8 largest slots whose corners all lie within CAL_GATE rad of the axis, each slot's corner rays as
+//                      pinhole coordinates through the same homography and planar pose, scored over all corners under the
+//                      fisheye, pose-only LM -- its pose, cost and code per rung (one rung, K_init's, with K_init)
+//   k_calib_fish_pick  one workgroup: every rung summed over the taking-part frames (cal_list_sum), the argmin, theta0, the
+//                      winning rung's poses and seed records into place (or frame status 3)
+//   k_calib_fish_lin   per frame: the normal equations at (K0, k = 0, that pose)
+// k_calib_schur / solve / decide / finish read no lens; k_calib_step has it as a template parameter.
 
 struct CalibResultRec {  // == asl_calib_result, 216 bytes
     double K[9], dist[5], std[9];
@@ -54,7 +67,16 @@ struct CalibArgs {
     double half, width, height, Kinit[4];
     int n_frames, max_tags, n_ids, n_dist, flags, has_init, np, max_iters;
     int sel[9];
+    // the fisheye's focal ladder: rungs per frame (1 with K_init), and per (frame, rung) the seed pose (12), its cost and code
+    int lens, n_rungs;
+    double *lpose, *lcost;
+    int *lcode;
 };
+
+#define CAL_LENS_BROWN 0
+#define CAL_LENS_FISHEYE 1
+#define CAL_RUNGS 13
+#define CAL_GATE 1.3  // rad: a slot seeds only if the equidistant unprojection of all its corners lies within it
 
 #define CAL_FIX_ASPECT 2
 
@@ -70,7 +92,8 @@ __device__ __forceinline__ int cal_gather(const CalibArgs &a, int f, int lane, c
 
 // Homography (row-major 3x3) of the square (+-1, +-1), lb rb rt lt, onto the corners in x' = (u - cx) / s: the closed-form
 // unit square -> quad mapping, composed with (X, Y) -> ((X + 1) / 2, (Y + 1) / 2)
-__device__ __forceinline__ void cal_square_h(const float *cf, double cx, double cy, double s, double *H)
+template <class T>  // float: a record's corners; double: corner rays as pinhole coordinates
+__device__ __forceinline__ void cal_square_h(const T *cf, double cx, double cy, double s, double *H)
 {
     double x[4], y[4];
 #pragma unroll
@@ -162,10 +185,132 @@ __device__ __forceinline__ bool cal_rows(const CamDev &c, bool fix_aspect, doubl
     return true;
 }
 
+// ---- the fisheye lens (CAL_LENS_FISHEYE)
+struct FishDev {
+    double fx, fy, cx, cy, k1, k2, k3, k4;
+};
+
+__device__ __forceinline__ FishDev cal_fish(const double *th, int n_dist)
+{
+    FishDev c;
+    c.fx = th[0]; c.fy = th[1]; c.cx = th[2]; c.cy = th[3];
+    c.k1 = n_dist >= 4 ? th[4] : 0.0; c.k2 = n_dist >= 4 ? th[5] : 0.0;
+    c.k3 = n_dist >= 4 ? th[6] : 0.0; c.k4 = n_dist >= 4 ? th[7] : 0.0;
+    return c;
+}
+
+struct FishPt {  // what the intrinsic columns of a corner's rows need
+    double th, ex, ey, sx, sy;  // theta, (X / r, Y / r), (theta_d / r) (X, Y)
+};
+
+// A corner costs its pixel error unless it sits in the camera centre: no "behind the camera" under this lens
+__device__ __forceinline__ bool fish_in_range(const double *P) { return (P[0] * P[0] + P[1] * P[1]) + P[2] * P[2] > LOC_Z_MIN * LOC_Z_MIN; }
+
+// Pixel of camera point P under the fisheye: theta = atan2(r, Z) by the arctangent the rectification is defined by
+// (rectify_atan2_pos), theta_d = theta (1 + k1 theta^2 + ..), u = fx theta_d X / r + cx.  JAC: d uv / d P (2 x 3, row-major)
+// into Jp and the intrinsic columns' terms into pt.  On the axis (r = 0, Z > 0) both are the finite limit: the direction
+// (X / r, Y / r) counts as 0 and theta_d / r as 1 / Z, which leaves d u / d X = fx / Z, d v / d Y = fy / Z and zeros (the ray
+// straight backwards, r = 0 with Z < 0, has no image: (cx, cy) and a zero Jacobian).
+template <bool JAC>
+__device__ __forceinline__ void project_fisheye_dev(const FishDev &c, const double *P, double *uv, double *Jp, FishPt *pt)
+{
+    const double X = P[0], Y = P[1], Z = P[2];
+    const double rr = X * X + Y * Y, r = sqrt(rr);
+    const double th = rectify_atan2_pos(r, Z), t2 = th * th;
+    const double td = th * (1 + t2 * (c.k1 + t2 * (c.k2 + t2 * (c.k3 + t2 * c.k4))));
+    const bool on = r == 0;
+    const double ex = on ? 0.0 : X / r, ey = on ? 0.0 : Y / r;
+    const double s = on ? (Z > 0 ? 1 / Z : 0.0) : td / r;
+    uv[0] = c.fx * (s * X) + c.cx;
+    uv[1] = c.fy * (s * Y) + c.cy;
+    if constexpr (JAC) {
+        const double dtd = 1 + t2 * (3 * c.k1 + t2 * (5 * c.k2 + t2 * (7 * c.k3 + t2 * 9 * c.k4)));
+        const double rho2 = rr + Z * Z;
+        const double a = on ? s : dtd * Z / rho2;  // d theta_d / d r at fixed Z
+        const double b = -dtd * r / rho2;          // d theta_d / d Z at fixed r
+        Jp[0] = c.fx * (a * ex * ex + s * (1 - ex * ex)); Jp[1] = c.fx * ((a - s) * ex * ey); Jp[2] = c.fx * (b * ex);
+        Jp[3] = c.fy * ((a - s) * ex * ey); Jp[4] = c.fy * (a * ey * ey + s * (1 - ey * ey)); Jp[5] = c.fy * (b * ey);
+        pt->th = th; pt->ex = ex; pt->ey = ey; pt->sx = s * X; pt->sy = s * Y;
+    }
+}
+
+// The slot model of one fisheye camera for loc_pass (k_localize.inc): loc_corner's sums under this lens.  The shared bodies
+// there stay Brown-only; this is the calibration's own pass.
+struct CalFishCam {
+    const FishDev &cam;
+    int n;
+    __device__ __forceinline__ int nslots() const { return n; }
+    template <bool NE, bool ROBUST = false>
+    __device__ __forceinline__ double corner(int, const double *R, const double *t, const double *X, double iu, double iv, double *acc,
+                                             double = 0.0, bool * = nullptr) const
+    {
+        static_assert(!ROBUST, "the calibration has no robust loss");
+        double P[3], uv[2];
+        [[maybe_unused]] double Jp[6];
+        [[maybe_unused]] FishPt pt;
+#pragma unroll
+        for (int r = 0; r < 3; r++) P[r] = R[3 * r] * X[0] + R[3 * r + 1] * X[1] + R[3 * r + 2] * X[2] + t[r];
+        if (!fish_in_range(P)) return LOC_BEHIND_COST;
+        project_fisheye_dev<NE>(cam, P, uv, Jp, &pt);
+        const double r0 = uv[0] - iu, r1 = uv[1] - iv;
+        if constexpr (NE) {
+            const double nPx[9] = {0, P[2], -P[1], -P[2], 0, P[0], P[1], -P[0], 0};  // -[P]x
+            double J0[6], J1[6];
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                J0[k] = Jp[0] * nPx[k] + Jp[1] * nPx[3 + k] + Jp[2] * nPx[6 + k];
+                J0[3 + k] = Jp[k];
+                J1[k] = Jp[3] * nPx[k] + Jp[4] * nPx[3 + k] + Jp[5] * nPx[6 + k];
+                J1[3 + k] = Jp[3 + k];
+            }
+#pragma unroll
+            for (int a = 0; a < 6; a++) {
+                acc[21 + a] += J0[a] * r0 + J1[a] * r1;
+#pragma unroll
+                for (int b = 0; b <= a; b++) acc[TRI(a, b)] += J0[a] * J0[b] + J1[a] * J1[b];
+            }
+        }
+        return r0 * r0 + r1 * r1;
+    }
+};
+
+// cal_rows under the fisheye, over (w, v, fx, fy, cx, cy, k1, k2, k3, k4, residual): d u / d k_i = fx (X / r) theta^(2 i + 1);
+// false if the corner sits in the camera centre
+template <int NT>
+__device__ __forceinline__ bool cal_rows(const FishDev &c, bool fix_aspect, double ratio, const double *R, const double *t, const double *X,
+                                         double iu, double iv, double *J0, double *J1)
+{
+    static_assert(NT == 11 || NT == 15, "a fisheye has 0 or 4 coefficients");
+    double P[3], uv[2], Jp[6];
+    FishPt pt;
+#pragma unroll
+    for (int r = 0; r < 3; r++) P[r] = R[3 * r] * X[0] + R[3 * r + 1] * X[1] + R[3 * r + 2] * X[2] + t[r];
+    if (!fish_in_range(P)) return false;
+    project_fisheye_dev<true>(c, P, uv, Jp, &pt);
+    const double nPx[9] = {0, P[2], -P[1], -P[2], 0, P[0], P[1], -P[0], 0};  // -[P]x
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        J0[k] = Jp[0] * nPx[k] + Jp[1] * nPx[3 + k] + Jp[2] * nPx[6 + k];
+        J0[3 + k] = Jp[k];
+        J1[k] = Jp[3] * nPx[k] + Jp[4] * nPx[3 + k] + Jp[5] * nPx[6 + k];
+        J1[3 + k] = Jp[3 + k];
+    }
+    J0[6] = pt.sx; J0[7] = fix_aspect ? ratio * pt.sx : 0.0; J0[8] = 1.0; J0[9] = 0.0;
+    J1[6] = 0.0; J1[7] = pt.sy; J1[8] = 0.0; J1[9] = 1.0;
+    if constexpr (NT >= 15) {
+        const double t2 = pt.th * pt.th, p3 = pt.th * t2, p5 = p3 * t2, p7 = p5 * t2, p9 = p7 * t2;
+        J0[10] = c.fx * pt.ex * p3; J0[11] = c.fx * pt.ex * p5; J0[12] = c.fx * pt.ex * p7; J0[13] = c.fx * pt.ex * p9;
+        J1[10] = c.fy * pt.ey * p3; J1[11] = c.fy * pt.ey * p5; J1[12] = c.fy * pt.ey * p7; J1[13] = c.fy * pt.ey * p9;
+    }
+    J0[NT - 1] = uv[0] - iu;
+    J1[NT - 1] = uv[1] - iv;
+    return true;
+}
+
 // Entries [LO, HI) of the frame's packed augmented normal equations, summed over its corners and written to Hf.  The
 // triangle is built in chunks so that the accumulators stay in registers (the corner's rows are recomputed per chunk).
-template <int NT, int LO, int HI>
-__device__ __forceinline__ void cal_chunk(const CamDev &c, bool fa, double ratio, const double *R, const double *t, const LocLds &L, int n4,
+template <int NT, int LO, int HI, class Cam>  // Cam: CamDev or FishDev, by cal_rows' overloads
+__device__ __forceinline__ void cal_chunk(const Cam &c, bool fa, double ratio, const double *R, const double *t, const LocLds &L, int n4,
                                           int lane, double *Hf)
 {
     constexpr int NTRI = NT * (NT + 1) / 2;
@@ -195,8 +340,8 @@ __device__ __forceinline__ void cal_chunk(const CamDev &c, bool fa, double ratio
     }
 }
 
-template <int NT>
-__device__ __forceinline__ void cal_linearise(const CamDev &c, bool fa, double ratio, const double *R, const double *t, const LocLds &L, int n4,
+template <int NT, class Cam>
+__device__ __forceinline__ void cal_linearise(const Cam &c, bool fa, double ratio, const double *R, const double *t, const LocLds &L, int n4,
                                               int lane, double *Hf)
 {
     constexpr int NTRI = NT * (NT + 1) / 2, C = (NTRI + 3) / 4;
@@ -307,7 +452,7 @@ __global__ void __launch_bounds__(64) k_calib_init(CalibArgs a)
         double hs = a.half;
         if (!((fl & 1) && id >= 0 && id < a.n_ids && map_tag_half(a.map[id], hs))) continue;
         npart++;
-        if (a.has_init) continue;
+        if (a.has_init || a.lens != CAL_LENS_BROWN) continue;  // no closed form to feed
         float cf[8];
 #pragma unroll
         for (int q = 0; q < 8; q++) cf[q] = fo[k].corners[q];
@@ -351,7 +496,7 @@ __global__ void __launch_bounds__(CAL_WG) k_calib_k0(CalibArgs a)
     const int n = cal_make_list(a, s_cnt);
     double th[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, ratio = 1.0;
     int status = n == 0 ? 1 : 0;
-    if (status == 0 && !a.has_init) {
+    if (status == 0 && !a.has_init && a.lens == CAL_LENS_BROWN) {
         cal_list_sum(a.zh, CAL_ZH, CAL_ZH, a.list, n, s_part, s_sum);
         const double s = 0.5 * (a.width + a.height);
         const double pp = s_sum[0], pq = s_sum[1], qq = s_sum[2], pc = s_sum[3], qc = s_sum[4], ee = s_sum[5], ec = s_sum[6];
@@ -369,7 +514,7 @@ __global__ void __launch_bounds__(CAL_WG) k_calib_k0(CalibArgs a)
         }
         if (!(fa > 1e-6 && fb > 1e-6 && isfinite(fa) && isfinite(fb))) status = 2;
         else { th[0] = s / sqrt(fa); th[1] = s / sqrt(fb); th[2] = 0.5 * a.width; th[3] = 0.5 * a.height; }
-    } else if (status == 0) {
+    } else if (status == 0 && a.has_init) {  // (a fisheye without K_init: k_calib_fish_pick writes theta0)
         th[0] = a.Kinit[0]; th[1] = a.Kinit[1]; th[2] = a.Kinit[2]; th[3] = a.Kinit[3];
         ratio = a.Kinit[0] / a.Kinit[1];
     }
@@ -433,6 +578,149 @@ __global__ void __launch_bounds__(64) k_calib_seed(CalibArgs a)
         a.fr[CAL_FR * f + 2] = code;
     }
     cal_linearise<NT>(cam0, (a.flags & CAL_FIX_ASPECT) != 0, a.st->ratio, R, t, L, n4, lane, a.H + (size_t)CAL_HS * f);
+}
+
+// ---- the fisheye's seed: one wavefront per (frame, rung)
+
+// f_j = max(width, height) / pi * 2^((j - 4) / 4): the quarter powers of two are four constants times an exact power of two
+__device__ __forceinline__ double cal_rung_focal(int j, double width, double height)
+{
+    const int q = j - 4, m = q & 3, e = (q - m) / 4;  // q = 4 e + m, 0 <= m < 4
+    const double quarter = m == 0 ? 1.0 : m == 1 ? 1.189207115002721 : m == 2 ? 1.4142135623730951 : 1.681792830507429;
+    const double two_e = e >= 0 ? (double)(1 << e) : 1.0 / (double)(1 << -e);
+    return (fmax(width, height) / 3.141592653589793) * (quarter * two_e);
+}
+
+__global__ void __launch_bounds__(64) k_calib_fish_seed(CalibArgs a)
+{
+    extern __shared__ double s_dyn[];
+    const int f = blockIdx.x, j = blockIdx.y, lane = threadIdx.x;
+    if (a.st->status != 0 || a.fr[CAL_FR * f] != 0 || j >= a.n_rungs) return;
+    const LocLds L = loc_lds(s_dyn, a.max_tags);
+    cal_gather(a, f, lane, L);
+    const ObsRec *fo = a.obs + (size_t)f * a.max_tags;
+    double th[4];
+    if (a.has_init) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) th[i] = a.st->theta[0][i];
+    } else {
+        th[0] = th[1] = cal_rung_focal(j, a.width, a.height);
+        th[2] = 0.5 * a.width; th[3] = 0.5 * a.height;
+    }
+    const FishDev cam0 = cal_fish(th, 0);
+    const CalFishCam model{cam0, a.max_tags};
+    auto pass = [&](const double *R, const double *t, auto ne_tag, double *ne) {
+        return loc_pass<decltype(ne_tag)::value>(model, R, t, L, lane, ne);
+    };
+
+    // the gate: a slot with a corner further than CAL_GATE from the axis does not seed (a lane reads back its own slots)
+    for (int s = lane; s < a.max_tags; s += ASL_WAVE) {
+        if (L.state[s] != 1) continue;
+        bool in = true;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const double xd = ((double)L.uv[2 * (4 * s + q)] - th[2]) / th[0], yd = ((double)L.uv[2 * (4 * s + q) + 1] - th[3]) / th[1];
+            in = in && sqrt(xd * xd + yd * yd) <= CAL_GATE;
+        }
+        if (!in) L.area[s] = -1.0;
+    }
+    __syncthreads();
+    int sel[LOC_MAX_SEEDS];
+    const int nsel = loc_top_k(a.max_tags, lane, [&](int k) { return L.area[k]; }, sel);
+    auto make = [&](int k) {
+        double c8[8], H[9], To[12], M[12];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {  // the corner's ray as pinhole coordinates: (tan(theta) / theta) (xd, yd)
+            const double xd = ((double)fo[k].corners[2 * q] - th[2]) / th[0], yd = ((double)fo[k].corners[2 * q + 1] - th[3]) / th[1];
+            const double ang = sqrt(xd * xd + yd * yd), kk = ang > 0 ? tan(ang) / ang : 1.0;
+            c8[2 * q] = kk * xd; c8[2 * q + 1] = kk * yd;
+        }
+        cal_square_h(c8, 0.0, 0.0, 1.0, H);
+        double hs = a.half;
+        map_tag_half(a.map[fo[k].id], hs);  // the slot's own half
+        cal_planar_pose(H, 1.0, 1.0, 1.0, hs, To);
+        const double *Mp = a.map[fo[k].id].T;
+#pragma unroll
+        for (int i = 0; i < 12; i++) M[i] = Mp[i];
+        return [=](bool mirror, double *C) { loc_candidate(To, M, mirror, C, C + 9); };
+    };
+    double Pb[12], best = INFINITY;
+    const int code = loc_best_candidate(sel, nsel, make, [&](const double *C) { return pass(C, C + 9, std::false_type{}, nullptr); }, best, Pb);
+    const size_t o = (size_t)f * a.n_rungs + j;
+    if (!(best < LOC_BEHIND_COST)) {  // no candidate at this rung: the rung pays LOC_BEHIND_COST for the frame
+        if (lane == 0) { a.lcost[o] = LOC_BEHIND_COST; a.lcode[o] = -1; }
+        return;
+    }
+    double *R = Pb, *t = Pb + 9;
+    const double cost = pose_lm(pass, R, t);
+    if (lane == 0) {
+        double *P = a.lpose + 12 * o;
+#pragma unroll
+        for (int i = 0; i < 9; i++) P[i] = R[i];
+        P[9] = t[0]; P[10] = t[1]; P[11] = t[2];
+        a.lcost[o] = cost;
+        a.lcode[o] = code;
+    }
+}
+
+// ---- one workgroup: the rungs' scores over the taking-part frames, the winner, theta0, its seeds into place
+__global__ void __launch_bounds__(CAL_WG) k_calib_fish_pick(CalibArgs a)
+{
+    __shared__ double s_part[CAL_WG], s_sum[64];
+    __shared__ int s_any, s_j;
+    CalibState *st = a.st;
+    if (st->status != 0) return;
+    const int n = st->n_take, nr = a.n_rungs;
+    cal_list_sum(a.lcost, nr, nr, a.list, n, s_part, s_sum);
+    if (threadIdx.x == 0) {
+        int jb = 0;
+        for (int j = 1; j < nr; j++)
+            if (s_sum[j] < s_sum[jb]) jb = j;  // ties: the lower rung
+        s_j = jb;
+        s_any = 0;
+    }
+    __syncthreads();
+    const int jw = s_j;
+    for (int k = threadIdx.x; k < n; k += CAL_WG)
+        if (a.lcode[(size_t)a.list[k] * nr + jw] >= 0) s_any = 1;
+    __syncthreads();
+    // no frame has a candidate at the winning rung: status 2, the frames stay taking part (status 4).  With K_init there is
+    // no ladder to fail: the frames are dropped and k_calib_start finds none (status 1), as under the Brown lens.
+    const bool none = !s_any && !a.has_init;
+    for (int k = threadIdx.x; k < n && !none; k += CAL_WG) {
+        const int f = a.list[k];
+        const size_t o = (size_t)f * nr + jw;
+        if (a.lcode[o] < 0) { a.fr[CAL_FR * f] = 3; continue; }
+        for (int i = 0; i < 12; i++) a.pose[(size_t)12 * f + i] = a.lpose[12 * o + i];  // buffer 0: cur = 0 at the start
+        a.seedc[f] = a.lcost[o];
+        a.fr[CAL_FR * f + 2] = a.lcode[o];
+    }
+    if (threadIdx.x == 0) {
+        if (none) { st->status = 2; st->done = 1; }
+        else if (!a.has_init) {
+            const double fj = cal_rung_focal(jw, a.width, a.height);
+            const double th[4] = {fj, fj, 0.5 * a.width, 0.5 * a.height};
+            for (int i = 0; i < 4; i++) { st->theta[0][i] = th[i]; st->theta[1][i] = th[i]; }
+        }
+    }
+}
+
+// ---- per frame: the normal equations at (K0, k = 0, the seed pose)
+template <int ND>
+__global__ void __launch_bounds__(64) k_calib_fish_lin(CalibArgs a)
+{
+    constexpr int NT = 11 + ND;
+    extern __shared__ double s_dyn[];
+    const int f = blockIdx.x, lane = threadIdx.x, n4 = 4 * a.max_tags;
+    if (a.st->status != 0 || a.fr[CAL_FR * f] != 0) return;
+    const LocLds L = loc_lds(s_dyn, a.max_tags);
+    cal_gather(a, f, lane, L);
+    const double *P = a.pose + (size_t)12 * f;
+    double R[9], t[3];
+#pragma unroll
+    for (int i = 0; i < 9; i++) R[i] = P[i];
+    t[0] = P[9]; t[1] = P[10]; t[2] = P[11];
+    cal_linearise<NT>(cal_fish(a.st->theta[0], 0), (a.flags & CAL_FIX_ASPECT) != 0, a.st->ratio, R, t, L, n4, lane, a.H + (size_t)CAL_HS * f);
 }
 
 // ---- one workgroup: used frames, initial cost, lambda0
@@ -548,7 +836,7 @@ __global__ void __launch_bounds__(CAL_WG) k_calib_solve(CalibArgs a)
 }
 
 // ---- per used frame: the pose step, the trial pose and its normal equations
-template <int ND>
+template <int ND, int LENS = CAL_LENS_BROWN>
 __global__ void __launch_bounds__(64) k_calib_step(CalibArgs a)
 {
     constexpr int NT = 11 + ND;
@@ -581,8 +869,11 @@ __global__ void __launch_bounds__(64) k_calib_step(CalibArgs a)
     }
     const LocLds L = loc_lds(s_dyn, a.max_tags);
     cal_gather(a, f, lane, L);
-    const CamDev c = cal_cam(st->theta[1 - cur], ND, a.half);
-    cal_linearise<NT>(c, (a.flags & CAL_FIX_ASPECT) != 0, st->ratio, R, t, L, n4, lane, a.H + ((size_t)(1 - cur) * a.n_frames + f) * CAL_HS);
+    double *Hn = a.H + ((size_t)(1 - cur) * a.n_frames + f) * CAL_HS;
+    if constexpr (LENS == CAL_LENS_FISHEYE)
+        cal_linearise<NT>(cal_fish(st->theta[1 - cur], ND), (a.flags & CAL_FIX_ASPECT) != 0, st->ratio, R, t, L, n4, lane, Hn);
+    else
+        cal_linearise<NT>(cal_cam(st->theta[1 - cur], ND, a.half), (a.flags & CAL_FIX_ASPECT) != 0, st->ratio, R, t, L, n4, lane, Hn);
 }
 
 // ---- one workgroup: accept or reject the trial

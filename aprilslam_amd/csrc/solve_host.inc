@@ -299,13 +299,15 @@ extern "C" int asl_solve_pnp_cov_batch(asl_detector *d, const float *corners, co
 // ---- calibration (k_calib.inc)
 
 // One calibration call, in the entry points' argument order; K_init may be NULL.  obs, map, result and poses are all host
-// (asl_calibrate_batch) or all device pointers (asl_calibrate_frames_device); no field is left empty by either.
+// (asl_calibrate_batch, asl_calibrate_lens_batch) or all device pointers (the *_frames_device forms); no field is left empty
+// by either.  lens_model comes last here: the asl_calibrate_* forms leave it out, which is ASL_LENS_BROWN.
 struct CalibCall {
     const void *obs; int n_frames, max_tags;
     const void *map; int n_ids;
     double tag_size; int width, height;
     const double *K_init; int n_dist, flags, max_iters;
     void *result, *poses;
+    int lens_model;
 };
 
 // every refusal, before anything is written or enqueued; the same for both forms
@@ -319,6 +321,11 @@ static int check_calibrate_call(const asl_detector *d, const CalibCall &c, bool)
     if (c.max_iters < 1) return fail(ASL_EINVAL, "max_iters must be >= 1 (got %d)", c.max_iters);
     if (c.flags & ~(ASL_CALIB_FIX_PRINCIPAL_POINT | ASL_CALIB_FIX_ASPECT_RATIO | ASL_CALIB_ZERO_TANGENT_DIST))
         return fail(ASL_EINVAL, "unknown calibration flags 0x%x", c.flags);
+    if (c.lens_model != ASL_LENS_BROWN && c.lens_model != ASL_LENS_FISHEYE) return fail(ASL_EINVAL, "lens_model must be 0 or 1 (got %d)", c.lens_model);
+    if (c.lens_model == ASL_LENS_FISHEYE) {
+        if (c.n_dist != 0 && c.n_dist != 4) return fail(ASL_EINVAL, "a fisheye lens has 0 or 4 coefficients (got n_dist = %d)", c.n_dist);
+        if (c.flags & ASL_CALIB_ZERO_TANGENT_DIST) return fail(ASL_EINVAL, "ASL_CALIB_ZERO_TANGENT_DIST has no meaning under the fisheye lens");
+    }
     if (const double *K = c.K_init; K && !(K[0] > 0 && K[4] > 0 && std::isfinite(K[0]) && std::isfinite(K[4]) && std::isfinite(K[2]) && std::isfinite(K[5])))
         return fail(ASL_EINVAL, "K_init must have finite, positive focal lengths");
     return ASL_OK;
@@ -328,11 +335,16 @@ static int check_calibrate_call(const asl_detector *d, const CalibCall &c, bool)
 static int launch_calibrate(asl_detector *d, const CalibCall &c, hipStream_t st)
 {
     const size_t nf = (size_t)c.n_frames;
+    const bool fisheye = c.lens_model == ASL_LENS_FISHEYE;
     CalibArgs a{};
+    a.lens = fisheye ? CAL_LENS_FISHEYE : CAL_LENS_BROWN;
+    a.n_rungs = fisheye ? (c.K_init ? 1 : CAL_RUNGS) : 0;  // the ladder's room: none under the Brown lens
+    const size_t nl = nf * (size_t)a.n_rungs;
     if (carve_ws(d->cal_ws, [&](WsCarve &w) {
             a.st = w.take<CalibState>(1); a.list = w.take<int>(nf); a.fr = w.take<int>(CAL_FR * nf);
             a.zh = w.take<double>(CAL_ZH * nf); a.seedc = w.take<double>(nf); a.pose = w.take<double>(2 * 12 * nf);
             a.H = w.take<double>(2 * CAL_HS * nf); a.SB = w.take<double>(CAL_SB * nf); a.back = w.take<double>(CAL_BK * nf);
+            a.lpose = w.take<double>(12 * nl); a.lcost = w.take<double>(nl); a.lcode = w.take<int>(nl);
         }))
         return fail(ASL_ENOMEM, "calibration workspace allocation failed");
     a.obs = (const ObsRec *)c.obs; a.map = (const MapTagRec *)c.map;
@@ -342,7 +354,7 @@ static int launch_calibrate(asl_detector *d, const CalibCall &c, hipStream_t st)
     a.has_init = c.K_init != nullptr;
     if (c.K_init) { a.Kinit[0] = c.K_init[0]; a.Kinit[1] = c.K_init[4]; a.Kinit[2] = c.K_init[2]; a.Kinit[3] = c.K_init[5]; }
     a.n_frames = c.n_frames; a.max_tags = c.max_tags; a.n_ids = c.n_ids; a.n_dist = c.n_dist; a.flags = c.flags; a.max_iters = c.max_iters;
-    int np = 0;  // the free entries of (fx, fy, cx, cy, k1, k2, p1, p2, k3)
+    int np = 0;  // the free entries of (fx, fy, cx, cy, k1, k2, p1, p2, k3); a fisheye: (.., k1, k2, k3, k4), all four free
     if (!(c.flags & ASL_CALIB_FIX_ASPECT_RATIO)) a.sel[np++] = 0;
     a.sel[np++] = 1;
     if (!(c.flags & ASL_CALIB_FIX_PRINCIPAL_POINT)) { a.sel[np++] = 2; a.sel[np++] = 3; }
@@ -356,9 +368,15 @@ static int launch_calibrate(asl_detector *d, const CalibCall &c, hipStream_t st)
     const size_t lds = loc_lds_bytes(c.max_tags);
     auto seed = c.n_dist == 5 ? k_calib_seed<5> : c.n_dist == 4 ? k_calib_seed<4> : k_calib_seed<0>;
     auto step = c.n_dist == 5 ? k_calib_step<5> : c.n_dist == 4 ? k_calib_step<4> : k_calib_step<0>;
+    if (fisheye) step = c.n_dist == 4 ? k_calib_step<4, CAL_LENS_FISHEYE> : k_calib_step<0, CAL_LENS_FISHEYE>;
     hipLaunchKernelGGL(k_calib_init, frames, wave, 0, st, a);
     hipLaunchKernelGGL(k_calib_k0, dim3(1), wg, 0, st, a);
-    hipLaunchKernelGGL(seed, frames, wave, lds, st, a);
+    if (fisheye) {
+        hipLaunchKernelGGL(k_calib_fish_seed, dim3((unsigned int)c.n_frames, (unsigned int)a.n_rungs), wave, lds, st, a);
+        hipLaunchKernelGGL(k_calib_fish_pick, dim3(1), wg, 0, st, a);
+        hipLaunchKernelGGL(c.n_dist == 4 ? k_calib_fish_lin<4> : k_calib_fish_lin<0>, frames, wave, lds, st, a);
+    } else
+        hipLaunchKernelGGL(seed, frames, wave, lds, st, a);
     hipLaunchKernelGGL(k_calib_start, dim3(1), wg, 0, st, a);
     for (int it = 0; it < c.max_iters; it++) {
         hipLaunchKernelGGL(k_calib_schur, frames, wave, 0, st, a, 0);
@@ -397,6 +415,22 @@ extern "C" int asl_calibrate_batch(asl_detector *d, const asl_obs *obs, int n_fr
                                    asl_calib_result *result, asl_cam_pose *poses)
 {
     return calibrate_batch(d, {obs, n_frames, max_tags, map, n_ids, tag_size, width, height, K_init, n_dist, flags, max_iters, result, poses});
+}
+
+// the same call records with the lens named: ASL_LENS_BROWN is the two entry points above
+extern "C" int asl_calibrate_lens_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                                double tag_size, int width, int height, const double *K_init, int lens_model, int n_dist, int flags,
+                                                int max_iters, void *d_result, void *d_poses, void *stream)
+{
+    return calibrate_frames_device(d, {d_obs, n_frames, max_tags, d_map, n_ids, tag_size, width, height, K_init, n_dist, flags, max_iters, d_result, d_poses, lens_model},
+                                   stream);
+}
+
+extern "C" int asl_calibrate_lens_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                        double tag_size, int width, int height, const double *K_init, int lens_model, int n_dist, int flags,
+                                        int max_iters, asl_calib_result *result, asl_cam_pose *poses)
+{
+    return calibrate_batch(d, {obs, n_frames, max_tags, map, n_ids, tag_size, width, height, K_init, n_dist, flags, max_iters, result, poses, lens_model});
 }
 
 // ---- rig mounting calibration (k_rigcal.inc)

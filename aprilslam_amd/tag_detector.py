@@ -39,9 +39,10 @@ class TagDetector:
         into the frame the camera delivered), and every pose call uses the pinhole rectified_K (default: the camera matrix)
         with no distortion.  False, the default, is the path without the keyword.
         lens_model: "brown" (dist_coeffs k1 k2 p1 p2 [k3]) or "fisheye" (dist_coeffs k1 k2 k3 k4, the cv2.fisheye model).  A
-        fisheye needs rectify=True, since no solver takes that lens: the frames go through asl_rectify_views_u8 /
+        fisheye needs rectify=True, since no pose solver takes that lens: the frames go through asl_rectify_views_u8 /
         asl_rectify_views_device into the one view rectified_K with R the identity.  A field of view no single pinhole
-        holds takes several views: rectify.ViewSet."""
+        holds takes several views: rectify.ViewSet.  A fisheye's K and coefficients come from
+        calibrate(.., lens_model="fisheye") of a detector on the raw frames."""
         if lens_model not in ("brown", "fisheye"):
             raise ValueError("lens_model must be 'brown' or 'fisheye'")
         if lens_model == "fisheye" and not rectify:
@@ -294,12 +295,15 @@ class TagDetector:
                 for k, (a, b) in enumerate(zip(start[:-1], start[1:]))]
 
     # -- camera calibration from frames of a known target (asl_calibrate_batch) ------------------------------------------
-    def calibrate(self, frames, tag_map, n_dist=5, K_init=None, flags=0, max_iters=30):
+    def calibrate(self, frames, tag_map, n_dist=5, K_init=None, flags=0, max_iters=30, lens_model="brown"):
         """Host frames ((n, H, W, 3) BGR or (n, H, W) gray uint8, or a list of them) that see the target tag_map (a
         localize.TagMap, e.g. TagMap.grid) -> calibrate.CalibrationResult: K, dist (n_dist coefficients), std, per-frame
         poses.  Detect, pack (asl_obs records) and calibrate; this detector's own camera model is not used.  Pass the
         result's camera_params to a TagDetector afterwards.  The target may mix tag sizes (TagMap.set_size); this detector's
-        tag_size is the size of the tags that have none of their own."""
+        tag_size is the size of the tags that have none of their own.
+        lens_model "fisheye" (n_dist 0 or 4: k1 k2 k3 k4): the frames are the fisheye's RAW frames, detected as they are --
+        tags out to some 75 degrees off axis are found there -- by a detector made with rectify=False; the result goes to
+        TagDetector(cr.camera_params, lens_model="fisheye", rectify=True) or cr.view_set(..)."""
         from .calibrate import CalibrationResult
         from .dist import pack_observations
         if self.rectify:
@@ -312,9 +316,11 @@ class TagDetector:
         npf = np.asarray(npf, dtype=np.int64)
         mt = max(1, min(256, int(npf.max()) if len(npf) else 1))
         obs = pack_observations(dets, np.zeros(len(dets), dtype=_lib.POSE_DTYPE), npf, mt)  # the calibration reads no PnP pose
+        if lens_model not in ("brown", "fisheye"):
+            raise ValueError("lens_model must be 'brown' or 'fisheye'")
         res, cam = self.detector._det.calibrate(obs, tag_map, self.tag_size, width, height, K_init=K_init, n_dist=n_dist, flags=flags,
-                                                max_iters=max_iters)
-        return CalibrationResult(res, cam, n_dist)
+                                                max_iters=max_iters, model=None if lens_model == "brown" else lens_model)
+        return CalibrationResult(res, cam, n_dist, lens_model)
 
     def build_map(self, frames, world_id=None, max_iters=30, with_std=True, huber_px=0.0, tag_sizes=None):
         """Host frames ((n, H, W, 3) BGR or (n, H, W) gray uint8, or a list of them) that see an unknown set of tags ->

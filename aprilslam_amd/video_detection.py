@@ -15,13 +15,16 @@ from .tag_detector import TagDetector
 
 def load_camera_calibration(calibration_path=None):
     """{'camera_matrix', 'dist_coeffs'} from an .npz written by the reference's calibration tool
-    (video_detection.py:33-66: same keys, same exceptions: FileNotFoundError, KeyError)."""
+    (video_detection.py:33-66: same keys, same exceptions: FileNotFoundError, KeyError).  A file that names its lens
+    (CalibrationResult.save_npz of a fisheye) also gives 'lens_model'."""
     if calibration_path is None:
         calibration_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'data', 'calibration',
                                         'camera_calibration_parameters.npz')
     try:
         with np.load(calibration_path) as data:
             camera_params = {'camera_matrix': data['camera_matrix'], 'dist_coeffs': data['dist_coeffs']}
+            if 'lens_model' in data.files:
+                camera_params['lens_model'] = str(data['lens_model'])
         print(f"Loaded camera calibration from: {calibration_path}")
         return camera_params
     except FileNotFoundError:

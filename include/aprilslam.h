@@ -996,6 +996,34 @@ int asl_rectify_views_u8(asl_detector *det, const uint8_t *src, int channels, in
                          const double *dist, int n_dist, int lens_model, const asl_rectify_view *views, int n_views,
                          double theta_max, int fill);
 
+/* ---- camera calibration with the lens named: asl_calibrate_frames_device / asl_calibrate_batch with lens_model before
+   n_dist, the same asl_calib_result (216 bytes), per-frame records, statuses, schedule and uncertainty.
+   ASL_LENS_BROWN: those two calls, byte for byte.
+   ASL_LENS_FISHEYE: the cv2.fisheye model as asl_rectify_views_device states it (the same arctangent), n_dist 0 (pure
+     equidistant) or 4: dist[0..3] = k1 k2 k3 k4 and std[4..7] their standard deviations, dist[4] and std[8] are 0.  What a
+     150-200 degree lens needs before asl_rectify_views_device can serve it: calibrate from the RAW frames' corners, then
+     rectify with the K and dist this returns.  A corner past 90 degrees off axis is an ordinary corner (none is "behind the
+     camera"; a corner costs 1e12 only in the camera centre itself, |P| <= 1e-9), and on the axis projection and Jacobian
+     are their finite limits.  Neither Zhang's closed form nor the planar pose of a quad holds under this lens, so without
+     K_init the principal point starts at the image centre and the focal length comes from a ladder of 13 rungs
+     f_j = max(width, height) / pi * 2^((j - 4) / 4), j = 0..12: at each rung every taking-part frame is seeded under the
+     equidistant (f_j, f_j, centre) -- of the slots whose four corners all unproject to within 1.3 rad of the axis, the <= 8
+     of largest area; each slot's corner rays as pinhole coordinates give its planar pose and the mirrored minimum, scored
+     over all the frame's corners under the fisheye; the strictly lowest is refined by the pose-only LM -- and the rung's
+     score is the sum of its frames' seed costs plus 1e12 per frame without a candidate; the lowest score wins (ties: the
+     lower rung); status 2 if no frame has a candidate there.  With K_init the ladder is skipped and the frames are seeded
+     under K_init.  A frame without a candidate at K0 gets status 3.  rms_init_px is the rms after the seed under K0 with
+     k = 0.  The joint LM's columns are (w, v, fx, fy, cx, cy, k1, k2, k3, k4).  One submission, no host wait,
+     deterministic.  tests/calib_fisheye_ref.py states the algorithm.
+   ASL_EINVAL, nothing written: everything asl_calibrate_frames_device refuses; lens_model not 0 or 1; ASL_LENS_FISHEYE
+   with n_dist not 0 or 4 or with ASL_CALIB_ZERO_TANGENT_DIST. */
+int asl_calibrate_lens_frames_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                     double tag_size, int width, int height, const double *K_init /* 9 or NULL */, int lens_model,
+                                     int n_dist, int flags, int max_iters, void *d_result, void *d_poses, void *stream);
+int asl_calibrate_lens_batch(asl_detector *det, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                             double tag_size, int width, int height, const double *K_init, int lens_model, int n_dist, int flags,
+                             int max_iters, asl_calib_result *result, asl_cam_pose *poses);
+
 /* ---- introspection and diagnostics.  asl_debug_fetch, asl_stage_times and the counters (item 5) describe the LAST batch
    the detector ran.  asl_detect_batch_u8 and asl_detect_batch_pose_u8 run a call of 128 frames or more as consecutive
    batches of 64 frames, so after such a call that is the call's last chunk (frames 128..149 of a 150-frame call), not the

@@ -8,6 +8,11 @@ warm-up), per iteration, and the errors against the renderer's camera: fx / fy r
 field's worst pixel difference over a 16 x 16 image grid.
 
     python tools/calib_lab.py [--frames 1024] [--reps 10] [--iters 30]
+
+--fisheye: the fisheye calibration (asl_calibrate_lens_frames_device, ASL_LENS_FISHEYE) instead, on corners projected on the
+host: --frames random views of the 5 x 7 board of tests/calib_fisheye_cases.py through its 640 x 480 lens, float32 corners
+with --noise px of Gaussian noise.  The same JSON line, the errors against that lens (the field error over rays within 95
+degrees of the axis).
 """
 import argparse
 import json
@@ -31,7 +36,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--max-tags", type=int, default=16)
+    ap.add_argument("--fisheye", action="store_true")
+    ap.add_argument("--noise", type=float, default=0.3)
     a = ap.parse_args()
+    if a.fisheye:
+        return fisheye(a)
 
     import torch
 
@@ -88,6 +97,54 @@ def main():
         "fx_rel_err": float(res["K"][0, 0] / K[0, 0] - 1), "fy_rel_err": float(res["K"][1, 1] / K[1, 1] - 1),
         "cx_err_px": float(res["K"][0, 2] - K[0, 2]), "cy_err_px": float(res["K"][1, 2] - K[1, 2]),
         "dist_field_err_px": CC.field_err(res["K"], res["dist"], K, DIST, W, H), "std": [float(v) for v in res["std"]],
+    }))
+    det.close()
+
+
+def fisheye(a):
+    import torch
+
+    import calib_fisheye_cases as FC
+    from aprilslam_amd import _lib
+    from aprilslam_amd.calibrate import CALIB_RESULT_DTYPE
+    from aprilslam_amd.localize import CAM_POSE_DTYPE
+
+    dev = torch.device("cuda:0")
+    n, mt = a.frames, FC.MAX_TAGS
+    rng = np.random.default_rng(11)
+    rec = FC.board_map().as_records()
+    # (distance, two tilts, roll, turn off axis, its direction), the ranges of the test views
+    views = zip(rng.uniform(35, 70, n), rng.uniform(-30, 30, n), rng.uniform(-30, 30, n), rng.uniform(-180, 180, n), rng.uniform(0, 55, n),
+                rng.uniform(0, 360, n))
+    obs = np.stack([FC.exact_row(rec, *FC.view_pose(v), FC.K_TRUE, FC.DIST, noise=(rng, a.noise) if a.noise > 0 else None) for v in views])
+    det = _lib.Detector("tagStandard41h12", id_limit=0)
+    stream = torch.cuda.Stream(dev)
+    st = stream.cuda_stream
+    d_obs = torch.from_numpy(obs.view(np.uint8).copy()).to(dev)
+    d_map = torch.from_numpy(rec.view(np.uint8)).to(dev)
+    d_res = torch.empty(CALIB_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    d_poses = torch.empty((n, CAM_POSE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+    times = []
+    for r in range(a.warmup + a.reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        det.calibrate_device(d_obs.data_ptr(), n, mt, d_map.data_ptr(), len(rec), FC.LC.TAG_INNER, FC.W, FC.H, d_res.data_ptr(), d_poses.data_ptr(),
+                             n_dist=4, max_iters=a.iters, stream=st, model="fisheye")
+        e1.record(stream)
+        stream.synchronize()
+        if r >= a.warmup:
+            times.append(e0.elapsed_time(e1))
+    res = d_res.cpu().numpy().view(CALIB_RESULT_DTYPE)[0]
+    ms = float(np.median(times))
+    K = FC.K_TRUE
+    print(json.dumps({
+        "lens": "fisheye", "frames": n, "frames_used": int(res["n_frames_used"]), "corners": int(res["n_corners"]), "status": int(res["status"]),
+        "iterations": int(res["iterations"]), "max_iters": a.iters, "noise_px": a.noise, "ms_per_solve": round(ms, 4),
+        "ms_per_iteration": round(ms / a.iters, 5), "rms_px": float(res["rms_px"]), "rms_init_px": float(res["rms_init_px"]),
+        "fx_rel_err": float(res["K"][0, 0] / K[0, 0] - 1), "fy_rel_err": float(res["K"][1, 1] / K[1, 1] - 1),
+        "cx_err_px": float(res["K"][0, 2] - K[0, 2]), "cy_err_px": float(res["K"][1, 2] - K[1, 2]),
+        "dist_field_err_px": FC.field_err(res["K"], res["dist"][:4], K, FC.DIST), "std": [float(v) for v in res["std"]],
     }))
     det.close()
 
