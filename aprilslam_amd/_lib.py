@@ -60,12 +60,14 @@ EXPORTS = [
     "asl_detect_bgr_u8", "asl_detect_batch_u8", "asl_detect_batch_pose_u8", "asl_detect_batch_device", "asl_submit_batch_device", "asl_collect_batch", "asl_collect_batch_view", "asl_solve_pnp_batch", "asl_gn_solve", "asl_pack_observations_device", "asl_graph_frames_device", "asl_graph_picks_device", "asl_render_frames_device",
     "asl_rectify_frames_device", "asl_rectify_u8", "asl_rectify_views_device", "asl_rectify_views_u8",
     "asl_localize_frames_device", "asl_localize_batch", "asl_localize_cov_frames_device", "asl_localize_cov_batch",
+    "asl_localize_mapcov_frames_device", "asl_localize_mapcov_batch", "asl_localize_rig_mapcov_frames_device", "asl_localize_rig_mapcov_batch",
     "asl_pose_cov_device", "asl_solve_pnp_cov_batch", "asl_calibrate_frames_device", "asl_calibrate_batch",
     "asl_calibrate_lens_frames_device", "asl_calibrate_lens_batch",
     "asl_localize_rig_frames_device", "asl_localize_rig_cov_frames_device", "asl_localize_rig_batch", "asl_localize_rig_cov_batch",
     "asl_calibrate_rig_frames_device", "asl_calibrate_rig_batch",
     "asl_map_frames_device", "asl_map_batch", "asl_map_robust_frames_device", "asl_map_robust_batch", "asl_map_rig_frames_device", "asl_map_rig_batch", "asl_map_sized_frames_device", "asl_map_sized_batch",
-    "asl_map_rig_sized_frames_device", "asl_map_rig_sized_batch", "asl_smooth_frames_device", "asl_smooth_batch", "asl_smooth_cov_frames_device", "asl_smooth_cov_batch",
+    "asl_map_rig_sized_frames_device", "asl_map_rig_sized_batch",
+    "asl_mapcov_frames_device", "asl_mapcov_batch", "asl_mapcov_rig_frames_device", "asl_mapcov_rig_batch", "asl_smooth_frames_device", "asl_smooth_batch", "asl_smooth_cov_frames_device", "asl_smooth_cov_batch",
     "asl_smooth_sequences_device", "asl_smooth_sequences_batch", "asl_smooth_robust_sequences_device", "asl_smooth_robust_sequences_batch",
     "asl_smooth_timed_sequences_device", "asl_smooth_timed_sequences_batch",
     "asl_smooth_rig_sequences_device", "asl_smooth_rig_sequences_batch",
@@ -216,11 +218,16 @@ def load():
     L.asl_localize_batch.argtypes = loc + [vp]
     L.asl_localize_cov_frames_device.argtypes = loc + [dbl, vp, vp, vp]
     L.asl_localize_cov_batch.argtypes = loc + [dbl, vp, vp]
+    map_cov_in = [vp, i32, vp]                                    # map_cov, ld, cov_slot: after the _cov forms' cov
+    L.asl_localize_mapcov_frames_device.argtypes = loc + [dbl, vp, vp] + map_cov_in + [vp]
+    L.asl_localize_mapcov_batch.argtypes = loc + [dbl, vp, vp] + map_cov_in
     rig = [vp, vp, i32, i32, i32] + tag_map + [vp, dbl, dbl]      # detector, obs, n_cams, n_frames, max_tags, ..., rig, tag_size, max_tag_rms_px
     L.asl_localize_rig_frames_device.argtypes = rig + [vp, vp]
     L.asl_localize_rig_batch.argtypes = rig + [vp]
     L.asl_localize_rig_cov_frames_device.argtypes = rig + [dbl, vp, vp, vp]
     L.asl_localize_rig_cov_batch.argtypes = rig + [dbl, vp, vp]
+    L.asl_localize_rig_mapcov_frames_device.argtypes = rig + [dbl, vp, vp] + map_cov_in + [vp]
+    L.asl_localize_rig_mapcov_batch.argtypes = rig + [dbl, vp, vp] + map_cov_in
     L.asl_pose_cov_device.argtypes = [vp, vp, i32] + camera + [dbl, vp, vp]
     L.asl_solve_pnp_cov_batch.argtypes = [vp, C.POINTER(C.c_float), dp] + camera + [dbl, vp, i32]
     calib = [vp] + obs_block + tag_map + [dbl, i32, i32, dp, i32, i32, i32, vp, vp]    # ..., tag_size, width, height, K_init, n_dist, flags, max_iters, the two results
@@ -246,6 +253,11 @@ def load():
     L.asl_map_sized_batch.argtypes = mapping_robust[:9] + [fp] + mapping_robust[9:]
     L.asl_map_rig_sized_frames_device.argtypes = mapping_rig[:8] + [fp] + mapping_rig[8:] + [vp]
     L.asl_map_rig_sized_batch.argtypes = mapping_rig[:8] + [fp] + mapping_rig[8:]
+    map_cov = [vp, vp, i32]                                       # cov_slot, map_cov, cap_tags: after the sized forms' slot_weight
+    L.asl_mapcov_frames_device.argtypes = L.asl_map_sized_batch.argtypes + map_cov + [vp]
+    L.asl_mapcov_batch.argtypes = L.asl_map_sized_batch.argtypes + map_cov
+    L.asl_mapcov_rig_frames_device.argtypes = L.asl_map_rig_sized_batch.argtypes + map_cov + [vp]
+    L.asl_mapcov_rig_batch.argtypes = L.asl_map_rig_sized_batch.argtypes + map_cov
     smooth, seqs = [vp] + obs_block + tag_map + camera + [vp], [C.POINTER(C.c_int32), i32]    # ..., seed; seq_start, n_seq
     solve = sigmas + [i32, vp, vp]                                # ..., max_iters, out, result
     L.asl_smooth_frames_device.argtypes = smooth + solve + [vp]
@@ -356,6 +368,22 @@ def _obs_records(obs):
     if o.ndim != 2:
         raise ValueError("obs must be (n_frames, max_tags) asl_obs records")
     return o
+
+
+def _map_cov_args(map_cov, n_ids):
+    """(cov_slot (n_ids,) int32, matrix C-contiguous float64, ld) of a mapping.MapCovariance or a (cov_slot, matrix) pair"""
+    if hasattr(map_cov, "as_args"):
+        return map_cov.as_args(n_ids)
+    slot, mat = map_cov
+    slot = np.ascontiguousarray(slot, dtype=np.int32).ravel()
+    mat = np.ascontiguousarray(mat, dtype=np.float64)
+    if len(slot) != n_ids:
+        raise ValueError("cov_slot has %d entries, the map %d" % (len(slot), n_ids))
+    if mat.ndim != 2 or mat.shape[0] != mat.shape[1] or mat.shape[0] % 6:
+        raise ValueError("the map covariance must be a square matrix of 6 x 6 blocks")
+    if mat.shape[0] == 0:
+        mat = np.zeros((6, 6))
+    return slot, mat, mat.shape[1]
 
 
 def _map_records(tag_map):
@@ -631,12 +659,16 @@ class Detector:
         check(self._L.asl_graph_picks_device(self._h, _ptr(obs_ptr), int(world), int(n_frames), int(max_tags), _ptr(status_ptr),
                                              int(order_lo), int(order_hi), _ptr(last_ptr), int(n_ids), _ptr(picks_ptr), _ptr(stream)))
 
-    def localize(self, obs, tag_map, K, dist, tag_size, max_tag_rms_px=0.0, sigma_px=None):
+    def localize(self, obs, tag_map, K, dist, tag_size, max_tag_rms_px=0.0, sigma_px=None, map_cov=None):
         """asl_localize_batch: host records obs (n_frames, max_tags) OBS_DTYPE (e.g. dist.pack_observations) against
         tag_map (n_ids,) MAP_TAG_DTYPE (or a localize.TagMap) -> (n_frames,) CAM_POSE_DTYPE, world<-camera per frame.
         sigma_px not None: asl_localize_cov_batch -> (poses, (n_frames,) POSE_COV_DTYPE), the covariance scaled by that
         corner sigma, or by the solve's own estimate for 0.
-        tag_size is the size of the map entries whose size is 0; an entry with a size of its own (TagMap.set_size) is solved at it."""
+        tag_size is the size of the map entries whose size is 0; an entry with a size of its own (TagMap.set_size) is solved at it.
+        map_cov (a mapping.MapCovariance, or (cov_slot, matrix) as build_map(with_cov=True) returns them; with sigma_px):
+        asl_localize_mapcov_batch -- the uncertainty of the map's tags is carried into the covariances."""
+        if map_cov is not None and sigma_px is None:
+            raise ValueError("map_cov needs the covariance form: give sigma_px (0: estimated from the solve)")
         o, m = _obs_records(obs), _map_records(tag_map)
         keep, Kp, dpp, nd = _camera(K, dist, square=True)
         out = np.zeros(o.shape[0], dtype=CAM_POSE_DTYPE)
@@ -645,26 +677,37 @@ class Detector:
             check(self._L.asl_localize_batch(*args, _data(out)))
             return out
         cov = np.zeros(o.shape[0], dtype=POSE_COV_DTYPE)
+        if map_cov is not None:
+            slot, mat, ld = _map_cov_args(map_cov, len(m))
+            check(self._L.asl_localize_mapcov_batch(*args, float(sigma_px), _data(out), _data(cov), mat.ctypes.data, ld, slot.ctypes.data))
+            return out, cov
         check(self._L.asl_localize_cov_batch(*args, float(sigma_px), _data(out), _data(cov)))
         return out, cov
 
     def localize_device(self, obs_ptr, n_frames, max_tags, map_ptr, n_ids, out_ptr, K, dist, tag_size, max_tag_rms_px=0.0,
-                        stream=0, cov_ptr=None, sigma_px=0.0):
+                        stream=0, cov_ptr=None, sigma_px=0.0, map_cov=None):
         """asl_localize_frames_device: obs_ptr (n_frames x max_tags asl_obs, e.g. from pack_observations_device), map_ptr
         (n_ids asl_map_tag) and out_ptr (n_frames asl_cam_pose) are device addresses; enqueued on `stream`, no wait.
-        cov_ptr not None (n_frames asl_pose_cov): asl_localize_cov_frames_device with sigma_px."""
+        cov_ptr not None (n_frames asl_pose_cov): asl_localize_cov_frames_device with sigma_px.  map_cov, (map_cov_ptr, ld,
+        cov_slot_ptr) as build_map_device's cov wrote them (ld = 6 cap_tags), with cov_ptr: asl_localize_mapcov_frames_device."""
         keep, Kp, dpp, nd = _camera(K, dist, square=True)
         args = (self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids), Kp, dpp, nd, float(tag_size), float(max_tag_rms_px))
-        if cov_ptr is None:
+        if map_cov is not None:
+            check(self._L.asl_localize_mapcov_frames_device(*args, float(sigma_px), _ptr(out_ptr), _opt_ptr(cov_ptr), _opt_ptr(map_cov[0]), int(map_cov[1]),
+                                                            _opt_ptr(map_cov[2]), _ptr(stream)))
+        elif cov_ptr is None:
             check(self._L.asl_localize_frames_device(*args, _ptr(out_ptr), _ptr(stream)))
         else:
             check(self._L.asl_localize_cov_frames_device(*args, float(sigma_px), _ptr(out_ptr), _ptr(cov_ptr), _ptr(stream)))
 
-    def localize_rig(self, obs, tag_map, rig, tag_size, max_tag_rms_px=0.0, sigma_px=None):
+    def localize_rig(self, obs, tag_map, rig, tag_size, max_tag_rms_px=0.0, sigma_px=None, map_cov=None):
         """asl_localize_rig_batch: host records obs (n_cams, n_frames, max_tags) OBS_DTYPE, camera-major, against tag_map and
         the camera table rig ((n_cams,) RIG_CAMERA_DTYPE, or a rig.Rig) -> (n_frames,) CAM_POSE_DTYPE, world<-rig per frame.
         sigma_px not None: asl_localize_rig_cov_batch -> (poses, (n_frames,) POSE_COV_DTYPE), as localize.
-        tag_size is the size of the map entries whose size is 0, as in localize."""
+        tag_size is the size of the map entries whose size is 0, as in localize.  map_cov as in localize:
+        asl_localize_rig_mapcov_batch."""
+        if map_cov is not None and sigma_px is None:
+            raise ValueError("map_cov needs the covariance form: give sigma_px (0: estimated from the solve)")
         o = np.ascontiguousarray(obs, dtype=OBS_DTYPE)
         if o.ndim != 3:
             raise ValueError("obs must be (n_cams, n_frames, max_tags) asl_obs records")
@@ -678,17 +721,25 @@ class Detector:
             check(self._L.asl_localize_rig_batch(*args, _data(out)))
             return out
         cov = np.zeros(o.shape[1], dtype=POSE_COV_DTYPE)
+        if map_cov is not None:
+            slot, mat, ld = _map_cov_args(map_cov, len(m))
+            check(self._L.asl_localize_rig_mapcov_batch(*args, float(sigma_px), _data(out), _data(cov), mat.ctypes.data, ld, slot.ctypes.data))
+            return out, cov
         check(self._L.asl_localize_rig_cov_batch(*args, float(sigma_px), _data(out), _data(cov)))
         return out, cov
 
     def localize_rig_device(self, obs_ptr, n_cams, n_frames, max_tags, map_ptr, n_ids, rig_ptr, out_ptr, tag_size, max_tag_rms_px=0.0,
-                            stream=0, cov_ptr=None, sigma_px=0.0):
+                            stream=0, cov_ptr=None, sigma_px=0.0, map_cov=None):
         """asl_localize_rig_frames_device: obs_ptr (n_cams x n_frames x max_tags asl_obs, camera-major), map_ptr (n_ids
         asl_map_tag), rig_ptr (n_cams asl_rig_camera, complete when the call is made) and out_ptr (n_frames asl_cam_pose) are
-        device addresses; enqueued on `stream`.  cov_ptr not None (n_frames asl_pose_cov): asl_localize_rig_cov_frames_device."""
+        device addresses; enqueued on `stream`.  cov_ptr not None (n_frames asl_pose_cov): asl_localize_rig_cov_frames_device.
+        map_cov as in localize_device: asl_localize_rig_mapcov_frames_device."""
         args = (self._h, _ptr(obs_ptr), int(n_cams), int(n_frames), int(max_tags), _ptr(map_ptr), int(n_ids), _ptr(rig_ptr), float(tag_size),
                 float(max_tag_rms_px))
-        if cov_ptr is None:
+        if map_cov is not None:
+            check(self._L.asl_localize_rig_mapcov_frames_device(*args, float(sigma_px), _ptr(out_ptr), _opt_ptr(cov_ptr), _opt_ptr(map_cov[0]),
+                                                                int(map_cov[1]), _opt_ptr(map_cov[2]), _ptr(stream)))
+        elif cov_ptr is None:
             check(self._L.asl_localize_rig_frames_device(*args, _ptr(out_ptr), _ptr(stream)))
         else:
             check(self._L.asl_localize_rig_cov_frames_device(*args, float(sigma_px), _ptr(out_ptr), _ptr(cov_ptr), _ptr(stream)))
@@ -854,36 +905,39 @@ class Detector:
                                                       _ptr(result_ptr), _ptr(cov_ptr), _ptr(poses_ptr), _ptr(stream)))
 
     def build_map(self, obs, n_ids, K, dist, tag_size, world_id=-1, max_iters=30, with_std=True, huber_px=0.0, with_slot_weight=False,
-                  tag_sizes=None):
+                  tag_sizes=None, with_cov=False):
         """asl_map_batch: host records obs (n_frames, max_tags) OBS_DTYPE that see an unknown set of tags -> (MAP_RESULT_DTYPE
         record, (n_ids,) MAP_TAG_DTYPE world<-tag map, (n_ids, 6) tag std or None, (n_frames,) CAM_POSE_DTYPE world<-camera).
         huber_px > 0 or with_slot_weight: asl_map_robust_batch -- a Huber loss of that many pixels on every corner residual of
         the joint LM (0: the plain computation); the result's n_soft counts the down-weighted observations.
         with_slot_weight: a fifth item, (n_frames, max_tags) doubles: a slot's smallest corner weight, 0 outside the solve.
         tag_sizes ({id: size} or n_ids sizes; 0: tag_size): asl_map_sized_batch -- tags of different known sizes, each solved
-        at its own and returned with it in the map's size field."""
+        at its own and returned with it in the map's size field.
+        with_cov: asl_mapcov_batch -- a last item (cov_slot (n_ids,) int32, matrix): the joint covariance of the mapped tags
+        other than the world tag, block cov_slot[id] of the 6 n_cov x 6 n_cov matrix (mapping.MapCovariance wraps the pair)."""
         o = _obs_records(obs)
         keep, Kp, dpp, nd = _camera(K, dist, square=True)
         return self._map_host(o, o.shape[0], n_ids, [o.shape[0], o.shape[1]], [Kp, dpp, nd], False, tag_size, tag_sizes, world_id, huber_px,
-                              max_iters, with_std, with_slot_weight)
+                              max_iters, with_std, with_slot_weight, with_cov)
 
     def build_map_device(self, obs_ptr, n_frames, max_tags, n_ids, K, dist, tag_size, map_ptr, std_ptr, poses_ptr, result_ptr,
-                         world_id=-1, max_iters=30, stream=0, huber_px=0.0, slot_weight_ptr=0, tag_sizes=None):
+                         world_id=-1, max_iters=30, stream=0, huber_px=0.0, slot_weight_ptr=0, tag_sizes=None, cov=None):
         """asl_map_frames_device: obs_ptr (n_frames x max_tags asl_obs, e.g. from pack_observations_device), map_ptr (n_ids
         asl_map_tag, out), std_ptr (n_ids x 6 doubles or 0), poses_ptr (n_frames asl_cam_pose) and result_ptr (one
         asl_map_result) are device addresses; enqueued on `stream` after one wait for the problem size.
         huber_px > 0 or slot_weight_ptr (n_frames x max_tags doubles): asl_map_robust_frames_device.
-        tag_sizes ({id: size} or n_ids sizes, on the host): asl_map_sized_frames_device."""
+        tag_sizes ({id: size} or n_ids sizes, on the host): asl_map_sized_frames_device.
+        cov, (cov_slot_ptr (n_ids int32), map_cov_ptr (6 cap_tags x 6 cap_tags doubles), cap_tags): asl_mapcov_frames_device."""
         keep, Kp, dpp, nd = _camera(K, dist, square=True)
         self._map_call(True, obs_ptr, [int(n_frames), int(max_tags)], n_ids, [Kp, dpp, nd], False, tag_size, tag_sizes, world_id, huber_px, max_iters,
-                       (map_ptr, std_ptr, poses_ptr, result_ptr), slot_weight_ptr, stream)
+                       (map_ptr, std_ptr, poses_ptr, result_ptr), slot_weight_ptr, stream, cov)
 
     def build_map_rig(self, obs, n_ids, rig, tag_size, world_id=-1, max_iters=30, with_std=True, huber_px=0.0, with_slot_weight=False,
-                      tag_sizes=None):
+                      tag_sizes=None, with_cov=False):
         """asl_map_rig_batch: host records obs (n_cams, n_frames, max_tags) OBS_DTYPE, camera-major, of a rig whose camera table
         is rig ((n_cams,) RIG_CAMERA_DTYPE, or a rig.Rig) -> build_map's items with poses = world<-rig per frame; huber_px as
         there (0: the squared loss).  with_slot_weight: a fifth item, (n_cams, n_frames, max_tags) doubles.  tag_sizes as
-        there: asl_map_rig_sized_batch."""
+        there: asl_map_rig_sized_batch.  with_cov as there: asl_mapcov_rig_batch."""
         o = np.ascontiguousarray(obs, dtype=OBS_DTYPE)
         if o.ndim != 3:
             raise ValueError("obs must be (n_cams, n_frames, max_tags) asl_obs records")
@@ -891,30 +945,43 @@ class Detector:
         if len(r) != o.shape[0]:
             raise ValueError("the rig has %d cameras, obs has %d" % (len(r), o.shape[0]))
         return self._map_host(o, o.shape[1], n_ids, list(o.shape), [_data(r)], True, tag_size, tag_sizes, world_id, huber_px, max_iters, with_std,
-                              with_slot_weight)
+                              with_slot_weight, with_cov)
 
     def build_map_rig_device(self, obs_ptr, n_cams, n_frames, max_tags, n_ids, rig_ptr, tag_size, map_ptr, std_ptr, poses_ptr, result_ptr,
-                             world_id=-1, max_iters=30, stream=0, huber_px=0.0, slot_weight_ptr=0, tag_sizes=None):
+                             world_id=-1, max_iters=30, stream=0, huber_px=0.0, slot_weight_ptr=0, tag_sizes=None, cov=None):
         """asl_map_rig_frames_device: obs_ptr (n_cams x n_frames x max_tags asl_obs, camera-major), rig_ptr (n_cams asl_rig_camera,
         complete when the call is made) and the outputs of build_map_device (slot_weight_ptr: n_cams x n_frames x max_tags
         doubles or 0) are device addresses; enqueued on `stream` after one wait for the problem size.  tag_sizes ({id: size} or
-        n_ids sizes, on the host): asl_map_rig_sized_frames_device."""
+        n_ids sizes, on the host): asl_map_rig_sized_frames_device.  cov as in build_map_device: asl_mapcov_rig_frames_device."""
         self._map_call(True, obs_ptr, [int(n_cams), int(n_frames), int(max_tags)], n_ids, [rig_ptr], True, tag_size, tag_sizes, world_id, huber_px,
-                       max_iters, (map_ptr, std_ptr, poses_ptr, result_ptr), slot_weight_ptr, stream)
+                       max_iters, (map_ptr, std_ptr, poses_ptr, result_ptr), slot_weight_ptr, stream, cov)
 
-    def _map_host(self, o, n_frames, n_ids, dims, model, rig, tag_size, tag_sizes, world_id, huber_px, max_iters, with_std, with_slot_weight):
-        """the host form of _map_call on the block o: the outputs allocated, build_map's items back"""
+    def _map_host(self, o, n_frames, n_ids, dims, model, rig, tag_size, tag_sizes, world_id, huber_px, max_iters, with_std, with_slot_weight,
+                  with_cov=False):
+        """the host form of _map_call on the block o: the outputs allocated, build_map's items back; with_cov: one more item,
+        (cov_slot (n_ids,) int32, the 6 n_cov x 6 n_cov joint covariance).  The matrix is sized by the distinct ids of the block's
+        flags & 1 slots, which bounds the tags of the problem."""
         res = np.zeros((), dtype=MAP_RESULT_DTYPE)
         tmap = np.zeros(max(int(n_ids), 1), dtype=MAP_TAG_DTYPE)
         std = np.zeros((max(int(n_ids), 1), 6), dtype=np.float64) if with_std else None
         poses = np.zeros(n_frames, dtype=CAM_POSE_DTYPE)
         weight = np.zeros(o.shape, dtype=np.float64) if with_slot_weight else None
+        cov = slot = mat = None
+        if with_cov:
+            seen = np.unique(o["id"][(o["flags"] & 1) != 0])
+            cap = max(int(((seen >= 0) & (seen < int(n_ids))).sum()) - 1, 1)
+            slot, mat = np.full(max(int(n_ids), 1), -1, dtype=np.int32), np.zeros((6 * cap, 6 * cap), dtype=np.float64)
+            cov = (slot.ctypes.data, mat.ctypes.data, cap)
         self._map_call(False, _data(o), dims, n_ids, model, rig, tag_size, tag_sizes, world_id, huber_px, max_iters,
                        (tmap.ctypes.data, std.ctypes.data if with_std else None, _data(poses), res.ctypes.data),
-                       weight.ctypes.data if with_slot_weight else None)
-        return (res, tmap, std, poses, weight) if with_slot_weight else (res, tmap, std, poses)
+                       weight.ctypes.data if with_slot_weight else None, cov=cov)
+        out = (res, tmap, std, poses, weight) if with_slot_weight else (res, tmap, std, poses)
+        if with_cov:
+            n = 6 * int((slot >= 0).sum())
+            out += ((slot, np.ascontiguousarray(mat[:n, :n])),)
+        return out
 
-    def _map_call(self, device, obs, dims, n_ids, model, rig, tag_size, tag_sizes, world_id, huber_px, max_iters, outs, weight, stream=0):
+    def _map_call(self, device, obs, dims, n_ids, model, rig, tag_size, tag_sizes, world_id, huber_px, max_iters, outs, weight, stream=0, cov=None):
         """The one tag-map call.  Its entry point, _batch or (device) _frames_device, whose addresses are then the device's:
 
             rig  tag_sizes  huber_px or weight   entry
@@ -924,20 +991,26 @@ class Detector:
             yes  no         any                  asl_map_rig
             yes  yes        any                  asl_map_rig_sized  (tag_sizes after tag_size)
 
+        cov, (cov_slot, map_cov, cap_tags): asl_mapcov / asl_mapcov_rig, the sized lists (tag_sizes may be None there) with
+        the three after the slot weights.
         dims: the block's extents; model: K, dist, n_dist or [the rig table's address]; outs: map, std (optional), poses, result."""
         sized = tag_sizes is not None
-        robust = bool(rig or sized or huber_px or (weight if device else weight is not None))
+        robust = bool(rig or sized or huber_px or cov or (weight if device else weight is not None))
         table = _size_table(tag_sizes, n_ids) if sized else None
         req, opt = (_ptr, _opt_ptr) if device else (lambda p: p, lambda p: p)
         args = [self._h, req(obs)] + dims + [int(n_ids)] + ([req(model[0])] if rig else model) + [float(tag_size)]
-        if sized:
-            args.append(table.ctypes.data_as(C.POINTER(C.c_float)))
+        if sized or cov:
+            args.append(table.ctypes.data_as(C.POINTER(C.c_float)) if sized else None)
         args += [int(world_id)] + ([float(huber_px)] if robust else []) + [int(max_iters), req(outs[0]), opt(outs[1]), req(outs[2]), req(outs[3])]
         if robust:
             args.append(opt(weight))
+        if cov:
+            args += [req(cov[0]), req(cov[1]), int(cov[2])]
         if device:
             args.append(_ptr(stream))
         name = "asl_map" + ("_rig" if rig else "") + ("_sized" if sized else "" if rig or not robust else "_robust")
+        if cov:
+            name = "asl_mapcov" + ("_rig" if rig else "")
         check(getattr(self._L, name + ("_frames_device" if device else "_batch"))(*args))
 
     def smooth(self, obs, tag_map, K, dist, tag_size, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20, seed=None,

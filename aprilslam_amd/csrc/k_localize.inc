@@ -13,6 +13,8 @@
 //           again (one slot at a time, at most 8)
 //   cov     k_localize<true> only (asl_localize_cov_*): one more linearisation at the pose written, then lane c solves column c
 //           of sigma^2 (J^T J)^-1 in the output convention (pose_cov_column_dev, k_pnp.inc; tests/pose_cov_ref.py)
+//   mapcov  k_localize_mapcov only (asl_localize_mapcov_*): the map's joint covariance carried into that covariance
+//           (loc_map_term; tests/localize_mapcov_ref.py)
 // tests/localize_ref.py is the NumPy statement of the same computation.  Latency-bound scalar float64 like k_pnp.inc:
 // the time goes into the dependent chains of the passes and reductions, not into bytes (136 B per slot in, 160 B per frame out).
 // These steps are written once, in loc_solve_frame<COV, Model>, over the slots of a model: where slot g's record lives,
@@ -120,6 +122,14 @@ struct LocOneCam {
                                              double hk = 0.0, bool *over = nullptr) const
     {
         return loc_corner<NE, ROBUST>(cam, R, t, X, iu, iv, acc, hk, over);
+    }
+    // d uv / d Pb (2 x 3) of a corner of slot s at the body point Pb = R X + t, here the camera's own; false behind the camera
+    __device__ __forceinline__ bool jac(int, const double *Pb, double *Jr) const
+    {
+        if (!(Pb[2] > LOC_Z_MIN)) return false;
+        double uv[2];
+        project_dev(cam, Pb, uv, Jr);
+        return true;
     }
     // the solved pose (R, t) that slot s's PnP pose To and map tag M propose (loc_candidate)
     __device__ __forceinline__ void candidate(int, const double *To, const double *M, bool mirror, double *R, double *t) const;
@@ -393,12 +403,182 @@ __device__ __forceinline__ void loc_cov_write_none(PoseCovRec *oc, double sigma_
     if (lane == 37) { oc->dof = 0; oc->status = 1; }
 }
 
+// ---- the uncertainty of the map carried into the pose covariance (asl_localize_mapcov_*, asl_localize_rig_mapcov_*;
+// tests/localize_mapcov_ref.py).  With J_s (8 x 6) the rows of slot s the solver forms, Jr [-[Pb]x | I] at the body point
+// Pb = R X + t, and M_s (8 x 6) the same residuals' rows over the tag's (omega, v), a left update of world<-tag in the
+// world frame: (Jr R) [-[X]x | I], a first-order error e of the map moves the pose by -A^-1 sum_s N_s e_j(s), A = sum
+// J_s^T J_s, N_s = J_s^T M_s.  So C = sigma^2 A^-1 + A^-1 Q A^-1 with Q = sum_{s, s'} N_s Sigma[j(s), j(s')] N_s'^T over the
+// active slots whose tag has a block in the map's joint covariance (asl_mapcov_*'s d_cov_slot, d_map_cov); a tag
+// without one is exact.
+enum { LOC_COV_NONE = 0, LOC_COV_PIXEL = 1, LOC_COV_MAP = 2 };  // loc_solve_frame's COV
+
+struct LocMapCov {  // what asl_mapcov_* wrote: the matrix (row-major, leading dimension ld = 6 * cap_tags), the block of every id
+    const double *cov;
+    const int *slot;
+    int ld;
+};
+
+#define LOC_MAPCOV_PITCH 37  /* doubles per slot of a round in LDS: 36, and odd so that the lanes' rows spread over the banks */
+
+// N_s = J_s^T M_s (row-major 6 x 6) of active slot s at the pose (R, t), from the corners in LDS; a corner behind its camera
+// adds no row, as in loc_corner
+template <class Model>
+__device__ __forceinline__ void loc_slot_cross(const Model &m, const LocLds &L, int s, const double *R, const double *t, double *N)
+{
+#pragma unroll
+    for (int i = 0; i < 36; i++) N[i] = 0;
+    for (int q = 0; q < 4; q++) {
+        const double *X = L.X + 3 * (4 * s + q);
+        double Pb[3], Jr[6];
+#pragma unroll
+        for (int r = 0; r < 3; r++) Pb[r] = R[3 * r] * X[0] + R[3 * r + 1] * X[1] + R[3 * r + 2] * X[2] + t[r];
+        if (!m.jac(s, Pb, Jr)) continue;
+#pragma unroll
+        for (int row = 0; row < 2; row++) {
+            const double *j = Jr + 3 * row;
+            double a[3];  // j R: d uv / d X
+#pragma unroll
+            for (int k = 0; k < 3; k++) a[k] = j[0] * R[k] + j[1] * R[3 + k] + j[2] * R[6 + k];
+            const double Jc[6] = {Pb[1] * j[2] - Pb[2] * j[1], Pb[2] * j[0] - Pb[0] * j[2], Pb[0] * j[1] - Pb[1] * j[0], j[0], j[1], j[2]};
+            const double Mc[6] = {X[1] * a[2] - X[2] * a[1], X[2] * a[0] - X[0] * a[2], X[0] * a[1] - X[1] * a[0], a[0], a[1], a[2]};
+#pragma unroll
+            for (int i = 0; i < 6; i++)
+#pragma unroll
+                for (int k = 0; k < 6; k++) N[6 * i + k] += Jc[i] * Mc[k];
+        }
+    }
+}
+
+// The block of the lane's slot of round r (slot 64 r + lane): -1 for a slot that is not active or whose tag has no block,
+// and *bad set for an entry outside [-1, ld / 6)
+template <class Model>
+__device__ __forceinline__ int loc_slot_block(const Model &m, const LocLds &L, const LocMapCov &mc, int s, bool *bad)
+{
+    if (s >= m.nslots() || L.state[s] != 1) return -1;
+    const int k = mc.slot[m.rec(s)->id];
+    if (k < -1 || k >= mc.ld / 6) { *bad = true; return -1; }
+    return k;
+}
+
+// E = G Q G^T (6 x 6 into sE, LDS, both triangles from one computation) with G = Amap A^-1 the map from the slots' pulls to
+// the output convention (Amap = diag(-R^T, -R^T), pose_cov_column_dev<true>'s) and A the packed J^T J in ne.  The pair sum:
+// the slots go by rounds of 64, one slot a lane.  For each pair of rounds (ra, rb) the lanes put their round-rb slot's N
+// and block into LDS, and every lane adds, for its own round-ra slot a and the 64 slots b of the round in lane order,
+// N_a Sigma[j(a), j(b)] N_b^T to its own lower triangle of Q; the lanes' triangles are then summed by butterfly_sum.  Every
+// order is fixed: the same input gives the same bytes.  256 active slots are 4 x 4 round pairs of 64 x 64 pairs.
+// Returns the number of slots that contribute (the same in every lane); *bad: a slot entry out of range or a Sigma entry
+// that is not finite.  A must be positive definite (the caller's pd).
+template <class Model>
+__device__ __forceinline__ int loc_map_term(const Model &m, const LocLds &L, const double *R, const double *t, const double *ne, const LocMapCov &mc,
+                                            int lane, double *sE, bool *bad_out)
+{
+    __shared__ double sN[ASL_WAVE * LOC_MAPCOV_PITCH];
+    __shared__ int sK[ASL_WAVE];
+    const int rounds = (m.nslots() + ASL_WAVE - 1) / ASL_WAVE;
+    double Q[21];
+#pragma unroll
+    for (int i = 0; i < 21; i++) Q[i] = 0;
+    bool bad = false;
+    int nq = 0;
+    for (int ra = 0; ra < rounds; ra++) {
+        double Na[36];
+        const int a = ASL_WAVE * ra + lane, ka = loc_slot_block(m, L, mc, a, &bad);
+        if (ka >= 0) { loc_slot_cross(m, L, a, R, t, Na); nq++; }
+        for (int rb = 0; rb < rounds; rb++) {
+            {
+                double Nb[36];
+                const int b = ASL_WAVE * rb + lane, kb = loc_slot_block(m, L, mc, b, &bad);
+                if (kb >= 0) {
+                    loc_slot_cross(m, L, b, R, t, Nb);
+#pragma unroll
+                    for (int i = 0; i < 36; i++) sN[lane * LOC_MAPCOV_PITCH + i] = Nb[i];
+                }
+                sK[lane] = kb;
+            }
+            __syncthreads();
+            for (int l2 = 0; l2 < ASL_WAVE; l2++) {
+                const int kb = sK[l2];  // the same in every lane
+                if (kb < 0 || ka < 0) continue;
+                const double *Nb = sN + l2 * LOC_MAPCOV_PITCH, *S = mc.cov + (size_t)6 * ka * mc.ld + 6 * kb;
+                double T[36];  // N_a Sigma_ab
+#pragma unroll
+                for (int i = 0; i < 36; i++) T[i] = 0;
+#pragma unroll
+                for (int k = 0; k < 6; k++)
+#pragma unroll
+                    for (int j = 0; j < 6; j++) {
+                        const double v = S[(size_t)k * mc.ld + j];
+                        bad = bad || !isfinite(v);
+#pragma unroll
+                        for (int i = 0; i < 6; i++) T[6 * i + j] += Na[6 * i + k] * v;
+                    }
+#pragma unroll
+                for (int i = 0; i < 6; i++)
+#pragma unroll
+                    for (int j = 0; j <= i; j++) {
+                        double s = 0;
+#pragma unroll
+                        for (int k = 0; k < 6; k++) s += T[6 * i + k] * Nb[6 * j + k];
+                        Q[TRI(i, j)] += s;
+                    }
+            }
+            __syncthreads();
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 21; i++) Q[i] = butterfly_sum<64>(Q[i]);
+    nq = butterfly_sum<64>(nq);
+    *bad_out = butterfly_sum<64>(bad ? 1 : 0) != 0;
+    // G = Amap A^-1, column c of A^-1 from one solve (identical in every lane)
+    double G[36];
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+        double A[21], x[6];
+#pragma unroll
+        for (int i = 0; i < 21; i++) A[i] = ne[i];
+#pragma unroll
+        for (int i = 0; i < 6; i++) x[i] = i == c ? 1.0 : 0.0;
+        chol6_solve_tri_dev(A, x);
+#pragma unroll
+        for (int b = 0; b < 2; b++)
+#pragma unroll
+            for (int i = 0; i < 3; i++) G[6 * (3 * b + i) + c] = -(R[i] * x[3 * b] + R[3 + i] * x[3 * b + 1] + R[6 + i] * x[3 * b + 2]);
+    }
+    double U[36];  // G Q
+#pragma unroll
+    for (int r = 0; r < 6; r++)
+#pragma unroll
+        for (int j = 0; j < 6; j++) {
+            double s = 0;
+#pragma unroll
+            for (int i = 0; i < 6; i++) s += G[6 * r + i] * Q[i >= j ? TRI(i, j) : TRI(j, i)];
+            U[6 * r + j] = s;
+        }
+    if (lane == 0) {
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+#pragma unroll
+            for (int c = 0; c <= r; c++) {
+                double s = 0;
+#pragma unroll
+                for (int j = 0; j < 6; j++) s += U[6 * r + j] * G[6 * c + j];
+                sE[6 * r + c] = s;
+                sE[6 * c + r] = s;
+            }
+    }
+    __syncthreads();
+    return nq;
+}
+
 // One frame's solve over the slots of model m, steps 1 to 6 of the header, by one wavefront: the pose solved for (the
 // camera's, or the rig's) goes to o as world<-body.  COV: also the first-order covariance of the pose written (asl_pose_cov)
 // into oc, scaled by sigma_px or, for 0, by the solve's own cost / dof.  The plain instantiation never touches oc and sigma_px.
-template <bool COV, class Model>
+// COV == LOC_COV_MAP (mc given): the map's uncertainty is added to it (loc_map_term); with no contributing slot the record is
+// the LOC_COV_PIXEL one to the byte, and a bad slot entry or block gives status 3, zeros, the pose as it is.
+template <int COV, class Model>
 __device__ __forceinline__ void loc_solve_frame(const Model &m, const LocLds &L, const MapTagRec *__restrict__ map, int n_ids, double half,
-                                                double gate, CamPoseRec *o, PoseCovRec *oc, double sigma_px, int lane)
+                                                double gate, CamPoseRec *o, PoseCovRec *oc, double sigma_px, int lane,
+                                                [[maybe_unused]] const LocMapCov &mc = LocMapCov{})
 {
     const int n = m.nslots();
     auto pass = [&](const double *R, const double *t, auto ne_tag, double *ne) {
@@ -410,7 +590,7 @@ __device__ __forceinline__ void loc_solve_frame(const Model &m, const LocLds &L,
     const int npart = loc_gather([&](int s) { return m.rec(s); }, n, map, n_ids, half, [](int fl) { return (fl & 2) != 0; }, L, lane, &nseed);
     if (npart == 0 || nseed == 0) {
         if (lane == 0) loc_write_none(o, npart == 0 ? 1 : 2);
-        if constexpr (COV) loc_cov_write_none(oc, sigma_px, lane);
+        if constexpr (COV != LOC_COV_NONE) loc_cov_write_none(oc, sigma_px, lane);
         return;
     }
 
@@ -456,7 +636,7 @@ __device__ __forceinline__ void loc_solve_frame(const Model &m, const LocLds &L,
     }
     if (code < 0) {  // every candidate scored NaN
         if (lane == 0) loc_write_none(o, 2);
-        if constexpr (COV) loc_cov_write_none(oc, sigma_px, lane);
+        if constexpr (COV != LOC_COV_NONE) loc_cov_write_none(oc, sigma_px, lane);
         return;
     }
 
@@ -510,16 +690,38 @@ __device__ __forceinline__ void loc_solve_frame(const Model &m, const LocLds &L,
 
     // 6: the covariance at the pose just written: one more linearisation over the corners still in LDS, then lane c
     // solves column c (every lane holds the same J^T J after the butterfly sums; lanes past 5 repeat column 5 and store nothing)
-    if constexpr (COV) {
+    if constexpr (COV != LOC_COV_NONE) {
         double ne[27], col[6], sig;
         const double c1 = loc_pass<true>(m, R, t, L, lane, ne);
         const int dof = 8 * nused - 6;
         const double s2 = pose_cov_sigma2(sigma_px, c1, dof, &sig);
         const int c = lane < 6 ? lane : 5;
         const bool pd = pose_cov_column_dev<true>(ne, R, t, c, col) && isfinite(s2);
-        if (lane < 6) pose_cov_store_column(oc, c, col, s2, pd);
-        if (lane == 36) oc->sigma_px = sig;
-        if (lane == 37) { oc->dof = dof; oc->status = pd ? 0 : 2; }
+        if constexpr (COV == LOC_COV_MAP) {
+            // 7: the map's share.  Without a contributing slot the column is stored as above, to the byte
+            __shared__ double sE[36];
+            bool bad = false;
+            const int nq = pd ? loc_map_term(m, L, R, t, ne, mc, lane, sE, &bad) : 0;
+            if (lane < 6) {
+                if (bad || !pd || nq == 0)
+                    pose_cov_store_column(oc, c, col, s2, pd && !bad);
+                else {
+#pragma unroll
+                    for (int r = 0; r < 6; r++) {
+                        if (r < c) continue;
+                        const double v = s2 * col[r] + sE[6 * r + c];
+                        oc->cov[6 * r + c] = v;
+                        oc->cov[6 * c + r] = v;
+                    }
+                }
+            }
+            if (lane == 36) oc->sigma_px = sig;
+            if (lane == 37) { oc->dof = dof; oc->status = !pd ? 2 : bad ? 3 : 0; }
+        } else {
+            if (lane < 6) pose_cov_store_column(oc, c, col, s2, pd);
+            if (lane == 36) oc->sigma_px = sig;
+            if (lane == 37) { oc->dof = dof; oc->status = pd ? 0 : 2; }
+        }
     }
 }
 
@@ -533,4 +735,16 @@ __global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs,
     const LocOneCam m{cam, obs + (size_t)blockIdx.x * max_tags, max_tags};
     loc_solve_frame<COV>(m, loc_lds(s_dyn, max_tags), map, n_ids, cam.half, gate, out + blockIdx.x, COV ? cov + blockIdx.x : nullptr, sigma_px,
                          (int)threadIdx.x);
+}
+
+// k_localize<true> with the map's joint covariance carried into cov[frame] (asl_localize_mapcov_*): loc_solve_frame's
+// LOC_COV_MAP mode, a kernel of its own, so that the two above keep their arguments and their code
+__global__ void __launch_bounds__(64) k_localize_mapcov(const ObsRec *__restrict__ obs, int max_tags, const MapTagRec *__restrict__ map, int n_ids,
+                                                        CamDev cam, double gate, CamPoseRec *__restrict__ out, PoseCovRec *__restrict__ cov,
+                                                        double sigma_px, LocMapCov mc)
+{
+    extern __shared__ double s_dyn[];
+    const LocOneCam m{cam, obs + (size_t)blockIdx.x * max_tags, max_tags};
+    loc_solve_frame<LOC_COV_MAP>(m, loc_lds(s_dyn, max_tags), map, n_ids, cam.half, gate, out + blockIdx.x, cov + blockIdx.x, sigma_px,
+                                 (int)threadIdx.x, mc);
 }

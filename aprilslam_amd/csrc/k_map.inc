@@ -20,6 +20,8 @@
 //   each trial, k_map_park: after the stop it empties the LM's copy of the list offsets, so that the remaining trials
 //   reduce and factor an identity system;
 //   k_map_std       per tag parameter: diag of S^-1 = |L^-1 e_i|^2 by blocked forward substitution with the factor
+//                   (the covariance calls, asl_mapcov_* / asl_mapcov_rig_*: k_map_cols keeps the columns, and after
+//                   k_map_finish k_map_cov_gram forms s^2 S^-1 over the tags k_map_finish numbered)
 //   k_map_finish    one workgroup: the records.
 // The robust calls (asl_map_robust_*, huber_px = k > 0; tests/map_ref.py "loss") keep every seeding stage as it is and put
 // a Huber loss on each corner's raw residual in the LM alone: k_map_linearize<true> scales a corner's two rows by
@@ -816,13 +818,13 @@ __global__ void __launch_bounds__(256) k_map_park(const double *__restrict__ lm,
     else if (i <= n_cams + 1 + n_tags) tag_ptr[i - n_cams - 1] = 0;
 }
 
-// diag(S^-1)_i = |L^-1 e_i|^2: one workgroup per tag parameter i, y in LDS (n doubles), forward substitution by blocks of
-// GN_NB with the diagonal-block inverses k_gn_chol_diag left in Linv; only the blocks from i's on are touched
-__global__ void __launch_bounds__(256) k_map_std(const double *__restrict__ S, const double *__restrict__ Linv, int n, double *__restrict__ var)
+// Column i of L^-1 by one workgroup of 256: y in LDS (n doubles), forward substitution by blocks of GN_NB with the
+// diagonal-block inverses k_gn_chol_diag left in Linv; only the blocks from i's on are touched, so y is zero above row i.
+// Returns |L^-1 e_i|^2 in thread 0 (a fixed tree over the threads); y is complete for every thread afterwards.
+__device__ __forceinline__ double map_linv_column(const double *__restrict__ S, const double *__restrict__ Linv, int n, int i, double *y)
 {
-    extern __shared__ double y[];
     __shared__ double yb[GN_NB], red[256];
-    const int i = blockIdx.x, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     for (int r = tid; r < n; r += 256) y[r] = r == i ? 1.0 : 0.0;
     __syncthreads();
     const int nblk = (n + GN_NB - 1) / GN_NB;
@@ -851,16 +853,95 @@ __global__ void __launch_bounds__(256) k_map_std(const double *__restrict__ S, c
         if (tid < st) red[tid] += red[tid + st];
         __syncthreads();
     }
-    if (tid == 0) var[i] = red[0];
+    return red[0];
+}
+
+// diag(S^-1)_i = |L^-1 e_i|^2: one workgroup per tag parameter i
+__global__ void __launch_bounds__(256) k_map_std(const double *__restrict__ S, const double *__restrict__ Linv, int n, double *__restrict__ var)
+{
+    extern __shared__ double y[];
+    const double v = map_linv_column(S, Linv, n, blockIdx.x, y);
+    if (threadIdx.x == 0) var[blockIdx.x] = v;
+}
+
+// ---- the joint covariance of the map (asl_mapcov_*, asl_mapcov_rig_*; tests/map_cov_ref.py): s^2 S^-1 = s^2 Y^T Y with
+// Y = L^-1, over the tags k_map_finish numbered (cov_slot: ascending id, neither the world tag nor an unmapped id).
+// k_map_cols is k_map_std with the column kept: Yt[i][.] = L^-1 e_i, n doubles, zero before entry i.  The variance is the
+// same sum in the same order, so d_tag_std has the bytes of a call without the covariance.
+__global__ void __launch_bounds__(256) k_map_cols(const double *__restrict__ S, const double *__restrict__ Linv, int n, double *__restrict__ var,
+                                                  double *__restrict__ Yt)
+{
+    extern __shared__ double y[];
+    const int i = blockIdx.x;
+    const double v = map_linv_column(S, Linv, n, i, y);
+    if (threadIdx.x == 0) var[i] = v;
+    for (int r = threadIdx.x; r < n; r += 256) Yt[(size_t)i * n + r] = y[r];
+}
+
+// C = s^2 Y^T Y on the matrix pipe: one workgroup per MAP_COV_T x MAP_COV_T tile of the lower triangle, its four
+// wavefronts one 16 x 16 block each.  Row p of C is parameter p % 6 of covariance block p / 6, which is row
+// 6 cov_tag[p / 6] + p % 6 of Yt.  The K loop runs over the entries of the columns, MAP_COV_KC at a time through LDS
+// (A[m][k] = Yt[row p0 + m][k], B[k][n] = Yt[row q0 + n][k], v_mfma_f64_16x16x4_f64 as in k_gn_chol_update), and starts at
+// the tile's first row of Yt rounded down to 4: the rows are ascending in p and a column is zero above its own row, so
+// everything before that is a product with zero.  The order of every sum depends on the tile alone: the same input gives
+// the same bytes.  An entry is computed once, for c <= r, and stored on both sides of the diagonal: symmetric to the bit.
+#define MAP_COV_T 32
+#define MAP_COV_KC 64
+#define MAP_COV_LDP (MAP_COV_KC + 1) /* odd LDS row pitch, as GN_LDP */
+__global__ void __launch_bounds__(256) k_map_cov_gram(const double *__restrict__ Yt, int n, const int *__restrict__ cov_tag,
+                                                      const int *__restrict__ cov_head, const double *__restrict__ cov_s2,
+                                                      double *__restrict__ C, int ld)
+{
+    const int nc = 6 * cov_head[0];
+    const int p0 = blockIdx.x * MAP_COV_T, q0 = blockIdx.y * MAP_COV_T;
+    if (blockIdx.y > blockIdx.x || p0 >= nc) return;
+    __shared__ double A[MAP_COV_T][MAP_COV_LDP], B[MAP_COV_T][MAP_COV_LDP];
+    __shared__ int rowA[MAP_COV_T], rowB[MAP_COV_T];
+    const int t = threadIdx.x;
+    if (t < MAP_COV_T) {
+        const int p = p0 + t, q = q0 + t;
+        rowA[t] = p < nc ? 6 * cov_tag[p / 6] + p % 6 : -1;  // past the matrix: a row of zeros
+        rowB[t] = q < nc ? 6 * cov_tag[q / 6] + q % 6 : -1;
+    }
+    __syncthreads();
+    const int lane = t & 63, wid = t >> 6, bi = wid >> 1, bj = wid & 1, m = lane & 15, kk = lane >> 4;
+    gn_v4d acc = {0, 0, 0, 0};
+    for (int k0 = max(rowA[0], rowB[0]) & ~3; k0 < n; k0 += MAP_COV_KC) {
+        for (int i = t; i < MAP_COV_T * MAP_COV_KC; i += 256) {
+            const int r = i / MAP_COV_KC, c = i - r * MAP_COV_KC, k = k0 + c;
+            A[r][c] = (rowA[r] >= 0 && k < n) ? Yt[(size_t)rowA[r] * n + k] : 0.0;
+            B[r][c] = (rowB[r] >= 0 && k < n) ? Yt[(size_t)rowB[r] * n + k] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int ks = 0; ks < MAP_COV_KC / 4; ks++)
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A[16 * bi + m][4 * ks + kk], B[16 * bj + m][4 * ks + kk], acc, 0, 0, 0);
+        __syncthreads();
+    }
+    const double s2 = *cov_s2;
+    // the lane holds rows kk + 4 i of column m of the block
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int r = p0 + 16 * bi + kk + 4 * i, c = q0 + 16 * bj + m;
+        if (r < nc && c < nc && c <= r) {
+            const double v = s2 * acc[i];
+            C[(size_t)r * ld + c] = v;
+            C[(size_t)c * ld + r] = v;
+        }
+    }
 }
 
 // ---- the records: one workgroup.  nothing: no world tag (sizes only, no stage after the gather ran).  wmin_obs and soft
 // (k_map_soft's; NULL in a plain call): n_soft, the slot weights and the variance factor over the corners not over the
 // threshold; a plain call has n_soft 0, weight 1 for the slots in the solve and cost / dof.  slot_weight may be NULL.
+// cov_slot (NULL but in the covariance calls): per id its block of the joint covariance, the ids with a std numbered in
+// ascending id, -1 for every other; with it cov_tag[block] = the block's tag, cov_head[0] = the number of blocks and
+// *cov_s2 = the variance factor, for k_map_cov_gram.
 __global__ void __launch_bounds__(MAP_WG) k_map_finish(MapArgs a, int n_cams, int n_tags, int n_obs, int wt, int nothing, const double *lm,
                                                        const double *cost_obs, const double *seed_obs, const double *var, const int *var_fail,
                                                        const double *wmin_obs, const double *soft, MapTagRec *map,
-                                                       double *tag_std, CamPoseRec *poses, MapResultRec *res, double *slot_weight)
+                                                       double *tag_std, CamPoseRec *poses, MapResultRec *res, double *slot_weight,
+                                                       int *cov_slot, int *cov_tag, int *cov_head, double *cov_s2)
 {
     __shared__ int s_part[MAP_WG + 1];
     const int tid = threadIdx.x;
@@ -918,6 +999,19 @@ __global__ void __launch_bounds__(MAP_WG) k_map_finish(MapArgs a, int n_cams, in
         r->size = ok ? a.sizes[i] : 0.0f;
         if (tag_std)
             for (int k = 0; k < 6; k++) tag_std[6 * (size_t)i + k] = (ok && j != wt && std_ok) ? sqrt(s2 * var[6 * j + k]) : 0.0;
+    }
+    if (cov_slot) {
+        auto has = [&](int i) {
+            const int j = (!nothing && a.seen[i]) ? a.id_tag[i] : -1;
+            return (j >= 0 && status == 0 && a.tag_state[j] == 1 && mapped(j) && j != wt && std_ok) ? 1 : 0;
+        };
+        const int n_cov = map_scan(a.n_ids, has, s_part, a.tmp);
+        for (int i = tid; i < a.n_ids; i += MAP_WG) {
+            const bool h = has(i);
+            cov_slot[i] = h ? a.tmp[i] : -1;
+            if (h) cov_tag[a.tmp[i]] = a.id_tag[i];
+        }
+        if (tid == 0) { cov_head[0] = n_cov; *cov_s2 = s2; }
     }
     if (slot_weight)
         for (size_t k = tid; k < (size_t)a.n_rig * a.n_frames * a.max_tags; k += MAP_WG) {

@@ -139,6 +139,22 @@ struct LocRig {
     {
         return rig_corner<NE, ROBUST>(cam_of(g), R, t, X, iu, iv, acc, hk, over);
     }
+    // d uv / d Pb (2 x 3) of a corner of slot g at the rig point Pb = R X + t: J_proj Re of its camera; false behind it
+    __device__ __forceinline__ bool jac(int g, const double *Pb, double *Jr) const
+    {
+        const double *cl = cam_of(g), *Re = cl + 9, *te = cl + 18;
+        double P[3], uv[2], Jp[6];
+#pragma unroll
+        for (int r = 0; r < 3; r++) P[r] = Re[3 * r] * Pb[0] + Re[3 * r + 1] * Pb[1] + Re[3 * r + 2] * Pb[2] + te[r];
+        if (!(P[2] > LOC_Z_MIN)) return false;
+        project_dev(rig_cam_dev(cl), P, uv, Jp);
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            Jr[k] = Jp[0] * Re[k] + Jp[1] * Re[3 + k] + Jp[2] * Re[6 + k];
+            Jr[3 + k] = Jp[3] * Re[k] + Jp[4] * Re[3 + k] + Jp[5] * Re[6 + k];
+        }
+        return true;
+    }
     // slot g's camera<-world candidate (loc_candidate) through its camera's mounting: rig<-world = inv(E) of it,
     // Re^T Rk, Re^T (tk - te)
     __device__ __forceinline__ void candidate(int g, const double *To, const double *M, bool mirror, double *R, double *t) const
@@ -202,4 +218,20 @@ __global__ void __launch_bounds__(64) k_localize_rig(const ObsRec *__restrict__ 
     const LocRig m{cams, obs, 65536u / (unsigned int)max_tags + 1u, n_cams, max_tags, (int)gridDim.x, (int)blockIdx.x};
     loc_solve_frame<COV>(m, loc_lds(s_dyn + RIG_CAM_DOUBLES * n_cams, m.nslots()), map, n_ids, half, gate, out + blockIdx.x,
                          COV ? cov + blockIdx.x : nullptr, sigma_px, lane);
+}
+
+// k_localize_rig<true> with the map's joint covariance carried into cov[frame] (asl_localize_rig_mapcov_*), as k_localize_mapcov
+__global__ void __launch_bounds__(64) k_localize_rig_mapcov(const ObsRec *__restrict__ obs, int n_cams, int max_tags, const MapTagRec *__restrict__ map,
+                                                            int n_ids, const RigCamRec *__restrict__ rig, double half, double gate,
+                                                            CamPoseRec *__restrict__ out, PoseCovRec *__restrict__ cov, double sigma_px, LocMapCov mc)
+{
+    extern __shared__ double s_dyn[];
+    const int lane = threadIdx.x;
+    double *cams = s_dyn;
+
+    rig_fill_cams(cams, rig, n_cams, lane);
+
+    const LocRig m{cams, obs, 65536u / (unsigned int)max_tags + 1u, n_cams, max_tags, (int)gridDim.x, (int)blockIdx.x};
+    loc_solve_frame<LOC_COV_MAP>(m, loc_lds(s_dyn + RIG_CAM_DOUBLES * n_cams, m.nslots()), map, n_ids, half, gate, out + blockIdx.x, cov + blockIdx.x,
+                                 sigma_px, lane, mc);
 }

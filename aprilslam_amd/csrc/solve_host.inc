@@ -107,7 +107,7 @@ static int check_rig_table(const asl_rig_camera *rig, int n_cams)
     return ASL_OK;
 }
 
-// One localisation call, whichever of the eight entry points made it, in their argument order.  The single-camera forms
+// One localisation call, whichever of the twelve entry points made it, in their argument order.  The single-camera forms
 // leave n_cams 0 and rig NULL; the rig forms give n_cams and the table and leave cam's K and dist NULL, n_dist 0.
 // The plain forms leave sigma_px 0 and cov NULL.  obs, map, rig, out and cov are all host or all device pointers.
 struct LocCall {
@@ -117,9 +117,28 @@ struct LocCall {
     double gate, sigma_px;
     void *out, *cov;
     bool with_cov;      // a covariance form: cov must be there
+    // the mapcov forms (asl_localize_mapcov_*, asl_localize_rig_mapcov_*): the map's joint covariance as asl_mapcov_* writes
+    // it, host or device as the rest; every other form leaves them NULL, 0 and false
+    const void *map_cov; int ld; const void *cov_slot;
+    bool with_mapcov;
 };
 
 static bool is_rig(const LocCall &c) { return c.n_cams || c.rig; }
+
+// The mapcov host forms' look at what the device forms can only report through asl_pose_cov.status 3: every cov_slot entry
+// in [-1, ld / 6), and every entry of the blocks they refer to finite
+static int check_map_cov_host(const int32_t *slot, int n_ids, const double *cov, int ld)
+{
+    int n = 0;
+    for (int i = 0; i < n_ids; i++) {
+        if (slot[i] < -1 || slot[i] >= ld / 6) return fail(ASL_EINVAL, "cov_slot[%d] must be in [-1, %d) (got %d)", i, ld / 6, slot[i]);
+        n = std::max(n, slot[i] + 1);
+    }
+    for (int r = 0; r < 6 * n; r++)
+        for (int c = 0; c < 6 * n; c++)
+            if (!std::isfinite(cov[(size_t)r * ld + c])) return fail(ASL_EINVAL, "map_cov is not finite at (%d, %d)", r, c);
+    return ASL_OK;
+}
 
 // Every refusal, before anything is written or enqueued.  A rig's table is checked last: where it is, or (device: the
 // pointers are the device's) in a copy read back, at most 16 x 216 bytes; it must be complete when the call is made.
@@ -136,6 +155,12 @@ static int check_localize_call(const asl_detector *d, const LocCall &c, bool dev
         return fail(ASL_EINVAL, "n_cams * max_tags must be <= %d (got %d x %d)", RIG_MAX_SLOTS, c.n_cams, c.max_tags);
     if (!(c.gate >= 0) || !std::isfinite(c.gate)) return fail(ASL_EINVAL, "max_tag_rms_px must be >= 0 (got %g)", c.gate);
     if (int rc = check_sigma_px(c.sigma_px)) return rc;
+    if (c.with_mapcov) {
+        if (!c.map_cov || !c.cov_slot) return fail(ASL_EINVAL, "NULL argument");
+        if (c.ld < 6 || c.ld % 6) return fail(ASL_EINVAL, "ld must be a positive multiple of 6 (got %d)", c.ld);
+        if (!device)
+            if (int rc = check_map_cov_host((const int32_t *)c.cov_slot, c.n_ids, (const double *)c.map_cov, c.ld)) return rc;
+    }
     if (!rig) return ASL_OK;
     asl_rig_camera tab[RIG_MAX_CAMS];
     if (device) {
@@ -159,7 +184,13 @@ static int launch_localize(asl_detector *d, const LocCall &c, hipStream_t st)
     CamPoseRec *out = (CamPoseRec *)c.out;
     PoseCovRec *cov = (PoseCovRec *)c.cov;
     const size_t lds = rig ? rig_lds_bytes(c.n_cams, c.max_tags) : loc_lds_bytes(c.max_tags);
-    if (!rig && cov)
+    const LocMapCov mc{(const double *)c.map_cov, (const int *)c.cov_slot, c.ld};
+    if (c.with_mapcov && !rig)
+        hipLaunchKernelGGL(k_localize_mapcov, grid, block, lds, st, obs, c.max_tags, map, c.n_ids, cam, c.gate, out, cov, c.sigma_px, mc);
+    else if (c.with_mapcov)
+        hipLaunchKernelGGL(k_localize_rig_mapcov, grid, block, lds, st, obs, c.n_cams, c.max_tags, map, c.n_ids, tab, cam.half, c.gate, out, cov,
+                           c.sigma_px, mc);
+    else if (!rig && cov)
         hipLaunchKernelGGL(k_localize<true>, grid, block, lds, st, obs, c.max_tags, map, c.n_ids, cam, c.gate, out, cov, c.sigma_px);
     else if (!rig)
         hipLaunchKernelGGL(k_localize<false>, grid, block, lds, st, obs, c.max_tags, map, c.n_ids, cam, c.gate, out, cov, c.sigma_px);
@@ -180,12 +211,24 @@ static int localize_batch(asl_detector *d, const LocCall &c)
     if (c.n_frames == 0) return ASL_OK;
     const bool rig = is_rig(c);
     const size_t n = (size_t)c.n_frames, rig_bytes = sizeof(asl_rig_camera) * (size_t)c.n_cams;
-    OutPiece o[] = {{c.out, sizeof(asl_cam_pose) * n}, {c.cov, c.cov ? sizeof(asl_pose_cov) * n : 0}, {nullptr, rig_bytes}};
+    // the mapcov forms: the blocks the slots refer to (the leading 6 n x 6 n region) staged with 6 n as the leading dimension
+    size_t nb = 0;
+    for (int i = 0; c.with_mapcov && i < c.n_ids; i++) nb = std::max(nb, (size_t)(((const int32_t *)c.cov_slot)[i] + 1));
+    const size_t ldd = 6 * std::max<size_t>(nb, 1), slot_bytes = c.with_mapcov ? sizeof(int32_t) * (size_t)c.n_ids : 0;
+    OutPiece o[] = {{c.out, sizeof(asl_cam_pose) * n}, {c.cov, c.cov ? sizeof(asl_pose_cov) * n : 0}, {nullptr, rig_bytes}, {nullptr, slot_bytes},
+                    {nullptr, c.with_mapcov ? sizeof(double) * ldd * ldd : 0}};
     if (int rc = stage_host_call(d, rig ? "rig localisation" : "localisation", o, c.obs, (rig ? c.n_cams : 1) * c.n_frames, c.max_tags, c.map, c.n_ids))
         return rc;
     if (rig) HIPCHK(hipMemcpy(o[2].dev, c.rig, rig_bytes, hipMemcpyHostToDevice));
     LocCall dc = c;
     dc.obs = d->loc_obs.p; dc.map = d->loc_map.p; dc.out = o[0].dev; dc.cov = o[1].dev; dc.rig = o[2].dev;
+    if (c.with_mapcov) {
+        HIPCHK(hipMemcpy(o[3].dev, c.cov_slot, slot_bytes, hipMemcpyHostToDevice));
+        if (nb)
+            HIPCHK(hipMemcpy2D(o[4].dev, sizeof(double) * ldd, c.map_cov, sizeof(double) * (size_t)c.ld, sizeof(double) * 6 * nb, 6 * nb,
+                               hipMemcpyHostToDevice));
+        dc.cov_slot = o[3].dev; dc.map_cov = o[4].dev; dc.ld = (int)ldd;
+    }
     if (int rc = launch_localize(d, dc, nullptr)) return rc;
     return fetch_out(o);
 }
@@ -241,6 +284,40 @@ extern "C" int asl_localize_rig_cov_batch(asl_detector *d, const asl_obs *obs, i
                                           asl_cam_pose *out, asl_pose_cov *cov)
 {
     return localize_batch(d, {obs, n_cams, n_frames, max_tags, map, n_ids, rig, {nullptr, nullptr, 0, tag_size}, max_tag_rms_px, sigma_px, out, cov, true});
+}
+
+// The mapcov forms: the _cov argument lists with the map's joint covariance (map_cov, ld, cov_slot) after cov.
+extern "C" int asl_localize_mapcov_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                                 const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
+                                                 double sigma_px, void *d_out, void *d_cov, const void *d_map_cov, int ld, const void *d_cov_slot,
+                                                 void *stream)
+{
+    return localize_frames_device(d, {d_obs, 0, n_frames, max_tags, d_map, n_ids, nullptr, {K, dist, n_dist, tag_size}, max_tag_rms_px, sigma_px, d_out, d_cov, true,
+                                      d_map_cov, ld, d_cov_slot, true}, stream);
+}
+
+extern "C" int asl_localize_mapcov_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                                         const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px, double sigma_px,
+                                         asl_cam_pose *out, asl_pose_cov *cov, const double *map_cov, int ld, const int32_t *cov_slot)
+{
+    return localize_batch(d, {obs, 0, n_frames, max_tags, map, n_ids, nullptr, {K, dist, n_dist, tag_size}, max_tag_rms_px, sigma_px, out, cov, true,
+                              map_cov, ld, cov_slot, true});
+}
+
+extern "C" int asl_localize_rig_mapcov_frames_device(asl_detector *d, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map,
+                                                     int n_ids, const void *d_rig, double tag_size, double max_tag_rms_px, double sigma_px,
+                                                     void *d_out, void *d_cov, const void *d_map_cov, int ld, const void *d_cov_slot, void *stream)
+{
+    return localize_frames_device(d, {d_obs, n_cams, n_frames, max_tags, d_map, n_ids, d_rig, {nullptr, nullptr, 0, tag_size}, max_tag_rms_px, sigma_px, d_out,
+                                      d_cov, true, d_map_cov, ld, d_cov_slot, true}, stream);
+}
+
+extern "C" int asl_localize_rig_mapcov_batch(asl_detector *d, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_map_tag *map,
+                                             int n_ids, const asl_rig_camera *rig, double tag_size, double max_tag_rms_px, double sigma_px,
+                                             asl_cam_pose *out, asl_pose_cov *cov, const double *map_cov, int ld, const int32_t *cov_slot)
+{
+    return localize_batch(d, {obs, n_cams, n_frames, max_tags, map, n_ids, rig, {nullptr, nullptr, 0, tag_size}, max_tag_rms_px, sigma_px, out, cov, true,
+                              map_cov, ld, cov_slot, true});
 }
 
 // ---- per-tag pose covariance (k_posecov.inc)
@@ -544,12 +621,16 @@ extern "C" int asl_calibrate_rig_batch(asl_detector *d, const asl_obs *obs, int 
 // (asl_map_rig_*) give n_cams and the table and leave cam's K and dist NULL, n_dist 0; their block is camera-major and their
 // slot weights n_cams x n_frames x max_tags.  obs, rig, map, tag_std, poses, result and slot_weight are all host (*_batch) or
 // all device pointers (*_frames_device).  tag_sizes (the sized forms; NULL: no table) is a host array of n_ids in both,
-// like K and dist: the side of each id, 0 for the call's tag_size.
+// like K and dist: the side of each id, 0 for the call's tag_size.  The covariance forms (asl_mapcov_*, asl_mapcov_rig_*)
+// set with_cov and give cov_slot (n_ids int32), map_cov (doubles, leading dimension 6 * cap_tags) and cap_tags, host or
+// device as the rest; every other form leaves them NULL, 0 and false.
 struct MapCall {
     const void *obs; int n_cams, n_frames, max_tags, n_ids;
     const void *rig; Camera cam; const float *tag_sizes;
     int world_id; double huber_px; int max_iters;
     void *map, *tag_std, *poses, *result, *slot_weight;
+    void *cov_slot, *map_cov; int cap_tags;
+    bool with_cov;      // a covariance form: cov_slot and map_cov must be there
 };
 
 static bool is_rig(const MapCall &c) { return c.n_cams || c.rig; }
@@ -561,6 +642,7 @@ static int check_map_call(const asl_detector *d, const MapCall &c, bool device)
     const bool rig = is_rig(c);
     if (!d) return fail(ASL_EINVAL, "NULL detector");
     if (!c.obs || !(rig ? c.rig : (const void *)c.cam.K) || !c.map || !c.poses || !c.result) return fail(ASL_EINVAL, "NULL argument");
+    if (c.with_cov && (!c.cov_slot || !c.map_cov)) return fail(ASL_EINVAL, "NULL argument");
     if (c.n_frames < 1) return fail(ASL_EINVAL, "n_frames must be >= 1 (got %d)", c.n_frames);
     if (rig && (c.n_cams < 1 || c.n_cams > RIG_MAX_CAMS)) return fail(ASL_EINVAL, "n_cams must be in [1, %d] (got %d)", RIG_MAX_CAMS, c.n_cams);
     if (int rc = check_obs_args(c.max_tags, c.n_ids, c.cam)) return rc;
@@ -572,6 +654,7 @@ static int check_map_call(const asl_detector *d, const MapCall &c, bool device)
     for (int i = 0; c.tag_sizes && i < c.n_ids; i++)
         if (!(c.tag_sizes[i] >= 0) || !std::isfinite(c.tag_sizes[i]))
             return fail(ASL_EINVAL, "tag_sizes[%d] must be 0 or positive and finite (got %g)", i, (double)c.tag_sizes[i]);
+    if (c.with_cov && c.cap_tags < 1) return fail(ASL_EINVAL, "cap_tags must be >= 1 (got %d)", c.cap_tags);
     if (!rig) return ASL_OK;
     asl_rig_camera tab[RIG_MAX_CAMS];
     if (device) {
@@ -588,13 +671,15 @@ static int launch_map_views(asl_detector *d, const MapCall &c, hipStream_t st)
     const size_t nf = (size_t)c.n_frames, ni = (size_t)c.n_ids, nsl = (RIG ? (size_t)c.n_cams : 1) * nf * (size_t)c.max_tags;
     MapArgs a{};
     int *per_id, *per_frame, *per_cam, *per_obs, *csr;  // the grouped int arrays, one piece per group
-    double *cams;
+    double *cams, *cov_s2;
     float *sizes;
+    int *cov_tag;  // the covariance calls': the tag of each block, then the number of blocks
     if (carve_ws(d->map_ws, [&](WsCarve &w) {
             a.head = w.take<MapHead>(1); per_id = w.take<int>(5 * (ni + 1)); per_frame = w.take<int>(4 * (nf + 1));
             per_cam = w.take<int>(4 * (nf + 1)); a.tag_state = w.take<int>(ni + 1); a.slot_obs = w.take<int>(nsl); per_obs = w.take<int>(5 * nsl);
             csr = w.take<int>(3 * nsl + nf + 2 * ni + 3); a.W = w.take<double>(12 * nf); a.G = w.take<double>(12 * ni);
             cams = w.take<double>(RIG_CAM_DOUBLES * RIG_MAX_CAMS); a.tag_half = w.take<double>(ni); sizes = w.take<float>(ni);
+            cov_s2 = w.take<double>(1); cov_tag = w.take<int>(ni + 1);
         }))
         return fail(ASL_ENOMEM, "map workspace allocation failed");
     a.obs = (const ObsRec *)c.obs; a.n_frames = c.n_frames; a.max_tags = c.max_tags; a.n_ids = c.n_ids; a.world_req = c.world_id;
@@ -620,11 +705,14 @@ static int launch_map_views(asl_detector *d, const MapCall &c, hipStream_t st)
     auto finish_nothing = [&]() {
         hipLaunchKernelGGL(k_map_finish, dim3(1), dim3(MAP_WG), 0, st, a, NC, NT, NM, WT, 1, (const double *)nullptr, (const double *)nullptr,
                            (const double *)nullptr, (const double *)nullptr, (const int *)nullptr, (const double *)nullptr, (const double *)nullptr,
-                           (MapTagRec *)c.map, (double *)c.tag_std, (CamPoseRec *)c.poses, (MapResultRec *)c.result, (double *)c.slot_weight);
+                           (MapTagRec *)c.map, (double *)c.tag_std, (CamPoseRec *)c.poses, (MapResultRec *)c.result, (double *)c.slot_weight,
+                           (int *)c.cov_slot, cov_tag, cov_tag + ni, cov_s2);
         HIPCHK(hipGetLastError());
         return ASL_OK;
     };
     if (NT > MAP_MAX_TAGS) return fail(ASL_EINVAL, "the frames see %d tags; the map's dense reduced system takes at most %d", NT, MAP_MAX_TAGS);
+    if (c.with_cov && NT - 1 > c.cap_tags)
+        return fail(ASL_EINVAL, "the frames see %d tags besides the world tag; the covariance matrix holds cap_tags = %d", NT - 1, c.cap_tags);
     if (WT < 0) {
         int rc = finish_nothing();
         if (rc) return rc;
@@ -639,11 +727,12 @@ static int launch_map_views(asl_detector *d, const MapCall &c, hipStream_t st)
     GnSystem sys = {nullptr, nullptr, a.cam_obs, nullptr, a.ptag_obs, a.obs_cam, a.obs_tag, nullptr, NC, NT, WT};  // the pair lists
     GnLmBufs b;
     const bool robust = c.huber_px > 0;  // 0: the plain kernels
-    double *seed_obs, *var, *wmin_obs = nullptr, *soft = nullptr;
+    double *seed_obs, *var, *wmin_obs = nullptr, *soft = nullptr, *Yt = nullptr;
     if (carve_ws(d->map_lm, [&](WsCarve &w) {
             b = gn_lm_carve(w, sys, NM, 2 * MAP_LM__N);
             seed_obs = w.take<double>(nm); var = w.take<double>(n); sys.cam_ptr = w.take<int>(nc + 1); sys.tag_ptr = w.take<int>(nt + 1);
             if (robust) { wmin_obs = w.take<double>(nm); soft = w.take<double>(MAP_SOFT__N); }
+            if (c.with_cov) Yt = w.take<double>((size_t)n * n);  // the columns of L^-1, one per row
         }))
         return fail(ASL_ENOMEM, "map workspace allocation failed");
     a.obs_of = sys.obs_of;
@@ -684,17 +773,24 @@ static int launch_map_views(asl_detector *d, const MapCall &c, hipStream_t st)
     lin(a.W, a.G, sys.D, 1);
     if (robust) hipLaunchKernelGGL(k_map_soft<RIG>, dim3(1), dim3(256), 0, st, a, NM, cam, c.huber_px, wmin_obs, soft);
     range_pop();
-    if (c.tag_std) {
+    const bool want_var = c.tag_std || c.with_cov;
+    if (want_var) {
         GnSystem full = sys;  // undamped, over every active observation
         full.cam_ptr = a.cam_ptr;
         full.tag_ptr = a.ptag_ptr;
         rc = gn_factor_step(full, lm0, b.flag + 1, st);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_map_std, dim3(n), dim3(256), (size_t)n * sizeof(double), st, sys.S, sys.Linv, n, var);
+        if (c.with_cov) hipLaunchKernelGGL(k_map_cols, dim3(n), dim3(256), (size_t)n * sizeof(double), st, sys.S, sys.Linv, n, var, Yt);
+        else hipLaunchKernelGGL(k_map_std, dim3(n), dim3(256), (size_t)n * sizeof(double), st, sys.S, sys.Linv, n, var);
     }
-    hipLaunchKernelGGL(k_map_finish, dim3(1), wg, 0, st, a, NC, NT, NM, WT, 0, lm, b.cost_obs, seed_obs, c.tag_std ? var : nullptr, b.flag + 1,
+    hipLaunchKernelGGL(k_map_finish, dim3(1), wg, 0, st, a, NC, NT, NM, WT, 0, lm, b.cost_obs, seed_obs, want_var ? var : nullptr, b.flag + 1,
                        (const double *)wmin_obs, (const double *)soft, (MapTagRec *)c.map, (double *)c.tag_std, (CamPoseRec *)c.poses,
-                       (MapResultRec *)c.result, (double *)c.slot_weight);
+                       (MapResultRec *)c.result, (double *)c.slot_weight, (int *)c.cov_slot, cov_tag, cov_tag + ni, cov_s2);
+    if (c.with_cov && NT > 1) {  // the blocks k_map_finish numbered: at most NT - 1 of them
+        const unsigned int tiles = (unsigned int)((6 * (NT - 1) + MAP_COV_T - 1) / MAP_COV_T);
+        hipLaunchKernelGGL(k_map_cov_gram, dim3(tiles, tiles), dim3(256), 0, st, (const double *)Yt, n, (const int *)cov_tag,
+                           (const int *)(cov_tag + ni), (const double *)cov_s2, (double *)c.map_cov, 6 * c.cap_tags);
+    }
     HIPCHK(hipGetLastError());
     return ASL_OK;
 }
@@ -714,14 +810,28 @@ static int map_batch(asl_detector *d, const MapCall &c)
     const size_t ni = (size_t)c.n_ids, rows = (size_t)(rig ? c.n_cams : 1) * (size_t)c.n_frames, rig_bytes = sizeof(asl_rig_camera) * (size_t)c.n_cams;
     OutPiece o[] = {{c.result, sizeof(asl_map_result)}, {c.map, sizeof(asl_map_tag) * ni}, {c.tag_std, c.tag_std ? sizeof(double) * 6 * ni : 0},
                     {c.poses, sizeof(asl_cam_pose) * (size_t)c.n_frames},
-                    {c.slot_weight, c.slot_weight ? sizeof(double) * rows * (size_t)c.max_tags : 0}, {nullptr, rig_bytes}};
+                    {c.slot_weight, c.slot_weight ? sizeof(double) * rows * (size_t)c.max_tags : 0}, {nullptr, rig_bytes},
+                    {c.cov_slot, c.with_cov ? sizeof(int32_t) * ni : 0}, {nullptr, 0}};
+    // the covariance is staged at the most blocks the call can have (cap_tags, and no more than the ids or the solver's
+    // tags), with that as its leading dimension; only the region written goes back, into the caller's leading dimension
+    const int cap = c.with_cov ? (int)std::min<size_t>({(size_t)c.cap_tags, ni, (size_t)MAP_MAX_TAGS}) : 0;
+    o[7].bytes = sizeof(double) * 36 * (size_t)cap * (size_t)cap;
     if (int rc = stage_host_call(d, rig ? "rig map" : "map", o, c.obs, (int)rows, c.max_tags, nullptr, c.n_ids)) return rc;
     if (rig) HIPCHK(hipMemcpy(o[5].dev, c.rig, rig_bytes, hipMemcpyHostToDevice));
     MapCall dc = c;
     dc.obs = d->loc_obs.p; dc.result = o[0].dev; dc.map = o[1].dev; dc.tag_std = o[2].dev; dc.poses = o[3].dev; dc.slot_weight = o[4].dev;
-    dc.rig = o[5].dev;
+    dc.rig = o[5].dev; dc.cov_slot = o[6].dev; dc.map_cov = o[7].dev; dc.cap_tags = cap;
     if (int rc = launch_map(d, dc, nullptr)) return rc;
-    return fetch_out(o);
+    if (int rc = fetch_out(o)) return rc;
+    if (c.with_cov) {
+        const int32_t *slot = (const int32_t *)c.cov_slot;
+        size_t n_cov = 0;
+        for (size_t i = 0; i < ni; i++) n_cov += slot[i] >= 0;
+        if (n_cov)
+            HIPCHK(hipMemcpy2D(c.map_cov, sizeof(double) * 6 * (size_t)c.cap_tags, o[7].dev, sizeof(double) * 6 * (size_t)cap, sizeof(double) * 6 * n_cov,
+                               6 * n_cov, hipMemcpyDeviceToHost));
+    }
+    return ASL_OK;
 }
 
 extern "C" int asl_map_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, int n_ids, const double *K, const double *dist,
@@ -804,6 +914,43 @@ extern "C" int asl_map_rig_sized_batch(asl_detector *d, const asl_obs *obs, int 
 {
     return map_batch(d, {obs, n_cams, n_frames, max_tags, n_ids, rig, {nullptr, nullptr, 0, tag_size}, tag_sizes, world_id, sized_huber_px, max_iters, map,
                          tag_std, poses, result, slot_weight});
+}
+
+// The covariance forms: the sized argument lists with the joint covariance of the map after slot_weight.
+extern "C" int asl_mapcov_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, int n_ids, const double *K,
+                                         const double *dist, int n_dist, double tag_size, const float *tag_sizes, int world_id,
+                                         double cov_huber_px, int max_iters, void *d_map, void *d_tag_std, void *d_poses, void *d_result,
+                                         void *d_slot_weight, void *d_cov_slot, void *d_map_cov, int cap_tags, void *stream)
+{
+    return map_frames_device(d, {d_obs, 0, n_frames, max_tags, n_ids, nullptr, {K, dist, n_dist, tag_size}, tag_sizes, world_id, cov_huber_px, max_iters,
+                                 d_map, d_tag_std, d_poses, d_result, d_slot_weight, d_cov_slot, d_map_cov, cap_tags, true}, stream);
+}
+
+extern "C" int asl_mapcov_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, int n_ids, const double *K, const double *dist,
+                                 int n_dist, double tag_size, const float *tag_sizes, int world_id, double cov_huber_px, int max_iters,
+                                 asl_map_tag *map, double *tag_std, asl_cam_pose *poses, asl_map_result *result, double *slot_weight,
+                                 int32_t *cov_slot, double *map_cov, int cap_tags)
+{
+    return map_batch(d, {obs, 0, n_frames, max_tags, n_ids, nullptr, {K, dist, n_dist, tag_size}, tag_sizes, world_id, cov_huber_px, max_iters, map,
+                         tag_std, poses, result, slot_weight, cov_slot, map_cov, cap_tags, true});
+}
+
+extern "C" int asl_mapcov_rig_frames_device(asl_detector *d, const void *d_obs, int n_cams, int n_frames, int max_tags, int n_ids,
+                                             const void *d_rig, double tag_size, const float *tag_sizes, int world_id, double cov_huber_px,
+                                             int max_iters, void *d_map, void *d_tag_std, void *d_poses, void *d_result, void *d_slot_weight,
+                                             void *d_cov_slot, void *d_map_cov, int cap_tags, void *stream)
+{
+    return map_frames_device(d, {d_obs, n_cams, n_frames, max_tags, n_ids, d_rig, {nullptr, nullptr, 0, tag_size}, tag_sizes, world_id, cov_huber_px,
+                                 max_iters, d_map, d_tag_std, d_poses, d_result, d_slot_weight, d_cov_slot, d_map_cov, cap_tags, true}, stream);
+}
+
+extern "C" int asl_mapcov_rig_batch(asl_detector *d, const asl_obs *obs, int n_cams, int n_frames, int max_tags, int n_ids,
+                                     const asl_rig_camera *rig, double tag_size, const float *tag_sizes, int world_id, double cov_huber_px,
+                                     int max_iters, asl_map_tag *map, double *tag_std, asl_cam_pose *poses, asl_map_result *result,
+                                     double *slot_weight, int32_t *cov_slot, double *map_cov, int cap_tags)
+{
+    return map_batch(d, {obs, n_cams, n_frames, max_tags, n_ids, rig, {nullptr, nullptr, 0, tag_size}, tag_sizes, world_id, cov_huber_px, max_iters, map,
+                         tag_std, poses, result, slot_weight, cov_slot, map_cov, cap_tags, true});
 }
 
 // ---- sequence localisation with a motion prior (k_smooth.inc)

@@ -99,17 +99,21 @@ class Rig:
                 raise ValueError("%s is not a saved Rig (K (n, 3, 3), dist (n, 5), n_dist (n,), T_cam_rig (n, 4, 4))" % path)
             return cls([RigCamera(K[k], dist[k][:int(nd[k])], T[k]) for k in range(n)])
 
-    def localize(self, det, obs, tag_map, tag_size, max_tag_rms_px=0.0, with_cov=False, sigma_px=0.0):
+    def localize(self, det, obs, tag_map, tag_size, max_tag_rms_px=0.0, with_cov=False, sigma_px=0.0, map_cov=None):
         """obs (n_cams, n_frames, max_tags) OBS_DTYPE, camera-major, against tag_map (a localize.TagMap or MAP_TAG_DTYPE
         records) on det (a _lib.Detector) -> (n_frames,) CAM_POSE_DTYPE with T = world<-rig; with_cov: (poses, (n_frames,)
         POSE_COV_DTYPE), scaled by sigma_px or, for 0, by the solve's own estimate.  tag_size is the size of the map entries
-        that have none of their own (TagMap.set_size), here and in localize_sequence / localize_sequences."""
+        that have none of their own (TagMap.set_size), here and in localize_sequence / localize_sequences.  map_cov (with
+        with_cov; a mapping.MapCovariance, e.g. build_map(with_cov=True).cov): the uncertainty of the map's tags is carried
+        into the covariances (asl_localize_rig_mapcov_batch)."""
+        if map_cov is not None and not with_cov:
+            raise ValueError("map_cov needs with_cov=True")
         o = np.asarray(obs)
         if o.dtype != OBS_DTYPE or o.ndim != 3 or o.shape[0] != len(self.cameras):
             raise ValueError("obs must be (%d, n_frames, max_tags) asl_obs records" % len(self.cameras))
         if o.shape[0] * o.shape[2] > MAX_SLOTS:
             raise ValueError("n_cams * max_tags must be <= %d" % MAX_SLOTS)
-        return det.localize_rig(o, tag_map, self.as_records(), tag_size, max_tag_rms_px, float(sigma_px) if with_cov else None)
+        return det.localize_rig(o, tag_map, self.as_records(), tag_size, max_tag_rms_px, float(sigma_px) if with_cov else None, map_cov=map_cov)
 
     def build_map(self, det, obs, n_ids, tag_size, world_id=-1, max_iters=30, with_std=True, huber_px=0.0):
         """The tag map from the rig's own frames (Detector.build_map_rig, asl_map_rig_batch): obs (n_cams, n_frames, max_tags)
@@ -118,18 +122,24 @@ class Rig:
         camera_poses = world<-rig.  Every camera's views enter one solve through the mountings, which are taken as exact, so
         tags that no single camera sees together share one map.  huber_px > 0: a Huber loss of that many pixels on every
         corner residual; the result's soft_slots() are then (camera, frame, slot, id, weight).  Tags of different known
-        sizes: build_map_sized."""
+        sizes: build_map_sized.  With the joint covariance of the mapped tags: build_map_cov."""
         return self.build_map_sized(det, obs, n_ids, tag_size, None, world_id=world_id, max_iters=max_iters, with_std=with_std, huber_px=huber_px)
 
-    def build_map_sized(self, det, obs, n_ids, tag_size, tag_sizes, world_id=-1, max_iters=30, with_std=True, huber_px=0.0):
+    def build_map_cov(self, det, obs, n_ids, tag_size, tag_sizes=None, world_id=-1, max_iters=30, huber_px=0.0):
+        """build_map / build_map_sized with the joint covariance of the mapped tags as result.cov, a mapping.MapCovariance
+        (asl_mapcov_rig_batch): what localize(with_cov=True, map_cov=result.cov) carries into the covariance of a rig pose."""
+        return self.build_map_sized(det, obs, n_ids, tag_size, tag_sizes, world_id=world_id, max_iters=max_iters, huber_px=huber_px, with_cov=True)
+
+    def build_map_sized(self, det, obs, n_ids, tag_size, tag_sizes, world_id=-1, max_iters=30, with_std=True, huber_px=0.0, with_cov=False):
         """build_map for tags of different known sizes (asl_map_rig_sized_batch): tag_sizes is a {id: size} dict or an array of
         n_ids sizes, 0 or an id not named standing for tag_size (None: build_map itself).  Every tag is solved at its own
-        size and the result's tag_map carries the sizes, so that localize() and localize_sequences() against it honour them."""
+        size and the result's tag_map carries the sizes, so that localize() and localize_sequences() against it honour them.
+        with_cov: build_map_cov."""
         from .mapping import MapResult
         o = self._block(obs)
         out = det.build_map_rig(o, n_ids, self.as_records(), tag_size, world_id=world_id, max_iters=max_iters, with_std=with_std,
-                                huber_px=huber_px, with_slot_weight=bool(huber_px), tag_sizes=tag_sizes)
-        return MapResult(*out, slot_ids=o["id"] if huber_px else None)
+                                huber_px=huber_px, with_slot_weight=bool(huber_px), tag_sizes=tag_sizes, with_cov=with_cov)
+        return MapResult.from_call(out, slot_ids=o["id"] if huber_px else None, with_cov=with_cov)
 
     def locate_tags(self, det, obs, poses, tag_map, tag_size, max_view_rms_px=0.0, min_views=2, sigma_px=None):
         """The tags the map does not have, located from the rig's posed frames (Detector.locate_tags_rig,

@@ -184,7 +184,7 @@ class TagDetector:
         return ok, rvec, tvec, T, cov
 
     # -- camera pose from every visible tag against a known map (asl_localize_batch) ---------------------------------
-    def localize(self, detections, tag_map, max_tag_rms_px=0.0, with_cov=False, sigma_px=0.0):
+    def localize(self, detections, tag_map, max_tag_rms_px=0.0, with_cov=False, sigma_px=0.0, map_cov=None):
         """One frame's detection dicts (as detect() returns them) -> the camera pose from all mapped tags at once:
         {"ok", "T" world<-camera 4x4, "rms_px", "n_tags", "n_rejected", "status"}.  The poses detect() solved in its own
         submission are reused; detections without one get their PnP first (one launch).  max_tag_rms_px > 0 drops tags
@@ -192,7 +192,11 @@ class TagDetector:
         rotation about the world axes | camera position, zeros unless "cov_status" is 0) and "sigma_px", the corner sigma
         that scaled it: the given one, or for 0 the solve's own estimate (localize.pose_std reads the std off it).
         A tag with a size of its own in tag_map (TagMap.set_size) is solved at it, here and in localize_batch /
-        localize_sequence / localize_sequences; this detector's tag_size is the size of the others."""
+        localize_sequence / localize_sequences; this detector's tag_size is the size of the others.
+        map_cov (with with_cov; a mapping.MapCovariance, e.g. build_map(with_cov=True).cov): the uncertainty of the map's
+        tags is carried into "cov" (asl_localize_mapcov_batch); "cov_status" 3: map_cov does not fit the map."""
+        if map_cov is not None and not with_cov:
+            raise ValueError("map_cov needs with_cov=True")
         dets = list(detections)
         if len(dets) > 256:
             raise ValueError("at most 256 detections per frame")
@@ -217,7 +221,7 @@ class TagDetector:
             obs["corners"][0, k] = np.asarray(d['lb-rb-rt-lt'], dtype=np.float32).reshape(8)
             obs["T"][0, k] = np.asarray(Ts[k], dtype=np.float64).reshape(16)[:12]
         res = self.detector._det.localize(obs, tag_map, self._K(), self._dist(), self.tag_size, max_tag_rms_px,
-                                          sigma_px=float(sigma_px) if with_cov else None)
+                                          sigma_px=float(sigma_px) if with_cov else None, map_cov=map_cov)
         r = (res[0] if with_cov else res)[0]
         out = {"ok": int(r["status"]) == 0, "T": np.array(r["T"]), "rms_px": float(r["rms_px"]), "n_tags": int(r["n_tags"]),
                "n_rejected": int(r["n_rejected"]), "status": int(r["status"])}
@@ -322,7 +326,7 @@ class TagDetector:
                                                 max_iters=max_iters, model=None if lens_model == "brown" else lens_model)
         return CalibrationResult(res, cam, n_dist, lens_model)
 
-    def build_map(self, frames, world_id=None, max_iters=30, with_std=True, huber_px=0.0, tag_sizes=None):
+    def build_map(self, frames, world_id=None, max_iters=30, with_std=True, huber_px=0.0, tag_sizes=None, with_cov=False):
         """Host frames ((n, H, W, 3) BGR or (n, H, W) gray uint8, or a list of them) that see an unknown set of tags ->
         mapping.MapResult: the tags' world<-tag poses (tag_map, world tag world_id, default the lowest id seen), every
         frame's camera pose and a per-tag std.  Detect with this detector's camera model and tag size, pack (asl_obs
@@ -331,7 +335,8 @@ class TagDetector:
         of bending the map; the result then has n_soft, slot_weight and soft_slots().  tag_sizes ({id: size}, or an
         array indexed by id that covers every id seen): tags whose side is not the detector's tag_size (0, or an id
         not named: tag_size), each solved at its own (asl_map_sized_batch); result.tag_map carries the sizes, so that
-        localize() and localize_sequence() against it, or against the file tag_map.save() writes, honour them."""
+        localize() and localize_sequence() against it, or against the file tag_map.save() writes, honour them.
+        with_cov: the joint covariance of the mapped tags as result.cov, a mapping.MapCovariance (asl_mapcov_batch)."""
         from .dist import pack_observations
         from .mapping import MapResult
         if self.camera_matrix is None:
@@ -355,8 +360,8 @@ class TagDetector:
             tag_sizes = table[:n_ids]
         out = self.detector._det.build_map(obs, n_ids, self._K(), dist, self.tag_size, world_id=-1 if world_id is None else int(world_id),
                                            max_iters=max_iters, with_std=with_std, huber_px=huber_px, with_slot_weight=bool(huber_px),
-                                           tag_sizes=tag_sizes)
-        return MapResult(*out, slot_ids=obs["id"] if huber_px else None)
+                                           tag_sizes=tag_sizes, with_cov=with_cov)
+        return MapResult.from_call(out, slot_ids=obs["id"] if huber_px else None, with_cov=with_cov)
 
     def extend_map(self, frames_or_obs, tag_map, tag_sizes=None, max_view_rms_px=0.0, min_views=2, sigma_px=None, max_tag_rms_px=0.0):
         """Frames that see tags of tag_map (a localize.TagMap) and tags it does not have -> (locate.LocateResult, one

@@ -309,12 +309,15 @@ int asl_localize_batch(asl_detector *det, const asl_obs *obs, int n_frames, int 
    sigma^2 = cost / dof with dof = 8 n_tags - 6.  For one tag that is 2 degrees of freedom: the estimate is then itself
    uncertain by a factor of about two either way, and a given sigma_px is the better choice.  A covariance is as good as
    the model: independent Gaussian corner noise, a linearisation that holds over the error, and (localisation) a map taken
-   as exact -- the uncertainty of the map tags is not propagated. */
+   as exact -- asl_localize_cov_* and asl_localize_rig_cov_* do not propagate the uncertainty of the map tags, which for a
+   map built by asl_map_* is most of the pose's error; asl_localize_mapcov_* below do, from the map's joint covariance. */
 typedef struct {
     double cov[36];     /* row-major 6x6, symmetric to the bit, order (rx ry rz | px py pz) */
     double sigma_px;    /* the pixel sigma that scaled it (given, or estimated) */
     int32_t dof;        /* residuals - 6 of the solve it belongs to (0 with status 1) */
-    int32_t status;     /* 0 ok; 1 the pose has none (its own status != 0 / PnP not ok); 2 J^T J not positive definite */
+    int32_t status;     /* 0 ok; 1 the pose has none (its own status != 0 / PnP not ok); 2 J^T J not positive definite;
+                           3 (asl_localize_mapcov_* only) a d_cov_slot entry of a slot in the solve outside [-1, ld / 6), or a
+                           block of d_map_cov that is not finite */
 } asl_pose_cov;         /* 304 bytes; status != 0: cov all zero */
 
 /* asl_localize_frames_device with the covariance of every frame's world<-camera pose: d_out receives exactly what
@@ -328,6 +331,31 @@ int asl_localize_cov_frames_device(asl_detector *det, const void *d_obs, int n_f
 int asl_localize_cov_batch(asl_detector *det, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
                            const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
                            double sigma_px, asl_cam_pose *out, asl_pose_cov *cov);
+
+/* asl_localize_cov_frames_device with the uncertainty of the map carried into the pose covariance.  d_map_cov (doubles,
+   row-major, leading dimension ld, a positive multiple of 6) and d_cov_slot (n_ids int32: the block of every id, -1 for an
+   id without one, which is then exact) are what asl_mapcov_frames_device writes, and may be handed over on the same stream
+   without a host copy.  d_out is byte for byte what the plain call writes.  Over the slots s in the final solve (after the
+   gate), tag j(s), at the returned pose (R, t) = camera<-world: J_s (8 x 6) the rows the solver forms,
+   Jp [-[p_c]x | I]; M_s (8 x 6) the rows of the same residuals over the tag's (omega, v), Jp R [-[X]x | I], X the world
+   corner; A = sum J_s^T J_s, N_s = J_s^T M_s, Q = sum over s, s' with a block of N_s Sigma[j(s), j(s')] N_s'^T, and
+   C = sigma^2 A^-1 + A^-1 Q A^-1, mapped to the world<-camera (r, d) convention above like the plain covariance; sigma and
+   dof as there.  With every slot -1 the record is byte for byte asl_localize_cov_frames_device's.  status 3 (zeros; the
+   pose is untouched): see asl_pose_cov.  The pair sum runs in a fixed order: the same input gives the same bytes;
+   max_tags = 256 with every slot in the solve is 65,536 pairs a frame.  ASL_EINVAL, nothing written: whatever
+   asl_localize_cov_frames_device refuses; d_map_cov or d_cov_slot NULL; ld < 6 or not a multiple of 6.  Mountings,
+   intrinsics and tag sizes stay exact.  tests/localize_mapcov_ref.py states the computation. */
+int asl_localize_mapcov_frames_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, const void *d_map, int n_ids,
+                                      const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
+                                      double sigma_px, void *d_out, void *d_cov, const void *d_map_cov, int ld,
+                                      const void *d_cov_slot, void *stream);
+/* The same computation on host records, synchronous.  The host form also refuses (ASL_EINVAL, nothing written) what the
+   device form can only report as status 3: a cov_slot entry outside [-1, ld / 6), or an entry of the blocks the slots
+   refer to that is not finite. */
+int asl_localize_mapcov_batch(asl_detector *det, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *map, int n_ids,
+                              const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
+                              double sigma_px, asl_cam_pose *out, asl_pose_cov *cov, const double *map_cov, int ld,
+                              const int32_t *cov_slot);
 
 /* ---- several cameras on one rigid body (a "rig") localised together: one pose rig<-world per frame, every camera's
    corners in one solve.  Camera c has its own model (K, dist: as asl_solve_pnp_batch) and a fixed mounting
@@ -360,7 +388,7 @@ int asl_localize_rig_frames_device(asl_detector *det, const void *d_obs, int n_c
                                    int n_ids, const void *d_rig, double tag_size, double max_tag_rms_px, void *d_out, void *stream);
 /* With the covariance of every frame's world<-rig pose (asl_pose_cov, dof = 8 n_tags - 6), as
    asl_localize_cov_frames_device: d_out byte for byte what the plain call writes.  The mountings and the map are taken as
-   exact: their uncertainty is not propagated. */
+   exact: their uncertainty is not propagated (the map's: asl_localize_rig_mapcov_frames_device below). */
 int asl_localize_rig_cov_frames_device(asl_detector *det, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_map,
                                        int n_ids, const void *d_rig, double tag_size, double max_tag_rms_px, double sigma_px,
                                        void *d_out, void *d_cov, void *stream);
@@ -370,6 +398,17 @@ int asl_localize_rig_batch(asl_detector *det, const asl_obs *obs, int n_cams, in
 int asl_localize_rig_cov_batch(asl_detector *det, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_map_tag *map,
                                int n_ids, const asl_rig_camera *rig, double tag_size, double max_tag_rms_px, double sigma_px,
                                asl_cam_pose *out, asl_pose_cov *cov);
+
+/* asl_localize_rig_cov_frames_device with the map's joint covariance carried into the covariance of the world<-rig pose,
+   as asl_localize_mapcov_frames_device: R is the rotation of E_c (rig<-world) for the view's camera, J_s the rows over the
+   rig pose as the solver forms them.  The mountings stay exact. */
+int asl_localize_rig_mapcov_frames_device(asl_detector *det, const void *d_obs, int n_cams, int n_frames, int max_tags,
+                                          const void *d_map, int n_ids, const void *d_rig, double tag_size, double max_tag_rms_px,
+                                          double sigma_px, void *d_out, void *d_cov, const void *d_map_cov, int ld,
+                                          const void *d_cov_slot, void *stream);
+int asl_localize_rig_mapcov_batch(asl_detector *det, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_map_tag *map,
+                                  int n_ids, const asl_rig_camera *rig, double tag_size, double max_tag_rms_px, double sigma_px,
+                                  asl_cam_pose *out, asl_pose_cov *cov, const double *map_cov, int ld, const int32_t *cov_slot);
 
 /* One asl_pose_cov per asl_obs record (n_records of them, as asl_pack_observations_device writes them; device pointers,
    asynchronous on `stream`): the covariance of the camera<-tag pose in the record from its 4 corners (8 residuals, dof 2),
@@ -618,6 +657,47 @@ int asl_map_rig_sized_batch(asl_detector *det, const asl_obs *obs, int n_cams, i
                             const asl_rig_camera *rig, double tag_size, const float *tag_sizes, int world_id, double sized_huber_px,
                             int max_iters, asl_map_tag *map, double *tag_std, asl_cam_pose *poses, asl_map_result *result,
                             double *slot_weight);
+
+/* The joint covariance of a reconstructed map: asl_map_sized_frames_device / asl_map_rig_sized_frames_device (tag_sizes may
+   be NULL, cov_huber_px is the threshold every other layer calls huber_px, 0: the squared loss) with, after d_slot_weight,
+   the covariance BETWEEN the tags that d_tag_std gives only the diagonal of.  A per-tag std is not enough to carry the
+   uncertainty of a map into a pose localised against it: the tags of a map share their frames, so their errors are
+   correlated.  Sigma_map = s^2 S^-1, S the undamped reduced system over the tags at the returned solution (the weighted
+   one under the Huber loss, with a rig's views folded: the system d_tag_std reads) and s^2 the variance factor of
+   d_tag_std, restricted to the mapped tags other than the world tag; six parameters per tag, (omega, v) of a left update
+   of world<-tag in the world frame, as d_tag_std.
+   d_cov_slot: n_ids int32.  Entry i is the block k of id i in the matrix, blocks numbered in ascending id; -1 for the ids
+   without a covariance: unmapped ids and the world tag.  d_map_cov: doubles, row-major with the leading dimension
+   ld = 6 * cap_tags, cap_tags stated by the caller; rows and columns 6 k .. 6 k + 5 belong to block k.  Only the leading
+   6 n_cov x 6 n_cov region is written, n_cov = result.n_tags - 1; it is symmetric to the bit, and the square roots of its
+   diagonal are d_tag_std to rounding.  If the undamped system is not positive definite, or the result's status is not 0,
+   every d_cov_slot entry is -1 and nothing of d_map_cov is written: the cases in which d_tag_std is all zero.  The gauge is
+   the world tag, taken as exact; the covariance of the frame poses is not reported.
+   Every other output is byte for byte that of the sized call on the same input (d_tag_std may be NULL).
+   ASL_EINVAL, nothing written: whatever the sized call refuses; d_cov_slot or d_map_cov NULL; cap_tags < 1; more tags
+   besides the world tag in the problem (the ids seen in used frames) than cap_tags, which is known after the call's one
+   host wait and refused there, before anything else is enqueued.  The columns of L^-1 (S = L L^T) are kept in the
+   detector's workspace, 8 (6 tags)^2 bytes.  Deterministic: the same input gives the same bytes.  tests/map_cov_ref.py
+   states the computation. */
+int asl_mapcov_frames_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, int n_ids, const double *K,
+                              const double *dist, int n_dist, double tag_size, const float *tag_sizes, int world_id,
+                              double cov_huber_px, int max_iters, void *d_map, void *d_tag_std, void *d_poses, void *d_result,
+                              void *d_slot_weight, void *d_cov_slot, void *d_map_cov, int cap_tags, void *stream);
+/* The same computation on host records, synchronous; tag_std and slot_weight may be NULL.  map_cov is cap_tags x cap_tags
+   blocks of the caller's; the part outside the leading 6 n_cov x 6 n_cov region is left as it was. */
+int asl_mapcov_batch(asl_detector *det, const asl_obs *obs, int n_frames, int max_tags, int n_ids, const double *K,
+                      const double *dist, int n_dist, double tag_size, const float *tag_sizes, int world_id, double cov_huber_px,
+                      int max_iters, asl_map_tag *map, double *tag_std, asl_cam_pose *poses, asl_map_result *result,
+                      double *slot_weight, int32_t *cov_slot, double *map_cov, int cap_tags);
+/* The rig forms: asl_map_rig_sized_frames_device / asl_map_rig_sized_batch with the same outputs. */
+int asl_mapcov_rig_frames_device(asl_detector *det, const void *d_obs, int n_cams, int n_frames, int max_tags, int n_ids,
+                                  const void *d_rig, double tag_size, const float *tag_sizes, int world_id, double cov_huber_px,
+                                  int max_iters, void *d_map, void *d_tag_std, void *d_poses, void *d_result, void *d_slot_weight,
+                                  void *d_cov_slot, void *d_map_cov, int cap_tags, void *stream);
+int asl_mapcov_rig_batch(asl_detector *det, const asl_obs *obs, int n_cams, int n_frames, int max_tags, int n_ids,
+                          const asl_rig_camera *rig, double tag_size, const float *tag_sizes, int world_id, double cov_huber_px,
+                          int max_iters, asl_map_tag *map, double *tag_std, asl_cam_pose *poses, asl_map_result *result,
+                          double *slot_weight, int32_t *cov_slot, double *map_cov, int cap_tags);
 
 /* ---- extending a map: the world<-tag pose of tags the map does not have, from frames whose camera poses are known
    (asl_localize_* against the tags the map does have, asl_smooth_*, or asl_map_*'s d_poses).  The dual of localisation:

@@ -11,7 +11,12 @@ inside every repetition; asl_pose_cov_device over the same records (the per-tag 
 Mahalanobis distance of the joint pose's error against the ground truth under the reported covariance (6 on average for
 Gaussian corner noise of the estimated sigma; detected corners are not that, so it is a finding, not a check).
 
-    python tools/localize_lab.py [--frames 1024] [--reps 30] [--max-tags 32] [--gate 0] [--cov]
+--map-cov (implies --cov) adds asl_localize_mapcov_frames_device as one more alternating leg: the same call with a joint
+covariance of the map carried into the pose covariance.  The map is the true one, so the matrix is a stand-in with the
+shape a reconstructed map's has: 2 mrad and 0.05 units per tag, 1 mrad and 0.03 units common to all, the lowest id exact.
+It prints the kernel time next to the plain and the _cov ones and how much larger the reported std becomes.
+
+    python tools/localize_lab.py [--frames 1024] [--reps 30] [--max-tags 32] [--gate 0] [--cov] [--map-cov]
 """
 import argparse
 import json
@@ -37,7 +42,9 @@ def main():
     ap.add_argument("--max-tags", type=int, default=32)
     ap.add_argument("--gate", type=float, default=0.0)
     ap.add_argument("--cov", action="store_true", help="also time the calls with covariance, interleaved with the plain one")
+    ap.add_argument("--map-cov", action="store_true", help="also time the call that carries a map covariance into the pose covariance")
     a = ap.parse_args()
+    a.cov = a.cov or a.map_cov
 
     import torch
 
@@ -75,6 +82,19 @@ def main():
     def launch_tag_cov():
         det.pose_cov_device(d_obs.data_ptr(), n * mt, d_tag_cov.data_ptr(), K, None, bench.TAG_INNER, 0.0, stream=stream.cuda_stream)
 
+    d_mapcov = torch.empty((n, POSE_COV_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    map_ids = sorted(tm.ids())[1:]
+    nb = len(map_ids)
+    sigma_map = np.kron(np.eye(nb), np.diag([2e-3 ** 2] * 3 + [0.05 ** 2] * 3)) + np.kron(np.ones((nb, nb)), np.diag([1e-3 ** 2] * 3 + [0.03 ** 2] * 3))
+    slot = np.full(len(rec), -1, dtype=np.int32)
+    slot[map_ids] = np.arange(nb)
+    d_sigma, d_slot = torch.from_numpy(sigma_map).to(dev), torch.from_numpy(slot).to(dev)
+
+    def launch_mapcov():
+        det.localize_device(d_obs.data_ptr(), n, mt, d_map.data_ptr(), len(rec), d_out.data_ptr(), K, None, bench.TAG_INNER,
+                            max_tag_rms_px=a.gate, stream=stream.cuda_stream, cov_ptr=d_mapcov.data_ptr(), sigma_px=0.0,
+                            map_cov=(d_sigma.data_ptr(), 6 * nb, d_slot.data_ptr()))
+
     def timed(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(stream)
@@ -83,7 +103,7 @@ def main():
         e1.synchronize()
         return e0.elapsed_time(e1)
 
-    legs = [launch] + ([launch_cov, launch_tag_cov] if a.cov else [])
+    legs = [launch] + ([launch_cov, launch_tag_cov] if a.cov else []) + ([launch_mapcov] if a.map_cov else [])
     with torch.cuda.stream(stream):
         for _ in range(a.warmup):
             for fn in legs:
@@ -147,6 +167,17 @@ def main():
             "single_tag_std": {"rotation_mrad_median": float(np.median(tstd[:, :3])) * 1e3,
                                "translation_mm_median": float(np.median(tstd[:, 3:])) * bench.MM_PER_UNIT},
             "note": "sigma estimated per solve (sigma_px = 0); chi-square(6) has mean 6, median 5.35",
+        }
+    if a.map_cov:
+        mc = d_mapcov.cpu().numpy().view(POSE_COV_DTYPE).reshape(n)
+        both = (cov["status"] == 0) & (mc["status"] == 0)
+        ratio = np.sqrt(np.diagonal(mc["cov"][both], axis1=1, axis2=2) / np.diagonal(cov["cov"][both], axis1=1, axis2=2))
+        line["map_cov"] = {
+            "kernel_ms_median": float(np.median(times[3])), "kernel_ms_min": float(np.min(times[3])),
+            "cov_ms_median_interleaved": float(np.median(times[1])), "plain_ms_median_interleaved": float(np.median(times[0])),
+            "map_blocks": nb, "frames_with_cov": int((mc["status"] == 0).sum()),
+            "std_over_pixel_only_std": {"rotation_median": float(np.median(ratio[:, :3])), "translation_median": float(np.median(ratio[:, 3:]))},
+            "note": "a stand-in map covariance: 2 mrad / 0.05 units per tag, 1 mrad / 0.03 units common, lowest id exact",
         }
     print(json.dumps(line))
     det.close()

@@ -16,6 +16,12 @@ is measured against the single-camera solve of the ring's camera 0 on the same f
 views, pairs, trials, median ms and the map errors against the truth.
 
     python tools/map_lab.py --rig 2 [--frames 256] [--huber 1.0]
+
+With --cov the covariance solve (asl_mapcov_frames_device) is measured against the same solve without it on the bench scene
+and on the 200-tag scene, the two legs alternating rep by rep: median ms of each, their difference (the kept columns of
+L^-1 and the Gram kernel), the blocks of the matrix and the bytes of the columns and of the matrix.
+
+    python tools/map_lab.py --cov [--frames 1024] [--huber 1.0]
 """
 import argparse
 import json
@@ -187,6 +193,53 @@ def rig_lab(det, a):
     return r
 
 
+def cov_lab(det, a):
+    """the solve without and with the joint covariance, alternating, on both scenes"""
+    import torch
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(7)
+    out = {}
+    for name, ntags, nf in (("bench_20", 20, a.frames), ("scene_200", 200, min(a.frames, 256))):
+        K, tags, cams, obs = scene_block(nf, ntags, 0.3, rng)
+        n_ids = 1 + max(t["id"] for t in tags)
+        n, mt = obs.shape
+        cap = len({int(i) for i in obs["id"].ravel() if i >= 0})
+        d_obs = torch.from_numpy(np.ascontiguousarray(obs).view(np.uint8).reshape(n, -1)).to(dev)
+        d_map = torch.empty((n_ids, _lib.MAP_TAG_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        d_std = torch.empty((n_ids, 6), dtype=torch.float64, device=dev)
+        d_poses = torch.empty((n, _lib.CAM_POSE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        d_res = torch.empty((64,), dtype=torch.uint8, device=dev)
+        d_slot = torch.empty((n_ids,), dtype=torch.int32, device=dev)
+        d_cov = torch.zeros((6 * cap, 6 * cap), dtype=torch.float64, device=dev)
+        s = torch.cuda.Stream(dev)
+        legs = {"plain": dict(), "cov": dict(cov=(d_slot.data_ptr(), d_cov.data_ptr(), cap))}
+        ms = {k: [] for k in legs}
+        for r in range(a.reps + 2):
+            for leg, kw in legs.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(s)
+                det.build_map_device(d_obs.data_ptr(), n, mt, n_ids, K, None, LC.TAG_INNER, d_map.data_ptr(), d_std.data_ptr(), d_poses.data_ptr(),
+                                     d_res.data_ptr(), max_iters=a.iters, stream=s.cuda_stream, huber_px=a.huber, **kw)
+                e1.record(s)
+                s.synchronize()
+                if r >= 2:
+                    ms[leg].append(e0.elapsed_time(e1))
+        res = d_res.cpu().numpy().view(_lib.MAP_RESULT_DTYPE).reshape(())
+        slot, std, C = d_slot.cpu().numpy(), d_std.cpu().numpy(), d_cov.cpu().numpy()
+        nb = int((slot >= 0).sum())
+        own = np.concatenate([std[i] for i in np.flatnonzero(slot >= 0)]) if nb else np.zeros(0)
+        diag = float(np.abs(np.sqrt(np.diag(C)[:6 * nb]) / own - 1).max()) if nb else 0.0
+        n_sys = 6 * int(res["n_tags"])
+        r = dict(frames=n, tags=int(res["n_tags"]), status=int(res["status"]), trials=int(res["iterations"]), huber_px=a.huber, blocks=nb,
+                 plain_ms=float(np.median(ms["plain"])), plain_ms_spread=[float(min(ms["plain"])), float(max(ms["plain"]))],
+                 cov_ms=float(np.median(ms["cov"])), cov_ms_spread=[float(min(ms["cov"])), float(max(ms["cov"]))],
+                 cov_extra_ms=float(np.median(np.array(ms["cov"]) - np.array(ms["plain"]))),
+                 columns_bytes=8 * n_sys * n_sys, matrix_bytes=8 * 36 * nb * nb, diag_vs_std=diag)
+        out[name] = r
+        print("cov_lab", name, json.dumps(r), flush=True)
+    return out
+
+
 def time_host(det, obs, K, iters):
     t0 = time.perf_counter()
     frames = [[(int(o["id"]), MR.rec4(o["T"]), o["corners"].astype(np.float64).reshape(4, 2)) for o in fr if o["flags"] & 1 and o["id"] >= 0]
@@ -238,8 +291,16 @@ def main():
     ap.add_argument("--huber", type=float, default=0.0, help="huber_px of the robust leg; > 0 runs the plain / robust comparison alone")
     ap.add_argument("--outliers", type=int, default=0, help="slots given their neighbour slot's corners")
     ap.add_argument("--rig", type=int, default=0, help="cameras of the rig; > 0 runs the rig / single-camera comparison alone")
+    ap.add_argument("--cov", action="store_true", help="runs the comparison of the solve without and with the joint covariance alone")
     a = ap.parse_args()
     det = _lib.Detector("tagStandard41h12", id_limit=0)
+    if a.cov:
+        r = cov_lab(det, a)
+        det.close()
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(r, f, indent=1)
+        return
     if a.rig > 0:
         r = rig_lab(det, a)
         det.close()
