@@ -43,6 +43,8 @@ assert SMOOTH_RESULT_DTYPE.itemsize == 64
 assert POSE_COV_DTYPE.itemsize == 304
 RIG_CAMERA_DTYPE = np.dtype([("K", "<f8", (3, 3)), ("dist", "<f8", (5,)), ("E", "<f8", (3, 4)), ("n_dist", "<i4"), ("reserved", "<i4")])  # asl_rig_camera
 assert RIG_CAMERA_DTYPE.itemsize == 216
+BUNDLE_REL_DTYPE = np.dtype([("T", "<f8", (4, 4)), ("cov", "<f8", (6, 6)), ("status", "<i4"), ("reserved", "<i4")])  # asl_bundle_rel; T = ref<-bundle
+assert BUNDLE_REL_DTYPE.itemsize == 424
 RIG_CALIB_RESULT_DTYPE = np.dtype([("rms_px", "<f8"), ("rms_init_px", "<f8"), ("sigma_px", "<f8"), ("n_frames_used", "<i4"), ("n_corners", "<i4"),
                                    ("iterations", "<i4"), ("status", "<i4"), ("n_solved", "<i4"), ("reserved", "<i4"),
                                    ("cam_status", "<i4", (16,)), ("cam_frames", "<i4", (16,))])  # asl_rig_calib_result
@@ -64,6 +66,8 @@ EXPORTS = [
     "asl_pose_cov_device", "asl_solve_pnp_cov_batch", "asl_calibrate_frames_device", "asl_calibrate_batch",
     "asl_calibrate_lens_frames_device", "asl_calibrate_lens_batch",
     "asl_localize_rig_frames_device", "asl_localize_rig_cov_frames_device", "asl_localize_rig_batch", "asl_localize_rig_cov_batch",
+    "asl_localize_bundles_frames_device", "asl_localize_bundles_batch", "asl_localize_bundles_rig_frames_device", "asl_localize_bundles_rig_batch",
+    "asl_bundle_relative_device", "asl_bundle_relative_batch",
     "asl_calibrate_rig_frames_device", "asl_calibrate_rig_batch",
     "asl_map_frames_device", "asl_map_batch", "asl_map_robust_frames_device", "asl_map_robust_batch", "asl_map_rig_frames_device", "asl_map_rig_batch", "asl_map_sized_frames_device", "asl_map_sized_batch",
     "asl_map_rig_sized_frames_device", "asl_map_rig_sized_batch",
@@ -228,6 +232,14 @@ def load():
     L.asl_localize_rig_cov_batch.argtypes = rig + [dbl, vp, vp]
     L.asl_localize_rig_mapcov_frames_device.argtypes = rig + [dbl, vp, vp] + map_cov_in + [vp]
     L.asl_localize_rig_mapcov_batch.argtypes = rig + [dbl, vp, vp] + map_cov_in
+    bundles = loc[:5] + [i32] + loc[5:] + [dbl, vp, vp]             # ..., maps, n_bundles, n_ids, ..., max_tag_rms_px, sigma_px, out, cov
+    L.asl_localize_bundles_frames_device.argtypes = bundles + [vp]
+    L.asl_localize_bundles_batch.argtypes = bundles
+    bundles_rig = rig[:6] + [i32] + rig[6:] + [dbl, vp, vp]
+    L.asl_localize_bundles_rig_frames_device.argtypes = bundles_rig + [vp]
+    L.asl_localize_bundles_rig_batch.argtypes = bundles_rig
+    L.asl_bundle_relative_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]    # detector, poses, cov, n_frames, n_bundles, ref, rel, stream
+    L.asl_bundle_relative_batch.argtypes = [vp, vp, vp, i32, i32, i32, vp]
     L.asl_pose_cov_device.argtypes = [vp, vp, i32] + camera + [dbl, vp, vp]
     L.asl_solve_pnp_cov_batch.argtypes = [vp, C.POINTER(C.c_float), dp] + camera + [dbl, vp, i32]
     calib = [vp] + obs_block + tag_map + [dbl, i32, i32, dp, i32, i32, i32, vp, vp]    # ..., tag_size, width, height, K_init, n_dist, flags, max_iters, the two results
@@ -409,6 +421,16 @@ def _size_table(tag_sizes, n_ids):
     if len(table) != n:
         raise ValueError("tag_sizes must be a {id: size} dict or an array of n_ids = %d sizes (got %d)" % (n, len(table)))
     return table
+
+
+def _bundle_tables(bundles, n_ids=None):
+    """(n_bundles, n_ids) MAP_TAG_DTYPE, C-contiguous, of a bundles.BundleSet or of such a block (table b: bundle_b<-tag)"""
+    if hasattr(bundles, "table"):
+        return bundles.table(n_ids)
+    t = np.ascontiguousarray(bundles, dtype=MAP_TAG_DTYPE)
+    if t.ndim != 2:
+        raise ValueError("bundles must be a BundleSet or (n_bundles, n_ids) asl_map_tag records")
+    return t
 
 
 def _rig_records(rig):
@@ -743,6 +765,74 @@ class Detector:
             check(self._L.asl_localize_rig_frames_device(*args, _ptr(out_ptr), _ptr(stream)))
         else:
             check(self._L.asl_localize_rig_cov_frames_device(*args, float(sigma_px), _ptr(out_ptr), _ptr(cov_ptr), _ptr(stream)))
+
+    def localize_bundles(self, obs, bundles, K, dist, tag_size, max_tag_rms_px=0.0, sigma_px=None):
+        """asl_localize_bundles_batch: host records obs (n_frames, max_tags) OBS_DTYPE against bundles (a bundles.BundleSet, or
+        (n_bundles, n_ids) MAP_TAG_DTYPE tables, bundle<-tag) -> (n_frames, n_bundles) CAM_POSE_DTYPE with T = bundle<-camera,
+        entry [f, b] what localize gives for frame f with table b as its map, to the byte.  sigma_px not None: (poses,
+        (n_frames, n_bundles) POSE_COV_DTYPE), as localize."""
+        o, t = _obs_records(obs), _bundle_tables(bundles)
+        keep, Kp, dpp, nd = _camera(K, dist, square=True)
+        shape = (o.shape[0], t.shape[0])
+        out = np.zeros(shape, dtype=CAM_POSE_DTYPE)
+        cov = np.zeros(shape, dtype=POSE_COV_DTYPE) if sigma_px is not None else None
+        check(self._L.asl_localize_bundles_batch(self._h, _data(o), o.shape[0], o.shape[1], _data(t), t.shape[0], t.shape[1], Kp, dpp, nd, float(tag_size),
+                                                 float(max_tag_rms_px), float(sigma_px or 0.0), _data(out), None if cov is None else _data(cov)))
+        return out if cov is None else (out, cov)
+
+    def localize_bundles_device(self, obs_ptr, n_frames, max_tags, maps_ptr, n_bundles, n_ids, out_ptr, K, dist, tag_size, max_tag_rms_px=0.0,
+                                stream=0, cov_ptr=None, sigma_px=0.0):
+        """asl_localize_bundles_frames_device: localize_device with maps_ptr (n_bundles x n_ids asl_map_tag) in place of the
+        map and n_frames x n_bundles records at out_ptr and, if not None, cov_ptr; enqueued on `stream`, no wait."""
+        keep, Kp, dpp, nd = _camera(K, dist, square=True)
+        check(self._L.asl_localize_bundles_frames_device(self._h, _ptr(obs_ptr), int(n_frames), int(max_tags), _ptr(maps_ptr), int(n_bundles), int(n_ids),
+                                                         Kp, dpp, nd, float(tag_size), float(max_tag_rms_px), float(sigma_px), _ptr(out_ptr),
+                                                         _opt_ptr(cov_ptr), _ptr(stream)))
+
+    def localize_bundles_rig(self, obs, bundles, rig, tag_size, max_tag_rms_px=0.0, sigma_px=None):
+        """asl_localize_bundles_rig_batch: localize_bundles for a rig's block obs (n_cams, n_frames, max_tags), camera-major ->
+        (n_frames, n_bundles) CAM_POSE_DTYPE with T = bundle<-rig, entry [f, b] what localize_rig gives with table b."""
+        o = np.ascontiguousarray(obs, dtype=OBS_DTYPE)
+        if o.ndim != 3:
+            raise ValueError("obs must be (n_cams, n_frames, max_tags) asl_obs records")
+        t, r = _bundle_tables(bundles), _rig_records(rig)
+        if len(r) != o.shape[0]:
+            raise ValueError("the rig has %d cameras, obs has %d" % (len(r), o.shape[0]))
+        shape = (o.shape[1], t.shape[0])
+        out = np.zeros(shape, dtype=CAM_POSE_DTYPE)
+        cov = np.zeros(shape, dtype=POSE_COV_DTYPE) if sigma_px is not None else None
+        check(self._L.asl_localize_bundles_rig_batch(self._h, _data(o), o.shape[0], o.shape[1], o.shape[2], _data(t), t.shape[0], t.shape[1], _data(r),
+                                                     float(tag_size), float(max_tag_rms_px), float(sigma_px or 0.0), _data(out),
+                                                     None if cov is None else _data(cov)))
+        return out if cov is None else (out, cov)
+
+    def localize_bundles_rig_device(self, obs_ptr, n_cams, n_frames, max_tags, maps_ptr, n_bundles, n_ids, rig_ptr, out_ptr, tag_size,
+                                    max_tag_rms_px=0.0, stream=0, cov_ptr=None, sigma_px=0.0):
+        """asl_localize_bundles_rig_frames_device: localize_rig_device with maps_ptr (n_bundles x n_ids asl_map_tag) in place of
+        the map and n_frames x n_bundles records at out_ptr and, if not None, cov_ptr; enqueued on `stream`."""
+        check(self._L.asl_localize_bundles_rig_frames_device(self._h, _ptr(obs_ptr), int(n_cams), int(n_frames), int(max_tags), _ptr(maps_ptr),
+                                                             int(n_bundles), int(n_ids), _ptr(rig_ptr), float(tag_size), float(max_tag_rms_px),
+                                                             float(sigma_px), _ptr(out_ptr), _opt_ptr(cov_ptr), _ptr(stream)))
+
+    def bundle_relative(self, poses, cov, ref):
+        """asl_bundle_relative_batch: poses (n_frames, n_bundles) CAM_POSE_DTYPE as localize_bundles returns them, cov their
+        (n_frames, n_bundles) POSE_COV_DTYPE or None -> (n_frames, n_bundles) BUNDLE_REL_DTYPE, T = ref<-bundle with its
+        covariance (status 2, zeros, without cov).  The two poses of a pair are taken as independent."""
+        p = np.ascontiguousarray(poses, dtype=CAM_POSE_DTYPE)
+        if p.ndim != 2:
+            raise ValueError("poses must be (n_frames, n_bundles) asl_cam_pose records")
+        c = None if cov is None else np.ascontiguousarray(cov, dtype=POSE_COV_DTYPE)
+        if c is not None and c.shape != p.shape:
+            raise ValueError("cov must have the shape of poses")
+        rel = np.zeros(p.shape, dtype=BUNDLE_REL_DTYPE)
+        check(self._L.asl_bundle_relative_batch(self._h, _data(p), None if c is None else _data(c), p.shape[0], p.shape[1], int(ref), _data(rel)))
+        return rel
+
+    def bundle_relative_device(self, poses_ptr, cov_ptr, n_frames, n_bundles, ref, rel_ptr, stream=0):
+        """asl_bundle_relative_device: poses_ptr (n_frames x n_bundles asl_cam_pose), cov_ptr (as many asl_pose_cov, or None)
+        and rel_ptr (as many asl_bundle_rel) are device addresses; enqueued on `stream`, no wait."""
+        check(self._L.asl_bundle_relative_device(self._h, _ptr(poses_ptr), _opt_ptr(cov_ptr), int(n_frames), int(n_bundles), int(ref), _ptr(rel_ptr),
+                                                 _ptr(stream)))
 
     def locate_tags(self, obs, poses, map_records, K, dist, tag_size, max_view_rms_px=0.0, min_views=2, sigma_px=None):
         """asl_locate_tags_batch: host records obs (n_frames, max_tags) OBS_DTYPE, their frames' poses (n_frames,)

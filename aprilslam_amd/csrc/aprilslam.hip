@@ -35,6 +35,7 @@
 #include "k_localize.inc"
 #include "k_posecov.inc"
 #include "k_rig.inc"
+#include "k_bundle.inc"
 #include "k_calib.inc"
 #include "k_rigcal.inc"
 #include "k_map.inc"

@@ -15,6 +15,8 @@
 //           of sigma^2 (J^T J)^-1 in the output convention (pose_cov_column_dev, k_pnp.inc; tests/pose_cov_ref.py)
 //   mapcov  k_localize_mapcov only (asl_localize_mapcov_*): the map's joint covariance carried into that covariance
 //           (loc_map_term; tests/localize_mapcov_ref.py)
+//   bundles asl_localize_bundles_*: the grid's second dimension chooses one of several maps (the tag layouts of several
+//           objects), one wavefront per (frame, bundle), each the solve above against its own table (loc_bundle_map)
 // tests/localize_ref.py is the NumPy statement of the same computation.  Latency-bound scalar float64 like k_pnp.inc:
 // the time goes into the dependent chains of the passes and reductions, not into bytes (136 B per slot in, 160 B per frame out).
 // These steps are written once, in loc_solve_frame<COV, Model>, over the slots of a model: where slot g's record lives,
@@ -725,7 +727,13 @@ __device__ __forceinline__ void loc_solve_frame(const Model &m, const LocLds &L,
     }
 }
 
-// One wavefront per frame; COV: also cov[frame] (world<-camera), which the plain instantiation never touches
+// The bundle dimension of k_localize and k_localize_rig (asl_localize_bundles_*): the grid is (frame, bundle), and wavefront
+// (f, b) solves frame f against table b of map (gridDim.y tables of n_ids entries, bundle<-tag) into record f * gridDim.y + b.
+// The one-map entry points launch gridDim.y = 1: table 0, record f.
+__device__ __forceinline__ const MapTagRec *loc_bundle_map(const MapTagRec *map, int n_ids) { return map + (size_t)blockIdx.y * (size_t)n_ids; }
+__device__ __forceinline__ size_t loc_bundle_record() { return (size_t)blockIdx.x * gridDim.y + blockIdx.y; }
+
+// One wavefront per (frame, bundle); COV: also cov[record] (world<-camera), which the plain instantiation never touches
 template <bool COV>
 __global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs, int max_tags, const MapTagRec *__restrict__ map, int n_ids,
                                                  CamDev cam, double gate, CamPoseRec *__restrict__ out, PoseCovRec *__restrict__ cov,
@@ -733,8 +741,9 @@ __global__ void __launch_bounds__(64) k_localize(const ObsRec *__restrict__ obs,
 {
     extern __shared__ double s_dyn[];
     const LocOneCam m{cam, obs + (size_t)blockIdx.x * max_tags, max_tags};
-    loc_solve_frame<COV>(m, loc_lds(s_dyn, max_tags), map, n_ids, cam.half, gate, out + blockIdx.x, COV ? cov + blockIdx.x : nullptr, sigma_px,
-                         (int)threadIdx.x);
+    const size_t rec = loc_bundle_record();
+    loc_solve_frame<COV>(m, loc_lds(s_dyn, max_tags), loc_bundle_map(map, n_ids), n_ids, cam.half, gate, out + rec, COV ? cov + rec : nullptr,
+                         sigma_px, (int)threadIdx.x);
 }
 
 // k_localize<true> with the map's joint covariance carried into cov[frame] (asl_localize_mapcov_*): loc_solve_frame's

@@ -203,7 +203,8 @@ __device__ __forceinline__ void rig_fill_cams(double *cams, const RigCamRec *__r
     }
 }
 
-// One wavefront per frame; COV: also the first-order covariance of the world<-rig pose written (asl_pose_cov) into cov[frame]
+// One wavefront per (frame, bundle) (loc_bundle_map, k_localize.inc); COV: also the first-order covariance of the world<-rig
+// pose written (asl_pose_cov) into cov[record]
 template <bool COV>
 __global__ void __launch_bounds__(64) k_localize_rig(const ObsRec *__restrict__ obs, int n_cams, int max_tags, const MapTagRec *__restrict__ map,
                                                      int n_ids, const RigCamRec *__restrict__ rig, double half, double gate,
@@ -216,8 +217,9 @@ __global__ void __launch_bounds__(64) k_localize_rig(const ObsRec *__restrict__ 
     rig_fill_cams(cams, rig, n_cams, lane);
 
     const LocRig m{cams, obs, 65536u / (unsigned int)max_tags + 1u, n_cams, max_tags, (int)gridDim.x, (int)blockIdx.x};
-    loc_solve_frame<COV>(m, loc_lds(s_dyn + RIG_CAM_DOUBLES * n_cams, m.nslots()), map, n_ids, half, gate, out + blockIdx.x,
-                         COV ? cov + blockIdx.x : nullptr, sigma_px, lane);
+    const size_t rec = loc_bundle_record();
+    loc_solve_frame<COV>(m, loc_lds(s_dyn + RIG_CAM_DOUBLES * n_cams, m.nslots()), loc_bundle_map(map, n_ids), n_ids, half, gate, out + rec,
+                         COV ? cov + rec : nullptr, sigma_px, lane);
 }
 
 // k_localize_rig<true> with the map's joint covariance carried into cov[frame] (asl_localize_rig_mapcov_*), as k_localize_mapcov

@@ -57,13 +57,14 @@ struct OutPiece {
     void *host; size_t bytes; void *dev;
 };
 
-// The host forms begin here: the pieces carved from solve_out, the host obs block (rows x max_tags) and the map, if given,
-// into the detector's device copies
+// The host forms begin here: the pieces carved from solve_out, the host obs block (rows x max_tags) and the map, if given
+// (n_maps tables of n_ids entries: the bundle forms have more than one), into the detector's device copies
 template <size_t N>
-static int stage_host_call(asl_detector *d, const char *what, OutPiece (&pieces)[N], const void *obs, int rows, int max_tags, const void *map, int n_ids)
+static int stage_host_call(asl_detector *d, const char *what, OutPiece (&pieces)[N], const void *obs, int rows, int max_tags, const void *map, int n_ids,
+                           size_t n_maps = 1)
 {
     HIPCHK(hipSetDevice(d->device));
-    const size_t obs_bytes = sizeof(asl_obs) * (size_t)rows * (size_t)max_tags, map_bytes = sizeof(asl_map_tag) * (size_t)n_ids;
+    const size_t obs_bytes = sizeof(asl_obs) * (size_t)rows * (size_t)max_tags, map_bytes = sizeof(asl_map_tag) * (size_t)n_ids * n_maps;
     if (carve_ws(d->solve_out, [&](WsCarve &w) { for (OutPiece &p : pieces) p.dev = p.bytes ? w.take<uint8_t>(p.bytes) : nullptr; }) ||
         d->loc_obs.ensure(obs_bytes) || (map && d->loc_map.ensure(map_bytes)))
         return fail(ASL_ENOMEM, "%s workspace allocation failed", what);
@@ -121,7 +122,13 @@ struct LocCall {
     // it, host or device as the rest; every other form leaves them NULL, 0 and false
     const void *map_cov; int ld; const void *cov_slot;
     bool with_mapcov;
+    // the bundle forms (asl_localize_bundles_*): map is n_bundles tables of n_ids entries (bundle<-tag), out and cov
+    // n_frames x n_bundles records; every other form leaves it 0, which is one table and one record per frame
+    int n_bundles;
+    bool with_bundles;
 };
+
+#define LOC_MAX_BUNDLES 1024
 
 static bool is_rig(const LocCall &c) { return c.n_cams || c.rig; }
 
@@ -149,6 +156,12 @@ static int check_localize_call(const asl_detector *d, const LocCall &c, bool dev
     if (!d) return fail(ASL_EINVAL, "NULL detector");
     if (!c.obs || !c.map || !(rig ? c.rig : (const void *)c.cam.K) || !c.out) return fail(ASL_EINVAL, "NULL argument");
     if (c.n_frames < 0) return fail(ASL_EINVAL, "n_frames < 0");
+    if (c.with_bundles) {
+        if (c.n_bundles < 1 || c.n_bundles > LOC_MAX_BUNDLES)
+            return fail(ASL_EINVAL, "n_bundles must be in [1, %d] (got %d)", LOC_MAX_BUNDLES, c.n_bundles);
+        if ((long long)c.n_frames * c.n_bundles > INT32_MAX)
+            return fail(ASL_EINVAL, "n_frames * n_bundles must fit 32 bits (got %d x %d)", c.n_frames, c.n_bundles);
+    }
     if (rig && (c.n_cams < 1 || c.n_cams > RIG_MAX_CAMS)) return fail(ASL_EINVAL, "n_cams must be in [1, %d] (got %d)", RIG_MAX_CAMS, c.n_cams);
     if (int rc = check_obs_args(c.max_tags, c.n_ids, c.cam)) return rc;
     if (rig && c.n_cams * c.max_tags > RIG_MAX_SLOTS)
@@ -177,7 +190,7 @@ static int launch_localize(asl_detector *d, const LocCall &c, hipStream_t st)
     static const double no_K[9] = {};
     const bool rig = is_rig(c);
     const CamDev cam = make_cam(d, rig ? no_K : c.cam.K, c.cam.dist, c.cam.n_dist, c.cam.tag_size);   // a rig: for its half alone
-    const dim3 grid((unsigned int)c.n_frames), block(ASL_WAVE);
+    const dim3 grid((unsigned int)c.n_frames, (unsigned int)std::max(c.n_bundles, 1)), block(ASL_WAVE);   // (frame, bundle)
     const ObsRec *obs = (const ObsRec *)c.obs;
     const MapTagRec *map = (const MapTagRec *)c.map;
     const RigCamRec *tab = (const RigCamRec *)c.rig;
@@ -210,14 +223,16 @@ static int localize_batch(asl_detector *d, const LocCall &c)
     if (int rc = check_localize_call(d, c, false)) return rc;
     if (c.n_frames == 0) return ASL_OK;
     const bool rig = is_rig(c);
-    const size_t n = (size_t)c.n_frames, rig_bytes = sizeof(asl_rig_camera) * (size_t)c.n_cams;
+    const size_t nb_maps = (size_t)std::max(c.n_bundles, 1);   // the bundle forms: that many tables in, records per frame out
+    const size_t n = (size_t)c.n_frames * nb_maps, rig_bytes = sizeof(asl_rig_camera) * (size_t)c.n_cams;
     // the mapcov forms: the blocks the slots refer to (the leading 6 n x 6 n region) staged with 6 n as the leading dimension
     size_t nb = 0;
     for (int i = 0; c.with_mapcov && i < c.n_ids; i++) nb = std::max(nb, (size_t)(((const int32_t *)c.cov_slot)[i] + 1));
     const size_t ldd = 6 * std::max<size_t>(nb, 1), slot_bytes = c.with_mapcov ? sizeof(int32_t) * (size_t)c.n_ids : 0;
     OutPiece o[] = {{c.out, sizeof(asl_cam_pose) * n}, {c.cov, c.cov ? sizeof(asl_pose_cov) * n : 0}, {nullptr, rig_bytes}, {nullptr, slot_bytes},
                     {nullptr, c.with_mapcov ? sizeof(double) * ldd * ldd : 0}};
-    if (int rc = stage_host_call(d, rig ? "rig localisation" : "localisation", o, c.obs, (rig ? c.n_cams : 1) * c.n_frames, c.max_tags, c.map, c.n_ids))
+    if (int rc = stage_host_call(d, rig ? "rig localisation" : "localisation", o, c.obs, (rig ? c.n_cams : 1) * c.n_frames, c.max_tags, c.map, c.n_ids,
+                                 nb_maps))
         return rc;
     if (rig) HIPCHK(hipMemcpy(o[2].dev, c.rig, rig_bytes, hipMemcpyHostToDevice));
     LocCall dc = c;
@@ -318,6 +333,95 @@ extern "C" int asl_localize_rig_mapcov_batch(asl_detector *d, const asl_obs *obs
 {
     return localize_batch(d, {obs, n_cams, n_frames, max_tags, map, n_ids, rig, {nullptr, nullptr, 0, tag_size}, max_tag_rms_px, sigma_px, out, cov, true,
                               map_cov, ld, cov_slot, true});
+}
+
+// The bundle forms: the one-map argument lists with n_bundles after the tables, and d_cov NULL (cov NULL) for the plain kernel.
+extern "C" int asl_localize_bundles_frames_device(asl_detector *d, const void *d_obs, int n_frames, int max_tags, const void *d_maps, int n_bundles,
+                                                  int n_ids, const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
+                                                  double sigma_px, void *d_out, void *d_cov, void *stream)
+{
+    return localize_frames_device(d, {d_obs, 0, n_frames, max_tags, d_maps, n_ids, nullptr, {K, dist, n_dist, tag_size}, max_tag_rms_px, sigma_px, d_out, d_cov,
+                                      false, nullptr, 0, nullptr, false, n_bundles, true}, stream);
+}
+
+extern "C" int asl_localize_bundles_batch(asl_detector *d, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *maps, int n_bundles,
+                                          int n_ids, const double *K, const double *dist, int n_dist, double tag_size, double max_tag_rms_px,
+                                          double sigma_px, asl_cam_pose *out, asl_pose_cov *cov)
+{
+    return localize_batch(d, {obs, 0, n_frames, max_tags, maps, n_ids, nullptr, {K, dist, n_dist, tag_size}, max_tag_rms_px, sigma_px, out, cov, false,
+                              nullptr, 0, nullptr, false, n_bundles, true});
+}
+
+extern "C" int asl_localize_bundles_rig_frames_device(asl_detector *d, const void *d_obs, int n_cams, int n_frames, int max_tags, const void *d_maps,
+                                                      int n_bundles, int n_ids, const void *d_rig, double tag_size, double max_tag_rms_px,
+                                                      double sigma_px, void *d_out, void *d_cov, void *stream)
+{
+    return localize_frames_device(d, {d_obs, n_cams, n_frames, max_tags, d_maps, n_ids, d_rig, {nullptr, nullptr, 0, tag_size}, max_tag_rms_px, sigma_px, d_out,
+                                      d_cov, false, nullptr, 0, nullptr, false, n_bundles, true}, stream);
+}
+
+extern "C" int asl_localize_bundles_rig_batch(asl_detector *d, const asl_obs *obs, int n_cams, int n_frames, int max_tags, const asl_map_tag *maps,
+                                              int n_bundles, int n_ids, const asl_rig_camera *rig, double tag_size, double max_tag_rms_px,
+                                              double sigma_px, asl_cam_pose *out, asl_pose_cov *cov)
+{
+    return localize_batch(d, {obs, n_cams, n_frames, max_tags, maps, n_ids, rig, {nullptr, nullptr, 0, tag_size}, max_tag_rms_px, sigma_px, out, cov, false,
+                              nullptr, 0, nullptr, false, n_bundles, true});
+}
+
+// ---- the pose of one bundle in another's frame (k_bundle.inc)
+
+static_assert(sizeof(BundleRelRec) == sizeof(asl_bundle_rel) && sizeof(asl_bundle_rel) == 424, "asl_bundle_rel layout");
+
+// n_frames x n_bundles poses, and their covariances or NULL -> as many asl_bundle_rel; all host or all device pointers
+struct BundleRelCall {
+    const void *poses, *cov; int n_frames, n_bundles, ref;
+    void *rel;
+};
+
+static int check_bundle_rel_call(const asl_detector *d, const BundleRelCall &c, bool)
+{
+    if (!d) return fail(ASL_EINVAL, "NULL detector");
+    if (!c.poses || !c.rel) return fail(ASL_EINVAL, "NULL argument");
+    if (c.n_frames < 0) return fail(ASL_EINVAL, "n_frames < 0");
+    if (c.n_bundles < 1 || c.n_bundles > LOC_MAX_BUNDLES) return fail(ASL_EINVAL, "n_bundles must be in [1, %d] (got %d)", LOC_MAX_BUNDLES, c.n_bundles);
+    if ((long long)c.n_frames * c.n_bundles > INT32_MAX)
+        return fail(ASL_EINVAL, "n_frames * n_bundles must fit 32 bits (got %d x %d)", c.n_frames, c.n_bundles);
+    if (c.ref < 0 || c.ref >= c.n_bundles) return fail(ASL_EINVAL, "ref must be in [0, %d) (got %d)", c.n_bundles, c.ref);
+    return ASL_OK;
+}
+
+static int launch_bundle_rel(asl_detector *, const BundleRelCall &c, hipStream_t st)
+{
+    const long long n = (long long)c.n_frames * c.n_bundles;
+    if (n == 0) return ASL_OK;
+    hipLaunchKernelGGL(k_bundle_relative, dim3((unsigned int)((n + ASL_WAVE - 1) / ASL_WAVE)), dim3(ASL_WAVE), 0, st, (const CamPoseRec *)c.poses,
+                       (const PoseCovRec *)c.cov, c.n_frames, c.n_bundles, c.ref, (BundleRelRec *)c.rel);
+    HIPCHK(hipGetLastError());
+    return ASL_OK;
+}
+
+extern "C" int asl_bundle_relative_device(asl_detector *d, const void *d_poses, const void *d_cov, int n_frames, int n_bundles, int ref, void *d_rel,
+                                          void *stream)
+{
+    return frames_device<BundleRelCall, check_bundle_rel_call, launch_bundle_rel>(d, {d_poses, d_cov, n_frames, n_bundles, ref, d_rel}, stream);
+}
+
+extern "C" int asl_bundle_relative_batch(asl_detector *d, const asl_cam_pose *poses, const asl_pose_cov *cov, int n_frames, int n_bundles, int ref,
+                                         asl_bundle_rel *rel)
+{
+    const BundleRelCall c{poses, cov, n_frames, n_bundles, ref, rel};
+    if (int rc = check_bundle_rel_call(d, c, false)) return rc;
+    const size_t n = (size_t)n_frames * (size_t)n_bundles;
+    if (n == 0) return ASL_OK;
+    HIPCHK(hipSetDevice(d->device));
+    // the poses and covariances in, staged in solve_out beside the result
+    OutPiece o[] = {{rel, sizeof(asl_bundle_rel) * n}, {nullptr, sizeof(asl_cam_pose) * n}, {nullptr, cov ? sizeof(asl_pose_cov) * n : 0}};
+    if (carve_ws(d->solve_out, [&](WsCarve &w) { for (OutPiece &p : o) p.dev = p.bytes ? w.take<uint8_t>(p.bytes) : nullptr; }))
+        return fail(ASL_ENOMEM, "bundle workspace allocation failed");
+    HIPCHK(hipMemcpy(o[1].dev, poses, o[1].bytes, hipMemcpyHostToDevice));
+    if (cov) HIPCHK(hipMemcpy(o[2].dev, cov, o[2].bytes, hipMemcpyHostToDevice));
+    if (int rc = launch_bundle_rel(d, {o[1].dev, o[2].dev, n_frames, n_bundles, ref, o[0].dev}, nullptr)) return rc;
+    return fetch_out(o);
 }
 
 // ---- per-tag pose covariance (k_posecov.inc)

@@ -9,16 +9,17 @@ scene (TagMap.from_scene).
                     library reads (indexed by id)
     CAM_POSE_DTYPE  one asl_cam_pose per frame: world<-camera T, rms_px, rms_seed_px, n_tags, n_rejected, status, seed_slot
     POSE_COV_DTYPE  one asl_pose_cov per pose: cov 6x6 (rx ry rz | px py pz), sigma_px, dof, status; pose_std reads it
+    BUNDLE_REL_DTYPE  one asl_bundle_rel per (frame, bundle): T = ref<-bundle, cov 6x6, status (bundles.py: several maps at once)
 """
 import numpy as np
 
-from ._lib import CAM_POSE_DTYPE, MAP_TAG_DTYPE, POSE_COV_DTYPE
+from ._lib import BUNDLE_REL_DTYPE, CAM_POSE_DTYPE, MAP_TAG_DTYPE, POSE_COV_DTYPE
 
 STATUS_OK, STATUS_NO_MAPPED_TAG, STATUS_NO_PNP = 0, 1, 2
 
 COV_OK, COV_NO_POSE, COV_NOT_POSITIVE_DEFINITE = 0, 1, 2
 
-__all__ = ["TagMap", "CAM_POSE_DTYPE", "MAP_TAG_DTYPE", "POSE_COV_DTYPE", "STATUS_OK", "STATUS_NO_MAPPED_TAG", "STATUS_NO_PNP",
+__all__ = ["TagMap", "CAM_POSE_DTYPE", "MAP_TAG_DTYPE", "POSE_COV_DTYPE", "BUNDLE_REL_DTYPE", "STATUS_OK", "STATUS_NO_MAPPED_TAG", "STATUS_NO_PNP",
            "COV_OK", "COV_NO_POSE", "COV_NOT_POSITIVE_DEFINITE", "pose_std"]
 
 

@@ -7,7 +7,7 @@ mounting.  A frame index is one instant for all cameras.
 
     RigCamera       one camera: K, dist (0, 4 or 5 coefficients), T_cam_rig = camera<-rig 4x4 (the mounting)
     Rig             the cameras in block order; as_records() -> RIG_CAMERA_DTYPE (asl_rig_camera), save / load,
-                    localize(), localize_sequence() / localize_sequences(), build_map() / build_map_sized(),
+                    localize(), localize_bundles(), localize_sequence() / localize_sequences(), build_map() / build_map_sized(),
                     locate_tags() / extend_map(), from_camera_poses(), calibrate_mountings()
     RigCalibrationResult   what calibrate_mountings returns: the refined Rig, the result record, the mountings' covariances
                     and the frames' poses
@@ -114,6 +114,15 @@ class Rig:
         if o.shape[0] * o.shape[2] > MAX_SLOTS:
             raise ValueError("n_cams * max_tags must be <= %d" % MAX_SLOTS)
         return det.localize_rig(o, tag_map, self.as_records(), tag_size, max_tag_rms_px, float(sigma_px) if with_cov else None, map_cov=map_cov)
+
+    def localize_bundles(self, det, obs, bundles, tag_size, max_tag_rms_px=0.0, with_cov=False, sigma_px=0.0):
+        """Every bundle of a bundles.BundleSet posed in every frame by one call (Detector.localize_bundles_rig,
+        asl_localize_bundles_rig_batch): obs as in localize -> bundles.BundleResult with T[f, b] = bundle_b<-rig, entry [f, b]
+        what localize gives for frame f with bundle b as the map; with_cov: with the covariances, which relative() carries
+        into those of the relative poses."""
+        from .bundles import BundleResult
+        got = det.localize_bundles_rig(self._block(obs), bundles, self.as_records(), tag_size, max_tag_rms_px, float(sigma_px) if with_cov else None)
+        return BundleResult(got[0], got[1], bundles, det) if with_cov else BundleResult(got, None, bundles, det)
 
     def build_map(self, det, obs, n_ids, tag_size, world_id=-1, max_iters=30, with_std=True, huber_px=0.0):
         """The tag map from the rig's own frames (Detector.build_map_rig, asl_map_rig_batch): obs (n_cams, n_frames, max_tags)

@@ -249,6 +249,12 @@ class SLAM:
         sizes (the graph has one tag_size); a map with sizes goes through TagDetector.localize."""
         return self.detector.localize(detections, self.tag_map(), max_tag_rms_px=max_tag_rms_px, with_cov=with_cov, sigma_px=sigma_px)
 
+    def localize_bundles(self, dets, poses, n_per_frame, bundles, **kw):
+        """Every bundle of a bundles.BundleSet posed in every frame (TagDetector.localize_bundles, whose keywords pass
+        through); the graph, the window and my_pose() stay as they are.  With tag_map() as one of the bundles and ref that
+        bundle, the relative poses are the objects' poses in the graph's world."""
+        return self.detector.localize_bundles(dets, poses, n_per_frame, bundles, **kw)
+
     def extend_map(self, frames_or_obs, **kw):
         """Tags the graph does not have, located from frames that also see tags of tag_map() (TagDetector.extend_map, whose
         keywords pass through) -> (locate.LocateResult, the frames' poses); the graph, the window and my_pose() stay as they are."""

@@ -241,6 +241,22 @@ class TagDetector:
         return self.detector._det.localize(obs, tag_map, self._K(), self._dist(), self.tag_size, max_tag_rms_px,
                                            sigma_px=float(sigma_px) if with_cov else None)
 
+    def localize_bundles(self, dets, poses, n_per_frame, bundles, ref=None, max_tag_rms_px=0.0, with_cov=False, sigma_px=0.0, max_tags=None):
+        """localize_batch against every bundle of a bundles.BundleSet at once (asl_localize_bundles_batch): several rigid
+        objects that each carry a few tags, every one posed in every frame -> bundles.BundleResult with T[f, b] =
+        bundle_b<-camera (status 1 where the frame sees no tag of the bundle) and, with_cov, the covariances.  ref (a
+        position or a name): (result, result.relative(ref)) instead, the second (n_frames, n_bundles) BUNDLE_REL_DTYPE with
+        T = ref<-bundle and its covariance."""
+        from .bundles import BundleResult
+        from .dist import pack_observations
+        npf = np.asarray(n_per_frame, dtype=np.int64)
+        mt = int(max_tags) if max_tags is not None else max(1, int(npf.max()) if len(npf) else 1)
+        obs = pack_observations(dets, poses, npf, mt)
+        det = self.detector._det
+        got = det.localize_bundles(obs, bundles, self._K(), self._dist(), self.tag_size, max_tag_rms_px, float(sigma_px) if with_cov else None)
+        res = BundleResult(got[0], got[1], bundles, det) if with_cov else BundleResult(got, None, bundles, det)
+        return res if ref is None else (res, res.relative(ref))
+
     def localize_sequence(self, dets, poses, n_per_frame, tag_map, sigma_px=1.0, sigma_rot=0.05, sigma_trans=0.5, max_iters=20,
                           max_tags=None, with_cov=False, huber_px=0.0, times=None):
         """The structured arrays detect_host / collect return for one camera's CONSECUTIVE frames -> smooth.SmoothResult: a

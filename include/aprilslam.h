@@ -410,6 +410,70 @@ int asl_localize_rig_mapcov_batch(asl_detector *det, const asl_obs *obs, int n_c
                                   int n_ids, const asl_rig_camera *rig, double tag_size, double max_tag_rms_px, double sigma_px,
                                   asl_cam_pose *out, asl_pose_cov *cov, const double *map_cov, int ld, const int32_t *cov_slot);
 
+/* ---- tag bundles: several rigid objects that each carry a few tags (a tool, a pallet, a landing pad, other robots), every
+   one posed in every frame by one launch.  Bundle b is a table of n_ids asl_map_tag with T = bundle_b<-tag, the object's
+   tag layout in its own frame (valid = 0 for the ids it does not carry; sizes honoured as everywhere); d_maps holds the
+   n_bundles tables one after another, table b at d_maps + b * n_ids records.  The grid is (frame, bundle): one wavefront
+   solves frame f against table b exactly as asl_localize_frames_device does with that table as its map -- "world<-camera"
+   with the bundle as the world -- and writes record f * n_bundles + b.
+   Contract: record (f, b) of d_out, and of d_cov where given, is byte for byte what asl_localize_frames_device /
+   asl_localize_cov_frames_device writes for frame f when called with table b alone: T = bundle_b<-camera, gate, statuses
+   and seed_slot included.  A frame that sees no tag of bundle b gets status 1 (the common case, and the solve's first
+   exit).  d_cov NULL: the plain solve (sigma_px is checked and not used); else n_frames x n_bundles asl_pose_cov, sigma_px
+   as in asl_localize_cov_frames_device.  The covariances take the layouts as exact: a bundle's own uncertainty (a table
+   cut from a map asl_map_* built) is not propagated, and there are no mapcov forms for bundles.
+   ASL_EINVAL, nothing written: whatever the one-map calls refuse; n_bundles outside [1, 1024]; n_frames * n_bundles past
+   2^31 - 1.  Nothing waits that the one-map forms do not wait for.  Deterministic: the same input gives the same bytes.
+   The library does not look for an id that is valid in two tables (see asl_bundle_relative_device); bundles.BundleSet of
+   the Python layer refuses one. */
+int asl_localize_bundles_frames_device(asl_detector *det, const void *d_obs, int n_frames, int max_tags, const void *d_maps,
+                                       int n_bundles, int n_ids, const double *K, const double *dist, int n_dist, double tag_size,
+                                       double max_tag_rms_px, double sigma_px, void *d_out, void *d_cov, void *stream);
+/* The same computation on host records, synchronous: maps is n_bundles x n_ids records, out and cov (NULL: plain)
+   n_frames x n_bundles. */
+int asl_localize_bundles_batch(asl_detector *det, const asl_obs *obs, int n_frames, int max_tags, const asl_map_tag *maps,
+                               int n_bundles, int n_ids, const double *K, const double *dist, int n_dist, double tag_size,
+                               double max_tag_rms_px, double sigma_px, asl_cam_pose *out, asl_pose_cov *cov);
+/* For a rig: asl_localize_rig_frames_device / asl_localize_rig_cov_frames_device per (frame, bundle) under the same contract,
+   T = bundle_b<-rig.  The table d_rig is read back and checked before the launch, the one synchronous step, as there. */
+int asl_localize_bundles_rig_frames_device(asl_detector *det, const void *d_obs, int n_cams, int n_frames, int max_tags,
+                                           const void *d_maps, int n_bundles, int n_ids, const void *d_rig, double tag_size,
+                                           double max_tag_rms_px, double sigma_px, void *d_out, void *d_cov, void *stream);
+int asl_localize_bundles_rig_batch(asl_detector *det, const asl_obs *obs, int n_cams, int n_frames, int max_tags,
+                                   const asl_map_tag *maps, int n_bundles, int n_ids, const asl_rig_camera *rig, double tag_size,
+                                   double max_tag_rms_px, double sigma_px, asl_cam_pose *out, asl_pose_cov *cov);
+
+/* The pose of bundle b in the frame of a reference bundle, per frame, from what the calls above wrote. */
+typedef struct {
+    double T[16];      /* ref<-bundle_b, row-major 4x4 */
+    double cov[36];    /* its covariance in the (r, d) convention of asl_pose_cov, row-major 6x6, symmetric to the bit */
+    int32_t status;    /* 0 ok; 1 bundle b or the reference has no pose in this frame (its asl_cam_pose.status != 0): T identity,
+                          cov zeros; 2 both poses ok, but d_cov is NULL or one of the two asl_pose_cov.status != 0: T valid, cov
+                          zeros */
+    int32_t reserved;  /* written 0 */
+} asl_bundle_rel;      /* 424 bytes */
+
+/* d_poses: n_frames x n_bundles asl_cam_pose (record f * n_bundles + b: T_b = bundle_b<-camera, or bundle_b<-rig); d_cov:
+   as many asl_pose_cov, or NULL; ref in [0, n_bundles).  d_rel: one asl_bundle_rel per (frame, bundle).  Device pointers,
+   asynchronous on `stream`; one lane per record, float64, no atomics, a fixed order of operations: the same input gives
+   the same bytes.  With a = ref, T_a = [R_a | p_a] and T_b = [R_b | p_b]:
+       R_ab = R_a R_b^T,  q = R_ab p_b,  p_ab = p_a - q                               (T_ab = T_a inv(T_b))
+       r_ab = r_a - R_ab r_b,  d_ab = d_a + [q]x r_ab - R_ab d_b                      (to first order)
+       J_a = [I 0; [q]x I],  J_b = [-R_ab 0; -[q]x R_ab  -R_ab],  C_ab = J_a C_a J_a^T + J_b C_b J_b^T
+   (built as J_a (C_a + D C_b D^T) J_a^T with D = diag(R_ab, R_ab), which is the same matrix; the Jacobians agree with
+   central differences of the exact composition, tests/test_bundle_ref.py).  b == ref: the identity, zero covariance,
+   status 0 or 1 by the reference's pose.
+   The sum takes the two poses as independent, which they are when their solves share no corner: an id that is valid in
+   two tables breaks that, and the covariance is then too small or too large by the shared part.  As in the solves, the
+   layouts are exact: the uncertainty of the bundles' own tables is not propagated.
+   ASL_EINVAL, nothing written: NULL det, d_poses or d_rel; n_frames < 0; n_bundles outside [1, 1024]; n_frames * n_bundles
+   past 2^31 - 1; ref outside [0, n_bundles).  tests/bundle_ref.py states the computation. */
+int asl_bundle_relative_device(asl_detector *det, const void *d_poses, const void *d_cov, int n_frames, int n_bundles, int ref,
+                               void *d_rel, void *stream);
+/* The same computation on host records, synchronous. */
+int asl_bundle_relative_batch(asl_detector *det, const asl_cam_pose *poses, const asl_pose_cov *cov, int n_frames, int n_bundles,
+                              int ref, asl_bundle_rel *rel);
+
 /* One asl_pose_cov per asl_obs record (n_records of them, as asl_pack_observations_device writes them; device pointers,
    asynchronous on `stream`): the covariance of the camera<-tag pose in the record from its 4 corners (8 residuals, dof 2),
    re-linearised at that pose with the camera model of asl_solve_pnp_batch.  Records without flags & 2 get status 1.
