@@ -479,10 +479,11 @@ __global__ void __launch_bounds__(64) k_pnp_dets(DetRec *dets, const long long *
     const bool ok = pnp_quad_dev(iu, iv, q, cam, s_ne + gi, rvec, tvec, T);
     if (!have) return;
     // the four lanes hold the same result: each writes a quarter of it
-    if (q < 3) { dets[i].rvec[q] = rvec[q]; dets[i].tvec[q] = tvec[q]; }
+    // a tag without a pose (ok false) stores zeros: pnp_quad_dev may have returned before it wrote rvec, tvec or T
+    if (q < 3) { dets[i].rvec[q] = ok ? rvec[q] : 0.0; dets[i].tvec[q] = ok ? tvec[q] : 0.0; }
     else dets[i].pose_ok = ok ? 1 : 0;
 #pragma unroll
-    for (int k = 0; k < 4; k++) dets[i].T[4 * q + k] = (q == 0 ? T[k] : (q == 1 ? T[4 + k] : (q == 2 ? T[8 + k] : T[12 + k])));
+    for (int k = 0; k < 4; k++) dets[i].T[4 * q + k] = ok ? (q == 0 ? T[k] : (q == 1 ? T[4 + k] : (q == 2 ? T[8 + k] : T[12 + k]))) : 0.0;
 }
 
 __global__ void __launch_bounds__(64) k_pnp_batch(const float *corners, int n, CamDev cam, double *rvec, double *tvec, double *T, uint8_t *ok, int tpw)
@@ -496,8 +497,8 @@ __global__ void __launch_bounds__(64) k_pnp_batch(const float *corners, int n, C
     double r[3], t[3], TT[16];
     const bool good = pnp_quad_dev(iu, iv, q, cam, s_ne + gi, r, t, TT);
     if (!have) return;
-    if (q < 3) { rvec[3 * i + q] = r[q]; tvec[3 * i + q] = t[q]; }
+    if (q < 3) { rvec[3 * i + q] = good ? r[q] : 0.0; tvec[3 * i + q] = good ? t[q] : 0.0; }  // no pose: zeros, as in k_pnp_dets
     else ok[i] = good ? 1 : 0;
 #pragma unroll
-    for (int k = 0; k < 4; k++) T[16 * i + 4 * q + k] = (q == 0 ? TT[k] : (q == 1 ? TT[4 + k] : (q == 2 ? TT[8 + k] : TT[12 + k])));
+    for (int k = 0; k < 4; k++) T[16 * i + 4 * q + k] = good ? (q == 0 ? TT[k] : (q == 1 ? TT[4 + k] : (q == 2 ? TT[8 + k] : TT[12 + k]))) : 0.0;
 }

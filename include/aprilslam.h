@@ -204,7 +204,9 @@ int asl_collect_batch_view(asl_detector *det, const asl_detection **out, const a
 
 /* Replaces cv2.solvePnP(ITERATIVE) + cv2.Rodrigues for N tags at once (reference
    tag_detector.py:30-52).  corners: N x 4 x 2 float32 (lb,rb,rt,lt), K row-major 3x3,
-   dist: n_dist in {0,4,5} coefficients (k1,k2,p1,p2[,k3]).  All pointers are host memory. */
+   dist: n_dist in {0,4,5} coefficients (k1,k2,p1,p2[,k3]).  All pointers are host memory.
+   A tag without a pose (degenerate or non-finite corners) has ok = 0 and zeros in all of its rvec, tvec and T, whatever
+   it shares a wavefront with; an asl_pose with ok = 0 from the detect calls with a camera holds the same zeros. */
 int asl_solve_pnp_batch(asl_detector *det, const float *corners, const double *K, const double *dist,
                         int n_dist, double tag_size, double *rvec /*N x 3*/, double *tvec /*N x 3*/,
                         double *T /*N x 16*/, uint8_t *ok /*N*/, int N);
